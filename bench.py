@@ -1,7 +1,13 @@
 #!/usr/bin/env python3
 """bench.py - throughput of the batched MP3 encode hot path on MI355X.
 
-  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5]
+  python bench.py --gpus N --steps K --warmup W [--config 2|3|4|5] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the line (value, ms_per_step, roofline of the timed
+kernel, per-stream times of the last step).  --full adds everything else the line can carry: --verify 16 streams
+against the CPU oracle, the host-fed rate, the worst-case signal set, the other BASELINE configs, strong scaling,
+the CPU baseline and the host libm report.  Each of these can also be asked for on its own by its option.
+--dump-outputs DIR writes what the last timed step handed its caller as DIR/*.npy (dump_outputs()).
 
 --gpus N > 1 without a torch.distributed environment starts N single-GPU worker processes itself
 (one rank per GPU, before anything in this process touches the GPU); under
@@ -20,7 +26,7 @@ stream state is carried from step to step, so K steps encode K x F consecutive f
 stream.  Streams shard over ranks with no collective; RCCL carries the barrier and the
 max-over-ranks time only.  After the timed region rank 0 copies --verify streams (PCM and the last
 step's bitstream) to the host and compares them byte for byte with the CPU oracle run over the
-same W + K steps.  Rank 0 prints ONE JSON line.
+same W + K steps (--verify, on by default with --full).  Rank 0 prints ONE JSON line.
 """
 import argparse
 import ctypes as C
@@ -30,6 +36,7 @@ import socket
 import subprocess
 import sys
 import time
+import zlib
 
 ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
@@ -38,6 +45,8 @@ HBM_PEAK_GBS = 8000.0                      # MI355X_MICROARCH.md: 8 TB/s spec
 # vector issue peak: 256 CUs x 4 SIMD-32, one wave64 vector instruction per 2 cycles and SIMD, 2.4 GHz
 VALU_PEAK_GINST = 256 * 4 * 2.4 / 2.0
 RHO_CYCLE = [0.7, 0.0, 1.0, 0.3]
+DUMP_SEED = 0x484D5033                     # the streams --dump-outputs writes in full
+DUMP_SAMPLE_BYTES = 48 << 20               # their float32 bytes at most (the whole dump stays below 64 MB)
 
 
 def workload(cfg):
@@ -119,6 +128,30 @@ def synth_batch_gpu(torch, np, nstreams, nframes, srs, rhos, bursts, dev, first_
             x = x * (0.95 / x.abs().amax(dim=(1, 2), keepdim=True))
             out[torch.as_tensor(ids, device=dev)] = torch.round(x * 32767.0).to(torch.int16).permute(0, 2, 1)
     return out
+
+
+def dump_outputs(path, torch, np, out, nbytes):
+    """--dump-outputs: what the last timed step handed its caller (out: uint8 [S, stride] bitstream buffers, nbytes: int32 [S]
+    bytes used), as float .npy files below 64 MB together, so that two builds can be compared output for output:
+      nbytes.npy               float64 [S]          bytes of bitstream each stream produced
+      bitstream_crc32.npy      float64 [S]          CRC-32 of each stream's bitstream (its first nbytes bytes)
+      bitstream_sample.npy     float32 [n, stride]  the whole buffers of n streams chosen with a fixed seed, zero past nbytes
+      bitstream_sample_ids.npy float64 [n]          which streams those are"""
+    S, stride = out.shape
+    nb = nbytes.cpu().numpy().astype(np.int64)
+    crc = np.zeros(S, dtype=np.float64)
+    for c0 in range(0, S, 256):                 # host copies of a few hundred MB at most
+        blk = out[c0:c0 + 256].cpu().numpy()
+        for k in range(blk.shape[0]):
+            crc[c0 + k] = zlib.crc32(blk[k, :nb[c0 + k]].tobytes())
+    n = max(1, min(S, DUMP_SAMPLE_BYTES // (4 * stride)))
+    ids = np.sort(np.random.RandomState(DUMP_SEED).choice(S, size=n, replace=False))
+    sample = out[torch.as_tensor(ids, device=out.device)].cpu().numpy()
+    sample[np.arange(stride)[None, :] >= nb[ids][:, None]] = 0      # the buffer's tail is never written
+    os.makedirs(path, exist_ok=True)
+    for name, a in (("nbytes", nb.astype(np.float64)), ("bitstream_crc32", crc),
+                    ("bitstream_sample", sample.astype(np.float32)), ("bitstream_sample_ids", ids.astype(np.float64))):
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # ---- CPU side: the checker (oracle/) as verifier and as the reported CPU baseline -------------
@@ -284,36 +317,45 @@ def main():
     ap.add_argument("--config", type=int, default=2, choices=[2, 3, 4, 5], help="BASELINE.json configs[n-1]")
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU (default: the config's)")
     ap.add_argument("--frames", type=int, default=0, help="frames per stream per step (default: the config's)")
-    ap.add_argument("--verify", default="16", help="streams checked against the CPU oracle after the timed region: a number (0 = off) or 'all' (every stream of every rank's block)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-worst-case", action="store_true", help="skip the second timed pass on the correlation-cycled signal set (config 2, one GPU)")
-    ap.add_argument("--host-fed", type=int, default=-1, help="1 / 0: also time (or not) the workload fed from page-locked host memory through the pipelined host-buffer calls; default: config 2 only")
-    ap.add_argument("--other-configs", type=int, default=-1, help="1 / 0: also run the other BASELINE configs at full width for 4 timed steps each and append them as other_configs (one GPU: 3, 4, 5; several: 4 and 5, the configs BASELINE defines on 8 GPUs), each with its host-fed rate; default: with config 2 at its own size")
-    ap.add_argument("--other-size", default="", help="S,F: run the other_configs (and their host-fed passes) at this reduced size per GPU instead of their full width, also next to --streams / --frames (the multi-GPU pre-flight test: everything of an 8-rank run except the devices)")
-    ap.add_argument("--strong-scaling", type=int, default=-1, help="1 / 0: with --gpus N > 1 also time config 2's 1024 streams split N ways (strong scaling, SURVEY 8e); default: with config 2 at its own size")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the last timed step's outputs (rank 0's block) as DIR/*.npy (see dump_outputs())")
+    ap.add_argument("--full", action="store_true", help="also run every measurement and check beyond the headline; the defaults below marked 'with --full' apply only then, without it they are off")
+    ap.add_argument("--verify", default=None, help="streams checked against the CPU oracle after the timed region: a number (0 = off) or 'all' (every stream of every rank's block); default: 16 with --full")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the CPU baseline (with --full)")
+    ap.add_argument("--no-worst-case", action="store_true", help="skip the second timed pass on the correlation-cycled signal set (with --full, config 2, one GPU)")
+    ap.add_argument("--host-fed", type=int, default=-1, help="1 / 0: also time (or not) the workload fed from page-locked host memory through the pipelined host-buffer calls; default: config 2 only, with --full")
+    ap.add_argument("--other-configs", type=int, default=-1, help="1 / 0: also run the other BASELINE configs at full width for 4 timed steps each and append them as other_configs (one GPU: 3, 4, 5; several: 4 and 5, the configs BASELINE defines on 8 GPUs), each with its host-fed rate; default: with --full, with config 2 at its own size")
+    ap.add_argument("--other-size", default="", help="S,F: run the other_configs (and their host-fed passes) at this reduced size per GPU instead of their full width, also next to --streams / --frames (the multi-GPU pre-flight test: everything of an 8-rank run except the devices); implies --other-configs 1 with --full")
+    ap.add_argument("--strong-scaling", type=int, default=-1, help="1 / 0: with --gpus N > 1 also time config 2's 1024 streams split N ways (strong scaling, SURVEY 8e); default: with --full, with config 2 at its own size")
     ap.add_argument("--no-pipeline", action="store_true", help="plain hx_batch_encode_s16_device calls instead of submit / wait")
     ap.add_argument("--gate", type=int, default=-1, help="hx_batch_set_gate percent (library default)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"], help="process group of the barrier / max-time (nccl = RCCL)")
     ap.add_argument("--share-gpu", action="store_true", help="every rank on GPU 0 (tests on a one-GPU box; needs --backend gloo)")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous, sharding and reporting only, no encode (CPU test of the multi-rank path)")
     args = ap.parse_args()
+    if args.verify is None:
+        args.verify = "16" if args.full else "0"
     try:
         args.verify = (1 << 30) if str(args.verify).lower() == "all" else int(args.verify)      # (capped at the batch's streams where it is used)
     except ValueError:
         raise SystemExit("--verify takes a number or 'all'")
+    if not args.full and args.host_fed < 0:
+        args.host_fed = 0
     if args.other_configs < 0:
-        args.other_configs = 1 if (args.config == 2 or args.other_size) else 0
+        args.other_configs = 1 if (args.full and (args.config == 2 or args.other_size)) else 0
     if args.strong_scaling < 0:
-        args.strong_scaling = 1 if (args.config == 2 and args.gpus > 1 and not args.streams and not args.frames) else 0
+        args.strong_scaling = 1 if (args.full and args.config == 2 and args.gpus > 1 and not args.streams and not args.frames) else 0
     if args.gpus < 1:
         raise SystemExit("--gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        raise SystemExit("--steps must be >= 1 and --warmup >= 0")
     # what the line will carry beside `value` (also printed by --dry-run, so that the multi-rank CPU tests can check the plan)
     other_size = tuple(int(x) for x in args.other_size.split(",")) if args.other_size else ()
     if other_size and (len(other_size) != 2 or min(other_size) < 1):
         raise SystemExit("--other-size takes S,F")
     plan_other = [c for c in ((3, 4, 5) if args.gpus == 1 else (4, 5)) if c != args.config] if (args.other_configs and ((not args.streams and not args.frames) or other_size)) else []
     plan = {"other_configs": plan_other, "host_fed_configs": ([args.config] if (args.host_fed == 1 or (args.host_fed < 0 and args.config == 2)) else []) + (plan_other if args.host_fed != 0 else []),
-            "strong_scaling": bool(args.strong_scaling and args.gpus > 1), "worst_case": bool(args.config == 2 and args.gpus == 1 and not args.no_worst_case)}
+            "strong_scaling": bool(args.strong_scaling and args.gpus > 1), "worst_case": bool(args.full and args.config == 2 and args.gpus == 1 and not args.no_worst_case),
+            "verify": args.verify, "cpu_baseline": bool(args.full and not args.no_cpu_baseline)}
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
 
@@ -394,9 +436,10 @@ def main():
     if dist is not None:
         dist.init_process_group(args.backend)     # RCCL; used for the barrier and the max-over-ranks time only
 
-    def run(pcm, verify_n, c=None, steps=None, warmup=None):
+    def run(pcm, verify_n, c=None, steps=None, warmup=None, dump=""):
         """warm-up + timed steps over one signal set with a fresh batch; returns measurements
-        (c: another configuration's set-up from config_setup(), default = the line's own)"""
+        (c: another configuration's set-up from config_setup(), default = the line's own; dump: directory for
+        dump_outputs() of the last step, rank 0)"""
         S, F, wl, kws, ncls = (c["S"], c["F"], c["wl"], c["kws"], c["ncls"]) if c else (S0, F0, wl0, kws0, ncls0)
         steps = args.steps if steps is None else steps
         warmup = args.warmup if warmup is None else warmup
@@ -464,6 +507,8 @@ def main():
             m["gate_timeouts"] = batch.gate_timeouts()
         except AttributeError:      # an older build of the library (HMP3AMD_LIB)
             m["gate_timeouts"] = None
+        if dump and rank == 0:
+            dump_outputs(dump, torch, np, out, nbytes)
         if verify_n > 0:            # every rank checks streams of its own block
             rs = np.random.RandomState(12345 + (c["cfg"] if c else args.config) + 1000 * rank)
             ids = sorted(rs.choice(S, size=min(verify_n, S), replace=False).tolist())
@@ -519,12 +564,12 @@ def main():
 
     pcm = synth_batch_gpu(torch, np, S, F, srs, rhos, wl["bursts"], dev, first_stream=first)
     vper = args.verify if world == 1 else (max(2, -(-args.verify // world)) if args.verify > 0 else 0)
-    m = run(pcm, vper)
+    m = run(pcm, vper, dump=args.dump_outputs)
     host_fed = None
     if args.host_fed == 1 or (args.host_fed < 0 and args.config == 2):
         host_fed = run_host_fed(pcm)
     worst = None
-    if args.config == 2 and world == 1 and not args.no_worst_case:
+    if plan["worst_case"] and world == 1:
         # the same config on the least friendly signal mix of the family: correlation cycled over {0.7, 0, 1, 0.3}
         del pcm
         pcm = synth_batch_gpu(torch, np, S, F, srs, [RHO_CYCLE[i % 4] for i in range(S)], wl["bursts"], dev, first_stream=first)
@@ -670,10 +715,11 @@ def main():
                                  "kernel_ms": round(worst["k_ms"], 3), "kernel_status": worst["status"], "stream_ms": worst.get("stream_ms")}
         if m.get("k6"):
             res["roofline"]["resident_streams"] = m["k6"]["resident_streams"]
-        try:        # which C library the checker on this box runs on (matters for first-generation-allocator streams only: hx_libm32.h)
-            res["host_libm"] = api.libm_report(1000)
-        except AttributeError:
-            pass
+        if args.full:
+            try:        # which C library the checker on this box runs on (matters for first-generation-allocator streams only: hx_libm32.h)
+                res["host_libm"] = api.libm_report(1000)
+            except AttributeError:
+                pass
         if others:
             oc = []
             for c, mo in others:
@@ -695,7 +741,7 @@ def main():
                                      "kernel_ms_rank0": round(ms_["k_ms"], 3), "kernel_status_rank0": ms_["status"],
                                      "what": "config 2's 1024 streams split over the %d ranks (total work fixed); the headline value is weak scaling (1024 streams per GPU)" % world}
         res["host_placement"] = placements      # per rank: device, its NUMA node, CPUs the rank was bound to, its own host-fed step time
-        if not args.no_cpu_baseline:
+        if plan["cpu_baseline"]:
             if cpus_before:
                 os.sched_setaffinity(0, cpus_before)        # the CPU baseline runs on every usable core, not on this GPU's socket only
             # the reference CPU encoder on this box's host cores, in the same run (rank 0, after the timed regions; the

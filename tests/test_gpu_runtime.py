@@ -128,7 +128,7 @@ def test_eight_rank_preflight_on_one_gpu():
     import time
     t0 = time.time()
     rc, line, err = _bench(["--gpus", "8", "--share-gpu", "--backend", "gloo", "--streams", "128", "--frames", "32", "--steps", "2", "--warmup", "1",
-                            "--verify", "16", "--no-cpu-baseline", "--no-worst-case", "--other-size", "128,32", "--strong-scaling", "1"], timeout=600)
+                            "--verify", "16", "--no-cpu-baseline", "--no-worst-case", "--other-size", "128,32", "--strong-scaling", "1", "--full"], timeout=600)
     wall = time.time() - t0
     assert rc == 0, (line, err[-2000:])
     assert line["n_gpus"] == 8 and line["ranks_seen"] == 8 and line["ranks_failed"] == [] and line["kernel_status"] == 0
@@ -163,6 +163,34 @@ def test_bench_configs_verify_against_oracle_at_reduced_size(cfg):
     assert rc == 0, (line, err[-2000:])
     assert line["config"]["baseline_config"] == cfg and line["kernel_status"] == 0
     assert line["verified_streams"] == 12, line["verify"]
+
+
+@pytest.mark.one_k6_build
+def test_bench_dump_outputs_repeat_and_agree_with_the_line(tmp_path):
+    """--dump-outputs: the last timed step's outputs as float arrays below 64 MB, the same from run to run with the same
+    arguments; every stream of the step checked against the oracle, so the dumped bytes are the right ones"""
+    import zlib
+    args = ["--config", "3", "--streams", "48", "--frames", "12", "--steps", "3", "--warmup", "1", "--verify", "48"]
+    runs = []
+    for r in range(2):
+        d = tmp_path / ("run%d" % r)
+        rc, line, err = _bench(args + ["--dump-outputs", str(d)])
+        assert rc == 0, (line, err[-2000:])
+        assert line["steps"] == 3 and line["ms_per_step"] > 0 and line["kernel_status"] == 0 and line["verified_streams"] == 48
+        files = sorted(d.glob("*.npy"))
+        assert sum(f.stat().st_size for f in files) <= 64 << 20
+        a = {f.stem: np.load(f) for f in files}
+        assert set(a) == {"nbytes", "bitstream_crc32", "bitstream_sample", "bitstream_sample_ids"}
+        assert all(x.dtype in (np.float32, np.float64) for x in a.values())
+        nb = a["nbytes"].astype(np.int64)
+        assert nb.shape == (48,) and abs(nb.sum() / (48.0 * 12) - line["bitstream_bytes_per_frame"]) < 0.01
+        for k, i in enumerate(a["bitstream_sample_ids"].astype(np.int64)):
+            row = a["bitstream_sample"][k]
+            assert not row[nb[i]:].any()
+            assert zlib.crc32(row[:nb[i]].astype(np.uint8).tobytes()) == a["bitstream_crc32"][i]
+        runs.append(a)
+    for name in runs[0]:
+        assert np.array_equal(runs[0][name], runs[1][name]), name
 
 
 @pytest.mark.parametrize("name", ["cli_cbr128_s16_44k", "cli_vbr50_s24_44k", "cli_lsf_vbr50_f32_24k", "cli_rifx_cbr64_s16_44k", "cli_rifx_cbr64_s24_44k"])

@@ -4,6 +4,7 @@ import os
 import socket
 
 import numpy as np
+import pytest
 import torch
 import torch.distributed as dist
 import torch.multiprocessing as mp
@@ -70,30 +71,52 @@ def _run_bench(args, timeout=600):
 def test_bench_gpus_flag_spawns_that_many_ranks():
     """`python bench.py --gpus 2` starts two ranks by itself (no torchrun); here without a GPU:
     rendezvous, sharding and the reporting path only (--dry-run), process group on gloo"""
-    rc, line, err = _run_bench(["--gpus", "2", "--dry-run", "--backend", "gloo"])
+    rc, line, err = _run_bench(["--gpus", "2", "--dry-run", "--backend", "gloo", "--full"])
     assert rc == 0, err
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and line["streams_total"] == 2 * 1024
     assert line["max_time_token"] == 2.0            # max over ranks of (1 + rank)
-    # what an N-rank line carries beside `value`: the configs BASELINE defines on 8 GPUs, their host-fed rates, strong scaling
-    assert line["plan"] == {"other_configs": [4, 5], "host_fed_configs": [2, 4, 5], "strong_scaling": True, "worst_case": False}
+    # what an N-rank --full line carries beside `value`: the configs BASELINE defines on 8 GPUs, their host-fed rates, strong scaling
+    assert line["plan"] == {"other_configs": [4, 5], "host_fed_configs": [2, 4, 5], "strong_scaling": True, "worst_case": False,
+                            "verify": 16, "cpu_baseline": True}
     assert line["strong_scaling_blocks"] == [[0, 512], [512, 1024]]
 
 
 def test_one_gpu_line_plans_every_other_config_with_its_host_fed_rate():
-    rc, line, err = _run_bench(["--dry-run"])
+    rc, line, err = _run_bench(["--dry-run", "--full"])
     assert rc == 0, err
-    assert line["plan"] == {"other_configs": [3, 4, 5], "host_fed_configs": [2, 3, 4, 5], "strong_scaling": False, "worst_case": True}
-    rc, line, err = _run_bench(["--dry-run", "--config", "3"])
+    assert line["plan"] == {"other_configs": [3, 4, 5], "host_fed_configs": [2, 3, 4, 5], "strong_scaling": False, "worst_case": True,
+                            "verify": 16, "cpu_baseline": True}
+    rc, line, err = _run_bench(["--dry-run", "--config", "3", "--full"])
     assert rc == 0 and line["plan"]["other_configs"] == [] and line["plan"]["host_fed_configs"] == []
+
+
+@pytest.mark.parametrize("gpus", [1, 2])
+def test_plain_line_plans_the_headline_only(gpus):
+    """without --full the run times its steps and prints the line: no oracle check, host-fed or worst-case pass, other
+    configs, strong scaling or CPU baseline, unless an option asks for one by name"""
+    rc, line, err = _run_bench(["--gpus", str(gpus), "--dry-run", "--backend", "gloo"])
+    assert rc == 0, err
+    assert line["plan"] == {"other_configs": [], "host_fed_configs": [], "strong_scaling": False, "worst_case": False,
+                            "verify": 0, "cpu_baseline": False}
+    rc, line, err = _run_bench(["--gpus", str(gpus), "--dry-run", "--backend", "gloo", "--verify", "4", "--host-fed", "1", "--other-configs", "1"])
+    assert rc == 0, err
+    other = [3, 4, 5] if gpus == 1 else [4, 5]
+    assert line["plan"]["verify"] == 4 and line["plan"]["other_configs"] == other and line["plan"]["host_fed_configs"] == [2] + other
+
+
+def test_bench_rejects_steps_below_one():
+    rc, line, err = _run_bench(["--dry-run", "--steps", "0"])
+    assert rc != 0 and "--steps" in err
 
 
 def test_eight_rank_config_2_line_plans_configs_4_and_5_and_the_strong_scaling_split():
     """the first 8-GPU run of the driver (`bench.py --gpus 8`, config 2): weak-scaling headline, plus other_configs 4 and 5 (each
     rank its 4096-stream share), their host-fed rates, and config 2's 1024 streams split eight ways"""
-    rc, line, err = _run_bench(["--gpus", "8", "--dry-run", "--backend", "gloo"], timeout=900)
+    rc, line, err = _run_bench(["--gpus", "8", "--dry-run", "--backend", "gloo", "--full"], timeout=900)
     assert rc == 0, err[-2000:]
     assert line["n_gpus"] == 8 and line["ranks_seen"] == 8 and line["streams_total"] == 8 * 1024
-    assert line["plan"] == {"other_configs": [4, 5], "host_fed_configs": [2, 4, 5], "strong_scaling": True, "worst_case": False}
+    assert line["plan"] == {"other_configs": [4, 5], "host_fed_configs": [2, 4, 5], "strong_scaling": True, "worst_case": False,
+                            "verify": 16, "cpu_baseline": True}
     assert line["strong_scaling_blocks"] == [[128 * r, 128 * (r + 1)] for r in range(8)]
 
 
@@ -135,3 +158,31 @@ def test_eight_ranks_take_eight_disjoint_blocks_and_the_class_cycles_run_on_acro
     assert nxt == 32768
     if cfg == 5:
         assert [b["cls_head"][0] for b in blocks] == [(4096 * r) % 3 for r in range(8)]      # 0, 1, 2, 0, ...: not reset per rank
+
+
+def test_dump_outputs_writes_float_arrays_of_what_the_caller_receives(tmp_path, monkeypatch):
+    """bench.dump_outputs on host tensors: byte counts and CRC-32 of every stream, a seeded sample of whole buffers (zero
+    past the byte count) capped by DUMP_SAMPLE_BYTES, float32 / float64 only"""
+    import sys
+    import zlib
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    S, stride = 300, 1000
+    g = torch.Generator().manual_seed(7)
+    out = torch.randint(0, 256, (S, stride), dtype=torch.uint8, generator=g)
+    nbytes = torch.randint(0, stride + 1, (S,), dtype=torch.int32, generator=g)
+    monkeypatch.setattr(bench, "DUMP_SAMPLE_BYTES", 20 * 4 * stride + 7)
+    for d in (tmp_path / "a", tmp_path / "b"):
+        bench.dump_outputs(str(d), torch, np, out, nbytes)
+    a = {f.stem: np.load(f) for f in sorted((tmp_path / "a").glob("*.npy"))}
+    assert set(a) == {"nbytes", "bitstream_crc32", "bitstream_sample", "bitstream_sample_ids"}
+    assert a["bitstream_sample"].dtype == np.float32 and all(a[k].dtype == np.float64 for k in a if k != "bitstream_sample")
+    nb = nbytes.numpy()
+    assert np.array_equal(a["nbytes"], nb)
+    assert all(a["bitstream_crc32"][i] == zlib.crc32(out[i, :nb[i]].numpy().tobytes()) for i in range(S))
+    ids = a["bitstream_sample_ids"].astype(np.int64)
+    assert len(ids) == 20 and len(set(ids.tolist())) == 20 and a["bitstream_sample"].shape == (20, stride)
+    for k, i in enumerate(ids):
+        assert np.array_equal(a["bitstream_sample"][k, :nb[i]], out[i, :nb[i]].numpy()) and not a["bitstream_sample"][k, nb[i]:].any()
+    for f in (tmp_path / "b").glob("*.npy"):            # the same arguments, the same files
+        assert np.array_equal(np.load(f), a[f.stem])

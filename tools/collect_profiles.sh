@@ -20,7 +20,7 @@ bash tools/collect_pmc.sh $O/pmc3 --config 3 && cp $O/pmc3/summary.json $O/${R}_
 # the bench lines last, with this build's counter files in place (in this scratch copy of the repo), so that they quote them
 cp $O/${R}_pmc_counters_*.json profiles/
 for c in 2 3 4 5; do
-  python3 bench.py --config $c ${BENCH_EXTRA} 2> $O/bench_config$c.err | tail -1 > $O/${R}_bench_line_config$c.json || true
+  python3 bench.py --full --config $c ${BENCH_EXTRA} 2> $O/bench_config$c.err | tail -1 > $O/${R}_bench_line_config$c.json || true
 done
-python3 bench.py --config 2 --no-pipeline --no-worst-case --host-fed 0 --other-configs 0 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${R}_bench_line_config2_no_pipeline.json || true
+python3 bench.py --full --config 2 --no-pipeline --no-worst-case --host-fed 0 --other-configs 0 --no-cpu-baseline 2>/dev/null | tail -1 > $O/${R}_bench_line_config2_no_pipeline.json || true
 ls -la $O
