@@ -347,7 +347,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
   for (;;) {        // master wave: one stream of the launch order after the other
     HX_LANE_DECL;
     int idx = 0;
-    if (LANE == 0) idx = atomicAdd(COLD(done_counter) + 5, 1);
+    if (LANE == 0) idx = atomicAdd(COLD(done_counter) + HX_CNT_CLAIMED, 1);
     idx = __builtin_amdgcn_readfirstlane(idx);
     if (idx >= a.S) break;
 #else
@@ -358,7 +358,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
     const long long t_start = wall_clock64();
     if (LANE == 0) {
         L.cur_s = s;
-        atomicAdd(COLD(done_counter) + 2, 1);        // this stream is being walked (the gates of the next call's front end count these)
+        atomicAdd(COLD(done_counter) + HX_CNT_STARTED, 1);        // this stream is being walked (the gates of the next call's front end count these)
         // where it runs (tests, placement experiments): XCC id << 16 | HW_ID[15:0], per position in the launch order
         const unsigned where = ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu);
         COLD(dur)[a.S + idx] = where;
@@ -370,7 +370,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         // nothing else fits there (a CU holds four of these workgroups: 153 of 160 KB of LDS, all vector registers).
         // (park_k bit 16: the CU that shares the instruction and scalar caches with it - CU id with the low bit flipped - as well)
         if (idx < (COLD(park_k) & 0xFFFF))
-            __hip_atomic_store((unsigned *) COLD(done_counter) + 8 + idx, (where & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, (where & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     HxStream *ss = a.st + s;
     const HxParams *gp = a.prm + ss->cls;
@@ -422,7 +422,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         L.up[c][b] = 0; L.lo[c][b] = 0;
     }
     if (LANE < 42) L.sf_save[LANE / 21][LANE % 21] = ss->sf_save[LANE / 21][LANE % 21];
-    if (LANE == 0) { L.pow43 = gt->pow43; L.big_counter = COLD(done_counter) + 3; L.nstrict = 0; }
+    if (LANE == 0) { L.pow43 = gt->pow43; L.big_counter = COLD(done_counter) + HX_CNT_BIG_SWEEPS; L.nstrict = 0; }
     if (LANE < 4) L.P.head[LANE] = gp->head[LANE];
     if (LANE < 16) L.P.vbr_main_framebytes[LANE] = gp->vbr_main_framebytes[LANE];
     if (LANE < 22) L.P.rnBand_l[LANE] = gp->rnBand_l[LANE];
@@ -852,11 +852,11 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         COLD(out_bytes)[s] = done;
         COLD(carry_len)[s] = opos - done;
         COLD(dur)[s] = (unsigned) (wall_clock64() - t_start);
-        if (L.nstrict) atomicAdd(COLD(done_counter) + 4, L.nstrict);
+        if (L.nstrict) atomicAdd(COLD(done_counter) + HX_CNT_STRICT_SUMS, L.nstrict);
         __threadfence();
-        atomicAdd(COLD(done_counter), 1);
+        atomicAdd(COLD(done_counter) + HX_CNT_RETIRED, 1);
         // this position's CU is no longer reserved (see "parking" above)
-        if (idx < (COLD(park_k) & 0xFFFF)) __hip_atomic_store((unsigned *) COLD(done_counter) + 8 + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (idx < (COLD(park_k) & 0xFFFF)) __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
 #if HX_PERSIST
     // the helper wave is through with this stream (its last stores read the outbox and the stream constants in LDS) before
@@ -870,7 +870,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         HX_LANE_DECL;
         const int pk = COLD(park_k) & 0xFFFF;
         if (pk > 0 && LANE == 0) {
-            unsigned *resv = (unsigned *) COLD(done_counter) + 8;
+            unsigned *resv = (unsigned *) COLD(done_counter) + HX_CNT_PARK;
             const unsigned me = ((((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu)) & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u;
             for (int k = 0; k < pk; k++) {
                 if (__hip_atomic_load(resv + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != me) continue;
@@ -882,9 +882,9 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         }
         // the last workgroup out leaves the claim counter at zero for the next launch (launches of a batch follow each other
         // on one HIP stream; a recorded graph replays the launch with the same arguments, so nothing here may depend on the host)
-        if (HX_PERSIST && LANE == 0 && atomicAdd(COLD(done_counter) + 6, 1) == (int) gridDim.x - 1) {
-            __hip_atomic_store(COLD(done_counter) + 5, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(COLD(done_counter) + 6, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (HX_PERSIST && LANE == 0 && atomicAdd(COLD(done_counter) + HX_CNT_IDLE, 1) == (int) gridDim.x - 1) {
+            __hip_atomic_store(COLD(done_counter) + HX_CNT_CLAIMED, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(COLD(done_counter) + HX_CNT_IDLE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         HELPER_POST(HCMD_EXIT, 0);
     }
@@ -896,20 +896,11 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
 #ifndef HX_WAVES
 #define HX_WAVES 2          // waves per SIMD the register allocation aims at (2: 256 VGPRs, 3: 168, 4: 128)
 #endif
-// HX_DYN_LDS (experiments): the workgroup's LDS as a dynamic allocation, so that the compiler does not derive the
-// kernel's occupancy (and with it the register budget) from the static size; the launch passes hx_k6_lds_bytes().
-#ifdef HX_DYN_LDS
-extern __shared__ __align__(16) unsigned char hx_dyn_lds[];
-#define HX_K6_LDS AllocLds &L = *reinterpret_cast<AllocLds *>(hx_dyn_lds)
-#else
-#define HX_K6_LDS __shared__ AllocLds L
-#endif
 // The stream walk's waves issue ahead of the front-end and packing waves that share a SIMD with them in the launch's tail
 // (measured: +0.6 % config 2, +0.8 % config 3).
 #define HX_K6_PRIO __builtin_amdgcn_s_setprio(3)
 #define HX_K6(name, lsf) \
-    __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void name(AllocArgs a) { HX_K6_PRIO; HX_K6_LDS; alloc_stream<lsf>(a, L); } \
-    extern "C" int name##_lds_bytes() { return (int) sizeof(AllocLds); } \
+    __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void name(AllocArgs a) { HX_K6_PRIO; __shared__ AllocLds L; alloc_stream<lsf>(a, L); } \
     extern "C" int name##_persistent() { return HX_PERSIST; }
 #if HX_A1 && !HX_LSF
 // streams of the first-generation allocator (intensity stereo, dual channel), MPEG-1 rates

@@ -5,6 +5,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
+#include <limits.h>
 #include <vector>
 #include <chrono>
 #include <atomic>
@@ -42,17 +43,7 @@ __global__ void k_alloc_slim(AllocArgs a);
 __global__ void k_alloc_lsf(AllocArgs a);
 __global__ void k_alloc1(AllocArgs a);
 __global__ void k_alloc1_lsf(AllocArgs a);
-extern "C" int k_alloc_lds_bytes();
-extern "C" int k_alloc_slim_lds_bytes();
 extern "C" int k_alloc_slim_persistent();      // 1: the kernel's workgroups claim streams from a counter (hx_alloc3.inc, HX_PERSIST)
-extern "C" int k_alloc_lsf_lds_bytes();
-extern "C" int k_alloc1_lds_bytes();
-extern "C" int k_alloc1_lsf_lds_bytes();
-#ifdef HX_DYN_LDS
-#define K6_LDS(name) ((size_t) name##_lds_bytes())
-#else
-#define K6_LDS(name) ((size_t) 0)
-#endif
 
 static thread_local std::string g_err;
 static void set_err(const char *fmt, const char *a = "")
@@ -65,11 +56,29 @@ static void set_err(const char *fmt, const char *a = "")
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 // every kernel launch is checked where it is made: a bad configuration or a lost device is reported
 // with the kernel's name instead of surfacing at some later call
-#define LAUNCH_LDS(kernel, grid, block, lds, stream, ...) do { hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
+#define LAUNCH(kernel, grid, block, stream, ...) do { hipLaunchKernelGGL(kernel, grid, block, 0, stream, __VA_ARGS__); \
         hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { set_err("launch of " #kernel " failed: %s", hipGetErrorString(e_)); return -1; } } while (0)
-#define LAUNCH(kernel, grid, block, stream, ...) LAUNCH_LDS(kernel, grid, block, 0, stream, __VA_ARGS__)
 
-#define HX_PARK_MAX 64
+// The buffers that hand a call's granules from the front end to the stream walk (layouts: AllocArgs).
+// The submit path keeps two sets: the front end of call n + 1 fills one while the stream walk of call n reads the other.
+struct FrontSet {
+    float *xr, *etab, *thr;
+    float *x34;                         // x^(3/4) of the magnitudes (k_prep writes it in debug mode only)
+    float *thrprev;                     // [S][2][64] pre-echo memory at the call's start
+    int *msbase, *msdec;
+    unsigned char *bt, *btprev, *msflag;
+    HxBandPrep *band;
+};
+// ... and from the stream walk to the packing: quantised lines, segment and frame records, slot lists, and the byte counts of
+// the pending frames' images at the call's start / end (views into hx_batch::d_lens)
+struct WalkSet {
+    short *ixq;
+    HxSegOut *seg;
+    HxFrameOut *frm;
+    HxSlot *slots;
+    int *pre_len, *carry_len;
+};
+
 struct hx_batch {
     int device = 0, S = 0, maxF = 0, ncls = 0;
     std::vector<HxParams> params;       // host copy per class
@@ -77,20 +86,12 @@ struct hx_batch {
     HxParams *d_prm = nullptr;
     HxGlobalTabs *d_gt = nullptr;
     HxStream *d_st = nullptr;
-    float *d_sb = nullptr, *d_xr = nullptr, *d_etab = nullptr, *d_thr = nullptr;
-    // k_msscan / k_prep -> k_alloc: x^(3/4), signs, band start values, stereo decision, pre-echo memory at call start
-    float *d_x34 = nullptr, *d_thrprev = nullptr, *d_xrdbg = nullptr;
-    unsigned *d_sgn = nullptr;          // the lines' signs, one bit per line: [S][NG][2][HX_SGN_WORDS]
-    unsigned char *d_msflag = nullptr;
-    HxBandPrep *d_band = nullptr;
-    int *d_msdec = nullptr;
-    // k_alloc -> k_pack: quantised lines, segment and frame records, slot lists
-    short *d_ixq = nullptr, *d_ixq2 = nullptr;          // (second set: the submit path, where call n + 1 is allocated while call n is packed)
-    HxSegOut *d_seg = nullptr, *d_seg2 = nullptr;
-    HxFrameOut *d_frm = nullptr, *d_frm2 = nullptr;
-    HxSlot *d_slots = nullptr, *d_slots2 = nullptr;
-    unsigned *d_sgn3 = nullptr;                    // third set of the signs: written by the front end of call n + 2 while call n is packed
-    int *d_lens = nullptr;                              // [2 sets][pre_len | carry_len][S]
+    float *d_sb = nullptr, *d_xrdbg = nullptr;
+    FrontSet front[2] = {};             // [1]: created at the first submit (pipe_init)
+    WalkSet walk[2] = {};
+    unsigned *sgn[3] = {};              // the lines' signs, one bit per line: [S][NG][2][HX_SGN_WORDS]; read by the packing, so three sets
+                                        // on the submit path (the front end of call n + 2 writes one while call n is packed)
+    int *d_lens = nullptr;              // [2 sets][pre_len | carry_len][S]
     int *frame_stats = nullptr;         // caller's per-frame counters (device), optional
     unsigned char *pk_buf = nullptr; long long pk_stride = 0; int *pk_bytes = nullptr;   // caller's packet buffers (device), optional
     float *d_pcmf = nullptr;            // DC-blocked input, only when a stream uses filter_select = 1
@@ -99,8 +100,8 @@ struct hx_batch {
     int lsf = 0;                        // 1: an MPEG-2 LSF batch (16 / 22.05 / 24 kHz): every 1152-sample block yields two frames
     int slim = 0;                       // 1: the low-footprint stream walk k_alloc_slim (six streams per CU instead of four), chosen at create
     int alloc1 = 0;                     // 1: streams of the first-generation allocator (intensity stereo, dual channel): k_alloc1*
-    int *d_eng = nullptr, *d_msbase = nullptr, *d_status = nullptr, *d_dbgmetric = nullptr;
-    unsigned char *d_flg = nullptr, *d_bt = nullptr, *d_btprev = nullptr;
+    int *d_eng = nullptr, *d_status = nullptr, *d_dbgmetric = nullptr;
+    unsigned char *d_flg = nullptr;
     HxFrameDebug *d_dbg = nullptr;
     unsigned long long *d_prof = nullptr;
     int lastNG = 0;                     // NG of the previous call (layout of the carry)
@@ -108,17 +109,10 @@ struct hx_batch {
     // staging for the host-buffer entry points
     int16_t *d_pcm = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr;
     long long pcm_cap = 0, out_cap = 0;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr;
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double alloc_ms_sum = 0; int alloc_calls = 0;
     // hx_batch_submit_*: the front-end kernels of call n+1 run (low-priority stream) while k_alloc of
-    // call n (high-priority stream) works through its slowest streams; a second set of the buffers
-    // that hand granules from the front end to k_alloc makes that safe.
-    float *d_xr2 = nullptr, *d_etab2 = nullptr, *d_thr2 = nullptr, *d_x342 = nullptr, *d_thrprev2 = nullptr;
-    int *d_msbase2 = nullptr, *d_msdec2 = nullptr;
-    unsigned char *d_bt2 = nullptr, *d_btprev2 = nullptr, *d_msflag2 = nullptr;
-    unsigned *d_sgn2 = nullptr;
-    HxBandPrep *d_band2 = nullptr;
+    // call n (high-priority stream) works through its slowest streams (see FrontSet)
     hipStream_t s_front = nullptr, s_alloc = nullptr, s_pack = nullptr;
     hipEvent_t ev_in = nullptr, ev_front[2] = {nullptr, nullptr}, ev_alloc[2] = {nullptr, nullptr};     // ev_alloc: a submit's packing is done (everything is)
     hipEvent_t ev_k6[2] = {nullptr, nullptr};           // a submit's allocator launch is done
@@ -136,7 +130,7 @@ struct hx_batch {
     long long nhost = 0;
     unsigned *d_dur = nullptr;          // [S] duration of each stream's allocator workgroup in the last launch
     int *d_order = nullptr;             // [S] workgroup -> stream for the next launch (used when the batch exceeds what the chip holds at once)
-    int *d_done = nullptr;              // [0] streams retired, [2] streams started by all k_alloc launches of this batch (wrap), [1] gate time-outs, [3] line passes on the double x^(4/3) table, [4] certified band sums that fell back to the strict sum
+    int *d_done = nullptr;              // [HX_CNT_WORDS] the counter block (hx_types.h, HxCounter)
     int resident = 0;                   // allocator workgroups the device holds at once
     long long alloc_launches = 0;
     unsigned long long cfg_hash = 0;    // fingerprint of the resolved configuration classes (checkpoint blobs carry their stream's)
@@ -160,8 +154,11 @@ struct hx_batch {
     int ncu = 256;                      // compute units of the device
     int park_k = 8;                     // HMP3AMD_PARK: the CUs of this many longest streams are kept free of other kernels' workgroups (0 = off; see hx_alloc3.inc, "parking")
     int park_pair = 0;                  // HMP3AMD_PARK_PAIR=1: also the CU that shares the instruction cache with a straggler's
-    int front_chunk = 0;                // HMP3AMD_FRONT_CHUNK: streams per pass of the front-end chain (0 = the whole batch at once)
     int strict_sums = 0;                // HMP3AMD_EXACT_SUMS=1: the stream walk adds every band in line order instead of certifying a parallel sum (tests)
+    // everything the batch allocates or creates on the device (dev_alloc, new_stream, new_event): hx_batch_destroy releases it
+    std::vector<void *> mem;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
 };
 
 extern "C" const char *hx_last_error(void) { return g_err.c_str(); }
@@ -184,6 +181,69 @@ extern "C" void hx_default_control(HX_E_CONTROL *ec) { hx_host_default_control((
 
 static int flush_pack(hx_batch *b, long long gate_base);
 
+// Every device buffer, HIP stream and event of a batch is made by one of these three and listed in the batch, whose
+// hx_batch_destroy releases them.
+template <class T> static int dev_alloc(hx_batch *b, T *&p, long long bytes)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, (size_t) bytes) != hipSuccess) { set_err("hipMalloc failed"); return -1; }
+    b->mem.push_back(q);
+    p = (T *) q;
+    return 0;
+}
+// (staging that grows with the call: the old buffer is freed, its contents are not kept)
+template <class T> static int dev_realloc(hx_batch *b, T *&p, long long bytes)
+{
+    if (p) {
+        hipFree(p);
+        for (void *&m : b->mem) if (m == p) { m = b->mem.back(); b->mem.pop_back(); break; }
+        p = nullptr;
+    }
+    return dev_alloc(b, p, bytes);
+}
+static int new_stream(hx_batch *b, hipStream_t &q, int priority = INT_MAX)     // (INT_MAX: the runtime's default priority)
+{
+    HIPCHK(priority == INT_MAX ? hipStreamCreateWithFlags(&q, hipStreamNonBlocking) : hipStreamCreateWithPriority(&q, hipStreamNonBlocking, priority));
+    b->streams.push_back(q);
+    return 0;
+}
+static int new_event(hx_batch *b, hipEvent_t &e)
+{
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    b->events.push_back(e);
+    return 0;
+}
+
+// Buffer set k: front[k], walk[k] and sgn[k] (k = 1: also sgn[2], the third set of signs).
+static int alloc_set(hx_batch *b, int k)
+{
+    const long long S = b->S, NG = 2LL * b->maxF;
+    FrontSet &f = b->front[k];
+    WalkSet &w = b->walk[k];
+    if (dev_alloc(b, f.xr, sizeof(float) * S * NG * 1152) || dev_alloc(b, f.etab, sizeof(float) * S * NG * 128) ||
+        dev_alloc(b, f.thr, sizeof(float) * S * NG * 128) || dev_alloc(b, f.x34, sizeof(float) * S * NG * 1152) ||
+        dev_alloc(b, f.thrprev, sizeof(float) * S * 128) || dev_alloc(b, f.msbase, sizeof(int) * S * NG) ||
+        dev_alloc(b, f.msdec, sizeof(int) * S * NG) || dev_alloc(b, f.bt, S * NG) || dev_alloc(b, f.btprev, S) ||
+        dev_alloc(b, f.msflag, S * NG) || dev_alloc(b, f.band, sizeof(HxBandPrep) * S * NG) ||
+        dev_alloc(b, w.ixq, sizeof(short) * S * NG * 1152) || dev_alloc(b, w.seg, sizeof(HxSegOut) * S * NG * 2) ||
+        dev_alloc(b, w.frm, sizeof(HxFrameOut) * S * NG) || dev_alloc(b, w.slots, sizeof(HxSlot) * S * (NG + HX_SLOTS_EXTRA)))
+        return -1;
+    w.pre_len = b->d_lens + 2 * k * S;
+    w.carry_len = w.pre_len + S;
+    const long long sgn_bytes = sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS;
+    return (dev_alloc(b, b->sgn[k], sgn_bytes) || (k == 1 && dev_alloc(b, b->sgn[2], sgn_bytes))) ? -1 : 0;
+}
+
+// Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
+// A packing that cannot be enqueued leaves the batch unusable (see encode_core).
+static int drain(hx_batch *b)
+{
+    HIPCHK(hipSetDevice(b->device));
+    if (flush_pack(b, -1) != 0) { b->poisoned = true; return -1; }
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
 extern "C" void hx_batch_destroy(hx_batch *b)
 {
     if (!b) return;
@@ -192,30 +252,9 @@ extern "C" void hx_batch_destroy(hx_batch *b)
     // is dropped, not enqueued: it would write into output buffers the caller may have freed already.
     b->pack_job.pending = false;
     hipDeviceSynchronize();
-    void *ptrs[] = {b->d_prm, b->d_gt, b->d_st, b->d_sb, b->d_xr, b->d_etab, b->d_thr, b->d_eng, b->d_msbase,
-                    b->d_status, b->d_dbgmetric, b->d_flg, b->d_bt, b->d_btprev, b->d_dbg, b->d_pcm, b->d_out, b->d_outbytes, b->d_pcmf, b->d_prof,
-                    b->d_xr2, b->d_etab2, b->d_thr2, b->d_msbase2, b->d_bt2, b->d_btprev2, b->d_done,
-                    b->d_x34, b->d_thrprev, b->d_xrdbg, b->d_sgn, b->d_msflag, b->d_band, b->d_msdec,
-                    b->d_x342, b->d_thrprev2, b->d_sgn2, b->d_msflag2, b->d_band2, b->d_msdec2,
-                    b->d_ixq, b->d_seg, b->d_frm, b->d_slots, b->d_dur, b->d_order,
-                    b->d_ixq2, b->d_seg2, b->d_frm2, b->d_slots2, b->d_sgn3, b->d_lens};
-    for (void *p : ptrs) if (p) hipFree(p);
-    for (int i = 0; i < 2; i++) {
-        if (b->hs_pcm[i]) hipFree(b->hs_pcm[i]);
-        if (b->hs_out[i]) hipFree(b->hs_out[i]);
-        if (b->hs_nb[i]) hipFree(b->hs_nb[i]);
-        if (b->ev_h2d[i]) hipEventDestroy(b->ev_h2d[i]);
-        if (b->ev_d2h[i]) hipEventDestroy(b->ev_d2h[i]);
-        if (b->ev_hfront[i]) hipEventDestroy(b->ev_hfront[i]);
-    }
-    if (b->s_h2d) hipStreamDestroy(b->s_h2d);
-    if (b->s_d2h) hipStreamDestroy(b->s_d2h);
-    if (b->s_host) hipStreamDestroy(b->s_host);
-    if (b->s_front) hipStreamDestroy(b->s_front);
-    if (b->s_alloc) hipStreamDestroy(b->s_alloc);
-    if (b->s_pack) hipStreamDestroy(b->s_pack);
-    hipEvent_t evs[] = {b->ev_in, b->ev_front[0], b->ev_front[1], b->ev_alloc[0], b->ev_alloc[1], b->ev_k6[0], b->ev_k6[1], b->ev_sgn[0], b->ev_sgn[1], b->ev_sgn[2]};
-    for (hipEvent_t e : evs) if (e) hipEventDestroy(e);
+    for (void *p : b->mem) hipFree(p);
+    for (hipStream_t q : b->streams) hipStreamDestroy(q);
+    for (hipEvent_t e : b->events) hipEventDestroy(e);
     for (auto &pr : b->pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     delete b;
 }
@@ -270,49 +309,32 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     hx_global_tabs(&gt);
     std::vector<HxStream> st(nstreams);
     for (int s = 0; s < nstreams; s++) hx_stream_reset(&b->params[b->cls_of[s]], b->cls_of[s], &st[s]);
-#define ALLOC(ptr, bytes) do { if (hipMalloc((void **) &(ptr), (size_t) (bytes)) != hipSuccess) { set_err("hipMalloc failed"); hx_batch_destroy(b); return nullptr; } } while (0)
+#define ALLOC(ptr, bytes) do { if (dev_alloc(b, ptr, bytes) != 0) { hx_batch_destroy(b); return nullptr; } } while (0)
     ALLOC(b->d_prm, sizeof(HxParams) * b->ncls + 256);        // (k_spec reads a spreading row in 16-byte pieces, up to 60 bytes past its end)
     ALLOC(b->d_gt, sizeof(HxGlobalTabs));
     ALLOC(b->d_st, sizeof(HxStream) * S);
     ALLOC(b->d_sb, sizeof(float) * S * 2 * (NG + 3) * 576);
-    ALLOC(b->d_xr, sizeof(float) * S * NG * 1152);
-    ALLOC(b->d_etab, sizeof(float) * S * NG * 128);
-    ALLOC(b->d_thr, sizeof(float) * S * NG * 128);
-    ALLOC(b->d_x34, sizeof(float) * S * NG * 1152);
-    ALLOC(b->d_sgn, sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS);
-    ALLOC(b->d_band, sizeof(HxBandPrep) * S * NG);
-    ALLOC(b->d_msflag, S * NG);
-    ALLOC(b->d_msdec, sizeof(int) * S * NG);
-    ALLOC(b->d_thrprev, sizeof(float) * S * 128);
-    ALLOC(b->d_ixq, sizeof(short) * S * NG * 1152);
-    ALLOC(b->d_seg, sizeof(HxSegOut) * S * NG * 2);
-    ALLOC(b->d_frm, sizeof(HxFrameOut) * S * NG);
-    ALLOC(b->d_slots, sizeof(HxSlot) * S * (NG + HX_SLOTS_EXTRA));
+    ALLOC(b->d_lens, sizeof(int) * 4 * S);
+    if (alloc_set(b, 0) != 0) { hx_batch_destroy(b); return nullptr; }
     ALLOC(b->d_eng, sizeof(int) * S * 2 * NG * 9);
-    ALLOC(b->d_msbase, sizeof(int) * S * NG);
     ALLOC(b->d_flg, S * NG);
-    ALLOC(b->d_bt, S * NG);
-    ALLOC(b->d_btprev, S);
     ALLOC(b->d_status, sizeof(int));
     ALLOC(b->d_outbytes, sizeof(int) * S);
     if (const char *e = getenv("HMP3AMD_LPT")) b->lpt = atoi(e);
     if (const char *e = getenv("HMP3AMD_EXACT_SUMS")) b->strict_sums = atoi(e) != 0;
-    if (const char *e = getenv("HMP3AMD_FRONT_CHUNK")) b->front_chunk = atoi(e);
     if (const char *e = getenv("HMP3AMD_PARK_PAIR")) b->park_pair = atoi(e) != 0;
     if (const char *e = getenv("HMP3AMD_PARK")) { b->park_k = atoi(e); if (b->park_k < 0) b->park_k = 0; if (b->park_k > HX_PARK_MAX) b->park_k = HX_PARK_MAX; }
-    ALLOC(b->d_lens, sizeof(int) * 4 * S);
     ALLOC(b->d_dur, sizeof(unsigned) * 2 * S);        // [S] durations, [S] where workgroup i of the last launch ran (see "place")
     ALLOC(b->d_order, sizeof(int) * S);
     HIPCHKN(hipMemset(b->d_dur, 0, sizeof(unsigned) * 2 * S));
-    ALLOC(b->d_done, (8 + HX_PARK_MAX) * sizeof(int));       // ([8 ..]: CU ids of the parking scheme, hx_alloc3.inc)
-    HIPCHKN(hipMemset(b->d_done, 0, (8 + HX_PARK_MAX) * sizeof(int)));
+    ALLOC(b->d_done, HX_CNT_WORDS * sizeof(int));
+    HIPCHKN(hipMemset(b->d_done, 0, HX_CNT_WORDS * sizeof(int)));
     {
         hipDeviceProp_t prop;
         int per_cu = 0;
         HIPCHKN(hipGetDeviceProperties(&prop, device));
         const void *kern = b->alloc1 ? (b->lsf ? (const void *) k_alloc1_lsf : (const void *) k_alloc1) : (b->lsf ? (const void *) k_alloc_lsf : (const void *) k_alloc);
-        const size_t dyn = b->alloc1 ? (b->lsf ? K6_LDS(k_alloc1_lsf) : K6_LDS(k_alloc1)) : (b->lsf ? K6_LDS(k_alloc_lsf) : K6_LDS(k_alloc));
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128, dyn) != hipSuccess || per_cu <= 0) per_cu = 4;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
         b->resident = per_cu * prop.multiProcessorCount;
         b->ncu = prop.multiProcessorCount;
         // Two builds of the MPEG-1 stream walk.  A batch that the chip holds at once (config 2: 1024 streams on 256 CUs x 4)
@@ -327,7 +349,7 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
         if (e && strcmp(e, "slim") == 0 && !slim_ok && !b->alloc1 && !b->lsf) { set_err("HMP3AMD_K6=slim: the host's tables do not have the structure k_alloc_slim derives them from"); hx_batch_destroy(b); return nullptr; }
         if (want && slim_ok) {
             b->slim = 1;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *) k_alloc_slim, 128, K6_LDS(k_alloc_slim)) != hipSuccess || per_cu <= 0) per_cu = 6;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *) k_alloc_slim, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 6;
             b->resident = per_cu * prop.multiProcessorCount;
         }
     }
@@ -367,9 +389,7 @@ extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b) { (void) b; 
 static int stream_state_copy(hx_batch *b, int i, void *host, bool save)
 {
     if (!b || i < 0 || i >= b->S || !host) { set_err("bad arguments"); return -1; }
-    HIPCHK(hipSetDevice(b->device));
-    if (b->s_pack) flush_pack(b, -1);
-    HIPCHK(hipDeviceSynchronize());
+    if (drain(b) != 0) return -1;
     HxStateHeader hd = {HX_STATE_MAGIC, HX_STATE_VERSION, (unsigned) sizeof(HxStream), 0, cfg_fingerprint(b->params[b->cls_of[i]])};
     if (save) memcpy(host, &hd, sizeof(hd));
     else {
@@ -403,9 +423,7 @@ extern "C" int hx_batch_set_stream_state(hx_batch *b, int i, const void *src) { 
 extern "C" int hx_batch_reset_stream(hx_batch *b, int i)
 {
     if (!b || i < 0 || i >= b->S) { set_err("stream index out of range"); return -1; }
-    HIPCHK(hipSetDevice(b->device));
-    if (b->s_pack) flush_pack(b, -1);
-    HIPCHK(hipDeviceSynchronize());
+    if (drain(b) != 0) return -1;
     HxStream *st = new HxStream;
     hx_stream_reset(&b->params[b->cls_of[i]], b->cls_of[i], st);
     hipError_t e = hipMemcpy(b->d_st + i, st, sizeof(HxStream), hipMemcpyHostToDevice);
@@ -442,11 +460,10 @@ extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
     b->debug = on != 0;
     if (on && !b->d_dbg) {
         hipSetDevice(b->device);
-        hipMalloc((void **) &b->d_dbg, sizeof(HxFrameDebug) * (size_t) b->S * b->maxF);
-        hipMalloc((void **) &b->d_xrdbg, sizeof(float) * (size_t) b->S * 2 * b->maxF * 1152);
-        hipMalloc((void **) &b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 2);
-        hipMalloc((void **) &b->d_prof, sizeof(unsigned long long) * (size_t) b->S * 64);
-        hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * 64);
+        dev_alloc(b, b->d_dbg, sizeof(HxFrameDebug) * (size_t) b->S * b->maxF);
+        dev_alloc(b, b->d_xrdbg, sizeof(float) * (size_t) b->S * 2 * b->maxF * 1152);
+        dev_alloc(b, b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 2);
+        if (dev_alloc(b, b->d_prof, sizeof(unsigned long long) * (size_t) b->S * 64) == 0) hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * 64);
     }
 }
 
@@ -454,37 +471,13 @@ extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
 static int pipe_init(hx_batch *b)
 {
     if (b->s_front) return 0;
-    const long long S = b->S, NG = 2LL * b->maxF;
     int lo = 0, hi = 0;
     HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));          // lo = least urgent, hi = most urgent
-    HIPCHK(hipStreamCreateWithPriority(&b->s_front, hipStreamNonBlocking, lo));
-    HIPCHK(hipStreamCreateWithPriority(&b->s_alloc, hipStreamNonBlocking, hi));
-    HIPCHK(hipStreamCreateWithPriority(&b->s_pack, hipStreamNonBlocking, lo));
-    HIPCHK(hipEventCreateWithFlags(&b->ev_in, hipEventDisableTiming));
-    for (int i = 0; i < 2; i++) {
-        HIPCHK(hipEventCreateWithFlags(&b->ev_front[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&b->ev_alloc[i], hipEventDisableTiming));
-        HIPCHK(hipEventCreateWithFlags(&b->ev_k6[i], hipEventDisableTiming));
-    }
-    for (int i = 0; i < 3; i++) HIPCHK(hipEventCreateWithFlags(&b->ev_sgn[i], hipEventDisableTiming));
-    HIPCHK(hipMalloc((void **) &b->d_ixq2, sizeof(short) * S * NG * 1152));
-    HIPCHK(hipMalloc((void **) &b->d_seg2, sizeof(HxSegOut) * S * NG * 2));
-    HIPCHK(hipMalloc((void **) &b->d_frm2, sizeof(HxFrameOut) * S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_slots2, sizeof(HxSlot) * S * (NG + HX_SLOTS_EXTRA)));
-    HIPCHK(hipMalloc((void **) &b->d_sgn3, sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS));
-    HIPCHK(hipMalloc((void **) &b->d_xr2, sizeof(float) * S * NG * 1152));
-    HIPCHK(hipMalloc((void **) &b->d_etab2, sizeof(float) * S * NG * 128));
-    HIPCHK(hipMalloc((void **) &b->d_thr2, sizeof(float) * S * NG * 128));
-    HIPCHK(hipMalloc((void **) &b->d_msbase2, sizeof(int) * S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_bt2, S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_btprev2, S));
-    HIPCHK(hipMalloc((void **) &b->d_x342, sizeof(float) * S * NG * 1152));
-    HIPCHK(hipMalloc((void **) &b->d_sgn2, sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS));
-    HIPCHK(hipMalloc((void **) &b->d_band2, sizeof(HxBandPrep) * S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_msflag2, S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_msdec2, sizeof(int) * S * NG));
-    HIPCHK(hipMalloc((void **) &b->d_thrprev2, sizeof(float) * S * 128));
-    return 0;
+    if (new_stream(b, b->s_front, lo) || new_stream(b, b->s_alloc, hi) || new_stream(b, b->s_pack, lo) || new_event(b, b->ev_in)) return -1;
+    for (int i = 0; i < 2; i++)
+        if (new_event(b, b->ev_front[i]) || new_event(b, b->ev_alloc[i]) || new_event(b, b->ev_k6[i])) return -1;
+    for (int i = 0; i < 3; i++) if (new_event(b, b->ev_sgn[i])) return -1;
+    return alloc_set(b, 1);
 }
 
 // Argument checks of every encode entry point, made before anything is allocated, copied or launched.
@@ -502,28 +495,22 @@ static int check_call(const hx_batch *b, const void *pcm, int nframes, const voi
 static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride, int *d_out_bytes, int nframes, int set, int sset, hipStream_t qp)
 {
     const int S = b->S, NG = 2 * nframes;
-    unsigned *const x_sgn = sset == 2 ? b->d_sgn3 : (sset ? b->d_sgn2 : b->d_sgn);
-    short *const x_ixq = set ? b->d_ixq2 : b->d_ixq;
-    HxSegOut *const x_seg = set ? b->d_seg2 : b->d_seg;
-    HxFrameOut *const x_frm = set ? b->d_frm2 : b->d_frm;
-    HxSlot *const x_slots = set ? b->d_slots2 : b->d_slots;
-    int *const x_prelen = b->d_lens + (2 * set) * (long long) b->S, *const x_carrylen = b->d_lens + (2 * set + 1) * (long long) b->S;
+    const WalkSet &w = b->walk[set];
+    const unsigned *sgn = b->sgn[sset];
     const int fps = (b->lsf ? 2 : 1) * nframes;
     const long long total = (long long) S * fps;
     // a handful of frames in all (the one-stream encoder's calls): one workgroup does the three kernels' work (hx_pack.hip, solo)
     const int solo = (S <= 4 && total <= 8) ? S : 0;
     if (solo) {
-        LAUNCH(k_pack, dim3(1), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxGlobalTabs *) b->d_gt,
-               (const short *) x_ixq, (const unsigned *) x_sgn, (const HxSegOut *) x_seg, (const HxFrameOut *) x_frm, (const HxSlot *) x_slots,
-               d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, (const int *) x_prelen, (const int *) d_out_bytes, (const int *) x_carrylen, b->cap_frames,
-               (solo == 1) ? b->cap_host : (unsigned char *) nullptr, (const int *) (b->d_done + 2));
+        LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
+               d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, d_out_bytes, w.carry_len, b->cap_frames,
+               (solo == 1) ? b->cap_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
         return 0;
     }
-    LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, (const HxStream *) b->d_st, d_out, out_stride, (const int *) x_prelen);
-    LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxGlobalTabs *) b->d_gt,
-           (const short *) x_ixq, (const unsigned *) x_sgn, (const HxSegOut *) x_seg, (const HxFrameOut *) x_frm, (const HxSlot *) x_slots,
+    LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, w.pre_len);
+    LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
            d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
-    LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, (const unsigned char *) d_out, out_stride, (const int *) d_out_bytes, (const int *) x_carrylen, b->cap_frames);
+    LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, d_out_bytes, w.carry_len, b->cap_frames);
     return 0;
 }
 
@@ -537,7 +524,8 @@ static int flush_pack(hx_batch *b, long long gate_base)
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && b->gate_percent > 0) {
         const long long fill = b->S < b->resident ? b->S : b->resident;
-        LAUNCH(k_gate, dim3(1), dim3(64), b->s_pack, (const unsigned *) (b->d_done + 2), (unsigned) gate_base, (unsigned) (fill * b->gate_percent / 100), b->d_done + 1);
+        LAUNCH(k_gate, dim3(1), dim3(64), b->s_pack, (const unsigned *) (b->d_done + HX_CNT_STARTED), (unsigned) gate_base, (unsigned) (fill * b->gate_percent / 100),
+               b->d_done + HX_CNT_GATE_TIMEOUTS);
     }
     if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
@@ -582,7 +570,7 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
             const unsigned base = (unsigned) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S);   // wraps with the counter
             const long long fill = b->S < b->resident ? b->S : b->resident;     // workgroups of the previous launch the device holds at once
             const unsigned need = (unsigned) (fill * b->gate_percent / 100);
-            LAUNCH(k_gate, dim3(1), dim3(64), q, (const unsigned *) (b->d_done + 2), base, need, b->d_done + 1);
+            LAUNCH(k_gate, dim3(1), dim3(64), q, (const unsigned *) (b->d_done + HX_CNT_STARTED), base, need, b->d_done + HX_CNT_GATE_TIMEOUTS);
         }
     } else if (b->inflight) {                                       // a plain call behind submits: order it after them
         if (flush_pack(b, -1) != 0) return -1;
@@ -591,22 +579,12 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
         HIPCHK(hipStreamWaitEvent(q, b->ev_alloc[last], 0));
         b->inflight = false;
     }
-    float *const x_xr = set ? b->d_xr2 : b->d_xr, *const x_etab = set ? b->d_etab2 : b->d_etab, *const x_thr = set ? b->d_thr2 : b->d_thr;
-    int *const x_msbase = set ? b->d_msbase2 : b->d_msbase;
-    unsigned char *const x_bt = set ? b->d_bt2 : b->d_bt, *const x_btprev = set ? b->d_btprev2 : b->d_btprev;
-    float *const x_x34 = set ? b->d_x342 : b->d_x34, *const x_thrprev = set ? b->d_thrprev2 : b->d_thrprev;
+    const FrontSet &f = b->front[set];
+    const WalkSet &w = b->walk[set];
     // (the signs are also read by the packing, which may still be busy with submit n-2 when the front end of submit n
     // writes them: three sets in rotation)
     const int sset = pipelined ? (int) (b->nsubmit % 3) : 0;
-    unsigned *const x_sgn = sset == 2 ? b->d_sgn3 : (sset ? b->d_sgn2 : b->d_sgn);
-    unsigned char *const x_msflag = set ? b->d_msflag2 : b->d_msflag;
-    short *const x_ixq = set ? b->d_ixq2 : b->d_ixq;
-    HxSegOut *const x_seg = set ? b->d_seg2 : b->d_seg;
-    HxFrameOut *const x_frm = set ? b->d_frm2 : b->d_frm;
-    HxSlot *const x_slots = set ? b->d_slots2 : b->d_slots;
-    int *const x_prelen = b->d_lens + (2 * set) * (long long) b->S, *const x_carrylen = b->d_lens + (2 * set + 1) * (long long) b->S;
-    HxBandPrep *const x_band = set ? b->d_band2 : b->d_band;
-    int *const x_msdec = set ? b->d_msdec2 : b->d_msdec;
+    unsigned *const sgn = b->sgn[sset];
     const int S = b->S, NG = 2 * nframes;
     const long long nsamp = 1152LL * nframes;
     // The subband carry sits in slots NG_prev..NG_prev+2 only if the previous call used another
@@ -616,41 +594,20 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
     const float *pcmf = b->any_dc ? b->d_pcmf : d_pcm32;       // fp32 samples the polyphase reads, or null for int16
     if (b->any_dc) LAUNCH(k_dcfilter, dim3((b->nchan * S + 63) / 64), dim3(64), q, d_pcm, d_pcm32, nsamp, b->d_st, b->d_prm, b->d_pcmf, S, b->nchan);
     // (the carry in slots 0..2 is not written by k_polyphase, so the two may run in either order)
-    // The chain runs over the whole batch, or (b->front_chunk, HMP3AMD_FRONT_CHUNK) over blocks of streams one after the
-    // other: a block's subband samples and spectrum (2.4 + 1.2 MB per stream at 256 frames) are then still in the memory-side
-    // cache when the next kernel of the chain reads them.  Every kernel indexes its per-stream arrays from the block's first stream.
-    const int C = (b->front_chunk > 0 && b->front_chunk < S && !b->debug) ? b->front_chunk : S;
-    auto front = [&](int s0, int Sc) -> int {
-        const long long o = s0;
-        float *sb_c = b->d_sb + o * 2 * SG * 576;
-        int *eng_c = b->d_eng + o * 2 * NG * 9;
-        HxStream *st_c = b->d_st + o;
-        const int16_t *pcm_c = d_pcm ? d_pcm + o * nsamp * b->nchan : nullptr;
-        const float *pcmf_c = pcmf ? pcmf + o * nsamp * b->nchan : nullptr;
-        unsigned char *bt_c = x_bt + o * NG;
-        dim3 g1c(Sc, (NG + K1_GPB - 1) / K1_GPB);
-        // (the detector energies of the carried granule are formed by k_polyphase's first tile of a stream, the carries rolled by
-        // k_msscan, flags and block types by one kernel - round 6: three launches less per call, which is what a one-stream call
-        // is made of)
-        LAUNCH(k_polyphase, g1c, dim3(K1_THREADS), q, pcm_c, nsamp, st_c, b->d_prm, b->d_gt, sb_c, NG, SG, pcmf_c, b->nchan, eng_c, b->lsf);
-        LAUNCH(k_detect, dim3((Sc + 3) / 4), dim3(256), q, st_c, b->d_prm, eng_c, b->d_flg + o * NG,
-               b->debug ? b->d_dbgmetric : nullptr, bt_c, x_btprev + o, NG, Sc, b->lsf);
-        // (the form of K4 that goes with the stream-walk kernel: hx_front.hip, spec_granule)
-        if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) Sc * nframes)), dim3(128), q, sb_c, st_c, b->d_prm, b->d_gt, bt_c, x_xr + o * NG * 1152,
-                            x_etab + o * NG * 128, x_thr + o * NG * 128, x_msbase + o * NG, NG, SG);
-        else LAUNCH(k_spec, dim3((unsigned) ((long long) Sc * nframes)), dim3(128), q, sb_c, st_c, b->d_prm, b->d_gt, bt_c, x_xr + o * NG * 1152,
-                    x_etab + o * NG * 128, x_thr + o * NG * 128, x_msbase + o * NG, NG, SG);
-        // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
-        // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
-        // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
-        LAUNCH(k_msscan, dim3(Sc), dim3(64), q, st_c, b->d_prm, x_msbase + o * NG, bt_c, x_msflag + o * NG, x_msdec + o * NG, x_thr + o * NG * 128, x_thrprev + o * 128, NG, b->lsf,
-               sb_c, SG, pcm_c, nsamp, pcmf_c, b->nchan);
-        LAUNCH(k_prep, dim3((unsigned) (((long long) Sc * NG + 3) / 4)), dim3(256), q, (const float *) (x_xr + o * NG * 1152), (b->debug && b->d_xrdbg) ? b->d_xrdbg : (float *) nullptr, b->debug ? x_x34 : (float *) nullptr,
-               x_sgn + o * NG * 2 * HX_SGN_WORDS, x_band + o * NG, st_c, b->d_prm, b->d_gt, bt_c, x_msflag + o * NG,
-               x_etab + o * NG * 128, x_thr + o * NG * 128, x_thrprev + o * 128, NG, (long long) Sc * NG);
-        return 0;
-    };
-    for (int s0 = 0; s0 < S; s0 += C) if (front(s0, (S - s0 < C) ? S - s0 : C) != 0) return -1;
+    // (the detector energies of the carried granule are formed by k_polyphase's first tile of a stream, the carries rolled by
+    // k_msscan, flags and block types by one kernel - round 6: three launches less per call, which is what a one-stream call
+    // is made of)
+    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf);
+    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf);
+    // (the form of K4 that goes with the stream-walk kernel: hx_front.hip, spec_granule)
+    if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
+    else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
+    // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
+    // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
+    // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
+    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->lsf, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan);
+    LAUNCH(k_prep, dim3((unsigned) (((long long) S * NG + 3) / 4)), dim3(256), q, f.xr, (b->debug && b->d_xrdbg) ? b->d_xrdbg : (float *) nullptr, b->debug ? f.x34 : (float *) nullptr,
+           sgn, f.band, b->d_st, b->d_prm, b->d_gt, f.bt, f.msflag, f.etab, f.thr, f.thrprev, NG, (long long) S * NG);
     if (pipelined) {
         HIPCHK(hipEventRecord(b->ev_front[set], q));
         HIPCHK(hipStreamWaitEvent(qa, b->ev_front[set], 0));
@@ -670,8 +627,8 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
         }
     }
     AllocArgs a;
-    a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = x_xr; a.etab = x_etab; a.thr = x_thr;
-    a.msbase = x_msbase; a.bt = x_bt; a.btprev = x_btprev; a.out = d_out; a.out_bytes = d_out_bytes;
+    a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
+    a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = d_out; a.out_bytes = d_out_bytes;
     a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = out_stride; a.NG = NG; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
     a.packet = b->pk_buf; a.packet_stride = b->pk_stride; a.packet_bytes = b->pk_bytes; a.frame_stats = b->frame_stats;
     a.done_counter = b->d_done;
@@ -686,9 +643,9 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
         // parked slot would keep a waiting stream out - and from the second call on (the order is the previous call's)
         if (S <= b->resident && b->alloc_launches > 0 && !b->alloc1 && !b->lsf) a.park_k = (b->park_k < S / 8 ? b->park_k : S / 8) | (b->park_pair << 16);
     }
-    a.x34 = x_x34; a.sgn = x_sgn; a.band = x_band; a.msflag = x_msflag; a.msdec = x_msdec; a.thrprev = x_thrprev;
-    a.ixq = x_ixq; a.sgn_w = x_sgn; a.seg = x_seg; a.frm = x_frm; a.slots = x_slots;
-    a.pre_len = x_prelen; a.carry_len = x_carrylen;
+    a.x34 = f.x34; a.sgn = sgn; a.band = f.band; a.msflag = f.msflag; a.msdec = f.msdec; a.thrprev = f.thrprev;
+    a.ixq = w.ixq; a.sgn_w = sgn; a.seg = w.seg; a.frm = w.frm; a.slots = w.slots;
+    a.pre_len = w.pre_len; a.carry_len = w.carry_len;
     b->alloc_launches++;
     hipEvent_t e0 = nullptr, e1 = nullptr;
     if (!b->capturing) {
@@ -700,10 +657,10 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
     // the launch order after the other (hx_alloc3.inc)
     // (built into k_alloc_slim, the kernel of batches beyond the resident set; the 256-register kernels keep one workgroup per stream)
     const int G = (b->slim && !b->alloc1 && !b->lsf && k_alloc_slim_persistent() && S > b->resident) ? b->resident : S;
-    if (b->alloc1) { if (b->lsf) LAUNCH_LDS(k_alloc1_lsf, dim3(G), dim3(128), K6_LDS(k_alloc1_lsf), qa, a); else LAUNCH_LDS(k_alloc1, dim3(G), dim3(128), K6_LDS(k_alloc1), qa, a); }
-    else if (b->lsf) LAUNCH_LDS(k_alloc_lsf, dim3(G), dim3(128), K6_LDS(k_alloc_lsf), qa, a);
-    else if (b->slim) LAUNCH_LDS(k_alloc_slim, dim3(G), dim3(128), K6_LDS(k_alloc_slim), qa, a);
-    else LAUNCH_LDS(k_alloc, dim3(G), dim3(128), K6_LDS(k_alloc), qa, a);
+    if (b->alloc1) { if (b->lsf) LAUNCH(k_alloc1_lsf, dim3(G), dim3(128), qa, a); else LAUNCH(k_alloc1, dim3(G), dim3(128), qa, a); }
+    else if (b->lsf) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, a);
+    else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, a);
+    else LAUNCH(k_alloc, dim3(G), dim3(128), qa, a);
     if (!b->capturing) {
         HIPCHK(hipEventRecord(e1, qa));
         b->pending.push_back({e0, e1});
@@ -825,22 +782,15 @@ static int submit_host_pass(hx_batch *b, const void *pcm, int is_f32, int nframe
     HIPCHK(hipSetDevice(b->device));
     const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (is_f32 ? sizeof(float) : sizeof(int16_t)), obytes = (long long) b->S * out_stride;
     if (!b->s_h2d) {
-        HIPCHK(hipStreamCreateWithFlags(&b->s_h2d, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&b->s_d2h, hipStreamNonBlocking));
-        HIPCHK(hipStreamCreateWithFlags(&b->s_host, hipStreamNonBlocking));
-        for (int i = 0; i < 2; i++) {
-            HIPCHK(hipEventCreateWithFlags(&b->ev_h2d[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&b->ev_d2h[i], hipEventDisableTiming));
-            HIPCHK(hipEventCreateWithFlags(&b->ev_hfront[i], hipEventDisableTiming));
-            HIPCHK(hipMalloc((void **) &b->hs_nb[i], sizeof(int) * b->S));
-        }
+        if (new_stream(b, b->s_h2d) || new_stream(b, b->s_d2h) || new_stream(b, b->s_host)) return -1;
+        for (int i = 0; i < 2; i++)
+            if (new_event(b, b->ev_h2d[i]) || new_event(b, b->ev_d2h[i]) || new_event(b, b->ev_hfront[i]) || dev_alloc(b, b->hs_nb[i], sizeof(int) * b->S)) return -1;
     }
     if (pbytes > b->hs_pcm_cap || obytes > b->hs_out_cap) {     // (re)size the staging: drain first
-        if (b->s_pack) flush_pack(b, -1);
-        HIPCHK(hipDeviceSynchronize());
+        if (drain(b) != 0) return -1;
         for (int i = 0; i < 2; i++) {
-            if (pbytes > b->hs_pcm_cap) { if (b->hs_pcm[i]) hipFree(b->hs_pcm[i]); HIPCHK(hipMalloc(&b->hs_pcm[i], (size_t) pbytes)); }
-            if (obytes > b->hs_out_cap) { if (b->hs_out[i]) hipFree(b->hs_out[i]); HIPCHK(hipMalloc((void **) &b->hs_out[i], (size_t) obytes)); }
+            if (pbytes > b->hs_pcm_cap && dev_realloc(b, b->hs_pcm[i], pbytes) != 0) return -1;
+            if (obytes > b->hs_out_cap && dev_realloc(b, b->hs_out[i], obytes) != 0) return -1;
         }
         if (pbytes > b->hs_pcm_cap) b->hs_pcm_cap = pbytes;
         if (obytes > b->hs_out_cap) b->hs_out_cap = obytes;
@@ -912,14 +862,13 @@ static int encode_host(hx_batch *b, const void *pcm, int is_f32, int nframes, un
     if (check_call(b, pcm, nframes, out, out_stride, out_bytes) != 0) return -1;
     HIPCHK(hipSetDevice(b->device));
     long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (is_f32 ? sizeof(float) : sizeof(int16_t)), obytes = (long long) b->S * out_stride;
-    if (pbytes > b->pcm_cap) { if (b->d_pcm) hipFree(b->d_pcm); HIPCHK(hipMalloc((void **) &b->d_pcm, pbytes)); b->pcm_cap = pbytes; }
-    if (obytes > b->out_cap) { if (b->d_out) hipFree(b->d_out); HIPCHK(hipMalloc((void **) &b->d_out, obytes)); b->out_cap = obytes; }
+    if (pbytes > b->pcm_cap) { if (dev_realloc(b, b->d_pcm, pbytes) != 0) return -1; b->pcm_cap = pbytes; }
+    if (obytes > b->out_cap) { if (dev_realloc(b, b->d_out, obytes) != 0) return -1; b->out_cap = obytes; }
     HIPCHK(hipMemcpy(b->d_pcm, pcm, pbytes, hipMemcpyHostToDevice));
     int r = encode_core(b, is_f32 ? nullptr : (const int16_t *) b->d_pcm, is_f32 ? (const float *) b->d_pcm : nullptr, nframes,
                         b->d_out, out_stride, b->d_outbytes, nullptr);
     if (r) return r;
-    if (b->s_pack) flush_pack(b, -1);
-    HIPCHK(hipDeviceSynchronize());
+    if (drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out, b->d_out, obytes, hipMemcpyDeviceToHost));
     return 0;
@@ -972,9 +921,7 @@ extern "C" int hx_batch_status(hx_batch *b)
     int v = -1;
     if (!b) return -1;
     if (b->poisoned) return -1;
-    hipSetDevice(b->device);
-    if (b->s_pack && flush_pack(b, -1) != 0) { b->poisoned = true; return -1; }     // (the last device-buffer submit's packing: it writes that submit's output buffers)
-    hipDeviceSynchronize();
+    if (drain(b) != 0) return -1;       // (the last device-buffer submit's packing: it writes that submit's output buffers)
     // (a gate that gave up waiting costs overlap, not correctness: it is counted in hx_batch_gate_timeouts, not here)
     if (hipMemcpy(&v, b->d_status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
     return v;
@@ -988,22 +935,18 @@ extern "C" int hx_batch_resident_streams(const hx_batch *b) { return b ? b->resi
 // submits whose front end started late because its gate gave up waiting (see hx_batch_set_gate); synchronises
 extern "C" int hx_batch_gate_timeouts(hx_batch *b)
 {
-    int gate[2] = {0, 0};
+    int v[HX_CNT_GATE_TIMEOUTS + 1] = {};
     if (!b) return -1;
-    hipSetDevice(b->device);
-    if (b->s_pack) flush_pack(b, -1);
-    hipDeviceSynchronize();
-    if (hipMemcpy(gate, b->d_done, sizeof(gate), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return gate[1];
+    if (drain(b) != 0) return -1;
+    if (hipMemcpy(v, b->d_done, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return v[HX_CNT_GATE_TIMEOUTS];
 }
 
 extern "C" HX_INT_PAIR hx_batch_frames_bytes(hx_batch *b, int i)
 {
     HX_INT_PAIR r = {0, 0};
     if (!b || i < 0 || i >= b->S) return r;
-    hipSetDevice(b->device);
-    if (b->s_pack) flush_pack(b, -1);
-    hipDeviceSynchronize();
+    (void) drain(b);
     unsigned v[2];
     hipMemcpy(&v[0], (char *) (b->d_st + i) + offsetof(HxStream, tot_frames_out), 4, hipMemcpyDeviceToHost);
     hipMemcpy(&v[1], (char *) (b->d_st + i) + offsetof(HxStream, tot_bytes_out), 4, hipMemcpyDeviceToHost);
@@ -1014,31 +957,31 @@ extern "C" HX_INT_PAIR hx_batch_frames_bytes(hx_batch *b, int i)
 extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap)
 {
     if (!b || !name || !dst) return -1;
-    hipSetDevice(b->device);
-    if (b->s_pack) flush_pack(b, -1);
-    hipDeviceSynchronize();
+    (void) drain(b);
     const long long S = b->S, NG = b->lastNG;
+    const FrontSet &f = b->front[0];
+    const WalkSet &w = b->walk[0];
     const void *src = nullptr;
     long long n = 0;
     std::string k(name);
     if (k == "sb") { src = b->d_sb; n = sizeof(float) * S * 2 * (2LL * b->maxF + 3) * 576; }
-    else if (k == "xr") { src = b->d_xr; n = sizeof(float) * S * NG * 1152; }       // the spectrum
+    else if (k == "xr") { src = f.xr; n = sizeof(float) * S * NG * 1152; }       // the spectrum
     else if (k == "xmag") { src = b->d_xrdbg; n = sizeof(float) * S * NG * 1152; }  // the magnitudes k_prep works on (written in debug mode only)
-    else if (k == "x34") { src = b->d_x34; n = sizeof(float) * S * NG * 1152; }
-    else if (k == "band") { src = b->d_band; n = sizeof(HxBandPrep) * S * NG; }
-    else if (k == "msflag") { src = b->d_msflag; n = S * NG; }
-    else if (k == "ixq") { src = b->d_ixq; n = sizeof(short) * S * NG * 1152; }
-    else if (k == "sgn") { src = b->d_sgn; n = (long long) sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS; }      // one bit per line, HX_SGN_WORDS words per (granule, channel)
-    else if (k == "seg") { src = b->d_seg; n = sizeof(HxSegOut) * S * NG * 2; }
-    else if (k == "frm") { src = b->d_frm; n = sizeof(HxFrameOut) * S * NG; }
-    else if (k == "etab") { src = b->d_etab; n = sizeof(float) * S * NG * 128; }
-    else if (k == "thr") { src = b->d_thr; n = sizeof(float) * S * NG * 128; }
-    else if (k == "msbase") { src = b->d_msbase; n = sizeof(int) * S * NG; }
+    else if (k == "x34") { src = f.x34; n = sizeof(float) * S * NG * 1152; }
+    else if (k == "band") { src = f.band; n = sizeof(HxBandPrep) * S * NG; }
+    else if (k == "msflag") { src = f.msflag; n = S * NG; }
+    else if (k == "ixq") { src = w.ixq; n = sizeof(short) * S * NG * 1152; }
+    else if (k == "sgn") { src = b->sgn[0]; n = (long long) sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS; }      // one bit per line, HX_SGN_WORDS words per (granule, channel)
+    else if (k == "seg") { src = w.seg; n = sizeof(HxSegOut) * S * NG * 2; }
+    else if (k == "frm") { src = w.frm; n = sizeof(HxFrameOut) * S * NG; }
+    else if (k == "etab") { src = f.etab; n = sizeof(float) * S * NG * 128; }
+    else if (k == "thr") { src = f.thr; n = sizeof(float) * S * NG * 128; }
+    else if (k == "msbase") { src = f.msbase; n = sizeof(int) * S * NG; }
     else if (k == "place") { src = b->d_dur + S; n = sizeof(unsigned) * S; }       // per WORKGROUP of the last allocator launch (launch order): XCC id << 16 | HW_ID[15:0] (CU [11:8], SH [12], SE [15:13])
     else if (k == "dur") { src = b->d_dur; n = sizeof(unsigned) * S; }              // the last allocator launch's per-stream durations, 100 MHz ticks
-    else if (k == "big_sweeps") { src = b->d_done + 3; n = sizeof(int); }        // gain-search line passes that took the double x^(4/3) table
-    else if (k == "strict_sums") { src = b->d_done + 4; n = sizeof(int); }       // certified band sums that fell back to the strict line-order sum
-    else if (k == "bt") { src = b->d_bt; n = S * NG; }
+    else if (k == "big_sweeps") { src = b->d_done + HX_CNT_BIG_SWEEPS; n = sizeof(int); }        // gain-search line passes that took the double x^(4/3) table
+    else if (k == "strict_sums") { src = b->d_done + HX_CNT_STRICT_SUMS; n = sizeof(int); }       // certified band sums that fell back to the strict line-order sum
+    else if (k == "bt") { src = f.bt; n = S * NG; }
     else if (k == "eng") { src = b->d_eng; n = sizeof(int) * S * 2 * NG * 9; }
     else if (k == "dbg" && b->d_dbg) { src = b->d_dbg; n = sizeof(HxFrameDebug) * S * (NG / 2); }
     else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * 64; }
@@ -1127,7 +1070,6 @@ struct hx_enc {
     float *h_pcm = nullptr;             // page-locked: one 1152-sample block, float at int16 scale
     unsigned char *h_out = nullptr;     // page-locked, coherent: [byte count | frame counter | sequence word | ... 256 | the call's bitstream], written by the packing workgroup
     int graph_state = 0;                // 0 = not built yet, 1 = ready, -1 = not available (disabled, or the build failed: plain calls)
-    bool spin_off = false;              // HMP3AMD_ENC_GRAPH=2: always wait with hipStreamSynchronize (A/B of the wait)
     int plain_calls = 0;                // calls made the plain way since init (the first ones: they also load the kernels' code objects)
 };
 #define HX_ENC_GRAPH_OFF 256
@@ -1188,13 +1130,13 @@ static int enc_graph_build(hx_enc *e)
     const long long stride = (long long) e->outbuf.size();
     const long long pbytes = 1152LL * b->nchan * (long long) sizeof(float);
     // allocated before the recording starts (no allocation inside one)
-    if (pbytes > b->pcm_cap) { if (b->d_pcm) hipFree(b->d_pcm); HIPCHK(hipMalloc((void **) &b->d_pcm, pbytes)); b->pcm_cap = pbytes; }
+    if (pbytes > b->pcm_cap) { if (dev_realloc(b, b->d_pcm, pbytes) != 0) return -1; b->pcm_cap = pbytes; }
     HIPCHK(hipMalloc((void **) &e->d_encbuf, (size_t) (HX_ENC_GRAPH_OFF + stride)));
     HIPCHK(hipMemset(e->d_encbuf, 0, (size_t) (HX_ENC_GRAPH_OFF + stride)));
     HIPCHK(hipHostMalloc((void **) &e->h_pcm, (size_t) pbytes, hipHostMallocDefault));
     HIPCHK(hipHostMalloc((void **) &e->h_out, (size_t) (HX_ENC_GRAPH_OFF + stride + 16), hipHostMallocCoherent));
     memset(e->h_out, 0, (size_t) (HX_ENC_GRAPH_OFF + stride + 16));
-    HIPCHK(hipMemcpy(e->h_out + 8, b->d_done + 2, sizeof(int), hipMemcpyDeviceToHost));       // the sequence word as the device has it now
+    HIPCHK(hipMemcpy(e->h_out + 8, b->d_done + HX_CNT_STARTED, sizeof(int), hipMemcpyDeviceToHost));       // the sequence word as the device has it now
     HIPCHK(hipStreamCreateWithFlags(&e->gq, hipStreamNonBlocking));
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipStreamBeginCapture(e->gq, hipStreamCaptureModeThreadLocal));
@@ -1229,7 +1171,6 @@ static HX_IN_OUT encode_one(hx_enc *e, const void *pcm, int is_f32, unsigned cha
     const bool plain = !is_f32 || b->debug || b->pk_buf || b->frame_stats || b->poisoned || b->inflight || e->graph_state < 0 || e->plain_calls < 2;
     if (!plain && e->graph_state == 0) {
         const char *env = getenv("HMP3AMD_ENC_GRAPH");
-        e->spin_off = env && atoi(env) == 2;
         if (env && atoi(env) == 0) e->graph_state = -1;
         else if (enc_graph_build(e) == 0) e->graph_state = 1;
         else {      // plain calls from here on (the staging stays allocated until the encoder is re-initialised or destroyed)
@@ -1248,11 +1189,11 @@ static HX_IN_OUT encode_one(hx_enc *e, const void *pcm, int is_f32, unsigned cha
             // behind which the kernel's writes are complete as well
             const auto t0 = std::chrono::steady_clock::now();
             int spins = 0;
-            while (!e->spin_off && *seq == before) {
+            while (*seq == before) {
                 __builtin_ia32_pause();
                 if ((++spins & 1023) == 0 && std::chrono::steady_clock::now() - t0 > std::chrono::milliseconds(2)) break;
             }
-            if (*seq == before || e->spin_off) ok = hipStreamSynchronize(e->gq) == hipSuccess;
+            if (*seq == before) ok = hipStreamSynchronize(e->gq) == hipSuccess;
             std::atomic_thread_fence(std::memory_order_acquire);
         }
         if (ok) {

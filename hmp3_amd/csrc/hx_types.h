@@ -201,6 +201,21 @@ struct alignas(16) HxFrameOut {
 // 16-byte alignment.  (As one byte per line they were 0.6 GB written and 0.6 GB read per config-2 step.)
 #define HX_SGN_WORDS 20
 
+// Slots of a batch's counter block (AllocArgs::done_counter; the host runtime reads some of them and hands two to k_gate and k_pack).
+enum HxCounter {
+    HX_CNT_RETIRED = 0,         // streams retired
+    HX_CNT_GATE_TIMEOUTS = 1,   // gates (k_gate) that gave up waiting
+    HX_CNT_STARTED = 2,         // streams started by all allocator launches of the batch (wraps): the gates wait on it, the one-stream
+                                // encoder's packing publishes it as the call's sequence word
+    HX_CNT_BIG_SWEEPS = 3,      // gain-search line passes that took the double x^(4/3) table
+    HX_CNT_STRICT_SUMS = 4,     // certified band sums that fell back to the strict line-order sum
+    HX_CNT_CLAIMED = 5,         // positions of the launch order claimed so far in this launch (persistent workgroups)
+    HX_CNT_IDLE = 6,            // workgroups of this launch that ran out of work (the last one zeroes this and the claim counter)
+    HX_CNT_PARK = 8,            // [HX_CNT_PARK ..]: the CU ids of the parking scheme, one per parked position (hx_alloc3.inc)
+};
+#define HX_PARK_MAX 64
+#define HX_CNT_WORDS (HX_CNT_PARK + HX_PARK_MAX)
+
 // Arguments of the allocator kernels (k_alloc / k_alloc_lsf), filled by the host runtime.
 struct AllocArgs {
     HxStream *st;
@@ -225,10 +240,9 @@ struct AllocArgs {
     int *pre_len, *carry_len;   // [S] bytes of pending frames' images at the call's start (k_pack_pre copies them in) / at its end (k_pack_carry saves them)
     const int *order;           // workgroup -> stream (longest-running first, from the previous call's durations), or null = identity
     unsigned *dur;              // [S] this call's duration of each stream's workgroup, 100 MHz ticks
-    int *done_counter;          // [0] streams retired, [2] streams started by all launches so far (k_gate of a pipelined submit waits on the latter), [3] double-table line passes, [4] certified band sums that fell back to the strict sum,
-                                // [5] positions of the launch order claimed so far in this launch, [6] workgroups of this launch that ran out of work (the last one zeroes both), [8 ..] parking
+    int *done_counter;          // [HX_CNT_WORDS] the batch's counter block (HxCounter)
     int park_k;                 // > 0: the workgroups that share a CU with one of the first park_k workgroups of the launch order (the streams that ran
-                                // longest in the previous call) keep their slot until that one retires (hx_alloc3.inc, "parking"); done_counter[8 ..] holds the CU ids
+                                // longest in the previous call) keep their slot until that one retires (hx_alloc3.inc, "parking")
     int strict_sums;            // 1 = no certified band sums: every band is added in line order (HMP3AMD_EXACT_SUMS=1; tests)
     // from k_msscan / k_prep (hx_front.hip); xr holds the coded magnitudes for long-block granules
     const float *x34;           // [S][NG][2][576] x^(3/4) of the magnitudes (long-block granules)
