@@ -20,12 +20,37 @@
 // The gain search of all 42 bands advances in the same sweep.
 #include "hx_dev.h"
 
+// ---- the five builds ("One source, five builds") ----
+// A wrapper translation unit says which build it is (HX_SLIM, HX_LSF, HX_A1); every other per-build setting follows from those
+// here, and nothing else sets them.
 #ifndef HX_LSF
 #define HX_LSF 0            // 1 when compiled as hx_alloc_lsf.hip: MPEG-2 LSF streams, one granule per frame
 #endif
 #ifndef HX_A1
 #define HX_A1 0             // 1 when compiled as hx_alloc1*.hip: streams of the first-generation allocator (intensity stereo, dual channel)
 #endif
+#ifndef HX_SLIM
+#define HX_SLIM 0           // 1 when compiled as hx_alloc_slim.hip: the low-footprint LDS layout (see AllocLds below)
+#endif
+#if HX_SLIM && HX_A1
+#error "the low-footprint layout is built for the second-generation allocator only"
+#endif
+// Waves per SIMD the register allocation aims at (2: 256 VGPRs, 3: 168, 4: 128): the low-footprint build holds six streams per CU.
+#define HX_WAVES (HX_SLIM ? 3 : 2)
+// Persistent workgroups (alloc_stream): built into the low-footprint kernel only, the one that runs batches beyond the resident
+// set.  In the 256-register builds the loop around the stream makes the compiler hoist lane predicates and addresses out of it:
+// 218 -> 256 VGPRs and 512 bytes of scratch; they keep one workgroup per stream.
+#define HX_PERSIST HX_SLIM
+// The rate loop's correction paths (HX_RATE) compiled for speed.  (Measured: config 2 +2.2 %, its worst-case signal set +2.4 %.
+// The 168-register build keeps them cold: compiled for speed they pull their callees in, the kernel grows by 6 KB and its scalar
+// spills by 55: config 3 -2.2 %.)
+#define HX_RATE_SPEED (!HX_SLIM)
+// The lane number opaque to the compiler (hx_lane_opaque): on for the 168-register build; the 256-register builds keep the plain
+// value - there the hoisted values stay in registers, and recomputing them costs the stream's chain 2 %.
+#define HX_OPAQUE_LANE HX_SLIM
+// The gain search (seek_actual_ch) inlined at its three call sites in the 168-register build: as a call it saved and restored 54
+// registers per lane each time.
+#define HX_SEEK_FORCEINLINE HX_SLIM
 #define GMIN_OFFSET 70
 #define PART23 4021
 #define NB 22
@@ -84,12 +109,6 @@ struct alignas(16) Outbox {
 //    the mB-log and log-subtract tables as 16-bit values;
 //  * the short-block allocator's gain-step arrays and the band tables as int16, the scalefactor outputs as bytes, big_lucky's
 //    work list in an array of its own.
-#ifndef HX_SLIM
-#define HX_SLIM 0
-#endif
-#if HX_SLIM && HX_A1
-#error "the low-footprint layout is built for the second-generation allocator only"
-#endif
 #if HX_SLIM
 typedef short ix_t;                     // a quantised line
 typedef short sgs_t;                    // short-block gain steps / scalefactors per band (0 .. 127, flags 0 / -1)
@@ -208,7 +227,7 @@ struct alignas(16) AllocLds {
     alignas(16) int cmdw[4];            // work order for the helper wave (see HELPER_POST): command + three arguments, one 16-byte read
     alignas(4) unsigned char gflag[HX_SLIM ? 64 : 256];     // block type | stereo decision << 2 of the next granules (frame loop, hx_alloc3.inc)
 #ifdef HX_PROFILE
-    unsigned prof[64];                  // (the profile build holds three workgroups per CU instead of four: per-stream cycles are what it is for)
+    unsigned prof[HX_PROF_WORDS];       // slots HxProf (hx_types.h).  (The profile build holds three workgroups per CU instead of four: per-stream cycles are what it is for)
 #endif
 };
 
@@ -245,17 +264,21 @@ __device__ __forceinline__ float lk_igain(const float *ig16, int g) { const int 
 
 #ifdef HX_PROFILE
 // (only the master wave's time is booked: the helper wave runs some of the same functions)
-#define PROF(id, stmt) do { SYNC(); long long t0_ = clock64(); stmt; SYNC(); if (threadIdx.x == 0 && (id) < 64) L.prof[(id) % 64] += (unsigned) (clock64() - t0_); } while (0)
+#define PROF(id, stmt) do { SYNC(); long long t0_ = clock64(); stmt; SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - t0_); } while (0)
 #define PROF_T0() long long tp_ = clock64()
 #define PROF_T1() tp_ = clock64()
-#define PROF_CNT(id) do { if (threadIdx.x == 0 && (id) < 64) L.prof[(id) % 64] += 1; } while (0)
-#define PROF_ACC(id) do { SYNC(); if (threadIdx.x == 0 && (id) < 64) L.prof[(id) % 64] += (unsigned) (clock64() - tp_); tp_ = clock64(); } while (0)
+#define PROF_CNT(id) do { if (threadIdx.x == 0) L.prof[(id)] += 1; } while (0)
+#define PROF_ACC(id) do { SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - tp_); tp_ = clock64(); } while (0)
+#define PROF_CLOCK , long long &tp_      // a phase of the frame loop (hx_alloc3.inc) books on the loop's running clock
+#define PROF_PASS , tp_
 #else
 #define PROF(id, stmt) do { stmt; } while (0)
 #define PROF_T0() do { } while (0)
 #define PROF_T1() do { } while (0)
 #define PROF_CNT(id) do { } while (0)
 #define PROF_ACC(id) do { } while (0)
+#define PROF_CLOCK
+#define PROF_PASS
 #endif
 // Rarely taken paths are kept out of line, away from the hot code: the kernel's instructions do not fit
 // the instruction cache that the waves of a CU share (DESIGN.md, K6 in detail).
@@ -264,12 +287,8 @@ __device__ __forceinline__ float lk_igain(const float *ig16, int g) { const int 
 #define HX_HFN __attribute__((noinline))
 // The rate loop's correction paths (increase_bits, decrease_bits, limit_bits and the requantise-and-count they share) run in a
 // minority of granules, but a launch ends with its slowest stream and that stream is one that lives in them: out of line like
-// the cold functions (their code stays away from the common path's), but compiled for speed, not - as `cold` implies - for size.
-// (Measured: config 2 +2.2 %, its worst-case signal set +2.4 %.  The 168-register build keeps them cold: compiled for speed they
-// pull their callees in, the kernel grows by 6 KB and its scalar spills by 55: config 3 -2.2 %.)
-#ifndef HX_RATE_SPEED
-#define HX_RATE_SPEED (!HX_SLIM)
-#endif
+// the cold functions (their code stays away from the common path's), but compiled for speed, not - as `cold` implies - for size
+// (HX_RATE_SPEED, at the top of this file).
 #if HX_RATE_SPEED
 #define HX_RATE __attribute__((noinline))
 #else
@@ -280,18 +299,13 @@ __device__ __forceinline__ float lk_igain(const float *ig16, int g) { const int 
 // dozens of them after inlining - is loop-invariant, gets hoisted out of the frame loop and stays live over all of it: some
 // 130 scalar registers (lane predicates are register pairs) spilled into VGPR lanes, and at the 168-register build those VGPRs
 // and 27 more into scratch, reloaded at 61 places of the frame loop.  Recomputed where a function starts, they cost two
-// instructions there and die with the function.
+// instructions there and die with the function.  (HX_OPAQUE_LANE, at the top of this file: the 168-register build only.)
 __device__ __forceinline__ int hx_lane_opaque()
 {
     int l;
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(l));
     return l;
 }
-// (HX_OPAQUE_LANE: on for the 168-register build; the 256-register builds keep the plain value - there the hoisted values
-// stay in registers, and recomputing them costs the stream's chain 2 %)
-#ifndef HX_OPAQUE_LANE
-#define HX_OPAQUE_LANE HX_SLIM
-#endif
 #if HX_OPAQUE_LANE
 #define HX_LANE_DECL const int lane_ = hx_lane_opaque()
 #else
@@ -549,12 +563,12 @@ __device__ __forceinline__ int noise_sweep(AllocLds &L, const SweepRegs &R, cons
         if (g >= 0) bslow = noise_band_needs_pow(ig, x34max);
     }
     SYNC();
-    PROF_ACC(27);
+    PROF_ACC(HX_PROF_SWEEP_PUBLISH);
     const int anyslow = __any(bslow) ? 1 : 0;
     float part;
     if (__builtin_expect(anyslow, 0)) part = sweep_run_stored(L, ch, W, 1);
     else part = sweep_run(L, R, q, W, ch);
-    PROF_ACC(28);
+    PROF_ACC(HX_PROF_SWEEP_LINES);
     // the band's total arrives in its last lane; the band lane fetches it and certifies the bucket
     float sxx = hx_lane_read(last4, hx_seg_scan(part, q.d, LANE));
     bool strict = false;
@@ -563,7 +577,7 @@ __device__ __forceinline__ int noise_sweep(AllocLds &L, const SweepRegs &R, cons
     int noise = 0;
     if (g >= 0) noise = MBLOG(1.0e-12f + sxx) - logcbw;
     SYNC();
-    PROF_ACC(29);
+    PROF_ACC(HX_PROF_SWEEP_SUMS);
     return noise;
 }
 
@@ -674,9 +688,6 @@ __device__ void seek_initial(AllocLds &L, const AllocPrm *p)
 }
 
 // reference bitallo3.cpp:1164-1296: all bands of channel ch walk their gain step concurrently (lane = sfb)
-#ifndef HX_SEEK_FORCEINLINE
-#define HX_SEEK_FORCEINLINE 0
-#endif
 #if HX_SEEK_FORCEINLINE
 #define HX_SEEK_INLINE __device__ __forceinline__
 #else
@@ -719,9 +730,9 @@ HX_SEEK_INLINE void seek_actual_ch(AllocLds &L, const AllocPrm *p, int ch)
     float ig_dn = 0.0f, gn_dn = 0.0f, ig_up = 0.0f, gn_up = 0.0f;          // pairs of the steps below / above it
     SYNC();
     while (__any(mode != 0)) {
-        PROF_CNT(20);
+        PROF_CNT(HX_PROF_N_SWEEPS);
 #ifdef HX_PROFILE
-        if (threadIdx.x == 64) L.prof[45] += 1;     // the helper wave's sweeps (channel 1)
+        if (threadIdx.x == 64) L.prof[HX_PROF_N_SWEEPS_HELPER] += 1;     // the helper wave's sweeps (channel 1)
 #endif
         const int gcur = (mode == 0) ? -1 : (mode == 1 ? s : t);
         // requested now, used after this sweep (low-footprint layout: the tables' mantissas now, their scaling then)
@@ -762,7 +773,7 @@ __device__ void seek_actual(AllocLds &L, const AllocPrm *p)
     if (two) HELPER_JOIN();
     else if (LANE < NB) L.geval[1][LANE] = -1;
     SYNC();
-    PROF_ACC(30);
+    PROF_ACC(HX_PROF_SEEK_JOIN);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -994,7 +1005,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         if (!(s >= s0) || (GG - s) >= g0) mode = 2;        // loop body never runs
     }
     while (__any(mode == 1)) {
-        PROF_CNT(21);
+        PROF_CNT(HX_PROF_N_LUCKY);
         PROF_T0();
         // valid candidates of this pass: the longest prefix c = 0.. with s - c*sdelta >= s0 and
         // G - s + c*sdelta < g0 (sdelta is 2 or 4)
@@ -1016,7 +1027,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         SYNC();
         const int ncmax = hx_wave_max(nc);
         const bool bslow = mode == 1 && noise_band_needs_pow(LK_IGAIN(GG - s), L.x34max[ch][i]);
-        PROF_ACC(23);
+        PROF_ACC(HX_PROF_LUCKY_SETUP);
         // slots of 64 flattened lines: 3 or 4 (MPEG-2 band tables: 5), shared between the two waves
         const bool two = p->nchan == 2;
         const int big = __any(bslow) ? 1 : 0;       // a band reaches beyond the 256-entry table
@@ -1025,14 +1036,14 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         if (two) HELPER_JOIN();
         else lucky_dispatch(L, nl, ncmax, tf, 1, big);
         SYNC();
-        PROF_ACC(24);
+        PROF_ACC(HX_PROF_LUCKY_TERMS);
         for (int u = LANE; u < total; u += 64) {
             const int e = list[u], c = e >> 8, cc = (e >> 7) & 1, b = e & 31;
             float sxx = band_sum(tf + c * 2 * nl + cc * nl + L.startBand[b], L.nBand[b], 0.0f);
             L.lucky[c][cc][b] = MBLOG(1.0e-12f + sxx) - L.logcbw[b];
         }
         SYNC();
-        PROF_ACC(25);
+        PROF_ACC(HX_PROF_LUCKY_SUMS);
         {   // replay the reference's scan: the last candidate that meets the target wins
             int nz[6];
 #pragma unroll
@@ -1049,7 +1060,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
             }
         }
         SYNC();
-        PROF_ACC(26);
+        PROF_ACC(HX_PROF_LUCKY_REPLAY);
     }
     if (mode == 2) {
         L.sf[ch][i] = smin;
@@ -1252,14 +1263,14 @@ __device__ int count_bits_ch(AllocLds &L, const AllocPrm *p, int ch, int ncb)
     if (bt == 0) { if (cb2 < 2) { cb2 = 2; if (cb3 < cb2) cb3 = cb2; } }
     else { cb0 = 8; cb2 = max(cb2, 8); cb3 = max(cb3, cb2); cb1 = cb0; }
     // topmost line > 1 in the last "big" band, topmost line > 0 in the last count1 band
-    PROF_ACC(36);
+    PROF_ACC(HX_PROF_CNT_BALLOTS);
     int lo2 = L.startBand[cb2 - 1], hi2 = L.startBand[cb2], lo3 = L.startBand[cb3 - 1], hi3 = L.startBand[cb3];
     int j2 = lo2, j3 = lo3;
     for (int j = lo2 + LANE; j < hi2; j += 64) if (ix[j] > 1) j2 = j;
     for (int j = lo3 + LANE; j < hi3; j += 64) if (ix[j] > 0) j3 = j;
     j2 = hx_wave_max(j2);
     j3 = hx_wave_max(j3);
-    PROF_ACC(37);
+    PROF_ACC(HX_PROF_CNT_J23);
     int nbig = (j2 + 2) & (~1);
     if (bt == 0) { if (nbig < L.startBand[2]) nbig = L.startBand[2]; }
     else { if (nbig < L.startBand[8]) nbig = L.startBand[8]; }
@@ -1298,7 +1309,7 @@ __device__ int count_bits_ch(AllocLds &L, const AllocPrm *p, int ch, int ncb)
         c2 = candidates(L, RMAX(cb0, cb2));
     }
 #undef RMAX
-    PROF_ACC(38);
+    PROF_ACC(HX_PROF_CNT_REGIONS);
     const int n0 = L.startBand[cb0], n1 = L.startBand[cb1];
     // pair lengths: region 0 = [0,n0), region 1 = [n0,n1), region 2 = [n1,nbig).
     // The table parameters of the three regions are wave-uniform and read once; a lane picks its
@@ -1354,7 +1365,7 @@ __device__ int count_bits_ch(AllocLds &L, const AllocPrm *p, int ch, int ncb)
             }
         }
     }
-    PROF_ACC(39);
+    PROF_ACC(HX_PROF_CNT_PAIRS);
     int qa = 0, qb = 0;
     {
         int2 qv[3][2];
@@ -1379,7 +1390,7 @@ __device__ int count_bits_ch(AllocLds &L, const AllocPrm *p, int ch, int ncb)
             qb += ok ? 4 + pop : 0;
         }
     }
-    PROF_ACC(40);
+    PROF_ACC(HX_PROF_CNT_QUADS);
     r0a = hx_wave_sum(r0a); r2a = hx_wave_sum(r2a);
     r0b = hx_wave_sum(r0b); r2b = hx_wave_sum(r2b);     // unconditional: the DPP chains interleave
     r1a = hx_wave_sum(r1a); r1b = hx_wave_sum(r1b);
@@ -1401,14 +1412,14 @@ __device__ int count_bits_ch(AllocLds &L, const AllocPrm *p, int ch, int ncb)
         L.hs_nbig[ch] = nbig; L.hs_nquads[ch] = nquads; L.hs_bits[ch] = bits;
         L.huff_bits[ch] = bits;
     }
-    PROF_ACC(41);
+    PROF_ACC(HX_PROF_CNT_REDUCE);
     return bits;
 }
 
 __device__ int count_bits(AllocLds &L, const AllocPrm *p, const int *ncb)
 {
     HX_LANE_DECL;
-    PROF_CNT(22);
+    PROF_CNT(HX_PROF_N_COUNTS);
     // the channels are counted at the same time: channel 1 by the helper wave
     const bool two = p->nchan == 2;
     if (two) HELPER_POST(HCMD_COUNT_BITS, ncb[1]);
@@ -1430,20 +1441,20 @@ __device__ int quant_count_bits(AllocLds &L, const AllocPrm *p, int opt, int zer
         L.gig[ch][i] = LK_IGAIN(L.gsf[ch][i] & 127);
     }
     SYNC();
-    PROF_CNT(22);
+    PROF_CNT(HX_PROF_N_COUNTS);
     const bool two = p->nchan == 2;
     PROF_T0();
     if (two) HELPER_POST2(HCMD_QUANT_COUNT, opt, ncb[1]);
-    PROF_ACC(42);
+    PROF_ACC(HX_PROF_QC_POST);
     quant_lines(L, p, opt, 0);
     SYNC();
-    PROF_ACC(43);
+    PROF_ACC(HX_PROF_QC_QUANT);
     if (zero21) { if (LANE == 0) L.ixmax[0][21] = 0; SYNC(); }
     int bits = count_bits_ch(L, p, 0, ncb[0]);
     PROF_T1();
     if (two) { HELPER_JOIN(); bits += L.hs_bits[1]; }
     SYNC();
-    PROF_ACC(44);
+    PROF_ACC(HX_PROF_QC_JOIN);
     return bits;
 }
 

@@ -401,32 +401,32 @@ __device__ int allocate(AllocLds &L, const AllocPrm *p, int ms)
         if (ms) hf_reset_ms(L, 1); else hf_reset_lr(L);
         clear_hf(L, 2);
     }
-    PROF(2, seek_initial(L, p));
-    PROF(3, seek_actual(L, p));
+    PROF(HX_PROF_SEEK_INITIAL, seek_initial(L, p));
+    PROF(HX_PROF_SEEK_ACTUAL, seek_actual(L, p));
     if (ms) { if (p->hf_flag) hf_adjust_ms(L, p); }
-    else { PROF(4, trade_dual(L, p)); if (p->hf_flag & 2) hf_adjust(L, p); }
-    PROF(5, scale_factors(L, p, ms));
-    PROF(6, big_lucky_noise(L, p));
-    if (!L.hf_quant) PROF(8, bits0 = bits = quant_count_bits(L, p, 1, ms, ms ? p->nsf2 : p->nsf3));
+    else { PROF(HX_PROF_TRADE_DUAL, trade_dual(L, p)); if (p->hf_flag & 2) hf_adjust(L, p); }
+    PROF(HX_PROF_SCALE_FACTORS, scale_factors(L, p, ms));
+    PROF(HX_PROF_BIG_LUCKY, big_lucky_noise(L, p));
+    if (!L.hf_quant) PROF(HX_PROF_QUANT_COUNT, bits0 = bits = quant_count_bits(L, p, 1, ms, ms ? p->nsf2 : p->nsf3));
     else {
-        PROF(7, do_quant(L, p, 1));
+        PROF(HX_PROF_DO_QUANT, do_quant(L, p, 1));
         if (ms) {
             if (LANE == 0) L.ixmax[0][21] = 0;
             SYNC();
             if (L.hf_quant) quant_hf_ch(L, 0, 0);
-            PROF(8, bits0 = bits = count_bits(L, p, p->nsf2));
+            PROF(HX_PROF_QUANT_COUNT, bits0 = bits = count_bits(L, p, p->nsf2));
         } else {
             if (L.hf_quant) { if (L.hf_quant_stereo[0]) quant_hf_ch(L, 0, 1); if (L.hf_quant_stereo[1]) quant_hf_ch(L, 1, 1); }
-            PROF(8, bits0 = bits = count_bits(L, p, p->nsf3));
+            PROF(HX_PROF_QUANT_COUNT, bits0 = bits = count_bits(L, p, p->nsf3));
         }
     }
-    if (bits < L.minTargetBits && L.MNR < 2000) PROF(9, bits = increase_bits(L, p, bits, ms));
+    if (bits < L.minTargetBits && L.MNR < 2000) PROF(HX_PROF_INCREASE_BITS, bits = increase_bits(L, p, bits, ms));
     if (ms) hf_reset_ms(L, 0);
     else if (p->hf_flag) hf_reset_lr(L);
-    if (bits > L.maxTargetBits) { clear_hf(L, ms ? 1 : 2); PROF(10, bits = decrease_bits(L, p, bits)); }
+    if (bits > L.maxTargetBits) { clear_hf(L, ms ? 1 : 2); PROF(HX_PROF_DECREASE_BITS, bits = decrease_bits(L, p, bits)); }
     if (bits > L.maxBits) { clear_hf(L, ms ? 1 : 2); bits = limit_bits(L, p, 0); }
     if (bits > PART23 && (L.huff_bits[0] > PART23 || L.huff_bits[1] > PART23)) { clear_hf(L, ms ? 1 : 2); bits = limit_bits(L, p, 1); }
-    PROF(11, inverse_sf2(L, p));
+    PROF(HX_PROF_INVERSE_SF2, inverse_sf2(L, p));
     return bits0;
 }
 
@@ -521,7 +521,7 @@ __device__ bool bitallo_long(AllocLds &L, const AllocPrm *p, int igr, int block_
     }
     if (!HX_SLIM && block_type == 3) for (int j = LANE; j < 1152; j += 64) IX(0)[j] = 0;     // (low-footprint layout: the quantiser writes every line)
     SYNC();
-    PROF(1, startup_prepped(L, p, ms, bin));
+    PROF(HX_PROF_STARTUP, startup_prepped(L, p, ms, bin));
 
     HxGr *g0 = &L.gr[igr][0];
     if (L.activeBands <= 0) {

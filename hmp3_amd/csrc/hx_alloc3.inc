@@ -1,6 +1,14 @@
 // hx_alloc3.inc - K6 entry point: one wavefront per stream walks the batch's frames
 // (reference mp3enc.cpp:1492-1597 encode_jointB, :2106-2333 CBR/VBR frame drivers).
 
+// Arguments used once per frame or less are re-read from the kernarg segment where they are needed instead of staying in
+// (spilled) scalar registers for the whole kernel.
+#define COLD(field) (((const __attribute__((address_space(4))) AllocArgs *) __builtin_amdgcn_kernarg_segment_ptr())->field)
+// The stream constants of the frame loop are read from LDS (L.P) in the section that uses them - a frame's budget, its
+// placement - a handful of reads in flight together; as scalar registers held over the whole loop they, too, ended up in
+// VGPR lanes and from there in scratch.
+#define RFL(x) __builtin_amdgcn_readfirstlane(x)
+
 // *_Packet entry points (reference mp3enc.cpp:3066-3074, :2944-2951): the frame as a self-contained
 // packet - header with the nominal bitrate index, side info with main_data_begin 0, unpadded main
 // data (header and side information here, the main data by k_pack).  Kept out of line: rarely used, and
@@ -265,120 +273,67 @@ __device__ __forceinline__ void x34_from_coded(AllocLds &L, int ms)
     }
 }
 
-// LSF = 1: MPEG-2 low-sampling-frequency streams.  Every granule is a frame of its own (reference
-// mp3enc.cpp:2483-2593 CBR, :2337-2479 VBR; encode_jointB_MPEG2 :1832-1907, encode_singleB_MPEG2
-// :1977-2027): budgets in bits = bytes << 3, reservoir capped at 255 bytes, no scfsi.
+// The helper wave: serves the master's work orders until it says stop (HCMD_EXIT).
 template <int LSF>
-__device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
+__device__ __forceinline__ void helper_serve(const AllocArgs &a, AllocLds &L)
+{
+    for (;;) {
+        HX_LANE_DECL;       // (per order: nothing derived from the lane number is carried around the loop and over the calls in it)
+        WG_BARRIER();
+        const int4 order = *reinterpret_cast<const int4 *>(&L.cmdw[0]);     // command and its three arguments
+        const int cmd = order.x;
+        // most frequent orders first
+        if (cmd == HCMD_SEEK) seek_actual_ch(L, &L.P, 1);
+        else if (cmd == HCMD_COUNT_BITS) count_bits_ch(L, &L.P, 1, order.y);
+        else if (cmd == HCMD_LUCKY) lucky_dispatch(L, order.y, order.z, &L.term[0][0], 1, order.w);
+        else if (cmd == HCMD_QUANT) quant_lines(L, &L.P, order.y, 1);
+        else if (cmd == HCMD_QUANT_COUNT) { quant_lines(L, &L.P, order.y, 1); SYNC(); count_bits_ch(L, &L.P, 1, order.z); }
+        else if (cmd == HCMD_ISF2) isf2_ch(L, &L.P, 1);
+        else if (cmd == HCMD_FETCH) {
+            // The next granule's operands into LDS; the finished granule's lines and the granule before's outbox to
+            // k_pack.  Only the loads are waited for: what goes out is picked up into registers, the helper reports
+            // back, and the stores are issued behind the master's back.
+            const int s = L.cur_s;      // the stream the master is walking (it changes between two orders only)
+            int nbt = 2, nms = 0;
+            if (order.y >= 0) {
+                granule_fetch(L, a, (long long) s * a.NG + order.y);
+                nbt = a.bt[(long long) s * a.NG + order.y]; nms = a.msflag[(long long) s * a.NG + order.y];
+            }
+            const int gl = order.z, gf = (gl >= 0) ? gl - 1 : ((order.y < 0) ? a.NG - 1 : -1);
+            // (defined on every path: left undefined where nothing is gathered, the compiler carried the previous order's
+            // 38 registers around the helper's loop and saved them over every call in it)
+            LinesRegs lr0 = {}, lr1 = {};
+            OutRegs orr = {};
+            const int two = L.P.nchan == 2;
+            const int gbt = order.w & 255;      // (order word 3: block type | channel c's segment is not empty << (8 + c))
+            if (gl >= 0) { lines_gather(L, (order.w >> 8) & 1, 0, gbt, lr0); if (two) lines_gather(L, (order.w >> 9) & 1, 1, gbt, lr1); }
+            if (gf >= 0) outbox_gather(L, gf, orr);
+            asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
+            const bool long_gr = !HX_A1 && nbt != 2;
+            if (long_gr) {
+                xr_to_coded(L, nms);
+                if (!two) x34_from_coded(L, nms);       // (a mono stream's master never meets the helper before it reads them)
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            }
+            WG_BARRIER();
+            if (gl >= 0) {
+                const long long unit = (long long) s * a.NG + gl;
+                lines_store(a, unit, 0, gbt, lr0);
+                if (two) lines_store(a, unit, 1, gbt, lr1);
+            }
+            if (gf >= 0) outbox_store<LSF>(L, a, s, gf, orr);
+            if (long_gr && two) { x34_from_coded(L, nms); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
+            continue;
+        }
+        else if (cmd == HCMD_EXIT) return;
+        WG_BARRIER();
+    }
+}
+
+// Tables and the stream's carried state into LDS (the profile build also clears the stream's profile and starts its clock).
+__device__ __forceinline__ void stage_stream(const AllocArgs &a, AllocLds &L, const HxStream *ss, const HxParams *gp, const HxGlobalTabs *gt)
 {
     HX_LANE_DECL;
-    // Arguments used once per frame or less are re-read from the kernarg segment where they are
-    // needed instead of staying in (spilled) scalar registers for the whole kernel.
-#define COLD(field) (((const __attribute__((address_space(4))) AllocArgs *) __builtin_amdgcn_kernarg_segment_ptr())->field)
-    // Persistent workgroups: the launch has as many workgroups as the chip holds at once (or one per stream if that is
-    // fewer); each claims the next stream of the launch order from a counter when it is done with one.  (Round 6: with one
-    // workgroup per stream and more streams than slots, the hardware dispatcher deals workgroup i to XCD i mod 8 in strict
-    // order, so a freed slot of another XCD waits for its turn, and every stream's end hands LDS and registers back and takes
-    // them again: config 3 48.6 -> 48.0 ms per step, four full rounds 52.9 -> 51.5 ms.  Most of what a multi-round launch
-    // idles - 14 % of its slot-time - is the last round's drain, which no claiming order removes: a stream's call is one job.)
-    // The launch order is the streams that ran longest in the previous call first (longest-processing-time-first: the
-    // launch's tail is made of short streams).
-    // (HX_PERSIST: built into the low-footprint kernel only, the one that runs batches beyond the resident set.  In the
-    // 256-register builds the loop around the stream makes the compiler hoist lane predicates and addresses out of it: 218 ->
-    // 256 VGPRs and 512 bytes of scratch; they keep one workgroup per stream.)
-#ifndef HX_PERSIST
-#define HX_PERSIST HX_SLIM
-#endif
-    if (!HX_PERSIST && (int) blockIdx.x >= a.S) return;
-    if (WAVE == 1) {        // helper wave: serve the master's work orders until it says stop
-        for (;;) {
-            HX_LANE_DECL;       // (per order: nothing derived from the lane number is carried around the loop and over the calls in it)
-            WG_BARRIER();
-            const int4 order = *reinterpret_cast<const int4 *>(&L.cmdw[0]);     // command and its three arguments
-            const int cmd = order.x;
-            // most frequent orders first
-            if (cmd == HCMD_SEEK) seek_actual_ch(L, &L.P, 1);
-            else if (cmd == HCMD_COUNT_BITS) count_bits_ch(L, &L.P, 1, order.y);
-            else if (cmd == HCMD_LUCKY) lucky_dispatch(L, order.y, order.z, &L.term[0][0], 1, order.w);
-            else if (cmd == HCMD_QUANT) quant_lines(L, &L.P, order.y, 1);
-            else if (cmd == HCMD_QUANT_COUNT) { quant_lines(L, &L.P, order.y, 1); SYNC(); count_bits_ch(L, &L.P, 1, order.z); }
-            else if (cmd == HCMD_ISF2) isf2_ch(L, &L.P, 1);
-            else if (cmd == HCMD_FETCH) {
-                // The next granule's operands into LDS; the finished granule's lines and the granule before's outbox to
-                // k_pack.  Only the loads are waited for: what goes out is picked up into registers, the helper reports
-                // back, and the stores are issued behind the master's back.
-                const int s = L.cur_s;      // the stream the master is walking (it changes between two orders only)
-                int nbt = 2, nms = 0;
-                if (order.y >= 0) {
-                    granule_fetch(L, a, (long long) s * a.NG + order.y);
-                    nbt = a.bt[(long long) s * a.NG + order.y]; nms = a.msflag[(long long) s * a.NG + order.y];
-                }
-                const int gl = order.z, gf = (gl >= 0) ? gl - 1 : ((order.y < 0) ? a.NG - 1 : -1);
-                // (defined on every path: left undefined where nothing is gathered, the compiler carried the previous order's
-                // 38 registers around the helper's loop and saved them over every call in it)
-                LinesRegs lr0 = {}, lr1 = {};
-                OutRegs orr = {};
-                const int two = L.P.nchan == 2;
-                const int gbt = order.w & 255;      // (order word 3: block type | channel c's segment is not empty << (8 + c))
-                if (gl >= 0) { lines_gather(L, (order.w >> 8) & 1, 0, gbt, lr0); if (two) lines_gather(L, (order.w >> 9) & 1, 1, gbt, lr1); }
-                if (gf >= 0) outbox_gather(L, gf, orr);
-                asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-                const bool long_gr = !HX_A1 && nbt != 2;
-                if (long_gr) {
-                    xr_to_coded(L, nms);
-                    if (!two) x34_from_coded(L, nms);       // (a mono stream's master never meets the helper before it reads them)
-                    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-                }
-                WG_BARRIER();
-                if (gl >= 0) {
-                    const long long unit = (long long) s * a.NG + gl;
-                    lines_store(a, unit, 0, gbt, lr0);
-                    if (two) lines_store(a, unit, 1, gbt, lr1);
-                }
-                if (gf >= 0) outbox_store<LSF>(L, a, s, gf, orr);
-                if (long_gr && two) { x34_from_coded(L, nms); asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); }
-                continue;
-            }
-            else if (cmd == HCMD_EXIT) return;
-            WG_BARRIER();
-        }
-    }
-#if HX_PERSIST
-  for (;;) {        // master wave: one stream of the launch order after the other
-    HX_LANE_DECL;
-    int idx = 0;
-    if (LANE == 0) idx = atomicAdd(COLD(done_counter) + HX_CNT_CLAIMED, 1);
-    idx = __builtin_amdgcn_readfirstlane(idx);
-    if (idx >= a.S) break;
-#else
-  {                 // master wave: the stream at this workgroup's position of the launch order
-    const int idx = (int) blockIdx.x;
-#endif
-    const int s = COLD(order) ? COLD(order)[idx] : idx;
-    const long long t_start = wall_clock64();
-    if (LANE == 0) {
-        L.cur_s = s;
-        atomicAdd(COLD(done_counter) + HX_CNT_STARTED, 1);        // this stream is being walked (the gates of the next call's front end count these)
-        // where it runs (tests, placement experiments): XCC id << 16 | HW_ID[15:0], per position in the launch order
-        const unsigned where = ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu);
-        COLD(dur)[a.S + idx] = where;
-        // Parking (resident-set batches): a launch lasts as long as its slowest stream, and the front end of the next call and
-        // the packing of the previous one move into every CU slot a retiring stream frees - also next to that slowest stream,
-        // whose LDS round trips they then lengthen (measured: K6 15.0 ms alone, 16.0 ms with them beside it).  The first
-        // park_k positions of the launch order (the longest streams of the previous call) publish which CU they run on; a
-        // workgroup that runs out of work on one of those CUs keeps its slot - asleep - until that stream has retired too, so
-        // nothing else fits there (a CU holds four of these workgroups: 153 of 160 KB of LDS, all vector registers).
-        // (park_k bit 16: the CU that shares the instruction and scalar caches with it - CU id with the low bit flipped - as well)
-        if (idx < (COLD(park_k) & 0xFFFF))
-            __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, (where & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    HxStream *ss = a.st + s;
-    const HxParams *gp = a.prm + ss->cls;
-    const AllocPrm *p = &L.P;
-    const HxGlobalTabs *gt = a.gt;
-    const int NG = a.NG, F = NG / 2;
-
-    // ---- stage tables and stream state ----
 #if HX_SLIM
     for (int i = LANE; i < 256; i += 64) { L.look_ix43[i] = gp->look_ix43[i]; L.mblog[i] = (unsigned short) (gt->mblog[i] + 38227); }
     if (LANE < 4) L.gain4[LANE] = gp->look_gain[8 + LANE];
@@ -469,22 +424,28 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         }
     }
 #ifdef HX_PROFILE
-    if (threadIdx.x < 64) L.prof[threadIdx.x] = 0;
-    long long tk0_ = clock64();
+    L.prof[LANE] = 0;
+    if (LANE == 0) L.prof[HX_PROF_TOTAL] = (unsigned) clock64();        // (the total is a difference of the low 32 bits)
 #endif
     SYNC();
+}
 
-    // Frame assembly (reference mp3enc.cpp:2258-2325 keeps main data in a ring and copies frames out
-    // when complete).  Here every frame is written straight to its final place in `out`: its slot
-    // offset is the running sum of the frame sizes, main_data_begin is the reservoir level at the
-    // frame's start, and a frame's main data never extends past its own slot.  Pending = frames
-    // whose slot is not full yet: ring [side_p0, side_p1) of slot sizes (r_mf) and header offsets
-    // (r_off); only the first pending slot is partly filled (main_bytes bytes), the later ones are
-    // empty.  Between calls the pending frames' images travel in ss->main_buf (length main_p1).
-    // The reservoir registers, ring positions and the layout cursor (opos: offset of the next frame's header) live in L.fs
-    // (see FrameState): read where a frame is budgeted and where it is placed, not held over the allocator's code between.
-    // (the images of the frames pending from earlier calls are copied to the head of `out` by k_pack_pre: the packer
-    // kernels own the main data, and an allocator launch does not have to wait for the previous call's packing)
+// Frame assembly (reference mp3enc.cpp:2258-2325 keeps main data in a ring and copies frames out
+// when complete).  Here every frame is written straight to its final place in `out`: its slot
+// offset is the running sum of the frame sizes, main_data_begin is the reservoir level at the
+// frame's start, and a frame's main data never extends past its own slot.  Pending = frames
+// whose slot is not full yet: ring [side_p0, side_p1) of slot sizes (r_mf) and header offsets
+// (r_off); only the first pending slot is partly filled (main_bytes bytes), the later ones are
+// empty.  Between calls the pending frames' images travel in ss->main_buf (length main_p1).
+// The reservoir registers, ring positions and the layout cursor (opos: offset of the next frame's header) live in L.fs
+// (see FrameState): read where a frame is budgeted and where it is placed, not held over the allocator's code between.
+// (the images of the frames pending from earlier calls are copied to the head of `out` by k_pack_pre: the packer
+// kernels own the main data, and an allocator launch does not have to wait for the previous call's packing)
+template <int LSF>
+__device__ __forceinline__ void slots_init(const AllocArgs &a, AllocLds &L, int s, const HxStream *ss, const HxParams *gp)
+{
+    HX_LANE_DECL;
+    const int F = a.NG / 2;
     if (LANE == 0) {
         FrameState &fs = L.fs;
         fs.padcount = ss->padcount;
@@ -510,307 +471,295 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         }
     }
     SYNC();
+}
 
-    int bt_last = a.btprev[s];
-    if (LANE == 0) { L.cmdw[2] = -1; L.cmdw[3] = 0; }
-    HELPER_POST(HCMD_FETCH, 0);         // the first granule's operands
-    BandIn bin;
-    // The stream constants of the frame loop are read from LDS (L.P) in the section that uses them - a frame's budget, its
-    // placement - a handful of reads in flight together; as scalar registers held over the whole loop they, too, ended up in
-    // VGPR lanes and from there in scratch.
-#define RFL(x) __builtin_amdgcn_readfirstlane(x)
-    for (int f = 0; f < F; f++) {
-        HX_LANE_DECL;           // (per frame: see hx_lane_opaque)
-        PROF_T0();
-        constexpr int GFN = (int) sizeof(L.gflag);       // granules staged at a time
-        // The per-granule block types and stereo decisions are staged in LDS GFN / 2 frames at a time: fetched from global
-        // memory one frame ahead, the compiler unpacked (= waited for) them at once and spilled them over the frame (2 k cycles).
-        if ((f & (GFN / 2 - 1)) == 0) {
-            const unsigned char *bt_s = COLD(bt) + (long long) s * NG;
-            const unsigned char *ms_s = COLD(msflag) + (long long) s * NG;
-            SYNC();
-            for (int i = LANE; i < GFN; i += 64) { const int g = 2 * f + i; L.gflag[i] = (g < NG) ? (unsigned char) (bt_s[g] | (ms_s[g] << 2)) : 0; }
-            SYNC();
-        }
-        const int gfl = RFL((int) *reinterpret_cast<const unsigned short *>(&L.gflag[(2 * f) & (GFN - 1)]));
-        const int bt0 = gfl & 3, msb1 = (gfl >> 2) & 1, bt1 = (gfl >> 8) & 3, msb2 = (gfl >> 10) & 1;
-        if (LANE == 0) { L.fs.bytesout = 0; L.fs.pk_first = 0; }
-        // an MPEG-1 frame holds both granules of the 1152-sample block, an MPEG-2 frame one of them
-      for (int part = 0; part < (LSF ? 2 : 1); part++) {
-        const int pool_cap = LSF ? 255 : 511;       // what main_data_begin can address
-        const int P_vbr = RFL(p->vbr_flag), nchan = RFL(p->nchan);
-        const int dual = HX_A1 && RFL(p->dual);
-        int ba_min, ba_max, inc_min, inc_max, dba_max, TargetBits, bit_pool;
-        {
-            // ---- frame budget (reference mp3enc.cpp:2241-2257 / 2117-2128; MPEG-2 :2500-2516 / :2355-2363) ----
-            int pad = 0, byte_pool, byte_max, byte_min;
-            int padcount = RFL(L.fs.padcount);
-            const int P_rem = RFL(p->remainder), P_div = RFL(p->divisor), P_mfb = RFL(p->main_framebytes);
-            const int P_fbmin = RFL(p->fbmin), P_fbmax = RFL(p->fbmax), P_sfmax = RFL(p->sf_bit_max), P_avg = RFL(p->AveTargetBits);
-            byte_pool = (int) (RFL(L.fs.mf_tot) - RFL(L.fs.main_tot));
-            if (!P_vbr) {
-                padcount -= P_rem;
-                if (padcount <= 0) { padcount += P_div; pad = 1; }
-            }
-            if (!P_vbr) { byte_max = P_mfb + pad + byte_pool; byte_min = byte_max - pool_cap; }
-            else { byte_max = P_fbmax + byte_pool; byte_min = P_fbmin + byte_pool - pool_cap; }
-            if (LANE == 0) { L.fs.padcount = padcount; L.fs.pad = pad; L.fs.byte_pool = byte_pool; L.fs.byte_max = byte_max; L.fs.byte_min = byte_min; }
-
-            // ---- encode_jointB ----
-            // stereo: encode_jointB (mp3enc.cpp:1500-1527); mono: encode_singleB (:1686-1699)
-            // (first-generation allocator: encode_jointA :1236-1318, encode_singleA :1601-1672 and their MPEG-2 twins
-            // :1753-1829, :1910-1973 - dual channel allocates each channel on its own from half the frame)
-            const int nalloc = dual ? 1 : nchan;        // channels allocated together
-            TargetBits = nalloc * P_avg;
-            const int bsh = (LSF ? 3 : 2) - dual;       // a frame's budget covers one granule (MPEG-2) or two
-            bit_pool = byte_pool << bsh;
-            const int bit_max = byte_max << bsh;
-            const int bit_min = (byte_min << bsh) + ((LSF && nchan == 2 && !dual && byte_pool > 245) ? 40 : 0);
-            const int sf_bits = nalloc * P_sfmax;
-            const int ba_bit_max = ((nchan == 2 && !LSF && !HX_A1) ? bit_max : min(bit_max, 4095)) - sf_bits, ba_bit_min = bit_min - sf_bits;
-            dba_max = (nchan == 2 && !LSF && !HX_A1) ? bit_pool >> 2 : 0;
-            ba_min = ba_bit_min; ba_max = ba_bit_max + dba_max;
-            inc_min = ba_bit_min + sf_bits; inc_max = ba_bit_max + sf_bits;       // what the next granule (or channel) gets on top
-        }
-        const int shortblock_frame = (bt0 == 2) | (bt1 == 2);
-        // the frame's stereo decision was made by k_msscan (hysteresis over the stream's granules)
-        const int ms = (LSF && part) ? msb2 : msb1;
-        SYNC();
-        PROF_ACC(14);
-        int pos = 0;
-        for (int igr = LSF ? part : 0; igr < (LSF ? part + 1 : 2); igr++) {
-            const int g = 2 * f + igr, bt = igr ? bt1 : bt0;
-            {   // the granule's operands were requested a hand-over phase ago (see below): wait for them; the band
-                // start values move out of their landing area.  (The signs of a long granule's lines go from k_prep
-                // straight to k_pack; the short-block and first-generation allocators take them from the raw spectrum.)
-                HELPER_JOIN();
-                bin = band_fetch(BAND_LANDING);
-                SYNC();
-            }
-            PROF_ACC(0);
-            const int btp = bt_last;
-            bt_last = bt;
-            // long blocks: x^(3/4) and signs of the lines from k_prep (requested here, landed in LDS after the
-            // band-parallel start below)
-            bool fetch_posted = false;      // the helper wave's fetch order went out inside the allocator already
-#if HX_A1
-            (void) btp; (void) bin;
-            {
-                const float *th_g = COLD(thr) + ((long long) s * NG + g) * 128;
-                const float *esv = (g == 0) ? COLD(thrprev) + (long long) s * 128 : th_g - 128;
-                a1_sigmask(L, p, COLD(etab) + ((long long) s * NG + g) * 128, th_g, esv, g == 0);
-            }
-            if (LANE < 2) { L.gr[igr][LANE].block_type = 0; }
-            SYNC();
-            if (!dual) { A1Ctx cx = {0, 2, ms, RFL(p->is_flag)}; bitallo1(L, p, gp, cx, igr, ba_min, TargetBits, ba_max); }
-#else
-            if (bt == 2) {
-                const float *th_g = COLD(thr) + ((long long) s * NG + g) * 128;
-                const float *esv = (g == 0) ? COLD(thrprev) + (long long) s * 128 : th_g - 128;
-                compute_mask_short(L, p, th_g, esv, g == 0, btp);
-            }
-            if (LANE < 2) { L.gr[igr][LANE].block_type = bt; }
-            SYNC();
-            PROF_ACC(15);
-            if (bt != 2) fetch_posted = bitallo_long(L, p, igr, bt, ba_min, TargetBits, ba_max, bit_pool, ms, bin, g, (g + 1 < NG) ? g + 1 : -1);
-            else {      // CBitAllo3::BitAllo, block_type 2 branch (reference bitallo3.cpp:496-547)
-                const int P_imnr = RFL(p->initialMNR);
-                int MNR0;
-                if (P_vbr == 0) {
-                    MNR0 = L.MNR - (max(L.MNR - P_imnr, 0) >> 1) - (max(L.MNR - P_imnr - 400, 0) >> 2);
-                    MNR0 = max(P_imnr + 400, MNR0);
-                } else MNR0 = P_imnr + 400;
-                if (LSF) MNR0 = min(MNR0, 850);         // bitallos.cpp:214-217
-                SYNC();
-                if (LANE == 0) { L.call_count++; L.block_type = 2; }
-                SYNC();
-                bitallo_short(L, p, igr, ba_min, TargetBits, ba_max, bit_pool, ms, MNR0, L.sfs);
-            }
-#endif
-            PROF_ACC(12);
-            // xr is dead from here on (packing reads ix / signx): request the next granule's
-            // spectrum and mask operands now, their latency hides behind the packing
-            // the helper wave hands this granule's lines to k_pack and requests the next granule's operands; joined at
-            // the start of the next granule (or behind the frame loop)
-            if (!HX_A1 && !fetch_posted) {
-                if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
-                HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
-            }
-            PROF_ACC(16);
-            {   // The bits are written by k_pack; here the granule's segments are sized and handed over: a channel's
-                // first bit follows from the sizes before it, because the Huffman bits were counted (aux_bits).
-                Outbox &ob = L.ob[g & 1];
-                if (LANE == 0) ob.has_frame = 0;
-                if (!LSF && !HX_A1 && bt != 2) {
-                    const int bits = handover_long2(L, ob, pos, igr, !shortblock_frame, nchan);
-                    pos += bits;
-                    ba_min -= bits;
-                    ba_max -= bits;
-                    SYNC();
-                } else
-#pragma unroll 1
-                for (int ch = 0; ch < nchan; ch++) {
-#if HX_A1
-                    if (dual) { A1Ctx cx = {ch, 1, 0, 0}; bitallo1(L, p, gp, cx, igr, ba_min, TargetBits, ba_max); }
-#endif
-                    HxGr *gg = &L.gr[igr][ch];
-                    const int not_null = gg->aux_not_null;
-                    const int start = pos;
-                    int sc = 0, bits = 0;
-                    pos = pack_sf_any<LSF>(L, pos, igr, ch, bt, !shortblock_frame && !dual, not_null, &sc, ob.seg[ch].sf);
-                    if (not_null) { pos += gg->aux_bits; bits = pos - start; }
-                    else pos = start;
-                    PROF_ACC(19);
-                    seg_out(L, &ob.seg[ch], gg, start);
-                    SYNC();
-                    if (LANE == 0) { gg->scalefac_compress = sc; gg->part2_3_length = bits; }
-                    ba_min -= bits;
-                    ba_max -= bits;
-                    if (dual) { ba_min += inc_min; ba_max += inc_max; }
-                }
-                PROF_ACC(13);
-            }
-            if (HX_A1) {    // (its line arrays stay live until the last channel is allocated)
-                if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
-                HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
-            }
-            if (!dual) {
-                ba_min += inc_min;
-                ba_max = ba_max - dba_max;
-                ba_max += inc_max;
-            }
-            SYNC();
-        }
-
-        // ---- place the frame: header, side info, main data; reservoir bookkeeping ----
-        PROF_ACC(46);
-        {
-        // the frame's budget and the stream's carried scalars, from where the budget section left them
-        const int byte_pool = RFL(L.fs.byte_pool), byte_max = RFL(L.fs.byte_max), pad = RFL(L.fs.pad);
-        int byte_min = RFL(L.fs.byte_min);
-        unsigned side_p0 = (unsigned) RFL((int) L.fs.side_p0), side_p1 = (unsigned) RFL((int) L.fs.side_p1);
-        int main_bytes = RFL(L.fs.main_bytes), opos = RFL(L.fs.opos), slot_lo = RFL(L.fs.slot_lo), slot_hi = RFL(L.fs.slot_hi);
-        unsigned main_tot = (unsigned) RFL((int) L.fs.main_tot), main_sent = (unsigned) RFL((int) L.fs.main_sent), mf_tot = (unsigned) RFL((int) L.fs.mf_tot);
-        unsigned tot_frames_out = (unsigned) RFL((int) L.fs.tot_frames_out);
-        int bytesout = RFL(L.fs.bytesout);
-        const int pk_first = RFL(L.fs.pk_first);
-        const int P_oflags = RFL(p->oflags), P_mfb = RFL(p->main_framebytes), hdr = 4 + RFL(p->side_bytes);     // header + side info: 36 bytes, 21 for mono
-        const int P_ivmin = RFL(p->ivbr_min), P_ivmax = RFL(p->ivbr_max), P_fbmin = RFL(p->fbmin), P_vpt = RFL(p->vbr_pool_target);
-        // VBR: lane i holds the main-data capacity of bitrate index i (and of i + 1), so that the frame's index comes from
-        // two ballots instead of two scans of the table in LDS (a dependent read per step: 2.2 k cycles per frame)
-        const int fb_lane = p->vbr_main_framebytes[min(LANE, 15)], fbn_lane = p->vbr_main_framebytes[min(LANE + 1, 15)];
-        int ring_mf = L.r_mf[LANE & 31];    // the ring's slot sizes, one per lane: the retire loop below reads them without an LDS round trip each
-        int bytes = (pos + 7) >> 3;
-        if (bytes > byte_max) atomicOr(COLD(status), 2);    // the reference asserts here
-        int ibr = 0;
-        if (P_vbr) {
-            int bytes2 = bytes - byte_pool, bytes3 = bytes2 + P_vpt;
-            {   // first index in [ivmin, ivmax] whose capacity holds bytes2 (ivmax + 1: none)
-                const unsigned long long m = __ballot(LANE >= P_ivmin && LANE <= P_ivmax && bytes2 <= fb_lane);
-                ibr = m ? (int) __builtin_ctzll(m) : P_ivmax + 1;
-            }
-            // MPEG-2 frames can be so small that the pool spans many of them: past 10 pending frames stop
-            // filling it, past 15 drain it through byte_min padding (reference mp3enc.cpp:2387-2411)
-            const int side_dp = (int) ((side_p1 - side_p0) & 31);
-            if (!LSF || side_dp < 10) {
-                const unsigned long long m = __ballot(LANE >= ibr && LANE <= P_ivmax && bytes3 < fbn_lane);
-                ibr = m ? (int) __builtin_ctzll(m) : P_ivmax + 1;
-            } else if (side_dp > 15) {
-                byte_min = P_fbmin + ((side_dp > 24) ? byte_pool : (byte_pool >> 4));
-            }
-            if (ibr > P_ivmax) ibr = P_ivmax;
-        }
-        const int raw_bytes = bytes;
-        if (bytes < byte_min) bytes = byte_min;
-        const int mf = P_vbr ? __builtin_amdgcn_readlane(fb_lane, ibr) : P_mfb + pad;
-        long long packet_off = -1;
-        if (P_oflags & 1) packet_off = ((long long) s * F + f) * COLD(packet_stride) + ((LSF && part) ? pk_first : 0) + hdr;
-        PROF_ACC(47);
-        // the frame's slot, and where its main data goes (k_pack moves the bits): into the outbox of its last granule
-        Outbox &ob = L.ob[LSF ? part : 1];
-        if ((LANE & 31) == (int) side_p1) ring_mf = (unsigned short) mf;
-        if (LANE == 0) {
-            L.r_mf[side_p1] = (unsigned short) mf; L.r_off[side_p1] = opos;
-            ob.slot.off = opos; ob.slot.mf = mf; ob.slot_index = slot_hi;
-            ob.frm.bytes = bytes; ob.frm.raw_bytes = raw_bytes; ob.frm.first_slot = slot_lo; ob.frm.main_bytes = main_bytes; ob.frm.packet_off = packet_off;
-            ob.frm_index = LSF ? 2 * f + part : f;
-            ob.ring_p0 = (int) side_p0;
-            ob.opos = opos;
-            ob.has_frame = 1;
-        }
-        slot_hi++;
-        PROF_ACC(48);
-        {
-            if (LANE < 4) {     // header (reference mp3enc.cpp:2077-2103): pad bit / bitrate index, mode extension
-                unsigned char h = p->head[LANE];
-                if (LANE == 2) {
-                    if (!P_vbr) { if (pad) h |= 2; }
-                    else h = (unsigned char) ((h & 0x0F) | (ibr << 4));
-                }
-                if (LANE == 3) h = (unsigned char) ((h & 0xCF) | ((ms + ms + (HX_A1 ? p->is_flag : 0)) << 4));     // mode extension: M/S, intensity
-                ob.head[LANE] = h;
-            }
-            // the side information's fields as they stand now; main_data_begin = reservoir level at frame start
-            (&ob.gr[0][0].part2_3_length)[LANE] = (&L.gr[0][0].part2_3_length)[LANE];
-            if (LANE < 32) (&ob.gr[0][0].part2_3_length)[64 + LANE] = (&L.gr[0][0].part2_3_length)[64 + LANE];
-            if (LANE == 0) { ob.scfsi[0] = L.scfsi[0]; ob.scfsi[1] = L.scfsi[1]; ob.mdb = byte_pool; ob.part = part; }
-        }
-        PROF_ACC(49);
-        if (P_oflags & 1) {     // nbytes_out[2] per call; the MPEG-2 call's two packets sit back to back (mp3enc.cpp:3352-3363)
-            int *nb = COLD(packet_bytes) + ((long long) s * F + f) * 2;
-            unsigned char *q = COLD(packet) + ((long long) s * F + f) * COLD(packet_stride);
-            if (LSF && part) q += pk_first;
-            emit_packet(L, p, q, nb + part, pad, ms, raw_bytes, hdr, LSF ? part : -1);
-            if (LANE == 0) L.fs.pk_first = hdr + raw_bytes;
-            if (!LSF && LANE == 0) nb[1] = 0;
-        }
-        if (LANE == 0 && (P_oflags & 2) && (!LSF || part)) {
-            HxFrameDebug *d = COLD(dbg) + (long long) s * F + f;
-            d->ms = ms; d->ms_metric[0] = LSF ? 0 : COLD(msdec)[(long long) s * NG + 2 * f]; d->ms_metric[1] = COLD(msdec)[(long long) s * NG + 2 * f + 1];
-            d->byte_pool = byte_pool; d->MNR_after = L.MNR;
-            for (int g2 = 0; g2 < 2; g2++) for (int c = 0; c < 2; c++) {
-                d->gr[g2][c] = L.gr[g2][c];
-                for (int b = 0; b < 22; b++) d->sf[g2][c][b] = L.sfout[g2][c][b];
-            }
-            d->scfsi[0] = L.scfsi[0]; d->scfsi[1] = L.scfsi[1];
-            d->main_bytes = raw_bytes;
-        }
-        opos += hdr + mf;
-        side_p1 = (side_p1 + 1) & 31;
-        SYNC();
-        PROF_ACC(17);
-        main_tot += bytes;
-        main_bytes += bytes;
-        mf_tot += mf;
-        // retire the slots that are now full (reference mp3enc.cpp:2293-2313)
-        while (side_p0 != side_p1) {
-            const int cap = __builtin_amdgcn_readlane(ring_mf, (int) side_p0);
-            if (main_bytes < cap) break;
-            tot_frames_out++;
-            main_sent += cap;
-            bytesout += hdr + cap;
-            main_bytes -= cap;
-            side_p0 = (side_p0 + 1) & 31;
-            slot_lo++;
-        }
-        if (LANE == 0) {
-            FrameState &fs = L.fs;
-            fs.side_p0 = side_p0; fs.side_p1 = side_p1; fs.main_bytes = main_bytes; fs.opos = opos; fs.slot_lo = slot_lo; fs.slot_hi = slot_hi;
-            fs.main_tot = main_tot; fs.main_sent = main_sent; fs.mf_tot = mf_tot; fs.tot_frames_out = tot_frames_out; fs.bytesout = bytesout;
-        }
-        if (!LSF || part) {     // the call's last frame: running totals (reference mp3enc.cpp:2316-2325)
-            const unsigned tot_bytes_out = (unsigned) RFL((int) L.fs.tot_bytes_out) + (unsigned) bytesout;
-            const int ave0 = RFL(L.fs.ave_tot), ave_tot = ave0 + ((((bytesout << 8) - ave0)) >> (LSF ? 6 : 7));
-            if (LANE == 0) { L.fs.tot_bytes_out = tot_bytes_out; L.fs.ave_tot = ave_tot; }
-            if ((P_oflags & 4) && LANE < 2) COLD(frame_stats)[((long long) s * F + f) * 2 + LANE] = (int) (LANE ? tot_bytes_out : tot_frames_out);
-        }
-        }
-        SYNC();
-      }
-        PROF_ACC(18);
+// A frame's budget (reference mp3enc.cpp:2241-2257 / 2117-2128; MPEG-2 :2500-2516 / :2355-2363): the reservoir's side goes to
+// L.fs for the frame's placement, the allocator's bounds come back.  ba_min / ba_max: the bits the next granule (or channel) may
+// take; inc_min / inc_max: what each later one gets on top.
+struct FrameBudget { int ba_min, ba_max, inc_min, inc_max, dba_max, TargetBits, bit_pool; };
+template <int LSF>
+__device__ __forceinline__ FrameBudget frame_budget(AllocLds &L, int P_vbr, int nchan, int dual)
+{
+    HX_LANE_DECL;
+    const AllocPrm *p = &L.P;
+    const int pool_cap = LSF ? 255 : 511;       // what main_data_begin can address
+    int ba_min, ba_max, inc_min, inc_max, dba_max, TargetBits, bit_pool;
+    int pad = 0, byte_pool, byte_max, byte_min;
+    int padcount = RFL(L.fs.padcount);
+    const int P_rem = RFL(p->remainder), P_div = RFL(p->divisor), P_mfb = RFL(p->main_framebytes);
+    const int P_fbmin = RFL(p->fbmin), P_fbmax = RFL(p->fbmax), P_sfmax = RFL(p->sf_bit_max), P_avg = RFL(p->AveTargetBits);
+    byte_pool = (int) (RFL(L.fs.mf_tot) - RFL(L.fs.main_tot));
+    if (!P_vbr) {
+        padcount -= P_rem;
+        if (padcount <= 0) { padcount += P_div; pad = 1; }
     }
-#undef RFL
+    if (!P_vbr) { byte_max = P_mfb + pad + byte_pool; byte_min = byte_max - pool_cap; }
+    else { byte_max = P_fbmax + byte_pool; byte_min = P_fbmin + byte_pool - pool_cap; }
+    if (LANE == 0) { L.fs.padcount = padcount; L.fs.pad = pad; L.fs.byte_pool = byte_pool; L.fs.byte_max = byte_max; L.fs.byte_min = byte_min; }
 
+    // ---- encode_jointB ----
+    // stereo: encode_jointB (mp3enc.cpp:1500-1527); mono: encode_singleB (:1686-1699)
+    // (first-generation allocator: encode_jointA :1236-1318, encode_singleA :1601-1672 and their MPEG-2 twins
+    // :1753-1829, :1910-1973 - dual channel allocates each channel on its own from half the frame)
+    const int nalloc = dual ? 1 : nchan;        // channels allocated together
+    TargetBits = nalloc * P_avg;
+    const int bsh = (LSF ? 3 : 2) - dual;       // a frame's budget covers one granule (MPEG-2) or two
+    bit_pool = byte_pool << bsh;
+    const int bit_max = byte_max << bsh;
+    const int bit_min = (byte_min << bsh) + ((LSF && nchan == 2 && !dual && byte_pool > 245) ? 40 : 0);
+    const int sf_bits = nalloc * P_sfmax;
+    const int ba_bit_max = ((nchan == 2 && !LSF && !HX_A1) ? bit_max : min(bit_max, 4095)) - sf_bits, ba_bit_min = bit_min - sf_bits;
+    dba_max = (nchan == 2 && !LSF && !HX_A1) ? bit_pool >> 2 : 0;
+    ba_min = ba_bit_min; ba_max = ba_bit_max + dba_max;
+    inc_min = ba_bit_min + sf_bits; inc_max = ba_bit_max + sf_bits;       // what the next granule (or channel) gets on top
+    return FrameBudget{ba_min, ba_max, inc_min, inc_max, dba_max, TargetBits, bit_pool};
+}
+
+// One granule: its operands joined, its allocation, the next granule's fetch order, its segments sized and handed over (the
+// outbox of g & 1).  pos: the frame's main-data bits so far; b: what is left of the frame's budget.
+template <int LSF>
+__device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, const HxParams *gp, int s, int g, int igr, int bt, int btp,
+                                              int ms, int shortblock_frame, int nchan, int dual, int P_vbr, FrameBudget &b, int &pos PROF_CLOCK)
+{
+    HX_LANE_DECL;
+    const AllocPrm *p = &L.P;
+    const int NG = a.NG;
+    BandIn bin;
+    {   // the granule's operands were requested a hand-over phase ago (see below): wait for them; the band
+        // start values move out of their landing area.  (The signs of a long granule's lines go from k_prep
+        // straight to k_pack; the short-block and first-generation allocators take them from the raw spectrum.)
+        HELPER_JOIN();
+        bin = band_fetch(BAND_LANDING);
+        SYNC();
+    }
+    PROF_ACC(HX_PROF_JOIN_FETCH);
+    // long blocks: x^(3/4) and signs of the lines from k_prep (requested here, landed in LDS after the
+    // band-parallel start below)
+    bool fetch_posted = false;      // the helper wave's fetch order went out inside the allocator already
+#if HX_A1
+    (void) btp; (void) bin;
+    {
+        const float *th_g = COLD(thr) + ((long long) s * NG + g) * 128;
+        const float *esv = (g == 0) ? COLD(thrprev) + (long long) s * 128 : th_g - 128;
+        a1_sigmask(L, p, COLD(etab) + ((long long) s * NG + g) * 128, th_g, esv, g == 0);
+    }
+    if (LANE < 2) { L.gr[igr][LANE].block_type = 0; }
+    SYNC();
+    if (!dual) { A1Ctx cx = {0, 2, ms, RFL(p->is_flag)}; bitallo1(L, p, gp, cx, igr, b.ba_min, b.TargetBits, b.ba_max); }
+#else
+    if (bt == 2) {
+        const float *th_g = COLD(thr) + ((long long) s * NG + g) * 128;
+        const float *esv = (g == 0) ? COLD(thrprev) + (long long) s * 128 : th_g - 128;
+        compute_mask_short(L, p, th_g, esv, g == 0, btp);
+    }
+    if (LANE < 2) { L.gr[igr][LANE].block_type = bt; }
+    SYNC();
+    PROF_ACC(HX_PROF_GR_PRE);
+    if (bt != 2) fetch_posted = bitallo_long(L, p, igr, bt, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, bin, g, (g + 1 < NG) ? g + 1 : -1);
+    else {      // CBitAllo3::BitAllo, block_type 2 branch (reference bitallo3.cpp:496-547)
+        const int P_imnr = RFL(p->initialMNR);
+        int MNR0;
+        if (P_vbr == 0) {
+            MNR0 = L.MNR - (max(L.MNR - P_imnr, 0) >> 1) - (max(L.MNR - P_imnr - 400, 0) >> 2);
+            MNR0 = max(P_imnr + 400, MNR0);
+        } else MNR0 = P_imnr + 400;
+        if (LSF) MNR0 = min(MNR0, 850);         // bitallos.cpp:214-217
+        SYNC();
+        if (LANE == 0) { L.call_count++; L.block_type = 2; }
+        SYNC();
+        bitallo_short(L, p, igr, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, MNR0, L.sfs);
+    }
+#endif
+    PROF_ACC(HX_PROF_BITALLO);
+    // xr is dead from here on (packing reads ix / signx): request the next granule's
+    // spectrum and mask operands now, their latency hides behind the packing
+    // the helper wave hands this granule's lines to k_pack and requests the next granule's operands; joined at
+    // the start of the next granule (or behind the frame loop)
+    if (!HX_A1 && !fetch_posted) {
+        if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
+        HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
+    }
+    PROF_ACC(HX_PROF_FETCH_POST);
+    {   // The bits are written by k_pack; here the granule's segments are sized and handed over: a channel's
+        // first bit follows from the sizes before it, because the Huffman bits were counted (aux_bits).
+        Outbox &ob = L.ob[g & 1];
+        if (LANE == 0) ob.has_frame = 0;
+        if (!LSF && !HX_A1 && bt != 2) {
+            const int bits = handover_long2(L, ob, pos, igr, !shortblock_frame, nchan);
+            pos += bits;
+            b.ba_min -= bits;
+            b.ba_max -= bits;
+            SYNC();
+        } else
+#pragma unroll 1
+        for (int ch = 0; ch < nchan; ch++) {
+#if HX_A1
+            if (dual) { A1Ctx cx = {ch, 1, 0, 0}; bitallo1(L, p, gp, cx, igr, b.ba_min, b.TargetBits, b.ba_max); }
+#endif
+            HxGr *gg = &L.gr[igr][ch];
+            const int not_null = gg->aux_not_null;
+            const int start = pos;
+            int sc = 0, bits = 0;
+            pos = pack_sf_any<LSF>(L, pos, igr, ch, bt, !shortblock_frame && !dual, not_null, &sc, ob.seg[ch].sf);
+            if (not_null) { pos += gg->aux_bits; bits = pos - start; }
+            else pos = start;
+            PROF_ACC(HX_PROF_PACK_SF);
+            seg_out(L, &ob.seg[ch], gg, start);
+            SYNC();
+            if (LANE == 0) { gg->scalefac_compress = sc; gg->part2_3_length = bits; }
+            b.ba_min -= bits;
+            b.ba_max -= bits;
+            if (dual) { b.ba_min += b.inc_min; b.ba_max += b.inc_max; }
+        }
+        PROF_ACC(HX_PROF_HANDOVER);
+    }
+    if (HX_A1) {    // (its line arrays stay live until the last channel is allocated)
+        if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
+        HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
+    }
+    if (!dual) {
+        b.ba_min += b.inc_min;
+        b.ba_max = b.ba_max - b.dba_max;
+        b.ba_max += b.inc_max;
+    }
+    SYNC();
+}
+
+// A coded frame placed: header, side information, main data (into the outbox of its last granule, for the helper wave and
+// k_pack); reservoir bookkeeping.
+template <int LSF>
+__device__ __forceinline__ void place_frame(const AllocArgs &a, AllocLds &L, int s, int f, int part, int ms, int pos, int P_vbr PROF_CLOCK)
+{
+    HX_LANE_DECL;
+    const AllocPrm *p = &L.P;
+    const int NG = a.NG, F = NG / 2;
+    // the frame's budget and the stream's carried scalars, from where the budget section left them
+    const int byte_pool = RFL(L.fs.byte_pool), byte_max = RFL(L.fs.byte_max), pad = RFL(L.fs.pad);
+    int byte_min = RFL(L.fs.byte_min);
+    unsigned side_p0 = (unsigned) RFL((int) L.fs.side_p0), side_p1 = (unsigned) RFL((int) L.fs.side_p1);
+    int main_bytes = RFL(L.fs.main_bytes), opos = RFL(L.fs.opos), slot_lo = RFL(L.fs.slot_lo), slot_hi = RFL(L.fs.slot_hi);
+    unsigned main_tot = (unsigned) RFL((int) L.fs.main_tot), main_sent = (unsigned) RFL((int) L.fs.main_sent), mf_tot = (unsigned) RFL((int) L.fs.mf_tot);
+    unsigned tot_frames_out = (unsigned) RFL((int) L.fs.tot_frames_out);
+    int bytesout = RFL(L.fs.bytesout);
+    const int pk_first = RFL(L.fs.pk_first);
+    const int P_oflags = RFL(p->oflags), P_mfb = RFL(p->main_framebytes), hdr = 4 + RFL(p->side_bytes);     // header + side info: 36 bytes, 21 for mono
+    const int P_ivmin = RFL(p->ivbr_min), P_ivmax = RFL(p->ivbr_max), P_fbmin = RFL(p->fbmin), P_vpt = RFL(p->vbr_pool_target);
+    // VBR: lane i holds the main-data capacity of bitrate index i (and of i + 1), so that the frame's index comes from
+    // two ballots instead of two scans of the table in LDS (a dependent read per step: 2.2 k cycles per frame)
+    const int fb_lane = p->vbr_main_framebytes[min(LANE, 15)], fbn_lane = p->vbr_main_framebytes[min(LANE + 1, 15)];
+    int ring_mf = L.r_mf[LANE & 31];    // the ring's slot sizes, one per lane: the retire loop below reads them without an LDS round trip each
+    int bytes = (pos + 7) >> 3;
+    if (bytes > byte_max) atomicOr(COLD(status), 2);    // the reference asserts here
+    int ibr = 0;
+    if (P_vbr) {
+        int bytes2 = bytes - byte_pool, bytes3 = bytes2 + P_vpt;
+        {   // first index in [ivmin, ivmax] whose capacity holds bytes2 (ivmax + 1: none)
+            const unsigned long long m = __ballot(LANE >= P_ivmin && LANE <= P_ivmax && bytes2 <= fb_lane);
+            ibr = m ? (int) __builtin_ctzll(m) : P_ivmax + 1;
+        }
+        // MPEG-2 frames can be so small that the pool spans many of them: past 10 pending frames stop
+        // filling it, past 15 drain it through byte_min padding (reference mp3enc.cpp:2387-2411)
+        const int side_dp = (int) ((side_p1 - side_p0) & 31);
+        if (!LSF || side_dp < 10) {
+            const unsigned long long m = __ballot(LANE >= ibr && LANE <= P_ivmax && bytes3 < fbn_lane);
+            ibr = m ? (int) __builtin_ctzll(m) : P_ivmax + 1;
+        } else if (side_dp > 15) {
+            byte_min = P_fbmin + ((side_dp > 24) ? byte_pool : (byte_pool >> 4));
+        }
+        if (ibr > P_ivmax) ibr = P_ivmax;
+    }
+    const int raw_bytes = bytes;
+    if (bytes < byte_min) bytes = byte_min;
+    const int mf = P_vbr ? __builtin_amdgcn_readlane(fb_lane, ibr) : P_mfb + pad;
+    long long packet_off = -1;
+    if (P_oflags & 1) packet_off = ((long long) s * F + f) * COLD(packet_stride) + ((LSF && part) ? pk_first : 0) + hdr;
+    PROF_ACC(HX_PROF_PL_SIZES);
+    // the frame's slot, and where its main data goes (k_pack moves the bits): into the outbox of its last granule
+    Outbox &ob = L.ob[LSF ? part : 1];
+    if ((LANE & 31) == (int) side_p1) ring_mf = (unsigned short) mf;
+    if (LANE == 0) {
+        L.r_mf[side_p1] = (unsigned short) mf; L.r_off[side_p1] = opos;
+        ob.slot.off = opos; ob.slot.mf = mf; ob.slot_index = slot_hi;
+        ob.frm.bytes = bytes; ob.frm.raw_bytes = raw_bytes; ob.frm.first_slot = slot_lo; ob.frm.main_bytes = main_bytes; ob.frm.packet_off = packet_off;
+        ob.frm_index = LSF ? 2 * f + part : f;
+        ob.ring_p0 = (int) side_p0;
+        ob.opos = opos;
+        ob.has_frame = 1;
+    }
+    slot_hi++;
+    PROF_ACC(HX_PROF_PL_SLOT);
+    {
+        if (LANE < 4) {     // header (reference mp3enc.cpp:2077-2103): pad bit / bitrate index, mode extension
+            unsigned char h = p->head[LANE];
+            if (LANE == 2) {
+                if (!P_vbr) { if (pad) h |= 2; }
+                else h = (unsigned char) ((h & 0x0F) | (ibr << 4));
+            }
+            if (LANE == 3) h = (unsigned char) ((h & 0xCF) | ((ms + ms + (HX_A1 ? p->is_flag : 0)) << 4));     // mode extension: M/S, intensity
+            ob.head[LANE] = h;
+        }
+        // the side information's fields as they stand now; main_data_begin = reservoir level at frame start
+        (&ob.gr[0][0].part2_3_length)[LANE] = (&L.gr[0][0].part2_3_length)[LANE];
+        if (LANE < 32) (&ob.gr[0][0].part2_3_length)[64 + LANE] = (&L.gr[0][0].part2_3_length)[64 + LANE];
+        if (LANE == 0) { ob.scfsi[0] = L.scfsi[0]; ob.scfsi[1] = L.scfsi[1]; ob.mdb = byte_pool; ob.part = part; }
+    }
+    PROF_ACC(HX_PROF_PL_HEAD);
+    if (P_oflags & 1) {     // nbytes_out[2] per call; the MPEG-2 call's two packets sit back to back (mp3enc.cpp:3352-3363)
+        int *nb = COLD(packet_bytes) + ((long long) s * F + f) * 2;
+        unsigned char *q = COLD(packet) + ((long long) s * F + f) * COLD(packet_stride);
+        if (LSF && part) q += pk_first;
+        emit_packet(L, p, q, nb + part, pad, ms, raw_bytes, hdr, LSF ? part : -1);
+        if (LANE == 0) L.fs.pk_first = hdr + raw_bytes;
+        if (!LSF && LANE == 0) nb[1] = 0;
+    }
+    if (LANE == 0 && (P_oflags & 2) && (!LSF || part)) {
+        HxFrameDebug *d = COLD(dbg) + (long long) s * F + f;
+        d->ms = ms; d->ms_metric[0] = LSF ? 0 : COLD(msdec)[(long long) s * NG + 2 * f]; d->ms_metric[1] = COLD(msdec)[(long long) s * NG + 2 * f + 1];
+        d->byte_pool = byte_pool; d->MNR_after = L.MNR;
+        for (int g2 = 0; g2 < 2; g2++) for (int c = 0; c < 2; c++) {
+            d->gr[g2][c] = L.gr[g2][c];
+            for (int b = 0; b < 22; b++) d->sf[g2][c][b] = L.sfout[g2][c][b];
+        }
+        d->scfsi[0] = L.scfsi[0]; d->scfsi[1] = L.scfsi[1];
+        d->main_bytes = raw_bytes;
+    }
+    opos += hdr + mf;
+    side_p1 = (side_p1 + 1) & 31;
+    SYNC();
+    PROF_ACC(HX_PROF_EMIT);
+    main_tot += bytes;
+    main_bytes += bytes;
+    mf_tot += mf;
+    // retire the slots that are now full (reference mp3enc.cpp:2293-2313)
+    while (side_p0 != side_p1) {
+        const int cap = __builtin_amdgcn_readlane(ring_mf, (int) side_p0);
+        if (main_bytes < cap) break;
+        tot_frames_out++;
+        main_sent += cap;
+        bytesout += hdr + cap;
+        main_bytes -= cap;
+        side_p0 = (side_p0 + 1) & 31;
+        slot_lo++;
+    }
+    if (LANE == 0) {
+        FrameState &fs = L.fs;
+        fs.side_p0 = side_p0; fs.side_p1 = side_p1; fs.main_bytes = main_bytes; fs.opos = opos; fs.slot_lo = slot_lo; fs.slot_hi = slot_hi;
+        fs.main_tot = main_tot; fs.main_sent = main_sent; fs.mf_tot = mf_tot; fs.tot_frames_out = tot_frames_out; fs.bytesout = bytesout;
+    }
+    if (!LSF || part) {     // the call's last frame: running totals (reference mp3enc.cpp:2316-2325)
+        const unsigned tot_bytes_out = (unsigned) RFL((int) L.fs.tot_bytes_out) + (unsigned) bytesout;
+        const int ave0 = RFL(L.fs.ave_tot), ave_tot = ave0 + ((((bytesout << 8) - ave0)) >> (LSF ? 6 : 7));
+        if (LANE == 0) { L.fs.tot_bytes_out = tot_bytes_out; L.fs.ave_tot = ave_tot; }
+        if ((P_oflags & 4) && LANE < 2) COLD(frame_stats)[((long long) s * F + f) * 2 + LANE] = (int) (LANE ? tot_bytes_out : tot_frames_out);
+    }
+    SYNC();
+}
+
+// The end of the stream's call: the last granule's lines and outbox out, the frames that are not complete yet and the carried
+// state into the stream record, the counters.
+__device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L, int s, int idx, HxStream *ss, long long t_start)
+{
+    HX_LANE_DECL;
     HELPER_JOIN();          // the last granule's lines are out
     if (LANE == 0) L.cmdw[2] = -1;
     HELPER_POST(HCMD_FETCH, -1);        // its outbox
@@ -823,11 +772,10 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
     SYNC_G();
     // (their images - with the main data k_pack writes - are copied into ss->main_buf by k_pack_carry)
     if (LANE < 32) ss->frame_mf_bytes[LANE] = L.r_mf[LANE];
-
 #ifdef HX_PROFILE
-    if (LANE == 0) L.prof[31] = (unsigned) (clock64() - tk0_);
+    if (LANE == 0) L.prof[HX_PROF_TOTAL] = (unsigned) clock64() - L.prof[HX_PROF_TOTAL];
     SYNC();
-    if (COLD(prof)) COLD(prof)[(long long) s * 64 + LANE] = L.prof[LANE];
+    if (COLD(prof)) COLD(prof)[(long long) s * HX_PROF_WORDS + LANE] = L.prof[LANE];
 #endif
     // ---- write the stream state back ----
     if (LANE < 44) ss->NTadjust[LANE / 22][LANE % 22] = L.NTadjust[LANE / 22][LANE % 22];
@@ -858,6 +806,129 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         // this position's CU is no longer reserved (see "parking" above)
         if (idx < (COLD(park_k) & 0xFFFF)) __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+}
+
+// Out of work: a workgroup that shares its CU with one of the launch's longest streams keeps the slot until that one retires
+// (see "parking" in alloc_stream); the last workgroup out resets the claim counter; the helper wave stops.
+__device__ __forceinline__ void walk_exit(AllocLds &L)
+{
+    HX_LANE_DECL;
+    const int pk = COLD(park_k) & 0xFFFF;
+    if (pk > 0 && LANE == 0) {
+        unsigned *resv = (unsigned *) COLD(done_counter) + HX_CNT_PARK;
+        const unsigned me = ((((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu)) & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u;
+        for (int k = 0; k < pk; k++) {
+            if (__hip_atomic_load(resv + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != me) continue;
+            // (bounded: 40 ms of wall clock - nothing depends on the wait, it only keeps the slot occupied)
+            const long long t_park = wall_clock64();
+            while (__hip_atomic_load(resv + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == me && wall_clock64() - t_park < 4000000LL)
+                __builtin_amdgcn_s_sleep(127);
+        }
+    }
+    // the last workgroup out leaves the claim counter at zero for the next launch (launches of a batch follow each other
+    // on one HIP stream; a recorded graph replays the launch with the same arguments, so nothing here may depend on the host)
+    if (HX_PERSIST && LANE == 0 && atomicAdd(COLD(done_counter) + HX_CNT_IDLE, 1) == (int) gridDim.x - 1) {
+        __hip_atomic_store(COLD(done_counter) + HX_CNT_CLAIMED, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(COLD(done_counter) + HX_CNT_IDLE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    HELPER_POST(HCMD_EXIT, 0);
+}
+
+// LSF = 1: MPEG-2 low-sampling-frequency streams.  Every granule is a frame of its own (reference
+// mp3enc.cpp:2483-2593 CBR, :2337-2479 VBR; encode_jointB_MPEG2 :1832-1907, encode_singleB_MPEG2
+// :1977-2027): budgets in bits = bytes << 3, reservoir capped at 255 bytes, no scfsi.
+template <int LSF>
+__device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
+{
+    HX_LANE_DECL;
+    // Persistent workgroups: the launch has as many workgroups as the chip holds at once (or one per stream if that is
+    // fewer); each claims the next stream of the launch order from a counter when it is done with one.  (Round 6: with one
+    // workgroup per stream and more streams than slots, the hardware dispatcher deals workgroup i to XCD i mod 8 in strict
+    // order, so a freed slot of another XCD waits for its turn, and every stream's end hands LDS and registers back and takes
+    // them again: config 3 48.6 -> 48.0 ms per step, four full rounds 52.9 -> 51.5 ms.  Most of what a multi-round launch
+    // idles - 14 % of its slot-time - is the last round's drain, which no claiming order removes: a stream's call is one job.)
+    // The launch order is the streams that ran longest in the previous call first (longest-processing-time-first: the
+    // launch's tail is made of short streams).
+    // (HX_PERSIST: the low-footprint build only, see the top of hx_alloc.hip)
+    if (!HX_PERSIST && (int) blockIdx.x >= a.S) return;
+    if (WAVE == 1) { helper_serve<LSF>(a, L); return; }
+#if HX_PERSIST
+  for (;;) {        // master wave: one stream of the launch order after the other
+    HX_LANE_DECL;
+    int idx = 0;
+    if (LANE == 0) idx = atomicAdd(COLD(done_counter) + HX_CNT_CLAIMED, 1);
+    idx = __builtin_amdgcn_readfirstlane(idx);
+    if (idx >= a.S) break;
+#else
+  {                 // master wave: the stream at this workgroup's position of the launch order
+    const int idx = (int) blockIdx.x;
+#endif
+    const int s = COLD(order) ? COLD(order)[idx] : idx;
+    const long long t_start = wall_clock64();
+    if (LANE == 0) {
+        L.cur_s = s;
+        atomicAdd(COLD(done_counter) + HX_CNT_STARTED, 1);        // this stream is being walked (the gates of the next call's front end count these)
+        // where it runs (tests, placement experiments): XCC id << 16 | HW_ID[15:0], per position in the launch order
+        const unsigned where = ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu);
+        COLD(dur)[a.S + idx] = where;
+        // Parking (resident-set batches): a launch lasts as long as its slowest stream, and the front end of the next call and
+        // the packing of the previous one move into every CU slot a retiring stream frees - also next to that slowest stream,
+        // whose LDS round trips they then lengthen (measured: K6 15.0 ms alone, 16.0 ms with them beside it).  The first
+        // park_k positions of the launch order (the longest streams of the previous call) publish which CU they run on; a
+        // workgroup that runs out of work on one of those CUs keeps its slot - asleep - until that stream has retired too, so
+        // nothing else fits there (a CU holds four of these workgroups: 153 of 160 KB of LDS, all vector registers).
+        // (park_k bit 16: the CU that shares the instruction and scalar caches with it - CU id with the low bit flipped - as well)
+        if (idx < (COLD(park_k) & 0xFFFF))
+            __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, (where & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    HxStream *ss = a.st + s;
+    const HxParams *gp = a.prm + ss->cls;
+    const AllocPrm *p = &L.P;
+    const int NG = a.NG, F = NG / 2;
+    stage_stream(a, L, ss, gp, a.gt);
+    slots_init<LSF>(a, L, s, ss, gp);
+
+    int bt_last = a.btprev[s];
+    if (LANE == 0) { L.cmdw[2] = -1; L.cmdw[3] = 0; }
+    HELPER_POST(HCMD_FETCH, 0);         // the first granule's operands
+    for (int f = 0; f < F; f++) {
+        HX_LANE_DECL;           // (per frame: see hx_lane_opaque)
+        PROF_T0();
+        constexpr int GFN = (int) sizeof(L.gflag);       // granules staged at a time
+        // The per-granule block types and stereo decisions are staged in LDS GFN / 2 frames at a time: fetched from global
+        // memory one frame ahead, the compiler unpacked (= waited for) them at once and spilled them over the frame (2 k cycles).
+        if ((f & (GFN / 2 - 1)) == 0) {
+            const unsigned char *bt_s = COLD(bt) + (long long) s * NG;
+            const unsigned char *ms_s = COLD(msflag) + (long long) s * NG;
+            SYNC();
+            for (int i = LANE; i < GFN; i += 64) { const int g = 2 * f + i; L.gflag[i] = (g < NG) ? (unsigned char) (bt_s[g] | (ms_s[g] << 2)) : 0; }
+            SYNC();
+        }
+        const int gfl = RFL((int) *reinterpret_cast<const unsigned short *>(&L.gflag[(2 * f) & (GFN - 1)]));
+        const int bt0 = gfl & 3, msb1 = (gfl >> 2) & 1, bt1 = (gfl >> 8) & 3, msb2 = (gfl >> 10) & 1;
+        if (LANE == 0) { L.fs.bytesout = 0; L.fs.pk_first = 0; }
+        // an MPEG-1 frame holds both granules of the 1152-sample block, an MPEG-2 frame one of them
+      for (int part = 0; part < (LSF ? 2 : 1); part++) {
+        const int P_vbr = RFL(p->vbr_flag), nchan = RFL(p->nchan);
+        const int dual = HX_A1 && RFL(p->dual);
+        FrameBudget b = frame_budget<LSF>(L, P_vbr, nchan, dual);
+        const int shortblock_frame = (bt0 == 2) | (bt1 == 2);
+        // the frame's stereo decision was made by k_msscan (hysteresis over the stream's granules)
+        const int ms = (LSF && part) ? msb2 : msb1;
+        SYNC();
+        PROF_ACC(HX_PROF_BUDGET);
+        int pos = 0;
+        for (int igr = LSF ? part : 0; igr < (LSF ? part + 1 : 2); igr++) {
+            const int bt = igr ? bt1 : bt0;
+            granule_alloc<LSF>(a, L, gp, s, 2 * f + igr, igr, bt, bt_last, ms, shortblock_frame, nchan, dual, P_vbr, b, pos PROF_PASS);
+            bt_last = bt;
+        }
+        PROF_ACC(HX_PROF_GR_TAIL);
+        place_frame<LSF>(a, L, s, f, part, ms, pos, P_vbr PROF_PASS);
+      }
+        PROF_ACC(HX_PROF_RETIRE);
+    }
+    stream_writeback(a, L, s, idx, ss, t_start);
 #if HX_PERSIST
     // the helper wave is through with this stream (its last stores read the outbox and the stream constants in LDS) before
     // the next stream's tables land there
@@ -865,43 +936,17 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
     HELPER_JOIN();
 #endif
   }
-    // out of work: a workgroup that shares its CU with one of the launch's longest streams keeps the slot until that one retires
-    {
-        HX_LANE_DECL;
-        const int pk = COLD(park_k) & 0xFFFF;
-        if (pk > 0 && LANE == 0) {
-            unsigned *resv = (unsigned *) COLD(done_counter) + HX_CNT_PARK;
-            const unsigned me = ((((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 20) << 16) | ((unsigned) __builtin_amdgcn_s_getreg((31 << 11) | 4) & 0xFFFFu)) & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u;
-            for (int k = 0; k < pk; k++) {
-                if (__hip_atomic_load(resv + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != me) continue;
-                // (bounded: 40 ms of wall clock - nothing depends on the wait, it only keeps the slot occupied)
-                const long long t_park = wall_clock64();
-                while (__hip_atomic_load(resv + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == me && wall_clock64() - t_park < 4000000LL)
-                    __builtin_amdgcn_s_sleep(127);
-            }
-        }
-        // the last workgroup out leaves the claim counter at zero for the next launch (launches of a batch follow each other
-        // on one HIP stream; a recorded graph replays the launch with the same arguments, so nothing here may depend on the host)
-        if (HX_PERSIST && LANE == 0 && atomicAdd(COLD(done_counter) + HX_CNT_IDLE, 1) == (int) gridDim.x - 1) {
-            __hip_atomic_store(COLD(done_counter) + HX_CNT_CLAIMED, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(COLD(done_counter) + HX_CNT_IDLE, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        HELPER_POST(HCMD_EXIT, 0);
-    }
+    walk_exit(L);
 }
 
 // The two instantiations live in separate translation units (hx_alloc.hip, hx_alloc_lsf.hip): with a
 // single caller the allocator's device functions are inlined into the kernel; sharing them between
 // two kernels of one module turns them into real calls (measured: +2 ms on the MPEG-1 kernel).
-#ifndef HX_WAVES
-#define HX_WAVES 2          // waves per SIMD the register allocation aims at (2: 256 VGPRs, 3: 168, 4: 128)
-#endif
 // The stream walk's waves issue ahead of the front-end and packing waves that share a SIMD with them in the launch's tail
 // (measured: +0.6 % config 2, +0.8 % config 3).
 #define HX_K6_PRIO __builtin_amdgcn_s_setprio(3)
 #define HX_K6(name, lsf) \
-    __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void name(AllocArgs a) { HX_K6_PRIO; __shared__ AllocLds L; alloc_stream<lsf>(a, L); } \
-    extern "C" int name##_persistent() { return HX_PERSIST; }
+    __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void name(AllocArgs a) { HX_K6_PRIO; __shared__ AllocLds L; alloc_stream<lsf>(a, L); }
 #if HX_A1 && !HX_LSF
 // streams of the first-generation allocator (intensity stereo, dual channel), MPEG-1 rates
 HX_K6(k_alloc1, 0)

@@ -412,8 +412,8 @@ __device__ void s_bump_gsf(AllocLds &L, const AllocPrm *p, int delta, int only_o
 
 // CBitAlloShort::BitAllo (reference bitallos.cpp:202-369) for one granule, both channels.
 // Inputs L.xr ([3][192] per channel), L.s_maskmb.  Outputs L.ix / L.signx in bitstream order,
-// L.gr[igr][*], L.sfout_s.
-__device__ void bitallo_short(AllocLds &L, const AllocPrm *p, int igr, int min_bits, int target_bits,
+// L.gr[igr][*], L.sfout_s.  Out of line: the frame loop's code stays small (short granules are the minority).
+__device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int igr, int min_bits, int target_bits,
                               int max_bits, int bit_pool, int ms, int MNR, sfo_t (*sfs)[3][12])
 {
     HX_LANE_DECL;

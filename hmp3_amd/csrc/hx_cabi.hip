@@ -43,7 +43,6 @@ __global__ void k_alloc_slim(AllocArgs a);
 __global__ void k_alloc_lsf(AllocArgs a);
 __global__ void k_alloc1(AllocArgs a);
 __global__ void k_alloc1_lsf(AllocArgs a);
-extern "C" int k_alloc_slim_persistent();      // 1: the kernel's workgroups claim streams from a counter (hx_alloc3.inc, HX_PERSIST)
 
 static thread_local std::string g_err;
 static void set_err(const char *fmt, const char *a = "")
@@ -463,7 +462,7 @@ extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
         dev_alloc(b, b->d_dbg, sizeof(HxFrameDebug) * (size_t) b->S * b->maxF);
         dev_alloc(b, b->d_xrdbg, sizeof(float) * (size_t) b->S * 2 * b->maxF * 1152);
         dev_alloc(b, b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 2);
-        if (dev_alloc(b, b->d_prof, sizeof(unsigned long long) * (size_t) b->S * 64) == 0) hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * 64);
+        if (dev_alloc(b, b->d_prof, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS) == 0) hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS);
     }
 }
 
@@ -656,7 +655,7 @@ static int encode_pass(hx_batch *b, const int16_t *d_pcm, const float *d_pcm32, 
     // persistent workgroups: as many as the chip holds at once (or one per stream if that is fewer); each walks one stream of
     // the launch order after the other (hx_alloc3.inc)
     // (built into k_alloc_slim, the kernel of batches beyond the resident set; the 256-register kernels keep one workgroup per stream)
-    const int G = (b->slim && !b->alloc1 && !b->lsf && k_alloc_slim_persistent() && S > b->resident) ? b->resident : S;
+    const int G = (b->slim && !b->alloc1 && !b->lsf && S > b->resident) ? b->resident : S;
     if (b->alloc1) { if (b->lsf) LAUNCH(k_alloc1_lsf, dim3(G), dim3(128), qa, a); else LAUNCH(k_alloc1, dim3(G), dim3(128), qa, a); }
     else if (b->lsf) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, a);
     else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, a);
@@ -984,7 +983,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "bt") { src = f.bt; n = S * NG; }
     else if (k == "eng") { src = b->d_eng; n = sizeof(int) * S * 2 * NG * 9; }
     else if (k == "dbg" && b->d_dbg) { src = b->d_dbg; n = sizeof(HxFrameDebug) * S * (NG / 2); }
-    else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * 64; }
+    else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
     else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
     else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 2; }
     if (!src) return -1;

@@ -216,6 +216,58 @@ enum HxCounter {
 #define HX_PARK_MAX 64
 #define HX_CNT_WORDS (HX_CNT_PARK + HX_PARK_MAX)
 
+// Slots of the stream walk's profile (built with -DHX_PROFILE: AllocArgs::prof, 64 per stream; tools/prof_slots.py reads this
+// table for the profile tools).  Master-wave clock64 ticks booked to a phase, except the counts (HX_PROF_N_*).
+enum HxProf {
+    HX_PROF_JOIN_FETCH = 0,         // frame loop: wait for the helper's fetch of the granule's operands, band start values out of the landing area
+    HX_PROF_STARTUP = 1,            // long granule: startup_prepped
+    HX_PROF_SEEK_INITIAL = 2,
+    HX_PROF_SEEK_ACTUAL = 3,
+    HX_PROF_TRADE_DUAL = 4,
+    HX_PROF_SCALE_FACTORS = 5,
+    HX_PROF_BIG_LUCKY = 6,
+    HX_PROF_DO_QUANT = 7,
+    HX_PROF_QUANT_COUNT = 8,        // quantise-and-count, or the count after do_quant
+    HX_PROF_INCREASE_BITS = 9,
+    HX_PROF_DECREASE_BITS = 10,
+    HX_PROF_INVERSE_SF2 = 11,
+    HX_PROF_BITALLO = 12,           // frame loop: the granule's allocation
+    HX_PROF_HANDOVER = 13,          // frame loop: the granule's segments sized and handed to the outbox
+    HX_PROF_BUDGET = 14,            // frame loop: the frame's budget
+    HX_PROF_GR_PRE = 15,            // frame loop: short-block mask, block types
+    HX_PROF_FETCH_POST = 16,        // frame loop: the next granule's fetch order
+    HX_PROF_EMIT = 17,              // frame placement: packets, debug taps
+    HX_PROF_RETIRE = 18,            // frame placement: full slots retired, running totals
+    HX_PROF_PACK_SF = 19,           // hand-over: scalefactor sizing of one channel
+    HX_PROF_N_SWEEPS = 20,          // count: gain-search sweeps of the master wave
+    HX_PROF_N_LUCKY = 21,           // count: big_lucky passes
+    HX_PROF_N_COUNTS = 22,          // count: bit counts
+    HX_PROF_LUCKY_SETUP = 23,
+    HX_PROF_LUCKY_TERMS = 24,
+    HX_PROF_LUCKY_SUMS = 25,
+    HX_PROF_LUCKY_REPLAY = 26,
+    HX_PROF_SWEEP_PUBLISH = 27,     // gain-search sweep: band lanes publish their gain pairs
+    HX_PROF_SWEEP_LINES = 28,
+    HX_PROF_SWEEP_SUMS = 29,
+    HX_PROF_SEEK_JOIN = 30,         // gain search: wait for the helper's channel
+    HX_PROF_TOTAL = 31,             // the stream's whole walk
+    HX_PROF_CNT_BALLOTS = 36,       // count_bits_ch: ...
+    HX_PROF_CNT_J23 = 37,
+    HX_PROF_CNT_REGIONS = 38,
+    HX_PROF_CNT_PAIRS = 39,
+    HX_PROF_CNT_QUADS = 40,
+    HX_PROF_CNT_REDUCE = 41,
+    HX_PROF_QC_POST = 42,           // quant_count_bits: the helper's order, the quantiser, the join
+    HX_PROF_QC_QUANT = 43,
+    HX_PROF_QC_JOIN = 44,
+    HX_PROF_N_SWEEPS_HELPER = 45,   // count: gain-search sweeps of the helper wave (channel 1)
+    HX_PROF_GR_TAIL = 46,           // frame loop: the granule loop's tail
+    HX_PROF_PL_SIZES = 47,          // frame placement: size, bitrate index
+    HX_PROF_PL_SLOT = 48,           // frame placement: slot and frame record
+    HX_PROF_PL_HEAD = 49,           // frame placement: header, side information copy
+};
+#define HX_PROF_WORDS 64            // slots per stream
+
 // Arguments of the allocator kernels (k_alloc / k_alloc_lsf), filled by the host runtime.
 struct AllocArgs {
     HxStream *st;

@@ -472,9 +472,9 @@ def test_parking_changes_no_byte_and_the_placement_tap_names_every_cu(park, monk
 @pytest.mark.one_k6_build
 def test_persistent_workgroups_walk_more_streams_than_slots_over_several_calls(monkeypatch):
     """Beyond the resident set k_alloc_slim runs as many workgroups as the chip holds and each claims stream after stream of
-    the launch order from a counter (hx_alloc3.inc, HX_PERSIST): 1600 streams on 1536 slots, three calls (the second and third
-    in the order of the previous call's durations), every stream against the oracle; the counter is back at zero after
-    every launch (the next one starts from position 0: all 1600 streams come out)."""
+    the launch order from a counter (hx_alloc3.inc; HX_PERSIST, set for that build only): 1600 streams on 1536 slots, three
+    calls (the second and third in the order of the previous call's durations), every stream against the oracle; the counter
+    is back at zero after every launch (the next one starts from position 0: all 1600 streams come out)."""
     monkeypatch.setenv("HMP3AMD_K6", "slim")
     kw = dict()      # VBR -V50, block switching
     S, F, calls = 1600, 5, 3

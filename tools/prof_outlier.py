@@ -5,6 +5,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch
 import bench
 from hmp3_amd import api
+import prof_slots
 S = int(sys.argv[1]) if len(sys.argv) > 1 else 1024
 F = int(sys.argv[2]) if len(sys.argv) > 2 else 64
 CFG = int(sys.argv[3]) if len(sys.argv) > 3 else 2
@@ -26,9 +27,11 @@ for c in range(CALLS):
     if c >= 1:
         acc += b.debug_read("prof", np.uint64, S * 64).reshape(S, 64).astype(np.float64)
 acc /= (CALLS - 1) * F
-names = {1: "startup", 3: "seek_actual", 5: "scale_factors", 6: "big_lucky", 8: "count_bits", 9: "increase_bits", 10: "decrease_bits", 11: "inverse_sf2", 12: "bitallo total",
-         13: "hand-over", 17: "flush+side", 20: "#seek sweeps", 21: "#lucky passes", 22: "#count_bits", 31: "kernel total"}
-tot = acc[:, 31]
+SHOW = ("startup", "seek_actual", "scale_factors", "big_lucky", "quant_count", "increase_bits", "decrease_bits", "inverse_sf2", "bitallo",
+        "handover", "emit", "n_sweeps", "n_lucky", "n_counts", "total")
+names = {k: n for k, n in prof_slots.slots().items() if n in SHOW}
+T = prof_slots.slot("total")
+tot = acc[:, T]
 order = np.argsort(-tot)
 print("per-stream ticks/frame: min %.0f mean %.0f p99 %.0f max %.0f" % (tot.min(), tot.mean(), np.percentile(tot, 99), tot.max()))
 print("%-16s %10s %10s %10s %10s %10s" % ("phase", "mean", "slowest", "2nd", "3rd", "p50 stream"))
