@@ -6,6 +6,7 @@ is no CPU fallback: if the library or a GPU is missing, calls raise.
 """
 import ctypes as C
 import os
+import re
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -36,34 +37,67 @@ class IntPair(C.Structure):
     _fields_ = [("a", C.c_int), ("b", C.c_int)]
 
 
-EXPORTS = [
-    "hx_last_error", "hx_device_count", "hx_default_control",
-    "hx_enc_create", "hx_enc_destroy", "hx_enc_L3_audio_encode_init", "hx_enc_L3_audio_encode",
-    "hx_enc_MP3_audio_encode_init", "hx_enc_MP3_audio_encode", "hx_enc_L3_audio_encode_Packet", "hx_enc_MP3_audio_encode_Packet", "hx_batch_packet_buffers", "hx_batch_frame_stats_buffer", "hx_batch_encode_f32_host_stats", "hx_control_info", "hx_enc_get_bitrate",
-    "hx_enc_get_bitrate_float", "hx_enc_get_bitrate2_float", "hx_enc_get_frames",
-    "hx_enc_get_frames_bytes", "hx_enc_info_ec", "hx_enc_info_head", "hx_enc_info_string",
-    "hx_batch_create", "hx_batch_destroy", "hx_batch_nstreams", "hx_batch_out_stride",
-    "hx_batch_reset_stream", "hx_batch_stream_state_bytes", "hx_batch_get_stream_state", "hx_batch_set_stream_state", "hx_src_create", "hx_src_destroy", "hx_src_init", "hx_src_convert",
-    "hx_batch_submit_s16_device", "hx_batch_submit_f32_device", "hx_batch_wait", "hx_batch_set_gate",
-    "hx_batch_submit_s16_host", "hx_batch_submit_f32_host", "hx_batch_wait_host", "hx_pinned_alloc", "hx_pinned_free",
-    "hx_batch_encode_s16_device", "hx_batch_encode_s16_host", "hx_batch_encode_f32_device", "hx_batch_encode_f32_host",
-    "hx_xing_create", "hx_xing_destroy", "hx_xing_header", "hx_xing_toc", "hx_xing_update_info", "hx_xing_update_crc", "hx_xing_bitrate_index", "hx_batch_status",
-    "hx_batch_gate_timeouts", "hx_enc_out_stats", "hx_multi_create", "hx_multi_destroy", "hx_multi_ndevices", "hx_multi_nstreams", "hx_multi_shard", "hx_multi_batch",
-    "hx_multi_out_stride", "hx_multi_encode_s16_host", "hx_multi_encode_f32_host", "hx_multi_encode_f32_host_stats", "hx_multi_status",
-    "hx_build_id", "hx_batch_frames_bytes", "hx_batch_alloc_kernel_ms", "hx_batch_debug_read", "hx_batch_debug_enable", "hx_debug_host_table",
-    "hx_batch_k6_variant", "hx_batch_resident_streams", "hx_debug_slim_tables_ok", "hx_libc_version", "hx_libm_spot_check", "hx_device_numa_node", "hx_bind_thread_to_device", "hx_bind_thread_to_node", "hx_refresh_process_cpus",
-]
+# The ctypes type of every C type in include/hmp3_amd.h.  A parameter that is any other pointer or an array is a
+# c_void_p, which takes byref(...), ctypes arrays, string buffers, plain integers and None.
+CTYPES = {
+    "int": C.c_int, "unsigned": C.c_uint, "unsigned short": C.c_ushort,
+    "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "float": C.c_float, "void": None,
+    "HX_IN_OUT": InOut, "HX_INT_PAIR": IntPair, "const char *": C.c_char_p,
+    "hx_batch *": C.c_void_p, "hx_enc *": C.c_void_p, "hx_multi *": C.c_void_p, "hx_src *": C.c_void_p,
+    "hx_xing *": C.c_void_p, "void *": C.c_void_p,
+}
+HEADER = os.path.join(os.path.dirname(HERE), "include", "hmp3_amd.h")
 
+
+def _norm(t):
+    return " ".join(t.replace("*", " * ").split())
+
+
+def _param_type(decl):
+    """`const HX_E_CONTROL *ec` -> "const HX_E_CONTROL *", `int nbytes_out[2]` -> "int *" """
+    m = re.fullmatch(r"\s*(.*?)\b\w+\s*(\[\w*\])?\s*", decl, re.S)
+    return _norm(m.group(1) + ("*" if m.group(2) else ""))
+
+
+def prototypes(path=HEADER):
+    """every hx_* prototype of a C header: [(name, return type, [parameter types])]"""
+    with open(path) as f:
+        text = re.sub(r"/\*.*?\*/|//[^\n]*|^\s*#[^\n]*", " ", f.read(), flags=re.S | re.M)
+    protos = []
+    for decl in re.split(r"[;{}]", text):
+        m = re.fullmatch(r"\s*(.*?)\b(hx_\w+)\s*\((.*)\)\s*", decl, re.S)
+        if m:
+            args = m.group(3).strip()
+            params = [] if args in ("", "void") else [_param_type(a) for a in args.split(",")]
+            protos.append((m.group(2), _norm(m.group(1)), params))
+    return protos
+
+
+def signature(name, ret, params):
+    """(restype, argtypes) of a prototype; a type outside CTYPES raises"""
+    def ctype(t, param):
+        if param and t.endswith("*") and t != "const char *":
+            return C.c_void_p
+        if t not in CTYPES:
+            raise TypeError("include/hmp3_amd.h: %s %s(%s): no ctypes type for '%s'" % (ret, name, ", ".join(params), t))
+        return CTYPES[t]
+    return ctype(ret, False), [ctype(t, True) for t in params]
+
+
+PROTOTYPES = prototypes()
+EXPORTS = [p[0] for p in PROTOTYPES]
 _lib = None
 
 
 def lib():
-    """load libhmp3amd.so (raises if it has not been built: run hmp3_amd/build.sh)"""
+    """load libhmp3amd.so (raises if it has not been built: run hmp3_amd/build.sh), every function declared as
+    include/hmp3_amd.h declares it"""
     global _lib
     if _lib is None:
         if not os.path.exists(LIB_PATH):
             raise RuntimeError("hmp3_amd/libhmp3amd.so is missing - build it with hmp3_amd/build.sh "
                                "(there is no CPU fallback)")
+        sigs = {p[0]: signature(*p) for p in PROTOTYPES}
         # One HIP runtime per process: PyTorch bundles its own libamdhip64, and whichever copy is
         # mapped first serves both.  Import torch (when present) before our library so that tensors
         # and our kernels share a runtime; without torch the system ROCm runtime is used.
@@ -72,88 +106,10 @@ def lib():
         except Exception:
             pass
         L = C.CDLL(LIB_PATH)
-        L.hx_last_error.restype = C.c_char_p
-        L.hx_default_control.argtypes = [C.POINTER(EControl)]
-        L.hx_enc_create.restype = C.c_void_p
-        L.hx_enc_create.argtypes = [C.c_int]
-        L.hx_enc_destroy.argtypes = [C.c_void_p]
-        L.hx_enc_L3_audio_encode_init.argtypes = [C.c_void_p, C.POINTER(EControl)]
-        L.hx_enc_L3_audio_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hx_enc_L3_audio_encode.restype = InOut
-        L.hx_enc_L3_audio_encode_Packet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hx_enc_L3_audio_encode_Packet.restype = InOut
-        L.hx_enc_MP3_audio_encode_Packet.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hx_enc_MP3_audio_encode_Packet.restype = InOut
-        L.hx_batch_packet_buffers.argtypes = [C.c_void_p, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.hx_batch_packet_buffers.restype = None
-        L.hx_enc_MP3_audio_encode_init.argtypes = [C.c_void_p, C.POINTER(EControl), C.c_int, C.c_int, C.c_int, C.c_int]
-        L.hx_enc_MP3_audio_encode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
-        L.hx_enc_MP3_audio_encode.restype = InOut
-        L.hx_enc_get_bitrate.argtypes = [C.c_void_p]
-        L.hx_enc_get_bitrate_float.argtypes = [C.c_void_p]
-        L.hx_enc_get_bitrate_float.restype = C.c_float
-        L.hx_enc_get_bitrate2_float.argtypes = [C.c_void_p]
-        L.hx_enc_get_bitrate2_float.restype = C.c_float
-        L.hx_enc_get_frames.argtypes = [C.c_void_p]
-        L.hx_enc_get_frames.restype = C.c_uint
-        L.hx_enc_get_frames_bytes.argtypes = [C.c_void_p]
-        L.hx_enc_get_frames_bytes.restype = IntPair
-        L.hx_enc_info_ec.argtypes = [C.c_void_p, C.POINTER(EControl)]
-        L.hx_enc_info_head.argtypes = [C.c_void_p, C.POINTER(MpegHead)]
-        L.hx_enc_info_string.argtypes = [C.c_void_p, C.c_char_p]
-        L.hx_batch_create.restype = C.c_void_p
-        L.hx_batch_create.argtypes = [C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int]
-        L.hx_batch_destroy.argtypes = [C.c_void_p]
-        L.hx_batch_nstreams.argtypes = [C.c_void_p]
-        L.hx_batch_out_stride.argtypes = [C.c_void_p, C.c_int]
-        L.hx_batch_out_stride.restype = C.c_longlong
-        L.hx_batch_encode_s16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
-        L.hx_batch_encode_s16_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.hx_batch_submit_s16_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
-        L.hx_batch_submit_f32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
-        L.hx_batch_wait.argtypes = [C.c_void_p, C.c_void_p]
-        L.hx_batch_submit_s16_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.hx_batch_submit_f32_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.hx_batch_wait_host.argtypes = [C.c_void_p]
-        L.hx_pinned_alloc.argtypes = [C.c_longlong]
-        L.hx_pinned_alloc.restype = C.c_void_p
-        L.hx_pinned_free.argtypes = [C.c_void_p]
-        L.hx_pinned_free.restype = None
-        L.hx_batch_reset_stream.argtypes = [C.c_void_p, C.c_int]
-        L.hx_batch_stream_state_bytes.argtypes = [C.c_void_p]
-        L.hx_batch_stream_state_bytes.restype = C.c_longlong
-        L.hx_batch_get_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.hx_batch_set_stream_state.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
-        L.hx_batch_set_gate.argtypes = [C.c_void_p, C.c_int]
-        L.hx_batch_set_gate.restype = None
-        L.hx_batch_encode_f32_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
-        L.hx_batch_encode_f32_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-        L.hx_batch_status.argtypes = [C.c_void_p]
-        if hasattr(L, "hx_multi_create"):           # absent from older builds selected through HMP3AMD_LIB (A/B timing runs)
-            L.hx_batch_gate_timeouts.argtypes = [C.c_void_p]
-            L.hx_multi_create.restype = C.c_void_p
-            L.hx_multi_create.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int]
-            L.hx_multi_destroy.argtypes = [C.c_void_p]
-            L.hx_multi_ndevices.argtypes = [C.c_void_p]
-            L.hx_multi_nstreams.argtypes = [C.c_void_p]
-            L.hx_multi_shard.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int)]
-            L.hx_multi_batch.restype = C.c_void_p
-            L.hx_multi_batch.argtypes = [C.c_void_p, C.c_int]
-            L.hx_multi_out_stride.restype = C.c_longlong
-            L.hx_multi_out_stride.argtypes = [C.c_void_p, C.c_int]
-            L.hx_multi_encode_s16_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-            L.hx_multi_encode_f32_host.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
-            L.hx_multi_encode_f32_host_stats.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_longlong, C.c_void_p, C.c_void_p]
-            L.hx_multi_status.argtypes = [C.c_void_p]
-        L.hx_batch_frames_bytes.argtypes = [C.c_void_p, C.c_int]
-        L.hx_batch_frames_bytes.restype = IntPair
-        L.hx_batch_alloc_kernel_ms.argtypes = [C.c_void_p, C.POINTER(C.c_int)]
-        L.hx_batch_alloc_kernel_ms.restype = C.c_float
-        L.hx_batch_debug_read.argtypes = [C.c_void_p, C.c_char_p, C.c_void_p, C.c_longlong]
-        L.hx_batch_debug_read.restype = C.c_longlong
-        L.hx_batch_debug_enable.argtypes = [C.c_void_p, C.c_int]
-        L.hx_debug_host_table.argtypes = [C.POINTER(EControl), C.c_char_p, C.c_void_p, C.c_longlong]
-        L.hx_debug_host_table.restype = C.c_longlong
+        for name, (restype, argtypes) in sigs.items():
+            if hasattr(L, name):        # a build picked through HMP3AMD_LIB (A/B runs) may predate the header
+                f = getattr(L, name)
+                f.restype, f.argtypes = restype, argtypes
         _lib = L
     return _lib
 
@@ -173,7 +129,6 @@ def libm_report(points=1000):
     """the host's C library and whether its logf / log10f agree with the restatement the first-generation allocator's
     kernels use (hx_libm32.h = glibc 2.35): {"glibc": "2.35", "points": 1000, "mismatches": 0}"""
     L = lib()
-    L.hx_libc_version.restype = C.c_char_p
     return {"glibc": L.hx_libc_version().decode(), "points": points, "mismatches": int(L.hx_libm_spot_check(points))}
 
 
@@ -199,10 +154,7 @@ def bind_thread_to_node(node):
 def build_id():
     """hash of the sources / flags the loaded library was built from (None for builds that predate it)"""
     L = lib()
-    if not hasattr(L, "hx_build_id"):
-        return None
-    L.hx_build_id.restype = C.c_char_p
-    return L.hx_build_id().decode()
+    return L.hx_build_id().decode() if hasattr(L, "hx_build_id") else None
 
 
 def last_error():
@@ -299,14 +251,10 @@ class Batch:
 
     def k6_variant(self):
         """0 = k_alloc (four streams per CU), 1 = k_alloc_slim (six)"""
-        L = lib()
-        L.hx_batch_k6_variant.argtypes = [C.c_void_p]
-        return int(L.hx_batch_k6_variant(self.h))
+        return int(lib().hx_batch_k6_variant(self.h))
 
     def resident_streams(self):
-        L = lib()
-        L.hx_batch_resident_streams.argtypes = [C.c_void_p]
-        return int(L.hx_batch_resident_streams(self.h))
+        return int(lib().hx_batch_resident_streams(self.h))
 
     def gate_timeouts(self):
         return int(lib().hx_batch_gate_timeouts(self.h))

@@ -32,7 +32,41 @@ def test_library_exports_every_declared_symbol():
     lib = C.CDLL(LIB)
     for name in sorted(declared):
         assert hasattr(lib, name), "include/hmp3_amd.h declares %s but the library does not export it" % name
-    assert set(api.EXPORTS) <= declared
+    assert set(api.EXPORTS) == declared
+
+
+def test_api_binds_every_function_as_the_header_declares_it():
+    """ctypes passes an undeclared argument as a C int and reads an undeclared result as one, which cuts a 64-bit pointer
+    in half: api.lib() declares every hx_* function from include/hmp3_amd.h, and nothing else declares one"""
+    from hmp3_amd import api
+    hdr = open(os.path.join(ROOT, "include", "hmp3_amd.h")).read()
+    args = dict(re.findall(r"\b(hx_[a-zA-Z0-9_]+)\s*\(([^)]*)\)", hdr))
+    ret = {name: r for name, r, _ in api.PROTOTYPES}
+    lib = api.lib()
+    sig = {name: (getattr(lib, name).restype, getattr(lib, name).argtypes) for name in args}
+    for name, a in args.items():
+        restype, argtypes = sig[name]
+        assert argtypes is not None and len(argtypes) == (0 if a.strip() == "void" else a.count(",") + 1), name
+        assert restype is api.CTYPES[ret[name]], name
+    vp, i, ll = C.c_void_p, C.c_int, C.c_longlong
+    for name in ("hx_enc_create", "hx_batch_create", "hx_multi_create", "hx_multi_batch", "hx_src_create", "hx_xing_create",
+                 "hx_pinned_alloc"):
+        assert sig[name][0] is vp, name
+    for name in ("hx_last_error", "hx_build_id", "hx_libc_version"):
+        assert sig[name][0] is C.c_char_p, name
+    assert sig["hx_batch_submit_s16_device"][1] == [vp, vp, i, vp, ll, vp, vp]
+    assert sig["hx_xing_update_info"][1][8] is C.c_ulonglong and sig["hx_xing_update_crc"][0] is C.c_ushort
+    assert sig["hx_enc_L3_audio_encode"][0] is api.InOut and sig["hx_batch_frames_bytes"][0] is api.IntPair
+    for bad in [("int", ["double"]), ("int *", [])]:
+        with pytest.raises(TypeError, match="hx_f"):
+            api.signature("hx_f", *bad)
+    hand = re.compile(rb"\.hx_\w+\.(argtypes|restype)")
+    for top in ("hmp3_amd", "tests", "tools"):
+        for d, dirs, files in os.walk(os.path.join(ROOT, top)):
+            dirs[:] = [x for x in dirs if x != "__pycache__"]
+            for fn in files:
+                with open(os.path.join(d, fn), "rb") as f:
+                    assert not hand.search(f.read()), "%s declares an hx_* function by hand" % os.path.join(d, fn)
 
 
 @pytest.mark.parametrize("kw", CONFIGS, ids=[str(i) for i in range(len(CONFIGS))])

@@ -22,10 +22,6 @@ PAIRS = [(44100, 44100),                    # case 0: copy
 def libs():
     from hmp3_amd import api
     P, R = api.lib(), O.ref()
-    P.hx_src_create.restype = C.c_void_p
-    P.hx_src_destroy.argtypes = [C.c_void_p]
-    P.hx_src_init.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
-    P.hx_src_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     R.ref_src_new.restype = C.c_void_p
     R.ref_src_free.argtypes = [C.c_void_p]
     R.ref_src_init.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]

@@ -7,23 +7,10 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from hmp3_amd import api
 from oracle import oracle as O
 
 pytestmark = pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built")
-
-
-def product():
-    from hmp3_amd import api
-    L = api.lib()
-    L.hx_xing_create.restype = C.c_void_p
-    L.hx_xing_destroy.argtypes = [C.c_void_p]
-    L.hx_xing_header.argtypes = [C.c_void_p] + [C.c_int] * 8 + [C.c_void_p] * 4 + [C.c_int]
-    L.hx_xing_toc.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    L.hx_xing_update_info.argtypes = [C.c_void_p, C.c_uint, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
-                                      C.c_ulonglong, C.c_uint, C.c_uint, C.c_uint, C.c_uint, C.c_ushort]
-    L.hx_xing_update_crc.argtypes = [C.c_ushort, C.c_void_p, C.c_int]
-    L.hx_xing_update_crc.restype = C.c_ushort
-    return L
 
 
 def reference():
@@ -52,7 +39,7 @@ CASES = [
 @pytest.mark.parametrize("case", CASES, ids=[str(c[:5]) for c in CASES])
 def test_tag_frame_matches_reference(case):
     sr, mode, flags, scale, kbps, nframes, (lo, hi) = case
-    P, R = product(), reference()
+    P, R = api.lib(), reference()
     rng = np.random.default_rng(sr + nframes)
     x = P.hx_xing_create()
     a = (C.c_ubyte * 2048)()
@@ -87,7 +74,7 @@ def test_tag_frame_matches_reference(case):
 
 
 def test_tag_does_not_fit_or_unknown_rate():
-    P, R = product(), reference()
+    P, R = api.lib(), reference()
     x = P.hx_xing_create()
     a = (C.c_ubyte * 2048)()
     for sr, kbps in [(44100, 32), (12345, 128), (44100, 999)]:
