@@ -24,6 +24,11 @@ class EControl(C.Structure):
         [(n, C.c_int) for n in ("cpu_select", "quick", "test1", "test2", "test3", "short_block_threshold")]
 
 
+class Source(C.Structure):
+    """HX_SOURCE: the other arguments of CMp3Enc::MP3_audio_encode_init (mp3enc.cpp:2655) for one source"""
+    _fields_ = [(n, C.c_int) for n in ("bits", "is_float", "mpeg_select", "mono_convert")]
+
+
 class MpegHead(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("sync", "id", "option", "prot", "br_index", "sr_index", "pad",
                                        "private_bit", "mode", "mode_ext", "cr", "original", "emphasis")]
@@ -290,6 +295,70 @@ class Batch:
             pass
 
 
+class SrcBatch(Batch):
+    """A converting batch (hx_batch_create_src): N streams whose sources are in any format and at any rate the converter
+    takes, converted on the GPU.  controls: what MP3_audio_encode_init takes per stream (samprate = the source's rate,
+    mode 3 = a mono source); sources: Source per stream (or one for all)."""
+
+    def __init__(self, controls, sources, nstreams=None, max_frames=256, device=0):
+        L = lib()
+        if isinstance(controls, EControl):
+            self.n = int(nstreams if nstreams is not None else (1 if isinstance(sources, Source) else len(sources)))
+            self._ec, ec_arg, shared_ec = controls, C.byref(controls), 1
+        else:
+            self.n = len(controls)
+            self._ec = (EControl * self.n)(*controls)
+            ec_arg, shared_ec = self._ec, 0
+        if isinstance(sources, Source):
+            self._src, src_arg, shared_src = sources, C.byref(sources), 1
+        else:
+            assert len(sources) == self.n
+            self._src = (Source * self.n)(*sources)
+            src_arg, shared_src = self._src, 0
+        self.h = L.hx_batch_create_src(device, self.n, ec_arg, shared_ec, src_arg, shared_src, max_frames)
+        if not self.h:
+            raise RuntimeError("hx_batch_create_src failed: " + last_error())
+        self.max_frames = max_frames
+
+    def schedule(self, i, nframes):
+        """(bytes each of stream i's next nframes calls consumes, bytes they read)"""
+        nb = np.zeros(nframes, dtype=np.int64)
+        rd = int(lib().hx_batch_src_schedule(self.h, i, nframes, nb.ctypes.data))
+        if rd < 0:
+            raise RuntimeError("hx_batch_src_schedule failed: " + last_error())
+        return nb, rd
+
+    def in_stride(self, nframes):
+        return int(lib().hx_batch_src_in_stride(self.h, nframes))
+
+    def encode_src_host(self, rows, nframes, frame_off=None, stats=False):
+        """rows: uint8 [n, in_stride], row i starting at stream i's first unconsumed byte; frame_off: None or int64
+        [n, nframes] byte offsets of each call's input in the row -> (list of bytes per stream, in_used int64 [n]
+        [, stats int32 [n, nframes, 2]])"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        assert rows.shape[0] == self.n
+        off = None if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+        stride = self.out_stride(nframes)
+        out = np.zeros((self.n, stride), dtype=np.uint8)
+        nb = np.zeros(self.n, dtype=np.int32)
+        used = np.zeros(self.n, dtype=np.int64)
+        st = np.zeros((self.n, nframes, 2), dtype=np.int32) if stats else None
+        r = lib().hx_batch_encode_src_host(self.h, rows.ctypes.data, rows.shape[1], None if off is None else off.ctypes.data, nframes,
+                                          out.ctypes.data, stride, nb.ctypes.data, used.ctypes.data, None if st is None else st.ctypes.data)
+        if r != 0:
+            raise RuntimeError("hx_batch_encode_src_host failed: " + last_error())
+        res = [out[i, :nb[i]].tobytes() for i in range(self.n)]
+        return (res, used, st) if stats else (res, used)
+
+
+def src_encode_control(ec, source):
+    """the control the encoder runs behind the converter for a source (what MP3_audio_encode_init derives), and the bytes
+    per call; (None, 0) when rejected"""
+    out = EControl()
+    n = int(lib().hx_src_encode_control(C.byref(ec), C.byref(source), C.byref(out)))
+    return (out if n else None), n
+
+
 class Multi:
     """nstreams streams over several GPUs of one node (hx_multi_*): contiguous blocks, one host thread per device"""
 
@@ -343,6 +412,40 @@ class Multi:
             self.close()
         except Exception:
             pass
+
+
+class SrcMulti(Multi):
+    """converting batches over several GPUs of one node (hx_multi_create_src): contiguous blocks, one host thread per device"""
+
+    def __init__(self, controls, sources, max_frames=256, ndev=0, devices=None):
+        L = lib()
+        dv = (C.c_int * len(devices))(*devices) if devices else None
+        if devices:
+            ndev = len(devices)
+        self.n = len(controls)
+        assert len(sources) == self.n
+        self._ec = (EControl * self.n)(*controls)
+        self._src = (Source * self.n)(*sources)
+        self.h = L.hx_multi_create_src(ndev, dv, self.n, self._ec, 0, self._src, 0, max_frames)
+        if not self.h:
+            raise RuntimeError("hx_multi_create_src failed: " + last_error())
+
+    def in_stride(self, nframes):
+        return int(lib().hx_multi_src_in_stride(self.h, nframes))
+
+    def encode_src_host(self, rows, nframes, frame_off=None):
+        """as SrcBatch.encode_src_host, over all streams -> (list of bytes per stream, in_used int64 [n])"""
+        rows = np.ascontiguousarray(rows, dtype=np.uint8)
+        off = None if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+        stride = int(lib().hx_multi_out_stride(self.h, nframes))
+        out = np.zeros((self.n, stride), dtype=np.uint8)
+        nb = np.zeros(self.n, dtype=np.int32)
+        used = np.zeros(self.n, dtype=np.int64)
+        r = lib().hx_multi_encode_src_host(self.h, rows.ctypes.data, rows.shape[1], None if off is None else off.ctypes.data, nframes,
+                                           out.ctypes.data, stride, nb.ctypes.data, used.ctypes.data, None)
+        if r != 0:
+            raise RuntimeError("hx_multi_encode_src_host failed: " + last_error())
+        return [out[i, :nb[i]].tobytes() for i in range(self.n)], used
 
 
 class Mp3Enc:

@@ -7,6 +7,7 @@
 #include <string.h>
 #include <limits.h>
 #include <vector>
+#include <algorithm>
 #include <chrono>
 #include <atomic>
 #include <string>
@@ -20,6 +21,7 @@
 __global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
                             const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf);
 __global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int nchan);
+__global__ void k_src(SrcArgs a);
 __global__ void k_detect(HxStream *st, const HxParams *prm, const int *eng, unsigned char *flg, int *dbg_metric, unsigned char *bt,
                          unsigned char *btprev, int NG, int S, int lsf);
 __global__ void k_spec(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
@@ -104,6 +106,22 @@ struct hx_batch {
     HxFrameDebug *d_dbg = nullptr;
     unsigned long long *d_prof = nullptr;
     int lastNG = 0;                     // NG of the previous call (layout of the carry)
+    // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
+    int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
+    std::vector<HxSrcPlan> src_plans;
+    std::vector<int> src_cls;           // stream -> plan
+    std::vector<long long> src_calls;   // stream -> converter calls made (authoritative; the device keeps a copy for k_src)
+    HxSrcPlan *d_src_plan = nullptr;
+    int *d_src_cls = nullptr;
+    long long *d_src_calls = nullptr;   // [2][S]: k_src reads copy src_par and writes the other
+    float *d_src_carry = nullptr;       // [2][S][2][HX_SRC_CARRY] the same for the case-4 intermediate samples
+    int src_par = 0;
+    float *d_src_pcm = nullptr;         // [S][nframes * 1152][nchan] the last call's converted PCM
+    long long *d_src_off = nullptr, *h_src_off = nullptr;      // [S][max_frames] the caller's frame offsets (device / page-locked)
+    hipEvent_t ev_src_off = nullptr;    // the last upload of h_src_off is done
+    unsigned char *d_src_in = nullptr; long long src_in_cap = 0;   // staging of hx_batch_encode_src_host
+    int src_xwin = 0, src_zwin = 0, src_zoff = 0, src_coff = 0, src_lastF = 0;
+    size_t src_lds = 0;
     bool debug = false;
     // staging for the host-buffer entry points
     int16_t *d_pcm = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr;
@@ -255,6 +273,7 @@ extern "C" void hx_batch_destroy(hx_batch *b)
     for (hipStream_t q : b->streams) hipStreamDestroy(q);
     for (hipEvent_t e : b->events) hipEventDestroy(e);
     for (auto &pr : b->pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    if (b->h_src_off) hipHostFree(b->h_src_off);
     delete b;
 }
 
@@ -383,22 +402,57 @@ static unsigned long long cfg_fingerprint(const HxParams &p)
     mix(v, sizeof(v));
     return h;
 }
-extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b) { (void) b; return (long long) (sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float)); }
+// A converting batch's blob (another magic: neither kind takes the other's) also holds the converter: a fingerprint of its
+// plan, its call count and the case-4 intermediate samples it carries.
+#define HX_STATE_MAGIC_SRC 0x43335848u  // "HX3C"
+static const size_t HX_STATE_SRC_BYTES = 2 * sizeof(long long) + 2 * HX_SRC_CARRY * sizeof(float);
+static unsigned long long plan_fingerprint(const HxSrcPlan &p)
+{
+    unsigned long long h = 1469598103934665603ull;
+    const unsigned char *c = (const unsigned char *) &p;
+    for (size_t i = 0; i < sizeof(p); i++) { h ^= c[i]; h *= 1099511628211ull; }
+    return h;
+}
+extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b)
+{
+    return (long long) (sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float) + (b && b->nsrc ? HX_STATE_SRC_BYTES : 0));
+}
 
 static int stream_state_copy(hx_batch *b, int i, void *host, bool save)
 {
     if (!b || i < 0 || i >= b->S || !host) { set_err("bad arguments"); return -1; }
     if (drain(b) != 0) return -1;
-    HxStateHeader hd = {HX_STATE_MAGIC, HX_STATE_VERSION, (unsigned) sizeof(HxStream), 0, cfg_fingerprint(b->params[b->cls_of[i]])};
+    HxStateHeader hd = {b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC, HX_STATE_VERSION, (unsigned) sizeof(HxStream), 0, cfg_fingerprint(b->params[b->cls_of[i]])};
+    char *h = (char *) host + sizeof(HxStateHeader);
+    const size_t per = (size_t) (2 * b->maxF + 3) * 576;        // floats per (stream, channel) in the subband buffer
+    char *hs = h + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float);    // the converter's part (converting batches)
+    const unsigned long long pfp = b->nsrc ? plan_fingerprint(b->src_plans[b->src_cls[i]]) : 0;
     if (save) memcpy(host, &hd, sizeof(hd));
     else {
         HxStateHeader in;
         memcpy(&in, host, sizeof(in));
-        if (in.magic != HX_STATE_MAGIC || in.version != HX_STATE_VERSION || in.state_bytes != hd.state_bytes) { set_err("not a stream-state blob of this library build"); return -1; }
+        if ((in.magic == HX_STATE_MAGIC) != (hd.magic == HX_STATE_MAGIC) && (in.magic == HX_STATE_MAGIC || in.magic == HX_STATE_MAGIC_SRC)) {
+            set_err(b->nsrc ? "a stream-state blob of a batch without converter: a converting batch does not take it" : "a stream-state blob of a converting batch: this batch has no converter");
+            return -1;
+        }
+        if (in.magic != hd.magic || in.version != HX_STATE_VERSION || in.state_bytes != hd.state_bytes) { set_err("not a stream-state blob of this library build"); return -1; }
         if (in.cfg != hd.cfg) { set_err("the stream state was saved under a different configuration than slot's"); return -1; }
+        unsigned long long fp = 0;
+        if (b->nsrc) memcpy(&fp, hs, sizeof(fp));
+        if (fp != pfp) { set_err("the stream state was saved with a different converter (source format, rates or layout) than slot's"); return -1; }
     }
-    char *h = (char *) host + sizeof(HxStateHeader);
-    const size_t per = (size_t) (2 * b->maxF + 3) * 576;        // floats per (stream, channel) in the subband buffer
+    if (b->nsrc) {
+        float *carry = b->d_src_carry + ((long long) b->src_par * b->S + i) * 2 * HX_SRC_CARRY;      // the copy the next call reads
+        if (save) {
+            memcpy(hs, &pfp, sizeof(pfp));
+            memcpy(hs + sizeof(pfp), &b->src_calls[i], sizeof(long long));
+            HIPCHK(hipMemcpy(hs + 2 * sizeof(long long), carry, 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            memcpy(&b->src_calls[i], hs + sizeof(pfp), sizeof(long long));
+            for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &b->src_calls[i], sizeof(long long), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(carry, hs + 2 * sizeof(long long), 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
     if (save) {
         HIPCHK(hipMemcpy(h, b->d_st + i, sizeof(HxStream), hipMemcpyDeviceToHost));
         for (int c = 0; c < 2; c++)
@@ -430,6 +484,11 @@ extern "C" int hx_batch_reset_stream(hx_batch *b, int i)
     if (e != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e)); return -1; }
     const size_t per = (size_t) (2 * b->maxF + 3) * 576 * sizeof(float);     // subband slots of one (stream, channel)
     HIPCHK(hipMemset((char *) b->d_sb + (size_t) i * 2 * per, 0, 2 * per));
+    if (b->nsrc) {      // the converter starts over too (call 0 reads no carried samples)
+        const long long zero = 0;
+        b->src_calls[i] = 0;
+        for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    }
     return 0;
 }
 
@@ -480,7 +539,7 @@ static int pipe_init(hx_batch *b)
 }
 
 // Argument checks of every encode entry point, made before anything is allocated, copied or launched.
-static int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
+static int check_args(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
 {
     if (!b) { set_err("null batch"); return -1; }
     if (b->poisoned) { set_err("the batch is unusable after a failed device call: destroy it"); return -1; }
@@ -488,6 +547,13 @@ static int check_call(const hx_batch *b, const void *pcm, int nframes, const voi
     if (!pcm || !out || !out_bytes) { set_err("null buffer"); return -1; }
     if (out_stride < hx_batch_out_stride(b, nframes)) { set_err("out_stride is smaller than hx_batch_out_stride(b, nframes)"); return -1; }
     return 0;
+}
+// ... of the PCM entry points: a converting batch takes its input through hx_batch_encode_src_* only (a plain call would
+// advance the encoder past its converter)
+static int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
+{
+    if (b && b->nsrc && pcm != (const void *) b->d_src_pcm) { set_err("a converting batch takes its input through hx_batch_encode_src_*"); return -1; }
+    return check_args(b, pcm, nframes, out, out_stride, out_bytes);
 }
 
 // the packing kernels of one call on stream qp (see encode_core)
@@ -985,6 +1051,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "dbg" && b->d_dbg) { src = b->d_dbg; n = sizeof(HxFrameDebug) * S * (NG / 2); }
     else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
     else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
+    else if (k == "srcpcm" && b->d_src_pcm) { src = b->d_src_pcm; n = sizeof(float) * S * b->src_lastF * 1152 * b->nchan; }   // the converted PCM of the last call
     else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 2; }
     if (!src) return -1;
     if (n > cap) n = cap;
@@ -1271,13 +1338,14 @@ static int nearest_rate(const int *table, int n, int x)
     return best;
 }
 
-// CMp3Enc::MP3_audio_encode_init (reference mp3enc.cpp:2655-2808): pick the encode rate for the source
-// rate and mpeg_select (0 track the input, 1 an MPEG-1 rate, 2 an MPEG-2 rate, else that rate), set up the
-// sample-format / rate converter (hx_src.cpp) and the encoder behind it.  Returns the bytes the caller
-// must hold before every hx_enc_MP3_audio_encode call (more than one call consumes: 1153 sample frames
-// when the rates are equal), 0 on failure.
-extern "C" int hx_enc_MP3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec, int source_bits, int source_is_float,
-                                            int mpeg_select, int mono_convert)
+// The encode control of a converted source: CMp3Enc::MP3_audio_encode_init's derivation (reference mp3enc.cpp:2655-2808),
+// shared by hx_enc_MP3_audio_encode_init and the converting batches.  Picks the encode rate for the source rate and
+// mpeg_select (0 track the input, 1 an MPEG-1 rate, 2 an MPEG-2 rate, else that rate), sets the converter `conv` up
+// (hx_src.cpp) and writes the control the encoder behind it runs: the encode rate, mode 3 for a mono target, and
+// nsb_limit bounded by the source's band when it is up-sampled.  Returns the bytes the caller must hold before every
+// call (more than one call consumes: 1153 sample frames when the rates are equal), 0 on failure (hx_last_error).
+static int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int source_is_float, int mpeg_select, int mono_convert,
+                              hx_src *conv, HX_E_CONTROL *ec_out)
 {
     static const int rate_table[6] = {22050, 24000, 16000, 44100, 48000, 32000};
     const int source = ec->samprate;
@@ -1306,9 +1374,8 @@ extern "C" int hx_enc_MP3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec, i
         if (target != mpeg_select) { set_err("mpeg_select is not an MPEG sample rate"); return 0; }
         break;
     }
-    if (!e->src) e->src = hx_src_create();
     int cutoff = 0;
-    const int min_input_bytes = hx_src_init(e->src, source, source_chan, source_bits, source_is_float, target, target_chan, &cutoff);
+    const int min_input_bytes = hx_src_init(conv, source, source_chan, source_bits, source_is_float, target, target_chan, &cutoff);
     if (min_input_bytes <= 0) { set_err("the sample-rate converter cannot handle this source format / rate pair"); return 0; }
     int nsb_limit = (64 * cutoff + target / 2) / target;
     if (nsb_limit > 30) nsb_limit = 30;
@@ -1320,10 +1387,32 @@ extern "C" int hx_enc_MP3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec, i
         if (ec2.nsb_limit > nsb_limit) ec2.nsb_limit = nsb_limit;
     }
     ec2.layer = 3;
+    *ec_out = ec2;
+    return min_input_bytes;
+}
+
+extern "C" int hx_src_encode_control(const HX_E_CONTROL *ec, const HX_SOURCE *src, HX_E_CONTROL *ec_out)
+{
+    if (!ec || !src || !ec_out) { set_err("bad arguments"); return 0; }
+    hx_src *conv = hx_src_create();
+    const int r = src_encode_control(ec, src->bits, src->is_float, src->mpeg_select, src->mono_convert, conv, ec_out);
+    hx_src_destroy(conv);
+    return r;
+}
+
+// CMp3Enc::MP3_audio_encode_init (reference mp3enc.cpp:2655-2808): the converter and the encoder behind it (see
+// src_encode_control).  Returns the bytes the caller must hold before every hx_enc_MP3_audio_encode call, 0 on failure.
+extern "C" int hx_enc_MP3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec, int source_bits, int source_is_float,
+                                            int mpeg_select, int mono_convert)
+{
+    if (!e->src) e->src = hx_src_create();
+    HX_E_CONTROL ec2;
+    const int min_input_bytes = src_encode_control(ec, source_bits, source_is_float, mpeg_select, mono_convert, e->src, &ec2);
+    if (!min_input_bytes) return 0;
     if (!hx_enc_L3_audio_encode_init(e, &ec2)) return 0;
     e->src_bits = source_bits;
     e->src_float = source_is_float;
-    e->src_chan = source_chan;
+    e->src_chan = (ec->mode == 3) ? 1 : 2;
     return min_input_bytes;
 }
 
@@ -1500,9 +1589,10 @@ extern "C" void hx_multi_destroy(hx_multi *m)
     delete m;
 }
 
-extern "C" hx_multi *hx_multi_create(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+// the blocks of streams and their batches; make(device, first, count) creates block k's batch
+template <class Make>
+static hx_multi *multi_create(int ndev, const int *devices, int nstreams, Make make)
 {
-    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
     const int have = hx_device_count();
     if (ndev <= 0) ndev = have;
     if (ndev > nstreams) ndev = nstreams;
@@ -1513,7 +1603,7 @@ extern "C" hx_multi *hx_multi_create(int ndev, const int *devices, int nstreams,
     for (int k = 0; k < ndev; k++) {
         const int first = k * base + (k < rem ? k : rem), count = base + (k < rem ? 1 : 0);
         const int dev = devices ? devices[k] : k;
-        hx_batch *b = hx_batch_create(dev, count, shared_control ? ec : ec + first, shared_control, max_frames);
+        hx_batch *b = make(dev, first, count);
         if (!b) { hx_multi_destroy(m); return nullptr; }            // hx_last_error is hx_batch_create's
         m->part.push_back(b); m->first.push_back(first); m->count.push_back(count); m->device.push_back(dev);
         cpu_set_t cs;
@@ -1525,6 +1615,24 @@ extern "C" hx_multi *hx_multi_create(int ndev, const int *devices, int nstreams,
         else if (b->nchan != m->nchan || b->lsf != m->part[0]->lsf) { set_err("mono / stereo and MPEG-1 / MPEG-2 streams cannot share a batch"); hx_multi_destroy(m); return nullptr; }
     }
     return m;
+}
+
+extern "C" hx_multi *hx_multi_create(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create(dev, count, shared_control ? ec : ec + first, shared_control, max_frames);
+    });
+}
+
+// converting batches over several devices (stream numbers in hx_last_error are the block's)
+extern "C" hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control,
+                                         const HX_SOURCE *src, int shared_source, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create_src(dev, count, shared_control ? ec : ec + first, shared_control, shared_source ? src : src + first, shared_source, max_frames);
+    });
 }
 
 extern "C" int hx_multi_ndevices(const hx_multi *m) { return m ? (int) m->part.size() : 0; }
@@ -1583,10 +1691,225 @@ extern "C" int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int
 {
     return multi_call(m, 2, pcm, nframes, out, out_stride, out_bytes, stats);
 }
+extern "C" long long hx_multi_src_in_stride(const hx_multi *m, int nframes)
+{
+    long long n = 0;
+    if (m) for (hx_batch *b : m->part) n = std::max(n, hx_batch_src_in_stride(b, nframes));
+    return n;
+}
+
+// hx_batch_encode_src_host over all streams: one host thread per device, each on its block's rows
+extern "C" int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                        unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats)
+{
+    if (!m || !in || !out || !out_bytes) { set_err("null buffer"); return -1; }
+    if (out_stride < hx_multi_out_stride(m, nframes)) { set_err("out_stride is smaller than hx_multi_out_stride(m, nframes)"); return -1; }
+    const size_t n = m->part.size();
+    std::vector<int> rc(n, 0);
+    std::vector<std::string> err(n);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < n; k++)
+        th.emplace_back([&, k]() {
+            if (m->ncpus[k] > 0) sched_setaffinity(0, sizeof(cpu_set_t), &m->cpus[k]);
+            const long long f = m->first[k];
+            rc[k] = hx_batch_encode_src_host(m->part[k], in + f * in_stride, in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes,
+                                             out + f * out_stride, out_stride, out_bytes + f, in_used ? in_used + f : nullptr,
+                                             stats ? stats + f * nframes * 2 : nullptr);
+            if (rc[k]) err[k] = hx_last_error();
+        });
+    for (std::thread &t : th) t.join();
+    for (size_t k = 0; k < n; k++) if (rc[k]) { set_err("%s", err[k].c_str()); return rc[k]; }
+    return 0;
+}
+
 extern "C" int hx_multi_status(hx_multi *m)
 {
     int v = 0;
     if (!m) return -1;
     for (hx_batch *b : m->part) v |= hx_batch_status(b);
     return v;
+}
+
+// ------------------------------------------------------------------------------------------
+// Converting batches: every stream's source goes through its converter on the GPU (k_src, hx_src.inc) into fp32 PCM at
+// the encode rate, which the fp32 path encodes.  The host keeps each stream's converter call count: every phase of the
+// converter is a closed form of it (hx_src.h), so the host knows each call's input extent without converting anything.
+extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, const HX_SOURCE *src,
+                                         int shared_source, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
+    std::vector<HX_E_CONTROL> ecs(nstreams);
+    std::vector<HxSrcPlan> plans;
+    std::vector<int> cls(nstreams);
+    hx_src *conv = hx_src_create();
+    for (int s = 0; s < nstreams; s++) {
+        const HX_SOURCE &sc = shared_source ? src[0] : src[s];
+        HxSrcPlan p;
+        if (!src_encode_control(shared_control ? ec : ec + s, sc.bits, sc.is_float, sc.mpeg_select, sc.mono_convert, conv, &ecs[s]) ||
+            !hx_src_plan(conv, &p)) {
+            char msg[64];
+            snprintf(msg, sizeof msg, "stream %d: ", s);
+            const std::string why = g_err;
+            set_err("%s", (msg + why).c_str());
+            hx_src_destroy(conv);
+            return nullptr;
+        }
+        int k = -1;
+        for (size_t i = 0; i < plans.size(); i++) if (memcmp(&plans[i], &p, sizeof(p)) == 0) { k = (int) i; break; }
+        if (k < 0) { plans.push_back(p); k = (int) plans.size() - 1; }
+        cls[s] = k;
+    }
+    hx_src_destroy(conv);
+    hx_batch *b = hx_batch_create(device, nstreams, ecs.data(), 0, max_frames);
+    if (!b) return nullptr;
+    b->nsrc = (int) plans.size();
+    b->src_plans = plans;
+    b->src_cls = cls;
+    b->src_calls.assign(nstreams, 0);
+    // LDS of a workgroup: the input window (source channels, interleaved), the intermediate samples (output channels,
+    // case 4) and the filter bank (cases 2 - 4), each sized for the batch's largest plan
+    int xf = 0, zf = 0, cf = 0;
+    for (const HxSrcPlan &p : plans) {
+        if (p.nch != b->nchan) { set_err("a converter's output channels differ from the batch's"); hx_batch_destroy(b); return nullptr; }
+        if (p.xwin > b->src_xwin) b->src_xwin = p.xwin;
+        if (p.zwin > b->src_zwin) b->src_zwin = p.zwin;
+        xf = std::max(xf, p.channels * p.xwin);
+        zf = std::max(zf, p.nch * p.zwin);
+        if (p.ncase >= 2) cf = std::max(cf, p.totcoef);
+    }
+    b->src_zoff = xf;
+    b->src_coff = xf + zf;
+    b->src_lds = sizeof(float) * ((size_t) xf + zf + cf);
+    if (b->src_lds > 160 * 1024) { set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr; }
+    if (b->src_lds > 64 * 1024 && hipFuncSetAttribute((const void *) k_src, hipFuncAttributeMaxDynamicSharedMemorySize, (int) b->src_lds) != hipSuccess) {
+        set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr;
+    }
+    const long long S = nstreams;
+#define ALLOC_SRC(ptr, bytes) do { if (dev_alloc(b, ptr, bytes) != 0) { hx_batch_destroy(b); return nullptr; } } while (0)
+    ALLOC_SRC(b->d_src_plan, sizeof(HxSrcPlan) * plans.size());
+    ALLOC_SRC(b->d_src_cls, sizeof(int) * S);
+    ALLOC_SRC(b->d_src_calls, sizeof(long long) * 2 * S);
+    ALLOC_SRC(b->d_src_carry, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY);
+    ALLOC_SRC(b->d_src_pcm, sizeof(float) * S * max_frames * 1152 * b->nchan);
+    ALLOC_SRC(b->d_src_off, sizeof(long long) * S * max_frames);
+#undef ALLOC_SRC
+    if (hipHostMalloc((void **) &b->h_src_off, sizeof(long long) * S * max_frames, 0) != hipSuccess) { b->h_src_off = nullptr; set_err("hipHostMalloc failed"); hx_batch_destroy(b); return nullptr; }
+    if (new_event(b, b->ev_src_off) != 0 ||
+        hipMemcpy(b->d_src_plan, plans.data(), sizeof(HxSrcPlan) * plans.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_src_cls, cls.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(b->d_src_calls, 0, sizeof(long long) * 2 * S) != hipSuccess ||
+        hipMemset(b->d_src_carry, 0, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY) != hipSuccess ||
+        hipEventRecord(b->ev_src_off, nullptr) != hipSuccess) {
+        set_err("HIP error while setting up the converter");
+        hx_batch_destroy(b);
+        return nullptr;
+    }
+    return b;
+}
+
+extern "C" long long hx_batch_src_schedule(const hx_batch *b, int i, int nframes, long long *in_bytes)
+{
+    if (!b || !b->nsrc || i < 0 || i >= b->S || nframes < 0) { set_err("bad arguments (or not a converting batch)"); return -1; }
+    return hx_src_plan_schedule(&b->src_plans[b->src_cls[i]], b->src_calls[i], nframes, in_bytes);
+}
+
+extern "C" long long hx_batch_src_in_stride(const hx_batch *b, int nframes)
+{
+    if (!b || !b->nsrc || nframes < 0) return 0;
+    long long n = 0;
+    for (const HxSrcPlan &p : b->src_plans) {
+        const long long v = ((long long) nframes * p.cmax + p.xwin) * p.channels * (p.bits / 8);
+        if (v > n) n = v;
+    }
+    return (n + 255) & ~255LL;
+}
+
+extern "C" int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
+                                          int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes,
+                                          long long *in_used, void *stream)
+{
+    if (b && !b->nsrc) { set_err("not a converting batch (hx_batch_create_src)"); return -1; }
+    if (check_args(b, d_in, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
+    if (in_stride <= 0) { set_err("in_stride must be positive"); return -1; }
+    // every call's input extent from the schedule, checked against the row before anything runs.  Consecutive calls: the
+    // consumption telescopes, and the last call reaches furthest (a call reads at most ntaps - k past its successor's
+    // start, and the last one reads at least ntaps), so one closed form per stream; with offsets every call is checked.
+    const int S = b->S;
+    std::vector<long long> used_end(S);
+    for (int s = 0; s < S; s++) {
+        const HxSrcPlan &p = b->src_plans[b->src_cls[s]];
+        const long long fb = (long long) p.channels * (p.bits / 8), c0 = b->src_calls[s];
+        long long used, rd;
+        int bad = -1;
+        long long off = 0;
+        if (!frame_off) {
+            off = hx_src_consumed(&p, c0, c0 + nframes - 1) * fb;
+            hx_src_call_extent(&p, c0 + nframes - 1, &used, &rd);
+            if (off + rd * fb > in_stride) bad = nframes - 1;
+        } else {
+            for (int f = 0; f < nframes && bad < 0; f++) {
+                off = frame_off[(long long) s * nframes + f];
+                hx_src_call_extent(&p, c0 + f, &used, &rd);
+                if (off < 0 || off + rd * fb > in_stride) bad = f;
+            }
+        }
+        if (bad >= 0) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "stream %d, call %d: its input [%lld, %lld) does not fit in_stride %lld", s, bad, off, off + rd * fb, in_stride);
+            set_err("%s", msg);
+            return -1;
+        }
+        used_end[s] = off + used * fb;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t q = (hipStream_t) stream;
+    if (frame_off) {
+        const size_t nb = sizeof(long long) * (size_t) S * nframes;
+        HIPCHK(hipEventSynchronize(b->ev_src_off));        // (the page-locked copy of the previous call's offsets is on the device)
+        memcpy(b->h_src_off, frame_off, nb);
+        HIPCHK(hipMemcpyAsync(b->d_src_off, b->h_src_off, nb, hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(b->ev_src_off, q));
+    }
+    SrcArgs a;
+    a.in = d_in; a.in_stride = in_stride; a.off = frame_off ? b->d_src_off : nullptr;
+    a.plan = b->d_src_plan; a.cls = b->d_src_cls;
+    a.calls_in = b->d_src_calls + (long long) b->src_par * S; a.calls_out = b->d_src_calls + (long long) (1 - b->src_par) * S;
+    a.carry_in = b->d_src_carry + (long long) b->src_par * S * 2 * HX_SRC_CARRY;
+    a.carry_out = b->d_src_carry + (long long) (1 - b->src_par) * S * 2 * HX_SRC_CARRY;
+    a.out = b->d_src_pcm; a.nframes = nframes; a.nch = b->nchan; a.xwin = b->src_xwin; a.zwin = b->src_zwin;
+    a.zoff = b->src_zoff; a.coff = b->src_coff; a.status = b->d_status;
+    hipLaunchKernelGGL(k_src, dim3((unsigned) ((long long) S * nframes)), dim3(256), b->src_lds, q, a);
+    hipError_t e = hipGetLastError();
+    if (e != hipSuccess) { set_err("launch of k_src failed: %s", hipGetErrorString(e)); b->poisoned = true; return -1; }
+    b->src_par ^= 1;
+    for (int s = 0; s < S; s++) b->src_calls[s] += nframes;
+    b->src_lastF = nframes;
+    if (in_used) memcpy(in_used, used_end.data(), sizeof(long long) * S);
+    return encode_core(b, nullptr, b->d_src_pcm, nframes, d_out, out_stride, d_out_bytes, stream);
+}
+
+extern "C" int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                        int nframes, unsigned char *out, long long out_stride, int *out_bytes,
+                                        long long *in_used, int *stats)
+{
+    if (b && !b->nsrc) { set_err("not a converting batch (hx_batch_create_src)"); return -1; }
+    if (check_args(b, in, nframes, out, out_stride, out_bytes) != 0) return -1;
+    if (in_stride <= 0) { set_err("in_stride must be positive"); return -1; }
+    HIPCHK(hipSetDevice(b->device));
+    const long long ibytes = (long long) b->S * in_stride, obytes = (long long) b->S * out_stride;
+    if (ibytes > b->src_in_cap) { if (dev_realloc(b, b->d_src_in, ibytes) != 0) return -1; b->src_in_cap = ibytes; }
+    if (obytes > b->out_cap) { if (dev_realloc(b, b->d_out, obytes) != 0) return -1; b->out_cap = obytes; }
+    if (drain(b) != 0) return -1;       // (the staging may still be read by an earlier call)
+    HIPCHK(hipMemcpy(b->d_src_in, in, ibytes, hipMemcpyHostToDevice));
+    int *d_stats = nullptr, *saved = b->frame_stats;
+    const size_t nst = sizeof(int) * (size_t) b->S * nframes * 2;
+    if (stats) { HIPCHK(hipMalloc((void **) &d_stats, nst)); b->frame_stats = d_stats; }
+    int r = hx_batch_encode_src_device(b, b->d_src_in, in_stride, frame_off, nframes, b->d_out, out_stride, b->d_outbytes, in_used, nullptr);
+    b->frame_stats = saved;
+    if (r == 0 && drain(b) != 0) r = -1;
+    if (r == 0 && (hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost) != hipSuccess ||
+                   hipMemcpy(out, b->d_out, obytes, hipMemcpyDeviceToHost) != hipSuccess ||
+                   (stats && hipMemcpy(stats, d_stats, nst, hipMemcpyDeviceToHost) != hipSuccess))) { set_err("copying the results back failed"); r = -1; }
+    if (d_stats) hipFree(d_stats);
+    return r;
 }

@@ -1,4 +1,5 @@
 // hx_front.hip - front-end kernels of the batched MP3 encoder for MI355X (gfx950):
+//   k_src        K0a converting batches only: source format / rate -> fp32 PCM at the encode rate (hx_src.inc)
 //   k_dcfilter   K0  optional input DC blocker, sequential per channel   (filter2.c:116-144)
 //   k_polyphase  K1  int16 / fp32 PCM -> 32 x 18 subband samples per granule (the stage of sbt.c:57-310), and in its
 //                    epilogue the subband energies in mB for the transient detector (detect.c:80-101)
@@ -1164,6 +1165,8 @@ __global__ void k_dcfilter(const int16_t *__restrict__ pcm, const float *__restr
     }
     ss->dc[ch] = d;
 }
+
+#include "hx_src.inc"
 
 // Gate of a pipelined submit (hx_batch_submit_*): holds the stream it is launched on until `need` workgroups of
 // the previous call's allocator kernel have started, i.e. until that kernel occupies its share of the chip.

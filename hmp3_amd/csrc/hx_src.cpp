@@ -427,3 +427,50 @@ extern "C" int hx_src_convert(hx_src *s, const unsigned char *xin, float *yout, 
     if (out_bytes) *out_bytes = s->out_bytes;
     return in_bytes;
 }
+
+extern "C" int hx_src_plan(const hx_src *s, HxSrcPlan *p)
+{
+    if (!s || !s->staged) return 0;
+    memset(p, 0, sizeof(*p));
+    p->ncase = s->ncase; p->layout = s->layout; p->channels = s->channels; p->bits = s->bits; p->is_float = s->is_float;
+    p->nch = s->layout == 1 ? 2 : 1;
+    p->n = s->n; p->m = s->m; p->k = s->k; p->ntaps = s->ntaps; p->totcoef = s->totcoef; p->n1 = s->n1; p->m1 = s->m1;
+    memcpy(p->coef1, s->coef1, sizeof(p->coef1));
+    memcpy(p->coef, s->coef, sizeof(p->coef));
+    // windows of one call, bounded from the rates: the main stage advances at most 1152 k + ceil(1152 m / n) positions per call
+    const long long adv = 1152LL * s->k + (1152LL * s->m + s->n - 1) / s->n;
+    switch (s->ncase) {
+    case 0: p->xwin = p->cmax = 1152; break;
+    case 1: p->xwin = 577; p->cmax = 576; break;
+    case 2: p->xwin = (int) adv + 2; p->cmax = (int) adv; break;
+    case 3: p->xwin = (int) adv + s->ntaps; p->cmax = (int) adv; break;
+    default:
+        p->zwin = (int) adv + s->ntaps + 128;
+        p->cmax = (int) (((adv + s->ntaps + 128) * s->m1 + s->n1 - 1) / s->n1);
+        p->xwin = p->cmax + 3;
+        break;
+    }
+    return 1;
+}
+
+extern "C" long long hx_src_schedule(const hx_src *s, long long calls, int nframes, long long *in_bytes)
+{
+    HxSrcPlan p;
+    if (!hx_src_plan(s, &p)) return -1;
+    return hx_src_plan_schedule(&p, calls, nframes, in_bytes);
+}
+
+extern "C" long long hx_src_plan_schedule(const HxSrcPlan *p, long long calls, int nframes, long long *in_bytes)
+{
+    if (calls < 0 || nframes < 0) return -1;
+    const long long fb = (long long) p->channels * p->bits / 8;
+    long long pos = 0, end = 0;
+    for (int f = 0; f < nframes; f++) {
+        long long used, rd;
+        hx_src_call_extent(p, calls + f, &used, &rd);
+        if (pos + rd > end) end = pos + rd;
+        pos += used;
+        if (in_bytes) in_bytes[f] = used * fb;
+    }
+    return end * fb;
+}

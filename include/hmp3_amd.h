@@ -89,7 +89,9 @@ void hx_enc_out_stats(hx_enc *e);
 
 /* ---- sample-format / sample-rate converter (host side) ----
    What CMp3Enc::MP3_audio_encode runs in front of every frame: Csrc (pub/srcc.h:87-97).  hx_enc_MP3_audio_encode
-   uses it internally; it is exported for callers that feed the batched API from sources at other rates. */
+   uses it internally.  Batched callers (hx_batch_* and hx_multi_*) whose sources are at other rates or in other formats
+   use the converting batches instead (hx_batch_create_src, hx_multi_create_src below), which run the same converter on
+   the GPU. */
 typedef struct hx_src hx_src;
 hx_src *hx_src_create(void);
 void hx_src_destroy(hx_src *s);
@@ -98,6 +100,15 @@ int hx_src_init(hx_src *s, int source, int channels, int bits, int is_float, int
                 int *encode_cutoff_freq);
 /* Csrc::sr_convert (srcc.cpp:795): 1152 samples per output channel, fp32 at int16 scale; returns input bytes used */
 int hx_src_convert(hx_src *s, const unsigned char *xin, float *yout, int *out_bytes);
+/* host only, changes nothing: the input bytes each of the next nframes calls of a converter that has made `calls` calls
+   consumes (the in_bytes of those hx_src_convert calls; in_bytes may be NULL); returns the bytes those calls read,
+   counted from the first unconsumed byte (-1: not initialised) */
+long long hx_src_schedule(const hx_src *s, long long calls, int nframes, long long *in_bytes);
+/* the other arguments of CMp3Enc::MP3_audio_encode_init (mp3enc.cpp:2655) for one source */
+typedef struct { int bits, is_float, mpeg_select, mono_convert; } HX_SOURCE;
+/* host only: the control the encoder runs behind the converter for a source (ec: samprate = the source's rate,
+   mode 3 = a mono source) - what MP3_audio_encode_init derives; returns its bytes per call, 0 = rejected */
+int hx_src_encode_control(const HX_E_CONTROL *ec, const HX_SOURCE *src, HX_E_CONTROL *ec_out);
 
 /* ---- batched encode (N independent streams) ---- */
 /* ec: nstreams controls, or one shared control when shared_control != 0.
@@ -199,6 +210,39 @@ HX_INT_PAIR hx_batch_frames_bytes(hx_batch *b, int stream_index);
    milliseconds, measured with HIP events on the launch stream; also returns the call count */
 float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls);
 
+/* ---- converting batches: sources in any format and at any rate the converter takes, converted on the GPU ----
+   Per stream, ec is the control CMp3Enc::MP3_audio_encode_init takes (samprate = the source's rate, mode 3 = a mono
+   source) and src its other arguments; the streams' resolved encode controls follow hx_batch_create's rules (one channel
+   count, MPEG-1 or MPEG-2 rates, first-generation allocator or not).  A source the converter rejects makes create return
+   NULL, with the stream named in hx_last_error.  Each call of nframes frames is nframes calls of
+   CMp3Enc::MP3_audio_encode per stream: the converter (k_src) writes the fp32 PCM the encoder reads, bit-identical to
+   hx_src_convert, and everything behind it is the fp32 path (DC filter, packets, frame counters, taps included).
+   The other hx_batch_* calls apply; hx_batch_reset_stream also restarts the stream's converter, and the stream-state blob
+   of a converting batch also holds the converter's phase and carried samples (it is larger, and refused by a batch of
+   the other kind).  hx_batch_debug_read(b, "srcpcm", ...): the converted PCM of the last call, [S][nframes*1152][nch].
+   A converting batch refuses the int16 / fp32 encode and submit calls (-1): they would advance the encoder past its
+   converter.  Status bit 8 (hx_batch_status): a call's window exceeded the converter plan's bound (cannot happen; the
+   call's converted PCM was not written). */
+hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, const HX_SOURCE *src,
+                              int shared_source, int max_frames);
+/* host only, changes nothing: the bytes each of stream i's next nframes calls consumes (in_bytes may be NULL); returns the
+   bytes those calls read, counted from the stream's first unconsumed byte */
+long long hx_batch_src_schedule(const hx_batch *b, int i, int nframes, long long *in_bytes);
+/* an in_stride that fits nframes consecutive calls of every stream, from the rates alone */
+long long hx_batch_src_in_stride(const hx_batch *b, int nframes);
+/* in: [nstreams][in_stride] bytes, row i starting at stream i's first unconsumed byte.  frame_off (host): NULL, or
+   [nstreams][nframes] byte offsets into the row where call f's input starts (the reference takes a pointer per call);
+   NULL = each call starts where the previous one's consumption ended.  in_used (host, [nstreams], may be NULL): where a
+   following call would start, known when the function returns.  A row shorter than its schedule or an offset that
+   reads past in_stride is refused before anything runs (-1, the batch stays usable).  Asynchronous on `stream`. */
+int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
+                               int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes,
+                               long long *in_used, void *stream);
+/* the same with host buffers (synchronous); stats: NULL or [nstreams][nframes][2], as hx_batch_encode_f32_host_stats */
+int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                             int nframes, unsigned char *out, long long out_stride, int *out_bytes,
+                             long long *in_used, int *stats);
+
 /* ---- host placement (no reference equivalent): a host-fed GPU reads ~50 GB/s of PCM over PCIe, so its page-locked
    buffers and the threads that submit its copies belong on the NUMA node the device hangs on.
    hx_device_numa_node: that node from sysfs (-1 = unknown or not a NUMA machine).  hx_bind_thread_to_device: restricts the
@@ -232,6 +276,13 @@ int hx_multi_encode_s16_host(hx_multi *m, const int16_t *pcm, int nframes, unsig
 int hx_multi_encode_f32_host(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes);
 int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats);
 int hx_multi_status(hx_multi *m);
+/* converting batches (hx_batch_create_src) in the same blocks: in [nstreams][in_stride], frame_off [nstreams][nframes] or NULL,
+   in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
+hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control,
+                              const HX_SOURCE *src, int shared_source, int max_frames);
+long long hx_multi_src_in_stride(const hx_multi *m, int nframes);
+int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                             unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats);
 
 /* ---- test taps (tests only; synchronise) ---- */
 /* name: "sb" "xr" "etab" "thr" "msbase" "bt" "eng" "dbg" (per-stage buffers), "ixq" "sgn" "seg" "frm" (what the allocator hands the
