@@ -31,11 +31,12 @@ $HIPCC $FLAGS -fno-slp-vectorize $ILP $HX_FRONT_EXTRA -DHX_FRONT_PART=2 -c hx_fr
 for f in hx_alloc hx_alloc_slim hx_alloc_lsf hx_alloc1 hx_alloc1_lsf; do
   $HIPCC $FLAGS $ALLOC_SCHED $NOLICM ${HX_ALLOC_OPT:--O2} $HX_ALLOC_EXTRA -c $f.hip -o $OBJ/$f.o & pids+=($!)
 done
-for f in hx_pack hx_cabi; do
+for f in hx_pack hx_batch hx_batch_src; do
   $HIPCC $FLAGS $HX_PACK_EXTRA -c $f.hip -o $OBJ/$f.o & pids+=($!)
 done
-for f in hx_host hx_xhead hx_src; do
-  g++ -O2 -fPIC -ffp-contract=off -std=c++17 -c $f.cpp -o $OBJ/$f.o & pids+=($!)
+# (the host runtime's units that launch no kernel: the HIP runtime's API through its C header)
+for f in hx_host hx_xhead hx_src hx_enc hx_multi; do
+  g++ -O2 -fPIC -ffp-contract=off -std=c++17 -Wno-unused-result -D__HIP_PLATFORM_AMD__ -I"$(dirname "$(dirname "$HIPCC")")/include" -c $f.cpp -o $OBJ/$f.o & pids+=($!)
 done
 # (every compiler is waited for before a failure ends the script: the EXIT trap removes the object directory)
 rc=0

@@ -1,0 +1,880 @@
+// hx_batch.hip - the batch of the C ABI (include/hmp3_amd.h) and its launch sequence.
+// Owns the device buffers of a batch (subband carry, spectra, psy data, stream state), groups streams into
+// configuration classes and launches K1..K8: create / destroy, checkpoints, the pass, submits, host-buffer calls, reads.
+#include <string>
+#include "hx_rt.h"
+
+static thread_local std::string g_err;
+void set_err(const char *fmt, const char *a)
+{
+    char buf[512];
+    snprintf(buf, sizeof(buf), fmt, a);
+    g_err = buf;
+}
+extern "C" const char *hx_last_error(void) { return g_err.c_str(); }
+
+// hash of the sources this library was built from (hmp3_amd/build.sh passes it): profiles/ and bench.py use it to tell
+// whether committed counter profiles belong to the loaded build
+#ifndef HX_BUILD_ID
+#define HX_BUILD_ID "unknown"
+#endif
+extern "C" const char *hx_build_id(void) { return HX_BUILD_ID; }
+
+extern "C" int hx_device_count(void)
+{
+    int n = 0;
+    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
+    return n;
+}
+
+static int flush_pack(hx_batch *b, long long gate_base);
+
+int new_stream(hx_batch *b, hipStream_t &q, int priority)
+{
+    HIPCHK(priority == INT_MAX ? hipStreamCreateWithFlags(&q, hipStreamNonBlocking) : hipStreamCreateWithPriority(&q, hipStreamNonBlocking, priority));
+    b->streams.push_back(q);
+    return 0;
+}
+int new_event(hx_batch *b, hipEvent_t &e)
+{
+    HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    b->events.push_back(e);
+    return 0;
+}
+
+// Buffer set k: front[k], walk[k] and sgn[k] (k = 1: also sgn[2], the third set of signs).
+static int alloc_set(hx_batch *b, int k)
+{
+    const long long S = b->S, NG = 2LL * b->maxF;
+    FrontSet &f = b->front[k];
+    WalkSet &w = b->walk[k];
+    if (dev_alloc(b, f.xr, sizeof(float) * S * NG * 1152) || dev_alloc(b, f.etab, sizeof(float) * S * NG * 128) ||
+        dev_alloc(b, f.thr, sizeof(float) * S * NG * 128) || dev_alloc(b, f.x34, sizeof(float) * S * NG * 1152) ||
+        dev_alloc(b, f.thrprev, sizeof(float) * S * 128) || dev_alloc(b, f.msbase, sizeof(int) * S * NG) ||
+        dev_alloc(b, f.msdec, sizeof(int) * S * NG) || dev_alloc(b, f.bt, S * NG) || dev_alloc(b, f.btprev, S) ||
+        dev_alloc(b, f.msflag, S * NG) || dev_alloc(b, f.band, sizeof(HxBandPrep) * S * NG) ||
+        dev_alloc(b, w.ixq, sizeof(short) * S * NG * 1152) || dev_alloc(b, w.seg, sizeof(HxSegOut) * S * NG * 2) ||
+        dev_alloc(b, w.frm, sizeof(HxFrameOut) * S * NG) || dev_alloc(b, w.slots, sizeof(HxSlot) * S * (NG + HX_SLOTS_EXTRA)))
+        return -1;
+    w.pre_len = b->d_lens + 2 * k * S;
+    w.carry_len = w.pre_len + S;
+    const long long sgn_bytes = sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS;
+    return (dev_alloc(b, b->sgn[k], sgn_bytes) || (k == 1 && dev_alloc(b, b->sgn[2], sgn_bytes))) ? -1 : 0;
+}
+
+// (a packing that cannot be enqueued leaves the batch unusable: Poison)
+int drain(hx_batch *b)
+{
+    HIPCHK(hipSetDevice(b->device));
+    if (flush_pack(b, -1) != 0) { b->poisoned = true; return -1; }
+    HIPCHK(hipDeviceSynchronize());
+    return 0;
+}
+
+extern "C" void hx_batch_destroy(hx_batch *b)
+{
+    if (!b) return;
+    hipSetDevice(b->device);
+    // A packing that was never asked for (no hx_batch_wait / plain call / status read after the last device-buffer submit)
+    // is dropped, not enqueued: it would write into output buffers the caller may have freed already.
+    b->pack_job.pending = false;
+    hipDeviceSynchronize();
+    for (void *p : b->mem) hipFree(p);
+    for (hipStream_t q : b->streams) hipStreamDestroy(q);
+    for (hipEvent_t e : b->events) hipEventDestroy(e);
+    for (auto &pr : b->pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
+    if (b->h_src_off) hipHostFree(b->h_src_off);
+    delete b;
+}
+
+extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return nullptr; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return nullptr; }
+    {   // written for gfx950 (MI355X) only: the code object holds no other target
+        hipDeviceProp_t prop;
+        HIPCHKN(hipGetDeviceProperties(&prop, device));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return nullptr; }
+    }
+    // the launch bookkeeping (streams x granules x 9 energies per channel) is 32-bit
+    if ((long long) nstreams * max_frames > 32LL * 1024 * 1024) { set_err("nstreams * max_frames exceeds 32 Mi frames per call: split the batch"); return nullptr; }
+    HIPCHKN(hipSetDevice(device));
+    hx_batch *b = new hx_batch;
+    b->device = device; b->S = nstreams; b->maxF = max_frames;
+    b->cls_of.resize(nstreams);
+    // group streams into configuration classes
+    std::vector<HxControl> seen;
+    for (int s = 0; s < nstreams; s++) {
+        const HxControl *c = (const HxControl *) (shared_control ? ec : ec + s);
+        int k = -1;
+        for (size_t i = 0; i < seen.size(); i++) if (memcmp(&seen[i], c, sizeof(HxControl)) == 0) { k = (int) i; break; }
+        if (k < 0) {
+            HxParams p;
+            if (!hx_resolve(c, &p)) {
+                // (a limit of this library's layout is named as such: the reference would have taken the configuration)
+                if (*hx_resolve_error()) set_err("configuration rejected: %s", hx_resolve_error());
+                else set_err("configuration rejected (the reference's L3_audio_encode_init returns 0 for it)");
+                delete b; return nullptr;
+            }
+            if (p.filter_dc) b->any_dc = true;
+            if (b->params.empty()) { b->nchan = p.nchan; b->lsf = p.h_id ? 0 : 1; b->alloc1 = p.alloc1; }
+            else if (p.alloc1 != b->alloc1) { set_err("intensity-stereo / dual-channel streams (first-generation allocator) cannot share a batch with the others"); delete b; return nullptr; }
+            else if (p.nchan != b->nchan) { set_err("mono and stereo streams cannot share a batch (the PCM layout differs)"); delete b; return nullptr; }
+            else if ((p.h_id ? 0 : 1) != b->lsf) { set_err("MPEG-1 and MPEG-2 sample rates cannot share a batch (frames per call differ)"); delete b; return nullptr; }
+            seen.push_back(*c);
+            b->params.push_back(p);
+            k = (int) seen.size() - 1;
+        }
+        b->cls_of[s] = k;
+        if (shared_control) { for (int t = 1; t < nstreams; t++) b->cls_of[t] = 0; break; }
+    }
+    b->ncls = (int) b->params.size();
+    const long long S = nstreams, NG = 2LL * max_frames;
+    std::vector<HxGlobalTabs> gt_host(1);       // (144 KB: not on the stack)
+    HxGlobalTabs &gt = gt_host[0];
+    hx_global_tabs(&gt);
+    std::vector<HxStream> st(nstreams);
+    for (int s = 0; s < nstreams; s++) hx_stream_reset(&b->params[b->cls_of[s]], b->cls_of[s], &st[s]);
+#define ALLOC(ptr, bytes) do { if (dev_alloc(b, ptr, bytes) != 0) { hx_batch_destroy(b); return nullptr; } } while (0)
+    ALLOC(b->d_prm, sizeof(HxParams) * b->ncls + 256);        // (k_spec reads a spreading row in 16-byte pieces, up to 60 bytes past its end)
+    ALLOC(b->d_gt, sizeof(HxGlobalTabs));
+    ALLOC(b->d_st, sizeof(HxStream) * S);
+    ALLOC(b->d_sb, sizeof(float) * S * 2 * (NG + 3) * 576);
+    ALLOC(b->d_lens, sizeof(int) * 4 * S);
+    if (alloc_set(b, 0) != 0) { hx_batch_destroy(b); return nullptr; }
+    ALLOC(b->d_eng, sizeof(int) * S * 2 * NG * 9);
+    ALLOC(b->d_flg, S * NG);
+    ALLOC(b->d_status, sizeof(int));
+    ALLOC(b->d_outbytes, sizeof(int) * S);
+    if (const char *e = getenv("HMP3AMD_LPT")) b->lpt = atoi(e);
+    if (const char *e = getenv("HMP3AMD_EXACT_SUMS")) b->strict_sums = atoi(e) != 0;
+    if (const char *e = getenv("HMP3AMD_PARK_PAIR")) b->park_pair = atoi(e) != 0;
+    if (const char *e = getenv("HMP3AMD_PARK")) { b->park_k = atoi(e); if (b->park_k < 0) b->park_k = 0; if (b->park_k > HX_PARK_MAX) b->park_k = HX_PARK_MAX; }
+    ALLOC(b->d_dur, sizeof(unsigned) * 2 * S);        // [S] durations, [S] where workgroup i of the last launch ran (see "place")
+    ALLOC(b->d_order, sizeof(int) * S);
+    HIPCHKN(hipMemset(b->d_dur, 0, sizeof(unsigned) * 2 * S));
+    ALLOC(b->d_done, HX_CNT_WORDS * sizeof(int));
+    HIPCHKN(hipMemset(b->d_done, 0, HX_CNT_WORDS * sizeof(int)));
+    {
+        hipDeviceProp_t prop;
+        int per_cu = 0;
+        HIPCHKN(hipGetDeviceProperties(&prop, device));
+        const void *kern = b->alloc1 ? (b->lsf ? (const void *) k_alloc1_lsf : (const void *) k_alloc1) : (b->lsf ? (const void *) k_alloc_lsf : (const void *) k_alloc);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
+        b->resident = per_cu * prop.multiProcessorCount;
+        b->ncu = prop.multiProcessorCount;
+        // Two builds of the MPEG-1 stream walk.  A batch that the chip holds at once (config 2: 1024 streams on 256 CUs x 4)
+        // runs the one written for 256 registers and 38 KB of LDS per stream; a larger one runs k_alloc_slim, whose streams
+        // take 168 registers and 26.5 KB, six to a CU: a stream is slower there, 1.5 x as many are in flight.
+        // HMP3AMD_K6 = fat | slim overrides the choice (tests run every case on both).
+        bool slim_ok = !b->alloc1 && !b->lsf;
+        for (int k = 0; k < b->ncls && slim_ok; k++) slim_ok = hx_slim_tables_ok(&b->params[k], &gt) != 0;
+        const char *e = getenv("HMP3AMD_K6");
+        if (e && strcmp(e, "slim") != 0 && strcmp(e, "fat") != 0) { set_err("HMP3AMD_K6 must be 'fat' or 'slim'"); hx_batch_destroy(b); return nullptr; }
+        const bool want = e ? (strcmp(e, "slim") == 0) : (S > b->resident);
+        if (e && strcmp(e, "slim") == 0 && !slim_ok && !b->alloc1 && !b->lsf) { set_err("HMP3AMD_K6=slim: the host's tables do not have the structure k_alloc_slim derives them from"); hx_batch_destroy(b); return nullptr; }
+        if (want && slim_ok) {
+            b->slim = 1;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *) k_alloc_slim, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 6;
+            b->resident = per_cu * prop.multiProcessorCount;
+        }
+    }
+    if (b->any_dc) ALLOC(b->d_pcmf, sizeof(float) * S * max_frames * 1152 * b->nchan);
+    HIPCHKN(hipMemcpy(b->d_prm, b->params.data(), sizeof(HxParams) * b->ncls, hipMemcpyHostToDevice));
+    HIPCHKN(hipMemcpy(b->d_gt, &gt, sizeof(gt), hipMemcpyHostToDevice));
+    HIPCHKN(hipMemcpy(b->d_st, st.data(), sizeof(HxStream) * S, hipMemcpyHostToDevice));
+    HIPCHKN(hipMemset(b->d_sb, 0, sizeof(float) * S * 2 * (NG + 3) * 576));
+    HIPCHKN(hipMemset(b->d_status, 0, sizeof(int)));
+    b->lastNG = 0;
+    return b;
+}
+
+extern "C" int hx_batch_nstreams(const hx_batch *b) { return b ? b->S : 0; }
+
+// Checkpoint of one stream: its HxStream record followed by the three carried subband granules of each
+// channel.  With it a stream continues in another slot, another batch of the same configuration, another GPU or
+// after a restart exactly where it stopped (the reference's equivalent is a copy of the CMp3Enc object).
+// The blob starts with a header {magic, format version, sizeof(HxStream), fingerprint of the stream's resolved
+// configuration}: a blob from another library build (other state layout) or saved under another control is
+// refused instead of silently yielding a corrupt bitstream.
+struct HxStateHeader { unsigned magic, version, state_bytes, pad; unsigned long long cfg; };
+#define HX_STATE_MAGIC 0x53335848u      // "HX3S"
+#define HX_STATE_VERSION 3u
+static unsigned long long cfg_fingerprint(const HxParams &p)
+{
+    unsigned long long h = 1469598103934665603ull;      // FNV-1a over the echoed control and the derived frame constants
+    auto mix = [&](const void *d, size_t n) { const unsigned char *c = (const unsigned char *) d; for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; } };
+    mix(&p.ec, sizeof(p.ec));
+    const int v[] = {p.totbitrate, p.samprate, p.h_mode, p.h_id, p.nchan, p.nsb_limit, p.band_limit, p.framebytes, p.main_framebytes, p.side_bytes,
+                     p.ms_flag, p.hf_flag, p.vbr_flag, p.initialMNR, p.short_block_threshold};
+    mix(v, sizeof(v));
+    return h;
+}
+// A converting batch's blob (another magic: neither kind takes the other's) also holds the converter: a fingerprint of its
+// plan, its call count and the case-4 intermediate samples it carries.
+#define HX_STATE_MAGIC_SRC 0x43335848u  // "HX3C"
+static const size_t HX_STATE_SRC_BYTES = 2 * sizeof(long long) + 2 * HX_SRC_CARRY * sizeof(float);
+static unsigned long long plan_fingerprint(const HxSrcPlan &p)
+{
+    unsigned long long h = 1469598103934665603ull;
+    const unsigned char *c = (const unsigned char *) &p;
+    for (size_t i = 0; i < sizeof(p); i++) { h ^= c[i]; h *= 1099511628211ull; }
+    return h;
+}
+extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b)
+{
+    return (long long) (sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float) + (b && b->nsrc ? HX_STATE_SRC_BYTES : 0));
+}
+
+static int stream_state_copy(hx_batch *b, int i, void *host, bool save)
+{
+    if (!b || i < 0 || i >= b->S || !host) { set_err("bad arguments"); return -1; }
+    if (drain(b) != 0) return -1;
+    HxStateHeader hd = {b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC, HX_STATE_VERSION, (unsigned) sizeof(HxStream), 0, cfg_fingerprint(b->params[b->cls_of[i]])};
+    char *h = (char *) host + sizeof(HxStateHeader);
+    const size_t per = (size_t) (2 * b->maxF + 3) * 576;        // floats per (stream, channel) in the subband buffer
+    char *hs = h + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float);    // the converter's part (converting batches)
+    const unsigned long long pfp = b->nsrc ? plan_fingerprint(b->src_plans[b->src_cls[i]]) : 0;
+    if (save) memcpy(host, &hd, sizeof(hd));
+    else {
+        HxStateHeader in;
+        memcpy(&in, host, sizeof(in));
+        if ((in.magic == HX_STATE_MAGIC) != (hd.magic == HX_STATE_MAGIC) && (in.magic == HX_STATE_MAGIC || in.magic == HX_STATE_MAGIC_SRC)) {
+            set_err(b->nsrc ? "a stream-state blob of a batch without converter: a converting batch does not take it" : "a stream-state blob of a converting batch: this batch has no converter");
+            return -1;
+        }
+        if (in.magic != hd.magic || in.version != HX_STATE_VERSION || in.state_bytes != hd.state_bytes) { set_err("not a stream-state blob of this library build"); return -1; }
+        if (in.cfg != hd.cfg) { set_err("the stream state was saved under a different configuration than slot's"); return -1; }
+        unsigned long long fp = 0;
+        if (b->nsrc) memcpy(&fp, hs, sizeof(fp));
+        if (fp != pfp) { set_err("the stream state was saved with a different converter (source format, rates or layout) than slot's"); return -1; }
+    }
+    if (b->nsrc) {
+        float *carry = b->d_src_carry + ((long long) b->src_par * b->S + i) * 2 * HX_SRC_CARRY;      // the copy the next call reads
+        if (save) {
+            memcpy(hs, &pfp, sizeof(pfp));
+            memcpy(hs + sizeof(pfp), &b->src_calls[i], sizeof(long long));
+            HIPCHK(hipMemcpy(hs + 2 * sizeof(long long), carry, 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyDeviceToHost));
+        } else {
+            memcpy(&b->src_calls[i], hs + sizeof(pfp), sizeof(long long));
+            for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &b->src_calls[i], sizeof(long long), hipMemcpyHostToDevice));
+            HIPCHK(hipMemcpy(carry, hs + 2 * sizeof(long long), 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyHostToDevice));
+        }
+    }
+    if (save) {
+        HIPCHK(hipMemcpy(h, b->d_st + i, sizeof(HxStream), hipMemcpyDeviceToHost));
+        for (int c = 0; c < 2; c++)
+            HIPCHK(hipMemcpy(h + sizeof(HxStream) + (size_t) c * 3 * 576 * sizeof(float), b->d_sb + ((size_t) i * 2 + c) * per, 3 * 576 * sizeof(float), hipMemcpyDeviceToHost));
+    } else {
+        HxStream st;
+        memcpy(&st, h, sizeof(HxStream));
+        st.cls = b->cls_of[i];      // the class index is the receiving batch's
+        HIPCHK(hipMemcpy(b->d_st + i, &st, sizeof(HxStream), hipMemcpyHostToDevice));
+        for (int c = 0; c < 2; c++)
+            HIPCHK(hipMemcpy(b->d_sb + ((size_t) i * 2 + c) * per, h + sizeof(HxStream) + (size_t) c * 3 * 576 * sizeof(float), 3 * 576 * sizeof(float), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+extern "C" int hx_batch_get_stream_state(hx_batch *b, int i, void *dst) { return stream_state_copy(b, i, dst, true); }
+extern "C" int hx_batch_set_stream_state(hx_batch *b, int i, const void *src) { return stream_state_copy(b, i, (void *) src, false); }
+
+// Start a new stream in slot i (same configuration as the slot's previous stream): the state a freshly created
+// batch would have for it - reservoir, histories, allocator feedback, subband carry - so a long-lived batch can
+// take over new inputs as old ones end.  Waits for the work in flight; the other streams are not touched.
+extern "C" int hx_batch_reset_stream(hx_batch *b, int i)
+{
+    if (!b || i < 0 || i >= b->S) { set_err("stream index out of range"); return -1; }
+    if (drain(b) != 0) return -1;
+    HxStream *st = new HxStream;
+    hx_stream_reset(&b->params[b->cls_of[i]], b->cls_of[i], st);
+    hipError_t e = hipMemcpy(b->d_st + i, st, sizeof(HxStream), hipMemcpyHostToDevice);
+    delete st;
+    if (e != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e)); return -1; }
+    const size_t per = (size_t) (2 * b->maxF + 3) * 576 * sizeof(float);     // subband slots of one (stream, channel)
+    HIPCHK(hipMemset((char *) b->d_sb + (size_t) i * 2 * per, 0, 2 * per));
+    if (b->nsrc) {      // the converter starts over too (call 0 reads no carried samples)
+        const long long zero = 0;
+        b->src_calls[i] = 0;
+        for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    }
+    return 0;
+}
+
+extern "C" long long hx_batch_out_stride(const hx_batch *b, int nframes)
+{
+    if (!b) return 0;
+    // nframes new frames plus the images of the frames still pending from earlier calls (their
+    // free space is at most the 511-byte reservoir, so a handful of frames; 4 KB covers them)
+    int maxframe = 0;
+    for (const HxParams &p : b->params) {
+        int fb = p.vbr_flag ? p.vbr_framebytes[p.ivbr_max] : p.framebytes + 1;
+        if (fb > maxframe) maxframe = fb;
+    }
+    long long n = (long long) ((b->lsf ? 2 : 1) * nframes + 2) * maxframe + 4096;
+    return (n + 255) & ~255LL;
+}
+
+extern "C" void hx_batch_packet_buffers(hx_batch *b, unsigned char *d_packet, long long frame_stride, int *d_packet_bytes)
+{
+    b->pk_buf = d_packet; b->pk_stride = frame_stride; b->pk_bytes = d_packet_bytes;
+}
+
+extern "C" void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats) { b->frame_stats = d_stats; }
+
+extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
+{
+    b->debug = on != 0;
+    if (on && !b->d_dbg) {
+        hipSetDevice(b->device);
+        dev_alloc(b, b->d_dbg, sizeof(HxFrameDebug) * (size_t) b->S * b->maxF);
+        dev_alloc(b, b->d_xrdbg, sizeof(float) * (size_t) b->S * 2 * b->maxF * 1152);
+        dev_alloc(b, b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 2);
+        if (dev_alloc(b, b->d_prof, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS) == 0) hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS);
+    }
+}
+
+// streams, events and the second buffer set of the submit path, created at the first submit
+static int pipe_init(hx_batch *b)
+{
+    if (b->s_front) return 0;
+    int lo = 0, hi = 0;
+    HIPCHK(hipDeviceGetStreamPriorityRange(&lo, &hi));          // lo = least urgent, hi = most urgent
+    if (new_stream(b, b->s_front, lo) || new_stream(b, b->s_alloc, hi) || new_stream(b, b->s_pack, lo) || new_event(b, b->ev_in)) return -1;
+    for (int i = 0; i < 2; i++)
+        if (new_event(b, b->ev_front[i]) || new_event(b, b->ev_alloc[i]) || new_event(b, b->ev_k6[i])) return -1;
+    for (int i = 0; i < 3; i++) if (new_event(b, b->ev_sgn[i])) return -1;
+    return alloc_set(b, 1);
+}
+
+int check_poisoned(const hx_batch *b)
+{
+    if (b->poisoned) { set_err("the batch is unusable after a failed device call: destroy it"); return -1; }
+    return 0;
+}
+int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (nframes <= 0 || nframes > b->maxF) { set_err("nframes out of range (1 .. max_frames of hx_batch_create)"); return -1; }
+    if (!in || !out || !out_bytes) { set_err("null buffer"); return -1; }
+    if (out_stride < hx_batch_out_stride(b, nframes)) { set_err("out_stride is smaller than hx_batch_out_stride(b, nframes)"); return -1; }
+    return 0;
+}
+// (a converting batch takes its input through hx_batch_encode_src_* only: a plain call would advance the encoder past its converter)
+int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
+{
+    if (b && b->nsrc) { set_err("a converting batch takes its input through hx_batch_encode_src_*"); return -1; }
+    return check_args(b, pcm, nframes, out, out_stride, out_bytes);
+}
+
+// the packing kernels of one call on stream qp (see place_pack)
+static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride, int *d_out_bytes, int nframes, int set, int sset, hipStream_t qp)
+{
+    const int S = b->S, NG = 2 * nframes;
+    const WalkSet &w = b->walk[set];
+    const unsigned *sgn = b->sgn[sset];
+    const int fps = (b->lsf ? 2 : 1) * nframes;
+    const long long total = (long long) S * fps;
+    // a handful of frames in all (the one-stream encoder's calls): one workgroup does the three kernels' work (hx_pack.hip, solo)
+    const int solo = (S <= 4 && total <= 8) ? S : 0;
+    if (solo) {
+        LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
+               d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, d_out_bytes, w.carry_len, b->cap_frames,
+               (solo == 1) ? b->cap_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
+        return 0;
+    }
+    LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, w.pre_len);
+    LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
+           d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
+    LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, d_out_bytes, w.carry_len, b->cap_frames);
+    return 0;
+}
+
+// A gate on stream q: what follows it there starts in the tail of the allocator launch whose first workgroup took number
+// `base` of the started-counter (it wraps with the counter), not at that launch's start.
+static int launch_gate(hx_batch *b, hipStream_t q, unsigned base)
+{
+    if (b->gate_percent <= 0) return 0;
+    const long long fill = b->S < b->resident ? b->S : b->resident;     // workgroups of that launch the device holds at once
+    LAUNCH(k_gate, dim3(1), dim3(64), q, (const unsigned *) (b->d_done + HX_CNT_STARTED), base, (unsigned) (fill * b->gate_percent / 100), b->d_done + HX_CNT_GATE_TIMEOUTS);
+    return 0;
+}
+
+// the deferred packing of the latest submit: out now, on the packing stream; gate_base >= 0: behind a gate on the allocator launch
+// that was just enqueued (the one after the job's own)
+static int flush_pack(hx_batch *b, long long gate_base)
+{
+    hx_batch::PackJob &j = b->pack_job;
+    if (!j.pending) return 0;
+    j.pending = false;
+    HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
+    if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
+    if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
+    HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
+    HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
+    return 0;
+}
+
+// One pass of the pipeline over the batch, as phases in the order they run.  What a phase leaves for the later ones:
+struct Pass {
+    PcmIn in; int nframes; unsigned char *d_out; long long out_stride; int *d_out_bytes; PassKind kind;       // the call
+    hipStream_t q, qa;                  // streams of the front end / of the stream walk and (unless deferred) the packing
+    int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
+                                        // submit n-2 when the front end of submit n writes them: three sets in rotation)
+    int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
+};
+
+// make stream q wait for everything submitted so far, the deferred packing included
+static int order_behind_submits(hx_batch *b, hipStream_t q)
+{
+    if (flush_pack(b, -1) != 0) return -1;
+    const int last = (int) ((b->nsubmit - 1) & 1);
+    HIPCHK(hipStreamWaitEvent(q, b->ev_front[last], 0));
+    HIPCHK(hipStreamWaitEvent(q, b->ev_alloc[last], 0));
+    return 0;
+}
+
+// event ordering on entry: a submit moves to the batch's own streams behind the calls that hold its buffer sets and a
+// gate; a plain call behind submits is ordered after them
+static int pipe_enter(hx_batch *b, Pass &p)
+{
+    if (p.kind != PASS_PLAIN) {
+        if (pipe_init(b) != 0) return -1;
+        if (p.kind == PASS_SUBMIT_HOST && b->pack_job.pending) {    // (a host-buffer submit behind device-buffer ones)
+            p.flushed_set = b->pack_job.set;
+            if (flush_pack(b, -1) != 0) return -1;
+        }
+        p.set = (int) (b->nsubmit & 1);
+        p.sset = (int) (b->nsubmit % 3);
+        HIPCHK(hipEventRecord(b->ev_in, p.q));                      // the caller's PCM is ready from here on
+        HIPCHK(hipStreamWaitEvent(b->s_front, b->ev_in, 0));
+        if (b->nsubmit >= 2) HIPCHK(hipStreamWaitEvent(b->s_front, b->ev_k6[p.set], 0));      // k_alloc of submit n-2 is done with this set
+        if (b->nsubmit >= 3) HIPCHK(hipStreamWaitEvent(b->s_front, b->ev_sgn[p.sset], 0));    // ... and the packing of submit n-3 with this set of signs
+        p.q = b->s_front; p.qa = b->s_alloc;
+        // (the front end starts in the previous allocator kernel's tail)
+        if (b->alloc_launches > 0 && launch_gate(b, p.q, (unsigned) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S)) != 0) return -1;
+    } else if (b->inflight) {                                       // a plain call behind submits
+        if (order_behind_submits(b, p.q) != 0) return -1;
+        b->inflight = false;
+    }
+    return 0;
+}
+
+// the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]
+static int launch_front(hx_batch *b, const Pass &p)
+{
+    const FrontSet &f = b->front[p.set];
+    const hipStream_t q = p.q;
+    const int S = b->S, nframes = p.nframes, NG = 2 * nframes;
+    const long long nsamp = 1152LL * nframes;
+    const int16_t *d_pcm = p.in.f32 ? nullptr : (const int16_t *) p.in.p;
+    const float *d_pcm32 = p.in.f32 ? (const float *) p.in.p : nullptr;
+    // The subband carry sits in slots NG_prev..NG_prev+2 only if the previous call used another
+    // frame count; k_msscan always rolls it to slots 0..2, so nothing to do here.
+    dim3 g1(S, (NG + K1_GPB - 1) / K1_GPB);
+    const int SG = 2 * b->maxF + 3;     // subband slots per (stream, channel): fixed layout
+    const float *pcmf = b->any_dc ? b->d_pcmf : d_pcm32;       // fp32 samples the polyphase reads, or null for int16
+    if (b->any_dc) LAUNCH(k_dcfilter, dim3((b->nchan * S + 63) / 64), dim3(64), q, d_pcm, d_pcm32, nsamp, b->d_st, b->d_prm, b->d_pcmf, S, b->nchan);
+    // (the carry in slots 0..2 is not written by k_polyphase, so the two may run in either order)
+    // (the detector energies of the carried granule are formed by k_polyphase's first tile of a stream, the carries rolled by
+    // k_msscan, flags and block types by one kernel - round 6: three launches less per call, which is what a one-stream call
+    // is made of)
+    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf);
+    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf);
+    // (the form of K4 that goes with the stream-walk kernel: hx_front.hip, spec_granule)
+    if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
+    else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
+    // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
+    // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
+    // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
+    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->lsf, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan);
+    LAUNCH(k_prep, dim3((unsigned) (((long long) S * NG + 3) / 4)), dim3(256), q, f.xr, (b->debug && b->d_xrdbg) ? b->d_xrdbg : (float *) nullptr, b->debug ? f.x34 : (float *) nullptr,
+           b->sgn[p.sset], f.band, b->d_st, b->d_prm, b->d_gt, f.bt, f.msflag, f.etab, f.thr, f.thrprev, NG, (long long) S * NG);
+    return 0;
+}
+
+// a submit's hand-over from the front-end stream to the stream walk's
+static int pipe_front_done(hx_batch *b, const Pass &p)
+{
+    HIPCHK(hipEventRecord(b->ev_front[p.set], p.q));
+    HIPCHK(hipStreamWaitEvent(p.qa, b->ev_front[p.set], 0));
+    if (b->nsubmit >= 2) HIPCHK(hipStreamWaitEvent(p.qa, b->ev_alloc[p.set], 0));     // the packing of submit n-2 is done with the lines / records of this set
+    // A caller that hands consecutive submits the same output buffers gets them one after the other: the previous
+    // submit's packing (which writes and reads its `out`) then has to be through before this allocator launch
+    // starts putting headers into it.  Alternate two sets of output buffers to have them overlap.
+    const hx_batch::PackJob &j = b->pack_job;
+    if (j.pending) {
+        const unsigned char *o0 = j.d_out, *o1 = j.d_out + (long long) b->S * j.out_stride, *n0 = p.d_out, *n1 = p.d_out + (long long) b->S * p.out_stride;
+        const char *b0 = (const char *) j.d_out_bytes, *b1 = b0 + sizeof(int) * (size_t) b->S, *m0 = (const char *) p.d_out_bytes, *m1 = m0 + sizeof(int) * (size_t) b->S;
+        if ((o0 < n1 && n0 < o1) || (b0 < m1 && m0 < b1)) {
+            const int js = j.set;
+            if (flush_pack(b, -1) != 0) return -1;
+            HIPCHK(hipStreamWaitEvent(p.qa, b->ev_alloc[js], 0));
+        }
+    }
+    return 0;
+}
+
+// the stream walk's arguments; with the longest-first order (see hx_batch::lpt), the kernel that sorts the streams
+static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
+{
+    const FrontSet &f = b->front[p.set];
+    const WalkSet &w = b->walk[p.set];
+    unsigned *const sgn = b->sgn[p.sset];
+    const int S = b->S;
+    a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
+    a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = p.d_out; a.out_bytes = p.d_out_bytes;
+    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = p.out_stride; a.NG = 2 * p.nframes; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
+    a.packet = b->pk_buf; a.packet_stride = b->pk_stride; a.packet_bytes = b->pk_bytes; a.frame_stats = b->frame_stats;
+    a.done_counter = b->d_done;
+    a.strict_sums = b->strict_sums;
+    a.dur = b->d_dur;
+    a.order = nullptr;
+    a.park_k = 0;
+    if ((S > b->resident && b->lpt) || (b->lpt == 2 && S > b->ncu) || b->lpt == 3) {
+        LAUNCH(k_order, dim3(1), dim3(1024), p.qa, (const unsigned *) b->d_dur, b->d_order, S);
+        a.order = b->d_order;
+        // parking (hx_alloc3.inc): only when every stream has a slot from the launch's start - beyond the resident set a
+        // parked slot would keep a waiting stream out - and from the second call on (the order is the previous call's)
+        if (S <= b->resident && b->alloc_launches > 0 && !b->alloc1 && !b->lsf) a.park_k = (b->park_k < S / 8 ? b->park_k : S / 8) | (b->park_pair << 16);
+    }
+    a.x34 = f.x34; a.sgn = sgn; a.band = f.band; a.msflag = f.msflag; a.msdec = f.msdec; a.thrprev = f.thrprev;
+    a.ixq = w.ixq; a.sgn_w = sgn; a.seg = w.seg; a.frm = w.frm; a.slots = w.slots;
+    a.pre_len = w.pre_len; a.carry_len = w.carry_len;
+    return 0;
+}
+
+// the stream walk, between two timing events (hx_batch_alloc_kernel_ms) unless the pass is being recorded
+static int launch_walk(hx_batch *b, const Pass &p, const AllocArgs &a)
+{
+    const hipStream_t qa = p.qa;
+    const int S = b->S;
+    b->alloc_launches++;
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (!b->capturing) {
+        HIPCHK(hipEventCreate(&e0));
+        HIPCHK(hipEventCreate(&e1));
+        HIPCHK(hipEventRecord(e0, qa));
+    }
+    // persistent workgroups: as many as the chip holds at once (or one per stream if that is fewer); each walks one stream of
+    // the launch order after the other (hx_alloc3.inc)
+    // (built into k_alloc_slim, the kernel of batches beyond the resident set; the 256-register kernels keep one workgroup per stream)
+    const int G = (b->slim && !b->alloc1 && !b->lsf && S > b->resident) ? b->resident : S;
+    if (b->alloc1) { if (b->lsf) LAUNCH(k_alloc1_lsf, dim3(G), dim3(128), qa, a); else LAUNCH(k_alloc1, dim3(G), dim3(128), qa, a); }
+    else if (b->lsf) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, a);
+    else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, a);
+    else LAUNCH(k_alloc, dim3(G), dim3(128), qa, a);
+    if (!b->capturing) {
+        HIPCHK(hipEventRecord(e1, qa));
+        b->pending.push_back({e0, e1});
+    }
+    return 0;
+}
+
+// Every frame of the call packed at once, between the pending frames' images coming out of the stream state and the
+// incomplete ones' going back in.  A plain call (and a host-buffer submit) packs right behind its allocator launch.  A
+// device-buffer submit leaves its packing for later: it is enqueued on a stream of its own behind the NEXT submit's
+// allocator launch and a gate on it, and so runs - like that submit's successor's front end - in that launch's tail
+// instead of between two allocator launches.
+static int place_pack(hx_batch *b, const Pass &p)
+{
+    const hipStream_t qa = p.qa;
+    if (p.kind == PASS_SUBMIT_DEVICE) {
+        HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
+        if (flush_pack(b, (long long) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S)) != 0) return -1;   // the previous submit's
+        hx_batch::PackJob &j = b->pack_job;
+        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
+        return 0;
+    }
+    if (p.kind != PASS_PLAIN) HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
+    // the previous device-buffer submit's packing went out on the packing stream in pipe_enter: its k_pack_carry writes
+    // the carried frame images that this call's k_pack_pre reads
+    if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
+    if (enqueue_pack(b, p.d_out, p.out_stride, p.d_out_bytes, p.nframes, p.set, p.sset, qa) != 0) return -1;
+    if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
+    return 0;
+}
+
+// the time between a stream walk's two events (both done), into the batch's sum
+static void take_timing(hx_batch *b, const std::pair<hipEvent_t, hipEvent_t> &pr)
+{
+    float ms = 0;
+    if (hipEventElapsedTime(&ms, pr.first, pr.second) == hipSuccess) { b->alloc_ms_sum += ms; b->alloc_calls++; }
+    hipEventDestroy(pr.first);
+    hipEventDestroy(pr.second);
+}
+// a caller that never asks for the timings must not accumulate events
+static void reap_timings(hx_batch *b)
+{
+    while (b->pending.size() > 512 && hipEventQuery(b->pending.front().second) == hipSuccess) {
+        take_timing(b, b->pending.front());
+        b->pending.erase(b->pending.begin());
+    }
+}
+
+int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
+{
+    Poison poison{b};
+    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream};
+    AllocArgs a;
+    HIPCHK(hipSetDevice(b->device));
+    if (pipe_enter(b, p) != 0 || launch_front(b, p) != 0) return -1;
+    if (kind != PASS_PLAIN && pipe_front_done(b, p) != 0) return -1;
+    if (fill_alloc_args(b, p, a) != 0 || launch_walk(b, p, a) != 0 || place_pack(b, p) != 0) return -1;
+    if (!b->capturing) reap_timings(b);
+    if (kind != PASS_PLAIN) {
+        b->nsubmit++;
+        b->inflight = true;
+    }
+    HIPCHK(hipGetLastError());
+    b->lastNG = 2 * nframes;
+    return poison.ok();
+}
+int encode_checked(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
+{
+    if (check_call(b, in.p, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
+    return encode_pass(b, in, nframes, d_out, out_stride, d_out_bytes, stream, kind);
+}
+
+extern "C" int hx_batch_encode_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
+                                          long long out_stride, int *d_out_bytes, void *stream)
+{
+    return encode_checked(b, {d_pcm, false}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN);
+}
+
+extern "C" int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
+                                          long long out_stride, int *d_out_bytes, void *stream)
+{
+    return encode_checked(b, {d_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN);
+}
+
+// Pipelined form of the device calls.  A submit returns at once like the plain call, but its output
+// (d_out, d_out_bytes) is ordered on the caller's stream only by a later hx_batch_wait (or by the next
+// plain call / host-buffer call on the batch).  The PCM must be ready on `stream` at the submit, and
+// d_pcm must stay unchanged until the submit's front end has run (hx_batch_wait covers that too).
+// Consecutive submits overlap: the front end of call n+1 fills the SIMDs that k_alloc of call n
+// leaves idle while its slowest streams finish.
+extern "C" int hx_batch_submit_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
+                                          long long out_stride, int *d_out_bytes, void *stream)
+{
+    return encode_checked(b, {d_pcm, false}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_SUBMIT_DEVICE);
+}
+
+extern "C" int hx_batch_submit_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
+                                          long long out_stride, int *d_out_bytes, void *stream)
+{
+    return encode_checked(b, {d_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_SUBMIT_DEVICE);
+}
+
+// share (percent) of the previous allocator launch's resident workgroups that must have started before a submit's front end is released; 0 = no gate
+extern "C" void hx_batch_set_gate(hx_batch *b, int percent) { if (b) b->gate_percent = percent < 0 ? 0 : (percent > 100 ? 100 : percent); }
+
+extern "C" int hx_batch_wait(hx_batch *b, void *stream)
+{
+    if (!b || check_poisoned(b) != 0) return -1;
+    if (!b->inflight) return 0;
+    Poison poison{b};                   // (the deferred packing may be half enqueued)
+    HIPCHK(hipSetDevice(b->device));
+    if (order_behind_submits(b, (hipStream_t) stream) != 0) return -1;
+    return poison.ok();
+}
+
+// ---- pipelined host-buffer calls ----
+// The PCM of call n+1 crosses PCIe while call n is encoded, and the bitstream of call n while call
+// n+1 is: two sets of device staging buffers, one stream per copy direction, events in between.
+// Truly asynchronous only with page-locked host memory (hx_pinned_alloc); with pageable memory the
+// copies fall back to staged, mostly synchronous transfers and the result is still correct.
+extern "C" void *hx_pinned_alloc(long long bytes)
+{
+    void *p = nullptr;
+    if (bytes <= 0 || hipHostMalloc(&p, (size_t) bytes, hipHostMallocDefault) != hipSuccess) return nullptr;
+    return p;
+}
+extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
+
+static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    if (check_call(b, in.p, nframes, out, out_stride, out_bytes) != 0) return -1;
+    Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
+    HIPCHK(hipSetDevice(b->device));
+    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t)), obytes = (long long) b->S * out_stride;
+    if (!b->s_h2d) {
+        if (new_stream(b, b->s_h2d) || new_stream(b, b->s_d2h) || new_stream(b, b->s_host)) return -1;
+        for (int i = 0; i < 2; i++)
+            if (new_event(b, b->ev_h2d[i]) || new_event(b, b->ev_d2h[i]) || new_event(b, b->ev_hfront[i]) || dev_alloc(b, b->hs_nb[i], sizeof(int) * b->S)) return -1;
+    }
+    if (pbytes > b->hs_pcm_cap || obytes > b->hs_out_cap) {     // (re)size the staging: drain first
+        if (drain(b) != 0) return -1;
+        for (int i = 0; i < 2; i++) {
+            if (pbytes > b->hs_pcm_cap && dev_realloc(b, b->hs_pcm[i], pbytes) != 0) return -1;
+            if (obytes > b->hs_out_cap && dev_realloc(b, b->hs_out[i], obytes) != 0) return -1;
+        }
+        if (pbytes > b->hs_pcm_cap) b->hs_pcm_cap = pbytes;
+        if (obytes > b->hs_out_cap) b->hs_out_cap = obytes;
+    }
+    const int k = (int) (b->nhost & 1);
+    if (b->nhost >= 2) {
+        HIPCHK(hipStreamWaitEvent(b->s_h2d, b->ev_hfront[k], 0));   // the front end of call n-2 has read this PCM buffer
+        HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_d2h[k], 0));     // the bitstream of call n-2 has left this output buffer
+    }
+    HIPCHK(hipMemcpyAsync(b->hs_pcm[k], in.p, (size_t) pbytes, hipMemcpyHostToDevice, b->s_h2d));
+    HIPCHK(hipEventRecord(b->ev_h2d[k], b->s_h2d));
+    HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_h2d[k], 0));
+    const int set = (int) (b->nsubmit & 1);
+    if (encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, b->hs_out[k], out_stride, b->hs_nb[k], b->s_host, PASS_SUBMIT_HOST) != 0) return -1;
+    HIPCHK(hipEventRecord(b->ev_hfront[k], b->s_front));
+    HIPCHK(hipStreamWaitEvent(b->s_d2h, b->ev_alloc[set], 0));
+    HIPCHK(hipMemcpyAsync(out_bytes, b->hs_nb[k], sizeof(int) * b->S, hipMemcpyDeviceToHost, b->s_d2h));
+    HIPCHK(hipMemcpyAsync(out, b->hs_out[k], (size_t) obytes, hipMemcpyDeviceToHost, b->s_d2h));
+    HIPCHK(hipEventRecord(b->ev_d2h[k], b->s_d2h));
+    b->nhost++;
+    return poison.ok();
+}
+
+extern "C" int hx_batch_submit_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    return submit_host(b, {pcm, false}, nframes, out, out_stride, out_bytes);
+}
+
+extern "C" int hx_batch_submit_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    return submit_host(b, {pcm, true}, nframes, out, out_stride, out_bytes);
+}
+
+// block until the outputs of every submitted host call are in host memory
+extern "C" int hx_batch_wait_host(hx_batch *b)
+{
+    if (!b || check_poisoned(b) != 0) return -1;
+    if (hipSetDevice(b->device) != hipSuccess || (b->s_d2h && (hipStreamSynchronize(b->s_front) != hipSuccess || hipStreamSynchronize(b->s_d2h) != hipSuccess))) {
+        set_err("HIP error while waiting for the host-buffer calls");
+        b->poisoned = true;
+        return -1;
+    }
+    return 0;
+}
+
+extern "C" float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls)
+{
+    hipSetDevice(b->device);
+    for (auto &pr : b->pending) {
+        hipEventSynchronize(pr.second);
+        take_timing(b, pr);
+    }
+    b->pending.clear();
+    float mean = b->alloc_calls ? (float) (b->alloc_ms_sum / b->alloc_calls) : 0.0f;
+    if (ncalls) *ncalls = b->alloc_calls;
+    b->alloc_ms_sum = 0;
+    b->alloc_calls = 0;
+    return mean;
+}
+
+// the host-buffer PCM calls (host_call; the staging is not waited for before the upload: these calls end drained).
+// With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer).
+int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats)
+{
+    if (check_call(b, in.p, nframes, out, out_stride, out_bytes) != 0) return -1;
+    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
+    return host_call(b, in.p, pbytes, false, nframes, out, out_stride, out_bytes, stats, [&] {
+        return encode_pass(b, {b->d_in, in.f32}, nframes, b->d_out, out_stride, b->d_outbytes, nullptr, PASS_PLAIN);
+    });
+}
+
+extern "C" int hx_batch_encode_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out,
+                                        long long out_stride, int *out_bytes)
+{
+    return encode_host(b, {pcm, false}, nframes, out, out_stride, out_bytes, nullptr);
+}
+
+extern "C" int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
+                                              long long out_stride, int *out_bytes, int *stats)
+{
+    if (!stats) { set_err("null buffer"); return -1; }
+    return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, stats);
+}
+
+extern "C" int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
+                                        long long out_stride, int *out_bytes)
+{
+    return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, nullptr);
+}
+
+extern "C" int hx_batch_status(hx_batch *b)
+{
+    int v = -1;
+    if (!b) return -1;
+    if (b->poisoned) return -1;
+    if (drain(b) != 0) return -1;       // (the last device-buffer submit's packing: it writes that submit's output buffers)
+    // (a gate that gave up waiting costs overlap, not correctness: it is counted in hx_batch_gate_timeouts, not here)
+    if (hipMemcpy(&v, b->d_status, sizeof(int), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return v;
+}
+
+// which build of the stream walk the batch runs: 0 = k_alloc (or the MPEG-2 / first-generation kernels), 1 = k_alloc_slim;
+// streams resident at once on the device
+extern "C" int hx_batch_k6_variant(const hx_batch *b) { return b ? b->slim : -1; }
+extern "C" int hx_batch_resident_streams(const hx_batch *b) { return b ? b->resident : -1; }
+
+// submits whose front end started late because its gate gave up waiting (see hx_batch_set_gate); synchronises
+extern "C" int hx_batch_gate_timeouts(hx_batch *b)
+{
+    int v[HX_CNT_GATE_TIMEOUTS + 1] = {};
+    if (!b) return -1;
+    if (drain(b) != 0) return -1;
+    if (hipMemcpy(v, b->d_done, sizeof(v), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+    return v[HX_CNT_GATE_TIMEOUTS];
+}
+
+extern "C" HX_INT_PAIR hx_batch_frames_bytes(hx_batch *b, int i)
+{
+    HX_INT_PAIR r = {0, 0};
+    if (!b || i < 0 || i >= b->S) return r;
+    (void) drain(b);
+    unsigned v[2];
+    hipMemcpy(&v[0], (char *) (b->d_st + i) + offsetof(HxStream, tot_frames_out), 4, hipMemcpyDeviceToHost);
+    hipMemcpy(&v[1], (char *) (b->d_st + i) + offsetof(HxStream, tot_bytes_out), 4, hipMemcpyDeviceToHost);
+    r.a = (int) v[0]; r.b = (int) v[1];
+    return r;
+}
+
+extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap)
+{
+    if (!b || !name || !dst) return -1;
+    (void) drain(b);
+    const long long S = b->S, NG = b->lastNG;
+    const FrontSet &f = b->front[0];
+    const WalkSet &w = b->walk[0];
+    const void *src = nullptr;
+    long long n = 0;
+    std::string k(name);
+    if (k == "sb") { src = b->d_sb; n = sizeof(float) * S * 2 * (2LL * b->maxF + 3) * 576; }
+    else if (k == "xr") { src = f.xr; n = sizeof(float) * S * NG * 1152; }       // the spectrum
+    else if (k == "xmag") { src = b->d_xrdbg; n = sizeof(float) * S * NG * 1152; }  // the magnitudes k_prep works on (written in debug mode only)
+    else if (k == "x34") { src = f.x34; n = sizeof(float) * S * NG * 1152; }
+    else if (k == "band") { src = f.band; n = sizeof(HxBandPrep) * S * NG; }
+    else if (k == "msflag") { src = f.msflag; n = S * NG; }
+    else if (k == "ixq") { src = w.ixq; n = sizeof(short) * S * NG * 1152; }
+    else if (k == "sgn") { src = b->sgn[0]; n = (long long) sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS; }      // one bit per line, HX_SGN_WORDS words per (granule, channel)
+    else if (k == "seg") { src = w.seg; n = sizeof(HxSegOut) * S * NG * 2; }
+    else if (k == "frm") { src = w.frm; n = sizeof(HxFrameOut) * S * NG; }
+    else if (k == "etab") { src = f.etab; n = sizeof(float) * S * NG * 128; }
+    else if (k == "thr") { src = f.thr; n = sizeof(float) * S * NG * 128; }
+    else if (k == "msbase") { src = f.msbase; n = sizeof(int) * S * NG; }
+    else if (k == "place") { src = b->d_dur + S; n = sizeof(unsigned) * S; }       // per WORKGROUP of the last allocator launch (launch order): XCC id << 16 | HW_ID[15:0] (CU [11:8], SH [12], SE [15:13])
+    else if (k == "dur") { src = b->d_dur; n = sizeof(unsigned) * S; }              // the last allocator launch's per-stream durations, 100 MHz ticks
+    else if (k == "big_sweeps") { src = b->d_done + HX_CNT_BIG_SWEEPS; n = sizeof(int); }        // gain-search line passes that took the double x^(4/3) table
+    else if (k == "strict_sums") { src = b->d_done + HX_CNT_STRICT_SUMS; n = sizeof(int); }       // certified band sums that fell back to the strict line-order sum
+    else if (k == "bt") { src = f.bt; n = S * NG; }
+    else if (k == "eng") { src = b->d_eng; n = sizeof(int) * S * 2 * NG * 9; }
+    else if (k == "dbg" && b->d_dbg) { src = b->d_dbg; n = sizeof(HxFrameDebug) * S * (NG / 2); }
+    else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
+    else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
+    else if (k == "srcpcm" && b->d_src_pcm) { src = b->d_src_pcm; n = sizeof(float) * S * b->src_lastF * 1152 * b->nchan; }   // the converted PCM of the last call
+    else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 2; }
+    if (!src) return -1;
+    if (n > cap) n = cap;
+    hipMemcpy(dst, src, (size_t) n, hipMemcpyDeviceToHost);
+    return n;
+}
+

@@ -1,0 +1,185 @@
+// hx_batch_src.hip - converting batches: every stream's source goes through its converter on the GPU (k_src, hx_src.inc)
+// into fp32 PCM at the encode rate, which the fp32 path encodes.  The host keeps each stream's converter call count: every
+// phase of the converter is a closed form of it (hx_src.h), so the host knows each call's input extent without converting
+// anything.
+#include <string>
+#include "hx_rt.h"
+
+extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, const HX_SOURCE *src,
+                                         int shared_source, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
+    std::vector<HX_E_CONTROL> ecs(nstreams);
+    std::vector<HxSrcPlan> plans;
+    std::vector<int> cls(nstreams);
+    hx_src *conv = hx_src_create();
+    for (int s = 0; s < nstreams; s++) {
+        const HX_SOURCE &sc = shared_source ? src[0] : src[s];
+        HxSrcPlan p;
+        if (!src_encode_control(shared_control ? ec : ec + s, sc.bits, sc.is_float, sc.mpeg_select, sc.mono_convert, conv, &ecs[s]) ||
+            !hx_src_plan(conv, &p)) {
+            char msg[64];
+            snprintf(msg, sizeof msg, "stream %d: ", s);
+            const std::string why = hx_last_error();
+            set_err("%s", (msg + why).c_str());
+            hx_src_destroy(conv);
+            return nullptr;
+        }
+        int k = -1;
+        for (size_t i = 0; i < plans.size(); i++) if (memcmp(&plans[i], &p, sizeof(p)) == 0) { k = (int) i; break; }
+        if (k < 0) { plans.push_back(p); k = (int) plans.size() - 1; }
+        cls[s] = k;
+    }
+    hx_src_destroy(conv);
+    hx_batch *b = hx_batch_create(device, nstreams, ecs.data(), 0, max_frames);
+    if (!b) return nullptr;
+    b->nsrc = (int) plans.size();
+    b->src_plans = plans;
+    b->src_cls = cls;
+    b->src_calls.assign(nstreams, 0);
+    // LDS of a workgroup: the input window (source channels, interleaved), the intermediate samples (output channels,
+    // case 4) and the filter bank (cases 2 - 4), each sized for the batch's largest plan
+    int xf = 0, zf = 0, cf = 0;
+    for (const HxSrcPlan &p : plans) {
+        if (p.nch != b->nchan) { set_err("a converter's output channels differ from the batch's"); hx_batch_destroy(b); return nullptr; }
+        if (p.xwin > b->src_xwin) b->src_xwin = p.xwin;
+        if (p.zwin > b->src_zwin) b->src_zwin = p.zwin;
+        xf = std::max(xf, p.channels * p.xwin);
+        zf = std::max(zf, p.nch * p.zwin);
+        if (p.ncase >= 2) cf = std::max(cf, p.totcoef);
+    }
+    b->src_zoff = xf;
+    b->src_coff = xf + zf;
+    b->src_lds = sizeof(float) * ((size_t) xf + zf + cf);
+    if (b->src_lds > 160 * 1024) { set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr; }
+    if (b->src_lds > 64 * 1024 && hipFuncSetAttribute((const void *) k_src, hipFuncAttributeMaxDynamicSharedMemorySize, (int) b->src_lds) != hipSuccess) {
+        set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr;
+    }
+    const long long S = nstreams;
+#define ALLOC_SRC(ptr, bytes) do { if (dev_alloc(b, ptr, bytes) != 0) { hx_batch_destroy(b); return nullptr; } } while (0)
+    ALLOC_SRC(b->d_src_plan, sizeof(HxSrcPlan) * plans.size());
+    ALLOC_SRC(b->d_src_cls, sizeof(int) * S);
+    ALLOC_SRC(b->d_src_calls, sizeof(long long) * 2 * S);
+    ALLOC_SRC(b->d_src_carry, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY);
+    ALLOC_SRC(b->d_src_pcm, sizeof(float) * S * max_frames * 1152 * b->nchan);
+    ALLOC_SRC(b->d_src_off, sizeof(long long) * S * max_frames);
+#undef ALLOC_SRC
+    if (hipHostMalloc((void **) &b->h_src_off, sizeof(long long) * S * max_frames, 0) != hipSuccess) { b->h_src_off = nullptr; set_err("hipHostMalloc failed"); hx_batch_destroy(b); return nullptr; }
+    if (new_event(b, b->ev_src_off) != 0 ||
+        hipMemcpy(b->d_src_plan, plans.data(), sizeof(HxSrcPlan) * plans.size(), hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_src_cls, cls.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemset(b->d_src_calls, 0, sizeof(long long) * 2 * S) != hipSuccess ||
+        hipMemset(b->d_src_carry, 0, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY) != hipSuccess ||
+        hipEventRecord(b->ev_src_off, nullptr) != hipSuccess) {
+        set_err("HIP error while setting up the converter");
+        hx_batch_destroy(b);
+        return nullptr;
+    }
+    return b;
+}
+
+extern "C" long long hx_batch_src_schedule(const hx_batch *b, int i, int nframes, long long *in_bytes)
+{
+    if (!b || !b->nsrc || i < 0 || i >= b->S || nframes < 0) { set_err("bad arguments (or not a converting batch)"); return -1; }
+    return hx_src_plan_schedule(&b->src_plans[b->src_cls[i]], b->src_calls[i], nframes, in_bytes);
+}
+
+extern "C" long long hx_batch_src_in_stride(const hx_batch *b, int nframes)
+{
+    if (!b || !b->nsrc || nframes < 0) return 0;
+    long long n = 0;
+    for (const HxSrcPlan &p : b->src_plans) {
+        const long long v = ((long long) nframes * p.cmax + p.xwin) * p.channels * (p.bits / 8);
+        if (v > n) n = v;
+    }
+    return (n + 255) & ~255LL;
+}
+
+// argument checks of the converting calls
+static int src_check(const hx_batch *b, const void *in, long long in_stride, int nframes, const void *out, long long out_stride, const void *out_bytes)
+{
+    if (b && !b->nsrc) { set_err("not a converting batch (hx_batch_create_src)"); return -1; }
+    if (check_args(b, in, nframes, out, out_stride, out_bytes) != 0) return -1;
+    if (in_stride <= 0) { set_err("in_stride must be positive"); return -1; }
+    return 0;
+}
+
+// one converting call on device buffers (arguments checked by the caller): k_src into d_src_pcm, then the fp32 pass over it
+static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off, int nframes,
+                      unsigned char *d_out, long long out_stride, int *d_out_bytes, long long *in_used, void *stream)
+{
+    // every call's input extent from the schedule, checked against the row before anything runs.  Consecutive calls: the
+    // consumption telescopes, and the last call reaches furthest (a call reads at most ntaps - k past its successor's
+    // start, and the last one reads at least ntaps), so one closed form per stream; with offsets every call is checked.
+    const int S = b->S;
+    std::vector<long long> used_end(S);
+    for (int s = 0; s < S; s++) {
+        const HxSrcPlan &p = b->src_plans[b->src_cls[s]];
+        const long long fb = (long long) p.channels * (p.bits / 8), c0 = b->src_calls[s];
+        long long used, rd;
+        int bad = -1;
+        long long off = 0;
+        if (!frame_off) {
+            off = hx_src_consumed(&p, c0, c0 + nframes - 1) * fb;
+            hx_src_call_extent(&p, c0 + nframes - 1, &used, &rd);
+            if (off + rd * fb > in_stride) bad = nframes - 1;
+        } else {
+            for (int f = 0; f < nframes && bad < 0; f++) {
+                off = frame_off[(long long) s * nframes + f];
+                hx_src_call_extent(&p, c0 + f, &used, &rd);
+                if (off < 0 || off + rd * fb > in_stride) bad = f;
+            }
+        }
+        if (bad >= 0) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "stream %d, call %d: its input [%lld, %lld) does not fit in_stride %lld", s, bad, off, off + rd * fb, in_stride);
+            set_err("%s", msg);
+            return -1;
+        }
+        used_end[s] = off + used * fb;
+    }
+    HIPCHK(hipSetDevice(b->device));
+    hipStream_t q = (hipStream_t) stream;
+    if (frame_off) {
+        const size_t nb = sizeof(long long) * (size_t) S * nframes;
+        HIPCHK(hipEventSynchronize(b->ev_src_off));        // (the page-locked copy of the previous call's offsets is on the device)
+        memcpy(b->h_src_off, frame_off, nb);
+        HIPCHK(hipMemcpyAsync(b->d_src_off, b->h_src_off, nb, hipMemcpyHostToDevice, q));
+        HIPCHK(hipEventRecord(b->ev_src_off, q));
+    }
+    SrcArgs a;
+    a.in = d_in; a.in_stride = in_stride; a.off = frame_off ? b->d_src_off : nullptr;
+    a.plan = b->d_src_plan; a.cls = b->d_src_cls;
+    a.calls_in = b->d_src_calls + (long long) b->src_par * S; a.calls_out = b->d_src_calls + (long long) (1 - b->src_par) * S;
+    a.carry_in = b->d_src_carry + (long long) b->src_par * S * 2 * HX_SRC_CARRY;
+    a.carry_out = b->d_src_carry + (long long) (1 - b->src_par) * S * 2 * HX_SRC_CARRY;
+    a.out = b->d_src_pcm; a.nframes = nframes; a.nch = b->nchan; a.xwin = b->src_xwin; a.zwin = b->src_zwin;
+    a.zoff = b->src_zoff; a.coff = b->src_coff; a.status = b->d_status;
+    Poison poison{b};                   // (from the first launch on)
+    LAUNCH_LDS(k_src, dim3((unsigned) ((long long) S * nframes)), dim3(256), b->src_lds, q, a);
+    b->src_par ^= 1;
+    for (int s = 0; s < S; s++) b->src_calls[s] += nframes;
+    b->src_lastF = nframes;
+    if (in_used) memcpy(in_used, used_end.data(), sizeof(long long) * S);
+    if (encode_pass(b, {b->d_src_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN) != 0) return -1;
+    return poison.ok();
+}
+
+extern "C" int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
+                                          int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes,
+                                          long long *in_used, void *stream)
+{
+    if (src_check(b, d_in, in_stride, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
+    return src_encode(b, d_in, in_stride, frame_off, nframes, d_out, out_stride, d_out_bytes, in_used, stream);
+}
+
+// (host_call with a drain before the upload: the staging may still be read by an earlier call)
+extern "C" int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                        int nframes, unsigned char *out, long long out_stride, int *out_bytes,
+                                        long long *in_used, int *stats)
+{
+    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0) return -1;
+    return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&] {
+        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, b->d_out, out_stride, b->d_outbytes, in_used, nullptr);
+    });
+}

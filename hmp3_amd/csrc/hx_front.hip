@@ -24,7 +24,7 @@
 #endif
 
 #if HX_FRONT_PART & 1
-// (K1_GPB granules per workgroup, K1_THREADS lanes: hx_types.h, shared with the launch in hx_cabi.hip)
+// (K1_GPB granules per workgroup, K1_THREADS lanes: hx_types.h, shared with the launch in hx_batch.hip)
 
 #define K1_NS (480 + 576 * K1_GPB)      // staged samples
 #define K1_LDS (K1_NS + (K1_NS >> 5) + 1)
@@ -653,7 +653,7 @@ __device__ __forceinline__ void msmetric_unit(const float *x0, const float *x1, 
 // (EXPERIMENTS.md, round 4): alone on the chip the direct form is 11 % faster (configs 3 - 5, where the stream walk's
 // low-footprint kernel leaves the front end no room beside it: +3.6 / +2.7 % per step); beside the resident stream walk of
 // config 2 it is 0.7 % slower per step - more of its smaller workgroups fit next to the walk's waves and take issue slots
-// from them.  hx_cabi.hip launches the form that goes with the stream-walk kernel it chose.
+// from them.  hx_batch.hip launches the form that goes with the stream-walk kernel it chose.
 template <bool DIRECT>
 __device__ __forceinline__ void spec_granule(const float *__restrict__ sb, const HxStream *__restrict__ st,
                                              const HxParams *__restrict__ prm, const HxGlobalTabs *__restrict__ gt,

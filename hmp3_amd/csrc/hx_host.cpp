@@ -7,6 +7,8 @@
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
+#include <string>
+#include "../../include/hmp3_amd.h"
 #include "hx_types.h"
 #include "hx_host.h"
 #include "iso_data.inc"
@@ -715,4 +717,71 @@ int hx_libm32_spot_check(int n)
         if (hx_f2u(a) != hx_f2u(hx_logf(x)) || hx_f2u(c) != hx_f2u(hx_log10f(x))) bad++;
     }
     return bad;
+}
+
+// ------------------------------------------------------------------------------------------
+// The exports of the C ABI (include/hmp3_amd.h) that touch nothing of the device.
+extern "C" void hx_default_control(HX_E_CONTROL *ec) { hx_host_default_control((HxControl *) ec); }
+
+// what CMp3Enc::L3_audio_encode_info_ec / _info_head would report for a control, without creating an
+// encoder (host only).  Returns 0 if the configuration is rejected.
+extern "C" int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *head_out)
+{
+    HxParams p;
+    if (!hx_resolve((const HxControl *) ec, &p)) return 0;
+    if (ec_out) memcpy(ec_out, &p.ec, sizeof(HxControl));
+    if (head_out) memcpy(head_out, &p.head_info, sizeof(HxMpegHead));
+    return 1;
+}
+
+extern "C" const char *hx_libc_version(void) { return hx_host_libc_version(); }
+extern "C" int hx_libm_spot_check(int n) { return hx_libm32_spot_check(n); }
+
+// 1 if the tables resolved for this control have the structure k_alloc_slim derives them from (hx_slim_tables_ok)
+extern "C" int hx_debug_slim_tables_ok(const HX_E_CONTROL *ec)
+{
+    static HxParams p;
+    static HxGlobalTabs g;
+    if (!hx_resolve((const HxControl *) ec, &p)) return -1;
+    hx_global_tabs(&g);
+    return hx_slim_tables_ok(&p, &g);
+}
+
+// host-side table generation exposed for the CPU tests (no GPU needed): resolves `ec` and copies
+// the named table; returns bytes copied, 0 if the configuration is rejected, -1 for a bad name
+extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *name, void *dst, long long cap)
+{
+    static HxParams p;
+    static HxGlobalTabs g;
+    if (!hx_resolve((const HxControl *) ec, &p)) return 0;
+    hx_global_tabs(&g);
+    std::string k(name);
+    const void *src = nullptr;
+    long long n = 0;
+#define TAB(nm, obj) else if (k == nm) { src = &(obj); n = sizeof(obj); }
+    if (k == "psy_w") { src = p.psyL.w; n = sizeof(p.psyL.w); }
+    TAB("psy_cnt", p.psyL.cnt) TAB("psy_off", p.psyL.off) TAB("psy_nsum", p.psyL.nsum) TAB("psy_npart", p.psyL.npart)
+    TAB("dct_tw", p.dct_tw) TAB("win", p.win) TAB("csa", p.csa) TAB("mdct_pre18", p.mdct_pre18) TAB("mdct_odd18", p.mdct_odd18)
+    TAB("dct9_even", p.dct9_even) TAB("dct9_odd", p.dct9_odd) TAB("dct9_k3", p.dct9_k3) TAB("mdct_pre6", p.mdct_pre6) TAB("mdct_odd6", p.mdct_odd6) TAB("dct3_k", p.dct3_k)
+    TAB("look_gain", p.look_gain) TAB("look_34igain", p.look_34igain) TAB("look_ix43", p.look_ix43)
+    TAB("look_log_cbwmb", p.look_log_cbwmb) TAB("nBand_l", p.nBand_l) TAB("startBand_l", p.startBand_l)
+    TAB("nsf", p.nsf) TAB("taperNT", p.taperNT) TAB("head", p.head) TAB("ec", p.ec)
+    TAB("anwin", g.anwin) TAB("mblog", g.mblog) TAB("mbexp_lo", g.mbexp_lo) TAB("mbexp_hi", g.mbexp_hi)
+    TAB("pow34_exp", g.pow34_exp) TAB("quant_off", g.quant_off) TAB("logsub", g.logsub)
+    TAB("huff_code", g.huff_code) TAB("huff_len", g.huff_len)
+    TAB("lane_run", p.lane_run) TAB("band_last_lane", p.band_last_lane)
+    TAB("nchan", p.nchan)
+#undef TAB
+    if (k == "run_w") { static int v[1]; v[0] = p.run_w; src = v; n = sizeof(v); }
+    if (k == "scalars") {
+        static int v[16];
+        v[0] = p.nsb_limit; v[1] = p.nsb_ms0; v[2] = p.band_limit; v[3] = p.main_framebytes; v[4] = p.AveTargetBits;
+        v[5] = p.initialMNR; v[6] = p.ms_flag; v[7] = p.hf_flag; v[8] = p.vbr_flag; v[9] = p.framebytes;
+        v[10] = p.remainder; v[11] = p.ivbr_max; v[12] = p.vbr_pool_target; v[13] = p.samprate; v[14] = p.totbitrate; v[15] = p.nsb_ms1;
+        src = v; n = sizeof(v);
+    }
+    if (!src) return -1;
+    if (n > cap) n = cap;
+    memcpy(dst, src, (size_t) n);
+    return n;
 }

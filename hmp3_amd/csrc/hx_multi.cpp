@@ -1,0 +1,257 @@
+// hx_multi.cpp - several GPUs of one node behind one handle: the streams are split into contiguous
+// blocks, one hx_batch per device, and every call runs one host thread per device on its block of the
+// caller's buffers.  Streams are independent, so nothing is exchanged between the devices.  With it, the host
+// placement those threads need.  Launches no kernel: built by the host compiler.
+#include <string>
+#include <thread>
+#include <sched.h>
+#include <unistd.h>
+#include "hx_rt.h"
+
+// ---- host placement: the NUMA node of a device, and threads / page-locked buffers next to it ----
+// A host-fed GPU takes 49 GB/s of PCM over PCIe (bench.py host_fed); eight of them read 394 GB/s of host memory.  That only
+// works out of the memory of the socket the GPU hangs on: a rank (or a dispatcher thread) binds itself to the CPUs of its
+// device's NUMA node before it allocates its page-locked buffers (first touch puts the pages there) and stays there for its
+// copies' submission.  Everything here is best effort: no sysfs entry, one node, or a CPU set that the cgroup does not allow
+// leaves the thread where it was and reports -1 / 0.
+static int read_int_file(const char *path, int *v)
+{
+    FILE *f = fopen(path, "r");
+    if (!f) return -1;
+    const int ok = fscanf(f, "%d", v) == 1;
+    fclose(f);
+    return ok ? 0 : -1;
+}
+
+// NUMA node of HIP device `device` (-1: unknown / not a NUMA machine), from its PCI address in sysfs
+extern "C" int hx_device_numa_node(int device)
+{
+    char bus[64] = {0}, path[256];
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) { (void) hipGetLastError(); return -1; }
+    if (hipDeviceGetPCIBusId(bus, (int) sizeof(bus), device) != hipSuccess) { (void) hipGetLastError(); return -1; }     // (the error is not left behind for the next launch check)
+    for (char *c = bus; *c; c++) if (*c >= 'A' && *c <= 'F') *c = (char) (*c - 'A' + 'a');      // sysfs spells the address in lower case
+    snprintf(path, sizeof(path), "/sys/bus/pci/devices/%s/numa_node", bus);
+    int node = -1;
+    if (read_int_file(path, &node) != 0) return -1;
+    return node;
+}
+
+// The CPUs this process may use, captured once when the library is loaded (= before any thread was bound by it): a thread
+// that was bound to one device's node must be able to move to another device's node afterwards, so a node's CPU list is
+// intersected with this set, not with the calling thread's current mask.
+static cpu_set_t g_proc_cpus;
+static bool g_proc_cpus_ok = false;
+__attribute__((constructor)) static void capture_process_cpus()
+{
+    CPU_ZERO(&g_proc_cpus);
+    g_proc_cpus_ok = sched_getaffinity(0, sizeof(g_proc_cpus), &g_proc_cpus) == 0;
+}
+// A process whose CPU set changes after the library was loaded (a launcher that calls sched_setaffinity / taskset on the
+// running process, a cpuset change; in Python the library loads lazily, so "when it was loaded" depends on import order)
+// takes the set again from its main thread's current mask: returns the number of CPUs, 0 on failure.  The bind calls also
+// do this once by themselves when the kernel refuses the mask they computed (EINVAL: none of its CPUs is allowed any more).
+extern "C" int hx_refresh_process_cpus(void)
+{
+    cpu_set_t now;
+    CPU_ZERO(&now);
+    if (sched_getaffinity(getpid(), sizeof(now), &now) != 0) return 0;      // (pid = the main thread's id)
+    g_proc_cpus = now;
+    g_proc_cpus_ok = true;
+    return CPU_COUNT(&now);
+}
+
+// the CPUs of a node that this process may use: parses /sys/devices/system/node/node<N>/cpulist ("0-15,128-143")
+static int node_cpus_allowed(int node, cpu_set_t *out)
+{
+    char path[128], buf[4096];
+    snprintf(path, sizeof(path), "/sys/devices/system/node/node%d/cpulist", node);
+    FILE *f = fopen(path, "r");
+    if (!f) return 0;
+    const bool got = fgets(buf, sizeof(buf), f) != nullptr;
+    fclose(f);
+    if (!got || !g_proc_cpus_ok) return 0;
+    CPU_ZERO(out);
+    int n = 0;
+    for (char *p = buf; *p;) {
+        char *e;
+        long a = strtol(p, &e, 10), z = a;
+        if (e == p) break;
+        if (*e == '-') { p = e + 1; z = strtol(p, &e, 10); }
+        for (long c = a; c <= z && c < CPU_SETSIZE; c++) if (CPU_ISSET((int) c, &g_proc_cpus)) { CPU_SET((int) c, out); n++; }
+        p = (*e == ',') ? e + 1 : e;
+        if (*e != ',') break;
+    }
+    return n;
+}
+
+// bind the calling thread to the allowed CPUs of NUMA node `node`; returns how many CPUs that is (0: left as it was)
+extern "C" int hx_bind_thread_to_node(int node)
+{
+    if (node < 0) return 0;
+    cpu_set_t set;
+    int n = node_cpus_allowed(node, &set);
+    if (n > 0 && sched_setaffinity(0, sizeof(set), &set) == 0) return n;
+    // the process's CPU set may have been narrowed since it was captured: take it again, try once more
+    if (hx_refresh_process_cpus() <= 0) return 0;
+    n = node_cpus_allowed(node, &set);
+    if (n <= 0) return 0;
+    return sched_setaffinity(0, sizeof(set), &set) == 0 ? n : 0;
+}
+
+// bind the calling thread to the allowed CPUs of `device`'s NUMA node; returns how many CPUs that is (0: left as it was)
+extern "C" int hx_bind_thread_to_device(int device)
+{
+    return hx_bind_thread_to_node(hx_device_numa_node(device));
+}
+
+struct hx_multi {
+    std::vector<hx_batch *> part;
+    std::vector<int> first, count, device;
+    std::vector<cpu_set_t> cpus;        // per device: the CPUs of its NUMA node this process may use (resolved once, at creation)
+    std::vector<int> ncpus;             // ... and how many (0: unknown, the device's thread stays where it is)
+    int S = 0, nchan = 2;
+};
+
+extern "C" void hx_multi_destroy(hx_multi *m)
+{
+    if (!m) return;
+    for (hx_batch *b : m->part) hx_batch_destroy(b);
+    delete m;
+}
+
+// the blocks of streams and their batches; make(device, first, count) creates block k's batch
+template <class Make>
+static hx_multi *multi_create(int ndev, const int *devices, int nstreams, Make make)
+{
+    const int have = hx_device_count();
+    if (ndev <= 0) ndev = have;
+    if (ndev > nstreams) ndev = nstreams;
+    if (ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return nullptr; }
+    hx_multi *m = new hx_multi;
+    m->S = nstreams;
+    const int base = nstreams / ndev, rem = nstreams % ndev;       // block sizes differ by at most one (hmp3_amd/shard.py)
+    for (int k = 0; k < ndev; k++) {
+        const int first = k * base + (k < rem ? k : rem), count = base + (k < rem ? 1 : 0);
+        const int dev = devices ? devices[k] : k;
+        hx_batch *b = make(dev, first, count);
+        if (!b) { hx_multi_destroy(m); return nullptr; }            // hx_last_error is hx_batch_create's
+        m->part.push_back(b); m->first.push_back(first); m->count.push_back(count); m->device.push_back(dev);
+        cpu_set_t cs;
+        CPU_ZERO(&cs);
+        const int node = hx_device_numa_node(dev);
+        m->ncpus.push_back(node >= 0 ? node_cpus_allowed(node, &cs) : 0);
+        m->cpus.push_back(cs);
+        if (k == 0) m->nchan = b->nchan;
+        else if (b->nchan != m->nchan || b->lsf != m->part[0]->lsf) { set_err("mono / stereo and MPEG-1 / MPEG-2 streams cannot share a batch"); hx_multi_destroy(m); return nullptr; }
+    }
+    return m;
+}
+
+extern "C" hx_multi *hx_multi_create(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create(dev, count, shared_control ? ec : ec + first, shared_control, max_frames);
+    });
+}
+
+// converting batches over several devices (stream numbers in hx_last_error are the block's)
+extern "C" hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control,
+                                         const HX_SOURCE *src, int shared_source, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create_src(dev, count, shared_control ? ec : ec + first, shared_control, shared_source ? src : src + first, shared_source, max_frames);
+    });
+}
+
+extern "C" int hx_multi_ndevices(const hx_multi *m) { return m ? (int) m->part.size() : 0; }
+extern "C" int hx_multi_nstreams(const hx_multi *m) { return m ? m->S : 0; }
+extern "C" hx_batch *hx_multi_batch(hx_multi *m, int k) { return (m && k >= 0 && k < (int) m->part.size()) ? m->part[k] : nullptr; }
+extern "C" int hx_multi_shard(const hx_multi *m, int k, int *device, int *first, int *count)
+{
+    if (!m || k < 0 || k >= (int) m->part.size()) return -1;
+    if (device) *device = m->device[k];
+    if (first) *first = m->first[k];
+    if (count) *count = m->count[k];
+    return 0;
+}
+
+extern "C" long long hx_multi_out_stride(const hx_multi *m, int nframes)
+{
+    long long n = 0;
+    if (m) for (hx_batch *b : m->part) { const long long v = hx_batch_out_stride(b, nframes); if (v > n) n = v; }
+    return n;
+}
+
+// Argument checks of the calls over all devices; then fn(k) on one thread per device, bound to the CPUs next to it.
+// Returns the first failing block's code, with its message as the caller's hx_last_error.
+template <class Fn>
+static int multi_fanout(hx_multi *m, bool buffers_ok, int nframes, long long out_stride, Fn fn)
+{
+    if (!m || !buffers_ok) { set_err("null buffer"); return -1; }
+    if (out_stride < hx_multi_out_stride(m, nframes)) { set_err("out_stride is smaller than hx_multi_out_stride(m, nframes)"); return -1; }
+    const size_t n = m->part.size();
+    std::vector<int> rc(n, 0);
+    std::vector<std::string> err(n);
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < n; k++)
+        th.emplace_back([&, k]() {
+            if (m->ncpus[k] > 0) sched_setaffinity(0, sizeof(cpu_set_t), &m->cpus[k]);     // this device's copies are issued from its own socket (best effort)
+            rc[k] = fn(k);
+            if (rc[k]) err[k] = hx_last_error();        // the message is thread-local: hand it to the caller's thread
+        });
+    for (std::thread &t : th) t.join();
+    for (size_t k = 0; k < n; k++) if (rc[k]) { set_err("%s", err[k].c_str()); return rc[k]; }
+    return 0;
+}
+
+// the PCM calls: each device on its block's rows of the caller's buffers
+static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats)
+{
+    return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
+        const long long f = m->first[k];
+        const char *p = (const char *) in.p + (size_t) f * nframes * 1152 * m->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
+        return encode_host(m->part[k], {p, in.f32}, nframes, out + f * out_stride, out_stride, out_bytes + f, stats ? stats + f * nframes * 2 : nullptr);
+    });
+}
+extern "C" int hx_multi_encode_s16_host(hx_multi *m, const int16_t *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    return multi_encode_host(m, {pcm, false}, nframes, out, out_stride, out_bytes, nullptr);
+}
+extern "C" int hx_multi_encode_f32_host(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    return multi_encode_host(m, {pcm, true}, nframes, out, out_stride, out_bytes, nullptr);
+}
+extern "C" int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats)
+{
+    if (!stats) { set_err("null buffer"); return -1; }
+    return multi_encode_host(m, {pcm, true}, nframes, out, out_stride, out_bytes, stats);
+}
+extern "C" long long hx_multi_src_in_stride(const hx_multi *m, int nframes)
+{
+    long long n = 0;
+    if (m) for (hx_batch *b : m->part) n = std::max(n, hx_batch_src_in_stride(b, nframes));
+    return n;
+}
+
+// hx_batch_encode_src_host over all streams
+extern "C" int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                        unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats)
+{
+    return multi_fanout(m, in && out && out_bytes, nframes, out_stride, [&](size_t k) {
+        const long long f = m->first[k];
+        return hx_batch_encode_src_host(m->part[k], in + f * in_stride, in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes,
+                                        out + f * out_stride, out_stride, out_bytes + f, in_used ? in_used + f : nullptr,
+                                        stats ? stats + f * nframes * 2 : nullptr);
+    });
+}
+
+extern "C" int hx_multi_status(hx_multi *m)
+{
+    int v = 0;
+    if (!m) return -1;
+    for (hx_batch *b : m->part) v |= hx_batch_status(b);
+    return v;
+}

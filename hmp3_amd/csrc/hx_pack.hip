@@ -201,7 +201,7 @@ __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, c
         L.tabpk[tid] = gt->huff_off[tid] | (dim << 12) | (lin << 20);
     }
     if (tid < 16) { L.quada_code[tid] = gt->quada_code[tid]; L.quada_len[tid] = gt->quada_len[tid]; }
-    // solo > 0 (a handful of frames in all - the one-stream encoder's calls: hx_cabi.hip launches ONE workgroup): this
+    // solo > 0 (a handful of frames in all - the one-stream encoder's calls: hx_batch.hip launches ONE workgroup): this
     // workgroup also does what k_pack_pre and k_pack_carry do for the call's `solo` streams - the pending frames' images to the
     // head of `out` before the packing, the incomplete ones' back into the stream state behind it - two launches less per call.
     if (solo > 0) {
@@ -298,7 +298,7 @@ __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, c
             const int n = carry_len[s];
             for (int i = tid; i < n; i += 256) ss->main_buf[i] = src[i];
         }
-        // The one-stream encoder's graph (hx_cabi.hip, hx_enc): the call's results go straight to page-locked host memory -
+        // The one-stream encoder's graph (hx_enc.cpp, hx_enc): the call's results go straight to page-locked host memory -
         // [byte count | frame counter | sequence word | ... 256 | bitstream] - and the sequence word last, behind system-scope
         // fences: when the host sees it change, the rest has landed.  (Round 6 first had copy nodes bring the results down and
         // polled the last of them: one call in 20 000 read the bytes before the copy ahead of it had landed - copies of one

@@ -1,0 +1,269 @@
+// hx_rt.h - what the units of the host runtime share: the batch, its error / allocation helpers, the kernels' prototypes
+// and the few entry points one unit needs of another.  Units: hx_batch.hip (the batch and its passes), hx_batch_src.hip
+// (converting batches), hx_enc.cpp (the single-stream encoder), hx_multi.cpp (several devices behind one handle).
+#pragma once
+#ifdef __HIPCC__
+#include <hip/hip_runtime.h>
+#else
+#include <hip/hip_runtime_api.h>    // (a unit that launches no kernel is built by the host compiler)
+#endif
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+#include <limits.h>
+#include <vector>
+#include <algorithm>
+#include "../../include/hmp3_amd.h"
+#include "hx_types.h"
+#include "hx_host.h"
+#include "hx_src.h"
+
+// what one unit of the library needs of another is not an export
+#define HX_LOCAL __attribute__((visibility("hidden")))
+
+HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling thread's hx_last_error
+#define HIPCHK(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return -1; } } while (0)
+#define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
+
+#ifdef __HIPCC__
+// kernels (hx_front.hip / hx_alloc.hip / hx_pack.hip / hx_src.inc)
+// (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
+__global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
+                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf);
+__global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int nchan);
+__global__ void k_src(SrcArgs a);
+__global__ void k_detect(HxStream *st, const HxParams *prm, const int *eng, unsigned char *flg, int *dbg_metric, unsigned char *bt,
+                         unsigned char *btprev, int NG, int S, int lsf);
+__global__ void k_spec(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
+                       float *xr, float *etab, float *thr, int *msbase, int NG, int SG);
+__global__ void k_spec_direct(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
+                              float *xr, float *etab, float *thr, int *msbase, int NG, int SG);
+__global__ void k_msscan(HxStream *st, const HxParams *prm, const int *msbase, const unsigned char *bt, unsigned char *msflag, int *msdec,
+                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int nchan);
+__global__ void k_prep(const float *xr, float *xmag_dbg, float *x34o, unsigned *sgn, HxBandPrep *band, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt,
+                       const unsigned char *bt, const unsigned char *msflag, const float *etab, const float *thr, const float *thrprev, int NG, long long nunits);
+__global__ void k_pack(const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const short *ixq, const unsigned *sgn, const HxSegOut *seg,
+                       const HxFrameOut *frm, const HxSlot *slots, unsigned char *out, long long out_stride, unsigned char *packet, int *status,
+                       int frames_per_stream, int NG, int lsf, long long nframes_total, int solo, HxStream *st_w, const int *pre_len, const int *out_bytes,
+                       const int *carry_len, unsigned *frames_out, unsigned char *host_out, const int *seq_src);
+__global__ void k_pack_carry(HxStream *st, const unsigned char *out, long long out_stride, const int *out_bytes, const int *carry_len, unsigned *frames_out);
+__global__ void k_pack_pre(const HxStream *st, unsigned char *out, long long out_stride, const int *pre_len);
+__global__ void k_order(const unsigned *dur, int *order, int S);
+__global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
+__global__ void k_alloc(AllocArgs a);
+__global__ void k_alloc_slim(AllocArgs a);
+__global__ void k_alloc_lsf(AllocArgs a);
+__global__ void k_alloc1(AllocArgs a);
+__global__ void k_alloc1_lsf(AllocArgs a);
+
+// every kernel launch is checked where it is made: a bad configuration or a lost device is reported
+// with the kernel's name instead of surfacing at some later call
+#define LAUNCH_LDS(kernel, grid, block, lds, stream, ...) do { hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__); \
+        hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) { set_err("launch of " #kernel " failed: %s", hipGetErrorString(e_)); return -1; } } while (0)
+#define LAUNCH(kernel, grid, block, stream, ...) LAUNCH_LDS(kernel, grid, block, 0, stream, __VA_ARGS__)
+#endif
+
+// The buffers that hand a call's granules from the front end to the stream walk (layouts: AllocArgs).
+// The submit path keeps two sets: the front end of call n + 1 fills one while the stream walk of call n reads the other.
+struct FrontSet {
+    float *xr, *etab, *thr;
+    float *x34;                         // x^(3/4) of the magnitudes (k_prep writes it in debug mode only)
+    float *thrprev;                     // [S][2][64] pre-echo memory at the call's start
+    int *msbase, *msdec;
+    unsigned char *bt, *btprev, *msflag;
+    HxBandPrep *band;
+};
+// ... and from the stream walk to the packing: quantised lines, segment and frame records, slot lists, and the byte counts of
+// the pending frames' images at the call's start / end (views into hx_batch::d_lens)
+struct WalkSet {
+    short *ixq;
+    HxSegOut *seg;
+    HxFrameOut *frm;
+    HxSlot *slots;
+    int *pre_len, *carry_len;
+};
+
+struct hx_batch {
+    int device = 0, S = 0, maxF = 0, ncls = 0;
+    std::vector<HxParams> params;       // host copy per class
+    std::vector<int> cls_of;            // stream -> class
+    HxParams *d_prm = nullptr;
+    HxGlobalTabs *d_gt = nullptr;
+    HxStream *d_st = nullptr;
+    float *d_sb = nullptr, *d_xrdbg = nullptr;
+    FrontSet front[2] = {};             // [1]: created at the first submit (pipe_init)
+    WalkSet walk[2] = {};
+    unsigned *sgn[3] = {};              // the lines' signs, one bit per line: [S][NG][2][HX_SGN_WORDS]; read by the packing, so three sets
+                                        // on the submit path (the front end of call n + 2 writes one while call n is packed)
+    int *d_lens = nullptr;              // [2 sets][pre_len | carry_len][S]
+    int *frame_stats = nullptr;         // caller's per-frame counters (device), optional
+    unsigned char *pk_buf = nullptr; long long pk_stride = 0; int *pk_bytes = nullptr;   // caller's packet buffers (device), optional
+    float *d_pcmf = nullptr;            // DC-blocked input, only when a stream uses filter_select = 1
+    bool any_dc = false;
+    int nchan = 2;                      // channels of the PCM input, the same for every stream of the batch
+    int lsf = 0;                        // 1: an MPEG-2 LSF batch (16 / 22.05 / 24 kHz): every 1152-sample block yields two frames
+    int slim = 0;                       // 1: the low-footprint stream walk k_alloc_slim (six streams per CU instead of four), chosen at create
+    int alloc1 = 0;                     // 1: streams of the first-generation allocator (intensity stereo, dual channel): k_alloc1*
+    int *d_eng = nullptr, *d_status = nullptr, *d_dbgmetric = nullptr;
+    unsigned char *d_flg = nullptr;
+    HxFrameDebug *d_dbg = nullptr;
+    unsigned long long *d_prof = nullptr;
+    int lastNG = 0;                     // NG of the previous call (layout of the carry)
+    // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
+    int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
+    std::vector<HxSrcPlan> src_plans;
+    std::vector<int> src_cls;           // stream -> plan
+    std::vector<long long> src_calls;   // stream -> converter calls made (authoritative; the device keeps a copy for k_src)
+    HxSrcPlan *d_src_plan = nullptr;
+    int *d_src_cls = nullptr;
+    long long *d_src_calls = nullptr;   // [2][S]: k_src reads copy src_par and writes the other
+    float *d_src_carry = nullptr;       // [2][S][2][HX_SRC_CARRY] the same for the case-4 intermediate samples
+    int src_par = 0;
+    float *d_src_pcm = nullptr;         // [S][nframes * 1152][nchan] the last call's converted PCM
+    long long *d_src_off = nullptr, *h_src_off = nullptr;      // [S][max_frames] the caller's frame offsets (device / page-locked)
+    hipEvent_t ev_src_off = nullptr;    // the last upload of h_src_off is done
+    int src_xwin = 0, src_zwin = 0, src_zoff = 0, src_coff = 0, src_lastF = 0;
+    size_t src_lds = 0;
+    bool debug = false;
+    // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
+    // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
+    void *d_in = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr, *d_stats = nullptr;
+    long long in_cap = 0, out_cap = 0, stats_cap = 0;
+    std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
+    double alloc_ms_sum = 0; int alloc_calls = 0;
+    // hx_batch_submit_*: the front-end kernels of call n+1 run (low-priority stream) while k_alloc of
+    // call n (high-priority stream) works through its slowest streams (see FrontSet)
+    hipStream_t s_front = nullptr, s_alloc = nullptr, s_pack = nullptr;
+    hipEvent_t ev_in = nullptr, ev_front[2] = {nullptr, nullptr}, ev_alloc[2] = {nullptr, nullptr};     // ev_alloc: a submit's packing is done (everything is)
+    hipEvent_t ev_k6[2] = {nullptr, nullptr};           // a submit's allocator launch is done
+    hipEvent_t ev_sgn[3] = {nullptr, nullptr, nullptr}; // the packing that read this set of signs is done
+    // the packing of the latest device-buffer submit, not enqueued yet: it goes out behind the next submit's allocator launch
+    // (released by a gate like the front end, into that launch's tail), or ungated at the next wait / plain call
+    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; int nframes = 0, set = 0, sset = 0; } pack_job;
+    long long nsubmit = 0;
+    bool inflight = false;
+    // hx_batch_submit_*_host: device staging for two calls in flight and the copy streams
+    void *hs_pcm[2] = {nullptr, nullptr}; unsigned char *hs_out[2] = {nullptr, nullptr}; int *hs_nb[2] = {nullptr, nullptr};
+    long long hs_pcm_cap = 0, hs_out_cap = 0;
+    hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_host = nullptr;
+    hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr}, ev_hfront[2] = {nullptr, nullptr};
+    long long nhost = 0;
+    unsigned *d_dur = nullptr;          // [S] duration of each stream's allocator workgroup in the last launch
+    int *d_order = nullptr;             // [S] workgroup -> stream for the next launch (used when the batch exceeds what the chip holds at once)
+    int *d_done = nullptr;              // [HX_CNT_WORDS] the counter block (hx_types.h, HxCounter)
+    int resident = 0;                   // allocator workgroups the device holds at once
+    long long alloc_launches = 0;
+    unsigned long long cfg_hash = 0;    // fingerprint of the resolved configuration classes (checkpoint blobs carry their stream's)
+    // a submit's front end is released once this share of the previous allocator launch's resident set has started.
+    // Not 100: the gate's own wavefront holds register space on one SIMD, so the last allocator workgroup of a full
+    // chip cannot start before a stream retires (measured: 10 .. 99 % all give the same step time, 100 % loses 30 %)
+    int gate_percent = 90;
+    bool capturing = false;             // the pass is being recorded into a HIP graph (hx_enc_*): no timing events, nothing that queries the stream
+    unsigned *cap_frames = nullptr;     // one-stream encoder: where k_pack_carry leaves the stream's frame counter (next to the byte count)
+    unsigned char *cap_host = nullptr;  // one-stream encoder: page-locked host memory the packing workgroup publishes the call's results to (hx_pack.hip)
+    bool poisoned = false;              // a HIP call failed in the middle of a pass: the event bookkeeping is incomplete, further calls are refused
+    // longest-first workgroup order: 2 = for every batch with more streams than the chip has CUs (default: below that no two
+    // streams share a CU and the order decides nothing), 3 = always (tests), 1 = only for batches beyond the resident set,
+    // 0 = never (HMP3AMD_LPT).
+    // Beyond the resident set it keeps the launch's last round short.  Within it the order decides which streams share a CU:
+    // workgroups are dealt over XCDs and CUs in turn, so a CU's four streams are 256 apart in launch order - in stream order
+    // those are streams of one residue class, and a batch whose slow streams recur with a period (BASELINE config 5: correlation
+    // by stream mod 4) had them all on the same CUs; sorted by the previous call's duration a CU gets one stream of each quartile.
+    // (Round 4: config 2 +1.0 %, its worst-case signal set +2.1 %.)
+    int lpt = 2;
+    int ncu = 256;                      // compute units of the device
+    int park_k = 8;                     // HMP3AMD_PARK: the CUs of this many longest streams are kept free of other kernels' workgroups (0 = off; see hx_alloc3.inc, "parking")
+    int park_pair = 0;                  // HMP3AMD_PARK_PAIR=1: also the CU that shares the instruction cache with a straggler's
+    int strict_sums = 0;                // HMP3AMD_EXACT_SUMS=1: the stream walk adds every band in line order instead of certifying a parallel sum (tests)
+    // everything the batch allocates or creates on the device (dev_alloc, new_stream, new_event): hx_batch_destroy releases it
+    std::vector<void *> mem;
+    std::vector<hipStream_t> streams;
+    std::vector<hipEvent_t> events;
+};
+
+// Every device buffer, HIP stream and event of a batch is made by one of these and listed in the batch, whose
+// hx_batch_destroy releases them.
+template <class T> static int dev_alloc(hx_batch *b, T *&p, long long bytes)
+{
+    void *q = nullptr;
+    if (hipMalloc(&q, (size_t) bytes) != hipSuccess) { set_err("hipMalloc failed"); return -1; }
+    b->mem.push_back(q);
+    p = (T *) q;
+    return 0;
+}
+// (staging that grows with the call: the old buffer is freed, its contents are not kept)
+template <class T> static int dev_realloc(hx_batch *b, T *&p, long long bytes)
+{
+    if (p) {
+        hipFree(p);
+        for (void *&m : b->mem) if (m == p) { m = b->mem.back(); b->mem.pop_back(); break; }
+        p = nullptr;
+    }
+    return dev_alloc(b, p, bytes);
+}
+// ... to at least `bytes`, where cap is what it holds
+template <class T> static int dev_grow(hx_batch *b, T *&p, long long &cap, long long bytes)
+{
+    if (bytes <= cap) return 0;
+    if (dev_realloc(b, p, bytes) != 0) return -1;
+    cap = bytes;
+    return 0;
+}
+HX_LOCAL int new_stream(hx_batch *b, hipStream_t &q, int priority = INT_MAX);     // (INT_MAX: the runtime's default priority)
+HX_LOCAL int new_event(hx_batch *b, hipEvent_t &e);
+
+// A launch or HIP call that fails once a pass has touched the batch leaves events unrecorded, buffer sets half handed
+// over or staging half updated: the batch is not reusable (this only happens on a device error).  A pass holds one of
+// these while it works; leaving it any other way than through ok() marks the batch, whose later calls are refused
+// (check_poisoned); hx_batch_destroy just synchronises.
+struct Poison {
+    hx_batch *b;
+    bool armed = true;
+    ~Poison() { if (armed) b->poisoned = true; }
+    int ok() { armed = false; return 0; }
+};
+HX_LOCAL int check_poisoned(const hx_batch *b);
+
+// the PCM of a pass: int16, or fp32 at int16 scale
+struct PcmIn { const void *p; bool f32; };
+// where a pass runs: every kernel on the caller's stream, or (hx_batch_submit_*) front end and stream walk on the batch's
+// own two streams, ordered by events (see hx_batch); a device-buffer submit also defers its packing
+enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
+
+// Argument checks of every encode entry point, made before anything is allocated, copied or launched; check_call: ... of
+// the PCM entry points, which a converting batch refuses
+HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes);
+HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes);
+// one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass
+HX_LOCAL int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind);
+HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind);
+HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats);
+// Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
+HX_LOCAL int drain(hx_batch *b);
+// the encode control of a converted source and its converter (hx_enc.cpp)
+HX_LOCAL int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int source_is_float, int mpeg_select, int mono_convert,
+                                hx_src *conv, HX_E_CONTROL *ec_out);
+
+// One host-buffer call: grow the staging, copy the input up, make the device call `encode()` on b->d_in / d_out /
+// d_outbytes, wait for it and copy the results back - with `stats`, also the call's per-frame counters (see
+// hx_batch_frame_stats_buffer), which the device call then writes to staging of the batch's instead of the caller's buffer.
+// drain_first: the staging may still be read by an earlier call that did not wait for its end.
+template <class Encode>
+static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
+                     long long out_stride, int *out_bytes, int *stats, Encode encode)
+{
+    HIPCHK(hipSetDevice(b->device));
+    const long long obytes = (long long) b->S * out_stride, sbytes = stats ? (long long) sizeof(int) * b->S * nframes * 2 : 0;
+    if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes)) return -1;
+    if (drain_first && drain(b) != 0) return -1;
+    HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));
+    int *const saved = b->frame_stats;
+    if (stats) b->frame_stats = b->d_stats;
+    const int r = encode();
+    b->frame_stats = saved;
+    if (r != 0 || drain(b) != 0) return -1;
+    HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, b->d_out, (size_t) obytes, hipMemcpyDeviceToHost));
+    if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, (size_t) sbytes, hipMemcpyDeviceToHost));
+    return 0;
+}

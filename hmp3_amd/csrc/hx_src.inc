@@ -15,7 +15,7 @@
 // launch reads the copy from before, so a one-call launch never reads what it writes).
 #include "hx_src.h"
 
-// (SrcArgs: hx_src.h, shared with the launch in hx_cabi.hip)
+// (SrcArgs: hx_src.h, shared with the launch in hx_batch_src.hip)
 
 // sample `idx` (interleaved channels) of a source in the given format, at int16 scale (hx_src_convert's staging)
 __device__ __forceinline__ float src_sample(const unsigned char *x, long long idx, int bits, int is_float, bool aligned)

@@ -185,7 +185,7 @@ struct alignas(16) HxFrameOut {
 };
 #define HX_SLOTS_EXTRA 40           // slots pending from earlier calls (the ring holds 32)
 
-// k_polyphase (hx_front.hip) and its launch (hx_cabi.hip): granules per workgroup (252 of 256 lanes busy: a lane is a time slot
+// k_polyphase (hx_front.hip) and its launch (hx_batch.hip): granules per workgroup (252 of 256 lanes busy: a lane is a time slot
 // of a granule) and the workgroup size that follows.  One definition: the kernel's launch bounds, its LDS staging stride and
 // register array are sized by the same numbers the host launches with.
 // (7 granules: 126 of the workgroup's 128 lanes have a time slot, 37 KB of LDS, four workgroups per CU; with 14 - 252 of 256 lanes,

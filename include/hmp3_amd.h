@@ -303,7 +303,7 @@ int hx_libm_spot_check(int n);
    the x^(3/4) exponent table as ldexp of 4 / 16 constants, mB tables within 16 bits); hx_batch_create checks the same
    before it picks that kernel.  -1 = configuration rejected.  Host only. */
 int hx_debug_slim_tables_ok(const HX_E_CONTROL *ec);
-/* host-side table generation for the CPU tests (no GPU): see hx_cabi.hip */
+/* host-side table generation for the CPU tests (no GPU): see hx_host.cpp */
 long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *name, void *dst, long long cap);
 
 /* ---- Xing / Info / LAME tag frame (first frame of a file; reference pub/xhead.h) ----

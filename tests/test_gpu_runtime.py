@@ -214,7 +214,7 @@ def test_cli_streams_from_a_pipe_with_bounded_buffers(name, tmp_path):
 @pytest.mark.parametrize("lpt", ["3", "0"])
 def test_longest_first_workgroup_order_changes_nothing_in_the_output(monkeypatch, lpt):
     """Batches with more streams than the chip has CUs start their allocator workgroups by the previous call's stream
-    durations, longest first (hx_cabi.hip k_order); forced here on a small batch (HMP3AMD_LPT=3), three calls so that the
+    durations, longest first (hx_batch.hip k_order); forced here on a small batch (HMP3AMD_LPT=3), three calls so that the
     order is a real permutation, against the oracle - and the identity order (HMP3AMD_LPT=0) the same"""
     import numpy as np
     from hmp3_amd import api, synth

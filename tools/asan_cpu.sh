@@ -1,5 +1,6 @@
 #!/bin/bash
-# Host side of the library (parameter resolution and tables, tag frame, sample-rate converter) under AddressSanitizer +
+# Host side of the library (parameter resolution and tables, tag frame, sample-rate converter, and the runtime units that
+# launch no kernel: single-stream encoder, placement and multi-device calls) under AddressSanitizer +
 # UBSan, on the CPU: the tests that need no GPU, against a variant library whose host-only sources are compiled with
 # the sanitizers (a g++ wrapper on PATH adds the flags, so hmp3_amd/build.sh - and with it the product's build id -
 # stays as it is).   bash tools/asan_cpu.sh
