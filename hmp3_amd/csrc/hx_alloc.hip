@@ -264,11 +264,11 @@ __device__ __forceinline__ float lk_igain(const float *ig16, int g) { const int 
 
 #ifdef HX_PROFILE
 // (only the master wave's time is booked: the helper wave runs some of the same functions)
-#define PROF(id, stmt) do { SYNC(); long long t0_ = clock64(); stmt; SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - t0_); } while (0)
+#define PROF(id, stmt) do { HX_WAVE_SYNC(); long long t0_ = clock64(); stmt; HX_WAVE_SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - t0_); } while (0)
 #define PROF_T0() long long tp_ = clock64()
 #define PROF_T1() tp_ = clock64()
 #define PROF_CNT(id) do { if (threadIdx.x == 0) L.prof[(id)] += 1; } while (0)
-#define PROF_ACC(id) do { SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - tp_); tp_ = clock64(); } while (0)
+#define PROF_ACC(id) do { HX_WAVE_SYNC(); if (threadIdx.x == 0) L.prof[(id)] += (unsigned) (clock64() - tp_); tp_ = clock64(); } while (0)
 #define PROF_CLOCK , long long &tp_      // a phase of the frame loop (hx_alloc3.inc) books on the loop's running clock
 #define PROF_PASS , tp_
 #else
@@ -313,15 +313,8 @@ __device__ __forceinline__ int hx_lane_opaque()
 #endif
 #define LANE lane_
 #define WAVE ((int) threadIdx.x >> 6)
-// The workgroup is a single wavefront, and a wave's LDS operations execute in issue order, so an
-// LDS hand-over between lanes only needs the compiler to keep the accesses in program order.
-// __syncthreads() would also drain every outstanding global load/store (s_waitcnt vmcnt(0)),
-// which costs a memory round trip per call in the frame-level code.  SYNC_G() is the full
-// barrier, used where lanes exchange data through global memory.
-// (No s_waitcnt: the LDS unit takes a wave's DS instructions in issue order, so a read issued behind a write of the same
-// wave sees it whichever lane wrote; waiting for the write's completion first only adds its latency - measured 1-2 % of
-// the launch.  The compiler places the waits that register results need.)
-#define SYNC() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
+// The encoder's wave works alone: its LDS hand-overs between lanes take HX_WAVE_SYNC() (hx_dev.h), no workgroup barrier.
+// SYNC_G() is the full barrier, used where lanes exchange data through global memory.
 #define SYNC_G() do { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
 
 // A stream's workgroup is two wavefronts.  Wave 0 (the master) runs the encoder; wave 1 (the helper)
@@ -536,7 +529,7 @@ __device__ __noinline__ float sweep_sum_strict(AllocLds &L, int ch, int W, int h
 {
     HX_LANE_DECL;
     if (!have_terms) (void) sweep_run_stored(L, ch, W, 0);
-    SYNC();
+    HX_WAVE_SYNC();
     if (LANE == 0) atomicAdd(&L.nstrict, 1);
     float sxx = fast;
     if (need) sxx = band_sum(&L.term[ch][sbeg], n, 0.0f);
@@ -562,7 +555,7 @@ __device__ __forceinline__ int noise_sweep(AllocLds &L, const SweepRegs &R, cons
         L.gpair[ch][LANE] = make_float2(ig, (g >= 0) ? gn_g : 0.0f);
         if (g >= 0) bslow = noise_band_needs_pow(ig, x34max);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_SWEEP_PUBLISH);
     const int anyslow = __any(bslow) ? 1 : 0;
     float part;
@@ -576,7 +569,7 @@ __device__ __forceinline__ int noise_sweep(AllocLds &L, const SweepRegs &R, cons
     if (__builtin_expect(__any(strict), 0)) sxx = sweep_sum_strict(L, ch, W, anyslow, strict, sbeg, send - sbeg, sxx);
     int noise = 0;
     if (g >= 0) noise = MBLOG(1.0e-12f + sxx) - logcbw;
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_SWEEP_SUMS);
     return noise;
 }
@@ -603,12 +596,12 @@ __device__ void adjust_nt(AllocLds &L, const AllocPrm *p)
         d = min(d, dmax);
         L.NT[ch][i] = L.NT[ch][i] + d;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // Start of a long-block granule (reference bitallo3.cpp:816-898 L/R, :902-1066 M/S).  The parts that do not
 // depend on the stream's carried state - magnitudes, signs, band energies, x^(3/4), band maxima, zero-gain
-// steps, masking thresholds - were computed by k_prep (hx_front.hip) and arrive in `in`; what is left here are
+// steps, masking thresholds - were computed by k_prep (hx_prep.hip) and arrive in `in`; what is left here are
 // the noise targets, which follow the long-term MNR: band-parallel integer work.
 struct BandIn { float xsxx, x34max; int n0, n0ms, gzero, maskmb; };     // band lane (ch, sfb)'s share of HxBandPrep
 
@@ -628,7 +621,7 @@ __device__ void startup_prepped(AllocLds &L, const AllocPrm *p, int ms, const Ba
     if (ms) {
         if (LANE == 0 && p->vbr_flag == 0 && L.call_count > 10 && (L.TargetBits - L.minTargetBits) < 100)
             L.MNR = min(L.MNR + 50, 2050);
-        SYNC();
+        HX_WAVE_SYNC();
     }
     const int mnr = ms ? L.MNR : L.MNR + 100;
     const int ch = LANE >> 5, i = LANE & 31;
@@ -650,7 +643,7 @@ __device__ void startup_prepped(AllocLds &L, const AllocPrm *p, int ms, const Ba
     if (i < nbz) { L.gzero[ch][i] = in.gzero; L.gmin[ch][i] = max(0, in.gzero - GMIN_OFFSET); }
     act = hx_wave_sum(act);
     if (LANE == 0) L.activeBands = act;
-    SYNC();
+    HX_WAVE_SYNC();
     adjust_nt(L, p);
     if (ms && LANE < p->nsf[0]) {       // targets of M and S from those of L and R (bitallo3.cpp:1014-1062)
         int b = LANE;
@@ -663,7 +656,7 @@ __device__ void startup_prepped(AllocLds &L, const AllocPrm *p, int ms, const Ba
         L.snr[0][b] = Nsum - nt0;
         L.snr[1][b] = Ndiff - nt1;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallo3.cpp:1130-1160
@@ -684,7 +677,7 @@ __device__ void seek_initial(AllocLds &L, const AllocPrm *p)
         gs = max(gs, L.gmin[ch][i]);
         L.gsf[ch][i] = gs;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallo3.cpp:1164-1296: all bands of channel ch walk their gain step concurrently (lane = sfb)
@@ -728,7 +721,7 @@ HX_SEEK_INLINE void seek_actual_ch(AllocLds &L, const AllocPrm *p, int ch)
     const int last4 = 4 * (int) L.band_last[ib];
     float ig_c = LK_IGAIN(s & 127), gn_c = LK_GAIN(s & 127);      // pair of the step to measure now
     float ig_dn = 0.0f, gn_dn = 0.0f, ig_up = 0.0f, gn_up = 0.0f;          // pairs of the steps below / above it
-    SYNC();
+    HX_WAVE_SYNC();
     while (__any(mode != 0)) {
         PROF_CNT(HX_PROF_N_SWEEPS);
 #ifdef HX_PROFILE
@@ -759,7 +752,7 @@ HX_SEEK_INLINE void seek_actual_ch(AllocLds &L, const AllocPrm *p, int ch)
     }
     if (band) { L.gsf[ch][i] = smin; L.Noise[ch][i] = tnmin; L.NTadjust[ch][i] = ntadj; }
     if (i < NB) L.geval[ch][i] = -1;
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // both channels: channel 1's whole search on the helper wave
@@ -772,7 +765,7 @@ __device__ void seek_actual(AllocLds &L, const AllocPrm *p)
     PROF_T0();
     if (two) HELPER_JOIN();
     else if (LANE < NB) L.geval[1][LANE] = -1;
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_SEEK_JOIN);
 }
 
@@ -781,9 +774,6 @@ __device__ void seek_actual(AllocLds &L, const AllocPrm *p)
 // Band-parallel: channel ch lives in lanes 32*ch .. 32*ch+21; maxima / ORs are half-wave
 // reductions.  The M/S variant carries the running maximum from a silent channel 0 into
 // channel 1 (the reference only resets it on the non-silent path).
-__device__ __forceinline__ int half_max(int v) { return hx_half_max(v); }
-__device__ __forceinline__ int half_or(int v) { return hx_half_or(v); }
-
 __device__ int scale_factors(AllocLds &L, const AllocPrm *p, int ms)
 {
     HX_LANE_DECL;
@@ -795,8 +785,8 @@ __device__ int scale_factors(AllocLds &L, const AllocPrm *p, int ms)
         gz = L.gzero[ch][i];
         act = (gsf < gz) ? -1 : 0;
     }
-    int gact = half_max((band && act) ? gsf : -1);          // max over active bands, -1 if none
-    int gzmax = half_max(band ? gz : -1);
+    int gact = hx_half_max((band && act) ? gsf : -1);          // max over active bands, -1 if none
+    int gzmax = hx_half_max(band ? gz : -1);
     int g0init, g1init;
     if (ms) {
         g0init = L.hf_quant ? L.gsf_hf : -1;
@@ -823,7 +813,7 @@ __device__ int scale_factors(AllocLds &L, const AllocPrm *p, int ms)
             sp2 = (sf_limit_hi(1, 0, i) - sf);
             sp3 = (sf_limit_hi(1, 1, i) - sf) | (sf - sf_limit_lo(1, 1, i));
         }
-        sp0 = half_or(sp0); sp1 = half_or(sp1); sp2 = half_or(sp2); sp3 = half_or(sp3);
+        sp0 = hx_half_or(sp0); sp1 = hx_half_or(sp1); sp2 = hx_half_or(sp2); sp3 = hx_half_or(sp3);
         if (sp0 >= 0) { scale = 0; pre = 0; }
         else if (sp1 >= 0) { scale = 0; pre = 1; }
         else if (sp2 >= 0) { scale = 1; pre = 0; }
@@ -872,7 +862,7 @@ __device__ int scale_factors(AllocLds &L, const AllocPrm *p, int ms)
         if (band) { L.gsf[ch][i] = gsf; L.sf[ch][i] = sf; L.active[ch][i] = silent ? 0 : act; }
     }
     if (i == 0) { L.G[ch] = Gtmp; L.preemp[ch] = pre; L.scale[ch] = scale; }
-    SYNC();
+    HX_WAVE_SYNC();
     return 0;
 }
 
@@ -1024,7 +1014,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         const int incl = hx_wave_scan(nc), total = __builtin_amdgcn_readlane(incl, 63);
 #pragma unroll
         for (int c = 0; c < 6; c++) if (c < nc) list[incl - nc + c] = (c << 8) | (ch << 7) | i;
-        SYNC();
+        HX_WAVE_SYNC();
         const int ncmax = hx_wave_max(nc);
         const bool bslow = mode == 1 && noise_band_needs_pow(LK_IGAIN(GG - s), L.x34max[ch][i]);
         PROF_ACC(HX_PROF_LUCKY_SETUP);
@@ -1035,14 +1025,14 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         lucky_dispatch(L, nl, ncmax, tf, 0, big);
         if (two) HELPER_JOIN();
         else lucky_dispatch(L, nl, ncmax, tf, 1, big);
-        SYNC();
+        HX_WAVE_SYNC();
         PROF_ACC(HX_PROF_LUCKY_TERMS);
         for (int u = LANE; u < total; u += 64) {
             const int e = list[u], c = e >> 8, cc = (e >> 7) & 1, b = e & 31;
             float sxx = band_sum(tf + c * 2 * nl + cc * nl + L.startBand[b], L.nBand[b], 0.0f);
             L.lucky[c][cc][b] = MBLOG(1.0e-12f + sxx) - L.logcbw[b];
         }
-        SYNC();
+        HX_WAVE_SYNC();
         PROF_ACC(HX_PROF_LUCKY_SUMS);
         {   // replay the reference's scan: the last candidate that meets the target wins
             int nz[6];
@@ -1059,7 +1049,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
                 if (!(s >= s0) || (GG - s) >= g0) mode = 2;
             }
         }
-        SYNC();
+        HX_WAVE_SYNC();
         PROF_ACC(HX_PROF_LUCKY_REPLAY);
     }
     if (mode == 2) {
@@ -1071,7 +1061,7 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
     // (found by the round-3 sweep with nsb_limit in the draw).  Lines past the coded range are zero by contract.
     // (the low-footprint layout keeps the list elsewhere, and its quantiser writes every line)
     if (!HX_SLIM) { for (int j = p->nbmax[0] + LANE; j < 6 * 26; j += 64) IX(0)[j] = 0; }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallo3.cpp:1540-1585 with l3math.c:656-694: quantise every coded band
@@ -1129,14 +1119,14 @@ __device__ void do_quant(AllocLds &L, const AllocPrm *p, int opt)
         L.ixmax[ch][i] = (i < p->nsf[ch]) ? 0 : L.ixmax[ch][i];
         L.gig[ch][i] = LK_IGAIN(L.gsf[ch][i] & 127);     // the band's 1/gain^(3/4), read per line below
     }
-    SYNC();
+    HX_WAVE_SYNC();
     // three lines per lane and chunk: band -> igain -> rounding offset are dependent LDS reads,
     // the three chains overlap; stores (and the band maximum) come after all loads of the chunk
     const bool two = p->nbmax[1] > 0;
     if (two) HELPER_POST(HCMD_QUANT, opt);          // channel 1 on the helper wave
     quant_lines(L, p, opt, 0);
     if (two) HELPER_JOIN();
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // ---------------------------------------------------------------------------------------
@@ -1425,7 +1415,7 @@ __device__ int count_bits(AllocLds &L, const AllocPrm *p, const int *ncb)
     if (two) HELPER_POST(HCMD_COUNT_BITS, ncb[1]);
     int bits = count_bits_ch(L, p, 0, ncb[0]);
     if (two) { HELPER_JOIN(); bits += L.hs_bits[1]; }
-    SYNC();
+    HX_WAVE_SYNC();
     return bits;
 }
 
@@ -1440,20 +1430,20 @@ __device__ int quant_count_bits(AllocLds &L, const AllocPrm *p, int opt, int zer
         L.ixmax[ch][i] = (i < p->nsf[ch]) ? 0 : L.ixmax[ch][i];
         L.gig[ch][i] = LK_IGAIN(L.gsf[ch][i] & 127);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_CNT(HX_PROF_N_COUNTS);
     const bool two = p->nchan == 2;
     PROF_T0();
     if (two) HELPER_POST2(HCMD_QUANT_COUNT, opt, ncb[1]);
     PROF_ACC(HX_PROF_QC_POST);
     quant_lines(L, p, opt, 0);
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_QC_QUANT);
-    if (zero21) { if (LANE == 0) L.ixmax[0][21] = 0; SYNC(); }
+    if (zero21) { if (LANE == 0) L.ixmax[0][21] = 0; HX_WAVE_SYNC(); }
     int bits = count_bits_ch(L, p, 0, ncb[0]);
     PROF_T1();
     if (two) { HELPER_JOIN(); bits += L.hs_bits[1]; }
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_QC_JOIN);
     return bits;
 }

@@ -57,7 +57,7 @@ __device__ void a1_sigmask(AllocLds &L, const AllocPrm *p, const float *etab, co
         L.a_sig[ch][m] = sig;
         L.a_smask[ch][m] = mask;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // signs, magnitudes, band energies, M/S and intensity processing, masks in dB (bitallo1.cpp:634-907)
@@ -98,7 +98,7 @@ __device__ void a1_smr(AllocLds &L, const AllocPrm *p, const HxParams *gp, const
         }
         L.xsxx[0][i] = e0; L.xsxx[1][i] = e1;
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (cx.is && cx.ms && ch == 0 && i >= 5 && i < nsf_st) {   // thin out the side channel: pairs weaker than a share of the band pair go
         const int k0 = L.startBand[i], n = L.nBand[i];
         const float ss = gp->a1_sparse[i];
@@ -145,15 +145,15 @@ __device__ void a1_smr(AllocLds &L, const AllocPrm *p, const HxParams *gp, const
         const float sg = L.a_sig[0][i] + L.a_sig[1][i], mk = L.a_smask[0][i] + L.a_smask[1][i];
         L.a_mask[0][i] = a1_mask_db(gp, sg, mk, e0 + e1, i);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (A1_BAND(cx) && (!cx.is || i < nsf_st)) L.a_mask[ch][i] = a1_mask_db(gp, L.a_sig[ch][i], L.a_smask[ch][i], L.xsxx[ch][i], i);
-    SYNC();
+    HX_WAVE_SYNC();
     if (cx.is && cx.ms && i < nsf_st) {
         const float m = 0.5f * (L.a_mask[0][i] + L.a_mask[1][i]);
-        SYNC();
+        HX_WAVE_SYNC();
         L.a_mask[ch][i] = m;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // x^(3/4) of the coded lines, band maxima, zero-gain steps (bitallo1.cpp:589-631); returns the largest x^(3/4)
@@ -176,7 +176,7 @@ __device__ float a1_x34(AllocLds &L, const AllocPrm *p, const HxParams *gp, cons
         L.gmin[ch][i] = max(0, gz - GMIN_OFFSET);
     }
     const int mm = hx_wave_max(__float_as_int(m));      // x^(3/4) >= 0: the bit patterns order like the values
-    SYNC();
+    HX_WAVE_SYNC();
     return __int_as_float(mm);
 }
 
@@ -184,7 +184,7 @@ __device__ __forceinline__ void a1_ixmax(AllocLds &L, const AllocPrm *p, const A
 {
     HX_LANE_DECL;
     if (A1_BAND(cx)) L.ixmax[A1_CH][A1_I] = (int) ((0.5f - 0.0946f) + L.x34max[A1_CH][A1_I] * L.look_34igain[L.gsf[A1_CH][A1_I]]);
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 __device__ __forceinline__ int a1_bit_est(AllocLds &L, const AllocPrm *p, const HxParams *gp, const A1Ctx cx)
@@ -214,7 +214,7 @@ __device__ int a1_bit_seek(AllocLds &L, const AllocPrm *p, const HxParams *gp, c
             int dG = (int) (dGdB * delta);
             if (dG < 1) dG = 1;
             if (band) L.gsf[ch][i] = min(L.gsf[ch][i] + dG, L.gzero[ch][i]);
-            SYNC();
+            HX_WAVE_SYNC();
             a1_ixmax(L, p, cx);
             nbits = a1_bit_est(L, p, gp, cx);
             delta = nbits - target;
@@ -234,7 +234,7 @@ __device__ int a1_bit_seek(AllocLds &L, const AllocPrm *p, const HxParams *gp, c
         int g = 0;
         if (band) { g = max(L.gsf[ch][i] - dG, 0); L.gsf[ch][i] = g; }
         const int gz_flag = hx_wave_or(g);
-        SYNC();
+        HX_WAVE_SYNC();
         a1_ixmax(L, p, cx);
         nbits = a1_bit_est(L, p, gp, cx);
         delta = target - nbits;
@@ -290,7 +290,7 @@ __device__ int a1_noise_seek(AllocLds &L, const AllocPrm *p, const HxParams *gp,
         L.tmp[0] = n;
         if (n > 1) { const float a = asum / n; L.a_alpha = a; L.tmp[1] = __float_as_int(a); }
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (L.tmp[0] <= 1) return 0;
     const float a = __int_as_float(L.tmp[1]);
     int dgmax = 0;
@@ -337,7 +337,7 @@ __device__ int a1_noise_seek(AllocLds &L, const AllocPrm *p, const HxParams *gp,
         }
     }
     dgmax = hx_wave_max(max(dgmax, 0));
-    SYNC();
+    HX_WAVE_SYNC();
     return dgmax;
 }
 
@@ -384,7 +384,7 @@ __device__ int a1_scale_factors(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
     if (i == 0 && ch >= cx.c0 && ch < cx.c0 + cx.nch) { L.G[ch] = Gout; L.preemp[ch] = pre; L.scale[ch] = scale; }
     const int in = (i == 0 && ch >= cx.c0 && ch < cx.c0 + cx.nch) ? (Gtmp < 0 ? 100 : Gtmp) : 999;
     const int gmin = -hx_wave_max(-in);
-    SYNC();
+    HX_WAVE_SYNC();
     return gmin;
 }
 
@@ -403,10 +403,10 @@ __device__ int a1_quant_count(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
             for (int k = k0; k < k0 + n; k++) L.ix[ch][k] = (int) ((0.5f - 0.0946f) + L.x34[ch][k] * igain);
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
     int bits = 0;
     for (int c = cx.c0; c < cx.c0 + cx.nch; c++) bits += count_bits_ch(L, p, c, p->nsf[c]);
-    SYNC();
+    HX_WAVE_SYNC();
     return bits;
 }
 
@@ -427,7 +427,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
     int target_bits = max(target_bits_arg - (target_bits_arg >> 4), min_bits);
     if (LANE == 0) L.block_type = 0;
     if (mych && i < NB) { L.ixmax[ch][i] = 0; L.sf[ch][i] = (cx.is && ch == 1) ? L.sf[ch][i] : 0; }
-    SYNC();
+    HX_WAVE_SYNC();
     a1_smr(L, p, gp, cx);
     const float x34mm = a1_x34(L, p, gp, cx);
     if (x34mm < 3.0f) {     // nothing worth coding in this granule
@@ -441,7 +441,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
             g->aux_nreg[0] = g->aux_nreg[1] = g->aux_nreg[2] = 0;
         }
         if (mych && i < NB) L.sfout[igr][ch][i] = 0;
-        SYNC();
+        HX_WAVE_SYNC();
         return;
     }
     if (LANE == 0) {
@@ -458,12 +458,12 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
     target0_max -= bitadjust;
     if (band) L.gsf[ch][i] = min(L.gsf[ch][i], L.gzero[ch][i]);        // start from the previous granule's gains
     if (mych && i < NB) L.a_lastGsf[ch][i] = -9999;
-    SYNC();
+    HX_WAVE_SYNC();
     // stage 1: noise estimated from each band's largest quantised value
     int nbits = a1_bit_seek(L, p, gp, cx, target0, dGdB);
     for (int it = 0; it < 4; it++) {
         if (band) L.a_noise[ch][i] = a1_noise_of(tab + 256, L.ixmax[ch][i], L.gsf[ch][i]);
-        SYNC();
+        HX_WAVE_SYNC();
         const int dsf = a1_noise_seek(L, p, gp, tab, cx, 0);
         if (dsf <= 0) break;
         nbits = a1_bit_seek(L, p, gp, cx, target0, dGdB);
@@ -472,7 +472,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
     // stage 2: noise estimated line by line; the bit target follows the noise level reached
     for (int it = 0; it < 4; it++) {
         if (band) a1_noise_cb(L, gp, tab, 1, ch, i);
-        SYNC();
+        HX_WAVE_SYNC();
         const int dsf = a1_noise_seek(L, p, gp, tab, cx, 1);
         if (dsf <= 0) break;
         int target = (int) (target0 + 0.5f * dBG * (L.a_alpha - L.a_ave));
@@ -481,7 +481,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
         if (dsf < 2) break;
     }
     if (mych && i < NB) L.a_lastGsf[ch][i] = -9999;
-    SYNC();
+    HX_WAVE_SYNC();
     a1_scale_factors(L, p, cx);
     int bits = a1_quant_count(L, p, cx);
     bitadjust = bitadjust + ((bits - nbits - bitadjust) >> 3);
@@ -496,7 +496,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
         int g = 0;
         if (band) { g = max(L.gsf[ch][i] - dG, 0); L.gsf[ch][i] = g; }
         const int gz_flag = hx_wave_or(g);
-        SYNC();
+        HX_WAVE_SYNC();
         a1_scale_factors(L, p, cx);
         bits = a1_quant_count(L, p, cx);
         if (gz_flag == 0) break;
@@ -506,7 +506,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
         int dG = (int) (dGdB * (bits - max_bits));
         if (dG < 1) dG = 1;
         if (band) L.gsf[ch][i] += dG;
-        SYNC();
+        HX_WAVE_SYNC();
         const int GG = a1_scale_factors(L, p, cx);
         bits = a1_quant_count(L, p, cx);
         if (GG >= 100) break;
@@ -525,7 +525,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
         } else if (cx.is && ch == 1 && i < p->nsf[0]) s = L.sf[1][i];      // intensity position
         L.sfout[igr][ch][i] = (i < 21) ? s : 0;
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (cx.is && LANE == 0) {   // below the intensity part, trailing silent bands of the right channel carry "no intensity"
         for (int b = p->nsf[1] - 1; b >= 0; b--) {
             if (L.ixmax[1][b] > 0) break;
@@ -543,5 +543,5 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
         g->aux_not_null = (cx.is && c == 1) ? 1 : L.huff_bits[c];      // the right channel's scalefactors carry the intensity positions
         huffsel_to_gr(L, c, g);
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }

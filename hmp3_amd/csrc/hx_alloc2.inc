@@ -1,6 +1,6 @@
 // hx_alloc2.inc - second half of the K6 allocator kernel (included by hx_alloc.hip):
-// -HF band handling, rate loop, scalefactor refinement, MNR feedback, bitstream packing,
-// reservoir / frame assembly and the kernel entry point.
+// -HF band handling, rate loop, scalefactor refinement, MNR feedback, bitstream packing and
+// reservoir / frame assembly (the kernel entry point is in hx_alloc3.inc).
 
 // ---- -HF support (reference bitallo3.cpp:1635-1737, 2421-2563) ----
 __device__ HX_HFN void clear_hf(AllocLds &L, int nch)
@@ -8,7 +8,7 @@ __device__ HX_HFN void clear_hf(AllocLds &L, int nch)
     HX_LANE_DECL;
     for (int ch = 0; ch < nch; ch++)
         for (int j = LANE; j < L.nBand[21]; j += 64) IX(ch)[L.startBand[21] + j] = 0;
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // quantise band 21 at the global gain with the first rounding offset replaced (l3math.c:698-727)
@@ -17,7 +17,7 @@ __device__ HX_HFN void quant_hf_ch(AllocLds &L, int ch, int sparse)
     HX_LANE_DECL;
     const int o = L.startBand[21], n = L.nBand[21];
     if (LANE == 0) L.ixmax[ch][21] = 0;
-    SYNC();
+    HX_WAVE_SYNC();
     const float igain = LK_IGAIN(L.G[ch]);
     for (int j = LANE; j < n; j += 64) {
         float t = igain * L.x34[ch][o + j] + (0.5f - 0.4375f);
@@ -28,7 +28,7 @@ __device__ HX_HFN void quant_hf_ch(AllocLds &L, int ch, int sparse)
         IX(ch)[o + j] = q;
         if (q > 0) atomicMax(&L.ixmax[ch][21], q);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (sparse) {       // sparse_quad_counted(qx, n, 4): serial, rare
         if (LANE == 0) {
             ix_t *qx = IX(ch) + o;
@@ -45,7 +45,7 @@ __device__ HX_HFN void quant_hf_ch(AllocLds &L, int ch, int sparse)
                     }
                 }
         }
-        SYNC();
+        HX_WAVE_SYNC();
     }
 }
 
@@ -63,7 +63,7 @@ __device__ HX_HFN int hf_adjust_ch(AllocLds &L, const AllocPrm *p, int ch, int *
         else if (gmax0 > gmax1) {
             int gset = max(gtar, gmax1);
             if (L.gzero[ch][21] > gset) {
-                SYNC();     // everyone has read gsf before lane 0 edits it
+                HX_WAVE_SYNC();     // everyone has read gsf before lane 0 edits it
                 if (LANE == 0)
                     for (int i = 0; i < 11; i++)
                         if (L.gsf[ch][i] < L.gzero[ch][i] && L.gsf[ch][i] > gset) L.gsf[ch][i] = gset;
@@ -71,7 +71,7 @@ __device__ HX_HFN int hf_adjust_ch(AllocLds &L, const AllocPrm *p, int ch, int *
             }
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
     *gsf_hf_out = gout;
     return res;
 }
@@ -88,7 +88,7 @@ __device__ HX_HFN void hf_adjust(AllocLds &L, const AllocPrm *p)
         if (r1) L.hf_quant_stereo[1] = 1;
         L.hf_quant = L.hf_quant_stereo[0] | L.hf_quant_stereo[1];
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 __device__ HX_HFN void hf_adjust_ms(AllocLds &L, const AllocPrm *p)
@@ -97,7 +97,7 @@ __device__ HX_HFN void hf_adjust_ms(AllocLds &L, const AllocPrm *p)
     int g0 = -1;
     int r0 = hf_adjust_ch(L, p, 0, &g0);
     if (LANE == 0 && r0) { L.hf_quant = 1; if (g0 >= 0) L.gsf_hf = g0; }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 __device__ HX_HFN void hf_reset_lr(AllocLds &L)
@@ -109,7 +109,7 @@ __device__ HX_HFN void hf_reset_lr(AllocLds &L)
         L.gsf_hf_stereo[0] = L.gsf_hf_stereo[1] = -1;
         L.ixmax[0][21] = L.ixmax[1][21] = 0;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 __device__ HX_HFN void hf_reset_ms(AllocLds &L, int both)
 {
@@ -120,7 +120,7 @@ __device__ HX_HFN void hf_reset_ms(AllocLds &L, int both)
         if (both) L.ixmax[1][21] = 0;
         L.gsf_hf = -1;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // ---- trade_dual (L/R only; reference bitallo3.cpp:2216-2306): flatten isolated peaks ----
@@ -137,7 +137,7 @@ __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
         L.ixmax[ch][i] = (int) (t - L.quant_off[iq]);
         L.ix10xmax[ch][i] = (int) (10.0f * (t - L.quant_off[iq]) + (0.5f - 5.0f));
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (i == 0) {       // one lane per channel runs the short serial scan
         // target_table = {0, 1, 2, 3, 3, 5, 5, 7, 7, 7, 7, 15, 15, 15, 15, 15} as nibbles; of the rounding offsets qo[16] =
         // {0.09460, 0.02799, 0.01671, 0.01192, 0.00927, 0.00758, 0.00641, 0.00556, ..., 0.00269} only the entries a
@@ -182,7 +182,7 @@ __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
             }
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // ---- rate loop pieces ----
@@ -200,7 +200,7 @@ __device__ HX_RATE int requant_count(AllocLds &L, const AllocPrm *p, int ms, int
             if (!L.hf_quant) return quant_count_bits(L, p, 1, 1, p->nsf2);     // one hand-over to the helper wave instead of two
             do_quant(L, p, 1);
             if (LANE == 0) L.ixmax[0][21] = 0;
-            SYNC();
+            HX_WAVE_SYNC();
             quant_hf_ch(L, 0, 0);
             return count_bits(L, p, p->nsf2);
         }
@@ -230,13 +230,13 @@ __device__ HX_RATE int increase_bits(AllocLds &L, const AllocPrm *p, int bits0, 
     int g = band ? L.gsf[ch][i] : 0, bits = bits0;
     for (int k = 0; k < 10; k++) {
         if (band) { g = max(g - 1, L.gmin[ch][i]); L.gsf[ch][i] = g; }
-        SYNC();
+        HX_WAVE_SYNC();
         bits = requant_count(L, p, ms, 1, 1);
         if (bits >= thres) break;
     }
     if (bits > L.maxTargetBits) {       // went too far: step back once
         if (band) L.gsf[ch][i] = g + 1;
-        SYNC();
+        HX_WAVE_SYNC();
         bits = requant_count(L, p, ms, 1, 1);
     }
     return bits;
@@ -253,14 +253,14 @@ __device__ HX_RATE int decrease_bits(AllocLds &L, const AllocPrm *p, int bits0)
     for (int k = 0; k < 10; k++) {
         dmnr += deltaN;
         if (band) L.NT[ch][i] += deltaN;
-        SYNC();
+        HX_WAVE_SYNC();
         seek_actual(L, p);
         bits = requant_count(L, p, 0, 0, 0);
         if (bits <= L.maxTargetBits) break;
         deltaN = max((f * (bits - L.maxTargetBits)) >> 10, 40);
     }
     if (LANE == 0) L.deltaMNR = dmnr;
-    SYNC();
+    HX_WAVE_SYNC();
     return bits;
 }
 
@@ -273,7 +273,7 @@ __device__ HX_RATE int limit_bits(AllocLds &L, const AllocPrm *p, int part23)
     int bits = 0;
     for (int k = 0; k < 100; k++) {
         if (band && !(part23 && L.huff_bits[ch] <= PART23)) L.gsf[ch][i] = min(127, L.gsf[ch][i] + 1);
-        SYNC();
+        HX_WAVE_SYNC();
         bits = requant_count(L, p, 0, 0, 0);
         if (part23) { if ((L.huff_bits[0] <= PART23) && (L.huff_bits[1] <= PART23)) break; }
         else if (bits <= L.maxBits) break;
@@ -357,7 +357,7 @@ __device__ void isf2_ch(AllocLds &L, const AllocPrm *p, int ch)
         // band or not: unread garbage is cheaper than a predicate)
         if (LANE == 0) atomicAdd(&L.nstrict, 1);
         isf2_lines(L, p, ch);
-        SYNC();
+        HX_WAVE_SYNC();
         if (strict) {
 #if HX_SLIM
             band_sum2(&L.x34[ch][L.startBand[ib]], &L.xr[ch][L.startBand[ib]], L.nBand[ib], &sqq, &sxx);
@@ -383,13 +383,13 @@ __device__ void inverse_sf2(AllocLds &L, const AllocPrm *p)
     const int ch = LANE >> 5, i = LANE & 31;
     const bool sel = (i < p->nsf[ch]) && ((L.ixmax[ch][i] == 1) || (L.ixmax[ch][i] == 2));
     if (i < NB) L.geval[ch][i] = sel ? 1 : -1;
-    if (!__any(sel)) { SYNC(); return; }
-    SYNC();
+    if (!__any(sel)) { HX_WAVE_SYNC(); return; }
+    HX_WAVE_SYNC();
     const bool two = p->nbmax[1] > 0;
     if (two) HELPER_POST(HCMD_ISF2, 0);             // channel 1 on the helper wave
     isf2_ch(L, p, 0);
     if (two) HELPER_JOIN();
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallo3.cpp:2948-3046 (ms = 0) / 3048-3149 (ms = 1)
@@ -412,7 +412,7 @@ __device__ int allocate(AllocLds &L, const AllocPrm *p, int ms)
         PROF(HX_PROF_DO_QUANT, do_quant(L, p, 1));
         if (ms) {
             if (LANE == 0) L.ixmax[0][21] = 0;
-            SYNC();
+            HX_WAVE_SYNC();
             if (L.hf_quant) quant_hf_ch(L, 0, 0);
             PROF(HX_PROF_QUANT_COUNT, bits0 = bits = count_bits(L, p, p->nsf2));
         } else {
@@ -453,7 +453,7 @@ __device__ void mnr_feedback(AllocLds &L, const AllocPrm *p, int activeBands, in
         if (bits > (L.TargetBits + 2000)) M = min(M, p->initialMNR);
         L.MNR = M;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitalloc.cpp:758-811
@@ -520,7 +520,7 @@ __device__ bool bitallo_long(AllocLds &L, const AllocPrm *p, int igr, int block_
         L.TargetBits = target_bits; L.PoolBits = bit_pool;
     }
     if (!HX_SLIM && block_type == 3) for (int j = LANE; j < 1152; j += 64) IX(0)[j] = 0;     // (low-footprint layout: the quantiser writes every line)
-    SYNC();
+    HX_WAVE_SYNC();
     PROF(HX_PROF_STARTUP, startup_prepped(L, p, ms, bin));
 
     HxGr *g0 = &L.gr[igr][0];
@@ -538,7 +538,7 @@ __device__ bool bitallo_long(AllocLds &L, const AllocPrm *p, int igr, int block_
             g->aux_nreg[0] = g->aux_nreg[1] = g->aux_nreg[2] = 0;
         }
         if (LANE < 44) L.sfout[igr][LANE / 22][LANE % 22] = 0;
-        SYNC();
+        HX_WAVE_SYNC();
         return false;
     }
     int fb = allocate(L, p, ms);
@@ -575,7 +575,7 @@ __device__ bool bitallo_long(AllocLds &L, const AllocPrm *p, int igr, int block_
         g->aux_not_null = L.huff_bits[c];
         huffsel_to_gr(L, c, g);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     return true;
 }
 
@@ -666,7 +666,7 @@ __device__ HX_COLD void compute_mask_short(AllocLds &L, const AllocPrm *p, const
         }
         L.s_maskmb[ch][0][i] = mb0; L.s_maskmb[ch][1][i] = mb1; L.s_maskmb[ch][2][i] = mb2;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // 32-byte stereo side information (reference l3pack.c:1123-1187), whole wave: lanes 0..3 build
@@ -676,7 +676,7 @@ __device__ void build_side(AllocLds &L, const AllocPrm *p, unsigned *sidew, cons
 {
     HX_LANE_DECL;
     if (LANE < 10) sidew[LANE] = 0;
-    SYNC();
+    HX_WAVE_SYNC();
     if (LANE < 5) {
         unsigned long long v = 0;
         int pos, n;
@@ -725,7 +725,7 @@ __device__ void build_side(AllocLds &L, const AllocPrm *p, unsigned *sidew, cons
             if (n + o > 64) { const unsigned w2 = (unsigned) (v << (96 - n - o)); if (w2) atomicOr(&sidew[wi + 2], w2); }
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 // ... and as bytes at dst (the packet outputs; a frame's own side information leaves through the outbox)
 __device__ HX_COLD void pack_side(AllocLds &L, const AllocPrm *p, unsigned char *dst, int main_data_begin)
@@ -804,14 +804,14 @@ __device__ HX_COLD int pack_sf_lsf_is(AllocLds &L, int pos, int igr, int nsf_ste
 // box: whose staging words and side-information fields - -1 = the allocator's own (L.sidew, L.gr: packet outputs), 0 / 1 = that
 // outbox's (the helper wave, a granule later).  Chosen in here rather than passed as pointers: this function is out of line,
 // pointer arguments into LDS would be generic pointers and their accesses FLAT instructions, which the wave-local hand-overs
-// (SYNC: DS instructions in issue order, no wait) do not order (tools/check_lds_flat.py).
+// (HX_WAVE_SYNC: DS instructions in issue order, no wait) do not order (tools/check_lds_flat.py).
 __device__ HX_COLD void build_side_lsf(AllocLds &L, const AllocPrm *p, int box, int igr, int main_data_begin)
 {
     HX_LANE_DECL;
     unsigned *sidew = (box < 0) ? L.sidew : L.ob[box & 1].sidew;
     const HxGr (*gr)[2] = (box < 0) ? L.gr : L.ob[box & 1].gr;
     if (LANE < 10) sidew[LANE] = 0;
-    SYNC();
+    HX_WAVE_SYNC();
     const int mono = p->nchan == 1, h = mono ? 9 : 10;
     if (LANE < p->nchan) {
         const HxGr *g = &gr[igr][LANE];
@@ -847,7 +847,7 @@ __device__ HX_COLD void build_side_lsf(AllocLds &L, const AllocPrm *p, int box, 
         if (n + o > 64) { const unsigned w2 = (unsigned) (v << (96 - n - o)); if (w2) atomicOr(&sidew[wi + 2], w2); }
     }
     if (LANE == 4) atomicOr(&sidew[0], (unsigned) main_data_begin << 24);
-    SYNC();
+    HX_WAVE_SYNC();
 }
 __device__ HX_COLD void pack_side_lsf(AllocLds &L, const AllocPrm *p, unsigned char *dst, int igr, int main_data_begin)
 {

@@ -287,7 +287,7 @@ __device__ __forceinline__ void helper_serve(const AllocArgs &a, AllocLds &L)
         else if (cmd == HCMD_COUNT_BITS) count_bits_ch(L, &L.P, 1, order.y);
         else if (cmd == HCMD_LUCKY) lucky_dispatch(L, order.y, order.z, &L.term[0][0], 1, order.w);
         else if (cmd == HCMD_QUANT) quant_lines(L, &L.P, order.y, 1);
-        else if (cmd == HCMD_QUANT_COUNT) { quant_lines(L, &L.P, order.y, 1); SYNC(); count_bits_ch(L, &L.P, 1, order.z); }
+        else if (cmd == HCMD_QUANT_COUNT) { quant_lines(L, &L.P, order.y, 1); HX_WAVE_SYNC(); count_bits_ch(L, &L.P, 1, order.z); }
         else if (cmd == HCMD_ISF2) isf2_ch(L, &L.P, 1);
         else if (cmd == HCMD_FETCH) {
             // The next granule's operands into LDS; the finished granule's lines and the granule before's outbox to
@@ -427,7 +427,7 @@ __device__ __forceinline__ void stage_stream(const AllocArgs &a, AllocLds &L, co
     L.prof[LANE] = 0;
     if (LANE == 0) L.prof[HX_PROF_TOTAL] = (unsigned) clock64();        // (the total is a difference of the low 32 bits)
 #endif
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // Frame assembly (reference mp3enc.cpp:2258-2325 keeps main data in a ring and copies frames out
@@ -459,7 +459,7 @@ __device__ __forceinline__ void slots_init(const AllocArgs &a, AllocLds &L, int 
         COLD(pre_len)[s] = ss->main_p1;
     }
     if (LANE < 32) L.r_mf[LANE] = (unsigned short) ss->frame_mf_bytes[LANE];
-    SYNC();
+    HX_WAVE_SYNC();
     // every slot of this call, in order, for k_pack: the pending ones first, then one per new frame
     if (LANE == 0) {
         HxSlot *slots = a.slots + (long long) s * ((LSF ? 2 : 1) * F + HX_SLOTS_EXTRA);
@@ -470,7 +470,7 @@ __device__ __forceinline__ void slots_init(const AllocArgs &a, AllocLds &L, int 
             o += 4 + gp->side_bytes + L.r_mf[k];
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // A frame's budget (reference mp3enc.cpp:2241-2257 / 2117-2128; MPEG-2 :2500-2516 / :2355-2363): the reservoir's side goes to
@@ -530,7 +530,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
         // straight to k_pack; the short-block and first-generation allocators take them from the raw spectrum.)
         HELPER_JOIN();
         bin = band_fetch(BAND_LANDING);
-        SYNC();
+        HX_WAVE_SYNC();
     }
     PROF_ACC(HX_PROF_JOIN_FETCH);
     // long blocks: x^(3/4) and signs of the lines from k_prep (requested here, landed in LDS after the
@@ -544,7 +544,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
         a1_sigmask(L, p, COLD(etab) + ((long long) s * NG + g) * 128, th_g, esv, g == 0);
     }
     if (LANE < 2) { L.gr[igr][LANE].block_type = 0; }
-    SYNC();
+    HX_WAVE_SYNC();
     if (!dual) { A1Ctx cx = {0, 2, ms, RFL(p->is_flag)}; bitallo1(L, p, gp, cx, igr, b.ba_min, b.TargetBits, b.ba_max); }
 #else
     if (bt == 2) {
@@ -553,7 +553,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
         compute_mask_short(L, p, th_g, esv, g == 0, btp);
     }
     if (LANE < 2) { L.gr[igr][LANE].block_type = bt; }
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_GR_PRE);
     if (bt != 2) fetch_posted = bitallo_long(L, p, igr, bt, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, bin, g, (g + 1 < NG) ? g + 1 : -1);
     else {      // CBitAllo3::BitAllo, block_type 2 branch (reference bitallo3.cpp:496-547)
@@ -564,9 +564,9 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
             MNR0 = max(P_imnr + 400, MNR0);
         } else MNR0 = P_imnr + 400;
         if (LSF) MNR0 = min(MNR0, 850);         // bitallos.cpp:214-217
-        SYNC();
+        HX_WAVE_SYNC();
         if (LANE == 0) { L.call_count++; L.block_type = 2; }
-        SYNC();
+        HX_WAVE_SYNC();
         bitallo_short(L, p, igr, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, MNR0, L.sfs);
     }
 #endif
@@ -589,7 +589,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
             pos += bits;
             b.ba_min -= bits;
             b.ba_max -= bits;
-            SYNC();
+            HX_WAVE_SYNC();
         } else
 #pragma unroll 1
         for (int ch = 0; ch < nchan; ch++) {
@@ -605,7 +605,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
             else pos = start;
             PROF_ACC(HX_PROF_PACK_SF);
             seg_out(L, &ob.seg[ch], gg, start);
-            SYNC();
+            HX_WAVE_SYNC();
             if (LANE == 0) { gg->scalefac_compress = sc; gg->part2_3_length = bits; }
             b.ba_min -= bits;
             b.ba_max -= bits;
@@ -622,7 +622,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
         b.ba_max = b.ba_max - b.dba_max;
         b.ba_max += b.inc_max;
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // A coded frame placed: header, side information, main data (into the outbox of its last granule, for the helper wave and
@@ -725,7 +725,7 @@ __device__ __forceinline__ void place_frame(const AllocArgs &a, AllocLds &L, int
     }
     opos += hdr + mf;
     side_p1 = (side_p1 + 1) & 31;
-    SYNC();
+    HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_EMIT);
     main_tot += bytes;
     main_bytes += bytes;
@@ -752,7 +752,7 @@ __device__ __forceinline__ void place_frame(const AllocArgs &a, AllocLds &L, int
         if (LANE == 0) { L.fs.tot_bytes_out = tot_bytes_out; L.fs.ave_tot = ave_tot; }
         if ((P_oflags & 4) && LANE < 2) COLD(frame_stats)[((long long) s * F + f) * 2 + LANE] = (int) (LANE ? tot_bytes_out : tot_frames_out);
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // The end of the stream's call: the last granule's lines and outbox out, the frames that are not complete yet and the carried
@@ -765,7 +765,7 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
     HELPER_POST(HCMD_FETCH, -1);        // its outbox
     HELPER_JOIN();
     // ---- frames that are not complete yet travel to the next call in the stream state ----
-    SYNC();
+    HX_WAVE_SYNC();
     const unsigned side_p0 = L.fs.side_p0, side_p1 = L.fs.side_p1;
     const int opos = L.fs.opos;
     const int done = (side_p0 != side_p1) ? L.r_off[side_p0] : opos;       // bytes of complete frames in `out`
@@ -774,7 +774,7 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
     if (LANE < 32) ss->frame_mf_bytes[LANE] = L.r_mf[LANE];
 #ifdef HX_PROFILE
     if (LANE == 0) L.prof[HX_PROF_TOTAL] = (unsigned) clock64() - L.prof[HX_PROF_TOTAL];
-    SYNC();
+    HX_WAVE_SYNC();
     if (COLD(prof)) COLD(prof)[(long long) s * HX_PROF_WORDS + LANE] = L.prof[LANE];
 #endif
     // ---- write the stream state back ----
@@ -900,9 +900,9 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         if ((f & (GFN / 2 - 1)) == 0) {
             const unsigned char *bt_s = COLD(bt) + (long long) s * NG;
             const unsigned char *ms_s = COLD(msflag) + (long long) s * NG;
-            SYNC();
+            HX_WAVE_SYNC();
             for (int i = LANE; i < GFN; i += 64) { const int g = 2 * f + i; L.gflag[i] = (g < NG) ? (unsigned char) (bt_s[g] | (ms_s[g] << 2)) : 0; }
-            SYNC();
+            HX_WAVE_SYNC();
         }
         const int gfl = RFL((int) *reinterpret_cast<const unsigned short *>(&L.gflag[(2 * f) & (GFN - 1)]));
         const int bt0 = gfl & 3, msb1 = (gfl >> 2) & 1, bt1 = (gfl >> 8) & 3, msb2 = (gfl >> 10) & 1;
@@ -915,7 +915,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         const int shortblock_frame = (bt0 == 2) | (bt1 == 2);
         // the frame's stereo decision was made by k_msscan (hysteresis over the stream's granules)
         const int ms = (LSF && part) ? msb2 : msb1;
-        SYNC();
+        HX_WAVE_SYNC();
         PROF_ACC(HX_PROF_BUDGET);
         int pos = 0;
         for (int igr = LSF ? part : 0; igr < (LSF ? part + 1 : 2); igr++) {

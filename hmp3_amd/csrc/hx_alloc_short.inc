@@ -36,12 +36,12 @@ __device__ void s_noise_sweep(AllocLds &L, const AllocPrm *p, int ch)
             }
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (SW < 3 && SI < p->nsfs && L.s_geval[SW][SI] >= 0) {
         float sxx = band_sum(&L.term[ch][192 * SW + L.startBand_s[SI]], L.nBand_s[SI], 0.0f);
         L.s_tmpn[SW][SI] = MBLOG(1.0e-12f + sxx) - L.logcbw_s[SI];
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallos.cpp:695-741
@@ -58,7 +58,7 @@ __device__ void s_adjust_nt(AllocLds &L, const AllocPrm *p)
     if (a > 500)
         for (int ch = 0; ch < p->nchan; ch++)
             if (band && L.s_snr[ch][SW][SI] > 0) L.s_NT[ch][SW][SI] = (L.s_NT[ch][SW][SI] + a) >> 1;
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 __device__ void s_pow34_gzero(AllocLds &L, const AllocPrm *p)
@@ -69,7 +69,7 @@ __device__ void s_pow34_gzero(AllocLds &L, const AllocPrm *p)
         int c = t / 576, r = t - 576 * c, j = r % 192;
         if (j < nb) L.x34[c][r] = pow34(L, L.xr[c][r]);
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (SW < 3 && SI < p->nsfs)
         for (int ch = 0; ch < p->nchan; ch++) {
             const float *y = &L.x34[ch][192 * SW + L.startBand_s[SI]];
@@ -80,7 +80,7 @@ __device__ void s_pow34_gzero(AllocLds &L, const AllocPrm *p)
             L.s_gzero[ch][SW][SI] = gz;
             L.s_gmin[ch][SW][SI] = max(0, gz - GMIN_OFFSET);
         }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallos.cpp:475-570 (L/R) and :573-692 (M/S)
@@ -110,11 +110,11 @@ __device__ void s_startup(AllocLds &L, const AllocPrm *p, int ms, int MNR)
         if (!ms && LANE == 0) L.sgnbits[c][r >> 6] = sm;
 #endif
     }
-    SYNC();
+    HX_WAVE_SYNC();
     if (band)
         for (int ch = 0; ch < p->nchan; ch++)
             L.s_xsxx[ch][SW][SI] = band_sum(&L.term[ch][192 * SW + L.startBand_s[SI]], L.nBand_s[SI], 0.0f);
-    SYNC();
+    HX_WAVE_SYNC();
     float ssum = 0.0f, sdif = 0.0f;
     if (ms) {
         for (int r = LANE; r < 576; r += 64) {
@@ -137,7 +137,7 @@ __device__ void s_startup(AllocLds &L, const AllocPrm *p, int ms, int MNR)
             if (LANE == 0) { L.sgnbits[0][r >> 6] = m0; L.sgnbits[1][r >> 6] = m1; }
 #endif
         }
-        SYNC();
+        HX_WAVE_SYNC();
         if (band) {
             ssum = band_sum(&L.term[0][192 * SW + L.startBand_s[SI]], L.nBand_s[SI], 0.0f);
             sdif = band_sum(&L.term[1][192 * SW + L.startBand_s[SI]], L.nBand_s[SI], 0.0f);
@@ -174,7 +174,7 @@ __device__ void s_startup(AllocLds &L, const AllocPrm *p, int ms, int MNR)
     }
     act = hx_wave_sum(act);
     if (LANE == 0) L.activeBands = act;
-    SYNC();
+    HX_WAVE_SYNC();
     s_adjust_nt(L, p);
     s_pow34_gzero(L, p);
 }
@@ -193,7 +193,7 @@ __device__ void s_seek_initial(AllocLds &L, const AllocPrm *p)
             gs = max(gs, L.s_gmin[ch][SW][SI]);
             L.s_gsf[ch][SW][SI] = gs;
         }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallos.cpp:772-898: gain walk, all bands of a channel in the same sweep
@@ -210,7 +210,7 @@ __device__ void s_seek_actual(AllocLds &L, const AllocPrm *p)
             else { L.s_gsf[ch][SW][SI] = L.s_gzero[ch][SW][SI] + 5; L.s_Noise[ch][SW][SI] = L.s_Noise0[ch][SW][SI]; }
         }
         if (SW < 3) L.s_geval[SW][SI] = (mode == 1) ? s : -1;
-        SYNC();
+        HX_WAVE_SYNC();
         while (__any(mode != 0)) {
             s_noise_sweep(L, p, ch);
             if (mode == 1) {
@@ -230,7 +230,7 @@ __device__ void s_seek_actual(AllocLds &L, const AllocPrm *p)
                 if (mode == 0) { L.s_gsf[ch][SW][SI] = smin; L.s_Noise[ch][SW][SI] = tnmin; }
             }
             if (SW < 3) L.s_geval[SW][SI] = (mode != 0) ? t : -1;
-            SYNC();
+            HX_WAVE_SYNC();
         }
     }
 }
@@ -291,7 +291,7 @@ __device__ void s_scale_factors(AllocLds &L, const AllocPrm *p)
         if (SW < 3 && SI == 0) { L.s_G[ch][SW] = G; L.s_subgain[ch][SW] = sub; }
         if (LANE == 0) { L.s_GG[ch] = GG; L.scale[ch] = scale; }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallos.cpp:943-998: opt = first rounding offset replaced by -0.30
@@ -300,7 +300,7 @@ __device__ void s_do_quant(AllocLds &L, const AllocPrm *p, int opt)
     HX_LANE_DECL;
     const int nb = p->nbmax_s;
     if (SW < 3 && SI < 16) { L.s_ixmax[0][SW][SI] = 0; L.s_ixmax[1][SW][SI] = 0; }
-    SYNC();
+    HX_WAVE_SYNC();
     for (int t = LANE; t < 1152; t += 64) {
         int c = t / 576, r = t - 576 * c, w = r / 192, j = r - 192 * w;
         if (j < nb) {
@@ -318,7 +318,7 @@ __device__ void s_do_quant(AllocLds &L, const AllocPrm *p, int opt)
             if (q > 0) atomicMax(&L.s_ixmax[c][w][b], q);
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reorder channel ch from [3][192] to sfb-major bitstream order into dst (int[576]); lines past
@@ -328,7 +328,7 @@ __device__ void s_reorder_ix(AllocLds &L, const AllocPrm *p, int ch, ix_t *dst)
     HX_LANE_DECL;
     const int nb = p->nbmax_s;
     for (int t = LANE; t < 576; t += 64) dst[t] = 0;
-    SYNC();
+    HX_WAVE_SYNC();
     for (int t = LANE; t < 576; t += 64) {
         int w = t / 192, j = t - 192 * w;
         if (j < nb) {
@@ -336,7 +336,7 @@ __device__ void s_reorder_ix(AllocLds &L, const AllocPrm *p, int ch, ix_t *dst)
             dst[3 * sb + w * L.nBand_s[b] + (j - sb)] = IX(ch)[t];
         }
     }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // reference bitallosc.cpp:296-428 on the reordered spectrum (pairs never straddle windows
@@ -385,7 +385,7 @@ __device__ int s_count_bits_ch(AllocLds &L, const AllocPrm *p, int ch)
         L.hs_nbig[ch] = L.startBand_s[cb1]; L.hs_nquads[ch] = nquads; L.hs_bits[ch] = bits;
         L.huff_bits[ch] = bits;
     }
-    SYNC();
+    HX_WAVE_SYNC();
     return bits;
 }
 
@@ -407,7 +407,7 @@ __device__ void s_bump_gsf(AllocLds &L, const AllocPrm *p, int delta, int only_o
             int g = L.s_gsf[ch][SW][SI];
             L.s_gsf[ch][SW][SI] = (delta < 0) ? max(g - 1, 0) : min(127, g + 1);
         }
-    SYNC();
+    HX_WAVE_SYNC();
 }
 
 // CBitAlloShort::BitAllo (reference bitallos.cpp:202-369) for one granule, both channels.
@@ -436,7 +436,7 @@ __device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int i
             g->aux_nreg[0] = g->aux_nreg[1] = g->aux_nreg[2] = 0;
         }
         for (int t = LANE; t < 72; t += 64) sfs[t / 36][(t % 36) / 12][t % 12] = 0;
-        SYNC();
+        HX_WAVE_SYNC();
         return;
     }
     if (MNR < -200) minT = max(minT, (3 * target_bits) >> 2);
@@ -454,7 +454,7 @@ __device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int i
         int deltaN = max((f * (bits - maxT)) >> 10, 40);
         for (int k = 0; k < 10; k++) {
             if (SW < 3 && SI < p->nsfs) { L.s_NT[0][SW][SI] += deltaN; L.s_NT[1][SW][SI] += deltaN; }
-            SYNC();
+            HX_WAVE_SYNC();
             s_seek_actual(L, p);
             bits = s_requant_count(L, p, 0);
             if (bits <= maxT) break;
@@ -508,7 +508,7 @@ __device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int i
         int c = t / 36, w = (t % 36) / 12, i = t % 12;
         sfs[c][w][i] = (i < p->nsfs) ? (L.s_sf[c][w][i] >> (L.scale[c] == 0 ? 1 : 2)) : 0;
     }
-    SYNC();
+    HX_WAVE_SYNC();
     // spectrum and signs to bitstream order: only up to the end of the count1 region is kept
     for (int ch = 0; ch < p->nchan; ch++) {
         ix_t *tmp = S_SCRATCH(ch);
@@ -516,7 +516,7 @@ __device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int i
         const int nend = 3 * L.startBand_s[L.hs_cbreg[ch][2]];
         unsigned char *stmp = (unsigned char *) &L.x34[ch][0];     // x34 is dead after the last quantisation
         for (int t = LANE; t < 576; t += 64) stmp[t] = 0;
-        SYNC();
+        HX_WAVE_SYNC();
         for (int t = LANE; t < 576; t += 64) {
             int w = t / 192, j = t - 192 * w;
             if (j < p->nbmax_s) {
@@ -528,14 +528,14 @@ __device__ __noinline__ void bitallo_short(AllocLds &L, const AllocPrm *p, int i
 #endif
             }
         }
-        SYNC();
+        HX_WAVE_SYNC();
         for (int t = LANE; t < 576; t += 64) {
             IX(ch)[t] = (t < nend) ? tmp[t] : 0;
 #if !HX_SLIM
             L.signx[ch][t] = stmp[t];       // (the low-footprint layout hands the signs over from where they are)
 #endif
         }
-        SYNC();
+        HX_WAVE_SYNC();
     }
 }
 

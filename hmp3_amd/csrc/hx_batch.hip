@@ -483,7 +483,7 @@ static int launch_front(hx_batch *b, const Pass &p)
     // is made of)
     LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf);
     LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf);
-    // (the form of K4 that goes with the stream-walk kernel: hx_front.hip, spec_granule)
+    // (the form of K4 that goes with the stream-walk kernel: hx_spec.hip, spec_granule)
     if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
     else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
     // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM

@@ -1,4 +1,4 @@
-// hx_batch_src.hip - converting batches: every stream's source goes through its converter on the GPU (k_src, hx_src.inc)
+// hx_batch_src.hip - converting batches: every stream's source goes through its converter on the GPU (k_src, hx_src.hip)
 // into fp32 PCM at the encode rate, which the fp32 path encodes.  The host keeps each stream's converter call count: every
 // phase of the converter is a closed form of it (hx_src.h), so the host knows each call's input extent without converting
 // anything.

@@ -7,6 +7,18 @@
 
 #define HX_WAVE 64
 
+// The ordering point of an LDS hand-over between lanes of one wave.  A wave's LDS operations execute in issue order, so the
+// hand-over needs no workgroup barrier, only the compiler keeping the accesses in program order.  __syncthreads() would also
+// drain every outstanding global load / store (s_waitcnt vmcnt(0)): a memory round trip per call in the frame-level code.
+// (No s_waitcnt: the LDS unit takes a wave's DS instructions in issue order, so a read issued behind a write of the same
+// wave sees it whichever lane wrote; waiting for the write's completion first only adds its latency - measured 1-2 % of
+// the allocator launch.  The compiler places the waits that register results need.)
+// This promises nothing about FLAT instructions that land in LDS: tools/check_lds_flat.py fails the build check where one
+// turns up, and out-of-line functions give their pointers an address space (HX_LDS / HX_GLB) so that none does.
+#define HX_WAVE_SYNC() do { asm volatile("" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
+#define HX_LDS __attribute__((address_space(3)))
+#define HX_GLB __attribute__((address_space(1)))
+
 __device__ __forceinline__ float hx_bits2f(unsigned u) { return __uint_as_float(u); }
 __device__ __forceinline__ unsigned hx_f2bits(float f) { return __float_as_uint(f); }
 

@@ -26,7 +26,7 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 
 #ifdef __HIPCC__
-// kernels (hx_front.hip / hx_alloc.hip / hx_pack.hip / hx_src.inc)
+// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
 __global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
                             const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf);

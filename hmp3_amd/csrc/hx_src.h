@@ -1,5 +1,5 @@
 // hx_src.h - host-side sample-format / sample-rate converter in front of the encoder (hx_src.cpp), and the plan that the
-// batch's conversion kernel (hx_src.inc) runs from
+// batch's conversion kernel (hx_src.hip) runs from
 #pragma once
 #ifdef __cplusplus
 extern "C" {
@@ -36,7 +36,7 @@ int hx_src_plan(const hx_src *s, HxSrcPlan *p);
 // hx_src_schedule from a plan
 long long hx_src_plan_schedule(const HxSrcPlan *p, long long calls, int nframes, long long *in_bytes);
 
-// arguments of the conversion kernel k_src (hx_src.inc)
+// arguments of the conversion kernel k_src (hx_src.hip)
 struct SrcArgs {
     const unsigned char *in;            // [S][in_stride] bytes
     long long in_stride;

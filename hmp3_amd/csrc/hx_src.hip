@@ -1,4 +1,4 @@
-// hx_src.inc - k_src: the sample-format / sample-rate converter of converting batches (included by hx_front.hip, part 1).
+// hx_src.hip - k_src (K0a): the sample-format / sample-rate converter of converting batches, source format / rate -> fp32 PCM at the encode rate.
 // The GPU form of hx_src.cpp (reference srcc.cpp / srccf.cpp): every case (copy, exact 1:2, linear up-sampling, one
 // polyphase bank, two stages), layout (mono, stereo, stereo summed to mono) and source format (u8, s16, s24 packed, s32,
 // f32), bit-identical to hx_src_convert: each expression has hx_src.cpp's operand types (double where that code promotes),
@@ -13,6 +13,7 @@
 //  - the down-mix of case 2 is a recurrence within a call (a = a + b does not give the midpoint back in float): one lane.
 // The last call of a launch writes the carry and the call count to the other copy of each (the first call of the
 // launch reads the copy from before, so a one-call launch never reads what it writes).
+#include "hx_dev.h"
 #include "hx_src.h"
 
 // (SrcArgs: hx_src.h, shared with the launch in hx_batch_src.hip)

@@ -185,7 +185,7 @@ struct alignas(16) HxFrameOut {
 };
 #define HX_SLOTS_EXTRA 40           // slots pending from earlier calls (the ring holds 32)
 
-// k_polyphase (hx_front.hip) and its launch (hx_batch.hip): granules per workgroup (252 of 256 lanes busy: a lane is a time slot
+// k_polyphase (hx_polyphase.hip) and its launch (hx_batch.hip): granules per workgroup (252 of 256 lanes busy: a lane is a time slot
 // of a granule) and the workgroup size that follows.  One definition: the kernel's launch bounds, its LDS staging stride and
 // register array are sized by the same numbers the host launches with.
 // (7 granules: 126 of the workgroup's 128 lanes have a time slot, 37 KB of LDS, four workgroups per CU; with 14 - 252 of 256 lanes,
@@ -296,7 +296,7 @@ struct AllocArgs {
     int park_k;                 // > 0: the workgroups that share a CU with one of the first park_k workgroups of the launch order (the streams that ran
                                 // longest in the previous call) keep their slot until that one retires (hx_alloc3.inc, "parking")
     int strict_sums;            // 1 = no certified band sums: every band is added in line order (HMP3AMD_EXACT_SUMS=1; tests)
-    // from k_msscan / k_prep (hx_front.hip); xr holds the coded magnitudes for long-block granules
+    // from k_msscan (hx_spec.hip) / k_prep (hx_prep.hip); xr holds the coded magnitudes for long-block granules
     const float *x34;           // [S][NG][2][576] x^(3/4) of the magnitudes (long-block granules)
     const unsigned *sgn;        // [S][NG][2][HX_SGN_WORDS] sign of each line, one bit per line in line order (bit j & 31 of word j >> 5)
     const HxBandPrep *band;     // [S][NG]

@@ -1,11 +1,11 @@
 /* cert_sums_check.c - CPU property test of the stream walk's certified band sums (hmp3_amd/csrc/hx_dev.h, "certified band
- * sums"; hx_alloc.hip noise_sweep / inverse_sf2; hx_front.hip msmetric_unit).  Test infrastructure: restates, in plain C and fp32, the
+ * sums"; hx_alloc.hip noise_sweep / inverse_sf2; hx_spec.hip msmetric_unit).  Test infrastructure: restates, in plain C and fp32, the
  * reduction the kernels run - a lane adds its run of at most W terms (both tree shapes the kernels use), a segmented
  * Hillis-Steele scan over the band's lanes (row_shr 1/2/4/8 inside 16-lane rows, row_bcast:15 / row_bcast:31 across a row
  * boundary) - and checks, for random and adversarial vectors of non-negative terms, that the reference's strict left-to-right
  * fp32 sum (l3math.c:521-537) lies inside the interval the kernels certify with, and that a certified bucket is the strict
  * sum's bucket of mbLogC (l3math.c:228-242: exponent and top 8 mantissa bits).  The same for the quotient of two sums and for
- * the stereo metric's sums (hx_front.hip msmetric_unit).
+ * the stereo metric's sums (hx_spec.hip msmetric_unit).
  *
  *   cert_sums_check <vectors> <seed>      exit 0 = every vector inside its interval; prints the straddle rate
  * Build: gcc -O2 -ffp-contract=off -o cert_sums_check cert_sums_check.c -lm
@@ -106,7 +106,7 @@ static float rand_term(int family, int i, int n, float scale)
     }
 }
 
-/* ---- the stereo metric's band sums (hx_front.hip msmetric_unit; reference bitallo3.cpp:695-742): el = 100 + sum l^2, er = 100 + sum r^2
+/* ---- the stereo metric's band sums (hx_spec.hip msmetric_unit; reference bitallo3.cpp:695-742): el = 100 + sum l^2, er = 100 + sum r^2
  * and the signed t = sum l r feed four mbLogC arguments only: el + er, max(el, er), es + ed and max(es, ed) with es = (el + er) + 2 t,
  * ed = (el + er) - 2 t.  The kernels certify all four buckets from tree sums and intervals (the signed sum's half-width from
  * sum |l r|) and run the strict loop otherwise.  Returns 0 = certified and equal to the strict buckets, 1 = not certified, 2 = WRONG. */

@@ -1,11 +1,19 @@
 """Build checks that need no GPU: hipcc cross-compiles the kernels for gfx950 and the listings are read."""
 import os
+import re
 import subprocess
 import sys
 
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, "hmp3_amd", "csrc")
+
+
+def checked_units():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lds_flat.py"), "--print-flags"], capture_output=True, text=True, timeout=60)
+    assert r.returncode == 0
+    return {l.split()[1]: l.split()[2:] for l in r.stdout.strip().splitlines()}
 
 
 def test_no_flat_instruction_touches_lds_in_any_kernel():
@@ -15,20 +23,34 @@ def test_no_flat_instruction_touches_lds_in_any_kernel():
         pytest.skip("no hipcc on this host")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lds_flat.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
-    assert "ok (8 translation units)" in r.stdout
+    assert "ok (12 translation units)" in r.stdout
 
 
 def test_flat_check_compiles_with_the_flags_of_the_build_script():
-    """tools/check_lds_flat.py restates the per-unit flags of hmp3_amd/build.sh: the optimisation level, scheduler strategy
-    and MachineLICM switch of every translation unit must be the build's"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_lds_flat.py"), "--print-flags"], capture_output=True, text=True, timeout=60)
-    assert r.returncode == 0
-    units = {l.split()[0]: l.split()[2:] for l in r.stdout.strip().splitlines()}
+    """tools/check_lds_flat.py and hmp3_amd/build.sh both take units and flags from hmp3_amd/csrc/hx_units.tab: the optimisation
+    level, scheduler strategy and MachineLICM switch of every translation unit must be the measured ones"""
+    units = checked_units()
+    ilp, nolicm = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"], ["-mllvm", "-disable-machine-licm"]
+    for u in ("hx_alloc", "hx_alloc_slim", "hx_alloc_lsf", "hx_alloc1", "hx_alloc1_lsf"):
+        assert units[u + ".hip"] == ["-O2"] + ilp + nolicm, u
+    for u in ("hx_polyphase", "hx_src"):
+        assert units[u + ".hip"] == ["-O3", "-fno-slp-vectorize"] + nolicm, u
+    for u in ("hx_spec", "hx_prep"):
+        assert units[u + ".hip"] == ["-O3", "-fno-slp-vectorize"] + ilp, u
+    assert units["hx_pack.hip"] == ["-O3"]
     sh = open(os.path.join(ROOT, "hmp3_amd", "build.sh")).read()
-    assert '${HX_ALLOC_OPT:--O2}' in sh and 'ALLOC_SCHED="${HX_ALLOC_SCHED-$ILP}"' in sh and 'NOLICM="${HX_NOLICM--mllvm -disable-machine-licm}"' in sh
-    for u in ("alloc", "alloc_slim", "alloc_lsf", "alloc1", "alloc1_lsf"):
-        assert units[u] == ["-O2", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp", "-mllvm", "-disable-machine-licm"], u
-        assert "for f in hx_alloc hx_alloc_slim hx_alloc_lsf hx_alloc1 hx_alloc1_lsf" in sh
-    assert "-fno-slp-vectorize $NOLICM $HX_FRONT_EXTRA -DHX_FRONT_PART=1" in sh and units["front1"] == ["-O3", "-fno-slp-vectorize", "-DHX_FRONT_PART=1", "-mllvm", "-disable-machine-licm"]
-    assert "-fno-slp-vectorize $ILP $HX_FRONT_EXTRA -DHX_FRONT_PART=2" in sh and units["front2"] == ["-O3", "-fno-slp-vectorize", "-DHX_FRONT_PART=2", "-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-    assert "${HX_OPT:--O3}" in sh and units["pack"] == ["-O3"]
+    assert "hx_units.tab" in sh and not re.search(r"\bhx_\w+\.(hip|cpp|inc)\b", sh), "build.sh names a unit of its own"
+    assert '${HX_ALLOC_OPT:--O2}' in sh and 'ALLOC_SCHED="${HX_ALLOC_SCHED-$ILP}"' in sh and 'NOLICM="${HX_NOLICM--mllvm -disable-machine-licm}"' in sh and "${HX_OPT:--O3}" in sh
+
+
+def test_every_kernel_file_is_under_the_flat_check():
+    """every source that defines a __global__ function is compiled by tools/check_lds_flat.py, as a unit or through #include:
+    a new kernel file cannot stay outside the check"""
+    reached, todo = set(), list(checked_units())
+    while todo:
+        f = todo.pop()
+        if f not in reached and os.path.exists(os.path.join(SRC, f)):
+            reached.add(f)
+            todo += re.findall(r'^\s*#\s*include\s+"([^"]+)"', open(os.path.join(SRC, f)).read(), re.M)
+    kernels = {f for f in os.listdir(SRC) if re.search(r"\b__global__\b", open(os.path.join(SRC, f), errors="replace").read())}
+    assert kernels and kernels <= reached, sorted(kernels - reached)

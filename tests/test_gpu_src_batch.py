@@ -1,5 +1,5 @@
 """Converting batches (hx_batch_create_src) on the GPU: sources in any format and at any rate the converter takes,
-converted by k_src (hmp3_amd/csrc/hx_src.inc) and encoded in one call.
+converted by k_src (hmp3_amd/csrc/hx_src.hip) and encoded in one call.
 
 The converted PCM (the "srcpcm" tap) is compared with the reference's own Csrc bit for bit, and every stream's bytes and
 in_used with the reference's MP3_audio_encode loop on the same source (oracle/_ref/libhmp3ref.so) and with this library's

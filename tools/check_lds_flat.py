@@ -1,10 +1,10 @@
 """Build check: no FLAT load / store in the front-end and packing kernels, none in the stream-walk kernels beyond the
 functions listed below.  Those kernels hand data between lanes of a wave through LDS with a compiler-level ordering point
-only (FE_WAVE_SYNC / WAVE_SYNC / SYNC: a wave's DS instructions execute in issue order); the ISA promises no such order
+only (HX_WAVE_SYNC, hx_dev.h: a wave's DS instructions execute in issue order); the ISA promises no such order
 between DS and FLAT instructions, so an LDS access that compiles to FLAT (a generic pointer in an out-of-line function)
-would make those hand-overs unsound.  Compiles the translation units to assembly with the product's flags (hipcc
-cross-compiles without a GPU) and reads the listings.  Exit code 1 and a list on failure.
-  python tools/check_lds_flat.py [--keep DIR]"""
+would make those hand-overs unsound.  Compiles every hipcc unit of hmp3_amd/csrc/hx_units.tab, the table the build reads,
+to assembly with the table's flags (hipcc cross-compiles without a GPU) and reads the listings.  Exit code 1 and a list on failure.
+  python tools/check_lds_flat.py [--keep DIR | --print-flags]"""
 import os
 import re
 import subprocess
@@ -15,18 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "hmp3_amd", "csrc")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 BASE = ["--offload-arch=gfx950", "-fPIC", "-ffp-contract=off", "-fno-fast-math", "-std=c++17", '-DHX_BUILD_ID="check"', "--cuda-device-only", "-S", "-w"]
-ILP = ["-mllvm", "-amdgpu-sched-strategy=iterative-ilp"]
-NOLICM = ["-mllvm", "-disable-machine-licm"]
-UNITS = [   # (name, source, flags) as hmp3_amd/build.sh compiles them
-    ("front1", "hx_front.hip", ["-O3", "-fno-slp-vectorize", "-DHX_FRONT_PART=1"] + NOLICM),
-    ("front2", "hx_front.hip", ["-O3", "-fno-slp-vectorize", "-DHX_FRONT_PART=2"] + ILP),
-    ("pack", "hx_pack.hip", ["-O3"]),
-    ("alloc", "hx_alloc.hip", ["-O2"] + ILP + NOLICM),
-    ("alloc_slim", "hx_alloc_slim.hip", ["-O2"] + ILP + NOLICM),
-    ("alloc_lsf", "hx_alloc_lsf.hip", ["-O2"] + ILP + NOLICM),
-    ("alloc1", "hx_alloc1.hip", ["-O2"] + ILP + NOLICM),
-    ("alloc1_lsf", "hx_alloc1_lsf.hip", ["-O2"] + ILP + NOLICM),
-]
+# (unit, flag group, flags) of every hipcc line of the build's table
+UNITS = [(r[0], r[2], r[3:]) for r in (l.split() for l in open(os.path.join(SRC, "hx_units.tab")) if not l.startswith("#")) if r and r[1] == "hipcc"]
 # Functions of the stream walk whose FLAT instructions address global or private memory (checked by reading them: the
 # double-precision x^(4/3) table and the double-table counter, the psy model's outputs of the front end, packet outputs, a
 # by-reference result on the stack), with the number of FLAT instructions each has today: one more in any of them fails the
@@ -55,19 +45,19 @@ def flat_ops(path):
 
 
 def main():
-    if "--print-flags" in sys.argv:      # the flags this check compiles with, unit by unit (tests compare them with hmp3_amd/build.sh)
-        for name, src, flags in UNITS:
-            print(name, src, " ".join(flags))
+    if "--print-flags" in sys.argv:      # the flags this check compiles with, unit by unit (tests hold them against the measured choices)
+        for name, group, flags in UNITS:
+            print(name, name + ".hip", " ".join(flags))
         return
     keep = sys.argv[sys.argv.index("--keep") + 1] if "--keep" in sys.argv else None
     tmp = keep or tempfile.mkdtemp(prefix="hxflat.")
     os.makedirs(tmp, exist_ok=True)
     procs = []
-    for name, src, flags in UNITS:
+    for name, group, flags in UNITS:
         out = os.path.join(tmp, name + ".s")
-        procs.append((name, out, subprocess.Popen([HIPCC] + BASE + flags + [src, "-o", out], cwd=SRC, stderr=subprocess.PIPE)))
+        procs.append((name, group, out, subprocess.Popen([HIPCC] + BASE + flags + [name + ".hip", "-o", out], cwd=SRC, stderr=subprocess.PIPE)))
     bad = []
-    for name, out, p in procs:
+    for name, group, out, p in procs:
         err = p.communicate()[1].decode()
         if p.returncode != 0:
             print(err[-2000:], file=sys.stderr)
@@ -75,7 +65,7 @@ def main():
         ops = flat_ops(out)
         names = subprocess.run(["c++filt"], input="\n".join(ops), capture_output=True, text=True).stdout.split("\n")
         for mangled, dem in zip(ops, names):
-            if name.startswith("alloc") and allowed(dem, ops[mangled]):
+            if group == "alloc" and allowed(dem, ops[mangled]):
                 continue
             bad.append("%s: %s has %d FLAT instruction(s)" % (name, dem, ops[mangled]))
     if bad:
