@@ -187,8 +187,19 @@ class Batch:
     def out_stride(self, nframes):
         return int(lib().hx_batch_out_stride(self.h, nframes))
 
-    def encode_host(self, pcm):
-        """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, 2] -> list of bytes per stream"""
+    def packet_buffers(self, d_packet_ptr, frame_stride, d_packet_bytes_ptr):
+        """device buffers [n, nframes, frame_stride] uint8 and [n, nframes, 2] int32 that the calls that follow write
+        every frame's self-contained packet and its size(s) to; packet_buffers(None, 0, None) switches them off"""
+        lib().hx_batch_packet_buffers(self.h, d_packet_ptr, frame_stride, d_packet_bytes_ptr)
+
+    def frame_stats_buffer(self, d_stats_ptr):
+        """device buffer [n, nframes, 2] int32 that the calls that follow write the stream's frames / bytes emitted so far
+        to, after every input frame; None switches it off"""
+        lib().hx_batch_frame_stats_buffer(self.h, d_stats_ptr)
+
+    def encode_host(self, pcm, stats=False):
+        """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, 2] -> list of bytes per stream; with stats (float32
+        only) -> (that list, int32 [n, nframes, 2]: frames / bytes emitted so far after every input frame)"""
         f32 = np.asarray(pcm).dtype == np.float32
         pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
         if pcm.ndim == 2:
@@ -198,27 +209,36 @@ class Batch:
         stride = self.out_stride(nfr)
         out = np.zeros((self.n, stride), dtype=np.uint8)
         nb = np.zeros(self.n, dtype=np.int32)
-        fn = lib().hx_batch_encode_f32_host if f32 else lib().hx_batch_encode_s16_host
-        r = fn(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data)
+        if stats:
+            if not f32:
+                raise TypeError("encode_host(stats=True) takes float32 PCM (hx_batch_encode_f32_host_stats)")
+            st = np.zeros((self.n, nfr, 2), dtype=np.int32)
+            r = lib().hx_batch_encode_f32_host_stats(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data)
+        else:
+            fn = lib().hx_batch_encode_f32_host if f32 else lib().hx_batch_encode_s16_host
+            r = fn(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data)
         if r != 0:
             raise RuntimeError("hx_batch_encode host call failed: " + last_error())
-        return [out[i, :nb[i]].tobytes() for i in range(self.n)]
+        res = [out[i, :nb[i]].tobytes() for i in range(self.n)]
+        return (res, st) if stats else res
 
-    def encode_device(self, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream=None):
-        r = lib().hx_batch_encode_s16_device(self.h, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream)
-        if r != 0:
-            raise RuntimeError("hx_batch_encode_s16_device failed: " + last_error())
+    def encode_device(self, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream=None, f32=False):
+        """f32: the PCM is float32 at int16 scale (here and in the submits)"""
+        fn = lib().hx_batch_encode_f32_device if f32 else lib().hx_batch_encode_s16_device
+        if fn(self.h, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream) != 0:
+            raise RuntimeError("hx_batch_encode_%s_device failed: " % ("f32" if f32 else "s16") + last_error())
 
-    def submit_device(self, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream=None):
+    def submit_device(self, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream=None, f32=False):
         """pipelined encode_device: outputs are ordered on `stream` by wait()"""
-        r = lib().hx_batch_submit_s16_device(self.h, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream)
-        if r != 0:
-            raise RuntimeError("hx_batch_submit_s16_device failed: " + last_error())
+        fn = lib().hx_batch_submit_f32_device if f32 else lib().hx_batch_submit_s16_device
+        if fn(self.h, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream) != 0:
+            raise RuntimeError("hx_batch_submit_%s_device failed: " % ("f32" if f32 else "s16") + last_error())
 
-    def submit_host(self, pcm_ptr, nframes, out_ptr, out_stride, out_bytes_ptr):
-        """pipelined host-buffer call (int16 PCM); outputs are valid after wait_host()"""
-        if lib().hx_batch_submit_s16_host(self.h, pcm_ptr, nframes, out_ptr, out_stride, out_bytes_ptr) != 0:
-            raise RuntimeError("hx_batch_submit_s16_host failed: " + last_error())
+    def submit_host(self, pcm_ptr, nframes, out_ptr, out_stride, out_bytes_ptr, f32=False):
+        """pipelined host-buffer call; outputs are valid after wait_host()"""
+        fn = lib().hx_batch_submit_f32_host if f32 else lib().hx_batch_submit_s16_host
+        if fn(self.h, pcm_ptr, nframes, out_ptr, out_stride, out_bytes_ptr) != 0:
+            raise RuntimeError("hx_batch_submit_%s_host failed: " % ("f32" if f32 else "s16") + last_error())
 
     def wait_host(self):
         if lib().hx_batch_wait_host(self.h) != 0:

@@ -370,7 +370,7 @@ int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out,
 }
 
 // the packing kernels of one call on stream qp (see place_pack)
-static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride, int *d_out_bytes, int nframes, int set, int sset, hipStream_t qp)
+static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride, int *d_out_bytes, unsigned char *packet, int nframes, int set, int sset, hipStream_t qp)
 {
     const int S = b->S, NG = 2 * nframes;
     const WalkSet &w = b->walk[set];
@@ -381,13 +381,13 @@ static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride,
     const int solo = (S <= 4 && total <= 8) ? S : 0;
     if (solo) {
         LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-               d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, d_out_bytes, w.carry_len, b->cap_frames,
+               d_out, out_stride, packet, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, d_out_bytes, w.carry_len, b->cap_frames,
                (solo == 1) ? b->cap_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
         return 0;
     }
     LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, w.pre_len);
     LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-           d_out, out_stride, b->pk_buf, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
+           d_out, out_stride, packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
     LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, d_out_bytes, w.carry_len, b->cap_frames);
     return 0;
 }
@@ -411,7 +411,7 @@ static int flush_pack(hx_batch *b, long long gate_base)
     j.pending = false;
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
-    if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
+    if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.packet, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -421,6 +421,9 @@ static int flush_pack(hx_batch *b, long long gate_base)
 struct Pass {
     PcmIn in; int nframes; unsigned char *d_out; long long out_stride; int *d_out_bytes; PassKind kind;       // the call
     hipStream_t q, qa;                  // streams of the front end / of the stream walk and (unless deferred) the packing
+    // the caller's optional outputs as they stand when the pass starts: the stream walk and the packing of this call write
+    // these, whatever the caller sets for later calls before a deferred packing goes out
+    unsigned char *pk_buf; long long pk_stride; int *pk_bytes, *frame_stats;
     int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
                                         // submit n-2 when the front end of submit n writes them: three sets in rotation)
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
@@ -527,7 +530,7 @@ static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
     a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
     a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = p.d_out; a.out_bytes = p.d_out_bytes;
     a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = p.out_stride; a.NG = 2 * p.nframes; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
-    a.packet = b->pk_buf; a.packet_stride = b->pk_stride; a.packet_bytes = b->pk_bytes; a.frame_stats = b->frame_stats;
+    a.packet = p.pk_buf; a.packet_stride = p.pk_stride; a.packet_bytes = p.pk_bytes; a.frame_stats = p.frame_stats;
     a.done_counter = b->d_done;
     a.strict_sums = b->strict_sums;
     a.dur = b->d_dur;
@@ -585,14 +588,14 @@ static int place_pack(hx_batch *b, const Pass &p)
         HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
         if (flush_pack(b, (long long) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S)) != 0) return -1;   // the previous submit's
         hx_batch::PackJob &j = b->pack_job;
-        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
+        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.packet = p.pk_buf; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
         return 0;
     }
     if (p.kind != PASS_PLAIN) HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
     // the previous device-buffer submit's packing went out on the packing stream in pipe_enter: its k_pack_carry writes
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
-    if (enqueue_pack(b, p.d_out, p.out_stride, p.d_out_bytes, p.nframes, p.set, p.sset, qa) != 0) return -1;
+    if (enqueue_pack(b, p.d_out, p.out_stride, p.d_out_bytes, p.pk_buf, p.nframes, p.set, p.sset, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -617,7 +620,7 @@ static void reap_timings(hx_batch *b)
 int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
 {
     Poison poison{b};
-    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream};
+    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream, b->pk_buf, b->pk_stride, b->pk_bytes, b->frame_stats};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
     if (pipe_enter(b, p) != 0 || launch_front(b, p) != 0) return -1;

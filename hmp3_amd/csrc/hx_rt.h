@@ -139,7 +139,8 @@ struct hx_batch {
     hipEvent_t ev_sgn[3] = {nullptr, nullptr, nullptr}; // the packing that read this set of signs is done
     // the packing of the latest device-buffer submit, not enqueued yet: it goes out behind the next submit's allocator launch
     // (released by a gate like the front end, into that launch's tail), or ungated at the next wait / plain call
-    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; int nframes = 0, set = 0, sset = 0; } pack_job;
+    // (packet: the packet buffer in force at the submit - the stream walk has put the packets' headers there already)
+    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; unsigned char *packet = nullptr; int nframes = 0, set = 0, sset = 0; } pack_job;
     long long nsubmit = 0;
     bool inflight = false;
     // hx_batch_submit_*_host: device staging for two calls in flight and the copy streams

@@ -151,7 +151,9 @@ int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nframes, unsigne
    submits overlap: the front-end kernels of call n+1 and the bit packing of call n-1 run on the SIMDs
    that the allocator kernel of call n leaves idle while its slowest streams finish.  Hand consecutive
    submits different d_out / d_out_bytes (two sets in turn): with overlapping ones the result is the
-   same, but the allocator launch waits for the previous call's packing. */
+   same, but the allocator launch waits for the previous call's packing.
+   hx_batch_wait enqueues the packing that the last submit left for later: it writes that submit's d_out and, where
+   packet outputs were on at the submit, that submit's packet buffer - they must still be valid then. */
 int hx_batch_submit_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
                                long long out_stride, int *d_out_bytes, void *stream);
 int hx_batch_submit_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
@@ -173,11 +175,17 @@ void hx_pinned_free(void *p);
    d_packet_bytes [nstreams][nframes][2] (the reference's nbytes_out[2] of every call: {size, 0},
    or the sizes of the two back-to-back packets of an MPEG-2 call); frame_stride >= the packet
    bytes of one call (4096 is always enough).  NULL switches them off.  Applies to the calls
-   that follow. */
+   that follow: a call writes the buffers in force when it is made - a submit too, all of whose
+   packet output (sizes, headers, side info and the main data its deferred packing adds) goes to the
+   buffers set at the submit, whatever is set or switched off afterwards.  Like d_out they must stay
+   valid until the hx_batch_wait behind the submit.  Consecutive submits take different packet
+   buffers (two sets in turn, like d_out): a submit's stream walk writes its packets' headers while
+   the previous submit's packing may still be writing main data, and nothing orders the two. */
 void hx_batch_packet_buffers(hx_batch *b, unsigned char *d_packet, long long frame_stride, int *d_packet_bytes);
 /* optional per-frame counters of the batched calls: d_stats [nstreams][nframes][2] = the stream's
    get_frames() / bytes emitted so far after each input frame, i.e. what a caller of the per-frame
-   API (CMp3Enc::L3_audio_encode_get_frames_bytes after every call) would have seen.  NULL = off. */
+   API (CMp3Enc::L3_audio_encode_get_frames_bytes after every call) would have seen.  NULL = off.
+   Applies to the calls that follow; a call writes the buffer in force when it is made. */
 void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats);
 /* fp32 host call that also returns those counters to a host array stats[nstreams][nframes][2] */
 int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
@@ -189,8 +197,8 @@ int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *
    there), 4 = the Huffman bits packed for a channel differ from the bits counted for it (an internal
    consistency check of the two-wave packer).  0 = healthy; -1 = no answer (the batch became unusable after a
    failed device call, or the status could not be read).  Synchronises - and, like hx_batch_wait, first enqueues the
-   packing that the last hx_batch_submit_*_device left for later: that writes the submit's output buffers, which must
-   therefore still be valid.
+   packing that the last hx_batch_submit_*_device left for later: that writes the submit's output buffers (d_out,
+   d_out_bytes and the packet buffer that was set at the submit), which must therefore still be valid.
    hx_batch_gate_timeouts: how many pipelined submits started their front end late because the gate on the previous
    allocator launch gave up waiting (results are correct, overlap was lost; a loaded or profiled GPU can cause it).
    It is a performance counter, not part of the health status. */

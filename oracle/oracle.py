@@ -59,6 +59,8 @@ def lib():
         _lib.hxo_mbexp.restype = C.c_float
         _lib.hxo_frames_out.argtypes = [C.c_void_p]
         _lib.hxo_frames_out.restype = C.c_uint
+        _lib.hxo_bytes_out.argtypes = [C.c_void_p]
+        _lib.hxo_bytes_out.restype = C.c_uint
     return _lib
 
 
@@ -78,6 +80,8 @@ def ref():
             _ref.ref_encode_stream_s16.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_long]
             _ref.ref_encode_stream_s16.restype = C.c_long
             _ref.ref_dump.argtypes = [C.c_void_p, C.c_void_p]
+            _ref.ref_frames.argtypes = [C.c_void_p]
+            _ref.ref_frames.restype = C.c_uint
             _ref.ref_mbLogC.argtypes = [C.c_float]
             _ref.ref_mbExp.argtypes = [C.c_int]
             _ref.ref_mbExp.restype = C.c_float
@@ -143,6 +147,14 @@ class OracleEncoder:
         self.packet_sizes = (nb[0], nb[1])      # MPEG-2: two single-granule packets back to back
         return bytes(self.out[:n]), bytes(pk[:nb[0] + nb[1]])
 
+    def frames_out(self):
+        """frames emitted so far (L3_audio_encode_get_frames)"""
+        return int(self.l.hxo_frames_out(self.h))
+
+    def bytes_out(self):
+        """bytes emitted so far"""
+        return int(self.l.hxo_bytes_out(self.h))
+
     def __del__(self):
         try:
             self.l.hxo_free(self.h)
@@ -177,6 +189,10 @@ class RefEncoder:
         n = self.r.ref_encode_packet(self.h, frame.ctypes.data, self.out, pk, nb)
         self.packet_sizes = (nb[0], nb[1])
         return bytes(self.out[:n]), bytes(pk[:nb[0] + nb[1]])
+
+    def frames(self):
+        """L3_audio_encode_get_frames"""
+        return int(self.r.ref_frames(self.h))
 
     def dump(self):
         d = RefDump()

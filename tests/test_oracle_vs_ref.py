@@ -9,6 +9,7 @@ import pytest
 
 from oracle import oracle as O
 from hmp3_amd import synth
+import packet_cases as PC
 
 pytestmark = pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built")
 
@@ -175,6 +176,30 @@ def test_mpeg2_packet_variant_byte_identical(kw):
         a = r.encode_packet(pcm[f * 1152:(f + 1) * 1152])
         b = o.encode_packet(pcm[f * 1152:(f + 1) * 1152])
         assert a == b and r.packet_sizes == o.packet_sizes and min(r.packet_sizes) >= 13, "frame %d" % f
+
+
+@pytest.mark.parametrize("kw", PC.MPEG1 + PC.MPEG2 + PC.A1, ids=PC.case_id)
+def test_packets_and_frame_counters_for_the_batched_outputs_controls(kw):
+    """The controls of tests/test_gpu_packets.py (both allocators, MPEG-1 and MPEG-2 rates, mono): the oracle's packets, packet
+    sizes and running frame / byte counters - the expectation of the batched calls' optional outputs - against the
+    reference's L3_audio_encode_Packet and L3_audio_encode_get_frames, 4 streams x 16 frames of fp32 input with
+    non-integral samples."""
+    S, F = 4, 16
+    pcm = PC.packet_pcm(6100, S, F, kw)
+    lsf = kw.get("samprate", 44100) < 32000
+    for s in range(S):
+        r = O.RefEncoder(O.default_control(**kw), s16=False)
+        assert r.bytes_in != 0
+        want = PC.oracle_frames(kw, pcm[s])
+        emitted = 0
+        for f in range(F):
+            bs, pk = r.encode_packet(pcm[s, f * 1152:(f + 1) * 1152])
+            w = want[f]
+            assert (bs, pk) == (w.bs, w.packet) and r.packet_sizes == w.sizes, "stream %d frame %d" % (s, f)
+            assert len(pk) == sum(w.sizes) and w.sizes[0] > 0 and (w.sizes[1] > 0) == lsf
+            emitted += len(bs)
+            assert r.frames() == w.frames_out and w.bytes_out == emitted, "stream %d frame %d" % (s, f)
+        assert emitted > 0 and want[-1].frames_out > 0
 
 
 def test_carried_state_matches_every_frame():
