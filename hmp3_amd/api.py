@@ -222,6 +222,42 @@ class Batch:
         res = [out[i, :nb[i]].tobytes() for i in range(self.n)]
         return (res, st) if stats else res
 
+    def dense_bound(self, nframes):
+        """worst-case bytes of a call's dense image"""
+        return int(lib().hx_batch_dense_bound(self.h, nframes))
+
+    def dense_buffers(self, d_dense_ptr, dense_cap, d_dense_off_ptr):
+        """device buffers [dense_cap] uint8 (16-byte aligned) and [n + 1] int64 that the device calls that follow write
+        their dense image and its offsets to (include/hmp3_amd.h, "dense output"); dense_buffers(None, 0, None) switches
+        it off"""
+        if lib().hx_batch_dense_buffers(self.h, d_dense_ptr, dense_cap, d_dense_off_ptr) != 0:
+            raise RuntimeError("hx_batch_dense_buffers failed: " + last_error())
+
+    def encode_host_dense(self, pcm, dense_cap=None):
+        """encode_host of which only the dense image crosses the link -> (list of bytes per stream, offsets int64 [n + 1]);
+        dense_cap: the image buffer's size (default: dense_bound) - streams whose segment does not fit it come back as None"""
+        f32 = np.asarray(pcm).dtype == np.float32
+        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+        if pcm.ndim == 2:
+            pcm = pcm[:, :, None]
+        assert pcm.shape[0] == self.n and pcm.shape[2] in (1, 2) and pcm.shape[1] % 1152 == 0
+        nfr = pcm.shape[1] // 1152
+        cap = self.dense_bound(nfr) if dense_cap is None else int(dense_cap)
+        dense = np.zeros(max(cap, 1), dtype=np.uint8)
+        off = np.zeros(self.n + 1, dtype=np.int64)
+        nb = np.zeros(self.n, dtype=np.int32)
+        fn = lib().hx_batch_encode_f32_host_dense if f32 else lib().hx_batch_encode_s16_host_dense
+        if fn(self.h, pcm.ctypes.data, nfr, dense.ctypes.data, cap, off.ctypes.data, nb.ctypes.data) != 0:
+            raise RuntimeError("hx_batch_encode host-dense call failed: " + last_error())
+        return [dense[off[i]:off[i] + nb[i]].tobytes() if off[i + 1] <= cap else None for i in range(self.n)], off
+
+    def submit_host_dense(self, pcm_ptr, nframes, dense_ptr, dense_cap, dense_off_ptr, out_bytes_ptr, f32=False):
+        """pipelined host-dense call: dense / dense_off are page-locked host memory the image kernels write; valid after
+        wait_host()"""
+        fn = lib().hx_batch_submit_f32_host_dense if f32 else lib().hx_batch_submit_s16_host_dense
+        if fn(self.h, pcm_ptr, nframes, dense_ptr, dense_cap, dense_off_ptr, out_bytes_ptr) != 0:
+            raise RuntimeError("hx_batch_submit_%s_host_dense failed: " % ("f32" if f32 else "s16") + last_error())
+
     def encode_device(self, d_pcm_ptr, nframes, d_out_ptr, out_stride, d_out_bytes_ptr, stream=None, f32=False):
         """f32: the PCM is float32 at int16 scale (here and in the submits)"""
         fn = lib().hx_batch_encode_f32_device if f32 else lib().hx_batch_encode_s16_device

@@ -323,6 +323,21 @@ extern "C" void hx_batch_packet_buffers(hx_batch *b, unsigned char *d_packet, lo
 
 extern "C" void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats) { b->frame_stats = d_stats; }
 
+extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
+{
+    return b ? (long long) b->S * ((hx_batch_out_stride(b, nframes) + 15) & ~15LL) : 0;
+}
+
+extern "C" int hx_batch_dense_buffers(hx_batch *b, unsigned char *d_dense, long long dense_cap, long long *d_dense_off)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (!d_dense) { b->dense = DenseOut(); return 0; }
+    if (((unsigned long long) d_dense & 15) != 0) { set_err("d_dense must be 16-byte aligned"); return -1; }
+    if (!d_dense_off || ((unsigned long long) d_dense_off & 7) != 0 || dense_cap < 0) { set_err("d_dense_off must be an array of nstreams + 1 long long and dense_cap >= 0"); return -1; }
+    b->dense.buf = d_dense; b->dense.cap = dense_cap; b->dense.off = d_dense_off; b->dense.off_copy = nullptr;
+    return 0;
+}
+
 extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
 {
     b->debug = on != 0;
@@ -392,6 +407,17 @@ static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride,
     return 0;
 }
 
+// the dense image of one call on stream qp, right behind its packing kernels (hx_pack.hip): offsets, then the gather over
+// (stream, chunk of the worst-case row)
+static int enqueue_dense(hx_batch *b, const DenseOut &d, const unsigned char *d_out, long long out_stride, const int *d_out_bytes, int nframes, hipStream_t qp)
+{
+    if (!d.buf) return 0;
+    const int chunks = (int) ((hx_batch_out_stride(b, nframes) + HX_DENSE_CHUNK - 1) / HX_DENSE_CHUNK);
+    LAUNCH(k_dense_off, dim3(1), dim3(1024), qp, d_out_bytes, d.off, d.off_copy, b->S, d.cap, b->d_status);
+    LAUNCH(k_dense_gather, dim3((unsigned) ((long long) b->S * chunks)), dim3(256), qp, d_out, out_stride, d_out_bytes, (const long long *) d.off, d.buf, d.cap, chunks);
+    return 0;
+}
+
 // A gate on stream q: what follows it there starts in the tail of the allocator launch whose first workgroup took number
 // `base` of the started-counter (it wraps with the counter), not at that launch's start.
 static int launch_gate(hx_batch *b, hipStream_t q, unsigned base)
@@ -412,6 +438,7 @@ static int flush_pack(hx_batch *b, long long gate_base)
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
     if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.packet, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
+    if (enqueue_dense(b, j.dense, j.d_out, j.out_stride, j.d_out_bytes, j.nframes, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -424,6 +451,7 @@ struct Pass {
     // the caller's optional outputs as they stand when the pass starts: the stream walk and the packing of this call write
     // these, whatever the caller sets for later calls before a deferred packing goes out
     unsigned char *pk_buf; long long pk_stride; int *pk_bytes, *frame_stats;
+    DenseOut dense;
     int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
                                         // submit n-2 when the front end of submit n writes them: three sets in rotation)
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
@@ -588,7 +616,7 @@ static int place_pack(hx_batch *b, const Pass &p)
         HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
         if (flush_pack(b, (long long) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S)) != 0) return -1;   // the previous submit's
         hx_batch::PackJob &j = b->pack_job;
-        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.packet = p.pk_buf; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
+        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.packet = p.pk_buf; j.dense = p.dense; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
         return 0;
     }
     if (p.kind != PASS_PLAIN) HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
@@ -596,6 +624,7 @@ static int place_pack(hx_batch *b, const Pass &p)
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
     if (enqueue_pack(b, p.d_out, p.out_stride, p.d_out_bytes, p.pk_buf, p.nframes, p.set, p.sset, qa) != 0) return -1;
+    if (enqueue_dense(b, p.dense, p.d_out, p.out_stride, p.d_out_bytes, p.nframes, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -620,7 +649,7 @@ static void reap_timings(hx_batch *b)
 int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
 {
     Poison poison{b};
-    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream, b->pk_buf, b->pk_stride, b->pk_bytes, b->frame_stats};
+    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream, b->pk_buf, b->pk_stride, b->pk_bytes, b->frame_stats, b->dense};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
     if (pipe_enter(b, p) != 0 || launch_front(b, p) != 0) return -1;
@@ -697,9 +726,11 @@ extern "C" void *hx_pinned_alloc(long long bytes)
 }
 extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
 
-static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
+// img: null, or (hx_batch_submit_*_host_dense) the caller's page-locked image and offsets as the device sees them - the
+// image kernels of the call write them, and the rows stay in the staging: out is not used
+static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, const DenseOut *img = nullptr)
 {
-    if (check_call(b, in.p, nframes, out, out_stride, out_bytes) != 0) return -1;
+    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
     const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t)), obytes = (long long) b->S * out_stride;
@@ -717,6 +748,8 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
         if (pbytes > b->hs_pcm_cap) b->hs_pcm_cap = pbytes;
         if (obytes > b->hs_out_cap) b->hs_out_cap = obytes;
     }
+    if (img && !b->hs_off[0])
+        for (int i = 0; i < 2; i++) if (dev_alloc(b, b->hs_off[i], sizeof(long long) * (b->S + 1)) != 0) return -1;
     const int k = (int) (b->nhost & 1);
     if (b->nhost >= 2) {
         HIPCHK(hipStreamWaitEvent(b->s_h2d, b->ev_hfront[k], 0));   // the front end of call n-2 has read this PCM buffer
@@ -726,12 +759,16 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
     HIPCHK(hipEventRecord(b->ev_h2d[k], b->s_h2d));
     HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_h2d[k], 0));
     const int set = (int) (b->nsubmit & 1);
-    if (encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, b->hs_out[k], out_stride, b->hs_nb[k], b->s_host, PASS_SUBMIT_HOST) != 0) return -1;
+    const DenseOut saved = b->dense;
+    if (img) b->dense = DenseOut{img->buf, img->cap, b->hs_off[k], img->off};
+    const int r = encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, b->hs_out[k], out_stride, b->hs_nb[k], b->s_host, PASS_SUBMIT_HOST);
+    b->dense = saved;
+    if (r != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_hfront[k], b->s_front));
     HIPCHK(hipStreamWaitEvent(b->s_d2h, b->ev_alloc[set], 0));
     HIPCHK(hipMemcpyAsync(out_bytes, b->hs_nb[k], sizeof(int) * b->S, hipMemcpyDeviceToHost, b->s_d2h));
-    HIPCHK(hipMemcpyAsync(out, b->hs_out[k], (size_t) obytes, hipMemcpyDeviceToHost, b->s_d2h));
-    HIPCHK(hipEventRecord(b->ev_d2h[k], b->s_d2h));
+    if (!img) HIPCHK(hipMemcpyAsync(out, b->hs_out[k], (size_t) obytes, hipMemcpyDeviceToHost, b->s_d2h));
+    HIPCHK(hipEventRecord(b->ev_d2h[k], b->s_d2h));     // (a dense call: its image kernels, which ev_alloc covers, are done)
     b->nhost++;
     return poison.ok();
 }
@@ -744,6 +781,52 @@ extern "C" int hx_batch_submit_s16_host(hx_batch *b, const int16_t *pcm, int nfr
 extern "C" int hx_batch_submit_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
 {
     return submit_host(b, {pcm, true}, nframes, out, out_stride, out_bytes);
+}
+
+// Pipelined host calls that return the dense image only.  Nothing waits for a byte count: k_dense_gather stores the image and
+// k_dense_off the offsets straight into the caller's page-locked memory, which the device reaches over the link (the
+// one-stream encoder's packing publishes its results the same way); the rows stay in the staging.  The gather reads the
+// offsets from a copy in device memory.
+// (Kernel-written host memory against the DMA copy of the rows has not been measured: DESIGN.md section 5.)
+// [p, p + bytes) as the current device addresses it, or null: page-locked host memory of ONE allocation or registration
+// (first and last byte are host memory and lie as far apart for the device as for the host) that is mapped for the device
+static void *pinned_device_ptr(const void *p, long long bytes)
+{
+    const long long span = bytes > 0 ? bytes - 1 : 0;
+    hipPointerAttribute_t a0, a1;
+    void *dp = nullptr;
+    if (hipPointerGetAttributes(&a0, p) != hipSuccess || hipPointerGetAttributes(&a1, (const char *) p + span) != hipSuccess ||
+        hipHostGetDevicePointer(&dp, const_cast<void *>(p), 0) != hipSuccess) {
+        (void) hipGetLastError();       // (pageable memory is an invalid value to some runtimes, unregistered memory to others)
+        return nullptr;
+    }
+    if (a0.type != hipMemoryTypeHost || a1.type != hipMemoryTypeHost || !dp) return nullptr;
+    if ((const char *) a1.devicePointer - (const char *) a0.devicePointer != span || (const char *) a1.hostPointer - (const char *) a0.hostPointer != span) return nullptr;
+    return dp;
+}
+static int submit_host_dense(hx_batch *b, PcmIn in, int nframes, unsigned char *dense, long long dense_cap, long long *dense_off, int *out_bytes)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (!dense || !dense_off || dense_cap < 0) { set_err("null buffer"); return -1; }
+    if (hipSetDevice(b->device) != hipSuccess) { set_err("hipSetDevice failed"); return -1; }
+    DenseOut img;
+    img.buf = (unsigned char *) pinned_device_ptr(dense, dense_cap);
+    img.off = (long long *) pinned_device_ptr(dense_off, (long long) sizeof(long long) * (b->S + 1));
+    img.cap = dense_cap;
+    if (!img.buf || !img.off) { set_err("dense and dense_off must be page-locked host memory (hx_pinned_alloc, or registered with the HIP runtime): the image kernels write them"); return -1; }
+    if (((unsigned long long) img.buf & 15) != 0) { set_err("dense must be 16-byte aligned"); return -1; }
+    if (((unsigned long long) img.off & 7) != 0) { set_err("dense_off must be 8-byte aligned"); return -1; }
+    return submit_host(b, in, nframes, nullptr, hx_batch_out_stride(b, nframes), out_bytes, &img);
+}
+extern "C" int hx_batch_submit_s16_host_dense(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                              long long *dense_off, int *out_bytes)
+{
+    return submit_host_dense(b, {pcm, false}, nframes, dense, dense_cap, dense_off, out_bytes);
+}
+extern "C" int hx_batch_submit_f32_host_dense(hx_batch *b, const float *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                              long long *dense_off, int *out_bytes)
+{
+    return submit_host_dense(b, {pcm, true}, nframes, dense, dense_cap, dense_off, out_bytes);
 }
 
 // block until the outputs of every submitted host call are in host memory
@@ -801,6 +884,31 @@ extern "C" int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nfram
                                         long long out_stride, int *out_bytes)
 {
     return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, nullptr);
+}
+
+// The synchronous host calls that return the dense image: rows, image and offsets in device staging, and only the byte
+// counts, the offsets and the image's used part cross the link.  (An image that does not fit dense_cap: the segments that
+// fit in whole are a prefix of the streams, and that prefix is what is copied.)
+static int encode_host_dense(hx_batch *b, PcmIn in, int nframes, unsigned char *dense, long long dense_cap, long long *dense_off, int *out_bytes)
+{
+    const long long stride = hx_batch_out_stride(b, nframes);
+    if (check_call(b, in.p, nframes, dense, stride, out_bytes) != 0) return -1;
+    if (!dense_off || dense_cap < 0) { set_err("null buffer"); return -1; }
+    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
+    const HostDense hd = {dense, dense_cap, dense_off, hx_batch_dense_bound(b, nframes)};
+    return host_call(b, in.p, pbytes, false, nframes, nullptr, stride, out_bytes, nullptr, [&] {
+        return encode_pass(b, {b->d_in, in.f32}, nframes, b->d_out, stride, b->d_outbytes, nullptr, PASS_PLAIN);
+    }, &hd);
+}
+extern "C" int hx_batch_encode_s16_host_dense(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                              long long *dense_off, int *out_bytes)
+{
+    return encode_host_dense(b, {pcm, false}, nframes, dense, dense_cap, dense_off, out_bytes);
+}
+extern "C" int hx_batch_encode_f32_host_dense(hx_batch *b, const float *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                              long long *dense_off, int *out_bytes)
+{
+    return encode_host_dense(b, {pcm, true}, nframes, dense, dense_cap, dense_off, out_bytes);
 }
 
 extern "C" int hx_batch_status(hx_batch *b)

@@ -368,3 +368,91 @@ __global__ __launch_bounds__(1024) void k_order(const unsigned *__restrict__ dur
     __syncthreads();
     for (int i = tid; i < S; i += 1024) order[atomicAdd(&hist[1023 - (unsigned) (((unsigned long long) (dur[i] - base) * 1024) / range)], 1u)] = i;
 }
+
+// ---- the dense image of a call (hx_batch_dense_buffers): behind the packing, the rows' used parts back to back ----
+// Segment i starts at off[i] = sum over j < i of out_bytes[j] rounded up to 16, holds the first out_bytes[i] bytes of row i
+// and zeros up to off[i + 1]; off[S] is the image's size.  The rows stay as they are.
+
+// The offsets: an exclusive scan over the streams in 16-byte units, one workgroup, 1024 streams a round - wave scans on the
+// DPP path (in two 16-bit halves: a wave's sum of 2^27-unit rows does not fit 32 bits), one LDS combine per round.
+// off_copy: null, or a second place the offsets go to (the pipelined host calls: the caller's page-locked array, while the
+// gather reads the copy in device memory).  Status bit 16: the image does not fit cap (the offsets are complete all the same).
+__global__ __launch_bounds__(1024) void k_dense_off(const int *__restrict__ out_bytes, long long *__restrict__ off, long long *__restrict__ off_copy,
+                                                    int S, long long cap, int *__restrict__ status)
+{
+    __shared__ long long wsum[16];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    long long base = 0;         // 16-byte units in front of this round
+    for (int i0 = 0; i0 < S; i0 += 1024) {
+        const int i = i0 + tid;
+        const int v = (i < S) ? (max(out_bytes[i], 0) + 15) >> 4 : 0;
+        const long long incl = ((long long) hx_wave_scan(v >> 16) << 16) + hx_wave_scan(v & 0xFFFF);
+        if (lane == 63) wsum[w] = incl;
+        __syncthreads();
+        long long before = 0, all = 0;
+        for (int k = 0; k < 16; k++) { const long long t = wsum[k]; all += t; before += (k < w) ? t : 0; }
+        if (i < S) {
+            const long long o = (base + before + incl - v) << 4;
+            off[i] = o;
+            if (off_copy) off_copy[i] = o;
+        }
+        base += all;
+        __syncthreads();        // wsum is rewritten by the next round
+    }
+    if (tid == 0) {
+        off[S] = base << 4;
+        if (off_copy) off_copy[S] = base << 4;
+        if ((base << 4) > cap) atomicOr(status, 16);
+    }
+}
+
+// The gather: workgroup (stream s, chunk c) moves bytes [c * HX_DENSE_CHUNK, ...) of row s, 16 per lane and step; the host
+// does not know the byte counts, so the grid covers the worst-case row and a workgroup past its stream's count leaves at
+// once.  The destination is 16-byte aligned by construction: every store is a dwordx4.  A row that is 16-byte aligned is
+// read the same way; any other from the two aligned 16-byte blocks a vector straddles, funnelled into place
+// (v_alignbyte_b32; the row's misalignment is workgroup-uniform) - an aligned block that holds a byte of the row lies in the
+// row's allocation.  The segment's last vector carries its zero padding.  A segment that does not fit below cap in whole is
+// not written.
+__global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__restrict__ out, long long out_stride, const int *__restrict__ out_bytes,
+                                                      const long long *__restrict__ off, unsigned char *__restrict__ dense, long long cap, int chunks)
+{
+    const int s = blockIdx.x / chunks, c = blockIdx.x % chunks;
+    const int n = max(out_bytes[s], 0);
+    if ((long long) c * HX_DENSE_CHUNK >= n) return;
+    if (off[s + 1] > cap) return;
+    const unsigned char *src = out + (long long) s * out_stride;
+    uint4 *dst = reinterpret_cast<uint4 *>(dense + off[s]);
+    const unsigned mis = (unsigned) (reinterpret_cast<unsigned long long>(src) & 15u), ws = mis >> 2, sh = mis & 3;
+    const uint4 *blk = reinterpret_cast<const uint4 *>(src - mis);
+    const int nv = (n + 15) >> 4;
+#pragma unroll
+    for (int k = 0; k < HX_DENSE_CHUNK / 16 / 256; k++) {
+        const int v = c * (HX_DENSE_CHUNK / 16) + 256 * k + (int) threadIdx.x;
+        if (v >= nv) break;
+        const int rem = n - 16 * v;         // bytes of the row in this vector: the rest is padding
+        uint4 val = blk[v];
+        if (mis) {
+            // (the second block only where the vector's row bytes reach into it: the last vector of the last row must not
+            // touch a block that holds no byte of the row)
+            const uint4 hi = (rem + (int) mis > 16) ? blk[v + 1] : make_uint4(0, 0, 0, 0);
+            unsigned q[8] = {val.x, val.y, val.z, val.w, hi.x, hi.y, hi.z, hi.w};
+            if (ws & 2) {
+#pragma unroll
+                for (int j = 0; j < 6; j++) q[j] = q[j + 2];
+            }
+            if (ws & 1) {
+#pragma unroll
+                for (int j = 0; j < 5; j++) q[j] = q[j + 1];
+            }
+            val.x = __builtin_amdgcn_alignbyte(q[1], q[0], sh);
+            val.y = __builtin_amdgcn_alignbyte(q[2], q[1], sh);
+            val.z = __builtin_amdgcn_alignbyte(q[3], q[2], sh);
+            val.w = __builtin_amdgcn_alignbyte(q[4], q[3], sh);
+        }
+        if (rem < 16) {
+            auto keep = [&](unsigned x, int r) { return r >= 4 ? x : (r <= 0 ? 0u : x & ((1u << (8 * r)) - 1u)); };
+            val.x = keep(val.x, rem); val.y = keep(val.y, rem - 4); val.z = keep(val.z, rem - 8); val.w = keep(val.w, rem - 12);
+        }
+        dst[v] = val;
+    }
+}

@@ -48,6 +48,9 @@ __global__ void k_pack(const HxStream *st, const HxParams *prm, const HxGlobalTa
                        const int *carry_len, unsigned *frames_out, unsigned char *host_out, const int *seq_src);
 __global__ void k_pack_carry(HxStream *st, const unsigned char *out, long long out_stride, const int *out_bytes, const int *carry_len, unsigned *frames_out);
 __global__ void k_pack_pre(const HxStream *st, unsigned char *out, long long out_stride, const int *pre_len);
+__global__ void k_dense_off(const int *out_bytes, long long *off, long long *off_copy, int S, long long cap, int *status);
+__global__ void k_dense_gather(const unsigned char *out, long long out_stride, const int *out_bytes, const long long *off, unsigned char *dense,
+                               long long cap, int chunks);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
 __global__ void k_alloc(AllocArgs a);
@@ -83,6 +86,10 @@ struct WalkSet {
     int *pre_len, *carry_len;
 };
 
+// Where a call's dense image goes (hx_batch_dense_buffers): buf null = off.  off_copy: a second place for the offsets (the
+// pipelined host calls, whose offsets go to the caller's page-locked array as well as to device staging).
+struct DenseOut { unsigned char *buf = nullptr; long long cap = 0; long long *off = nullptr, *off_copy = nullptr; };
+
 struct hx_batch {
     int device = 0, S = 0, maxF = 0, ncls = 0;
     std::vector<HxParams> params;       // host copy per class
@@ -98,6 +105,7 @@ struct hx_batch {
     int *d_lens = nullptr;              // [2 sets][pre_len | carry_len][S]
     int *frame_stats = nullptr;         // caller's per-frame counters (device), optional
     unsigned char *pk_buf = nullptr; long long pk_stride = 0; int *pk_bytes = nullptr;   // caller's packet buffers (device), optional
+    DenseOut dense;                     // caller's dense image (device), optional
     float *d_pcmf = nullptr;            // DC-blocked input, only when a stream uses filter_select = 1
     bool any_dc = false;
     int nchan = 2;                      // channels of the PCM input, the same for every stream of the batch
@@ -129,6 +137,7 @@ struct hx_batch {
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
     void *d_in = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr, *d_stats = nullptr;
     long long in_cap = 0, out_cap = 0, stats_cap = 0;
+    unsigned char *d_dense = nullptr; long long *d_dense_off = nullptr; long long dense_cap = 0;   // ... and of the *_host_dense calls: image and offsets
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double alloc_ms_sum = 0; int alloc_calls = 0;
     // hx_batch_submit_*: the front-end kernels of call n+1 run (low-priority stream) while k_alloc of
@@ -139,12 +148,14 @@ struct hx_batch {
     hipEvent_t ev_sgn[3] = {nullptr, nullptr, nullptr}; // the packing that read this set of signs is done
     // the packing of the latest device-buffer submit, not enqueued yet: it goes out behind the next submit's allocator launch
     // (released by a gate like the front end, into that launch's tail), or ungated at the next wait / plain call
-    // (packet: the packet buffer in force at the submit - the stream walk has put the packets' headers there already)
-    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; unsigned char *packet = nullptr; int nframes = 0, set = 0, sset = 0; } pack_job;
+    // (packet: the packet buffer in force at the submit - the stream walk has put the packets' headers there already;
+    // dense: the dense image's buffers in force at the submit - the image kernels go out with the packing)
+    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; unsigned char *packet = nullptr; DenseOut dense; int nframes = 0, set = 0, sset = 0; } pack_job;
     long long nsubmit = 0;
     bool inflight = false;
     // hx_batch_submit_*_host: device staging for two calls in flight and the copy streams
     void *hs_pcm[2] = {nullptr, nullptr}; unsigned char *hs_out[2] = {nullptr, nullptr}; int *hs_nb[2] = {nullptr, nullptr};
+    long long *hs_off[2] = {nullptr, nullptr};      // the dense submits' offsets (the gather reads them here, not over the link)
     long long hs_pcm_cap = 0, hs_out_cap = 0;
     hipStream_t s_h2d = nullptr, s_d2h = nullptr, s_host = nullptr;
     hipEvent_t ev_h2d[2] = {nullptr, nullptr}, ev_d2h[2] = {nullptr, nullptr}, ev_hfront[2] = {nullptr, nullptr};
@@ -249,22 +260,37 @@ HX_LOCAL int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int sou
 // d_outbytes, wait for it and copy the results back - with `stats`, also the call's per-frame counters (see
 // hx_batch_frame_stats_buffer), which the device call then writes to staging of the batch's instead of the caller's buffer.
 // drain_first: the staging may still be read by an earlier call that did not wait for its end.
+// hd (the *_host_dense calls): the device call also writes the dense image and its offsets to staging, and those come back
+// instead of the rows (`out` is not used): the offsets, and the image up to the last segment that fits hd->cap in whole -
+// the segments that fit are a prefix of the streams, and none of them ends beyond hd->bound.
+struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 template <class Encode>
 static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
-                     long long out_stride, int *out_bytes, int *stats, Encode encode)
+                     long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr)
 {
     HIPCHK(hipSetDevice(b->device));
     const long long obytes = (long long) b->S * out_stride, sbytes = stats ? (long long) sizeof(int) * b->S * nframes * 2 : 0;
     if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes)) return -1;
+    if (hd && (dev_grow(b, b->d_dense, b->dense_cap, std::max(16LL, std::min(hd->cap, hd->bound))) ||
+               (!b->d_dense_off && dev_alloc(b, b->d_dense_off, (long long) sizeof(long long) * (b->S + 1))))) return -1;
     if (drain_first && drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));
     int *const saved = b->frame_stats;
+    const DenseOut saved_dense = b->dense;
     if (stats) b->frame_stats = b->d_stats;
+    if (hd) b->dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
     const int r = encode();
     b->frame_stats = saved;
+    b->dense = saved_dense;
     if (r != 0 || drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(out, b->d_out, (size_t) obytes, hipMemcpyDeviceToHost));
+    if (hd) {
+        HIPCHK(hipMemcpy(hd->off, b->d_dense_off, sizeof(long long) * (b->S + 1), hipMemcpyDeviceToHost));
+        long long k = b->S;
+        while (k > 0 && hd->off[k] > hd->cap) k--;
+        if (hd->off[k] > 0) HIPCHK(hipMemcpy(hd->dense, b->d_dense, (size_t) hd->off[k], hipMemcpyDeviceToHost));
+    } else
+        HIPCHK(hipMemcpy(out, b->d_out, (size_t) obytes, hipMemcpyDeviceToHost));
     if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, (size_t) sbytes, hipMemcpyDeviceToHost));
     return 0;
 }

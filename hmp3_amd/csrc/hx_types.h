@@ -201,6 +201,10 @@ struct alignas(16) HxFrameOut {
 // 16-byte alignment.  (As one byte per line they were 0.6 GB written and 0.6 GB read per config-2 step.)
 #define HX_SGN_WORDS 20
 
+// The dense image (hx_batch_dense_buffers): a workgroup of k_dense_gather (hx_pack.hip) moves this many bytes of one row -
+// 256 lanes x 4 vectors of 16 bytes; the host sizes the grid with it from the worst-case row.
+#define HX_DENSE_CHUNK 16384
+
 // Slots of a batch's counter block (AllocArgs::done_counter; the host runtime reads some of them and hands two to k_gate and k_pack).
 enum HxCounter {
     HX_CNT_RETIRED = 0,         // streams retired

@@ -190,12 +190,47 @@ void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats);
 /* fp32 host call that also returns those counters to a host array stats[nstreams][nframes][2] */
 int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
                                    long long out_stride, int *out_bytes, int *stats);
+/* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
+   The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
+   gathers them on the GPU, behind its packing, into one image.  With nb[i] = out_bytes[i]:
+     off[i] = sum over j < i of round_up(nb[j], 16), i = 0 .. nstreams; off[nstreams] is the image's size;
+     dense[off[i] .. off[i] + nb[i]) = the first nb[i] bytes of row i; the bytes from there to off[i + 1] are zero.
+   Every segment starts on a 16-byte boundary (at most 15 bytes of padding per stream and call); a stream that emitted
+   nothing has an empty segment.  The rows and out_bytes are written as always: the image is in addition to them.
+   If off[nstreams] > dense_cap, the offsets are still complete (the caller can size a retry), every segment that fits in
+   whole (off[i + 1] <= dense_cap) is written, the others are not, nothing is written at or beyond dense + dense_cap, and
+   status bit 16 is set (hx_batch_status).
+   Not covered: hx_multi_* and the command-line tool's batch mode keep rows, and converting batches have no *_host_dense
+   calls (their device call takes hx_batch_dense_buffers like any other). */
+/* worst-case size of a call's dense image: nstreams * round_up(hx_batch_out_stride(b, nframes), 16) */
+long long hx_batch_dense_bound(const hx_batch *b, int nframes);
+/* optional dense output of the batched device calls; NULL switches it off.  d_dense: 16-byte aligned (else -1),
+   d_dense_off: [nstreams + 1] long long.  Applies to the calls that follow; a call writes the buffers in force when
+   it is made - a submit too: they travel with its deferred packing, must stay valid until the hx_batch_wait behind
+   it, and consecutive submits take different sets (two in turn, like d_out). */
+int hx_batch_dense_buffers(hx_batch *b, unsigned char *d_dense, long long dense_cap, long long *d_dense_off);
+/* Host calls of which only the image crosses the link: dense [dense_cap] bytes, dense_off [nstreams + 1], out_bytes
+   [nstreams]; the rows stay in the batch's device staging.  An image that does not fit still returns 0: the caller sees
+   dense_off[nstreams] > dense_cap (and status bit 16), and has the segments that fit.  Synchronous calls: any host memory. */
+int hx_batch_encode_s16_host_dense(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                   long long *dense_off, int *out_bytes);
+int hx_batch_encode_f32_host_dense(hx_batch *b, const float *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                   long long *dense_off, int *out_bytes);
+/* The pipelined form, completed by hx_batch_wait_host like hx_batch_submit_*_host (two sets of buffers in turn).  No copy
+   brings the image down: the gather kernel stores it, and the offsets kernel dense_off, straight into the caller's memory,
+   so dense (16-byte aligned) and dense_off must be page-locked (hx_pinned_alloc, or registered with the HIP runtime); with
+   anything else the call is refused (-1, hx_last_error) before anything runs.  out_bytes travels by a small copy. */
+int hx_batch_submit_s16_host_dense(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                   long long *dense_off, int *out_bytes);
+int hx_batch_submit_f32_host_dense(hx_batch *b, const float *pcm, int nframes, unsigned char *dense, long long dense_cap,
+                                   long long *dense_off, int *out_bytes);
 /* the settings an encoder would run a control with (what L3_audio_encode_info_ec / _info_head report,
    mp3enc.cpp:839-866), host only; 0 = configuration rejected */
 int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *head_out);
 /* status bits accumulated by the kernels: 2 = main data overflow (the reference would assert
    there), 4 = the Huffman bits packed for a channel differ from the bits counted for it (an internal
-   consistency check of the two-wave packer).  0 = healthy; -1 = no answer (the batch became unusable after a
+   consistency check of the two-wave packer), 8 = a converter window out of bounds (converting batches), 16 = a dense image
+   did not fit its dense_cap (hx_batch_dense_buffers).  0 = healthy; -1 = no answer (the batch became unusable after a
    failed device call, or the status could not be read).  Synchronises - and, like hx_batch_wait, first enqueues the
    packing that the last hx_batch_submit_*_device left for later: that writes the submit's output buffers (d_out,
    d_out_bytes and the packet buffer that was set at the submit), which must therefore still be valid.
