@@ -318,10 +318,10 @@ extern "C" long long hx_batch_out_stride(const hx_batch *b, int nframes)
 
 extern "C" void hx_batch_packet_buffers(hx_batch *b, unsigned char *d_packet, long long frame_stride, int *d_packet_bytes)
 {
-    b->pk_buf = d_packet; b->pk_stride = frame_stride; b->pk_bytes = d_packet_bytes;
+    b->opt.packet = d_packet; b->opt.packet_stride = frame_stride; b->opt.packet_bytes = d_packet_bytes;
 }
 
-extern "C" void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats) { b->frame_stats = d_stats; }
+extern "C" void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats) { b->opt.frame_stats = d_stats; }
 
 extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
 {
@@ -331,10 +331,10 @@ extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
 extern "C" int hx_batch_dense_buffers(hx_batch *b, unsigned char *d_dense, long long dense_cap, long long *d_dense_off)
 {
     if (!b) { set_err("null batch"); return -1; }
-    if (!d_dense) { b->dense = DenseOut(); return 0; }
+    if (!d_dense) { b->opt.dense = DenseOut(); return 0; }
     if (((unsigned long long) d_dense & 15) != 0) { set_err("d_dense must be 16-byte aligned"); return -1; }
     if (!d_dense_off || ((unsigned long long) d_dense_off & 7) != 0 || dense_cap < 0) { set_err("d_dense_off must be an array of nstreams + 1 long long and dense_cap >= 0"); return -1; }
-    b->dense.buf = d_dense; b->dense.cap = dense_cap; b->dense.off = d_dense_off; b->dense.off_copy = nullptr;
+    b->opt.dense = DenseOut{d_dense, dense_cap, d_dense_off, nullptr};
     return 0;
 }
 
@@ -385,7 +385,7 @@ int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out,
 }
 
 // the packing kernels of one call on stream qp (see place_pack)
-static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride, int *d_out_bytes, unsigned char *packet, int nframes, int set, int sset, hipStream_t qp)
+static int enqueue_pack(hx_batch *b, const Call &c, int nframes, int set, int sset, hipStream_t qp)
 {
     const int S = b->S, NG = 2 * nframes;
     const WalkSet &w = b->walk[set];
@@ -396,25 +396,26 @@ static int enqueue_pack(hx_batch *b, unsigned char *d_out, long long out_stride,
     const int solo = (S <= 4 && total <= 8) ? S : 0;
     if (solo) {
         LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-               d_out, out_stride, packet, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, d_out_bytes, w.carry_len, b->cap_frames,
-               (solo == 1) ? b->cap_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
+               c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, c.out_bytes, w.carry_len, c.rec_frames,
+               (solo == 1) ? c.rec_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
         return 0;
     }
-    LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, w.pre_len);
+    LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, w.pre_len);
     LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-           d_out, out_stride, packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
-    LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, d_out, out_stride, d_out_bytes, w.carry_len, b->cap_frames);
+           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
+    LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, c.out_bytes, w.carry_len, c.rec_frames);
     return 0;
 }
 
 // the dense image of one call on stream qp, right behind its packing kernels (hx_pack.hip): offsets, then the gather over
 // (stream, chunk of the worst-case row)
-static int enqueue_dense(hx_batch *b, const DenseOut &d, const unsigned char *d_out, long long out_stride, const int *d_out_bytes, int nframes, hipStream_t qp)
+static int enqueue_dense(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
 {
+    const DenseOut &d = c.opt.dense;
     if (!d.buf) return 0;
     const int chunks = (int) ((hx_batch_out_stride(b, nframes) + HX_DENSE_CHUNK - 1) / HX_DENSE_CHUNK);
-    LAUNCH(k_dense_off, dim3(1), dim3(1024), qp, d_out_bytes, d.off, d.off_copy, b->S, d.cap, b->d_status);
-    LAUNCH(k_dense_gather, dim3((unsigned) ((long long) b->S * chunks)), dim3(256), qp, d_out, out_stride, d_out_bytes, (const long long *) d.off, d.buf, d.cap, chunks);
+    LAUNCH(k_dense_off, dim3(1), dim3(1024), qp, c.out_bytes, d.off, d.off_copy, b->S, d.cap, b->d_status);
+    LAUNCH(k_dense_gather, dim3((unsigned) ((long long) b->S * chunks)), dim3(256), qp, c.out, c.out_stride, c.out_bytes, (const long long *) d.off, d.buf, d.cap, chunks);
     return 0;
 }
 
@@ -437,8 +438,7 @@ static int flush_pack(hx_batch *b, long long gate_base)
     j.pending = false;
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
-    if (enqueue_pack(b, j.d_out, j.out_stride, j.d_out_bytes, j.packet, j.nframes, j.set, j.sset, b->s_pack) != 0) return -1;
-    if (enqueue_dense(b, j.dense, j.d_out, j.out_stride, j.d_out_bytes, j.nframes, b->s_pack) != 0) return -1;
+    if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -446,12 +446,8 @@ static int flush_pack(hx_batch *b, long long gate_base)
 
 // One pass of the pipeline over the batch, as phases in the order they run.  What a phase leaves for the later ones:
 struct Pass {
-    PcmIn in; int nframes; unsigned char *d_out; long long out_stride; int *d_out_bytes; PassKind kind;       // the call
+    PcmIn in; int nframes; Call call; PassKind kind;    // the call: the stream walk and the packing write its record's outputs
     hipStream_t q, qa;                  // streams of the front end / of the stream walk and (unless deferred) the packing
-    // the caller's optional outputs as they stand when the pass starts: the stream walk and the packing of this call write
-    // these, whatever the caller sets for later calls before a deferred packing goes out
-    unsigned char *pk_buf; long long pk_stride; int *pk_bytes, *frame_stats;
-    DenseOut dense;
     int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
                                         // submit n-2 when the front end of submit n writes them: three sets in rotation)
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
@@ -537,8 +533,9 @@ static int pipe_front_done(hx_batch *b, const Pass &p)
     // starts putting headers into it.  Alternate two sets of output buffers to have them overlap.
     const hx_batch::PackJob &j = b->pack_job;
     if (j.pending) {
-        const unsigned char *o0 = j.d_out, *o1 = j.d_out + (long long) b->S * j.out_stride, *n0 = p.d_out, *n1 = p.d_out + (long long) b->S * p.out_stride;
-        const char *b0 = (const char *) j.d_out_bytes, *b1 = b0 + sizeof(int) * (size_t) b->S, *m0 = (const char *) p.d_out_bytes, *m1 = m0 + sizeof(int) * (size_t) b->S;
+        const Call &jc = j.call, &pc = p.call;
+        const unsigned char *o0 = jc.out, *o1 = jc.out + (long long) b->S * jc.out_stride, *n0 = pc.out, *n1 = pc.out + (long long) b->S * pc.out_stride;
+        const char *b0 = (const char *) jc.out_bytes, *b1 = b0 + sizeof(int) * (size_t) b->S, *m0 = (const char *) pc.out_bytes, *m1 = m0 + sizeof(int) * (size_t) b->S;
         if ((o0 < n1 && n0 < o1) || (b0 < m1 && m0 < b1)) {
             const int js = j.set;
             if (flush_pack(b, -1) != 0) return -1;
@@ -555,10 +552,11 @@ static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
     const WalkSet &w = b->walk[p.set];
     unsigned *const sgn = b->sgn[p.sset];
     const int S = b->S;
+    const Call &c = p.call;
     a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
-    a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = p.d_out; a.out_bytes = p.d_out_bytes;
-    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = p.out_stride; a.NG = 2 * p.nframes; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
-    a.packet = p.pk_buf; a.packet_stride = p.pk_stride; a.packet_bytes = p.pk_bytes; a.frame_stats = p.frame_stats;
+    a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = c.out; a.out_bytes = c.out_bytes;
+    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = c.out_stride; a.NG = 2 * p.nframes; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
+    a.packet = c.opt.packet; a.packet_stride = c.opt.packet_stride; a.packet_bytes = c.opt.packet_bytes; a.frame_stats = c.opt.frame_stats;
     a.done_counter = b->d_done;
     a.strict_sums = b->strict_sums;
     a.dur = b->d_dur;
@@ -584,7 +582,7 @@ static int launch_walk(hx_batch *b, const Pass &p, const AllocArgs &a)
     const int S = b->S;
     b->alloc_launches++;
     hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (!b->capturing) {
+    if (!p.call.recording) {
         HIPCHK(hipEventCreate(&e0));
         HIPCHK(hipEventCreate(&e1));
         HIPCHK(hipEventRecord(e0, qa));
@@ -597,7 +595,7 @@ static int launch_walk(hx_batch *b, const Pass &p, const AllocArgs &a)
     else if (b->lsf) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, a);
     else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, a);
     else LAUNCH(k_alloc, dim3(G), dim3(128), qa, a);
-    if (!b->capturing) {
+    if (!p.call.recording) {
         HIPCHK(hipEventRecord(e1, qa));
         b->pending.push_back({e0, e1});
     }
@@ -615,16 +613,14 @@ static int place_pack(hx_batch *b, const Pass &p)
     if (p.kind == PASS_SUBMIT_DEVICE) {
         HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
         if (flush_pack(b, (long long) ((unsigned long long) (b->alloc_launches - 1) * (unsigned long long) b->S)) != 0) return -1;   // the previous submit's
-        hx_batch::PackJob &j = b->pack_job;
-        j.pending = true; j.d_out = p.d_out; j.out_stride = p.out_stride; j.d_out_bytes = p.d_out_bytes; j.packet = p.pk_buf; j.dense = p.dense; j.nframes = p.nframes; j.set = p.set; j.sset = p.sset;
+        b->pack_job = {true, p.call, p.nframes, p.set, p.sset};
         return 0;
     }
     if (p.kind != PASS_PLAIN) HIPCHK(hipEventRecord(b->ev_k6[p.set], qa));
     // the previous device-buffer submit's packing went out on the packing stream in pipe_enter: its k_pack_carry writes
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
-    if (enqueue_pack(b, p.d_out, p.out_stride, p.d_out_bytes, p.pk_buf, p.nframes, p.set, p.sset, qa) != 0) return -1;
-    if (enqueue_dense(b, p.dense, p.d_out, p.out_stride, p.d_out_bytes, p.nframes, qa) != 0) return -1;
+    if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -646,16 +642,16 @@ static void reap_timings(hx_batch *b)
     }
 }
 
-int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
+int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
     Poison poison{b};
-    Pass p = {in, nframes, d_out, out_stride, d_out_bytes, kind, (hipStream_t) stream, (hipStream_t) stream, b->pk_buf, b->pk_stride, b->pk_bytes, b->frame_stats, b->dense};
+    Pass p = {in, nframes, c, kind, (hipStream_t) stream, (hipStream_t) stream};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
     if (pipe_enter(b, p) != 0 || launch_front(b, p) != 0) return -1;
     if (kind != PASS_PLAIN && pipe_front_done(b, p) != 0) return -1;
     if (fill_alloc_args(b, p, a) != 0 || launch_walk(b, p, a) != 0 || place_pack(b, p) != 0) return -1;
-    if (!b->capturing) reap_timings(b);
+    if (!c.recording) reap_timings(b);
     if (kind != PASS_PLAIN) {
         b->nsubmit++;
         b->inflight = true;
@@ -664,22 +660,22 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long l
     b->lastNG = 2 * nframes;
     return poison.ok();
 }
-int encode_checked(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind)
+int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
-    if (check_call(b, in.p, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
-    return encode_pass(b, in, nframes, d_out, out_stride, d_out_bytes, stream, kind);
+    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0) return -1;
+    return encode_pass(b, in, nframes, c, stream, kind);
 }
 
 extern "C" int hx_batch_encode_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, false}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN);
+    return encode_checked(b, {d_pcm, false}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
 }
 
 extern "C" int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN);
+    return encode_checked(b, {d_pcm, true}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
 }
 
 // Pipelined form of the device calls.  A submit returns at once like the plain call, but its output
@@ -691,13 +687,13 @@ extern "C" int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int n
 extern "C" int hx_batch_submit_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, false}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_SUBMIT_DEVICE);
+    return encode_checked(b, {d_pcm, false}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
 }
 
 extern "C" int hx_batch_submit_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_SUBMIT_DEVICE);
+    return encode_checked(b, {d_pcm, true}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
 }
 
 // share (percent) of the previous allocator launch's resident workgroups that must have started before a submit's front end is released; 0 = no gate
@@ -733,7 +729,7 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
     if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
-    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t)), obytes = (long long) b->S * out_stride;
+    const long long pbytes = in.bytes(b->S, nframes, b->nchan), obytes = (long long) b->S * out_stride;
     if (!b->s_h2d) {
         if (new_stream(b, b->s_h2d) || new_stream(b, b->s_d2h) || new_stream(b, b->s_host)) return -1;
         for (int i = 0; i < 2; i++)
@@ -759,11 +755,9 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
     HIPCHK(hipEventRecord(b->ev_h2d[k], b->s_h2d));
     HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_h2d[k], 0));
     const int set = (int) (b->nsubmit & 1);
-    const DenseOut saved = b->dense;
-    if (img) b->dense = DenseOut{img->buf, img->cap, b->hs_off[k], img->off};
-    const int r = encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, b->hs_out[k], out_stride, b->hs_nb[k], b->s_host, PASS_SUBMIT_HOST);
-    b->dense = saved;
-    if (r != 0) return -1;
+    Call c = call_on(b, b->hs_out[k], out_stride, b->hs_nb[k]);
+    if (img) c.opt.dense = DenseOut{img->buf, img->cap, b->hs_off[k], img->off};
+    if (encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, c, b->s_host, PASS_SUBMIT_HOST) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_hfront[k], b->s_front));
     HIPCHK(hipStreamWaitEvent(b->s_d2h, b->ev_alloc[set], 0));
     HIPCHK(hipMemcpyAsync(out_bytes, b->hs_nb[k], sizeof(int) * b->S, hipMemcpyDeviceToHost, b->s_d2h));
@@ -857,14 +851,14 @@ extern "C" float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls)
 }
 
 // the host-buffer PCM calls (host_call; the staging is not waited for before the upload: these calls end drained).
-// With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer).
-int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats)
+// With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer); with hd the dense image instead of the rows.
+int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd)
 {
-    if (check_call(b, in.p, nframes, out, out_stride, out_bytes) != 0) return -1;
-    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
-    return host_call(b, in.p, pbytes, false, nframes, out, out_stride, out_bytes, stats, [&] {
-        return encode_pass(b, {b->d_in, in.f32}, nframes, b->d_out, out_stride, b->d_outbytes, nullptr, PASS_PLAIN);
-    });
+    if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes) != 0) return -1;
+    if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
+    return host_call(b, in.p, in.bytes(b->S, nframes, b->nchan), false, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
+        return encode_pass(b, {b->d_in, in.f32}, nframes, c, nullptr, PASS_PLAIN);
+    }, hd);
 }
 
 extern "C" int hx_batch_encode_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out,
@@ -891,14 +885,8 @@ extern "C" int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nfram
 // fit in whole are a prefix of the streams, and that prefix is what is copied.)
 static int encode_host_dense(hx_batch *b, PcmIn in, int nframes, unsigned char *dense, long long dense_cap, long long *dense_off, int *out_bytes)
 {
-    const long long stride = hx_batch_out_stride(b, nframes);
-    if (check_call(b, in.p, nframes, dense, stride, out_bytes) != 0) return -1;
-    if (!dense_off || dense_cap < 0) { set_err("null buffer"); return -1; }
-    const long long pbytes = (long long) b->S * nframes * 1152 * b->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
     const HostDense hd = {dense, dense_cap, dense_off, hx_batch_dense_bound(b, nframes)};
-    return host_call(b, in.p, pbytes, false, nframes, nullptr, stride, out_bytes, nullptr, [&] {
-        return encode_pass(b, {b->d_in, in.f32}, nframes, b->d_out, stride, b->d_outbytes, nullptr, PASS_PLAIN);
-    }, &hd);
+    return encode_host(b, in, nframes, nullptr, hx_batch_out_stride(b, nframes), out_bytes, nullptr, &hd);
 }
 extern "C" int hx_batch_encode_s16_host_dense(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *dense, long long dense_cap,
                                               long long *dense_off, int *out_bytes)

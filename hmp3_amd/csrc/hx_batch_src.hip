@@ -106,7 +106,7 @@ static int src_check(const hx_batch *b, const void *in, long long in_stride, int
 
 // one converting call on device buffers (arguments checked by the caller): k_src into d_src_pcm, then the fp32 pass over it
 static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off, int nframes,
-                      unsigned char *d_out, long long out_stride, int *d_out_bytes, long long *in_used, void *stream)
+                      const Call &c, long long *in_used, void *stream)
 {
     // every call's input extent from the schedule, checked against the row before anything runs.  Consecutive calls: the
     // consumption telescopes, and the last call reaches furthest (a call reads at most ntaps - k past its successor's
@@ -161,7 +161,7 @@ static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_strid
     for (int s = 0; s < S; s++) b->src_calls[s] += nframes;
     b->src_lastF = nframes;
     if (in_used) memcpy(in_used, used_end.data(), sizeof(long long) * S);
-    if (encode_pass(b, {b->d_src_pcm, true}, nframes, d_out, out_stride, d_out_bytes, stream, PASS_PLAIN) != 0) return -1;
+    if (encode_pass(b, {b->d_src_pcm, true}, nframes, c, stream, PASS_PLAIN) != 0) return -1;
     return poison.ok();
 }
 
@@ -170,7 +170,7 @@ extern "C" int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in
                                           long long *in_used, void *stream)
 {
     if (src_check(b, d_in, in_stride, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
-    return src_encode(b, d_in, in_stride, frame_off, nframes, d_out, out_stride, d_out_bytes, in_used, stream);
+    return src_encode(b, d_in, in_stride, frame_off, nframes, call_on(b, d_out, out_stride, d_out_bytes), in_used, stream);
 }
 
 // (host_call with a drain before the upload: the staging may still be read by an earlier call)
@@ -179,7 +179,7 @@ extern "C" int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, lo
                                         long long *in_used, int *stats)
 {
     if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0) return -1;
-    return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&] {
-        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, b->d_out, out_stride, b->d_outbytes, in_used, nullptr);
+    return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
+        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, c, in_used, nullptr);
     });
 }

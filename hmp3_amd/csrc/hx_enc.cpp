@@ -98,14 +98,12 @@ static int enc_graph_build(hx_enc *e)
     HIPCHK(hipDeviceSynchronize());
     HIPCHK(hipStreamBeginCapture(e->gq, hipStreamCaptureModeThreadLocal));
     int r = 0;
-    b->capturing = true;
-    b->cap_frames = reinterpret_cast<unsigned *>(e->d_encbuf) + 1;
-    b->cap_host = e->h_out;
+    Call c = {e->d_encbuf + HX_ENC_GRAPH_OFF, stride, reinterpret_cast<int *>(e->d_encbuf)};    // (no optional outputs: encode_one)
+    c.rec_frames = reinterpret_cast<unsigned *>(e->d_encbuf) + 1;
+    c.rec_host = e->h_out;
+    c.recording = true;
     if (hipMemcpyAsync(b->d_in, e->h_pcm, (size_t) pbytes, hipMemcpyHostToDevice, e->gq) != hipSuccess) r = -1;
-    if (!r) r = encode_checked(b, {b->d_in, true}, 1, e->d_encbuf + HX_ENC_GRAPH_OFF, stride, reinterpret_cast<int *>(e->d_encbuf), e->gq, PASS_PLAIN);
-    b->capturing = false;
-    b->cap_frames = nullptr;
-    b->cap_host = nullptr;
+    if (!r) r = encode_checked(b, {b->d_in, true}, 1, c, e->gq, PASS_PLAIN);
     hipGraph_t g = nullptr;
     const hipError_t ce = hipStreamEndCapture(e->gq, &g);       // (always ended, also after a failure inside)
     if (r || ce != hipSuccess || !g) { if (g) hipGraphDestroy(g); (void) hipGetLastError(); set_err("recording the single-stream graph failed"); return -1; }
@@ -150,17 +148,17 @@ static bool enc_graph_call(hx_enc *e, const float *pcm, int *nb, unsigned *frame
     return true;
 }
 
-static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, int in_bytes)
+// opt: the call's optional outputs (the packet of the *_Packet entry points; the encoder's batch has none set)
+static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, int in_bytes, const OptOut &opt = OptOut())
 {
     HX_IN_OUT x = {in_bytes, 0};
     int nb = 0;
     unsigned frames = 0;
     const unsigned char *bs = nullptr;
     hx_batch *b = e->b;
-    // The graph replays a call with exactly the arguments it was recorded with: anything optional (packets, per-frame
-    // counters, debug taps: all set per call by the entry points that need them) goes the plain way, and so do the first
-    // two calls (which load the kernels).
-    const bool plain = b->debug || b->pk_buf || b->frame_stats || b->poisoned || b->inflight || e->graph_state < 0 || e->plain_calls < 2;
+    // The graph replays a call with exactly the arguments it was recorded with: anything optional (packets, debug taps)
+    // goes the plain way, and so do the first two calls (which load the kernels).
+    const bool plain = b->debug || opt.packet || b->poisoned || b->inflight || e->graph_state < 0 || e->plain_calls < 2;
     if (!plain && e->graph_state == 0) {
         const char *env = getenv("HMP3AMD_ENC_GRAPH");
         if (env && atoi(env) == 0) e->graph_state = -1;
@@ -174,7 +172,11 @@ static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, 
         if (!enc_graph_call(e, pcm, &nb, &frames)) return x;
         bs = e->h_out + HX_ENC_GRAPH_OFF;
     } else {
-        if (encode_host(b, {pcm, true}, 1, e->outbuf.data(), (long long) e->outbuf.size(), &nb, nullptr) != 0) return x;
+        // (encode_host's steps, with the call's own optional outputs in the record)
+        const long long cap = (long long) e->outbuf.size();
+        const auto pass = [&](Call c) { c.opt = opt; return encode_pass(b, {b->d_in, true}, 1, c, nullptr, PASS_PLAIN); };
+        if (check_call(b, pcm, 1, e->outbuf.data(), cap, &nb) != 0 ||
+            host_call(b, pcm, PcmIn{pcm, true}.bytes(1, 1, b->nchan), false, 1, e->outbuf.data(), cap, &nb, nullptr, pass) != 0) return x;
         bs = e->outbuf.data();
         frames = (unsigned) hx_batch_frames_bytes(b, 0).a;
         e->plain_calls++;
@@ -197,24 +199,25 @@ extern "C" HX_IN_OUT hx_enc_L3_audio_encode(hx_enc *e, const float *pcm, unsigne
 // bitstream in bs_out (may be NULL) plus this call's frame as a self-contained packet
 // (nbytes_out[0] bytes, nbytes_out[1] = 0; at the MPEG-2 rates two packets, nbytes_out[0] then
 // nbytes_out[1] bytes); packet may be NULL.
-extern "C" HX_IN_OUT hx_enc_MP3_audio_encode(hx_enc *e, const unsigned char *pcm, unsigned char *bs_out);
 static HX_IN_OUT encode_packet(hx_enc *e, const void *pcm, int mp3_entry, unsigned char *bs_out, unsigned char *packet, int nbytes_out[2])
 {
     std::vector<unsigned char> scratch;
     if (!bs_out) { scratch.resize(e->outbuf.size()); bs_out = scratch.data(); }
+    OptOut opt;
     if (packet) {
         hipSetDevice(e->device);
         if (!e->d_packet) { hipMalloc((void **) &e->d_packet, 4096); hipMalloc((void **) &e->d_packet_bytes, 2 * sizeof(int)); }
-        hx_batch_packet_buffers(e->b, e->d_packet, 4096, e->d_packet_bytes);
+        opt.packet = e->d_packet; opt.packet_stride = 4096; opt.packet_bytes = e->d_packet_bytes;
     }
-    HX_IN_OUT x = mp3_entry ? hx_enc_MP3_audio_encode(e, (const unsigned char *) pcm, bs_out) : hx_enc_L3_audio_encode(e, (const float *) pcm, bs_out);
+    float t[2304];      // (the MP3_audio_encode entry: convert, then encode)
+    const int in_bytes = mp3_entry ? hx_src_convert(e->src, (const unsigned char *) pcm, t, nullptr) : 4608 * e->p.nchan;
+    HX_IN_OUT x = encode_one(e, mp3_entry ? t : (const float *) pcm, bs_out, in_bytes, opt);
     if (packet) {
         int n[2] = {0, 0};      // an MPEG-2 call returns two single-granule packets back to back (mp3enc.cpp:3363)
         hipMemcpy(n, e->d_packet_bytes, 2 * sizeof(int), hipMemcpyDeviceToHost);
         hipMemcpy(packet, e->d_packet, (size_t) (n[0] + n[1]), hipMemcpyDeviceToHost);
         nbytes_out[0] = n[0];
         nbytes_out[1] = n[1];
-        hx_batch_packet_buffers(e->b, nullptr, 0, nullptr);
     }
     return x;
 }
@@ -320,10 +323,7 @@ extern "C" int hx_enc_MP3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec, i
 extern "C" HX_IN_OUT hx_enc_MP3_audio_encode(hx_enc *e, const unsigned char *pcm, unsigned char *bs_out)
 {
     float t[2304];
-    const int in_bytes = hx_src_convert(e->src, pcm, t, nullptr);
-    HX_IN_OUT x = hx_enc_L3_audio_encode(e, t, bs_out);
-    x.in_bytes = in_bytes;
-    return x;
+    return encode_one(e, t, bs_out, hx_src_convert(e->src, pcm, t, nullptr));
 }
 
 extern "C" void hx_enc_out_stats(hx_enc *e)

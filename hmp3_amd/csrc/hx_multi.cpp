@@ -212,7 +212,7 @@ static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *
 {
     return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
         const long long f = m->first[k];
-        const char *p = (const char *) in.p + (size_t) f * nframes * 1152 * m->nchan * (in.f32 ? sizeof(float) : sizeof(int16_t));
+        const char *p = (const char *) in.p + in.bytes(f, nframes, m->nchan);
         return encode_host(m->part[k], {p, in.f32}, nframes, out + f * out_stride, out_stride, out_bytes + f, stats ? stats + f * nframes * 2 : nullptr);
     });
 }

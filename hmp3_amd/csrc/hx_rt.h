@@ -89,6 +89,18 @@ struct WalkSet {
 // Where a call's dense image goes (hx_batch_dense_buffers): buf null = off.  off_copy: a second place for the offsets (the
 // pipelined host calls, whose offsets go to the caller's page-locked array as well as to device staging).
 struct DenseOut { unsigned char *buf = nullptr; long long cap = 0; long long *off = nullptr, *off_copy = nullptr; };
+// The optional outputs of a call, all in device memory, null = off: every frame as a packet (hx_batch_packet_buffers), the
+// per-frame counters (hx_batch_frame_stats_buffer) and the dense image.
+struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; };
+// Everything one call writes, fixed when the call is made: the rows, the optional outputs and, for the pass the one-stream
+// encoder records into a HIP graph (hx_enc.cpp; no timing events, nothing that queries the stream), where k_pack_carry
+// leaves the stream's frame counter and the page-locked host memory the packing workgroup publishes the call's results to
+// (hx_pack.hip).  The stream walk and the packing get this record, so nothing set on the batch afterwards reaches the call.
+struct Call {
+    unsigned char *out = nullptr; long long out_stride = 0; int *out_bytes = nullptr;
+    OptOut opt;
+    unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
+};
 
 struct hx_batch {
     int device = 0, S = 0, maxF = 0, ncls = 0;
@@ -103,9 +115,7 @@ struct hx_batch {
     unsigned *sgn[3] = {};              // the lines' signs, one bit per line: [S][NG][2][HX_SGN_WORDS]; read by the packing, so three sets
                                         // on the submit path (the front end of call n + 2 writes one while call n is packed)
     int *d_lens = nullptr;              // [2 sets][pre_len | carry_len][S]
-    int *frame_stats = nullptr;         // caller's per-frame counters (device), optional
-    unsigned char *pk_buf = nullptr; long long pk_stride = 0; int *pk_bytes = nullptr;   // caller's packet buffers (device), optional
-    DenseOut dense;                     // caller's dense image (device), optional
+    OptOut opt;                         // the caller's optional outputs: what the three setters leave, and what a call made now takes (call_on)
     float *d_pcmf = nullptr;            // DC-blocked input, only when a stream uses filter_select = 1
     bool any_dc = false;
     int nchan = 2;                      // channels of the PCM input, the same for every stream of the batch
@@ -148,9 +158,9 @@ struct hx_batch {
     hipEvent_t ev_sgn[3] = {nullptr, nullptr, nullptr}; // the packing that read this set of signs is done
     // the packing of the latest device-buffer submit, not enqueued yet: it goes out behind the next submit's allocator launch
     // (released by a gate like the front end, into that launch's tail), or ungated at the next wait / plain call
-    // (packet: the packet buffer in force at the submit - the stream walk has put the packets' headers there already;
-    // dense: the dense image's buffers in force at the submit - the image kernels go out with the packing)
-    struct PackJob { bool pending = false; unsigned char *d_out = nullptr; long long out_stride = 0; int *d_out_bytes = nullptr; unsigned char *packet = nullptr; DenseOut dense; int nframes = 0, set = 0, sset = 0; } pack_job;
+    // (call: the submit's record - the stream walk has put the packets' headers into its packet buffer already, and the image
+    // kernels go out with the packing)
+    struct PackJob { bool pending = false; Call call; int nframes = 0, set = 0, sset = 0; } pack_job;
     long long nsubmit = 0;
     bool inflight = false;
     // hx_batch_submit_*_host: device staging for two calls in flight and the copy streams
@@ -170,9 +180,6 @@ struct hx_batch {
     // Not 100: the gate's own wavefront holds register space on one SIMD, so the last allocator workgroup of a full
     // chip cannot start before a stream retires (measured: 10 .. 99 % all give the same step time, 100 % loses 30 %)
     int gate_percent = 90;
-    bool capturing = false;             // the pass is being recorded into a HIP graph (hx_enc_*): no timing events, nothing that queries the stream
-    unsigned *cap_frames = nullptr;     // one-stream encoder: where k_pack_carry leaves the stream's frame counter (next to the byte count)
-    unsigned char *cap_host = nullptr;  // one-stream encoder: page-locked host memory the packing workgroup publishes the call's results to (hx_pack.hip)
     bool poisoned = false;              // a HIP call failed in the middle of a pass: the event bookkeeping is incomplete, further calls are refused
     // longest-first workgroup order: 2 = for every batch with more streams than the chip has CUs (default: below that no two
     // streams share a CU and the order decides nothing), 3 = always (tests), 1 = only for batches beyond the resident set,
@@ -236,8 +243,13 @@ struct Poison {
 };
 HX_LOCAL int check_poisoned(const hx_batch *b);
 
-// the PCM of a pass: int16, or fp32 at int16 scale
-struct PcmIn { const void *p; bool f32; };
+// the PCM of a pass: int16, or fp32 at int16 scale; bytes: of nframes frames of S streams
+struct PcmIn {
+    const void *p; bool f32;
+    long long bytes(long long S, int nframes, int nchan) const { return S * nframes * 1152 * nchan * (long long) (f32 ? sizeof(float) : sizeof(int16_t)); }
+};
+// a call that writes the caller's rows and the optional outputs set on the batch (a null batch: the argument checks refuse it)
+static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_stride, int *out_bytes) { return {out, out_stride, out_bytes, b ? b->opt : OptOut()}; }
 // where a pass runs: every kernel on the caller's stream, or (hx_batch_submit_*) front end and stream walk on the batch's
 // own two streams, ordered by events (see hx_batch); a device-buffer submit also defers its packing
 enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
@@ -247,23 +259,25 @@ enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
 HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes);
 HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes);
 // one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass
-HX_LOCAL int encode_pass(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind);
-HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes, void *stream, PassKind kind);
-HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats);
+HX_LOCAL int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
+HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
+// the host-buffer PCM calls; hd: the *_host_dense calls' image, its capacity and offsets in host memory (see host_call)
+struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
+HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr);
 // Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
 HX_LOCAL int drain(hx_batch *b);
 // the encode control of a converted source and its converter (hx_enc.cpp)
 HX_LOCAL int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int source_is_float, int mpeg_select, int mono_convert,
                                 hx_src *conv, HX_E_CONTROL *ec_out);
 
-// One host-buffer call: grow the staging, copy the input up, make the device call `encode()` on b->d_in / d_out /
-// d_outbytes, wait for it and copy the results back - with `stats`, also the call's per-frame counters (see
-// hx_batch_frame_stats_buffer), which the device call then writes to staging of the batch's instead of the caller's buffer.
+// One host-buffer call: grow the staging, copy the input up, make the device call `encode(c)`, wait for it and copy the
+// results back.  c is the call's record: the rows are b->d_out / d_outbytes; with `stats` the call's per-frame counters
+// (see hx_batch_frame_stats_buffer) go to b->d_stats and come back to the host, and the caller's device counter buffer is
+// not written; every other optional output is the one set on the batch.
 // drain_first: the staging may still be read by an earlier call that did not wait for its end.
-// hd (the *_host_dense calls): the device call also writes the dense image and its offsets to staging, and those come back
-// instead of the rows (`out` is not used): the offsets, and the image up to the last segment that fits hd->cap in whole -
-// the segments that fit are a prefix of the streams, and none of them ends beyond hd->bound.
-struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
+// hd (the *_host_dense calls): the dense image and its offsets go to staging too, not to the caller's device image, and
+// come back instead of the rows (`out` is not used): the offsets, and the image up to the last segment that fits hd->cap
+// in whole - the segments that fit are a prefix of the streams, and none of them ends beyond hd->bound.
 template <class Encode>
 static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
                      long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr)
@@ -275,14 +289,10 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
                (!b->d_dense_off && dev_alloc(b, b->d_dense_off, (long long) sizeof(long long) * (b->S + 1))))) return -1;
     if (drain_first && drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));
-    int *const saved = b->frame_stats;
-    const DenseOut saved_dense = b->dense;
-    if (stats) b->frame_stats = b->d_stats;
-    if (hd) b->dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
-    const int r = encode();
-    b->frame_stats = saved;
-    b->dense = saved_dense;
-    if (r != 0 || drain(b) != 0) return -1;
+    Call c = call_on(b, b->d_out, out_stride, b->d_outbytes);
+    if (stats) c.opt.frame_stats = b->d_stats;
+    if (hd) c.opt.dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
+    if (encode(c) != 0 || drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
     if (hd) {
         HIPCHK(hipMemcpy(hd->off, b->d_dense_off, sizeof(long long) * (b->S + 1), hipMemcpyDeviceToHost));

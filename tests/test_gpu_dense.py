@@ -100,6 +100,12 @@ class Image:
     def set_on(self, b):
         b.dense_buffers(self.ptr, self.cap, self.off.data_ptr())
 
+    def prefill(self):
+        """(again: the same buffers for a further call, the batch's setter untouched)"""
+        self.buf.fill_(self.fill)
+        self.off.fill_(-1)
+        sync()
+
     def host(self):
         return self.buf.cpu().numpy()[self.o:self.o + self.cap + GUARD], self.off.cpu().numpy()
 
@@ -337,6 +343,39 @@ def test_synchronous_host_calls_return_the_image_of_the_row_calls():
     assert off2.tolist() == off1.tolist() and b.status() == 16
     fits = int(np.searchsorted(off2, half, side="right")) - 1
     assert 0 < fits < S and got[:fits] == want[1][:fits] and all(g is None for g in got[fits:])
+    b.close()
+
+
+def test_device_image_set_once_holds_across_a_host_call_that_returns_the_image():
+    """The setter is sticky, and a host call that returns the image takes it for itself only: device dense buffers set once,
+    then a device call, hx_batch_encode_f32_host_dense and a device call (3 streams, VBR-50, 2 frames each), the image and
+    offsets prefilled again before each without a word to the batch.  The device calls' image equals their rows, which are
+    a twin batch's; the host call returns the twin's bitstreams and leaves the device image and offsets as prefilled."""
+    S, nf = 3, 2
+    controls, pcm = mixed_controls(S), mixed_pcm(S, 3 * nf, 3500)
+    t = api().Batch(controls, max_frames=nf)
+    want = [t.encode_host(cut(pcm, c * nf, nf)) for c in range(3)]
+    assert t.status() == 0 and sum(len(w) for ws in want for w in ws) > 0
+    t.close()
+    b = api().Batch(controls, max_frames=nf)
+    img = Image(S, b.dense_bound(nf))
+    img.set_on(b)
+    for c in range(3):
+        blk = cut(pcm, c * nf, nf)
+        if c > 0:
+            img.prefill()
+        if c == 1:
+            got, off = b.encode_host_dense(blk)
+            assert got == want[c] and off.tolist() == closed_form([len(w) for w in want[c]]).tolist()
+            dense, d_off = img.host()
+            assert (dense == FILL).all() and (d_off == -1).all(), "the host call wrote the caller's device image"
+        else:
+            r, d_pcm = device_call(b, blk, nf, None)
+            sync()
+            rows, nb = r.host()
+            assert [rows[s, :nb[s]].tobytes() for s in range(S)] == want[c], "call %d: rows differ from the twin batch's" % c
+            check_image(rows, nb, *img.host(), img.cap, tag="call %d" % c)
+        assert b.status() == 0
     b.close()
 
 

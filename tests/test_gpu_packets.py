@@ -31,11 +31,20 @@ class Outputs:
         import torch
         dev = torch.device("cuda:0")
         self.nf, self.frame_stride, self.stride = nf, frame_stride, b.out_stride(nf)
-        self.out = torch.zeros((b.n, self.stride), dtype=torch.uint8, device=dev)
-        self.nb = torch.full((b.n,), -1, dtype=torch.int32, device=dev)
-        self.pk = torch.full((b.n, nf, frame_stride), FILL, dtype=torch.uint8, device=dev)
-        self.pkb = torch.full((b.n, nf, 2), -1, dtype=torch.int32, device=dev)
-        self.st = torch.full((b.n, nf, 2), -1, dtype=torch.int32, device=dev)
+        self.out = torch.empty((b.n, self.stride), dtype=torch.uint8, device=dev)
+        self.nb = torch.empty((b.n,), dtype=torch.int32, device=dev)
+        self.pk = torch.empty((b.n, nf, frame_stride), dtype=torch.uint8, device=dev)
+        self.pkb = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
+        self.st = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
+        self.prefill()
+
+    def prefill(self):
+        """(again: the same buffers for a further call, the batch's setters untouched)"""
+        import torch
+        self.out.zero_()
+        self.pk.fill_(FILL)
+        for t in (self.nb, self.pkb, self.st):
+            t.fill_(-1)
         torch.cuda.synchronize()
 
     def set_on(self, b, stats=True):
@@ -162,6 +171,39 @@ def test_solo_packing_with_more_than_one_stream(kw, S):
     """at most 4 streams and 8 frames in a call: one workgroup packs them all and moves the pending frames' images in and
     out of the stream state (k_pack, solo); streams behind the first, the second case with exactly 8 frames"""
     run_calls(kw, S, [(2, device_call), (2, host_call), (2, device_call)], 4096, seed=6500)
+
+
+@pytest.mark.parametrize("S", [3, 6], ids=["one_workgroup_packing", "many_workgroup_packing"])
+def test_buffers_set_once_hold_across_a_host_call_that_returns_the_counters(S):
+    """The setters are sticky, and a host call that returns the counters takes them for itself only: packet and counter
+    buffers set once, then a device call, hx_batch_encode_f32_host_stats and a device call, the buffers prefilled again
+    before each without a word to the batch.  The device calls write packets, sizes and counters; the host call writes
+    packets and sizes, returns its counters to the host and leaves the device counter buffer as it was prefilled.  CBR
+    128, calls of 2 frames: 3 streams are packed by one workgroup, 6 by the many-workgroup k_pack."""
+    import torch
+    kw, nf = dict(bitrate=64), 2
+    pcm = PC.packet_pcm(6800, S, 3 * nf, kw)
+    want = [PC.oracle_frames(kw, pcm[s]) for s in range(S)]
+    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
+    o = Outputs(b, nf, 4096)
+    o.set_on(b)
+    for c in range(3):
+        blk = cut(pcm, c * nf, nf)
+        if c > 0:
+            o.prefill()
+        if c == 1:
+            bs, stats = b.encode_host(blk, stats=True)
+            pk, pkb, st = o.host()
+            assert (st == -1).all(), "the host call wrote the caller's device counter buffer"
+        else:
+            d_pcm = torch.from_numpy(blk).to(torch.device("cuda:0"))
+            torch.cuda.synchronize()
+            b.encode_device(d_pcm.data_ptr(), nf, o.out.data_ptr(), o.stride, o.nb.data_ptr(), torch.cuda.current_stream().cuda_stream, f32=True)
+            torch.cuda.synchronize()
+            bs, (pk, pkb, stats) = o.bitstreams(), o.host()
+        assert b.status() == 0
+        check_call(want, c * nf, nf, bs, pk, pkb, stats, 0, "call %d" % c)
+    b.close()
 
 
 def test_packets_and_counters_are_indexed_by_stream_under_a_launch_order(monkeypatch):

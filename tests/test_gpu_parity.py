@@ -192,6 +192,33 @@ def test_packet_variant_matches_oracle(kw):
     e.close()
 
 
+@pytest.mark.parametrize("kw", [dict(bitrate=64), dict(samprate=22050, bitrate=32)], ids=["cbr128", "mpeg2_cbr32"])
+def test_packet_calls_between_plain_and_replayed_calls_of_one_encoder(kw):
+    """The packet buffers are an argument of the *_Packet call alone: one encoder's frames 0-3 through L3_audio_encode (two
+    plain calls, then the recorded graph), 4-5 through L3_audio_encode_Packet, 6-9 through L3_audio_encode again; every
+    call's bitstream and the two calls' packets against one oracle encoder (MPEG-2: two packets per call)."""
+    nfr = 10
+    pcm = synth.stream_pcm(29, nfr, sr=kw.get("samprate", 44100), bursts=True).astype(np.float32)
+    e = api().Mp3Enc()
+    assert e.L3_audio_encode_init(api().default_control(**kw)) == 9216
+    o = O.OracleEncoder(O.default_control(**kw))
+    total = 0
+    for f in range(nfr):
+        blk = pcm[f * 1152:(f + 1) * 1152]
+        if f in (4, 5):
+            nin, bs, pk = e.L3_audio_encode_Packet(blk)
+            want_bs, want_pk = o.encode_packet(blk)
+            assert pk == want_pk and e.packet_sizes == tuple(o.packet_sizes), "frame %d: packet" % f
+            assert e.packet_sizes[0] > 0 and (e.packet_sizes[1] > 0) == (kw.get("samprate", 44100) < 32000)
+        else:
+            nin, bs = e.L3_audio_encode(blk)
+            want_bs = o.encode_f32(blk)
+        assert nin == 9216 and bs == want_bs, "frame %d" % f
+        total += len(bs)
+    assert total > 0
+    e.close()
+
+
 SHIM_CLI = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "hmp3_on_amd")
 
 
