@@ -166,6 +166,11 @@ def last_error():
     return lib().hx_last_error().decode()
 
 
+def crc_combine(a, b, n):
+    """the MusicCRC of A ++ B from a = CRC(0, A), b = CRC(0, B) and n = len(B) (hx_xing_crc_combine)"""
+    return int(lib().hx_xing_crc_combine(int(a), int(b), int(n)))
+
+
 class Batch:
     """N independent streams on one GPU (hx_batch_*)."""
 
@@ -197,9 +202,16 @@ class Batch:
         to, after every input frame; None switches it off"""
         lib().hx_batch_frame_stats_buffer(self.h, d_stats_ptr)
 
-    def encode_host(self, pcm, stats=False):
+    def crc_buffer(self, d_crc_ptr):
+        """device buffer [n, nframes] uint16 that the calls that follow write the MusicCRC of their bytes up to every input
+        frame to (include/hmp3_amd.h, "MusicCRC"; needs a frame_stats_buffer in force); None switches it off"""
+        if lib().hx_batch_crc_buffer(self.h, d_crc_ptr) != 0:
+            raise RuntimeError("hx_batch_crc_buffer failed: " + last_error())
+
+    def encode_host(self, pcm, stats=False, crc=False):
         """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, 2] -> list of bytes per stream; with stats (float32
-        only) -> (that list, int32 [n, nframes, 2]: frames / bytes emitted so far after every input frame)"""
+        only) -> (that list, int32 [n, nframes, 2]: frames / bytes emitted so far after every input frame); with stats and
+        crc -> (list, stats, uint16 [n, nframes]: the CRC of the call's bytes up to every input frame)"""
         f32 = np.asarray(pcm).dtype == np.float32
         pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
         if pcm.ndim == 2:
@@ -209,18 +221,24 @@ class Batch:
         stride = self.out_stride(nfr)
         out = np.zeros((self.n, stride), dtype=np.uint8)
         nb = np.zeros(self.n, dtype=np.int32)
+        if crc and not stats:
+            raise TypeError("encode_host(crc=True) needs stats=True (hx_batch_encode_f32_host_crc returns both)")
         if stats:
             if not f32:
                 raise TypeError("encode_host(stats=True) takes float32 PCM (hx_batch_encode_f32_host_stats)")
             st = np.zeros((self.n, nfr, 2), dtype=np.int32)
-            r = lib().hx_batch_encode_f32_host_stats(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data)
+            if crc:
+                cr = np.zeros((self.n, nfr), dtype=np.uint16)
+                r = lib().hx_batch_encode_f32_host_crc(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data, cr.ctypes.data)
+            else:
+                r = lib().hx_batch_encode_f32_host_stats(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data)
         else:
             fn = lib().hx_batch_encode_f32_host if f32 else lib().hx_batch_encode_s16_host
             r = fn(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data)
         if r != 0:
             raise RuntimeError("hx_batch_encode host call failed: " + last_error())
         res = [out[i, :nb[i]].tobytes() for i in range(self.n)]
-        return (res, st) if stats else res
+        return (res, st, cr) if crc else (res, st) if stats else res
 
     def dense_bound(self, nframes):
         """worst-case bytes of a call's dense image"""
@@ -443,17 +461,32 @@ class Multi:
             raise IndexError(k)
         return d.value, f.value, c.value
 
-    def encode_host(self, pcm):
+    def encode_host(self, pcm, stats=False, crc=False):
+        """as Batch.encode_host, over all streams"""
         f32 = np.asarray(pcm).dtype == np.float32
         pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
         nfr = pcm.shape[1] // 1152
         stride = int(lib().hx_multi_out_stride(self.h, nfr))
         out = np.zeros((self.n, stride), dtype=np.uint8)
         nb = np.zeros(self.n, dtype=np.int32)
-        fn = lib().hx_multi_encode_f32_host if f32 else lib().hx_multi_encode_s16_host
-        if fn(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data) != 0:
+        if crc and not stats:
+            raise TypeError("encode_host(crc=True) needs stats=True (hx_multi_encode_f32_host_crc returns both)")
+        if stats:
+            if not f32:
+                raise TypeError("encode_host(stats=True) takes float32 PCM (hx_multi_encode_f32_host_stats)")
+            st = np.zeros((self.n, nfr, 2), dtype=np.int32)
+            if crc:
+                cr = np.zeros((self.n, nfr), dtype=np.uint16)
+                r = lib().hx_multi_encode_f32_host_crc(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data, cr.ctypes.data)
+            else:
+                r = lib().hx_multi_encode_f32_host_stats(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data)
+        else:
+            fn = lib().hx_multi_encode_f32_host if f32 else lib().hx_multi_encode_s16_host
+            r = fn(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data)
+        if r != 0:
             raise RuntimeError("hx_multi_encode host call failed: " + last_error())
-        return [out[i, :nb[i]].tobytes() for i in range(self.n)]
+        res = [out[i, :nb[i]].tobytes() for i in range(self.n)]
+        return (res, st, cr) if crc else (res, st) if stats else res
 
     def status(self):
         return int(lib().hx_multi_status(self.h))

@@ -464,6 +464,10 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
     const std::vector<unsigned char> zero_frame(2304 * 4, 0);
     std::vector<unsigned char> out((size_t) S * stride);
     std::vector<int> nb(S), stats((size_t) S * CH * 2);
+    // the MusicCRC per file: every call returns the CRC of its own bytes up to each input frame (k_crc, on the GPU), and the
+    // file's is those joined by hx_xing_crc_combine - whole calls, then the call in which the file's drain ends up to there
+    std::vector<unsigned short> crc((size_t) S * CH), file_crc(S, 0);
+    std::vector<char> crc_done(S, 0);
     std::vector<std::vector<unsigned char>> stream(S);
     std::vector<std::vector<unsigned>> fr(S), by(S);    // per input frame: frames / bytes out so far
     for (size_t c0 = 0; c0 < total; c0 += CH) {
@@ -477,7 +481,7 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
                 memcpy(&pcm[((size_t) i * CH + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
             }
         }
-        if (hx_multi_encode_f32_host_stats(b, pcm.data(), CH, out.data(), stride, nb.data(), stats.data()) != 0) {
+        if (hx_multi_encode_f32_host_crc(b, pcm.data(), CH, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
             return 1;
@@ -485,6 +489,17 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
         for (int i = 0; i < S; i++) {
             stream[i].insert(stream[i].end(), out.begin() + (size_t) i * stride, out.begin() + (size_t) i * stride + nb[i]);
             for (int k = 0; k < CH; k++) { fr[i].push_back((unsigned) stats[((size_t) i * CH + k) * 2]); by[i].push_back((unsigned) stats[((size_t) i * CH + k) * 2 + 1]); }
+            if (crc_done[i]) continue;
+            // the last input frame the file uses (the per-file loop below: u - 1), if it lies in this call
+            const size_t calls = ncalls(in[i]), expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);
+            int k = c0 + CH >= calls ? (int) (calls - 1 > c0 ? calls - 1 - c0 : 0) : CH;
+            while (k < CH && fr[i][c0 + k] < expected) k++;
+            if (k < CH) {
+                const unsigned e = (unsigned) nb[i] - (by[i][c0 + CH - 1] - by[i][c0 + k]);     // this call's bytes up to there
+                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * CH + k], (long long) e);
+                crc_done[i] = 1;
+            } else
+                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * CH + CH - 1], nb[i]);
         }
     }
     if (hx_multi_status(b) != 0) fprintf(stderr, "\n WARNING: kernel status %d\n", hx_multi_status(b));
@@ -501,7 +516,7 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
         while (u < fr[i].size() && fr[i][u - 1] < expected) u++;
         if (fr[i][u - 1] < expected) { fprintf(stderr, "\n %s: drain did not complete\n", files[2 * i]); rc = 1; }
         const unsigned frames = fr[i][u - 1], nbytes = by[i][u - 1];
-        tg.bytes(stream[i].data(), (int) nbytes);
+        tg.crc = file_crc[i];
         const uint64_t out_bytes = (uint64_t) tg.head_bytes + nbytes;
         if (opt.xing_flag) tg.finish(in[i], frames, out_bytes);
         FILE *o = fopen(files[2 * i + 1], "wb");

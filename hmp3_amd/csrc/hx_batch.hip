@@ -323,6 +323,14 @@ extern "C" void hx_batch_packet_buffers(hx_batch *b, unsigned char *d_packet, lo
 
 extern "C" void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats) { b->opt.frame_stats = d_stats; }
 
+extern "C" int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (((unsigned long long) d_crc & 1) != 0) { set_err("d_crc must be 2-byte aligned"); return -1; }
+    b->opt.crc = d_crc;
+    return 0;
+}
+
 extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
 {
     return b ? (long long) b->S * ((hx_batch_out_stride(b, nframes) + 15) & ~15LL) : 0;
@@ -377,6 +385,13 @@ int check_args(const hx_batch *b, const void *in, int nframes, const void *out, 
     if (out_stride < hx_batch_out_stride(b, nframes)) { set_err("out_stride is smaller than hx_batch_out_stride(b, nframes)"); return -1; }
     return 0;
 }
+// (k_crc takes every e[f] from the call's frame counters, and the batch keeps no counter buffer of its own for it: two
+// pipelined submits would race on one)
+int check_opt(const OptOut &o)
+{
+    if (o.crc && !o.frame_stats) { set_err("a CRC buffer (hx_batch_crc_buffer) needs a frame-counter buffer (hx_batch_frame_stats_buffer) in force"); return -1; }
+    return 0;
+}
 // (a converting batch takes its input through hx_batch_encode_src_* only: a plain call would advance the encoder past its converter)
 int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
 {
@@ -419,6 +434,14 @@ static int enqueue_dense(hx_batch *b, const Call &c, int nframes, hipStream_t qp
     return 0;
 }
 
+// the per-frame MusicCRC of one call on stream qp, behind its packing (hx_crc.hip): one workgroup per stream
+static int enqueue_crc(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
+{
+    if (!c.opt.crc) return 0;
+    LAUNCH(k_crc, dim3(b->S), dim3(256), qp, c.out, c.out_stride, c.out_bytes, (const int *) c.opt.frame_stats, nframes, c.opt.crc);
+    return 0;
+}
+
 // A gate on stream q: what follows it there starts in the tail of the allocator launch whose first workgroup took number
 // `base` of the started-counter (it wraps with the counter), not at that launch's start.
 static int launch_gate(hx_batch *b, hipStream_t q, unsigned base)
@@ -438,7 +461,8 @@ static int flush_pack(hx_batch *b, long long gate_base)
     j.pending = false;
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
-    if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0) return -1;
+    if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0 ||
+        enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -620,7 +644,7 @@ static int place_pack(hx_batch *b, const Pass &p)
     // the previous device-buffer submit's packing went out on the packing stream in pipe_enter: its k_pack_carry writes
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
-    if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0) return -1;
+    if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0 || enqueue_crc(b, p.call, p.nframes, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -662,7 +686,7 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream,
 }
 int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
-    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0) return -1;
+    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(c.opt) != 0) return -1;
     return encode_pass(b, in, nframes, c, stream, kind);
 }
 
@@ -726,7 +750,7 @@ extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
 // image kernels of the call write them, and the rows stay in the staging: out is not used
 static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, const DenseOut *img = nullptr)
 {
-    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0) return -1;
+    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b->opt) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
     const long long pbytes = in.bytes(b->S, nframes, b->nchan), obytes = (long long) b->S * out_stride;
@@ -852,13 +876,14 @@ extern "C" float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls)
 
 // the host-buffer PCM calls (host_call; the staging is not waited for before the upload: these calls end drained).
 // With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer); with hd the dense image instead of the rows.
-int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd)
+int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd,
+                unsigned short *crc)
 {
     if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes) != 0) return -1;
     if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
     return host_call(b, in.p, in.bytes(b->S, nframes, b->nchan), false, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
         return encode_pass(b, {b->d_in, in.f32}, nframes, c, nullptr, PASS_PLAIN);
-    }, hd);
+    }, hd, crc);
 }
 
 extern "C" int hx_batch_encode_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out,
@@ -872,6 +897,13 @@ extern "C" int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int
 {
     if (!stats) { set_err("null buffer"); return -1; }
     return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, stats);
+}
+
+extern "C" int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
+                                            long long out_stride, int *out_bytes, int *stats, unsigned short *crc)
+{
+    if (!stats || !crc) { set_err("null buffer"); return -1; }
+    return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, stats, nullptr, crc);
 }
 
 extern "C" int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out,

@@ -169,7 +169,7 @@ extern "C" int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in
                                           int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes,
                                           long long *in_used, void *stream)
 {
-    if (src_check(b, d_in, in_stride, nframes, d_out, out_stride, d_out_bytes) != 0) return -1;
+    if (src_check(b, d_in, in_stride, nframes, d_out, out_stride, d_out_bytes) != 0 || check_opt(b->opt) != 0) return -1;
     return src_encode(b, d_in, in_stride, frame_off, nframes, call_on(b, d_out, out_stride, d_out_bytes), in_used, stream);
 }
 

@@ -208,12 +208,14 @@ static int multi_fanout(hx_multi *m, bool buffers_ok, int nframes, long long out
 }
 
 // the PCM calls: each device on its block's rows of the caller's buffers
-static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats)
+static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats,
+                             unsigned short *crc = nullptr)
 {
     return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
         const long long f = m->first[k];
         const char *p = (const char *) in.p + in.bytes(f, nframes, m->nchan);
-        return encode_host(m->part[k], {p, in.f32}, nframes, out + f * out_stride, out_stride, out_bytes + f, stats ? stats + f * nframes * 2 : nullptr);
+        return encode_host(m->part[k], {p, in.f32}, nframes, out + f * out_stride, out_stride, out_bytes + f, stats ? stats + f * nframes * 2 : nullptr,
+                           nullptr, crc ? crc + f * nframes : nullptr);
     });
 }
 extern "C" int hx_multi_encode_s16_host(hx_multi *m, const int16_t *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes)
@@ -228,6 +230,12 @@ extern "C" int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int
 {
     if (!stats) { set_err("null buffer"); return -1; }
     return multi_encode_host(m, {pcm, true}, nframes, out, out_stride, out_bytes, stats);
+}
+extern "C" int hx_multi_encode_f32_host_crc(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats,
+                                            unsigned short *crc)
+{
+    if (!stats || !crc) { set_err("null buffer"); return -1; }
+    return multi_encode_host(m, {pcm, true}, nframes, out, out_stride, out_bytes, stats, crc);
 }
 extern "C" long long hx_multi_src_in_stride(const hx_multi *m, int nframes)
 {

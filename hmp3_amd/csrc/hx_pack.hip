@@ -456,3 +456,6 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
         dst[v] = val;
     }
 }
+
+// ---- the MusicCRC of a call's rows (hx_batch_crc_buffer): k_crc, a file of its own, built as part of this unit ----
+#include "hx_crc.hip"

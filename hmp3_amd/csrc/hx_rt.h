@@ -51,6 +51,7 @@ __global__ void k_pack_pre(const HxStream *st, unsigned char *out, long long out
 __global__ void k_dense_off(const int *out_bytes, long long *off, long long *off_copy, int S, long long cap, int *status);
 __global__ void k_dense_gather(const unsigned char *out, long long out_stride, const int *out_bytes, const long long *off, unsigned char *dense,
                                long long cap, int chunks);
+__global__ void k_crc(const unsigned char *out, long long out_stride, const int *out_bytes, const int *stats, int nframes, unsigned short *crc);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
 __global__ void k_alloc(AllocArgs a);
@@ -90,8 +91,9 @@ struct WalkSet {
 // pipelined host calls, whose offsets go to the caller's page-locked array as well as to device staging).
 struct DenseOut { unsigned char *buf = nullptr; long long cap = 0; long long *off = nullptr, *off_copy = nullptr; };
 // The optional outputs of a call, all in device memory, null = off: every frame as a packet (hx_batch_packet_buffers), the
-// per-frame counters (hx_batch_frame_stats_buffer) and the dense image.
-struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; };
+// per-frame counters (hx_batch_frame_stats_buffer), the dense image and the per-frame MusicCRC (hx_batch_crc_buffer; k_crc
+// reads the counters, so a call with crc needs frame_stats: check_opt).
+struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; unsigned short *crc = nullptr; };
 // Everything one call writes, fixed when the call is made: the rows, the optional outputs and, for the pass the one-stream
 // encoder records into a HIP graph (hx_enc.cpp; no timing events, nothing that queries the stream), where k_pack_carry
 // leaves the stream's frame counter and the page-locked host memory the packing workgroup publishes the call's results to
@@ -148,6 +150,7 @@ struct hx_batch {
     void *d_in = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr, *d_stats = nullptr;
     long long in_cap = 0, out_cap = 0, stats_cap = 0;
     unsigned char *d_dense = nullptr; long long *d_dense_off = nullptr; long long dense_cap = 0;   // ... and of the *_host_dense calls: image and offsets
+    unsigned short *d_crc = nullptr; long long crc_cap = 0;                                         // ... and of the *_host_crc calls: the per-frame CRCs
     std::vector<std::pair<hipEvent_t, hipEvent_t>> pending;
     double alloc_ms_sum = 0; int alloc_calls = 0;
     // hx_batch_submit_*: the front-end kernels of call n+1 run (low-priority stream) while k_alloc of
@@ -258,12 +261,15 @@ enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
 // the PCM entry points, which a converting batch refuses
 HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes);
 HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes);
+// ... and of the optional outputs a call would take: a CRC buffer without frame counters is refused
+HX_LOCAL int check_opt(const OptOut &o);
 // one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass
 HX_LOCAL int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
 HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
 // the host-buffer PCM calls; hd: the *_host_dense calls' image, its capacity and offsets in host memory (see host_call)
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
-HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr);
+HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
+                         unsigned short *crc = nullptr);
 // Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
 HX_LOCAL int drain(hx_batch *b);
 // the encode control of a converted source and its converter (hx_enc.cpp)
@@ -273,24 +279,34 @@ HX_LOCAL int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int sou
 // One host-buffer call: grow the staging, copy the input up, make the device call `encode(c)`, wait for it and copy the
 // results back.  c is the call's record: the rows are b->d_out / d_outbytes; with `stats` the call's per-frame counters
 // (see hx_batch_frame_stats_buffer) go to b->d_stats and come back to the host, and the caller's device counter buffer is
-// not written; every other optional output is the one set on the batch.
+// not written; with `crc` (the *_host_crc calls, which pass `stats` too) the same for the per-frame CRCs, through b->d_crc;
+// every other optional output is the one set on the batch.
 // drain_first: the staging may still be read by an earlier call that did not wait for its end.
 // hd (the *_host_dense calls): the dense image and its offsets go to staging too, not to the caller's device image, and
 // come back instead of the rows (`out` is not used): the offsets, and the image up to the last segment that fits hd->cap
 // in whole - the segments that fit are a prefix of the streams, and none of them ends beyond hd->bound.
 template <class Encode>
 static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
-                     long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr)
+                     long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr, unsigned short *crc = nullptr)
 {
+    {   // (the optional outputs the call will take, checked before anything is allocated or copied)
+        OptOut o = b->opt;
+        if (stats) o.frame_stats = stats;
+        if (crc) o.crc = crc;
+        if (check_opt(o) != 0) return -1;
+    }
     HIPCHK(hipSetDevice(b->device));
     const long long obytes = (long long) b->S * out_stride, sbytes = stats ? (long long) sizeof(int) * b->S * nframes * 2 : 0;
-    if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes)) return -1;
+    const long long cbytes = crc ? (long long) sizeof(unsigned short) * b->S * nframes : 0;
+    if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes) ||
+        dev_grow(b, b->d_crc, b->crc_cap, cbytes)) return -1;
     if (hd && (dev_grow(b, b->d_dense, b->dense_cap, std::max(16LL, std::min(hd->cap, hd->bound))) ||
                (!b->d_dense_off && dev_alloc(b, b->d_dense_off, (long long) sizeof(long long) * (b->S + 1))))) return -1;
     if (drain_first && drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));
     Call c = call_on(b, b->d_out, out_stride, b->d_outbytes);
     if (stats) c.opt.frame_stats = b->d_stats;
+    if (crc) c.opt.crc = b->d_crc;
     if (hd) c.opt.dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
     if (encode(c) != 0 || drain(b) != 0) return -1;
     HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
@@ -302,5 +318,6 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     } else
         HIPCHK(hipMemcpy(out, b->d_out, (size_t) obytes, hipMemcpyDeviceToHost));
     if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, (size_t) sbytes, hipMemcpyDeviceToHost));
+    if (crc) HIPCHK(hipMemcpy(crc, b->d_crc, (size_t) cbytes, hipMemcpyDeviceToHost));
     return 0;
 }

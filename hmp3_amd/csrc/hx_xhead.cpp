@@ -30,6 +30,17 @@ unsigned short crc_step(unsigned short crc, unsigned char d)
     return (unsigned short) ((crc >> 8) ^ x);
 }
 
+// a * b mod P in the register's bit order (bit 15 = x^0): the CRC register after a message M from seed 0 is M(x) x^16 mod P
+unsigned short crc_mulmod(unsigned short a, unsigned short b)
+{
+    unsigned short r = 0;
+    for (int i = 0; i < 16; i++) {
+        if (a & (0x8000 >> i)) r ^= b;
+        b = (b & 1) ? (unsigned short) ((b >> 1) ^ 0xA001) : (unsigned short) (b >> 1);     // times x
+    }
+    return r;
+}
+
 }  // namespace
 
 struct hx_xing {
@@ -49,6 +60,19 @@ extern "C" unsigned short hx_xing_update_crc(unsigned short crc, const unsigned 
 {
     for (int i = 0; i < len; i++) crc = crc_step(crc, data[i]);
     return crc;
+}
+
+// CRC(0, A ++ B) = CRC(0, A) x^(8 |B|) mod P ^ CRC(0, B), with x^(8 n) by square-and-multiply on x^8.  A negative len_b is
+// no length: crc_a comes back unchanged.
+extern "C" unsigned short hx_xing_crc_combine(unsigned short crc_a, unsigned short crc_b, long long len_b)
+{
+    if (len_b < 0) return crc_a;
+    unsigned short p = 0x8000, sq = 0x0080;     // 1, x^8
+    for (unsigned long long n = (unsigned long long) len_b; n; n >>= 1) {
+        if (n & 1) p = crc_mulmod(p, sq);
+        sq = crc_mulmod(sq, sq);
+    }
+    return (unsigned short) (crc_mulmod(crc_a, p) ^ crc_b);
 }
 
 extern "C" int hx_xing_bitrate_index(int mpeg1, int kbps)

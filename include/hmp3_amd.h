@@ -190,6 +190,32 @@ void hx_batch_frame_stats_buffer(hx_batch *b, int *d_stats);
 /* fp32 host call that also returns those counters to a host array stats[nstreams][nframes][2] */
 int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
                                    long long out_stride, int *out_bytes, int *stats);
+/* ---- MusicCRC: the CRC-16 of a call's bitstreams, per stream and input frame (no reference equivalent; the value is
+   xhead.c's XingHeaderUpdateCRC) ----
+   The Xing / Info / LAME tag carries a CRC over every audio byte of the file.  A call's CRC output is stateless - the CRC
+   of THIS call's bytes from seed 0 - and the host joins calls with hx_xing_crc_combine: no CRC state in the stream-state
+   blob (its size and format are unchanged), no ordering question between pipelined submits, no special case for
+   hx_batch_reset_stream.
+   d_crc [nstreams][nframes] unsigned short.  With e[f] = the bytes of row i that the stream had emitted in THIS call
+   after input frame f (e[nframes-1] = out_bytes[i]; e[f] = out_bytes[i] - (stats[nframes-1][1] - stats[f][1]) in
+   unsigned arithmetic), d_crc[i][f] = hx_xing_update_crc(0, row i, e[f]); e[f] = 0 gives 0.  NULL = off (nothing is
+   launched for it).  d_crc must be 2-byte aligned (else -1).
+   Applies to the calls that follow; a call writes the buffer in force when it is made - a submit too: the CRC kernel
+   travels with its deferred packing, d_crc (and the frame counters it reads) must stay valid until the hx_batch_wait
+   behind the submit, and consecutive submits take different buffers (two in turn, like d_out).
+   A CRC call needs a frame-counter buffer (hx_batch_frame_stats_buffer) in force, because e[f] comes from it: a call
+   with d_crc set and no frame counters is refused (-1, hx_last_error) before anything runs, and the batch stays usable.
+   The rows, out_bytes, packets, counters and the dense image are written exactly as without it, by every kind of batch
+   (MPEG-1 and MPEG-2, both builds of the rate-loop kernel, the first-generation allocator, converting batches through
+   hx_batch_encode_src_device).
+   Not covered: hx_batch_encode_src_host and hx_multi_encode_src_host have no CRC argument (a CRC buffer set on a
+   converting batch is written by them like any other optional output), and the per-frame hx_enc_* calls keep the host
+   function hx_xing_update_crc. */
+int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc);
+/* fp32 host call that returns the counters and the CRCs to host arrays stats[nstreams][nframes][2] and
+   crc[nstreams][nframes]; both are required */
+int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride,
+                                 int *out_bytes, int *stats, unsigned short *crc);
 /* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
    The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
    gathers them on the GPU, behind its packing, into one image.  With nb[i] = out_bytes[i]:
@@ -318,6 +344,9 @@ long long hx_multi_out_stride(const hx_multi *m, int nframes);
 int hx_multi_encode_s16_host(hx_multi *m, const int16_t *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes);
 int hx_multi_encode_f32_host(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes);
 int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats);
+/* hx_batch_encode_f32_host_crc over all streams: stats [nstreams][nframes][2] and crc [nstreams][nframes], both required */
+int hx_multi_encode_f32_host_crc(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats,
+                                 unsigned short *crc);
 int hx_multi_status(hx_multi *m);
 /* converting batches (hx_batch_create_src) in the same blocks: in [nstreams][in_stride], frame_off [nstreams][nframes] or NULL,
    in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
@@ -368,6 +397,10 @@ int hx_xing_update_info(hx_xing *x, unsigned frames, int bs_bytes, int vbr_scale
                         unsigned in_samplerate, unsigned out_samplerate, unsigned short musiccrc);
 /* xhead.c:223 XingHeaderUpdateCRC (MusicCRC), xhead.c:236 XingHeaderBitrateIndex */
 unsigned short hx_xing_update_crc(unsigned short crc, const unsigned char *data, int len);
+/* host only: the CRC of A ++ B from crc_a = CRC(0, A), crc_b = CRC(0, B) and len_b = |B| >= 0, in O(log len_b):
+   CRC(0, A ++ B) = crc_a * x^(8 len_b) mod P ^ crc_b (reflected CRC-16, polynomial 0xA001, bit 15 = x^0).  len_b = 0
+   returns crc_a ^ crc_b (crc_b of an empty B is 0); a negative len_b is no length and returns crc_a unchanged. */
+unsigned short hx_xing_crc_combine(unsigned short crc_a, unsigned short crc_b, long long len_b);
 int hx_xing_bitrate_index(int mpeg1, int kbps);
 
 #ifdef __cplusplus
