@@ -450,34 +450,32 @@ __device__ __forceinline__ LaneRun lane_run(const AllocLds &L)
     return q;
 }
 
-__device__ __forceinline__ void sweep_load(const AllocLds &L, SweepRegs &R, const LaneRun &q, int W, int ch)
+// (No guard on the class's run width inside the unrolled loops here and in sweep_run: W is a run-time value, a guard
+// on it splits the loop into one basic block per pair, and each block then waits for its own LDS reads - four or five
+// round trips one after the other where one does.  All RUNW_MAX / 2 pairs are processed instead: a pair past the
+// lane's run - and so any pair past W - is zeros, and its terms are the +0 the tree sum adds anyway.  The host
+// promises start + W <= 576 for the class's own W only, so the address of a later pair is clamped into the array.)
+__device__ __forceinline__ void sweep_load(const AllocLds &L, SweepRegs &R, const LaneRun &q, int ch)
 {
 #pragma unroll
     for (int k = 0; k < RUNW_MAX; k += 2) {
-        float2 a = make_float2(0.0f, 0.0f), b = make_float2(0.0f, 0.0f);
-        if (k < W) {
-            // (a run never ends inside a pair; a read past the run stays inside the LDS block and is dropped)
-            a = *reinterpret_cast<const float2 *>(&L.x34[ch][q.start + k]);
-            b = *reinterpret_cast<const float2 *>(&L.xr[ch][q.start + k]);
-            if (k >= q.cnt) { a = make_float2(0.0f, 0.0f); b = a; }
-        }
+        // (a run never ends inside a pair; what is read past the run is dropped)
+        const int j = min(q.start + k, 576 - 2);
+        float2 a = *reinterpret_cast<const float2 *>(&L.x34[ch][j]);
+        float2 b = *reinterpret_cast<const float2 *>(&L.xr[ch][j]);
+        if (k >= q.cnt) { a = make_float2(0.0f, 0.0f); b = a; }
         R.x34[k] = a.x; R.x34[k + 1] = a.y; R.xr[k] = b.x; R.xr[k + 1] = b.y;
     }
 }
 
 // The lane's share of a band's noise: terms of its run for the band's published gain pair, added up (tree of pairs).
-__device__ __forceinline__ float sweep_run(const AllocLds &L, const SweepRegs &R, const LaneRun &q, int W, int ch)
+// One basic block: the table reads of all ten lines are in flight together.
+__device__ __forceinline__ float sweep_run(const AllocLds &L, const SweepRegs &R, const LaneRun &q, int ch)
 {
     const float2 gp = L.gpair[ch][q.band];
     float t[RUNW_MAX];
 #pragma unroll
-    for (int k = 0; k < RUNW_MAX; k += 2) {
-        t[k] = t[k + 1] = 0.0f;
-        if (k < W) {
-            t[k] = noise_term_fast(L, gp.x, gp.y, R.x34[k], R.xr[k]);
-            t[k + 1] = noise_term_fast(L, gp.x, gp.y, R.x34[k + 1], R.xr[k + 1]);
-        }
-    }
+    for (int k = 0; k < RUNW_MAX; k++) t[k] = noise_term_fast(L, gp.x, gp.y, R.x34[k], R.xr[k]);
     return (((t[0] + t[1]) + (t[2] + t[3])) + ((t[4] + t[5]) + (t[6] + t[7]))) + (t[8] + t[9]);
 }
 
@@ -560,7 +558,7 @@ __device__ __forceinline__ int noise_sweep(AllocLds &L, const SweepRegs &R, cons
     const int anyslow = __any(bslow) ? 1 : 0;
     float part;
     if (__builtin_expect(anyslow, 0)) part = sweep_run_stored(L, ch, W, 1);
-    else part = sweep_run(L, R, q, W, ch);
+    else part = sweep_run(L, R, q, ch);
     PROF_ACC(HX_PROF_SWEEP_LINES);
     // the band's total arrives in its last lane; the band lane fetches it and certifies the bucket
     float sxx = hx_lane_read(last4, hx_seg_scan(part, q.d, LANE));
@@ -708,7 +706,7 @@ HX_SEEK_INLINE void seek_actual_ch(AllocLds &L, const AllocPrm *p, int ch)
     SweepRegs R;
     const int W = p->run_w;
     const LaneRun q = lane_run(L);
-    sweep_load(L, R, q, W, ch);
+    sweep_load(L, R, q, ch);
     // The gain pair of a step comes from two tables in LDS.  A walking band's next step is known before the current
     // one is measured (one down or one up), so its pair is read a sweep ahead and the sweep starts without that
     // round trip; the first measurement reads both neighbours.  (Indices are clamped for the reads only: a step
@@ -1075,6 +1073,7 @@ __device__ __forceinline__ void quant_lines(AllocLds &L, const AllocPrm *p, int 
 #if HX_SLIM
     const int nfill = (opt & 2) ? nl : 576;
 #endif
+    const bool tab = (opt & 1) != 0;
     int q[9], b[9];
 #pragma unroll
     for (int k = 0; k < 9; k++) b[k] = BAND_OF_LINE(LANE + 64 * k);
@@ -1082,14 +1081,12 @@ __device__ __forceinline__ void quant_lines(AllocLds &L, const AllocPrm *p, int 
     for (int k = 0; k < 9; k++) {
         const int j = LANE + 64 * k;
         const float igain = L.gig[c][b[k]];
-        if (opt & 1) {
-            float t = igain * L.x34[c][j] + (0.5f - 0.4375f);
-            int iq = (int) t;
-            if (iq > 31) iq = 31;
-            q[k] = (int) (t - L.quant_off[iq < 0 ? 0 : iq]);
-        } else {
-            q[k] = (int) (igain * L.x34[c][j] + (0.5f - 0.0946f));
-        }
+        // opt & 1: rounding offset from the table, else the fixed one.  Written as selects, not as a branch: where opt is a
+        // run-time value (the helper wave's work orders, the out-of-line builds) a branch here puts every line into a block
+        // of its own that waits for its own reads; where it is a literal the unused side folds away, table read included.
+        const float t = igain * L.x34[c][j] + (tab ? (0.5f - 0.4375f) : (0.5f - 0.0946f));
+        const float off = L.quant_off[max(min((int) t, 31), 0)];
+        q[k] = (int) (t - (tab ? off : 0.0f));
     }
 #pragma unroll
     for (int k = 0; k < 9; k++) {

@@ -186,11 +186,13 @@ __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
 }
 
 // ---- rate loop pieces ----
-__device__ HX_RATE int requant_count(AllocLds &L, const AllocPrm *p, int ms, int opt, int hfmode)
+// HF: 1 = the step towards more bits, with the HF handling and the table-offset quantiser (increase_bits); 0 = plain
+// (decrease_bits, limit_bits).  A template parameter, so each copy holds its own quantiser only, with a literal opt.
+template <int HF>
+__device__ HX_RATE int requant_count(AllocLds &L, const AllocPrm *p, int ms)
 {
     HX_LANE_DECL;
-    // hfmode: 0 = none (decrease / limit), 1 = increase-style with HF handling
-    if (hfmode) {
+    if (HF) {
         if (ms) {
             hf_reset_ms(L, 0);
             // (without -HF nothing ever writes the lines of band 21 beyond what the quantiser below rewrites: clearing
@@ -216,7 +218,7 @@ __device__ HX_RATE int requant_count(AllocLds &L, const AllocPrm *p, int ms, int
         return count_bits(L, p, p->nsf3);
     }
     scale_factors(L, p, 0);
-    return quant_count_bits(L, p, opt, 0, p->nsf2);
+    return quant_count_bits(L, p, 0, 0, p->nsf2);
 }
 
 // reference bitallo3.cpp:2569-2722
@@ -231,13 +233,13 @@ __device__ HX_RATE int increase_bits(AllocLds &L, const AllocPrm *p, int bits0, 
     for (int k = 0; k < 10; k++) {
         if (band) { g = max(g - 1, L.gmin[ch][i]); L.gsf[ch][i] = g; }
         HX_WAVE_SYNC();
-        bits = requant_count(L, p, ms, 1, 1);
+        bits = requant_count<1>(L, p, ms);
         if (bits >= thres) break;
     }
     if (bits > L.maxTargetBits) {       // went too far: step back once
         if (band) L.gsf[ch][i] = g + 1;
         HX_WAVE_SYNC();
-        bits = requant_count(L, p, ms, 1, 1);
+        bits = requant_count<1>(L, p, ms);
     }
     return bits;
 }
@@ -255,7 +257,7 @@ __device__ HX_RATE int decrease_bits(AllocLds &L, const AllocPrm *p, int bits0)
         if (band) L.NT[ch][i] += deltaN;
         HX_WAVE_SYNC();
         seek_actual(L, p);
-        bits = requant_count(L, p, 0, 0, 0);
+        bits = requant_count<0>(L, p, 0);
         if (bits <= L.maxTargetBits) break;
         deltaN = max((f * (bits - L.maxTargetBits)) >> 10, 40);
     }
@@ -274,7 +276,7 @@ __device__ HX_RATE int limit_bits(AllocLds &L, const AllocPrm *p, int part23)
     for (int k = 0; k < 100; k++) {
         if (band && !(part23 && L.huff_bits[ch] <= PART23)) L.gsf[ch][i] = min(127, L.gsf[ch][i] + 1);
         HX_WAVE_SYNC();
-        bits = requant_count(L, p, 0, 0, 0);
+        bits = requant_count<0>(L, p, 0);
         if (part23) { if ((L.huff_bits[0] <= PART23) && (L.huff_bits[1] <= PART23)) break; }
         else if (bits <= L.maxBits) break;
     }
@@ -307,26 +309,26 @@ __device__ __forceinline__ void isf2_lines(AllocLds &L, const AllocPrm *p, int c
 // The lane's share of inverse_sf2's two band sums of channel c - squares of the quantised magnitudes (x^(4/3) of the
 // line's value: a selected band only holds 0, 1 and 2, so the table always covers it) and of the original ones - over its run
 // of lines (hx_dev.h, "certified band sums").
-__device__ __forceinline__ void isf2_run(AllocLds &L, const LaneRun &q, int W, int c, float *sq, float *sx)
+// (all RUNW_MAX / 2 pairs whatever the class's run width, as in sweep_load: a guard on the run-time W would split the
+// loop into blocks that each wait for their own line words and then for their own table reads)
+__device__ __forceinline__ void isf2_run(AllocLds &L, const LaneRun &q, int c, float *sq, float *sx)
 {
     float tq[RUNW_MAX], tx[RUNW_MAX];
 #pragma unroll
     for (int k = 0; k < RUNW_MAX; k += 2) {
-        tq[k] = tq[k + 1] = tx[k] = tx[k + 1] = 0.0f;
-        if (k < W) {
+        const int j = min(q.start + k, 576 - 2);
 #if HX_SLIM
-            const unsigned w = *reinterpret_cast<const unsigned *>(IX(c) + q.start + k);
-            const unsigned i0 = w & 0xFFFFu, i1 = w >> 16;
+        const unsigned w = *reinterpret_cast<const unsigned *>(IX(c) + j);
+        const unsigned i0 = w & 0xFFFFu, i1 = w >> 16;
 #else
-            const int2 w = *reinterpret_cast<const int2 *>(IX(c) + q.start + k);
-            const unsigned i0 = (unsigned) w.x, i1 = (unsigned) w.y;
+        const int2 w = *reinterpret_cast<const int2 *>(IX(c) + j);
+        const unsigned i0 = (unsigned) w.x, i1 = (unsigned) w.y;
 #endif
-            const float2 x = *reinterpret_cast<const float2 *>(&L.xr[c][q.start + k]);
-            const float q0 = L.look_ix43[min(i0, 255u)], q1 = L.look_ix43[min(i1, 255u)];
-            const bool in = k < q.cnt;
-            tq[k] = in ? q0 * q0 : 0.0f; tq[k + 1] = in ? q1 * q1 : 0.0f;
-            tx[k] = in ? x.x * x.x : 0.0f; tx[k + 1] = in ? x.y * x.y : 0.0f;
-        }
+        const float2 x = *reinterpret_cast<const float2 *>(&L.xr[c][j]);
+        const float q0 = L.look_ix43[min(i0, 255u)], q1 = L.look_ix43[min(i1, 255u)];
+        const bool in = k < q.cnt;
+        tq[k] = in ? q0 * q0 : 0.0f; tq[k + 1] = in ? q1 * q1 : 0.0f;
+        tx[k] = in ? x.x * x.x : 0.0f; tx[k + 1] = in ? x.y * x.y : 0.0f;
     }
     *sq = (((tq[0] + tq[1]) + (tq[2] + tq[3])) + ((tq[4] + tq[5]) + (tq[6] + tq[7]))) + (tq[8] + tq[9]);
     *sx = (((tx[0] + tx[1]) + (tx[2] + tx[3])) + ((tx[4] + tx[5]) + (tx[6] + tx[7]))) + (tx[8] + tx[9]);
@@ -347,7 +349,7 @@ __device__ void isf2_ch(AllocLds &L, const AllocPrm *p, int ch)
     const LaneRun q = lane_run(L);
     const int last4 = 4 * (int) L.band_last[ib];
     float sqq, sxx;
-    isf2_run(L, q, W, ch, &sqq, &sxx);
+    isf2_run(L, q, ch, &sqq, &sxx);
     sqq = hx_lane_read(last4, hx_seg_scan(sqq, q.d, LANE));
     sxx = hx_lane_read(last4, hx_seg_scan(sxx, q.d, LANE));
     bool strict = false;
