@@ -51,6 +51,10 @@
 // The gain search (seek_actual_ch) inlined at its three call sites in the 168-register build: as a call it saved and restored 54
 // registers per lane each time.
 #define HX_SEEK_FORCEINLINE HX_SLIM
+// Candidates per band that one pass of big_lucky_noise measures at the most.  The 256-register builds have room for twelve
+// candidates' terms (the term buffer and the quantised lines behind it, dead until the quantiser runs): 93 % of a CBR-128
+// granule's bands' candidate lists fit one pass, with six 19 %.  The low-footprint build's lines live inside the term buffer.
+#define HX_LUCKY_K (HX_SLIM ? 6 : 12)
 #define GMIN_OFFSET 70
 #define PART23 4021
 #define NB 22
@@ -107,8 +111,8 @@ struct alignas(16) Outbox {
 //  * gain tables, the x^(3/4) exponent table: 2^(k/4) and 2^(-3k/16) have period 4 / 16 in the mantissa, the tables are
 //    ldexp of 4 / 16 constants (hx_host.cpp checks that identity on the host's tables before a batch may use this kernel);
 //    the mB-log and log-subtract tables as 16-bit values;
-//  * the short-block allocator's gain-step arrays and the band tables as int16, the scalefactor outputs as bytes, big_lucky's
-//    work list in an array of its own.
+//  * the short-block allocator's gain-step arrays and the band tables as int16, the scalefactor outputs as bytes; big_lucky
+//    measures six candidates per band and pass, not twelve (its terms cannot run on into the lines: they share the buffer).
 #if HX_SLIM
 typedef short ix_t;                     // a quantised line
 typedef short sgs_t;                    // short-block gain steps / scalefactors per band (0 .. 127, flags 0 / -1)
@@ -174,10 +178,8 @@ struct alignas(16) AllocLds {
             float xsxx[2][NB], x34max[2][NB];
             float gig[2][NB];                   // 1 / gain^(3/4) of the band's quantiser step
             alignas(8) float2 gpair[2][NB];     // gain pair (1 / gain^(3/4), gain) of the band's current evaluation step: one read per line
-            int lucky[6][2][13];                // big_lucky_noise: noise of candidate c of band (ch, sfb)
-#if HX_SLIM
-            unsigned short llist[6 * 26 + 4];   // big_lucky_noise: its work list
-#endif
+            int lucky[HX_LUCKY_K][2][13];       // big_lucky_noise: noise of candidate c of band (ch, sfb)
+            unsigned short llist[HX_LUCKY_K * 26 + 4];      // big_lucky_noise: its work list
         };
         struct {    // first-generation allocator (hx_alloc1.inc): psy model output and noise / mask levels per band in dB
             int a_pad[17][2][NB];       // (the long-block arrays up to x34max stay in use)
@@ -223,6 +225,9 @@ struct alignas(16) AllocLds {
     const double *pow43;                // HxGlobalTabs::pow43 (global memory)
     int *big_counter;                   // device counter of line passes that took the double table (tests)
     int nstrict;                        // certified band sums of this stream that fell back to the strict sum (added to big_counter[1] when the stream retires)
+#if !HX_SLIM
+    int nlucky[3];                      // big_lucky_noise of this stream: granules it measured, its passes, granules with a pass of more than six candidates (HX_CNT_LUCKY, when the stream retires)
+#endif
     int cur_s;                          // the stream this workgroup is walking (the helper wave reads it with a fetch order)
     alignas(16) int cmdw[4];            // work order for the helper wave (see HELPER_POST): command + three arguments, one 16-byte read
     alignas(4) unsigned char gflag[HX_SLIM ? 64 : 256];     // block type | stereo decision << 2 of the next granules (frame loop, hx_alloc3.inc)
@@ -230,6 +235,11 @@ struct alignas(16) AllocLds {
     unsigned prof[HX_PROF_WORDS];       // slots HxProf (hx_types.h).  (The profile build holds three workgroups per CU instead of four: per-stream cycles are what it is for)
 #endif
 };
+
+#if !HX_SLIM
+static_assert(offsetof(AllocLds, ix) == offsetof(AllocLds, term) + sizeof(float) * 2 * 576 && sizeof(int) == sizeof(float),
+              "big_lucky_noise's terms run on from the term buffer into the quantised lines: 2304 words in one piece");
+#endif
 
 // Layout-dependent accessors (see HX_SLIM above)
 #if HX_SLIM
@@ -978,9 +988,15 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
     const int ch = LANE >> 5, i = LANE & 31;
     const int m = min(13, p->nsf[ch]);
     const int nl = L.startBand[13];                         // lines of sfb 0..12
-    const int K = min(6, 1152 / (2 * nl));
+    // K: what the terms [K][2][nl] have room for.  The 256-register builds let them run on from the term buffer into the
+    // quantised lines behind it (2304 words: K = 12 at 44.1 / 48 kHz, 11 at 32 kHz, 8 .. 12 with the MPEG-2 band tables): the
+    // lines are not live before do_quant, and what a pass leaves past the coded range is wiped below.
+    const int K = min(HX_LUCKY_K, (HX_SLIM ? 1152 : 2304) / (2 * nl));
     float *tf = &L.term[0][0];                               // [K][2][nl]
     int mode = 0, s = 0, s0 = 0, g0 = 0, GG = 0, sdelta = 2, smin = 0, nt = 0;
+#if !HX_SLIM
+    int npass = 0, reach = 0;                                // passes of this granule, the most candidates one of them held
+#endif
     if (i < m && L.active[ch][i] && (L.gsf[ch][i] < (L.gzero[ch][i] - 5))) {
         sdelta = 2 * (1 + L.scale[ch]);
         GG = L.G[ch];
@@ -1004,16 +1020,15 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         }
         if (i < NB) { L.geval[ch][i] = (mode == 1) ? GG - s : -1; L.tmpn[ch][i] = nc; }
         // work list of the sums: one entry (c, ch, sfb) per candidate, compacted over the band lanes
-#if HX_SLIM
         unsigned short *list = L.llist;
-#else
-        int *list = IX(0);                            // ix is not live before do_quant
-#endif
         const int incl = hx_wave_scan(nc), total = __builtin_amdgcn_readlane(incl, 63);
 #pragma unroll
-        for (int c = 0; c < 6; c++) if (c < nc) list[incl - nc + c] = (c << 8) | (ch << 7) | i;
+        for (int c = 0; c < HX_LUCKY_K; c++) if (c < nc) list[incl - nc + c] = (c << 8) | (ch << 7) | i;
         HX_WAVE_SYNC();
         const int ncmax = hx_wave_max(nc);
+#if !HX_SLIM
+        npass++; reach = max(reach, ncmax);
+#endif
         const bool bslow = mode == 1 && noise_band_needs_pow(LK_IGAIN(GG - s), L.x34max[ch][i]);
         PROF_ACC(HX_PROF_LUCKY_SETUP);
         // slots of 64 flattened lines: 3 or 4 (MPEG-2 band tables: 5), shared between the two waves
@@ -1033,14 +1048,20 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         HX_WAVE_SYNC();
         PROF_ACC(HX_PROF_LUCKY_SUMS);
         {   // replay the reference's scan: the last candidate that meets the target wins
-            int nz[6];
-#pragma unroll
-            for (int c = 0; c < 6; c++) nz[c] = L.lucky[c][ch][min(i, 12)];
+            // (six results at a time; the second six only in a pass that has them: twelve at once are six more registers)
             int best = 0;
             bool hit = false;
 #pragma unroll
-            for (int c = 0; c < 6; c++)
-                if (c < nc && nz[c] <= nt) { best = nz[c]; smin = s - c * sdelta; hit = true; }
+            for (int h = 0; h < HX_LUCKY_K; h += 6) {
+                if (h == 0 || ncmax > h) {
+                    int nz[6];
+#pragma unroll
+                    for (int c = 0; c < 6; c++) nz[c] = L.lucky[h + c][ch][min(i, 12)];
+#pragma unroll
+                    for (int c = 0; c < 6; c++)
+                        if (h + c < nc && nz[c] <= nt) { best = nz[c]; smin = s - (h + c) * sdelta; hit = true; }
+                }
+            }
             if (hit) L.Noise[ch][i] = best;
             if (mode == 1) {
                 s -= nc * sdelta;
@@ -1054,11 +1075,18 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         L.sf[ch][i] = smin;
         L.gsf[ch][i] = max(GG - smin, 0);
     }
-    // The work list lived in channel 0's line buffer (at most 6 x 26 entries).  The quantiser rewrites the coded lines
-    // only: with a very low subband limit (E_CONTROL.nsb_limit = 4 at 48 kHz: 72 lines) the list's tail would stay behind as lines
-    // (found by the round-3 sweep with nsb_limit in the draw).  Lines past the coded range are zero by contract.
-    // (the low-footprint layout keeps the list elsewhere, and its quantiser writes every line)
-    if (!HX_SLIM) { for (int j = p->nbmax[0] + LANE; j < 6 * 26; j += 64) IX(0)[j] = 0; }
+#if !HX_SLIM
+    // A pass of more than 1152 / (2 nl) candidates wrote terms into the line buffers.  The quantiser rewrites the coded lines
+    // only, and lines past the coded range are zero by contract (the bit count's last quadruples and -HF's band 21 rely on it;
+    // with a very low subband limit - E_CONTROL.nsb_limit = 4 at 48 kHz: 72 lines - almost all of a channel is past it): they
+    // are zero again here, as far as the widest pass reached.  (the low-footprint layout's quantiser writes every line)
+    if (reach * 2 * nl > 1152) {
+        const int end = reach * 2 * nl - 1152;      // words of ix[2][576], flat, that held terms
+        for (int j = p->nbmax[0] + LANE; j < min(end, 576); j += 64) IX(0)[j] = 0;
+        for (int j = p->nbmax[1] + LANE; j < end - 576; j += 64) IX(1)[j] = 0;
+    }
+    if (npass && LANE == 0) { L.nlucky[0] += 1; L.nlucky[1] += npass; L.nlucky[2] += (reach > 6); }
+#endif
     HX_WAVE_SYNC();
 }
 

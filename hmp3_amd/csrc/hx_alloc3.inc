@@ -378,6 +378,9 @@ __device__ __forceinline__ void stage_stream(const AllocArgs &a, AllocLds &L, co
     }
     if (LANE < 42) L.sf_save[LANE / 21][LANE % 21] = ss->sf_save[LANE / 21][LANE % 21];
     if (LANE == 0) { L.pow43 = gt->pow43; L.big_counter = COLD(done_counter) + HX_CNT_BIG_SWEEPS; L.nstrict = 0; }
+#if !HX_SLIM
+    if (LANE < 3) L.nlucky[LANE] = 0;
+#endif
     if (LANE < 4) L.P.head[LANE] = gp->head[LANE];
     if (LANE < 16) L.P.vbr_main_framebytes[LANE] = gp->vbr_main_framebytes[LANE];
     if (LANE < 22) L.P.rnBand_l[LANE] = gp->rnBand_l[LANE];
@@ -801,6 +804,9 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
         COLD(carry_len)[s] = opos - done;
         COLD(dur)[s] = (unsigned) (wall_clock64() - t_start);
         if (L.nstrict) atomicAdd(COLD(done_counter) + HX_CNT_STRICT_SUMS, L.nstrict);
+#if !HX_SLIM
+        if (L.nlucky[0]) for (int k = 0; k < 3; k++) atomicAdd(COLD(done_counter) + HX_CNT_LUCKY + k, L.nlucky[k]);
+#endif
         __threadfence();
         atomicAdd(COLD(done_counter) + HX_CNT_RETIRED, 1);
         // this position's CU is no longer reserved (see "parking" above)
@@ -959,6 +965,9 @@ static_assert(sizeof(AllocLds) <= 26880, "six workgroups of the low-footprint st
 #endif
 HX_K6(k_alloc_slim, 0)
 #elif !HX_LSF
+#ifndef HX_PROFILE
+static_assert(sizeof(AllocLds) <= 40960, "four workgroups of the stream walk must fit a CU's 160 KB of LDS, which is handed out in pieces of 1280 bytes");
+#endif
 HX_K6(k_alloc, 0)
 #else
 // the same stream walk for MPEG-2 LSF batches (16 / 22.05 / 24 kHz)

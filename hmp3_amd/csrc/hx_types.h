@@ -216,9 +216,12 @@ enum HxCounter {
     HX_CNT_CLAIMED = 5,         // positions of the launch order claimed so far in this launch (persistent workgroups)
     HX_CNT_IDLE = 6,            // workgroups of this launch that ran out of work (the last one zeroes this and the claim counter)
     HX_CNT_PARK = 8,            // [HX_CNT_PARK ..]: the CU ids of the parking scheme, one per parked position (hx_alloc3.inc)
+    HX_CNT_LUCKY = 72,          // [3] big_lucky_noise of the 256-register stream walks: granules it measured, its passes, granules
+                                // one of whose passes held more than six candidates per band
 };
 #define HX_PARK_MAX 64
-#define HX_CNT_WORDS (HX_CNT_PARK + HX_PARK_MAX)
+#define HX_CNT_WORDS (HX_CNT_LUCKY + 3)
+static_assert(HX_CNT_LUCKY == HX_CNT_PARK + HX_PARK_MAX, "the big_lucky counters follow the parking scheme's words");
 
 // Slots of the stream walk's profile (built with -DHX_PROFILE: AllocArgs::prof, 64 per stream; tools/prof_slots.py reads this
 // table for the profile tools).  Master-wave clock64 ticks booked to a phase, except the counts (HX_PROF_N_*).

@@ -31,6 +31,7 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
     extra = ""
     try:
         extra = " strict %d big %d" % (int(b.debug_read("strict_sums", np.int32, 1)[0]), int(b.debug_read("big_sweeps", np.int32, 1)[0]))
+        extra += " lucky granules/passes/wide %d/%d/%d" % tuple(int(v) for v in b.debug_read("lucky", np.int32, 3))
     except Exception:
         pass
     print("K6 %.3f ms | stream ms: min %.3f mean %.3f p99 %.3f max %.3f | status %d bytes %d%s" % (ms, d.min(), d.mean(), np.percentile(d, 99), d.max(), b.status(), int(nb.sum().item()), extra))
