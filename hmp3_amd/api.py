@@ -171,6 +171,17 @@ def crc_combine(a, b, n):
     return int(lib().hx_xing_crc_combine(int(a), int(b), int(n)))
 
 
+def _frame_counts(setter, handle, n, counts):
+    arr = None
+    if counts is not None:
+        counts = [int(c) for c in counts]
+        if len(counts) != n:
+            raise ValueError("frame counts: %d values for %d streams" % (len(counts), n))
+        arr = (C.c_int * n)(*counts)
+    if setter(handle, arr) != 0:
+        raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
+
+
 class Batch:
     """N independent streams on one GPU (hx_batch_*)."""
 
@@ -207,6 +218,11 @@ class Batch:
         frame to (include/hmp3_amd.h, "MusicCRC"; needs a frame_stats_buffer in force); None switches it off"""
         if lib().hx_batch_crc_buffer(self.h, d_crc_ptr) != 0:
             raise RuntimeError("hx_batch_crc_buffer failed: " + last_error())
+
+    def frame_counts(self, counts):
+        """per-stream frame counts of the calls that follow: a sequence of n ints (stream i takes the first counts[i] frames of
+        its row; 0 = it sits the call out), or None = every stream takes the call's nframes (hx_batch_frame_counts)"""
+        _frame_counts(lib().hx_batch_frame_counts, self.h, self.n, counts)
 
     def encode_host(self, pcm, stats=False, crc=False):
         """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, 2] -> list of bytes per stream; with stats (float32
@@ -460,6 +476,10 @@ class Multi:
         if lib().hx_multi_shard(self.h, k, C.byref(d), C.byref(f), C.byref(c)) != 0:
             raise IndexError(k)
         return d.value, f.value, c.value
+
+    def frame_counts(self, counts):
+        """as Batch.frame_counts, over all streams (hx_multi_frame_counts)"""
+        _frame_counts(lib().hx_multi_frame_counts, self.h, self.n, counts)
 
     def encode_host(self, pcm, stats=False, crc=False):
         """as Batch.encode_host, over all streams"""

@@ -435,7 +435,6 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
     const int S = (int) in.size();
     std::vector<HX_E_CONTROL> ctl(S);
     int nch = 0;
-    size_t max_calls = 0;
     for (int i = 0; i < S; i++) {
         HX_E_CONTROL ec = in[i].ec;
         if (in[i].mono_convert) ec.mode = 3;
@@ -449,11 +448,9 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
             return 1;
         }
         in[i].pad(init_bytes_same_rate(in[i]));
-        const size_t calls = ncalls(in[i]);
-        if (calls > max_calls) max_calls = calls;
     }
-    const int CH = 96;                                  // frames per batched call
-    const size_t total = max_calls + 32;                // room for the drain frames (a reservoir never spans that many)
+    const int CH = 96;                                  // frames per batched call at most
+    const size_t DRAIN = 32;                            // room for a file's drain frames (a reservoir never spans that many)
     // the files spread over the node's GPUs in contiguous blocks (-Gn limits the count), one host thread per device
     hx_multi *b = hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
     if (!b) { fprintf(stderr, "\n ENCODER INIT FAIL: %s\n", hx_last_error()); return 1; }
@@ -467,39 +464,53 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
     // the MusicCRC per file: every call returns the CRC of its own bytes up to each input frame (k_crc, on the GPU), and the
     // file's is those joined by hx_xing_crc_combine - whole calls, then the call in which the file's drain ends up to there
     std::vector<unsigned short> crc((size_t) S * CH), file_crc(S, 0);
-    std::vector<char> crc_done(S, 0);
+    std::vector<char> done(S, 0);                       // the file's drain has ended: it takes no more frames
     std::vector<std::vector<unsigned char>> stream(S);
-    std::vector<std::vector<unsigned>> fr(S), by(S);    // per input frame: frames / bytes out so far
-    for (size_t c0 = 0; c0 < total; c0 += CH) {
+    std::vector<std::vector<unsigned>> fr(S), by(S);    // per frame fed to the file's stream: frames / bytes out so far
+    // Every call gives each file the frames it still needs (hx_multi_frame_counts): its input frames, then silence up to the
+    // frame at which its drain ends; a finished file takes 0 and costs nothing, and the loop ends with the last file, not
+    // DRAIN frames behind the longest one for all.  The call is as long as its largest count.
+    std::vector<int> cnt(S);
+    for (;;) {
+        int nf = 0;
         for (int i = 0; i < S; i++) {
-            const size_t calls = ncalls(in[i]);
-            for (int k = 0; k < CH; k++) {
+            const size_t fed = fr[i].size(), room = ncalls(in[i]) + DRAIN;
+            cnt[i] = (done[i] || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
+            nf = std::max(nf, cnt[i]);
+        }
+        if (nf == 0) break;
+        for (int i = 0; i < S; i++) {
+            const size_t calls = ncalls(in[i]), p0 = fr[i].size();
+            for (int k = 0; k < cnt[i]; k++) {
                 // past the end the single-file loop feeds frames of zero BYTES: silence, except for
                 // 8-bit unsigned input where a zero byte is full-scale negative
-                if (c0 + k < calls) frame_to_float(in[i], in[i].data.data() + (c0 + k) * in[i].frame_in, tmp.data());
+                if (p0 + k < calls) frame_to_float(in[i], in[i].data.data() + (p0 + k) * in[i].frame_in, tmp.data());
                 else frame_to_float(in[i], zero_frame.data(), tmp.data());
-                memcpy(&pcm[((size_t) i * CH + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
+                memcpy(&pcm[((size_t) i * nf + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
             }
         }
-        if (hx_multi_encode_f32_host_crc(b, pcm.data(), CH, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0) {
+        if (hx_multi_frame_counts(b, cnt.data()) != 0 ||
+            hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
             return 1;
         }
         for (int i = 0; i < S; i++) {
+            const int n = cnt[i];
+            if (n == 0) continue;
+            const size_t p0 = fr[i].size();
             stream[i].insert(stream[i].end(), out.begin() + (size_t) i * stride, out.begin() + (size_t) i * stride + nb[i]);
-            for (int k = 0; k < CH; k++) { fr[i].push_back((unsigned) stats[((size_t) i * CH + k) * 2]); by[i].push_back((unsigned) stats[((size_t) i * CH + k) * 2 + 1]); }
-            if (crc_done[i]) continue;
-            // the last input frame the file uses (the per-file loop below: u - 1), if it lies in this call
+            for (int k = 0; k < n; k++) { fr[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2]); by[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2 + 1]); }
+            // the last frame the file uses (the per-file loop below: u - 1), if it lies in this call
             const size_t calls = ncalls(in[i]), expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);
-            int k = c0 + CH >= calls ? (int) (calls - 1 > c0 ? calls - 1 - c0 : 0) : CH;
-            while (k < CH && fr[i][c0 + k] < expected) k++;
-            if (k < CH) {
-                const unsigned e = (unsigned) nb[i] - (by[i][c0 + CH - 1] - by[i][c0 + k]);     // this call's bytes up to there
-                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * CH + k], (long long) e);
-                crc_done[i] = 1;
+            int k = p0 + n >= calls ? (int) (calls > p0 + 1 ? calls - 1 - p0 : 0) : n;
+            while (k < n && fr[i][p0 + k] < expected) k++;
+            if (k < n) {
+                const unsigned e = (unsigned) nb[i] - (by[i][p0 + n - 1] - by[i][p0 + k]);      // this call's bytes up to there
+                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * nf + k], (long long) e);
+                done[i] = 1;
             } else
-                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * CH + CH - 1], nb[i]);
+                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * nf + n - 1], nb[i]);
         }
     }
     if (hx_multi_status(b) != 0) fprintf(stderr, "\n WARNING: kernel status %d\n", hx_multi_status(b));

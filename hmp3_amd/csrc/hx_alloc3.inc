@@ -145,15 +145,15 @@ __device__ __forceinline__ void outbox_store(AllocLds &L, const AllocArgs &a, in
         Outbox &ob = L.ob[g & 1];
         if (LSF) build_side_lsf(L, &L.P, g & 1, ob.part, ob.mdb);
         else build_side(L, &L.P, ob.sidew, ob.gr, ob.scfsi, ob.mdb);
-        const int nfr = LSF ? a.NG : a.NG / 2;
+        const int fpc = LSF ? a.NG : a.NG / 2;      // frame records per stream: the stride
         unsigned char *o = a.out + (long long) s * a.out_stride + r.opos;
         const int k = max(LANE - 4, 0);
         const unsigned byte = (LANE < 4) ? ob.head[LANE] : ((ob.sidew[min(k >> 2, 9)] >> (24 - 8 * (k & 3))) & 255);
         if (LANE < 4 + L.P.side_bytes) o[LANE] = (unsigned char) byte;
         if (LANE == 0) {
-            hx_u4 *fd = reinterpret_cast<hx_u4 *>(&a.frm[(long long) s * nfr + r.frm_index]);
+            hx_u4 *fd = reinterpret_cast<hx_u4 *>(&a.frm[(long long) s * fpc + r.frm_index]);
             fd[0] = r.f0; fd[1] = r.f1; fd[2] = r.f2; fd[3] = r.f3;
-            *reinterpret_cast<hx_u2 *>(&a.slots[(long long) s * (nfr + HX_SLOTS_EXTRA) + r.slot_index]) = r.slot;
+            *reinterpret_cast<hx_u2 *>(&a.slots[(long long) s * (fpc + HX_SLOTS_EXTRA) + r.slot_index]) = r.slot;
         }
     }
 }
@@ -299,7 +299,8 @@ __device__ __forceinline__ void helper_serve(const AllocArgs &a, AllocLds &L)
                 granule_fetch(L, a, (long long) s * a.NG + order.y);
                 nbt = a.bt[(long long) s * a.NG + order.y]; nms = a.msflag[(long long) s * a.NG + order.y];
             }
-            const int gl = order.z, gf = (gl >= 0) ? gl - 1 : ((order.y < 0) ? a.NG - 1 : -1);
+            // (the order behind the stream's last granule - nothing to fetch, no lines - carries that granule's number in word 3)
+            const int gl = order.z, gf = (gl >= 0) ? gl - 1 : ((order.y < 0) ? order.w : -1);
             // (defined on every path: left undefined where nothing is gathered, the compiler carried the previous order's
             // 38 registers around the helper's loop and saved them over every call in it)
             LinesRegs lr0 = {}, lr1 = {};
@@ -520,8 +521,9 @@ __device__ __forceinline__ FrameBudget frame_budget(AllocLds &L, int P_vbr, int 
 
 // One granule: its operands joined, its allocation, the next granule's fetch order, its segments sized and handed over (the
 // outbox of g & 1).  pos: the frame's main-data bits so far; b: what is left of the frame's budget.
+// NGs: the stream's granules of this call, the bound of the look-ahead fetch (a.NG is the stride of the granule arrays).
 template <int LSF>
-__device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, const HxParams *gp, int s, int g, int igr, int bt, int btp,
+__device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, const HxParams *gp, int s, int g, int NGs, int igr, int bt, int btp,
                                               int ms, int shortblock_frame, int nchan, int dual, int P_vbr, FrameBudget &b, int &pos PROF_CLOCK)
 {
     HX_LANE_DECL;
@@ -558,7 +560,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
     if (LANE < 2) { L.gr[igr][LANE].block_type = bt; }
     HX_WAVE_SYNC();
     PROF_ACC(HX_PROF_GR_PRE);
-    if (bt != 2) fetch_posted = bitallo_long(L, p, igr, bt, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, bin, g, (g + 1 < NG) ? g + 1 : -1);
+    if (bt != 2) fetch_posted = bitallo_long(L, p, igr, bt, b.ba_min, b.TargetBits, b.ba_max, b.bit_pool, ms, bin, g, (g + 1 < NGs) ? g + 1 : -1);
     else {      // CBitAllo3::BitAllo, block_type 2 branch (reference bitallo3.cpp:496-547)
         const int P_imnr = RFL(p->initialMNR);
         int MNR0;
@@ -580,7 +582,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
     // the start of the next granule (or behind the frame loop)
     if (!HX_A1 && !fetch_posted) {
         if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
-        HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
+        HELPER_POST(HCMD_FETCH, (g + 1 < NGs) ? g + 1 : -1);
     }
     PROF_ACC(HX_PROF_FETCH_POST);
     {   // The bits are written by k_pack; here the granule's segments are sized and handed over: a channel's
@@ -618,7 +620,7 @@ __device__ __forceinline__ void granule_alloc(const AllocArgs &a, AllocLds &L, c
     }
     if (HX_A1) {    // (its line arrays stay live until the last channel is allocated)
         if (LANE == 0) { L.cmdw[2] = g; L.cmdw[3] = bt | ((L.gr[igr][0].aux_not_null != 0) << 8) | ((L.gr[igr][1].aux_not_null != 0) << 9); }
-        HELPER_POST(HCMD_FETCH, (g + 1 < NG) ? g + 1 : -1);
+        HELPER_POST(HCMD_FETCH, (g + 1 < NGs) ? g + 1 : -1);
     }
     if (!dual) {
         b.ba_min += b.inc_min;
@@ -758,13 +760,48 @@ __device__ __forceinline__ void place_frame(const AllocArgs &a, AllocLds &L, int
     HX_WAVE_SYNC();
 }
 
+// The counters and packet sizes of the frames behind the stream's count (hx_batch_frame_counts), frames nf .. F - 1 of its
+// row: the counters repeat the stream's as they stand at the end of its call, the packets there are empty.
+__device__ __forceinline__ void tail_fill(int s, int nf, int F, unsigned tot_frames_out, unsigned tot_bytes_out)
+{
+    HX_LANE_DECL;
+    if (nf >= F) return;
+    int *fs = COLD(frame_stats), *pb = COLD(packet) ? COLD(packet_bytes) : nullptr;
+    for (int i = 2 * nf + LANE; i < 2 * F; i += 64) {
+        if (fs) fs[(long long) s * F * 2 + i] = (int) ((i & 1) ? tot_bytes_out : tot_frames_out);
+        if (pb) pb[(long long) s * F * 2 + i] = 0;
+    }
+}
+
+// A launch's bookkeeping at a stream's end: its duration for the next launch's order, the retired-counter, and its position's
+// CU no longer reserved (see "parking" in alloc_stream) - for every stream of the launch, one that took no frame included.
+__device__ __forceinline__ void stream_retire(int s, int idx, long long t_start)
+{
+    COLD(dur)[s] = (unsigned) (wall_clock64() - t_start);
+    __threadfence();
+    atomicAdd(COLD(done_counter) + HX_CNT_RETIRED, 1);
+    if (idx < (COLD(park_k) & 0xFFFF)) __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// A stream that takes no frame of this call (count 0): its state, its pending frames' images and its row stay as they are;
+// the call's byte counts are zero, its counters those it came with.  The master wave alone, no order to the helper.
+__device__ __forceinline__ void stream_idle(int s, int idx, int F, const HxStream *ss, long long t_start)
+{
+    HX_LANE_DECL;
+    tail_fill(s, 0, F, ss->tot_frames_out, ss->tot_bytes_out);
+    if (LANE == 0) {
+        COLD(pre_len)[s] = 0; COLD(carry_len)[s] = 0; COLD(out_bytes)[s] = 0;
+        stream_retire(s, idx, t_start);
+    }
+}
+
 // The end of the stream's call: the last granule's lines and outbox out, the frames that are not complete yet and the carried
-// state into the stream record, the counters.
-__device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L, int s, int idx, HxStream *ss, long long t_start)
+// state into the stream record, the counters.  NGs: the stream's granules of this call.
+__device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L, int s, int idx, int NGs, HxStream *ss, long long t_start)
 {
     HX_LANE_DECL;
     HELPER_JOIN();          // the last granule's lines are out
-    if (LANE == 0) L.cmdw[2] = -1;
+    if (LANE == 0) { L.cmdw[2] = -1; L.cmdw[3] = NGs - 1; }
     HELPER_POST(HCMD_FETCH, -1);        // its outbox
     HELPER_JOIN();
     // ---- frames that are not complete yet travel to the next call in the stream state ----
@@ -802,16 +839,13 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
             ss->gr_subblock_gain[g][c][k] = L.gr[g][c].subblock_gain[k];
         COLD(out_bytes)[s] = done;
         COLD(carry_len)[s] = opos - done;
-        COLD(dur)[s] = (unsigned) (wall_clock64() - t_start);
         if (L.nstrict) atomicAdd(COLD(done_counter) + HX_CNT_STRICT_SUMS, L.nstrict);
 #if !HX_SLIM
         if (L.nlucky[0]) for (int k = 0; k < 3; k++) atomicAdd(COLD(done_counter) + HX_CNT_LUCKY + k, L.nlucky[k]);
 #endif
-        __threadfence();
-        atomicAdd(COLD(done_counter) + HX_CNT_RETIRED, 1);
-        // this position's CU is no longer reserved (see "parking" above)
-        if (idx < (COLD(park_k) & 0xFFFF)) __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        stream_retire(s, idx, t_start);
     }
+    tail_fill(s, NGs / 2, a.NG / 2, L.fs.tot_frames_out, L.fs.tot_bytes_out);
 }
 
 // Out of work: a workgroup that shares its CU with one of the launch's longest streams keeps the slot until that one retires
@@ -888,9 +922,22 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
             __hip_atomic_store((unsigned *) COLD(done_counter) + HX_CNT_PARK + idx, (where & ((COLD(park_k) >> 16) ? 0xFFFFFE00u : 0xFFFFFF00u)) | 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     HxStream *ss = a.st + s;
+    // The frames this stream takes of the call (hx_batch_frame_counts; null: all of them): the bound of the frame loop and of
+    // the look-ahead fetch, while a.NG stays the stride of every [S][NG] array.  A stream that takes none still did all of the
+    // launch's bookkeeping above and retires (stream_idle): the gates, the claim counter's reset, the next launch's order and
+    // the workgroups parked on its CU count on every position of the launch.  It gives the helper wave no order: both waves
+    // go on to the next claim, or to walk_exit, together.
+    const int *nfr = COLD(nfr);
+    const int F = nfr ? __builtin_amdgcn_readfirstlane(nfr[s]) : a.NG / 2;
+    if (F == 0) {
+        stream_idle(s, idx, a.NG / 2, ss, t_start);
+#if HX_PERSIST
+        continue;
+#endif
+    } else {
     const HxParams *gp = a.prm + ss->cls;
     const AllocPrm *p = &L.P;
-    const int NG = a.NG, F = NG / 2;
+    const int NG = a.NG, NGs = 2 * F;
     stage_stream(a, L, ss, gp, a.gt);
     slots_init<LSF>(a, L, s, ss, gp);
 
@@ -926,7 +973,7 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
         int pos = 0;
         for (int igr = LSF ? part : 0; igr < (LSF ? part + 1 : 2); igr++) {
             const int bt = igr ? bt1 : bt0;
-            granule_alloc<LSF>(a, L, gp, s, 2 * f + igr, igr, bt, bt_last, ms, shortblock_frame, nchan, dual, P_vbr, b, pos PROF_PASS);
+            granule_alloc<LSF>(a, L, gp, s, 2 * f + igr, NGs, igr, bt, bt_last, ms, shortblock_frame, nchan, dual, P_vbr, b, pos PROF_PASS);
             bt_last = bt;
         }
         PROF_ACC(HX_PROF_GR_TAIL);
@@ -934,13 +981,14 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
       }
         PROF_ACC(HX_PROF_RETIRE);
     }
-    stream_writeback(a, L, s, idx, ss, t_start);
+    stream_writeback(a, L, s, idx, NGs, ss, t_start);
 #if HX_PERSIST
     // the helper wave is through with this stream (its last stores read the outbox and the stream constants in LDS) before
     // the next stream's tables land there
     HELPER_POST(HCMD_SYNC, 0);
     HELPER_JOIN();
 #endif
+    }
   }
     walk_exit(L);
 }

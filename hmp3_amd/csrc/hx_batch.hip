@@ -84,6 +84,7 @@ extern "C" void hx_batch_destroy(hx_batch *b)
     for (hipEvent_t e : b->events) hipEventDestroy(e);
     for (auto &pr : b->pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
     if (b->h_src_off) hipHostFree(b->h_src_off);
+    if (b->h_nfr) hipHostFree(b->h_nfr);
     delete b;
 }
 
@@ -331,6 +332,35 @@ extern "C" int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc)
     return 0;
 }
 
+// Per-stream frame counts of the calls that follow.  Only the host copy changes here: a call checks it against its nframes
+// (check_args) and uploads it for itself (encode_pass), so what is set later never reaches a call already made.
+// counts_reserve: everything that can fail - whether the batch takes counts at all, and (buffers) at the first use their
+// staging, events and device copies (a never-recorded event counts as done).  Each piece is made once: a call that fails half way leaves what it made to the next one (and
+// to hx_batch_destroy), which makes only the rest.  The calling thread's current device is left as it was.
+int counts_reserve(hx_batch *b, bool buffers)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (b->nsrc) { set_err("a converting batch takes no per-stream frame counts: its converter's schedule is per call"); return -1; }
+    if (!buffers || (b->h_nfr && b->d_nfr && b->ev_nfr[2])) return 0;
+    int dev0 = -1;
+    HIPCHK(hipGetDevice(&dev0));
+    HIPCHK(hipSetDevice(b->device));
+    int rc = 0;
+    if (!b->h_nfr && hipHostMalloc((void **) &b->h_nfr, sizeof(int) * 3 * (size_t) b->S, 0) != hipSuccess) { b->h_nfr = nullptr; set_err("hipHostMalloc failed"); rc = -1; }
+    for (int k = 0; k < 3 && rc == 0; k++)
+        if (!b->ev_nfr[k]) rc = new_event(b, b->ev_nfr[k]);
+    if (rc == 0 && !b->d_nfr) rc = dev_alloc(b, b->d_nfr, (long long) sizeof(int) * 3 * b->S);
+    (void) hipSetDevice(dev0);
+    return rc;
+}
+extern "C" int hx_batch_frame_counts(hx_batch *b, const int *nfr)
+{
+    if (counts_reserve(b, nfr != nullptr) != 0) return -1;
+    if (nfr) b->nfr.assign(nfr, nfr + b->S);
+    else b->nfr.clear();
+    return 0;
+}
+
 extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
 {
     return b ? (long long) b->S * ((hx_batch_out_stride(b, nframes) + 15) & ~15LL) : 0;
@@ -383,6 +413,18 @@ int check_args(const hx_batch *b, const void *in, int nframes, const void *out, 
     if (nframes <= 0 || nframes > b->maxF) { set_err("nframes out of range (1 .. max_frames of hx_batch_create)"); return -1; }
     if (!in || !out || !out_bytes) { set_err("null buffer"); return -1; }
     if (out_stride < hx_batch_out_stride(b, nframes)) { set_err("out_stride is smaller than hx_batch_out_stride(b, nframes)"); return -1; }
+    return check_counts(b, nframes, 0);
+}
+// (hx_batch_frame_counts: a count no kernel could honour never reaches one)
+int check_counts(const hx_batch *b, int nframes, int first)
+{
+    for (size_t i = 0; i < b->nfr.size(); i++)
+        if (b->nfr[i] < 0 || b->nfr[i] > nframes) {
+            char msg[96];
+            snprintf(msg, sizeof(msg), "stream %d: frame count %d out of range (0 .. nframes = %d)", first + (int) i, b->nfr[i], nframes);
+            set_err("%s", msg);
+            return -1;
+        }
     return 0;
 }
 // (k_crc takes every e[f] from the call's frame counters, and the batch keeps no counter buffer of its own for it: two
@@ -412,12 +454,12 @@ static int enqueue_pack(hx_batch *b, const Call &c, int nframes, int set, int ss
     if (solo) {
         LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
                c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, c.out_bytes, w.carry_len, c.rec_frames,
-               (solo == 1) ? c.rec_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED);
+               (solo == 1) ? c.rec_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED, c.nfr);
         return 0;
     }
     LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, w.pre_len);
     LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr);
+           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr, c.nfr);
     LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, c.out_bytes, w.carry_len, c.rec_frames);
     return 0;
 }
@@ -513,6 +555,30 @@ static int pipe_enter(hx_batch *b, Pass &p)
     return 0;
 }
 
+// The call's frame counts to the device: through page-locked staging into copy k of three, on the stream the front end runs
+// on (the kernels of the call follow it there or wait for that stream's events).  The staging copy is free when its previous
+// upload, three calls ago, is done: the host waits for that here, so a call under counts is not made under stream capture
+// and may block behind the call three before it (include/hmp3_amd.h says so).
+// Which copy: a submit takes the one of its set of signs - the packing that reads both is done before that set comes round
+// again (pipe_enter waits for ev_sgn).  A plain call has no set of signs of its own, so plain calls count their own
+// rotation; copy k of a plain call may therefore be the copy of a submit still in flight, and what keeps the upload off
+// that submit's kernels is stream order: the upload goes onto the caller's stream behind order_behind_submits (a plain
+// call after submits) or, for a submit after plain calls, onto the front-end stream behind ev_in, which is behind
+// everything the plain calls put on the caller's stream.
+static int upload_counts(hx_batch *b, Pass &p)
+{
+    if (b->nfr.empty()) return 0;
+    const int k = p.kind == PASS_PLAIN ? (int) (b->nplain++ % 3) : p.sset;
+    const size_t nb = sizeof(int) * (size_t) b->S;
+    int *h = b->h_nfr + (size_t) k * b->S, *d = b->d_nfr + (size_t) k * b->S;
+    HIPCHK(hipEventSynchronize(b->ev_nfr[k]));
+    memcpy(h, b->nfr.data(), nb);
+    HIPCHK(hipMemcpyAsync(d, h, nb, hipMemcpyHostToDevice, p.q));
+    HIPCHK(hipEventRecord(b->ev_nfr[k], p.q));
+    p.call.nfr = d;
+    return 0;
+}
+
 // the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]
 static int launch_front(hx_batch *b, const Pass &p)
 {
@@ -527,22 +593,24 @@ static int launch_front(hx_batch *b, const Pass &p)
     dim3 g1(S, (NG + K1_GPB - 1) / K1_GPB);
     const int SG = 2 * b->maxF + 3;     // subband slots per (stream, channel): fixed layout
     const float *pcmf = b->any_dc ? b->d_pcmf : d_pcm32;       // fp32 samples the polyphase reads, or null for int16
-    if (b->any_dc) LAUNCH(k_dcfilter, dim3((b->nchan * S + 63) / 64), dim3(64), q, d_pcm, d_pcm32, nsamp, b->d_st, b->d_prm, b->d_pcmf, S, b->nchan);
+    // (launch dimensions are those of nframes with or without counts: a unit beyond its stream's count does nothing)
+    const int *nfr = p.call.nfr;
+    if (b->any_dc) LAUNCH(k_dcfilter, dim3((b->nchan * S + 63) / 64), dim3(64), q, d_pcm, d_pcm32, nsamp, b->d_st, b->d_prm, b->d_pcmf, S, b->nchan, nfr);
     // (the carry in slots 0..2 is not written by k_polyphase, so the two may run in either order)
     // (the detector energies of the carried granule are formed by k_polyphase's first tile of a stream, the carries rolled by
     // k_msscan, flags and block types by one kernel - round 6: three launches less per call, which is what a one-stream call
     // is made of)
-    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf);
-    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf);
+    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf, nfr);
+    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf, nfr);
     // (the form of K4 that goes with the stream-walk kernel: hx_spec.hip, spec_granule)
-    if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
-    else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG);
+    if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
+    else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
     // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
     // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
     // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
-    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->lsf, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan);
+    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->lsf, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan, nfr);
     LAUNCH(k_prep, dim3((unsigned) (((long long) S * NG + 3) / 4)), dim3(256), q, f.xr, (b->debug && b->d_xrdbg) ? b->d_xrdbg : (float *) nullptr, b->debug ? f.x34 : (float *) nullptr,
-           b->sgn[p.sset], f.band, b->d_st, b->d_prm, b->d_gt, f.bt, f.msflag, f.etab, f.thr, f.thrprev, NG, (long long) S * NG);
+           b->sgn[p.sset], f.band, b->d_st, b->d_prm, b->d_gt, f.bt, f.msflag, f.etab, f.thr, f.thrprev, NG, (long long) S * NG, nfr);
     return 0;
 }
 
@@ -579,7 +647,7 @@ static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
     const Call &c = p.call;
     a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
     a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = c.out; a.out_bytes = c.out_bytes;
-    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = c.out_stride; a.NG = 2 * p.nframes; a.S = S; a.status = b->d_status; a.prof = b->d_prof;
+    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = c.out_stride; a.NG = 2 * p.nframes; a.S = S; a.nfr = c.nfr; a.status = b->d_status; a.prof = b->d_prof;
     a.packet = c.opt.packet; a.packet_stride = c.opt.packet_stride; a.packet_bytes = c.opt.packet_bytes; a.frame_stats = c.opt.frame_stats;
     a.done_counter = b->d_done;
     a.strict_sums = b->strict_sums;
@@ -672,7 +740,7 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream,
     Pass p = {in, nframes, c, kind, (hipStream_t) stream, (hipStream_t) stream};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
-    if (pipe_enter(b, p) != 0 || launch_front(b, p) != 0) return -1;
+    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || launch_front(b, p) != 0) return -1;
     if (kind != PASS_PLAIN && pipe_front_done(b, p) != 0) return -1;
     if (fill_alloc_args(b, p, a) != 0 || launch_walk(b, p, a) != 0 || place_pack(b, p) != 0) return -1;
     if (!c.recording) reap_timings(b);
@@ -785,7 +853,7 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
     HIPCHK(hipEventRecord(b->ev_hfront[k], b->s_front));
     HIPCHK(hipStreamWaitEvent(b->s_d2h, b->ev_alloc[set], 0));
     HIPCHK(hipMemcpyAsync(out_bytes, b->hs_nb[k], sizeof(int) * b->S, hipMemcpyDeviceToHost, b->s_d2h));
-    if (!img) HIPCHK(hipMemcpyAsync(out, b->hs_out[k], (size_t) obytes, hipMemcpyDeviceToHost, b->s_d2h));
+    if (!img && rows_to_host(b, out, b->hs_out[k], out_stride, b->s_d2h) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_d2h[k], b->s_d2h));     // (a dense call: its image kernels, which ev_alloc covers, are done)
     b->nhost++;
     return poison.ok();

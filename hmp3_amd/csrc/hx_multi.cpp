@@ -185,7 +185,20 @@ extern "C" long long hx_multi_out_stride(const hx_multi *m, int nframes)
     return n;
 }
 
-// Argument checks of the calls over all devices; then fn(k) on one thread per device, bound to the CPUs next to it.
+// hx_batch_frame_counts over all streams: every block's batch takes its streams' part.  All blocks or none: what can fail
+// (a converting batch, the first use's allocations) is settled for every block before one of them is set.
+extern "C" int hx_multi_frame_counts(hx_multi *m, const int *nfr)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    for (hx_batch *b : m->part) if (counts_reserve(b, nfr != nullptr) != 0) return -1;
+    for (size_t k = 0; k < m->part.size(); k++)
+        if (hx_batch_frame_counts(m->part[k], nfr ? nfr + m->first[k] : nullptr) != 0) return -1;     // (cannot fail any more)
+    return 0;
+}
+
+// Argument checks of the calls over all devices, the per-stream frame counts of every block included: a call that one
+// block would refuse for its counts starts on no block, and its message names the stream by the caller's number.
+// Then fn(k) on one thread per device, bound to the CPUs next to it.
 // Returns the first failing block's code, with its message as the caller's hx_last_error.
 template <class Fn>
 static int multi_fanout(hx_multi *m, bool buffers_ok, int nframes, long long out_stride, Fn fn)
@@ -193,6 +206,8 @@ static int multi_fanout(hx_multi *m, bool buffers_ok, int nframes, long long out
     if (!m || !buffers_ok) { set_err("null buffer"); return -1; }
     if (out_stride < hx_multi_out_stride(m, nframes)) { set_err("out_stride is smaller than hx_multi_out_stride(m, nframes)"); return -1; }
     const size_t n = m->part.size();
+    if (nframes <= 0 || nframes > m->part[0]->maxF) { set_err("nframes out of range (1 .. max_frames of hx_multi_create)"); return -1; }     // (one max_frames for all blocks)
+    for (size_t k = 0; k < n; k++) if (check_counts(m->part[k], nframes, m->first[k]) != 0) return -1;
     std::vector<int> rc(n, 0);
     std::vector<std::string> err(n);
     std::vector<std::thread> th;

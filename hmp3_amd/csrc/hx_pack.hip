@@ -191,7 +191,7 @@ __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, c
                                               int *__restrict__ status, int frames_per_stream, int NG, int lsf, long long nframes_total,
                                               int solo, HxStream *__restrict__ st_w, const int *__restrict__ pre_len, const int *__restrict__ out_bytes,
                                               const int *__restrict__ carry_len, unsigned *__restrict__ frames_out,
-                                              unsigned char *__restrict__ host_out, const int *__restrict__ seq_src)
+                                              unsigned char *__restrict__ host_out, const int *__restrict__ seq_src, const int *__restrict__ nfr)
 {
     __shared__ PackLds L;
     const int tid = threadIdx.x, lane = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6);      // (wave-uniform, made provably so)
@@ -214,6 +214,7 @@ __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, c
     }
     for (long long fr = blockIdx.x; fr < nframes_total; fr += gridDim.x) {
         const int s = (int) (fr / frames_per_stream), f = (int) (fr % frames_per_stream);
+        if (nfr && f >= (lsf ? 2 : 1) * nfr[s]) continue;       // beyond the stream's count: no record (the whole workgroup, ahead of its barriers)
         for (int i = tid; i < 640; i += 256) L.bitw[i] = 0;
         if (tid == 0) L.negflag = 0;
         const HxParams *p = prm + __builtin_amdgcn_readfirstlane(st[s].cls);

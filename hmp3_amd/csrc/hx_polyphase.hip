@@ -61,12 +61,17 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
                                                    const HxParams *__restrict__ prm,
                                                    const HxGlobalTabs *__restrict__ gt,
                                                    float *__restrict__ sb, int NG, int SG,
-                                                   const float *__restrict__ pcmf, int nchan, int *__restrict__ eng, int lsf)
+                                                   const float *__restrict__ pcmf, int nchan, int *__restrict__ eng, int lsf,
+                                                   const int *__restrict__ nfr)
 {
     __shared__ __attribute__((aligned(16))) v2f xs[K1_LDS];
     const int s = blockIdx.x, lt = threadIdx.x;
     const int g0 = blockIdx.y * K1_GPB;
-    const int ng = min(K1_GPB, NG - g0);
+    // the stream's granules of this call (hx_batch_frame_counts): the bound; NG stays the stride of eng.  A tile may be cut by
+    // the count or lie beyond it: the workgroup is one stream's, so it leaves as one, ahead of its barrier
+    const int NGs = nfr ? 2 * nfr[s] : NG;
+    const int ng = min(K1_GPB, NGs - g0);
+    if (ng <= 0) return;
     const int count = 480 + 576 * ng;
     const HxStream *ss = st + s;
     const HxParams *p = prm + __builtin_amdgcn_readfirstlane(ss->cls);
@@ -201,7 +206,7 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
             for (int i = 8; i < 28; i++) ENG_TERM(i)
         }
 #undef ENG_TERM
-        if (!(t & 1) && g0 + gl + 1 < NG) {
+        if (!(t & 1) && g0 + gl + 1 < NGs) {
             int *eo = eng + ((long long) (s * 2) * NG + g0 + gl + 1) * 9 + (t >> 1);
             eo[0] = hx_mblog(gt->mblog, sum.x);
             eo[(long long) NG * 9] = hx_mblog(gt->mblog, sum.y);
@@ -243,12 +248,16 @@ __device__ __forceinline__ void attack_metric(const int *hist, const int *eng, i
 __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const HxParams *__restrict__ prm,
                                                 const int *__restrict__ eng, unsigned char *__restrict__ flg,
                                                 int *__restrict__ dbg_metric, unsigned char *__restrict__ bt,
-                                                unsigned char *__restrict__ btprev, int NG, int S, int lsf)
+                                                unsigned char *__restrict__ btprev, int NG, int S, int lsf, const int *__restrict__ nfr)
 {
     __shared__ unsigned char sflg[4][64], sbt[4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int s = blockIdx.x * 4 + wv;
     if (s >= S) return;         // (wave-uniform; nothing below is a workgroup barrier)
+    // the stream's granules of this call: the bound of everything below (NG: the stride of eng, flg, bt).  A stream that takes
+    // no frame keeps its detector history and block-type state as they are.
+    const int NGs = nfr ? __builtin_amdgcn_readfirstlane(2 * nfr[s]) : NG;
+    if (NGs == 0) return;
     HxStream *ss = st + s;
     const int thr = prm[ss->cls].short_block_threshold;
     // sel[prev type * 4 + short now * 2 + short next] = {0, 1, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 0, 1, 2, 2} as nibbles of a constant
@@ -258,9 +267,9 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
     const int *e0 = eng + (long long) (s * 2 + 0) * NG * 9, *e1 = eng + (long long) (s * 2 + 1) * NG * 9;
     // (the hand-overs through sflg / sbt wait for the LDS writes themselves: a different primitive from HX_WAVE_SYNC)
 #define DETECT_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); } while (0)
-    for (int gb = 0; gb < NG; gb += 64) {
+    for (int gb = 0; gb < NGs; gb += 64) {
         const int g = gb + lane;
-        if (g < NG) {
+        if (g < NGs) {
             int a0, a1, b0, b1;
             attack_metric(ss->attack_hist[0], e0, g, &a0, &a1, lsf);
             attack_metric(ss->attack_hist[1], e1, g, &b0, &b1, lsf);
@@ -272,7 +281,7 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
         }
         DETECT_SYNC();
         if (lane == 0) {
-            const int n = min(64, NG - gb);
+            const int n = min(64, NGs - gb);
             for (int k = 0; k < n; k++) {
                 const int f = sflg[wv][k];
                 const int next = prev_next ? (f >> 1) & 1 : f & 1;
@@ -283,7 +292,7 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
             }
         }
         DETECT_SYNC();
-        if (g < NG) bt[(long long) s * NG + g] = sbt[wv][lane];
+        if (g < NGs) bt[(long long) s * NG + g] = sbt[wv][lane];
         __builtin_amdgcn_wave_barrier();
     }
 #undef DETECT_SYNC
@@ -292,7 +301,7 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
     const int c = lane >> 5, j = lane & 31;
     {
         const int *e = c ? e1 : e0;
-        const int a = 9 * NG + j;
+        const int a = 9 * NGs + j;
         keep = (a < 32) ? ss->attack_hist[c][a] : e[a - 32];
     }
     __builtin_amdgcn_wave_barrier();
@@ -305,23 +314,25 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
 // evaluated in the reference's order, so it is sequential per channel: one lane per
 // (stream, channel) walks its samples; streams without the filter are converted to float only.
 __global__ void k_dcfilter(const int16_t *__restrict__ pcm, const float *__restrict__ pcm32, long long nsamp,
-                           HxStream *__restrict__ st, const HxParams *__restrict__ prm, float *__restrict__ pcmf, int S, int nchan)
+                           HxStream *__restrict__ st, const HxParams *__restrict__ prm, float *__restrict__ pcmf, int S, int nchan,
+                           const int *__restrict__ nfr)
 {
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
     if (u >= nchan * S) return;
     const int s = u / nchan, ch = u - s * nchan;
+    const long long nown = nfr ? 1152LL * nfr[s] : nsamp;      // the stream's samples of this call (nsamp: the row stride)
     HxStream *ss = st + s;
     const HxParams *p = prm + ss->cls;
     const int16_t *src = pcm + (long long) s * nsamp * nchan + ch;
     const float *srcf = pcm32 + (long long) s * nsamp * nchan + ch;
     float *dst = pcmf + (long long) s * nsamp * nchan + ch;
     if (!p->filter_dc) {
-        for (long long n = 0; n < nsamp; n++) dst[nchan * n] = pcm32 ? srcf[nchan * n] : (float) src[nchan * n];
+        for (long long n = 0; n < nown; n++) dst[nchan * n] = pcm32 ? srcf[nchan * n] : (float) src[nchan * n];
         return;
     }
     const float alpha = p->filter_alpha;
     float d = ss->dc[ch];
-    for (long long n0 = 0; n0 < nsamp; n0 += 8) {      // nsamp is a multiple of 1152
+    for (long long n0 = 0; n0 < nown; n0 += 8) {       // (a multiple of 1152)
         float x[8];
 #pragma unroll
         for (int k = 0; k < 8; k++) x[k] = pcm32 ? srcf[nchan * (n0 + k)] : (float) src[nchan * (n0 + k)];

@@ -18,7 +18,7 @@ __global__ __launch_bounds__(64 * PREP_GPB) void k_prep(const float *__restrict_
                                              const HxParams *__restrict__ prm, const HxGlobalTabs *__restrict__ gt,
                                              const unsigned char *__restrict__ bt, const unsigned char *__restrict__ msflag,
                                              const float *__restrict__ etab, const float *__restrict__ thr,
-                                             const float *__restrict__ thrprev, int NG, long long nunits)
+                                             const float *__restrict__ thrprev, int NG, long long nunits, const int *__restrict__ nfr)
 {
     // Per wave only the squares that the band lanes add up live in LDS (one pair of channels at a time: L / R, then
     // M / S); magnitudes, x^(3/4) and signs stay in the registers of the lane that owns the lines, from the load
@@ -35,6 +35,7 @@ __global__ __launch_bounds__(64 * PREP_GPB) void k_prep(const float *__restrict_
     const long long unit = (long long) blockIdx.x * PREP_GPB + wv;      // (s, g)
     if (unit >= nunits) return;
     const int g = (int) (unit % NG), s = (int) (unit / NG);
+    if (nfr && g >= 2 * nfr[s]) return;         // beyond the stream's count (behind the barrier: the four waves may be of different streams)
     const int btype = bt[unit];
     if (btype == 2) return;
     // (from here on the wave works alone: LDS hand-overs inside a wave need no workgroup barrier)

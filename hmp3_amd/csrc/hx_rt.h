@@ -28,24 +28,27 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #ifdef __HIPCC__
 // kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
+// nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
+// frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
+// by 2 * nfr[s] granules; NG, nsamp and frames_per_stream stay the strides of the rows.
 __global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
-                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf);
-__global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int nchan);
+                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf, const int *nfr);
+__global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int nchan, const int *nfr);
 __global__ void k_src(SrcArgs a);
 __global__ void k_detect(HxStream *st, const HxParams *prm, const int *eng, unsigned char *flg, int *dbg_metric, unsigned char *bt,
-                         unsigned char *btprev, int NG, int S, int lsf);
+                         unsigned char *btprev, int NG, int S, int lsf, const int *nfr);
 __global__ void k_spec(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
-                       float *xr, float *etab, float *thr, int *msbase, int NG, int SG);
+                       float *xr, float *etab, float *thr, int *msbase, int NG, int SG, const int *nfr);
 __global__ void k_spec_direct(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
-                              float *xr, float *etab, float *thr, int *msbase, int NG, int SG);
+                              float *xr, float *etab, float *thr, int *msbase, int NG, int SG, const int *nfr);
 __global__ void k_msscan(HxStream *st, const HxParams *prm, const int *msbase, const unsigned char *bt, unsigned char *msflag, int *msdec,
-                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int nchan);
+                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int nchan, const int *nfr);
 __global__ void k_prep(const float *xr, float *xmag_dbg, float *x34o, unsigned *sgn, HxBandPrep *band, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt,
-                       const unsigned char *bt, const unsigned char *msflag, const float *etab, const float *thr, const float *thrprev, int NG, long long nunits);
+                       const unsigned char *bt, const unsigned char *msflag, const float *etab, const float *thr, const float *thrprev, int NG, long long nunits, const int *nfr);
 __global__ void k_pack(const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const short *ixq, const unsigned *sgn, const HxSegOut *seg,
                        const HxFrameOut *frm, const HxSlot *slots, unsigned char *out, long long out_stride, unsigned char *packet, int *status,
                        int frames_per_stream, int NG, int lsf, long long nframes_total, int solo, HxStream *st_w, const int *pre_len, const int *out_bytes,
-                       const int *carry_len, unsigned *frames_out, unsigned char *host_out, const int *seq_src);
+                       const int *carry_len, unsigned *frames_out, unsigned char *host_out, const int *seq_src, const int *nfr);
 __global__ void k_pack_carry(HxStream *st, const unsigned char *out, long long out_stride, const int *out_bytes, const int *carry_len, unsigned *frames_out);
 __global__ void k_pack_pre(const HxStream *st, unsigned char *out, long long out_stride, const int *pre_len);
 __global__ void k_dense_off(const int *out_bytes, long long *off, long long *off_copy, int S, long long cap, int *status);
@@ -101,6 +104,8 @@ struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; in
 struct Call {
     unsigned char *out = nullptr; long long out_stride = 0; int *out_bytes = nullptr;
     OptOut opt;
+    const int *nfr = nullptr;           // device copy of the per-stream frame counts in force when the call was made (encode_pass
+                                        // uploads it: hx_batch::d_nfr), null = every stream takes the call's nframes
     unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
 };
 
@@ -128,7 +133,14 @@ struct hx_batch {
     unsigned char *d_flg = nullptr;
     HxFrameDebug *d_dbg = nullptr;
     unsigned long long *d_prof = nullptr;
-    int lastNG = 0;                     // NG of the previous call (layout of the carry)
+    int lastNG = 0;                     // NG of the previous call (the debug taps' row stride)
+    // per-stream frame counts (hx_batch_frame_counts): the host copy a call checks and takes (empty = uniform calls), its
+    // page-locked staging and the device copies, three of each in rotation with the sets of signs - a device-buffer submit's
+    // deferred packing still reads its copy while two later submits are in flight
+    std::vector<int> nfr;
+    int *h_nfr = nullptr, *d_nfr = nullptr;     // [3][S] each
+    hipEvent_t ev_nfr[3] = {nullptr, nullptr, nullptr};    // the upload out of staging copy k is done
+    long long nplain = 0;               // plain calls made under counts (they rotate the copies too: no call waits for its predecessor's upload)
     // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
     int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
     std::vector<HxSrcPlan> src_plans;
@@ -261,6 +273,11 @@ enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
 // the PCM entry points, which a converting batch refuses
 HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes);
 HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes);
+// ... of the per-stream frame counts in force against the call's nframes (check_args makes it; hx_multi for all its blocks
+// before any of them starts, with `first` = the block's first stream, so the message names the caller's stream number)
+HX_LOCAL int check_counts(const hx_batch *b, int nframes, int first);
+// what hx_batch_frame_counts needs before it can set counts, and nothing else of it (hx_multi: all blocks, then set all)
+HX_LOCAL int counts_reserve(hx_batch *b, bool buffers);
 // ... and of the optional outputs a call would take: a CRC buffer without frame counters is refused
 HX_LOCAL int check_opt(const OptOut &o);
 // one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass
@@ -275,6 +292,28 @@ HX_LOCAL int drain(hx_batch *b);
 // the encode control of a converted source and its converter (hx_enc.cpp)
 HX_LOCAL int src_encode_control(const HX_E_CONTROL *ec, int source_bits, int source_is_float, int mpeg_select, int mono_convert,
                                 hx_src *conv, HX_E_CONTROL *ec_out);
+
+// The rows of a host-buffer call from the staging d_out to the caller's `out`: in one copy, or under per-stream frame counts
+// one copy per run of streams that took frames - the host row of a stream that sat the call out is not written either
+// (its staging row holds an earlier call's bytes).  q: null = synchronous copies, else asynchronous on q.
+// The guarantee costs copies: counts that alternate between 0 and more make S / 2 of them, one row each (4096 streams, every
+// second one idle: 2048), and no gap is bridged, since that would write the idle rows in between.  The step times of uneven
+// calls in DESIGN.md section 5 are of device-buffer calls and do not contain this.
+static inline int rows_to_host(const hx_batch *b, unsigned char *out, const unsigned char *d_out, long long out_stride, hipStream_t q)
+{
+    const int S = b->S;
+    for (int s = 0, e; s < S; s = e) {
+        e = S;
+        if (!b->nfr.empty()) {
+            while (s < S && b->nfr[s] == 0) s++;
+            for (e = s; e < S && b->nfr[e] > 0; e++) {}
+            if (s == S) break;
+        }
+        const size_t at = (size_t) s * out_stride, nb = (size_t) (e - s) * out_stride;
+        HIPCHK(q ? hipMemcpyAsync(out + at, d_out + at, nb, hipMemcpyDeviceToHost, q) : hipMemcpy(out + at, d_out + at, nb, hipMemcpyDeviceToHost));
+    }
+    return 0;
+}
 
 // One host-buffer call: grow the staging, copy the input up, make the device call `encode(c)`, wait for it and copy the
 // results back.  c is the call's record: the rows are b->d_out / d_outbytes; with `stats` the call's per-frame counters
@@ -315,8 +354,7 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
         long long k = b->S;
         while (k > 0 && hd->off[k] > hd->cap) k--;
         if (hd->off[k] > 0) HIPCHK(hipMemcpy(hd->dense, b->d_dense, (size_t) hd->off[k], hipMemcpyDeviceToHost));
-    } else
-        HIPCHK(hipMemcpy(out, b->d_out, (size_t) obytes, hipMemcpyDeviceToHost));
+    } else if (rows_to_host(b, out, b->d_out, out_stride, nullptr) != 0) return -1;
     if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, (size_t) sbytes, hipMemcpyDeviceToHost));
     if (crc) HIPCHK(hipMemcpy(crc, b->d_crc, (size_t) cbytes, hipMemcpyDeviceToHost));
     return 0;

@@ -352,7 +352,7 @@ __device__ __forceinline__ void spec_granule(const float *__restrict__ sb, const
                                              const HxParams *__restrict__ prm, const HxGlobalTabs *__restrict__ gt,
                                              const unsigned char *__restrict__ bt,
                                              float *__restrict__ xr, float *__restrict__ etab_out, float *__restrict__ thr_out,
-                                             int *__restrict__ msbase, int NG, int SG)
+                                             int *__restrict__ msbase, int NG, int SG, const int *__restrict__ nfr)
 {
     // in: [ch][S[g-3] | S[g-2]][576] subband samples; the first 2 x 576 floats are reused as the
     // spectrum [ch][576] once every lane holds its inputs in registers (DIRECT: the spectrum only)
@@ -382,6 +382,7 @@ __device__ __forceinline__ void spec_granule(const float *__restrict__ sb, const
     const unsigned run_word = p->lane_run[lane];            // the lane's line run and its band's last lane, for the stereo metric's sums
     const int band_last = p->band_last_lane[min(lane, 21)];
     __syncthreads();        // the tables (the only workgroup barrier: from here on each wave is on its own)
+    if (nfr && g >= 2 * nfr[s]) return;         // beyond the stream's count (the two waves may be of different streams: behind the barrier)
     const int nsb = p->nsb_ms0;
     const int btype = bt[sg];
     float g1[DIRECT ? 18 : 1], g2[DIRECT ? 18 : 1];
@@ -499,8 +500,9 @@ __device__ __forceinline__ void spec_granule(const float *__restrict__ sb, const
 #define HX_K4(name, direct) \
 __global__ __launch_bounds__(128) void name(const float *__restrict__ sb, const HxStream *__restrict__ st, const HxParams *__restrict__ prm, \
                                            const HxGlobalTabs *__restrict__ gt, const unsigned char *__restrict__ bt, float *__restrict__ xr, \
-                                           float *__restrict__ etab_out, float *__restrict__ thr_out, int *__restrict__ msbase, int NG, int SG) \
-{ spec_granule<direct>(sb, st, prm, gt, bt, xr, etab_out, thr_out, msbase, NG, SG); }
+                                           float *__restrict__ etab_out, float *__restrict__ thr_out, int *__restrict__ msbase, int NG, int SG, \
+                                           const int *__restrict__ nfr) \
+{ spec_granule<direct>(sb, st, prm, gt, bt, xr, etab_out, thr_out, msbase, NG, SG, nfr); }
 HX_K4(k_spec, false)
 HX_K4(k_spec_direct, true)
 
@@ -516,11 +518,17 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
                                                const unsigned char *__restrict__ bt, unsigned char *__restrict__ msflag, int *__restrict__ msdec,
                                                const float *__restrict__ thr, float *__restrict__ thrprev, int NG, int lsf,
                                                float *__restrict__ sb, int SG, const int16_t *__restrict__ pcm, long long nsamp,
-                                               const float *__restrict__ pcmf, int nchan)
+                                               const float *__restrict__ pcmf, int nchan, const int *__restrict__ nfr)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     HxStream *ss = st + s;
     const long long g0 = (long long) s * NG;
+    // The stream's granules of this call (hx_batch_frame_counts): the bound of the scan, and where the hand-overs to the next
+    // call come from - the pre-echo memory from granule NGs - 1, the subband carry from slots NGs .. NGs + 2, the PCM history
+    // from the last 480 of its 576 NGs samples.  NG stays the stride of the rows.  A stream that takes no frame keeps all of it.
+    const int NGs = nfr ? 2 * nfr[s] : NG;
+    if (NGs == 0) return;
+    const long long nown = 576LL * NGs;
     if (lane == 0) {
         const int on = prm[ss->cls].ms_flag, plain = prm[ss->cls].alloc1;    // (the first-generation allocator's measure takes no hysteresis)
         int mem = ss->ms_memory;
@@ -541,7 +549,7 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
         int g = 0;
         // eight granules per round of loads and stores (the rows are 16-byte aligned when NG % 8 == 0)
         if ((NG & 7) == 0)
-            for (; g + 8 <= NG; g += 8) {
+            for (; g + 8 <= NGs; g += 8) {
                 const int4 va = *reinterpret_cast<const int4 *>(msbase + g0 + g), vb = *reinterpret_cast<const int4 *>(msbase + g0 + g + 4);
                 const uint2 bb = *reinterpret_cast<const uint2 *>(bt + g0 + g);
                 int4 da, db;
@@ -553,7 +561,7 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
                 *reinterpret_cast<int4 *>(msdec + g0 + g + 4) = db;
                 *reinterpret_cast<uint2 *>(msflag + g0 + g) = make_uint2(fa | (fb << 16), fc | (fd << 16));
             }
-        for (; g < NG; g += 2) {
+        for (; g < NGs; g += 2) {
             int m1, m2;
             const unsigned f = frame(bt[g0 + g], bt[g0 + g + 1], msbase[g0 + g], msbase[g0 + g + 1], &m1, &m2);
             msdec[g0 + g] = m1; msdec[g0 + g + 1] = m2;
@@ -564,8 +572,8 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
     // pre-echo memory ("ecsave", reference spdsmr.c:112-117,283-298): this call's first granule is clamped against
     // the stream's carried values, which then become the doubled unclamped thresholds of this call's last granule
     // (long), or its doubled window-2 sums in entries 0..11 (short)
-    const float *last = thr + (g0 + NG - 1) * 128;
-    const int lastbt = bt[g0 + NG - 1];
+    const float *last = thr + (g0 + NGs - 1) * 128;
+    const int lastbt = bt[g0 + NGs - 1];
     for (int i = lane; i < 128; i += 64) {
         const float old = (&ss->thr_prev[0][0])[i];
         thrprev[(long long) s * 128 + i] = old;
@@ -578,13 +586,13 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
     for (int ch = 0; ch < 2; ch++) {
         float *base = sb + (long long) (s * 2 + ch) * SG * 576;
         for (int e = lane; e < 576; e += 64)
-            for (int k = 0; k < 3; k++) base[k * 576 + e] = base[(NG + k) * 576 + e];
+            for (int k = 0; k < 3; k++) base[k * 576 + e] = base[(NGs + k) * 576 + e];
         const int16_t *src = pcm + (long long) s * nsamp * nchan + ch;
         for (int i = lane; i < 480 && ch < nchan; i += 64) {
-            const long long n = nsamp - 480 + i;
+            const long long n = nown - 480 + i;
             // fewer than 480 new samples never happens (a frame is 1152), so all come from this batch
             ss->pcm_hist[ch][i] = pcmf ? pcmf[((long long) s * nsamp + n) * nchan + ch] : (float) src[nchan * n];
         }
     }
-    if (lane == 0) ss->frames_in += (int) (nsamp / 1152);
+    if (lane == 0) ss->frames_in += NGs / 2;
 }

@@ -289,7 +289,9 @@ struct AllocArgs {
     int *out_bytes;             // [S]
     HxFrameDebug *dbg;          // [S][F] or null
     long long out_stride;
-    int NG, S;
+    int NG, S;                  // NG: granules of the call = the row stride of every [S][NG] array
+    const int *nfr;             // [S] frames each stream takes of this call (hx_batch_frame_counts: stream s walks 2 nfr[s] granules
+                                // of its row), or null = NG / 2 each
     int *status;
     unsigned long long *prof;
     unsigned char *packet;      // optional [S][F][packet_stride]: each frame as a self-contained packet

@@ -216,6 +216,32 @@ int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc);
    crc[nstreams][nframes]; both are required */
 int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride,
                                  int *out_bytes, int *stats, unsigned short *crc);
+/* ---- per-stream frame counts: each stream of a call advances on its own (no reference equivalent; per stream it is the
+   reference called nfr[i] times) ----
+   nfr: HOST array [nstreams], copied by this function; NULL = every stream takes the call's nframes (the default).
+   Returns 0 / -1.  Sticky like the other per-batch setters; a call takes the counts in force when it is made - a submit
+   too: its deferred packing works with the counts of its own submit whatever is set afterwards.  Honoured by every encode
+   and submit entry point of a plain batch, device and host buffers, and by hx_multi_encode_*_host*.  With n = nfr[i]:
+     - a call with any n < 0 or n > nframes is refused (-1, hx_last_error names the stream) before anything is allocated,
+       copied or launched; the batch stays usable;
+     - the input layout is unchanged, [nstreams][nframes*1152][nch]: stream i's input is the first n*1152 samples of its
+       row, and the rest of the row has no influence on any output or state (it may be uninitialised);
+     - row i and out_bytes[i] hold exactly what the reference emits over those n calls; hx_batch_out_stride(b, nframes)
+       remains the bound;
+     - n = 0: out_bytes[i] = 0, row i is not written, and the stream's checkpoint (hx_batch_get_stream_state) is
+       bit-identical before and after the call - an idle slot of a long-lived batch sits the call out (row i: of the
+       device calls the device row, of the host-buffer calls the caller's host row, which is left out of the copy back);
+     - optional outputs: entries f < n are as without counts; frame counters at f >= n repeat the stream's counters as
+       they stand at the end of the call (n = 0: those it entered with); packet sizes at f >= n are {0, 0} and the packet
+       bytes there are not written; the MusicCRC follows from the counters by its e[f] formula, so d_crc[i][f >= n] is
+       the CRC of the whole of this call's row i; the dense image follows out_bytes.
+   The counts travel to the device through one of three page-locked staging copies: a call under counts waits on the
+   host until the upload of the third call before it is done, which can be as long as the earlier calls' kernels on that
+   stream take, and it cannot be made while its stream is being captured into a graph.  Calls without counts do neither.
+   The setter either sets the counts or (-1) changes nothing, and leaves the calling thread's current device alone.
+   Not covered: converting batches (the setter returns -1 on them: their converter's schedule is per call), the hx_enc_*
+   encoder, and bench.py, which measures uniform calls. */
+int hx_batch_frame_counts(hx_batch *b, const int *nfr);
 /* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
    The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
    gathers them on the GPU, behind its packing, into one image.  With nb[i] = out_bytes[i]:
@@ -347,6 +373,9 @@ int hx_multi_encode_f32_host_stats(hx_multi *m, const float *pcm, int nframes, u
 /* hx_batch_encode_f32_host_crc over all streams: stats [nstreams][nframes][2] and crc [nstreams][nframes], both required */
 int hx_multi_encode_f32_host_crc(hx_multi *m, const float *pcm, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats,
                                  unsigned short *crc);
+/* [nstreams] over all blocks; fanned out to the blocks' batches, all of them or (-1) none.  A call whose counts do not fit
+   its nframes is refused for all blocks before any of them starts, and hx_last_error names the stream by its number here */
+int hx_multi_frame_counts(hx_multi *m, const int *nfr);
 int hx_multi_status(hx_multi *m);
 /* converting batches (hx_batch_create_src) in the same blocks: in [nstreams][in_stride], frame_off [nstreams][nframes] or NULL,
    in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
