@@ -171,14 +171,38 @@ def crc_combine(a, b, n):
     return int(lib().hx_xing_crc_combine(int(a), int(b), int(n)))
 
 
+def _counts_array(n, counts):
+    if counts is None:
+        return None
+    counts = [int(c) for c in counts]
+    if len(counts) != n:
+        raise ValueError("frame counts: %d values for %d streams" % (len(counts), n))
+    return (C.c_int * n)(*counts)
+
+
+def _encode_src_counts_host(fn, handle, n, stride, rows, nframes, counts, frame_off, stats, crc):
+    """the converting host calls under per-call counts (hx_batch_ / hx_multi_encode_src_counts_host)"""
+    if crc and not stats:
+        raise TypeError("encode_src_counts_host(crc=True) needs stats=True (the CRCs follow from the call's frame counters)")
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    assert rows.ndim == 2 and rows.shape[0] == n
+    off = None if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+    assert off is None or off.shape == (n, nframes)
+    out = np.zeros((n, stride), dtype=np.uint8)
+    nb = np.zeros(n, dtype=np.int32)
+    used = np.zeros(n, dtype=np.int64)
+    st = np.zeros((n, nframes, 2), dtype=np.int32) if stats else None
+    cr = np.zeros((n, nframes), dtype=np.uint16) if crc else None
+    r = fn(handle, rows.ctypes.data, rows.shape[1], None if off is None else off.ctypes.data, nframes, _counts_array(n, counts),
+           out.ctypes.data, stride, nb.ctypes.data, used.ctypes.data, None if st is None else st.ctypes.data, None if cr is None else cr.ctypes.data)
+    if r != 0:
+        raise RuntimeError("%s failed: %s" % (fn.__name__, last_error()))
+    res = [out[i, :nb[i]].tobytes() for i in range(n)]
+    return (res, used) + ((st,) if stats else ()) + ((cr,) if crc else ())
+
+
 def _frame_counts(setter, handle, n, counts):
-    arr = None
-    if counts is not None:
-        counts = [int(c) for c in counts]
-        if len(counts) != n:
-            raise ValueError("frame counts: %d values for %d streams" % (len(counts), n))
-        arr = (C.c_int * n)(*counts)
-    if setter(handle, arr) != 0:
+    if setter(handle, _counts_array(n, counts)) != 0:
         raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
 
 
@@ -441,6 +465,26 @@ class SrcBatch(Batch):
         return (res, used, st) if stats else (res, used)
 
 
+    def encode_src_counts_host(self, rows, nframes, counts, frame_off=None, stats=False, crc=False):
+        """encode_src_host under per-stream frame counts: counts = a sequence of n ints (stream i makes the first counts[i]
+        calls of the nframes; 0 = it sits the call out, and its row and offsets are not read), or None = all of them; only
+        the offsets f < counts[i] are read -> (list of bytes per stream, in_used int64 [n][, stats int32 [n, nframes, 2]]
+        [, crc uint16 [n, nframes]]); crc needs stats (hx_batch_encode_src_counts_host)"""
+        return _encode_src_counts_host(lib().hx_batch_encode_src_counts_host, self.h, self.n, self.out_stride(nframes), rows, nframes,
+                                       counts, frame_off, stats, crc)
+
+    def encode_src_counts_device(self, d_in_ptr, in_stride, nframes, counts, d_out_ptr, out_stride, d_out_bytes_ptr, frame_off=None, stream=None):
+        """the device call (hx_batch_encode_src_counts_device): counts and frame_off are host arrays as above, the buffers
+        device pointers; asynchronous on stream -> in_used int64 [n]"""
+        off = None if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+        used = np.zeros(self.n, dtype=np.int64)
+        r = lib().hx_batch_encode_src_counts_device(self.h, d_in_ptr, in_stride, None if off is None else off.ctypes.data, nframes,
+                                                    _counts_array(self.n, counts), d_out_ptr, out_stride, d_out_bytes_ptr, used.ctypes.data, stream)
+        if r != 0:
+            raise RuntimeError("hx_batch_encode_src_counts_device failed: " + last_error())
+        return used
+
+
 def src_encode_control(ec, source):
     """the control the encoder runs behind the converter for a source (what MP3_audio_encode_init derives), and the bytes
     per call; (None, 0) when rejected"""
@@ -555,6 +599,11 @@ class SrcMulti(Multi):
         if r != 0:
             raise RuntimeError("hx_multi_encode_src_host failed: " + last_error())
         return [out[i, :nb[i]].tobytes() for i in range(self.n)], used
+
+    def encode_src_counts_host(self, rows, nframes, counts, frame_off=None, stats=False, crc=False):
+        """as SrcBatch.encode_src_counts_host, over all streams (hx_multi_encode_src_counts_host)"""
+        return _encode_src_counts_host(lib().hx_multi_encode_src_counts_host, self.h, self.n, int(lib().hx_multi_out_stride(self.h, nframes)),
+                                       rows, nframes, counts, frame_off, stats, crc)
 
 
 class Mp3Enc:

@@ -1,6 +1,8 @@
 // hmp3amd - file front end over libhmp3amd.
-//   hmp3amd <input.wav|-> <output.mp3|-> [flags]                 one file, frame by frame (hx_enc_* API)
-//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_batch_* API)
+//   hmp3amd <input.wav|-> <output.mp3|-> [flags]                 one file: a bounded regular file as a batch of one, a pipe or
+//                                                                 a very large file frame by frame (hx_enc_* API)
+//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API); files at any rate and
+//                                                                 -A go through the converting batches (hx_multi_create_src)
 // Same flags, encode loop and output files as the reference CLI (reference
 // test/tomp3.cpp:336-602 main, :645-1088 ff_encode): Xing/Info tag frame first, audio frames, four
 // frames of silence behind the input, drain until every submitted frame is out, then the tag is
@@ -242,6 +244,45 @@ struct Tagger {
 int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files, const Options &opt);
 
 bool mpeg_rate(int r) { return r == 32000 || r == 44100 || r == 48000 || r == 16000 || r == 22050 || r == 24000; }
+// The reference appends the four calls' worth of silence only if it fits a limit derived from its input buffer
+// (128 frames of stereo floats) and a per-format factor (tomp3.cpp:268,802,925; pcmhpm.c:450): with 32-bit
+// samples and a down-conversion by more than 1.14 (24-bit: 2.03) it never does, and the tail of the input that
+// is shorter than one call's need is dropped.  Found by tools/fuzz_cli.py.
+bool pad_fits(const WavInfo &wi, int init_bytes)
+{
+    const uint64_t ref_bufbytes = 128ull * sizeof(float) * 2304, fmt_factor = (uint64_t) wi.channels * (uint64_t) ((wi.bits * 7) / 8);
+    return fmt_factor != 0 && (((ref_bufbytes << 1) / fmt_factor) & ~1ull) > 4ull * (uint64_t) init_bytes;
+}
+
+// the file goes through the sample-rate converter: its rate is no MPEG rate, or -A asks for another one
+bool needs_conversion(const Input &in, const Options &opt) { return opt.mpeg_select || !mpeg_rate(in.wi.rate); }
+
+// The calls the frame-by-frame loop (encode_streaming) makes on a file that goes through the converter, computed on the host:
+// over the window audio ++ 4 x init_bytes zero bytes (where pad_fits allows them) one call while at least init_bytes are left,
+// each consuming what the converter's schedule says.  Sets in->size to the window's size and appends the zero bytes and the
+// slack to in->data; start: the byte position of every call's input; ec_enc: the control the encoder behind the converter
+// runs.  Returns the number of calls, -1 if the converter rejects the source (hx_last_error).
+long long converter_calls(Input &in, const Options &opt, std::vector<long long> *start, HX_E_CONTROL *ec_enc)
+{
+    const HX_SOURCE src = {in.wi.bits, in.is_float, opt.mpeg_select, in.mono_convert};
+    HX_E_CONTROL ec2;
+    const int init_bytes = hx_src_encode_control(&in.ec, &src, &ec2);
+    if (!init_bytes) return -1;
+    if (ec_enc) *ec_enc = ec2;
+    hx_src *conv = hx_src_create();
+    int cutoff = 0;
+    if (!hx_src_init(conv, in.wi.rate, in.wi.channels, in.wi.bits, in.is_float, ec2.samprate, ec2.mode == 3 ? 1 : 2, &cutoff)) { hx_src_destroy(conv); return -1; }
+    in.size = (size_t) in.audio_bytes + (pad_fits(in.wi, init_bytes) ? 4 * (size_t) init_bytes : 0);
+    in.data.resize(in.size + (1 << 17), 0);
+    long long calls = 0, pos = 0, nbytes = 0;
+    while ((long long) in.size - pos >= init_bytes) {
+        if (start) start->push_back(pos);
+        hx_src_schedule(conv, calls++, 1, &nbytes);
+        pos += nbytes;
+    }
+    hx_src_destroy(conv);
+    return calls;
+}
 
 // tomp3.cpp:1169-1196 (-EC)
 void print_ec(const HX_E_CONTROL *ec)
@@ -310,13 +351,7 @@ int encode_streaming(const char *fin, const char *fout, const Options &opt)
         const size_t slack = 1 << 17, piece = 1 << 20;
         std::vector<unsigned char> win(piece + (size_t) init_bytes + slack, 0), bs(128 * 1024), zero((size_t) 4 * init_bytes + slack, 0);
         size_t lo = 0, hi = 0;                  // valid bytes of the window: [lo, hi)
-        // The reference appends the four calls' worth of silence only if it fits a limit derived from its input buffer
-        // (128 frames of stereo floats) and a per-format factor (tomp3.cpp:268,802,925; pcmhpm.c:450): with 32-bit
-        // samples and a down-conversion by more than 1.14 (24-bit: 2.03) it never does, and the tail of the input that
-        // is shorter than one call's need is dropped.  Found by tools/fuzz_cli.py.
-        const uint64_t ref_bufbytes = 128ull * sizeof(float) * 2304, fmt_factor = (uint64_t) in.wi.channels * (uint64_t) ((in.wi.bits * 7) / 8);
-        const bool pad_fits = fmt_factor != 0 && (((ref_bufbytes << 1) / fmt_factor) & ~1ull) > 4ull * (uint64_t) init_bytes;
-        uint64_t audio = 0, zeros_left = pad_fits ? 4ull * (uint64_t) init_bytes : 0;
+        uint64_t audio = 0, zeros_left = pad_fits(in.wi, init_bytes) ? 4ull * (uint64_t) init_bytes : 0;      // (the silence behind the input)
         bool eof = false, werr = false;
         unsigned frames_expected = 0;
         auto emit = [&](const HX_IN_OUT &x) {
@@ -382,14 +417,15 @@ int encode_streaming(const char *fin, const char *fout, const Options &opt)
 
 int encode_one_file(const char *fin, const char *fout, const Options &opt)
 {
-    // A regular file of bounded size at an MPEG rate with a seekable output goes through the batched API as a
-    // batch of one (96 frames per call instead of one), which writes exactly what the frame-by-frame loop
-    // writes.  Pipes, very large files and inputs that need a rate conversion stream frame by frame.
+    // A regular file of bounded size with a seekable output goes through the batched API as a batch of one (96
+    // frames per call instead of one), which writes exactly what the frame-by-frame loop writes - a file that needs a
+    // rate conversion (its rate, or -A) through a converting batch.  Pipes and very large files stream frame by frame,
+    // and so does an input too short for one converter call, which that loop answers with a file of the tag alone.
     uint64_t fsize = 0;
-    if (!opt.mpeg_select && strcmp(fin, "-") && strcmp(fout, "-") && regular_file_size(fin, &fsize) && fsize <= kBatchRouteMaxBytes) {
+    if (strcmp(fin, "-") && strcmp(fout, "-") && regular_file_size(fin, &fsize) && fsize <= kBatchRouteMaxBytes) {
         std::vector<Input> one(1);
         if (!load_input(fin, opt, &one[0])) return 1;
-        if (mpeg_rate(one[0].wi.rate)) return encode_loaded(one, {fin, fout}, opt);
+        if (!needs_conversion(one[0], opt) || converter_calls(one[0], opt, nullptr, nullptr) > 0) return encode_loaded(one, {fin, fout}, opt);
     }
     return encode_streaming(fin, fout, opt);
 }
@@ -434,31 +470,55 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
 {
     const int S = (int) in.size();
     std::vector<HX_E_CONTROL> ctl(S);
+    // One file that needs the converter sends all of them through a converting batch (a file at its own MPEG rate is the
+    // converter's copy case); without one the plain batch runs, fed fp32 frames made here.
+    bool conv = false;
+    for (int i = 0; i < S; i++) conv = conv || needs_conversion(in[i], opt);
+    std::vector<HX_SOURCE> srcs(S);
+    std::vector<size_t> nc(S);                          // calls of the single-file loop on the file's input (the drain follows them)
+    std::vector<std::vector<long long>> start(S);       // converting route: where each of them starts in the file's bytes
     int nch = 0;
     for (int i = 0; i < S; i++) {
         HX_E_CONTROL ec = in[i].ec;
-        if (in[i].mono_convert) ec.mode = 3;
+        if (conv) {
+            srcs[i] = {in[i].wi.bits, in[i].is_float, opt.mpeg_select, in[i].mono_convert};
+            const long long n = converter_calls(in[i], opt, &start[i], &ec);
+            if (n < 0) { fprintf(stderr, "\n ENCODER INIT FAIL (%s): %s\n", files[2 * i], hx_last_error()); return 1; }
+            if (n == 0) { fprintf(stderr, "\n %s is shorter than one call of its converter\n", files[2 * i]); return 1; }
+            nc[i] = (size_t) n;
+            ctl[i] = in[i].ec;                          // (the batch derives the encoder's control from the source's, as converter_calls did)
+        } else if (in[i].mono_convert) ec.mode = 3;
         const int c = ec.mode == 3 ? 1 : 2;
         if (nch && c != nch) { fprintf(stderr, "\n -batch needs files that all encode to the same channel count\n"); return 1; }
         nch = c;
         if (!hx_control_info(&ec, &in[i].ec_used, &in[i].head)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s)\n", files[2 * i]); return 1; }
+        if (conv) continue;
         ctl[i] = ec;
-        if (opt.mpeg_select || !mpeg_rate(in[i].wi.rate)) {
-            fprintf(stderr, "\n -batch encodes files at their own MPEG sample rate; %s needs a rate conversion (use the single-file mode)\n", files[2 * i]);
-            return 1;
-        }
         in[i].pad(init_bytes_same_rate(in[i]));
+        nc[i] = ncalls(in[i]);
     }
     const int CH = 96;                                  // frames per batched call at most
     const size_t DRAIN = 32;                            // room for a file's drain frames (a reservoir never spans that many)
     // the files spread over the node's GPUs in contiguous blocks (-Gn limits the count), one host thread per device
-    hx_multi *b = hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
-    if (!b) { fprintf(stderr, "\n ENCODER INIT FAIL: %s\n", hx_last_error()); return 1; }
+    hx_multi *b = conv ? hx_multi_create_src(opt.ngpus, nullptr, S, ctl.data(), 0, srcs.data(), 0, CH) : hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
+    if (!b) {
+        // (what cannot share a batch - channel counts, MPEG-1 with MPEG-2 rates, allocator generations: the first file that differs from files[0] in the rates)
+        fprintf(stderr, "\n ENCODER INIT FAIL: %s", hx_last_error());
+        for (int i = 1; i < S; i++)
+            if ((in[i].ec_used.samprate < 32000) != (in[0].ec_used.samprate < 32000)) { fprintf(stderr, " (%s encodes at %d Hz, %s at %d Hz)", files[2 * i], in[i].ec_used.samprate, files[0], in[0].ec_used.samprate); break; }
+        fprintf(stderr, "\n");
+        return 1;
+    }
     if (S > 1) fprintf(stderr, "\n %d files on %d GPU(s)", S, hx_multi_ndevices(b));
     if (opt.ec_display) print_ec(&in[0].ec_used);
     const long long stride = hx_multi_out_stride(b, CH);
-    std::vector<float> pcm((size_t) S * CH * 1152 * nch), tmp(2304);
+    std::vector<float> pcm(conv ? 0 : (size_t) S * CH * 1152 * nch), tmp(2304);
     const std::vector<unsigned char> zero_frame(2304 * 4, 0);
+    // converting route: a row holds the file's bytes from its next call on, enough for CH calls of any file, then a region of
+    // zero bytes that every drain call reads, as the single-file loop hands one zero buffer to all of them
+    const long long row_data = conv ? hx_multi_src_in_stride(b, CH) : 0, in_stride = row_data + (conv ? hx_multi_src_in_stride(b, 1) : 0);
+    std::vector<unsigned char> rows((size_t) S * in_stride);
+    std::vector<long long> off(conv ? (size_t) S * CH : 0);
     std::vector<unsigned char> out((size_t) S * stride);
     std::vector<int> nb(S), stats((size_t) S * CH * 2);
     // the MusicCRC per file: every call returns the CRC of its own bytes up to each input frame (k_crc, on the GPU), and the
@@ -467,30 +527,42 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
     std::vector<char> done(S, 0);                       // the file's drain has ended: it takes no more frames
     std::vector<std::vector<unsigned char>> stream(S);
     std::vector<std::vector<unsigned>> fr(S), by(S);    // per frame fed to the file's stream: frames / bytes out so far
-    // Every call gives each file the frames it still needs (hx_multi_frame_counts): its input frames, then silence up to the
+    // Every call gives each file the frames it still needs (per-stream frame counts): its input frames, then silence up to the
     // frame at which its drain ends; a finished file takes 0 and costs nothing, and the loop ends with the last file, not
     // DRAIN frames behind the longest one for all.  The call is as long as its largest count.
     std::vector<int> cnt(S);
     for (;;) {
         int nf = 0;
         for (int i = 0; i < S; i++) {
-            const size_t fed = fr[i].size(), room = ncalls(in[i]) + DRAIN;
+            const size_t fed = fr[i].size(), room = nc[i] + DRAIN;
             cnt[i] = (done[i] || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
             nf = std::max(nf, cnt[i]);
         }
         if (nf == 0) break;
-        for (int i = 0; i < S; i++) {
-            const size_t calls = ncalls(in[i]), p0 = fr[i].size();
+        for (int i = 0; i < S && !conv; i++) {
+            const size_t p0 = fr[i].size();
             for (int k = 0; k < cnt[i]; k++) {
                 // past the end the single-file loop feeds frames of zero BYTES: silence, except for
                 // 8-bit unsigned input where a zero byte is full-scale negative
-                if (p0 + k < calls) frame_to_float(in[i], in[i].data.data() + (p0 + k) * in[i].frame_in, tmp.data());
+                if (p0 + k < nc[i]) frame_to_float(in[i], in[i].data.data() + (p0 + k) * in[i].frame_in, tmp.data());
                 else frame_to_float(in[i], zero_frame.data(), tmp.data());
                 memcpy(&pcm[((size_t) i * nf + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
             }
         }
-        if (hx_multi_frame_counts(b, cnt.data()) != 0 ||
-            hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0) {
+        for (int i = 0; i < S && conv; i++) {
+            // the calls on the file's input start where the schedule puts them, counted from the row's first byte; the
+            // drain calls all read the zero region (zero bytes: 8-bit input stays full-scale negative there too)
+            const size_t p0 = fr[i].size();
+            unsigned char *row = rows.data() + (size_t) i * in_stride;
+            if (cnt[i] == 0) continue;
+            memset(row, 0, (size_t) in_stride);
+            const long long base = p0 < nc[i] ? start[i][p0] : 0;
+            if (p0 < nc[i]) memcpy(row, in[i].data.data() + base, (size_t) std::min<long long>(row_data, (long long) in[i].data.size() - base));
+            for (int k = 0; k < nf; k++) off[(size_t) i * nf + k] = (k < cnt[i] && p0 + k < nc[i]) ? start[i][p0 + k] - base : row_data;
+        }
+        const int rc_call = conv ? hx_multi_encode_src_counts_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), out.data(), stride, nb.data(), nullptr, stats.data(), crc.data())
+                                 : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
+        if (rc_call != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
             return 1;
@@ -502,7 +574,7 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
             stream[i].insert(stream[i].end(), out.begin() + (size_t) i * stride, out.begin() + (size_t) i * stride + nb[i]);
             for (int k = 0; k < n; k++) { fr[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2]); by[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2 + 1]); }
             // the last frame the file uses (the per-file loop below: u - 1), if it lies in this call
-            const size_t calls = ncalls(in[i]), expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);
+            const size_t calls = nc[i], expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);
             int k = p0 + n >= calls ? (int) (calls > p0 + 1 ? calls - 1 - p0 : 0) : n;
             while (k < n && fr[i][p0 + k] < expected) k++;
             if (k < n) {
@@ -518,7 +590,7 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
     // per file: what the single-file loop would have written
     int rc = 0;
     for (int i = 0; i < S; i++) {
-        const size_t calls = ncalls(in[i]);
+        const size_t calls = nc[i];
         Tagger tg;
         tg.begin(in[i], opt.xing_flag);
         for (size_t u = 0; u < calls; u++) tg.after_call(fr[i][u], by[i][u]);

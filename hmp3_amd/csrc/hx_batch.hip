@@ -337,11 +337,17 @@ extern "C" int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc)
 // counts_reserve: everything that can fail - whether the batch takes counts at all, and (buffers) at the first use their
 // staging, events and device copies (a never-recorded event counts as done).  Each piece is made once: a call that fails half way leaves what it made to the next one (and
 // to hx_batch_destroy), which makes only the rest.  The calling thread's current device is left as it was.
+// counts_buffers: the second part alone - a converting batch, which the setter refuses, takes its counts as an argument of
+// hx_batch_encode_src_counts_* and needs the same staging.
 int counts_reserve(hx_batch *b, bool buffers)
 {
     if (!b) { set_err("null batch"); return -1; }
-    if (b->nsrc) { set_err("a converting batch takes no per-stream frame counts: its converter's schedule is per call"); return -1; }
-    if (!buffers || (b->h_nfr && b->d_nfr && b->ev_nfr[2])) return 0;
+    if (b->nsrc) { set_err("a converting batch takes its per-stream frame counts per call, not from this setter: hx_batch_encode_src_counts_*"); return -1; }
+    return buffers ? counts_buffers(b) : 0;
+}
+int counts_buffers(hx_batch *b)
+{
+    if (b->h_nfr && b->d_nfr && b->ev_nfr[2]) return 0;
     int dev0 = -1;
     HIPCHK(hipGetDevice(&dev0));
     HIPCHK(hipSetDevice(b->device));
@@ -418,10 +424,14 @@ int check_args(const hx_batch *b, const void *in, int nframes, const void *out, 
 // (hx_batch_frame_counts: a count no kernel could honour never reaches one)
 int check_counts(const hx_batch *b, int nframes, int first)
 {
-    for (size_t i = 0; i < b->nfr.size(); i++)
-        if (b->nfr[i] < 0 || b->nfr[i] > nframes) {
+    return check_counts_arg(b->nfr.data(), (int) b->nfr.size(), nframes, first);
+}
+int check_counts_arg(const int *nfr, int S, int nframes, int first)
+{
+    for (int i = 0; nfr && i < S; i++)
+        if (nfr[i] < 0 || nfr[i] > nframes) {
             char msg[96];
-            snprintf(msg, sizeof(msg), "stream %d: frame count %d out of range (0 .. nframes = %d)", first + (int) i, b->nfr[i], nframes);
+            snprintf(msg, sizeof(msg), "stream %d: frame count %d out of range (0 .. nframes = %d)", first + i, nfr[i], nframes);
             set_err("%s", msg);
             return -1;
         }
@@ -565,18 +575,27 @@ static int pipe_enter(hx_batch *b, Pass &p)
 // that submit's kernels is stream order: the upload goes onto the caller's stream behind order_behind_submits (a plain
 // call after submits) or, for a submit after plain calls, onto the front-end stream behind ev_in, which is behind
 // everything the plain calls put on the caller's stream.
-static int upload_counts(hx_batch *b, Pass &p)
+// A converting call has made its upload already, in front of k_src, which reads the same copy (counts_upload_plain: it is a
+// plain call, and no submit of a converting batch exists that it could follow): its record arrives with nfr set.
+static int counts_upload(hx_batch *b, int k, hipStream_t q, const int *&d_nfr)
 {
-    if (b->nfr.empty()) return 0;
-    const int k = p.kind == PASS_PLAIN ? (int) (b->nplain++ % 3) : p.sset;
     const size_t nb = sizeof(int) * (size_t) b->S;
     int *h = b->h_nfr + (size_t) k * b->S, *d = b->d_nfr + (size_t) k * b->S;
     HIPCHK(hipEventSynchronize(b->ev_nfr[k]));
     memcpy(h, b->nfr.data(), nb);
-    HIPCHK(hipMemcpyAsync(d, h, nb, hipMemcpyHostToDevice, p.q));
-    HIPCHK(hipEventRecord(b->ev_nfr[k], p.q));
-    p.call.nfr = d;
+    HIPCHK(hipMemcpyAsync(d, h, nb, hipMemcpyHostToDevice, q));
+    HIPCHK(hipEventRecord(b->ev_nfr[k], q));
+    d_nfr = d;
     return 0;
+}
+int counts_upload_plain(hx_batch *b, hipStream_t q, const int *&d_nfr)
+{
+    return counts_upload(b, (int) (b->nplain++ % 3), q, d_nfr);
+}
+static int upload_counts(hx_batch *b, Pass &p)
+{
+    if (b->nfr.empty() || p.call.nfr) return 0;
+    return p.kind == PASS_PLAIN ? counts_upload_plain(b, p.q, p.call.nfr) : counts_upload(b, p.sset, p.q, p.call.nfr);
 }
 
 // the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]

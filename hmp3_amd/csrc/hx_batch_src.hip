@@ -104,27 +104,28 @@ static int src_check(const hx_batch *b, const void *in, long long in_stride, int
     return 0;
 }
 
-// one converting call on device buffers (arguments checked by the caller): k_src into d_src_pcm, then the fp32 pass over it
-static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off, int nframes,
-                      const Call &c, long long *in_used, void *stream)
+// Every call's input extent from the schedule, checked against the row before anything runs.  Consecutive calls: the
+// consumption telescopes, and the last call reaches furthest (a call reads at most ntaps - k past its successor's
+// start, and the last one reads at least ntaps), so one closed form per stream; with offsets every call is checked.
+// Under counts (nfr, host) stream s makes n = nfr[s] calls: its last call is c0 + n - 1, only the offsets f < n are read,
+// and a stream with n = 0 reads nothing, offsets included.
+int src_extents(const hx_batch *b, long long in_stride, const long long *frame_off, int nframes, const int *nfr, int first, long long *used_end)
 {
-    // every call's input extent from the schedule, checked against the row before anything runs.  Consecutive calls: the
-    // consumption telescopes, and the last call reaches furthest (a call reads at most ntaps - k past its successor's
-    // start, and the last one reads at least ntaps), so one closed form per stream; with offsets every call is checked.
-    const int S = b->S;
-    std::vector<long long> used_end(S);
-    for (int s = 0; s < S; s++) {
+    for (int s = 0; s < b->S; s++) {
+        const int n = nfr ? nfr[s] : nframes;
+        if (used_end) used_end[s] = 0;
+        if (n == 0) continue;
         const HxSrcPlan &p = b->src_plans[b->src_cls[s]];
         const long long fb = (long long) p.channels * (p.bits / 8), c0 = b->src_calls[s];
         long long used, rd;
         int bad = -1;
         long long off = 0;
         if (!frame_off) {
-            off = hx_src_consumed(&p, c0, c0 + nframes - 1) * fb;
-            hx_src_call_extent(&p, c0 + nframes - 1, &used, &rd);
-            if (off + rd * fb > in_stride) bad = nframes - 1;
+            off = hx_src_consumed(&p, c0, c0 + n - 1) * fb;
+            hx_src_call_extent(&p, c0 + n - 1, &used, &rd);
+            if (off + rd * fb > in_stride) bad = n - 1;
         } else {
-            for (int f = 0; f < nframes && bad < 0; f++) {
+            for (int f = 0; f < n && bad < 0; f++) {
                 off = frame_off[(long long) s * nframes + f];
                 hx_src_call_extent(&p, c0 + f, &used, &rd);
                 if (off < 0 || off + rd * fb > in_stride) bad = f;
@@ -132,15 +133,35 @@ static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_strid
         }
         if (bad >= 0) {
             char msg[160];
-            snprintf(msg, sizeof msg, "stream %d, call %d: its input [%lld, %lld) does not fit in_stride %lld", s, bad, off, off + rd * fb, in_stride);
+            snprintf(msg, sizeof msg, "stream %d, call %d: its input [%lld, %lld) does not fit in_stride %lld", first + s, bad, off, off + rd * fb, in_stride);
             set_err("%s", msg);
             return -1;
         }
-        used_end[s] = off + used * fb;
+        if (used_end) used_end[s] = off + used * fb;
     }
+    return 0;
+}
+
+// The counts of a converting call under counts are the batch's for as long as the call runs: its pass and the copy back of
+// a host call (rows_to_host) take them from there, as a plain batch's calls do.  Between calls a converting batch has none.
+struct CallCounts {
+    hx_batch *b;
+    CallCounts(hx_batch *b_, const int *nfr) : b(b_) { if (nfr) b->nfr.assign(nfr, nfr + b->S); }
+    ~CallCounts() { b->nfr.clear(); }
+};
+
+// one converting call on device buffers (arguments and extents checked by the caller, counts in b->nfr): k_src into
+// d_src_pcm, then the fp32 pass over it.  Both read the same device copy of the counts, uploaded in front of k_src.
+static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off, int nframes,
+                      Call c, const long long *used_end, long long *in_used, void *stream)
+{
+    const int S = b->S;
     HIPCHK(hipSetDevice(b->device));
     hipStream_t q = (hipStream_t) stream;
+    Poison poison{b};                   // (from the first upload on)
+    if (!b->nfr.empty() && counts_upload_plain(b, q, c.nfr) != 0) return -1;
     if (frame_off) {
+        // (entries beyond a stream's count travel as they are: no workgroup reads them)
         const size_t nb = sizeof(long long) * (size_t) S * nframes;
         HIPCHK(hipEventSynchronize(b->ev_src_off));        // (the page-locked copy of the previous call's offsets is on the device)
         memcpy(b->h_src_off, frame_off, nb);
@@ -153,33 +174,62 @@ static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_strid
     a.calls_in = b->d_src_calls + (long long) b->src_par * S; a.calls_out = b->d_src_calls + (long long) (1 - b->src_par) * S;
     a.carry_in = b->d_src_carry + (long long) b->src_par * S * 2 * HX_SRC_CARRY;
     a.carry_out = b->d_src_carry + (long long) (1 - b->src_par) * S * 2 * HX_SRC_CARRY;
-    a.out = b->d_src_pcm; a.nframes = nframes; a.nch = b->nchan; a.xwin = b->src_xwin; a.zwin = b->src_zwin;
+    a.out = b->d_src_pcm; a.nfr = c.nfr; a.nframes = nframes; a.nch = b->nchan; a.xwin = b->src_xwin; a.zwin = b->src_zwin;
     a.zoff = b->src_zoff; a.coff = b->src_coff; a.status = b->d_status;
-    Poison poison{b};                   // (from the first launch on)
     LAUNCH_LDS(k_src, dim3((unsigned) ((long long) S * nframes)), dim3(256), b->src_lds, q, a);
     b->src_par ^= 1;
-    for (int s = 0; s < S; s++) b->src_calls[s] += nframes;
+    for (int s = 0; s < S; s++) b->src_calls[s] += b->nfr.empty() ? nframes : b->nfr[s];
     b->src_lastF = nframes;
-    if (in_used) memcpy(in_used, used_end.data(), sizeof(long long) * S);
+    if (in_used) memcpy(in_used, used_end, sizeof(long long) * S);
     if (encode_pass(b, {b->d_src_pcm, true}, nframes, c, stream, PASS_PLAIN) != 0) return -1;
     return poison.ok();
 }
 
+// what a converting call checks before anything is allocated, copied, launched or counted: the arguments, the counts'
+// range, the optional outputs it would take and every stream's input extent (used_end: see src_extents)
+static int src_checked(hx_batch *b, const void *in, long long in_stride, const long long *frame_off, int nframes, const int *nfr,
+                       const void *out, long long out_stride, const void *out_bytes, const OptOut &o, std::vector<long long> &used_end)
+{
+    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0 || check_counts_arg(nfr, b->S, nframes, 0) != 0 || check_opt(o) != 0) return -1;
+    used_end.resize(b->S);
+    if (src_extents(b, in_stride, frame_off, nframes, nfr, 0, used_end.data()) != 0) return -1;
+    return nfr ? counts_buffers(b) : 0;
+}
+
+extern "C" int hx_batch_encode_src_counts_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
+                                                 int nframes, const int *nfr, unsigned char *d_out, long long out_stride, int *d_out_bytes,
+                                                 long long *in_used, void *stream)
+{
+    std::vector<long long> used_end;
+    if (src_checked(b, d_in, in_stride, frame_off, nframes, nfr, d_out, out_stride, d_out_bytes, b ? b->opt : OptOut(), used_end) != 0) return -1;
+    CallCounts counts(b, nfr);
+    return src_encode(b, d_in, in_stride, frame_off, nframes, call_on(b, d_out, out_stride, d_out_bytes), used_end.data(), in_used, stream);
+}
 extern "C" int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
                                           int nframes, unsigned char *d_out, long long out_stride, int *d_out_bytes,
                                           long long *in_used, void *stream)
 {
-    if (src_check(b, d_in, in_stride, nframes, d_out, out_stride, d_out_bytes) != 0 || check_opt(b->opt) != 0) return -1;
-    return src_encode(b, d_in, in_stride, frame_off, nframes, call_on(b, d_out, out_stride, d_out_bytes), in_used, stream);
+    return hx_batch_encode_src_counts_device(b, d_in, in_stride, frame_off, nframes, nullptr, d_out, out_stride, d_out_bytes, in_used, stream);
 }
 
 // (host_call with a drain before the upload: the staging may still be read by an earlier call)
+extern "C" int hx_batch_encode_src_counts_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                               int nframes, const int *nfr, unsigned char *out, long long out_stride, int *out_bytes,
+                                               long long *in_used, int *stats, unsigned short *crc)
+{
+    std::vector<long long> used_end;
+    OptOut o = b ? b->opt : OptOut();
+    if (stats) o.frame_stats = stats;
+    if (crc) { o.crc = crc; if (!stats) o.frame_stats = nullptr; }      // (the host call's CRC comes from the host call's counters)
+    if (src_checked(b, in, in_stride, frame_off, nframes, nfr, out, out_stride, out_bytes, o, used_end) != 0) return -1;
+    CallCounts counts(b, nfr);
+    return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
+        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, c, used_end.data(), in_used, nullptr);
+    }, nullptr, crc);
+}
 extern "C" int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
                                         int nframes, unsigned char *out, long long out_stride, int *out_bytes,
                                         long long *in_used, int *stats)
 {
-    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0) return -1;
-    return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
-        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, c, in_used, nullptr);
-    });
+    return hx_batch_encode_src_counts_host(b, in, in_stride, frame_off, nframes, nullptr, out, out_stride, out_bytes, in_used, stats, nullptr);
 }

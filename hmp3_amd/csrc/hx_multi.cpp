@@ -259,16 +259,32 @@ extern "C" long long hx_multi_src_in_stride(const hx_multi *m, int nframes)
     return n;
 }
 
-// hx_batch_encode_src_host over all streams
+// hx_batch_encode_src_counts_host over all streams.  All blocks or none: the counts' range, the optional outputs and every
+// stream's input extent are checked for all blocks, with the caller's stream numbers, before one block starts.
+extern "C" int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                               const int *nfr, unsigned char *out, long long out_stride, int *out_bytes, long long *in_used,
+                                               int *stats, unsigned short *crc)
+{
+    if (m && nframes > 0 && in_stride > 0) {
+        if (crc && !stats) { set_err("crc needs stats: the CRCs follow from the call's frame counters"); return -1; }
+        if (check_counts_arg(nfr, m->S, nframes, 0) != 0) return -1;
+        for (size_t k = 0; k < m->part.size(); k++) {
+            const long long f = m->first[k];
+            if (!m->part[k]->nsrc) { set_err("not a converting batch (hx_multi_create_src)"); return -1; }
+            if (src_extents(m->part[k], in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes, nfr ? nfr + f : nullptr, (int) f, nullptr) != 0) return -1;
+        }
+    }
+    return multi_fanout(m, in && out && out_bytes, nframes, out_stride, [&](size_t k) {
+        const long long f = m->first[k];
+        return hx_batch_encode_src_counts_host(m->part[k], in + f * in_stride, in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes,
+                                               nfr ? nfr + f : nullptr, out + f * out_stride, out_stride, out_bytes + f, in_used ? in_used + f : nullptr,
+                                               stats ? stats + f * nframes * 2 : nullptr, crc ? crc + f * nframes : nullptr);
+    });
+}
 extern "C" int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
                                         unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats)
 {
-    return multi_fanout(m, in && out && out_bytes, nframes, out_stride, [&](size_t k) {
-        const long long f = m->first[k];
-        return hx_batch_encode_src_host(m->part[k], in + f * in_stride, in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes,
-                                        out + f * out_stride, out_stride, out_bytes + f, in_used ? in_used + f : nullptr,
-                                        stats ? stats + f * nframes * 2 : nullptr);
-    });
+    return hx_multi_encode_src_counts_host(m, in, in_stride, frame_off, nframes, nullptr, out, out_stride, out_bytes, in_used, stats, nullptr);
 }
 
 extern "C" int hx_multi_status(hx_multi *m)

@@ -105,7 +105,8 @@ struct Call {
     unsigned char *out = nullptr; long long out_stride = 0; int *out_bytes = nullptr;
     OptOut opt;
     const int *nfr = nullptr;           // device copy of the per-stream frame counts in force when the call was made (encode_pass
-                                        // uploads it: hx_batch::d_nfr), null = every stream takes the call's nframes
+                                        // uploads it: hx_batch::d_nfr; a converting call under counts has, in front of k_src),
+                                        // null = every stream takes the call's nframes
     unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
 };
 
@@ -134,7 +135,8 @@ struct hx_batch {
     HxFrameDebug *d_dbg = nullptr;
     unsigned long long *d_prof = nullptr;
     int lastNG = 0;                     // NG of the previous call (the debug taps' row stride)
-    // per-stream frame counts (hx_batch_frame_counts): the host copy a call checks and takes (empty = uniform calls), its
+    // per-stream frame counts (hx_batch_frame_counts; of a converting batch the counts of the hx_batch_encode_src_counts_*
+    // call being made, empty between calls): the host copy a call checks and takes (empty = uniform calls), its
     // page-locked staging and the device copies, three of each in rotation with the sets of signs - a device-buffer submit's
     // deferred packing still reads its copy while two later submits are in flight
     std::vector<int> nfr;
@@ -278,6 +280,15 @@ HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const v
 HX_LOCAL int check_counts(const hx_batch *b, int nframes, int first);
 // what hx_batch_frame_counts needs before it can set counts, and nothing else of it (hx_multi: all blocks, then set all)
 HX_LOCAL int counts_reserve(hx_batch *b, bool buffers);
+// ... the staging, events and device copies alone, and one upload of b->nfr in the plain calls' rotation on stream q (d_nfr: the
+// device copy it went to) - the converting calls under counts (hx_batch_src.hip), whose k_src reads the counts before the pass
+HX_LOCAL int counts_buffers(hx_batch *b);
+HX_LOCAL int counts_upload_plain(hx_batch *b, hipStream_t q, const int *&d_nfr);
+// ... and the range check of counts that come as a call's argument (first: as for check_counts)
+HX_LOCAL int check_counts_arg(const int *nfr, int S, int nframes, int first);
+// A converting call's input extents against its rows, per stream under its count (nfr null: nframes), before anything runs;
+// used_end [S] or null: where each stream's following call would start.  first: as for check_counts.
+HX_LOCAL int src_extents(const hx_batch *b, long long in_stride, const long long *frame_off, int nframes, const int *nfr, int first, long long *used_end);
 // ... and of the optional outputs a call would take: a CRC buffer without frame counters is refused
 HX_LOCAL int check_opt(const OptOut &o);
 // one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass

@@ -48,6 +48,7 @@ struct SrcArgs {
     const float *carry_in;              // [S][2][HX_SRC_CARRY] case 4: the last intermediate samples formed, per channel
     float *carry_out;
     float *out;                         // [S][nframes * 1152][nch] fp32 at int16 scale
+    const int *nfr;                     // [S] the calls each stream makes of the launch's nframes, or null: all of them
     int nframes, nch, xwin, zwin;       // xwin / zwin: sample frames of the input / intermediate samples per call, at most
     int zoff, coff;                     // LDS floats before the intermediate samples / before the filter bank
     int *status;                        // the batch's status word (HX_SRC_STATUS_WINDOW)

@@ -11,8 +11,9 @@
 //    previous launch left (formed samples, not input: the previous call's pointer may have read bytes the next call's
 //    input does not hold); call f > 0 forms them again from call f - 1's input, as that call did.
 //  - the down-mix of case 2 is a recurrence within a call (a = a + b does not give the midpoint back in float): one lane.
-// The last call of a launch writes the carry and the call count to the other copy of each (the first call of the
-// launch reads the copy from before, so a one-call launch never reads what it writes).
+// A stream's last call of a launch (per stream: SrcArgs::nfr) writes the carry and the call count to the other copy of each
+// (the first call of the launch reads the copy from before, so a one-call launch never reads what it writes).  The copies
+// change roles with every launch, for the whole batch: a stream without a call in the launch copies both across.
 #include "hx_dev.h"
 #include "hx_src.h"
 
@@ -66,6 +67,20 @@ __global__ __launch_bounds__(256) void k_src(SrcArgs a)
 {
     extern __shared__ float src_lds[];
     const int s = blockIdx.x / a.nframes, f = blockIdx.x - s * a.nframes, tid = threadIdx.x;
+    // per-stream counts: the stream makes the first nn calls of the launch.  A workgroup beyond them leaves as a whole,
+    // before it reads the plan, an offset or a byte of the row (s, f and nn are uniform: no barrier is split).  A stream
+    // that sits the launch out has no last call, so its first workgroup hands the call count and the carried samples
+    // from the copy this launch reads to the copy the next one reads.
+    const int nn = a.nfr ? a.nfr[s] : a.nframes;
+    if (f >= nn) {
+        if (nn == 0 && f == 0) {
+            const float *cin = a.carry_in + (long long) s * 2 * HX_SRC_CARRY;
+            float *cout = a.carry_out + (long long) s * 2 * HX_SRC_CARRY;
+            for (int t = tid; t < 2 * HX_SRC_CARRY; t += 256) cout[t] = cin[t];
+            if (tid == 0) a.calls_out[s] = a.calls_in[s];
+        }
+        return;
+    }
     const HxSrcPlan *p = a.plan + a.cls[s];
     const int ncase = p->ncase, layout = p->layout, C = p->channels, bits = p->bits, is_float = p->is_float;
     const long long c0 = a.calls_in[s], c = c0 + f, i0 = 1152 * c;
@@ -201,7 +216,7 @@ __global__ __launch_bounds__(256) void k_src(SrcArgs a)
                 y[nc * t + ch] = acc;
             }
         }
-        if (f == a.nframes - 1) {
+        if (f == nn - 1) {
             float *cout = a.carry_out + (long long) s * 2 * HX_SRC_CARRY;
             for (int t = tid; t < HX_SRC_CARRY; t += 256)
                 for (int ch = 0; ch < nc; ch++) cout[ch * HX_SRC_CARRY + t] = zs[ch * a.zwin + nz - HX_SRC_CARRY + t];
@@ -209,5 +224,5 @@ __global__ __launch_bounds__(256) void k_src(SrcArgs a)
         break;
     }
     }
-    if (f == a.nframes - 1 && tid == 0) a.calls_out[s] = c0 + a.nframes;
+    if (f == nn - 1 && tid == 0) a.calls_out[s] = c0 + nn;
 }

@@ -208,9 +208,11 @@ int hx_batch_encode_f32_host_stats(hx_batch *b, const float *pcm, int nframes, u
    The rows, out_bytes, packets, counters and the dense image are written exactly as without it, by every kind of batch
    (MPEG-1 and MPEG-2, both builds of the rate-loop kernel, the first-generation allocator, converting batches through
    hx_batch_encode_src_device).
-   Not covered: hx_batch_encode_src_host and hx_multi_encode_src_host have no CRC argument (a CRC buffer set on a
-   converting batch is written by them like any other optional output), and the per-frame hx_enc_* calls keep the host
-   function hx_xing_update_crc. */
+   The converting host calls return it through the crc argument of hx_batch_encode_src_counts_host and
+   hx_multi_encode_src_counts_host (nfr = NULL for a uniform call); hx_batch_encode_src_host and hx_multi_encode_src_host
+   themselves have no CRC argument (a CRC buffer set on a converting batch is written by them like any other optional
+   output).
+   Not covered: the per-frame hx_enc_* calls keep the host function hx_xing_update_crc. */
 int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc);
 /* fp32 host call that returns the counters and the CRCs to host arrays stats[nstreams][nframes][2] and
    crc[nstreams][nframes]; both are required */
@@ -239,8 +241,9 @@ int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, uns
    host until the upload of the third call before it is done, which can be as long as the earlier calls' kernels on that
    stream take, and it cannot be made while its stream is being captured into a graph.  Calls without counts do neither.
    The setter either sets the counts or (-1) changes nothing, and leaves the calling thread's current device alone.
-   Not covered: converting batches (the setter returns -1 on them: their converter's schedule is per call), the hx_enc_*
-   encoder, and bench.py, which measures uniform calls. */
+   Converting batches take their counts per call, as an argument of hx_batch_encode_src_counts_* (below, with their
+   contract); this setter returns -1 on a converting batch.
+   Not covered: the hx_enc_* encoder, and bench.py, which measures uniform calls. */
 int hx_batch_frame_counts(hx_batch *b, const int *nfr);
 /* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
    The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
@@ -337,6 +340,35 @@ int hx_batch_encode_src_device(hx_batch *b, const unsigned char *d_in, long long
 int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
                              int nframes, unsigned char *out, long long out_stride, int *out_bytes,
                              long long *in_used, int *stats);
+/* ---- converting calls under per-stream frame counts: the counts come with the call, like frame_off and in_used ----
+   nfr: HOST array [nstreams], copied by the call; NULL = every stream takes nframes, which is exactly
+   hx_batch_encode_src_device / _host.  stats: NULL or [nstreams][nframes][2]; crc: NULL or [nstreams][nframes], the
+   per-frame MusicCRC as hx_batch_encode_f32_host_crc returns it; crc without stats is refused (-1) before anything runs.
+   With n = nfr[i]:
+     - refusals: a call with any n < 0 or n > nframes returns -1 before anything is allocated, copied, launched or
+       counted, and hx_last_error names the stream (hx_multi: by its number over all blocks, and no block starts).  After
+       a refusal the batch stays usable and hx_batch_src_schedule answers as before the call;
+     - input: stream i's row must hold the input of its first n calls - the extent check uses n, not nframes: without
+       frame_off the closed form at the stream's call c0 + n - 1, with frame_off the entries f < n only (entries f >= n may
+       hold anything, they are neither read nor checked).  n = 0: nothing of row i and none of its offsets is read.  Row
+       bytes beyond what those n calls read have no influence on any output or state;
+     - converter: the stream's converter advances n calls; in_used[i] is where call n would start (n = 0: 0); the
+       "srcpcm" tap holds frames f < n, the rest of the stream's row there is not written;
+     - n = 0: the converter's call count and its carried samples are unchanged, the stream's checkpoint
+       (hx_batch_get_stream_state, converter part included) is bit-identical before and after, out_bytes[i] = 0 and row i
+       is not written;
+     - rows, out_bytes, frame counters, packet sizes, MusicCRC, the dense image and the encoder state follow the rules of
+       hx_batch_frame_counts word for word: per stream it is the reference's MP3_audio_encode called n times.
+   The restrictions of plain calls under counts apply (three page-locked copies in rotation: the call may wait on the
+   host for the upload of the third call before it, and cannot be captured into a graph); calls with nfr = NULL have
+   neither.
+   Not covered: pipelined submits of converting batches, and *_host_dense calls for them. */
+int hx_batch_encode_src_counts_device(hx_batch *b, const unsigned char *d_in, long long in_stride, const long long *frame_off,
+                                      int nframes, const int *nfr, unsigned char *d_out, long long out_stride, int *d_out_bytes,
+                                      long long *in_used, void *stream);
+int hx_batch_encode_src_counts_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                    int nframes, const int *nfr, unsigned char *out, long long out_stride, int *out_bytes,
+                                    long long *in_used, int *stats, unsigned short *crc);
 
 /* ---- host placement (no reference equivalent): a host-fed GPU reads ~50 GB/s of PCM over PCIe, so its page-locked
    buffers and the threads that submit its copies belong on the NUMA node the device hangs on.
@@ -384,6 +416,11 @@ hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstreams, const 
 long long hx_multi_src_in_stride(const hx_multi *m, int nframes);
 int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
                              unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats);
+/* hx_batch_encode_src_counts_host over all streams: nfr [nstreams] or NULL, crc NULL or [nstreams][nframes] (needs stats).
+   A count out of range or a row too short for its stream's calls refuses the call for all blocks before any of them starts */
+int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                    const int *nfr, unsigned char *out, long long out_stride, int *out_bytes, long long *in_used,
+                                    int *stats, unsigned short *crc);
 
 /* ---- test taps (tests only; synchronise) ---- */
 /* name: "sb" "xr" "etab" "thr" "msbase" "bt" "eng" "dbg" (per-stage buffers), "ixq" "sgn" "seg" "frm" (what the allocator hands the
