@@ -358,6 +358,56 @@ class Batch:
         if lib().hx_batch_set_stream_state(self.h, i, buf) != 0:
             raise RuntimeError("hx_batch_set_stream_state failed: " + last_error())
 
+    def states_stride(self):
+        """blob_stride of the calls below: the blob size rounded up to 16"""
+        return int(lib().hx_batch_stream_states_stride(self.h))
+
+    def _slots(self, idx):
+        idx = [int(i) for i in idx]
+        return (C.c_int * max(len(idx), 1))(*idx), len(idx)
+
+    def reset_streams(self, idx, stream=None):
+        """every slot of idx starts a new stream (same configuration), in one launch, asynchronous on `stream` and ordered
+        like a plain device call (hx_batch_reset_streams)"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_reset_streams(self.h, arr, n, stream) != 0:
+            raise RuntimeError("hx_batch_reset_streams failed: " + last_error())
+
+    def get_stream_states(self, idx):
+        """checkpoints of the streams in idx, one launch and one copy -> list of bytes, blob e of slot idx[e]"""
+        arr, n = self._slots(idx)
+        stride, need = self.states_stride(), int(lib().hx_batch_stream_state_bytes(self.h))
+        buf = np.zeros(max(n, 1) * stride, dtype=np.uint8)
+        if lib().hx_batch_get_stream_states(self.h, arr, n, buf.ctypes.data, stride) != 0:
+            raise RuntimeError("hx_batch_get_stream_states failed: " + last_error())
+        return [buf[e * stride:e * stride + need].tobytes() for e in range(n)]
+
+    def set_stream_states(self, idx, blobs):
+        """blob e continues in slot idx[e]; all slots or (RuntimeError) none"""
+        arr, n = self._slots(idx)
+        stride, need = self.states_stride(), int(lib().hx_batch_stream_state_bytes(self.h))
+        if len(blobs) != n:
+            raise ValueError("%d blobs for %d slots" % (len(blobs), n))
+        buf = np.zeros(max(n, 1) * stride, dtype=np.uint8)
+        for e, blob in enumerate(blobs):
+            if len(blob) != need:
+                raise ValueError("stream state blob has %d bytes, this library's has %d" % (len(blob), need))
+            buf[e * stride:e * stride + need] = np.frombuffer(blob, dtype=np.uint8)
+        if lib().hx_batch_set_stream_states(self.h, arr, n, buf.ctypes.data, stride) != 0:
+            raise RuntimeError("hx_batch_set_stream_states failed: " + last_error())
+
+    def get_stream_states_device(self, idx, d_blobs_ptr, blob_stride, stream=None):
+        """the blobs into device memory [len(idx), blob_stride] (16-byte aligned), asynchronous on `stream`"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_get_stream_states_device(self.h, arr, n, d_blobs_ptr, blob_stride, stream) != 0:
+            raise RuntimeError("hx_batch_get_stream_states_device failed: " + last_error())
+
+    def set_stream_states_device(self, idx, d_blobs_ptr, blob_stride, stream=None):
+        """the reverse; a blob its slot does not take leaves the slot as it was and sets status bit 32"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_set_stream_states_device(self.h, arr, n, d_blobs_ptr, blob_stride, stream) != 0:
+            raise RuntimeError("hx_batch_set_stream_states_device failed: " + last_error())
+
     def set_gate(self, percent):
         lib().hx_batch_set_gate(self.h, percent)
 

@@ -460,3 +460,7 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
 
 // ---- the MusicCRC of a call's rows (hx_batch_crc_buffer): k_crc, a file of its own, built as part of this unit ----
 #include "hx_crc.hip"
+
+// ---- slot operations on many streams (hx_batch_reset_streams, hx_batch_get / set_stream_states*): k_slot_*, a file of its
+// own, built as part of this unit ----
+#include "hx_slots.hip"

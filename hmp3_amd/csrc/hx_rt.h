@@ -26,7 +26,7 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 
 #ifdef __HIPCC__
-// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip / hx_src.hip)
+// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip and hx_slots.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
 // nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
 // frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
@@ -55,6 +55,9 @@ __global__ void k_dense_off(const int *out_bytes, long long *off, long long *off
 __global__ void k_dense_gather(const unsigned char *out, long long out_stride, const int *out_bytes, const long long *off, unsigned char *dense,
                                long long cap, int chunks);
 __global__ void k_crc(const unsigned char *out, long long out_stride, const int *out_bytes, const int *stats, int nframes, unsigned short *crc);
+__global__ void k_slot_reset(SlotArgs a);
+__global__ void k_slot_gather(SlotArgs a, uint2 *blobs);
+__global__ void k_slot_scatter(SlotArgs a, const uint2 *blobs);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
 __global__ void k_alloc(AllocArgs a);
@@ -158,6 +161,19 @@ struct hx_batch {
     hipEvent_t ev_src_off = nullptr;    // the last upload of h_src_off is done
     int src_xwin = 0, src_zwin = 0, src_zoff = 0, src_coff = 0, src_lastF = 0;
     size_t src_lds = 0;
+    // slot operations (hx_batch_reset_streams, hx_batch_get / set_stream_states*): what a new stream of each class starts with
+    // and each class's blob fingerprint (made at create), of a converting batch each stream's plan fingerprint; the entry lists'
+    // page-locked staging and device copies, three of each in rotation (made at the first operation) - the host refills copy
+    // k when the operation three before, upload and kernel, is done; the host-blob calls' device staging
+    HxStream *d_init = nullptr;         // [ncls]
+    std::vector<unsigned long long> cls_fp;     // [ncls]
+    unsigned long long *d_src_fp = nullptr;     // [S]
+    HxSlotEntry *h_ent = nullptr, *d_ent = nullptr;     // [3][S] each
+    hipEvent_t ev_ent[3] = {nullptr, nullptr, nullptr};
+    long long nslotops = 0;
+    std::vector<long long> slot_mark;   // [S] the last operation that listed the slot (duplicates)
+    long long slot_serial = 0;
+    unsigned char *d_blobs = nullptr; long long blobs_cap = 0;
     bool debug = false;
     // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
@@ -298,6 +314,8 @@ HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, v
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
                          unsigned short *crc = nullptr);
+// a converting batch's per-stream plan fingerprints on the device, which the slot kernels check and write (hx_batch_create_src)
+HX_LOCAL int slots_src_init(hx_batch *b);
 // Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
 HX_LOCAL int drain(hx_batch *b);
 // the encode control of a converted source and its converter (hx_enc.cpp)

@@ -320,3 +320,30 @@ struct AllocArgs {
     HxSlot *slots;              // [S][frames per call + HX_SLOTS_EXTRA]
 };
 
+
+// ---- slot operations (hx_slots.hip: k_slot_reset / k_slot_gather / k_slot_scatter) ----
+// One listed slot of an operation: the slot, the receiving batch's class of it and the configuration fingerprint a
+// stream-state blob of it carries (gather) or must carry (scatter).
+struct HxSlotEntry { int slot, cls; unsigned long long cfg; };
+// A stream-state blob in 8-byte words, the unit the kernels move: header {magic, version | sizeof(HxStream), 0 | cfg}, HxStream,
+// three carried granules per channel, then (converting batches) plan fingerprint, call count and the carried samples.
+#define HX_SLOT_HDR_WORDS 3
+#define HX_SLOT_ST_WORDS ((int) (sizeof(HxStream) / 8))
+#define HX_SLOT_CARRY_WORDS (3 * 576 * 4 / 8)       // per channel
+#define HX_SLOT_VEC 4                               // words per lane
+#define HX_SLOT_CHUNK (256 * HX_SLOT_VEC)           // words per workgroup
+struct SlotArgs {
+    const HxSlotEntry *ent;     // [n], entry e = blockIdx.x / chunks
+    HxStream *st;               // [S]
+    const HxStream *init;       // [classes] the state a new stream of the class starts with (k_slot_reset)
+    float *sb;                  // the subband buffer; sb_row floats per (stream, channel), the carry in the first 3 * 576
+    long long sb_row;
+    long long *src_calls;       // converting batches: [2][S] call counts, [2][S][2][HX_SRC_CARRY] carried samples and [S] plan
+    float *src_carry;           // fingerprints; src_par = the copy the next call reads.  src_calls null: no converter part
+    const unsigned long long *src_fp;
+    int S, src_par;
+    unsigned magic, version;    // of the batch's kind of blob
+    int *status;                // bit 32: k_slot_scatter refused a blob
+    int chunks;                 // workgroups per entry
+    long long blob_words;       // blob_stride / 8
+};

@@ -127,6 +127,50 @@ int hx_batch_reset_stream(hx_batch *b, int i);
 long long hx_batch_stream_state_bytes(const hx_batch *b);
 int hx_batch_get_stream_state(hx_batch *b, int i, void *dst);
 int hx_batch_set_stream_state(hx_batch *b, int i, const void *src);
+/* ---- slot operations in stream order: reset, save, restore many streams at once (no reference equivalent) ----
+   The three calls above serve one slot each and wait for everything in flight.  These take a list of slots, do their work
+   in one kernel launch whatever n is, and are enqueued like a plain device call - a long-lived batch recycles slots between
+   two pipelined submits without a wait.
+   idx: HOST array of n distinct slots, copied by the call.  A blob array is [n][blob_stride] bytes; blob e belongs to
+   idx[e], not to the slot number.  Its first hx_batch_stream_state_bytes bytes are byte for byte what
+   hx_batch_get_stream_state writes for that slot, the bytes from there to blob_stride are written as zero, and nothing
+   at or beyond n * blob_stride is written.  blob_stride: a multiple of 16 and at least hx_batch_stream_state_bytes;
+   hx_batch_stream_states_stride is the smallest one.  A device blob array starts on a 16-byte boundary.
+   hx_batch_reset_streams: every listed slot starts a new stream of its configuration, as hx_batch_reset_stream does
+   (of a converting batch the converter too: its call count is 0 when the call returns, so hx_batch_src_schedule answers
+   as on a new batch).  The other slots are not touched.
+   Ordering: an operation is ordered like a plain device call.  It runs on `stream` behind everything the batch has in
+   flight.  After pipelined submits it first enqueues the packing that the last submit left for later - ungated, exactly
+   as hx_batch_wait does: that submit's output buffers must still be valid, and the batch is no longer "in flight"
+   afterwards.  Calls made on the batch afterwards see its effect under the same rule as plain calls: on the same stream,
+   or on streams the caller orders behind it.  Between two submits an operation costs that one step's packing overlap, and
+   nothing else.
+   Host waits: none but the staging's.  The list travels to the device through one of three page-locked staging copies:
+   an operation waits on the host until the operation three before it is done, which can be as long as the work that one
+   was ordered behind, and it cannot be made while its stream is being captured into a graph.
+   Refusals (-1, before anything is allocated, uploaded or launched; hx_last_error names the entry; the batch stays usable
+   and unchanged): a null batch, n < 0, a null idx with n > 0; a slot out of range or listed twice; a blob_stride below
+   hx_batch_stream_state_bytes or not a multiple of 16; a null blob array with n > 0, a device blob array that is not
+   16-byte aligned; a batch that became unusable.  n = 0 returns 0 and launches nothing.
+   Restored blobs: hx_batch_set_stream_states checks all n headers on the host first, with hx_batch_set_stream_state's
+   messages, and restores all slots or (-1) none.  hx_batch_set_stream_states_device cannot know: its kernel checks each
+   blob's header {magic of the batch's kind, format version, state size, configuration fingerprint of the slot}; a blob
+   that fails leaves its slot untouched and sets status bit 32 (hx_batch_status), the other listed slots are restored.
+   A restored stream's class index is the receiving batch's, as with hx_batch_set_stream_state.
+   The host-blob calls are synchronous like the single-slot calls (they wait for the work in flight), and make one gather /
+   scatter launch and one copy whatever n is.  On converting batches they carry the converter part.
+   Not covered: device blobs of converting batches - the two *_states_device calls return -1 there, because the host's
+   converter call counts are authoritative for hx_batch_src_schedule and the extent checks and a device blob cannot
+   update them without a wait; hx_multi_* (use hx_multi_batch), the hx_enc_* encoder and the command-line tool. */
+/* blob_stride of the calls below: hx_batch_stream_state_bytes rounded up to 16 */
+long long hx_batch_stream_states_stride(const hx_batch *b);
+/* idx: HOST array of n distinct slots, copied by the call.  Asynchronous on `stream`. */
+int hx_batch_reset_streams(hx_batch *b, const int *idx, int n, void *stream);
+int hx_batch_get_stream_states_device(hx_batch *b, const int *idx, int n, void *d_blobs, long long blob_stride, void *stream);
+int hx_batch_set_stream_states_device(hx_batch *b, const int *idx, int n, const void *d_blobs, long long blob_stride, void *stream);
+/* host blobs, synchronous: one gather / scatter launch and one copy, whatever n is */
+int hx_batch_get_stream_states(hx_batch *b, const int *idx, int n, void *blobs, long long blob_stride);
+int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *blobs, long long blob_stride);
 /* worst-case bytes one stream can emit in a call of nframes frames */
 long long hx_batch_out_stride(const hx_batch *b, int nframes);
 /* PCM: int16 interleaved L/R, [nstreams][nframes*1152][2]; out: [nstreams][out_stride] bytes;
@@ -285,7 +329,8 @@ int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *
 /* status bits accumulated by the kernels: 2 = main data overflow (the reference would assert
    there), 4 = the Huffman bits packed for a channel differ from the bits counted for it (an internal
    consistency check of the two-wave packer), 8 = a converter window out of bounds (converting batches), 16 = a dense image
-   did not fit its dense_cap (hx_batch_dense_buffers).  0 = healthy; -1 = no answer (the batch became unusable after a
+   did not fit its dense_cap (hx_batch_dense_buffers), 32 = hx_batch_set_stream_states_device was handed a blob its slot does
+   not take (that slot was left as it was).  0 = healthy; -1 = no answer (the batch became unusable after a
    failed device call, or the status could not be read).  Synchronises - and, like hx_batch_wait, first enqueues the
    packing that the last hx_batch_submit_*_device left for later: that writes the submit's output buffers (d_out,
    d_out_bytes and the packet buffer that was set at the submit), which must therefore still be valid.
