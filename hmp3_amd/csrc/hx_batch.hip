@@ -1,6 +1,6 @@
 // hx_batch.hip - the batch of the C ABI (include/hmp3_amd.h) and its launch sequence.
 // Owns the device buffers of a batch (subband carry, spectra, psy data, stream state), groups streams into
-// configuration classes and launches K1..K8: create / destroy, checkpoints, the pass, submits, host-buffer calls, reads.
+// configuration classes and launches K1..K8: create / destroy, the pass, submits, host-buffer calls, reads.
 #include <string>
 #include "hx_rt.h"
 
@@ -83,13 +83,9 @@ extern "C" void hx_batch_destroy(hx_batch *b)
     for (hipStream_t q : b->streams) hipStreamDestroy(q);
     for (hipEvent_t e : b->events) hipEventDestroy(e);
     for (auto &pr : b->pending) { hipEventDestroy(pr.first); hipEventDestroy(pr.second); }
-    if (b->h_src_off) hipHostFree(b->h_src_off);
-    if (b->h_nfr) hipHostFree(b->h_nfr);
-    if (b->h_ent) hipHostFree(b->h_ent);
+    for (void *p : b->pinned) hipHostFree(p);
     delete b;
 }
-
-static unsigned long long cfg_fingerprint(const HxParams &p);
 
 extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
 {
@@ -145,7 +141,6 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     ALLOC(b->d_prm, sizeof(HxParams) * b->ncls + 256);        // (k_spec reads a spreading row in 16-byte pieces, up to 60 bytes past its end)
     ALLOC(b->d_gt, sizeof(HxGlobalTabs));
     ALLOC(b->d_st, sizeof(HxStream) * S);
-    ALLOC(b->d_init, sizeof(HxStream) * b->ncls);
     ALLOC(b->d_sb, sizeof(float) * S * 2 * (NG + 3) * 576);
     ALLOC(b->d_lens, sizeof(int) * 4 * S);
     if (alloc_set(b, 0) != 0) { hx_batch_destroy(b); return nullptr; }
@@ -190,12 +185,7 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     HIPCHKN(hipMemcpy(b->d_prm, b->params.data(), sizeof(HxParams) * b->ncls, hipMemcpyHostToDevice));
     HIPCHKN(hipMemcpy(b->d_gt, &gt, sizeof(gt), hipMemcpyHostToDevice));
     HIPCHKN(hipMemcpy(b->d_st, st.data(), sizeof(HxStream) * S, hipMemcpyHostToDevice));
-    {   // what hx_batch_reset_streams copies into a slot, and what a blob of each class carries
-        std::vector<HxStream> init(b->ncls);
-        for (int k = 0; k < b->ncls; k++) { hx_stream_reset(&b->params[k], k, &init[k]); b->cls_fp.push_back(cfg_fingerprint(b->params[k])); }
-        HIPCHKN(hipMemcpy(b->d_init, init.data(), sizeof(HxStream) * b->ncls, hipMemcpyHostToDevice));
-        b->slot_mark.assign(nstreams, 0);
-    }
+    if (slots_init(b) != 0) { hx_batch_destroy(b); return nullptr; }
     HIPCHKN(hipMemset(b->d_sb, 0, sizeof(float) * S * 2 * (NG + 3) * 576));
     HIPCHKN(hipMemset(b->d_status, 0, sizeof(int)));
     b->lastNG = 0;
@@ -203,122 +193,6 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
 }
 
 extern "C" int hx_batch_nstreams(const hx_batch *b) { return b ? b->S : 0; }
-
-// Checkpoint of one stream: its HxStream record followed by the three carried subband granules of each
-// channel.  With it a stream continues in another slot, another batch of the same configuration, another GPU or
-// after a restart exactly where it stopped (the reference's equivalent is a copy of the CMp3Enc object).
-// The blob starts with a header {magic, format version, sizeof(HxStream), fingerprint of the stream's resolved
-// configuration}: a blob from another library build (other state layout) or saved under another control is
-// refused instead of silently yielding a corrupt bitstream.
-struct HxStateHeader { unsigned magic, version, state_bytes, pad; unsigned long long cfg; };
-#define HX_STATE_MAGIC 0x53335848u      // "HX3S"
-#define HX_STATE_VERSION 3u
-static unsigned long long cfg_fingerprint(const HxParams &p)
-{
-    unsigned long long h = 1469598103934665603ull;      // FNV-1a over the echoed control and the derived frame constants
-    auto mix = [&](const void *d, size_t n) { const unsigned char *c = (const unsigned char *) d; for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; } };
-    mix(&p.ec, sizeof(p.ec));
-    const int v[] = {p.totbitrate, p.samprate, p.h_mode, p.h_id, p.nchan, p.nsb_limit, p.band_limit, p.framebytes, p.main_framebytes, p.side_bytes,
-                     p.ms_flag, p.hf_flag, p.vbr_flag, p.initialMNR, p.short_block_threshold};
-    mix(v, sizeof(v));
-    return h;
-}
-// A converting batch's blob (another magic: neither kind takes the other's) also holds the converter: a fingerprint of its
-// plan, its call count and the case-4 intermediate samples it carries.
-#define HX_STATE_MAGIC_SRC 0x43335848u  // "HX3C"
-static const size_t HX_STATE_SRC_BYTES = 2 * sizeof(long long) + 2 * HX_SRC_CARRY * sizeof(float);
-static unsigned long long plan_fingerprint(const HxSrcPlan &p)
-{
-    unsigned long long h = 1469598103934665603ull;
-    const unsigned char *c = (const unsigned char *) &p;
-    for (size_t i = 0; i < sizeof(p); i++) { h ^= c[i]; h *= 1099511628211ull; }
-    return h;
-}
-extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b)
-{
-    return (long long) (sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float) + (b && b->nsrc ? HX_STATE_SRC_BYTES : 0));
-}
-
-// why slot i does not take the blob at `host` (hx_last_error is set), or 0
-static int blob_refused(const hx_batch *b, int i, const void *host, const char *prefix = "")
-{
-    const unsigned magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC;
-    const char *why = nullptr;
-    HxStateHeader in;
-    memcpy(&in, host, sizeof(in));
-    unsigned long long fp = 0;
-    if (b->nsrc) memcpy(&fp, (const char *) host + sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float), sizeof(fp));
-    if ((in.magic == HX_STATE_MAGIC) != (magic == HX_STATE_MAGIC) && (in.magic == HX_STATE_MAGIC || in.magic == HX_STATE_MAGIC_SRC))
-        why = b->nsrc ? "a stream-state blob of a batch without converter: a converting batch does not take it" : "a stream-state blob of a converting batch: this batch has no converter";
-    else if (in.magic != magic || in.version != HX_STATE_VERSION || in.state_bytes != (unsigned) sizeof(HxStream)) why = "not a stream-state blob of this library build";
-    else if (in.cfg != cfg_fingerprint(b->params[b->cls_of[i]])) why = "the stream state was saved under a different configuration than slot's";
-    else if (fp != (b->nsrc ? plan_fingerprint(b->src_plans[b->src_cls[i]]) : 0)) why = "the stream state was saved with a different converter (source format, rates or layout) than slot's";
-    if (!why) return 0;
-    set_err("%s", (std::string(prefix) + why).c_str());
-    return -1;
-}
-
-static int stream_state_copy(hx_batch *b, int i, void *host, bool save)
-{
-    if (!b || i < 0 || i >= b->S || !host) { set_err("bad arguments"); return -1; }
-    if (drain(b) != 0) return -1;
-    HxStateHeader hd = {b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC, HX_STATE_VERSION, (unsigned) sizeof(HxStream), 0, cfg_fingerprint(b->params[b->cls_of[i]])};
-    char *h = (char *) host + sizeof(HxStateHeader);
-    const size_t per = (size_t) (2 * b->maxF + 3) * 576;        // floats per (stream, channel) in the subband buffer
-    char *hs = h + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float);    // the converter's part (converting batches)
-    const unsigned long long pfp = b->nsrc ? plan_fingerprint(b->src_plans[b->src_cls[i]]) : 0;
-    if (save) memcpy(host, &hd, sizeof(hd));
-    else if (blob_refused(b, i, host) != 0) return -1;
-    if (b->nsrc) {
-        float *carry = b->d_src_carry + ((long long) b->src_par * b->S + i) * 2 * HX_SRC_CARRY;      // the copy the next call reads
-        if (save) {
-            memcpy(hs, &pfp, sizeof(pfp));
-            memcpy(hs + sizeof(pfp), &b->src_calls[i], sizeof(long long));
-            HIPCHK(hipMemcpy(hs + 2 * sizeof(long long), carry, 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyDeviceToHost));
-        } else {
-            memcpy(&b->src_calls[i], hs + sizeof(pfp), sizeof(long long));
-            for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &b->src_calls[i], sizeof(long long), hipMemcpyHostToDevice));
-            HIPCHK(hipMemcpy(carry, hs + 2 * sizeof(long long), 2 * HX_SRC_CARRY * sizeof(float), hipMemcpyHostToDevice));
-        }
-    }
-    if (save) {
-        HIPCHK(hipMemcpy(h, b->d_st + i, sizeof(HxStream), hipMemcpyDeviceToHost));
-        for (int c = 0; c < 2; c++)
-            HIPCHK(hipMemcpy(h + sizeof(HxStream) + (size_t) c * 3 * 576 * sizeof(float), b->d_sb + ((size_t) i * 2 + c) * per, 3 * 576 * sizeof(float), hipMemcpyDeviceToHost));
-    } else {
-        HxStream st;
-        memcpy(&st, h, sizeof(HxStream));
-        st.cls = b->cls_of[i];      // the class index is the receiving batch's
-        HIPCHK(hipMemcpy(b->d_st + i, &st, sizeof(HxStream), hipMemcpyHostToDevice));
-        for (int c = 0; c < 2; c++)
-            HIPCHK(hipMemcpy(b->d_sb + ((size_t) i * 2 + c) * per, h + sizeof(HxStream) + (size_t) c * 3 * 576 * sizeof(float), 3 * 576 * sizeof(float), hipMemcpyHostToDevice));
-    }
-    return 0;
-}
-extern "C" int hx_batch_get_stream_state(hx_batch *b, int i, void *dst) { return stream_state_copy(b, i, dst, true); }
-extern "C" int hx_batch_set_stream_state(hx_batch *b, int i, const void *src) { return stream_state_copy(b, i, (void *) src, false); }
-
-// Start a new stream in slot i (same configuration as the slot's previous stream): the state a freshly created
-// batch would have for it - reservoir, histories, allocator feedback, subband carry - so a long-lived batch can
-// take over new inputs as old ones end.  Waits for the work in flight; the other streams are not touched.
-extern "C" int hx_batch_reset_stream(hx_batch *b, int i)
-{
-    if (!b || i < 0 || i >= b->S) { set_err("stream index out of range"); return -1; }
-    if (drain(b) != 0) return -1;
-    HxStream *st = new HxStream;
-    hx_stream_reset(&b->params[b->cls_of[i]], b->cls_of[i], st);
-    hipError_t e = hipMemcpy(b->d_st + i, st, sizeof(HxStream), hipMemcpyHostToDevice);
-    delete st;
-    if (e != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e)); return -1; }
-    const size_t per = (size_t) (2 * b->maxF + 3) * 576 * sizeof(float);     // subband slots of one (stream, channel)
-    HIPCHK(hipMemset((char *) b->d_sb + (size_t) i * 2 * per, 0, 2 * per));
-    if (b->nsrc) {      // the converter starts over too (call 0 reads no carried samples)
-        const long long zero = 0;
-        b->src_calls[i] = 0;
-        for (int k = 0; k < 2; k++) HIPCHK(hipMemcpy(b->d_src_calls + (long long) k * b->S + i, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    }
-    return 0;
-}
 
 extern "C" long long hx_batch_out_stride(const hx_batch *b, int nframes)
 {
@@ -352,8 +226,7 @@ extern "C" int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc)
 // Per-stream frame counts of the calls that follow.  Only the host copy changes here: a call checks it against its nframes
 // (check_args) and uploads it for itself (encode_pass), so what is set later never reaches a call already made.
 // counts_reserve: everything that can fail - whether the batch takes counts at all, and (buffers) at the first use their
-// staging, events and device copies (a never-recorded event counts as done).  Each piece is made once: a call that fails half way leaves what it made to the next one (and
-// to hx_batch_destroy), which makes only the rest.  The calling thread's current device is left as it was.
+// staging (staging_make).  The calling thread's current device is left as it was.
 // counts_buffers: the second part alone - a converting batch, which the setter refuses, takes its counts as an argument of
 // hx_batch_encode_src_counts_* and needs the same staging.
 int counts_reserve(hx_batch *b, bool buffers)
@@ -364,15 +237,11 @@ int counts_reserve(hx_batch *b, bool buffers)
 }
 int counts_buffers(hx_batch *b)
 {
-    if (b->h_nfr && b->d_nfr && b->ev_nfr[2]) return 0;
+    if (b->nfr_stage.d) return 0;
     int dev0 = -1;
     HIPCHK(hipGetDevice(&dev0));
     HIPCHK(hipSetDevice(b->device));
-    int rc = 0;
-    if (!b->h_nfr && hipHostMalloc((void **) &b->h_nfr, sizeof(int) * 3 * (size_t) b->S, 0) != hipSuccess) { b->h_nfr = nullptr; set_err("hipHostMalloc failed"); rc = -1; }
-    for (int k = 0; k < 3 && rc == 0; k++)
-        if (!b->ev_nfr[k]) rc = new_event(b, b->ev_nfr[k]);
-    if (rc == 0 && !b->d_nfr) rc = dev_alloc(b, b->d_nfr, (long long) sizeof(int) * 3 * b->S);
+    const int rc = staging_make(b, b->nfr_stage, sizeof(int) * (size_t) b->S);
     (void) hipSetDevice(dev0);
     return rc;
 }
@@ -546,8 +415,7 @@ struct Pass {
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
 };
 
-// make stream q wait for everything submitted so far, the deferred packing included
-static int order_behind_submits(hx_batch *b, hipStream_t q)
+int order_behind_submits(hx_batch *b, hipStream_t q)
 {
     if (flush_pack(b, -1) != 0) return -1;
     const int last = (int) ((b->nsubmit - 1) & 1);
@@ -596,13 +464,12 @@ static int pipe_enter(hx_batch *b, Pass &p)
 // plain call, and no submit of a converting batch exists that it could follow): its record arrives with nfr set.
 static int counts_upload(hx_batch *b, int k, hipStream_t q, const int *&d_nfr)
 {
-    const size_t nb = sizeof(int) * (size_t) b->S;
-    int *h = b->h_nfr + (size_t) k * b->S, *d = b->d_nfr + (size_t) k * b->S;
-    HIPCHK(hipEventSynchronize(b->ev_nfr[k]));
-    memcpy(h, b->nfr.data(), nb);
-    HIPCHK(hipMemcpyAsync(d, h, nb, hipMemcpyHostToDevice, q));
-    HIPCHK(hipEventRecord(b->ev_nfr[k], q));
-    d_nfr = d;
+    Staging &s = b->nfr_stage;
+    void *h = staging_take(s, k);
+    if (!h) return -1;
+    memcpy(h, b->nfr.data(), s.bytes);
+    if (staging_upload(s, k, s.bytes, q) != 0 || staging_done(s, k, q) != 0) return -1;
+    d_nfr = s.dev<int>(k);
     return 0;
 }
 int counts_upload_plain(hx_batch *b, hipStream_t q, const int *&d_nfr)
@@ -1114,162 +981,3 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     return n;
 }
 
-
-// ---- slot operations in stream order: reset, save, restore many streams in one launch (hx_slots.hip) ----
-// An operation is ordered like a plain device call: on the caller's stream, behind everything the batch has in flight
-// (order_behind_submits: the deferred packing goes out ungated first), and without a host wait but the staging's.
-enum SlotOp { SLOT_RESET, SLOT_GATHER, SLOT_SCATTER };
-
-extern "C" long long hx_batch_stream_states_stride(const hx_batch *b)
-{
-    return b ? (hx_batch_stream_state_bytes(b) + 15) & ~15LL : 0;
-}
-
-// The refusals, made before anything is allocated, uploaded or launched; hx_last_error names the entry.
-// blobs: the operation moves blobs ([n][stride] at `blobs`; device: in device memory)
-static int slots_check(hx_batch *b, const int *idx, int n, bool blobs, const void *p_blobs, long long stride, bool device)
-{
-    char msg[160];
-    if (!b) { set_err("null batch"); return -1; }
-    if (check_poisoned(b) != 0) return -1;
-    if (n < 0) { snprintf(msg, sizeof msg, "n = %d: the number of listed slots cannot be negative", n); set_err("%s", msg); return -1; }
-    if (n > 0 && !idx) { set_err("idx is null with n > 0"); return -1; }
-    if (blobs && device && b->nsrc) {
-        set_err("a converting batch has no device-blob calls (the host's converter call counts are authoritative): use hx_batch_get / set_stream_states");
-        return -1;
-    }
-    if (blobs) {
-        if (stride < hx_batch_stream_state_bytes(b) || (stride & 15) != 0) {
-            snprintf(msg, sizeof msg, "blob_stride %lld: it must be a multiple of 16 and at least hx_batch_stream_state_bytes = %lld (hx_batch_stream_states_stride)",
-                     stride, hx_batch_stream_state_bytes(b));
-            set_err("%s", msg);
-            return -1;
-        }
-        if (n > 0 && !p_blobs) { set_err("the blob array is null with n > 0"); return -1; }
-        if (device && ((unsigned long long) p_blobs & 15) != 0) { set_err("d_blobs must be 16-byte aligned"); return -1; }
-    }
-    const long long serial = ++b->slot_serial;
-    for (int e = 0; e < n; e++) {
-        if (idx[e] < 0 || idx[e] >= b->S) {
-            snprintf(msg, sizeof msg, "entry %d: slot %d out of range (0 .. %d)", e, idx[e], b->S - 1);
-            set_err("%s", msg);
-            return -1;
-        }
-        if (b->slot_mark[idx[e]] == serial) {
-            snprintf(msg, sizeof msg, "entry %d: slot %d is listed twice", e, idx[e]);
-            set_err("%s", msg);
-            return -1;
-        }
-        b->slot_mark[idx[e]] = serial;
-    }
-    return 0;
-}
-
-// the entry lists' staging, events and device copies, made once (a call that fails half way leaves what it made to the next)
-static int slots_reserve(hx_batch *b)
-{
-    if (b->h_ent && b->d_ent && b->ev_ent[2]) return 0;
-    if (!b->h_ent && hipHostMalloc((void **) &b->h_ent, sizeof(HxSlotEntry) * 3 * (size_t) b->S, 0) != hipSuccess) { b->h_ent = nullptr; set_err("hipHostMalloc failed"); return -1; }
-    for (int k = 0; k < 3; k++)
-        if (!b->ev_ent[k] && new_event(b, b->ev_ent[k]) != 0) return -1;
-    return b->d_ent ? 0 : dev_alloc(b, b->d_ent, (long long) sizeof(HxSlotEntry) * 3 * b->S);
-}
-
-// a converting batch's per-stream plan fingerprints on the device (hx_batch_create_src)
-int slots_src_init(hx_batch *b)
-{
-    std::vector<unsigned long long> fp(b->S);
-    for (int s = 0; s < b->S; s++) fp[s] = plan_fingerprint(b->src_plans[b->src_cls[s]]);
-    if (dev_alloc(b, b->d_src_fp, (long long) sizeof(unsigned long long) * b->S) != 0) return -1;
-    HIPCHK(hipMemcpy(b->d_src_fp, fp.data(), sizeof(unsigned long long) * b->S, hipMemcpyHostToDevice));
-    return 0;
-}
-
-// One operation on stream q (arguments checked, n > 0).  The entry list goes up through staging copy k of three; the copy's
-// event is recorded behind the kernel that reads the device list, so refilling copy k three operations later waits for
-// that operation as a whole, whatever streams the operations in between were made on.
-static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs, long long stride, hipStream_t q)
-{
-    HIPCHK(hipSetDevice(b->device));
-    if (slots_reserve(b) != 0) return -1;
-    Poison poison{b};
-    if (b->inflight) {
-        if (order_behind_submits(b, q) != 0) return -1;
-        b->inflight = false;
-    }
-    const int k = (int) (b->nslotops++ % 3);
-    HxSlotEntry *h = b->h_ent + (size_t) k * b->S, *d = b->d_ent + (size_t) k * b->S;
-    HIPCHK(hipEventSynchronize(b->ev_ent[k]));
-    for (int e = 0; e < n; e++) h[e] = HxSlotEntry{idx[e], b->cls_of[idx[e]], b->cls_fp[b->cls_of[idx[e]]]};
-    HIPCHK(hipMemcpyAsync(d, h, sizeof(HxSlotEntry) * (size_t) n, hipMemcpyHostToDevice, q));
-    SlotArgs a;
-    a.ent = d; a.st = b->d_st; a.init = b->d_init; a.sb = b->d_sb; a.sb_row = (2LL * b->maxF + 3) * 576;
-    a.src_calls = b->nsrc ? b->d_src_calls : nullptr; a.src_carry = b->d_src_carry; a.src_fp = b->d_src_fp;
-    a.S = b->S; a.src_par = b->src_par;
-    a.magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC; a.version = HX_STATE_VERSION;
-    a.status = b->d_status;
-    a.blob_words = stride / 8;
-    const long long state_words = (hx_batch_stream_state_bytes(b) - (long long) sizeof(HxStateHeader)) / 8;
-    const long long words = op == SLOT_GATHER ? a.blob_words : op == SLOT_SCATTER ? state_words : state_words - (b->nsrc ? (long long) (2 * HX_SRC_CARRY * sizeof(float) / 8) : 0);      // (a reset leaves the converter's carried samples: call 0 reads none)
-    a.chunks = (int) ((words + HX_SLOT_CHUNK - 1) / HX_SLOT_CHUNK);
-    const dim3 grid((unsigned) ((long long) n * a.chunks));
-    if (op == SLOT_RESET) LAUNCH(k_slot_reset, grid, dim3(256), q, a);
-    else if (op == SLOT_GATHER) LAUNCH(k_slot_gather, grid, dim3(256), q, a, (uint2 *) d_blobs);
-    else LAUNCH(k_slot_scatter, grid, dim3(256), q, a, (const uint2 *) d_blobs);
-    HIPCHK(hipEventRecord(b->ev_ent[k], q));
-    return poison.ok();
-}
-
-extern "C" int hx_batch_reset_streams(hx_batch *b, const int *idx, int n, void *stream)
-{
-    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
-    if (n == 0) return 0;
-    if (slot_op(b, SLOT_RESET, idx, n, nullptr, 0, (hipStream_t) stream) != 0) return -1;
-    for (int e = 0; e < n && b->nsrc; e++) b->src_calls[idx[e]] = 0;        // (the converters start over: the host's count is the authoritative one)
-    return 0;
-}
-
-extern "C" int hx_batch_get_stream_states_device(hx_batch *b, const int *idx, int n, void *d_blobs, long long blob_stride, void *stream)
-{
-    if (slots_check(b, idx, n, true, d_blobs, blob_stride, true) != 0) return -1;
-    return n == 0 ? 0 : slot_op(b, SLOT_GATHER, idx, n, d_blobs, blob_stride, (hipStream_t) stream);
-}
-
-extern "C" int hx_batch_set_stream_states_device(hx_batch *b, const int *idx, int n, const void *d_blobs, long long blob_stride, void *stream)
-{
-    if (slots_check(b, idx, n, true, d_blobs, blob_stride, true) != 0) return -1;
-    return n == 0 ? 0 : slot_op(b, SLOT_SCATTER, idx, n, (void *) d_blobs, blob_stride, (hipStream_t) stream);
-}
-
-// The host-blob calls: synchronous like the single-slot calls (they wait for the work in flight first), but one launch and
-// one copy whatever n is, through device staging that grows with n.
-static int host_blobs(hx_batch *b, SlotOp op, const int *idx, int n, void *blobs, long long stride)
-{
-    if (slots_check(b, idx, n, true, blobs, stride, false) != 0) return -1;
-    if (n == 0) return 0;
-    if (op == SLOT_SCATTER)     // all or nothing: every header before anything is written
-        for (int e = 0; e < n; e++) {
-            char prefix[32];
-            snprintf(prefix, sizeof prefix, "entry %d: ", e);
-            if (blob_refused(b, idx[e], (const char *) blobs + (long long) e * stride, prefix) != 0) return -1;
-        }
-    if (drain(b) != 0) return -1;
-    const long long nb = (long long) n * stride;
-    if (dev_grow(b, b->d_blobs, b->blobs_cap, nb) != 0) return -1;
-    if (op == SLOT_SCATTER) HIPCHK(hipMemcpy(b->d_blobs, blobs, (size_t) nb, hipMemcpyHostToDevice));
-    if (slot_op(b, op, idx, n, b->d_blobs, stride, nullptr) != 0) return -1;
-    HIPCHK(hipStreamSynchronize(nullptr));
-    if (op == SLOT_GATHER) HIPCHK(hipMemcpy(blobs, b->d_blobs, (size_t) nb, hipMemcpyDeviceToHost));
-    else if (b->nsrc)
-        for (int e = 0; e < n; e++)
-            memcpy(&b->src_calls[idx[e]], (const char *) blobs + (long long) e * stride + sizeof(HxStateHeader) + sizeof(HxStream) + 2 * 3 * 576 * sizeof(float) + sizeof(long long), sizeof(long long));
-    return 0;
-}
-extern "C" int hx_batch_get_stream_states(hx_batch *b, const int *idx, int n, void *blobs, long long blob_stride)
-{
-    return host_blobs(b, SLOT_GATHER, idx, n, blobs, blob_stride);
-}
-extern "C" int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *blobs, long long blob_stride)
-{
-    return host_blobs(b, SLOT_SCATTER, idx, n, (void *) blobs, blob_stride);
-}

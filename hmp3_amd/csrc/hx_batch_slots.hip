@@ -1,0 +1,209 @@
+// hx_batch_slots.hip - slot state: everything that saves, restores or restarts a stream of a batch (kernels: hx_slots.hip).
+// A stream's checkpoint is its HxStream record and the three carried subband granules of each channel, of a converting batch
+// the converter's state too; the blob that carries it is laid out in hx_types.h (HxStateHeader and the HX_STATE_OFF_* parts).
+// With it a stream continues in another slot, another batch of the same configuration, another GPU or after a restart exactly
+// where it stopped (the reference's equivalent is a copy of the CMp3Enc object).
+// There is one implementation of each operation: a list of n slots, one launch.  The device-blob calls and
+// hx_batch_reset_streams enqueue it like a plain device call: on the caller's stream, behind everything the batch has in
+// flight (order_behind_submits: the deferred packing goes out ungated first), and without a host wait but the staging's.
+// The host-blob calls wait for the work in flight, run it on the null stream through device staging and wait again; the
+// single-slot calls are their n = 1 case.
+#include <string>
+#include "hx_rt.h"
+
+static unsigned long long fnv1a(const void *d, size_t n, unsigned long long h = 1469598103934665603ull)
+{
+    const unsigned char *c = (const unsigned char *) d;
+    for (size_t i = 0; i < n; i++) { h ^= c[i]; h *= 1099511628211ull; }
+    return h;
+}
+// over the echoed control and the derived frame constants
+static unsigned long long cfg_fingerprint(const HxParams &p)
+{
+    const int v[] = {p.totbitrate, p.samprate, p.h_mode, p.h_id, p.nchan, p.nsb_limit, p.band_limit, p.framebytes, p.main_framebytes, p.side_bytes,
+                     p.ms_flag, p.hf_flag, p.vbr_flag, p.initialMNR, p.short_block_threshold};
+    return fnv1a(v, sizeof(v), fnv1a(&p.ec, sizeof(p.ec)));
+}
+static unsigned long long plan_fingerprint(const HxSrcPlan &p) { return fnv1a(&p, sizeof(p)); }
+
+extern "C" long long hx_batch_stream_state_bytes(const hx_batch *b) { return (long long) (b && b->nsrc ? HX_STATE_END_SRC : HX_STATE_END); }
+extern "C" long long hx_batch_stream_states_stride(const hx_batch *b) { return b ? (hx_batch_stream_state_bytes(b) + 15) & ~15LL : 0; }
+
+// what hx_batch_reset_stream[s] copies into a slot, and what a blob of each class carries
+int slots_init(hx_batch *b)
+{
+    std::vector<HxStream> init(b->ncls);
+    for (int k = 0; k < b->ncls; k++) { hx_stream_reset(&b->params[k], k, &init[k]); b->cls_fp.push_back(cfg_fingerprint(b->params[k])); }
+    if (dev_alloc(b, b->d_init, sizeof(HxStream) * b->ncls) != 0) return -1;
+    HIPCHK(hipMemcpy(b->d_init, init.data(), sizeof(HxStream) * b->ncls, hipMemcpyHostToDevice));
+    b->slot_mark.assign(b->S, 0);
+    return 0;
+}
+int slots_src_init(hx_batch *b)
+{
+    std::vector<unsigned long long> fp(b->S);
+    for (int s = 0; s < b->S; s++) fp[s] = plan_fingerprint(b->src_plans[b->src_cls[s]]);
+    if (dev_alloc(b, b->d_src_fp, (long long) sizeof(unsigned long long) * b->S) != 0) return -1;
+    HIPCHK(hipMemcpy(b->d_src_fp, fp.data(), sizeof(unsigned long long) * b->S, hipMemcpyHostToDevice));
+    return 0;
+}
+
+// why slot i does not take the blob at `host` (hx_last_error is set), or 0
+static int blob_refused(const hx_batch *b, int i, const void *host, const char *prefix)
+{
+    const unsigned magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC;
+    const char *why = nullptr;
+    HxStateHeader in;
+    memcpy(&in, host, sizeof(in));
+    unsigned long long fp = 0;
+    if (b->nsrc) memcpy(&fp, (const char *) host + HX_STATE_OFF_SRC_FP, sizeof(fp));
+    if ((in.magic == HX_STATE_MAGIC) != (magic == HX_STATE_MAGIC) && (in.magic == HX_STATE_MAGIC || in.magic == HX_STATE_MAGIC_SRC))
+        why = b->nsrc ? "a stream-state blob of a batch without converter: a converting batch does not take it" : "a stream-state blob of a converting batch: this batch has no converter";
+    else if (in.magic != magic || in.version != HX_STATE_VERSION || in.state_bytes != (unsigned) sizeof(HxStream)) why = "not a stream-state blob of this library build";
+    else if (in.cfg != b->cls_fp[b->cls_of[i]]) why = "the stream state was saved under a different configuration than slot's";
+    else if (fp != (b->nsrc ? plan_fingerprint(b->src_plans[b->src_cls[i]]) : 0)) why = "the stream state was saved with a different converter (source format, rates or layout) than slot's";
+    if (!why) return 0;
+    set_err("%s", (std::string(prefix) + why).c_str());
+    return -1;
+}
+
+enum SlotOp { SLOT_RESET, SLOT_GATHER, SLOT_SCATTER };
+
+// The refusals, made before anything is allocated, uploaded or launched; hx_last_error names the entry.
+// blobs: the operation moves blobs ([n][stride] at `blobs`; device: in device memory)
+static int slots_check(hx_batch *b, const int *idx, int n, bool blobs, const void *p_blobs, long long stride, bool device)
+{
+    char msg[160];
+#define REFUSE(...) do { snprintf(msg, sizeof msg, __VA_ARGS__); set_err("%s", msg); return -1; } while (0)
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (n < 0) REFUSE("n = %d: the number of listed slots cannot be negative", n);
+    if (n > 0 && !idx) { set_err("idx is null with n > 0"); return -1; }
+    if (blobs && device && b->nsrc) {
+        set_err("a converting batch has no device-blob calls (the host's converter call counts are authoritative): use hx_batch_get / set_stream_states");
+        return -1;
+    }
+    if (blobs) {
+        if (stride < hx_batch_stream_state_bytes(b) || (stride & 15) != 0)
+            REFUSE("blob_stride %lld: it must be a multiple of 16 and at least hx_batch_stream_state_bytes = %lld (hx_batch_stream_states_stride)", stride, hx_batch_stream_state_bytes(b));
+        if (n > 0 && !p_blobs) { set_err("the blob array is null with n > 0"); return -1; }
+        if (device && ((unsigned long long) p_blobs & 15) != 0) { set_err("d_blobs must be 16-byte aligned"); return -1; }
+    }
+    const long long serial = ++b->slot_serial;
+    for (int e = 0; e < n; e++) {
+        if (idx[e] < 0 || idx[e] >= b->S) REFUSE("entry %d: slot %d out of range (0 .. %d)", e, idx[e], b->S - 1);
+        if (b->slot_mark[idx[e]] == serial) REFUSE("entry %d: slot %d is listed twice", e, idx[e]);
+        b->slot_mark[idx[e]] = serial;
+    }
+#undef REFUSE
+    return 0;
+}
+
+// One operation on stream q (arguments checked, n > 0).  The entry list goes up through staging copy k of three, in a
+// rotation of the slot operations' own; the copy's event is recorded behind the kernel that reads the device list, so
+// refilling copy k three operations later waits for that operation as a whole, whatever streams the operations in between
+// were made on.
+static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs, long long stride, hipStream_t q)
+{
+    HIPCHK(hipSetDevice(b->device));
+    Staging &s = b->ent_stage;
+    if (!s.d && staging_make(b, s, sizeof(HxSlotEntry) * (size_t) b->S) != 0) return -1;
+    Poison poison{b};
+    if (b->inflight) {
+        if (order_behind_submits(b, q) != 0) return -1;
+        b->inflight = false;
+    }
+    const int k = (int) (b->nslotops++ % 3);
+    HxSlotEntry *h = (HxSlotEntry *) staging_take(s, k);
+    if (!h) return -1;
+    for (int e = 0; e < n; e++) h[e] = HxSlotEntry{idx[e], b->cls_of[idx[e]], b->cls_fp[b->cls_of[idx[e]]]};
+    if (staging_upload(s, k, sizeof(HxSlotEntry) * (size_t) n, q) != 0) return -1;
+    SlotArgs a;
+    a.ent = s.dev<HxSlotEntry>(k); a.st = b->d_st; a.init = b->d_init; a.sb = b->d_sb; a.sb_row = (2LL * b->maxF + 3) * 576;
+    a.src_calls = b->nsrc ? b->d_src_calls : nullptr; a.src_carry = b->d_src_carry; a.src_fp = b->d_src_fp;
+    a.S = b->S; a.src_par = b->src_par;
+    a.magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC; a.version = HX_STATE_VERSION;
+    a.status = b->d_status;
+    a.blob_words = stride / 8;
+    // words behind the header that the kernel walks (a reset leaves the converter's carried samples: call 0 reads none)
+    const long long state_words = b->nsrc ? HX_SLOT_SRC_CARRY_WORD + HX_SLOT_SRC_CARRY_WORDS : HX_SLOT_SRC_WORD;
+    const long long words = op == SLOT_GATHER ? a.blob_words : op == SLOT_SCATTER ? state_words : b->nsrc ? HX_SLOT_SRC_CARRY_WORD : HX_SLOT_SRC_WORD;
+    a.chunks = (int) ((words + HX_SLOT_CHUNK - 1) / HX_SLOT_CHUNK);
+    const dim3 grid((unsigned) ((long long) n * a.chunks));
+    if (op == SLOT_RESET) LAUNCH(k_slot_reset, grid, dim3(256), q, a);
+    else if (op == SLOT_GATHER) LAUNCH(k_slot_gather, grid, dim3(256), q, a, (uint2 *) d_blobs);
+    else LAUNCH(k_slot_scatter, grid, dim3(256), q, a, (const uint2 *) d_blobs);
+    if (staging_done(s, k, q) != 0) return -1;
+    return poison.ok();
+}
+
+// A reset of n slots on stream q; wait (hx_batch_reset_stream): behind everything in flight, and done when it returns.
+static int reset_slots(hx_batch *b, const int *idx, int n, hipStream_t q, bool wait)
+{
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n == 0) return 0;
+    if (wait && drain(b) != 0) return -1;
+    if (slot_op(b, SLOT_RESET, idx, n, nullptr, 0, q) != 0) return -1;
+    for (int e = 0; e < n && b->nsrc; e++) b->src_calls[idx[e]] = 0;        // (the converters start over: the host's count is the authoritative one)
+    if (wait) HIPCHK(hipStreamSynchronize(q));
+    return 0;
+}
+extern "C" int hx_batch_reset_streams(hx_batch *b, const int *idx, int n, void *stream) { return reset_slots(b, idx, n, (hipStream_t) stream, false); }
+extern "C" int hx_batch_reset_stream(hx_batch *b, int i) { return reset_slots(b, &i, 1, nullptr, true); }
+
+extern "C" int hx_batch_get_stream_states_device(hx_batch *b, const int *idx, int n, void *d_blobs, long long blob_stride, void *stream)
+{
+    if (slots_check(b, idx, n, true, d_blobs, blob_stride, true) != 0) return -1;
+    return n == 0 ? 0 : slot_op(b, SLOT_GATHER, idx, n, d_blobs, blob_stride, (hipStream_t) stream);
+}
+extern "C" int hx_batch_set_stream_states_device(hx_batch *b, const int *idx, int n, const void *d_blobs, long long blob_stride, void *stream)
+{
+    if (slots_check(b, idx, n, true, d_blobs, blob_stride, true) != 0) return -1;
+    return n == 0 ? 0 : slot_op(b, SLOT_SCATTER, idx, n, (void *) d_blobs, blob_stride, (hipStream_t) stream);
+}
+
+// The host-blob calls: synchronous (they wait for the work in flight first), one launch and one copy whatever n is, through
+// device staging [n][stride] that grows with n.  A restore is all or nothing: every header is checked on the host before
+// anything is written, so no blob of it can set status bit 32.  What crosses between the staging and the caller's memory is
+// the blobs up to the end of the last one's state and not a byte more; the list form of a save writes the zeros from there to
+// the stride on the host.  one (the single-slot calls): the caller's buffer ends with the state - no zeros behind it - and
+// a refusal names no entry.
+static int host_blobs(hx_batch *b, SlotOp op, const int *idx, int n, void *blobs, long long stride, bool one)
+{
+    if (slots_check(b, idx, n, true, blobs, stride, false) != 0) return -1;
+    if (n == 0) return 0;
+    for (int e = 0; e < n && op == SLOT_SCATTER; e++) {
+        char prefix[32] = "";
+        if (!one) snprintf(prefix, sizeof prefix, "entry %d: ", e);
+        if (blob_refused(b, idx[e], (const char *) blobs + (long long) e * stride, prefix) != 0) return -1;
+    }
+    if (drain(b) != 0) return -1;
+    const long long need = hx_batch_stream_state_bytes(b), nb = (long long) (n - 1) * stride + need;
+    if (dev_grow(b, b->d_blobs, b->blobs_cap, (long long) n * stride) != 0) return -1;
+    if (op == SLOT_SCATTER) HIPCHK(hipMemcpy(b->d_blobs, blobs, (size_t) nb, hipMemcpyHostToDevice));
+    if (slot_op(b, op, idx, n, b->d_blobs, stride, nullptr) != 0) return -1;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    if (op == SLOT_GATHER) {
+        HIPCHK(hipMemcpy(blobs, b->d_blobs, (size_t) nb, hipMemcpyDeviceToHost));
+        if (!one) memset((char *) blobs + nb, 0, (size_t) (stride - need));
+    }
+    for (int e = 0; e < n && op == SLOT_SCATTER && b->nsrc; e++)        // (the host's converter call count is the authoritative one)
+        memcpy(&b->src_calls[idx[e]], (const char *) blobs + (long long) e * stride + HX_STATE_OFF_SRC_CALLS, sizeof(long long));
+    return 0;
+}
+extern "C" int hx_batch_get_stream_states(hx_batch *b, const int *idx, int n, void *blobs, long long blob_stride)
+{
+    return host_blobs(b, SLOT_GATHER, idx, n, blobs, blob_stride, false);
+}
+extern "C" int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *blobs, long long blob_stride)
+{
+    return host_blobs(b, SLOT_SCATTER, idx, n, (void *) blobs, blob_stride, false);
+}
+extern "C" int hx_batch_get_stream_state(hx_batch *b, int i, void *dst)
+{
+    return host_blobs(b, SLOT_GATHER, &i, 1, dst, hx_batch_stream_states_stride(b), true);
+}
+extern "C" int hx_batch_set_stream_state(hx_batch *b, int i, const void *src)
+{
+    return host_blobs(b, SLOT_SCATTER, &i, 1, (void *) src, hx_batch_stream_states_stride(b), true);
+}

@@ -64,7 +64,7 @@ extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CO
     ALLOC_SRC(b->d_src_pcm, sizeof(float) * S * max_frames * 1152 * b->nchan);
     ALLOC_SRC(b->d_src_off, sizeof(long long) * S * max_frames);
 #undef ALLOC_SRC
-    if (hipHostMalloc((void **) &b->h_src_off, sizeof(long long) * S * max_frames, 0) != hipSuccess) { b->h_src_off = nullptr; set_err("hipHostMalloc failed"); hx_batch_destroy(b); return nullptr; }
+    if (host_alloc(b, b->h_src_off, sizeof(long long) * S * max_frames) != 0) { hx_batch_destroy(b); return nullptr; }
     if (new_event(b, b->ev_src_off) != 0 || slots_src_init(b) != 0 ||
         hipMemcpy(b->d_src_plan, plans.data(), sizeof(HxSrcPlan) * plans.size(), hipMemcpyHostToDevice) != hipSuccess ||
         hipMemcpy(b->d_src_cls, cls.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess ||

@@ -1,6 +1,7 @@
 // hx_rt.h - what the units of the host runtime share: the batch, its error / allocation helpers, the kernels' prototypes
 // and the few entry points one unit needs of another.  Units: hx_batch.hip (the batch and its passes), hx_batch_src.hip
-// (converting batches), hx_enc.cpp (the single-stream encoder), hx_multi.cpp (several devices behind one handle).
+// (converting batches), hx_batch_slots.hip (slot state: reset, save, restore), hx_enc.cpp (the single-stream encoder),
+// hx_multi.cpp (several devices behind one handle).
 #pragma once
 #ifdef __HIPCC__
 #include <hip/hip_runtime.h>
@@ -108,9 +109,19 @@ struct Call {
     unsigned char *out = nullptr; long long out_stride = 0; int *out_bytes = nullptr;
     OptOut opt;
     const int *nfr = nullptr;           // device copy of the per-stream frame counts in force when the call was made (encode_pass
-                                        // uploads it: hx_batch::d_nfr; a converting call under counts has, in front of k_src),
+                                        // uploads it: hx_batch::nfr_stage; a converting call under counts has, in front of k_src),
                                         // null = every stream takes the call's nframes
     unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
+};
+
+// Three staging copies in rotation for a small list that a call hands to its kernels: page-locked host memory and device
+// memory, [3][bytes] each, and one event per copy that says when the copy's last user is done (operations below, behind
+// dev_alloc).  Which copy a call takes, and behind what it records the event, is the call's own business.
+struct Staging {
+    char *h = nullptr, *d = nullptr;
+    size_t bytes = 0;
+    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};     // (a never-recorded event counts as done)
+    template <class T> T *dev(int k) const { return (T *) (d + (size_t) k * bytes); }
 };
 
 struct hx_batch {
@@ -139,12 +150,11 @@ struct hx_batch {
     unsigned long long *d_prof = nullptr;
     int lastNG = 0;                     // NG of the previous call (the debug taps' row stride)
     // per-stream frame counts (hx_batch_frame_counts; of a converting batch the counts of the hx_batch_encode_src_counts_*
-    // call being made, empty between calls): the host copy a call checks and takes (empty = uniform calls), its
-    // page-locked staging and the device copies, three of each in rotation with the sets of signs - a device-buffer submit's
-    // deferred packing still reads its copy while two later submits are in flight
+    // call being made, empty between calls): the host copy a call checks and takes (empty = uniform calls) and its
+    // staging, [S] counts per copy, in rotation with the sets of signs - a device-buffer submit's deferred packing still
+    // reads its copy while two later submits are in flight.  A copy's event: the upload out of it is done.
     std::vector<int> nfr;
-    int *h_nfr = nullptr, *d_nfr = nullptr;     // [3][S] each
-    hipEvent_t ev_nfr[3] = {nullptr, nullptr, nullptr};    // the upload out of staging copy k is done
+    Staging nfr_stage;
     long long nplain = 0;               // plain calls made under counts (they rotate the copies too: no call waits for its predecessor's upload)
     // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
     int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
@@ -163,13 +173,12 @@ struct hx_batch {
     size_t src_lds = 0;
     // slot operations (hx_batch_reset_streams, hx_batch_get / set_stream_states*): what a new stream of each class starts with
     // and each class's blob fingerprint (made at create), of a converting batch each stream's plan fingerprint; the entry lists'
-    // page-locked staging and device copies, three of each in rotation (made at the first operation) - the host refills copy
-    // k when the operation three before, upload and kernel, is done; the host-blob calls' device staging
+    // staging, [S] HxSlotEntry per copy (made at the first operation) - the host refills copy k when the operation three
+    // before, upload and kernel, is done; the host-blob calls' device staging
     HxStream *d_init = nullptr;         // [ncls]
     std::vector<unsigned long long> cls_fp;     // [ncls]
     unsigned long long *d_src_fp = nullptr;     // [S]
-    HxSlotEntry *h_ent = nullptr, *d_ent = nullptr;     // [3][S] each
-    hipEvent_t ev_ent[3] = {nullptr, nullptr, nullptr};
+    Staging ent_stage;
     long long nslotops = 0;
     std::vector<long long> slot_mark;   // [S] the last operation that listed the slot (duplicates)
     long long slot_serial = 0;
@@ -227,8 +236,9 @@ struct hx_batch {
     int park_k = 8;                     // HMP3AMD_PARK: the CUs of this many longest streams are kept free of other kernels' workgroups (0 = off; see hx_alloc3.inc, "parking")
     int park_pair = 0;                  // HMP3AMD_PARK_PAIR=1: also the CU that shares the instruction cache with a straggler's
     int strict_sums = 0;                // HMP3AMD_EXACT_SUMS=1: the stream walk adds every band in line order instead of certifying a parallel sum (tests)
-    // everything the batch allocates or creates on the device (dev_alloc, new_stream, new_event): hx_batch_destroy releases it
-    std::vector<void *> mem;
+    // everything the batch allocates or creates on the device (dev_alloc, new_stream, new_event) and its page-locked host
+    // memory (host_alloc): hx_batch_destroy releases it
+    std::vector<void *> mem, pinned;
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> events;
 };
@@ -261,8 +271,41 @@ template <class T> static int dev_grow(hx_batch *b, T *&p, long long &cap, long 
     cap = bytes;
     return 0;
 }
+template <class T> static int host_alloc(hx_batch *b, T *&p, size_t bytes)
+{
+    void *q = nullptr;
+    if (hipHostMalloc(&q, bytes, 0) != hipSuccess) { set_err("hipHostMalloc failed"); return -1; }
+    b->pinned.push_back(q);
+    p = (T *) q;
+    return 0;
+}
 HX_LOCAL int new_stream(hx_batch *b, hipStream_t &q, int priority = INT_MAX);     // (INT_MAX: the runtime's default priority)
 HX_LOCAL int new_event(hx_batch *b, hipEvent_t &e);
+
+// A Staging's four operations.  make: its pieces, `bytes` per copy, each made once - a call that fails half way leaves what
+// it made to the next one (and to hx_batch_destroy), which makes only the rest.  take: wait on the host until copy k's event
+// is done and hand out its host memory to fill (null: the wait failed).  upload: the first n bytes of copy k to the device
+// on stream q.  done: copy k's event on stream q.
+static inline int staging_make(hx_batch *b, Staging &s, size_t bytes)
+{
+    s.bytes = bytes;
+    if (!s.h && host_alloc(b, s.h, 3 * bytes) != 0) return -1;
+    for (int k = 0; k < 3; k++)
+        if (!s.ev[k] && new_event(b, s.ev[k]) != 0) return -1;
+    return s.d ? 0 : dev_alloc(b, s.d, (long long) (3 * bytes));
+}
+static inline void *staging_take(Staging &s, int k)
+{
+    const hipError_t e = hipEventSynchronize(s.ev[k]);
+    if (e != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e)); return nullptr; }
+    return s.h + (size_t) k * s.bytes;
+}
+static inline int staging_upload(Staging &s, int k, size_t n, hipStream_t q)
+{
+    HIPCHK(hipMemcpyAsync(s.dev<char>(k), s.h + (size_t) k * s.bytes, n, hipMemcpyHostToDevice, q));
+    return 0;
+}
+static inline int staging_done(Staging &s, int k, hipStream_t q) { HIPCHK(hipEventRecord(s.ev[k], q)); return 0; }
 
 // A launch or HIP call that fails once a pass has touched the batch leaves events unrecorded, buffer sets half handed
 // over or staging half updated: the batch is not reusable (this only happens on a device error).  A pass holds one of
@@ -314,8 +357,13 @@ HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, v
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
                          unsigned short *crc = nullptr);
-// a converting batch's per-stream plan fingerprints on the device, which the slot kernels check and write (hx_batch_create_src)
+// Slot state (hx_batch_slots.hip), set up at create: what a new stream of each class starts with, each class's blob
+// fingerprint and the duplicate marks (hx_batch_create); a converting batch's per-stream plan fingerprints on the device,
+// which the slot kernels check and write (hx_batch_create_src)
+HX_LOCAL int slots_init(hx_batch *b);
 HX_LOCAL int slots_src_init(hx_batch *b);
+// make stream q wait for everything submitted so far, the deferred packing included
+HX_LOCAL int order_behind_submits(hx_batch *b, hipStream_t q);
 // Wait until everything enqueued on the batch is done, the deferred packing of the last device-buffer submit included.
 HX_LOCAL int drain(hx_batch *b);
 // the encode control of a converted source and its converter (hx_enc.cpp)

@@ -1,9 +1,9 @@
-// hx_slots.hip - K9: slot operations on many streams of a batch in one launch (hx_batch_reset_streams,
-// hx_batch_get / set_stream_states*): k_slot_reset, k_slot_gather, k_slot_scatter.  Built as part of hx_pack.hip's unit.
+// hx_slots.hip - K9: slot operations on one or many streams of a batch in one launch (hx_batch_slots.hip: every reset, save
+// and restore): k_slot_reset, k_slot_gather, k_slot_scatter.  Built as part of hx_pack.hip's unit.
 //
 // Pure data movers, no LDS.  Grid (entry, chunk): workgroup e * chunks + c handles 8-byte words [c * HX_SLOT_CHUNK, ...) of
 // entry e, HX_SLOT_VEC words per lane, all loads of a lane issued before its stores.  The unit is the 8-byte word (dwordx2):
-// HxStream sits sizeof(header) = 24 bytes into a blob whose base is 16-byte aligned, so the blob side of every copy is
+// HxStream sits sizeof(HxStateHeader) = 24 bytes into a blob whose base is 16-byte aligned, so the blob side of every copy is
 // 8-byte aligned and no more, while the batch side (d_st rows, subband rows, converter carry) is 16-byte aligned.  With
 // dwordx2 both sides are aligned as they stand and a wave still covers 512 contiguous bytes per instruction; the other
 // choice - dwordx4 on the batch side, two aligned vectors funnelled on the blob side as k_dense_gather does - halves the
@@ -11,14 +11,9 @@
 // What a kernel may touch: the listed slots' HxStream, slots 0..2 of their subband rows, their converter words, and bytes
 // [0, n * blob_stride) of the blob array.  The host has checked that every slot is in range and listed once.
 #include "hx_dev.h"
-#include "hx_src.h"
 
-static_assert(sizeof(HxStream) % 8 == 0, "the slot kernels move HxStream in 8-byte words");
 static_assert(sizeof(HxSlotEntry) == 16, "the host stages the entries as 16-byte records");
-static_assert((2 * HX_SRC_CARRY * sizeof(float)) % 8 == 0, "the converter's carried samples are moved in 8-byte words");
-
-#define HX_SLOT_SRC_CARRY_WORDS ((int) (2 * HX_SRC_CARRY * sizeof(float) / 8))
-#define HX_SLOT_SRC_WORD (HX_SLOT_ST_WORDS + 2 * HX_SLOT_CARRY_WORDS)   // first word of the converter part, counted from HxStream
+static_assert(HX_SLOT_SRC_WORD == HX_SLOT_ST_WORDS + 2 * HX_SLOT_CARRY_WORDS, "slot_word walks the parts in the blob's order (hx_types.h)");
 
 __device__ __forceinline__ uint2 slot_split(unsigned long long v) { return make_uint2((unsigned) v, (unsigned) (v >> 32)); }
 __device__ __forceinline__ unsigned long long slot_join(uint2 v) { return (unsigned long long) v.x | ((unsigned long long) v.y << 32); }
@@ -34,7 +29,7 @@ __device__ __forceinline__ uint2 *slot_word(const SlotArgs &a, int slot, int w)
         const int ch = w >= HX_SLOT_CARRY_WORDS;
         return reinterpret_cast<uint2 *>(a.sb + ((long long) slot * 2 + ch) * a.sb_row) + (w - ch * HX_SLOT_CARRY_WORDS);
     }
-    w -= 2 * HX_SLOT_CARRY_WORDS + 2;
+    w -= HX_SLOT_SRC_CARRY_WORD - HX_SLOT_ST_WORDS;
     if (a.src_calls && w >= 0 && w < HX_SLOT_SRC_CARRY_WORDS)
         return reinterpret_cast<uint2 *>(a.src_carry + ((long long) a.src_par * a.S + slot) * 2 * HX_SRC_CARRY) + w;
     return nullptr;
@@ -63,8 +58,8 @@ __global__ __launch_bounds__(256) void k_slot_reset(SlotArgs a)
     }
 }
 
-// Blob e of blobs [n][blob_words] = the stream-state blob of entry e's slot, byte for byte what hx_batch_get_stream_state
-// writes, and zeros from the blob's end to the stride.
+// Blob e of blobs [n][blob_words] = the stream-state blob of entry e's slot (layout: hx_types.h), and zeros from the blob's
+// end to the stride.
 __global__ __launch_bounds__(256) void k_slot_gather(SlotArgs a, uint2 *__restrict__ blobs)
 {
     const int e = blockIdx.x / a.chunks, c = blockIdx.x - e * a.chunks;
@@ -76,9 +71,9 @@ __global__ __launch_bounds__(256) void k_slot_gather(SlotArgs a, uint2 *__restri
         const int w = c * HX_SLOT_CHUNK + 256 * k + (int) threadIdx.x, ws = w - HX_SLOT_HDR_WORDS;
         v[k] = make_uint2(0, 0);
         if (w >= a.blob_words) continue;
-        if (w == 0) v[k] = make_uint2(a.magic, a.version);
-        else if (w == 1) v[k] = make_uint2((unsigned) sizeof(HxStream), 0);
-        else if (w == 2) v[k] = slot_split(en.cfg);
+        if (w == HX_SLOT_HDR_MAGIC) v[k] = make_uint2(a.magic, a.version);
+        else if (w == HX_SLOT_HDR_STATE_BYTES) v[k] = make_uint2((unsigned) sizeof(HxStream), 0);
+        else if (w == HX_SLOT_HDR_CFG) v[k] = slot_split(en.cfg);
         else if (const uint2 *p = slot_word(a, en.slot, ws)) v[k] = *p;
         else if (a.src_calls && ws == HX_SLOT_SRC_WORD) v[k] = slot_split(a.src_fp[en.slot]);
         else if (a.src_calls && ws == HX_SLOT_SRC_WORD + 1) v[k] = slot_split((unsigned long long) a.src_calls[(long long) a.src_par * a.S + en.slot]);
@@ -99,14 +94,14 @@ __global__ __launch_bounds__(256) void k_slot_scatter(SlotArgs a, const uint2 *_
     const int e = blockIdx.x / a.chunks, c = blockIdx.x - e * a.chunks;
     const HxSlotEntry en = a.ent[e];
     const uint2 *src = blobs + (long long) e * a.blob_words;
-    const uint2 h0 = src[0], h1 = src[1], h2 = src[2];
-    bool ok = h0.x == a.magic && h0.y == a.version && h1.x == (unsigned) sizeof(HxStream) && slot_join(h2) == en.cfg;
+    const uint2 magic_version = src[HX_SLOT_HDR_MAGIC], state_bytes = src[HX_SLOT_HDR_STATE_BYTES], cfg = src[HX_SLOT_HDR_CFG];
+    bool ok = magic_version.x == a.magic && magic_version.y == a.version && state_bytes.x == (unsigned) sizeof(HxStream) && slot_join(cfg) == en.cfg;
     if (a.src_calls) ok = ok && slot_join(src[HX_SLOT_HDR_WORDS + HX_SLOT_SRC_WORD]) == a.src_fp[en.slot];
     if (!ok) {
         if (c == 0 && threadIdx.x == 0) atomicOr(a.status, 32);
         return;
     }
-    const int nw = HX_SLOT_SRC_WORD + (a.src_calls ? 2 + HX_SLOT_SRC_CARRY_WORDS : 0);      // words of state behind the header
+    const int nw = a.src_calls ? HX_SLOT_SRC_CARRY_WORD + HX_SLOT_SRC_CARRY_WORDS : HX_SLOT_SRC_WORD;      // words of state behind the header
     uint2 v[HX_SLOT_VEC];
 #pragma unroll
     for (int k = 0; k < HX_SLOT_VEC; k++) {

@@ -2,6 +2,8 @@
 // MI355X batched MP3 encoder.  Domain names follow the reference (granule, sfb, part2_3...).
 #pragma once
 #include <stdint.h>
+#include <stddef.h>
+#include "hx_src.h"
 
 // Same field order as the reference's E_CONTROL (pub/encapp.h:42-72): passed verbatim
 // through the C-ABI.
@@ -325,11 +327,39 @@ struct AllocArgs {
 // One listed slot of an operation: the slot, the receiving batch's class of it and the configuration fingerprint a
 // stream-state blob of it carries (gather) or must carry (scatter).
 struct HxSlotEntry { int slot, cls; unsigned long long cfg; };
-// A stream-state blob in 8-byte words, the unit the kernels move: header {magic, version | sizeof(HxStream), 0 | cfg}, HxStream,
-// three carried granules per channel, then (converting batches) plan fingerprint, call count and the carried samples.
+// A stream-state blob, the one description of its layout.  A header {magic of the batch's kind, format version,
+// sizeof(HxStream), 0, fingerprint of the stream's resolved configuration}: a blob from another library build (other state
+// layout) or saved under another control is refused instead of silently yielding a corrupt bitstream.  Then the parts, each
+// at its byte offset: HxStream, the three carried subband granules of channels 0 and 1, and (a converting batch's blob: another
+// magic, neither kind takes the other's) the converter's plan fingerprint, call count and carried case-4 samples.
+struct HxStateHeader { unsigned magic, version, state_bytes, pad; unsigned long long cfg; };
+#define HX_STATE_MAGIC 0x53335848u          // "HX3S"
+#define HX_STATE_MAGIC_SRC 0x43335848u      // "HX3C"
+#define HX_STATE_VERSION 3u
+#define HX_STATE_CARRY_BYTES (3 * 576 * sizeof(float))       // per channel
+#define HX_STATE_SRC_CARRY_BYTES (2 * HX_SRC_CARRY * sizeof(float))
+#define HX_STATE_OFF_STREAM sizeof(HxStateHeader)
+#define HX_STATE_OFF_CARRY (HX_STATE_OFF_STREAM + sizeof(HxStream))
+#define HX_STATE_END (HX_STATE_OFF_CARRY + 2 * HX_STATE_CARRY_BYTES)      // the end of a plain batch's blob
+#define HX_STATE_OFF_SRC_FP HX_STATE_END
+#define HX_STATE_OFF_SRC_CALLS (HX_STATE_OFF_SRC_FP + sizeof(unsigned long long))
+#define HX_STATE_OFF_SRC_CARRY (HX_STATE_OFF_SRC_CALLS + sizeof(long long))
+#define HX_STATE_END_SRC (HX_STATE_OFF_SRC_CARRY + HX_STATE_SRC_CARRY_BYTES)      // the end of a converting batch's
+// ... and in 8-byte words, the unit the kernels move.  The header's words by the fields they hold: {magic, version},
+// {state_bytes, pad}, cfg; the parts behind it are counted from the start of HxStream.
 #define HX_SLOT_HDR_WORDS 3
+#define HX_SLOT_HDR_MAGIC ((int) (offsetof(HxStateHeader, magic) / 8))
+#define HX_SLOT_HDR_STATE_BYTES ((int) (offsetof(HxStateHeader, state_bytes) / 8))
+#define HX_SLOT_HDR_CFG ((int) (offsetof(HxStateHeader, cfg) / 8))
 #define HX_SLOT_ST_WORDS ((int) (sizeof(HxStream) / 8))
-#define HX_SLOT_CARRY_WORDS (3 * 576 * 4 / 8)       // per channel
+#define HX_SLOT_CARRY_WORDS ((int) (HX_STATE_CARRY_BYTES / 8))      // per channel
+#define HX_SLOT_SRC_WORD ((int) ((HX_STATE_OFF_SRC_FP - HX_STATE_OFF_STREAM) / 8))     // plan fingerprint; the call count is the next word
+#define HX_SLOT_SRC_CARRY_WORD ((int) ((HX_STATE_OFF_SRC_CARRY - HX_STATE_OFF_STREAM) / 8))
+#define HX_SLOT_SRC_CARRY_WORDS ((int) (HX_STATE_SRC_CARRY_BYTES / 8))
+static_assert(sizeof(HxStateHeader) == 8 * HX_SLOT_HDR_WORDS && offsetof(HxStateHeader, version) == 8 * HX_SLOT_HDR_MAGIC + 4 &&
+              offsetof(HxStateHeader, pad) == 8 * HX_SLOT_HDR_STATE_BYTES + 4, "the header is three 8-byte words: {magic, version}, {state_bytes, pad}, cfg");
+static_assert(HX_STATE_OFF_STREAM % 8 == 0 && HX_STATE_OFF_CARRY % 8 == 0 && HX_STATE_CARRY_BYTES % 8 == 0 && HX_STATE_OFF_SRC_FP % 8 == 0 &&
+              HX_STATE_OFF_SRC_CALLS % 8 == 0 && HX_STATE_OFF_SRC_CARRY % 8 == 0 && HX_STATE_END_SRC % 8 == 0, "every part of a blob starts on an 8-byte boundary");
 #define HX_SLOT_VEC 4                               // words per lane
 #define HX_SLOT_CHUNK (256 * HX_SLOT_VEC)           // words per workgroup
 struct SlotArgs {

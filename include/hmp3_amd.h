@@ -117,13 +117,20 @@ hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int 
 void hx_batch_destroy(hx_batch *b);
 int hx_batch_nstreams(const hx_batch *b);
 /* start a new stream in slot i with the slot's configuration (the state CMp3Enc::L3_audio_encode_init leaves,
-   mp3enc.cpp:278-287, 788-837); waits for work in flight, leaves the other streams alone */
+   mp3enc.cpp:278-287, 788-837); waits for work in flight, leaves the other streams alone.  It is the one-slot form of
+   hx_batch_reset_streams below - the same launch, the same refusals - made synchronous: done when it returns.  Like the
+   list call it zeroes the slot's three carried subband granules and not the rest of its subband rows, which no kernel
+   reads before a later call has rewritten them: the output is a new batch's, and the one place where the slot differs
+   from a new batch's is the "sb" debug tap beyond the carry. */
 int hx_batch_reset_stream(hx_batch *b, int i);
 /* checkpoint / resume of one stream (header + encoder state + subband carry, hx_batch_stream_state_bytes bytes):
    what is saved from slot i continues, after hx_batch_set_stream_state, in any slot of any batch created with
    the same control for that slot (any size, any max_frames) - another GPU or a later process included.  src
    must hold hx_batch_stream_state_bytes bytes; a blob of another library build or saved under another
-   control is refused (-1, hx_last_error). */
+   control is refused (-1, hx_last_error), on the host, before anything is copied or launched.
+   The two calls are the one-slot form of hx_batch_get / set_stream_states below (one launch, one copy, the same
+   refusals), except that dst / src hold hx_batch_stream_state_bytes bytes, not the list calls' stride: no byte beyond
+   them is read or written. */
 long long hx_batch_stream_state_bytes(const hx_batch *b);
 int hx_batch_get_stream_state(hx_batch *b, int i, void *dst);
 int hx_batch_set_stream_state(hx_batch *b, int i, const void *src);
@@ -157,8 +164,8 @@ int hx_batch_set_stream_state(hx_batch *b, int i, const void *src);
    blob's header {magic of the batch's kind, format version, state size, configuration fingerprint of the slot}; a blob
    that fails leaves its slot untouched and sets status bit 32 (hx_batch_status), the other listed slots are restored.
    A restored stream's class index is the receiving batch's, as with hx_batch_set_stream_state.
-   The host-blob calls are synchronous like the single-slot calls (they wait for the work in flight), and make one gather /
-   scatter launch and one copy whatever n is.  On converting batches they carry the converter part.
+   The host-blob calls are synchronous (they wait for the work in flight), and make one gather / scatter launch and one
+   copy whatever n is; the single-slot calls are their n = 1 case.  On converting batches they carry the converter part.
    Not covered: device blobs of converting batches - the two *_states_device calls return -1 there, because the host's
    converter call counts are authoritative for hx_batch_src_schedule and the extent checks and a device blob cannot
    update them without a wait; hx_multi_* (use hx_multi_batch), the hx_enc_* encoder and the command-line tool. */

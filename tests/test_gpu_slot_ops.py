@@ -6,6 +6,7 @@ a signal around one of its noise bursts, so that the reservoir, the pending-fram
 hold something when a slot is saved.  Expected bytes are the oracle's; blobs are compared bit for bit."""
 import ctypes as C
 import functools
+import struct
 
 import numpy as np
 import pytest
@@ -124,15 +125,141 @@ def test_reset_between_pipelined_submits_without_a_wait(counts, k6_build):
     b.close()
 
 
+def test_single_slot_reset_over_stale_subband_slots(k6_build):
+    """hx_batch_reset_stream zeroes subband slots 0..2 like the list call: a 7-frame call, two slots reset one by one, then
+    2-frame calls of new input - the subband slots the long call wrote lie beyond the short calls' extent.  The reset slots
+    encode the new input from scratch, the others continue"""
+    F1, F2, reset = 7, 2, [4, 1]
+    b = api().Batch(controls(), nstreams=S, max_frames=7)
+    out1 = b.encode_host(cut(1500, F1))
+    for i in reset:
+        b.reset_stream(i)
+    new = cut(1600, 2 * F2)
+    out2 = [x + y for x, y in zip(b.encode_host(new[:, :F2 * 1152]), b.encode_host(new[:, F2 * 1152:]))]
+    assert b.status() == 0
+    for i in range(S):
+        assert (out1[i], out2[i]) == expected(i, F1, 2 * F2, i in reset), i
+    b.close()
+
+
+HEADER = struct.Struct("<IIIIQ")        # HxStateHeader: magic, format version, sizeof(HxStream), 0, configuration fingerprint
+CARRY = 3 * 576 * 4                     # bytes of the three carried subband granules of one channel
+
+
+def ints(v):
+    return (C.c_int * max(len(v), 1))(*v), len(v)
+
+
+def saved_both_ways(b, idx):
+    """the blobs of the slots in idx from the list call - nothing is written behind the array, every blob ends in zeros up to
+    the stride - and from the single-slot call, which gives the same bytes -> the blobs"""
+    need, stride = int(api().lib().hx_batch_stream_state_bytes(b.h)), b.states_stride()
+    arr, n = ints(idx)
+    buf = np.full(n * stride + 64, 0xA5, np.uint8)
+    assert api().lib().hx_batch_get_stream_states(b.h, arr, n, buf.ctypes.data, stride) == 0, api().last_error()
+    assert (buf[n * stride:] == 0xA5).all()
+    blobs = []
+    for e, i in enumerate(idx):
+        blob = buf[e * stride:(e + 1) * stride]
+        assert not blob[need:].any(), (e, i)
+        blobs.append(blob[:need].tobytes())
+        assert blobs[e] == b.get_stream_state(i), (e, i)
+    return blobs
+
+
+def header_state_carry(b, i, blob, magic, max_frames):
+    """blob = header {magic, 3, sizeof(HxStream), 0, cfg}, row i of the "state" tap, slots 0..2 of both channels of row i of the
+    "sb" tap, the rest -> (cfg, the rest)"""
+    n = b.n
+    state = b.debug_read("state", np.uint8, 1 << 22)
+    st = len(state) // n
+    row = (2 * max_frames + 3) * 576
+    sb = b.debug_read("sb", np.float32, n * 2 * row).reshape(n, 2, row)
+    assert len(state) == n * st and blob[:4] == magic
+    m, version, state_bytes, pad, cfg = HEADER.unpack(blob[:HEADER.size])
+    assert (version, state_bytes, pad) == (3, st, 0)
+    assert blob[HEADER.size:HEADER.size + st] == state[i * st:(i + 1) * st].tobytes(), i
+    assert blob[HEADER.size + st:HEADER.size + st + 2 * CARRY] == sb[i, :, :3 * 576].tobytes(), i
+    return cfg, blob[HEADER.size + st + 2 * CARRY:]
+
+
+@functools.lru_cache(maxsize=None)
+def converting_streams():
+    """six sources over two converter plans and configurations: 48 kHz -> 44.1 kHz (case 4, carried samples) and 44.1 -> 32 kHz"""
+    from test_gpu_src_batch import Stream
+    return [Stream(*((48000, 16, 0) if i % 2 == 0 else (44100, 16, 0)), mpeg_select=44100 if i % 2 == 0 else 32000, seed=60 + i, seconds=1.0)
+            for i in range(S)]
+
+
 @pytest.mark.one_k6_build
 @pytest.mark.parametrize("idx", [[4, 0, 3], [2], list(range(S))], ids=["three", "one", "all"])
 def test_gather_equals_the_single_slot_call(idx):
+    """what a blob holds, after two uneven calls, against the batch's debug taps; the list form and the single-slot form give
+    the same bytes.  A plain batch of three classes; a converting batch of two plans, whose blob goes on with the plan's
+    fingerprint, the stream's converter call count and the carried samples"""
+    from test_gpu_src_counts import make_rows
     b = api().Batch(controls(), nstreams=S, max_frames=7)
-    b.encode_host(cut(1500, 5))
-    got = b.get_stream_states(idx)
-    assert len(got) == len(idx)
+    for seed, F, counts in ((1500, 5, [5, 2, 4, 0, 3, 5]), (1600, 3, [2, 3, 0, 3, 1, 2])):
+        b.frame_counts(counts)
+        b.encode_host(cut(seed, F))
+    blobs = saved_both_ways(b, idx)
     for e, i in enumerate(idx):
-        assert got[e] == b.get_stream_state(i), (e, i)
+        cfg, rest = header_state_carry(b, i, blobs[e], b"HX3S", 7)
+        assert rest == b"", i
+    cfgs = [HEADER.unpack(x[:HEADER.size])[4] for x in all_blobs(b)]
+    for i in range(S):
+        for j in range(S):
+            assert (cfgs[i] == cfgs[j]) == (i % 3 == j % 3), (i, j)
+    assert b.status() == 0
+    b.close()
+
+    from test_gpu_src_batch import make_batch
+    streams = converting_streams()
+    b = make_batch(streams, 7)
+    pos, done = [0] * S, [0] * S
+    for F, counts in ((5, [5, 2, 4, 0, 3, 5]), (3, [2, 3, 0, 3, 1, 2])):
+        _, used = b.encode_src_counts_host(make_rows(b, streams, pos, F, counts), F, counts)
+        pos = [p + int(u) for p, u in zip(pos, used)]
+        done = [d + c for d, c in zip(done, counts)]
+
+    def converter_words(idx):
+        out = {}
+        for i, blob in zip(idx, saved_both_ways(b, idx)):
+            cfg, rest = header_state_carry(b, i, blob, b"HX3C", 7)
+            assert len(rest) == 16 + 2 * 192 * 4, i     # plan fingerprint, call count, HX_SRC_CARRY samples per channel
+            out[i] = (cfg,) + struct.unpack("<Qq", rest[:16])
+        return out
+    got = converter_words(idx)
+    for i in idx:
+        assert got[i][2] == done[i], i
+        for j in idx:
+            assert (got[i][1] == got[j][1]) == (i % 2 == j % 2) and (got[i][0] == got[j][0]) == (i % 2 == j % 2), (i, j)
+    b.reset_stream(idx[0])
+    b.reset_streams(idx[1:])
+    assert all(v[2] == 0 for v in converter_words(idx).values())
+    assert b.status() == 0
+    b.close()
+
+
+@pytest.mark.one_k6_build
+@pytest.mark.parametrize("kind", ["plain", "converting"])
+def test_single_slot_save_writes_no_byte_beyond_the_state(kind):
+    """hx_batch_get_stream_state into a buffer of hx_batch_stream_state_bytes + 64 bytes: the state, and the 64 bytes behind it
+    untouched (the list form's blob goes on with zeros up to its stride; the single-slot call's buffer ends with the state)"""
+    from test_gpu_src_batch import make_batch
+    L = api().lib()
+    if kind == "plain":
+        b = api().Batch(controls(), nstreams=S, max_frames=7)
+        b.encode_host(cut(1500, 4))
+    else:
+        b = make_batch(converting_streams(), 7)
+    need = int(L.hx_batch_stream_state_bytes(b.h))
+    assert need < b.states_stride()
+    for i in (0, S - 1):
+        buf = (C.c_ubyte * (need + 64))(*([0xA5] * (need + 64)))
+        assert L.hx_batch_get_stream_state(b.h, i, buf) == 0, api().last_error()
+        assert bytes(buf[need:]) == b"\xA5" * 64, i
+        assert bytes(buf[:need]) == b.get_stream_states([i])[0], i
     assert b.status() == 0
     b.close()
 
@@ -182,6 +309,44 @@ def test_scatter_into_another_batch():
 
 
 @pytest.mark.one_k6_build
+@pytest.mark.parametrize("kind", ["plain", "converting"])
+def test_single_slot_and_list_forms_cross(kind):
+    """streams saved with the single-slot call are restored with the list call and the other way round, into other slots of a
+    second batch, and continue there over two calls as if nothing had happened"""
+    if kind == "plain":
+        F1, F2 = 5, 6
+        b1 = api().Batch(api().default_control(**KW4), nstreams=4, max_frames=5)
+        out1 = b1.encode_host(cut(1700, F1, 44100, n=4))
+        single, listed = [b1.get_stream_state(i) for i in (0, 1)], b1.get_stream_states([2, 3])
+        b1.close()
+        b2 = api().Batch(api().default_control(**KW4), nstreams=6, max_frames=7)
+        b2.set_stream_states(PLACE[:2], single)
+        for slot, blob in zip(PLACE[2:], listed):
+            b2.set_stream_state(slot, blob)
+        pcm2 = moved_second_call(F1, F2, PLACE, 6)
+        out2 = [x + y for x, y in zip(b2.encode_host(pcm2[:, :4 * 1152]), b2.encode_host(pcm2[:, 4 * 1152:]))]
+        assert b2.status() == 0
+        for i, slot in enumerate(PLACE):
+            assert (out1[i], out2[slot]) == moved_expected(i, F1, F2), i
+        b2.close()
+        return
+    from test_gpu_src_batch import Stream, make_batch, run
+    s0, s1 = (Stream(48000, 16, 0, mpeg_select=44100, seed=k, seconds=1.0) for k in (41, 42))
+    b1 = make_batch([s0, s1], 8)
+    o1, p1, _ = run(b1, [s0, s1], [6])
+    single, listed = b1.get_stream_state(0), b1.get_stream_states([1])[0]
+    b1.close()
+    b2 = make_batch([s0, s0, s0], 7)
+    b2.set_stream_states([2], [single])
+    b2.set_stream_state(0, listed)
+    o2, _, _ = run(b2, [s1, s0, s0], [3, 2], pos=[p1[1], 0, p1[0]])
+    assert o1[0] + o2[2] == s0.per_frame(11)[0]
+    assert o1[1] + o2[0] == s1.per_frame(11)[0]
+    assert o2[1] == s0.per_frame(5)[0]
+    b2.close()
+
+
+@pytest.mark.one_k6_build
 def test_device_blobs_move_streams_without_a_host_wait():
     """gather into a device buffer, scatter into another batch and that batch's next call, all on one stream: the bytes
     continue, nothing beyond n * blob_stride is written, a blob's tail up to the stride is zero, and the blobs are the
@@ -221,10 +386,6 @@ def test_device_blobs_move_streams_without_a_host_wait():
         assert blob[:need].tobytes() == host[e], e
         assert not blob[need:].any(), e
     b1.close(); b2.close()
-
-
-def ints(v):
-    return (C.c_int * max(len(v), 1))(*v), len(v)
 
 
 @pytest.mark.one_k6_build
