@@ -940,10 +940,31 @@ extern "C" HX_INT_PAIR hx_batch_frames_bytes(hx_batch *b, int i)
     return r;
 }
 
+// For tests: ix^(4/3) as the device's pow() returns it, the expression of pow43_beyond (hx_alloc.hip) and of the short-block
+// noise measurement (hx_alloc_short.inc), for ix = first .. first + n - 1.  The only kernel of this unit.
+__global__ void k_debug_pow43(double *out, int first, int n)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = pow((double) (first + i), (4.0 / 3.0));
+}
+
+static long long debug_pow43(void *dst, long long cap)
+{
+    const long long n = cap / (long long) sizeof(double);
+    if (n <= 0 || n > (1LL << 24)) return -1;
+    double *d = nullptr;
+    if (hipMalloc(&d, sizeof(double) * n) != hipSuccess) return -1;
+    hipLaunchKernelGGL(k_debug_pow43, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, 0, d, HX_POW43_N, (int) n);
+    const hipError_t e = hipMemcpy(dst, d, sizeof(double) * n, hipMemcpyDeviceToHost);
+    (void) hipFree(d);
+    return e == hipSuccess ? (long long) sizeof(double) * n : -1;
+}
+
 extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap)
 {
     if (!b || !name || !dst) return -1;
     (void) drain(b);
+    if (!strcmp(name, "pow43_beyond")) return debug_pow43(dst, cap);      // double [cap / 8]: the device's pow(ix, 4/3), ix = HX_POW43_N + i
     const long long S = b->S, NG = b->lastNG;
     const FrontSet &f = b->front[0];
     const WalkSet &w = b->walk[0];

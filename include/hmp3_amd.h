@@ -190,7 +190,10 @@ int hx_batch_encode_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, u
 int hx_batch_encode_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out,
                              long long out_stride, int *out_bytes);
 /* the same for fp32 PCM at int16 scale (+-32768), the form CMp3Enc::L3_audio_encode takes
-   (pub/mp3enc.h:90-98; a1 of the path: srcc.cpp:805-808 scales [-1,1) floats by 32768 first) */
+   (pub/mp3enc.h:90-98; a1 of the path: srcc.cpp:805-808 scales [-1,1) floats by 32768 first).
+   Samples are not limited to that scale: the bytes are the reference's for any finite value, and the tests check it from
+   float32's subnormal range (which the kernels keep: no flush to zero) up to 2^16 x full scale.  NaN and infinite samples
+   are outside what the reference defines. */
 int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
                                long long out_stride, int *d_out_bytes, void *stream);
 int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out,

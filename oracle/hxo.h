@@ -164,6 +164,11 @@ typedef struct {
     int main_bytes;
 } hxo_frame_debug;
 
+/* what the noise measurement (noise_actual of the long and of the short allocator) saw beyond the 256-entry float table
+   of ix^(4/3) since hxo_init: the lines dequantised through pow(), those of them quantised to 16384 or more, the largest
+   quantised value.  For tests that must know an input reached that path; the encoder never reads them. */
+typedef struct { long long beyond_table, from_16384; int max_qx; } hxo_range_counts;
+
 typedef struct hxo_encoder {
     hxo_params p;
     hxo_state s;
@@ -171,6 +176,7 @@ typedef struct hxo_encoder {
     hxo_frame_debug *dbg;
     unsigned char *packet;      /* set for the duration of hxo_encode_frame_packet */
     int packet_bytes, packet_bytes2[2];    /* MPEG-2: two packets per call, back to back */
+    hxo_range_counts range[2];  /* [0] long blocks, [1] short blocks */
 } hxo_encoder;
 void hxo_set_debug(hxo_encoder *e, hxo_frame_debug *d);
 int hxo_sizeof_frame_debug(void);
@@ -188,6 +194,8 @@ int hxo_encode_frame_s16(hxo_encoder *e, const int16_t *pcm, unsigned char *out)
 int hxo_encode_frame_packet(hxo_encoder *e, const float *pcm, unsigned char *out, unsigned char *packet, int nbytes[2]);
 unsigned hxo_frames_out(const hxo_encoder *e);
 unsigned hxo_bytes_out(const hxo_encoder *e);
+/* short_blocks = 0 / 1 -> out = { beyond_table, from_16384, max_qx } of that allocator's noise measurement */
+void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3]);
 void hxo_default_control(hxo_control *ec);      /* test/tomp3.cpp:357-384 */
 int hxo_sizeof_encoder(void);
 
@@ -195,6 +203,7 @@ int hxo_sizeof_encoder(void);
 int   hxo_mblog(float x);                       /* l3math.c:228 */
 float hxo_mbexp(int mb);                        /* l3math.c:342 */
 void  hxo_pow34(const float *x, float *y, int n);   /* pow34.c:132 */
+void  hxo_pow43(int first, int n, double *out);     /* pow(ix, 4/3) as l3math.c:527 calls it, ix = first .. first + n - 1 */
 void  hxo_polyphase_granule(const hxo_params *p, const float *vbuf, float *samp);   /* sbt.c:293 */
 void  hxo_freq_invert(float *samp, int nsb);    /* hwin.c:282 */
 void  hxo_hybrid_long(const hxo_params *p, const float *prev, const float *cur, float *xr, int btype, int nsb, int clear); /* hwin.c:147 */

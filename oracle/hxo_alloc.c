@@ -62,7 +62,7 @@ static void set_limits(ba_t *b, int ch, int scale, int pre)
 
 /* ---- l3math.c vector helpers ---- */
 /* l3math.c:512-541: quantise a band at gain step gsf, dequantise, return noise power in mB */
-static int noise_actual(const hxo_params *p, const float *x34, const float *x, int gsf, int n, int logn)
+static int noise_actual(const hxo_params *p, hxo_range_counts *rc, const float *x34, const float *x, int gsf, int n, int logn)
 {
     float sxx = 0.0f, igain = p->look_34igain[gsf], gain = p->look_gain[gsf], xhat, tmp;
     int i, qx;
@@ -70,11 +70,23 @@ static int noise_actual(const hxo_params *p, const float *x34, const float *x, i
         tmp = (igain * x34[i] + (0.0f - 0.0946f));
         qx = (int) (tmp + copysignf(0.5f, tmp));
         if (qx >= 0 && qx < 256) xhat = gain * p->look_ix43[qx];
-        else xhat = (float) (gain * pow(qx, (4.0 / 3.0)));
+        else {
+            rc->beyond_table++;
+            if (qx >= 16384) rc->from_16384++;
+            if (qx > rc->max_qx) rc->max_qx = qx;
+            xhat = (float) (gain * pow(qx, (4.0 / 3.0)));
+        }
         tmp = x[i] - xhat;
         sxx += tmp * tmp;
     }
     return hxo_mblog(1.0e-12f + sxx) - logn;
+}
+
+/* what noise_actual multiplies the gain with for lines first .. first + n - 1 beyond the float table: this machine's libm */
+void hxo_pow43(int first, int n, double *out)
+{
+    int i;
+    for (i = 0; i < n; i++) out[i] = pow(first + i, (4.0 / 3.0));
 }
 
 /* l3math.c:656-671 */
@@ -400,13 +412,13 @@ static void seek_actual(ba_t *b)
             int NTarget = b->NT[ch][i], n = p->nBand_l[i], s = b->gsf[ch][i];
             if (b->Noise0[ch][i] > NTarget) {
                 int logn = p->look_log_cbwmb[i];
-                int noise = noise_actual(p, y34, y, s, n, logn);
+                int noise = noise_actual(p, &b->e->range[0], y34, y, s, n, logn);
                 int dn = noise - NTarget;
                 st->NTadjust[ch][i] = st->NTadjust[ch][i] + (dn >> 3);
                 if (dn > 100) {                     /* decrease_noise */
                     int t = s - 1, absmin = abs(dn), tnmin = noise, smin = s, niter = HXO_MIN(t, 20);
                     for (k = 0; k < niter; k++) {
-                        int tn = noise_actual(p, y34, y, t, n, logn), ad = abs(tn - NTarget);
+                        int tn = noise_actual(p, &b->e->range[0], y34, y, t, n, logn), ad = abs(tn - NTarget);
                         if (ad < absmin) { absmin = ad; tnmin = tn; smin = t; }
                         if (tn <= NTarget) break;
                         t--;
@@ -417,7 +429,7 @@ static void seek_actual(ba_t *b)
                     for (k = 0; k < 20; k++) {
                         int tn, ad;
                         t++;
-                        tn = noise_actual(p, y34, y, t, n, logn);
+                        tn = noise_actual(p, &b->e->range[0], y34, y, t, n, logn);
                         ad = abs(tn - NTarget);
                         if (ad < absmin) { absmin = ad; tnmin = tn; smin = t; }
                         if (tn >= NTarget) break;
@@ -574,7 +586,7 @@ static void big_lucky_noise(ba_t *b)
                 for (; s >= s0; s -= sdelta) {
                     g = GG - s;
                     if (g >= g0) break;
-                    noise = noise_actual(p, y34, y, g, n, logn);
+                    noise = noise_actual(p, &b->e->range[0], y34, y, g, n, logn);
                     if (noise <= b->NT[ch][i]) { b->Noise[ch][i] = noise; smin = s; }
                 }
                 b->sf[ch][i] = smin;

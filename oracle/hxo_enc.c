@@ -16,6 +16,11 @@ void hxo_set_debug(hxo_encoder *e, hxo_frame_debug *d) { e->dbg = d; }
 extern float *hxo_tap_etab, *hxo_tap_thr;
 unsigned hxo_frames_out(const hxo_encoder *e) { return e->s.tot_frames_out; }
 unsigned hxo_bytes_out(const hxo_encoder *e) { return e->s.tot_bytes_out; }
+void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3])
+{
+    const hxo_range_counts *c = &e->range[short_blocks ? 1 : 0];
+    out[0] = c->beyond_table; out[1] = c->from_16384; out[2] = c->max_qx;
+}
 
 /* test/tomp3.cpp:357-384 */
 void hxo_default_control(hxo_control *ec)

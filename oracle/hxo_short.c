@@ -63,7 +63,7 @@ int hxo_ms_metric_short(hxo_encoder *e, const float xx[2][576])
     return (p->nsfs - d) * 1024;     /* (the reference shifts; the value may be negative) */
 }
 
-static int noise_actual(const hxo_params *p, const float *x34, const float *x, int gsf, int n, int logn)
+static int noise_actual(const hxo_params *p, hxo_range_counts *rc, const float *x34, const float *x, int gsf, int n, int logn)
 {
     float sxx = 0.0f, igain = p->look_34igain[gsf], gain = p->look_gain[gsf], xhat, tmp;
     int i, qx;
@@ -71,7 +71,12 @@ static int noise_actual(const hxo_params *p, const float *x34, const float *x, i
         tmp = (igain * x34[i] + (0.0f - 0.0946f));
         qx = (int) (tmp + copysignf(0.5f, tmp));
         if (qx >= 0 && qx < 256) xhat = gain * p->look_ix43[qx];
-        else xhat = (float) (gain * pow(qx, (4.0 / 3.0)));
+        else {
+            rc->beyond_table++;
+            if (qx >= 16384) rc->from_16384++;
+            if (qx > rc->max_qx) rc->max_qx = qx;
+            xhat = (float) (gain * pow(qx, (4.0 / 3.0)));
+        }
         tmp = x[i] - xhat;
         sxx += tmp * tmp;
     }
@@ -234,11 +239,11 @@ static void seek_actual(sba_t *b)
                 int NTarget = b->NT[ch][w][i], n = p->nBand_s[i], s = b->gsf[ch][w][i];
                 if (b->Noise0[ch][w][i] > NTarget) {
                     int logn = p->look_log_cbwmb_s[i];
-                    int noise = noise_actual(p, y34, y, s, n, logn), dn = noise - NTarget;
+                    int noise = noise_actual(p, &b->e->range[1], y34, y, s, n, logn), dn = noise - NTarget;
                     if (dn > 100) {
                         int t = s - 1, absmin = abs(dn), tnmin = noise, smin = s, niter = HXO_MIN(t, 20);
                         for (k = 0; k < niter; k++) {
-                            int tn = noise_actual(p, y34, y, t, n, logn), ad = abs(tn - NTarget);
+                            int tn = noise_actual(p, &b->e->range[1], y34, y, t, n, logn), ad = abs(tn - NTarget);
                             if (ad < absmin) { absmin = ad; tnmin = tn; smin = t; }
                             if (tn <= NTarget) break;
                             t--;
@@ -249,7 +254,7 @@ static void seek_actual(sba_t *b)
                         for (k = 0; k < 20; k++) {
                             int tn, ad;
                             t++;
-                            tn = noise_actual(p, y34, y, t, n, logn);
+                            tn = noise_actual(p, &b->e->range[1], y34, y, t, n, logn);
                             ad = abs(tn - NTarget);
                             if (ad < absmin) { absmin = ad; tnmin = tn; smin = t; }
                             if (tn >= NTarget) break;

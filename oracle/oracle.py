@@ -61,6 +61,8 @@ def lib():
         _lib.hxo_frames_out.restype = C.c_uint
         _lib.hxo_bytes_out.argtypes = [C.c_void_p]
         _lib.hxo_bytes_out.restype = C.c_uint
+        _lib.hxo_range_counts_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        _lib.hxo_range_counts_get.restype = None
     return _lib
 
 
@@ -116,6 +118,15 @@ class RefDump(C.Structure):
         ("initialMNR", C.c_int), ("nsf", C.c_int * 2)]
 
 
+def pow43(first, n):
+    """float64 [n]: pow(ix, 4/3) for ix = first .. first + n - 1 as the oracle's noise measurement calls it (this machine's libm)"""
+    out = np.zeros(n, dtype=np.float64)
+    lib().hxo_pow43.argtypes = [C.c_int, C.c_int, C.c_void_p]
+    lib().hxo_pow43.restype = None
+    lib().hxo_pow43(first, n, out.ctypes.data)
+    return out
+
+
 class OracleEncoder:
     """one stream through the restatement"""
 
@@ -154,6 +165,14 @@ class OracleEncoder:
     def bytes_out(self):
         """bytes emitted so far"""
         return int(self.l.hxo_bytes_out(self.h))
+
+    def range_counts(self, short_blocks=False):
+        """what the noise measurement of the long-block (or short-block) allocator met beyond the 256-entry float table of
+        ix^(4/3) so far: {"beyond_table": lines dequantised through pow(), "from_16384": those quantised to 16384 or more
+        (past the kernels' double table, HX_POW43_N), "max_qx": the largest quantised value}"""
+        v = (C.c_longlong * 3)()
+        self.l.hxo_range_counts_get(self.h, 1 if short_blocks else 0, v)
+        return {"beyond_table": int(v[0]), "from_16384": int(v[1]), "max_qx": int(v[2])}
 
     def __del__(self):
         try:

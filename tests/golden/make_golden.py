@@ -15,6 +15,9 @@ sys.path.insert(0, ROOT)
 from oracle import oracle as O          # noqa: E402
 from hmp3_amd import synth              # noqa: E402
 
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import dynamic_range_cases as DR        # noqa: E402
+
 GOLD = os.path.join(ROOT, "tests", "golden")
 
 # name -> (E_CONTROL overrides, sample rate, frames, rho, bursts)
@@ -56,6 +59,39 @@ def extra_case_pcm(name):
     if len(EXTRA_CASES[name]) > 8:
         pcm = np.clip(pcm.astype(np.int32) + EXTRA_CASES[name][8], -32768, 32767).astype(np.int16)
     return pcm
+
+
+# the ends of the float range (tests/dynamic_range_cases.py): name -> (E_CONTROL overrides, frames, sample format)
+# range_tone_x64_cbr320: float input, the full-scale 110 Hz tone at 64 x full scale; its noise measurement quantises lines
+# up to 70215, past the kernels' double table of ix^(4/3), where the reference calls pow() of the libm it was built with
+# range_dc_tail_cbr128_dc: int16 material on a DC offset, then digital silence, through the DC blocker (-S1): the
+# blocker's state decays into float32's subnormal range after 66 frames and stays there
+RANGE_CASES = {
+    "range_tone_x64_cbr320": (dict(bitrate=160), DR.OVER_RANGE_F, "f32"),
+    "range_dc_tail_cbr128_dc": (dict(bitrate=64, filter_select=1), 120, "s16"),
+}
+
+
+def range_case_pcm(name):
+    kw, nfr, fmt = RANGE_CASES[name]
+    return DR.over_range_stream(kw, 64) if fmt == "f32" else DR.dc_tail_stream(kw, nfr)
+
+
+def encode_range_case(enc, name, flush_frames=2):
+    """the case's frames and then zero frames through enc (a RefEncoder made with s16 = (format is s16), or an OracleEncoder)"""
+    kw, nfr, fmt = RANGE_CASES[name]
+    pcm = range_case_pcm(name)
+    pcm = np.concatenate([pcm, np.zeros((flush_frames * 1152, 2), dtype=pcm.dtype)])
+    fn = enc.encode_f32 if fmt == "f32" else enc.encode_s16
+    return b"".join(fn(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr + flush_frames))
+
+
+def write_range_cases():
+    for name, (kw, nfr, fmt) in RANGE_CASES.items():
+        data = encode_range_case(O.RefEncoder(O.default_control(**kw), s16=(fmt == "s16")), name)
+        with open(os.path.join(GOLD, name + ".mp3frames"), "wb") as fh:
+            fh.write(data)
+        print("%-26s %6d bytes, %d frames" % (name, len(data), nfr))
 
 
 def main():
@@ -153,6 +189,7 @@ def main():
         with open(os.path.join(GOLD, name + ".mp3frames"), "wb") as fh:
             fh.write(data)
         print("%-26s %6d bytes, %d frames" % (name, len(data), nfr))
+    write_range_cases()
     with open(os.path.join(GOLD, "streams.json"), "w") as fh:
         json.dump(meta, fh)
     print("golden vectors written to", GOLD)

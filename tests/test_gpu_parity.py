@@ -13,6 +13,7 @@ import pytest
 from oracle import oracle as O
 from hmp3_amd import synth
 from conftest import skip_unless_host_libm_is_the_restated_one
+from stage_taps import TapBatch
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -772,79 +773,15 @@ def test_every_stage_bit_exact(name):
     kw, sr, bursts, taps = STAGE_CASES[name]
     mono = kw.get("mode") == 3
     S, F = 4, 24
-    NG = 2 * F
     pcm = np.stack([synth.stream_pcm(200 + i, F, sr=sr, rho=RHOS[i % 4], bursts=bursts) for i in range(S)])
     if mono:
         pcm = pcm[:, :, 0]
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
-    b.debug_enable(True)
-    got = b.encode_host(pcm)
-    assert b.status() == 0
-    sb = b.debug_read("sb", np.float32, S * 2 * (NG + 3) * 576).reshape(S, 2, NG + 3, 576)
-    xr = b.debug_read("xr", np.float32, S * NG * 1152).reshape(S, NG, 2, 576)
-    etab = b.debug_read("etab", np.float32, S * NG * 128).reshape(S, NG, 2, 64)
-    thr = b.debug_read("thr", np.float32, S * NG * 128).reshape(S, NG, 2, 64)
-    btg = b.debug_read("bt", np.uint8, S * NG).reshape(S, NG)
-    ixq = b.debug_read("ixq", np.int16, S * NG * 1152).reshape(S, NG, 2, 576).astype(np.int32) & 0xFFFF
-    # the signs travel as one bit per line (bit j & 31 of word j >> 5; 20 words per granule and channel, 18 used)
-    sgw = b.debug_read("sgn", np.uint32, S * NG * 2 * 20).reshape(S, NG, 2, 20)
-    sgn = np.unpackbits(sgw[..., :18].copy().view(np.uint8), axis=-1, bitorder="little").reshape(S, NG, 2, 576)
-    npart = np.zeros(1, np.int32)
-    assert api().lib().hx_debug_host_table(C.byref(api().default_control(**kw)), b"psy_npart", npart.ctypes.data, 4) == 4
-    np2 = int(npart[0] + 1) & ~1
-
-    class GDbg(C.Structure):
-        _fields_ = [("ms", C.c_int), ("ms_metric", C.c_int * 2), ("byte_pool", C.c_int), ("MNR_after", C.c_int),
-                    ("mask_mb", C.c_int * 88), ("gr", C.c_int * 96), ("sf", C.c_int * 88), ("scfsi", C.c_int * 2),
-                    ("main_bytes", C.c_int)]
-    raw = b.debug_read("dbg", np.uint8, S * F * C.sizeof(GDbg))
-    seen_bt = set()
-    for s in range(S):
-        enc = O.OracleEncoder(O.default_control(**kw))
-        d = O.oracle_enable_debug(enc)
-        out = []
-        for f in range(F):
-            out.append(enc.encode_s16(pcm[s, f * 1152:(f + 1) * 1152]))
-            xp = np.array(d.xr_pre).reshape(2, 2, 576)
-            oix = np.array(d.ix).reshape(2, 2, 576)
-            osg = np.array(d.signx).reshape(2, 2, 576)
-            ogr = np.array(d.gr).reshape(2, 2, 27)
-            gd = GDbg.from_buffer_copy(raw[(s * F + f) * C.sizeof(GDbg):(s * F + f + 1) * C.sizeof(GDbg)].tobytes())
-            ggr = np.array(gd.gr).reshape(2, 2, 24)
-            for igr in range(2):
-                g = 2 * f + igr
-                bt = int(d.block_type[igr])
-                seen_bt.add(bt)
-                assert btg[s, g] == bt, ("block type", s, f, igr)
-                for ch in range(1 if mono else 2):
-                    assert np.array_equal(bits(xr[s, g, ch]), bits(xp[igr, ch])), ("mdct", s, f, igr, ch, bt)
-                    # what K6 hands to k_pack: the quantised lines of the coded range and the signs of the non-zero ones
-                    n = 2 * int(ggr[igr, ch, 1]) + 4 * max(int(ggr[igr, ch, 18]), 0) if ggr[igr, ch, 20] else 0
-                    assert np.array_equal(ixq[s, g, ch, :n], oix[igr, ch, :n]), ("ix", s, f, igr, ch, bt)
-                    nz = oix[igr, ch, :n] != 0
-                    assert np.array_equal(sgn[s, g, ch, :n][nz], osg[igr, ch, :n][nz]), ("signs", s, f, igr, ch, bt)
-                    assert np.array_equal(ggr[igr, ch], ogr[igr, ch, :24]), ("side info", s, f, igr, ch, bt)
-            if taps != "full":
-                continue
-            sn = np.array(d.sample_new).reshape(2, 2, 576)
-            oe = np.array(d.etab).reshape(2, 2, 64)
-            ot = np.array(d.thr).reshape(2, 2, 64)
-            for igr in range(2):
-                g = 2 * f + igr
-                for ch in range(2):
-                    assert np.array_equal(bits(sb[s, ch, 3 + g]), bits(sn[igr, ch])), ("polyphase", s, f, igr, ch)
-                    if d.block_type[igr] != 2:      # (the oracle taps the long model's partition tables)
-                        assert np.array_equal(bits(etab[s, g, ch, :np2]), bits(oe[igr, ch, :np2])), ("etab", s, f, igr, ch)
-                        assert np.array_equal(bits(thr[s, g, ch, :np2]), bits(ot[igr, ch, :np2])), ("thr", s, f, igr, ch)
-            assert gd.ms == d.ms and list(gd.ms_metric) == list(d.ms_metric)
-            assert gd.byte_pool == d.byte_pool and gd.MNR_after == d.MNR_after and gd.main_bytes == d.main_bytes
-            if d.block_type[0] != 2 and d.block_type[1] != 2:
-                assert np.array_equal(np.array(gd.sf), np.array(d.sf))
-                assert list(gd.scfsi) == list(d.scfsi)
-        assert got[s] == b"".join(out)
+    tb = TapBatch(api(), kw, S, F, taps)        # (tests/stage_taps.py: the comparison itself, shared with test_gpu_dynamic_range.py)
+    tb.call(pcm)
+    assert tb.frames == [F] * S and all(len(g) > 0 for g in tb.got)
     if bursts and "long" not in name:
-        assert {0, 1, 2, 3} <= seen_bt, seen_bt      # every block type went through the stage comparison
-    b.close()
+        assert {0, 1, 2, 3} <= tb.seen_bt, tb.seen_bt      # every block type went through the stage comparison
+    tb.close()
 
 
 @pytest.mark.parametrize("cfg", ["config3", "config4_share", "config5_share"])

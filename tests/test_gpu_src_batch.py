@@ -184,6 +184,45 @@ def test_srcpcm_tap_equals_the_reference_converter(pairs, layout, k6_build):
     b.close()
 
 
+def range_streams(layout):
+    """float sources (at the +-1 scale: k_src multiplies by 32768) far outside it: samples up to 16.0, and at 1e-41, which
+    float32 holds as a subnormal; rate pairs without conversion, down and up"""
+    out = []
+    for k, (src, tgt) in enumerate([(44100, 44100), (48000, 44100), (22050, 44100)]):
+        for scale in (16.0, 1e-41):
+            ch, mono = {"stereo": (2, 0), "downmix": (2, 1)}[layout]
+            s = Stream(src, 32, 1, ch, mpeg_select=tgt, mono_convert=mono, seed=900 + k, seconds=1.0)
+            x = signal(900 + k, src, ch) * scale
+            x[5::97] = scale                    # the level itself, exactly
+            s.data = x.astype("<f4").tobytes() + bytes(1 << 18)
+            s.target, s.scale = tgt, scale
+            out.append(s)
+    return out
+
+
+@pytest.mark.one_k6_build
+@pytest.mark.parametrize("layout", ["stereo", "downmix"])
+def test_srcpcm_tap_on_float_sources_outside_the_unit_range(layout, k6_build):
+    """k_src on float sources at 16 x full scale and at 1e-41 (subnormal in the source, 3.3e-37 once scaled; the filter's
+    products of it are subnormal again): the converted PCM equals the reference's Csrc bit for bit over calls of 1, 5 and
+    12 frames, zero signs included, and the streams' bytes equal the reference's MP3_audio_encode loop"""
+    streams = range_streams(layout)
+    raw = [np.frombuffer(s.data[:4 * 2 * s.source], "<f4") for s in streams]
+    assert all(float(np.abs(r).max()) == 16.0 for r in raw[0::2])
+    assert all(0 < float(np.abs(r).max()) < 2.0 ** -126 and np.count_nonzero(r) > 40000 for r in raw[1::2])
+    b = make_batch(streams, 12)
+    outs, _, pcm = run(b, streams, [1, 5, 12], taps=True)
+    got = np.concatenate(pcm, axis=1)
+    for i, s in enumerate(streams):
+        want = ref_converted(s, s.target, 18)
+        g = got[i][:, :want.shape[1]]
+        assert np.count_nonzero(want) > 10000
+        assert np.array_equal(g.view(np.uint32), want.view(np.uint32)), (s.source, s.target, s.scale, layout,
+                                                                         int(np.argmax(np.any(g.view(np.uint32) != want.view(np.uint32), axis=1))))
+        assert outs[i] == s.reference(18)[0], (s.source, s.target, s.scale, layout)
+    b.close()
+
+
 def mixed_stereo():
     return [Stream(48000, 24, 0, mpeg_select=44100, seed=1), Stream(32000, 32, 1, mpeg_select=44100, seed=2),
             Stream(22050, 16, 0, mpeg_select=44100, seed=3), Stream(44100, 8, 0, seed=4),

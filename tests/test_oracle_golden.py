@@ -139,3 +139,15 @@ def test_extra_golden_streams(name):
     kw = M.EXTRA_CASES[name][0]
     got = O.encode_stream(O.OracleEncoder(O.default_control(**kw)), M.extra_case_pcm(name))
     assert got == open(os.path.join(GOLD, name + ".mp3frames"), "rb").read()
+
+
+@pytest.mark.parametrize("name", ["range_tone_x64_cbr320", "range_dc_tail_cbr128_dc"])
+def test_range_golden_streams(name):
+    """the ends of the float range (make_golden.RANGE_CASES): float input at 64 x full scale, whose noise measurement goes
+    through pow() beyond 16384; int16 input whose DC-blocker tail is subnormal for 54 frames"""
+    M = _extra()
+    kw = M.RANGE_CASES[name][0]
+    enc = O.OracleEncoder(O.default_control(**kw))
+    assert M.encode_range_case(enc, name) == open(os.path.join(GOLD, name + ".mp3frames"), "rb").read()
+    if name == "range_tone_x64_cbr320":
+        assert enc.range_counts()["from_16384"] > 0 and enc.range_counts()["max_qx"] > 65536

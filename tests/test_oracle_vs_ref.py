@@ -10,6 +10,7 @@ import pytest
 from oracle import oracle as O
 from hmp3_amd import synth
 import packet_cases as PC
+import dynamic_range_cases as DR
 
 pytestmark = pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built")
 
@@ -358,3 +359,68 @@ def test_uninitialised_psy_local_is_defined_as_zero():
     pcm2 = synth.stream_pcm(7, 24, sr=44100, rho=0.7, bursts=True)
     assert O.encode_stream(O.RefEncoder(O.default_control(**kw2), zero_locals=True), pcm2) == \
         O.encode_stream(O.RefEncoder(O.default_control(**kw2)), pcm2)
+
+
+# ---- the ends of the float range: exactly the inputs of tests/test_gpu_dynamic_range.py (tests/dynamic_range_cases.py) ----
+def _both(kw, pcm, nfr, f32):
+    """-> (reference bytes, oracle bytes, the oracle encoder) of one stream, frame by frame"""
+    r = O.RefEncoder(O.default_control(**kw), s16=not f32)
+    o = O.OracleEncoder(O.default_control(**kw))
+    a = b"".join((r.encode_f32 if f32 else r.encode_s16)(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr))
+    b = b"".join((o.encode_f32 if f32 else o.encode_s16)(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr))
+    return a, b, o
+
+
+@pytest.mark.parametrize("name", list(DR.OVER_RANGE))
+def test_over_range_float_input_byte_identical(name):
+    """float input up to 2^16 x full scale (a tone and its gated form at six gains): the oracle is the reference there too, and
+    the streams that are there for the pow() path of the noise measurement reach it (the oracle's counters)"""
+    kw = DR.OVER_RANGE[name]
+    pcm = DR.over_range_batch(kw)
+    for s in range(len(pcm)):
+        a, b, o = _both(kw, pcm[s], DR.OVER_RANGE_F, True)
+        assert len(a) > 0 and a == b, s
+        lo, sh = o.range_counts(), o.range_counts(short_blocks=True)
+        if s in DR.OVER_RANGE_REACHES_POW.get(name, {}):
+            assert lo["from_16384"] > 0, (s, lo)
+        assert (lo["from_16384"] > 0) == (lo["max_qx"] >= 16384) and lo["from_16384"] <= lo["beyond_table"]
+        # no input of this set takes the short-block noise measurement past the double table: its largest quantised value is
+        # 7915 (cbr128_thr0_all_short, gain 65536); the first-generation allocator has no such measurement at all
+        assert sh["from_16384"] == 0 and sh["max_qx"] < 16384, (s, sh)
+        if name == "a1_is_n8":
+            assert lo["beyond_table"] == 0 and sh["beyond_table"] == 0
+    if name == "cbr128_thr0_all_short":
+        assert sh["beyond_table"] > 0 and sh["max_qx"] >= 256      # (the last stream: the gated tone at gain 65536)
+
+
+@pytest.mark.parametrize("name", list(DR.SUBNORMAL))
+def test_subnormal_float_input_byte_identical(name):
+    """float input with its peak at 1e-18 .. 1e-44 and the two 60-decade ramps: bytes (which are the silence pattern for the
+    peaks, whatever an encoder does with subnormals: the GPU test compares taps)"""
+    kw = DR.SUBNORMAL[name][0]
+    for pcm, nfr in ((DR.subnormal_peaks(kw), DR.PEAKS_F), (DR.subnormal_ramps(kw), DR.RAMPS_F)):
+        for s in range(len(pcm)):
+            a, b, _ = _both(kw, pcm[s], nfr, True)
+            assert a == b, (nfr, s)
+    assert len(a) > 0
+
+
+@pytest.mark.parametrize("name", list(DR.DC_TAIL))
+def test_dc_blocker_tail_byte_identical(name):
+    """int16 material on a DC offset, then digital silence, DC blocker on: the blocker's state goes subnormal and stays"""
+    kw, nfr, _ = DR.DC_TAIL[name]
+    pcm = DR.dc_tail_batch(kw, nfr)
+    for s in range(len(pcm)):
+        a, b, _ = _both(kw, pcm[s], nfr, False)
+        assert len(a) > 0 and a == b, s
+
+
+def test_range_goldens_regenerate_from_the_reference():
+    """tests/golden/range_*.mp3frames are what the reference built here writes for make_golden.RANGE_CASES, and what the
+    oracle writes"""
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden"))
+    import make_golden as M
+    for name, (kw, nfr, fmt) in M.RANGE_CASES.items():
+        want = open(os.path.join(M.GOLD, name + ".mp3frames"), "rb").read()
+        assert M.encode_range_case(O.RefEncoder(O.default_control(**kw), s16=(fmt == "s16")), name) == want, name
+        assert M.encode_range_case(O.OracleEncoder(O.default_control(**kw)), name) == want, name
