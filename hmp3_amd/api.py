@@ -201,6 +201,26 @@ def _encode_src_counts_host(fn, handle, n, stride, rows, nframes, counts, frame_
     return (res, used) + ((st,) if stats else ()) + ((cr,) if crc else ())
 
 
+def _menu_args(controls, sources, nstreams, cfg):
+    """ctypes arguments of the menu constructors: (ec array, nmenu, src array or None, cfg array or None)"""
+    nmenu = len(controls)
+    ec = (EControl * nmenu)(*controls)
+    src = None
+    if sources is not None:
+        if len(sources) != nmenu:
+            raise ValueError("a menu of %d controls and %d sources" % (nmenu, len(sources)))
+        src = (Source * nmenu)(*sources)
+    return ec, nmenu, src, _counts_array(nstreams, cfg)
+
+
+def _int_pair_arrays(idx, cfg):
+    idx, cfg = [int(i) for i in idx], [int(c) for c in cfg]
+    if len(idx) != len(cfg):
+        raise ValueError("%d slots and %d configurations" % (len(idx), len(cfg)))
+    n = len(idx)
+    return (C.c_int * max(n, 1))(*idx), (C.c_int * max(n, 1))(*cfg), n
+
+
 def _frame_counts(setter, handle, n, counts):
     if setter(handle, _counts_array(n, counts)) != 0:
         raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
@@ -223,6 +243,38 @@ class Batch:
         if not self.h:
             raise RuntimeError("hx_batch_create failed: " + last_error())
         self.max_frames = max_frames
+
+    @classmethod
+    def menu(cls, controls, nstreams, cfg=None, max_frames=256, device=0, sources=None):
+        """a batch over a menu of configurations (hx_batch_create_menu): controls = the menu's entries, cfg = the entry each
+        of the nstreams slots starts with (None: entry 0); assign_streams hands slots other entries later.  sources (one
+        Source per entry): a converting batch - SrcBatch.menu passes it"""
+        self = cls.__new__(cls)
+        self.n = int(nstreams)
+        self._ec, nmenu, self._src, arr = _menu_args(controls, sources, self.n, cfg)
+        self.h = lib().hx_batch_create_menu(device, self.n, self._ec, nmenu, self._src, arr, max_frames)
+        if not self.h:
+            raise RuntimeError("hx_batch_create_menu failed: " + last_error())
+        self.max_frames = max_frames
+        return self
+
+    def nconfigs(self):
+        """entries of the batch's menu (a batch not created from a menu: its distinct controls)"""
+        return int(lib().hx_batch_nconfigs(self.h))
+
+    def stream_config(self, i):
+        """the menu entry slot i runs, as of the calls made so far"""
+        k = int(lib().hx_batch_stream_config(self.h, int(i)))
+        if k < 0:
+            raise IndexError(i)
+        return k
+
+    def assign_streams(self, idx, cfg, stream=None):
+        """slot idx[e] starts a new stream of menu entry cfg[e]: one launch, asynchronous on `stream` and ordered like a
+        plain device call, exactly as reset_streams (hx_batch_assign_streams)"""
+        ai, ac, n = _int_pair_arrays(idx, cfg)
+        if lib().hx_batch_assign_streams(self.h, ai, ac, n, stream) != 0:
+            raise RuntimeError("hx_batch_assign_streams failed: " + last_error())
 
     def out_stride(self, nframes):
         return int(lib().hx_batch_out_stride(self.h, nframes))
@@ -484,6 +536,11 @@ class SrcBatch(Batch):
             raise RuntimeError("hx_batch_create_src failed: " + last_error())
         self.max_frames = max_frames
 
+    @classmethod
+    def menu(cls, controls, sources, nstreams, cfg=None, max_frames=256, device=0):
+        """a converting batch over a menu whose entry j is the pair (controls[j], sources[j]) (hx_batch_create_menu)"""
+        return super().menu(controls, nstreams, cfg=cfg, max_frames=max_frames, device=device, sources=sources)
+
     def schedule(self, i, nframes):
         """(bytes each of stream i's next nframes calls consumes, bytes they read)"""
         nb = np.zeros(nframes, dtype=np.int64)
@@ -562,6 +619,41 @@ class Multi:
         if not self.h:
             raise RuntimeError("hx_multi_create failed: " + last_error())
 
+    @classmethod
+    def menu(cls, controls, nstreams, cfg=None, max_frames=256, ndev=0, devices=None, sources=None):
+        """as Batch.menu, in blocks over several devices (hx_multi_create_menu): every block gets the whole menu"""
+        self = cls.__new__(cls)
+        dv = (C.c_int * len(devices))(*devices) if devices else None
+        if devices:
+            ndev = len(devices)
+        self.n = int(nstreams)
+        self._ec, nmenu, self._src, arr = _menu_args(controls, sources, self.n, cfg)
+        self.h = lib().hx_multi_create_menu(ndev, dv, self.n, self._ec, nmenu, self._src, arr, max_frames)
+        if not self.h:
+            raise RuntimeError("hx_multi_create_menu failed: " + last_error())
+        return self
+
+    def batch(self, k):
+        """block k's batch handle, for the per-batch C calls (hx_multi_batch)"""
+        return lib().hx_multi_batch(self.h, int(k))
+
+    def nconfigs(self):
+        return int(lib().hx_batch_nconfigs(self.batch(0)))
+
+    def stream_config(self, i):
+        """the menu entry stream i (counted over all blocks) runs"""
+        for k in range(self.ndevices()):
+            _, first, count = self.shard(k)
+            if first <= i < first + count:
+                return int(lib().hx_batch_stream_config(self.batch(k), int(i) - first))
+        raise IndexError(i)
+
+    def assign_streams(self, idx, cfg):
+        """as Batch.assign_streams over all blocks, synchronous; all blocks or (RuntimeError) none (hx_multi_assign_streams)"""
+        ai, ac, n = _int_pair_arrays(idx, cfg)
+        if lib().hx_multi_assign_streams(self.h, ai, ac, n) != 0:
+            raise RuntimeError("hx_multi_assign_streams failed: " + last_error())
+
     def ndevices(self):
         return int(lib().hx_multi_ndevices(self.h))
 
@@ -632,6 +724,11 @@ class SrcMulti(Multi):
         self.h = L.hx_multi_create_src(ndev, dv, self.n, self._ec, 0, self._src, 0, max_frames)
         if not self.h:
             raise RuntimeError("hx_multi_create_src failed: " + last_error())
+
+    @classmethod
+    def menu(cls, controls, sources, nstreams, cfg=None, max_frames=256, ndev=0, devices=None):
+        """as SrcBatch.menu, in blocks over several devices"""
+        return super().menu(controls, nstreams, cfg=cfg, max_frames=max_frames, ndev=ndev, devices=devices, sources=sources)
 
     def in_stride(self, nframes):
         return int(lib().hx_multi_src_in_stride(self.h, nframes))

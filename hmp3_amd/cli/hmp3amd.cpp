@@ -3,6 +3,8 @@
 //                                                                 a very large file frame by frame (hx_enc_* API)
 //   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API); files at any rate and
 //                                                                 -A go through the converting batches (hx_multi_create_src)
+//   ... -slots<n>                                                 the files of -batch through n slots of one batch: a file is
+//                                                                 read when a slot is free and written when its drain ends
 // Same flags, encode loop and output files as the reference CLI (reference
 // test/tomp3.cpp:336-602 main, :645-1088 ff_encode): Xing/Info tag frame first, audio frames, four
 // frames of silence behind the input, drain until every submitted frame is out, then the tag is
@@ -24,7 +26,7 @@
 namespace {
 
 struct WavInfo { int channels = 0, rate = 0, bits = 0, type = 0, bigendian = 0; uint64_t data_bytes = 0; };
-struct Options { HX_E_CONTROL ec; int xing_flag = 3 | 0x40, ignore_length = 0, mpeg_select = 0, ec_display = 0, ngpus = 0; };
+struct Options { HX_E_CONTROL ec; int xing_flag = 3 | 0x40, ignore_length = 0, mpeg_select = 0, ec_display = 0, ngpus = 0, nslots = 0; };
 
 // a header field of n bytes in the file's byte order
 uint64_t field(const unsigned char *p, int n, int be)
@@ -130,7 +132,8 @@ void usage()
             "\n   -SBTn short-block threshold      -S1  DC blocker       -Xn  0 no tag, 1 Xing, 2/3 + TOC, default + info"
             "\n   -Cn -On copyright / original bits   -Ln VBR bitrate cap   -Tn -TXn tuning   -IL ignore the WAV length field"
             "\n   -An  encode rate: 0 track the input (default), 1 an MPEG-1 rate, 2 an MPEG-2 rate, else that rate in Hz"
-            "\n   -EC  print the encoder settings in use    -D  no progress display    -Gn  GPUs used by -batch (default all)\n");
+            "\n   -EC  print the encoder settings in use    -D  no progress display    -Gn  GPUs used by -batch (default all)"
+            "\n   -slotsn  -batch through n slots: at most n files in memory, a slot takes the next file when its file is done\n");
 }
 
 // one input file, read and checked
@@ -152,7 +155,8 @@ struct Input {
 
 // open the input, parse and check its header; on success *fp is positioned at the first audio byte and
 // *indatasize is the number of audio bytes to read (UINT64_MAX: until the end of the file)
-bool open_input(const char *path, const Options &opt, Input *in, FILE **fp, uint64_t *indatasize_out)
+// (announce: print the header line - a file of -slots is opened twice, for its header and for its audio)
+bool open_input(const char *path, const Options &opt, Input *in, FILE **fp, uint64_t *indatasize_out, bool announce = true)
 {
     FILE *f = strcmp(path, "-") ? fopen(path, "rb") : stdin;
     if (!f) { fprintf(stderr, "\n CANNOT_OPEN_INPUT_FILE %s\n", path); return false; }
@@ -164,7 +168,7 @@ bool open_input(const char *path, const Options &opt, Input *in, FILE **fp, uint
     const uint64_t indatasize = (ignore_length || wi.data_bytes == 0xFFFFFFFFu) ? UINT64_MAX : wi.data_bytes;
     if (indatasize == 0) { fprintf(stderr, "\n INPUT FILE CONTAINS NO AUDIO\n"); return false; }
     *indatasize_out = indatasize;
-    fprintf(stderr, "\n pcm file:  channels = %d  bits = %d,  rate = %d  type = %d", wi.channels, wi.bits, wi.rate, wi.type);
+    if (announce) fprintf(stderr, "\n pcm file:  channels = %d  bits = %d,  rate = %d  type = %d", wi.channels, wi.bits, wi.rate, wi.type);
     in->is_float = wi.type == 3;
     if ((wi.channels != 1 && wi.channels != 2) ||
         !((wi.type == 1 && (wi.bits == 8 || wi.bits == 16 || wi.bits == 24 || wi.bits == 32)) || (in->is_float && wi.bits == 32)) ||
@@ -191,11 +195,12 @@ void to_host_order(const WavInfo &wi, unsigned char *p, size_t nbytes)
 }
 
 // a whole input in memory (regular files of the batched routes)
-bool load_input(const char *path, const Options &opt, Input *in)
+bool load_input(const char *path, const Options &opt, Input *in, bool announce = true)
 {
     FILE *f = nullptr;
     uint64_t indatasize = 0;
-    if (!open_input(path, opt, in, &f, &indatasize)) { if (f && f != stdin) fclose(f); return false; }
+    *in = Input();
+    if (!open_input(path, opt, in, &f, &indatasize, announce)) { if (f && f != stdin) fclose(f); return false; }
     const WavInfo &wi = in->wi;
     std::vector<unsigned char> chunk(1 << 20);
     while (in->data.size() < indatasize) {
@@ -241,7 +246,20 @@ struct Tagger {
     }
 };
 
-int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files, const Options &opt);
+// One file on its way through a batch: its input, what the batch takes for it, the calls of the single-file loop on it and
+// what its stream has produced so far.
+struct Job {
+    Input in;
+    HX_E_CONTROL ctl;                   // the control the batch is created with for the file (converting route: the source's)
+    HX_SOURCE src = {0, 0, 0, 0};
+    size_t nc = 0;                      // calls of the single-file loop on the file's input (the drain follows them)
+    std::vector<long long> start;       // converting route: where each of them starts in the file's bytes
+    std::vector<unsigned char> stream;
+    std::vector<unsigned> fr, by;       // per frame fed to the file's stream: frames / bytes out so far
+    unsigned short crc = 0;             // the MusicCRC of the file's bytes so far
+    bool done = false;                  // the file's drain has ended: it takes no more frames
+};
+int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, const Options &opt, bool loaded);
 
 bool mpeg_rate(int r) { return r == 32000 || r == 44100 || r == 48000 || r == 16000 || r == 22050 || r == 24000; }
 // The reference appends the four calls' worth of silence only if it fits a limit derived from its input buffer
@@ -423,9 +441,9 @@ int encode_one_file(const char *fin, const char *fout, const Options &opt)
     // and so does an input too short for one converter call, which that loop answers with a file of the tag alone.
     uint64_t fsize = 0;
     if (strcmp(fin, "-") && strcmp(fout, "-") && regular_file_size(fin, &fsize) && fsize <= kBatchRouteMaxBytes) {
-        std::vector<Input> one(1);
-        if (!load_input(fin, opt, &one[0])) return 1;
-        if (!needs_conversion(one[0], opt) || converter_calls(one[0], opt, nullptr, nullptr) > 0) return encode_loaded(one, {fin, fout}, opt);
+        std::vector<Job> one(1);
+        if (!load_input(fin, opt, &one[0].in)) return 1;
+        if (!needs_conversion(one[0].in, opt) || converter_calls(one[0].in, opt, nullptr, nullptr) > 0) return encode_jobs(one, {fin, fout}, opt, true);
     }
     return encode_streaming(fin, fout, opt);
 }
@@ -458,107 +476,181 @@ void frame_to_float(const Input &in, const unsigned char *src, float *dst)
         for (int i = 0; i < 1152; i++) dst[i] = (float) ((dst[2 * i] + dst[2 * i + 1]) * 0.5);
 }
 
+// Without -slots every file is read whole before the first call and has a slot of its own.  With -slots<n> only the headers
+// are read here: the files go through min(n, files) slots, and a file's audio is read when it gets one.
 int encode_batch(const std::vector<const char *> &files, const Options &opt)
 {
     const int S = (int) files.size() / 2;
-    std::vector<Input> in(S);
-    for (int i = 0; i < S; i++) if (!load_input(files[2 * i], opt, &in[i])) return 1;
-    return encode_loaded(in, files, opt);
+    std::vector<Job> jobs(S);
+    for (int i = 0; i < S; i++) {
+        if (opt.nslots <= 0) { if (!load_input(files[2 * i], opt, &jobs[i].in)) return 1; continue; }
+        FILE *f = nullptr;
+        uint64_t indatasize = 0;
+        const bool ok = open_input(files[2 * i], opt, &jobs[i].in, &f, &indatasize);
+        if (f && f != stdin) fclose(f);
+        if (!ok) return 1;
+    }
+    return encode_jobs(jobs, files, opt, opt.nslots <= 0);
 }
 
-int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files, const Options &opt)
+// the calls of the single-file loop on a file whose audio is in memory (conv: through the converter); false: no such call
+bool job_calls(Job &j, const char *name, const Options &opt, bool conv)
 {
-    const int S = (int) in.size();
-    std::vector<HX_E_CONTROL> ctl(S);
+    if (!conv) { j.in.pad(init_bytes_same_rate(j.in)); j.nc = ncalls(j.in); return true; }
+    const long long n = converter_calls(j.in, opt, &j.start, nullptr);
+    if (n < 0) { fprintf(stderr, "\n ENCODER INIT FAIL (%s): %s\n", name, hx_last_error()); return false; }
+    if (n == 0) { fprintf(stderr, "\n %s is shorter than one call of its converter\n", name); return false; }
+    j.nc = (size_t) n;
+    return true;
+}
+
+// what the batch takes for a file and the settings its encoder will report, from the header alone; *nch: the channel count
+// every file of the batch encodes to (0: none seen yet)
+bool job_control(Job &j, const char *name, const Options &opt, bool conv, int *nch)
+{
+    Input &in = j.in;
+    HX_E_CONTROL ec = in.ec;
+    if (conv) {
+        j.src = {in.wi.bits, in.is_float, opt.mpeg_select, in.mono_convert};
+        if (!hx_src_encode_control(&in.ec, &j.src, &ec)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s): %s\n", name, hx_last_error()); return false; }
+    } else if (in.mono_convert) ec.mode = 3;
+    const int c = ec.mode == 3 ? 1 : 2;
+    if (*nch && c != *nch) { fprintf(stderr, "\n -batch needs files that all encode to the same channel count\n"); return false; }
+    *nch = c;
+    if (!hx_control_info(&ec, &in.ec_used, &in.head)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s)\n", name); return false; }
+    j.ctl = conv ? in.ec : ec;          // (a converting batch derives the encoder's control from the source's, as converter_calls did)
+    return true;
+}
+
+// a finished file: what the single-file loop would have written
+bool job_write(Job &j, const char *name, const Options &opt)
+{
+    const Input &in = j.in;
+    const size_t calls = j.nc;
+    Tagger tg;
+    tg.begin(in, opt.xing_flag);
+    for (size_t u = 0; u < calls; u++) tg.after_call(j.fr[u], j.by[u]);
+    size_t u = calls;                               // drain calls: while (get_frames() < frames_expected) encode silence
+    const size_t expected = calls * (in.ec_used.samprate < 32000 ? 2 : 1);   // MPEG-2: two frames per call
+    bool ok = true;
+    while (u < j.fr.size() && j.fr[u - 1] < expected) u++;
+    if (j.fr[u - 1] < expected) { fprintf(stderr, "\n %s: drain did not complete\n", name); ok = false; }
+    const unsigned frames = j.fr[u - 1], nbytes = j.by[u - 1];
+    tg.crc = j.crc;
+    const uint64_t out_bytes = (uint64_t) tg.head_bytes + nbytes;
+    if (opt.xing_flag) tg.finish(in, frames, out_bytes);
+    FILE *o = fopen(name, "wb");
+    if (!o) { fprintf(stderr, "\n CANNOT CREATE OUTPUT FILE %s\n", name); return false; }
+    fwrite(tg.tag.data(), 1, tg.head_bytes, o);
+    fwrite(j.stream.data(), 1, nbytes, o);
+    fclose(o);
+    fprintf(stderr, "\n %s: %u frames, %llu bytes", name, frames, (unsigned long long) out_bytes);
+    return ok;
+}
+
+// loaded: every file's audio is in memory and every file has its own slot; else (-slots) jobs hold the headers only
+int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, const Options &opt, bool loaded)
+{
+    const int S = (int) jobs.size(), NS = loaded ? S : std::min(S, opt.nslots);
     // One file that needs the converter sends all of them through a converting batch (a file at its own MPEG rate is the
     // converter's copy case); without one the plain batch runs, fed fp32 frames made here.
     bool conv = false;
-    for (int i = 0; i < S; i++) conv = conv || needs_conversion(in[i], opt);
-    std::vector<HX_SOURCE> srcs(S);
-    std::vector<size_t> nc(S);                          // calls of the single-file loop on the file's input (the drain follows them)
-    std::vector<std::vector<long long>> start(S);       // converting route: where each of them starts in the file's bytes
+    for (int i = 0; i < S; i++) conv = conv || needs_conversion(jobs[i].in, opt);
     int nch = 0;
-    for (int i = 0; i < S; i++) {
-        HX_E_CONTROL ec = in[i].ec;
-        if (conv) {
-            srcs[i] = {in[i].wi.bits, in[i].is_float, opt.mpeg_select, in[i].mono_convert};
-            const long long n = converter_calls(in[i], opt, &start[i], &ec);
-            if (n < 0) { fprintf(stderr, "\n ENCODER INIT FAIL (%s): %s\n", files[2 * i], hx_last_error()); return 1; }
-            if (n == 0) { fprintf(stderr, "\n %s is shorter than one call of its converter\n", files[2 * i]); return 1; }
-            nc[i] = (size_t) n;
-            ctl[i] = in[i].ec;                          // (the batch derives the encoder's control from the source's, as converter_calls did)
-        } else if (in[i].mono_convert) ec.mode = 3;
-        const int c = ec.mode == 3 ? 1 : 2;
-        if (nch && c != nch) { fprintf(stderr, "\n -batch needs files that all encode to the same channel count\n"); return 1; }
-        nch = c;
-        if (!hx_control_info(&ec, &in[i].ec_used, &in[i].head)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s)\n", files[2 * i]); return 1; }
-        if (conv) continue;
-        ctl[i] = ec;
-        in[i].pad(init_bytes_same_rate(in[i]));
-        nc[i] = ncalls(in[i]);
-    }
+    for (int i = 0; i < S; i++)
+        if ((loaded && conv && !job_calls(jobs[i], files[2 * i], opt, conv)) || !job_control(jobs[i], files[2 * i], opt, conv, &nch) ||
+            (loaded && !conv && !job_calls(jobs[i], files[2 * i], opt, conv))) return 1;
     const int CH = 96;                                  // frames per batched call at most
     const size_t DRAIN = 32;                            // room for a file's drain frames (a reservoir never spans that many)
-    // the files spread over the node's GPUs in contiguous blocks (-Gn limits the count), one host thread per device
-    hx_multi *b = conv ? hx_multi_create_src(opt.ngpus, nullptr, S, ctl.data(), 0, srcs.data(), 0, CH) : hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
+    // the files (the slots) spread over the node's GPUs in contiguous blocks (-Gn limits the count), one host thread per device
+    hx_multi *b = nullptr;
+    std::vector<int> file_cfg(S, 0);                    // -slots: the menu entry of each file
+    if (loaded) {
+        std::vector<HX_E_CONTROL> ctl(S);
+        std::vector<HX_SOURCE> srcs(S);
+        for (int i = 0; i < S; i++) { ctl[i] = jobs[i].ctl; srcs[i] = jobs[i].src; }
+        b = conv ? hx_multi_create_src(opt.ngpus, nullptr, S, ctl.data(), 0, srcs.data(), 0, CH) : hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
+    } else {
+        // the menu: the distinct (control, source) pairs of all files; the slots start with the first files' entries
+        std::vector<HX_E_CONTROL> ctl;
+        std::vector<HX_SOURCE> srcs;
+        for (int i = 0; i < S; i++) {
+            size_t k = 0;
+            while (k < ctl.size() && (memcmp(&ctl[k], &jobs[i].ctl, sizeof(HX_E_CONTROL)) || memcmp(&srcs[k], &jobs[i].src, sizeof(HX_SOURCE)))) k++;
+            if (k == ctl.size()) { ctl.push_back(jobs[i].ctl); srcs.push_back(jobs[i].src); }
+            file_cfg[i] = (int) k;
+        }
+        b = hx_multi_create_menu(opt.ngpus, nullptr, NS, ctl.data(), (int) ctl.size(), conv ? srcs.data() : nullptr, file_cfg.data(), CH);
+    }
     if (!b) {
         // (what cannot share a batch - channel counts, MPEG-1 with MPEG-2 rates, allocator generations: the first file that differs from files[0] in the rates)
         fprintf(stderr, "\n ENCODER INIT FAIL: %s", hx_last_error());
         for (int i = 1; i < S; i++)
-            if ((in[i].ec_used.samprate < 32000) != (in[0].ec_used.samprate < 32000)) { fprintf(stderr, " (%s encodes at %d Hz, %s at %d Hz)", files[2 * i], in[i].ec_used.samprate, files[0], in[0].ec_used.samprate); break; }
+            if ((jobs[i].in.ec_used.samprate < 32000) != (jobs[0].in.ec_used.samprate < 32000)) { fprintf(stderr, " (%s encodes at %d Hz, %s at %d Hz)", files[2 * i], jobs[i].in.ec_used.samprate, files[0], jobs[0].in.ec_used.samprate); break; }
         fprintf(stderr, "\n");
         return 1;
     }
-    if (S > 1) fprintf(stderr, "\n %d files on %d GPU(s)", S, hx_multi_ndevices(b));
-    if (opt.ec_display) print_ec(&in[0].ec_used);
+    if (!loaded) fprintf(stderr, "\n %d files through %d slots on %d GPU(s)", S, NS, hx_multi_ndevices(b));
+    else if (S > 1) fprintf(stderr, "\n %d files on %d GPU(s)", S, hx_multi_ndevices(b));
+    if (opt.ec_display) print_ec(&jobs[0].in.ec_used);
+    // slot -> the file it holds (-1: none any more), and the next file that waits for a slot
+    std::vector<int> held(NS);
+    int next = NS, rc = 0;
+    for (int s = 0; s < NS; s++) {
+        held[s] = s;
+        if (!loaded && (!load_input(files[2 * s], opt, &jobs[s].in, false) || !job_control(jobs[s], files[2 * s], opt, conv, &nch) || !job_calls(jobs[s], files[2 * s], opt, conv))) { hx_multi_destroy(b); return 1; }
+    }
     const long long stride = hx_multi_out_stride(b, CH);
-    std::vector<float> pcm(conv ? 0 : (size_t) S * CH * 1152 * nch), tmp(2304);
+    std::vector<float> pcm(conv ? 0 : (size_t) NS * CH * 1152 * nch), tmp(2304);
     const std::vector<unsigned char> zero_frame(2304 * 4, 0);
     // converting route: a row holds the file's bytes from its next call on, enough for CH calls of any file, then a region of
     // zero bytes that every drain call reads, as the single-file loop hands one zero buffer to all of them
     const long long row_data = conv ? hx_multi_src_in_stride(b, CH) : 0, in_stride = row_data + (conv ? hx_multi_src_in_stride(b, 1) : 0);
-    std::vector<unsigned char> rows((size_t) S * in_stride);
-    std::vector<long long> off(conv ? (size_t) S * CH : 0);
-    std::vector<unsigned char> out((size_t) S * stride);
-    std::vector<int> nb(S), stats((size_t) S * CH * 2);
+    std::vector<unsigned char> rows((size_t) NS * in_stride);
+    std::vector<long long> off(conv ? (size_t) NS * CH : 0);
+    std::vector<unsigned char> out((size_t) NS * stride);
+    std::vector<int> nb(NS), stats((size_t) NS * CH * 2);
     // the MusicCRC per file: every call returns the CRC of its own bytes up to each input frame (k_crc, on the GPU), and the
     // file's is those joined by hx_xing_crc_combine - whole calls, then the call in which the file's drain ends up to there
-    std::vector<unsigned short> crc((size_t) S * CH), file_crc(S, 0);
-    std::vector<char> done(S, 0);                       // the file's drain has ended: it takes no more frames
-    std::vector<std::vector<unsigned char>> stream(S);
-    std::vector<std::vector<unsigned>> fr(S), by(S);    // per frame fed to the file's stream: frames / bytes out so far
+    std::vector<unsigned short> crc((size_t) NS * CH);
     // Every call gives each file the frames it still needs (per-stream frame counts): its input frames, then silence up to the
     // frame at which its drain ends; a finished file takes 0 and costs nothing, and the loop ends with the last file, not
     // DRAIN frames behind the longest one for all.  The call is as long as its largest count.
-    std::vector<int> cnt(S);
+    std::vector<int> cnt(NS), take_slot, take_cfg;
     for (;;) {
         int nf = 0;
-        for (int i = 0; i < S; i++) {
-            const size_t fed = fr[i].size(), room = nc[i] + DRAIN;
-            cnt[i] = (done[i] || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
-            nf = std::max(nf, cnt[i]);
+        for (int s = 0; s < NS; s++) {
+            cnt[s] = 0;
+            if (held[s] < 0) continue;
+            const Job &j = jobs[held[s]];
+            const size_t fed = j.fr.size(), room = j.nc + DRAIN;
+            cnt[s] = (j.done || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
+            nf = std::max(nf, cnt[s]);
         }
         if (nf == 0) break;
-        for (int i = 0; i < S && !conv; i++) {
-            const size_t p0 = fr[i].size();
-            for (int k = 0; k < cnt[i]; k++) {
+        for (int s = 0; s < NS && !conv; s++) {
+            if (cnt[s] == 0) continue;
+            const Job &j = jobs[held[s]];
+            const size_t p0 = j.fr.size();
+            for (int k = 0; k < cnt[s]; k++) {
                 // past the end the single-file loop feeds frames of zero BYTES: silence, except for
                 // 8-bit unsigned input where a zero byte is full-scale negative
-                if (p0 + k < nc[i]) frame_to_float(in[i], in[i].data.data() + (p0 + k) * in[i].frame_in, tmp.data());
-                else frame_to_float(in[i], zero_frame.data(), tmp.data());
-                memcpy(&pcm[((size_t) i * nf + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
+                if (p0 + k < j.nc) frame_to_float(j.in, j.in.data.data() + (p0 + k) * j.in.frame_in, tmp.data());
+                else frame_to_float(j.in, zero_frame.data(), tmp.data());
+                memcpy(&pcm[((size_t) s * nf + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
             }
         }
-        for (int i = 0; i < S && conv; i++) {
+        for (int s = 0; s < NS && conv; s++) {
             // the calls on the file's input start where the schedule puts them, counted from the row's first byte; the
             // drain calls all read the zero region (zero bytes: 8-bit input stays full-scale negative there too)
-            const size_t p0 = fr[i].size();
-            unsigned char *row = rows.data() + (size_t) i * in_stride;
-            if (cnt[i] == 0) continue;
+            if (cnt[s] == 0) continue;
+            const Job &j = jobs[held[s]];
+            const size_t p0 = j.fr.size();
+            unsigned char *row = rows.data() + (size_t) s * in_stride;
             memset(row, 0, (size_t) in_stride);
-            const long long base = p0 < nc[i] ? start[i][p0] : 0;
-            if (p0 < nc[i]) memcpy(row, in[i].data.data() + base, (size_t) std::min<long long>(row_data, (long long) in[i].data.size() - base));
-            for (int k = 0; k < nf; k++) off[(size_t) i * nf + k] = (k < cnt[i] && p0 + k < nc[i]) ? start[i][p0 + k] - base : row_data;
+            const long long base = p0 < j.nc ? j.start[p0] : 0;
+            if (p0 < j.nc) memcpy(row, j.in.data.data() + base, (size_t) std::min<long long>(row_data, (long long) j.in.data.size() - base));
+            for (int k = 0; k < nf; k++) off[(size_t) s * nf + k] = (k < cnt[s] && p0 + k < j.nc) ? j.start[p0 + k] - base : row_data;
         }
         const int rc_call = conv ? hx_multi_encode_src_counts_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), out.data(), stride, nb.data(), nullptr, stats.data(), crc.data())
                                  : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
@@ -567,48 +659,44 @@ int encode_loaded(std::vector<Input> &in, const std::vector<const char *> &files
             hx_multi_destroy(b);
             return 1;
         }
-        for (int i = 0; i < S; i++) {
-            const int n = cnt[i];
+        take_slot.clear(); take_cfg.clear();
+        for (int s = 0; s < NS; s++) {
+            const int n = cnt[s];
             if (n == 0) continue;
-            const size_t p0 = fr[i].size();
-            stream[i].insert(stream[i].end(), out.begin() + (size_t) i * stride, out.begin() + (size_t) i * stride + nb[i]);
-            for (int k = 0; k < n; k++) { fr[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2]); by[i].push_back((unsigned) stats[((size_t) i * nf + k) * 2 + 1]); }
-            // the last frame the file uses (the per-file loop below: u - 1), if it lies in this call
-            const size_t calls = nc[i], expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);
+            Job &j = jobs[held[s]];
+            const size_t p0 = j.fr.size();
+            j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + nb[s]);
+            for (int k = 0; k < n; k++) { j.fr.push_back((unsigned) stats[((size_t) s * nf + k) * 2]); j.by.push_back((unsigned) stats[((size_t) s * nf + k) * 2 + 1]); }
+            // the last frame the file uses (job_write: u - 1), if it lies in this call
+            const size_t calls = j.nc, expected = calls * (j.in.ec_used.samprate < 32000 ? 2 : 1);
             int k = p0 + n >= calls ? (int) (calls > p0 + 1 ? calls - 1 - p0 : 0) : n;
-            while (k < n && fr[i][p0 + k] < expected) k++;
+            while (k < n && j.fr[p0 + k] < expected) k++;
             if (k < n) {
-                const unsigned e = (unsigned) nb[i] - (by[i][p0 + n - 1] - by[i][p0 + k]);      // this call's bytes up to there
-                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * nf + k], (long long) e);
-                done[i] = 1;
+                const unsigned e = (unsigned) nb[s] - (j.by[p0 + n - 1] - j.by[p0 + k]);        // this call's bytes up to there
+                j.crc = hx_xing_crc_combine(j.crc, crc[(size_t) s * nf + k], (long long) e);
+                j.done = true;
             } else
-                file_crc[i] = hx_xing_crc_combine(file_crc[i], crc[(size_t) i * nf + n - 1], nb[i]);
+                j.crc = hx_xing_crc_combine(j.crc, crc[(size_t) s * nf + n - 1], nb[s]);
+            if (loaded || !(j.done || j.fr.size() >= j.nc + DRAIN)) continue;
+            // -slots: the file is written and freed, and its slot goes to the next file that waits
+            if (!job_write(j, files[2 * held[s] + 1], opt)) rc = 1;
+            j = Job();
+            held[s] = -1;
+            if (next == S) continue;
+            const int i = next++;
+            if (!load_input(files[2 * i], opt, &jobs[i].in, false) || !job_control(jobs[i], files[2 * i], opt, conv, &nch) || !job_calls(jobs[i], files[2 * i], opt, conv)) { hx_multi_destroy(b); return 1; }
+            held[s] = i;
+            take_slot.push_back(s); take_cfg.push_back(file_cfg[i]);
+        }
+        if (!take_slot.empty() && hx_multi_assign_streams(b, take_slot.data(), take_cfg.data(), (int) take_slot.size()) != 0) {
+            fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
+            hx_multi_destroy(b);
+            return 1;
         }
     }
     if (hx_multi_status(b) != 0) fprintf(stderr, "\n WARNING: kernel status %d\n", hx_multi_status(b));
     hx_multi_destroy(b);
-    // per file: what the single-file loop would have written
-    int rc = 0;
-    for (int i = 0; i < S; i++) {
-        const size_t calls = nc[i];
-        Tagger tg;
-        tg.begin(in[i], opt.xing_flag);
-        for (size_t u = 0; u < calls; u++) tg.after_call(fr[i][u], by[i][u]);
-        size_t u = calls;                               // drain calls: while (get_frames() < frames_expected) encode silence
-        const size_t expected = calls * (in[i].ec_used.samprate < 32000 ? 2 : 1);   // MPEG-2: two frames per call
-        while (u < fr[i].size() && fr[i][u - 1] < expected) u++;
-        if (fr[i][u - 1] < expected) { fprintf(stderr, "\n %s: drain did not complete\n", files[2 * i]); rc = 1; }
-        const unsigned frames = fr[i][u - 1], nbytes = by[i][u - 1];
-        tg.crc = file_crc[i];
-        const uint64_t out_bytes = (uint64_t) tg.head_bytes + nbytes;
-        if (opt.xing_flag) tg.finish(in[i], frames, out_bytes);
-        FILE *o = fopen(files[2 * i + 1], "wb");
-        if (!o) { fprintf(stderr, "\n CANNOT CREATE OUTPUT FILE %s\n", files[2 * i + 1]); rc = 1; continue; }
-        fwrite(tg.tag.data(), 1, tg.head_bytes, o);
-        fwrite(stream[i].data(), 1, nbytes, o);
-        fclose(o);
-        fprintf(stderr, "\n %s: %u frames, %llu bytes", files[2 * i + 1], frames, (unsigned long long) out_bytes);
-    }
+    for (int i = 0; i < S && loaded; i++) if (!job_write(jobs[i], files[2 * i + 1], opt)) rc = 1;
     fprintf(stderr, "\n");
     return rc;
 }
@@ -626,6 +714,7 @@ int main(int argc, char **argv)
         const char *a = argv[i];
         if (a[0] != '-' || a[1] == '\0') { files.push_back(a); continue; }
         if (!strcmp(a, "-batch")) { batch = true; continue; }
+        if (!strncmp(a, "-slots", 6)) { opt.nslots = atoi(a + 6); continue; }      // (before the switch: -s... is -S<n>, the DC blocker)
         HX_E_CONTROL &ec = opt.ec;
         const char c = (char) (a[1] | 0x20), c2 = (char) (a[2] | 0x20);
         switch (c) {

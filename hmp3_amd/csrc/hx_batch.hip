@@ -87,9 +87,33 @@ extern "C" void hx_batch_destroy(hx_batch *b)
     delete b;
 }
 
-extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+// "<label> <number>: " in front of a refusal that names a menu entry (MenuNames)
+static std::string entry_prefix(const char *label, const int *origin, int j)
 {
-    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
+    char msg[64] = "";
+    if (label) snprintf(msg, sizeof msg, "%s %d: ", label, origin ? origin[j] : j);
+    return msg;
+}
+
+hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg, int max_frames,
+                       const MenuNames &names)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
+    for (int s = 0; cfg && s < nstreams; s++)
+        if (cfg[s] < 0 || cfg[s] >= nmenu) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "stream %d: configuration %d out of range (0 .. %d)", s, cfg[s], nmenu - 1);
+            set_err("%s", msg);
+            return nullptr;
+        }
+    // a converting batch: every entry's encode control and converter plan
+    std::vector<HX_E_CONTROL> ecs;
+    std::vector<HxSrcPlan> plans;
+    std::vector<int> menu_plan;
+    if (src) {
+        if (src_menu(ec, src, nmenu, names, ecs, plans, menu_plan) != 0) return nullptr;
+        ec = ecs.data();
+    }
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return nullptr; }
     if (device < 0 || device >= ndev) { set_err("device index out of range"); return nullptr; }
@@ -104,32 +128,38 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     hx_batch *b = new hx_batch;
     b->device = device; b->S = nstreams; b->maxF = max_frames;
     b->cls_of.resize(nstreams);
-    // group streams into configuration classes
+    b->cfg_of.resize(nstreams);
+    b->menu_cls.resize(nmenu);
+    b->menu_plan = menu_plan;
+    // group the menu's entries into configuration classes: everything the batch sizes or decides from its classes is taken
+    // over the whole menu, whichever entries the slots start with
     std::vector<HxControl> seen;
-    for (int s = 0; s < nstreams; s++) {
-        const HxControl *c = (const HxControl *) (shared_control ? ec : ec + s);
+    for (int j = 0; j < nmenu; j++) {
+        const HxControl *c = (const HxControl *) (ec + j);
         int k = -1;
         for (size_t i = 0; i < seen.size(); i++) if (memcmp(&seen[i], c, sizeof(HxControl)) == 0) { k = (int) i; break; }
         if (k < 0) {
+            const std::string pre = entry_prefix(names.cls_label, names.origin, j);
+#define REFUSE_ENTRY(text) do { set_err("%s", (pre + (text)).c_str()); delete b; return nullptr; } while (0)
             HxParams p;
             if (!hx_resolve(c, &p)) {
                 // (a limit of this library's layout is named as such: the reference would have taken the configuration)
-                if (*hx_resolve_error()) set_err("configuration rejected: %s", hx_resolve_error());
-                else set_err("configuration rejected (the reference's L3_audio_encode_init returns 0 for it)");
-                delete b; return nullptr;
+                if (*hx_resolve_error()) REFUSE_ENTRY(std::string("configuration rejected: ") + hx_resolve_error());
+                REFUSE_ENTRY("configuration rejected (the reference's L3_audio_encode_init returns 0 for it)");
             }
             if (p.filter_dc) b->any_dc = true;
             if (b->params.empty()) { b->nchan = p.nchan; b->lsf = p.h_id ? 0 : 1; b->alloc1 = p.alloc1; }
-            else if (p.alloc1 != b->alloc1) { set_err("intensity-stereo / dual-channel streams (first-generation allocator) cannot share a batch with the others"); delete b; return nullptr; }
-            else if (p.nchan != b->nchan) { set_err("mono and stereo streams cannot share a batch (the PCM layout differs)"); delete b; return nullptr; }
-            else if ((p.h_id ? 0 : 1) != b->lsf) { set_err("MPEG-1 and MPEG-2 sample rates cannot share a batch (frames per call differ)"); delete b; return nullptr; }
+            else if (p.alloc1 != b->alloc1) REFUSE_ENTRY("intensity-stereo / dual-channel streams (first-generation allocator) cannot share a batch with the others");
+            else if (p.nchan != b->nchan) REFUSE_ENTRY("mono and stereo streams cannot share a batch (the PCM layout differs)");
+            else if ((p.h_id ? 0 : 1) != b->lsf) REFUSE_ENTRY("MPEG-1 and MPEG-2 sample rates cannot share a batch (frames per call differ)");
+#undef REFUSE_ENTRY
             seen.push_back(*c);
             b->params.push_back(p);
             k = (int) seen.size() - 1;
         }
-        b->cls_of[s] = k;
-        if (shared_control) { for (int t = 1; t < nstreams; t++) b->cls_of[t] = 0; break; }
+        b->menu_cls[j] = k;
     }
+    for (int s = 0; s < nstreams; s++) { b->cfg_of[s] = cfg ? cfg[s] : 0; b->cls_of[s] = b->menu_cls[b->cfg_of[s]]; }
     b->ncls = (int) b->params.size();
     const long long S = nstreams, NG = 2LL * max_frames;
     std::vector<HxGlobalTabs> gt_host(1);       // (144 KB: not on the stack)
@@ -189,8 +219,32 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     HIPCHKN(hipMemset(b->d_sb, 0, sizeof(float) * S * 2 * (NG + 3) * 576));
     HIPCHKN(hipMemset(b->d_status, 0, sizeof(int)));
     b->lastNG = 0;
+    if (src && src_setup(b, plans) != 0) { hx_batch_destroy(b); return nullptr; }
     return b;
 }
+
+extern "C" hx_batch *hx_batch_create_menu(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg, int max_frames)
+{
+    return batch_create(device, nstreams, ec, nmenu, src, cfg, max_frames, MenuNames{"menu entry", "menu entry", nullptr});
+}
+// the menu of a batch created from per-stream controls: the distinct ones, in order of first appearance
+extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec) { set_err("bad arguments"); return nullptr; }
+    if (shared_control) return batch_create(device, nstreams, ec, 1, nullptr, nullptr, max_frames, MenuNames{nullptr, nullptr, nullptr});
+    std::vector<HX_E_CONTROL> menu;
+    std::vector<int> cfg(nstreams);
+    for (int s = 0; s < nstreams; s++) {
+        int k = -1;
+        for (size_t i = 0; i < menu.size(); i++) if (memcmp(&menu[i], ec + s, sizeof(HX_E_CONTROL)) == 0) { k = (int) i; break; }
+        if (k < 0) { menu.push_back(ec[s]); k = (int) menu.size() - 1; }
+        cfg[s] = k;
+    }
+    return batch_create(device, nstreams, menu.data(), (int) menu.size(), nullptr, cfg.data(), max_frames, MenuNames{nullptr, nullptr, nullptr});
+}
+
+extern "C" int hx_batch_nconfigs(const hx_batch *b) { return b ? (int) b->menu_cls.size() : 0; }
+extern "C" int hx_batch_stream_config(const hx_batch *b, int i) { return (b && i >= 0 && i < b->S) ? b->cfg_of[i] : -1; }
 
 extern "C" int hx_batch_nstreams(const hx_batch *b) { return b ? b->S : 0; }
 

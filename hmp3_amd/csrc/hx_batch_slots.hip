@@ -41,10 +41,13 @@ int slots_init(hx_batch *b)
 }
 int slots_src_init(hx_batch *b)
 {
-    std::vector<unsigned long long> fp(b->S);
-    for (int s = 0; s < b->S; s++) fp[s] = plan_fingerprint(b->src_plans[b->src_cls[s]]);
-    if (dev_alloc(b, b->d_src_fp, (long long) sizeof(unsigned long long) * b->S) != 0) return -1;
+    std::vector<unsigned long long> fp(b->S), pfp(b->nsrc);
+    for (int k = 0; k < b->nsrc; k++) pfp[k] = plan_fingerprint(b->src_plans[k]);
+    for (int s = 0; s < b->S; s++) fp[s] = pfp[b->src_cls[s]];
+    if (dev_alloc(b, b->d_src_fp, (long long) sizeof(unsigned long long) * b->S) != 0 ||
+        dev_alloc(b, b->d_plan_fp, (long long) sizeof(unsigned long long) * b->nsrc) != 0) return -1;
     HIPCHK(hipMemcpy(b->d_src_fp, fp.data(), sizeof(unsigned long long) * b->S, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(b->d_plan_fp, pfp.data(), sizeof(unsigned long long) * b->nsrc, hipMemcpyHostToDevice));
     return 0;
 }
 
@@ -103,7 +106,8 @@ static int slots_check(hx_batch *b, const int *idx, int n, bool blobs, const voi
 // rotation of the slot operations' own; the copy's event is recorded behind the kernel that reads the device list, so
 // refilling copy k three operations later waits for that operation as a whole, whatever streams the operations in between
 // were made on.
-static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs, long long stride, hipStream_t q)
+// cfg (a reset): null, or [n] the menu entry each listed slot takes; its entry then carries that menu entry's class and plan
+static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs, long long stride, hipStream_t q, const int *cfg = nullptr)
 {
     HIPCHK(hipSetDevice(b->device));
     Staging &s = b->ent_stage;
@@ -116,18 +120,23 @@ static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs,
     const int k = (int) (b->nslotops++ % 3);
     HxSlotEntry *h = (HxSlotEntry *) staging_take(s, k);
     if (!h) return -1;
-    for (int e = 0; e < n; e++) h[e] = HxSlotEntry{idx[e], b->cls_of[idx[e]], b->cls_fp[b->cls_of[idx[e]]]};
+    for (int e = 0; e < n; e++) {
+        const int cls = cfg ? b->menu_cls[cfg[e]] : b->cls_of[idx[e]];
+        h[e] = HxSlotEntry{idx[e], cls, b->cls_fp[cls], b->nsrc ? (cfg ? b->menu_plan[cfg[e]] : b->src_cls[idx[e]]) : 0, 0};
+    }
     if (staging_upload(s, k, sizeof(HxSlotEntry) * (size_t) n, q) != 0) return -1;
     SlotArgs a;
     a.ent = s.dev<HxSlotEntry>(k); a.st = b->d_st; a.init = b->d_init; a.sb = b->d_sb; a.sb_row = (2LL * b->maxF + 3) * 576;
     a.src_calls = b->nsrc ? b->d_src_calls : nullptr; a.src_carry = b->d_src_carry; a.src_fp = b->d_src_fp;
+    a.src_cls = b->d_src_cls; a.plan_fp = b->d_plan_fp;
     a.S = b->S; a.src_par = b->src_par;
     a.magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC; a.version = HX_STATE_VERSION;
     a.status = b->d_status;
     a.blob_words = stride / 8;
-    // words behind the header that the kernel walks (a reset leaves the converter's carried samples: call 0 reads none)
+    // words behind the header that the kernel walks (a reset leaves the converter's carried samples - call 0 of any plan
+    // reads none - and its lane behind the two call counts writes the slot's plan and plan fingerprint)
     const long long state_words = b->nsrc ? HX_SLOT_SRC_CARRY_WORD + HX_SLOT_SRC_CARRY_WORDS : HX_SLOT_SRC_WORD;
-    const long long words = op == SLOT_GATHER ? a.blob_words : op == SLOT_SCATTER ? state_words : b->nsrc ? HX_SLOT_SRC_CARRY_WORD : HX_SLOT_SRC_WORD;
+    const long long words = op == SLOT_GATHER ? a.blob_words : op == SLOT_SCATTER ? state_words : b->nsrc ? HX_SLOT_SRC_CARRY_WORD + 1 : HX_SLOT_SRC_WORD;
     a.chunks = (int) ((words + HX_SLOT_CHUNK - 1) / HX_SLOT_CHUNK);
     const dim3 grid((unsigned) ((long long) n * a.chunks));
     if (op == SLOT_RESET) LAUNCH(k_slot_reset, grid, dim3(256), q, a);
@@ -137,19 +146,41 @@ static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs,
     return poison.ok();
 }
 
-// A reset of n slots on stream q; wait (hx_batch_reset_stream): behind everything in flight, and done when it returns.
-static int reset_slots(hx_batch *b, const int *idx, int n, hipStream_t q, bool wait)
+// n slots start new streams on stream q, slot idx[e] of menu entry cfg[e] (cfg null, hx_batch_reset_streams: of the entry it
+// runs); wait (hx_batch_reset_stream): behind everything in flight, and done when it returns.  The host's view of the
+// slots - entry, class, plan, converter call count - moves here, when the call is made; the device follows in stream order.
+int assign_slots(hx_batch *b, const int *idx, const int *cfg, int n, void *stream, bool wait)
 {
+    const hipStream_t q = (hipStream_t) stream;
     if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    for (int e = 0; cfg && e < n; e++)
+        if (cfg[e] < 0 || cfg[e] >= (int) b->menu_cls.size()) {
+            char msg[96];
+            snprintf(msg, sizeof msg, "entry %d: configuration %d out of range (0 .. %d)", e, cfg[e], (int) b->menu_cls.size() - 1);
+            set_err("%s", msg);
+            return -1;
+        }
     if (n == 0) return 0;
     if (wait && drain(b) != 0) return -1;
-    if (slot_op(b, SLOT_RESET, idx, n, nullptr, 0, q) != 0) return -1;
-    for (int e = 0; e < n && b->nsrc; e++) b->src_calls[idx[e]] = 0;        // (the converters start over: the host's count is the authoritative one)
+    if (slot_op(b, SLOT_RESET, idx, n, nullptr, 0, q, cfg) != 0) return -1;
+    for (int e = 0; e < n; e++) {
+        const int s = idx[e];
+        if (cfg) { b->cfg_of[s] = cfg[e]; b->cls_of[s] = b->menu_cls[cfg[e]]; }
+        if (b->nsrc) {          // (the converters start over: the host's count is the authoritative one)
+            if (cfg) b->src_cls[s] = b->menu_plan[cfg[e]];
+            b->src_calls[s] = 0;
+        }
+    }
     if (wait) HIPCHK(hipStreamSynchronize(q));
     return 0;
 }
-extern "C" int hx_batch_reset_streams(hx_batch *b, const int *idx, int n, void *stream) { return reset_slots(b, idx, n, (hipStream_t) stream, false); }
-extern "C" int hx_batch_reset_stream(hx_batch *b, int i) { return reset_slots(b, &i, 1, nullptr, true); }
+extern "C" int hx_batch_reset_streams(hx_batch *b, const int *idx, int n, void *stream) { return assign_slots(b, idx, nullptr, n, stream, false); }
+extern "C" int hx_batch_reset_stream(hx_batch *b, int i) { return assign_slots(b, &i, nullptr, 1, nullptr, true); }
+extern "C" int hx_batch_assign_streams(hx_batch *b, const int *idx, const int *cfg, int n, void *stream)
+{
+    if (b && n > 0 && !cfg) { set_err("cfg is null with n > 0"); return -1; }
+    return assign_slots(b, idx, cfg, n, stream, false);
+}
 
 extern "C" int hx_batch_get_stream_states_device(hx_batch *b, const int *idx, int n, void *d_blobs, long long blob_stride, void *stream)
 {

@@ -5,43 +5,46 @@
 #include <string>
 #include "hx_rt.h"
 
-extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, const HX_SOURCE *src,
-                                         int shared_source, int max_frames)
+int src_menu(const HX_E_CONTROL *ec, const HX_SOURCE *src, int nmenu, const MenuNames &names, std::vector<HX_E_CONTROL> &ecs,
+             std::vector<HxSrcPlan> &plans, std::vector<int> &menu_plan)
 {
-    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
-    std::vector<HX_E_CONTROL> ecs(nstreams);
-    std::vector<HxSrcPlan> plans;
-    std::vector<int> cls(nstreams);
+    ecs.resize(nmenu);
+    menu_plan.resize(nmenu);
     hx_src *conv = hx_src_create();
-    for (int s = 0; s < nstreams; s++) {
-        const HX_SOURCE &sc = shared_source ? src[0] : src[s];
+    for (int j = 0; j < nmenu; j++) {
+        const HX_SOURCE &sc = src[j];
         HxSrcPlan p;
-        if (!src_encode_control(shared_control ? ec : ec + s, sc.bits, sc.is_float, sc.mpeg_select, sc.mono_convert, conv, &ecs[s]) ||
-            !hx_src_plan(conv, &p)) {
-            char msg[64];
-            snprintf(msg, sizeof msg, "stream %d: ", s);
+        if (!src_encode_control(ec + j, sc.bits, sc.is_float, sc.mpeg_select, sc.mono_convert, conv, &ecs[j]) || !hx_src_plan(conv, &p)) {
+            char msg[64] = "";
+            if (names.src_label) snprintf(msg, sizeof msg, "%s %d: ", names.src_label, names.origin ? names.origin[j] : j);
             const std::string why = hx_last_error();
             set_err("%s", (msg + why).c_str());
             hx_src_destroy(conv);
-            return nullptr;
+            return -1;
         }
         int k = -1;
         for (size_t i = 0; i < plans.size(); i++) if (memcmp(&plans[i], &p, sizeof(p)) == 0) { k = (int) i; break; }
         if (k < 0) { plans.push_back(p); k = (int) plans.size() - 1; }
-        cls[s] = k;
+        menu_plan[j] = k;
     }
     hx_src_destroy(conv);
-    hx_batch *b = hx_batch_create(device, nstreams, ecs.data(), 0, max_frames);
-    if (!b) return nullptr;
+    return 0;
+}
+
+// the converter of a batch whose encoder part stands: LDS layout, buffers and tables over all of the menu's plans
+int src_setup(hx_batch *b, const std::vector<HxSrcPlan> &plans)
+{
+    const int nstreams = b->S, max_frames = b->maxF;
     b->nsrc = (int) plans.size();
     b->src_plans = plans;
-    b->src_cls = cls;
+    b->src_cls.resize(nstreams);
+    for (int s = 0; s < nstreams; s++) b->src_cls[s] = b->menu_plan[b->cfg_of[s]];
     b->src_calls.assign(nstreams, 0);
     // LDS of a workgroup: the input window (source channels, interleaved), the intermediate samples (output channels,
     // case 4) and the filter bank (cases 2 - 4), each sized for the batch's largest plan
     int xf = 0, zf = 0, cf = 0;
     for (const HxSrcPlan &p : plans) {
-        if (p.nch != b->nchan) { set_err("a converter's output channels differ from the batch's"); hx_batch_destroy(b); return nullptr; }
+        if (p.nch != b->nchan) { set_err("a converter's output channels differ from the batch's"); return -1; }
         if (p.xwin > b->src_xwin) b->src_xwin = p.xwin;
         if (p.zwin > b->src_zwin) b->src_zwin = p.zwin;
         xf = std::max(xf, p.channels * p.xwin);
@@ -51,31 +54,46 @@ extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CO
     b->src_zoff = xf;
     b->src_coff = xf + zf;
     b->src_lds = sizeof(float) * ((size_t) xf + zf + cf);
-    if (b->src_lds > 160 * 1024) { set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr; }
+    if (b->src_lds > 160 * 1024) { set_err("the converter's window does not fit a workgroup's LDS"); return -1; }
     if (b->src_lds > 64 * 1024 && hipFuncSetAttribute((const void *) k_src, hipFuncAttributeMaxDynamicSharedMemorySize, (int) b->src_lds) != hipSuccess) {
-        set_err("the converter's window does not fit a workgroup's LDS"); hx_batch_destroy(b); return nullptr;
+        set_err("the converter's window does not fit a workgroup's LDS"); return -1;
     }
     const long long S = nstreams;
-#define ALLOC_SRC(ptr, bytes) do { if (dev_alloc(b, ptr, bytes) != 0) { hx_batch_destroy(b); return nullptr; } } while (0)
-    ALLOC_SRC(b->d_src_plan, sizeof(HxSrcPlan) * plans.size());
-    ALLOC_SRC(b->d_src_cls, sizeof(int) * S);
-    ALLOC_SRC(b->d_src_calls, sizeof(long long) * 2 * S);
-    ALLOC_SRC(b->d_src_carry, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY);
-    ALLOC_SRC(b->d_src_pcm, sizeof(float) * S * max_frames * 1152 * b->nchan);
-    ALLOC_SRC(b->d_src_off, sizeof(long long) * S * max_frames);
-#undef ALLOC_SRC
-    if (host_alloc(b, b->h_src_off, sizeof(long long) * S * max_frames) != 0) { hx_batch_destroy(b); return nullptr; }
+    if (dev_alloc(b, b->d_src_plan, sizeof(HxSrcPlan) * plans.size()) || dev_alloc(b, b->d_src_cls, sizeof(int) * S) ||
+        dev_alloc(b, b->d_src_calls, sizeof(long long) * 2 * S) || dev_alloc(b, b->d_src_carry, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY) ||
+        dev_alloc(b, b->d_src_pcm, sizeof(float) * S * max_frames * 1152 * b->nchan) || dev_alloc(b, b->d_src_off, sizeof(long long) * S * max_frames) ||
+        host_alloc(b, b->h_src_off, sizeof(long long) * S * max_frames) != 0)
+        return -1;
     if (new_event(b, b->ev_src_off) != 0 || slots_src_init(b) != 0 ||
         hipMemcpy(b->d_src_plan, plans.data(), sizeof(HxSrcPlan) * plans.size(), hipMemcpyHostToDevice) != hipSuccess ||
-        hipMemcpy(b->d_src_cls, cls.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess ||
+        hipMemcpy(b->d_src_cls, b->src_cls.data(), sizeof(int) * S, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(b->d_src_calls, 0, sizeof(long long) * 2 * S) != hipSuccess ||
         hipMemset(b->d_src_carry, 0, sizeof(float) * 2 * S * 2 * HX_SRC_CARRY) != hipSuccess ||
         hipEventRecord(b->ev_src_off, nullptr) != hipSuccess) {
         set_err("HIP error while setting up the converter");
-        hx_batch_destroy(b);
-        return nullptr;
+        return -1;
     }
-    return b;
+    return 0;
+}
+
+// the menu of a batch created from per-stream controls and sources: the distinct pairs, in order of first appearance (a
+// refusal names the first stream of the pair, which is the first stream it would have been refused for)
+extern "C" hx_batch *hx_batch_create_src(int device, int nstreams, const HX_E_CONTROL *ec, int shared_control, const HX_SOURCE *src,
+                                         int shared_source, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || !src) { set_err("bad arguments"); return nullptr; }
+    std::vector<HX_E_CONTROL> mec;
+    std::vector<HX_SOURCE> msrc;
+    std::vector<int> cfg(nstreams), origin;
+    for (int s = 0; s < nstreams; s++) {
+        const HX_E_CONTROL &c = shared_control ? ec[0] : ec[s];
+        const HX_SOURCE &sc = shared_source ? src[0] : src[s];
+        int k = -1;
+        for (size_t i = 0; i < mec.size(); i++) if (memcmp(&mec[i], &c, sizeof(c)) == 0 && memcmp(&msrc[i], &sc, sizeof(sc)) == 0) { k = (int) i; break; }
+        if (k < 0) { mec.push_back(c); msrc.push_back(sc); origin.push_back(s); k = (int) mec.size() - 1; }
+        cfg[s] = k;
+    }
+    return batch_create(device, nstreams, mec.data(), (int) mec.size(), msrc.data(), cfg.data(), max_frames, MenuNames{"stream", nullptr, origin.data()});
 }
 
 extern "C" long long hx_batch_src_schedule(const hx_batch *b, int i, int nframes, long long *in_bytes)

@@ -166,6 +166,48 @@ extern "C" hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstre
     });
 }
 
+// every block's batch gets the whole menu, and its streams' part of cfg
+extern "C" hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                                          const int *cfg, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create_menu(dev, count, ec, nmenu, src, cfg ? cfg + first : nullptr, max_frames);
+    });
+}
+
+// hx_batch_assign_streams over all streams.  All blocks or none: every refusal is made here, with the caller's entry
+// numbers, before one block starts; then each block takes its part of the list, waits for its work in flight and is done
+// when the call returns.
+extern "C" int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *cfg, int n)
+{
+    char msg[160];
+#define REFUSE(...) do { snprintf(msg, sizeof msg, __VA_ARGS__); set_err("%s", msg); return -1; } while (0)
+    if (!m) { set_err("null handle"); return -1; }
+    for (hx_batch *b : m->part) if (check_poisoned(b) != 0) return -1;
+    if (n < 0) REFUSE("n = %d: the number of listed slots cannot be negative", n);
+    if (n > 0 && !idx) { set_err("idx is null with n > 0"); return -1; }
+    if (n > 0 && !cfg) { set_err("cfg is null with n > 0"); return -1; }
+    const int nmenu = hx_batch_nconfigs(m->part[0]);
+    const size_t nb = m->part.size();
+    std::vector<char> listed(m->S, 0);
+    std::vector<std::vector<int>> bi(nb), bc(nb);
+    for (int e = 0; e < n; e++) {
+        if (idx[e] < 0 || idx[e] >= m->S) REFUSE("entry %d: slot %d out of range (0 .. %d)", e, idx[e], m->S - 1);
+        if (listed[idx[e]]) REFUSE("entry %d: slot %d is listed twice", e, idx[e]);
+        if (cfg[e] < 0 || cfg[e] >= nmenu) REFUSE("entry %d: configuration %d out of range (0 .. %d)", e, cfg[e], nmenu - 1);
+        listed[idx[e]] = 1;
+        size_t k = 0;
+        while (k + 1 < nb && idx[e] >= m->first[k + 1]) k++;
+        bi[k].push_back(idx[e] - m->first[k]);
+        bc[k].push_back(cfg[e]);
+    }
+#undef REFUSE
+    for (size_t k = 0; k < nb; k++)
+        if (!bi[k].empty() && assign_slots(m->part[k], bi[k].data(), bc[k].data(), (int) bi[k].size(), nullptr, true) != 0) return -1;
+    return 0;
+}
+
 extern "C" int hx_multi_ndevices(const hx_multi *m) { return m ? (int) m->part.size() : 0; }
 extern "C" int hx_multi_nstreams(const hx_multi *m) { return m ? m->S : 0; }
 extern "C" hx_batch *hx_multi_batch(hx_multi *m, int k) { return (m && k >= 0 && k < (int) m->part.size()) ? m->part[k] : nullptr; }

@@ -128,6 +128,11 @@ struct hx_batch {
     int device = 0, S = 0, maxF = 0, ncls = 0;
     std::vector<HxParams> params;       // host copy per class
     std::vector<int> cls_of;            // stream -> class
+    // The menu of configurations the batch was created with (hx_batch_create_menu; hx_batch_create[_src]: their deduplicated
+    // controls): entry -> class and (converting batches) entry -> plan, identical entries sharing theirs, and the caller's
+    // entry each slot runs.  cfg_of, cls_of and src_cls move when hx_batch_assign_streams is called; the device follows in
+    // stream order.
+    std::vector<int> menu_cls, menu_plan, cfg_of;
     HxParams *d_prm = nullptr;
     HxGlobalTabs *d_gt = nullptr;
     HxStream *d_st = nullptr;
@@ -178,6 +183,7 @@ struct hx_batch {
     HxStream *d_init = nullptr;         // [ncls]
     std::vector<unsigned long long> cls_fp;     // [ncls]
     unsigned long long *d_src_fp = nullptr;     // [S]
+    unsigned long long *d_plan_fp = nullptr;    // [nsrc] each plan's fingerprint (k_slot_reset takes a slot's from here)
     Staging ent_stage;
     long long nslotops = 0;
     std::vector<long long> slot_mark;   // [S] the last operation that listed the slot (duplicates)
@@ -357,6 +363,21 @@ HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, v
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
                          unsigned short *crc = nullptr);
+// The one create path (hx_batch.hip).  ec[nmenu] (and src[nmenu]: a converting batch) is the menu, cfg[nstreams] or null
+// (= entry 0) the entry each slot starts with.  A refusal names the entry as "<label> <origin[j]>: " - src_label for what
+// the converter rejects, cls_label for what the encoder's init or the batch's kind rejects; a null label: no prefix; a null
+// origin: the entry's own number.
+struct MenuNames { const char *src_label, *cls_label; const int *origin; };
+HX_LOCAL hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg,
+                                int max_frames, const MenuNames &names);
+// ... its converter parts (hx_batch_src.hip): every entry's encode control and plan (plans deduplicated), before anything
+// touches the device; and the converter's buffers, sized over all plans
+HX_LOCAL int src_menu(const HX_E_CONTROL *ec, const HX_SOURCE *src, int nmenu, const MenuNames &names, std::vector<HX_E_CONTROL> &ecs,
+                      std::vector<HxSrcPlan> &plans, std::vector<int> &menu_plan);
+HX_LOCAL int src_setup(hx_batch *b, const std::vector<HxSrcPlan> &plans);
+// hx_batch_assign_streams (cfg null: hx_batch_reset_streams) on stream q; wait: behind everything in flight, and done when
+// it returns
+HX_LOCAL int assign_slots(hx_batch *b, const int *idx, const int *cfg, int n, void *stream, bool wait);
 // Slot state (hx_batch_slots.hip), set up at create: what a new stream of each class starts with, each class's blob
 // fingerprint and the duplicate marks (hx_batch_create); a converting batch's per-stream plan fingerprints on the device,
 // which the slot kernels check and write (hx_batch_create_src)

@@ -12,7 +12,7 @@
 // [0, n * blob_stride) of the blob array.  The host has checked that every slot is in range and listed once.
 #include "hx_dev.h"
 
-static_assert(sizeof(HxSlotEntry) == 16, "the host stages the entries as 16-byte records");
+static_assert(sizeof(HxSlotEntry) == 24, "the host stages the entries as 24-byte records");
 static_assert(HX_SLOT_SRC_WORD == HX_SLOT_ST_WORDS + 2 * HX_SLOT_CARRY_WORDS, "slot_word walks the parts in the blob's order (hx_types.h)");
 
 __device__ __forceinline__ uint2 slot_split(unsigned long long v) { return make_uint2((unsigned) v, (unsigned) (v >> 32)); }
@@ -35,8 +35,10 @@ __device__ __forceinline__ uint2 *slot_word(const SlotArgs &a, int slot, int w)
     return nullptr;
 }
 
-// Every listed slot becomes a new stream of its class: the class's initial HxStream, a zero subband carry and (converting
-// batches) zero call counts in both copies.  Only slots 0..2 of the two subband rows are zeroed: k_polyphase writes slots
+// Every listed slot becomes a new stream of its entry's class: the class's initial HxStream, a zero subband carry and
+// (converting batches) zero call counts in both copies, the entry's plan in the slot's word of src_cls and that plan's
+// fingerprint in its word of src_fp - the same values as before when the slot keeps its configuration.  The converter's
+// carried samples stay: call 0 of any plan reads none (hx_src.hip: qstart(0) = u(0) = 0).  Only slots 0..2 of the two subband rows are zeroed: k_polyphase writes slots
 // 3 .. NG + 2 of a call before k_spec (slots 0 .. NG) and k_msscan (slots NG .. NG + 2) read them, and its own read is of
 // slot 2.
 __global__ __launch_bounds__(256) void k_slot_reset(SlotArgs a)
@@ -55,6 +57,7 @@ __global__ __launch_bounds__(256) void k_slot_reset(SlotArgs a)
         const int w = c * HX_SLOT_CHUNK + 256 * k + (int) threadIdx.x;
         if (w < HX_SLOT_SRC_WORD) *slot_word(a, en.slot, w) = v[k];
         else if (a.src_calls && w < HX_SLOT_SRC_WORD + 2) a.src_calls[(long long) (w - HX_SLOT_SRC_WORD) * a.S + en.slot] = 0;
+        else if (a.src_calls && w == HX_SLOT_SRC_WORD + 2) { a.src_cls[en.slot] = en.plan; a.src_fp[en.slot] = a.plan_fp[en.plan]; }
     }
 }
 

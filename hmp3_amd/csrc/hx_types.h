@@ -324,9 +324,11 @@ struct AllocArgs {
 
 
 // ---- slot operations (hx_slots.hip: k_slot_reset / k_slot_gather / k_slot_scatter) ----
-// One listed slot of an operation: the slot, the receiving batch's class of it and the configuration fingerprint a
-// stream-state blob of it carries (gather) or must carry (scatter).
-struct HxSlotEntry { int slot, cls; unsigned long long cfg; };
+// One listed slot of an operation: the slot, the receiving batch's class of it, the configuration fingerprint a
+// stream-state blob of it carries (gather) or must carry (scatter) and, of a converting batch, its converter plan.  cls and
+// plan are what the slot runs once the operation is done: a reset stamps them into the slot (hx_batch_assign_streams hands
+// it another menu entry's, hx_batch_reset_streams the present one's).
+struct HxSlotEntry { int slot, cls; unsigned long long cfg; int plan, pad; };
 // A stream-state blob, the one description of its layout.  A header {magic of the batch's kind, format version,
 // sizeof(HxStream), 0, fingerprint of the stream's resolved configuration}: a blob from another library build (other state
 // layout) or saved under another control is refused instead of silently yielding a corrupt bitstream.  Then the parts, each
@@ -370,7 +372,9 @@ struct SlotArgs {
     long long sb_row;
     long long *src_calls;       // converting batches: [2][S] call counts, [2][S][2][HX_SRC_CARRY] carried samples and [S] plan
     float *src_carry;           // fingerprints; src_par = the copy the next call reads.  src_calls null: no converter part
-    const unsigned long long *src_fp;
+    unsigned long long *src_fp;
+    int *src_cls;               // [S] stream -> plan, as k_src reads it, and [plans] each plan's fingerprint: k_slot_reset
+    const unsigned long long *plan_fp;      // writes the slot's word of src_cls and of src_fp from its entry's plan
     int S, src_par;
     unsigned magic, version;    // of the batch's kind of blob
     int *status;                // bit 32: k_slot_scatter refused a blob

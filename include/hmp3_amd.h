@@ -178,6 +178,53 @@ int hx_batch_set_stream_states_device(hx_batch *b, const int *idx, int n, const 
 /* host blobs, synchronous: one gather / scatter launch and one copy, whatever n is */
 int hx_batch_get_stream_states(hx_batch *b, const int *idx, int n, void *blobs, long long blob_stride);
 int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *blobs, long long blob_stride);
+/* ---- slot configurations: a freed slot takes a stream of any control of the batch's menu (no reference equivalent) ----
+   A batch created with hx_batch_create / hx_batch_create_src ties every slot to the control it was created with: a slot whose
+   44.1 kHz CBR file has ended takes another 44.1 kHz CBR file and nothing else.  A menu lifts that: the batch is created with
+   the nmenu configurations it will ever run, every slot starts on one of them, and hx_batch_assign_streams hands listed slots
+   other entries in stream order.
+   The menu: ec[nmenu]; src NULL = a plain batch, else src[nmenu] = a converting batch whose entry j is the pair (ec[j], src[j])
+   as hx_batch_create_src takes them.  cfg: [nstreams] the entry each slot starts with, NULL = entry 0 for all.
+   Everything create sizes or decides from the batch's configurations is taken over the whole menu, whichever entries the slots
+   start with: the DC-blocker's PCM staging, the choice of the stream-walk build, hx_batch_out_stride, the parameter and
+   initial-state tables and the blob fingerprints; of a converting batch the plan table, the plans' fingerprints, the
+   converter's LDS layout and hx_batch_src_in_stride.
+   A batch is still of one kind: entries that differ in channel count, in MPEG-1 / MPEG-2 rates or in allocator generation are
+   refused at create with hx_batch_create's messages, and so is an entry the reference's init or the converter rejects;
+   hx_last_error names it ("menu entry 2: ...").  Identical entries are allowed, and hx_batch_stream_config returns the
+   caller's index whatever they share internally.  hx_batch_create and hx_batch_create_src are the case whose menu is their
+   distinct controls (control / source pairs) in order of first appearance; hx_batch_nconfigs counts those.
+   The menu is fixed for the batch's life: entries cannot be added after create.
+   hx_batch_assign_streams: slot idx[e] starts a new stream of menu entry cfg[e].  Its contract is hx_batch_reset_streams' word
+   for word - one launch whatever n is, ordered like a plain device call behind everything the batch has in flight (the
+   deferred packing of the last submit goes out first, ungated), the list through the slot operations' staging rotation, no
+   host wait but that rotation's, not under stream capture, the other slots untouched, n = 0 returns 0 and launches nothing,
+   and the same refusals before anything is allocated, uploaded or launched, plus a null cfg with n > 0 and
+   "entry e: configuration c out of range".  With cfg[e] equal to the slot's present entry it is hx_batch_reset_streams for
+   that slot: the two are one implementation.
+   After the call slot idx[e] produces, from its next frame on, exactly the bytes of slot 0 of a new batch created with
+   ec[cfg[e]] (and src[cfg[e]]): rows, out_bytes, packets, frame counters, MusicCRC, dense image and checkpoint blob.
+   The host's view of the slot moves when the call is made, as the converter's call count does at a reset: from the call's
+   return on hx_batch_stream_config, hx_batch_src_schedule, the extent checks of later converting calls, the host-blob
+   restores' header checks and the entries of later slot operations are the new entry's.  The device follows in stream order.
+   Converter: the carried case-4 samples of the slot's previous occupant stay where they are; a stream's call 0 reads none
+   under any plan.
+   Restoring a blob into a slot that runs another entry stays refused (on the host by hx_batch_set_stream_states, with status
+   bit 32 by the device form).  The way to do it is to assign, then restore: two calls, two launches.  There is no call that
+   adopts whatever configuration a blob carries.
+   hx_multi_assign_streams: the same over all blocks; idx counts streams over all blocks.  Synchronous like the other
+   hx_multi calls; every refusal is made for all blocks before one of them starts: all blocks or (-1) none.
+   The checkpoint blob of an assigned slot is a new batch's but for one word: the class index at the start of the stream
+   record is the batch's own numbering of its menu's configurations, which a restore replaces with the receiving batch's.
+   The command-line tool's -batch -slots<n> runs any number of files through n slots this way.
+   Not covered: entries added after create; mixed channel counts, MPEG-1 / MPEG-2 rates or allocator generations in one
+   batch; device blobs and pipelined submits of converting batches, as before. */
+hx_batch *hx_batch_create_menu(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                               const int *cfg, int max_frames);
+int hx_batch_nconfigs(const hx_batch *b);
+int hx_batch_stream_config(const hx_batch *b, int i);      /* the entry slot i runs as of the calls made so far; -1 bad arguments */
+/* slot idx[e] starts a new stream of menu entry cfg[e]; idx, cfg: HOST arrays of n, copied by the call; asynchronous on `stream` */
+int hx_batch_assign_streams(hx_batch *b, const int *idx, const int *cfg, int n, void *stream);
 /* worst-case bytes one stream can emit in a call of nframes frames */
 long long hx_batch_out_stride(const hx_batch *b, int nframes);
 /* PCM: int16 interleaved L/R, [nstreams][nframes*1152][2]; out: [nstreams][out_stride] bytes;
@@ -468,6 +515,11 @@ int hx_multi_status(hx_multi *m);
    in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
 hx_multi *hx_multi_create_src(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int shared_control,
                               const HX_SOURCE *src, int shared_source, int max_frames);
+/* hx_batch_create_menu in the same blocks: every block's batch gets the whole menu, cfg [nstreams] over all blocks or NULL */
+hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu,
+                               const HX_SOURCE *src, const int *cfg, int max_frames);
+/* the same over all blocks (idx counts streams over all blocks); synchronous like the other hx_multi calls; all blocks or (-1) none */
+int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *cfg, int n);
 long long hx_multi_src_in_stride(const hx_multi *m, int nframes);
 int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
                              unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats);

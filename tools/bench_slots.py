@@ -4,6 +4,9 @@
   b. the three kernels alone: bytes moved over the device time of (a);
   c. pipelined submits of --frames frames with --share of the slots reset between every two submits: step time with
      hx_batch_reset_streams, with the loop of hx_batch_reset_stream, and with no resets.
+The batch is created over a menu of two entries that cost the same to encode (they differ in the copyright bit), every slot on
+the first: the "assign" rows hand all slots (a), or the share of (c), the other entry with hx_batch_assign_streams - the
+reset kernel with another class in its entries - next to the reset rows of the same run.
 Every comparison is alternated --rounds times in one process on one batch.  One JSON document to --out (and stdout).
   python tools/bench_slots.py [--streams 4096] [--max-frames 256] [--frames 64] [--steps 8] [--share 0.05] [--rounds 2]
 (d, the regression check of the encode path, is bench.py itself run on this build and on the parent's library through
@@ -34,7 +37,7 @@ def main():
     from hmp3_amd import api, synth
     S, F = args.streams, args.frames
     L = api.lib()
-    b = api.Batch(api.default_control(bitrate=64), nstreams=S, max_frames=args.max_frames)
+    b = api.Batch.menu([api.default_control(bitrate=64), api.default_control(bitrate=64, cr_bit=1)], S, max_frames=args.max_frames)
     dev = torch.device("cuda:0")
     q = torch.cuda.current_stream().cuda_stream
     pcm = torch.from_numpy(synth.batch_pcm(S, F, unique=16)).to(dev)
@@ -46,6 +49,8 @@ def main():
     h_blobs = np.zeros(S * stride, dtype=np.uint8)
     one = (C.c_ubyte * need)()
     everything = (C.c_int * S)(*range(S))
+    entry = [(C.c_int * S)(*([k] * S)) for k in range(2)]
+    cur = np.zeros(S, dtype=np.int32)       # the entry each slot runs
 
     def submit(k):
         b.submit_device(pcm.data_ptr(), F, d_out[k & 1].data_ptr(), ostride, d_nb[k & 1].data_ptr(), q)
@@ -86,7 +91,7 @@ def main():
         if rc != 0:
             raise RuntimeError(api.last_error())
 
-    a = {k: [] for k in ("get_device", "get_host_ms", "get_loop_ms", "set_device", "set_host_ms", "set_loop_ms", "reset_device", "reset_loop_ms")}
+    a = {k: [] for k in ("get_device", "get_host_ms", "get_loop_ms", "set_device", "set_host_ms", "set_loop_ms", "reset_device", "reset_loop_ms", "assign_device", "assign_back_device")}
     for _ in range(args.rounds + 1):        # (the first round warms up: staging, device staging of the host calls)
         a["get_device"].append(timed_device(lambda: L.hx_batch_get_stream_states_device(b.h, everything, S, d_blobs.data_ptr(), stride, q)))
         a["get_host_ms"].append(wall(lambda: check(L.hx_batch_get_stream_states(b.h, everything, S, h_blobs.ctypes.data, stride))))
@@ -97,6 +102,8 @@ def main():
         a["set_loop_ms"].append(wall(loop(lambda i: L.hx_batch_set_stream_state(b.h, i, one))))
         a["reset_device"].append(timed_device(lambda: L.hx_batch_reset_streams(b.h, everything, S, q)))
         a["reset_loop_ms"].append(wall(loop(lambda i: L.hx_batch_reset_stream(b.h, i))))
+        a["assign_device"].append(timed_device(lambda: L.hx_batch_assign_streams(b.h, everything, entry[1], S, q)))
+        a["assign_back_device"].append(timed_device(lambda: L.hx_batch_assign_streams(b.h, everything, entry[0], S, q)))
     assert b.status() == 0
     res = {"streams": S, "max_frames": args.max_frames, "build_id": api.build_id(), "blob_bytes": need, "blob_stride": stride, "rounds": args.rounds, "all_slots": {}}
     for k, v in a.items():
@@ -125,6 +132,10 @@ def main():
                 idx = rng.choice(S, nrec, replace=False).astype(np.int32)
                 if variant == "new":
                     check(L.hx_batch_reset_streams(b.h, idx.ctypes.data, nrec, q))
+                elif variant == "assign":
+                    cfg = (1 - cur[idx]).astype(np.int32)
+                    check(L.hx_batch_assign_streams(b.h, idx.ctypes.data, cfg.ctypes.data, nrec, q))
+                    cur[idx] = cfg
                 else:
                     for i in idx:
                         check(L.hx_batch_reset_stream(b.h, int(i)))
@@ -133,13 +144,14 @@ def main():
         return 1e3 * (time.perf_counter() - t0) / args.steps
 
     steps("none")
-    c = {v: [] for v in ("none", "new", "loop")}
+    c = {v: [] for v in ("none", "new", "loop", "assign")}
     for _ in range(args.rounds):
         for v in c:
             c[v].append(round(steps(v), 3))
     assert b.status() == 0
     res["pipelined"] = {"frames": F, "steps": args.steps, "slots_reset_between_submits": nrec, "step_ms_no_resets": c["none"],
-                        "step_ms_reset_streams": c["new"], "step_ms_loop_of_reset_stream": c["loop"]}
+                        "step_ms_reset_streams": c["new"], "step_ms_loop_of_reset_stream": c["loop"],
+                        "step_ms_assign_streams": c["assign"]}
     text = json.dumps(res, indent=1)
     print(text, flush=True)
     if args.out:
