@@ -42,6 +42,25 @@ class IntPair(C.Structure):
     _fields_ = [("a", C.c_int), ("b", C.c_int)]
 
 
+LEDGER_POINTS = 513     # HX_LEDGER_POINTS
+
+
+class Ledger(C.Structure):
+    """HX_LEDGER: one stream's file record (include/hmp3_amd.h: where the file ends, its MusicCRC, its seek points)"""
+    _fields_ = [(n, C.c_int) for n in ("ncalls", "frames_per_call", "head_bytes", "flags", "open", "ended", "fed")] + \
+        [(n, C.c_uint) for n in ("frames", "bytes", "crc")] + \
+        [(n, C.c_int) for n in ("call_bytes", "toc_counter", "npt", "every")] + \
+        [("pad0", C.c_int * 2), ("pt", C.c_int * 2 * LEDGER_POINTS), ("pad1", C.c_int * 2)]
+
+    def tobytes(self):
+        return bytes(memoryview(self))
+
+
+class LedgerOpen(C.Structure):
+    """HX_LEDGER_OPEN: what hx_batch_ledger_begin takes per listed slot"""
+    _fields_ = [(n, C.c_int) for n in ("ncalls", "head_bytes", "flags", "reserved")]
+
+
 # The ctypes type of every C type in include/hmp3_amd.h.  A parameter that is any other pointer or an array is a
 # c_void_p, which takes byref(...), ctypes arrays, string buffers, plain integers and None.
 CTYPES = {
@@ -169,6 +188,42 @@ def last_error():
 def crc_combine(a, b, n):
     """the MusicCRC of A ++ B from a = CRC(0, A), b = CRC(0, B) and n = len(B) (hx_xing_crc_combine)"""
     return int(lib().hx_xing_crc_combine(int(a), int(b), int(n)))
+
+
+def ledger_open(ncalls, frames_per_call=1, head_bytes=0, flags=0):
+    """a new open record (hx_ledger_open)"""
+    r = Ledger()
+    lib().hx_ledger_open(C.byref(r), int(ncalls), int(frames_per_call), int(head_bytes), int(flags))
+    return r
+
+
+def ledger_update(rec, stats, crc, out_bytes):
+    """one stream's slice of one call into its record, on the host (hx_ledger_update): stats [n][2] frame counters, crc [n]
+    per-frame CRCs, out_bytes the stream's byte count of the call; True when the call ended the file"""
+    st = np.ascontiguousarray(stats, dtype=np.int32).reshape(-1, 2)
+    cr = np.ascontiguousarray(crc, dtype=np.uint16).reshape(-1)
+    if len(cr) != len(st):
+        raise ValueError("%d frame counters and %d CRCs" % (len(st), len(cr)))
+    return bool(lib().hx_ledger_update(C.byref(rec), st.ctypes.data, cr.ctypes.data, len(st), int(out_bytes)))
+
+
+def xing_load_points(xing_handle, rec):
+    """the record's seek points into an hx_xing (hx_xing_load_points)"""
+    if lib().hx_xing_load_points(xing_handle, C.byref(rec)) != 1:
+        raise RuntimeError("hx_xing_load_points: not a record's seek-point state")
+
+
+def _ledger_open_array(idx, ncalls, head_bytes, flags):
+    idx = [int(i) for i in idx]
+    n = len(idx)
+
+    def per_slot(v):
+        v = [int(v)] * n if np.isscalar(v) else [int(x) for x in v]
+        if len(v) != n:
+            raise ValueError("%d values for %d slots" % (len(v), n))
+        return v
+    nc, hb, fl = per_slot(ncalls), per_slot(head_bytes), per_slot(flags)
+    return (C.c_int * max(n, 1))(*idx), (LedgerOpen * max(n, 1))(*[LedgerOpen(nc[e], hb[e], fl[e], 0) for e in range(n)]), n
 
 
 def _counts_array(n, counts):
@@ -425,6 +480,27 @@ class Batch:
         if lib().hx_batch_reset_streams(self.h, arr, n, stream) != 0:
             raise RuntimeError("hx_batch_reset_streams failed: " + last_error())
 
+    def ledger_begin(self, idx, ncalls, head_bytes=0, flags=0, stream=None):
+        """slot idx[e] gets a new open file record (hx_batch_ledger_begin): ncalls, head_bytes, flags per slot or one value
+        for all; one launch, asynchronous on `stream`, ordered like a plain device call.  It does not reset the encoder"""
+        ai, ao, n = _ledger_open_array(idx, ncalls, head_bytes, flags)
+        if lib().hx_batch_ledger_begin(self.h, ai, ao, n, stream) != 0:
+            raise RuntimeError("hx_batch_ledger_begin failed: " + last_error())
+
+    def ledger_read(self, idx):
+        """the records of the slots in idx, synchronous: one gather launch and one copy -> list of Ledger"""
+        arr, n = self._slots(idx)
+        out = (Ledger * max(n, 1))()
+        if lib().hx_batch_ledger_read(self.h, arr, n, out) != 0:
+            raise RuntimeError("hx_batch_ledger_read failed: " + last_error())
+        return [Ledger.from_buffer_copy(out[e]) for e in range(n)]
+
+    def ledger_read_device(self, idx, d_out_ptr, stream=None):
+        """the records into device memory [len(idx)] HX_LEDGER (16-byte aligned), asynchronous on `stream`"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_ledger_read_device(self.h, arr, n, d_out_ptr, stream) != 0:
+            raise RuntimeError("hx_batch_ledger_read_device failed: " + last_error())
+
     def get_stream_states(self, idx):
         """checkpoints of the streams in idx, one launch and one copy -> list of bytes, blob e of slot idx[e]"""
         arr, n = self._slots(idx)
@@ -653,6 +729,21 @@ class Multi:
         ai, ac, n = _int_pair_arrays(idx, cfg)
         if lib().hx_multi_assign_streams(self.h, ai, ac, n) != 0:
             raise RuntimeError("hx_multi_assign_streams failed: " + last_error())
+
+    def ledger_begin(self, idx, ncalls, head_bytes=0, flags=0):
+        """as Batch.ledger_begin over all blocks, synchronous; all blocks or (RuntimeError) none (hx_multi_ledger_begin)"""
+        ai, ao, n = _ledger_open_array(idx, ncalls, head_bytes, flags)
+        if lib().hx_multi_ledger_begin(self.h, ai, ao, n) != 0:
+            raise RuntimeError("hx_multi_ledger_begin failed: " + last_error())
+
+    def ledger_read(self, idx):
+        """as Batch.ledger_read over all blocks (hx_multi_ledger_read)"""
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        out = (Ledger * max(n, 1))()
+        if lib().hx_multi_ledger_read(self.h, (C.c_int * max(n, 1))(*idx), n, out) != 0:
+            raise RuntimeError("hx_multi_ledger_read failed: " + last_error())
+        return [Ledger.from_buffer_copy(out[e]) for e in range(n)]
 
     def ndevices(self):
         return int(lib().hx_multi_ndevices(self.h))

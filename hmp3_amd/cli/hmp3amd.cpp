@@ -255,9 +255,8 @@ struct Job {
     size_t nc = 0;                      // calls of the single-file loop on the file's input (the drain follows them)
     std::vector<long long> start;       // converting route: where each of them starts in the file's bytes
     std::vector<unsigned char> stream;
-    std::vector<unsigned> fr, by;       // per frame fed to the file's stream: frames / bytes out so far
-    unsigned short crc = 0;             // the MusicCRC of the file's bytes so far
-    bool done = false;                  // the file's drain has ended: it takes no more frames
+    HX_LEDGER led = {};                 // the file's record as last read from the batch's ledger: calls fed, frames / bytes out so far,
+                                        // the MusicCRC of those bytes, the seek points; ended: the drain has ended, it takes no more frames
 };
 int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, const Options &opt, bool loaded);
 
@@ -526,17 +525,15 @@ bool job_control(Job &j, const char *name, const Options &opt, bool conv, int *n
 bool job_write(Job &j, const char *name, const Options &opt)
 {
     const Input &in = j.in;
-    const size_t calls = j.nc;
     Tagger tg;
     tg.begin(in, opt.xing_flag);
-    for (size_t u = 0; u < calls; u++) tg.after_call(j.fr[u], j.by[u]);
-    size_t u = calls;                               // drain calls: while (get_frames() < frames_expected) encode silence
-    const size_t expected = calls * (in.ec_used.samprate < 32000 ? 2 : 1);   // MPEG-2: two frames per call
+    // the ledger has made the tagger's calls on the device (k_ledger): one seek point per input call, the end of the drain
+    // (while (get_frames() < frames_expected) encode silence) and the CRC up to there
     bool ok = true;
-    while (u < j.fr.size() && j.fr[u - 1] < expected) u++;
-    if (j.fr[u - 1] < expected) { fprintf(stderr, "\n %s: drain did not complete\n", name); ok = false; }
-    const unsigned frames = j.fr[u - 1], nbytes = j.by[u - 1];
-    tg.crc = j.crc;
+    if (!j.led.ended) { fprintf(stderr, "\n %s: drain did not complete\n", name); ok = false; }
+    const unsigned frames = j.led.frames, nbytes = j.led.bytes;
+    tg.crc = j.led.crc;
+    hx_xing_load_points(tg.xg, &j.led);
     const uint64_t out_bytes = (uint64_t) tg.head_bytes + nbytes;
     if (opt.xing_flag) tg.finish(in, frames, out_bytes);
     FILE *o = fopen(name, "wb");
@@ -546,6 +543,15 @@ bool job_write(Job &j, const char *name, const Options &opt)
     fclose(o);
     fprintf(stderr, "\n %s: %u frames, %llu bytes", name, frames, (unsigned long long) out_bytes);
     return ok;
+}
+
+// what the batch's ledger takes for a file when the file gets its slot (the tag frame's size and whether it has seek
+// points: Tagger::begin)
+HX_LEDGER_OPEN job_ledger(const Job &j, const Options &opt)
+{
+    Tagger tg;
+    tg.begin(j.in, opt.xing_flag);
+    return {(int) j.nc, tg.head_bytes, (tg.head_flags & 4) ? 1 : 0, 0};
 }
 
 // loaded: every file's audio is in memory and every file has its own slot; else (-slots) jobs hold the headers only
@@ -616,22 +622,33 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     // Every call gives each file the frames it still needs (per-stream frame counts): its input frames, then silence up to the
     // frame at which its drain ends; a finished file takes 0 and costs nothing, and the loop ends with the last file, not
     // DRAIN frames behind the longest one for all.  The call is as long as its largest count.
-    std::vector<int> cnt(NS), take_slot, take_cfg;
+    std::vector<int> cnt(NS), take_slot, take_cfg, fed_slot;
+    // The ledger (k_ledger, on the GPU) decides where each file ends and keeps its byte count, MusicCRC and seek points: a
+    // file's record begins when the file gets its slot, and after each call the records of the slots that took frames come down
+    std::vector<HX_LEDGER_OPEN> take_open(NS);
+    std::vector<HX_LEDGER> led(NS);
+    for (int s = 0; s < NS; s++) { fed_slot.push_back(s); take_open[s] = job_ledger(jobs[s], opt); }
+    if (hx_multi_ledger_begin(b, fed_slot.data(), take_open.data(), NS) != 0) {
+        fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
+        hx_multi_destroy(b);
+        return 1;
+    }
+    for (int s = 0; s < NS; s++) hx_ledger_open(&jobs[s].led, take_open[s].ncalls, 1, take_open[s].head_bytes, take_open[s].flags);
     for (;;) {
         int nf = 0;
         for (int s = 0; s < NS; s++) {
             cnt[s] = 0;
             if (held[s] < 0) continue;
             const Job &j = jobs[held[s]];
-            const size_t fed = j.fr.size(), room = j.nc + DRAIN;
-            cnt[s] = (j.done || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
+            const size_t fed = (size_t) j.led.fed, room = j.nc + DRAIN;
+            cnt[s] = (j.led.ended || fed >= room) ? 0 : (int) std::min<size_t>(CH, room - fed);
             nf = std::max(nf, cnt[s]);
         }
         if (nf == 0) break;
         for (int s = 0; s < NS && !conv; s++) {
             if (cnt[s] == 0) continue;
             const Job &j = jobs[held[s]];
-            const size_t p0 = j.fr.size();
+            const size_t p0 = (size_t) j.led.fed;
             for (int k = 0; k < cnt[s]; k++) {
                 // past the end the single-file loop feeds frames of zero BYTES: silence, except for
                 // 8-bit unsigned input where a zero byte is full-scale negative
@@ -645,7 +662,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             // drain calls all read the zero region (zero bytes: 8-bit input stays full-scale negative there too)
             if (cnt[s] == 0) continue;
             const Job &j = jobs[held[s]];
-            const size_t p0 = j.fr.size();
+            const size_t p0 = (size_t) j.led.fed;
             unsigned char *row = rows.data() + (size_t) s * in_stride;
             memset(row, 0, (size_t) in_stride);
             const long long base = p0 < j.nc ? j.start[p0] : 0;
@@ -659,25 +676,20 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             hx_multi_destroy(b);
             return 1;
         }
-        take_slot.clear(); take_cfg.clear();
-        for (int s = 0; s < NS; s++) {
-            const int n = cnt[s];
-            if (n == 0) continue;
+        take_slot.clear(); take_cfg.clear(); take_open.clear(); fed_slot.clear();
+        for (int s = 0; s < NS; s++) if (cnt[s] > 0) fed_slot.push_back(s);
+        if (hx_multi_ledger_read(b, fed_slot.data(), (int) fed_slot.size(), led.data()) != 0) {
+            fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
+            hx_multi_destroy(b);
+            return 1;
+        }
+        for (size_t e = 0; e < fed_slot.size(); e++) {
+            const int s = fed_slot[e];
             Job &j = jobs[held[s]];
-            const size_t p0 = j.fr.size();
-            j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + nb[s]);
-            for (int k = 0; k < n; k++) { j.fr.push_back((unsigned) stats[((size_t) s * nf + k) * 2]); j.by.push_back((unsigned) stats[((size_t) s * nf + k) * 2 + 1]); }
-            // the last frame the file uses (job_write: u - 1), if it lies in this call
-            const size_t calls = j.nc, expected = calls * (j.in.ec_used.samprate < 32000 ? 2 : 1);
-            int k = p0 + n >= calls ? (int) (calls > p0 + 1 ? calls - 1 - p0 : 0) : n;
-            while (k < n && j.fr[p0 + k] < expected) k++;
-            if (k < n) {
-                const unsigned e = (unsigned) nb[s] - (j.by[p0 + n - 1] - j.by[p0 + k]);        // this call's bytes up to there
-                j.crc = hx_xing_crc_combine(j.crc, crc[(size_t) s * nf + k], (long long) e);
-                j.done = true;
-            } else
-                j.crc = hx_xing_crc_combine(j.crc, crc[(size_t) s * nf + n - 1], nb[s]);
-            if (loaded || !(j.done || j.fr.size() >= j.nc + DRAIN)) continue;
+            // the bytes of this call's row that belong to the file: all of it, or up to the frame at which its drain ended
+            j.led = led[e];
+            j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + j.led.call_bytes);
+            if (loaded || !(j.led.ended || (size_t) j.led.fed >= j.nc + DRAIN)) continue;
             // -slots: the file is written and freed, and its slot goes to the next file that waits
             if (!job_write(j, files[2 * held[s] + 1], opt)) rc = 1;
             j = Job();
@@ -686,9 +698,11 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             const int i = next++;
             if (!load_input(files[2 * i], opt, &jobs[i].in, false) || !job_control(jobs[i], files[2 * i], opt, conv, &nch) || !job_calls(jobs[i], files[2 * i], opt, conv)) { hx_multi_destroy(b); return 1; }
             held[s] = i;
-            take_slot.push_back(s); take_cfg.push_back(file_cfg[i]);
+            take_slot.push_back(s); take_cfg.push_back(file_cfg[i]); take_open.push_back(job_ledger(jobs[i], opt));
+            hx_ledger_open(&jobs[i].led, take_open.back().ncalls, 1, take_open.back().head_bytes, take_open.back().flags);
         }
-        if (!take_slot.empty() && hx_multi_assign_streams(b, take_slot.data(), take_cfg.data(), (int) take_slot.size()) != 0) {
+        if (!take_slot.empty() && (hx_multi_assign_streams(b, take_slot.data(), take_cfg.data(), (int) take_slot.size()) != 0 ||
+                                   hx_multi_ledger_begin(b, take_slot.data(), take_open.data(), (int) take_slot.size()) != 0)) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
             return 1;

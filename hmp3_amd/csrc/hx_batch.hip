@@ -379,9 +379,18 @@ int check_counts_arg(const int *nfr, int S, int nframes, int first)
 }
 // (k_crc takes every e[f] from the call's frame counters, and the batch keeps no counter buffer of its own for it: two
 // pipelined submits would race on one)
-int check_opt(const OptOut &o)
+// (k_ledger takes a live record's end, bytes and CRC from the call's counters and CRCs: the same rule, for both buffers)
+int check_opt(const hx_batch *b, const OptOut &o, const int *nfr, int first)
 {
     if (o.crc && !o.frame_stats) { set_err("a CRC buffer (hx_batch_crc_buffer) needs a frame-counter buffer (hx_batch_frame_stats_buffer) in force"); return -1; }
+    if (!b || !b->d_ledger || (o.crc && o.frame_stats)) return 0;
+    for (int s = 0; s < b->S; s++)
+        if (b->led_live[s] && (!nfr || nfr[s] > 0)) {
+            char msg[192];
+            snprintf(msg, sizeof msg, "stream %d has an open ledger record (hx_batch_ledger_begin): a call that feeds it needs a frame-counter buffer and a CRC buffer in force", first + s);
+            set_err("%s", msg);
+            return -1;
+        }
     return 0;
 }
 // (a converting batch takes its input through hx_batch_encode_src_* only: a plain call would advance the encoder past its converter)
@@ -434,6 +443,15 @@ static int enqueue_crc(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
     return 0;
 }
 
+// the file ledger's update from one call on stream qp, behind its CRC kernel (hx_ledger.hip): one wave per stream.  A call
+// made before the batch's first hx_batch_ledger_begin has no ledger in its record
+static int enqueue_ledger(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
+{
+    if (!c.ledger) return 0;
+    LAUNCH(k_ledger, dim3((unsigned) ((b->S + 3) / 4)), dim3(256), qp, c.ledger, (const int *) c.opt.frame_stats, (const unsigned short *) c.opt.crc, (const int *) c.out_bytes, c.nfr, nframes, b->S);
+    return 0;
+}
+
 // A gate on stream q: what follows it there starts in the tail of the allocator launch whose first workgroup took number
 // `base` of the started-counter (it wraps with the counter), not at that launch's start.
 static int launch_gate(hx_batch *b, hipStream_t q, unsigned base)
@@ -454,7 +472,7 @@ static int flush_pack(hx_batch *b, long long gate_base)
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
     if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0 ||
-        enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0) return -1;
+        enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0 || enqueue_ledger(b, j.call, j.nframes, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -669,7 +687,8 @@ static int place_pack(hx_batch *b, const Pass &p)
     // the previous device-buffer submit's packing went out on the packing stream in pipe_enter: its k_pack_carry writes
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
-    if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0 || enqueue_crc(b, p.call, p.nframes, qa) != 0) return -1;
+    if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0 || enqueue_crc(b, p.call, p.nframes, qa) != 0 ||
+        enqueue_ledger(b, p.call, p.nframes, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -711,7 +730,7 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream,
 }
 int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
-    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(c.opt) != 0) return -1;
+    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(b, c.opt, counts_in_force(b)) != 0) return -1;
     return encode_pass(b, in, nframes, c, stream, kind);
 }
 
@@ -775,7 +794,7 @@ extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
 // image kernels of the call write them, and the rows stay in the staging: out is not used
 static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, const DenseOut *img = nullptr)
 {
-    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b->opt) != 0) return -1;
+    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b, b->opt, counts_in_force(b)) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
     const long long pbytes = in.bytes(b->S, nframes, b->nchan), obytes = (long long) b->S * out_stride;

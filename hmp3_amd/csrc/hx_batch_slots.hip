@@ -238,3 +238,94 @@ extern "C" int hx_batch_set_stream_state(hx_batch *b, int i, const void *src)
 {
     return host_blobs(b, SLOT_SCATTER, &i, 1, (void *) src, hx_batch_stream_states_stride(b), true);
 }
+
+// ---- the file ledger's slot operations (include/hmp3_amd.h; kernels: hx_ledger.hip) ----
+// hx_batch_ledger_begin and the two reads list slots like the operations above and share their refusals, their staging
+// rotation and their ordering: on the caller's stream behind everything in flight, the deferred packing - and with it the
+// previous occupant's last update, which travels with that packing - out first.
+
+// One ledger operation on stream q (arguments checked, n > 0): open == null: a gather into d_out
+static int ledger_op(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n, HX_LEDGER *d_out, hipStream_t q)
+{
+    HIPCHK(hipSetDevice(b->device));
+    Staging &s = b->ent_stage;
+    if (!s.d && staging_make(b, s, sizeof(HxSlotEntry) * (size_t) b->S) != 0) return -1;
+    if (!b->d_ledger) {         // (the first begin: all records closed, in stream order in front of its kernel)
+        HX_LEDGER *led = nullptr;
+        if (dev_alloc(b, led, (long long) sizeof(HX_LEDGER) * b->S) != 0) return -1;
+        HIPCHK(hipMemsetAsync(led, 0, sizeof(HX_LEDGER) * (size_t) b->S, q));
+        b->d_ledger = led;
+        b->led_live.assign(b->S, 0);
+    }
+    Poison poison{b};
+    if (b->inflight) {
+        if (order_behind_submits(b, q) != 0) return -1;
+        b->inflight = false;
+    }
+    const int k = (int) (b->nslotops++ % 3);
+    HxLedgerEntry *h = (HxLedgerEntry *) staging_take(s, k);
+    if (!h) return -1;
+    for (int e = 0; e < n; e++) h[e] = open ? HxLedgerEntry{idx[e], open[e].ncalls, open[e].head_bytes, open[e].flags} : HxLedgerEntry{idx[e], 0, 0, 0};
+    if (staging_upload(s, k, sizeof(HxLedgerEntry) * (size_t) n, q) != 0) return -1;
+    if (open) LAUNCH(k_ledger_begin, dim3((unsigned) n), dim3(256), q, b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), b->lsf ? 2 : 1);
+    else LAUNCH(k_ledger_gather, dim3((unsigned) n), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), d_out);
+    if (staging_done(s, k, q) != 0) return -1;
+    return poison.ok();
+}
+
+int ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n, void *stream, bool wait)
+{
+    const hipStream_t q = (hipStream_t) stream;
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && !open) { set_err("open is null with n > 0"); return -1; }
+    for (int e = 0; e < n; e++)
+        if (open[e].ncalls < 1 || open[e].head_bytes < 0) {
+            char msg[96];
+            snprintf(msg, sizeof msg, open[e].ncalls < 1 ? "entry %d: ncalls < 1" : "entry %d: head_bytes < 0", e);
+            set_err("%s", msg);
+            return -1;
+        }
+    if (n == 0) return 0;
+    if (wait && drain(b) != 0) return -1;
+    if (ledger_op(b, idx, open, n, nullptr, q) != 0) return -1;
+    for (int e = 0; e < n; e++) b->led_live[idx[e]] = 1;       // (the host's view moves when the call is made, like a slot's configuration)
+    if (wait) HIPCHK(hipStreamSynchronize(q));
+    return 0;
+}
+extern "C" int hx_batch_ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n, void *stream)
+{
+    return ledger_begin(b, idx, open, n, stream, false);
+}
+
+// a batch without a ledger has [S] closed records: all zero
+extern "C" int hx_batch_ledger_read_device(hx_batch *b, const int *idx, int n, HX_LEDGER *d_out, void *stream)
+{
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && !d_out) { set_err("d_out is null with n > 0"); return -1; }
+    if (((unsigned long long) d_out & 15) != 0) { set_err("d_out must be 16-byte aligned"); return -1; }
+    if (n == 0) return 0;
+    if (!b->d_ledger) {
+        HIPCHK(hipSetDevice(b->device));
+        HIPCHK(hipMemsetAsync(d_out, 0, sizeof(HX_LEDGER) * (size_t) n, (hipStream_t) stream));
+        return 0;
+    }
+    return ledger_op(b, idx, nullptr, n, d_out, (hipStream_t) stream);
+}
+
+// synchronous: behind everything in flight, one gather launch into device staging, one copy; a record it shows ended is no
+// longer live for the host
+int ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out)
+{
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && !out) { set_err("out is null with n > 0"); return -1; }
+    if (n == 0) return 0;
+    if (!b->d_ledger) { memset(out, 0, sizeof(HX_LEDGER) * (size_t) n); return 0; }
+    if (drain(b) != 0) return -1;
+    if (dev_grow(b, b->d_blobs, b->blobs_cap, (long long) sizeof(HX_LEDGER) * n) != 0) return -1;
+    if (ledger_op(b, idx, nullptr, n, (HX_LEDGER *) b->d_blobs, nullptr) != 0) return -1;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(out, b->d_blobs, sizeof(HX_LEDGER) * (size_t) n, hipMemcpyDeviceToHost));
+    for (int e = 0; e < n; e++) if (out[e].ended || !out[e].open) b->led_live[idx[e]] = 0;
+    return 0;
+}
+extern "C" int hx_batch_ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out) { return ledger_read(b, idx, n, out); }

@@ -208,7 +208,7 @@ static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_strid
 static int src_checked(hx_batch *b, const void *in, long long in_stride, const long long *frame_off, int nframes, const int *nfr,
                        const void *out, long long out_stride, const void *out_bytes, const OptOut &o, std::vector<long long> &used_end)
 {
-    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0 || check_counts_arg(nfr, b->S, nframes, 0) != 0 || check_opt(o) != 0) return -1;
+    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0 || check_counts_arg(nfr, b->S, nframes, 0) != 0 || check_opt(b, o, nfr) != 0) return -1;
     used_end.resize(b->S);
     if (src_extents(b, in_stride, frame_off, nframes, nfr, 0, used_end.data()) != 0) return -1;
     return nfr ? counts_buffers(b) : 0;

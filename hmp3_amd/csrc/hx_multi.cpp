@@ -208,6 +208,62 @@ extern "C" int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *c
     return 0;
 }
 
+// hx_batch_ledger_begin / hx_batch_ledger_read over all streams, like hx_multi_assign_streams: every refusal here, with the
+// caller's entry numbers, before one block starts; then each block takes its part of the list and is done when the call
+// returns.  where[e] = (block, position in the block's list) of entry e.
+static int multi_ledger_split(hx_multi *m, const int *idx, const HX_LEDGER_OPEN *open, bool begin, const void *out, int n,
+                              std::vector<std::vector<int>> &bi, std::vector<std::pair<size_t, size_t>> &where)
+{
+    char msg[160];
+#define REFUSE(...) do { snprintf(msg, sizeof msg, __VA_ARGS__); set_err("%s", msg); return -1; } while (0)
+    if (!m) { set_err("null handle"); return -1; }
+    for (hx_batch *b : m->part) if (check_poisoned(b) != 0) return -1;
+    if (n < 0) REFUSE("n = %d: the number of listed slots cannot be negative", n);
+    if (n > 0 && !idx) { set_err("idx is null with n > 0"); return -1; }
+    if (n > 0 && begin && !open) { set_err("open is null with n > 0"); return -1; }
+    if (n > 0 && !begin && !out) { set_err("out is null with n > 0"); return -1; }
+    const size_t nb = m->part.size();
+    std::vector<char> listed(m->S, 0);
+    bi.assign(nb, std::vector<int>());
+    for (int e = 0; e < n; e++) {
+        if (idx[e] < 0 || idx[e] >= m->S) REFUSE("entry %d: slot %d out of range (0 .. %d)", e, idx[e], m->S - 1);
+        if (listed[idx[e]]) REFUSE("entry %d: slot %d is listed twice", e, idx[e]);
+        if (begin && open[e].ncalls < 1) REFUSE("entry %d: ncalls < 1", e);
+        if (begin && open[e].head_bytes < 0) REFUSE("entry %d: head_bytes < 0", e);
+        listed[idx[e]] = 1;
+        size_t k = 0;
+        while (k + 1 < nb && idx[e] >= m->first[k + 1]) k++;
+        where.push_back({k, bi[k].size()});
+        bi[k].push_back(idx[e] - m->first[k]);
+    }
+#undef REFUSE
+    return 0;
+}
+extern "C" int hx_multi_ledger_begin(hx_multi *m, const int *idx, const HX_LEDGER_OPEN *open, int n)
+{
+    std::vector<std::vector<int>> bi;
+    std::vector<std::pair<size_t, size_t>> where;
+    if (multi_ledger_split(m, idx, open, true, nullptr, n, bi, where) != 0) return -1;
+    std::vector<std::vector<HX_LEDGER_OPEN>> bo(bi.size());
+    for (int e = 0; e < n; e++) bo[where[e].first].push_back(open[e]);
+    for (size_t k = 0; k < bi.size(); k++)
+        if (!bi[k].empty() && ledger_begin(m->part[k], bi[k].data(), bo[k].data(), (int) bi[k].size(), nullptr, true) != 0) return -1;
+    return 0;
+}
+extern "C" int hx_multi_ledger_read(hx_multi *m, const int *idx, int n, HX_LEDGER *out)
+{
+    std::vector<std::vector<int>> bi;
+    std::vector<std::pair<size_t, size_t>> where;
+    if (multi_ledger_split(m, idx, nullptr, false, out, n, bi, where) != 0) return -1;
+    std::vector<std::vector<HX_LEDGER>> br(bi.size());
+    for (size_t k = 0; k < bi.size(); k++) {
+        br[k].resize(bi[k].size());
+        if (!bi[k].empty() && ledger_read(m->part[k], bi[k].data(), (int) bi[k].size(), br[k].data()) != 0) return -1;
+    }
+    for (int e = 0; e < n; e++) out[e] = br[where[e].first][where[e].second];
+    return 0;
+}
+
 extern "C" int hx_multi_ndevices(const hx_multi *m) { return m ? (int) m->part.size() : 0; }
 extern "C" int hx_multi_nstreams(const hx_multi *m) { return m ? m->S : 0; }
 extern "C" hx_batch *hx_multi_batch(hx_multi *m, int k) { return (m && k >= 0 && k < (int) m->part.size()) ? m->part[k] : nullptr; }
@@ -264,10 +320,26 @@ static int multi_fanout(hx_multi *m, bool buffers_ok, int nframes, long long out
     return 0;
 }
 
+// the optional outputs every block's call would take (stats / crc: the host call's own; nfr: [S] a converting call's counts,
+// null: each block's counts in force), checked for all blocks before one starts: a block with a live ledger record refuses
+// a call without counters and CRCs, and its message names the stream by the caller's number
+static int multi_check_opt(const hx_multi *m, const int *stats, const unsigned short *crc, const int *nfr)
+{
+    for (size_t k = 0; k < m->part.size(); k++) {
+        const hx_batch *b = m->part[k];
+        OptOut o = b->opt;
+        if (stats) o.frame_stats = (int *) stats;
+        if (crc) o.crc = (unsigned short *) crc;
+        if (check_opt(b, o, nfr ? nfr + m->first[k] : counts_in_force(b), m->first[k]) != 0) return -1;
+    }
+    return 0;
+}
+
 // the PCM calls: each device on its block's rows of the caller's buffers
 static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats,
                              unsigned short *crc = nullptr)
 {
+    if (m && multi_check_opt(m, stats, crc, nullptr) != 0) return -1;
     return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
         const long long f = m->first[k];
         const char *p = (const char *) in.p + in.bytes(f, nframes, m->nchan);
@@ -309,7 +381,7 @@ extern "C" int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char 
 {
     if (m && nframes > 0 && in_stride > 0) {
         if (crc && !stats) { set_err("crc needs stats: the CRCs follow from the call's frame counters"); return -1; }
-        if (check_counts_arg(nfr, m->S, nframes, 0) != 0) return -1;
+        if (check_counts_arg(nfr, m->S, nframes, 0) != 0 || multi_check_opt(m, stats, crc, nfr) != 0) return -1;
         for (size_t k = 0; k < m->part.size(); k++) {
             const long long f = m->first[k];
             if (!m->part[k]->nsrc) { set_err("not a converting batch (hx_multi_create_src)"); return -1; }

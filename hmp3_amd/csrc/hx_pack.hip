@@ -464,3 +464,6 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
 // ---- slot operations on many streams (hx_batch_reset_streams, hx_batch_get / set_stream_states*): k_slot_*, a file of its
 // own, built as part of this unit ----
 #include "hx_slots.hip"
+
+// ---- the file ledger (hx_batch_ledger_*): k_ledger*, a file of its own, built as part of this unit (behind hx_crc.hip) ----
+#include "hx_ledger.hip"

@@ -27,7 +27,7 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 
 #ifdef __HIPCC__
-// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip and hx_slots.hip / hx_src.hip)
+// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip, hx_slots.hip and hx_ledger.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
 // nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
 // frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
@@ -59,6 +59,9 @@ __global__ void k_crc(const unsigned char *out, long long out_stride, const int 
 __global__ void k_slot_reset(SlotArgs a);
 __global__ void k_slot_gather(SlotArgs a, uint2 *blobs);
 __global__ void k_slot_scatter(SlotArgs a, const uint2 *blobs);
+__global__ void k_ledger(HX_LEDGER *led, const int *stats, const unsigned short *crc, const int *out_bytes, const int *nfr, int nframes, int S);
+__global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent, int frames_per_call);
+__global__ void k_ledger_gather(const HX_LEDGER *led, const HxLedgerEntry *ent, HX_LEDGER *out);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
 __global__ void k_alloc(AllocArgs a);
@@ -112,6 +115,7 @@ struct Call {
                                         // uploads it: hx_batch::nfr_stage; a converting call under counts has, in front of k_src),
                                         // null = every stream takes the call's nframes
     unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
+    HX_LEDGER *ledger = nullptr;        // the batch's file ledger as it stood when the call was made (null: none yet): k_ledger goes out behind the call's k_crc
 };
 
 // Three staging copies in rotation for a small list that a call hands to its kernels: page-locked host memory and device
@@ -189,6 +193,11 @@ struct hx_batch {
     std::vector<long long> slot_mark;   // [S] the last operation that listed the slot (duplicates)
     long long slot_serial = 0;
     unsigned char *d_blobs = nullptr; long long blobs_cap = 0;
+    // the file ledger (hx_batch_ledger_*): [S] records, made and zeroed at the first hx_batch_ledger_begin, and which of them
+    // the host takes for live - begun, and not shown ended by a hx_batch_ledger_read since (a call that feeds a live record
+    // needs frame counters and CRCs: check_opt)
+    HX_LEDGER *d_ledger = nullptr;
+    std::vector<unsigned char> led_live;
     bool debug = false;
     // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
@@ -331,7 +340,12 @@ struct PcmIn {
     long long bytes(long long S, int nframes, int nchan) const { return S * nframes * 1152 * nchan * (long long) (f32 ? sizeof(float) : sizeof(int16_t)); }
 };
 // a call that writes the caller's rows and the optional outputs set on the batch (a null batch: the argument checks refuse it)
-static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_stride, int *out_bytes) { return {out, out_stride, out_bytes, b ? b->opt : OptOut()}; }
+static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_stride, int *out_bytes)
+{
+    Call c = {out, out_stride, out_bytes, b ? b->opt : OptOut()};
+    c.ledger = b ? b->d_ledger : nullptr;
+    return c;
+}
 // where a pass runs: every kernel on the caller's stream, or (hx_batch_submit_*) front end and stream walk on the batch's
 // own two streams, ordered by events (see hx_batch); a device-buffer submit also defers its packing
 enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
@@ -354,8 +368,11 @@ HX_LOCAL int check_counts_arg(const int *nfr, int S, int nframes, int first);
 // A converting call's input extents against its rows, per stream under its count (nfr null: nframes), before anything runs;
 // used_end [S] or null: where each stream's following call would start.  first: as for check_counts.
 HX_LOCAL int src_extents(const hx_batch *b, long long in_stride, const long long *frame_off, int nframes, const int *nfr, int first, long long *used_end);
-// ... and of the optional outputs a call would take: a CRC buffer without frame counters is refused
-HX_LOCAL int check_opt(const OptOut &o);
+// ... and of the optional outputs a call would take: a CRC buffer without frame counters is refused, and so is a call
+// without both that feeds a live ledger record (nfr: the call's per-stream counts or null; first: as for check_counts)
+HX_LOCAL int check_opt(const hx_batch *b, const OptOut &o, const int *nfr, int first = 0);
+// the counts a call made now on a plain batch would take (null: uniform)
+static inline const int *counts_in_force(const hx_batch *b) { return b->nfr.empty() ? nullptr : b->nfr.data(); }
 // one pass of the pipeline over the batch (arguments checked by the caller); encode_checked: check_call, then the pass
 HX_LOCAL int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
 HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind);
@@ -378,6 +395,10 @@ HX_LOCAL int src_setup(hx_batch *b, const std::vector<HxSrcPlan> &plans);
 // hx_batch_assign_streams (cfg null: hx_batch_reset_streams) on stream q; wait: behind everything in flight, and done when
 // it returns
 HX_LOCAL int assign_slots(hx_batch *b, const int *idx, const int *cfg, int n, void *stream, bool wait);
+// hx_batch_ledger_begin on stream q (wait: as for assign_slots) and hx_batch_ledger_read (hx_multi calls them per block,
+// after it has made their refusals for all blocks)
+HX_LOCAL int ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n, void *stream, bool wait);
+HX_LOCAL int ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out);
 // Slot state (hx_batch_slots.hip), set up at create: what a new stream of each class starts with, each class's blob
 // fingerprint and the duplicate marks (hx_batch_create); a converting batch's per-stream plan fingerprints on the device,
 // which the slot kernels check and write (hx_batch_create_src)
@@ -430,7 +451,7 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
         OptOut o = b->opt;
         if (stats) o.frame_stats = stats;
         if (crc) o.crc = crc;
-        if (check_opt(o) != 0) return -1;
+        if (check_opt(b, o, counts_in_force(b)) != 0) return -1;
     }
     HIPCHK(hipSetDevice(b->device));
     const long long obytes = (long long) b->S * out_stride, sbytes = stats ? (long long) sizeof(int) * b->S * nframes * 2 : 0;

@@ -362,6 +362,14 @@ static_assert(sizeof(HxStateHeader) == 8 * HX_SLOT_HDR_WORDS && offsetof(HxState
               offsetof(HxStateHeader, pad) == 8 * HX_SLOT_HDR_STATE_BYTES + 4, "the header is three 8-byte words: {magic, version}, {state_bytes, pad}, cfg");
 static_assert(HX_STATE_OFF_STREAM % 8 == 0 && HX_STATE_OFF_CARRY % 8 == 0 && HX_STATE_CARRY_BYTES % 8 == 0 && HX_STATE_OFF_SRC_FP % 8 == 0 &&
               HX_STATE_OFF_SRC_CALLS % 8 == 0 && HX_STATE_OFF_SRC_CARRY % 8 == 0 && HX_STATE_END_SRC % 8 == 0, "every part of a blob starts on an 8-byte boundary");
+// ---- the file ledger (hx_ledger.hip: k_ledger / k_ledger_begin / k_ledger_gather; the record: HX_LEDGER, include/hmp3_amd.h) ----
+// One listed slot of hx_batch_ledger_begin (the file's parameters) or of a read (the slot alone).  It travels through the
+// slot operations' staging, whose copies hold [S] HxSlotEntry.
+struct HxLedgerEntry { int slot, ncalls, head_bytes, flags; };
+static_assert(sizeof(HxLedgerEntry) <= sizeof(HxSlotEntry), "a ledger list fits the slot operations' staging");
+#define HX_LEDGER_KEPT 512                          // seek points before a decimation halves them (hx_xing_toc)
+#define HX_LEDGER_HDR_WORDS 16                      // 4-byte words in front of the points
+
 #define HX_SLOT_VEC 4                               // words per lane
 #define HX_SLOT_CHUNK (256 * HX_SLOT_VEC)           // words per workgroup
 struct SlotArgs {

@@ -3,6 +3,7 @@
 // :695-719 XingHeaderTOC, :132-182 BuildTOC, :188-231 MusicCRC).  Host-only code.
 // Unlike the reference (file-static table, one stream per process) the seek-table state lives in
 // a context object, so any number of files can be written concurrently.
+#include <cstddef>
 #include <cstdint>
 #include <cstring>
 #include <new>
@@ -149,6 +150,70 @@ extern "C" int hx_xing_toc(hx_xing *x, int frames, int bs_bytes)
     x->npt = kPoints / 2;
     x->every += x->every;
     return x->every;
+}
+
+// ---- the file ledger's record on the host (include/hmp3_amd.h, HX_LEDGER; the kernel: hx_ledger.hip) ----
+static_assert(HX_LEDGER_POINTS == kPoints + 1, "a record holds hx_xing's seek points as they are");
+static_assert(sizeof(HX_LEDGER) == 4176 && sizeof(HX_LEDGER) % 16 == 0 && offsetof(HX_LEDGER, open) == 16 && offsetof(HX_LEDGER, crc) == 36 &&
+              offsetof(HX_LEDGER, toc_counter) == 44 && offsetof(HX_LEDGER, pt) == 64, "HX_LEDGER's layout is public");
+
+extern "C" void hx_ledger_open(HX_LEDGER *r, int ncalls, int frames_per_call, int head_bytes, int flags)
+{
+    memset(r, 0, sizeof(*r));
+    r->ncalls = ncalls; r->frames_per_call = frames_per_call; r->head_bytes = head_bytes; r->flags = flags;
+    r->open = 1;
+    r->every = 1;
+}
+
+// hx_xing_toc on a record's points
+static int ledger_toc(HX_LEDGER *r, int frames, int bs_bytes)
+{
+    r->pt[r->npt][0] = frames;
+    r->pt[r->npt][1] = bs_bytes;
+    r->npt++;
+    if (r->npt < kPoints) return r->every;
+    for (int i = 0, k = 1; i < kPoints / 2; i++, k += 2) { r->pt[i][0] = r->pt[k][0]; r->pt[i][1] = r->pt[k][1]; }
+    r->npt = kPoints / 2;
+    r->every += r->every;
+    return r->every;
+}
+
+// One stream's slice of one call (the rule: include/hmp3_amd.h).  It restates, per input frame, Tagger::after_call and the
+// end scan of the command-line tool's batch loop, which follow tomp3.cpp:976-1036.
+extern "C" int hx_ledger_update(HX_LEDGER *r, const int *stats, const unsigned short *crc, int n, int out_bytes)
+{
+    if (!r->open || n <= 0) return 0;
+    if (r->ended) { r->call_bytes = 0; return 0; }
+    const unsigned expected = (unsigned) r->ncalls * (unsigned) r->frames_per_call, last = (unsigned) stats[2 * (n - 1) + 1];
+    for (int f = 0; f < n; f++) {
+        const int u = r->fed + f;
+        const unsigned fr = (unsigned) stats[2 * f], by = (unsigned) stats[2 * f + 1];
+        if (u < r->ncalls && (r->flags & 1) && --r->toc_counter <= 0) r->toc_counter = ledger_toc(r, (int) fr + 1, (int) by + r->head_bytes);
+        if (u >= r->ncalls - 1 && fr >= expected) {
+            const unsigned e = (unsigned) out_bytes - (last - by);
+            r->frames = fr; r->bytes = by;
+            r->crc = hx_xing_crc_combine((unsigned short) r->crc, crc[f], (long long) e);
+            r->call_bytes = (int) e;
+            r->fed = u + 1;
+            r->ended = 1;
+            return 1;
+        }
+    }
+    r->frames = (unsigned) stats[2 * (n - 1)]; r->bytes = last;
+    r->crc = hx_xing_crc_combine((unsigned short) r->crc, crc[n - 1], out_bytes);
+    r->call_bytes = out_bytes;
+    r->fed += n;
+    return 0;
+}
+
+extern "C" int hx_xing_load_points(hx_xing *x, const HX_LEDGER *r)
+{
+    if (r->npt < 0 || r->npt >= kPoints || r->every < 1) return 0;
+    memset(x->pt, 0, sizeof(x->pt));
+    memcpy(x->pt, r->pt, sizeof(int) * 2 * (size_t) r->npt);
+    x->npt = r->npt;
+    x->every = r->every;
+    return 1;
 }
 
 // 100 seek bytes: byte i = 256 * (file offset at i % of the frames) / file size, linear between points

@@ -472,6 +472,87 @@ int hx_batch_encode_src_counts_host(hx_batch *b, const unsigned char *in, long l
                                     int nframes, const int *nfr, unsigned char *out, long long out_stride, int *out_bytes,
                                     long long *in_used, int *stats, unsigned short *crc);
 
+/* ---- file ledger: where each stream's file ends, its MusicCRC and its seek points, kept on the GPU (no reference
+   equivalent; per file it is what the single-file loop of tomp3.cpp:976-1036 keeps on the host) ----
+   A caller that runs files through a batch has to decide, per file, at which frame the file's drain ends
+   ("while (get_frames() < frames_expected)"), which bytes of the call that holds this frame belong to the file, the
+   MusicCRC of those bytes, and the seek points of the Xing tag (one hx_xing_toc per input call).  From the frame counters
+   and CRCs that is one host iteration per encoded frame.  A ledger does it on the device: one HX_LEDGER record per
+   stream, updated by a kernel right behind a call's CRC kernel, read when convenient.
+   The record (fixed layout, sizeof a multiple of 16, padding words always 0: two records compare bytewise): */
+#define HX_LEDGER_POINTS 513    /* xhead.c:71 keeps 512 seek points; XingHeaderUpdateInfo appends the file's end */
+typedef struct {
+    /* the file's parameters (hx_ledger_open) */
+    int ncalls;                 /* >= 1: the calls of the single-file loop on the file's input */
+    int frames_per_call;        /* 1, or 2 at the MPEG-2 rates */
+    int head_bytes;             /* the tag frame's size, 0 without a tag */
+    int flags;                  /* bit 0: keep seek points */
+    /* the state; expected = ncalls * frames_per_call */
+    int open, ended;
+    int fed;                    /* calls consumed so far */
+    unsigned frames, bytes;     /* the file's get_frames() and bytes so far; final once ended */
+    unsigned crc;               /* the MusicCRC of those bytes (16 bits) */
+    int call_bytes;             /* how many bytes of the row of the last call that fed it belong to the file */
+    int toc_counter, npt, every;                /* the seek-point state of hx_xing: calls to the next point, points held, */
+    int pad0[2];                                /* and the spacing of the points in calls */
+    int pt[HX_LEDGER_POINTS][2];                /* (frames, bytes) */
+    int pad1[2];
+} HX_LEDGER;
+/* A call updates stream i's record as follows.  The stream takes n frames (its per-stream count, or nframes);
+   (fr[f], by[f]) are its frame counters, c[f] its per-frame CRCs, nb = out_bytes[i], e[f] as under hx_batch_crc_buffer:
+     not open, or n == 0:   the record is bit-identical before and after
+     ended:                 call_bytes = 0, nothing else changes (the slot may go on encoding silence; it no longer counts)
+     otherwise, for f = 0 .. n-1, with u = fed + f:
+         if u < ncalls and (flags & 1):  if (--toc_counter <= 0) toc_counter = toc_step(fr[f] + 1, by[f] + head_bytes)
+         if u >= ncalls - 1 and (unsigned) fr[f] >= expected:     the drain ends here:
+             frames = fr[f]; bytes = by[f]; crc = combine(crc, c[f], e[f]); call_bytes = e[f]; fed = u + 1; ended = 1; stop
+     not ended after f = n-1:
+         frames = fr[n-1]; bytes = by[n-1]; crc = combine(crc, c[n-1], nb); call_bytes = nb; fed += n
+   toc_step is hx_xing_toc (append; at 512 points keep every second one and double `every`), combine is
+   hx_xing_crc_combine.
+   Host side, no GPU: hx_ledger_open fills a new record; hx_ledger_update applies the rule to one stream's slice of one
+   call (stats [n][2], crc [n]; returns 1 when the call ended the file) - for callers that keep their counters on the host
+   and for the hx_enc_* route; hx_xing_load_points copies a record's seek points into an hx_xing, after which
+   hx_xing_update_info(..., toc = NULL, ...) builds the 100 TOC bytes as after the hx_xing_toc calls themselves (1 = ok,
+   0 = a record whose point count is out of range). */
+void hx_ledger_open(HX_LEDGER *r, int ncalls, int frames_per_call, int head_bytes, int flags);
+int hx_ledger_update(HX_LEDGER *r, const int *stats, const unsigned short *crc, int n, int out_bytes);
+/* The batch's records: [nstreams] on the device, allocated and zeroed (all closed) at the first hx_batch_ledger_begin; a
+   batch that never calls it allocates nothing and launches nothing more than before.
+   hx_batch_ledger_begin: slot idx[e] gets a new open record with open[e]'s ncalls, head_bytes and flags (reserved: 0) and
+   the batch's frames_per_call.  A slot operation with hx_batch_reset_streams' contract word for word: a HOST list of
+   distinct slots, one launch whatever n is, ordered like a plain device call behind everything the batch has in flight
+   (the deferred packing of the last submit goes out first, ungated, so the previous occupant's last update is through),
+   the list through the slot operations' staging rotation, not under stream capture, n = 0 returns 0 and launches nothing,
+   the same refusals before anything is allocated, uploaded or launched, plus a null `open` with n > 0 and
+   "entry e: ncalls < 1" / "entry e: head_bytes < 0".  It does not reset the encoder: pair it with hx_batch_reset_streams
+   or hx_batch_assign_streams, in either order (the second of the two finds nothing deferred).  The counters a ledger reads
+   are the stream's absolute get_frames() and bytes, so a record is meaningful only for a stream that was reset (or new)
+   when its file began.
+   Calls while the ledger exists: the update kernel goes out right behind the call's CRC kernel - of a submit with its
+   deferred packing, reading the counters, CRCs, byte counts and per-stream counts of its own submit; deferred packings go
+   out in submit order on one stream, so the records advance in call order.  Every encode or submit entry point, plain
+   and converting, device and host buffers, whose call feeds (n > 0) at least one record that is open and not known to have
+   ended needs a frame-counter buffer and a CRC buffer in force (host calls: the forms that return both, *_host_crc and
+   hx_batch_encode_src_counts_host with stats and crc); otherwise the call is refused (-1, hx_last_error names the stream)
+   before anything runs and the batch stays usable.  "Known to have ended": the end is decided on the device, and the host
+   learns it from hx_batch_ledger_read; until a read has shown a record ended, it counts as live.  Rows, out_bytes, packets,
+   counters, CRCs and the dense image are written exactly as without a ledger; the dense image follows out_bytes, not
+   call_bytes.
+   hx_batch_ledger_read: record e of out[n] is slot idx[e]'s.  Synchronous like hx_batch_status: enqueues the deferred
+   packing first, then one gather launch and one copy whatever n is.  hx_batch_ledger_read_device: the same gather in
+   stream order into device memory (16-byte aligned, else -1), like hx_batch_get_stream_states_device; it does not tell the
+   host which records ended.
+   hx_multi_ledger_begin / hx_multi_ledger_read: the same over all blocks (idx counts streams over all blocks); synchronous,
+   every refusal made for all blocks before one of them starts: all blocks or (-1) none.
+   Not covered: the checkpoint blob (state version 3, no ledger in it) - a stream moved between batches takes its record
+   along through hx_batch_ledger_read and a new hx_batch_ledger_begin, which restarts it; moving a half-built record; the
+   hx_enc_* encoder, which has hx_ledger_update on the host. */
+typedef struct { int ncalls, head_bytes, flags, reserved; } HX_LEDGER_OPEN;
+int hx_batch_ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n, void *stream);
+int hx_batch_ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out);
+int hx_batch_ledger_read_device(hx_batch *b, const int *idx, int n, HX_LEDGER *d_out, void *stream);
+
 /* ---- host placement (no reference equivalent): a host-fed GPU reads ~50 GB/s of PCM over PCIe, so its page-locked
    buffers and the threads that submit its copies belong on the NUMA node the device hangs on.
    hx_device_numa_node: that node from sysfs (-1 = unknown or not a NUMA machine).  hx_bind_thread_to_device: restricts the
@@ -520,6 +601,9 @@ hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstreams, const
                                const HX_SOURCE *src, const int *cfg, int max_frames);
 /* the same over all blocks (idx counts streams over all blocks); synchronous like the other hx_multi calls; all blocks or (-1) none */
 int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *cfg, int n);
+/* hx_batch_ledger_begin / hx_batch_ledger_read over all blocks (idx counts streams over all blocks); synchronous; all blocks or (-1) none */
+int hx_multi_ledger_begin(hx_multi *m, const int *idx, const HX_LEDGER_OPEN *open, int n);
+int hx_multi_ledger_read(hx_multi *m, const int *idx, int n, HX_LEDGER *out);
 long long hx_multi_src_in_stride(const hx_multi *m, int nframes);
 int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
                              unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats);
@@ -563,6 +647,8 @@ int hx_xing_header(hx_xing *x, int samprate, int h_mode, int cr_bit, int origina
                    const unsigned char *buf20, const unsigned char *buf20b, int kbps);
 /* xhead.c:695 XingHeaderTOC: record a seek point; returns how many encode calls to wait for the next one */
 int hx_xing_toc(hx_xing *x, int frames, int bs_bytes);
+/* the seek points a ledger record holds (HX_LEDGER above) become x's, as if x had taken the record's hx_xing_toc calls */
+int hx_xing_load_points(hx_xing *x, const HX_LEDGER *r);
 /* xhead.c:486 XingHeaderUpdateInfo: final frame / byte counts, TOC, LAME info fields and CRCs; 1 = ok */
 int hx_xing_update_info(hx_xing *x, unsigned frames, int bs_bytes, int vbr_scale, const unsigned char *toc,
                         unsigned char *buf, const unsigned char *buf20, const unsigned char *buf20b,
