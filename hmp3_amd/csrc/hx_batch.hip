@@ -329,7 +329,7 @@ extern "C" void hx_batch_debug_enable(hx_batch *b, int on)
         hipSetDevice(b->device);
         dev_alloc(b, b->d_dbg, sizeof(HxFrameDebug) * (size_t) b->S * b->maxF);
         dev_alloc(b, b->d_xrdbg, sizeof(float) * (size_t) b->S * 2 * b->maxF * 1152);
-        dev_alloc(b, b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 2);
+        dev_alloc(b, b->d_dbgmetric, sizeof(int) * (size_t) b->S * 2 * b->maxF * 4);      // k_detect's metrics: a0, b0, a1, b1 per granule
         if (dev_alloc(b, b->d_prof, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS) == 0) hipMemset(b->d_prof, 0, sizeof(unsigned long long) * (size_t) b->S * HX_PROF_WORDS);
     }
 }
@@ -1056,6 +1056,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "frm") { src = w.frm; n = sizeof(HxFrameOut) * S * NG; }
     else if (k == "etab") { src = f.etab; n = sizeof(float) * S * NG * 128; }
     else if (k == "thr") { src = f.thr; n = sizeof(float) * S * NG * 128; }
+    else if (k == "thrprev") { src = f.thrprev; n = sizeof(float) * S * 128; }      // the pre-echo memory the last call started with (rows of streams that took no frame: not written)
     else if (k == "msbase") { src = f.msbase; n = sizeof(int) * S * NG; }
     else if (k == "place") { src = b->d_dur + S; n = sizeof(unsigned) * S; }       // per WORKGROUP of the last allocator launch (launch order): XCC id << 16 | HW_ID[15:0] (CU [11:8], SH [12], SE [15:13])
     else if (k == "dur") { src = b->d_dur; n = sizeof(unsigned) * S; }              // the last allocator launch's per-stream durations, 100 MHz ticks
@@ -1068,7 +1069,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
     else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
     else if (k == "srcpcm" && b->d_src_pcm) { src = b->d_src_pcm; n = sizeof(float) * S * b->src_lastF * 1152 * b->nchan; }   // the converted PCM of the last call
-    else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 2; }
+    else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 4; }      // [S][NG][4]: the attack metric of channel 0 / 1 for short_flag_prev = 0, then for 1
     if (!src) return -1;
     if (n > cap) n = cap;
     hipMemcpy(dst, src, (size_t) n, hipMemcpyDeviceToHost);

@@ -771,7 +771,10 @@ extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *nam
     TAB("huff_code", g.huff_code) TAB("huff_len", g.huff_len)
     TAB("lane_run", p.lane_run) TAB("band_last_lane", p.band_last_lane)
     TAB("nchan", p.nchan)
+    TAB("nsf2", p.nsf2) TAB("nsf3", p.nsf3) TAB("nbmax", p.nbmax) TAB("nbmax2", p.nbmax2) TAB("nbmax3", p.nbmax3)
+    TAB("psy_short_npart", p.psyS.npart) TAB("alloc1", p.alloc1)
 #undef TAB
+    if (k == "sizeof_band_prep") { static int v[1]; v[0] = (int) sizeof(HxBandPrep); src = v; n = sizeof(v); }     // for the tests' mirror of the "band" tap
     if (k == "run_w") { static int v[1]; v[0] = p.run_w; src = v; n = sizeof(v); }
     if (k == "scalars") {
         static int v[16];

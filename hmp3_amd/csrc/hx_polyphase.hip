@@ -277,7 +277,8 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
             const unsigned char f = (unsigned char) (f0 | (f1 << 1));
             sflg[wv][lane] = f;
             flg[(long long) s * NG + g] = f;
-            if (dbg_metric) { dbg_metric[((long long) s * NG + g) * 2] = a0; dbg_metric[((long long) s * NG + g) * 2 + 1] = b0; }
+            // (tests only: the metric of both channels for short_flag_prev = 0 and 1 - a0, b0, a1, b1)
+            if (dbg_metric) *reinterpret_cast<int4 *>(dbg_metric + ((long long) s * NG + g) * 4) = make_int4(a0, b0, a1, b1);
         }
         DETECT_SYNC();
         if (lane == 0) {

@@ -157,7 +157,7 @@ struct alignas(16) HxBandPrep {
 // Optional per-frame debug taps written by the allocator kernel (tests only).
 struct HxFrameDebug {
     int ms, ms_metric[2], byte_pool, MNR_after;
-    int mask_mb[2][2][22];      // [gr][ch] mbLog of the per-sfb mask
+    int mask_mb[2][2][22];      // unused: no kernel writes it (kept for the layout, which two test mirrors share); the masks after pre-echo control are HxBandPrep.maskmb, the "band" tap
     HxGr gr[2][2];
     int sf[2][2][22];
     int scfsi[2];

@@ -163,6 +163,26 @@ typedef struct {
     int scfsi[2];
     int main_bytes;
 } hxo_frame_debug;
+/* (etab / thr / mask are filled on every path that runs the long model - MPEG-1 and MPEG-2, stereo and mono, both
+   allocators - and attack on every path that runs the detector.) */
+
+/* Further per-frame taps, a record of their own (filled when hxo_set_stage_taps() has been called): hxo_frame_debug keeps
+   its size, so a caller that mirrors the record above as it was is never written past its end. */
+typedef struct {
+    /* short granules, [gr][ch][12 * w + sfb]: the spread sums of hxo_psy_short before pre-echo control (what the kernels'
+       psy_short stores as thr; their allocator applies the control), and the masks the function returns after it */
+    float thr_short[2][2][36], mask_short[2][2][36];
+    /* start values of the long-block allocator (hxo_alloc.c: startup_lr / startup_ms / gzero_gmin), [gr][ch][sfb];
+       the nb_* counts are zero for a granule that did not go through that start (short, or first-generation allocator) */
+    float xsxx[2][2][22], x34max[2][2][22];
+    int gzero[2][2][22];
+    int noise0[2][2][22];           /* band energy per line in mB of L / R */
+    int noise0_ms[2][2][22];        /* the same of M / S (frames coded M/S; zero otherwise) */
+    int mask_mb[2][2][22];          /* hxo_mblog(sm[ch][i].mask), i < 21, before the band width is subtracted */
+    int nb_x[2][2], nb_e[2][2], nb_z[2][2];    /* [gr][ch] bands formed: of xsxx, of noise0 / noise0_ms, of x34max / gzero */
+    int start_ms[2];                /* [gr] 1 = that start was the M/S one (MPEG-2: each granule is a frame with its own decision) */
+    int attack_prev[2];             /* [gr] the short_flag_prev the detector was called with (hxo_frame_debug.attack[gr][ch] is its result) */
+} hxo_stage_taps;
 
 /* what the noise measurement (noise_actual of the long and of the short allocator) saw beyond the 256-entry float table
    of ix^(4/3) since hxo_init: the lines dequantised through pow(), those of them quantised to 16384 or more, the largest
@@ -177,9 +197,12 @@ typedef struct hxo_encoder {
     unsigned char *packet;      /* set for the duration of hxo_encode_frame_packet */
     int packet_bytes, packet_bytes2[2];    /* MPEG-2: two packets per call, back to back */
     hxo_range_counts range[2];  /* [0] long blocks, [1] short blocks */
+    hxo_stage_taps *taps;
 } hxo_encoder;
 void hxo_set_debug(hxo_encoder *e, hxo_frame_debug *d);
 int hxo_sizeof_frame_debug(void);
+void hxo_set_stage_taps(hxo_encoder *e, hxo_stage_taps *t);
+int hxo_sizeof_stage_taps(void);
 
 /* --- API --- */
 hxo_encoder *hxo_new(void);

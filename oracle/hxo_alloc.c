@@ -25,6 +25,7 @@ typedef struct {
     int nchan, ms_flag, block_type;
     int maxBits, maxTargetBits, minTargetBits, PoolBits, TargetBits, deltaMNR, activeBands;
     int snr[2][22], Noise0[2][22], Noise[2][22], NT[2][22];
+    int Noise0lr[2][22];            /* M/S start: the L / R values (N0L, N0R), kept for the stage taps */
     float xsxx[2][22], xsxxms[2][22], x34max[2][22];
     int ix10xmax[2][22], gzero[2][22], gmin[2][22], gsf[2][22], sf[2][22], G[2], active_sf[2][22];
     float x34[2][576];
@@ -349,6 +350,7 @@ static void startup_ms(ba_t *b, hxo_sigmask sm[][36])
         }
         b->NT[0][i] = NTL; b->NT[1][i] = NTR;
         b->snr[0][i] = N0L - NTL; b->snr[1][i] = N0R - NTR;
+        b->Noise0lr[0][i] = N0L; b->Noise0lr[1][i] = N0R;
         b->Noise0[0][i] = hxo_mblog(ss) - cbw;
         b->Noise0[1][i] = hxo_mblog(sd) - cbw;
     }
@@ -956,6 +958,30 @@ static void null_gr(hxo_gr *g, int block_type)
     g->aux_nreg[0] = g->aux_nreg[1] = g->aux_nreg[2] = 0;
 }
 
+/* stage taps: the start values of granule igr as startup_lr / startup_ms and gzero_gmin left them, with the number of bands
+   each loop formed (its bound) */
+int hxo_tap_igr;
+static void tap_start(const ba_t *b, hxo_sigmask sm[][36], int igr)
+{
+    hxo_stage_taps *d = b->e->taps;
+    const hxo_params *p = b->p;
+    int ch, i;
+    d->start_ms[igr] = b->ms_flag;
+    for (ch = 0; ch < b->nchan; ch++) {
+        d->nb_x[igr][ch] = b->ms_flag ? p->nsf[0] : p->nsf3[ch];
+        d->nb_e[igr][ch] = b->ms_flag ? p->nsf[0] : p->nsf[ch];
+        d->nb_z[igr][ch] = b->ms_flag ? p->nsf2[ch] : p->nsf3[ch];
+        for (i = 0; i < 22; i++) {
+            d->xsxx[igr][ch][i] = b->xsxx[ch][i];
+            d->x34max[igr][ch][i] = b->x34max[ch][i];
+            d->gzero[igr][ch][i] = b->gzero[ch][i];
+            d->noise0[igr][ch][i] = b->ms_flag ? b->Noise0lr[ch][i] : b->Noise0[ch][i];
+            d->noise0_ms[igr][ch][i] = b->ms_flag ? b->Noise0[ch][i] : 0;
+            d->mask_mb[igr][ch][i] = (i < 21) ? hxo_mblog(sm[ch][i].mask) : 0;
+        }
+    }
+}
+
 /* bitallo3.cpp:484-678 */
 void hxo_bitallo_long(hxo_encoder *e, float xr[2][576], hxo_sigmask sm[2][36],
                       int min_bits, int target_bits, int max_bits, int bit_pool,
@@ -1017,6 +1043,7 @@ void hxo_bitallo_long(hxo_encoder *e, float xr[2][576], hxo_sigmask sm[2][36],
     b->minTargetBits = HXO_MIN(b->minTargetBits, b->maxTargetBits - 100);
 
     if (ms_flag) startup_ms(b, sm); else startup_lr(b, sm);
+    if (e->taps) tap_start(b, sm, hxo_tap_igr & 1);
 
     if (b->activeBands <= 0) {
         for (i = 0; i < b->nchan; i++) {

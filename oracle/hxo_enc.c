@@ -13,7 +13,10 @@ void hxo_free(hxo_encoder *e) { free(e); }
 int hxo_sizeof_encoder(void) { return (int) sizeof(hxo_encoder); }
 int hxo_sizeof_frame_debug(void) { return (int) sizeof(hxo_frame_debug); }
 void hxo_set_debug(hxo_encoder *e, hxo_frame_debug *d) { e->dbg = d; }
-extern float *hxo_tap_etab, *hxo_tap_thr;
+int hxo_sizeof_stage_taps(void) { return (int) sizeof(hxo_stage_taps); }
+void hxo_set_stage_taps(hxo_encoder *e, hxo_stage_taps *t) { e->taps = t; }
+extern float *hxo_tap_etab, *hxo_tap_thr, *hxo_tap_thr_short;
+extern int hxo_tap_igr;
 unsigned hxo_frames_out(const hxo_encoder *e) { return e->s.tot_frames_out; }
 unsigned hxo_bytes_out(const hxo_encoder *e) { return e->s.tot_bytes_out; }
 void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3])
@@ -383,6 +386,8 @@ static void blocktype_select(hxo_encoder *e, int igr)
     v1 = detect(s->sample[0][ahead], s->attack_buf[0], s->short_flag_next[prev_gr]);
     v2 = (e->p.nchan == 2) ? detect(s->sample[1][ahead], s->attack_buf[1], s->short_flag_next[prev_gr]) : 0;
     s->last_attack[igr][0] = v1; s->last_attack[igr][1] = v2;
+    if (e->dbg) { e->dbg->attack[igr][0] = v1; e->dbg->attack[igr][1] = v2; }
+    if (e->taps) e->taps->attack_prev[igr] = s->short_flag_next[prev_gr];
     if (v1 > e->p.short_block_threshold) sf = 1;
     if (v2 > e->p.short_block_threshold) sf = 1;
     s->short_flag_next[igr] = sf;
@@ -412,6 +417,22 @@ static void transform_granule(hxo_encoder *e, int igr)
         hxo_polyphase_granule(p, s->buf[ch] + (igr == 0 ? 576 : 0), s->sample[ch][ahead]);
     }
     s->igrx = (s->igrx + 1) & 3;
+}
+
+/* the psy model of one granule and channel (long or short), with its stage taps when they are on */
+static void psy_granule(hxo_encoder *e, int igr, int ch, int bt)
+{
+    hxo_state *s = &e->s;
+    hxo_frame_debug *d = e->dbg;
+    hxo_stage_taps *t = e->taps;
+    int i;
+    if (d) { hxo_tap_etab = d->etab[igr][ch]; hxo_tap_thr = d->thr[igr][ch]; }
+    if (t) hxo_tap_thr_short = t->thr_short[igr][ch];
+    if (bt != 2) hxo_psy_long(&e->p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], bt);
+    else hxo_psy_short(&e->p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], s->block_type_prev[igr]);
+    hxo_tap_etab = hxo_tap_thr = hxo_tap_thr_short = 0;
+    if (d) for (i = 0; i < 22; i++) d->mask[igr][ch][i] = s->sig_mask[ch][i].mask;
+    if (t && bt == 2) for (i = 0; i < 36; i++) t->mask_short[igr][ch][i] = s->sig_mask[ch][i].mask;
 }
 
 /* mp3enc.cpp:1492-1597 */
@@ -466,13 +487,10 @@ static int encode_joint(hxo_encoder *e, hxo_bitw *w)
     for (igr = 0; igr < 2; igr++) {
         int bt = s->block_type[igr];
         for (ch = 0; ch < 2; ch++) {
-            if (e->dbg) { hxo_tap_etab = e->dbg->etab[igr][ch]; hxo_tap_thr = e->dbg->thr[igr][ch]; }
-            if (bt != 2) hxo_psy_long(p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], bt);
-            else hxo_psy_short(p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], s->block_type_prev[igr]);
-            hxo_tap_etab = hxo_tap_thr = 0;
-            if (e->dbg) { int i; for (i = 0; i < 22; i++) e->dbg->mask[igr][ch][i] = s->sig_mask[ch][i].mask; }
+            psy_granule(e, igr, ch, bt);
         }
         s->gr[igr][0].block_type = s->gr[igr][1].block_type = bt;
+        hxo_tap_igr = igr;
         hxo_bitallo_long(e, s->xr[igr], s->sig_mask, ba_min, TargetBits, ba_max, bit_pool,
                          s->sf[igr], s->gr[igr], ms);
         if (e->dbg) {
@@ -535,9 +553,9 @@ static int encode_single(hxo_encoder *e, hxo_bitw *w)
     for (igr = 0; igr < 2; igr++) {
         int bt = s->block_type[igr];
         hxo_gr *g = &s->gr[igr][0];
-        if (bt != 2) hxo_psy_long(p, s->xr[igr][0], s->ecsave[0], s->sig_mask[0], bt);
-        else hxo_psy_short(p, s->xr[igr][0], s->ecsave[0], s->sig_mask[0], s->block_type_prev[igr]);
+        psy_granule(e, igr, 0, bt);
         g->block_type = bt;
+        hxo_tap_igr = igr;
         hxo_bitallo_long(e, s->xr[igr], s->sig_mask, ba_min, p->AveTargetBits, ba_max, bit_pool, s->sf[igr], s->gr[igr], 0);
         if (e->dbg) {
             int i;
@@ -566,7 +584,7 @@ static int encode_single(hxo_encoder *e, hxo_bitw *w)
 static void psy_long_all(hxo_encoder *e, int igr)
 {
     int ch;
-    for (ch = 0; ch < e->p.nchan; ch++) hxo_psy_long(&e->p, e->s.xr[igr][ch], e->s.ecsave[ch], e->s.sig_mask[ch], 0);
+    for (ch = 0; ch < e->p.nchan; ch++) psy_granule(e, igr, ch, 0);
 }
 
 /* encode_jointA (mp3enc.cpp:1236-1318): joint stereo with an intensity part, both channels allocated together */
@@ -763,11 +781,9 @@ static int encode_granule_lsf(hxo_encoder *e, hxo_bitw *w, int igr)
         e->dbg->block_type[igr] = bt;
         memcpy(e->dbg->xr_pre[igr], s->xr[igr], sizeof(s->xr[igr]));
     }
-    for (ch = 0; ch < p->nchan; ch++) {
-        if (bt != 2) hxo_psy_long(p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], bt);
-        else hxo_psy_short(p, s->xr[igr][ch], s->ecsave[ch], s->sig_mask[ch], s->block_type_prev[igr]);
-    }
+    for (ch = 0; ch < p->nchan; ch++) psy_granule(e, igr, ch, bt);
     s->gr[igr][0].block_type = s->gr[igr][1].block_type = bt;
+    hxo_tap_igr = igr;
     hxo_bitallo_long(e, s->xr[igr], s->sig_mask, ba_min, p->nchan * p->AveTargetBits, ba_max, bit_pool,
                      s->sf[igr], s->gr[igr], ms);
     if (e->dbg) {
@@ -904,6 +920,9 @@ int hxo_encode_frame(hxo_encoder *e, const float *pcm, unsigned char *out)
     int bytes, raw_bytes, pad = 0, ms, ibr = 0, mf, bytesout;
 
     input_filter(e, pcm);
+    if (e->taps) {      /* (a granule that does not go through the long allocator's start leaves its counts at zero) */
+        memset(e->taps->nb_x, 0, sizeof(e->taps->nb_x)); memset(e->taps->nb_e, 0, sizeof(e->taps->nb_e)); memset(e->taps->nb_z, 0, sizeof(e->taps->nb_z));
+    }
     if (!p->h_id) return encode_block_lsf(e, out);
     if (!p->vbr_flag) {
         s->padcount -= p->remainder;

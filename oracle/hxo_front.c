@@ -287,8 +287,9 @@ int hxo_attack_detect_lsf(const float *sample, int eng[32], int short_flag_prev)
     return m;
 }
 
-/* test taps: when set, hxo_psy_long also stores etab and the unclamped thresholds */
-float *hxo_tap_etab, *hxo_tap_thr;
+/* test taps: when set, hxo_psy_long also stores etab and the unclamped thresholds, hxo_psy_short its spread sums before
+   pre-echo control ([12 * w + sfb]) */
+float *hxo_tap_etab, *hxo_tap_thr, *hxo_tap_thr_short;
 
 /* emap.c:96-121 + spdsmr.c:188-320 */
 void hxo_psy_long(const hxo_params *p, const float *xr, float *esave, hxo_sigmask *sm, int block_type)
@@ -408,6 +409,7 @@ void hxo_psy_short(const hxo_params *p, const float *xr, float *esave, hxo_sigma
         for (j = 0; j < n; j++, k++)
             for (wn = 0; wn < 3; wn++) ts[wn] += w[k] * e[wn][q + j];
         for (wn = 0; wn < 3; wn++) mask[wn][m] = sm[12 * wn + m].mask = s[wn] + ts[wn];
+        if (hxo_tap_thr_short) for (wn = 0; wn < 3; wn++) hxo_tap_thr_short[12 * wn + m] = mask[wn][m];
     }
     mpart = (npart + 1) >> 1;
     for (i = 0; i < mpart; i++) {

@@ -127,6 +127,16 @@ def pow43(first, n):
     return out
 
 
+def pow34(x):
+    """float32 [n]: x^(3/4) of non-negative float32 values as the allocator forms it (hxo_pow34)"""
+    x = np.ascontiguousarray(x, dtype=np.float32)
+    y = np.zeros(x.shape, dtype=np.float32)
+    lib().hxo_pow34.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    lib().hxo_pow34.restype = None
+    lib().hxo_pow34(x.ctypes.data, y.ctypes.data, x.size)
+    return y
+
+
 class OracleEncoder:
     """one stream through the restatement"""
 
@@ -255,6 +265,18 @@ class FrameDebug(C.Structure):
         ("signx", C.c_ubyte * (2 * 2 * 576)), ("scfsi", C.c_int * 2), ("main_bytes", C.c_int)]
 
 
+class StageTaps(C.Structure):
+    """hxo_stage_taps (oracle/hxo.h): the taps beside FrameDebug, a record of their own"""
+    _fields_ = [
+        # short granules [gr][ch][12 * w + sfb]: spread sums before pre-echo control, masks after it
+        ("thr_short", C.c_float * (2 * 2 * 36)), ("mask_short", C.c_float * (2 * 2 * 36)),
+        # start values of the long-block allocator [gr][ch][sfb], and how many bands of each were formed [gr][ch]
+        ("xsxx", C.c_float * (2 * 2 * 22)), ("x34max", C.c_float * (2 * 2 * 22)), ("gzero", C.c_int * (2 * 2 * 22)),
+        ("noise0", C.c_int * (2 * 2 * 22)), ("noise0_ms", C.c_int * (2 * 2 * 22)), ("mask_mb", C.c_int * (2 * 2 * 22)),
+        ("nb_x", C.c_int * 4), ("nb_e", C.c_int * 4), ("nb_z", C.c_int * 4),
+        ("start_ms", C.c_int * 2), ("attack_prev", C.c_int * 2)]
+
+
 def oracle_enable_debug(enc):
     """attach a FrameDebug record to an OracleEncoder; returns it (refilled on every frame)"""
     l = lib()
@@ -265,3 +287,15 @@ def oracle_enable_debug(enc):
     l.hxo_set_debug(enc.h, C.byref(d))
     enc._dbg = d
     return d
+
+
+def oracle_enable_stage_taps(enc):
+    """attach a StageTaps record to an OracleEncoder; returns it (refilled on every frame)"""
+    l = lib()
+    l.hxo_sizeof_stage_taps.restype = C.c_int
+    assert l.hxo_sizeof_stage_taps() == C.sizeof(StageTaps), (l.hxo_sizeof_stage_taps(), C.sizeof(StageTaps))
+    t = StageTaps()
+    l.hxo_set_stage_taps.argtypes = [C.c_void_p, C.c_void_p]
+    l.hxo_set_stage_taps(enc.h, C.byref(t))
+    enc._taps = t
+    return t

@@ -768,8 +768,9 @@ STAGE_CASES = {
 def test_every_stage_bit_exact(name):
     """Stage by stage against the oracle's taps, bit patterns compared with == : K1 polyphase, K4 MDCT (long and
     short layouts) and psy model, block types, K5 stereo decision, K6 side info / scalefactors / reservoir, and
-    what K6 hands to the packer (quantised lines and signs).  Mono and MPEG-2 paths: the taps the oracle has there
-    (spectrum, block types, quantised lines, signs)."""
+    what K6 hands to the packer (quantised lines and signs); on every path also the attack metric, the short model's sums
+    and masks, and k_prep's magnitudes, x^(3/4), band start values and masks after pre-echo control.  Mono and MPEG-2
+    paths lack polyphase and the allocator's frame record, which the oracle taps on the MPEG-1 stereo path only."""
     kw, sr, bursts, taps = STAGE_CASES[name]
     mono = kw.get("mode") == 3
     S, F = 4, 24
@@ -779,6 +780,7 @@ def test_every_stage_bit_exact(name):
     tb = TapBatch(api(), kw, S, F, taps)        # (tests/stage_taps.py: the comparison itself, shared with test_gpu_dynamic_range.py)
     tb.call(pcm)
     assert tb.frames == [F] * S and all(len(g) > 0 for g in tb.got)
+    assert tb.msscan_paths == {"vector"} and tb.prep_granules > 0        # NG = 48: k_msscan's eight-granule loop (the scalar one: test_gpu_stage_taps.py)
     if bursts and "long" not in name:
         assert {0, 1, 2, 3} <= tb.seen_bt, tb.seen_bt      # every block type went through the stage comparison
     tb.close()
