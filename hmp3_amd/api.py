@@ -281,6 +281,33 @@ def _frame_counts(setter, handle, n, counts):
         raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
 
 
+def _pitch(batch_handle):
+    """hx_batch_pcm_channels, or None from a library build that predates it (A/B runs through HMP3AMD_LIB)"""
+    L = lib()
+    return int(L.hx_batch_pcm_channels(batch_handle)) if hasattr(L, "hx_batch_pcm_channels") else None
+
+
+def _pcm_rows(pcm, n, P):
+    """-> (a host call's PCM as the C ABI takes it, [n, nframes * 1152 * P], and nframes) from [n, nframes * 1152, P] or from
+    the rows as they lie in memory, [n, nframes * 1152 * P]: the form the callers of a mixed batch fill, a mono stream's
+    samples first in its row.  P: the batch's pitch (_pitch), or None: the channels of the three-dimensional form, else 1"""
+    f32 = np.asarray(pcm).dtype == np.float32
+    pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
+    if pcm.ndim == 3:
+        ch, nsamp = pcm.shape[2], pcm.shape[1]
+        if ch not in (1, 2) or (P is not None and ch != P):
+            raise ValueError("PCM of %d channels for a batch whose rows hold %s" % (ch, P))
+    elif pcm.ndim == 2:
+        nsamp, rem = divmod(pcm.shape[1], P or 1)
+        if rem:
+            raise ValueError("a PCM row of %d samples is no multiple of the %d channels it holds" % (pcm.shape[1], P))
+    else:
+        raise ValueError("PCM must be [n, nframes * 1152 * channels] or [n, nframes * 1152, channels]")
+    if pcm.shape[0] != n or nsamp % 1152 != 0:
+        raise ValueError("PCM must hold %d rows of whole frames (1152 samples per channel)" % n)
+    return pcm.reshape(n, -1), nsamp // 1152
+
+
 class Batch:
     """N independent streams on one GPU (hx_batch_*)."""
 
@@ -304,14 +331,35 @@ class Batch:
         """a batch over a menu of configurations (hx_batch_create_menu): controls = the menu's entries, cfg = the entry each
         of the nstreams slots starts with (None: entry 0); assign_streams hands slots other entries later.  sources (one
         Source per entry): a converting batch - SrcBatch.menu passes it"""
+        return cls._from_menu("hx_batch_create_menu", controls, nstreams, cfg, max_frames, device, sources)
+
+    @classmethod
+    def mixed(cls, controls, nstreams, cfg=None, max_frames=256, device=0, sources=None):
+        """Batch.menu whose entries may differ in channel count (hx_batch_create_mixed): the PCM rows are pitched for
+        P = pcm_channels() channels, and a mono stream of a P = 2 batch has its samples contiguous at the start of its row"""
+        return cls._from_menu("hx_batch_create_mixed", controls, nstreams, cfg, max_frames, device, sources)
+
+    @classmethod
+    def _from_menu(cls, create, controls, nstreams, cfg, max_frames, device, sources):
         self = cls.__new__(cls)
         self.n = int(nstreams)
         self._ec, nmenu, self._src, arr = _menu_args(controls, sources, self.n, cfg)
-        self.h = lib().hx_batch_create_menu(device, self.n, self._ec, nmenu, self._src, arr, max_frames)
+        self.h = getattr(lib(), create)(device, self.n, self._ec, nmenu, self._src, arr, max_frames)
         if not self.h:
-            raise RuntimeError("hx_batch_create_menu failed: " + last_error())
+            raise RuntimeError(create + " failed: " + last_error())
         self.max_frames = max_frames
         return self
+
+    def pcm_channels(self):
+        """P: the channels every PCM row is pitched for = the largest channel count over the menu"""
+        return int(lib().hx_batch_pcm_channels(self.h))
+
+    def stream_channels(self, i):
+        """channels of the entry slot i runs, as of the calls made so far"""
+        k = int(lib().hx_batch_stream_channels(self.h, int(i)))
+        if k < 0:
+            raise IndexError(i)
+        return k
 
     def nconfigs(self):
         """entries of the batch's menu (a batch not created from a menu: its distinct controls)"""
@@ -356,15 +404,12 @@ class Batch:
         _frame_counts(lib().hx_batch_frame_counts, self.h, self.n, counts)
 
     def encode_host(self, pcm, stats=False, crc=False):
-        """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, 2] -> list of bytes per stream; with stats (float32
+        """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, P] or [n, nframes*1152*P], P = pcm_channels() (a mono
+        stream of a mixed batch: its samples first in its row) -> list of bytes per stream; with stats (float32
         only) -> (that list, int32 [n, nframes, 2]: frames / bytes emitted so far after every input frame); with stats and
         crc -> (list, stats, uint16 [n, nframes]: the CRC of the call's bytes up to every input frame)"""
-        f32 = np.asarray(pcm).dtype == np.float32
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
-        if pcm.ndim == 2:
-            pcm = pcm[:, :, None]           # mono batch: [n, samples]
-        assert pcm.shape[0] == self.n and pcm.shape[2] in (1, 2) and pcm.shape[1] % 1152 == 0
-        nfr = pcm.shape[1] // 1152
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        f32 = pcm.dtype == np.float32
         stride = self.out_stride(nfr)
         out = np.zeros((self.n, stride), dtype=np.uint8)
         nb = np.zeros(self.n, dtype=np.int32)
@@ -401,12 +446,8 @@ class Batch:
     def encode_host_dense(self, pcm, dense_cap=None):
         """encode_host of which only the dense image crosses the link -> (list of bytes per stream, offsets int64 [n + 1]);
         dense_cap: the image buffer's size (default: dense_bound) - streams whose segment does not fit it come back as None"""
-        f32 = np.asarray(pcm).dtype == np.float32
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
-        if pcm.ndim == 2:
-            pcm = pcm[:, :, None]
-        assert pcm.shape[0] == self.n and pcm.shape[2] in (1, 2) and pcm.shape[1] % 1152 == 0
-        nfr = pcm.shape[1] // 1152
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        f32 = pcm.dtype == np.float32
         cap = self.dense_bound(nfr) if dense_cap is None else int(dense_cap)
         dense = np.zeros(max(cap, 1), dtype=np.uint8)
         off = np.zeros(self.n + 1, dtype=np.int64)
@@ -617,6 +658,11 @@ class SrcBatch(Batch):
         """a converting batch over a menu whose entry j is the pair (controls[j], sources[j]) (hx_batch_create_menu)"""
         return super().menu(controls, nstreams, cfg=cfg, max_frames=max_frames, device=device, sources=sources)
 
+    @classmethod
+    def mixed(cls, controls, sources, nstreams, cfg=None, max_frames=256, device=0):
+        """SrcBatch.menu whose entries may differ in the converter's output channels (hx_batch_create_mixed)"""
+        return super().mixed(controls, nstreams, cfg=cfg, max_frames=max_frames, device=device, sources=sources)
+
     def schedule(self, i, nframes):
         """(bytes each of stream i's next nframes calls consumes, bytes they read)"""
         nb = np.zeros(nframes, dtype=np.int64)
@@ -698,16 +744,37 @@ class Multi:
     @classmethod
     def menu(cls, controls, nstreams, cfg=None, max_frames=256, ndev=0, devices=None, sources=None):
         """as Batch.menu, in blocks over several devices (hx_multi_create_menu): every block gets the whole menu"""
+        return cls._from_menu("hx_multi_create_menu", controls, nstreams, cfg, max_frames, ndev, devices, sources)
+
+    @classmethod
+    def mixed(cls, controls, nstreams, cfg=None, max_frames=256, ndev=0, devices=None, sources=None):
+        """as Batch.mixed, in blocks over several devices (hx_multi_create_mixed)"""
+        return cls._from_menu("hx_multi_create_mixed", controls, nstreams, cfg, max_frames, ndev, devices, sources)
+
+    @classmethod
+    def _from_menu(cls, create, controls, nstreams, cfg, max_frames, ndev, devices, sources):
         self = cls.__new__(cls)
         dv = (C.c_int * len(devices))(*devices) if devices else None
         if devices:
             ndev = len(devices)
         self.n = int(nstreams)
         self._ec, nmenu, self._src, arr = _menu_args(controls, sources, self.n, cfg)
-        self.h = lib().hx_multi_create_menu(ndev, dv, self.n, self._ec, nmenu, self._src, arr, max_frames)
+        self.h = getattr(lib(), create)(ndev, dv, self.n, self._ec, nmenu, self._src, arr, max_frames)
         if not self.h:
-            raise RuntimeError("hx_multi_create_menu failed: " + last_error())
+            raise RuntimeError(create + " failed: " + last_error())
         return self
+
+    def pcm_channels(self):
+        """as Batch.pcm_channels: the same for every block"""
+        return int(lib().hx_batch_pcm_channels(self.batch(0)))
+
+    def stream_channels(self, i):
+        """channels of the entry stream i (counted over all blocks) runs"""
+        for k in range(self.ndevices()):
+            _, first, count = self.shard(k)
+            if first <= i < first + count:
+                return int(lib().hx_batch_stream_channels(self.batch(k), int(i) - first))
+        raise IndexError(i)
 
     def batch(self, k):
         """block k's batch handle, for the per-batch C calls (hx_multi_batch)"""
@@ -760,9 +827,8 @@ class Multi:
 
     def encode_host(self, pcm, stats=False, crc=False):
         """as Batch.encode_host, over all streams"""
-        f32 = np.asarray(pcm).dtype == np.float32
-        pcm = np.ascontiguousarray(pcm, dtype=np.float32 if f32 else np.int16)
-        nfr = pcm.shape[1] // 1152
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.batch(0)))
+        f32 = pcm.dtype == np.float32
         stride = int(lib().hx_multi_out_stride(self.h, nfr))
         out = np.zeros((self.n, stride), dtype=np.uint8)
         nb = np.zeros(self.n, dtype=np.int32)
@@ -820,6 +886,11 @@ class SrcMulti(Multi):
     def menu(cls, controls, sources, nstreams, cfg=None, max_frames=256, ndev=0, devices=None):
         """as SrcBatch.menu, in blocks over several devices"""
         return super().menu(controls, nstreams, cfg=cfg, max_frames=max_frames, ndev=ndev, devices=devices, sources=sources)
+
+    @classmethod
+    def mixed(cls, controls, sources, nstreams, cfg=None, max_frames=256, ndev=0, devices=None):
+        """as SrcBatch.mixed, in blocks over several devices"""
+        return super().mixed(controls, nstreams, cfg=cfg, max_frames=max_frames, ndev=ndev, devices=devices, sources=sources)
 
     def in_stride(self, nframes):
         return int(lib().hx_multi_src_in_stride(self.h, nframes))

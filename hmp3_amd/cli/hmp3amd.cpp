@@ -1,8 +1,9 @@
 // hmp3amd - file front end over libhmp3amd.
 //   hmp3amd <input.wav|-> <output.mp3|-> [flags]                 one file: a bounded regular file as a batch of one, a pipe or
 //                                                                 a very large file frame by frame (hx_enc_* API)
-//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API); files at any rate and
-//                                                                 -A go through the converting batches (hx_multi_create_src)
+//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API), mono and stereo together
+//                                                                 (hx_multi_create_mixed); files at any rate and -A go through
+//                                                                 a converting batch
 //   ... -slots<n>                                                 the files of -batch through n slots of one batch: a file is
 //                                                                 read when a slot is free and written when its drain ends
 // Same flags, encode loop and output files as the reference CLI (reference
@@ -11,7 +12,7 @@
 // completed in place.  Accepted: RIFF/WAVE, mono or stereo, 8/16/24/32-bit PCM or 32-bit float,
 // 8 - 48 kHz (rates other than 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz, or -A, go through the sample-rate
 // converter first, as in the reference); everything else fails like an unsupported file.
-// Batch mode encodes all files as one batch of streams (same channel count, same flags) and
+// Batch mode encodes all files as one batch of streams (either channel count, one MPEG version, same flags) and
 // reproduces per file exactly what the single-file loop writes.  Containers: RIFF, RIFX, RF64 / BW64, Wave64.
 #include <algorithm>
 #include <cstdint>
@@ -252,6 +253,7 @@ struct Job {
     Input in;
     HX_E_CONTROL ctl;                   // the control the batch is created with for the file (converting route: the source's)
     HX_SOURCE src = {0, 0, 0, 0};
+    int nch = 0;                        // channels the file encodes to (mono, or stereo summed to mono: 1)
     size_t nc = 0;                      // calls of the single-file loop on the file's input (the drain follows them)
     std::vector<long long> start;       // converting route: where each of them starts in the file's bytes
     std::vector<unsigned char> stream;
@@ -503,9 +505,8 @@ bool job_calls(Job &j, const char *name, const Options &opt, bool conv)
     return true;
 }
 
-// what the batch takes for a file and the settings its encoder will report, from the header alone; *nch: the channel count
-// every file of the batch encodes to (0: none seen yet)
-bool job_control(Job &j, const char *name, const Options &opt, bool conv, int *nch)
+// what the batch takes for a file and the settings its encoder will report, from the header alone
+bool job_control(Job &j, const char *name, const Options &opt, bool conv)
 {
     Input &in = j.in;
     HX_E_CONTROL ec = in.ec;
@@ -513,9 +514,7 @@ bool job_control(Job &j, const char *name, const Options &opt, bool conv, int *n
         j.src = {in.wi.bits, in.is_float, opt.mpeg_select, in.mono_convert};
         if (!hx_src_encode_control(&in.ec, &j.src, &ec)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s): %s\n", name, hx_last_error()); return false; }
     } else if (in.mono_convert) ec.mode = 3;
-    const int c = ec.mode == 3 ? 1 : 2;
-    if (*nch && c != *nch) { fprintf(stderr, "\n -batch needs files that all encode to the same channel count\n"); return false; }
-    *nch = c;
+    j.nch = ec.mode == 3 ? 1 : 2;
     if (!hx_control_info(&ec, &in.ec_used, &in.head)) { fprintf(stderr, "\n ENCODER INIT FAIL (%s)\n", name); return false; }
     j.ctl = conv ? in.ec : ec;          // (a converting batch derives the encoder's control from the source's, as converter_calls did)
     return true;
@@ -562,22 +561,17 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     // converter's copy case); without one the plain batch runs, fed fp32 frames made here.
     bool conv = false;
     for (int i = 0; i < S; i++) conv = conv || needs_conversion(jobs[i].in, opt);
-    int nch = 0;
     for (int i = 0; i < S; i++)
-        if ((loaded && conv && !job_calls(jobs[i], files[2 * i], opt, conv)) || !job_control(jobs[i], files[2 * i], opt, conv, &nch) ||
+        if ((loaded && conv && !job_calls(jobs[i], files[2 * i], opt, conv)) || !job_control(jobs[i], files[2 * i], opt, conv) ||
             (loaded && !conv && !job_calls(jobs[i], files[2 * i], opt, conv))) return 1;
     const int CH = 96;                                  // frames per batched call at most
     const size_t DRAIN = 32;                            // room for a file's drain frames (a reservoir never spans that many)
     // the files (the slots) spread over the node's GPUs in contiguous blocks (-Gn limits the count), one host thread per device
     hx_multi *b = nullptr;
-    std::vector<int> file_cfg(S, 0);                    // -slots: the menu entry of each file
-    if (loaded) {
-        std::vector<HX_E_CONTROL> ctl(S);
-        std::vector<HX_SOURCE> srcs(S);
-        for (int i = 0; i < S; i++) { ctl[i] = jobs[i].ctl; srcs[i] = jobs[i].src; }
-        b = conv ? hx_multi_create_src(opt.ngpus, nullptr, S, ctl.data(), 0, srcs.data(), 0, CH) : hx_multi_create(opt.ngpus, nullptr, S, ctl.data(), 0, CH);
-    } else {
-        // the menu: the distinct (control, source) pairs of all files; the slots start with the first files' entries
+    std::vector<int> file_cfg(S, 0);                    // the menu entry of each file
+    {
+        // the menu: the distinct (control, source) pairs of all files, mono and stereo ones together (a mixed batch); the
+        // slots start with the first files' entries - without -slots every file has its own
         std::vector<HX_E_CONTROL> ctl;
         std::vector<HX_SOURCE> srcs;
         for (int i = 0; i < S; i++) {
@@ -586,10 +580,10 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             if (k == ctl.size()) { ctl.push_back(jobs[i].ctl); srcs.push_back(jobs[i].src); }
             file_cfg[i] = (int) k;
         }
-        b = hx_multi_create_menu(opt.ngpus, nullptr, NS, ctl.data(), (int) ctl.size(), conv ? srcs.data() : nullptr, file_cfg.data(), CH);
+        b = hx_multi_create_mixed(opt.ngpus, nullptr, NS, ctl.data(), (int) ctl.size(), conv ? srcs.data() : nullptr, file_cfg.data(), CH);
     }
     if (!b) {
-        // (what cannot share a batch - channel counts, MPEG-1 with MPEG-2 rates, allocator generations: the first file that differs from files[0] in the rates)
+        // (what cannot share a batch - MPEG-1 with MPEG-2 rates, allocator generations: the first file that differs from files[0] in the rates)
         fprintf(stderr, "\n ENCODER INIT FAIL: %s", hx_last_error());
         for (int i = 1; i < S; i++)
             if ((jobs[i].in.ec_used.samprate < 32000) != (jobs[0].in.ec_used.samprate < 32000)) { fprintf(stderr, " (%s encodes at %d Hz, %s at %d Hz)", files[2 * i], jobs[i].in.ec_used.samprate, files[0], jobs[0].in.ec_used.samprate); break; }
@@ -604,10 +598,12 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     int next = NS, rc = 0;
     for (int s = 0; s < NS; s++) {
         held[s] = s;
-        if (!loaded && (!load_input(files[2 * s], opt, &jobs[s].in, false) || !job_control(jobs[s], files[2 * s], opt, conv, &nch) || !job_calls(jobs[s], files[2 * s], opt, conv))) { hx_multi_destroy(b); return 1; }
+        if (!loaded && (!load_input(files[2 * s], opt, &jobs[s].in, false) || !job_control(jobs[s], files[2 * s], opt, conv) || !job_calls(jobs[s], files[2 * s], opt, conv))) { hx_multi_destroy(b); return 1; }
     }
     const long long stride = hx_multi_out_stride(b, CH);
-    std::vector<float> pcm(conv ? 0 : (size_t) NS * CH * 1152 * nch), tmp(2304);
+    // the plain route's rows are pitched for the widest file's channels; a mono file's frames sit contiguous at its row's start
+    const int pitch = hx_batch_pcm_channels(hx_multi_batch(b, 0));
+    std::vector<float> pcm(conv ? 0 : (size_t) NS * CH * 1152 * pitch), tmp(2304);
     const std::vector<unsigned char> zero_frame(2304 * 4, 0);
     // converting route: a row holds the file's bytes from its next call on, enough for CH calls of any file, then a region of
     // zero bytes that every drain call reads, as the single-file loop hands one zero buffer to all of them
@@ -654,7 +650,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
                 // 8-bit unsigned input where a zero byte is full-scale negative
                 if (p0 + k < j.nc) frame_to_float(j.in, j.in.data.data() + (p0 + k) * j.in.frame_in, tmp.data());
                 else frame_to_float(j.in, zero_frame.data(), tmp.data());
-                memcpy(&pcm[((size_t) s * nf + k) * 1152 * nch], tmp.data(), sizeof(float) * 1152 * nch);
+                memcpy(&pcm[((size_t) s * nf * pitch + (size_t) k * j.nch) * 1152], tmp.data(), sizeof(float) * 1152 * j.nch);
             }
         }
         for (int s = 0; s < NS && conv; s++) {
@@ -696,7 +692,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             held[s] = -1;
             if (next == S) continue;
             const int i = next++;
-            if (!load_input(files[2 * i], opt, &jobs[i].in, false) || !job_control(jobs[i], files[2 * i], opt, conv, &nch) || !job_calls(jobs[i], files[2 * i], opt, conv)) { hx_multi_destroy(b); return 1; }
+            if (!load_input(files[2 * i], opt, &jobs[i].in, false) || !job_control(jobs[i], files[2 * i], opt, conv) || !job_calls(jobs[i], files[2 * i], opt, conv)) { hx_multi_destroy(b); return 1; }
             held[s] = i;
             take_slot.push_back(s); take_cfg.push_back(file_cfg[i]); take_open.push_back(job_ledger(jobs[i], opt));
             hx_ledger_open(&jobs[i].led, take_open.back().ncalls, 1, take_open.back().head_bytes, take_open.back().flags);

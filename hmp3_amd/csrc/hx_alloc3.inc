@@ -835,8 +835,10 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
         ss->main_bytes = fs.main_bytes; ss->main_p0 = 0; ss->main_p1 = opos - done;
         ss->side_p0 = side_p0; ss->side_p1 = side_p1;
         ss->tot_frames_out = fs.tot_frames_out; ss->tot_bytes_out = fs.tot_bytes_out; ss->ave_tot_bytes_out = fs.ave_tot;
+        // (a mono stream has no second channel: bitallo_short's side information of it is formed from LDS no one wrote, and the
+        // stream state - the checkpoint blob - keeps the zeros it started with)
         for (int g = 0; g < 2; g++) for (int c = 0; c < 2; c++) for (int k = 0; k < 3; k++)
-            ss->gr_subblock_gain[g][c][k] = L.gr[g][c].subblock_gain[k];
+            ss->gr_subblock_gain[g][c][k] = c < L.P.nchan ? L.gr[g][c].subblock_gain[k] : 0;
         COLD(out_bytes)[s] = done;
         COLD(carry_len)[s] = opos - done;
         if (L.nstrict) atomicAdd(COLD(done_counter) + HX_CNT_STRICT_SUMS, L.nstrict);

@@ -114,17 +114,6 @@ hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nme
         if (src_menu(ec, src, nmenu, names, ecs, plans, menu_plan) != 0) return nullptr;
         ec = ecs.data();
     }
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return nullptr; }
-    if (device < 0 || device >= ndev) { set_err("device index out of range"); return nullptr; }
-    {   // written for gfx950 (MI355X) only: the code object holds no other target
-        hipDeviceProp_t prop;
-        HIPCHKN(hipGetDeviceProperties(&prop, device));
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return nullptr; }
-    }
-    // the launch bookkeeping (streams x granules x 9 energies per channel) is 32-bit
-    if ((long long) nstreams * max_frames > 32LL * 1024 * 1024) { set_err("nstreams * max_frames exceeds 32 Mi frames per call: split the batch"); return nullptr; }
-    HIPCHKN(hipSetDevice(device));
     hx_batch *b = new hx_batch;
     b->device = device; b->S = nstreams; b->maxF = max_frames;
     b->cls_of.resize(nstreams);
@@ -150,16 +139,40 @@ hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nme
             if (p.filter_dc) b->any_dc = true;
             if (b->params.empty()) { b->nchan = p.nchan; b->lsf = p.h_id ? 0 : 1; b->alloc1 = p.alloc1; }
             else if (p.alloc1 != b->alloc1) REFUSE_ENTRY("intensity-stereo / dual-channel streams (first-generation allocator) cannot share a batch with the others");
-            else if (p.nchan != b->nchan) REFUSE_ENTRY("mono and stereo streams cannot share a batch (the PCM layout differs)");
+            else if (p.nchan != b->nchan && !names.mixed) REFUSE_ENTRY("mono and stereo streams cannot share a batch (the PCM layout differs)");
             else if ((p.h_id ? 0 : 1) != b->lsf) REFUSE_ENTRY("MPEG-1 and MPEG-2 sample rates cannot share a batch (frames per call differ)");
-#undef REFUSE_ENTRY
+            if (p.nchan > b->nchan) b->nchan = p.nchan;         // (a mixed menu: the rows are pitched for its widest entry)
             seen.push_back(*c);
             b->params.push_back(p);
             k = (int) seen.size() - 1;
         }
         b->menu_cls[j] = k;
+        // (what src_encode_control derived and what the plan was made for are one decision: a difference is this library's error)
+        if (src && plans[menu_plan[j]].nch != b->params[k].nchan) {
+            const std::string pre = entry_prefix(names.cls_label, names.origin, j);
+            REFUSE_ENTRY("a converter's output channels differ from its encode control's");
+        }
     }
+#undef REFUSE_ENTRY
     for (int s = 0; s < nstreams; s++) { b->cfg_of[s] = cfg ? cfg[s] : 0; b->cls_of[s] = b->menu_cls[b->cfg_of[s]]; }
+    // the device, once the menu stands (nothing of the batch is on it yet: a refusal here only drops the host record)
+#define REFUSE_DEVICE(...) do { set_err(__VA_ARGS__); delete b; return nullptr; } while (0)
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) REFUSE_DEVICE("no HIP device available: the encoder has no CPU fallback");
+    if (device < 0 || device >= ndev) REFUSE_DEVICE("device index out of range");
+    {   // written for gfx950 (MI355X) only: the code object holds no other target
+        hipDeviceProp_t prop;
+        const hipError_t e = hipGetDeviceProperties(&prop, device);
+        if (e != hipSuccess) REFUSE_DEVICE("HIP error: %s", hipGetErrorString(e));
+        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) REFUSE_DEVICE("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName);
+    }
+    // the launch bookkeeping (streams x granules x 9 energies per channel) is 32-bit
+    if ((long long) nstreams * max_frames > 32LL * 1024 * 1024) REFUSE_DEVICE("nstreams * max_frames exceeds 32 Mi frames per call: split the batch");
+    {
+        const hipError_t e = hipSetDevice(device);
+        if (e != hipSuccess) REFUSE_DEVICE("HIP error: %s", hipGetErrorString(e));
+    }
+#undef REFUSE_DEVICE
     b->ncls = (int) b->params.size();
     const long long S = nstreams, NG = 2LL * max_frames;
     std::vector<HxGlobalTabs> gt_host(1);       // (144 KB: not on the stack)
@@ -242,6 +255,14 @@ extern "C" hx_batch *hx_batch_create(int device, int nstreams, const HX_E_CONTRO
     }
     return batch_create(device, nstreams, menu.data(), (int) menu.size(), nullptr, cfg.data(), max_frames, MenuNames{nullptr, nullptr, nullptr});
 }
+
+// ... whose entries may differ in channel count
+extern "C" hx_batch *hx_batch_create_mixed(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg, int max_frames)
+{
+    return batch_create(device, nstreams, ec, nmenu, src, cfg, max_frames, MenuNames{"menu entry", "menu entry", nullptr, true});
+}
+extern "C" int hx_batch_pcm_channels(const hx_batch *b) { return b ? b->nchan : 0; }
+extern "C" int hx_batch_stream_channels(const hx_batch *b, int i) { return (b && i >= 0 && i < b->S) ? b->params[b->cls_of[i]].nchan : -1; }
 
 extern "C" int hx_batch_nconfigs(const hx_batch *b) { return b ? (int) b->menu_cls.size() : 0; }
 extern "C" int hx_batch_stream_config(const hx_batch *b, int i) { return (b && i >= 0 && i < b->S) ? b->cfg_of[i] : -1; }

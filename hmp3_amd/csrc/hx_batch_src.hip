@@ -41,10 +41,10 @@ int src_setup(hx_batch *b, const std::vector<HxSrcPlan> &plans)
     for (int s = 0; s < nstreams; s++) b->src_cls[s] = b->menu_plan[b->cfg_of[s]];
     b->src_calls.assign(nstreams, 0);
     // LDS of a workgroup: the input window (source channels, interleaved), the intermediate samples (output channels,
-    // case 4) and the filter bank (cases 2 - 4), each sized for the batch's largest plan
+    // case 4) and the filter bank (cases 2 - 4), each sized for the batch's largest plan (batch_create has held every
+    // entry's plan against its own encode control's channel count)
     int xf = 0, zf = 0, cf = 0;
     for (const HxSrcPlan &p : plans) {
-        if (p.nch != b->nchan) { set_err("a converter's output channels differ from the batch's"); return -1; }
         if (p.xwin > b->src_xwin) b->src_xwin = p.xwin;
         if (p.zwin > b->src_zwin) b->src_zwin = p.zwin;
         xf = std::max(xf, p.channels * p.xwin);

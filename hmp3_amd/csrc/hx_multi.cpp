@@ -110,7 +110,7 @@ struct hx_multi {
     std::vector<int> first, count, device;
     std::vector<cpu_set_t> cpus;        // per device: the CPUs of its NUMA node this process may use (resolved once, at creation)
     std::vector<int> ncpus;             // ... and how many (0: unknown, the device's thread stays where it is)
-    int S = 0, nchan = 2;
+    int S = 0, nchan = 2;               // nchan: the pitch of the PCM rows (hx_batch::nchan), the same for every block
 };
 
 extern "C" void hx_multi_destroy(hx_multi *m)
@@ -173,6 +173,16 @@ extern "C" hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstr
     if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
     return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
         return hx_batch_create_menu(dev, count, ec, nmenu, src, cfg ? cfg + first : nullptr, max_frames);
+    });
+}
+
+// ... entries of either channel count: every block's rows are pitched for the menu's widest entry, so the blocks agree
+extern "C" hx_multi *hx_multi_create_mixed(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                                           const int *cfg, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create_mixed(dev, count, ec, nmenu, src, cfg ? cfg + first : nullptr, max_frames);
     });
 }
 

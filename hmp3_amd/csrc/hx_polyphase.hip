@@ -61,9 +61,11 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
                                                    const HxParams *__restrict__ prm,
                                                    const HxGlobalTabs *__restrict__ gt,
                                                    float *__restrict__ sb, int NG, int SG,
-                                                   const float *__restrict__ pcmf, int nchan, int *__restrict__ eng, int lsf,
+                                                   const float *__restrict__ pcmf, int pitch, int *__restrict__ eng, int lsf,
                                                    const int *__restrict__ nfr)
 {
+    // pitch: the channels every PCM row is laid out for (hx_batch_pcm_channels); nchan below: the stream's own, which in a
+    // mixed batch may be 1 under a pitch of 2 - its samples then sit contiguous at the start of its row
     __shared__ __attribute__((aligned(16))) v2f xs[K1_LDS];
     const int s = blockIdx.x, lt = threadIdx.x;
     const int g0 = blockIdx.y * K1_GPB;
@@ -75,7 +77,8 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
     const int count = 480 + 576 * ng;
     const HxStream *ss = st + s;
     const HxParams *p = prm + __builtin_amdgcn_readfirstlane(ss->cls);
-    const int16_t *src = pcm + (long long) s * nsamp * nchan;   // interleaved L R (or one channel)
+    const int nchan = p->nchan;                                 // (a scalar load: cls is wave-uniform)
+    const int16_t *src = pcm + (long long) s * nsamp * pitch;   // interleaved L R (or one channel)
     if (blockIdx.y == 0 && lt < 18) {
         // The detector energies of eng index 0 (this kernel's epilogue writes the others): from the carried last granule of the
         // previous call, subband slot 2, which no workgroup of this launch writes.  (A kernel of its own until round 6: eighteen
@@ -92,12 +95,12 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
     }
     const long long n0 = 576LL * g0 - 480;                      // sample index of staged slot 0
     const int hist = (g0 == 0) ? 480 : 0;                       // slots that come from the carry
-    if (nchan == 1) {       // mono batch: the right half of every pair is silence
-        const float *srcf = pcmf + (long long) s * nsamp;
+    if (nchan == 1) {       // mono stream: the right half of every pair is silence
+        const float *srcf = pcmf + (long long) s * nsamp * pitch;
         for (int idx = hist + lt; idx < count; idx += K1_THREADS)
             xs[idx + (idx >> 5)] = v2f{pcmf ? srcf[n0 + idx] : (float) src[n0 + idx], 0.0f};
     } else if (pcmf) {      // DC-blocked input from k_dcfilter: fp32, interleaved like the PCM
-        const v2f *srcf = reinterpret_cast<const v2f *>(pcmf) + (long long) s * nsamp;
+        const v2f *srcf = reinterpret_cast<const v2f *>(pcmf) + (long long) s * nsamp;       // (a stereo stream: pitch = 2)
         for (int idx = hist + lt; idx < count; idx += K1_THREADS) xs[idx + (idx >> 5)] = srcf[n0 + idx];
     } else if ((reinterpret_cast<unsigned long long>(pcm) & 15ull) == 0) {
         const int nv = count >> 2, vh = hist >> 2;              // 4 stereo samples per 16 bytes
@@ -190,6 +193,12 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
         float *out1 = out + (long long) SG * 576;
 #pragma unroll
         for (int k = 0; k < 32; k++) out1[18 * k] = X[k].y;
+    } else if (pitch == 2) {
+        // A mono stream of a mixed batch: its slot may have run a stereo stream before (hx_batch_assign_streams), whose
+        // channel-1 rows k_spec and k_msscan's carry would read again.  Zeros, as a mono batch's rows hold from create on.
+        float *out1 = out + (long long) SG * 576;
+#pragma unroll
+        for (int k = 0; k < 32; k++) out1[18 * k] = 0.0f;
     }
     {   // transient detector input (reference detect.c:147-196): energy of subbands 4..17 (MPEG-2 LSF rates: 8..27) per pair
         // of time slots, as mB: slots 2 k (this lane) and 2 k + 1 (the next lane), subband after subband, in the reference's
@@ -315,18 +324,21 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
 // evaluated in the reference's order, so it is sequential per channel: one lane per
 // (stream, channel) walks its samples; streams without the filter are converted to float only.
 __global__ void k_dcfilter(const int16_t *__restrict__ pcm, const float *__restrict__ pcm32, long long nsamp,
-                           HxStream *__restrict__ st, const HxParams *__restrict__ prm, float *__restrict__ pcmf, int S, int nchan,
+                           HxStream *__restrict__ st, const HxParams *__restrict__ prm, float *__restrict__ pcmf, int S, int pitch,
                            const int *__restrict__ nfr)
 {
+    // one lane per (stream, channel of the pitch): a lane whose channel its stream does not have leaves
     const int u = blockIdx.x * blockDim.x + threadIdx.x;
-    if (u >= nchan * S) return;
-    const int s = u / nchan, ch = u - s * nchan;
+    if (u >= pitch * S) return;
+    const int s = u / pitch, ch = u - s * pitch;
     const long long nown = nfr ? 1152LL * nfr[s] : nsamp;      // the stream's samples of this call (nsamp: the row stride)
     HxStream *ss = st + s;
     const HxParams *p = prm + ss->cls;
-    const int16_t *src = pcm + (long long) s * nsamp * nchan + ch;
-    const float *srcf = pcm32 + (long long) s * nsamp * nchan + ch;
-    float *dst = pcmf + (long long) s * nsamp * nchan + ch;
+    const int nchan = p->nchan;                                 // the stream's own: the stride inside its row
+    if (ch >= nchan) return;
+    const int16_t *src = pcm + (long long) s * nsamp * pitch + ch;
+    const float *srcf = pcm32 + (long long) s * nsamp * pitch + ch;
+    float *dst = pcmf + (long long) s * nsamp * pitch + ch;
     if (!p->filter_dc) {
         for (long long n = 0; n < nown; n++) dst[nchan * n] = pcm32 ? srcf[nchan * n] : (float) src[nchan * n];
         return;

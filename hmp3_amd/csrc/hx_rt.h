@@ -32,9 +32,11 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 // nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
 // frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
 // by 2 * nfr[s] granules; NG, nsamp and frames_per_stream stay the strides of the rows.
+// pitch (the kernels that read PCM): the channels every PCM row is laid out for, hx_batch::nchan; a stream's own channel
+// count comes from its class (HxParams::nchan) or its plan (HxSrcPlan::nch).
 __global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
-                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int nchan, int *eng, int lsf, const int *nfr);
-__global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int nchan, const int *nfr);
+                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int pitch, int *eng, int lsf, const int *nfr);
+__global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int pitch, const int *nfr);
 __global__ void k_src(SrcArgs a);
 __global__ void k_detect(HxStream *st, const HxParams *prm, const int *eng, unsigned char *flg, int *dbg_metric, unsigned char *bt,
                          unsigned char *btprev, int NG, int S, int lsf, const int *nfr);
@@ -43,7 +45,7 @@ __global__ void k_spec(const float *sb, const HxStream *st, const HxParams *prm,
 __global__ void k_spec_direct(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
                               float *xr, float *etab, float *thr, int *msbase, int NG, int SG, const int *nfr);
 __global__ void k_msscan(HxStream *st, const HxParams *prm, const int *msbase, const unsigned char *bt, unsigned char *msflag, int *msdec,
-                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int nchan, const int *nfr);
+                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int pitch, const int *nfr);
 __global__ void k_prep(const float *xr, float *xmag_dbg, float *x34o, unsigned *sgn, HxBandPrep *band, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt,
                        const unsigned char *bt, const unsigned char *msflag, const float *etab, const float *thr, const float *thrprev, int NG, long long nunits, const int *nfr);
 __global__ void k_pack(const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const short *ixq, const unsigned *sgn, const HxSegOut *seg,
@@ -149,7 +151,8 @@ struct hx_batch {
     OptOut opt;                         // the caller's optional outputs: what the three setters leave, and what a call made now takes (call_on)
     float *d_pcmf = nullptr;            // DC-blocked input, only when a stream uses filter_select = 1
     bool any_dc = false;
-    int nchan = 2;                      // channels of the PCM input, the same for every stream of the batch
+    int nchan = 2;                      // P, the pitch: channels every PCM row (the caller's, d_pcmf, d_src_pcm) is laid out for = the largest
+                                        // over the menu.  A stream's own count is its class's (params[cls].nchan): they differ in a mixed batch only
     int lsf = 0;                        // 1: an MPEG-2 LSF batch (16 / 22.05 / 24 kHz): every 1152-sample block yields two frames
     int slim = 0;                       // 1: the low-footprint stream walk k_alloc_slim (six streams per CU instead of four), chosen at create
     int alloc1 = 0;                     // 1: streams of the first-generation allocator (intensity stereo, dual channel): k_alloc1*
@@ -175,7 +178,7 @@ struct hx_batch {
     long long *d_src_calls = nullptr;   // [2][S]: k_src reads copy src_par and writes the other
     float *d_src_carry = nullptr;       // [2][S][2][HX_SRC_CARRY] the same for the case-4 intermediate samples
     int src_par = 0;
-    float *d_src_pcm = nullptr;         // [S][nframes * 1152][nchan] the last call's converted PCM
+    float *d_src_pcm = nullptr;         // [S][nframes * 1152 * nchan] the last call's converted PCM, laid out like a plain call's
     long long *d_src_off = nullptr, *h_src_off = nullptr;      // [S][max_frames] the caller's frame offsets (device / page-locked)
     hipEvent_t ev_src_off = nullptr;    // the last upload of h_src_off is done
     int src_xwin = 0, src_zwin = 0, src_zoff = 0, src_coff = 0, src_lastF = 0;
@@ -383,8 +386,8 @@ HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out,
 // The one create path (hx_batch.hip).  ec[nmenu] (and src[nmenu]: a converting batch) is the menu, cfg[nstreams] or null
 // (= entry 0) the entry each slot starts with.  A refusal names the entry as "<label> <origin[j]>: " - src_label for what
 // the converter rejects, cls_label for what the encoder's init or the batch's kind rejects; a null label: no prefix; a null
-// origin: the entry's own number.
-struct MenuNames { const char *src_label, *cls_label; const int *origin; };
+// origin: the entry's own number.  mixed: entries may differ in channel count (hx_batch_create_mixed).
+struct MenuNames { const char *src_label, *cls_label; const int *origin; bool mixed = false; };
 HX_LOCAL hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg,
                                 int max_frames, const MenuNames &names);
 // ... its converter parts (hx_batch_src.hip): every entry's encode control and plan (plans deduplicated), before anything

@@ -518,10 +518,11 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
                                                const unsigned char *__restrict__ bt, unsigned char *__restrict__ msflag, int *__restrict__ msdec,
                                                const float *__restrict__ thr, float *__restrict__ thrprev, int NG, int lsf,
                                                float *__restrict__ sb, int SG, const int16_t *__restrict__ pcm, long long nsamp,
-                                               const float *__restrict__ pcmf, int nchan, const int *__restrict__ nfr)
+                                               const float *__restrict__ pcmf, int pitch, const int *__restrict__ nfr)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     HxStream *ss = st + s;
+    const int nchan = prm[ss->cls].nchan;       // the stream's own channels; pitch: those its PCM row is laid out for
     const long long g0 = (long long) s * NG;
     // The stream's granules of this call (hx_batch_frame_counts): the bound of the scan, and where the hand-overs to the next
     // call come from - the pre-echo memory from granule NGs - 1, the subband carry from slots NGs .. NGs + 2, the PCM history
@@ -587,11 +588,11 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
         float *base = sb + (long long) (s * 2 + ch) * SG * 576;
         for (int e = lane; e < 576; e += 64)
             for (int k = 0; k < 3; k++) base[k * 576 + e] = base[(NGs + k) * 576 + e];
-        const int16_t *src = pcm + (long long) s * nsamp * nchan + ch;
+        const int16_t *src = pcm + (long long) s * nsamp * pitch + ch;
         for (int i = lane; i < 480 && ch < nchan; i += 64) {
             const long long n = nown - 480 + i;
             // fewer than 480 new samples never happens (a frame is 1152), so all come from this batch
-            ss->pcm_hist[ch][i] = pcmf ? pcmf[((long long) s * nsamp + n) * nchan + ch] : (float) src[nchan * n];
+            ss->pcm_hist[ch][i] = pcmf ? pcmf[(long long) s * nsamp * pitch + n * nchan + ch] : (float) src[nchan * n];
         }
     }
     if (lane == 0) ss->frames_in += NGs / 2;

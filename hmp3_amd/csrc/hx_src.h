@@ -47,7 +47,7 @@ struct SrcArgs {
     long long *calls_out;
     const float *carry_in;              // [S][2][HX_SRC_CARRY] case 4: the last intermediate samples formed, per channel
     float *carry_out;
-    float *out;                         // [S][nframes * 1152][nch] fp32 at int16 scale
+    float *out;                         // [S][nframes * 1152 * nch] fp32 at int16 scale: a stream of plan->nch < nch channels fills the start of its row
     const int *nfr;                     // [S] the calls each stream makes of the launch's nframes, or null: all of them
     int nframes, nch, xwin, zwin;       // xwin / zwin: sample frames of the input / intermediate samples per call, at most
     int zoff, coff;                     // LDS floats before the intermediate samples / before the filter bank

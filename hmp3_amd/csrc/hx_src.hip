@@ -99,7 +99,8 @@ __global__ __launch_bounds__(256) void k_src(SrcArgs a)
     for (int t = tid; t < nx; t += 256) xs[t] = src_sample(xin, t, bits, is_float, aligned);
     if (ncase >= 2) for (int t = tid; t < p->totcoef; t += 256) cl[t] = p->coef[t];
     __syncthreads();
-    float *y = a.out + ((long long) s * a.nframes + f) * 1152 * a.nch;
+    // (the row is pitched for a.nch channels, the stream's calls sit contiguous at its start: p->nch <= a.nch)
+    float *y = a.out + ((long long) s * a.nframes * a.nch + (long long) f * p->nch) * 1152;
     // phase of the call's first output: r0 = i0 m mod n, i0 mod n; output t of the call sits w(i0 + t) - w(i0) =
     // (r0 + t m) / n bank steps after it (32-bit from here: t m < 1152 n)
     const int r0 = (int) ((i0 * m) % n), ph0 = (int) (i0 % n);

@@ -217,14 +217,46 @@ int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *b
    The checkpoint blob of an assigned slot is a new batch's but for one word: the class index at the start of the stream
    record is the batch's own numbering of its menu's configurations, which a restore replaces with the receiving batch's.
    The command-line tool's -batch -slots<n> runs any number of files through n slots this way.
-   Not covered: entries added after create; mixed channel counts, MPEG-1 / MPEG-2 rates or allocator generations in one
-   batch; device blobs and pipelined submits of converting batches, as before. */
+   Not covered: entries added after create; MPEG-1 / MPEG-2 rates or allocator generations in one batch (channel counts:
+   hx_batch_create_mixed below); device blobs and pipelined submits of converting batches, as before. */
 hx_batch *hx_batch_create_menu(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
                                const int *cfg, int max_frames);
 int hx_batch_nconfigs(const hx_batch *b);
 int hx_batch_stream_config(const hx_batch *b, int i);      /* the entry slot i runs as of the calls made so far; -1 bad arguments */
 /* slot idx[e] starts a new stream of menu entry cfg[e]; idx, cfg: HOST arrays of n, copied by the call; asynchronous on `stream` */
 int hx_batch_assign_streams(hx_batch *b, const int *idx, const int *cfg, int n, void *stream);
+/* ---- mixed batches: mono and stereo streams share one batch and one menu (no reference equivalent) ----
+   hx_batch_create_mixed is hx_batch_create_menu word for word, except that its entries may differ in channel count: mode 3
+   (mono) beside the stereo modes; of a converting batch the converter's output channels, so a mono source, a stereo source and
+   a stereo source with mono_convert share a batch.  The three other create calls keep refusing that, with their messages.
+   Row pitch: P = hx_batch_pcm_channels = the largest channel count over the menu.  The PCM of every plain encode / submit call
+   (device and host buffers, s16 and f32, *_stats, *_crc, *_host_dense) is [nstreams][nframes * 1152 * P] samples.  A stream of
+   P channels fills its row interleaved, as in any batch.
+   A mono stream of a P = 2 batch: its nframes * 1152 samples sit contiguous at the start of its row (under per-stream frame
+   counts: the first n * 1152).  The rest of the row has no influence on any output or state and may be uninitialised.
+   A uniform menu: P is that channel count, and the batch is in every respect what hx_batch_create_menu returns for the same
+   arguments - same layout, same bytes, same kernel choice.
+   Sizing: everything create sizes from the configurations is taken over the whole menu as for any menu (hx_batch_out_stride,
+   the DC blocker's staging, hx_batch_src_in_stride, the converter's LDS layout, the choice of the stream-walk build); what is
+   sized by a channel count is sized by P.  A host-fed mono stream of a P = 2 batch therefore moves the unused half of its
+   row over the link with the rest.
+   hx_batch_assign_streams / hx_multi_assign_streams move a slot between a mono and a stereo entry under their contract above,
+   unchanged: from its next frame on the slot produces exactly the bytes of slot 0 of a new batch created with that entry -
+   rows, out_bytes, packets, frame counters, MusicCRC, dense image and checkpoint blob (but for the class index word).
+   Converting batches: the input rows are bytes and per stream already.  The converted PCM (the "srcpcm" tap) takes the
+   layout above: row pitch nframes * 1152 * P floats, a mono stream's frames contiguous at the row's start.
+   Checkpoint blobs are those of any batch and interchangeable with them: a mono stream saved from a mixed batch restores
+   into a uniform mono batch of the same control, and back (the fingerprint is per control and holds the channel count).
+   Still refused at create, with hx_batch_create's messages ("menu entry j: ..."): MPEG-1 with MPEG-2 rates, and the two
+   allocator generations - dual channel (mode 2) and intensity stereo stay apart from the others.
+   hx_batch_frames_bytes, the ledger (frames_per_call is the batch's MPEG version), hx_batch_nconfigs and
+   hx_batch_stream_config are what they are for any menu.
+   hx_multi_create_mixed: the same in blocks over several devices; every block gets the whole menu and so the same P, and the
+   caller's PCM is split between the blocks by P. */
+hx_batch *hx_batch_create_mixed(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                                const int *cfg, int max_frames);
+int hx_batch_pcm_channels(const hx_batch *b);              /* P: the channel count the PCM rows are pitched for = the largest over the menu */
+int hx_batch_stream_channels(const hx_batch *b, int i);    /* channels of the entry slot i runs as of the calls made so far; -1 bad arguments */
 /* worst-case bytes one stream can emit in a call of nframes frames */
 long long hx_batch_out_stride(const hx_batch *b, int nframes);
 /* PCM: int16 interleaved L/R, [nstreams][nframes*1152][2]; out: [nstreams][out_stride] bytes;
@@ -601,6 +633,9 @@ hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstreams, const
                                const HX_SOURCE *src, const int *cfg, int max_frames);
 /* the same over all blocks (idx counts streams over all blocks); synchronous like the other hx_multi calls; all blocks or (-1) none */
 int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *cfg, int n);
+/* hx_batch_create_mixed in blocks over several devices ("mixed batches" above) */
+hx_multi *hx_multi_create_mixed(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu,
+                                const HX_SOURCE *src, const int *cfg, int max_frames);
 /* hx_batch_ledger_begin / hx_batch_ledger_read over all blocks (idx counts streams over all blocks); synchronous; all blocks or (-1) none */
 int hx_multi_ledger_begin(hx_multi *m, const int *idx, const HX_LEDGER_OPEN *open, int n);
 int hx_multi_ledger_read(hx_multi *m, const int *idx, int n, HX_LEDGER *out);
