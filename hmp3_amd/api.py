@@ -340,6 +340,13 @@ class Batch:
         return cls._from_menu("hx_batch_create_mixed", controls, nstreams, cfg, max_frames, device, sources)
 
     @classmethod
+    def any(cls, controls, nstreams, cfg=None, max_frames=256, device=0, sources=None):
+        """Batch.mixed whose entries may also differ in MPEG version and allocator generation (hx_batch_create_any): MPEG-1
+        and MPEG-2 rates, dual channel and intensity stereo beside the others; stream_frames_per_block says how many frames a
+        slot makes of a 1152-sample block"""
+        return cls._from_menu("hx_batch_create_any", controls, nstreams, cfg, max_frames, device, sources)
+
+    @classmethod
     def _from_menu(cls, create, controls, nstreams, cfg, max_frames, device, sources):
         self = cls.__new__(cls)
         self.n = int(nstreams)
@@ -357,6 +364,13 @@ class Batch:
     def stream_channels(self, i):
         """channels of the entry slot i runs, as of the calls made so far"""
         k = int(lib().hx_batch_stream_channels(self.h, int(i)))
+        if k < 0:
+            raise IndexError(i)
+        return k
+
+    def stream_frames_per_block(self, i):
+        """frames per 1152-sample block (1, or 2 at the MPEG-2 rates) of the entry slot i runs, as of the calls made so far"""
+        k = int(lib().hx_batch_stream_frames_per_block(self.h, int(i)))
         if k < 0:
             raise IndexError(i)
         return k
@@ -663,6 +677,11 @@ class SrcBatch(Batch):
         """SrcBatch.menu whose entries may differ in the converter's output channels (hx_batch_create_mixed)"""
         return super().mixed(controls, nstreams, cfg=cfg, max_frames=max_frames, device=device, sources=sources)
 
+    @classmethod
+    def any(cls, controls, sources, nstreams, cfg=None, max_frames=256, device=0):
+        """SrcBatch.mixed whose entries may also differ in the encoder's MPEG version and allocator generation (hx_batch_create_any)"""
+        return super().any(controls, nstreams, cfg=cfg, max_frames=max_frames, device=device, sources=sources)
+
     def schedule(self, i, nframes):
         """(bytes each of stream i's next nframes calls consumes, bytes they read)"""
         nb = np.zeros(nframes, dtype=np.int64)
@@ -752,6 +771,11 @@ class Multi:
         return cls._from_menu("hx_multi_create_mixed", controls, nstreams, cfg, max_frames, ndev, devices, sources)
 
     @classmethod
+    def any(cls, controls, nstreams, cfg=None, max_frames=256, ndev=0, devices=None, sources=None):
+        """as Batch.any, in blocks over several devices (hx_multi_create_any)"""
+        return cls._from_menu("hx_multi_create_any", controls, nstreams, cfg, max_frames, ndev, devices, sources)
+
+    @classmethod
     def _from_menu(cls, create, controls, nstreams, cfg, max_frames, ndev, devices, sources):
         self = cls.__new__(cls)
         dv = (C.c_int * len(devices))(*devices) if devices else None
@@ -774,6 +798,14 @@ class Multi:
             _, first, count = self.shard(k)
             if first <= i < first + count:
                 return int(lib().hx_batch_stream_channels(self.batch(k), int(i) - first))
+        raise IndexError(i)
+
+    def stream_frames_per_block(self, i):
+        """frames per 1152-sample block of the entry stream i (counted over all blocks) runs"""
+        for k in range(self.ndevices()):
+            _, first, count = self.shard(k)
+            if first <= i < first + count:
+                return int(lib().hx_batch_stream_frames_per_block(self.batch(k), int(i) - first))
         raise IndexError(i)
 
     def batch(self, k):
@@ -891,6 +923,11 @@ class SrcMulti(Multi):
     def mixed(cls, controls, sources, nstreams, cfg=None, max_frames=256, ndev=0, devices=None):
         """as SrcBatch.mixed, in blocks over several devices"""
         return super().mixed(controls, nstreams, cfg=cfg, max_frames=max_frames, ndev=ndev, devices=devices, sources=sources)
+
+    @classmethod
+    def any(cls, controls, sources, nstreams, cfg=None, max_frames=256, ndev=0, devices=None):
+        """as SrcBatch.any, in blocks over several devices"""
+        return super().any(controls, nstreams, cfg=cfg, max_frames=max_frames, ndev=ndev, devices=devices, sources=sources)
 
     def in_stride(self, nframes):
         return int(lib().hx_multi_src_in_stride(self.h, nframes))

@@ -1,9 +1,9 @@
 // hmp3amd - file front end over libhmp3amd.
 //   hmp3amd <input.wav|-> <output.mp3|-> [flags]                 one file: a bounded regular file as a batch of one, a pipe or
 //                                                                 a very large file frame by frame (hx_enc_* API)
-//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API), mono and stereo together
-//                                                                 (hx_multi_create_mixed); files at any rate and -A go through
-//                                                                 a converting batch
+//   hmp3amd -batch in1.wav out1.mp3 in2.wav out2.mp3 ... [flags]  many files at once (hx_multi_* API): mono and stereo, MPEG-1
+//                                                                 and MPEG-2 rates, any stereo mode together (hx_multi_create_any);
+//                                                                 files at any rate and -A go through a converting batch
 //   ... -slots<n>                                                 the files of -batch through n slots of one batch: a file is
 //                                                                 read when a slot is free and written when its drain ends
 // Same flags, encode loop and output files as the reference CLI (reference
@@ -12,7 +12,7 @@
 // completed in place.  Accepted: RIFF/WAVE, mono or stereo, 8/16/24/32-bit PCM or 32-bit float,
 // 8 - 48 kHz (rates other than 16 / 22.05 / 24 / 32 / 44.1 / 48 kHz, or -A, go through the sample-rate
 // converter first, as in the reference); everything else fails like an unsupported file.
-// Batch mode encodes all files as one batch of streams (either channel count, one MPEG version, same flags) and
+// Batch mode encodes all files as one batch of streams (either channel count, either MPEG version, same flags) and
 // reproduces per file exactly what the single-file loop writes.  Containers: RIFF, RIFX, RF64 / BW64, Wave64.
 #include <algorithm>
 #include <cstdint>
@@ -570,7 +570,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     hx_multi *b = nullptr;
     std::vector<int> file_cfg(S, 0);                    // the menu entry of each file
     {
-        // the menu: the distinct (control, source) pairs of all files, mono and stereo ones together (a mixed batch); the
+        // the menu: the distinct (control, source) pairs of all files, of whatever channel count, rate and stereo mode; the
         // slots start with the first files' entries - without -slots every file has its own
         std::vector<HX_E_CONTROL> ctl;
         std::vector<HX_SOURCE> srcs;
@@ -580,14 +580,10 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             if (k == ctl.size()) { ctl.push_back(jobs[i].ctl); srcs.push_back(jobs[i].src); }
             file_cfg[i] = (int) k;
         }
-        b = hx_multi_create_mixed(opt.ngpus, nullptr, NS, ctl.data(), (int) ctl.size(), conv ? srcs.data() : nullptr, file_cfg.data(), CH);
+        b = hx_multi_create_any(opt.ngpus, nullptr, NS, ctl.data(), (int) ctl.size(), conv ? srcs.data() : nullptr, file_cfg.data(), CH);
     }
     if (!b) {
-        // (what cannot share a batch - MPEG-1 with MPEG-2 rates, allocator generations: the first file that differs from files[0] in the rates)
-        fprintf(stderr, "\n ENCODER INIT FAIL: %s", hx_last_error());
-        for (int i = 1; i < S; i++)
-            if ((jobs[i].in.ec_used.samprate < 32000) != (jobs[0].in.ec_used.samprate < 32000)) { fprintf(stderr, " (%s encodes at %d Hz, %s at %d Hz)", files[2 * i], jobs[i].in.ec_used.samprate, files[0], jobs[0].in.ec_used.samprate); break; }
-        fprintf(stderr, "\n");
+        fprintf(stderr, "\n ENCODER INIT FAIL: %s\n", hx_last_error());
         return 1;
     }
     if (!loaded) fprintf(stderr, "\n %d files through %d slots on %d GPU(s)", S, NS, hx_multi_ndevices(b));

@@ -145,7 +145,7 @@ __device__ __forceinline__ void outbox_store(AllocLds &L, const AllocArgs &a, in
         Outbox &ob = L.ob[g & 1];
         if (LSF) build_side_lsf(L, &L.P, g & 1, ob.part, ob.mdb);
         else build_side(L, &L.P, ob.sidew, ob.gr, ob.scfsi, ob.mdb);
-        const int fpc = LSF ? a.NG : a.NG / 2;      // frame records per stream: the stride
+        const int fpc = COLD(fpc);                  // frame records per stream: the stride (AllocArgs::fpc)
         unsigned char *o = a.out + (long long) s * a.out_stride + r.opos;
         const int k = max(LANE - 4, 0);
         const unsigned byte = (LANE < 4) ? ob.head[LANE] : ((ob.sidew[min(k >> 2, 9)] >> (24 - 8 * (k & 3))) & 255);
@@ -466,7 +466,7 @@ __device__ __forceinline__ void slots_init(const AllocArgs &a, AllocLds &L, int 
     HX_WAVE_SYNC();
     // every slot of this call, in order, for k_pack: the pending ones first, then one per new frame
     if (LANE == 0) {
-        HxSlot *slots = a.slots + (long long) s * ((LSF ? 2 : 1) * F + HX_SLOTS_EXTRA);
+        HxSlot *slots = a.slots + (long long) s * (COLD(fpc) + HX_SLOTS_EXTRA);
         int o = 0, j = 0;
         for (unsigned k = L.fs.side_p0; k != L.fs.side_p1; k = (k + 1) & 31, j++) {
             L.r_off[k] = o;
@@ -892,18 +892,19 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
     // The launch order is the streams that ran longest in the previous call first (longest-processing-time-first: the
     // launch's tail is made of short streams).
     // (HX_PERSIST: the low-footprint build only, see the top of hx_alloc.hip)
-    if (!HX_PERSIST && (int) blockIdx.x >= a.S) return;
+    // (the launch walks positions pos0 .. pos0 + npos - 1 of the batch-wide launch order: AllocArgs::pos0)
+    if (!HX_PERSIST && (int) blockIdx.x >= a.npos) return;
     if (WAVE == 1) { helper_serve<LSF>(a, L); return; }
 #if HX_PERSIST
   for (;;) {        // master wave: one stream of the launch order after the other
     HX_LANE_DECL;
     int idx = 0;
     if (LANE == 0) idx = atomicAdd(COLD(done_counter) + HX_CNT_CLAIMED, 1);
-    idx = __builtin_amdgcn_readfirstlane(idx);
-    if (idx >= a.S) break;
+    idx = a.pos0 + __builtin_amdgcn_readfirstlane(idx);
+    if (idx >= a.pos0 + a.npos) break;
 #else
   {                 // master wave: the stream at this workgroup's position of the launch order
-    const int idx = (int) blockIdx.x;
+    const int idx = a.pos0 + (int) blockIdx.x;
 #endif
     const int s = COLD(order) ? COLD(order)[idx] : idx;
     const long long t_start = wall_clock64();

@@ -138,12 +138,15 @@ hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nme
             }
             if (p.filter_dc) b->any_dc = true;
             if (b->params.empty()) { b->nchan = p.nchan; b->lsf = p.h_id ? 0 : 1; b->alloc1 = p.alloc1; }
+            else if (names.any) { if (!p.h_id) b->lsf = 1; }     // (any kind beside any other: hx_batch::kinds)
             else if (p.alloc1 != b->alloc1) REFUSE_ENTRY("intensity-stereo / dual-channel streams (first-generation allocator) cannot share a batch with the others");
             else if (p.nchan != b->nchan && !names.mixed) REFUSE_ENTRY("mono and stereo streams cannot share a batch (the PCM layout differs)");
             else if ((p.h_id ? 0 : 1) != b->lsf) REFUSE_ENTRY("MPEG-1 and MPEG-2 sample rates cannot share a batch (frames per call differ)");
             if (p.nchan > b->nchan) b->nchan = p.nchan;         // (a mixed menu: the rows are pitched for its widest entry)
             seen.push_back(*c);
             b->params.push_back(p);
+            b->cls_kind.push_back(2 * (p.alloc1 ? 1 : 0) + (p.h_id ? 0 : 1));
+            b->kinds |= 1u << b->cls_kind.back();
             k = (int) seen.size() - 1;
         }
         b->menu_cls[j] = k;
@@ -204,7 +207,11 @@ hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nme
         hipDeviceProp_t prop;
         int per_cu = 0;
         HIPCHKN(hipGetDeviceProperties(&prop, device));
-        const void *kern = b->alloc1 ? (b->lsf ? (const void *) k_alloc1_lsf : (const void *) k_alloc1) : (b->lsf ? (const void *) k_alloc_lsf : (const void *) k_alloc);
+        // (of a batch of several kinds: the resident set of its first kind's kernel - what the gates, the launch order's rule
+        // and the choice below count in; the kernels' footprints differ by little)
+        const void *const walk[4] = {(const void *) k_alloc, (const void *) k_alloc_lsf, (const void *) k_alloc1, (const void *) k_alloc1_lsf};
+        const bool kind0 = (b->kinds & 1u) != 0;
+        const void *kern = walk[__builtin_ctz(b->kinds)];
         if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kern, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 4;
         b->resident = per_cu * prop.multiProcessorCount;
         b->ncu = prop.multiProcessorCount;
@@ -212,12 +219,13 @@ hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nme
         // runs the one written for 256 registers and 38 KB of LDS per stream; a larger one runs k_alloc_slim, whose streams
         // take 168 registers and 26.5 KB, six to a CU: a stream is slower there, 1.5 x as many are in flight.
         // HMP3AMD_K6 = fat | slim overrides the choice (tests run every case on both).
-        bool slim_ok = !b->alloc1 && !b->lsf;
-        for (int k = 0; k < b->ncls && slim_ok; k++) slim_ok = hx_slim_tables_ok(&b->params[k], &gt) != 0;
+        // (the choice is the kind-0 streams': the other kinds have one kernel each)
+        bool slim_ok = kind0;
+        for (int k = 0; k < b->ncls && slim_ok; k++) if (b->cls_kind[k] == 0) slim_ok = hx_slim_tables_ok(&b->params[k], &gt) != 0;
         const char *e = getenv("HMP3AMD_K6");
         if (e && strcmp(e, "slim") != 0 && strcmp(e, "fat") != 0) { set_err("HMP3AMD_K6 must be 'fat' or 'slim'"); hx_batch_destroy(b); return nullptr; }
         const bool want = e ? (strcmp(e, "slim") == 0) : (S > b->resident);
-        if (e && strcmp(e, "slim") == 0 && !slim_ok && !b->alloc1 && !b->lsf) { set_err("HMP3AMD_K6=slim: the host's tables do not have the structure k_alloc_slim derives them from"); hx_batch_destroy(b); return nullptr; }
+        if (e && strcmp(e, "slim") == 0 && !slim_ok && kind0) { set_err("HMP3AMD_K6=slim: the host's tables do not have the structure k_alloc_slim derives them from"); hx_batch_destroy(b); return nullptr; }
         if (want && slim_ok) {
             b->slim = 1;
             if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void *) k_alloc_slim, 128, 0) != hipSuccess || per_cu <= 0) per_cu = 6;
@@ -261,7 +269,13 @@ extern "C" hx_batch *hx_batch_create_mixed(int device, int nstreams, const HX_E_
 {
     return batch_create(device, nstreams, ec, nmenu, src, cfg, max_frames, MenuNames{"menu entry", "menu entry", nullptr, true});
 }
+// ... and in MPEG version and allocator generation
+extern "C" hx_batch *hx_batch_create_any(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg, int max_frames)
+{
+    return batch_create(device, nstreams, ec, nmenu, src, cfg, max_frames, MenuNames{"menu entry", "menu entry", nullptr, true, true});
+}
 extern "C" int hx_batch_pcm_channels(const hx_batch *b) { return b ? b->nchan : 0; }
+extern "C" int hx_batch_stream_frames_per_block(const hx_batch *b, int i) { return (b && i >= 0 && i < b->S) ? frames_per_block(b->params[b->cls_of[i]]) : -1; }
 extern "C" int hx_batch_stream_channels(const hx_batch *b, int i) { return (b && i >= 0 && i < b->S) ? b->params[b->cls_of[i]].nchan : -1; }
 
 extern "C" int hx_batch_nconfigs(const hx_batch *b) { return b ? (int) b->menu_cls.size() : 0; }
@@ -274,12 +288,12 @@ extern "C" long long hx_batch_out_stride(const hx_batch *b, int nframes)
     if (!b) return 0;
     // nframes new frames plus the images of the frames still pending from earlier calls (their
     // free space is at most the 511-byte reservoir, so a handful of frames; 4 KB covers them)
-    int maxframe = 0;
+    // (over the menu's classes, each with its own frames per block: a menu of one MPEG version takes its largest frame)
+    long long n = 0;
     for (const HxParams &p : b->params) {
-        int fb = p.vbr_flag ? p.vbr_framebytes[p.ivbr_max] : p.framebytes + 1;
-        if (fb > maxframe) maxframe = fb;
+        const int fb = p.vbr_flag ? p.vbr_framebytes[p.ivbr_max] : p.framebytes + 1;
+        n = std::max(n, (long long) (frames_per_block(p) * nframes + 2) * fb + 4096);
     }
-    long long n = (long long) ((b->lsf ? 2 : 1) * nframes + 2) * maxframe + 4096;
     return (n + 255) & ~255LL;
 }
 
@@ -427,19 +441,19 @@ static int enqueue_pack(hx_batch *b, const Call &c, int nframes, int set, int ss
     const int S = b->S, NG = 2 * nframes;
     const WalkSet &w = b->walk[set];
     const unsigned *sgn = b->sgn[sset];
-    const int fps = (b->lsf ? 2 : 1) * nframes;
+    const int fps = (b->lsf ? 2 : 1) * nframes;      // frame positions per stream = the records' stride (AllocArgs::fpc)
     const long long total = (long long) S * fps;
     // a handful of frames in all (the one-stream encoder's calls): one workgroup does the three kernels' work (hx_pack.hip, solo)
     const int solo = (S <= 4 && total <= 8) ? S : 0;
     if (solo) {
         LAUNCH(k_pack, dim3(1), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-               c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, solo, b->d_st, w.pre_len, c.out_bytes, w.carry_len, c.rec_frames,
+               c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, total, solo, b->d_st, w.pre_len, c.out_bytes, w.carry_len, c.rec_frames,
                (solo == 1) ? c.rec_host : (unsigned char *) nullptr, b->d_done + HX_CNT_STARTED, c.nfr);
         return 0;
     }
     LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, w.pre_len);
     LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, b->lsf, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr, c.nfr);
+           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr, c.nfr);
     LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, c.out_bytes, w.carry_len, c.rec_frames);
     return 0;
 }
@@ -596,15 +610,15 @@ static int launch_front(hx_batch *b, const Pass &p)
     // (the detector energies of the carried granule are formed by k_polyphase's first tile of a stream, the carries rolled by
     // k_msscan, flags and block types by one kernel - round 6: three launches less per call, which is what a one-stream call
     // is made of)
-    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, b->lsf, nfr);
-    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, b->lsf, nfr);
+    LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, nfr);
+    LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, nfr);
     // (the form of K4 that goes with the stream-walk kernel: hx_spec.hip, spec_granule)
     if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
     else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
     // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
     // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
     // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
-    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->lsf, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan, nfr);
+    LAUNCH(k_msscan, dim3(S), dim3(64), q, b->d_st, b->d_prm, f.msbase, f.bt, f.msflag, f.msdec, f.thr, f.thrprev, NG, b->d_sb, SG, d_pcm, nsamp, pcmf, b->nchan, nfr);
     LAUNCH(k_prep, dim3((unsigned) (((long long) S * NG + 3) / 4)), dim3(256), q, f.xr, (b->debug && b->d_xrdbg) ? b->d_xrdbg : (float *) nullptr, b->debug ? f.x34 : (float *) nullptr,
            b->sgn[p.sset], f.band, b->d_st, b->d_prm, b->d_gt, f.bt, f.msflag, f.etab, f.thr, f.thrprev, NG, (long long) S * NG, nfr);
     return 0;
@@ -650,7 +664,11 @@ static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
     a.dur = b->d_dur;
     a.order = nullptr;
     a.park_k = 0;
-    if ((S > b->resident && b->lpt) || (b->lpt == 2 && S > b->ncu) || b->lpt == 3) {
+    a.pos0 = 0; a.npos = S; a.fpc = (b->lsf ? 2 : 1) * p.nframes;
+    if (several_kinds(b)) {     // the streams partitioned by kind, whatever the batch's size: launch_walk takes the spans
+        LAUNCH(k_order_kinds, dim3(1), dim3(1024), p.qa, (const unsigned *) b->d_dur, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, b->d_order, S);
+        a.order = b->d_order;
+    } else if ((S > b->resident && b->lpt) || (b->lpt == 2 && S > b->ncu) || b->lpt == 3) {
         LAUNCH(k_order, dim3(1), dim3(1024), p.qa, (const unsigned *) b->d_dur, b->d_order, S);
         a.order = b->d_order;
         // parking (hx_alloc3.inc): only when every stream has a slot from the launch's start - beyond the resident set a
@@ -678,11 +696,26 @@ static int launch_walk(hx_batch *b, const Pass &p, const AllocArgs &a)
     // persistent workgroups: as many as the chip holds at once (or one per stream if that is fewer); each walks one stream of
     // the launch order after the other (hx_alloc3.inc)
     // (built into k_alloc_slim, the kernel of batches beyond the resident set; the 256-register kernels keep one workgroup per stream)
-    const int G = (b->slim && !b->alloc1 && !b->lsf && S > b->resident) ? b->resident : S;
-    if (b->alloc1) { if (b->lsf) LAUNCH(k_alloc1_lsf, dim3(G), dim3(128), qa, a); else LAUNCH(k_alloc1, dim3(G), dim3(128), qa, a); }
-    else if (b->lsf) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, a);
-    else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, a);
-    else LAUNCH(k_alloc, dim3(G), dim3(128), qa, a);
+    // A batch of several kinds: one launch per kind that has streams, kinds 0 .. 3, each over its span of the order that
+    // k_order_kinds made, one after the other on this one stream - the claim and idle counters are the batch's, so two walks
+    // never run at once.  The spans come from the host's view of the slots, which is the device's at this point of the stream
+    // (an assign moves both, the device in stream order).  Every position of the order is walked by exactly one launch, so a
+    // call still adds S to the started-counter, whatever its split.
+    int count[4] = {0, 0, 0, 0};
+    if (several_kinds(b)) for (int s = 0; s < S; s++) count[b->cls_kind[b->cls_of[s]]]++;
+    else count[__builtin_ctz(b->kinds)] = S;
+    AllocArgs ak = a;
+    for (int kind = 0, pos = 0; kind < 4; pos += count[kind++]) {
+        const int n = count[kind];
+        if (n == 0) continue;
+        ak.pos0 = pos; ak.npos = n;
+        const int G = (kind == 0 && b->slim && n > b->resident) ? b->resident : n;
+        if (kind == 3) LAUNCH(k_alloc1_lsf, dim3(G), dim3(128), qa, ak);
+        else if (kind == 2) LAUNCH(k_alloc1, dim3(G), dim3(128), qa, ak);
+        else if (kind == 1) LAUNCH(k_alloc_lsf, dim3(G), dim3(128), qa, ak);
+        else if (b->slim) LAUNCH(k_alloc_slim, dim3(G), dim3(128), qa, ak);
+        else LAUNCH(k_alloc, dim3(G), dim3(128), qa, ak);
+    }
     if (!p.call.recording) {
         HIPCHK(hipEventRecord(e1, qa));
         b->pending.push_back({e0, e1});

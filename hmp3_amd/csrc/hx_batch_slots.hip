@@ -265,9 +265,9 @@ static int ledger_op(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, in
     const int k = (int) (b->nslotops++ % 3);
     HxLedgerEntry *h = (HxLedgerEntry *) staging_take(s, k);
     if (!h) return -1;
-    for (int e = 0; e < n; e++) h[e] = open ? HxLedgerEntry{idx[e], open[e].ncalls, open[e].head_bytes, open[e].flags} : HxLedgerEntry{idx[e], 0, 0, 0};
+    for (int e = 0; e < n; e++) h[e] = open ? HxLedgerEntry{idx[e], open[e].ncalls, open[e].head_bytes, open[e].flags, frames_per_block(b->params[b->cls_of[idx[e]]])} : HxLedgerEntry{idx[e], 0, 0, 0, 0};
     if (staging_upload(s, k, sizeof(HxLedgerEntry) * (size_t) n, q) != 0) return -1;
-    if (open) LAUNCH(k_ledger_begin, dim3((unsigned) n), dim3(256), q, b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), b->lsf ? 2 : 1);
+    if (open) LAUNCH(k_ledger_begin, dim3((unsigned) n), dim3(256), q, b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k));
     else LAUNCH(k_ledger_gather, dim3((unsigned) n), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), d_out);
     if (staging_done(s, k, q) != 0) return -1;
     return poison.ok();

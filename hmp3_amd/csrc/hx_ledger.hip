@@ -122,14 +122,15 @@ __global__ __launch_bounds__(256) void k_ledger(HX_LEDGER *__restrict__ led, con
     }
 }
 
-// slot ent[e].slot gets a new open record: the entry's parameters, the batch's frames per call, everything else 0 but every = 1
-__global__ __launch_bounds__(256) void k_ledger_begin(HX_LEDGER *__restrict__ led, const HxLedgerEntry *__restrict__ ent, int frames_per_call)
+// slot ent[e].slot gets a new open record: the entry's parameters, its frames per call among them (the host's view of the slot
+// when the call was made), everything else 0 but every = 1
+__global__ __launch_bounds__(256) void k_ledger_begin(HX_LEDGER *__restrict__ led, const HxLedgerEntry *__restrict__ ent)
 {
     const HxLedgerEntry en = ent[blockIdx.x];
     uint4 *dst = reinterpret_cast<uint4 *>(led + en.slot);
     for (int w = (int) threadIdx.x; w < HX_LEDGER_VECS; w += 256) {
         uint4 v = make_uint4(0, 0, 0, 0);
-        if (w == 0) v = make_uint4((unsigned) en.ncalls, (unsigned) frames_per_call, (unsigned) en.head_bytes, (unsigned) en.flags);
+        if (w == 0) v = make_uint4((unsigned) en.ncalls, (unsigned) en.fpc, (unsigned) en.head_bytes, (unsigned) en.flags);
         else if (w == (int) (offsetof(HX_LEDGER, open) / 16)) v.x = 1;
         else if (w == (int) (offsetof(HX_LEDGER, every) / 16)) v.y = 1;
         dst[w] = v;

@@ -142,6 +142,8 @@ static hx_multi *multi_create(int ndev, const int *devices, int nstreams, Make m
         const int node = hx_device_numa_node(dev);
         m->ncpus.push_back(node >= 0 ? node_cpus_allowed(node, &cs) : 0);
         m->cpus.push_back(cs);
+        // (what the blocks must agree in - the rows' pitch and the frame positions per block, which size out_stride - is the
+        // menu's, whichever entries a block's slots start with: blocks that get the whole menu agree, of whatever kinds it is)
         if (k == 0) m->nchan = b->nchan;
         else if (b->nchan != m->nchan || b->lsf != m->part[0]->lsf) { set_err("mono / stereo and MPEG-1 / MPEG-2 streams cannot share a batch"); hx_multi_destroy(m); return nullptr; }
     }
@@ -183,6 +185,16 @@ extern "C" hx_multi *hx_multi_create_mixed(int ndev, const int *devices, int nst
     if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
     return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
         return hx_batch_create_mixed(dev, count, ec, nmenu, src, cfg ? cfg + first : nullptr, max_frames);
+    });
+}
+
+// ... and of either MPEG version and allocator generation (hx_batch_create_any)
+extern "C" hx_multi *hx_multi_create_any(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                                         const int *cfg, int max_frames)
+{
+    if (nstreams <= 0 || max_frames <= 0 || !ec || nmenu <= 0) { set_err("bad arguments"); return nullptr; }
+    return multi_create(ndev, devices, nstreams, [&](int dev, int first, int count) {
+        return hx_batch_create_any(dev, count, ec, nmenu, src, cfg ? cfg + first : nullptr, max_frames);
     });
 }
 

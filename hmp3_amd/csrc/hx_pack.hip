@@ -180,15 +180,17 @@ __device__ __noinline__ void unmasked_writer_fixup(PackLds &L, int nseg)
     }
 }
 
-// frames_per_stream = frames a stream produces per call (nframes, or 2 nframes at the MPEG-2 rates where every
-// granule is a frame); lsf selects that layout.  The grid is sized to fill the chip once; a workgroup stages the
-// code tables once and then takes every gridDim.x-th frame.
+// frames_per_stream = frame positions per stream and call = the stride of the frm / slots records the stream walk wrote
+// (AllocArgs::fpc): nframes, or 2 nframes when the batch's menu holds an MPEG-2 class, where every granule is a frame.  The
+// stream's own version comes from its class: an MPEG-1 stream has nframes frames, and its positions beyond them leave like
+// positions beyond a stream's count.  The grid is sized to fill the chip once; a workgroup stages the code tables once and
+// then takes every gridDim.x-th frame position.
 __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, const HxParams *__restrict__ prm,
                                               const HxGlobalTabs *__restrict__ gt, const short *__restrict__ ixq,
                                               const unsigned *__restrict__ sgn, const HxSegOut *__restrict__ seg,
                                               const HxFrameOut *__restrict__ frm, const HxSlot *__restrict__ slots,
                                               unsigned char *__restrict__ out, long long out_stride, unsigned char *__restrict__ packet,
-                                              int *__restrict__ status, int frames_per_stream, int NG, int lsf, long long nframes_total,
+                                              int *__restrict__ status, int frames_per_stream, int NG, long long nframes_total,
                                               int solo, HxStream *__restrict__ st_w, const int *__restrict__ pre_len, const int *__restrict__ out_bytes,
                                               const int *__restrict__ carry_len, unsigned *__restrict__ frames_out,
                                               unsigned char *__restrict__ host_out, const int *__restrict__ seq_src, const int *__restrict__ nfr)
@@ -214,10 +216,14 @@ __global__ __launch_bounds__(256) void k_pack(const HxStream *__restrict__ st, c
     }
     for (long long fr = blockIdx.x; fr < nframes_total; fr += gridDim.x) {
         const int s = (int) (fr / frames_per_stream), f = (int) (fr % frames_per_stream);
-        if (nfr && f >= (lsf ? 2 : 1) * nfr[s]) continue;       // beyond the stream's count: no record (the whole workgroup, ahead of its barriers)
+        // (the bit buffer is cleared while the stream's class is on its way; a position that leaves below cleared it for nothing)
         for (int i = tid; i < 640; i += 256) L.bitw[i] = 0;
         if (tid == 0) L.negflag = 0;
         const HxParams *p = prm + __builtin_amdgcn_readfirstlane(st[s].cls);
+        const int lsf = !p->h_id;                               // (a workgroup stages one frame: uniform ahead of its barriers)
+        // beyond the stream's frames of the call - its count, or the first half of its positions for an MPEG-1 stream beside
+        // MPEG-2 ones: no record (the whole workgroup, ahead of its barriers)
+        if (f >= (lsf ? 2 : 1) * (nfr ? nfr[s] : NG / 2)) continue;
         const int nchan = p->nchan, hdr = 4 + p->side_bytes;
         // wave w <-> segment (granule, channel)
         const int g = lsf ? f : 2 * f + (w >> 1), ch = w & 1;
@@ -368,6 +374,39 @@ __global__ __launch_bounds__(1024) void k_order(const unsigned *__restrict__ dur
     if (tid == 0) { unsigned acc = 0; for (int b = 0; b < 1024; b++) { const unsigned c = hist[b]; hist[b] = acc; acc += c; } }
     __syncthreads();
     for (int i = tid; i < S; i += 1024) order[atomicAdd(&hist[1023 - (unsigned) (((unsigned long long) (dur[i] - base) * 1024) / range)], 1u)] = i;
+}
+
+// ... of a batch whose menu holds several kinds of stream (kind = 2 * alloc1 + lsf, read from the stream's class): the
+// streams partitioned by kind, kinds 0 .. 3 in that order, and within a kind by duration as above - the same counting sort
+// on 4 x 256 buckets, bucket = kind * 256 + duration class.  Each kind's walk kernel takes its span of the order
+// (AllocArgs::pos0 / npos): the host sizes the spans from its own count of streams per kind, which is the device's at this
+// point of the stream (hx_batch.hip, launch_walk).  One workgroup.
+__global__ __launch_bounds__(1024) void k_order_kinds(const unsigned *__restrict__ dur, const HxStream *__restrict__ st, const HxParams *__restrict__ prm,
+                                                      int *__restrict__ order, int S)
+{
+    __shared__ unsigned hist[1024];
+    __shared__ unsigned lo, hi;
+    const int tid = threadIdx.x;
+    if (tid == 0) { lo = 0xFFFFFFFFu; hi = 0; }
+    hist[tid] = 0;
+    __syncthreads();
+    unsigned mn = 0xFFFFFFFFu, mx = 0;
+    for (int i = tid; i < S; i += 1024) { const unsigned d = dur[i]; mn = min(mn, d); mx = max(mx, d); }
+    atomicMin(&lo, mn);
+    atomicMax(&hi, mx);
+    __syncthreads();
+    const unsigned base = lo;
+    const unsigned long long range = (unsigned long long) (hi - lo) + 1;
+    auto bucket = [&](int i) {
+        const HxParams *p = prm + st[i].cls;
+        const unsigned kind = 2u * (p->alloc1 ? 1u : 0u) + (p->h_id ? 0u : 1u);
+        return kind * 256u + 255u - (unsigned) (((unsigned long long) (dur[i] - base) * 256) / range);
+    };
+    for (int i = tid; i < S; i += 1024) atomicAdd(&hist[bucket(i)], 1u);
+    __syncthreads();
+    if (tid == 0) { unsigned acc = 0; for (int b = 0; b < 1024; b++) { const unsigned c = hist[b]; hist[b] = acc; acc += c; } }
+    __syncthreads();
+    for (int i = tid; i < S; i += 1024) order[atomicAdd(&hist[bucket(i)], 1u)] = i;
 }
 
 // ---- the dense image of a call (hx_batch_dense_buffers): behind the packing, the rows' used parts back to back ----

@@ -61,7 +61,7 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
                                                    const HxParams *__restrict__ prm,
                                                    const HxGlobalTabs *__restrict__ gt,
                                                    float *__restrict__ sb, int NG, int SG,
-                                                   const float *__restrict__ pcmf, int pitch, int *__restrict__ eng, int lsf,
+                                                   const float *__restrict__ pcmf, int pitch, int *__restrict__ eng,
                                                    const int *__restrict__ nfr)
 {
     // pitch: the channels every PCM row is laid out for (hx_batch_pcm_channels); nchan below: the stream's own, which in a
@@ -78,6 +78,7 @@ __global__ __launch_bounds__(K1_THREADS) void k_polyphase(const int16_t *__restr
     const HxStream *ss = st + s;
     const HxParams *p = prm + __builtin_amdgcn_readfirstlane(ss->cls);
     const int nchan = p->nchan;                                 // (a scalar load: cls is wave-uniform)
+    const int lsf = !p->h_id;                                   // the stream's own version (the same: the workgroup is one stream's)
     const int16_t *src = pcm + (long long) s * nsamp * pitch;   // interleaved L R (or one channel)
     if (blockIdx.y == 0 && lt < 18) {
         // The detector energies of eng index 0 (this kernel's epilogue writes the others): from the carried last granule of the
@@ -257,7 +258,7 @@ __device__ __forceinline__ void attack_metric(const int *hist, const int *eng, i
 __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const HxParams *__restrict__ prm,
                                                 const int *__restrict__ eng, unsigned char *__restrict__ flg,
                                                 int *__restrict__ dbg_metric, unsigned char *__restrict__ bt,
-                                                unsigned char *__restrict__ btprev, int NG, int S, int lsf, const int *__restrict__ nfr)
+                                                unsigned char *__restrict__ btprev, int NG, int S, const int *__restrict__ nfr)
 {
     __shared__ unsigned char sflg[4][64], sbt[4][64];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
@@ -268,7 +269,10 @@ __global__ __launch_bounds__(256) void k_detect(HxStream *__restrict__ st, const
     const int NGs = nfr ? __builtin_amdgcn_readfirstlane(2 * nfr[s]) : NG;
     if (NGs == 0) return;
     HxStream *ss = st + s;
-    const int thr = prm[ss->cls].short_block_threshold;
+    // (the stream's class through a scalar register: the wave is one stream's, its neighbours in the workgroup may be of
+    // another MPEG version, and nothing below is a workgroup barrier)
+    const HxParams *p = prm + __builtin_amdgcn_readfirstlane(ss->cls);
+    const int thr = p->short_block_threshold, lsf = !p->h_id;
     // sel[prev type * 4 + short now * 2 + short next] = {0, 1, 2, 2, 3, 2, 2, 2, 3, 2, 2, 2, 0, 1, 2, 2} as nibbles of a constant
     const unsigned long long sel = 0x2210222322232210ull;
     int prev_next = ss->short_flag_next_prev, prev_bt = ss->bt_prev;

@@ -35,22 +35,22 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 // pitch (the kernels that read PCM): the channels every PCM row is laid out for, hx_batch::nchan; a stream's own channel
 // count comes from its class (HxParams::nchan) or its plan (HxSrcPlan::nch).
 __global__ void k_polyphase(const int16_t *pcm, long long nsamp, const HxStream *st, const HxParams *prm,
-                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int pitch, int *eng, int lsf, const int *nfr);
+                            const HxGlobalTabs *gt, float *sb, int NG, int SG, const float *pcmf, int pitch, int *eng, const int *nfr);
 __global__ void k_dcfilter(const int16_t *pcm, const float *pcm32, long long nsamp, HxStream *st, const HxParams *prm, float *pcmf, int S, int pitch, const int *nfr);
 __global__ void k_src(SrcArgs a);
 __global__ void k_detect(HxStream *st, const HxParams *prm, const int *eng, unsigned char *flg, int *dbg_metric, unsigned char *bt,
-                         unsigned char *btprev, int NG, int S, int lsf, const int *nfr);
+                         unsigned char *btprev, int NG, int S, const int *nfr);
 __global__ void k_spec(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
                        float *xr, float *etab, float *thr, int *msbase, int NG, int SG, const int *nfr);
 __global__ void k_spec_direct(const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const unsigned char *bt,
                               float *xr, float *etab, float *thr, int *msbase, int NG, int SG, const int *nfr);
 __global__ void k_msscan(HxStream *st, const HxParams *prm, const int *msbase, const unsigned char *bt, unsigned char *msflag, int *msdec,
-                         const float *thr, float *thrprev, int NG, int lsf, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int pitch, const int *nfr);
+                         const float *thr, float *thrprev, int NG, float *sb, int SG, const int16_t *pcm, long long nsamp, const float *pcmf, int pitch, const int *nfr);
 __global__ void k_prep(const float *xr, float *xmag_dbg, float *x34o, unsigned *sgn, HxBandPrep *band, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt,
                        const unsigned char *bt, const unsigned char *msflag, const float *etab, const float *thr, const float *thrprev, int NG, long long nunits, const int *nfr);
 __global__ void k_pack(const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const short *ixq, const unsigned *sgn, const HxSegOut *seg,
                        const HxFrameOut *frm, const HxSlot *slots, unsigned char *out, long long out_stride, unsigned char *packet, int *status,
-                       int frames_per_stream, int NG, int lsf, long long nframes_total, int solo, HxStream *st_w, const int *pre_len, const int *out_bytes,
+                       int frames_per_stream, int NG, long long nframes_total, int solo, HxStream *st_w, const int *pre_len, const int *out_bytes,
                        const int *carry_len, unsigned *frames_out, unsigned char *host_out, const int *seq_src, const int *nfr);
 __global__ void k_pack_carry(HxStream *st, const unsigned char *out, long long out_stride, const int *out_bytes, const int *carry_len, unsigned *frames_out);
 __global__ void k_pack_pre(const HxStream *st, unsigned char *out, long long out_stride, const int *pre_len);
@@ -62,9 +62,10 @@ __global__ void k_slot_reset(SlotArgs a);
 __global__ void k_slot_gather(SlotArgs a, uint2 *blobs);
 __global__ void k_slot_scatter(SlotArgs a, const uint2 *blobs);
 __global__ void k_ledger(HX_LEDGER *led, const int *stats, const unsigned short *crc, const int *out_bytes, const int *nfr, int nframes, int S);
-__global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent, int frames_per_call);
+__global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent);
 __global__ void k_ledger_gather(const HX_LEDGER *led, const HxLedgerEntry *ent, HX_LEDGER *out);
 __global__ void k_order(const unsigned *dur, int *order, int S);
+__global__ void k_order_kinds(const unsigned *dur, const HxStream *st, const HxParams *prm, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
 __global__ void k_alloc(AllocArgs a);
 __global__ void k_alloc_slim(AllocArgs a);
@@ -153,9 +154,16 @@ struct hx_batch {
     bool any_dc = false;
     int nchan = 2;                      // P, the pitch: channels every PCM row (the caller's, d_pcmf, d_src_pcm) is laid out for = the largest
                                         // over the menu.  A stream's own count is its class's (params[cls].nchan): they differ in a mixed batch only
-    int lsf = 0;                        // 1: an MPEG-2 LSF batch (16 / 22.05 / 24 kHz): every 1152-sample block yields two frames
-    int slim = 0;                       // 1: the low-footprint stream walk k_alloc_slim (six streams per CU instead of four), chosen at create
-    int alloc1 = 0;                     // 1: streams of the first-generation allocator (intensity stereo, dual channel): k_alloc1*
+    // A class's kind = 2 * alloc1 + lsf: alloc1 = the first-generation allocator (intensity stereo, dual channel), lsf = an
+    // MPEG-2 rate (16 / 22.05 / 24 kHz), where every 1152-sample block yields two frames.  Each kind has its own stream-walk
+    // kernel.  kinds: the kinds of the menu's classes as a bit mask; a batch of one kind (every create call but
+    // hx_batch_create_any allows no other) has that kind in lsf / alloc1 and walks all streams in one launch.  With several
+    // kinds, lsf = 1 when any class is MPEG-2 (the frame positions per block the packing covers: AllocArgs::fpc) and alloc1
+    // is not used: launch_walk makes one launch per kind over its span of the order k_order_kinds made.
+    int lsf = 0, alloc1 = 0;
+    unsigned kinds = 0;
+    std::vector<int> cls_kind;          // class -> kind
+    int slim = 0;                       // 1: the low-footprint stream walk k_alloc_slim (six streams per CU instead of four) for the kind-0 streams, chosen at create
     int *d_eng = nullptr, *d_status = nullptr, *d_dbgmetric = nullptr;
     unsigned char *d_flg = nullptr;
     HxFrameDebug *d_dbg = nullptr;
@@ -260,6 +268,11 @@ struct hx_batch {
     std::vector<hipStream_t> streams;
     std::vector<hipEvent_t> events;
 };
+
+// more than one kind of stream in the menu (hx_batch_create_any): one stream-walk launch per kind
+static inline bool several_kinds(const hx_batch *b) { return (b->kinds & (b->kinds - 1)) != 0; }
+// frames per 1152-sample block of a class: 1, or 2 at the MPEG-2 rates
+static inline int frames_per_block(const HxParams &p) { return p.h_id ? 1 : 2; }
 
 // Every device buffer, HIP stream and event of a batch is made by one of these and listed in the batch, whose
 // hx_batch_destroy releases them.
@@ -386,8 +399,9 @@ HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out,
 // The one create path (hx_batch.hip).  ec[nmenu] (and src[nmenu]: a converting batch) is the menu, cfg[nstreams] or null
 // (= entry 0) the entry each slot starts with.  A refusal names the entry as "<label> <origin[j]>: " - src_label for what
 // the converter rejects, cls_label for what the encoder's init or the batch's kind rejects; a null label: no prefix; a null
-// origin: the entry's own number.  mixed: entries may differ in channel count (hx_batch_create_mixed).
-struct MenuNames { const char *src_label, *cls_label; const int *origin; bool mixed = false; };
+// origin: the entry's own number.  mixed: entries may differ in channel count (hx_batch_create_mixed); any: also in MPEG
+// version and allocator generation (hx_batch_create_any).
+struct MenuNames { const char *src_label, *cls_label; const int *origin; bool mixed = false, any = false; };
 HX_LOCAL hx_batch *batch_create(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src, const int *cfg,
                                 int max_frames, const MenuNames &names);
 // ... its converter parts (hx_batch_src.hip): every entry's encode control and plan (plans deduplicated), before anything

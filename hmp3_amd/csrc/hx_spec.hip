@@ -516,13 +516,15 @@ HX_K4(k_spec_direct, true)
 // when this kernel starts, and 63 of its 64 lanes had nothing to do.)
 __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const HxParams *__restrict__ prm, const int *__restrict__ msbase,
                                                const unsigned char *__restrict__ bt, unsigned char *__restrict__ msflag, int *__restrict__ msdec,
-                                               const float *__restrict__ thr, float *__restrict__ thrprev, int NG, int lsf,
+                                               const float *__restrict__ thr, float *__restrict__ thrprev, int NG,
                                                float *__restrict__ sb, int SG, const int16_t *__restrict__ pcm, long long nsamp,
                                                const float *__restrict__ pcmf, int pitch, const int *__restrict__ nfr)
 {
     const int s = blockIdx.x, lane = threadIdx.x;
     HxStream *ss = st + s;
-    const int nchan = prm[ss->cls].nchan;       // the stream's own channels; pitch: those its PCM row is laid out for
+    const HxParams *p = prm + __builtin_amdgcn_readfirstlane(ss->cls);
+    const int nchan = p->nchan;                 // the stream's own channels; pitch: those its PCM row is laid out for
+    const int lsf = !p->h_id;                   // ... and its own MPEG version: an MPEG-2 frame is one granule
     const long long g0 = (long long) s * NG;
     // The stream's granules of this call (hx_batch_frame_counts): the bound of the scan, and where the hand-overs to the next
     // call come from - the pre-echo memory from granule NGs - 1, the subband carry from slots NGs .. NGs + 2, the PCM history
@@ -531,7 +533,7 @@ __global__ __launch_bounds__(64) void k_msscan(HxStream *__restrict__ st, const 
     if (NGs == 0) return;
     const long long nown = 576LL * NGs;
     if (lane == 0) {
-        const int on = prm[ss->cls].ms_flag, plain = prm[ss->cls].alloc1;    // (the first-generation allocator's measure takes no hysteresis)
+        const int on = p->ms_flag, plain = p->alloc1;    // (the first-generation allocator's measure takes no hysteresis)
         int mem = ss->ms_memory;
         auto frame = [&](int b1, int b2, int v1, int v2, int *m1o, int *m2o) {      // one pair of granules; returns the two flags
             int m1 = 0, m2 = 0;

@@ -318,8 +318,16 @@ struct AllocArgs {
     short *ixq;                 // [S][NG][2][576] quantised magnitudes
     unsigned *sgn_w;            // the sign buffer again, writable: short-block granules store their reordered signs
     HxSegOut *seg;              // [S][NG][2]
-    HxFrameOut *frm;            // [S][frames per call]
-    HxSlot *slots;              // [S][frames per call + HX_SLOTS_EXTRA]
+    HxFrameOut *frm;            // [S][fpc]
+    HxSlot *slots;              // [S][fpc + HX_SLOTS_EXTRA]
+    // The launch's span of the batch-wide launch order: positions pos0 .. pos0 + npos - 1 (`order` [S] maps a position to its
+    // stream; null = identity).  A batch of one kind walks 0 .. S - 1 in one launch; a batch of several kinds makes one launch
+    // per kind, each over that kind's span of the order k_order_kinds made (hx_batch.hip, launch_walk).
+    int pos0, npos;
+    // fpc: frame records per stream = the stride of frm and (+ HX_SLOTS_EXTRA) of slots, one value for every walk kernel of a
+    // call and for k_pack, which reads them: NG / 2 when every class of the batch is MPEG-1, else NG (an MPEG-1 stream of such
+    // a batch uses the first NG / 2 of its row)
+    int fpc;
 };
 
 
@@ -365,7 +373,8 @@ static_assert(HX_STATE_OFF_STREAM % 8 == 0 && HX_STATE_OFF_CARRY % 8 == 0 && HX_
 // ---- the file ledger (hx_ledger.hip: k_ledger / k_ledger_begin / k_ledger_gather; the record: HX_LEDGER, include/hmp3_amd.h) ----
 // One listed slot of hx_batch_ledger_begin (the file's parameters) or of a read (the slot alone).  It travels through the
 // slot operations' staging, whose copies hold [S] HxSlotEntry.
-struct HxLedgerEntry { int slot, ncalls, head_bytes, flags; };
+// fpc: the frames per call (1152-sample block) of the entry the slot runs when the record begins: 1, or 2 at the MPEG-2 rates.
+struct HxLedgerEntry { int slot, ncalls, head_bytes, flags, fpc; };
 static_assert(sizeof(HxLedgerEntry) <= sizeof(HxSlotEntry), "a ledger list fits the slot operations' staging");
 #define HX_LEDGER_KEPT 512                          // seek points before a decimation halves them (hx_xing_toc)
 #define HX_LEDGER_HDR_WORDS 16                      // 4-byte words in front of the points

@@ -217,8 +217,9 @@ int hx_batch_set_stream_states(hx_batch *b, const int *idx, int n, const void *b
    The checkpoint blob of an assigned slot is a new batch's but for one word: the class index at the start of the stream
    record is the batch's own numbering of its menu's configurations, which a restore replaces with the receiving batch's.
    The command-line tool's -batch -slots<n> runs any number of files through n slots this way.
-   Not covered: entries added after create; MPEG-1 / MPEG-2 rates or allocator generations in one batch (channel counts:
-   hx_batch_create_mixed below); device blobs and pipelined submits of converting batches, as before. */
+   Not covered: entries added after create; device blobs and pipelined submits of converting batches, as before.  (Entries
+   of different channel counts: hx_batch_create_mixed below; of different MPEG versions or allocator generations:
+   hx_batch_create_any below.) */
 hx_batch *hx_batch_create_menu(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
                                const int *cfg, int max_frames);
 int hx_batch_nconfigs(const hx_batch *b);
@@ -248,8 +249,9 @@ int hx_batch_assign_streams(hx_batch *b, const int *idx, const int *cfg, int n, 
    Checkpoint blobs are those of any batch and interchangeable with them: a mono stream saved from a mixed batch restores
    into a uniform mono batch of the same control, and back (the fingerprint is per control and holds the channel count).
    Still refused at create, with hx_batch_create's messages ("menu entry j: ..."): MPEG-1 with MPEG-2 rates, and the two
-   allocator generations - dual channel (mode 2) and intensity stereo stay apart from the others.
-   hx_batch_frames_bytes, the ledger (frames_per_call is the batch's MPEG version), hx_batch_nconfigs and
+   allocator generations - dual channel (mode 2) and intensity stereo stay apart from the others (hx_batch_create_any below
+   takes them).
+   hx_batch_frames_bytes, the ledger (frames_per_call is the MPEG version of the entry the slot runs), hx_batch_nconfigs and
    hx_batch_stream_config are what they are for any menu.
    hx_multi_create_mixed: the same in blocks over several devices; every block gets the whole menu and so the same P, and the
    caller's PCM is split between the blocks by P. */
@@ -257,6 +259,35 @@ hx_batch *hx_batch_create_mixed(int device, int nstreams, const HX_E_CONTROL *ec
                                 const int *cfg, int max_frames);
 int hx_batch_pcm_channels(const hx_batch *b);              /* P: the channel count the PCM rows are pitched for = the largest over the menu */
 int hx_batch_stream_channels(const hx_batch *b, int i);    /* channels of the entry slot i runs as of the calls made so far; -1 bad arguments */
+/* ---- one batch for every stream kind: MPEG-1 and MPEG-2 rates, both allocator generations (no reference equivalent) ----
+   hx_batch_create_any is hx_batch_create_mixed word for word, except that its entries may also differ in MPEG version (the
+   MPEG-1 rates 32 / 44.1 / 48 kHz beside the MPEG-2 rates 16 / 22.05 / 24 kHz) and in allocator generation (dual channel,
+   mode 2, and intensity stereo beside the others).  The four other create calls keep refusing that, with their messages.
+   An entry's kind is 2 * (first-generation allocator) + (MPEG-2 rate).  A menu of one kind gives a batch that is in every
+   respect what hx_batch_create_mixed returns for the same arguments: same kernel choice, same launches, same bytes.
+   Input: a call's PCM is nframes blocks of 1152 samples per channel for every stream, whatever its rate; the row layout is
+   hx_batch_create_mixed's.  Of a block an MPEG-1 stream makes one frame, an MPEG-2 stream two: hx_batch_stream_frames_per_block
+   says which for the entry a slot runs as of the calls made so far; callers size their hx_batch_frames_bytes-style
+   bookkeeping from it.  Everything that counts per call - nframes, per-stream frame counts, frame counters, packets, CRCs,
+   the ledger's ncalls - counts input blocks for every stream.
+   hx_batch_out_stride is the largest over the menu's classes of (frames per block * nframes + 2) * the class's largest frame
+   + 4096, rounded up to 256; for a menu of one MPEG version that is what it always was.
+   Per slot, every contract stands as it is: hx_batch_assign_streams / hx_multi_assign_streams between entries of any kinds
+   (from its next frame on the slot produces exactly the bytes of slot 0 of a new batch created with that entry); reset,
+   save and restore in their host and device forms (a blob is its control's, whatever batch saved it); per-stream frame
+   counts; packets - an MPEG-2 stream's two packet sizes per block sit beside an MPEG-1 stream's {size, 0}; frame counters,
+   MusicCRC and the dense image; the ledger, whose frames_per_call is that of the entry the slot runs when
+   hx_batch_ledger_begin is called; converting batches - one 44.1 kHz source may feed a 22.05 kHz entry beside a 44.1 kHz
+   one; pipelined submits of plain batches.
+   The stream walk of a batch of several kinds is one launch per kind that has streams, one after the other: hx_batch_alloc_kernel_ms
+   covers them all.  The low-footprint build (HMP3AMD_K6) is chosen for the kind-0 streams by the usual rule, which counts
+   all of the batch's streams against the resident set, not the kind-0 streams alone: a large batch with few kind-0 streams
+   walks those few with the low-footprint build, slower per stream, for no gain - HMP3AMD_K6=fat overrides it.
+   hx_multi_create_any: the same in blocks over several devices; every block gets the whole menu, so the blocks agree in
+   row pitch and out_stride whichever entries their slots start with. */
+hx_batch *hx_batch_create_any(int device, int nstreams, const HX_E_CONTROL *ec, int nmenu, const HX_SOURCE *src,
+                              const int *cfg, int max_frames);
+int hx_batch_stream_frames_per_block(const hx_batch *b, int i);   /* 1 or 2: frames per 1152-sample block of the entry slot i runs as of the calls made so far; -1 bad arguments */
 /* worst-case bytes one stream can emit in a call of nframes frames */
 long long hx_batch_out_stride(const hx_batch *b, int nframes);
 /* PCM: int16 interleaved L/R, [nstreams][nframes*1152][2]; out: [nstreams][out_stride] bytes;
@@ -633,6 +664,9 @@ hx_multi *hx_multi_create_menu(int ndev, const int *devices, int nstreams, const
                                const HX_SOURCE *src, const int *cfg, int max_frames);
 /* the same over all blocks (idx counts streams over all blocks); synchronous like the other hx_multi calls; all blocks or (-1) none */
 int hx_multi_assign_streams(hx_multi *m, const int *idx, const int *cfg, int n);
+/* hx_batch_create_any in blocks over several devices ("one batch for every stream kind" above) */
+hx_multi *hx_multi_create_any(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu,
+                              const HX_SOURCE *src, const int *cfg, int max_frames);
 /* hx_batch_create_mixed in blocks over several devices ("mixed batches" above) */
 hx_multi *hx_multi_create_mixed(int ndev, const int *devices, int nstreams, const HX_E_CONTROL *ec, int nmenu,
                                 const HX_SOURCE *src, const int *cfg, int max_frames);
