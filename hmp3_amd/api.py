@@ -281,6 +281,34 @@ def _frame_counts(setter, handle, n, counts):
         raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
 
 
+def packed_layout(nframes, channels, counts=None, f32=False):
+    """the tight layout of a call's PCM image (hx_pcm_packed_layout; host only): stream i's segment is counts[i] (None:
+    nframes) frames of channels[i] channels, int16 or float32, the segments back to back -> (offsets int64 [n + 1], the
+    image's bytes = offsets[n])"""
+    ch = [int(c) for c in channels]
+    n = len(ch)
+    off = np.zeros(n + 1, dtype=np.int64)
+    total = int(lib().hx_pcm_packed_layout(n, int(nframes), _counts_array(n, counts), (C.c_int * max(n, 1))(*ch), 4 if f32 else 2, off.ctypes.data))
+    if total < 0:
+        raise ValueError("hx_pcm_packed_layout: bad arguments (channels 1 or 2, counts within 0 .. nframes)")
+    return off, total
+
+
+def _pcm_segments(setter, handle, n, off, in_bytes):
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        if len(off) not in (n, n + 1):
+            raise ValueError("PCM segments: %d offsets for %d streams" % (len(off), n))
+    if setter(handle, None if off is None else off.ctypes.data, int(in_bytes)) != 0:
+        raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
+
+
+def _pcm_image(image):
+    """-> a host call's flat PCM image as the C ABI takes it: contiguous int16 or float32 (at int16 scale), any shape"""
+    f32 = np.asarray(image).dtype == np.float32
+    return np.ascontiguousarray(image, dtype=np.float32 if f32 else np.int16)
+
+
 def _pitch(batch_handle):
     """hx_batch_pcm_channels, or None from a library build that predates it (A/B runs through HMP3AMD_LIB)"""
     L = lib()
@@ -416,6 +444,18 @@ class Batch:
         """per-stream frame counts of the calls that follow: a sequence of n ints (stream i takes the first counts[i] frames of
         its row; 0 = it sits the call out), or None = every stream takes the call's nframes (hx_batch_frame_counts)"""
         _frame_counts(lib().hx_batch_frame_counts, self.h, self.n, counts)
+        self._counts = None if counts is None else [int(c) for c in counts]
+
+    def pcm_segments(self, off, in_bytes=0):
+        """PCM segments of the calls that follow (hx_batch_pcm_segments): off = n byte offsets (n + 1, as packed_layout returns
+        them, is taken too) into one image of in_bytes bytes - the pcm / d_pcm argument of every encode and submit call is
+        then the image's base, and stream i's input the bytes at off[i]; None = back to rows"""
+        _pcm_segments(lib().hx_batch_pcm_segments, self.h, self.n, off, in_bytes)
+
+    def packed_layout(self, nframes, f32=False):
+        """the tight layout (api.packed_layout) of a call of nframes made now: the counts in force (frame_counts) and the
+        channels of the entries the slots run -> (offsets int64 [n + 1], the image's bytes)"""
+        return packed_layout(nframes, [self.stream_channels(i) for i in range(self.n)], getattr(self, "_counts", None), f32)
 
     def encode_host(self, pcm, stats=False, crc=False):
         """pcm: int16 (or float32 at int16 scale) [n, nframes*1152, P] or [n, nframes*1152*P], P = pcm_channels() (a mono
@@ -423,6 +463,15 @@ class Batch:
         only) -> (that list, int32 [n, nframes, 2]: frames / bytes emitted so far after every input frame); with stats and
         crc -> (list, stats, uint16 [n, nframes]: the CRC of the call's bytes up to every input frame)"""
         pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        return self._encode_host(pcm, nfr, stats, crc)
+
+    def encode_host_image(self, image, nframes, stats=False, crc=False):
+        """encode_host under pcm_segments: image = the flat PCM image the segments in force address (int16, or float32 at
+        int16 scale; any shape), nframes = the call's frames, which no shape gives here.  The device calls take a pointer
+        and nframes already: under segments encode_device / submit_device / submit_host get the image's base"""
+        return self._encode_host(_pcm_image(image), int(nframes), stats, crc)
+
+    def _encode_host(self, pcm, nfr, stats, crc):
         f32 = pcm.dtype == np.float32
         stride = self.out_stride(nfr)
         out = np.zeros((self.n, stride), dtype=np.uint8)
@@ -461,6 +510,13 @@ class Batch:
         """encode_host of which only the dense image crosses the link -> (list of bytes per stream, offsets int64 [n + 1]);
         dense_cap: the image buffer's size (default: dense_bound) - streams whose segment does not fit it come back as None"""
         pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        return self._encode_host_dense(pcm, nfr, dense_cap)
+
+    def encode_host_dense_image(self, image, nframes, dense_cap=None):
+        """encode_host_dense under pcm_segments: a flat image plus nframes, as encode_host_image"""
+        return self._encode_host_dense(_pcm_image(image), int(nframes), dense_cap)
+
+    def _encode_host_dense(self, pcm, nfr, dense_cap):
         f32 = pcm.dtype == np.float32
         cap = self.dense_bound(nfr) if dense_cap is None else int(dense_cap)
         dense = np.zeros(max(cap, 1), dtype=np.uint8)
@@ -856,10 +912,26 @@ class Multi:
     def frame_counts(self, counts):
         """as Batch.frame_counts, over all streams (hx_multi_frame_counts)"""
         _frame_counts(lib().hx_multi_frame_counts, self.h, self.n, counts)
+        self._counts = None if counts is None else [int(c) for c in counts]
+
+    def pcm_segments(self, off, in_bytes=0):
+        """as Batch.pcm_segments, over all streams: the offsets address the caller's one image (hx_multi_pcm_segments)"""
+        _pcm_segments(lib().hx_multi_pcm_segments, self.h, self.n, off, in_bytes)
+
+    def packed_layout(self, nframes, f32=False):
+        """as Batch.packed_layout, over all streams"""
+        return packed_layout(nframes, [self.stream_channels(i) for i in range(self.n)], getattr(self, "_counts", None), f32)
 
     def encode_host(self, pcm, stats=False, crc=False):
         """as Batch.encode_host, over all streams"""
         pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.batch(0)))
+        return self._encode_host(pcm, nfr, stats, crc)
+
+    def encode_host_image(self, image, nframes, stats=False, crc=False):
+        """as Batch.encode_host_image, over all streams"""
+        return self._encode_host(_pcm_image(image), int(nframes), stats, crc)
+
+    def _encode_host(self, pcm, nfr, stats, crc):
         f32 = pcm.dtype == np.float32
         stride = int(lib().hx_multi_out_stride(self.h, nfr))
         out = np.zeros((self.n, stride), dtype=np.uint8)

@@ -597,9 +597,14 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
         if (!loaded && (!load_input(files[2 * s], opt, &jobs[s].in, false) || !job_control(jobs[s], files[2 * s], opt, conv) || !job_calls(jobs[s], files[2 * s], opt, conv))) { hx_multi_destroy(b); return 1; }
     }
     const long long stride = hx_multi_out_stride(b, CH);
-    // the plain route's rows are pitched for the widest file's channels; a mono file's frames sit contiguous at its row's start
+    // the plain route feeds one tight image per call (PCM segments): every file's frames of the call back to back, a mono
+    // file's at half a stereo file's size, nothing for a slot that sits the call out - only that crosses the link.  (Its
+    // capacity is the rows': pitched for the widest file's channels.)
     const int pitch = hx_batch_pcm_channels(hx_multi_batch(b, 0));
     std::vector<float> pcm(conv ? 0 : (size_t) NS * CH * 1152 * pitch), tmp(2304);
+    std::vector<long long> seg(NS + 1, 0);
+    std::vector<int> seg_ch(NS, 1);
+    long long image = 0;
     const std::vector<unsigned char> zero_frame(2304 * 4, 0);
     // converting route: a row holds the file's bytes from its next call on, enough for CH calls of any file, then a region of
     // zero bytes that every drain call reads, as the single-file loop hands one zero buffer to all of them
@@ -637,6 +642,10 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             nf = std::max(nf, cnt[s]);
         }
         if (nf == 0) break;
+        if (!conv) {
+            for (int s = 0; s < NS; s++) seg_ch[s] = held[s] >= 0 ? jobs[held[s]].nch : 1;
+            image = hx_pcm_packed_layout(NS, nf, cnt.data(), seg_ch.data(), (int) sizeof(float), seg.data());
+        }
         for (int s = 0; s < NS && !conv; s++) {
             if (cnt[s] == 0) continue;
             const Job &j = jobs[held[s]];
@@ -646,7 +655,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
                 // 8-bit unsigned input where a zero byte is full-scale negative
                 if (p0 + k < j.nc) frame_to_float(j.in, j.in.data.data() + (p0 + k) * j.in.frame_in, tmp.data());
                 else frame_to_float(j.in, zero_frame.data(), tmp.data());
-                memcpy(&pcm[((size_t) s * nf * pitch + (size_t) k * j.nch) * 1152], tmp.data(), sizeof(float) * 1152 * j.nch);
+                memcpy(&pcm[(size_t) seg[s] / sizeof(float) + (size_t) k * j.nch * 1152], tmp.data(), sizeof(float) * 1152 * j.nch);
             }
         }
         for (int s = 0; s < NS && conv; s++) {
@@ -662,7 +671,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             for (int k = 0; k < nf; k++) off[(size_t) s * nf + k] = (k < cnt[s] && p0 + k < j.nc) ? j.start[p0 + k] - base : row_data;
         }
         const int rc_call = conv ? hx_multi_encode_src_counts_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), out.data(), stride, nb.data(), nullptr, stats.data(), crc.data())
-                                 : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
+                                 : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_pcm_segments(b, seg.data(), image) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
         if (rc_call != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);

@@ -342,6 +342,56 @@ extern "C" int hx_batch_frame_counts(hx_batch *b, const int *nfr)
     return 0;
 }
 
+// PCM segments of the calls that follow.  Like the counts, only the host copy changes here: a call checks it against its
+// nframes, its sample size and the counts and channels as of the call (check_segments) and uploads it for itself
+// (upload_segments), so what is set later never reaches a call already made.
+extern "C" long long hx_pcm_packed_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off)
+{
+    if (nstreams < 0 || nframes < 0 || !off || !channels || (sample_bytes != 2 && sample_bytes != 4)) return -1;
+    for (int i = 0; i < nstreams; i++)
+        if ((channels[i] != 1 && channels[i] != 2) || (nfr && (nfr[i] < 0 || nfr[i] > nframes))) return -1;
+    off[0] = 0;
+    for (int i = 0; i < nstreams; i++) off[i + 1] = off[i] + (long long) (nfr ? nfr[i] : nframes) * 1152 * channels[i] * sample_bytes;
+    return off[nstreams];
+}
+int segs_reserve(hx_batch *b, bool buffers)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (b->nsrc) { set_err("a converting batch takes no PCM segments: its input is per stream already (in_stride, frame_off)"); return -1; }
+    if (!buffers || b->seg_stage.d) return 0;
+    int dev0 = -1;
+    HIPCHK(hipGetDevice(&dev0));
+    HIPCHK(hipSetDevice(b->device));
+    const int rc = staging_make(b, b->seg_stage, sizeof(long long) * (size_t) b->S);
+    (void) hipSetDevice(dev0);
+    return rc;
+}
+extern "C" int hx_batch_pcm_segments(hx_batch *b, const long long *off, long long in_bytes)
+{
+    if (segs_reserve(b, off != nullptr) != 0) return -1;
+    if (off && in_bytes < 0) { set_err("in_bytes < 0"); return -1; }
+    if (off) { b->seg_off.assign(off, off + b->S); b->seg_bytes = in_bytes; }
+    else { b->seg_off.clear(); b->seg_bytes = 0; }
+    return 0;
+}
+int check_segments(const hx_batch *b, int nframes, int sample_bytes, int first)
+{
+    if (!b || b->seg_off.empty()) return 0;
+    for (int i = 0; i < b->S; i++) {
+        const long long n = seg_len(b, i, nframes, sample_bytes), o = b->seg_off[i];
+        if (n <= 0) continue;
+        const char *what = o < 0 ? "is negative" : (o % sample_bytes) != 0 ? "is no multiple of the call's sample size" :
+                           (n > b->seg_bytes || o > b->seg_bytes - n) ? "ends beyond in_bytes" : nullptr;
+        if (what) {
+            char msg[192];
+            snprintf(msg, sizeof msg, "stream %d: PCM segment at offset %lld (%lld bytes, in_bytes = %lld) %s", first + i, o, n, b->seg_bytes, what);
+            set_err("%s", msg);
+            return -1;
+        }
+    }
+    return 0;
+}
+
 extern "C" long long hx_batch_dense_bound(const hx_batch *b, int nframes)
 {
     return b ? (long long) b->S * ((hx_batch_out_stride(b, nframes) + 15) & ~15LL) : 0;
@@ -520,6 +570,7 @@ struct Pass {
     int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
                                         // submit n-2 when the front end of submit n writes them: three sets in rotation)
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
+    const long long *d_seg = nullptr;   // under PCM segments: the device copy of the call's offsets, relative to in.p (upload_segments)
 };
 
 int order_behind_submits(hx_batch *b, hipStream_t q)
@@ -589,6 +640,38 @@ static int upload_counts(hx_batch *b, Pass &p)
     return p.kind == PASS_PLAIN ? counts_upload_plain(b, p.q, p.call.nfr) : counts_upload(b, p.sset, p.q, p.call.nfr);
 }
 
+// The call's PCM segments to the device, like its counts and in their rotation: through page-locked staging into copy k of
+// three on the stream the front end runs on, where k_pcm_spread - the only reader - follows.  The same two notes apply: the
+// host may wait for the upload of the call three before, and the call is not made under stream capture.  What goes up is
+// relative to the pointer the kernel gets (PcmIn::shift); the offset of a stream that takes no frame is not looked at.
+static int upload_segments(hx_batch *b, Pass &p)
+{
+    if (!p.in.seg) return 0;
+    Staging &s = b->seg_stage;
+    const int k = p.kind == PASS_PLAIN ? (int) (b->nplain_seg++ % 3) : p.sset;
+    long long *h = (long long *) staging_take(s, k);
+    if (!h) return -1;
+    for (int i = 0; i < b->S; i++) h[i] = seg_len(b, i, p.nframes, p.in.sample_bytes()) > 0 ? p.in.seg[i] - p.in.shift : 0;
+    if (staging_upload(s, k, s.bytes, p.q) != 0 || staging_done(s, k, p.q) != 0) return -1;
+    p.d_seg = s.dev<long long>(k);
+    return 0;
+}
+// ... and the row buffer of a call under segments, before the pass touches anything: made at the first such call, grown
+// behind a drain (an earlier call's front end may still read it)
+static int rows_reserve(hx_batch *b, PcmIn in, int nframes)
+{
+    const long long need = in.bytes(b->S, nframes, b->nchan);
+    const long long chunks = (in.bytes(1, nframes, b->nchan) + HX_PCM_CHUNK - 1) / HX_PCM_CHUNK;
+    if ((long long) b->S * chunks > INT_MAX) { set_err("nstreams * nframes too large for a call under PCM segments: split the call"); return -1; }
+    if (need <= b->rows_cap) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (b->rows_cap > 0 && drain(b) != 0) return -1;
+    b->rows_cap = 0;
+    if (dev_realloc(b, b->d_rows, need) != 0) return -1;
+    b->rows_cap = need;
+    return 0;
+}
+
 // the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]
 static int launch_front(hx_batch *b, const Pass &p)
 {
@@ -596,8 +679,18 @@ static int launch_front(hx_batch *b, const Pass &p)
     const hipStream_t q = p.q;
     const int S = b->S, nframes = p.nframes, NG = 2 * nframes;
     const long long nsamp = 1152LL * nframes;
-    const int16_t *d_pcm = p.in.f32 ? nullptr : (const int16_t *) p.in.p;
-    const float *d_pcm32 = p.in.f32 ? (const float *) p.in.p : nullptr;
+    // under segments: the rows come from k_pcm_spread (hx_pcmin.hip), and the kernels below read them in place of the caller's pointer
+    const void *pcm = p.in.p;
+    if (p.d_seg) {
+        const long long row_bytes = p.in.bytes(1, nframes, b->nchan);
+        const int chunks = (int) ((row_bytes + HX_PCM_CHUNK - 1) / HX_PCM_CHUNK);
+        LAUNCH(k_pcm_spread, dim3((unsigned) ((long long) S * chunks)), dim3(256), q, (const unsigned char *) p.in.p, p.d_seg, b->d_rows, row_bytes, nframes,
+               p.in.sample_bytes(), (const HxStream *) b->d_st, (const HxParams *) b->d_prm, p.call.nfr, chunks);
+        b->rows_bytes = row_bytes * S;
+        pcm = b->d_rows;
+    }
+    const int16_t *d_pcm = p.in.f32 ? nullptr : (const int16_t *) pcm;
+    const float *d_pcm32 = p.in.f32 ? (const float *) pcm : nullptr;
     // The subband carry sits in slots NG_prev..NG_prev+2 only if the previous call used another
     // frame count; k_msscan always rolls it to slots 0..2, so nothing to do here.
     dim3 g1(S, (NG + K1_GPB - 1) / K1_GPB);
@@ -766,11 +859,12 @@ static void reap_timings(hx_batch *b)
 
 int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
+    if (in.seg && rows_reserve(b, in, nframes) != 0) return -1;
     Poison poison{b};
     Pass p = {in, nframes, c, kind, (hipStream_t) stream, (hipStream_t) stream};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
-    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || launch_front(b, p) != 0) return -1;
+    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || upload_segments(b, p) != 0 || launch_front(b, p) != 0) return -1;
     if (kind != PASS_PLAIN && pipe_front_done(b, p) != 0) return -1;
     if (fill_alloc_args(b, p, a) != 0 || launch_walk(b, p, a) != 0 || place_pack(b, p) != 0) return -1;
     if (!c.recording) reap_timings(b);
@@ -784,20 +878,21 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream,
 }
 int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
-    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(b, c.opt, counts_in_force(b)) != 0) return -1;
+    if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(b, c.opt, counts_in_force(b)) != 0 ||
+        check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
     return encode_pass(b, in, nframes, c, stream, kind);
 }
 
 extern "C" int hx_batch_encode_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, false}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
+    return encode_checked(b, pcm_in(b, d_pcm, false), nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
 }
 
 extern "C" int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, true}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
+    return encode_checked(b, pcm_in(b, d_pcm, true), nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_PLAIN);
 }
 
 // Pipelined form of the device calls.  A submit returns at once like the plain call, but its output
@@ -809,13 +904,13 @@ extern "C" int hx_batch_encode_f32_device(hx_batch *b, const float *d_pcm, int n
 extern "C" int hx_batch_submit_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, false}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
+    return encode_checked(b, pcm_in(b, d_pcm, false), nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
 }
 
 extern "C" int hx_batch_submit_f32_device(hx_batch *b, const float *d_pcm, int nframes, unsigned char *d_out,
                                           long long out_stride, int *d_out_bytes, void *stream)
 {
-    return encode_checked(b, {d_pcm, true}, nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
+    return encode_checked(b, pcm_in(b, d_pcm, true), nframes, call_on(b, d_out, out_stride, d_out_bytes), stream, PASS_SUBMIT_DEVICE);
 }
 
 // share (percent) of the previous allocator launch's resident workgroups that must have started before a submit's front end is released; 0 = no gate
@@ -848,10 +943,16 @@ extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
 // image kernels of the call write them, and the rows stay in the staging: out is not used
 static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, const DenseOut *img = nullptr)
 {
-    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b, b->opt, counts_in_force(b)) != 0) return -1;
+    if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b, b->opt, counts_in_force(b)) != 0 ||
+        check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
+    // (under segments: the span of the image its segments cover, as in encode_host; the staging is sized by what goes up)
+    in = pcm_in(b, in.p, in.f32);
+    long long lo = 0, hi = in.bytes(b->S, nframes, b->nchan);
+    if (in.seg) seg_span(b, nframes, in.sample_bytes(), lo, hi);
+    if (in.seg && rows_reserve(b, in, nframes) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
-    const long long pbytes = in.bytes(b->S, nframes, b->nchan), obytes = (long long) b->S * out_stride;
+    const long long pbytes = hi - lo, obytes = (long long) b->S * out_stride;
     if (!b->s_h2d) {
         if (new_stream(b, b->s_h2d) || new_stream(b, b->s_d2h) || new_stream(b, b->s_host)) return -1;
         for (int i = 0; i < 2; i++)
@@ -873,13 +974,15 @@ static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, l
         HIPCHK(hipStreamWaitEvent(b->s_h2d, b->ev_hfront[k], 0));   // the front end of call n-2 has read this PCM buffer
         HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_d2h[k], 0));     // the bitstream of call n-2 has left this output buffer
     }
-    HIPCHK(hipMemcpyAsync(b->hs_pcm[k], in.p, (size_t) pbytes, hipMemcpyHostToDevice, b->s_h2d));
+    if (pbytes > 0) HIPCHK(hipMemcpyAsync(b->hs_pcm[k], (const char *) in.p + lo, (size_t) pbytes, hipMemcpyHostToDevice, b->s_h2d));
     HIPCHK(hipEventRecord(b->ev_h2d[k], b->s_h2d));
     HIPCHK(hipStreamWaitEvent(b->s_host, b->ev_h2d[k], 0));
     const int set = (int) (b->nsubmit & 1);
     Call c = call_on(b, b->hs_out[k], out_stride, b->hs_nb[k]);
     if (img) c.opt.dense = DenseOut{img->buf, img->cap, b->hs_off[k], img->off};
-    if (encode_pass(b, {b->hs_pcm[k], in.f32}, nframes, c, b->s_host, PASS_SUBMIT_HOST) != 0) return -1;
+    PcmIn up = in;
+    up.p = b->hs_pcm[k]; up.shift = lo;
+    if (encode_pass(b, up, nframes, c, b->s_host, PASS_SUBMIT_HOST) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_hfront[k], b->s_front));
     HIPCHK(hipStreamWaitEvent(b->s_d2h, b->ev_alloc[set], 0));
     HIPCHK(hipMemcpyAsync(out_bytes, b->hs_nb[k], sizeof(int) * b->S, hipMemcpyDeviceToHost, b->s_d2h));
@@ -979,8 +1082,15 @@ int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long lon
 {
     if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes) != 0) return -1;
     if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
-    return host_call(b, in.p, in.bytes(b->S, nframes, b->nchan), false, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
-        return encode_pass(b, {b->d_in, in.f32}, nframes, c, nullptr, PASS_PLAIN);
+    if (check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
+    // under segments one span of the image goes up, from the lowest segment start to the highest segment end; rows: all of them
+    in = pcm_in(b, in.p, in.f32);
+    long long lo = 0, hi = in.bytes(b->S, nframes, b->nchan);
+    if (in.seg) seg_span(b, nframes, in.sample_bytes(), lo, hi);
+    return host_call(b, (const char *) in.p + lo, hi - lo, false, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
+        PcmIn up = in;
+        up.p = b->d_in; up.shift = lo;
+        return encode_pass(b, up, nframes, c, nullptr, PASS_PLAIN);
     }, hd, crc);
 }
 
@@ -1123,6 +1233,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
     else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
     else if (k == "srcpcm" && b->d_src_pcm) { src = b->d_src_pcm; n = sizeof(float) * S * b->src_lastF * 1152 * b->nchan; }   // the converted PCM of the last call
+    else if (k == "pcmrows" && b->d_rows) { src = b->d_rows; n = b->rows_bytes; }      // the row buffer as the last call under PCM segments left it (its stride: that call's nframes and sample type)
     else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 4; }      // [S][NG][4]: the attack metric of channel 0 / 1 for short_flag_prev = 0, then for 1
     if (!src) return -1;
     if (n > cap) n = cap;

@@ -316,6 +316,18 @@ extern "C" int hx_multi_frame_counts(hx_multi *m, const int *nfr)
     return 0;
 }
 
+// hx_batch_pcm_segments over all streams, the same way: every block's batch takes its streams' offsets, which address the
+// caller's one image - so every block keeps the image's size, and its calls get the image's base (multi_encode_host).
+extern "C" int hx_multi_pcm_segments(hx_multi *m, const long long *off, long long in_bytes)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    if (off && in_bytes < 0) { set_err("in_bytes < 0"); return -1; }
+    for (hx_batch *b : m->part) if (segs_reserve(b, off != nullptr) != 0) return -1;
+    for (size_t k = 0; k < m->part.size(); k++)
+        if (hx_batch_pcm_segments(m->part[k], off ? off + m->first[k] : nullptr, in_bytes) != 0) return -1;     // (cannot fail any more)
+    return 0;
+}
+
 // Argument checks of the calls over all devices, the per-stream frame counts of every block included: a call that one
 // block would refuse for its counts starts on no block, and its message names the stream by the caller's number.
 // Then fn(k) on one thread per device, bound to the CPUs next to it.
@@ -362,9 +374,16 @@ static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *
                              unsigned short *crc = nullptr)
 {
     if (m && multi_check_opt(m, stats, crc, nullptr) != 0) return -1;
+    // PCM segments: checked for all blocks, with the caller's stream numbers, before one starts - behind the counts, which
+    // a segment's length comes from (an nframes out of range is multi_fanout's to refuse); each block then gets the image's
+    // base and copies its own span
+    const bool segs = m && !m->part[0]->seg_off.empty();
+    if (segs && nframes > 0 && nframes <= m->part[0]->maxF)
+        for (size_t k = 0; k < m->part.size(); k++)
+            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_segments(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
     return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
         const long long f = m->first[k];
-        const char *p = (const char *) in.p + in.bytes(f, nframes, m->nchan);
+        const char *p = (const char *) in.p + (segs ? 0 : in.bytes(f, nframes, m->nchan));
         return encode_host(m->part[k], {p, in.f32}, nframes, out + f * out_stride, out_stride, out_bytes + f, stats ? stats + f * nframes * 2 : nullptr,
                            nullptr, crc ? crc + f * nframes : nullptr);
     });

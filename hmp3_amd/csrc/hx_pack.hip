@@ -506,3 +506,6 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
 
 // ---- the file ledger (hx_batch_ledger_*): k_ledger*, a file of its own, built as part of this unit (behind hx_crc.hip) ----
 #include "hx_ledger.hip"
+
+// ---- PCM segments (hx_batch_pcm_segments): k_pcm_spread, a file of its own, built as part of this unit ----
+#include "hx_pcmin.hip"

@@ -27,7 +27,7 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 
 #ifdef __HIPCC__
-// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip, hx_slots.hip and hx_ledger.hip / hx_src.hip)
+// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip, hx_slots.hip, hx_ledger.hip and hx_pcmin.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
 // nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
 // frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
@@ -64,6 +64,8 @@ __global__ void k_slot_scatter(SlotArgs a, const uint2 *blobs);
 __global__ void k_ledger(HX_LEDGER *led, const int *stats, const unsigned short *crc, const int *out_bytes, const int *nfr, int nframes, int S);
 __global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent);
 __global__ void k_ledger_gather(const HX_LEDGER *led, const HxLedgerEntry *ent, HX_LEDGER *out);
+__global__ void k_pcm_spread(const unsigned char *img, const long long *off, unsigned char *rows, long long row_bytes, int nframes, int sample_bytes,
+                             const HxStream *st, const HxParams *prm, const int *nfr, int chunks);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_order_kinds(const unsigned *dur, const HxStream *st, const HxParams *prm, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
@@ -176,6 +178,17 @@ struct hx_batch {
     std::vector<int> nfr;
     Staging nfr_stage;
     long long nplain = 0;               // plain calls made under counts (they rotate the copies too: no call waits for its predecessor's upload)
+    // PCM segments (hx_batch_pcm_segments): the host copy a call checks and takes - seg_off [S] byte offsets into the call's
+    // image of seg_bytes bytes, empty = rows - and its staging, [S] offsets per copy, in the rotation of the counts' (a
+    // submit: the copy of its set of signs; plain calls: their own count, nplain_seg).  d_rows: the row buffer k_pcm_spread
+    // fills and the front end reads in place of the caller's pointer, [S][nframes * 1152 * P] samples of the call's type; one
+    // for all pass kinds (the front end's stream is in order), made at the first call under segments and grown behind a
+    // drain.  rows_bytes: what the last call under segments used of it (the "pcmrows" tap).
+    std::vector<long long> seg_off;
+    long long seg_bytes = 0;
+    Staging seg_stage;
+    long long nplain_seg = 0;
+    unsigned char *d_rows = nullptr; long long rows_cap = 0, rows_bytes = 0;
     // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
     int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
     std::vector<HxSrcPlan> src_plans;
@@ -351,10 +364,39 @@ struct Poison {
 HX_LOCAL int check_poisoned(const hx_batch *b);
 
 // the PCM of a pass: int16, or fp32 at int16 scale; bytes: of nframes frames of S streams
+// Under PCM segments (pcm_in): p is not rows but an image, seg [S] the host's byte offsets of the streams' segments in the
+// caller's image as of the call, and p stands for byte `shift` of that image - a device call's p is the image's base, a host
+// call copies up only the span its segments cover (seg_span) and shifts by the span's start.
 struct PcmIn {
     const void *p; bool f32;
-    long long bytes(long long S, int nframes, int nchan) const { return S * nframes * 1152 * nchan * (long long) (f32 ? sizeof(float) : sizeof(int16_t)); }
+    const long long *seg = nullptr; long long shift = 0;
+    int sample_bytes() const { return f32 ? (int) sizeof(float) : (int) sizeof(int16_t); }
+    long long bytes(long long S, int nframes, int nchan) const { return S * nframes * 1152 * nchan * (long long) sample_bytes(); }
 };
+// a call's PCM argument as the batch takes it now: rows, or the segments in force
+static inline PcmIn pcm_in(const hx_batch *b, const void *p, bool f32)
+{
+    PcmIn in = {p, f32};
+    if (b && !b->seg_off.empty()) in.seg = b->seg_off.data();
+    return in;
+}
+// bytes of stream i's segment in a call of nframes: its count in force (or nframes) x 1152 x its channels as of now x sample_bytes
+static inline long long seg_len(const hx_batch *b, int i, int nframes, int sample_bytes)
+{
+    return (long long) (b->nfr.empty() ? nframes : b->nfr[i]) * 1152 * b->params[b->cls_of[i]].nchan * sample_bytes;
+}
+// [lo, hi): from the lowest segment start to the highest segment end among the streams that take frames (none: lo = hi = 0)
+static inline void seg_span(const hx_batch *b, int nframes, int sample_bytes, long long &lo, long long &hi)
+{
+    lo = LLONG_MAX; hi = 0;
+    for (int i = 0; i < b->S; i++) {
+        const long long n = seg_len(b, i, nframes, sample_bytes);
+        if (n <= 0) continue;
+        lo = std::min(lo, b->seg_off[i]);
+        hi = std::max(hi, b->seg_off[i] + n);
+    }
+    if (lo > hi) lo = hi = 0;
+}
 // a call that writes the caller's rows and the optional outputs set on the batch (a null batch: the argument checks refuse it)
 static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_stride, int *out_bytes)
 {
@@ -379,6 +421,13 @@ HX_LOCAL int counts_reserve(hx_batch *b, bool buffers);
 // device copy it went to) - the converting calls under counts (hx_batch_src.hip), whose k_src reads the counts before the pass
 HX_LOCAL int counts_buffers(hx_batch *b);
 HX_LOCAL int counts_upload_plain(hx_batch *b, hipStream_t q, const int *&d_nfr);
+// PCM segments.  segs_reserve: what hx_batch_pcm_segments needs before it can set segments, and nothing else of it (hx_multi:
+// all blocks, then set all) - whether the batch takes them at all and (buffers) at the first use their staging.
+// check_segments: the segments in force against a call of nframes and this sample size, per stream that takes frames, before
+// anything is allocated, copied or launched (none in force: 0); first: as for check_counts.  The counts in force must have
+// passed check_counts.
+HX_LOCAL int segs_reserve(hx_batch *b, bool buffers);
+HX_LOCAL int check_segments(const hx_batch *b, int nframes, int sample_bytes, int first);
 // ... and the range check of counts that come as a call's argument (first: as for check_counts)
 HX_LOCAL int check_counts_arg(const int *nfr, int S, int nframes, int first);
 // A converting call's input extents against its rows, per stream under its count (nfr null: nframes), before anything runs;
@@ -478,7 +527,7 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     if (hd && (dev_grow(b, b->d_dense, b->dense_cap, std::max(16LL, std::min(hd->cap, hd->bound))) ||
                (!b->d_dense_off && dev_alloc(b, b->d_dense_off, (long long) sizeof(long long) * (b->S + 1))))) return -1;
     if (drain_first && drain(b) != 0) return -1;
-    HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));
+    if (in_bytes > 0) HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));    // (0: a call under segments of which no stream takes a frame)
     Call c = call_on(b, b->d_out, out_stride, b->d_outbytes);
     if (stats) c.opt.frame_stats = b->d_stats;
     if (crc) c.opt.crc = b->d_crc;

@@ -206,6 +206,9 @@ struct alignas(16) HxFrameOut {
 // The dense image (hx_batch_dense_buffers): a workgroup of k_dense_gather (hx_pack.hip) moves this many bytes of one row -
 // 256 lanes x 4 vectors of 16 bytes; the host sizes the grid with it from the worst-case row.
 #define HX_DENSE_CHUNK 16384
+// PCM segments (hx_batch_pcm_segments): a workgroup of k_pcm_spread (hx_pcmin.hip) moves this many bytes of one segment, the
+// same way; the host sizes the grid with it from the call's row.
+#define HX_PCM_CHUNK 16384
 
 // Slots of a batch's counter block (AllocArgs::done_counter; the host runtime reads some of them and hands two to k_gate and k_pack).
 enum HxCounter {

@@ -240,7 +240,7 @@ int hx_batch_assign_streams(hx_batch *b, const int *idx, const int *cfg, int n, 
    Sizing: everything create sizes from the configurations is taken over the whole menu as for any menu (hx_batch_out_stride,
    the DC blocker's staging, hx_batch_src_in_stride, the converter's LDS layout, the choice of the stream-walk build); what is
    sized by a channel count is sized by P.  A host-fed mono stream of a P = 2 batch therefore moves the unused half of its
-   row over the link with the rest.
+   row over the link with the rest (unless the call is fed an image: "PCM segments" below).
    hx_batch_assign_streams / hx_multi_assign_streams move a slot between a mono and a stereo entry under their contract above,
    unchanged: from its next frame on the slot produces exactly the bytes of slot 0 of a new batch created with that entry -
    rows, out_bytes, packets, frame counters, MusicCRC, dense image and checkpoint blob (but for the class index word).
@@ -409,6 +409,41 @@ int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, uns
    contract); this setter returns -1 on a converting batch.
    Not covered: the hx_enc_* encoder, and bench.py, which measures uniform calls. */
 int hx_batch_frame_counts(hx_batch *b, const int *nfr);
+/* ---- PCM segments: a call's input packed back to back, spread on the GPU (no reference equivalent) ----
+   The rows [nstreams][nframes * 1152 * P] are sized for the worst case: a stream that takes fewer frames than the call, or
+   that is mono in a P = 2 batch, still has a full row, and a host call copies all of it.  With segments in force the
+   `pcm` / `d_pcm` argument of every encode and submit entry point of the batch is instead the base of one image of
+   in_bytes bytes, and stream i's input is the len_i bytes at pcm + off[i], in the order its row would hold them:
+     len_i = n_i * 1152 * ch_i * sample size, n_i = the frame count in force (hx_batch_frame_counts) or nframes,
+     ch_i = hx_batch_stream_channels(b, i) as of the call, interleaved for a stereo stream.
+   A kernel at the head of the call's front end (k_pcm_spread) copies the segments into a row buffer the batch owns
+   (nstreams * nframes * 1152 * P samples of the call's type, made at the first call under segments), and the front end
+   reads that: everything a call writes or leaves in the stream state is exactly what the same call writes when fed rows
+   holding the same samples.  Device calls read the caller's image where it lies.
+   hx_batch_pcm_segments: off is a HOST array [nstreams], copied by the function; NULL switches back to rows.  Returns
+   0 / -1; sticky like hx_batch_frame_counts: a call takes the segments in force when it is made, and a submit's stay its
+   own whatever is set afterwards.  It either sets the segments or (-1) changes nothing, and leaves the calling thread's
+   current device alone.  Honoured by every encode and submit entry point of a plain batch: device and host buffers, s16
+   and f32, *_stats, *_crc, *_host_dense, submit_*.  A converting batch returns -1: its input is per stream already.
+   A call is refused (-1, hx_last_error names the stream) before anything is allocated, copied or launched, and the batch
+   stays usable, unless for every stream with n_i > 0: off[i] >= 0, off[i] is a multiple of the call's sample size, and
+   off[i] + len_i <= in_bytes.  off[i] of a stream with n_i = 0 is not looked at.
+   Segments may leave gaps, come in any order and overlap (they are only read).  No 16-byte alignment is asked of the
+   offsets or of a device image's base: a file's data chunk 44 bytes into a buffer is a valid segment start.
+   Host calls copy one span of the image up: from the lowest segment start to the highest segment end among the streams
+   that take frames.  Gaps inside the span cross the link with it, so a caller who wants minimal traffic packs tight:
+   hx_pcm_packed_layout.  hx_batch_submit_*_host size their staging by the span.
+   The offsets travel to the device through page-locked staging in rotation, as the counts do, with the same two notes:
+   a call under segments may wait on the host for the upload of the third call before it, and it cannot be made while
+   its stream is being captured into a graph.  Calls without segments do neither.
+   hx_pcm_packed_layout: pure host code, no batch and no device.  The tight layout: off[0] = 0, off[i + 1] = off[i] + len_i
+   with n_i = nfr ? nfr[i] : nframes and ch_i = channels[i]; sample_bytes is 2 or 4; off has nstreams + 1 entries.
+   Returns off[nstreams], the image's size, or -1 for bad arguments: a null off or channels, a channel count other than 1
+   or 2, a sample size other than 2 or 4, a count outside 0 .. nframes.  Every len_i is a multiple of 2304, so the tight
+   layout is 16-byte aligned without padding.
+   Not covered: converting batches, the hx_enc_* encoder, and bench.py, which measures calls fed rows. */
+long long hx_pcm_packed_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off);
+int hx_batch_pcm_segments(hx_batch *b, const long long *off, long long in_bytes);
 /* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
    The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
    gathers them on the GPU, behind its packing, into one image.  With nb[i] = out_bytes[i]:
@@ -654,6 +689,10 @@ int hx_multi_encode_f32_host_crc(hx_multi *m, const float *pcm, int nframes, uns
 /* [nstreams] over all blocks; fanned out to the blocks' batches, all of them or (-1) none.  A call whose counts do not fit
    its nframes is refused for all blocks before any of them starts, and hx_last_error names the stream by its number here */
 int hx_multi_frame_counts(hx_multi *m, const int *nfr);
+/* hx_batch_pcm_segments over all blocks ("PCM segments" above): off [nstreams] addresses the caller's ONE image of in_bytes
+   bytes, whose base every hx_multi_encode_*_host* call then takes as pcm; each block copies only its own streams' span.
+   All blocks or (-1) none.  A call's segment checks run for all blocks, with the caller's stream numbers, before any block starts */
+int hx_multi_pcm_segments(hx_multi *m, const long long *off, long long in_bytes);
 int hx_multi_status(hx_multi *m);
 /* converting batches (hx_batch_create_src) in the same blocks: in [nstreams][in_stride], frame_off [nstreams][nframes] or NULL,
    in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
@@ -688,7 +727,9 @@ int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long l
    order ran: XCC id << 16 | HW_ID[15:0], i.e. CU [11:8], SH [12], SE [15:13]), "state", and two device counters (one int
    each, running over the batch's calls): "big_sweeps" = noise passes that took the double-precision x^(4/3) table,
    "strict_sums" = certified band sums that fell back to the reference's strict line-order sum (DESIGN.md section 2;
-   HMP3AMD_EXACT_SUMS=1 sends every sum there).  Copies at most cap bytes, returns bytes, -1 for an unknown name. */
+   HMP3AMD_EXACT_SUMS=1 sends every sum there), and "pcmrows" (the row buffer as the last call under PCM segments left it,
+   [nstreams][that call's nframes * 1152 * P] samples of its type; -1 before the first such call).  Copies at most cap
+   bytes, returns bytes, -1 for an unknown name. */
 long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap);
 void hx_batch_debug_enable(hx_batch *b, int on);
 /* The first-generation allocator (intensity stereo, dual channel; reference bitallo1.cpp) calls libm's logf / log10f, which
