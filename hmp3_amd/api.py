@@ -56,6 +56,15 @@ class Ledger(C.Structure):
         return bytes(memoryview(self))
 
 
+class LedgerBrief(C.Structure):
+    """HX_LEDGER_BRIEF: the short form of a record, with the slot's image_bytes (include/hmp3_amd.h, "file images")"""
+    _fields_ = [(n, C.c_int) for n in ("open", "ended", "fed")] + [(n, C.c_uint) for n in ("frames", "bytes", "crc")] + \
+        [("call_bytes", C.c_int), ("image_bytes", C.c_uint)]
+
+    def tobytes(self):
+        return bytes(memoryview(self))
+
+
 class LedgerOpen(C.Structure):
     """HX_LEDGER_OPEN: what hx_batch_ledger_begin takes per listed slot"""
     _fields_ = [(n, C.c_int) for n in ("ncalls", "head_bytes", "flags", "reserved")]
@@ -68,7 +77,7 @@ CTYPES = {
     "long long": C.c_longlong, "unsigned long long": C.c_ulonglong, "float": C.c_float, "void": None,
     "HX_IN_OUT": InOut, "HX_INT_PAIR": IntPair, "const char *": C.c_char_p,
     "hx_batch *": C.c_void_p, "hx_enc *": C.c_void_p, "hx_multi *": C.c_void_p, "hx_src *": C.c_void_p,
-    "hx_xing *": C.c_void_p, "void *": C.c_void_p,
+    "hx_xing *": C.c_void_p, "void *": C.c_void_p, "unsigned char *": C.c_void_p,
 }
 HEADER = os.path.join(os.path.dirname(HERE), "include", "hmp3_amd.h")
 
@@ -205,6 +214,44 @@ def ledger_update(rec, stats, crc, out_bytes):
     if len(cr) != len(st):
         raise ValueError("%d frame counters and %d CRCs" % (len(st), len(cr)))
     return bool(lib().hx_ledger_update(C.byref(rec), st.ctypes.data, cr.ctypes.data, len(st), int(out_bytes)))
+
+
+def ledger_brief(rec, image_bytes=0):
+    """the short form of a record, on the host (hx_ledger_brief)"""
+    out = LedgerBrief()
+    lib().hx_ledger_brief(C.byref(rec), int(image_bytes), C.byref(out))
+    return out
+
+
+def _ledger_poll(fn, handle, n):
+    out = (LedgerBrief * n)()
+    if fn(handle, out) != 0:
+        raise RuntimeError("%s failed: %s" % (fn.__name__, last_error()))
+    return [LedgerBrief.from_buffer_copy(out[e]) for e in range(n)]
+
+
+def _file_fetch(fn, handle, i, cap, fill):
+    """-> the file's bytes as fetched into a buffer of cap bytes pre-filled with `fill` (the tag's bytes keep the fill)"""
+    buf = np.full(max(int(cap), 1), fill, dtype=np.uint8)
+    n = int(fn(handle, int(i), buf.ctypes.data, int(cap)))
+    if n < 0:
+        raise RuntimeError("%s failed: %s" % (fn.__name__, last_error()))
+    return buf[:n].tobytes()
+
+
+def _files_status(name, r):
+    if r < 0:
+        raise RuntimeError("%s failed: %s" % (name, last_error()))
+    return int(r)
+
+
+def _encode_src_files_host(fn, handle, n, rows, nframes, counts, frame_off):
+    rows = np.ascontiguousarray(rows, dtype=np.uint8)
+    assert rows.ndim == 2 and rows.shape[0] == n
+    off = None if frame_off is None else np.ascontiguousarray(frame_off, dtype=np.int64)
+    used = np.zeros(n, dtype=np.int64)
+    r = fn(handle, rows.ctypes.data, rows.shape[1], None if off is None else off.ctypes.data, nframes, _counts_array(n, counts), used.ctypes.data)
+    return _files_status(fn.__name__, r), used
 
 
 def xing_load_points(xing_handle, rec):
@@ -612,6 +659,44 @@ class Batch:
         if lib().hx_batch_ledger_read_device(self.h, arr, n, d_out_ptr, stream) != 0:
             raise RuntimeError("hx_batch_ledger_read_device failed: " + last_error())
 
+    def file_images(self, cap):
+        """file images of cap bytes per slot on, or off with cap = 0 (hx_batch_file_images); refused while a record is live"""
+        if lib().hx_batch_file_images(self.h, int(cap)) != 0:
+            raise RuntimeError("hx_batch_file_images failed: " + last_error())
+
+    def file_image_cap(self):
+        return int(lib().hx_batch_file_image_cap(self.h))
+
+    def file_image_ptr(self, i):
+        """the device address of slot i's image (None: images off)"""
+        return lib().hx_batch_file_image_ptr(self.h, int(i))
+
+    def ledger_poll(self):
+        """the short form of every slot's record, synchronous: one launch, one copy -> list of LedgerBrief"""
+        return _ledger_poll(lib().hx_batch_ledger_poll, self.h, self.n)
+
+    def ledger_poll_device(self, d_out_ptr, stream=None):
+        """the same into device memory [n] HX_LEDGER_BRIEF (16-byte aligned), asynchronous on `stream`"""
+        if lib().hx_batch_ledger_poll_device(self.h, d_out_ptr, stream) != 0:
+            raise RuntimeError("hx_batch_ledger_poll_device failed: " + last_error())
+
+    def file_fetch(self, i, cap, fill=0):
+        """slot i's file (hx_batch_file_fetch) -> bytes: head_bytes of `fill`, which the call leaves alone, then the audio"""
+        return _file_fetch(lib().hx_batch_file_fetch, self.h, i, cap, fill)
+
+    def encode_host_files(self, pcm):
+        """encode_host that brings nothing down but the status (hx_batch_encode_*_host_files) -> the status bits"""
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        return self._encode_host_files(pcm, nfr)
+
+    def encode_host_files_image(self, image, nframes):
+        """encode_host_files under pcm_segments: a flat image plus nframes, as encode_host_image"""
+        return self._encode_host_files(_pcm_image(image), int(nframes))
+
+    def _encode_host_files(self, pcm, nfr):
+        fn = lib().hx_batch_encode_f32_host_files if pcm.dtype == np.float32 else lib().hx_batch_encode_s16_host_files
+        return _files_status(fn.__name__, fn(self.h, pcm.ctypes.data, nfr))
+
     def get_stream_states(self, idx):
         """checkpoints of the streams in idx, one launch and one copy -> list of bytes, blob e of slot idx[e]"""
         arr, n = self._slots(idx)
@@ -777,6 +862,11 @@ class SrcBatch(Batch):
         return _encode_src_counts_host(lib().hx_batch_encode_src_counts_host, self.h, self.n, self.out_stride(nframes), rows, nframes,
                                        counts, frame_off, stats, crc)
 
+    def encode_src_files_host(self, rows, nframes, counts=None, frame_off=None):
+        """encode_src_counts_host that brings nothing down but the status (hx_batch_encode_src_files_host)
+        -> (the status bits, in_used int64 [n])"""
+        return _encode_src_files_host(lib().hx_batch_encode_src_files_host, self.h, self.n, rows, nframes, counts, frame_off)
+
     def encode_src_counts_device(self, d_in_ptr, in_stride, nframes, counts, d_out_ptr, out_stride, d_out_bytes_ptr, frame_off=None, stream=None):
         """the device call (hx_batch_encode_src_counts_device): counts and frame_off are host arrays as above, the buffers
         device pointers; asynchronous on stream -> in_used int64 [n]"""
@@ -900,6 +990,32 @@ class Multi:
             raise RuntimeError("hx_multi_ledger_read failed: " + last_error())
         return [Ledger.from_buffer_copy(out[e]) for e in range(n)]
 
+    def file_images(self, cap):
+        """as Batch.file_images over all blocks; all blocks or (RuntimeError) none (hx_multi_file_images)"""
+        if lib().hx_multi_file_images(self.h, int(cap)) != 0:
+            raise RuntimeError("hx_multi_file_images failed: " + last_error())
+
+    def ledger_poll(self):
+        """as Batch.ledger_poll over all blocks (hx_multi_ledger_poll)"""
+        return _ledger_poll(lib().hx_multi_ledger_poll, self.h, self.n)
+
+    def file_fetch(self, i, cap, fill=0):
+        """as Batch.file_fetch, i over all blocks (hx_multi_file_fetch)"""
+        return _file_fetch(lib().hx_multi_file_fetch, self.h, i, cap, fill)
+
+    def encode_host_files(self, pcm):
+        """as Batch.encode_host_files, over all streams"""
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.batch(0)))
+        return self._encode_host_files(pcm, nfr)
+
+    def encode_host_files_image(self, image, nframes):
+        """as Batch.encode_host_files_image, over all streams"""
+        return self._encode_host_files(_pcm_image(image), int(nframes))
+
+    def _encode_host_files(self, pcm, nfr):
+        fn = lib().hx_multi_encode_f32_host_files if pcm.dtype == np.float32 else lib().hx_multi_encode_s16_host_files
+        return _files_status(fn.__name__, fn(self.h, pcm.ctypes.data, nfr))
+
     def ndevices(self):
         return int(lib().hx_multi_ndevices(self.h))
 
@@ -1017,6 +1133,10 @@ class SrcMulti(Multi):
         if r != 0:
             raise RuntimeError("hx_multi_encode_src_host failed: " + last_error())
         return [out[i, :nb[i]].tobytes() for i in range(self.n)], used
+
+    def encode_src_files_host(self, rows, nframes, counts=None, frame_off=None):
+        """as SrcBatch.encode_src_files_host, over all streams (hx_multi_encode_src_files_host)"""
+        return _encode_src_files_host(lib().hx_multi_encode_src_files_host, self.h, self.n, rows, nframes, counts, frame_off)
 
     def encode_src_counts_host(self, rows, nframes, counts, frame_off=None, stats=False, crc=False):
         """as SrcBatch.encode_src_counts_host, over all streams (hx_multi_encode_src_counts_host)"""

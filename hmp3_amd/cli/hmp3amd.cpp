@@ -256,7 +256,9 @@ struct Job {
     int nch = 0;                        // channels the file encodes to (mono, or stereo summed to mono: 1)
     size_t nc = 0;                      // calls of the single-file loop on the file's input (the drain follows them)
     std::vector<long long> start;       // converting route: where each of them starts in the file's bytes
-    std::vector<unsigned char> stream;
+    std::vector<unsigned char> stream;  // the file's audio bytes; whole: the output file as fetched from its file image, the tag frame's
+    bool whole = false;                 // room in front
+    size_t est_calls = 0;               // -slots: an upper bound of nc from the header alone (0: the header does not say)
     HX_LEDGER led = {};                 // the file's record as last read from the batch's ledger: calls fed, frames / bytes out so far,
                                         // the MusicCRC of those bytes, the seek points; ended: the drain has ended, it takes no more frames
 };
@@ -490,6 +492,11 @@ int encode_batch(const std::vector<const char *> &files, const Options &opt)
         const bool ok = open_input(files[2 * i], opt, &jobs[i].in, &f, &indatasize);
         if (f && f != stdin) fclose(f);
         if (!ok) return 1;
+        // what the file's image must hold at most: its sample frames at the highest rate an encoder runs at, in blocks of 1152,
+        // and the calls on the zero bytes behind them
+        const WavInfo &wi = jobs[i].in.wi;
+        if (indatasize != UINT64_MAX)
+            jobs[i].est_calls = (size_t) (indatasize / (uint64_t) (wi.channels * (wi.bits / 8)) * 48000 / (uint64_t) wi.rate / 1152) + 16;
     }
     return encode_jobs(jobs, files, opt, opt.nslots <= 0);
 }
@@ -537,8 +544,15 @@ bool job_write(Job &j, const char *name, const Options &opt)
     if (opt.xing_flag) tg.finish(in, frames, out_bytes);
     FILE *o = fopen(name, "wb");
     if (!o) { fprintf(stderr, "\n CANNOT CREATE OUTPUT FILE %s\n", name); return false; }
-    fwrite(tg.tag.data(), 1, tg.head_bytes, o);
-    fwrite(j.stream.data(), 1, nbytes, o);
+    if (j.whole) {
+        // (the file came down once, from its image on the GPU, behind room for the tag frame)
+        if (j.stream.size() != (size_t) out_bytes) { fprintf(stderr, "\n %s: the file image holds %zu bytes of %llu\n", name, j.stream.size(), (unsigned long long) out_bytes); ok = false; }
+        else memcpy(j.stream.data(), tg.tag.data(), (size_t) tg.head_bytes);
+        fwrite(j.stream.data(), 1, std::min<size_t>(j.stream.size(), (size_t) out_bytes), o);
+    } else {
+        fwrite(tg.tag.data(), 1, tg.head_bytes, o);
+        fwrite(j.stream.data(), 1, nbytes, o);
+    }
     fclose(o);
     fprintf(stderr, "\n %s: %u frames, %llu bytes", name, frames, (unsigned long long) out_bytes);
     return ok;
@@ -624,6 +638,27 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     // file's record begins when the file gets its slot, and after each call the records of the slots that took frames come down
     std::vector<HX_LEDGER_OPEN> take_open(NS);
     std::vector<HX_LEDGER> led(NS);
+    // File images: the bytes the ledger gives to a file are put behind the file's bytes so far in the slot's image on the GPU
+    // (k_file_append), so a call brings down its status and one short record per slot, and a file comes down once, when it
+    // has ended.  An image holds the largest file of the run at the bound of hx_multi_out_stride: every block it is fed, the
+    // drain's included, at the size of the largest frames a block can yield, behind the tag frame.  Where the device cannot
+    // hold that for every slot, the rows come back with every call as before.
+    bool use_img = true;
+    {
+        size_t most = 0;
+        for (const Job &j : jobs) {
+            const size_t calls = loaded ? j.nc : j.est_calls;
+            use_img = use_img && calls > 0;
+            most = std::max(most, calls);
+        }
+        const long long cap = 2048 + (long long) (most + DRAIN) * hx_multi_out_stride(b, 1);
+        if (!use_img) fprintf(stderr, "\n an input's length is not known in advance: no file images, every call's rows come back");
+        else if (hx_multi_file_images(b, cap) != 0) {
+            fprintf(stderr, "\n no file images of %lld bytes per slot (%s): every call's rows come back", cap, hx_last_error());
+            use_img = false;
+        }
+    }
+    std::vector<HX_LEDGER_BRIEF> brief(NS);
     for (int s = 0; s < NS; s++) { fed_slot.push_back(s); take_open[s] = job_ledger(jobs[s], opt); }
     if (hx_multi_ledger_begin(b, fed_slot.data(), take_open.data(), NS) != 0) {
         fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
@@ -670,8 +705,22 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             if (p0 < j.nc) memcpy(row, j.in.data.data() + base, (size_t) std::min<long long>(row_data, (long long) j.in.data.size() - base));
             for (int k = 0; k < nf; k++) off[(size_t) s * nf + k] = (k < cnt[s] && p0 + k < j.nc) ? j.start[p0 + k] - base : row_data;
         }
-        const int rc_call = conv ? hx_multi_encode_src_counts_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), out.data(), stride, nb.data(), nullptr, stats.data(), crc.data())
-                                 : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_pcm_segments(b, seg.data(), image) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
+        int rc_call;
+        if (!use_img)
+            rc_call = conv ? hx_multi_encode_src_counts_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), out.data(), stride, nb.data(), nullptr, stats.data(), crc.data())
+                           : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_pcm_segments(b, seg.data(), image) != 0 || hx_multi_encode_f32_host_crc(b, pcm.data(), nf, out.data(), stride, nb.data(), stats.data(), crc.data()) != 0);
+        else {
+            // (the call's return value is the status word: a file that outgrew its image ends the run, anything else is
+            // reported at the end as before)
+            rc_call = conv ? hx_multi_encode_src_files_host(b, rows.data(), in_stride, off.data(), nf, cnt.data(), nullptr)
+                           : (hx_multi_frame_counts(b, cnt.data()) != 0 || hx_multi_pcm_segments(b, seg.data(), image) != 0) ? -1 : hx_multi_encode_f32_host_files(b, pcm.data(), nf);
+            if (rc_call > 0 && (rc_call & 64)) {
+                fprintf(stderr, "\n ENCODE FAIL: a file outgrew its image on the GPU\n");
+                hx_multi_destroy(b);
+                return 1;
+            }
+            if (rc_call > 0) rc_call = 0;
+        }
         if (rc_call != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
@@ -679,7 +728,7 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
         }
         take_slot.clear(); take_cfg.clear(); take_open.clear(); fed_slot.clear();
         for (int s = 0; s < NS; s++) if (cnt[s] > 0) fed_slot.push_back(s);
-        if (hx_multi_ledger_read(b, fed_slot.data(), (int) fed_slot.size(), led.data()) != 0) {
+        if ((use_img ? hx_multi_ledger_poll(b, brief.data()) : hx_multi_ledger_read(b, fed_slot.data(), (int) fed_slot.size(), led.data())) != 0) {
             fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
             hx_multi_destroy(b);
             return 1;
@@ -687,9 +736,25 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
         for (size_t e = 0; e < fed_slot.size(); e++) {
             const int s = fed_slot[e];
             Job &j = jobs[held[s]];
-            // the bytes of this call's row that belong to the file: all of it, or up to the frame at which its drain ended
-            j.led = led[e];
-            j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + j.led.call_bytes);
+            if (use_img) {
+                // the short record says how far the file is; when it has ended (or reached its drain bound) the whole record
+                // comes down for the seek points, and the file, from its image, behind room for the tag frame
+                const HX_LEDGER_BRIEF &r = brief[s];
+                j.led.open = r.open; j.led.ended = r.ended; j.led.fed = r.fed; j.led.frames = r.frames; j.led.bytes = r.bytes; j.led.crc = r.crc;
+                j.led.call_bytes = r.call_bytes;
+                if (!(j.led.ended || (size_t) j.led.fed >= j.nc + DRAIN)) continue;
+                j.stream.resize((size_t) j.led.head_bytes + r.image_bytes);
+                j.whole = true;
+                if (hx_multi_ledger_read(b, &s, 1, &j.led) != 0 || hx_multi_file_fetch(b, s, j.stream.data(), (long long) j.stream.size()) != (long long) j.stream.size()) {
+                    fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
+                    hx_multi_destroy(b);
+                    return 1;
+                }
+            } else {
+                // the bytes of this call's row that belong to the file: all of it, or up to the frame at which its drain ended
+                j.led = led[e];
+                j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + j.led.call_bytes);
+            }
             if (loaded || !(j.led.ended || (size_t) j.led.fed >= j.nc + DRAIN)) continue;
             // -slots: the file is written and freed, and its slot goes to the next file that waits
             if (!job_write(j, files[2 * held[s] + 1], opt)) rc = 1;

@@ -437,12 +437,13 @@ int check_poisoned(const hx_batch *b)
     if (b->poisoned) { set_err("the batch is unusable after a failed device call: destroy it"); return -1; }
     return 0;
 }
-int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes)
+// outputs = false (the *_host_files calls): the call has no output buffers of the caller's, `out` and `out_bytes` are not looked at
+int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes, bool outputs)
 {
     if (!b) { set_err("null batch"); return -1; }
     if (check_poisoned(b) != 0) return -1;
     if (nframes <= 0 || nframes > b->maxF) { set_err("nframes out of range (1 .. max_frames of hx_batch_create)"); return -1; }
-    if (!in || !out || !out_bytes) { set_err("null buffer"); return -1; }
+    if (!in || (outputs && (!out || !out_bytes))) { set_err("null buffer"); return -1; }
     if (out_stride < hx_batch_out_stride(b, nframes)) { set_err("out_stride is smaller than hx_batch_out_stride(b, nframes)"); return -1; }
     return check_counts(b, nframes, 0);
 }
@@ -479,10 +480,10 @@ int check_opt(const hx_batch *b, const OptOut &o, const int *nfr, int first)
     return 0;
 }
 // (a converting batch takes its input through hx_batch_encode_src_* only: a plain call would advance the encoder past its converter)
-int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes)
+int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes, bool outputs)
 {
     if (b && b->nsrc) { set_err("a converting batch takes its input through hx_batch_encode_src_*"); return -1; }
-    return check_args(b, pcm, nframes, out, out_stride, out_bytes);
+    return check_args(b, pcm, nframes, out, out_stride, out_bytes, outputs);
 }
 
 // the packing kernels of one call on stream qp (see place_pack)
@@ -537,6 +538,19 @@ static int enqueue_ledger(hx_batch *b, const Call &c, int nframes, hipStream_t q
     return 0;
 }
 
+// the file images' append of one call on stream qp, right behind its ledger update (hx_fileimg.hip): (stream, chunk of the
+// worst-case row - plus the 15 bytes a piece may start off a destination vector).  A call without counters and CRCs leaves
+// the live records alone (k_ledger), so nothing of it belongs to a file: no launch
+static int enqueue_file(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
+{
+    const FileImages &f = c.files;
+    if (!c.ledger || !f.img || !c.opt.frame_stats || !c.opt.crc) return 0;
+    const int chunks = (int) ((hx_batch_out_stride(b, nframes) + 15 + HX_FILE_CHUNK - 1) / HX_FILE_CHUNK);
+    LAUNCH(k_file_append, dim3((unsigned) ((long long) b->S * chunks)), dim3(256), qp, (const HX_LEDGER *) c.ledger, (uint2 *) f.fw, f.img, f.pitch, f.cap,
+           (const unsigned char *) c.out, c.out_stride, c.nfr, nframes, chunks, b->d_status);
+    return 0;
+}
+
 // A gate on stream q: what follows it there starts in the tail of the allocator launch whose first workgroup took number
 // `base` of the started-counter (it wraps with the counter), not at that launch's start.
 static int launch_gate(hx_batch *b, hipStream_t q, unsigned base)
@@ -557,7 +571,8 @@ static int flush_pack(hx_batch *b, long long gate_base)
     HIPCHK(hipStreamWaitEvent(b->s_pack, b->ev_k6[j.set], 0));
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
     if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0 ||
-        enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0 || enqueue_ledger(b, j.call, j.nframes, b->s_pack) != 0) return -1;
+        enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0 || enqueue_ledger(b, j.call, j.nframes, b->s_pack) != 0 ||
+        enqueue_file(b, j.call, j.nframes, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -835,7 +850,7 @@ static int place_pack(hx_batch *b, const Pass &p)
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
     if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0 || enqueue_crc(b, p.call, p.nframes, qa) != 0 ||
-        enqueue_ledger(b, p.call, p.nframes, qa) != 0) return -1;
+        enqueue_ledger(b, p.call, p.nframes, qa) != 0 || enqueue_file(b, p.call, p.nframes, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -1077,10 +1092,11 @@ extern "C" float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls)
 
 // the host-buffer PCM calls (host_call; the staging is not waited for before the upload: these calls end drained).
 // With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer); with hd the dense image instead of the rows.
+// files (encode_host_files): no host outputs at all, see host_call.
 int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd,
-                unsigned short *crc)
+                unsigned short *crc, bool files)
 {
-    if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes) != 0) return -1;
+    if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes, !files) != 0) return -1;
     if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
     if (check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
     // under segments one span of the image goes up, from the lowest segment start to the highest segment end; rows: all of them
@@ -1091,8 +1107,26 @@ int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long lon
         PcmIn up = in;
         up.p = b->d_in; up.shift = lo;
         return encode_pass(b, up, nframes, c, nullptr, PASS_PLAIN);
-    }, hd, crc);
+    }, hd, crc, files);
 }
+
+// what every *_host_files call needs of the batch (hx_multi: for all blocks before one starts)
+int check_files(const hx_batch *b)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (!b->d_ledger) { set_err("a *_host_files call needs a file ledger (hx_batch_ledger_begin)"); return -1; }
+    if (!b->files.img) { set_err("a *_host_files call needs file images (hx_batch_file_images)"); return -1; }
+    return 0;
+}
+// The host calls that bring nothing down but the status: rows, byte counts, counters and CRCs stay in the batch's staging,
+// from which the ledger and the file images advance.
+int encode_host_files(hx_batch *b, PcmIn in, int nframes)
+{
+    if (check_files(b) != 0) return -1;
+    return encode_host(b, in, nframes, nullptr, hx_batch_out_stride(b, nframes), nullptr, nullptr, nullptr, nullptr, true);
+}
+extern "C" int hx_batch_encode_s16_host_files(hx_batch *b, const int16_t *pcm, int nframes) { return encode_host_files(b, {pcm, false}, nframes); }
+extern "C" int hx_batch_encode_f32_host_files(hx_batch *b, const float *pcm, int nframes) { return encode_host_files(b, {pcm, true}, nframes); }
 
 extern "C" int hx_batch_encode_s16_host(hx_batch *b, const int16_t *pcm, int nframes, unsigned char *out,
                                         long long out_stride, int *out_bytes)

@@ -267,8 +267,11 @@ static int ledger_op(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, in
     if (!h) return -1;
     for (int e = 0; e < n; e++) h[e] = open ? HxLedgerEntry{idx[e], open[e].ncalls, open[e].head_bytes, open[e].flags, frames_per_block(b->params[b->cls_of[idx[e]]])} : HxLedgerEntry{idx[e], 0, 0, 0, 0};
     if (staging_upload(s, k, sizeof(HxLedgerEntry) * (size_t) n, q) != 0) return -1;
-    if (open) LAUNCH(k_ledger_begin, dim3((unsigned) n), dim3(256), q, b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k));
-    else LAUNCH(k_ledger_gather, dim3((unsigned) n), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), d_out);
+    if (open) {
+        LAUNCH(k_ledger_begin, dim3((unsigned) n), dim3(256), q, b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k));
+        // (file images: the opened slots' length words restart, and say whether the record has an image)
+        if (b->files.fw) LAUNCH(k_file_begin, dim3((unsigned) ((n + 255) / 256)), dim3(256), q, (uint2 *) b->files.fw, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), n, b->files.img ? 1u : 0u);
+    } else LAUNCH(k_ledger_gather, dim3((unsigned) n), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), d_out);
     if (staging_done(s, k, q) != 0) return -1;
     return poison.ok();
 }
@@ -288,7 +291,8 @@ int ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n,
     if (n == 0) return 0;
     if (wait && drain(b) != 0) return -1;
     if (ledger_op(b, idx, open, n, nullptr, q) != 0) return -1;
-    for (int e = 0; e < n; e++) b->led_live[idx[e]] = 1;       // (the host's view moves when the call is made, like a slot's configuration)
+    if (b->led_head.empty()) b->led_head.assign(b->S, 0);
+    for (int e = 0; e < n; e++) { b->led_live[idx[e]] = 1; b->led_head[idx[e]] = open[e].head_bytes; }     // (the host's view moves when the call is made, like a slot's configuration)
     if (wait) HIPCHK(hipStreamSynchronize(q));
     return 0;
 }
@@ -329,3 +333,137 @@ int ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out)
     return 0;
 }
 extern "C" int hx_batch_ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out) { return ledger_read(b, idx, n, out); }
+
+// ---- file images (include/hmp3_amd.h, "file images"; kernels: hx_fileimg.hip) ----
+// The images are one allocation, [S][pitch]; the length words fw [S][2] are made at the first switch-on and kept.  Switching
+// is synchronous and refused while the host counts a record as live, so no call in flight or to come holds a record that
+// points into the images that go.  A switch is all or nothing: the new images are allocated while the old ones still stand,
+// so a refused allocation changes nothing - at the price that a change of cap needs both sets on the device for a moment (a
+// caller short of memory switches off first, with cap = 0).
+
+static void dev_release(hx_batch *b, void *p)
+{
+    if (!p) return;
+    hipFree(p);
+    for (void *&m : b->mem) if (m == p) { m = b->mem.back(); b->mem.pop_back(); break; }
+}
+int images_reserve(hx_batch *b, long long cap, FileImages &next)
+{
+    next = FileImages();
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (cap < 0) { set_err("cap < 0"); return -1; }
+    for (int s = 0; s < (int) b->led_live.size(); s++)
+        if (b->led_live[s]) {
+            char msg[160];
+            snprintf(msg, sizeof msg, "stream %d has a live ledger record: file images are switched between files (read or poll the record's end first)", s);
+            set_err("%s", msg);
+            return -1;
+        }
+    if (cap == 0) return 0;
+    if (cap > LLONG_MAX - 15 || ((cap + 15) & ~15LL) > LLONG_MAX / b->S) { set_err("the file images do not fit the device's memory"); return -1; }
+    HIPCHK(hipSetDevice(b->device));
+    // (a refused hipMalloc leaves its error with the runtime, where the next launch check of this thread would find it and
+    // poison the batch: it is read away here, so that a refusal leaves the batch as usable as it was)
+    if (!b->files.fw) {
+        if (dev_alloc(b, b->files.fw, (long long) sizeof(unsigned) * 2 * b->S) != 0) { (void) hipGetLastError(); return -1; }
+        HIPCHK(hipMemset(b->files.fw, 0, sizeof(unsigned) * 2 * (size_t) b->S));
+    }
+    next.cap = cap;
+    next.pitch = (cap + 15) & ~15LL;
+    if (dev_alloc(b, next.img, next.pitch * b->S) != 0) {
+        (void) hipGetLastError();
+        set_err("the file images do not fit the device's memory");
+        next = FileImages();
+        return -1;
+    }
+    return 0;
+}
+void images_drop(hx_batch *b, FileImages &next)
+{
+    dev_release(b, next.img);
+    next = FileImages();
+}
+int images_commit(hx_batch *b, const FileImages &next)
+{
+    if (drain(b) != 0) return -1;
+    HIPCHK(hipSetDevice(b->device));
+    HIPCHK(hipDeviceSynchronize());
+    unsigned *fw = b->files.fw;
+    if (fw) HIPCHK(hipMemset(fw, 0, sizeof(unsigned) * 2 * (size_t) b->S));
+    // (nothing fails from here on: a commit that returns -1 has not taken `next`)
+    dev_release(b, b->files.img);
+    b->files = next;
+    b->files.fw = fw;
+    return 0;
+}
+extern "C" int hx_batch_file_images(hx_batch *b, long long cap)
+{
+    FileImages next;
+    if (images_reserve(b, cap, next) != 0) return -1;
+    return images_commit(b, next);
+}
+extern "C" long long hx_batch_file_image_cap(const hx_batch *b) { return b ? b->files.cap : 0; }
+extern "C" unsigned char *hx_batch_file_image_ptr(hx_batch *b, int i)
+{
+    return (b && b->files.img && i >= 0 && i < b->S) ? b->files.img + (long long) i * b->files.pitch : nullptr;
+}
+
+// the briefs of all slots on stream q into d_out (ordered like a ledger operation: behind everything in flight)
+static int brief_op(hx_batch *b, HX_LEDGER_BRIEF *d_out, hipStream_t q)
+{
+    HIPCHK(hipSetDevice(b->device));
+    Poison poison{b};
+    if (b->inflight) {
+        if (order_behind_submits(b, q) != 0) return -1;
+        b->inflight = false;
+    }
+    LAUNCH(k_ledger_brief, dim3((unsigned) ((b->S + 255) / 256)), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const uint2 *) b->files.fw, d_out, b->S);
+    return poison.ok();
+}
+extern "C" int hx_batch_ledger_poll_device(hx_batch *b, HX_LEDGER_BRIEF *d_out, void *stream)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (!d_out) { set_err("d_out is null"); return -1; }
+    if (((unsigned long long) d_out & 15) != 0) { set_err("d_out must be 16-byte aligned"); return -1; }
+    return brief_op(b, d_out, (hipStream_t) stream);
+}
+// synchronous: behind everything in flight, one launch into device staging, one copy; a record it shows ended is no longer
+// live for the host
+int ledger_poll(hx_batch *b, HX_LEDGER_BRIEF *out)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (!out) { set_err("out is null"); return -1; }
+    if (drain(b) != 0) return -1;
+    if (dev_grow(b, b->d_blobs, b->blobs_cap, (long long) sizeof(HX_LEDGER_BRIEF) * b->S) != 0) return -1;
+    if (brief_op(b, (HX_LEDGER_BRIEF *) b->d_blobs, nullptr) != 0) return -1;
+    HIPCHK(hipStreamSynchronize(nullptr));
+    HIPCHK(hipMemcpy(out, b->d_blobs, sizeof(HX_LEDGER_BRIEF) * (size_t) b->S, hipMemcpyDeviceToHost));
+    for (int s = 0; s < (int) b->led_live.size(); s++) if (out[s].ended || !out[s].open) b->led_live[s] = 0;
+    return 0;
+}
+extern "C" int hx_batch_ledger_poll(hx_batch *b, HX_LEDGER_BRIEF *out) { return ledger_poll(b, out); }
+
+extern "C" long long hx_batch_file_fetch(hx_batch *b, int i, unsigned char *dst, long long dst_cap)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (!b->files.img) { set_err("file images are off (hx_batch_file_images)"); return -1; }
+    if (i < 0 || i >= b->S) { set_err("stream index out of range"); return -1; }
+    if (!dst) { set_err("dst is null"); return -1; }
+    if (drain(b) != 0) return -1;
+    HIPCHK(hipSetDevice(b->device));
+    unsigned w[2] = {0, 0};
+    HIPCHK(hipMemcpy(w, b->files.fw + 2 * (size_t) i, sizeof w, hipMemcpyDeviceToHost));
+    const long long head = b->led_head.empty() ? 0 : b->led_head[i], total = head + (long long) w[0];
+    if (total > dst_cap) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "stream %d: the file's %lld bytes do not fit dst_cap %lld", i, total, dst_cap);
+        set_err("%s", msg);
+        return -1;
+    }
+    if (w[0]) HIPCHK(hipMemcpy(dst + head, b->files.img + (long long) i * b->files.pitch + head, (size_t) w[0], hipMemcpyDeviceToHost));
+    return total;
+}

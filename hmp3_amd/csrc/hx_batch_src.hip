@@ -114,10 +114,10 @@ extern "C" long long hx_batch_src_in_stride(const hx_batch *b, int nframes)
 }
 
 // argument checks of the converting calls
-static int src_check(const hx_batch *b, const void *in, long long in_stride, int nframes, const void *out, long long out_stride, const void *out_bytes)
+static int src_check(const hx_batch *b, const void *in, long long in_stride, int nframes, const void *out, long long out_stride, const void *out_bytes, bool outputs)
 {
     if (b && !b->nsrc) { set_err("not a converting batch (hx_batch_create_src)"); return -1; }
-    if (check_args(b, in, nframes, out, out_stride, out_bytes) != 0) return -1;
+    if (check_args(b, in, nframes, out, out_stride, out_bytes, outputs) != 0) return -1;
     if (in_stride <= 0) { set_err("in_stride must be positive"); return -1; }
     return 0;
 }
@@ -204,11 +204,13 @@ static int src_encode(hx_batch *b, const unsigned char *d_in, long long in_strid
 }
 
 // what a converting call checks before anything is allocated, copied, launched or counted: the arguments, the counts'
-// range, the optional outputs it would take and every stream's input extent (used_end: see src_extents)
+// range, the optional outputs it would take and every stream's input extent (used_end: see src_extents).  files (the _files
+// call): it has no output buffers of the caller's, and its counters and CRCs are the staging's own - nothing of either to check
 static int src_checked(hx_batch *b, const void *in, long long in_stride, const long long *frame_off, int nframes, const int *nfr,
-                       const void *out, long long out_stride, const void *out_bytes, const OptOut &o, std::vector<long long> &used_end)
+                       const void *out, long long out_stride, const void *out_bytes, const OptOut &o, std::vector<long long> &used_end, bool files = false)
 {
-    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes) != 0 || check_counts_arg(nfr, b->S, nframes, 0) != 0 || check_opt(b, o, nfr) != 0) return -1;
+    if (src_check(b, in, in_stride, nframes, out, out_stride, out_bytes, !files) != 0 || check_counts_arg(nfr, b->S, nframes, 0) != 0 ||
+        (!files && check_opt(b, o, nfr) != 0)) return -1;
     used_end.resize(b->S);
     if (src_extents(b, in_stride, frame_off, nframes, nfr, 0, used_end.data()) != 0) return -1;
     return nfr ? counts_buffers(b) : 0;
@@ -244,6 +246,20 @@ extern "C" int hx_batch_encode_src_counts_host(hx_batch *b, const unsigned char 
     return host_call(b, in, (long long) b->S * in_stride, true, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
         return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, c, used_end.data(), in_used, nullptr);
     }, nullptr, crc);
+}
+// The converting host call that brings nothing down but the status (file images): counters and CRCs are the staging's own,
+// so the optional outputs it takes always satisfy the ledger.
+extern "C" int hx_batch_encode_src_files_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                              int nframes, const int *nfr, long long *in_used)
+{
+    std::vector<long long> used_end;
+    if (check_files(b) != 0) return -1;
+    const long long out_stride = hx_batch_out_stride(b, nframes);
+    if (src_checked(b, in, in_stride, frame_off, nframes, nfr, nullptr, out_stride, nullptr, b->opt, used_end, true) != 0) return -1;
+    CallCounts counts(b, nfr);
+    return host_call(b, in, (long long) b->S * in_stride, true, nframes, nullptr, out_stride, nullptr, nullptr, [&](const Call &c) {
+        return src_encode(b, (const unsigned char *) b->d_in, in_stride, frame_off, nframes, c, used_end.data(), in_used, nullptr);
+    }, nullptr, nullptr, true);
 }
 extern "C" int hx_batch_encode_src_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
                                         int nframes, unsigned char *out, long long out_stride, int *out_bytes,

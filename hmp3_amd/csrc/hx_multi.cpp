@@ -442,6 +442,108 @@ extern "C" int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, lo
     return hx_multi_encode_src_counts_host(m, in, in_stride, frame_off, nframes, nullptr, out, out_stride, out_bytes, in_used, stats, nullptr);
 }
 
+// ---- file images over all blocks (include/hmp3_amd.h, "file images") ----
+// hx_batch_file_images: all blocks or none - every block's refusals and its allocation first (a live record is named by the
+// caller's stream number), and only when all of them have theirs does one block switch
+extern "C" int hx_multi_file_images(hx_multi *m, long long cap)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    const size_t nb = m->part.size();
+    for (size_t k = 0; k < nb; k++)
+        for (int s = 0; s < (int) m->part[k]->led_live.size(); s++)
+            if (m->part[k]->led_live[s]) {
+                char msg[160];
+                snprintf(msg, sizeof msg, "stream %d has a live ledger record: file images are switched between files (read or poll the record's end first)", m->first[k] + s);
+                set_err("%s", msg);
+                return -1;
+            }
+    std::vector<FileImages> next(nb);
+    for (size_t k = 0; k < nb; k++)
+        if (images_reserve(m->part[k], cap, next[k]) != 0) {
+            const std::string why = hx_last_error();
+            for (size_t j = 0; j < k; j++) images_drop(m->part[j], next[j]);
+            set_err("%s", why.c_str());
+            return -1;
+        }
+    // (a commit fails on a device error only: the blocks before it have switched and stay so, the reservations of the blocks
+    // behind it are released)
+    for (size_t k = 0; k < nb; k++)
+        if (images_commit(m->part[k], next[k]) != 0) {
+            const std::string why = hx_last_error();
+            for (size_t j = k; j < nb; j++) images_drop(m->part[j], next[j]);
+            set_err("%s", why.c_str());
+            return -1;
+        }
+    return 0;
+}
+extern "C" int hx_multi_ledger_poll(hx_multi *m, HX_LEDGER_BRIEF *out)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    if (!out) { set_err("out is null"); return -1; }
+    for (hx_batch *b : m->part) if (check_poisoned(b) != 0) return -1;
+    for (size_t k = 0; k < m->part.size(); k++) if (ledger_poll(m->part[k], out + m->first[k]) != 0) return -1;
+    return 0;
+}
+extern "C" long long hx_multi_file_fetch(hx_multi *m, int i, unsigned char *dst, long long dst_cap)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    if (i < 0 || i >= m->S) { set_err("stream index out of range"); return -1; }
+    size_t k = 0;
+    while (k + 1 < m->part.size() && i >= m->first[k + 1]) k++;
+    return hx_batch_file_fetch(m->part[k], i - m->first[k], dst, dst_cap);
+}
+// the *_host_files calls: ledger and images of every block checked before one starts; the blocks' status bits or'ed
+static int multi_check_files(const hx_multi *m)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    for (const hx_batch *b : m->part) if (check_files(b) != 0) return -1;
+    return 0;
+}
+static int multi_encode_host_files(hx_multi *m, PcmIn in, int nframes)
+{
+    if (multi_check_files(m) != 0) return -1;
+    const bool segs = !m->part[0]->seg_off.empty();
+    if (segs && nframes > 0 && nframes <= m->part[0]->maxF)
+        for (size_t k = 0; k < m->part.size(); k++)
+            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_segments(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
+    std::vector<int> st(m->part.size(), 0);
+    const int rc = multi_fanout(m, in.p != nullptr, nframes, hx_multi_out_stride(m, nframes), [&](size_t k) {
+        const char *p = (const char *) in.p + (segs ? 0 : in.bytes(m->first[k], nframes, m->nchan));
+        st[k] = encode_host_files(m->part[k], {p, in.f32}, nframes);
+        return st[k] < 0 ? -1 : 0;
+    });
+    if (rc != 0) return rc;
+    int v = 0;
+    for (int x : st) v |= x;
+    return v;
+}
+extern "C" int hx_multi_encode_s16_host_files(hx_multi *m, const int16_t *pcm, int nframes) { return multi_encode_host_files(m, {pcm, false}, nframes); }
+extern "C" int hx_multi_encode_f32_host_files(hx_multi *m, const float *pcm, int nframes) { return multi_encode_host_files(m, {pcm, true}, nframes); }
+extern "C" int hx_multi_encode_src_files_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                              const int *nfr, long long *in_used)
+{
+    if (multi_check_files(m) != 0) return -1;
+    if (nframes > 0 && in_stride > 0) {
+        if (check_counts_arg(nfr, m->S, nframes, 0) != 0) return -1;
+        for (size_t k = 0; k < m->part.size(); k++) {
+            const long long f = m->first[k];
+            if (!m->part[k]->nsrc) { set_err("not a converting batch (hx_multi_create_src)"); return -1; }
+            if (src_extents(m->part[k], in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes, nfr ? nfr + f : nullptr, (int) f, nullptr) != 0) return -1;
+        }
+    }
+    std::vector<int> st(m->part.size(), 0);
+    const int rc = multi_fanout(m, in != nullptr, nframes, hx_multi_out_stride(m, nframes), [&](size_t k) {
+        const long long f = m->first[k];
+        st[k] = hx_batch_encode_src_files_host(m->part[k], in + f * in_stride, in_stride, frame_off ? frame_off + f * nframes : nullptr, nframes,
+                                               nfr ? nfr + f : nullptr, in_used ? in_used + f : nullptr);
+        return st[k] < 0 ? -1 : 0;
+    });
+    if (rc != 0) return rc;
+    int v = 0;
+    for (int x : st) v |= x;
+    return v;
+}
+
 extern "C" int hx_multi_status(hx_multi *m)
 {
     int v = 0;

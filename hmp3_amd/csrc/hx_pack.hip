@@ -509,3 +509,6 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
 
 // ---- PCM segments (hx_batch_pcm_segments): k_pcm_spread, a file of its own, built as part of this unit ----
 #include "hx_pcmin.hip"
+
+// ---- file images (hx_batch_file_images): k_file_append, k_file_begin, k_ledger_brief, a file of its own, built as part of this unit ----
+#include "hx_fileimg.hip"

@@ -27,7 +27,7 @@ HX_LOCAL void set_err(const char *fmt, const char *a = "");       // the calling
 #define HIPCHKN(x) do { hipError_t e_ = (x); if (e_ != hipSuccess) { set_err("HIP error: %s", hipGetErrorString(e_)); return nullptr; } } while (0)
 
 #ifdef __HIPCC__
-// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip, hx_slots.hip, hx_ledger.hip and hx_pcmin.hip / hx_src.hip)
+// kernels (hx_polyphase.hip / hx_spec.hip / hx_prep.hip / hx_alloc.hip / hx_pack.hip with hx_crc.hip, hx_slots.hip, hx_ledger.hip, hx_pcmin.hip and hx_fileimg.hip / hx_src.hip)
 // (K1_GPB / K1_THREADS, k_polyphase's tile and launch dimension: hx_types.h)
 // nfr (the last argument of every kernel that walks a stream's granules or frames; AllocArgs::nfr for the stream walk): [S] the
 // frames each stream takes of the call (hx_batch_frame_counts), or null = all of them.  A kernel bounds its work on stream s
@@ -66,6 +66,10 @@ __global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent);
 __global__ void k_ledger_gather(const HX_LEDGER *led, const HxLedgerEntry *ent, HX_LEDGER *out);
 __global__ void k_pcm_spread(const unsigned char *img, const long long *off, unsigned char *rows, long long row_bytes, int nframes, int sample_bytes,
                              const HxStream *st, const HxParams *prm, const int *nfr, int chunks);
+__global__ void k_file_append(const HX_LEDGER *led, uint2 *fw, unsigned char *img, long long pitch, long long cap, const unsigned char *out, long long out_stride,
+                              const int *nfr, int nframes, int chunks, int *status);
+__global__ void k_file_begin(uint2 *fw, const HxLedgerEntry *ent, int n, unsigned on);
+__global__ void k_ledger_brief(const HX_LEDGER *led, const uint2 *fw, HX_LEDGER_BRIEF *out, int S);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_order_kinds(const unsigned *dur, const HxStream *st, const HxParams *prm, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
@@ -109,6 +113,9 @@ struct DenseOut { unsigned char *buf = nullptr; long long cap = 0; long long *of
 // per-frame counters (hx_batch_frame_stats_buffer), the dense image and the per-frame MusicCRC (hx_batch_crc_buffer; k_crc
 // reads the counters, so a call with crc needs frame_stats: check_opt).
 struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; unsigned short *crc = nullptr; };
+// The file images of a batch (hx_batch_file_images): img null = off.  [S] images of `pitch` bytes each, of which `cap` count;
+// fw [S][2]: per slot {image_bytes, the record has an image} (hx_fileimg.hip) - made at the first switch-on and kept
+struct FileImages { unsigned char *img = nullptr; long long pitch = 0, cap = 0; unsigned *fw = nullptr; };
 // Everything one call writes, fixed when the call is made: the rows, the optional outputs and, for the pass the one-stream
 // encoder records into a HIP graph (hx_enc.cpp; no timing events, nothing that queries the stream), where k_pack_carry
 // leaves the stream's frame counter and the page-locked host memory the packing workgroup publishes the call's results to
@@ -121,6 +128,7 @@ struct Call {
                                         // null = every stream takes the call's nframes
     unsigned *rec_frames = nullptr; unsigned char *rec_host = nullptr; bool recording = false;
     HX_LEDGER *ledger = nullptr;        // the batch's file ledger as it stood when the call was made (null: none yet): k_ledger goes out behind the call's k_crc
+    FileImages files;                   // ... and its file images (img null: off): k_file_append goes out behind the call's k_ledger
 };
 
 // Three staging copies in rotation for a small list that a call hands to its kernels: page-locked host memory and device
@@ -222,6 +230,10 @@ struct hx_batch {
     // needs frame counters and CRCs: check_opt)
     HX_LEDGER *d_ledger = nullptr;
     std::vector<unsigned char> led_live;
+    // file images (hx_batch_file_images): the images and the length words, and the host's view of each slot's head_bytes
+    // (its latest hx_batch_ledger_begin's; it moves when that call is made, like led_live)
+    FileImages files;
+    std::vector<int> led_head;
     bool debug = false;
     // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
@@ -402,6 +414,7 @@ static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_
 {
     Call c = {out, out_stride, out_bytes, b ? b->opt : OptOut()};
     c.ledger = b ? b->d_ledger : nullptr;
+    if (b) c.files = b->files;
     return c;
 }
 // where a pass runs: every kernel on the caller's stream, or (hx_batch_submit_*) front end and stream walk on the batch's
@@ -410,8 +423,8 @@ enum PassKind { PASS_PLAIN, PASS_SUBMIT_DEVICE, PASS_SUBMIT_HOST };
 
 // Argument checks of every encode entry point, made before anything is allocated, copied or launched; check_call: ... of
 // the PCM entry points, which a converting batch refuses
-HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes);
-HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes);
+HX_LOCAL int check_args(const hx_batch *b, const void *in, int nframes, const void *out, long long out_stride, const void *out_bytes, bool outputs = true);
+HX_LOCAL int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out, long long out_stride, const void *out_bytes, bool outputs = true);
 // ... of the per-stream frame counts in force against the call's nframes (check_args makes it; hx_multi for all its blocks
 // before any of them starts, with `first` = the block's first stream, so the message names the caller's stream number)
 HX_LOCAL int check_counts(const hx_batch *b, int nframes, int first);
@@ -444,7 +457,16 @@ HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, v
 // the host-buffer PCM calls; hd: the *_host_dense calls' image, its capacity and offsets in host memory (see host_call)
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
-                         unsigned short *crc = nullptr);
+                         unsigned short *crc = nullptr, bool files = false);
+// the *_host_files calls (file images): what they need of the batch, and the PCM form
+HX_LOCAL int check_files(const hx_batch *b);
+HX_LOCAL int encode_host_files(hx_batch *b, PcmIn in, int nframes);
+// hx_batch_file_images in two steps (hx_multi: reserve for all blocks, then commit all): images_reserve makes the refusals and
+// allocates what `cap` needs into `next`, changing nothing of the batch's view; images_commit releases the old images and takes `next`
+HX_LOCAL int images_reserve(hx_batch *b, long long cap, FileImages &next);
+HX_LOCAL int images_commit(hx_batch *b, const FileImages &next);
+HX_LOCAL void images_drop(hx_batch *b, FileImages &next);
+HX_LOCAL int ledger_poll(hx_batch *b, HX_LEDGER_BRIEF *out);
 // The one create path (hx_batch.hip).  ec[nmenu] (and src[nmenu]: a converting batch) is the menu, cfg[nstreams] or null
 // (= entry 0) the entry each slot starts with.  A refusal names the entry as "<label> <origin[j]>: " - src_label for what
 // the converter rejects, cls_label for what the encoder's init or the batch's kind rejects; a null label: no prefix; a null
@@ -509,19 +531,23 @@ static inline int rows_to_host(const hx_batch *b, unsigned char *out, const unsi
 // hd (the *_host_dense calls): the dense image and its offsets go to staging too, not to the caller's device image, and
 // come back instead of the rows (`out` is not used): the offsets, and the image up to the last segment that fits hd->cap
 // in whole - the segments that fit are a prefix of the streams, and none of them ends beyond hd->bound.
+// files (the *_host_files calls; out, out_bytes, stats and crc null): rows, byte counts, counters and CRCs all go to the
+// staging and stay there - the call's ledger update and file images take them from it - and what comes back is the batch's
+// status word, which is the call's return value.
 template <class Encode>
 static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
-                     long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr, unsigned short *crc = nullptr)
+                     long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr, unsigned short *crc = nullptr,
+                     bool files = false)
 {
-    {   // (the optional outputs the call will take, checked before anything is allocated or copied)
+    if (!files) {   // (the optional outputs the call will take, checked before anything is allocated or copied; files: it takes both)
         OptOut o = b->opt;
         if (stats) o.frame_stats = stats;
         if (crc) o.crc = crc;
         if (check_opt(b, o, counts_in_force(b)) != 0) return -1;
     }
     HIPCHK(hipSetDevice(b->device));
-    const long long obytes = (long long) b->S * out_stride, sbytes = stats ? (long long) sizeof(int) * b->S * nframes * 2 : 0;
-    const long long cbytes = crc ? (long long) sizeof(unsigned short) * b->S * nframes : 0;
+    const long long obytes = (long long) b->S * out_stride, sbytes = (stats || files) ? (long long) sizeof(int) * b->S * nframes * 2 : 0;
+    const long long cbytes = (crc || files) ? (long long) sizeof(unsigned short) * b->S * nframes : 0;
     if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes) ||
         dev_grow(b, b->d_crc, b->crc_cap, cbytes)) return -1;
     if (hd && (dev_grow(b, b->d_dense, b->dense_cap, std::max(16LL, std::min(hd->cap, hd->bound))) ||
@@ -529,10 +555,15 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     if (drain_first && drain(b) != 0) return -1;
     if (in_bytes > 0) HIPCHK(hipMemcpy(b->d_in, in, (size_t) in_bytes, hipMemcpyHostToDevice));    // (0: a call under segments of which no stream takes a frame)
     Call c = call_on(b, b->d_out, out_stride, b->d_outbytes);
-    if (stats) c.opt.frame_stats = b->d_stats;
-    if (crc) c.opt.crc = b->d_crc;
+    if (stats || files) c.opt.frame_stats = b->d_stats;
+    if (crc || files) c.opt.crc = b->d_crc;
     if (hd) c.opt.dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
     if (encode(c) != 0 || drain(b) != 0) return -1;
+    if (files) {
+        int v = -1;
+        HIPCHK(hipMemcpy(&v, b->d_status, sizeof(int), hipMemcpyDeviceToHost));
+        return v;
+    }
     HIPCHK(hipMemcpy(out_bytes, b->d_outbytes, sizeof(int) * b->S, hipMemcpyDeviceToHost));
     if (hd) {
         HIPCHK(hipMemcpy(hd->off, b->d_dense_off, sizeof(long long) * (b->S + 1), hipMemcpyDeviceToHost));

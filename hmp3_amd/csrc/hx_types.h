@@ -209,6 +209,9 @@ struct alignas(16) HxFrameOut {
 // PCM segments (hx_batch_pcm_segments): a workgroup of k_pcm_spread (hx_pcmin.hip) moves this many bytes of one segment, the
 // same way; the host sizes the grid with it from the call's row.
 #define HX_PCM_CHUNK 16384
+// File images (hx_batch_file_images): a workgroup of k_file_append (hx_fileimg.hip) moves this many bytes of one image, the
+// same way; the host sizes the grid with it from the worst-case row plus the 15 bytes a piece may start off a vector.
+#define HX_FILE_CHUNK 16384
 
 // Slots of a batch's counter block (AllocArgs::done_counter; the host runtime reads some of them and hands two to k_gate and k_pack).
 enum HxCounter {

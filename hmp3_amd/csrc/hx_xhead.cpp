@@ -165,6 +165,17 @@ extern "C" void hx_ledger_open(HX_LEDGER *r, int ncalls, int frames_per_call, in
     r->every = 1;
 }
 
+// the short form of a record (file images; the kernel: k_ledger_brief, hx_fileimg.hip)
+extern "C" void hx_ledger_brief(const HX_LEDGER *r, unsigned image_bytes, HX_LEDGER_BRIEF *out)
+{
+    static_assert(sizeof(HX_LEDGER_BRIEF) == 32, "HX_LEDGER_BRIEF is eight words without padding");
+    if (!r || !out) return;
+    out->open = r->open; out->ended = r->ended; out->fed = r->fed;
+    out->frames = r->frames; out->bytes = r->bytes; out->crc = r->crc;
+    out->call_bytes = r->call_bytes;
+    out->image_bytes = image_bytes;
+}
+
 // hx_xing_toc on a record's points
 static int ledger_toc(HX_LEDGER *r, int frames, int bs_bytes)
 {

@@ -485,7 +485,8 @@ int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *
    there), 4 = the Huffman bits packed for a channel differ from the bits counted for it (an internal
    consistency check of the two-wave packer), 8 = a converter window out of bounds (converting batches), 16 = a dense image
    did not fit its dense_cap (hx_batch_dense_buffers), 32 = hx_batch_set_stream_states_device was handed a blob its slot does
-   not take (that slot was left as it was).  0 = healthy; -1 = no answer (the batch became unusable after a
+   not take (that slot was left as it was), 64 = a file did not fit its image (hx_batch_file_images; the bytes that fit
+   were written).  0 = healthy; -1 = no answer (the batch became unusable after a
    failed device call, or the status could not be read).  Synchronises - and, like hx_batch_wait, first enqueues the
    packing that the last hx_batch_submit_*_device left for later: that writes the submit's output buffers (d_out,
    d_out_bytes and the packet buffer that was set at the submit), which must therefore still be valid.
@@ -651,6 +652,73 @@ int hx_batch_ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *ope
 int hx_batch_ledger_read(hx_batch *b, const int *idx, int n, HX_LEDGER *out);
 int hx_batch_ledger_read_device(hx_batch *b, const int *idx, int n, HX_LEDGER *d_out, void *stream);
 
+/* ---- file images: each file's bitstream gathered on the GPU, fetched once (no reference equivalent) ----
+   The ledger decides on the device which bytes of a call belong to a file (call_bytes).  With file images on, a kernel
+   right behind the ledger's update also puts those bytes where the file is: every slot owns an image of `cap` bytes of
+   device memory (16-byte aligned start), of which
+     bytes [0, head_bytes) are reserved for the tag frame - no kernel ever writes them;
+     the file's audio bytes follow from head_bytes, contiguous, in call order.
+   Per slot the batch keeps one length word beside the ledger, image_bytes: the audio bytes present in the image.  It equals
+   the record's `bytes`, or less after an overflow.  HX_LEDGER and the checkpoint blob are as before.
+   A call appends for stream i when the stream takes n > 0 frames of it, its record is open, and the record was begun while
+   images were on: the call_bytes bytes at the start of row i go to image_i + head_bytes + (bytes - call_bytes), bytes and
+   call_bytes as the call's ledger update left them.  A stream that takes no frames, a record that is not open and a record
+   that had already ended keep image and length word bit-identical.  Nothing at or beyond cap is written: of a file that
+   does not fit, the bytes that fit are written, image_bytes stops at cap - head_bytes and status bit 64 is set
+   (hx_batch_status); the other streams are unaffected and the batch stays usable.
+   Composition: every encode or submit entry point of a batch with images on appends - device and host buffers, plain and
+   converting, a submit with its deferred packing - under the ledger's own rule (the call has a frame-counter and a CRC buffer
+   in force).  Rows, out_bytes, packets, counters, CRCs, the dense image and the ledger records are written exactly as
+   without images, and a batch that never switches images on allocates and launches nothing more than before.
+   hx_batch_file_images: switches images on with cap > 0 (allocates nstreams * round_up(cap, 16) bytes; an earlier set of
+   images is released) or off with cap = 0.  Synchronous; sticky.  Refused (-1, nothing changes) while the host counts any
+   record as live (begun, and not shown ended by hx_batch_ledger_read or hx_batch_ledger_poll), for a negative cap, and when
+   the allocation fails - the batch stays usable, and the earlier images and their cap stay in force: the new set is
+   allocated before the old one is released, so a change of cap needs room for both for a moment (switch off first where
+   that is too much).  Records begun before it was called have no image (image_bytes stays 0); it sets every length word
+   to 0.
+   hx_batch_ledger_begin sets image_bytes to 0 for the slots it opens; it does not clear the image, so the previous file's
+   bytes stay until overwritten.  Reset, assign, save and restore do not touch images.
+   hx_batch_file_image_cap: cap, 0 = off.  hx_batch_file_image_ptr: the device address of slot i's image (NULL: off, or i
+   out of range), for device consumers and tests.
+   The short form of a record (fixed layout, 32 bytes, two of them compare bytewise): */
+typedef struct { int open, ended, fed; unsigned frames, bytes, crc; int call_bytes; unsigned image_bytes; } HX_LEDGER_BRIEF;
+/* hx_ledger_brief: host only, the reference for the kernel: the record's fields of the same names, and image_bytes as given.
+   hx_batch_ledger_poll: out [nstreams], the brief of every slot's record (all zero but image_bytes for a batch without a
+   ledger).  Synchronous like hx_batch_ledger_read: the deferred packing first, then one launch and one copy of
+   32 * nstreams bytes.  It teaches the host which records have ended, exactly as a read does.
+   hx_batch_ledger_poll_device: the same launch in stream order into device memory, d_out [nstreams], 16-byte aligned (else
+   -1); it does not inform the host.
+   hx_batch_file_fetch: synchronous.  Copies the image_bytes audio bytes of slot i to dst + head_bytes (head_bytes: of the
+   slot's latest hx_batch_ledger_begin), leaves dst[0, head_bytes) untouched for the caller's tag frame, and returns
+   head_bytes + image_bytes - or -1 without copying if that exceeds dst_cap, if images are off, or for a bad argument.
+   Works for live and ended records alike.
+   Host-fed calls that bring nothing down but the call's status: hx_batch_encode_{s16,f32}_host_files and, for converting
+   batches, hx_batch_encode_src_files_host (nfr: HOST [nstreams] or NULL, in_used: [nstreams] or NULL, as
+   hx_batch_encode_src_counts_host).  Rows, byte counts, frame counters and CRCs live in staging the batch owns on the
+   device; the ledger and the images advance.  They honour hx_batch_frame_counts and hx_batch_pcm_segments like every other
+   host call, and are refused (-1, before anything runs) when the batch has no ledger or no images.  They return the status
+   bits as hx_batch_status would after the call (0 = healthy; bit 64 = a file did not fit), or -1.
+   hx_multi_file_images / hx_multi_ledger_poll / hx_multi_file_fetch (i counts streams over all blocks) /
+   hx_multi_encode_{s16,f32}_host_files / hx_multi_encode_src_files_host: the same over all blocks, under the hx_multi rules:
+   all blocks or (-1) none, refusals made for all blocks before one starts, the caller's stream numbers in messages; the
+   encode calls return the blocks' status bits or'ed.  (hx_multi_file_images: a block whose allocation fails after another's
+   succeeded has that one's images released again.)
+   Not covered: images in the checkpoint blob - a stream moved between batches leaves its image behind; building the tag
+   frame on the GPU; pipelined host submits in a _files form; the hx_enc_* encoder; bench.py, which measures calls that
+   return rows. */
+void hx_ledger_brief(const HX_LEDGER *r, unsigned image_bytes, HX_LEDGER_BRIEF *out);
+int hx_batch_file_images(hx_batch *b, long long cap);
+long long hx_batch_file_image_cap(const hx_batch *b);
+unsigned char *hx_batch_file_image_ptr(hx_batch *b, int i);
+int hx_batch_ledger_poll(hx_batch *b, HX_LEDGER_BRIEF *out);
+int hx_batch_ledger_poll_device(hx_batch *b, HX_LEDGER_BRIEF *d_out, void *stream);
+long long hx_batch_file_fetch(hx_batch *b, int i, unsigned char *dst, long long dst_cap);
+int hx_batch_encode_s16_host_files(hx_batch *b, const int16_t *pcm, int nframes);
+int hx_batch_encode_f32_host_files(hx_batch *b, const float *pcm, int nframes);
+int hx_batch_encode_src_files_host(hx_batch *b, const unsigned char *in, long long in_stride, const long long *frame_off,
+                                   int nframes, const int *nfr, long long *in_used);
+
 /* ---- host placement (no reference equivalent): a host-fed GPU reads ~50 GB/s of PCM over PCIe, so its page-locked
    buffers and the threads that submit its copies belong on the NUMA node the device hangs on.
    hx_device_numa_node: that node from sysfs (-1 = unknown or not a NUMA machine).  hx_bind_thread_to_device: restricts the
@@ -712,6 +780,14 @@ hx_multi *hx_multi_create_mixed(int ndev, const int *devices, int nstreams, cons
 /* hx_batch_ledger_begin / hx_batch_ledger_read over all blocks (idx counts streams over all blocks); synchronous; all blocks or (-1) none */
 int hx_multi_ledger_begin(hx_multi *m, const int *idx, const HX_LEDGER_OPEN *open, int n);
 int hx_multi_ledger_read(hx_multi *m, const int *idx, int n, HX_LEDGER *out);
+/* file images over all blocks ("file images" above): cap is per stream; out [nstreams]; i counts streams over all blocks */
+int hx_multi_file_images(hx_multi *m, long long cap);
+int hx_multi_ledger_poll(hx_multi *m, HX_LEDGER_BRIEF *out);
+long long hx_multi_file_fetch(hx_multi *m, int i, unsigned char *dst, long long dst_cap);
+int hx_multi_encode_s16_host_files(hx_multi *m, const int16_t *pcm, int nframes);
+int hx_multi_encode_f32_host_files(hx_multi *m, const float *pcm, int nframes);
+int hx_multi_encode_src_files_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
+                                   const int *nfr, long long *in_used);
 long long hx_multi_src_in_stride(const hx_multi *m, int nframes);
 int hx_multi_encode_src_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
                              unsigned char *out, long long out_stride, int *out_bytes, long long *in_used, int *stats);

@@ -40,6 +40,9 @@ int main()
         std::vector<int> st(2, 0);
         unsigned short c = 0;
         hx_ledger_update(&r, st.data(), &c, 1, 0);          // a call after the end
+        HX_LEDGER_BRIEF brief;
+        hx_ledger_brief(&r, r.bytes, &brief);               // the record's short form (file images)
+        if (!brief.ended || brief.bytes != r.bytes || brief.call_bytes != 0) { fprintf(stderr, "file %d: brief differs\n", it); return 1; }
         if (!hx_xing_load_points(x, &r)) { fprintf(stderr, "file %d: points refused\n", it); return 1; }
         hx_xing_update_info(x, r.frames, head + (int) r.bytes, 50, nullptr, tag, nullptr, nullptr, (unsigned long long) ncalls * 1152, (unsigned) head + r.bytes,
                             16000, 44100, 44100, (unsigned short) r.crc);
