@@ -219,6 +219,12 @@ unsigned hxo_frames_out(const hxo_encoder *e);
 unsigned hxo_bytes_out(const hxo_encoder *e);
 /* short_blocks = 0 / 1 -> out = { beyond_table, from_16384, max_qx } of that allocator's noise measurement */
 void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3]);
+/* path census (hxo_int.h, HXO_PATHS): hxo_path_counts[hxo_path_count_n()] counts the branches taken by every encoder of the
+   process; hxo_path_count_names() names all but the last 32 (the Huffman tables), separated by blanks; hxo_stream_kind():
+   bit 0 MPEG-1 rates, bit 1 first-generation allocator, bit 2 mono, bit 3 -HF in force */
+int hxo_path_count_n(void);
+const char *hxo_path_count_names(void);
+int hxo_stream_kind(const hxo_encoder *e);
 void hxo_default_control(hxo_control *ec);      /* test/tomp3.cpp:357-384 */
 int hxo_sizeof_encoder(void);
 

@@ -776,23 +776,37 @@ static void trade_dual(ba_t *b)
    decrease_bits, [5] its rounds, [6] limit_bits rounds, [7] quantise-and-count passes in all.  Not part of the encoder. */
 long long hxo_rate_stats[8];
 
+/* Path census (hxo_int.h): counts of the branches taken.  Not part of the encoder. */
+long long hxo_path_counts[HXO_P_N];
+int hxo_path_count_n(void) { return HXO_P_N; }
+#define HXO_PATH_NAME(n) #n " "
+const char *hxo_path_count_names(void) { return HXO_PATHS(HXO_PATH_NAME); }
+static int path_stepped_back, path_dec_capped;       /* census only: what the granule's increase_bits / decrease_bits did */
+
 /* bitallo3.cpp:2569-2722 */
 static int increase_bits(ba_t *b, int bits0, int ms)
 {
     const hxo_params *p = b->p;
     hxo_state *st = &b->e->s;
     int i, k, ch, bits = bits0, g[2][22], thres = b->minTargetBits - (b->minTargetBits >> 4), pass;
+    int held, moved, hold_seen = 0;
     if (bits0 > thres) return bits0;
     hxo_rate_stats[1]++;
+    if (ms) HXO_HIT(L_inc_ms); else HXO_HIT(L_inc_lr);
+    if (p->hf_flag) HXO_HIT(L_inc_hf);
     for (ch = 0; ch < 2; ch++) for (i = 0; i < p->nsf[ms ? 0 : ch]; i++) g[ch][i] = b->gsf[ch][i];
     for (pass = 0; pass < 2; pass++) {
         for (k = 0; k < (pass ? 1 : 10); k++) {
             hxo_rate_stats[pass ? 3 : 2]++; hxo_rate_stats[7]++;
+            if (pass) { HXO_HIT(L_inc_stepback); path_stepped_back = 1; }
+            held = moved = 0;
             for (ch = 0; ch < b->nchan; ch++)
                 for (i = 0; i < p->nsf[ch]; i++) {
+                    if (!pass) { if (g[ch][i] - 1 < b->gmin[ch][i]) held = 1; else moved = 1; }
                     if (pass) b->gsf[ch][i] = g[ch][i] + 1;
                     else b->gsf[ch][i] = g[ch][i] = HXO_MAX(g[ch][i] - 1, b->gmin[ch][i]);
                 }
+            if (held && moved && !hold_seen) { hold_seen = 1; HXO_HIT(L_inc_gmin_hold); }
             if (ms) {
                 st->hf_quant = 0; st->ixmax[0][21] = 0; st->gsf_hf = -1;
                 clear_hf(b, 1);
@@ -811,6 +825,7 @@ static int increase_bits(ba_t *b, int bits0, int ms)
             }
             if (!pass && bits >= thres) break;
         }
+        if (!pass) { if (k == 0) HXO_HIT(L_inc_first); else if (k < 10) HXO_HIT(L_inc_several); else HXO_HIT(L_inc_cap); }
         if (bits <= b->maxTargetBits) break;     /* else fall back one step (second pass) */
     }
     return bits;
@@ -826,8 +841,11 @@ static int decrease_bits(ba_t *b, int bits0)
     deltaN = HXO_MAX(deltaN, 40);
     b->deltaMNR = 0;
     hxo_rate_stats[4]++;
+    if (b->ms_flag) HXO_HIT(L_dec_ms); else HXO_HIT(L_dec_lr);
+    if (path_stepped_back) HXO_HIT(L_dec_after_stepback);
     for (k = 0; k < 10; k++) {
         hxo_rate_stats[5]++; hxo_rate_stats[7]++;
+        if (deltaN == 40) HXO_HIT(L_dec_delta_floor); else HXO_HIT(L_dec_delta_formula);
         b->deltaMNR += deltaN;
         for (ch = 0; ch < b->nchan; ch++) for (i = 0; i < p->nsf[ch]; i++) b->NT[ch][i] += deltaN;
         seek_actual(b);
@@ -838,6 +856,8 @@ static int decrease_bits(ba_t *b, int bits0)
         deltaN = (f * (bits - b->maxTargetBits)) >> 10;
         deltaN = HXO_MAX(deltaN, 40);
     }
+    if (k == 0) HXO_HIT(L_dec_one); else if (k < 10) HXO_HIT(L_dec_several); else HXO_HIT(L_dec_cap);
+    path_dec_capped = (k == 10);
     return bits;
 }
 
@@ -847,8 +867,13 @@ static int limit_bits(ba_t *b, int part23)
     const hxo_params *p = b->p;
     hxo_state *st = &b->e->s;
     int i, k, ch, bits = 0;
+    if (path_dec_capped) { HXO_HIT(L_lim_after_dec_cap); path_dec_capped = 0; }
+    if (!part23) HXO_HIT(L_lim_max);
+    else if (st->huff_bits[0] > PART23 && b->nchan == 2 && st->huff_bits[1] > PART23) HXO_HIT(L_lim_p23_both);
+    else HXO_HIT(L_lim_p23_one);
     for (k = 0; k < 100; k++) {
         hxo_rate_stats[6]++; hxo_rate_stats[7]++;
+        if (!part23 && k == 1) HXO_HIT(L_lim_max_several);
         for (ch = 0; ch < b->nchan; ch++) {
             if (part23 && st->huff_bits[ch] <= PART23) continue;
             for (i = 0; i < p->nsf[ch]; i++) b->gsf[ch][i] = HXO_MIN(127, b->gsf[ch][i] + 1);
@@ -877,6 +902,9 @@ static void inverse_sf2(ba_t *b)
             if ((st->ixmax[ch][i] == 1) || (st->ixmax[ch][i] == 2)) {
                 t = inverse_gsf_xfer(p, qx, y, n);
                 s = ((Gscale - t + (1 << sh)) & (~((1 << (sh + 1)) - 1))) >> 13;
+                HXO_HIT(L_isf2_refined);
+                if (s > b->up[ch][i]) HXO_HIT(L_isf2_clamp_up);
+                else if (s < b->lo[ch][i]) HXO_HIT(L_isf2_clamp_lo);
                 s = HXO_MIN(s, b->up[ch][i]);
                 s = HXO_MAX(s, b->lo[ch][i]);
                 b->sf[ch][i] = s;
@@ -892,6 +920,7 @@ static int allocate(ba_t *b, int ms)
     const hxo_params *p = b->p;
     hxo_state *st = &b->e->s;
     int ch, bits, bits0;
+    path_stepped_back = path_dec_capped = 0;
     if (p->hf_flag) {
         if (ms) { st->hf_quant = 0; st->ixmax[0][21] = st->ixmax[1][21] = 0; st->gsf_hf = -1; }
         else hf_reset_lr(b);
@@ -937,9 +966,13 @@ static void mnr_feedback(ba_t *b, int activeBands, int bits, int block_type)
         mnr0 = (int) (0.2 * deltaNB * HXO_MAX((b->minTargetBits - bits), 0));
         dmnr = mnr + mnr2 + mnrp - mnr0;
         maxdmnr = HXO_MAX(st->MNR - p->initialMNR, b->TargetBits >> 3);
+        if (dmnr > maxdmnr) HXO_HIT(L_fb_dmnr_cut);
         dmnr = HXO_MIN(dmnr, maxdmnr);
+        if (b->deltaMNR && dmnr < (b->deltaMNR >> 1)) HXO_HIT(L_fb_dmnr_raised);
         if (b->deltaMNR) dmnr = HXO_MAX(dmnr, (b->deltaMNR >> 1));
         st->MNR = st->MNR - dmnr;
+        if (st->MNR > 2000) HXO_HIT(L_fb_mnr_cap);
+        if (bits > (b->TargetBits + 2000) && HXO_MIN(st->MNR, 2000) > p->initialMNR) HXO_HIT(L_fb_reset);
         st->MNR = HXO_MIN(st->MNR, 2000);
         if (bits > (b->TargetBits + 2000)) st->MNR = HXO_MIN(st->MNR, p->initialMNR);
     }
@@ -1000,16 +1033,19 @@ void hxo_bitallo_long(hxo_encoder *e, float xr[2][576], hxo_sigmask sm[2][36],
     b->deltaMNR = 0;
     if (block_type == 1) {
         if (st->MNR > p->initialMNR) {
+            HXO_HIT(L_bt1_adjust);
             st->MNR = (st->MNR + p->initialMNR) >> 1;
             st->MNR = HXO_MIN(st->MNR, p->initialMNR + 500);
         }
     } else if (block_type == 3) {
+        HXO_HIT(L_bt3_adjust);
         st->MNR = (st->MNR + p->initialMNR) >> 1;
         st->MNR = HXO_MIN(st->MNR, p->initialMNR + 500);
         memset(st->ix, 0, p->nchan * 576 * sizeof(int));
     }
     if (block_type == 2) {
         int MNR0 = st->MNR;
+        if (p->vbr_flag == 0) HXO_HIT(L_short_mnr0_cbr); else HXO_HIT(L_short_mnr0_vbr);
         if (p->vbr_flag == 0) {
             MNR0 = st->MNR - (HXO_MAX(st->MNR - p->initialMNR, 0) >> 1) - (HXO_MAX(st->MNR - p->initialMNR - 400, 0) >> 2);
             MNR0 = HXO_MAX(p->initialMNR + 400, MNR0);

@@ -590,28 +590,32 @@ static int allo_2(a1_t *b)
     for (i = 0; i < 4; i++) {
         fnc_noise(b);
         dsf = fnc_noise_seek(b);
-        if (dsf <= 0) break;
+        if (dsf <= 0) { HXO_HIT(A_seek1_dsf0); break; }
         nbits = fnc_bit_seek(b, 0);
-        if (dsf < 2) break;
+        if (dsf < 2) { HXO_HIT(A_seek1_dsf2); break; }
     }
+    if (i == 4) HXO_HIT(A_seek1_four);
     b->noise_fn = 1;
     for (i = 0; i < 4; i++) {
         fnc_noise2(b);
         dsf = fnc_noise_seek(b);
-        if (dsf <= 0) break;
+        if (dsf <= 0) { HXO_HIT(A_seek2_dsf0); break; }
         nbits = fnc_bit_seek(b, 1);
-        if (dsf < 2) break;
+        if (dsf < 2) { HXO_HIT(A_seek2_dsf2); break; }
     }
+    if (i == 4) HXO_HIT(A_seek2_four);
     fnc_noise2_init(b);
     fnc_scale_factors(b);
     bits = quant_and_count(b);
     a->bitadjust = a->bitadjust + ((bits - nbits - a->bitadjust) >> 3);
     if ((tmp = b->min_bits - bits) > 0) {
         if (tmp > 200) tmp = 200;
+        if (tmp >> 2) HXO_HIT(A_minbits_corr);
         a->bitadjust = a->bitadjust - (tmp >> 2);
     }
     for (j = 0; j < 3; j++) {       /* spend more if below the minimum */
         if ((b->min_bits - bits) < 50) break;
+        if (j == 0) HXO_HIT(A_more_enter);
         dG = (int) (b->dGdB * (b->min_bits - bits));
         if (dG < 1) dG = 1;
         gz_flag = 0;
@@ -623,16 +627,18 @@ static int allo_2(a1_t *b)
             }
         fnc_scale_factors(b);
         bits = quant_and_count(b);
-        if (gz_flag == 0) break;
+        if (gz_flag == 0) { HXO_HIT(A_more_gz); break; }
     }
+    if (j == 3) HXO_HIT(A_more_three);
     for (j = 0; j < 100; j++) {     /* give back if above the maximum */
         if (bits <= b->max_cnt_bits) break;
+        if (j == 0) HXO_HIT(A_back_enter); else if (j == 1) HXO_HIT(A_back_several);
         dG = (int) (b->dGdB * (bits - b->max_cnt_bits));
         if (dG < 1) dG = 1;
         for (ch = 0; ch < b->nchan; ch++) for (i = 0; i < b->t->nsf[ch]; i++) a->gsf[ch][i] += dG;
         GG = fnc_scale_factors(b);
         bits = quant_and_count(b);
-        if (GG >= 100) break;
+        if (GG >= 100) { HXO_HIT(A_back_gg100); break; }
     }
     for (ch = 0; ch < b->nchan; ch++)
         for (i = 0; i < b->t->nsf[ch]; i++) if (b->ixmax[ch][i] <= 0) a->sf[ch][i] = 0;

@@ -19,6 +19,9 @@ extern float *hxo_tap_etab, *hxo_tap_thr, *hxo_tap_thr_short;
 extern int hxo_tap_igr;
 unsigned hxo_frames_out(const hxo_encoder *e) { return e->s.tot_frames_out; }
 unsigned hxo_bytes_out(const hxo_encoder *e) { return e->s.tot_bytes_out; }
+/* which kernel a stream of this configuration runs on (path census): bit 0 MPEG-1 rates, bit 1 first-generation allocator,
+   bit 2 mono, bit 3 -HF in force */
+int hxo_stream_kind(const hxo_encoder *e) { return e->p.h_id | (e->p.alloc1 << 1) | ((e->p.nchan == 1) << 2) | ((e->p.hf_flag != 0) << 3); }
 void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3])
 {
     const hxo_range_counts *c = &e->range[short_blocks ? 1 : 0];
@@ -687,6 +690,13 @@ static int encode_single_a1(hxo_encoder *e, hxo_bitw *w)
     return 0;
 }
 
+/* debug record: the long-block scalefactors of granule igr as the allocator left them */
+static void dbg_sf(hxo_encoder *e, int igr)
+{
+    int ch, i;
+    for (ch = 0; ch < e->p.nchan; ch++) for (i = 0; i < 22; i++) e->dbg->sf[igr][ch][i] = e->s.sf[igr][ch].l[i];
+}
+
 /* encode_jointA_MPEG2 (mp3enc.cpp:1753-1829) and encode_singleA_MPEG2 (:1910-1973): one granule = one frame */
 static int encode_granule_lsf_a1(hxo_encoder *e, hxo_bitw *w, int igr)
 {
@@ -716,12 +726,12 @@ static int encode_granule_lsf_a1(hxo_encoder *e, hxo_bitw *w, int igr)
             ba_max += ba_bit_max + p->sf_bit_max - bits;
             g->part2_3_length = bits;
         }
-        if (e->dbg) { memcpy(e->dbg->ix[igr], s->ix, sizeof(s->ix)); memcpy(e->dbg->signx[igr], s->signx, sizeof(s->signx)); }
+        if (e->dbg) { memcpy(e->dbg->ix[igr], s->ix, sizeof(s->ix)); memcpy(e->dbg->signx[igr], s->signx, sizeof(s->signx)); dbg_sf(e, igr); }
         return 0;
     }
     bit_max = s->byte_max << 3;
     bit_min = s->byte_min * (1 << 3);        /* (may be negative: a multiplication, not a shift) */
-    if (s->byte_pool > 245) bit_min += 40;
+    if (s->byte_pool > 245) { bit_min += 40; HXO_HIT(D_lsf_bitmin_40); }
     ba_max = HXO_MIN(bit_max, 4095) - 2 * p->sf_bit_max;
     ba_min = bit_min - 2 * p->sf_bit_max;
     transform_granule(e, igr);
@@ -734,7 +744,7 @@ static int encode_granule_lsf_a1(hxo_encoder *e, hxo_bitw *w, int igr)
     psy_long_all(e, igr);
     hxo_bitallo1(e, s->xr[igr], s->sig_mask, 0, 2, ba_min, p->AveTargetBits + p->AveTargetBits, ba_max, s->sf[igr], s->gr[igr],
                  s->ix, s->signx, ms);
-    if (e->dbg) { memcpy(e->dbg->ix[igr], s->ix, sizeof(s->ix)); memcpy(e->dbg->signx[igr], s->signx, sizeof(s->signx)); }
+    if (e->dbg) { memcpy(e->dbg->ix[igr], s->ix, sizeof(s->ix)); memcpy(e->dbg->signx[igr], s->signx, sizeof(s->signx)); dbg_sf(e, igr); }
     for (ch = 0; ch < 2; ch++) {
         hxo_gr *g = &s->gr[igr][ch];
         bits = 0;
@@ -759,7 +769,7 @@ static int encode_granule_lsf(hxo_encoder *e, hxo_bitw *w, int igr)
     bit_pool = s->byte_pool << 3;
     bit_max = s->byte_max << 3;
     bit_min = s->byte_min * (1 << 3);        /* (may be negative: a multiplication, not a shift) */
-    if (p->nchan == 2 && s->byte_pool > 245) bit_min += 40;
+    if (p->nchan == 2 && s->byte_pool > 245) { bit_min += 40; HXO_HIT(D_lsf_bitmin_40); }
     ba_max = bit_max;
     if (ba_max > 4095) ba_max = 4095;
     sf_bits = p->nchan * p->sf_bit_max;
@@ -789,6 +799,7 @@ static int encode_granule_lsf(hxo_encoder *e, hxo_bitw *w, int igr)
     if (e->dbg) {
         memcpy(e->dbg->ix[igr], s->ix, sizeof(s->ix));
         memcpy(e->dbg->signx[igr], s->signx, sizeof(s->signx));
+        dbg_sf(e, igr);
     }
     for (ch = 0; ch < p->nchan; ch++) {
         hxo_gr *g = &s->gr[igr][ch];
@@ -817,7 +828,7 @@ static int encode_block_lsf(hxo_encoder *e, unsigned char *out)
         pad = 0; ibr = 0;
         if (!p->vbr_flag) {
             s->padcount -= p->remainder;
-            if (s->padcount <= 0) { s->padcount += p->divisor; pad = 1; }
+            if (s->padcount <= 0) { s->padcount += p->divisor; pad = 1; HXO_HIT(D_cbr_padding_slot); }
             s->frame_mf_bytes[s->side_p1] = p->main_framebytes + pad;
         }
         s->frame_main_pos[s->side_p1] = s->main_tot;
@@ -832,6 +843,7 @@ static int encode_block_lsf(hxo_encoder *e, unsigned char *out)
         hxo_bw_init(&w, s->main_buf + s->main_p1);
         ms = p->alloc1 ? encode_granule_lsf_a1(e, &w, igr) : encode_granule_lsf(e, &w, igr);
         s->last_ms = ms;
+        if (ms) HXO_HIT(D_ms_frame); else HXO_HIT(D_lr_frame);
         s->mode_ext_buf[s->side_p1] = (unsigned char) (ms + ms + p->is_flag);
         bytes = hxo_bw_flush(&w);
         assert(bytes <= s->byte_max);
@@ -845,17 +857,23 @@ static int encode_block_lsf(hxo_encoder *e, unsigned char *out)
             int side_dp = (s->side_p1 - s->side_p0) & 31;
             for (ibr = p->ivbr_min; ibr <= p->ivbr_max; ibr++) if (bytes2 <= p->vbr_main_framebytes[ibr]) break;
             if (side_dp < 10) {
+                int ibr0 = ibr;
                 for (; ibr <= p->ivbr_max; ibr++) if (bytes3 < p->vbr_main_framebytes[ibr + 1]) break;
+                if (ibr > ibr0) HXO_HIT(D_vbr_pool_step);
             } else if (side_dp > 15) {      /* many frames span the pool: drain it through byte_min padding */
-                if (side_dp > 24) s->byte_min = p->vbr_main_framebytes[p->ivbr_min] + s->byte_pool;
-                else s->byte_min = p->vbr_main_framebytes[p->ivbr_min] + (s->byte_pool >> 4);
-            }
+                if (side_dp > 24) { HXO_HIT(D_lsf_vbr_span25); s->byte_min = p->vbr_main_framebytes[p->ivbr_min] + s->byte_pool; }
+                else { HXO_HIT(D_lsf_vbr_span16); s->byte_min = p->vbr_main_framebytes[p->ivbr_min] + (s->byte_pool >> 4); }
+            } else HXO_HIT(D_lsf_vbr_span10);
+            if (ibr > p->ivbr_max) HXO_HIT(D_vbr_limit_cut);
             if (ibr > p->ivbr_max) ibr = p->ivbr_max;
+            if (ibr == p->ivbr_min) HXO_HIT(D_vbr_ibr_min);
+            if (ibr == p->ivbr_max) HXO_HIT(D_vbr_ibr_max);
             s->br_index_buf[s->side_p1] = (unsigned char) ibr;
             s->frame_mf_bytes[s->side_p1] = p->vbr_main_framebytes[ibr];
         }
         raw_bytes = bytes;
         if (bytes < s->byte_min) {
+            HXO_HIT(D_pool_cap_stuffing);
             memset(s->main_buf + s->main_p1 + bytes, 0, s->byte_min - bytes);
             bytes = s->byte_min;
         }
@@ -926,7 +944,7 @@ int hxo_encode_frame(hxo_encoder *e, const float *pcm, unsigned char *out)
     if (!p->h_id) return encode_block_lsf(e, out);
     if (!p->vbr_flag) {
         s->padcount -= p->remainder;
-        if (s->padcount <= 0) { s->padcount += p->divisor; pad = 1; }
+        if (s->padcount <= 0) { s->padcount += p->divisor; pad = 1; HXO_HIT(D_cbr_padding_slot); }
         s->frame_mf_bytes[s->side_p1] = p->main_framebytes + pad;
     }
     s->frame_main_pos[s->side_p1] = s->main_tot;
@@ -942,6 +960,8 @@ int hxo_encode_frame(hxo_encoder *e, const float *pcm, unsigned char *out)
     if (p->alloc1) ms = (p->h_mode == 2) ? encode_single_a1(e, &w) : encode_joint_a1(e, &w);
     else ms = (p->nchan == 2) ? encode_joint(e, &w) : encode_single(e, &w);
     s->last_ms = ms;
+    if (ms) HXO_HIT(D_ms_frame); else HXO_HIT(D_lr_frame);
+    if (s->scfsi[0] | s->scfsi[1]) HXO_HIT(D_scfsi_shared);
     s->mode_ext_buf[s->side_p1] = (unsigned char) (ms + ms + p->is_flag);
     bytes = hxo_bw_flush(&w);
     assert(bytes <= s->byte_max);
@@ -954,13 +974,19 @@ int hxo_encode_frame(hxo_encoder *e, const float *pcm, unsigned char *out)
     if (p->vbr_flag) {
         int bytes2 = bytes - s->byte_pool, bytes3 = bytes2 + p->vbr_pool_target;
         for (ibr = p->ivbr_min; ibr <= p->ivbr_max; ibr++) if (bytes2 <= p->vbr_main_framebytes[ibr]) break;
-        for (; ibr <= p->ivbr_max; ibr++) if (bytes3 < p->vbr_main_framebytes[ibr + 1]) break;
+        { int ibr0 = ibr;
+          for (; ibr <= p->ivbr_max; ibr++) if (bytes3 < p->vbr_main_framebytes[ibr + 1]) break;
+          if (ibr > ibr0) HXO_HIT(D_vbr_pool_step); }
+        if (ibr > p->ivbr_max) HXO_HIT(D_vbr_limit_cut);
         if (ibr > p->ivbr_max) ibr = p->ivbr_max;
+        if (ibr == p->ivbr_min) HXO_HIT(D_vbr_ibr_min);
+        if (ibr == p->ivbr_max) HXO_HIT(D_vbr_ibr_max);
         s->br_index_buf[s->side_p1] = (unsigned char) ibr;
         s->frame_mf_bytes[s->side_p1] = p->vbr_main_framebytes[ibr];
     }
     raw_bytes = bytes;
     if (bytes < s->byte_min) {
+        HXO_HIT(D_pool_cap_stuffing);
         memset(s->main_buf + s->main_p1 + bytes, 0, s->byte_min - bytes);
         bytes = s->byte_min;
     }
@@ -1004,6 +1030,8 @@ int hxo_encode_frame(hxo_encoder *e, const float *pcm, unsigned char *out)
         s->side_p0 = (s->side_p0 + 1) & 31;
     }
     bytesout = (int) (out - out0);
+    if (bytesout == 0) HXO_HIT(D_no_frame_out);
+    else if (bytesout > 4 + p->side_bytes + s->frame_mf_bytes[(s->side_p0 - 1) & 31]) HXO_HIT(D_two_frames_out);
     s->tot_bytes_out += bytesout;
     s->ave_tot_bytes_out = s->ave_tot_bytes_out + ((((bytesout << 8) - s->ave_tot_bytes_out)) >> 7);
     if (s->main_p1 > 16384) {

@@ -388,10 +388,15 @@ int hxo_pack_sf_long_scfsi(hxo_bitw *w, int sf_save[21], const hxo_scalefact *sf
 /* l3pack.c:946-1119: returns part2_3_length (scalefactor bits since bit_pos_start + Huffman bits) */
 int hxo_pack_huff(hxo_bitw *w, const hxo_gr *g, const int *ix, const unsigned char *sign)
 {
-    int r, j, n, t, x, y, lin;
+    int r, j, n, t, x, y, lin, esc = 0;
+    if (g->big_values == 0) HXO_HIT(H_no_bigv);
+    if (g->big_values == 288) HXO_HIT(H_bigv_limit);
+    if (g->aux_nquads > 0) { if (g->count1table_select) HXO_HIT(H_count1_b); else HXO_HIT(H_count1_a); }
     for (r = 0; r < 3; r++) {
         n = g->aux_nreg[r];
         t = g->table_select[r];
+        if (n > 0) hxo_path_counts[HXO_P_H_tab0 + (t & 31)]++;
+        else if (g->big_values > 0 && g->block_type == 0) HXO_HIT(H_empty_region);
         if (hxo_huff_dim(t) != 0) {
             lin = hxo_huff_linbits(t);
             for (j = 0; j < n; j++) {
@@ -399,6 +404,7 @@ int hxo_pack_huff(hxo_bitw *w, const hxo_gr *g, const int *ix, const unsigned ch
                 if (t >= 16) {
                     int cx = x > 15 ? 15 : x, cy = y > 15 ? 15 : y;
                     hxo_bw_put(w, hxo_huff_code(t, cx, cy), hxo_huff_len(t, cx, cy));
+                    if ((cx >= 15 || cy >= 15) && lin) esc = 1;
                     if (cx >= 15) hxo_bw_put(w, x - 15, lin);
                     if (cx) hxo_bw_put(w, sign[2 * j], 1);
                     if (cy >= 15) hxo_bw_put(w, y - 15, lin);
@@ -413,6 +419,7 @@ int hxo_pack_huff(hxo_bitw *w, const hxo_gr *g, const int *ix, const unsigned ch
         ix += 2 * n;
         sign += 2 * n;
     }
+    if (esc) HXO_HIT(H_escape);
     n = g->aux_nquads;
     for (j = 0; j < n; j++, ix += 4, sign += 4) {
         int v = (ix[0] << 3) + (ix[1] << 2) + (ix[2] << 1) + ix[3];

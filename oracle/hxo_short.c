@@ -459,29 +459,36 @@ static void bump_gsf(sba_t *b, int delta, int only_over)
 {
     int ch, w, i;
     for (ch = 0; ch < b->nchan; ch++) {
-        if (only_over && b->huff_bits[ch] <= PART23) continue;
+        if (only_over && b->huff_bits[ch] <= PART23) { HXO_HIT(S_only_over_skip); continue; }
         for (w = 0; w < 3; w++)
             for (i = 0; i < b->nsf[ch]; i++)
                 b->gsf[ch][w][i] = (delta < 0) ? HXO_MAX(b->gsf[ch][w][i] - 1, 0) : HXO_MIN(127, b->gsf[ch][w][i] + 1);
     }
 }
 
+/* path census (hxo_int.h): how a rate loop that was entered left, from its round counter k */
+#define PATH_LOOP(name, rounds) do { HXO_HIT(name##_enter); \
+    if (k == 0) HXO_HIT(name##_first); else if (k < (rounds)) HXO_HIT(name##_several); else HXO_HIT(name##_cap); } while (0)
+
 /* bitallos.cpp:1450-1503 with :1279-1447 */
 static void allocate(sba_t *b)
 {
     int ch, w, i, k, bits, f, deltaN;
+    if (b->MNR < -200 && b->minTargetBits < ((3 * b->TargetBits) >> 2)) HXO_HIT(S_mnr_raise);
     if (b->MNR < -200) b->minTargetBits = HXO_MAX(b->minTargetBits, (3 * b->TargetBits) >> 2);
     seek_initial(b);
     seek_actual(b);
     scale_factors(b);
     do_quant(b, 1);
     b->FeedbackBits = bits = count_bits(b);
-    if (bits < b->minTargetBits)
+    if (bits < b->minTargetBits) {
         for (k = 0; k < 10; k++) {
             bump_gsf(b, -1, 0);
             scale_factors(b); do_quant(b, 1); bits = count_bits(b);
             if (bits >= b->minTargetBits) break;
         }
+        PATH_LOOP(S_inc, 10);
+    }
     if (bits > b->maxTargetBits) {
         f = (250 * 1024) / (b->activeBands + 10);
         deltaN = HXO_MAX((f * (bits - b->maxTargetBits)) >> 10, 40);
@@ -492,19 +499,24 @@ static void allocate(sba_t *b)
             if (bits <= b->maxTargetBits) break;
             deltaN = HXO_MAX((f * (bits - b->maxTargetBits)) >> 10, 40);
         }
+        PATH_LOOP(S_dec, 10);
     }
-    if (bits > b->maxBits)
+    if (bits > b->maxBits) {
         for (k = 0; k < 100; k++) {
             bump_gsf(b, 1, 0);
             scale_factors(b); do_quant(b, 0); bits = count_bits(b);
             if (bits <= b->maxBits) break;
         }
-    if (bits > PART23 && (b->huff_bits[0] > PART23 || b->huff_bits[1] > PART23))
+        PATH_LOOP(S_lim, 100);
+    }
+    if (bits > PART23 && (b->huff_bits[0] > PART23 || b->huff_bits[1] > PART23)) {
         for (k = 0; k < 100; k++) {
             bump_gsf(b, 1, 1);
             scale_factors(b); do_quant(b, 0); bits = count_bits(b);
             if ((b->huff_bits[0] <= PART23) && (b->huff_bits[1] <= PART23)) break;
         }
+        PATH_LOOP(S_p23, 100);
+    }
 }
 
 /* bitallos.cpp:202-369 */

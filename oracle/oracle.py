@@ -63,6 +63,8 @@ def lib():
         _lib.hxo_bytes_out.restype = C.c_uint
         _lib.hxo_range_counts_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
         _lib.hxo_range_counts_get.restype = None
+        _lib.hxo_stream_kind.argtypes = [C.c_void_p]
+        _lib.hxo_stream_kind.restype = C.c_int
     return _lib
 
 
@@ -299,3 +301,39 @@ def oracle_enable_stage_taps(enc):
     l.hxo_set_stage_taps(enc.h, C.byref(t))
     enc._taps = t
     return t
+
+
+# Path census (oracle/hxo_int.h, HXO_PATHS): the names of hxo_path_counts, in its order.  Not part of the encoder.
+# L_ long allocator, S_ short allocator, A_ first-generation allocator, H_ Huffman pick per coded channel-granule,
+# D_ frame driver; H_tab0 .. H_tab31 (a region of one or more pairs coded with that table) follow.
+PATH_NAMES = """
+    L_inc_ms L_inc_lr L_inc_hf L_inc_first L_inc_several L_inc_cap L_inc_gmin_hold L_inc_stepback L_dec_ms L_dec_lr
+    L_dec_one L_dec_several L_dec_cap L_dec_delta_floor L_dec_delta_formula L_dec_after_stepback L_lim_max
+    L_lim_max_several L_lim_p23_one L_lim_p23_both L_lim_after_dec_cap L_isf2_refined L_isf2_clamp_up
+    L_isf2_clamp_lo L_fb_dmnr_raised L_fb_dmnr_cut L_fb_mnr_cap L_fb_reset L_bt1_adjust L_bt3_adjust
+    L_short_mnr0_cbr L_short_mnr0_vbr S_inc_enter S_inc_first S_inc_several S_inc_cap S_dec_enter S_dec_first
+    S_dec_several S_dec_cap S_lim_enter S_lim_first S_lim_several S_lim_cap S_p23_enter S_p23_first S_p23_several
+    S_p23_cap S_mnr_raise S_only_over_skip A_seek1_dsf0 A_seek1_dsf2 A_seek1_four A_seek2_dsf0 A_seek2_dsf2
+    A_seek2_four A_minbits_corr A_more_enter A_more_gz A_more_three A_back_enter A_back_several A_back_gg100
+    H_count1_a H_count1_b H_escape H_bigv_limit H_empty_region H_no_bigv D_pool_cap_stuffing D_cbr_padding_slot
+    D_vbr_ibr_min D_vbr_ibr_max D_vbr_pool_step D_vbr_limit_cut D_ms_frame D_lr_frame D_scfsi_shared D_no_frame_out
+    D_two_frames_out D_lsf_bitmin_40 D_lsf_vbr_span10 D_lsf_vbr_span16 D_lsf_vbr_span25
+""".split() + ["H_tab%d" % t for t in range(32)]
+HUFF_TABLES = [t for t in range(32) if t not in (4, 14)]        # the format's 30 big-value table indices
+
+
+def path_counts():
+    """{name: count}: the branches every oracle encoder of this process has taken so far (hxo_path_counts)"""
+    l = lib()
+    l.hxo_path_count_n.restype = C.c_int
+    l.hxo_path_count_names.restype = C.c_char_p
+    assert l.hxo_path_count_n() == len(PATH_NAMES)
+    assert l.hxo_path_count_names().decode().split() == PATH_NAMES[:-32]
+    v = (C.c_longlong * len(PATH_NAMES)).in_dll(l, "hxo_path_counts")
+    return dict(zip(PATH_NAMES, (int(x) for x in v)))
+
+
+def path_counts_since(before):
+    """{name: count} of the entries counted since `before` (an earlier path_counts()), zero ones left out"""
+    now = path_counts()
+    return {k: now[k] - before[k] for k in PATH_NAMES if now[k] != before[k]}

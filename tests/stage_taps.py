@@ -100,21 +100,35 @@ class TapBatch:
     taken in some partition / held by the 0.1 * thr floor in some partition, and clamp_first: those of them that were a
     call's first granule; msscan_paths: which of k_msscan's loops the calls took ("vector": NG % 8 == 0, "scalar")."""
 
-    def __init__(self, api, kw, nstreams, max_frames, taps="full"):
-        self.api, self.kw, self.S, self.maxF, self.taps = api, kw, nstreams, max_frames, taps
-        self.mono = kw.get("mode") == 3
-        self.b = api.Batch(api.default_control(**kw), nstreams=nstreams, max_frames=max_frames)
+    def __init__(self, api, kw, nstreams, max_frames, taps="full", alloc_state=False):
+        """kw: one control, or a list of nstreams controls of one kind (channel count, MPEG version and allocator
+        generation in common; sample rates, bit rates and switches may differ).  alloc_state: compare the allocator's frame
+        record on the "lines" paths too (reservoir, MNR, main-data bytes, long-block scalefactors granule by granule), and
+        on the "full" path the scalefactors of the long granule of a frame that has a short one.  The scalefactors of short
+        granules are in neither record: they are compared through scalefac_compress in the side information and the bytes"""
+        self.api, self.S, self.maxF, self.taps, self.alloc_state = api, nstreams, max_frames, taps, alloc_state
+        self.kws = list(kw) if isinstance(kw, (list, tuple)) else [kw] * nstreams
+        assert len(self.kws) == nstreams
+        self.kw = self.kws[0]
+        self.mono = self.kw.get("mode") == 3
+        assert all((k.get("mode") == 3) == self.mono for k in self.kws)
+        if isinstance(kw, (list, tuple)):
+            self.b = api.Batch([api.default_control(**k) for k in self.kws], max_frames=max_frames)
+        else:
+            self.b = api.Batch(api.default_control(**kw), nstreams=nstreams, max_frames=max_frames)
         self.b.debug_enable(True)
-        tab = lambda name, n: host_table(api, kw, name, n)
-        self.np2 = int(tab("psy_npart", 1)[0] + 1) & ~1
-        self.mpart = int(tab("psy_short_npart", 1)[0] + 1) >> 1
-        self.alloc1 = int(tab("alloc1", 1)[0])
-        self.hf = int(tab("scalars", 16)[7])
-        self.nbmax, self.nbmax2, self.nbmax3 = tab("nbmax", 2), tab("nbmax2", 2), tab("nbmax3", 2)
-        self.start_l = tab("startBand_l", 23)
-        assert int(tab("sizeof_band_prep", 1)[0]) == C.sizeof(GBand)
-        assert 0 < self.mpart <= 12 and self.np2 <= 64
-        self.enc = [O.OracleEncoder(O.default_control(**kw)) for _ in range(nstreams)]
+        self.tabs = []
+        for k in self.kws:
+            tab = lambda name, n: host_table(api, k, name, n)
+            t = dict(np2=int(tab("psy_npart", 1)[0] + 1) & ~1, mpart=int(tab("psy_short_npart", 1)[0] + 1) >> 1,
+                     alloc1=int(tab("alloc1", 1)[0]), hf=int(tab("scalars", 16)[7]), nbmax=tab("nbmax", 2), nbmax2=tab("nbmax2", 2),
+                     nbmax3=tab("nbmax3", 2), start_l=tab("startBand_l", 23))
+            assert int(tab("sizeof_band_prep", 1)[0]) == C.sizeof(GBand)
+            assert 0 < t["mpart"] <= 12 and t["np2"] <= 64
+            self.tabs.append(t)
+        assert len({t["alloc1"] for t in self.tabs}) == 1
+        self._use(0)
+        self.enc = [O.OracleEncoder(O.default_control(**k)) for k in self.kws]
         self.dbg = [O.oracle_enable_debug(e) for e in self.enc]
         self.tap = [O.oracle_enable_stage_taps(e) for e in self.enc]      # (the taps beside the frame record: short model, start values, attack_prev)
         self.seen_bt = set()
@@ -131,6 +145,12 @@ class TapBatch:
 
     def close(self):
         self.b.close()
+
+    def _use(self, s):
+        """the host tables of stream s's control"""
+        t = self.tabs[s]
+        self.np2, self.mpart, self.alloc1, self.hf = t["np2"], t["mpart"], t["alloc1"], t["hf"]
+        self.nbmax, self.nbmax2, self.nbmax3, self.start_l = t["nbmax"], t["nbmax2"], t["nbmax3"], t["start_l"]
 
     def _prep(self, where, d, igr, xp, xmag, x34, band):
         """k_prep's outputs of one long granule against the allocator's start values in the oracle"""
@@ -172,7 +192,7 @@ class TapBatch:
         pcm = np.asarray(pcm)
         f32 = pcm.dtype == np.float32
         assert f32 or pcm.dtype == np.int16
-        b, S, mono, np2, mpart = self.b, self.S, self.mono, self.np2, self.mpart
+        b, S, mono = self.b, self.S, self.mono
         F = pcm.shape[1] // 1152
         NG = 2 * F
         assert pcm.shape[0] == S and pcm.shape[1] == F * 1152 and 0 < F <= self.maxF
@@ -206,6 +226,8 @@ class TapBatch:
                 assert got[s] == b"", ("bytes of a stream that took no frame", s)
                 continue
             enc, d, t = self.enc[s], self.dbg[s], self.tap[s]
+            self._use(s)
+            np2, mpart = self.np2, self.mpart
             where = lambda *a: (s, self.frames[s] + f) + a      # stream, frame of the stream
             out = []
             for f in range(cnt[s]):
@@ -274,6 +296,16 @@ class TapBatch:
                         assert np.array_equal(ggr[igr, ch], ogr[igr, ch, :24]), ("side info",) + where(igr, ch, bt)
                 if self.taps != "full":
                     self.sub_sb[s].append(0)
+                    if self.alloc_state:        # (at the MPEG-2 rates both records hold the block's second frame)
+                        assert gd.byte_pool == d.byte_pool and gd.main_bytes == d.main_bytes, ("reservoir",) + where(gd.byte_pool, d.byte_pool, gd.main_bytes, d.main_bytes)
+                        if not self.alloc1:
+                            assert gd.MNR_after == d.MNR_after, ("MNR",) + where(gd.MNR_after, d.MNR_after)
+                        gsf, osf = np.array(gd.sf).reshape(2, 2, 22), np.array(d.sf).reshape(2, 2, 22)
+                        for igr in range(2):
+                            if d.block_type[igr] != 2:
+                                for ch in range(nch):
+                                    if ogr[igr, ch, 20]:        # (a granule coded as nothing carries no scalefactors)
+                                        assert np.array_equal(gsf[igr, ch, :21], osf[igr, ch, :21]), ("scalefactors",) + where(igr, ch)
                     continue
                 sn = np.array(d.sample_new).reshape(2, 2, 576)
                 self.sub_sb[s].append(subnormals(sn))
@@ -286,6 +318,13 @@ class TapBatch:
                 if d.block_type[0] != 2 and d.block_type[1] != 2:
                     assert np.array_equal(np.array(gd.sf), np.array(d.sf)), where()
                     assert list(gd.scfsi) == list(d.scfsi), where()
+                elif self.alloc_state:      # a frame with a short granule: the scalefactors of its long (start / stop) granule
+                    gsf, osf = np.array(gd.sf).reshape(2, 2, 22), np.array(d.sf).reshape(2, 2, 22)
+                    for igr in range(2):
+                        if d.block_type[igr] != 2:
+                            for ch in range(2):
+                                if ogr[igr, ch, 20]:
+                                    assert np.array_equal(gsf[igr, ch, :21], osf[igr, ch, :21]), ("scalefactors",) + where(igr, ch)
             assert got[s] == b"".join(out), ("bytes", s, self.frames[s])
             self.got[s] += got[s]
             self.frames[s] += cnt[s]

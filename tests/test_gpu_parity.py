@@ -930,18 +930,29 @@ def test_edge_inputs_silence_fullscale_single_stream():
     b.close()
 
 
+# what the oracle counts on test_stress_signals_rare_paths' inputs (oracle.PATH_NAMES), per control
+STRESS_PATHS = {
+    "cbr96_lowrate": ["L_inc_ms", "L_inc_lr", "L_inc_cap", "L_dec_ms", "L_dec_cap", "L_fb_dmnr_raised", "L_fb_mnr_cap", "S_inc_enter", "S_dec_enter", "H_escape"],
+    "cbr320_highrate": ["L_inc_ms", "L_inc_lr", "L_inc_cap", "L_fb_mnr_cap", "S_inc_enter", "S_dec_enter", "H_escape"],
+    "vbr150_hf": ["L_inc_ms", "L_inc_hf", "S_dec_enter", "H_escape"],
+    "vbr0": ["L_inc_ms", "L_inc_cap", "H_escape"],
+    "cbr128_lr": ["L_inc_lr", "L_inc_cap", "L_dec_lr", "L_fb_dmnr_raised", "L_fb_mnr_cap", "S_inc_enter", "S_dec_enter", "H_escape"],
+}
+
+
 @pytest.mark.parametrize("name,kw", [
-    ("cbr96_lowrate", dict(bitrate=48)),                       # starved: decrease_bits / limit_bits / part2_3 cap
+    ("cbr96_lowrate", dict(bitrate=48)),                       # starved: decrease_bits to its ten-round cap
     ("cbr320_highrate", dict(bitrate=160)),                    # rich: increase_bits, large quantised values, linbits
     ("vbr150_hf", dict(vbr_mnr=150, hf_flag=3, freq_limit=22000)),
     ("vbr0", dict(vbr_mnr=0)),
     ("cbr128_lr", dict(bitrate=64, mode=0)),
 ])
 def test_stress_signals_rare_paths(name, kw):
-    """signals built to reach the allocator's rare branches: full-scale white noise (bit starvation, the
-    4021-bit part2_3 cap), a full-scale low tone (quantised values beyond the 256-entry x^(4/3) table ->
-    pow() path, escape codes), Nyquist alternation, DC offset, clicks in silence, hard-panned and
-    anti-phase channels, and a stream that changes character every few frames"""
+    """signals built to stress the allocator: full-scale white noise (bit starvation), a full-scale low tone (quantised
+    values beyond the 256-entry x^(4/3) table -> pow() path, escape codes), Nyquist alternation, DC offset, clicks in
+    silence, hard-panned and anti-phase channels, and a stream that changes character every few frames.  What they reach
+    is asserted from the oracle's path counters (STRESS_PATHS); they reach neither limit_bits nor the part2_3 cap nor the
+    step-back of increase_bits - tests/test_gpu_alloc_paths.py has inputs that do"""
     F = 36
     n = F * 1152
     rng = np.random.default_rng(77)
@@ -960,9 +971,13 @@ def test_stress_signals_rare_paths(name, kw):
     b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
+    before = O.path_counts()
     for s in range(S):
         assert got[s] == oracle_bytes(kw, pcm[s], F), "%s: stress stream %d" % (name, s)
     b.close()
+    reached = O.path_counts_since(before)
+    print(name, "reaches", sorted(reached))
+    assert all(reached.get(e, 0) > 0 for e in STRESS_PATHS[name]), sorted(set(STRESS_PATHS[name]) - set(reached))
 
 
 @pytest.mark.parametrize("kw", [dict(bitrate=64), dict(vbr_mnr=80), dict(bitrate=56, samprate=32000)], ids=["cbr128", "vbr80", "cbr112_32k"])
