@@ -70,6 +70,12 @@ class LedgerOpen(C.Structure):
     _fields_ = [(n, C.c_int) for n in ("ncalls", "head_bytes", "flags", "reserved")]
 
 
+class FileTag(C.Structure):
+    """HX_FILE_TAG: what a finished file's tag frame needs beside its record (include/hmp3_amd.h, "finished files")"""
+    _fields_ = [(n, C.c_int) for n in ("samprate", "h_mode", "cr_bit", "original_bit", "flags", "kbps", "vbr_scale")] + \
+        [(n, C.c_uint) for n in ("lowpass", "in_samplerate", "reserved")] + [("samples_audio", C.c_ulonglong)]
+
+
 # The ctypes type of every C type in include/hmp3_amd.h.  A parameter that is any other pointer or an array is a
 # c_void_p, which takes byref(...), ctypes arrays, string buffers, plain integers and None.
 CTYPES = {
@@ -237,6 +243,34 @@ def _file_fetch(fn, handle, i, cap, fill):
     if n < 0:
         raise RuntimeError("%s failed: %s" % (fn.__name__, last_error()))
     return buf[:n].tobytes()
+
+
+def file_tag_bytes(tag):
+    """the size of the tag frame a FileTag describes, 0 = none (hx_file_tag_bytes): the head_bytes of the file's ledger_begin"""
+    return int(lib().hx_file_tag_bytes(C.byref(tag)))
+
+
+def file_tag_build(rec, tag):
+    """the tag frame of a record, on the host (hx_file_tag_build) -> bytes, b"" where the function returns 0"""
+    buf = (C.c_ubyte * 1440)()
+    return bytes(buf[:int(lib().hx_file_tag_build(C.byref(rec), C.byref(tag), buf, 1440))])
+
+
+def _tag_array(tags, n):
+    tags = list(tags)
+    if len(tags) != n:
+        raise ValueError("%d tags for %d slots" % (len(tags), n))
+    return (FileTag * max(n, 1))(*tags)
+
+
+def _file_fetch_many(fn, handle, idx, cap, fill):
+    """-> (the dense image as fetched into a buffer of cap bytes pre-filled with `fill`, whole; off [n + 1]; the call's return)"""
+    idx = [int(i) for i in idx]
+    n = len(idx)
+    buf = np.full(max(int(cap), 1), fill, dtype=np.uint8)
+    off = np.full(n + 1, -1, dtype=np.int64)
+    r = int(fn(handle, (C.c_int * max(n, 1))(*idx), n, buf.ctypes.data, int(cap), off.ctypes.data))
+    return buf[:int(cap)], off, r
 
 
 def _files_status(name, r):
@@ -684,6 +718,28 @@ class Batch:
         """slot i's file (hx_batch_file_fetch) -> bytes: head_bytes of `fill`, which the call leaves alone, then the audio"""
         return _file_fetch(lib().hx_batch_file_fetch, self.h, i, cap, fill)
 
+    def file_tags(self, idx, tags, stream=None):
+        """the tag frame of slot idx[e]'s file, described by the FileTag tags[e], into the head room of its image
+        (hx_batch_file_tags): one launch, asynchronous on `stream`, ordered like a plain device call"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_file_tags(self.h, arr, _tag_array(tags, n), n, stream) != 0:
+            raise RuntimeError("hx_batch_file_tags failed: " + last_error())
+
+    def file_fetch_many(self, idx, cap, fill=0):
+        """the files of the slots in idx as one dense image (hx_batch_file_fetch_many) -> (the buffer of cap bytes, pre-filled
+        with `fill`, that took the image; off [n + 1]; off[n], the image's size); RuntimeError when the image does not fit cap"""
+        buf, off, r = _file_fetch_many(lib().hx_batch_file_fetch_many, self.h, idx, cap, fill)
+        if r < 0:
+            raise RuntimeError("hx_batch_file_fetch_many failed: " + last_error())
+        return buf, off, r
+
+    def file_gather_device(self, idx, d_dst_ptr, dst_cap, d_off_ptr, stream=None):
+        """the same image into device memory (16-byte aligned) and its offsets [len(idx) + 1] long long, asynchronous on
+        `stream` (hx_batch_file_gather_device)"""
+        arr, n = self._slots(idx)
+        if lib().hx_batch_file_gather_device(self.h, arr, n, d_dst_ptr, int(dst_cap), d_off_ptr, stream) != 0:
+            raise RuntimeError("hx_batch_file_gather_device failed: " + last_error())
+
     def encode_host_files(self, pcm):
         """encode_host that brings nothing down but the status (hx_batch_encode_*_host_files) -> the status bits"""
         pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
@@ -1002,6 +1058,20 @@ class Multi:
     def file_fetch(self, i, cap, fill=0):
         """as Batch.file_fetch, i over all blocks (hx_multi_file_fetch)"""
         return _file_fetch(lib().hx_multi_file_fetch, self.h, i, cap, fill)
+
+    def file_tags(self, idx, tags):
+        """as Batch.file_tags over all blocks, synchronous (hx_multi_file_tags)"""
+        idx = [int(i) for i in idx]
+        n = len(idx)
+        if lib().hx_multi_file_tags(self.h, (C.c_int * max(n, 1))(*idx), _tag_array(tags, n), n) != 0:
+            raise RuntimeError("hx_multi_file_tags failed: " + last_error())
+
+    def file_fetch_many(self, idx, cap, fill=0):
+        """as Batch.file_fetch_many, idx over all blocks (hx_multi_file_fetch_many)"""
+        buf, off, r = _file_fetch_many(lib().hx_multi_file_fetch_many, self.h, idx, cap, fill)
+        if r < 0:
+            raise RuntimeError("hx_multi_file_fetch_many failed: " + last_error())
+        return buf, off, r
 
     def encode_host_files(self, pcm):
         """as Batch.encode_host_files, over all streams"""

@@ -238,6 +238,18 @@ struct Tagger {
         if ((head_flags & 4) && --toc_counter <= 0) toc_counter = hx_xing_toc(xg, (int) frames_out + 1, (int) bytes_out + head_bytes);
     }
     void bytes(const unsigned char *p, int n) { crc = hx_xing_update_crc((unsigned short) crc, p, n); }
+    // what begin() and finish() pass, for the tag frame that the GPU builds from the file's record (hx_multi_file_tags); a
+    // file without a tag: all zero, which describes no frame
+    HX_FILE_TAG describe(const Input &in) const
+    {
+        HX_FILE_TAG t = {};
+        if (!head_bytes) return t;
+        t.samprate = in.ec_used.samprate; t.h_mode = in.head.mode; t.cr_bit = in.ec_used.cr_bit; t.original_bit = in.ec_used.original;
+        t.flags = head_flags; t.kbps = in.ec_used.bitrate * in.wi.channels; t.vbr_scale = vbr_scale;
+        t.lowpass = (unsigned) in.ec_used.freq_limit; t.in_samplerate = (unsigned) in.wi.rate;
+        t.samples_audio = in.audio_bytes / (uint64_t) (in.wi.channels * (in.wi.bits / 8));
+        return t;
+    }
     void finish(const Input &in, unsigned frames, uint64_t out_bytes)
     {
         const uint64_t samples_audio = in.audio_bytes / (uint64_t) (in.wi.channels * (in.wi.bits / 8));
@@ -256,8 +268,8 @@ struct Job {
     int nch = 0;                        // channels the file encodes to (mono, or stereo summed to mono: 1)
     size_t nc = 0;                      // calls of the single-file loop on the file's input (the drain follows them)
     std::vector<long long> start;       // converting route: where each of them starts in the file's bytes
-    std::vector<unsigned char> stream;  // the file's audio bytes; whole: the output file as fetched from its file image, the tag frame's
-    bool whole = false;                 // room in front
+    std::vector<unsigned char> stream;  // the file's audio bytes; whole: the output file as fetched from its file image, the tag frame
+    bool whole = false;                 // (built on the GPU, k_file_tag) in front
     size_t est_calls = 0;               // -slots: an upper bound of nc from the header alone (0: the header does not say)
     HX_LEDGER led = {};                 // the file's record as last read from the batch's ledger: calls fed, frames / bytes out so far,
                                         // the MusicCRC of those bytes, the seek points; ended: the drain has ended, it takes no more frames
@@ -531,31 +543,39 @@ bool job_control(Job &j, const char *name, const Options &opt, bool conv)
 bool job_write(Job &j, const char *name, const Options &opt)
 {
     const Input &in = j.in;
-    Tagger tg;
-    tg.begin(in, opt.xing_flag);
-    // the ledger has made the tagger's calls on the device (k_ledger): one seek point per input call, the end of the drain
-    // (while (get_frames() < frames_expected) encode silence) and the CRC up to there
     bool ok = true;
     if (!j.led.ended) { fprintf(stderr, "\n %s: drain did not complete\n", name); ok = false; }
     const unsigned frames = j.led.frames, nbytes = j.led.bytes;
-    tg.crc = j.led.crc;
-    hx_xing_load_points(tg.xg, &j.led);
-    const uint64_t out_bytes = (uint64_t) tg.head_bytes + nbytes;
-    if (opt.xing_flag) tg.finish(in, frames, out_bytes);
+    const uint64_t out_bytes = (uint64_t) j.led.head_bytes + nbytes;
     FILE *o = fopen(name, "wb");
     if (!o) { fprintf(stderr, "\n CANNOT CREATE OUTPUT FILE %s\n", name); return false; }
     if (j.whole) {
-        // (the file came down once, from its image on the GPU, behind room for the tag frame)
+        // (the file came down once, from its image on the GPU, the tag frame in front of it: built there from the file's
+        // record, k_file_tag - it is written as it came)
         if (j.stream.size() != (size_t) out_bytes) { fprintf(stderr, "\n %s: the file image holds %zu bytes of %llu\n", name, j.stream.size(), (unsigned long long) out_bytes); ok = false; }
-        else memcpy(j.stream.data(), tg.tag.data(), (size_t) tg.head_bytes);
         fwrite(j.stream.data(), 1, std::min<size_t>(j.stream.size(), (size_t) out_bytes), o);
     } else {
+        // the ledger has made the tagger's calls on the device (k_ledger): one seek point per input call, the end of the drain
+        // (while (get_frames() < frames_expected) encode silence) and the CRC up to there
+        Tagger tg;
+        tg.begin(in, opt.xing_flag);
+        tg.crc = j.led.crc;
+        hx_xing_load_points(tg.xg, &j.led);
+        if (opt.xing_flag) tg.finish(in, frames, out_bytes);
         fwrite(tg.tag.data(), 1, tg.head_bytes, o);
         fwrite(j.stream.data(), 1, nbytes, o);
     }
     fclose(o);
     fprintf(stderr, "\n %s: %u frames, %llu bytes", name, frames, (unsigned long long) out_bytes);
     return ok;
+}
+
+// the description of a file's tag frame (Tagger::begin, Tagger::finish), for the GPU to build it from the file's record
+HX_FILE_TAG job_tag(const Job &j, const Options &opt)
+{
+    Tagger tg;
+    tg.begin(j.in, opt.xing_flag);
+    return tg.describe(j.in);
 }
 
 // what the batch's ledger takes for a file when the file gets its slot (the tag frame's size and whether it has seek
@@ -640,7 +660,9 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
     std::vector<HX_LEDGER> led(NS);
     // File images: the bytes the ledger gives to a file are put behind the file's bytes so far in the slot's image on the GPU
     // (k_file_append), so a call brings down its status and one short record per slot, and a file comes down once, when it
-    // has ended.  An image holds the largest file of the run at the bound of hx_multi_out_stride: every block it is fed, the
+    // has ended: the files that end in a call get their tag frames built into their images' head room (k_file_tag, from the
+    // records on the device) and come down together as one dense image (hx_multi_file_tags, hx_multi_file_fetch_many).  An
+    // image holds the largest file of the run at the bound of hx_multi_out_stride: every block it is fed, the
     // drain's included, at the size of the largest frames a block can yield, behind the tag frame.  Where the device cannot
     // hold that for every slot, the rows come back with every call as before.
     bool use_img = true;
@@ -659,6 +681,10 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
         }
     }
     std::vector<HX_LEDGER_BRIEF> brief(NS);
+    std::vector<int> done;                              // the slots whose files have finished in this call, their tags' descriptions,
+    std::vector<HX_FILE_TAG> done_tag;                  // and their files as one image: segment e at many_off[e]
+    std::vector<unsigned char> many;
+    std::vector<long long> many_off;
     for (int s = 0; s < NS; s++) { fed_slot.push_back(s); take_open[s] = job_ledger(jobs[s], opt); }
     if (hx_multi_ledger_begin(b, fed_slot.data(), take_open.data(), NS) != 0) {
         fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
@@ -733,24 +759,43 @@ int encode_jobs(std::vector<Job> &jobs, const std::vector<const char *> &files, 
             hx_multi_destroy(b);
             return 1;
         }
+        done.clear(); done_tag.clear();
+        for (size_t e = 0; e < fed_slot.size() && use_img; e++) {
+            // the short record says how far the file is; when it has ended (or reached its drain bound) it is one of this call's
+            // finished files
+            const int s = fed_slot[e];
+            Job &j = jobs[held[s]];
+            const HX_LEDGER_BRIEF &r = brief[s];
+            j.led.open = r.open; j.led.ended = r.ended; j.led.fed = r.fed; j.led.frames = r.frames; j.led.bytes = r.bytes; j.led.crc = r.crc;
+            j.led.call_bytes = r.call_bytes;
+            if (!(j.led.ended || (size_t) j.led.fed >= j.nc + DRAIN)) continue;
+            done.push_back(s);
+            done_tag.push_back(job_tag(j, opt));
+        }
+        if (!done.empty()) {
+            // one launch builds their tag frames, two launches and two copies bring them down, however many they are
+            const int n = (int) done.size();
+            long long need = 0;
+            for (int s : done) need += ((long long) jobs[held[s]].led.head_bytes + brief[s].image_bytes + 15) & ~15LL;
+            many.resize((size_t) std::max(need, 16LL));
+            many_off.assign((size_t) n + 1, 0);
+            if (hx_multi_file_tags(b, done.data(), done_tag.data(), n) != 0 ||
+                hx_multi_file_fetch_many(b, done.data(), n, many.data(), (long long) many.size(), many_off.data()) != need) {
+                fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
+                hx_multi_destroy(b);
+                return 1;
+            }
+            for (int e = 0; e < n; e++) {
+                Job &j = jobs[held[done[e]]];
+                const size_t len = (size_t) j.led.head_bytes + brief[done[e]].image_bytes;
+                j.stream.assign(many.begin() + many_off[e], many.begin() + many_off[e] + (long long) len);
+                j.whole = true;
+            }
+        }
         for (size_t e = 0; e < fed_slot.size(); e++) {
             const int s = fed_slot[e];
             Job &j = jobs[held[s]];
-            if (use_img) {
-                // the short record says how far the file is; when it has ended (or reached its drain bound) the whole record
-                // comes down for the seek points, and the file, from its image, behind room for the tag frame
-                const HX_LEDGER_BRIEF &r = brief[s];
-                j.led.open = r.open; j.led.ended = r.ended; j.led.fed = r.fed; j.led.frames = r.frames; j.led.bytes = r.bytes; j.led.crc = r.crc;
-                j.led.call_bytes = r.call_bytes;
-                if (!(j.led.ended || (size_t) j.led.fed >= j.nc + DRAIN)) continue;
-                j.stream.resize((size_t) j.led.head_bytes + r.image_bytes);
-                j.whole = true;
-                if (hx_multi_ledger_read(b, &s, 1, &j.led) != 0 || hx_multi_file_fetch(b, s, j.stream.data(), (long long) j.stream.size()) != (long long) j.stream.size()) {
-                    fprintf(stderr, "\n ENCODE FAIL: %s\n", hx_last_error());
-                    hx_multi_destroy(b);
-                    return 1;
-                }
-            } else {
+            if (!use_img) {
                 // the bytes of this call's row that belong to the file: all of it, or up to the frame at which its drain ended
                 j.led = led[e];
                 j.stream.insert(j.stream.end(), out.begin() + (size_t) s * stride, out.begin() + (size_t) s * stride + j.led.call_bytes);

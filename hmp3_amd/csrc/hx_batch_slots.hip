@@ -292,7 +292,8 @@ int ledger_begin(hx_batch *b, const int *idx, const HX_LEDGER_OPEN *open, int n,
     if (wait && drain(b) != 0) return -1;
     if (ledger_op(b, idx, open, n, nullptr, q) != 0) return -1;
     if (b->led_head.empty()) b->led_head.assign(b->S, 0);
-    for (int e = 0; e < n; e++) { b->led_live[idx[e]] = 1; b->led_head[idx[e]] = open[e].head_bytes; }     // (the host's view moves when the call is made, like a slot's configuration)
+    if (b->led_img.empty()) b->led_img.assign(b->S, 0);
+    for (int e = 0; e < n; e++) { b->led_live[idx[e]] = 1; b->led_head[idx[e]] = open[e].head_bytes; b->led_img[idx[e]] = b->files.img ? 1 : 0; }     // (the host's view moves when the call is made, like a slot's configuration)
     if (wait) HIPCHK(hipStreamSynchronize(q));
     return 0;
 }
@@ -393,6 +394,9 @@ int images_commit(hx_batch *b, const FileImages &next)
     if (fw) HIPCHK(hipMemset(fw, 0, sizeof(unsigned) * 2 * (size_t) b->S));
     // (nothing fails from here on: a commit that returns -1 has not taken `next`)
     dev_release(b, b->files.img);
+    dev_release(b, b->d_many);          // (the fetch of many's staging goes with the images it was sized for)
+    b->d_many = nullptr; b->many_cap = 0;
+    std::fill(b->led_img.begin(), b->led_img.end(), 0);     // (records begun before a switch have no image)
     b->files = next;
     b->files.fw = fw;
     return 0;
@@ -466,4 +470,165 @@ extern "C" long long hx_batch_file_fetch(hx_batch *b, int i, unsigned char *dst,
     }
     if (w[0]) HIPCHK(hipMemcpy(dst + head, b->files.img + (long long) i * b->files.pitch + head, (size_t) w[0], hipMemcpyDeviceToHost));
     return total;
+}
+
+// ---- finished files (include/hmp3_amd.h, "finished files"; kernels: hx_fileimg.hip) ----
+// hx_batch_file_tags is a slot operation like hx_batch_ledger_begin; its entries are larger than a slot entry and go through
+// a staging of their own, in the same rotation.  The fetch of many lists slots like a ledger read.
+
+static int not_capturing(hipStream_t q, const char *what)
+{
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    if (hipStreamIsCapturing(q, &cs) != hipSuccess) { (void) hipGetLastError(); return 0; }    // (the null stream while another captures: the call's own launches will say)
+    if (cs == hipStreamCaptureStatusNone) return 0;
+    set_err("%s is not made under stream capture", what);
+    return -1;
+}
+
+int files_refused(const hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, const int *entry, int first)
+{
+    char msg[192];
+    if (!b->files.img) { set_err("file images are off (hx_batch_file_images)"); return -1; }
+    for (int e = 0; e < n && tags; e++) {
+        const int s = idx[e], en = entry ? entry[e] : e, name = first + s;
+        if (b->led_img.empty() || !b->led_img[s]) {
+            snprintf(msg, sizeof msg, "entry %d: slot %d's record was not begun with an image (hx_batch_ledger_begin while images are on)", en, name);
+            set_err("%s", msg);
+            return -1;
+        }
+        const int size = hx_file_tag_bytes(&tags[e]);
+        if (size != b->led_head[s]) {
+            snprintf(msg, sizeof msg, "entry %d: the tag frame takes %d bytes, slot %d's record was begun with head_bytes %d", en, size, name, b->led_head[s]);
+            set_err("%s", msg);
+            return -1;
+        }
+    }
+    return 0;
+}
+
+int file_tags(hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, void *stream, bool wait)
+{
+    const hipStream_t q = (hipStream_t) stream;
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && !tags) { set_err("tags is null with n > 0"); return -1; }
+    if (n == 0) return 0;
+    if (files_refused(b, idx, tags, n, nullptr, 0) != 0) return -1;
+    HIPCHK(hipSetDevice(b->device));
+    if (not_capturing(q, "hx_batch_file_tags") != 0) return -1;
+    int live = 0;
+    for (int e = 0; e < n; e++) live += b->led_head[idx[e]] > 0;
+    if (!live) return 0;        // (no listed slot has a head room: nothing to write)
+    if (wait && drain(b) != 0) return -1;
+    Staging &s = b->tag_stage;
+    if (!s.d && staging_make(b, s, sizeof(HxFileTagEntry) * (size_t) b->S) != 0) return -1;
+    Poison poison{b};
+    if (b->inflight) {
+        if (order_behind_submits(b, q) != 0) return -1;
+        b->inflight = false;
+    }
+    const int k = (int) (b->nslotops++ % 3);
+    HxFileTagEntry *h = (HxFileTagEntry *) staging_take(s, k);
+    if (!h) return -1;
+    int m = 0;
+    for (int e = 0; e < n; e++) {
+        if (b->led_head[idx[e]] <= 0) continue;
+        h[m] = HxFileTagEntry{idx[e], {0, 0, 0}, {0, 0, 0, 0, 0, 0}};
+        memcpy(h[m].tag, &tags[e], sizeof(HX_FILE_TAG));
+        m++;
+    }
+    if (staging_upload(s, k, sizeof(HxFileTagEntry) * (size_t) m, q) != 0) return -1;
+    LAUNCH(k_file_tag, dim3((unsigned) m), dim3(256), q, (const HX_LEDGER *) b->d_ledger, (const uint2 *) b->files.fw, b->files.img, b->files.pitch, b->files.cap,
+           (const HxFileTagEntry *) s.dev<HxFileTagEntry>(k));
+    if (staging_done(s, k, q) != 0) return -1;
+    if (poison.ok() != 0) return -1;
+    if (wait) HIPCHK(hipStreamSynchronize(q));
+    return 0;
+}
+extern "C" int hx_batch_file_tags(hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, void *stream)
+{
+    return file_tags(b, idx, tags, n, stream, false);
+}
+
+// the list on stream q through the slot operations' staging (copy k of the rotation, returned), then k_file_off into d_off
+static int files_off_op(hx_batch *b, const int *idx, int n, long long *d_off, long long dst_cap, hipStream_t q, int &k)
+{
+    Staging &s = b->ent_stage;
+    if (!s.d && staging_make(b, s, sizeof(HxSlotEntry) * (size_t) b->S) != 0) return -1;
+    if (b->inflight) {
+        if (order_behind_submits(b, q) != 0) return -1;
+        b->inflight = false;
+    }
+    k = (int) (b->nslotops++ % 3);
+    HxLedgerEntry *h = (HxLedgerEntry *) staging_take(s, k);
+    if (!h) return -1;
+    for (int e = 0; e < n; e++) h[e] = HxLedgerEntry{idx[e], 0, 0, 0, 0};
+    if (staging_upload(s, k, sizeof(HxLedgerEntry) * (size_t) n, q) != 0) return -1;
+    LAUNCH(k_file_off, dim3(1), dim3(1024), q, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), n, (const HX_LEDGER *) b->d_ledger, (const uint2 *) b->files.fw,
+           b->files.cap, d_off, dst_cap, b->d_status);
+    return 0;
+}
+// ... and k_file_gather over that list into d_dst; the copy's event goes behind it
+static int files_gather_op(hx_batch *b, int n, int k, const long long *d_off, unsigned char *d_dst, long long dst_cap, hipStream_t q)
+{
+    Staging &s = b->ent_stage;
+    const int chunks = (int) ((b->files.pitch + HX_FILE_GATHER_CHUNK - 1) / HX_FILE_GATHER_CHUNK);
+    LAUNCH(k_file_gather, dim3((unsigned) ((long long) n * chunks)), dim3(256), q, (const HxLedgerEntry *) s.dev<HxLedgerEntry>(k), (const HX_LEDGER *) b->d_ledger,
+           (const uint2 *) b->files.fw, (const unsigned char *) b->files.img, b->files.pitch, b->files.cap, d_off, d_dst, dst_cap, chunks);
+    return staging_done(s, k, q);
+}
+
+extern "C" int hx_batch_file_gather_device(hx_batch *b, const int *idx, int n, unsigned char *d_dst, long long dst_cap, long long *d_off, void *stream)
+{
+    const hipStream_t q = (hipStream_t) stream;
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && (!d_dst || !d_off)) { set_err("d_dst or d_off is null with n > 0"); return -1; }
+    if (((unsigned long long) d_dst & 15) != 0) { set_err("d_dst must be 16-byte aligned"); return -1; }
+    if (((unsigned long long) d_off & 7) != 0) { set_err("d_off must be 8-byte aligned"); return -1; }
+    if (dst_cap < 0) { set_err("dst_cap < 0"); return -1; }
+    if (n == 0) return 0;
+    if (files_refused(b, idx, nullptr, n, nullptr, 0) != 0) return -1;
+    HIPCHK(hipSetDevice(b->device));
+    if (not_capturing(q, "hx_batch_file_gather_device") != 0) return -1;
+    Poison poison{b};
+    int k = 0;
+    if (files_off_op(b, idx, n, d_off, dst_cap, q, k) != 0 || files_gather_op(b, n, k, d_off, d_dst, dst_cap, q) != 0) return -1;
+    return poison.ok();
+}
+
+int files_many_scan(hx_batch *b, const int *idx, int n, long long *off)
+{
+    if (drain(b) != 0) return -1;
+    HIPCHK(hipSetDevice(b->device));
+    if (!b->d_many_off && dev_alloc(b, b->d_many_off, (long long) sizeof(long long) * (b->S + 1)) != 0) return -1;
+    Poison poison{b};
+    if (files_off_op(b, idx, n, b->d_many_off, LLONG_MAX, nullptr, b->many_k) != 0) return -1;
+    if (staging_done(b->ent_stage, b->many_k, nullptr) != 0) return -1;       // (a refused fetch launches no gather behind it)
+    HIPCHK(hipMemcpy(off, b->d_many_off, sizeof(long long) * (size_t) (n + 1), hipMemcpyDeviceToHost));
+    return poison.ok();
+}
+int files_many_bring(hx_batch *b, int n, long long total, unsigned char *dst)
+{
+    if (total <= 0) return 0;
+    HIPCHK(hipSetDevice(b->device));
+    if (dev_grow(b, b->d_many, b->many_cap, total) != 0) { (void) hipGetLastError(); return -1; }
+    Poison poison{b};
+    if (files_gather_op(b, n, b->many_k, b->d_many_off, b->d_many, total, nullptr) != 0) return -1;
+    HIPCHK(hipMemcpy(dst, b->d_many, (size_t) total, hipMemcpyDeviceToHost));
+    return poison.ok();
+}
+extern "C" long long hx_batch_file_fetch_many(hx_batch *b, const int *idx, int n, unsigned char *dst, long long dst_cap, long long *off)
+{
+    if (slots_check(b, idx, n, false, nullptr, 0, false) != 0) return -1;
+    if (n > 0 && (!dst || !off)) { set_err("dst or off is null with n > 0"); return -1; }
+    if (n == 0) { if (off) off[0] = 0; return 0; }
+    if (files_refused(b, idx, nullptr, n, nullptr, 0) != 0) return -1;
+    if (files_many_scan(b, idx, n, off) != 0) return -1;
+    if (off[n] > dst_cap) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "the files' %lld bytes do not fit dst_cap %lld", off[n], dst_cap);
+        set_err("%s", msg);
+        return -1;
+    }
+    if (files_many_bring(b, n, off[n], dst) != 0) return -1;
+    return off[n];
 }

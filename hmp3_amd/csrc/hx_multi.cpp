@@ -492,6 +492,66 @@ extern "C" long long hx_multi_file_fetch(hx_multi *m, int i, unsigned char *dst,
     while (k + 1 < m->part.size() && i >= m->first[k + 1]) k++;
     return hx_batch_file_fetch(m->part[k], i - m->first[k], dst, dst_cap);
 }
+// hx_batch_file_tags / hx_batch_file_fetch_many over all blocks ("finished files"): the list's own errors with the caller's
+// entry numbers (multi_ledger_split), then what each block refuses about its files, for all blocks before one starts
+static int multi_files_split(hx_multi *m, const int *idx, const HX_FILE_TAG *tags, int n, std::vector<std::vector<int>> &bi,
+                             std::vector<std::pair<size_t, size_t>> &where, std::vector<std::vector<HX_FILE_TAG>> &bt)
+{
+    if (multi_ledger_split(m, idx, nullptr, false, idx, n, bi, where) != 0) return -1;      // (out: the callers have checked their own outputs; any non-null pointer passes the split's test)
+    std::vector<std::vector<int>> entry(bi.size());
+    bt.assign(bi.size(), std::vector<HX_FILE_TAG>());
+    for (int e = 0; e < n; e++) {
+        entry[where[e].first].push_back(e);
+        if (tags) bt[where[e].first].push_back(tags[e]);
+    }
+    for (size_t k = 0; k < bi.size(); k++)
+        if (!bi[k].empty() && files_refused(m->part[k], bi[k].data(), tags ? bt[k].data() : nullptr, (int) bi[k].size(), entry[k].data(), m->first[k]) != 0) return -1;
+    return 0;
+}
+extern "C" int hx_multi_file_tags(hx_multi *m, const int *idx, const HX_FILE_TAG *tags, int n)
+{
+    if (m && n > 0 && !tags) { set_err("tags is null with n > 0"); return -1; }
+    std::vector<std::vector<int>> bi;
+    std::vector<std::pair<size_t, size_t>> where;
+    std::vector<std::vector<HX_FILE_TAG>> bt;
+    if (multi_files_split(m, idx, tags, n, bi, where, bt) != 0) return -1;
+    for (size_t k = 0; k < bi.size(); k++)
+        if (!bi[k].empty() && file_tags(m->part[k], bi[k].data(), bt[k].data(), (int) bi[k].size(), nullptr, true) != 0) return -1;
+    return 0;
+}
+// every block scans its part of the list; the caller's offsets follow from the blocks' (a segment's rounded length is the
+// difference of two of them); then every block brings its dense image down and the segments go to their places in dst, each
+// with its zero padding
+extern "C" long long hx_multi_file_fetch_many(hx_multi *m, const int *idx, int n, unsigned char *dst, long long dst_cap, long long *off)
+{
+    if (m && n > 0 && (!dst || !off)) { set_err("dst or off is null with n > 0"); return -1; }
+    std::vector<std::vector<int>> bi;
+    std::vector<std::pair<size_t, size_t>> where;
+    std::vector<std::vector<HX_FILE_TAG>> bt;
+    if (multi_files_split(m, idx, nullptr, n, bi, where, bt) != 0) return -1;
+    if (n == 0) { if (off) off[0] = 0; return 0; }
+    std::vector<std::vector<long long>> bo(bi.size());
+    for (size_t k = 0; k < bi.size(); k++) {
+        bo[k].assign(bi[k].size() + 1, 0);
+        if (!bi[k].empty() && files_many_scan(m->part[k], bi[k].data(), (int) bi[k].size(), bo[k].data()) != 0) return -1;
+    }
+    off[0] = 0;
+    for (int e = 0; e < n; e++) off[e + 1] = off[e] + bo[where[e].first][where[e].second + 1] - bo[where[e].first][where[e].second];
+    if (off[n] > dst_cap) {
+        char msg[128];
+        snprintf(msg, sizeof msg, "the files' %lld bytes do not fit dst_cap %lld", off[n], dst_cap);
+        set_err("%s", msg);
+        return -1;
+    }
+    std::vector<std::vector<unsigned char>> img(bi.size());
+    for (size_t k = 0; k < bi.size(); k++) {
+        img[k].resize((size_t) bo[k].back());
+        if (!bi[k].empty() && files_many_bring(m->part[k], (int) bi[k].size(), bo[k].back(), img[k].data()) != 0) return -1;
+    }
+    for (int e = 0; e < n; e++)
+        if (off[e + 1] > off[e]) memcpy(dst + off[e], img[where[e].first].data() + bo[where[e].first][where[e].second], (size_t) (off[e + 1] - off[e]));
+    return off[n];
+}
 // the *_host_files calls: ledger and images of every block checked before one starts; the blocks' status bits or'ed
 static int multi_check_files(const hx_multi *m)
 {

@@ -70,6 +70,10 @@ __global__ void k_file_append(const HX_LEDGER *led, uint2 *fw, unsigned char *im
                               const int *nfr, int nframes, int chunks, int *status);
 __global__ void k_file_begin(uint2 *fw, const HxLedgerEntry *ent, int n, unsigned on);
 __global__ void k_ledger_brief(const HX_LEDGER *led, const uint2 *fw, HX_LEDGER_BRIEF *out, int S);
+__global__ void k_file_tag(const HX_LEDGER *led, const uint2 *fw, unsigned char *img, long long pitch, long long cap, const HxFileTagEntry *ent);
+__global__ void k_file_off(const HxLedgerEntry *ent, int n, const HX_LEDGER *led, const uint2 *fw, long long cap, long long *off, long long dst_cap, int *status);
+__global__ void k_file_gather(const HxLedgerEntry *ent, const HX_LEDGER *led, const uint2 *fw, const unsigned char *img, long long pitch, long long cap,
+                              const long long *off, unsigned char *dst, long long dst_cap, int chunks);
 __global__ void k_order(const unsigned *dur, int *order, int S);
 __global__ void k_order_kinds(const unsigned *dur, const HxStream *st, const HxParams *prm, int *order, int S);
 __global__ void k_gate(const unsigned *done_counter, unsigned base, unsigned need, int *timeouts);
@@ -234,6 +238,15 @@ struct hx_batch {
     // (its latest hx_batch_ledger_begin's; it moves when that call is made, like led_live)
     FileImages files;
     std::vector<int> led_head;
+    // finished files (hx_batch_file_tags, hx_batch_file_fetch_many): which slots' latest begin was made with images on (like
+    // led_head); the tag entries' staging, [S] HxFileTagEntry per copy, made at the first hx_batch_file_tags, in the slot
+    // operations' rotation (nslotops); the host fetch's device staging - the dense image, grown to the largest total so far and
+    // released with the images, and its offsets [S + 1] - and the list of the scan that the gather behind it reads
+    std::vector<unsigned char> led_img;
+    Staging tag_stage;
+    unsigned char *d_many = nullptr; long long many_cap = 0;
+    long long *d_many_off = nullptr;
+    int many_k = 0;
     bool debug = false;
     // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
@@ -467,6 +480,17 @@ HX_LOCAL int images_reserve(hx_batch *b, long long cap, FileImages &next);
 HX_LOCAL int images_commit(hx_batch *b, const FileImages &next);
 HX_LOCAL void images_drop(hx_batch *b, FileImages &next);
 HX_LOCAL int ledger_poll(hx_batch *b, HX_LEDGER_BRIEF *out);
+// Finished files (hx_batch_slots.hip).  files_refused: what hx_batch_file_tags refuses about the files themselves (tags null:
+// what the fetch of many does) - images off, a record begun without an image, a tag of another size than the slot's head room -
+// for a list that has passed the slot operations' checks; entry: null, or the caller's number of entry e, and first: the block's
+// first stream (hx_multi, whose blocks take parts of the caller's list: the message names the caller's entry and stream).  file_tags: hx_batch_file_tags on stream q; wait: as for assign_slots.
+// The host fetch in its two halves (hx_multi: scan all blocks, decide, then bring all): files_many_scan drains, runs k_file_off
+// over the list and copies the offsets to off [n + 1]; files_many_bring gathers that list into the batch's staging and copies
+// the image's off[n] = total bytes to dst.
+HX_LOCAL int files_refused(const hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, const int *entry, int first);
+HX_LOCAL int file_tags(hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, void *stream, bool wait);
+HX_LOCAL int files_many_scan(hx_batch *b, const int *idx, int n, long long *off);
+HX_LOCAL int files_many_bring(hx_batch *b, int n, long long total, unsigned char *dst);
 // The one create path (hx_batch.hip).  ec[nmenu] (and src[nmenu]: a converting batch) is the menu, cfg[nstreams] or null
 // (= entry 0) the entry each slot starts with.  A refusal names the entry as "<label> <origin[j]>: " - src_label for what
 // the converter rejects, cls_label for what the encoder's init or the batch's kind rejects; a null label: no prefix; a null

@@ -212,6 +212,9 @@ struct alignas(16) HxFrameOut {
 // File images (hx_batch_file_images): a workgroup of k_file_append (hx_fileimg.hip) moves this many bytes of one image, the
 // same way; the host sizes the grid with it from the worst-case row plus the 15 bytes a piece may start off a vector.
 #define HX_FILE_CHUNK 16384
+// The fetch of many files (hx_batch_file_fetch_many): a workgroup of k_file_gather (hx_fileimg.hip) moves this many bytes of
+// one listed image, the same way; the host sizes the grid with it from the images' pitch.
+#define HX_FILE_GATHER_CHUNK 16384
 
 // Slots of a batch's counter block (AllocArgs::done_counter; the host runtime reads some of them and hands two to k_gate and k_pack).
 enum HxCounter {
@@ -382,7 +385,13 @@ static_assert(HX_STATE_OFF_STREAM % 8 == 0 && HX_STATE_OFF_CARRY % 8 == 0 && HX_
 // fpc: the frames per call (1152-sample block) of the entry the slot runs when the record begins: 1, or 2 at the MPEG-2 rates.
 struct HxLedgerEntry { int slot, ncalls, head_bytes, flags, fpc; };
 static_assert(sizeof(HxLedgerEntry) <= sizeof(HxSlotEntry), "a ledger list fits the slot operations' staging");
-#define HX_LEDGER_KEPT 512                          // seek points before a decimation halves them (hx_xing_toc)
+// One listed slot of hx_batch_file_tags: the slot and its tag's description (HX_FILE_TAG, include/hmp3_amd.h, as six 8-byte
+// words: this header stays free of the public one).  The list travels through a staging of its own, [S] entries per copy, in
+// the slot operations' rotation.
+struct HxFileTagEntry { int slot, pad[3]; unsigned long long tag[6]; };
+static_assert(sizeof(HxFileTagEntry) == 64, "a tag entry is four 16-byte vectors");
+#define HX_FILE_TAG_MAX 1440                        // the largest tag frame: 320 kbit/s at 32 kHz
+#define HX_LEDGER_KEPT 512                         // seek points before a decimation halves them (hx_xing_toc)
 #define HX_LEDGER_HDR_WORDS 16                      // 4-byte words in front of the points
 
 #define HX_SLOT_VEC 4                               // words per lane

@@ -306,3 +306,32 @@ extern "C" int hx_xing_update_info(hx_xing *x, unsigned frames, int bs_bytes, in
     }
     return 1;
 }
+
+// ---- a finished file's tag frame from its record (include/hmp3_amd.h, "finished files"; the kernel: k_file_tag, hx_fileimg.hip) ----
+static_assert(sizeof(HX_FILE_TAG) == 48 && offsetof(HX_FILE_TAG, lowpass) == 28 && offsetof(HX_FILE_TAG, samples_audio) == 40, "HX_FILE_TAG's layout is public");
+enum { kMaxTagFrame = 1440 };       // the largest frame a tag can take: 320 kbit/s at 32 kHz
+
+extern "C" int hx_file_tag_bytes(const HX_FILE_TAG *t)
+{
+    if (!t) return 0;
+    hx_xing x;
+    unsigned char frame[kMaxTagFrame];
+    return hx_xing_header(&x, t->samprate, t->h_mode, t->cr_bit, t->original_bit, t->flags, 0, 0, t->vbr_scale, nullptr, frame, nullptr, nullptr, t->kbps);
+}
+
+// the three calls of the command-line tool's Tagger on a seek table of its own: the record's points are copied, so build_toc's
+// end point and scaling never reach *r
+extern "C" int hx_file_tag_build(const HX_LEDGER *r, const HX_FILE_TAG *t, unsigned char *buf, int cap)
+{
+    if (!r || !t || !buf) return 0;
+    hx_xing x;
+    unsigned char frame[kMaxTagFrame];
+    const int size = hx_xing_header(&x, t->samprate, t->h_mode, t->cr_bit, t->original_bit, t->flags, 0, 0, t->vbr_scale, nullptr, frame, nullptr, nullptr, t->kbps);
+    if (size <= 0 || size != r->head_bytes || size > cap) return 0;
+    if (!hx_xing_load_points(&x, r)) return 0;
+    const unsigned n = (unsigned) r->head_bytes + r->bytes;
+    if (!hx_xing_update_info(&x, r->frames, (int) n, t->vbr_scale, nullptr, frame, nullptr, nullptr, t->samples_audio, n, t->lowpass, t->in_samplerate,
+                             (unsigned) t->samprate, (unsigned short) r->crc)) return 0;
+    memcpy(buf, frame, (size_t) size);
+    return size;
+}

@@ -484,7 +484,7 @@ int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_MPEG_HEAD *
 /* status bits accumulated by the kernels: 2 = main data overflow (the reference would assert
    there), 4 = the Huffman bits packed for a channel differ from the bits counted for it (an internal
    consistency check of the two-wave packer), 8 = a converter window out of bounds (converting batches), 16 = a dense image
-   did not fit its dense_cap (hx_batch_dense_buffers), 32 = hx_batch_set_stream_states_device was handed a blob its slot does
+   did not fit its dense_cap (hx_batch_dense_buffers; also the image of hx_batch_file_gather_device and its dst_cap), 32 = hx_batch_set_stream_states_device was handed a blob its slot does
    not take (that slot was left as it was), 64 = a file did not fit its image (hx_batch_file_images; the bytes that fit
    were written).  0 = healthy; -1 = no answer (the batch became unusable after a
    failed device call, or the status could not be read).  Synchronises - and, like hx_batch_wait, first enqueues the
@@ -656,7 +656,8 @@ int hx_batch_ledger_read_device(hx_batch *b, const int *idx, int n, HX_LEDGER *d
    The ledger decides on the device which bytes of a call belong to a file (call_bytes).  With file images on, a kernel
    right behind the ledger's update also puts those bytes where the file is: every slot owns an image of `cap` bytes of
    device memory (16-byte aligned start), of which
-     bytes [0, head_bytes) are reserved for the tag frame - no kernel ever writes them;
+     bytes [0, head_bytes) are reserved for the tag frame - only k_file_tag writes them, when asked (hx_batch_file_tags,
+     "finished files" below);
      the file's audio bytes follow from head_bytes, contiguous, in call order.
    Per slot the batch keeps one length word beside the ledger, image_bytes: the audio bytes present in the image.  It equals
    the record's `bytes`, or less after an overflow.  HX_LEDGER and the checkpoint blob are as before.
@@ -704,9 +705,61 @@ typedef struct { int open, ended, fed; unsigned frames, bytes, crc; int call_byt
    all blocks or (-1) none, refusals made for all blocks before one starts, the caller's stream numbers in messages; the
    encode calls return the blocks' status bits or'ed.  (hx_multi_file_images: a block whose allocation fails after another's
    succeeded has that one's images released again.)
-   Not covered: images in the checkpoint blob - a stream moved between batches leaves its image behind; building the tag
-   frame on the GPU; pipelined host submits in a _files form; the hx_enc_* encoder; bench.py, which measures calls that
-   return rows. */
+   Not covered: images in the checkpoint blob - a stream moved between batches leaves its image behind; pipelined host
+   submits in a _files form; the hx_enc_* encoder; bench.py, which measures calls that return rows.
+
+   ---- finished files: the tag frame built on the GPU, many files fetched at once ----
+   The tag's description: what the command-line tool's Tagger passes to hx_xing_header and hx_xing_update_info that the
+   record does not hold (fixed layout, 48 bytes, reserved: 0). */
+typedef struct { int samprate, h_mode, cr_bit, original_bit, flags, kbps, vbr_scale;   /* hx_xing_header's arguments; vbr_scale -1 = CBR */
+                 unsigned lowpass, in_samplerate, reserved;                             /* hx_xing_update_info's; out_samplerate = samprate */
+                 unsigned long long samples_audio; } HX_FILE_TAG;
+/* hx_file_tag_bytes: host only; the tag frame's size, what hx_xing_header returns for these arguments (0 = no tag, or it
+   does not fit the frame) - the head_bytes to give hx_batch_ledger_begin.
+   hx_file_tag_build: host only, pure, the reference for the kernel.  Writes into buf [cap] exactly the bytes that
+     hx_xing_header(x, samprate .. flags, frames 0, bytes 0, vbr_scale, toc NULL, buf, NULL, NULL, kbps);
+     hx_xing_load_points(x, r);
+     hx_xing_update_info(x, r->frames, n, vbr_scale, NULL, buf, NULL, NULL, samples_audio, n, lowpass, in_samplerate, samprate, r->crc)
+   leave in the first head_bytes bytes, with n = r->head_bytes + r->bytes, on a seek table of its own: *r is not changed
+   (the TOC's end point and scaling go into a copy).  Returns the size, or 0 - nothing written - when
+   hx_file_tag_bytes(t) != r->head_bytes, when that is 0 or exceeds cap, or when the record's point state is out of range.
+   hx_batch_file_tags: after it, bytes [0, head_bytes) of slot idx[e]'s image equal hx_file_tag_build(record, &tags[e]) byte
+   for byte - of a live record the tag of the state so far, of an ended one the file's.  A slot operation with
+   hx_batch_ledger_begin's contract word for word: a HOST list of distinct slots, one launch whatever n is (k_file_tag, one
+   workgroup per listed slot), ordered behind everything the batch has in flight (the deferred packing first), the entries
+   through the slot operations' staging rotation, not under stream capture, n = 0 returns 0 and launches nothing.  Refused
+   before anything is uploaded or launched, with the entry named: images off; a slot whose record was not begun with an
+   image; a null `tags` with n > 0; hx_file_tag_bytes(&tags[e]) differing from the head_bytes of the slot's latest begin.
+   A slot with head_bytes 0 is accepted and nothing is written for it.  Idempotent: a second call with other parameters
+   rebuilds the whole head.  It writes nothing at or beyond head_bytes and leaves the record, the length word and every other
+   slot's image bit-identical.  (A record whose point state is out of range, or whose head_bytes on the device is not the
+   tag's size or exceeds cap, gets nothing written - where the host function returns 0.)
+   The fetch of many files: the layout is the dense image's.  Segment e is slot idx[e]'s head_bytes + image_bytes bytes from
+   the start of its image - head room included, so behind hx_batch_file_tags a complete file - at
+     off[e] = sum over j < e of round_up(len_j, 16), e = 0 .. n; off[n] is the total;
+   the bytes from the segment's end to off[e + 1] are zero.  Segments come in list order; any order and any subset of
+   distinct slots.  The lengths are the device's own words (the record's head_bytes, the slot's image_bytes; never more than
+   cap), so a live record's segment is what the device holds at that point of the stream order.
+   hx_batch_file_gather_device: in stream order like hx_batch_ledger_poll_device, behind everything in flight: k_file_off
+   (the scan, into d_off [n + 1]) and k_file_gather (into d_dst), the list through the slot operations' staging; d_dst 16-byte
+   and d_off 8-byte aligned, else -1; not under stream capture.  The offsets are always complete; a segment that does not
+   fit dst_cap in whole (off[e + 1] > dst_cap) is not written, nothing at or beyond d_dst + dst_cap is, and status bit 16 is set.
+   hx_batch_file_fetch_many: synchronous, behind a drain: the scan, a copy of the offsets into off [n + 1], refusal (-1, dst
+   untouched, off filled) when off[n] > dst_cap, the gather into device staging that the batch owns (grown to the largest
+   total so far, released with the images), one copy of off[n] bytes: two launches and two copies whatever n is.  Returns
+   off[n].  Sets no status bit.
+   Both refuse (-1) images off, a null idx / off / dst with n > 0 and the slot operations' list errors; n = 0 returns 0,
+   launches nothing and writes off[0] = 0 where off is given (the device form: nothing).
+   hx_multi_file_tags / hx_multi_file_fetch_many: the same over all blocks (idx counts streams over all blocks); synchronous;
+   refusals made for all blocks before one starts; the result is what the one-batch call would give for the list: segments
+   in the caller's order, one off array.
+   Not covered: a _files form of the pipelined host submits; images in the checkpoint blob; the hx_enc_* encoder; a gather
+   straight into the caller's page-locked memory (the host form goes through device staging and one copy). */
+int hx_file_tag_bytes(const HX_FILE_TAG *t);
+int hx_file_tag_build(const HX_LEDGER *r, const HX_FILE_TAG *t, unsigned char *buf, int cap);
+int hx_batch_file_tags(hx_batch *b, const int *idx, const HX_FILE_TAG *tags, int n, void *stream);
+long long hx_batch_file_fetch_many(hx_batch *b, const int *idx, int n, unsigned char *dst, long long dst_cap, long long *off);
+int hx_batch_file_gather_device(hx_batch *b, const int *idx, int n, unsigned char *d_dst, long long dst_cap, long long *d_off, void *stream);
 void hx_ledger_brief(const HX_LEDGER *r, unsigned image_bytes, HX_LEDGER_BRIEF *out);
 int hx_batch_file_images(hx_batch *b, long long cap);
 long long hx_batch_file_image_cap(const hx_batch *b);
@@ -784,6 +837,9 @@ int hx_multi_ledger_read(hx_multi *m, const int *idx, int n, HX_LEDGER *out);
 int hx_multi_file_images(hx_multi *m, long long cap);
 int hx_multi_ledger_poll(hx_multi *m, HX_LEDGER_BRIEF *out);
 long long hx_multi_file_fetch(hx_multi *m, int i, unsigned char *dst, long long dst_cap);
+/* hx_batch_file_tags / hx_batch_file_fetch_many over all blocks ("finished files" above) */
+int hx_multi_file_tags(hx_multi *m, const int *idx, const HX_FILE_TAG *tags, int n);
+long long hx_multi_file_fetch_many(hx_multi *m, const int *idx, int n, unsigned char *dst, long long dst_cap, long long *off);
 int hx_multi_encode_s16_host_files(hx_multi *m, const int16_t *pcm, int nframes);
 int hx_multi_encode_f32_host_files(hx_multi *m, const float *pcm, int nframes);
 int hx_multi_encode_src_files_host(hx_multi *m, const unsigned char *in, long long in_stride, const long long *frame_off, int nframes,
