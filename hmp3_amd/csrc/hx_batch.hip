@@ -486,6 +486,17 @@ int check_call(const hx_batch *b, const void *pcm, int nframes, const void *out,
     return check_args(b, pcm, nframes, out, out_stride, out_bytes, outputs);
 }
 
+// k_pack over every frame position of a call on stream qp (solo 0: the packing alone): the grid fills the chip once, a
+// workgroup takes every gridDim.x-th position (hx_pack.hip).  The one launch expression: a batch's call and hx_debug_pack.
+static int launch_pack(hipStream_t qp, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const short *ixq, const unsigned *sgn,
+                       const HxSegOut *seg, const HxFrameOut *frm, const HxSlot *slots, unsigned char *out, long long out_stride,
+                       unsigned char *packet, int *status, int fps, int NG, long long total, const int *nfr)
+{
+    LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, st, prm, gt, ixq, sgn, seg, frm, slots,
+           out, out_stride, packet, status, fps, NG, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr, nfr);
+    return 0;
+}
+
 // the packing kernels of one call on stream qp (see place_pack)
 static int enqueue_pack(hx_batch *b, const Call &c, int nframes, int set, int sset, hipStream_t qp)
 {
@@ -503,8 +514,7 @@ static int enqueue_pack(hx_batch *b, const Call &c, int nframes, int set, int ss
         return 0;
     }
     LAUNCH(k_pack_pre, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, w.pre_len);
-    LAUNCH(k_pack, dim3((unsigned) (total < 8LL * 256 * 8 ? total : 8LL * 256 * 8)), dim3(256), qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots,
-           c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, total, 0, (HxStream *) nullptr, (const int *) nullptr, (const int *) nullptr, (const int *) nullptr, (unsigned *) nullptr, (unsigned char *) nullptr, (const int *) nullptr, c.nfr);
+    if (launch_pack(qp, b->d_st, b->d_prm, b->d_gt, w.ixq, sgn, w.seg, w.frm, w.slots, c.out, c.out_stride, c.opt.packet, b->d_status, fps, NG, total, c.nfr) != 0) return -1;
     LAUNCH(k_pack_carry, dim3(S), dim3(64), qp, b->d_st, c.out, c.out_stride, c.out_bytes, w.carry_len, c.rec_frames);
     return 0;
 }
@@ -1275,3 +1285,168 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     return n;
 }
 
+
+// ---- hx_debug_pack: k_pack on records of the caller's (tests only; include/hmp3_amd.h) ----
+// What the packer reads of a call - segment records, lines, signs, frame records, slot lists - comes from the caller instead
+// of the stream walk; the kernel and its launch are the batch's (launch_pack).  Every record is checked on the host first:
+// one the stream walk cannot emit is refused with a message before anything is launched, so nothing the kernel indexes with
+// a record's value - a code table, the 640-word bit buffer, the slot list, a row, the packet buffer - can leave its bounds.
+
+// HxFrameOut::near: copies of the frame's first four slots, as the stream walk's helper wave gathers them from its ring
+// (hx_alloc3.inc, outbox_gather); entries past the list are never used by the packer and stay zero here
+static void frame_near(HxFrameOut &fo, const HxSlot *sl, int nslots)
+{
+    for (int k = 0; k < 4; k++) {
+        const int j = fo.first_slot + k;
+        fo.near[k] = (j >= 0 && j < nslots) ? sl[j] : HxSlot{0, 0};
+    }
+}
+
+static int pack_refuse(long long s, long long f, int w, const char *what)
+{
+    char msg[256];
+    if (w >= 0) snprintf(msg, sizeof msg, "stream %lld frame position %lld segment %d: %s", s, f, w, what);
+    else snprintf(msg, sizeof msg, "stream %lld frame position %lld: %s", s, f, what);
+    set_err("%s", msg);
+    return -1;
+}
+
+static int check_pack_records(const std::vector<HxParams> &prm, const HxGlobalTabs &gt, const int *cls, int S, int NG, int fps, const int *nfr,
+                              const HxSegOut *seg, const short *ixq, const HxFrameOut *frm, const HxSlot *slots, long long out_stride,
+                              const unsigned char *packet, long long packet_bytes)
+{
+    const int nslots = fps + HX_SLOTS_EXTRA;
+    for (long long s = 0; s < S; s++) {
+        const HxParams &p = prm[cls[s]];
+        const int lsf = !p.h_id, nchan = p.nchan, hdr = 4 + p.side_bytes;
+        const int nf = (lsf ? 2 : 1) * (nfr ? nfr[s] : NG / 2);
+        const HxSlot *sl = slots + s * nslots;
+        for (int f = 0; f < nf; f++) {
+            const HxFrameOut &fo = frm[s * fps + f];
+            int pos = 0;
+            for (int w = 0; w < (lsf ? 2 : 4); w++) {
+                const int g = lsf ? f : 2 * f + (w >> 1), ch = w & 1;
+                if (ch >= nchan) continue;
+                const long long unit = (s * NG + g) * 2 + ch;
+                const HxSegOut &so = seg[unit];
+                const short *ix = ixq + unit * 576;
+                if (so.start_bit != pos) return pack_refuse(s, f, w, "start_bit is not the end of the segment before it");
+                int bits = 0;
+                for (int j = 0; j < 40; j++) {
+                    const int fld = so.sf[j], len = (fld >> 8) & 15, v = fld & 255;
+                    if (!fld) continue;
+                    if (fld & 0x7000) return pack_refuse(s, f, w, "a scalefactor field has bits 12 .. 14 set");
+                    if (len > 5) return pack_refuse(s, f, w, "a scalefactor field is longer than 5 bits");
+                    if ((fld & 0x8000) ? v < 128 : (v >> len) != 0) return pack_refuse(s, f, w, "a scalefactor field's value does not fit its length or its sign flag");
+                    bits += len;
+                }
+                if (so.not_null != 0 && so.not_null != 1) return pack_refuse(s, f, w, "not_null is neither 0 nor 1");
+                if (so.not_null) {
+                    const int n0 = so.nreg01 & 0xFFFF, n1 = so.nreg01 >> 16, n2 = so.nreg2_quads & 0xFFFF, nq = so.nreg2_quads >> 16, npairs = n0 + n1 + n2;
+                    const int t3[3] = {(int) (so.tabs & 255), (int) ((so.tabs >> 8) & 255), (int) ((so.tabs >> 16) & 255)}, c1 = (int) (so.tabs >> 24);
+                    if (npairs > 288 || nq > 144 || 2 * npairs + 4 * nq > 576) return pack_refuse(s, f, w, "more than 576 lines in pairs and quads");
+                    if (c1 > 1) return pack_refuse(s, f, w, "count1 table above 1");
+                    for (int r = 0; r < 3; r++)
+                        if (t3[r] > 31 || t3[r] == 4 || t3[r] == 14) return pack_refuse(s, f, w, "a Huffman table the format does not have");
+                    for (int pi = 0; pi < npairs; pi++) {
+                        const int t = t3[pi < n0 ? 0 : (pi < n0 + n1 ? 1 : 2)], x = ix[2 * pi], y = ix[2 * pi + 1];
+                        const int dim = t >= 16 ? 16 : gt.huff_dim[t], lin = t >= 16 ? gt.huff_lin[t] : 0, top = t >= 16 ? 15 + (1 << lin) - 1 : dim - 1;
+                        if (x < 0 || y < 0 || x > std::max(top, 0) || y > std::max(top, 0)) return pack_refuse(s, f, w, "a value above its table's range");
+                        if (!t) continue;
+                        bits += gt.huff_len[gt.huff_off[t] + std::min(x, 15) * dim + std::min(y, 15)] + (x >= 15 ? lin : 0) + (y >= 15 ? lin : 0) + (x != 0) + (y != 0);
+                    }
+                    for (int q = 0; q < nq; q++) {
+                        const short *v = ix + 2 * npairs + 4 * q;
+                        for (int k = 0; k < 4; k++) if (v[k] != 0 && v[k] != 1) return pack_refuse(s, f, w, "a count1 value that is neither 0 nor 1");
+                        bits += (c1 ? 4 : gt.quada_len[(v[0] << 3) + (v[1] << 2) + (v[2] << 1) + v[3]]) + v[0] + v[1] + v[2] + v[3];
+                    }
+                }
+                if (bits > 4095) return pack_refuse(s, f, w, "longer than 4095 bits");
+                pos += bits;
+            }
+            if (pos > 640 * 32) return pack_refuse(s, f, -1, "main data beyond the packer's bit buffer");
+            if (fo.raw_bytes != (pos + 7) >> 3) return pack_refuse(s, f, -1, "raw_bytes is not the segments' bits rounded up to bytes");
+            if (fo.bytes < fo.raw_bytes) return pack_refuse(s, f, -1, "bytes below raw_bytes");
+            if (fo.first_slot < 0 || fo.first_slot >= nslots || fo.main_bytes < 0) return pack_refuse(s, f, -1, "first_slot or main_bytes out of range");
+            long long q = fo.main_bytes;
+            int left = fo.bytes, k = fo.first_slot;
+            while (left > 0) {
+                if (k >= nslots) return pack_refuse(s, f, -1, "the slots from first_slot on hold less than the frame's bytes");
+                if (sl[k].mf < 0) return pack_refuse(s, f, -1, "a slot of negative capacity");
+                if (q >= sl[k].mf) { q -= sl[k].mf; k++; continue; }
+                if (sl[k].off < 0 || (long long) sl[k].off + hdr + sl[k].mf > out_stride) return pack_refuse(s, f, -1, "a slot outside the row");
+                const int take = (int) std::min<long long>(left, sl[k].mf - q);
+                left -= take; q += take;
+            }
+            if (fo.packet_off >= 0 && (!packet || fo.packet_off + fo.raw_bytes > packet_bytes)) return pack_refuse(s, f, -1, "packet_off outside the packet buffer");
+        }
+    }
+    return 0;
+}
+
+extern "C" int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, int fps, const int *nfr,
+                             const void *seg, const short *ixq, const unsigned *sgn, const void *frm, const void *slots,
+                             unsigned char *rows, long long out_stride, unsigned char *packet, long long packet_bytes, int *status)
+{
+    if (!ec || !cls || !seg || !ixq || !sgn || !frm || !slots || !rows || !status) { set_err("null buffer"); return -1; }
+    if (ncls <= 0 || S <= 0 || NG <= 0 || (NG & 1) || (long long) S * NG > (1LL << 20) || out_stride <= 0 || packet_bytes < 0) { set_err("bad arguments"); return -1; }
+    // the classes, resolved the way batch_create resolves a menu's entries
+    std::vector<HxParams> prm(ncls);
+    bool any_lsf = false;
+    for (int k = 0; k < ncls; k++) {
+        if (!hx_resolve((const HxControl *) (ec + k), &prm[k])) { set_err("configuration rejected"); return -1; }
+        any_lsf = any_lsf || !prm[k].h_id;
+    }
+    for (int s = 0; s < S; s++) if (cls[s] < 0 || cls[s] >= ncls) { set_err("a stream's class is out of range"); return -1; }
+    // frame positions per stream (AllocArgs::fpc)
+    if (fps != (any_lsf ? NG : NG / 2)) { set_err("the frame stride is NG with an MPEG-2 class in play, else NG / 2"); return -1; }
+    if (check_counts_arg(nfr, S, NG / 2, 0) != 0) return -1;
+    std::vector<HxGlobalTabs> gt_host(1);
+    hx_global_tabs(&gt_host[0]);
+    const int nslots = fps + HX_SLOTS_EXTRA;
+    if (check_pack_records(prm, gt_host[0], cls, S, NG, fps, nfr, (const HxSegOut *) seg, ixq, (const HxFrameOut *) frm, (const HxSlot *) slots,
+                           out_stride, packet, packet_bytes) != 0) return -1;
+    std::vector<HxFrameOut> fo((const HxFrameOut *) frm, (const HxFrameOut *) frm + (size_t) S * fps);
+    for (long long i = 0; i < (long long) S * fps; i++) frame_near(fo[i], (const HxSlot *) slots + (i / fps) * nslots, nslots);
+    std::vector<HxStream> st(S);
+    for (int s = 0; s < S; s++) hx_stream_reset(&prm[cls[s]], cls[s], &st[s]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return -1; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return -1; }
+    HIPCHK(hipSetDevice(device));
+    // device copies: everything is released on every way out
+    struct Dev {
+        std::vector<void *> mem;
+        ~Dev() { for (void *p : mem) (void) hipFree(p); }
+        void *up(const void *src, size_t bytes)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+            mem.push_back(q);
+            if (src && bytes && hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return q;
+        }
+    } dev;
+    const size_t units = (size_t) S * NG * 2;
+    const int zero = 0;
+    void *d_st = dev.up(st.data(), sizeof(HxStream) * S), *d_prm = dev.up(prm.data(), sizeof(HxParams) * ncls), *d_gt = dev.up(&gt_host[0], sizeof(HxGlobalTabs));
+    void *d_ixq = dev.up(ixq, sizeof(short) * 576 * units), *d_sgn = dev.up(sgn, sizeof(unsigned) * HX_SGN_WORDS * units), *d_seg = dev.up(seg, sizeof(HxSegOut) * units);
+    void *d_frm = dev.up(fo.data(), sizeof(HxFrameOut) * fo.size()), *d_slots = dev.up(slots, sizeof(HxSlot) * (size_t) S * nslots);
+    void *d_rows = dev.up(rows, (size_t) S * out_stride), *d_packet = packet ? dev.up(packet, (size_t) packet_bytes) : nullptr;
+    void *d_status = dev.up(&zero, sizeof(int)), *d_nfr = nfr ? dev.up(nfr, sizeof(int) * S) : nullptr;
+    if (!d_st || !d_prm || !d_gt || !d_ixq || !d_sgn || !d_seg || !d_frm || !d_slots || !d_rows || (packet && !d_packet) || !d_status || (nfr && !d_nfr)) {
+        set_err("hipMalloc or upload failed");
+        return -1;
+    }
+    if (launch_pack(nullptr, (const HxStream *) d_st, (const HxParams *) d_prm, (const HxGlobalTabs *) d_gt, (const short *) d_ixq, (const unsigned *) d_sgn,
+                    (const HxSegOut *) d_seg, (const HxFrameOut *) d_frm, (const HxSlot *) d_slots, (unsigned char *) d_rows, out_stride,
+                    (unsigned char *) d_packet, (int *) d_status, fps, NG, (long long) S * fps, (const int *) d_nfr) != 0) return -1;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(rows, d_rows, (size_t) S * out_stride, hipMemcpyDeviceToHost));
+    if (packet && packet_bytes) HIPCHK(hipMemcpy(packet, d_packet, (size_t) packet_bytes, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}

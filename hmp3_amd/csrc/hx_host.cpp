@@ -768,13 +768,19 @@ extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *nam
     TAB("nsf", p.nsf) TAB("taperNT", p.taperNT) TAB("head", p.head) TAB("ec", p.ec)
     TAB("anwin", g.anwin) TAB("mblog", g.mblog) TAB("mbexp_lo", g.mbexp_lo) TAB("mbexp_hi", g.mbexp_hi)
     TAB("pow34_exp", g.pow34_exp) TAB("quant_off", g.quant_off) TAB("logsub", g.logsub)
-    TAB("huff_code", g.huff_code) TAB("huff_len", g.huff_len)
+    TAB("huff_code", g.huff_code) TAB("huff_len", g.huff_len) TAB("huff_off", g.huff_off) TAB("huff_dim", g.huff_dim) TAB("huff_lin", g.huff_lin)
+    TAB("quada_code", g.quada_code) TAB("quada_len", g.quada_len)
     TAB("lane_run", p.lane_run) TAB("band_last_lane", p.band_last_lane)
-    TAB("nchan", p.nchan)
+    TAB("nchan", p.nchan) TAB("side_bytes", p.side_bytes) TAB("h_id", p.h_id)
     TAB("nsf2", p.nsf2) TAB("nsf3", p.nsf3) TAB("nbmax", p.nbmax) TAB("nbmax2", p.nbmax2) TAB("nbmax3", p.nbmax3)
     TAB("psy_short_npart", p.psyS.npart) TAB("alloc1", p.alloc1)
 #undef TAB
     if (k == "sizeof_band_prep") { static int v[1]; v[0] = (int) sizeof(HxBandPrep); src = v; n = sizeof(v); }     // for the tests' mirror of the "band" tap
+    if (k == "sizeof_pack_records") {       // for the tests' mirrors of what hx_debug_pack takes; [3]: slots pending from earlier calls
+        static int v[5];
+        v[0] = (int) sizeof(HxSegOut); v[1] = (int) sizeof(HxFrameOut); v[2] = (int) sizeof(HxSlot); v[3] = HX_SLOTS_EXTRA; v[4] = HX_SGN_WORDS;
+        src = v; n = sizeof(v);
+    }
     if (k == "run_w") { static int v[1]; v[0] = p.run_w; src = v; n = sizeof(v); }
     if (k == "scalars") {
         static int v[16];

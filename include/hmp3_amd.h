@@ -876,6 +876,20 @@ int hx_libm_spot_check(int n);
 int hx_debug_slim_tables_ok(const HX_E_CONTROL *ec);
 /* host-side table generation for the CPU tests (no GPU): see hx_host.cpp */
 long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *name, void *dst, long long cap);
+/* For tests: the packing kernel on records of the caller's instead of the stream walk's, launched the way a batch's call
+   launches it.  All pointers are host memory.  ec [ncls]: the controls of the classes in play; cls [S]: each stream's class;
+   NG: granule positions per stream (even), fps: frame records per stream = NG with an MPEG-2 class among ec, else NG / 2;
+   nfr [S] or null: per-stream frame counts (0 .. NG / 2).  seg [S][NG][2], ixq [S][NG][2][576], sgn [S][NG][2][20],
+   frm [S][fps] and slots [S][fps + 40] in the layouts of hmp3_amd/csrc/hx_types.h (HxSegOut, quantised magnitudes, one sign
+   bit per line, HxFrameOut - whose copies of the first four slots the call fills in itself - and HxSlot; the record sizes:
+   hx_debug_host_table "sizeof_pack_records").  rows [S][out_stride] and packet [packet_bytes] (null: none) go to the device
+   as the caller filled them and come back as the kernel left them; *status gets the kernel's status word.
+   Every record is checked on the host first: one the stream walk cannot emit - a value above its table's range, segments
+   that do not follow one another, more than 4095 bits in a segment, a slot outside its row or list ... - is refused with
+   -1 and hx_last_error before anything is launched.  Returns 0. */
+int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, int fps, const int *nfr,
+                  const void *seg, const short *ixq, const unsigned *sgn, const void *frm, const void *slots,
+                  unsigned char *rows, long long out_stride, unsigned char *packet, long long packet_bytes, int *status);
 
 /* ---- Xing / Info / LAME tag frame (first frame of a file; reference pub/xhead.h) ----
    Same arguments and return values as the reference functions; the seek-table state that the

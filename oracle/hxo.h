@@ -264,6 +264,16 @@ int  hxo_pack_huff(hxo_bitw *w, const hxo_gr *g, const int *ix, const unsigned c
 void hxo_pack_side(unsigned char out[32], int mode, const int scfsi[2], hxo_gr gr[2][2], int nchan);      /* l3pack.c:1123 */
 void hxo_pack_side_lsf(unsigned char out[32], int mode, hxo_gr gr[2], int nchan);      /* l3pack.c:1189 */
 int  hxo_pack_sf_lsf(hxo_bitw *w, const hxo_scalefact *sf, int block_type);           /* l3pack.c:561,732 */
+/* One frame's main data from a list of segments (tests/pack_cases.py; ref_pack_frame in ref_harness.cpp is the same over the
+   reference's own writer): hxo_bw_init, per segment the scalefactor fields, then hxo_pack_huff, then hxo_bw_flush.
+   hdr [nseg][HXO_PACK_HDR] = {not_null, pairs of region 0 / 1 / 2, quads, table of region 0 / 1 / 2, count1 table};
+   fld_val / fld_len [nseg][40]: the fields in transmission order, length -1 = none; the value goes to the writer as the
+   signed int it is, so a negative one is OR-ed in unmasked; ix / sign [nseg][576].  Returns the bytes written to out
+   (the caller's, at least 4 * 512 + 8 bytes) and each segment's bit length in seg_bits.  Leaves the path census alone. */
+#define HXO_PACK_HDR 9
+int  hxo_pack_frame(int nseg, const int *hdr, const int *fld_val, const int *fld_len, const int *ix, const unsigned char *sign,
+                    unsigned char *out, int *seg_bits);
+int  hxo_huff_pair_len(int t, int x, int y);    /* coded length of one pair in table t: code word, sign bits, linbits */
 
 #ifdef __cplusplus
 }

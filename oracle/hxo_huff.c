@@ -433,6 +433,37 @@ int hxo_pack_huff(hxo_bitw *w, const hxo_gr *g, const int *ix, const unsigned ch
     return bw_pos(w) - w->bit_pos_start;
 }
 
+/* a frame's main data from a list of segments (hxo.h) */
+int hxo_pack_frame(int nseg, const int *hdr, const int *fld_val, const int *fld_len, const int *ix, const unsigned char *sign,
+                   unsigned char *out, int *seg_bits)
+{
+    long long census[HXO_P_N];
+    hxo_bitw w;
+    int s, j, n;
+    memcpy(census, hxo_path_counts, sizeof(census));
+    hxo_bw_init(&w, out);
+    for (s = 0; s < nseg; s++) {
+        const int *h = hdr + HXO_PACK_HDR * s;
+        const int start = bw_pos(&w);
+        for (j = 0; j < 40; j++)
+            if (fld_len[40 * s + j] >= 0) hxo_bw_put(&w, (unsigned) fld_val[40 * s + j], fld_len[40 * s + j]);
+        if (h[0]) {
+            hxo_gr g;
+            memset(&g, 0, sizeof(g));
+            g.aux_nreg[0] = h[1]; g.aux_nreg[1] = h[2]; g.aux_nreg[2] = h[3];
+            g.big_values = h[1] + h[2] + h[3];
+            g.aux_nquads = h[4];
+            g.table_select[0] = h[5]; g.table_select[1] = h[6]; g.table_select[2] = h[7];
+            g.count1table_select = h[8];
+            hxo_pack_huff(&w, &g, ix + 576 * s, sign + 576 * s);
+        }
+        seg_bits[s] = bw_pos(&w) - start;
+    }
+    n = hxo_bw_flush(&w);
+    memcpy(hxo_path_counts, census, sizeof(census));
+    return n;
+}
+
 /* l3pack.c:1123-1187 (stereo: 32 bytes; main_data_begin left 0, patched at emit time) */
 void hxo_pack_side(unsigned char out[32], int mode, const int scfsi[2], hxo_gr gr[2][2], int nchan)
 {

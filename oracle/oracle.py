@@ -337,3 +337,93 @@ def path_counts_since(before):
     """{name: count} of the entries counted since `before` (an earlier path_counts()), zero ones left out"""
     now = path_counts()
     return {k: now[k] - before[k] for k in PATH_NAMES if now[k] != before[k]}
+
+
+# ---- the bit writer on a list of segments (hxo_pack_frame, oracle/hxo.h; ref_pack_frame, oracle/ref_harness.cpp) ----
+# A segment is a plain record (tests/pack_cases.py): "fields" 40 entries in transmission order, None or (value, length),
+# "not_null", "pairs" (n0, n1, n2), "tables" (t0, t1, t2), "c1", "quads", "ix" and "sign" of 576 lines each.
+def _pack_frame_args(segs):
+    n = len(segs)
+    hdr = np.zeros((n, 9), np.int32)
+    val = np.zeros((n, 40), np.int32)
+    ln = np.full((n, 40), -1, np.int32)
+    ix = np.zeros((n, 576), np.int32)
+    sg = np.zeros((n, 576), np.uint8)
+    for i, s in enumerate(segs):
+        hdr[i] = [s["not_null"], *s["pairs"], s["quads"], *s["tables"], s["c1"]]
+        for j, f in enumerate(s["fields"]):
+            if f is not None:
+                val[i, j], ln[i, j] = f
+        ix[i] = s["ix"]
+        sg[i] = s["sign"]
+    return n, hdr, val, ln, ix, sg
+
+
+def ref_has_pack_frame():
+    """whether the reference build at hand was made with ref_pack_frame in its harness"""
+    return ref() is not None and hasattr(ref(), "ref_pack_frame")
+
+
+def _ref_pack_frame_direct(n, hdr, val, ln, ix, sg, out, bits):
+    """ref_pack_frame's steps (oracle/ref_harness.cpp) made from here, on the writer functions every reference build
+    exports - L3_outbits_init, L3_outbits, L3_pack_huff, L3_outbits_flush: a machine that has no reference sources runs the
+    oracle/_ref it was handed, which may have been made before the harness had ref_pack_frame.  GR (pub/l3e.h:72-96) as 27
+    ints: big_values [1], table_select [7..9], count1table_select [17], aux_nquads [18], aux_nreg [21..23]."""
+    r = ref()
+    r.L3_outbits_init.argtypes = [C.c_void_p]
+    r.L3_outbits.argtypes = [C.c_uint, C.c_int]
+    r.L3_pack_huff.argtypes = [C.c_void_p] * 3
+    r.L3_pack_huff.restype = r.L3_outbits_flush.restype = C.c_int
+    none = (C.c_int * 27)()
+    pos = lambda: r.L3_pack_huff(none, ix.ctypes.data, sg.ctypes.data)      # (codes nothing: the writer's position against a file static)
+    r.L3_outbits_init(out.ctypes.data)
+    for s in range(n):
+        start = pos()
+        for j in range(40):
+            if ln[s, j] >= 0:
+                r.L3_outbits(int(val[s, j]) & 0xFFFFFFFF, int(ln[s, j]))
+        if hdr[s, 0]:
+            g = (C.c_int * 27)()
+            g[21], g[22], g[23] = (int(v) for v in hdr[s, 1:4])
+            g[1], g[18] = int(hdr[s, 1:4].sum()), int(hdr[s, 4])
+            g[7], g[8], g[9], g[17] = (int(v) for v in hdr[s, 5:9])
+            r.L3_pack_huff(g, ix[s].ctypes.data, sg[s].ctypes.data)
+        bits[s] = pos() - start
+    return r.L3_outbits_flush()
+
+
+def pack_frame(segs, use_ref=False, harness=None):
+    """(main-data bytes, [bit length of each segment]) of one frame made of `segs`, by the oracle's writer or (use_ref) the
+    reference's own: through the harness's ref_pack_frame where the reference build has it (harness: None = that rule,
+    True / False = that way)"""
+    n, hdr, val, ln, ix, sg = _pack_frame_args(segs)
+    out = np.zeros(4 * 512 + 64, np.uint8)
+    bits = np.zeros(max(n, 1), np.int32)
+    if use_ref and not (ref_has_pack_frame() if harness is None else harness):
+        nb = _ref_pack_frame_direct(n, hdr, val, ln, ix, sg, out, bits)
+    else:
+        f = ref().ref_pack_frame if use_ref else lib().hxo_pack_frame
+        f.restype = C.c_int
+        f.argtypes = [C.c_int] + [C.c_void_p] * 7
+        nb = f(n, hdr.ctypes.data, val.ctypes.data, ln.ctypes.data, ix.ctypes.data, sg.ctypes.data, out.ctypes.data, bits.ctypes.data)
+    return out[:nb].tobytes(), [int(b) for b in bits[:n]]
+
+
+def huff_pair_len(t, x, y):
+    """coded length of one pair in table t: code word, sign bits, linbits (hxo_huff_pair_len)"""
+    return int(lib().hxo_huff_pair_len(int(t), int(x), int(y)))
+
+
+def huff_tables():
+    """the oracle's code tables: {"dim": [32], "linbits": [32], "len": {(t, x, y): bits}, "code": {(t, x, y): word},
+    "quada": [(code, len)] * 16}; x, y below the table's dimension"""
+    l = lib()
+    dim = [int(l.hxo_huff_dim(t)) for t in range(32)]
+    tabs = {"dim": dim, "linbits": [int(l.hxo_huff_linbits(t)) for t in range(32)], "len": {}, "code": {},
+            "quada": [(int(l.hxo_quada_code(v)), int(l.hxo_quada_len(v))) for v in range(16)]}
+    for t in range(32):
+        for x in range(dim[t]):
+            for y in range(dim[t]):
+                tabs["len"][t, x, y] = int(l.hxo_huff_len(t, x, y))
+                tabs["code"][t, x, y] = int(l.hxo_huff_code(t, x, y))
+    return tabs

@@ -35,6 +35,37 @@ int ref_src_convert(void *h, unsigned char *xin, float *yout, int *out_bytes)
     *out_bytes = x.out_bytes;
     return x.in_bytes;
 }
+/* the reference's bit writer on a list of segments (pins hxo_pack_frame, oracle/hxo.h, which documents the arguments, and
+ * through it k_pack): L3_outbits_init, per segment the scalefactor fields through L3_outbits - the value as the signed int
+ * the reference would pass - then L3_pack_huff, then L3_outbits_flush.  L3_pack_huff reports the writer's position against
+ * a file static that only the scalefactor packers set, so a segment's length is the difference of two positions, each asked
+ * for with a granule record that codes nothing. */
+int ref_pack_frame(int nseg, const int *hdr, const int *fld_val, const int *fld_len, int *ix, unsigned char *sign,
+                   unsigned char *out, int *seg_bits)
+{
+    GR none;
+    memset(&none, 0, sizeof(none));
+    L3_outbits_init(out);
+    for (int s = 0; s < nseg; s++) {
+        const int *h = hdr + 9 * s;
+        const int start = L3_pack_huff(&none, ix, sign);
+        for (int j = 0; j < 40; j++)
+            if (fld_len[40 * s + j] >= 0) L3_outbits((unsigned int) fld_val[40 * s + j], fld_len[40 * s + j]);
+        if (h[0]) {
+            GR g;
+            memset(&g, 0, sizeof(g));
+            g.aux_nreg[0] = h[1]; g.aux_nreg[1] = h[2]; g.aux_nreg[2] = h[3];
+            g.big_values = h[1] + h[2] + h[3];
+            g.aux_nquads = h[4];
+            g.table_select[0] = h[5]; g.table_select[1] = h[6]; g.table_select[2] = h[7];
+            g.count1table_select = h[8];
+            L3_pack_huff(&g, ix + 576 * s, sign + 576 * s);
+        }
+        seg_bits[s] = L3_pack_huff(&none, ix, sign) - start;
+    }
+    return L3_outbits_flush();
+}
+
 /* CMp3Enc::MP3_audio_encode_init / MP3_audio_encode with every argument */
 struct ZeroHeap;
 int ref_init_mp3(void *h, E_CONTROL *ec, int bits, int is_float, int mpeg_select, int mono_convert)
