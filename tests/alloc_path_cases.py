@@ -21,6 +21,7 @@ import functools
 import numpy as np
 
 from oracle import oracle as O
+from stage_taps import TapBatch
 
 KINDS = ["m1_long", "m1_short", "m1_mono", "m1_hf", "m2_long", "m2_short", "a1_m1", "a1_m2"]
 FRAMES = 10             # frames per case (at most 12): the search judges a hit by the frame it first shows at
@@ -170,6 +171,25 @@ def batches():
             for i in range(0, len(names), 8):
                 out[kind + tag + ("" if i == 0 else "_" + "bcdefgh"[i // 8 - 1])] = names[i:i + 8]
     return out
+
+
+def batch_input(batch):
+    """(controls, float32 PCM [S, FRAMES * 1152, 2] or [S, FRAMES * 1152]) of a batch"""
+    names = batches()[batch]
+    return [CASES[n][2] for n in names], np.stack([case_pcm(CASES[n][1], CASES[n][3]) for n in names])
+
+
+def run_batch(api, batch, frames_per_call):
+    """the batch through the C ABI in calls of frames_per_call frames, every frame compared with the oracle (tests/stage_taps.py,
+    TapBatch) -> the TapBatch, closed"""
+    kws, pcm = batch_input(batch)
+    full = batch.startswith("m1_") and "mono" not in batch
+    tb = TapBatch(api, kws, len(kws), frames_per_call, "full" if full else "lines", alloc_state=True)
+    for f in range(0, FRAMES, frames_per_call):
+        tb.call(pcm[:, f * 1152:(f + frames_per_call) * 1152])
+    tb.close()
+    assert tb.frames == [FRAMES] * len(kws) and all(len(g) > 0 for g in tb.got)
+    return tb
 
 
 @functools.lru_cache(maxsize=None)

@@ -1,14 +1,20 @@
 """The inputs of the file-image tests (tests/test_gpu_file_images.py runs them on the GPU; tests/test_file_images_abi.py checks
 on the CPU, with the oracle alone, that they reach the edges they exist for).
 
-The small shape is the ledger test's (tests/test_gpu_ledger.py): 9 slots, files of 1 .. 20 calls in calls of 8 frames under
+The small shape is the ledger test's (tests/ledger_cases.py): 9 slots, files of 1 .. 20 calls in calls of 8 frames under
 per-stream counts - here VBR, so that the byte counts and with them the places a piece starts at take every residue mod 16.
 Slot NEVER is never begun, slot SITS_OUT sits call 1 out, slot RESTART gets a second file between calls 2 and 3, and slot
 ONE_FRAME takes a single frame of call 0: the encoder emits nothing for it, so a fed live stream has a piece of 0 bytes."""
+import os
+import re
+
 import numpy as np
 
-from test_gpu_ledger import DRAIN, NEVER, RESTART, SITS_OUT, SMALL_NCALLS, small_counts, small_pcm, small_restart_pcm
+from ledger_cases import DRAIN, NEVER, RESTART, SITS_OUT, SMALL_NCALLS, block, small_counts, small_pcm, small_restart_pcm  # noqa: F401
 
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PAT = 0xA5              # what a file image holds before anything is written
+CHUNK = int(re.search(r"#define HX_FILE_CHUNK (\d+)", open(os.path.join(ROOT, "hmp3_amd", "csrc", "hx_types.h")).read()).group(1))
 ONE_FRAME = 3
 RESTART_NCALLS, RESTART_AT = 6, 3
 # head_bytes per slot: all different, chosen (with the oracle, tests/test_file_images_abi.py) so that the shape's 17 pieces
@@ -42,11 +48,12 @@ def schedule():
         call += 1
 
 
-def block(full, given, counts, nf):
-    """the call's PCM [S, nf * 1152, ch]: stream s's next counts[s] frames of full[s], silence behind its end"""
-    blk = np.zeros((len(full), nf * 1152, full[0].shape[1]), np.float32)
+def rows_block(full, given, counts, nf, P, dtype):
+    """the call's PCM rows [S, nf * 1152 * P]: stream s's next counts[s] frames of full[s] first in its row (a mono stream of
+    a stereo-pitched batch: its samples back to back), silence behind its end"""
+    blk = np.zeros((len(full), nf * 1152 * P), dtype)
     for s, n in enumerate(counts):
-        part = full[s][given[s] * 1152:(given[s] + n) * 1152]
+        part = full[s][given[s] * 1152:(given[s] + n) * 1152].reshape(-1)
         blk[s, :len(part)] = part
     return blk
 

@@ -9,43 +9,20 @@ import os
 import subprocess
 import sys
 
-import numpy as np
 import pytest
 
 import alloc_path_cases as K
 from conftest import skip_unless_host_libm_is_the_restated_one
-from stage_taps import TapBatch
+from gpu_support import ROOT
+from hmp3_amd import api
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BATCHES = K.batches()
 
 
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def batch_input(batch):
-    """(controls, float32 PCM [S, FRAMES * 1152, 2] or [S, FRAMES * 1152]) of a batch"""
-    names = BATCHES[batch]
-    return [K.CASES[n][2] for n in names], np.stack([K.case_pcm(K.CASES[n][1], K.CASES[n][3]) for n in names])
-
-
-def run_batch(batch, frames_per_call):
-    kws, pcm = batch_input(batch)
-    full = batch.startswith("m1_") and "mono" not in batch
-    tb = TapBatch(api(), kws, len(kws), frames_per_call, "full" if full else "lines", alloc_state=True)
-    for f in range(0, K.FRAMES, frames_per_call):
-        tb.call(pcm[:, f * 1152:(f + frames_per_call) * 1152])
-    tb.close()
-    assert tb.frames == [K.FRAMES] * len(kws) and all(len(g) > 0 for g in tb.got)
-    return tb
-
-
 def check(batch):
-    one = run_batch(batch, K.FRAMES)
-    by_frame = run_batch(batch, 1)
+    one = K.run_batch(api, batch, K.FRAMES)
+    by_frame = K.run_batch(api, batch, 1)
     assert one.got == by_frame.got
 
 
@@ -73,8 +50,9 @@ def test_first_generation_paths(batch):
 CHILD = """
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
-import test_gpu_alloc_paths as T
-T.run_batch("m1_long", T.K.FRAMES)
+import alloc_path_cases as K
+from hmp3_amd import api
+K.run_batch(api, "m1_long", K.FRAMES)
 print("compared")
 """
 

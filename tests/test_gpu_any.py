@@ -5,23 +5,23 @@ A stream's kind is 2 * (first-generation allocator) + (MPEG-2 rate); every kind 
 its span of one launch order.  The slots here are assigned interleaved (kinds 0, 1, 2, 3, 0, 1, ...), so no kind is
 contiguous in stream order, the four waves of a k_detect workgroup differ in MPEG version and every span but the first
 starts at a position > 0.  Every expectation is byte identity against the oracle, one encoder per stream life fed frame by
-frame, as in test_gpu_mixed.py, whose helpers this file uses; converting streams go through this library's host converter
+frame, as in test_gpu_mixed.py (both on tests/mixed_cases.py); converting streams go through this library's host converter
 and then the oracle.  Blob comparisons across batches use device calls into zeroed rows, as explained there."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import packet_cases as PC
 from conftest import skip_unless_host_libm_is_the_restated_one
-from hmp3_amd import synth
-from test_gpu_mixed import CLI, RHOS, api, blob_diff, controls, device_call, host_converted, joined, key, rows_of, want_f32, want_s16
+from gpu_support import FILL, CallBufs, Image, controls, plain_call as device_call, run_cli, write_wav
+from hmp3_amd import api, synth
+from mixed_cases import RHOS, blob_diff, joined, key, rows_of, streams_of, want_f32
+from oracle_pool import oracle_bytes_many
+from output_checks import check_image, expected_crc
+from src_cases import Stream, host_converted
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 # kind 0: stereo 44.1 kHz CBR, mono 48 kHz VBR (test_gpu_mixed.ENTRIES); kind 1: stereo 22.05 kHz CBR-32, mono 16 kHz CBR-32
 # behind the DC blocker, 24 kHz VBR (test_gpu_slot_menu's mpeg2 menu, packet_cases.MPEG2); kind 2: dual channel at 44.1 kHz and
@@ -39,16 +39,12 @@ SWITCHING = [s for s in range(S) if KINDS[s] < 2]        # (the first-generation
 
 def any_batch(menu=ENTRIES, cfg=None, n=None, max_frames=4):
     n = len(menu) if n is None else n
-    return api().Batch.any(controls(menu), n, cfg=list(range(n)) if cfg is None else cfg, max_frames=max_frames)
+    return api.Batch.any(controls(menu), n, cfg=list(range(n)) if cfg is None else cfg, max_frames=max_frames)
 
 
 def eight(f32, seed=1700):
     """the eight streams of ENTRIES: (signals, the oracle's bytes per frame)"""
-    if f32:
-        w = [want_f32(seed + i, key(kw)) for i, kw in enumerate(ENTRIES)]
-        return [x for x, _ in w], [[fr.bs for fr in frames] for _, frames in w]
-    w = [want_s16(seed + i, key(kw)) for i, kw in enumerate(ENTRIES)]
-    return [x for x, _ in w], [list(frames) for _, frames in w]
+    return streams_of(ENTRIES, f32, seed)
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["s16", "f32"])
@@ -109,7 +105,7 @@ def test_a_menu_of_one_kind_is_the_mixed_batch(kind, k6_build):
     menu = [kw for kw, k in zip(ENTRIES, KINDS) if k == kind]
     x = [want_f32(1740 + i, key(kw))[0] for i, kw in enumerate(menu)]
     res = []
-    for make in (api().Batch.any, api().Batch.mixed):
+    for make in (api.Batch.any, api.Batch.mixed):
         b = make(controls(menu), len(menu), cfg=list(range(len(menu))), max_frames=4)
         assert [b.stream_frames_per_block(i) for i in range(b.n)] == [1 + kind] * b.n
         outs = []
@@ -167,7 +163,7 @@ def test_assign_across_kinds(mode, k6_build):
     menu = [ENTRIES[0], ENTRIES[1], ENTRIES[3], ENTRIES[2]]        # kinds 0, 1, 3, 2
     F = 2       # (slots 1 - 3 walk 20 frames of their 22-frame signals)
     lives = [[1800, 0, 0], [1801, 1, 0], [1802, 3, 0], [1803, 0, 0]]      # per slot: [seed, menu entry, frames done]
-    b = api().Batch.any(controls(menu), 4, cfg=[e for _, e, _ in lives], max_frames=F)
+    b = api.Batch.any(controls(menu), 4, cfg=[e for _, e, _ in lives], max_frames=F)
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
 
@@ -197,7 +193,7 @@ def test_assign_across_kinds(mode, k6_build):
             lives[s][2] += 2 * F
         # slot 0's blob against a new uniform batch of its control, fed the same frames
         if lives[0][2] == 2 * F:
-            one = api().Batch(api().default_control(**menu[lives[0][1]]), nstreams=1, max_frames=F)
+            one = api.Batch(api.default_control(**menu[lives[0][1]]), nstreams=1, max_frames=F)
             for c in range(2):
                 blk = np.ascontiguousarray(w[0][0][F * c * 1152:F * (c + 1) * 1152].reshape(1, -1))
                 assert device_call(one, blk, F)[0][0] == got[c][0]
@@ -221,11 +217,8 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
     derive from the oracle's frames.  Every record was opened with its slot's own frames per block; the files in slots 1
     (MPEG-2) and 4 (MPEG-1) end inside the second call."""
     import torch
-    from test_gpu_packets import FILL
-    from test_gpu_crc import expected_crc
-    from test_gpu_dense import check_image
     skip_unless_host_libm_is_the_restated_one()
-    A = api()
+    A = api
     F, NC, PK = 4, 3, 2048
     w = [want_f32(1700 + i, key(kw)) for i, kw in enumerate(ENTRIES)]
     pcm, frames = [x for x, _ in w], [list(f) for _, f in w]
@@ -238,32 +231,16 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
     recs = [A.ledger_open(n, FPB[s], 0, 0) for s, n in enumerate(ncalls)]
     LB = C.sizeof(A.Ledger)
 
-    class Set:
-        def __init__(self):
-            self.pk = torch.full((S, F, PK), FILL, dtype=torch.uint8, device=dev)
-            self.pkb = torch.full((S, F, 2), -1, dtype=torch.int32, device=dev)
-            self.stats = torch.full((S, F, 2), -1, dtype=torch.int32, device=dev)
-            self.crc = torch.full((S, F), -1, dtype=torch.int16, device=dev)
-            self.dense = torch.full((cap,), FILL, dtype=torch.uint8, device=dev)
-            self.off = torch.full((S + 1,), -1, dtype=torch.int64, device=dev)
-            self.led = torch.full((S * LB,), FILL, dtype=torch.uint8, device=dev)
-            assert self.dense.data_ptr() % 16 == 0 and self.led.data_ptr() % 16 == 0
-
-        def set_on(self):
-            b.packet_buffers(self.pk.data_ptr(), PK, self.pkb.data_ptr())
-            b.frame_stats_buffer(self.stats.data_ptr())
-            b.crc_buffer(self.crc.data_ptr())
-            b.dense_buffers(self.dense.data_ptr(), cap, self.off.data_ptr())
-
-    sets = [Set() for _ in range(NC)]
-    d_rows = [torch.zeros((S, stride), dtype=torch.uint8, device=dev) for _ in range(2)]
-    d_nb = [torch.full((S,), -1, dtype=torch.int32, device=dev) for _ in range(2)]
+    # rows and byte counts alternate between two sets, so call 2 overwrites call 0's; the optional outputs are per call
+    sets = [CallBufs(b, F, counters=True, crc=True, packets=PK, image=Image(S, cap, guard=0)) for _ in range(NC)]
+    leds = [torch.full((S * LB,), FILL, dtype=torch.uint8, device=dev) for _ in range(NC)]
+    assert all(led.data_ptr() % 16 == 0 for led in leds)
     d_pcm = [torch.from_numpy(rows_of(pcm, [F * c] * S, [F] * S, F, True)).to(dev) for c in range(NC)]
     torch.cuda.synchronize()
     for c in range(NC):
-        sets[c].set_on()
-        b.submit_device(d_pcm[c].data_ptr(), F, d_rows[c & 1].data_ptr(), stride, d_nb[c & 1].data_ptr(), st, f32=True)
-        b.ledger_read_device(list(range(S)), sets[c].led.data_ptr(), stream=st)
+        sets[c].set_on(b)
+        b.submit_device(d_pcm[c].data_ptr(), F, sets[c & 1].ptr, stride, sets[c & 1].nb.data_ptr(), st, f32=True)
+        b.ledger_read_device(list(range(S)), leds[c].data_ptr(), stream=st)
     b.wait(st)
     torch.cuda.synchronize()
     assert b.status() == 0
@@ -280,9 +257,9 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
         ended = [bool(A.ledger_update(recs[s], stats[s], crc[s], nb[s])) for s in range(S)]
         assert ended == [c == 1 and s in (1, 4) for s in range(S)], "call %d: which files the host's rule ends" % c
         o, tag = sets[c], "call %d" % c
-        dense, off = o.dense.cpu().numpy(), o.off.cpu().numpy()
+        dense, off = o.image.host()
         check_image(rows, nb, dense, off, cap, tag=tag)
-        pk, pkb, g_stats = o.pk.cpu().numpy(), o.pkb.cpu().numpy(), o.stats.cpu().numpy()
+        pk, pkb, g_stats = o.packets()
         for s in range(S):
             assert dense[off[s]:off[s] + nb[s]].tobytes() == rows[s, :nb[s]].tobytes(), "%s stream %d: bitstream" % (tag, s)
             for f in range(F):
@@ -295,10 +272,10 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
                 assert (pk[s, f, n0 + n1:] == FILL).all(), at + ": bytes written behind the packet"
                 assert tuple(g_stats[s, f]) == (fr.frames_out, fr.bytes_out), at + ": frames / bytes emitted so far"
         if c > 0:
-            g_rows, g_nb = d_rows[c & 1].cpu().numpy(), d_nb[c & 1].cpu().numpy()
+            g_rows, g_nb = sets[c & 1].rows()
             assert g_nb.tolist() == nb.tolist() and all(g_rows[s, :nb[s]].tobytes() == rows[s, :nb[s]].tobytes() for s in range(S)), tag + ": rows"
-        assert (o.crc.cpu().numpy().view(np.uint16) == crc).all(), tag + ": per-frame CRCs"
-        led = o.led.cpu().numpy()
+        assert (o.host()[3] == crc).all(), tag + ": per-frame CRCs"
+        led = leds[c].cpu().numpy()
         for s in range(S):
             assert led[s * LB:(s + 1) * LB].tobytes() == recs[s].tobytes(), "%s: the record of slot %d differs from hx_ledger_update's" % (tag, s)
     got = b.ledger_read(list(range(S)))
@@ -315,7 +292,7 @@ def test_beyond_the_resident_set(monkeypatch, k6_build):
     skip_unless_host_libm_is_the_restated_one()
     monkeypatch.setenv("HMP3AMD_K6", "slim")
     menu = [dict(), ENTRIES[1], ENTRIES[7], ENTRIES[2], ENTRIES[3]]      # VBR -V50 stereo; 22.05 and 24 kHz; dual channel 44.1 and 16 kHz
-    probe = api().Batch.any(controls(menu), 1, cfg=[0], max_frames=2)
+    probe = api.Batch.any(controls(menu), 1, cfg=[0], max_frames=2)
     resident = probe.resident_streams()
     assert probe.k6_variant() == 1
     probe.close()
@@ -329,7 +306,7 @@ def test_beyond_the_resident_set(monkeypatch, k6_build):
     base = {e: [synth.stream_pcm(7400 + 20 * e + u, F * calls, sr=menu[e].get("samprate", 44100), rho=RHOS[u % 4], bursts=True) for u in range(16 if e == 0 else 2)]
             for e in range(len(menu))}
     pcm = np.stack([np.roll(base[e][i % len(base[e])], 1152 * ((i // 16) % (F * calls)), axis=0) for i, e in enumerate(cfg)])
-    b = api().Batch.any(controls(menu), S_all, cfg=cfg, max_frames=F)
+    b = api.Batch.any(controls(menu), S_all, cfg=cfg, max_frames=F)
     assert b.k6_variant() == 1 and b.resident_streams() < n0
     got = [b"" for _ in range(S_all)]
     for c in range(calls):
@@ -338,7 +315,6 @@ def test_beyond_the_resident_set(monkeypatch, k6_build):
             got[s] += out[s]
     assert b.status() == 0
     b.close()
-    from oracle_pool import oracle_bytes_many
     want = oracle_bytes_many([menu[e] for e in cfg], pcm, F * calls)
     bad = [s for s in range(S_all) if got[s] != want[s]]
     assert not bad, "%d of %d streams differ from the oracle, first: %s (entries %s)" % (len(bad), S_all, bad[:8], [cfg[s] for s in bad[:8]])
@@ -350,7 +326,7 @@ def test_multi_over_two_blocks(k6_build):
     skip_unless_host_libm_is_the_restated_one()
     menu = [ENTRIES[0], ENTRIES[1], ENTRIES[2], ENTRIES[3], ENTRIES[4]]      # kinds 0, 1, 2, 3, 0 (mono)
     cfg = [0, 1, 2, 1, 3]
-    m = api().Multi.any(controls(menu), 5, cfg=cfg, max_frames=3, devices=[0, 0])
+    m = api.Multi.any(controls(menu), 5, cfg=cfg, max_frames=3, devices=[0, 0])
     assert m.ndevices() == 2 and [m.shard(k)[1:] for k in range(2)] == [(0, 3), (3, 2)]
     assert m.pcm_channels() == 2 and [m.stream_frames_per_block(i) for i in range(5)] == [1, 2, 1, 2, 2]
     w = [want_f32(1900 + i, key(menu[c])) for i, c in enumerate(cfg)]
@@ -374,8 +350,7 @@ def test_multi_over_two_blocks(k6_build):
 def test_converting_batch(counts, k6_build):
     """44.1 kHz s16 sources into a 44.1 kHz entry and into a 22.05 kHz entry, a 48 kHz s24 source summed to mono into a 16 kHz
     entry: the rows are the oracle's for hx_src_convert's PCM under the control src_encode_control derives"""
-    from test_gpu_src_batch import Stream
-    A = api()
+    A = api
     F = 3
     streams = [Stream(44100, 16, 0, seed=31, seconds=1.0), Stream(44100, 16, 0, mpeg_select=22050, seed=32, seconds=1.0, bitrate=32),
                Stream(48000, 24, 0, mono_convert=1, mpeg_select=16000, seed=33, seconds=1.0, bitrate=32)]
@@ -419,9 +394,6 @@ def test_cli_batch_of_files_of_every_kind(tmp_path, flags, k6_build):
     the mono MPEG-2 one."""
     if flags:
         skip_unless_host_libm_is_the_restated_one()
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    from make_golden_cli import write_wav
-    assert os.path.exists(CLI), "hmp3_amd/build.sh builds the CLI"
     files = [("a", 44100, 2, 21), ("b", 22050, 2, 9), ("c", 16000, 1, 14), ("d", 44100, 2, 6)]
     args = {"batch": [], "slots2": []}
     for k, (name, sr, ch, nframes) in enumerate(files):
@@ -430,13 +402,11 @@ def test_cli_batch_of_files_of_every_kind(tmp_path, flags, k6_build):
         wav = str(tmp_path / (name + ".wav"))
         write_wav(wav, x if ch == 2 else np.ascontiguousarray(x[:, 0]), sr, False)
         one = str(tmp_path / (name + ".one.mp3"))
-        r = subprocess.run([CLI, wav, one] + flags, capture_output=True, timeout=120)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
+        run_cli([wav, one] + flags)
         for how in args:
             args[how] += [wav, str(tmp_path / ("%s.%s.mp3" % (name, how)))]
     for how, slots in (("batch", []), ("slots2", ["-slots2"])):
-        r = subprocess.run([CLI, "-batch"] + slots + args[how] + flags, capture_output=True, timeout=120)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
+        run_cli(["-batch"] + slots + args[how] + flags)
         for name, *_ in files:
             got = open(str(tmp_path / ("%s.%s.mp3" % (name, how))), "rb").read()
             assert len(got) > 1000 and got == open(str(tmp_path / (name + ".one.mp3")), "rb").read(), "%s (%s): differs from its single-file run" % (name, how)

@@ -11,66 +11,31 @@ import os
 import struct
 import subprocess
 import sys
-import wave
 
 import numpy as np
 import pytest
 
-from hmp3_amd import synth
-from test_gpu_dense import Rows, api, cur_stream, cut, dev, mixed_controls, mixed_pcm, sync
+from dense_cases import mixed_controls, mixed_pcm
+from gpu_support import ROOT, CallBufs, batch_vs_single_vs_reference, cur_stream, cut, dev, host_crc, sync, write_wav
+import gpu_support as G
+from hmp3_amd import api, synth
+from output_checks import expected_crc
+from src_cases import Stream, make_batch
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FILL16 = 0xA5A5
 GUARD = 2048            # uint16 entries behind [S][F]
 PASS_BYTES = 64 * 256   # what one pass of k_crc's workgroup covers (HX_CRC_CHUNK * HX_CRC_LANES)
 
 
-def host_crc(data, seed=0):
-    data = bytes(data)
-    return int(api().lib().hx_xing_update_crc(seed, data, len(data)))
-
-
-class Out:
+def out_bufs(b, nf, shift=0, extra=0):
     """every output buffer of one call: rows (first row `shift` bytes past a 16-byte boundary, `extra` bytes added to the
-    stride), byte counts, frame counters and the prefilled CRC buffer with its guard region"""
-
-    def __init__(self, b, nf, shift=0, extra=0):
-        import torch
-        self.S, self.nf = b.n, nf
-        self.rows = Rows(b, nf, shift, extra)
-        self.stats = torch.full((self.S, nf, 2), -1, dtype=torch.int32, device=dev())
-        self.crc = torch.full((self.S * nf + GUARD,), FILL16 - 65536, dtype=torch.int16, device=dev())
-
-    def set_on(self, b, crc=True):
-        b.frame_stats_buffer(self.stats.data_ptr())
-        b.crc_buffer(self.crc.data_ptr() if crc else None)
-
-    def host(self):
-        """rows, nb, stats, crc [S, F] uint16, the guard region"""
-        rows, nb = self.rows.host()
-        c = self.crc.cpu().numpy().view(np.uint16)
-        return rows, nb, self.stats.cpu().numpy(), c[:self.S * self.nf].reshape(self.S, self.nf), c[self.S * self.nf:]
+    stride), byte counts, frame counters and the CRC buffer prefilled with FILL16, its guard region behind it"""
+    return CallBufs(b, nf, shift=shift, extra=extra, counters=True, crc=True, crc_fill=FILL16, crc_guard=GUARD)
 
 
-def emitted(nb, stats):
-    """e[s][f]: the call's bytes of row s after input frame f, in unsigned arithmetic"""
-    by = stats[:, :, 1].astype(np.int64)
-    return (nb.astype(np.int64)[:, None] - ((by[:, -1:] - by) & 0xFFFFFFFF)) & 0xFFFFFFFF
-
-
-def expected_crc(rows, nb, stats):
-    """the host's CRC of every prefix rows[s][:e[s][f]] (e does not decrease with f: one chained pass per row)"""
-    e = emitted(nb, stats)
-    want = np.zeros(e.shape, np.uint16)
-    for s in range(len(nb)):
-        run, at = 0, 0
-        assert (np.diff(e[s]) >= 0).all() and e[s, -1] == nb[s]
-        for f in range(e.shape[1]):
-            run = host_crc(rows[s, at:e[s, f]], run)
-            at = int(e[s, f])
-            want[s, f] = run
-    return want, e
+def device_call(b, blk, nf, crc=True, shift=0, extra=0, submit=False):
+    return G.device_call(b, blk, nf, out_bufs(b, nf, shift, extra).set_on(b, crc=crc), submit=submit)
 
 
 def check(out, tag):
@@ -86,14 +51,6 @@ def check(out, tag):
     return rows, nb, stats, crc, e
 
 
-def device_call(b, blk, nf, crc=True, shift=0, extra=0, submit=False):
-    import torch
-    o = Out(b, nf, shift, extra)
-    d_pcm = torch.from_numpy(np.ascontiguousarray(blk)).to(dev())
-    sync()
-    o.set_on(b, crc)
-    (b.submit_device if submit else b.encode_device)(d_pcm.data_ptr(), nf, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=True)
-    return o, d_pcm
 
 
 def run_twins(make, pcm, calls, shift=0, extra=0, tag=""):
@@ -102,8 +59,8 @@ def run_twins(make, pcm, calls, shift=0, extra=0, tag=""):
     bc, bt = make(), make()
     res, f0 = [], 0
     for c, nf in enumerate(calls):
-        oc, _ = device_call(bc, cut(pcm, f0, nf), nf, True, shift, extra)
-        ot, _ = device_call(bt, cut(pcm, f0, nf), nf, False, shift, extra)
+        oc = device_call(bc, cut(pcm, f0, nf), nf, True, shift, extra)
+        ot = device_call(bt, cut(pcm, f0, nf), nf, False, shift, extra)
         sync()
         r = check(oc, "%s call %d" % (tag, c))
         trows, tnb, tstats, tcrc, tguard = ot.host()
@@ -118,7 +75,7 @@ def run_twins(make, pcm, calls, shift=0, extra=0, tag=""):
 
 
 def batch_of(controls, maxF, **kw):
-    return lambda: api().Batch(controls, max_frames=maxF, **kw)
+    return lambda: api.Batch(controls, max_frames=maxF, **kw)
 
 
 def test_mixed_rates_three_calls_and_their_fold():
@@ -130,7 +87,7 @@ def test_mixed_rates_three_calls_and_their_fold():
     for s in range(S):
         run, whole = 0, b""
         for rows, nb, stats, crc, e in res:
-            run = api().crc_combine(run, int(crc[s, -1]), int(nb[s]))
+            run = api.crc_combine(run, int(crc[s, -1]), int(nb[s]))
             whole += rows[s, :nb[s]].tobytes()
         assert run == host_crc(whole) and len(whole) > 0, "stream %d" % s
 
@@ -139,7 +96,7 @@ def test_rows_longer_than_one_pass_of_the_workgroup():
     """3 streams, CBR-320 stereo, 48 frames: rows of about 48 KB, which take three passes of 16 KB each"""
     S, F = 3, 48
     pcm = np.stack([synth.stream_pcm(4100 + i, F, rho=(0.7, 0.0, 0.3)[i], bursts=True) for i in range(S)]).astype(np.float32)
-    (rows, nb, stats, crc, e), = run_twins(batch_of(api().default_control(bitrate=160), F, nstreams=S), pcm, [F], tag="cbr320")
+    (rows, nb, stats, crc, e), = run_twins(batch_of(api.default_control(bitrate=160), F, nstreams=S), pcm, [F], tag="cbr320")
     assert nb.min() > 2 * PASS_BYTES + 16
     assert len(set((e[0] // PASS_BYTES).tolist())) >= 3        # frames end in several passes
 
@@ -159,20 +116,20 @@ def test_pipelined_submits_write_the_buffers_set_at_the_submit():
     import torch
     S, calls = 5, [3, 4]
     controls, pcm = mixed_controls(S), mixed_pcm(S, sum(calls), 4000)
-    t = api().Batch(controls, max_frames=max(calls))
+    t = api.Batch(controls, max_frames=max(calls))
     want = []
     for c, nf in enumerate(calls):
-        o, _ = device_call(t, cut(pcm, sum(calls[:c]), nf), nf, crc=False)
+        o = device_call(t, cut(pcm, sum(calls[:c]), nf), nf, crc=False)
         sync()
         want.append(o.host())
     t.close()
-    b = api().Batch(controls, max_frames=max(calls))
-    outs = [Out(b, nf) for nf in calls]
+    b = api.Batch(controls, max_frames=max(calls))
+    outs = [out_bufs(b, nf) for nf in calls]
     d_pcm = [torch.from_numpy(cut(pcm, sum(calls[:c]), nf)).to(dev()) for c, nf in enumerate(calls)]
     sync()
     for c, nf in enumerate(calls):
         outs[c].set_on(b)
-        b.submit_device(d_pcm[c].data_ptr(), nf, outs[c].rows.ptr, outs[c].rows.stride, outs[c].rows.nb.data_ptr(), cur_stream(), f32=True)
+        b.submit_device(d_pcm[c].data_ptr(), nf, outs[c].ptr, outs[c].stride, outs[c].nb.data_ptr(), cur_stream(), f32=True)
     b.crc_buffer(None)
     b.wait(cur_stream())
     sync()
@@ -190,14 +147,14 @@ def test_mpeg2_batch():
     """22.05 kHz: every input frame yields two frames; two frames per call"""
     S = 4
     pcm = np.stack([synth.stream_pcm(4200 + i, 6, sr=22050, rho=(0.7, 0.0, 1.0, 0.3)[i], bursts=True) for i in range(S)]).astype(np.float32)
-    res = run_twins(batch_of([api().default_control(samprate=22050) for _ in range(S)], 2), pcm, [2, 2, 2], tag="mpeg2")
+    res = run_twins(batch_of([api.default_control(samprate=22050) for _ in range(S)], 2), pcm, [2, 2, 2], tag="mpeg2")
     assert res[2][1].min() > 0
 
 
 def test_mono_batch():
     S = 4
     pcm = np.stack([synth.stream_pcm(4300 + i, 8, bursts=True)[:, 0] for i in range(S)]).astype(np.float32)[:, :, None]
-    res = run_twins(batch_of(api().default_control(mode=3), 5, nstreams=S), pcm, [3, 5], tag="mono")
+    res = run_twins(batch_of(api.default_control(mode=3), 5, nstreams=S), pcm, [3, 5], tag="mono")
     assert res[1][1].min() > 0
 
 
@@ -205,14 +162,14 @@ def test_first_generation_allocator_batch():
     """dual channel at 16 kHz, 2 x 8 kbit/s (the configuration of the golden stream a1_dual_16k_antiphase): k_alloc1_lsf"""
     S = 3
     pcm = np.stack([synth.stream_pcm(4400 + i, 8, sr=16000, rho=(1.0, 0.25, 0.0)[i], bursts=True) for i in range(S)]).astype(np.float32)
-    res = run_twins(batch_of(api().default_control(samprate=16000, mode=2, bitrate=8), 4, nstreams=S), pcm, [4, 4], tag="dual 16k")
+    res = run_twins(batch_of(api.default_control(samprate=16000, mode=2, bitrate=8), 4, nstreams=S), pcm, [4, 4], tag="dual 16k")
     assert res[1][1].min() > 0
 
 
 def child_check(build):
     """(runs in a child process with HMP3AMD_K6 = build in its environment, which a batch reads when it is created)"""
     S = 5
-    b = api().Batch(mixed_controls(S), max_frames=4)
+    b = api.Batch(mixed_controls(S), max_frames=4)
     assert b.k6_variant() == {"fat": 0, "slim": 1}[build]
     b.close()
     res = run_twins(batch_of(mixed_controls(S), 4), mixed_pcm(S, 8, 4000), [4, 4], tag=build)
@@ -229,7 +186,6 @@ def test_both_builds_of_the_rate_loop_kernel(build):
 def test_converting_batch():
     """hx_batch_encode_src_device, 48 kHz 24-bit sources encoded at 44.1 kHz, two calls"""
     import torch
-    from test_gpu_src_batch import Stream, make_batch
     streams = [Stream(48000, 24, 0, mpeg_select=44100, seed=91 + i, seconds=1.0) for i in range(4)]
     S, nf = len(streams), 4
     pos = {True: [0] * S, False: [0] * S}
@@ -243,12 +199,12 @@ def test_converting_batch():
                 chunk = np.frombuffer(s.data[pos[with_crc][i]:pos[with_crc][i] + in_stride], np.uint8)
                 rows_in[i, :len(chunk)] = chunk
             d_in = torch.from_numpy(rows_in).to(dev())
-            o = Out(b, nf)
+            o = out_bufs(b, nf)
             used = np.zeros(S, np.int64)
             sync()
-            o.set_on(b, with_crc)
-            assert api().lib().hx_batch_encode_src_device(b.h, d_in.data_ptr(), in_stride, None, nf, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(),
-                                                          used.ctypes.data, cur_stream()) == 0, api().last_error()
+            o.set_on(b, crc=with_crc)
+            assert api.lib().hx_batch_encode_src_device(b.h, d_in.data_ptr(), in_stride, None, nf, o.ptr, o.stride, o.nb.data_ptr(),
+                                                          used.ctypes.data, cur_stream()) == 0, api.last_error()
             sync()
             assert b.status() == 0
             got[with_crc] = o
@@ -268,8 +224,8 @@ def test_host_calls_return_the_crcs_of_the_device_path():
     S, calls = 7, [1, 3]
     controls, pcm = mixed_controls(S), mixed_pcm(S, sum(calls), 4000)
     want = run_twins(batch_of(controls, max(calls)), pcm, calls, tag="device path")
-    b = api().Batch(controls, max_frames=max(calls))
-    m = api().Multi(controls, max_frames=max(calls), devices=[0, 0, 0])
+    b = api.Batch(controls, max_frames=max(calls))
+    m = api.Multi(controls, max_frames=max(calls), devices=[0, 0, 0])
     assert [m.shard(k)[2] for k in range(3)] == [3, 2, 2]
     for c, nf in enumerate(calls):
         rows, nb, stats, crc, e = want[c]
@@ -280,7 +236,7 @@ def test_host_calls_return_the_crcs_of_the_device_path():
             assert (st == stats).all() and cr.dtype == np.uint16 and (cr == crc).all(), "%s call %d" % (name, c)
     assert b.status() == 0 and m.status() == 0 and want[1][1].min() > 0
     n = S * calls[1]
-    null = [(b.h, api().lib().hx_batch_encode_f32_host_crc), (m.h, api().lib().hx_multi_encode_f32_host_crc)]
+    null = [(b.h, api.lib().hx_batch_encode_f32_host_crc), (m.h, api.lib().hx_multi_encode_f32_host_crc)]
     out, nb, st, cr = np.zeros((S, b.out_stride(3)), np.uint8), np.zeros(S, np.int32), np.zeros(2 * n, np.int32), np.zeros(n, np.uint16)
     for h, fn in null:      # both arrays are required
         assert fn(h, blk.ctypes.data, 3, out.ctypes.data, out.shape[1], nb.ctypes.data, st.ctypes.data, None) == -1
@@ -296,23 +252,23 @@ def test_crc_buffer_without_frame_counters_is_refused():
     S, nf = 5, 4
     controls, pcm = mixed_controls(S), mixed_pcm(S, 8, 4000)
     want = run_twins(batch_of(controls, nf), pcm, [nf, nf], tag="twin")
-    b = api().Batch(controls, max_frames=nf)
-    o = Out(b, nf)
+    b = api.Batch(controls, max_frames=nf)
+    o = out_bufs(b, nf)
     d_pcm = torch.from_numpy(cut(pcm, 0, nf)).to(dev())
     sync()
-    L = api().lib()
+    L = api.lib()
     with pytest.raises(RuntimeError, match="2-byte aligned"):
         b.crc_buffer(o.crc.data_ptr() + 1)
     b.crc_buffer(o.crc.data_ptr())
     for fn in (L.hx_batch_encode_f32_device, L.hx_batch_submit_f32_device):
-        assert fn(b.h, d_pcm.data_ptr(), nf, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream()) == -1
-        assert "frame-counter" in api().last_error()
+        assert fn(b.h, d_pcm.data_ptr(), nf, o.ptr, o.stride, o.nb.data_ptr(), cur_stream()) == -1
+        assert "frame-counter" in api.last_error()
     assert b.status() == 0
     sync()
     rows, nb, stats, crc, guard = o.host()
     assert (nb == -1).all() and (stats == -1).all() and (crc == FILL16).all() and not rows.any()
     for c in range(2):
-        o, _ = device_call(b, cut(pcm, c * nf, nf), nf)
+        o = device_call(b, cut(pcm, c * nf, nf), nf)
         sync()
         rows, nb, stats, crc, e = check(o, "after the refusal, call %d" % c)
         assert nb.tolist() == want[c][1].tolist() and (rows == want[c][0]).all() and (crc == want[c][3]).all()
@@ -320,34 +276,18 @@ def test_crc_buffer_without_frame_counters_is_refused():
     b.close()
 
 
-def write_wav(path, pcm_i16, sr):
-    with wave.open(path, "wb") as w:
-        w.setnchannels(2)
-        w.setsampwidth(2)
-        w.setframerate(sr)
-        w.writeframes(np.ascontiguousarray(pcm_i16, dtype="<i2").tobytes())
-
-
 def test_cli_batch_mode_writes_the_crc_of_the_audio_bytes(tmp_path):
     """`hmp3amd -batch` on three WAVs of 40, 100 and 200 frames (calls of 96 frames: the files end in the first, second
     and third call, each inside it): the outputs equal the single-file mode's byte for byte, and the MusicCRC field of
     the tag is the host's CRC of the audio bytes behind the tag frame"""
-    exe = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-    assert os.path.exists(exe), "hmp3_amd/build.sh builds the CLI"
     kbps = [0, 32, 40, 48, 56, 64, 80, 96, 112, 128, 160, 192, 224, 256, 320]
-    args, names = [], []
+    files = []
     for i, frames in enumerate((40, 100, 200)):
         wav = str(tmp_path / ("in%d.wav" % i))
-        write_wav(wav, synth.stream_pcm(4500 + i, frames, bursts=True)[:frames * 1152 - 333 * i], 44100)
-        names.append((wav, str(tmp_path / ("batch%d.mp3" % i)), str(tmp_path / ("single%d.mp3" % i))))
-        args += [wav, names[-1][1]]
-    r = subprocess.run([exe, "-batch"] + args, capture_output=True)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
-    for wav, batch, single in names:
-        r = subprocess.run([exe, wav, single], capture_output=True)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
-        data = open(batch, "rb").read()
-        assert data == open(single, "rb").read(), wav
+        write_wav(wav, synth.stream_pcm(4500 + i, frames, bursts=True)[:frames * 1152 - 333 * i], 44100, False)
+        files.append((wav, wav, str(tmp_path / ("batch%d.mp3" % i))))
+    _, outputs = batch_vs_single_vs_reference(files, reference=False)
+    for (wav, _, _), data in zip(files, outputs):
         assert data[0] == 0xFF and (data[1] >> 3) & 1 == 1 and (data[2] >> 2) & 3 == 0       # MPEG-1, 44.1 kHz
         head_bytes = 144000 * kbps[data[2] >> 4] // 44100
         at = data.index(b"LAMEH5.24", 0, head_bytes) + 32     # version 9, revision 1, lowpass 1, ReplayGain 8, flags 2, delays 3, misc 4, length 4

@@ -5,150 +5,36 @@ host calls that move only the image, a converting batch and an MPEG-2 batch.
 Every comparison is equality.  The contract, with nb = out_bytes: off = [0, cumsum(round_up(nb, 16))]; segment i is the first
 nb[i] bytes of row i; the bytes up to off[i + 1] are zero; the rows and nb are what a twin batch without dense output
 writes.  Images are prefilled with 0xA5, so a byte a call must not write stays recognisable."""
-import ctypes as C
-import functools
-
 import numpy as np
 import pytest
 
-from hmp3_amd import synth
+from dense_cases import RATES, mixed_controls, mixed_pcm
+from gpu_support import FILL, CallBufs, Image, Pinned, cur_stream, cut, dev, oracle_bytes, sync
+import gpu_support as G
+from hmp3_amd import api, synth
+from output_checks import check_image, closed_form, round16
+from src_cases import Stream, make_batch
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
-GUARD = 4096
-RATES = (32000, 44100, 48000)
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def dev():
-    import torch
-    return torch.device("cuda:0")
-
-
-def sync():
-    import torch
-    torch.cuda.synchronize()
-
-
-def cur_stream():
-    import torch
-    return torch.cuda.current_stream().cuda_stream
-
-
-def round16(n):
-    return (np.asarray(n, dtype=np.int64) + 15) & ~15
-
-
-def closed_form(nb):
-    return np.concatenate([[0], np.cumsum(round16(nb))]).astype(np.int64)
-
-
-@functools.lru_cache(maxsize=None)
-def mixed_pcm(S, F, first, unique=66):
-    """fp32 PCM [S, F * 1152, 2] at int16 values, stream i at RATES[i % 3]; beyond `unique` distinct streams the rest are
-    time-rotated copies of their class (generation stays cheap at S = 1100)"""
-    base = [synth.stream_pcm(first + i, F, sr=RATES[i % 3], rho=(0.7, 0.0, 1.0, 0.3)[i % 4], bursts=True) for i in range(min(S, unique))]
-    out = np.empty((S, F * 1152, 2), dtype=np.float32)
-    for i in range(S):
-        out[i] = base[i] if i < unique else np.roll(base[i % unique], 1152 * (i // unique) // 2 + 97 * (i // unique), axis=0)
-    out.setflags(write=False)
-    return out
-
-
-def mixed_controls(S, **kw):
-    """VBR-50 by default: the streams' byte counts differ"""
-    a = api()
-    return [a.default_control(samprate=RATES[i % 3], **kw) for i in range(S)]
-
-
-def cut(pcm, f0, nf):
-    return np.ascontiguousarray(pcm[:, f0 * 1152:(f0 + nf) * 1152])
-
-
-class Rows:
-    """row buffers of one call inside a larger allocation: the first row `shift` bytes past a 16-byte boundary, `extra` bytes
-    added to hx_batch_out_stride"""
-
-    def __init__(self, b, nf, shift=0, extra=0):
-        import torch
-        self.S, self.stride = b.n, b.out_stride(nf) + extra
-        self.buf = torch.zeros(self.S * self.stride + 64, dtype=torch.uint8, device=dev())
-        self.o = (-self.buf.data_ptr()) % 16 + shift
-        self.nb = torch.full((self.S,), -1, dtype=torch.int32, device=dev())
-        self.ptr = self.buf.data_ptr() + self.o
-
-    def host(self):
-        r = self.buf.cpu().numpy()[self.o:self.o + self.S * self.stride].reshape(self.S, self.stride)
-        return r, self.nb.cpu().numpy()
-
-
-class Image:
-    """a prefilled dense image of `cap` bytes with a guard region behind it, and its offsets"""
-
-    def __init__(self, S, cap, fill=FILL):
-        import torch
-        self.cap, self.fill = int(cap), fill
-        self.buf = torch.full((self.cap + GUARD + 16,), fill, dtype=torch.uint8, device=dev())
-        self.o = (-self.buf.data_ptr()) % 16
-        self.off = torch.full((S + 1,), -1, dtype=torch.int64, device=dev())
-        self.ptr = self.buf.data_ptr() + self.o
-
-    def set_on(self, b):
-        b.dense_buffers(self.ptr, self.cap, self.off.data_ptr())
-
-    def prefill(self):
-        """(again: the same buffers for a further call, the batch's setter untouched)"""
-        self.buf.fill_(self.fill)
-        self.off.fill_(-1)
-        sync()
-
-    def host(self):
-        return self.buf.cpu().numpy()[self.o:self.o + self.cap + GUARD], self.off.cpu().numpy()
-
-
-def check_image(rows, nb, dense, off, cap, fill=FILL, tag=""):
-    """the contract: closed-form offsets; every segment that fits below cap equals its row and its padding is zero; from the
-    first segment that does not fit (or the image's end) to the end of the guard region nothing was written"""
-    S = len(nb)
-    assert (nb >= 0).all(), tag
-    assert off.tolist() == closed_form(nb).tolist(), tag + ": offsets"
-    fits = int(np.searchsorted(off, cap, side="right")) - 1         # segments 0 .. fits - 1 end at or below cap
-    want = np.zeros(int(off[fits]), dtype=np.uint8)
-    for i in range(fits):
-        want[off[i]:off[i] + nb[i]] = rows[i, :nb[i]]
-    bad = np.nonzero(dense[:len(want)] != want)[0]
-    assert bad.size == 0, "%s: image differs from the rows at byte %d (stream %d)" % (tag, bad[0], np.searchsorted(off, bad[0], side="right") - 1)
-    assert (dense[len(want):] == fill).all(), tag + ": bytes written behind the last segment that fits"
-    return fits
+GUARD = 4096            # (gpu_support.Image's guard region behind the image)
 
 
 def device_call(b, blk, nf, image, shift=0, extra=0, submit=False):
     """one fp32 device call into fresh row buffers, dense on when `image` is given (not waited for)"""
-    import torch
-    r = Rows(b, nf, shift, extra)
-    d_pcm = torch.from_numpy(blk).to(dev())
-    sync()
-    if image is not None:
-        image.set_on(b)
-    (b.submit_device if submit else b.encode_device)(d_pcm.data_ptr(), nf, r.ptr, r.stride, r.nb.data_ptr(), cur_stream(), f32=True)
-    return r, d_pcm
+    return G.device_call(b, blk, nf, CallBufs(b, nf, shift=shift, extra=extra, image=image).set_on(b), submit=submit)
 
 
 def run_twins(controls, pcm, calls, shift=0, extra=0, caps=None, tag=""):
     """the same plain device calls on two batches, one with dense output (caps[c]: the image's capacity, default the bound),
     one without: rows and byte counts identical, every image checked -> (per call: rows, nb, dense, off), the dense batch"""
     maxF = max(calls)
-    bd, bt = api().Batch(controls, max_frames=maxF), api().Batch(controls, max_frames=maxF)
+    bd, bt = api.Batch(controls, max_frames=maxF), api.Batch(controls, max_frames=maxF)
     res, f0 = [], 0
     for c, nf in enumerate(calls):
         cap = bd.dense_bound(nf) if caps is None or caps[c] is None else caps[c]
         img = Image(bd.n, cap)
-        rd, _ = device_call(bd, cut(pcm, f0, nf), nf, img, shift, extra)
-        rt, _ = device_call(bt, cut(pcm, f0, nf), nf, None, shift, extra)
+        rd = device_call(bd, cut(pcm, f0, nf), nf, img, shift, extra)
+        rt = device_call(bt, cut(pcm, f0, nf), nf, None, shift, extra)
         sync()
         (rows, nb), (trows, tnb) = rd.host(), rt.host()
         assert nb.tolist() == tnb.tolist() and (rows == trows).all(), "%s call %d: rows / byte counts differ from the twin batch's" % (tag, c)
@@ -165,7 +51,6 @@ def test_image_equals_rows_and_offsets_equal_the_closed_form():
     """1100 streams (more than one 1024-lane round of the offsets scan, many wave boundaries) of three rates, VBR-50: a
     first call of one frame, in which no stream emits anything (empty segments, the image untouched), then three frames;
     the first streams' segments against the oracle"""
-    from test_gpu_parity import oracle_bytes
     S = 1100
     pcm = mixed_pcm(S, 4, 3000)
     res, b = run_twins(mixed_controls(S), pcm, [1, 3], tag="1100 streams")
@@ -200,7 +85,7 @@ def test_capacity():
     img = Image(S, b.dense_bound(F))
     with pytest.raises(RuntimeError, match="16-byte aligned"):
         b.dense_buffers(img.ptr + 4, img.cap - 16, img.off.data_ptr())
-    r, _ = device_call(b, cut(pcm, F, F), F, img)
+    r = device_call(b, cut(pcm, F, F), F, img)
     sync()
     assert b.status() == 0 and r.host()[1].min() > 0
     check_image(*r.host(), *img.host(), img.cap, tag="after the refusal")
@@ -221,10 +106,10 @@ def test_capacity():
 
 def plain_rows(controls, pcm, calls):
     """(rows, nb) of plain device calls on a batch without dense output"""
-    b = api().Batch(controls, max_frames=max(calls))
+    b = api.Batch(controls, max_frames=max(calls))
     out, f0 = [], 0
     for nf in calls:
-        r, _ = device_call(b, cut(pcm, f0, nf), nf, None)
+        r = device_call(b, cut(pcm, f0, nf), nf, None)
         sync()
         out.append(r.host())
         f0 += nf
@@ -244,10 +129,10 @@ def test_pipelined_device_submits(nsets, calls, last):
     S = 37
     controls, pcm = mixed_controls(S), mixed_pcm(S, sum(calls), 3200)
     want = plain_rows(controls, pcm, calls)
-    b = api().Batch(controls, max_frames=max(calls))
+    b = api.Batch(controls, max_frames=max(calls))
     bound = b.dense_bound(max(calls))
     images = [Image(S, bound) for _ in range(nsets)]
-    rows = [Rows(b, max(calls)) for _ in range(nsets)]
+    rows = [CallBufs(b, max(calls)) for _ in range(nsets)]
     scratch = Image(S, bound, fill=0x5A)
     import torch
     d_pcm, f0 = [], 0
@@ -285,27 +170,6 @@ def test_pipelined_device_submits(nsets, calls, last):
     assert sum(int(want[c][1].sum()) for c in range(len(calls))) > 0
 
 
-class Pinned:
-    """page-locked host arrays from hx_pinned_alloc"""
-
-    def __init__(self):
-        self.ptrs = []
-
-    def array(self, n, dtype, fill):
-        nbytes = int(n) * np.dtype(dtype).itemsize
-        p = api().lib().hx_pinned_alloc(nbytes)
-        assert p
-        self.ptrs.append(p)
-        a = np.frombuffer((C.c_ubyte * nbytes).from_address(p), dtype=dtype)
-        a[:] = fill
-        return a
-
-    def free(self):
-        for p in self.ptrs:
-            api().lib().hx_pinned_free(p)
-        self.ptrs = []
-
-
 def check_host_image(want, nb, dense, off, tag):
     """a host call's image against the list of bitstreams a row call of a twin batch returned"""
     S = len(want)
@@ -322,21 +186,21 @@ def test_synchronous_host_calls_return_the_image_of_the_row_calls():
     second call through Batch.encode_host_dense; a capacity of half the image returns the segments that fit"""
     S, F = 37, 6
     controls, pcm = mixed_controls(S), mixed_pcm(S, 2 * F, 3300)
-    t = api().Batch(controls, max_frames=F)
+    t = api.Batch(controls, max_frames=F)
     want = [t.encode_host(cut(pcm, c * F, F)) for c in range(2)]
     t.close()
-    b = api().Batch(controls, max_frames=F)
+    b = api.Batch(controls, max_frames=F)
     cap = b.dense_bound(F)
     assert cap == S * round16(b.out_stride(F))
     dense, off, nb = np.full(cap + GUARD, FILL, np.uint8), np.full(S + 1, -1, np.int64), np.full(S, -1, np.int32)
     blk = cut(pcm, 0, F)
-    assert api().lib().hx_batch_encode_f32_host_dense(b.h, blk.ctypes.data, F, dense.ctypes.data, cap, off.ctypes.data, nb.ctypes.data) == 0, api().last_error()
+    assert api.lib().hx_batch_encode_f32_host_dense(b.h, blk.ctypes.data, F, dense.ctypes.data, cap, off.ctypes.data, nb.ctypes.data) == 0, api.last_error()
     check_host_image(want[0], nb, dense, off, "call 0")
     got, off1 = b.encode_host_dense(cut(pcm, F, F))
     assert got == want[1] and off1.tolist() == closed_form([len(w) for w in want[1]]).tolist()
     assert b.status() == 0 and sum(len(w) for w in want[1]) > 0
     b.close()
-    b = api().Batch(controls, max_frames=F)
+    b = api.Batch(controls, max_frames=F)
     b.encode_host_dense(cut(pcm, 0, F))
     half = (int(off1[S]) // 2) & ~15
     got, off2 = b.encode_host_dense(cut(pcm, F, F), dense_cap=half)
@@ -353,11 +217,11 @@ def test_device_image_set_once_holds_across_a_host_call_that_returns_the_image()
     a twin batch's; the host call returns the twin's bitstreams and leaves the device image and offsets as prefilled."""
     S, nf = 3, 2
     controls, pcm = mixed_controls(S), mixed_pcm(S, 3 * nf, 3500)
-    t = api().Batch(controls, max_frames=nf)
+    t = api.Batch(controls, max_frames=nf)
     want = [t.encode_host(cut(pcm, c * nf, nf)) for c in range(3)]
     assert t.status() == 0 and sum(len(w) for ws in want for w in ws) > 0
     t.close()
-    b = api().Batch(controls, max_frames=nf)
+    b = api.Batch(controls, max_frames=nf)
     img = Image(S, b.dense_bound(nf))
     img.set_on(b)
     for c in range(3):
@@ -370,7 +234,7 @@ def test_device_image_set_once_holds_across_a_host_call_that_returns_the_image()
             dense, d_off = img.host()
             assert (dense == FILL).all() and (d_off == -1).all(), "the host call wrote the caller's device image"
         else:
-            r, d_pcm = device_call(b, blk, nf, None)
+            r = device_call(b, blk, nf, None)
             sync()
             rows, nb = r.host()
             assert [rows[s, :nb[s]].tobytes() for s in range(S)] == want[c], "call %d: rows differ from the twin batch's" % c
@@ -386,7 +250,7 @@ def test_pipelined_host_calls_write_the_image_into_page_locked_memory():
     S, F, calls = 37, 6, 3
     controls = mixed_controls(S)
     pcm = mixed_pcm(S, calls * F, 3300).astype(np.int16)
-    t = api().Batch(controls, max_frames=F)
+    t = api.Batch(controls, max_frames=F)
     stride = t.out_stride(F)
     t_out = [np.zeros((S, stride), np.uint8) for _ in range(calls)]
     t_nb = [np.zeros(S, np.int32) for _ in range(calls)]
@@ -397,7 +261,7 @@ def test_pipelined_host_calls_write_the_image_into_page_locked_memory():
     assert t.status() == 0
     t.close()
     want = [[t_out[c][s, :t_nb[c][s]].tobytes() for s in range(S)] for c in range(calls)]
-    b = api().Batch(controls, max_frames=F)
+    b = api.Batch(controls, max_frames=F)
     cap = b.dense_bound(F)
     pin = Pinned()
     try:
@@ -431,7 +295,6 @@ def test_converting_batch_image_equals_its_rows():
     """hx_batch_encode_src_device (48 kHz 24-bit sources encoded at 44.1 kHz) with dense output: the image of what the
     converting call wrote into its rows"""
     import torch
-    from test_gpu_src_batch import Stream, make_batch
     streams = [Stream(48000, 24, 0, mpeg_select=44100, seed=81 + i, seconds=1.0) for i in range(5)]
     S, nf = len(streams), 4
     b = make_batch(streams, nf)
@@ -443,11 +306,11 @@ def test_converting_batch_image_equals_its_rows():
             chunk = np.frombuffer(s.data[pos[i]:pos[i] + in_stride], np.uint8)
             rows_in[i, :len(chunk)] = chunk
         d_in = torch.from_numpy(rows_in).to(dev())
-        r, img = Rows(b, nf), Image(S, b.dense_bound(nf))
+        r, img = CallBufs(b, nf), Image(S, b.dense_bound(nf))
         used = np.zeros(S, np.int64)
         sync()
         img.set_on(b)
-        assert api().lib().hx_batch_encode_src_device(b.h, d_in.data_ptr(), in_stride, None, nf, r.ptr, r.stride, r.nb.data_ptr(), used.ctypes.data, cur_stream()) == 0, api().last_error()
+        assert api.lib().hx_batch_encode_src_device(b.h, d_in.data_ptr(), in_stride, None, nf, r.ptr, r.stride, r.nb.data_ptr(), used.ctypes.data, cur_stream()) == 0, api.last_error()
         sync()
         assert b.status() == 0
         (rows, nb), (dense, off) = r.host(), img.host()
@@ -462,7 +325,7 @@ def test_converting_batch_image_equals_its_rows():
 def test_mpeg2_image_equals_rows():
     """an MPEG-2 batch (22.05 kHz): every input frame yields two frames, and the byte counts cover both"""
     S, F = 9, 4
-    a = api()
+    a = api
     pcm = np.stack([synth.stream_pcm(3400 + i, 2 * F, sr=22050, rho=(0.7, 0.0, 1.0, 0.3)[i % 4], bursts=True) for i in range(S)]).astype(np.float32)
     res, b = run_twins([a.default_control(samprate=22050) for _ in range(S)], pcm, [F, F], tag="mpeg2")
     assert b.status() == 0

@@ -20,14 +20,10 @@ from oracle import oracle as O
 from conftest import skip_unless_host_libm_is_the_restated_one
 import dynamic_range_cases as DR
 from stage_taps import TapBatch
+from hmp3_amd import api
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 def check_over_range(name):
@@ -36,7 +32,7 @@ def check_over_range(name):
     pcm = DR.over_range_batch(kw)
     S, F = len(pcm), DR.OVER_RANGE_F
     assert S == 12 and float(np.abs(pcm).max()) > 65536.0 * 32000 and np.isfinite(pcm).all()
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     short_beyond = 0
@@ -87,8 +83,8 @@ def test_over_range_stream_through_the_per_frame_entry():
     graph; every call's bytes"""
     kw = DR.OVER_RANGE["cbr320"]
     pcm = DR.over_range_stream(kw, 64)
-    e = api().Mp3Enc()
-    assert e.L3_audio_encode_init(api().default_control(**kw)) == 9216
+    e = api.Mp3Enc()
+    assert e.L3_audio_encode_init(api.default_control(**kw)) == 9216
     o = O.OracleEncoder(O.default_control(**kw))
     total = 0
     for f in range(DR.OVER_RANGE_F):
@@ -113,7 +109,7 @@ def test_device_pow_gives_the_reference_noise_term_at_every_gain_step():
     (oracle.pow43: the C library of the machine the test runs on)."""
     import math
     first, n = 16384, (1 << 21) - 16384
-    b = api().Batch(api().default_control(bitrate=64), nstreams=1, max_frames=1)
+    b = api.Batch(api.default_control(bitrate=64), nstreams=1, max_frames=1)
     dev = b.debug_read("pow43_beyond", np.float64, n)
     b.close()
     host = O.pow43(first, n)
@@ -132,7 +128,7 @@ def test_device_pow_gives_the_reference_noise_term_at_every_gain_step():
 def run_subnormal(name, which):
     kw, taps = DR.SUBNORMAL[name]
     pcm, F = (DR.subnormal_peaks(kw), DR.PEAKS_F) if which == "peaks" else (DR.subnormal_ramps(kw), DR.RAMPS_F)
-    tb = TapBatch(api(), kw, len(pcm), F, taps)
+    tb = TapBatch(api, kw, len(pcm), F, taps)
     tb.call(pcm)
     sb, xr = [sum(v) for v in tb.sub_sb], [sum(v) for v in tb.sub_xr]
     print("%s %s: subnormal values in the oracle's sample_new %s, xr_pre %s" % (name, which, sb, xr))
@@ -184,7 +180,7 @@ def check_dc_tail(name):
     pcm = DR.dc_tail_batch(kw, F)
     calls = [1, 7, 40, 30, F - 78] if F > 78 else [1, 7, 40, F - 48]
     starts = list(np.cumsum(calls)[:-1])
-    tb = TapBatch(api(), kw, len(pcm), max(calls), "full" if kw.get("samprate", 44100) >= 32000 else "lines")
+    tb = TapBatch(api, kw, len(pcm), max(calls), "full" if kw.get("samprate", 44100) >= 32000 else "lines")
     pos = 0
     for n in calls:
         tb.call(pcm[:, pos * 1152:(pos + n) * 1152])
@@ -226,7 +222,7 @@ def test_range_golden_reference_streams(name):
     kw, nfr, fmt = M.RANGE_CASES[name]
     pcm = M.range_case_pcm(name)
     pcm = np.concatenate([pcm, np.zeros((2 * 1152, 2), dtype=pcm.dtype)])
-    b = api().Batch(api().default_control(**kw), nstreams=3, max_frames=nfr + 2)
+    b = api.Batch(api.default_control(**kw), nstreams=3, max_frames=nfr + 2)
     got = b.encode_host(np.stack([pcm, pcm, pcm]))
     assert b.status() == 0
     want = open(os.path.join(GOLD, name + ".mp3frames"), "rb").read()

@@ -12,9 +12,11 @@ import pytest
 
 import file_image_cases as K
 import file_tag_cases as T
-from hmp3_amd import synth
-from test_gpu_dense import api, cur_stream, dev, sync
-from test_gpu_file_images import CHUNK, PAT, Files, Out, image_of, prefill, rows_block, small_pcm, small_restart_pcm, vbr_small
+from file_image_cases import CHUNK, PAT, rows_block
+from file_image_support import Files, file_bufs, image_of, prefill, vbr_small
+from gpu_support import cur_stream, dev, sync
+from hmp3_amd import api, synth
+from ledger_cases import small_pcm, small_restart_pcm
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
 SENT = 0x6B
@@ -68,7 +70,7 @@ def test_small_shape_all_slots_a_subset_and_the_live_state():
     """in the middle of the run (live records: the segments are what the device holds then) and after the last call: all
     slots, and a shuffled subset; slot NEVER and - with head_bytes 0 - the slot that was fed one frame before its file has a
     byte give empty segments; a list of one; the empty list"""
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     r = run_small(upto=2)
     S = r.S
     live = [s for s in range(S) if r.want[s].open and not r.want[s].ended]
@@ -103,7 +105,7 @@ def chunk_edge_batch():
     """four slots with the same stream at 320 kbit/s (test_chunk_edges' means), files of 12 calls: run once with head_bytes 0
     to learn the files' size B, then begun again with the heads that make the segments 16 KB - 1, 16 KB, 16 KB + 1 and
     2 x 16 KB + 5 long"""
-    A = api()
+    A = api
     nc, nf = 12, 8
     pcm = synth.stream_pcm(7300, nc, bursts=True).astype(np.float32)
     b = A.Batch(A.default_control(bitrate=160), nstreams=4, max_frames=nf)
@@ -132,7 +134,7 @@ def chunk_edge_batch():
 def test_chunk_edges_and_a_dst_cap_one_byte_short():
     """segments of 16 KB - 1, 16 KB, 16 KB + 1 and 2 x 16 KB + 5 bytes, in every order of first slot; dst_cap one byte short:
     -1, dst untouched, the offsets filled in"""
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     b, want = chunk_edge_batch()
     for first in range(4):
         idx = [(first + k) % 4 for k in range(4)]
@@ -152,7 +154,7 @@ def test_device_form_against_the_host_form():
     offsets are complete, the segments that fit in whole are written, the others are not, nothing at or beyond dst_cap is, and
     status bit 16 is set; a misaligned d_dst or d_off and the list errors are refused"""
     import torch
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     b, want = chunk_edge_batch()
     idx = [2, 0, 3, 1]
     total = sum(r16(w) for w in want)
@@ -203,7 +205,7 @@ def test_device_form_against_the_host_form():
 def test_multi_in_two_blocks_against_the_one_batch_twin():
     """hx_multi_file_tags and hx_multi_file_fetch_many over two blocks of device 0 (5 streams: uneven blocks), with a list that
     crosses the blocks out of order, against a one-batch twin that takes the same calls: the same image, the same offsets"""
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     ncalls = [3, 8, 13, 6, 2]
     full = [synth.stream_pcm(9300 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     ec = A.default_control()
@@ -258,9 +260,9 @@ def test_behind_a_pipelined_submit_with_deferred_packing():
     append - first, so the segments hold the bytes of all three calls (the host's model of the images)"""
     ncalls = [3, 40, 9, 14]
     full = [synth.stream_pcm(7600 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    r = Files(lambda: api().Batch(api().default_control(), nstreams=4, max_frames=8), full, 12000)
+    r = Files(lambda: api.Batch(api.default_control(), nstreams=4, max_frames=8), full, 12000)
     r.begin([0, 1, 2, 3], ncalls, [4, 11, 0, 15])
-    sets, keep = [Out(r.b, 8), Out(r.b, 8, shift=7)], []
+    sets, keep = [file_bufs(r.b, 8), file_bufs(r.b, 8, shift=7)], []
     for c in range(3):
         feed = lambda blk, counts, nf: keep.append(r.device_call(r.b, blk, counts, nf, submit=True, out=sets[c & 1])) and None
         r.step([8, 8, 0 if c == 1 else 8, 5], nf=8, feed=feed, check=False)

@@ -10,185 +10,18 @@ hx_batch_file_image_ptr, so after every call image == model says at once that th
 front of head_bytes, behind the file's end or at or beyond cap has changed (a restarted slot keeps the old file's bytes
 behind the new one's end: the model does too).  The twin's rows, counts, counters, CRCs and records must equal the image
 batch's.  Nothing here depends on the build of the rate-loop kernel: the tests run once (one_k6_build)."""
-import ctypes as C
-import functools
-import os
-import re
-
 import numpy as np
 import pytest
 
 import file_image_cases as K
-from hmp3_amd import synth
-from test_gpu_dense import Rows, api, cur_stream, dev, sync
-from test_gpu_ledger import Bufs, DRAIN, same_outputs, small_pcm, small_restart_pcm
+from file_image_cases import CHUNK, PAT
+from file_image_support import Files, file_bufs, image_of, prefill, vbr_small
+from gpu_support import cur_stream, dev, sync
+from hmp3_amd import api, synth
+from ledger_cases import DRAIN, small_pcm, small_restart_pcm
+from src_cases import Stream, make_batch
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-PAT = 0xA5
-CHUNK = int(re.search(r"#define HX_FILE_CHUNK (\d+)", open(os.path.join(ROOT, "hmp3_amd", "csrc", "hx_types.h")).read()).group(1))
-
-
-@functools.lru_cache(maxsize=None)
-def hip():
-    """the HIP runtime the library runs on (the copy the process has mapped), for copies from and to an image's address"""
-    api().lib()
-    for line in open("/proc/self/maps"):
-        if "libamdhip64" in line:
-            h = C.CDLL(line.split()[-1])
-            h.hipMemcpy.argtypes, h.hipMemset.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], [C.c_void_p, C.c_int, C.c_size_t]
-            return h
-    raise RuntimeError("no HIP runtime mapped")
-
-
-def pitch_of(b):
-    """the bytes from one slot's image to the next: cap rounded up to 16 (the header's allocation rule)"""
-    return (b.file_image_cap() + 15) & ~15
-
-
-def image_of(b, s):
-    """slot s's image, cap bytes; the bytes from cap to the next slot's image must hold the guard pattern"""
-    out = np.zeros(pitch_of(b), np.uint8)
-    assert hip().hipMemcpy(out.ctypes.data, b.file_image_ptr(s), len(out), 2) == 0
-    assert (out[b.file_image_cap():] == PAT).all(), "slot %d: a byte at or beyond cap was written" % s
-    return out[:b.file_image_cap()]
-
-
-def prefill(b):
-    for s in range(b.n):
-        assert b.file_image_ptr(s) == b.file_image_ptr(0) + s * pitch_of(b) and b.file_image_ptr(s) % 16 == 0
-    assert hip().hipMemset(b.file_image_ptr(0), PAT, b.n * pitch_of(b)) == 0
-    sync()
-
-
-def rows_block(full, given, counts, nf, P, dtype):
-    """the call's PCM rows [S, nf * 1152 * P]: stream s's next counts[s] frames of full[s] first in its row (a mono stream of
-    a stereo-pitched batch: its samples back to back), silence behind its end"""
-    blk = np.zeros((len(full), nf * 1152 * P), dtype)
-    for s, n in enumerate(counts):
-        part = full[s][given[s] * 1152:(given[s] + n) * 1152].reshape(-1)
-        blk[s, :len(part)] = part
-    return blk
-
-
-class Out(Bufs):
-    """Bufs with the first row `shift` bytes past a 16-byte boundary and `extra` bytes added to the stride"""
-
-    def __init__(self, b, nf, shift=0, extra=0):
-        super().__init__(b, nf)
-        self.rows = Rows(b, nf, shift, extra)
-
-
-class Files:
-    """a batch with file images (b: a Batch, or a Multi when `multi`) and its twin t without, both with a ledger; `want` the
-    host's records, `model` the host's images"""
-
-    def __init__(self, make, full, cap, f32=True, shift=0, extra=0, make_b=None, prefilled=True):
-        self.t, self.b = make(), (make_b or make)()
-        self.full, self.cap, self.f32, self.shift, self.extra = list(full), cap, f32, shift, extra
-        self.S, self.P = self.t.n, self.t.pcm_channels()
-        self.b.file_images(cap)
-        self.direct = prefilled and hasattr(self.b, "file_image_ptr")
-        if self.direct:
-            assert self.b.file_image_cap() == cap
-            prefill(self.b)
-        self.want = [api().Ledger() for _ in range(self.S)]
-        self.model = [np.full(cap, PAT, np.uint8) for _ in range(self.S)]
-        self.head, self.has, self.length = [0] * self.S, [False] * self.S, [0] * self.S
-        self.given, self.calls, self.pieces, self.status = [0] * self.S, 0, [], 0
-
-    def begin(self, idx, ncalls, heads):
-        fpc = [self.t.stream_frames_per_block(s) for s in idx]
-        for h in (self.b, self.t):
-            h.ledger_begin(idx, ncalls, heads, **({} if isinstance(h, api().Multi) else {"stream": cur_stream()}))
-        for e, s in enumerate(idx):
-            self.want[s] = api().ledger_open(ncalls[e], fpc[e], heads[e], 0)
-            self.head[s], self.has[s], self.length[s] = heads[e], True, 0
-
-    def block(self, counts, nf):
-        return rows_block(self.full, self.given, counts, nf, self.P, np.float32 if self.f32 else np.int16)
-
-    def device_call(self, h, blk, counts, nf, shift=0, extra=0, submit=False, out=None):
-        import torch
-        d_pcm = torch.from_numpy(blk).to(dev())
-        sync()
-        o = out or Out(h, nf, shift, extra)
-        o.set_on(h)
-        h.frame_counts(counts)
-        (h.submit_device if submit else h.encode_device)(d_pcm.data_ptr(), nf, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=self.f32)
-        o.keep = d_pcm
-        return o
-
-    def host_update(self, counts, rows, nb, st, cr):
-        """the twin's outputs of one call into the host's records and images"""
-        for s, n in enumerate(counts):
-            live = bool(self.want[s].open and not self.want[s].ended)
-            api().ledger_update(self.want[s], st[s, :n], cr[s, :n], nb[s])
-            w = self.want[s]
-            if n and w.open and self.has[s]:
-                at = self.head[s] + w.bytes - w.call_bytes
-                piece = rows[s, :w.call_bytes]
-                fit = max(0, min(len(piece), self.cap - at))
-                self.model[s][at:at + fit] = piece[:fit]
-                self.length[s] = max(0, min(w.bytes, self.cap - self.head[s]))
-                if fit < len(piece):
-                    self.status |= 64
-                self.pieces.append(dict(s=s, n=n, nb=int(nb[s]), cb=int(w.call_bytes), live=live, at=at, cut=fit < len(piece)))
-            self.given[s] += n
-
-    def check(self, tag, read=True):
-        polls = self.b.ledger_poll()
-        if read:
-            recs = self.b.ledger_read(list(range(self.S)))
-            trecs = self.t.ledger_read(list(range(self.S)))
-        for s in range(self.S):
-            assert polls[s].tobytes() == api().ledger_brief(self.want[s], self.length[s]).tobytes(), "%s: slot %d's brief (image_bytes %d, want %d)" % (
-                tag, s, polls[s].image_bytes, self.length[s])
-            if read:
-                assert recs[s].tobytes() == self.want[s].tobytes() == trecs[s].tobytes(), "%s: slot %d's record" % (tag, s)
-                assert polls[s].tobytes() == api().ledger_brief(recs[s], polls[s].image_bytes).tobytes()
-            if self.direct:
-                got = image_of(self.b, s)
-                bad = np.flatnonzero(got != self.model[s])
-                assert not len(bad), "%s: slot %d's image differs from the model at byte %d (head %d, length %d, cap %d; %d bytes differ)" % (
-                    tag, s, bad[0], self.head[s], self.length[s], self.cap, len(bad))
-            if self.has[s] and self.head[s] + self.length[s] <= self.cap + 64:
-                got = self.b.file_fetch(s, self.head[s] + self.length[s], fill=0x3C)
-                assert got == bytes([0x3C]) * self.head[s] + self.model[s][self.head[s]:self.head[s] + self.length[s]].tobytes(), "%s: fetch of slot %d" % (tag, s)
-
-    def step(self, counts, nf=None, feed=None, check=True, read=True):
-        """one call on both: the twin by a plain device call, the image batch the same way or through feed(blk, counts, nf)"""
-        nf = nf or max(counts)
-        blk = self.block(counts, nf)
-        tw = self.device_call(self.t, blk, counts, nf)
-        got = self.device_call(self.b, blk, counts, nf, self.shift, self.extra) if feed is None else feed(blk, counts, nf)
-        sync()
-        tag = "call %d" % self.calls
-        twin = tw.host()
-        if got is not None:
-            same_outputs(got.host(), twin, counts, tag)
-        self.host_update(counts, *twin)
-        self.calls += 1
-        if check:
-            self.check(tag, read)
-        return twin
-
-    def run(self, ncalls, call, stop=None, **kw):
-        """calls of `call` frames under counts until every begun file has ended"""
-        while True:
-            counts = [0 if (not self.want[s].open or self.want[s].ended) else max(0, min(call, ncalls[s] + DRAIN - self.given[s])) for s in range(self.S)]
-            if not any(counts) or (stop and self.calls >= stop):
-                break
-            self.step(counts, nf=call, **kw)
-
-    def close(self, status=None):
-        assert self.b.status() == (self.status if status is None else status) and self.t.status() == 0
-        self.b.close()
-        self.t.close()
-
-
-def vbr_small():
-    return api().Batch(api().default_control(), nstreams=len(K.SMALL_NCALLS), max_frames=8)
 
 
 # ---- 1: the small shape ----
@@ -238,7 +71,7 @@ def test_misaligned_rows(shift, extra):
     """d_out 1, 5 and 15 bytes past a 16-byte boundary, and an odd out_stride: the rows start at every misalignment"""
     ncalls = [2, 5, 9, 3]
     full = [synth.stream_pcm(7100 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    r = Files(lambda: api().Batch(api().default_control(), nstreams=4, max_frames=4), full, 6000, shift=shift, extra=extra)
+    r = Files(lambda: api.Batch(api.default_control(), nstreams=4, max_frames=4), full, 6000, shift=shift, extra=extra)
     r.begin([0, 1, 2, 3], ncalls, [3, 0, 8, 13])
     r.run(ncalls, 4)
     assert sum(q["cb"] > 0 for q in r.pieces) >= 5 and {q["at"] % 16 for q in r.pieces if q["cb"]} > {0} and all(w.ended for w in r.want)
@@ -250,7 +83,7 @@ def test_small_pieces():
     """calls of one frame: pieces of 0 bytes and of a few hundred, most vectors partial; the pieces start at every residue"""
     ncalls = [30, 34, 38]
     full = [synth.stream_pcm(7200 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    r = Files(lambda: api().Batch(api().default_control(), nstreams=3, max_frames=1), full, 16000)
+    r = Files(lambda: api.Batch(api.default_control(), nstreams=3, max_frames=1), full, 16000)
     r.begin([0, 1, 2], ncalls, [7, 0, 2])
     while not all(w.ended for w in r.want):
         r.step([1, 1, 1], check=r.calls % 8 == 0)
@@ -266,7 +99,7 @@ def test_chunk_edges():
     16-byte boundary: the second call's piece starts wherever the first one's ended"""
     nf = 2 * CHUNK // 1044 + 2
     full = [synth.stream_pcm(7300, 2 * nf, bursts=True).astype(np.float32)]
-    r = Files(lambda: api().Batch(api().default_control(bitrate=160), nstreams=1, max_frames=nf), full, 3 * nf * 1100)
+    r = Files(lambda: api.Batch(api.default_control(bitrate=160), nstreams=1, max_frames=nf), full, 3 * nf * 1100)
     r.begin([0], [2 * nf], [5])
     r.run([2 * nf], nf)
     big = [q for q in r.pieces if q["cb"] + q["at"] % 16 > 2 * CHUNK]
@@ -282,7 +115,7 @@ def test_overflow():
     slot 1 gets a shorter file that fits"""
     ncalls, heads = [4, 11, 6], [9, 6, 0]
     full = [synth.stream_pcm(7400 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    make = lambda: api().Batch(api().default_control(), nstreams=3, max_frames=8)
+    make = lambda: api.Batch(api.default_control(), nstreams=3, max_frames=8)
     scout = Files(make, full, 20000)            # the same calls with room for everything: where slot 1's second piece lies
     scout.begin([0, 1, 2], ncalls, heads)
     scout.run(ncalls, 8, check=False)
@@ -309,7 +142,7 @@ def test_overflow():
 # ---- 6: mixed kinds ----
 def test_mixed_kinds():
     """a create_any batch: MPEG-1 stereo, MPEG-2 (two frames per block) and a mono entry, in rows pitched for two channels"""
-    A = api()
+    A = api
     menu = [dict(), dict(samprate=22050), dict(mode=3, samprate=48000)]
     ncalls = [6, 9, 4]
     full = [synth.stream_pcm(7500, 6, bursts=True), synth.stream_pcm(7501, 9, sr=22050, bursts=True), synth.stream_pcm(7502, 4, sr=48000, bursts=True)[:, :1]]
@@ -328,9 +161,9 @@ def test_pipelined_submits():
     images, lengths and records equal those of the twin's plain calls"""
     ncalls = [3, 40, 9, 14]
     full = [synth.stream_pcm(7600 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    r = Files(lambda: api().Batch(api().default_control(), nstreams=4, max_frames=8), full, 12000)
+    r = Files(lambda: api.Batch(api.default_control(), nstreams=4, max_frames=8), full, 12000)
     r.begin([0, 1, 2, 3], ncalls, [4, 11, 0, 15])
-    sets, keep = [Out(r.b, 8), Out(r.b, 8, shift=7)], []
+    sets, keep = [file_bufs(r.b, 8), file_bufs(r.b, 8, shift=7)], []
     for c in range(3):
         counts = [8, 8, 0 if c == 1 else 8, 5]
         feed = lambda blk, counts, nf: keep.append(r.device_call(r.b, blk, counts, nf, submit=True, out=sets[c & 1])) and None
@@ -350,7 +183,7 @@ def test_host_files_calls_under_counts_and_segments(f32):
     ncalls = [2, 7, 12, 5]
     full = [synth.stream_pcm(7700 + i, nc, bursts=True) for i, nc in enumerate(ncalls)]
     full = [x.astype(np.float32) if f32 else x.astype(np.int16) for x in full]
-    r = Files(lambda: api().Batch(api().default_control(), nstreams=4, max_frames=8), full, 9000, f32=f32)
+    r = Files(lambda: api.Batch(api.default_control(), nstreams=4, max_frames=8), full, 9000, f32=f32)
     r.begin([0, 1, 2, 3], ncalls, [2, 0, 13, 8])
 
     def feed(blk, counts, nf):
@@ -378,8 +211,7 @@ def test_converting_host_files_call(multi):
     """hx_batch_encode_src_files_host - and hx_multi_encode_src_files_host over two blocks of device 0, whose images are
     seen through the fetch - with counts and frame_off against hx_batch_encode_src_counts_host with stats and crc on a twin:
     48 kHz 24-bit sources encoded at 44.1 kHz, files of 5, 9 and 14 converter calls"""
-    from test_gpu_src_batch import Stream, make_batch
-    A = api()
+    A = api
     streams = [Stream(48000, 24, 0, mpeg_select=44100, seed=95 + i, seconds=0.6) for i in range(3)]
     S, nf, ncalls, heads, cap = 3, 8, [5, 9, 14], [0, 7, 12], 12000
     t = make_batch(streams, nf)
@@ -433,7 +265,7 @@ def test_converting_host_files_call(multi):
 def test_multi_in_two_blocks_on_one_device(f32):
     """hx_multi_file_images / _ledger_poll / _file_fetch / _encode_{s16,f32}_host_files over two blocks of device 0 (5
     streams: uneven blocks) under hx_multi_frame_counts, against a one-batch twin's device calls"""
-    A = api()
+    A = api
     ncalls, heads = [3, 8, 13, 6, 2], [5, 0, 9, 14, 3]
     full = [synth.stream_pcm(7800 + i, nc, bursts=True).astype(np.float32 if f32 else np.int16) for i, nc in enumerate(ncalls)]
     ec = A.default_control()
@@ -459,19 +291,19 @@ def test_poll_teaches_the_host_which_records_ended():
     like a read it tells the host that a record has ended: a call that feeds only that slot, without counters and CRCs, is
     refused before the poll and taken after it"""
     import torch
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     ncalls = [1, 12]
     full = [synth.stream_pcm(7900 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     r = Files(lambda: A.Batch(A.default_control(), nstreams=2, max_frames=8), full, 9000)
     r.begin([0, 1], ncalls, [0, 0])
     r.step([8, 8], check=False)
     assert r.want[0].ended and not r.want[1].ended
-    o = Out(r.b, 8)
+    o = file_bufs(r.b, 8)
     o.set_on(r.b, stats=False, crc=False)
     r.b.frame_counts([8, 0])
     d_pcm = torch.zeros((2, 8 * 1152, 2), dtype=torch.float32, device=dev())
     sync()
-    call = lambda: L.hx_batch_encode_f32_device(r.b.h, d_pcm.data_ptr(), 8, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream())
+    call = lambda: L.hx_batch_encode_f32_device(r.b.h, d_pcm.data_ptr(), 8, o.ptr, o.stride, o.nb.data_ptr(), cur_stream())
     assert call() == -1 and "stream 0 has an open ledger record" in A.last_error()
     polls = r.b.ledger_poll()
     assert polls[0].ended == 1 and polls[1].ended == 0
@@ -479,10 +311,10 @@ def test_poll_teaches_the_host_which_records_ended():
     sync()
     assert r.t.ledger_read([0])[0].ended == 1
     # (the twin takes the same call, so that the two go on alike; slot 0's record is frozen but for call_bytes = 0)
-    o2 = Out(r.t, 8)
+    o2 = file_bufs(r.t, 8)
     o2.set_on(r.t, stats=False, crc=False)
     r.t.frame_counts([8, 0])
-    assert L.hx_batch_encode_f32_device(r.t.h, d_pcm.data_ptr(), 8, o2.rows.ptr, o2.rows.stride, o2.rows.nb.data_ptr(), cur_stream()) == 0
+    assert L.hx_batch_encode_f32_device(r.t.h, d_pcm.data_ptr(), 8, o2.ptr, o2.stride, o2.nb.data_ptr(), cur_stream()) == 0
     sync()
     r.want[0].call_bytes = 0
     r.given[0] += 8
@@ -496,7 +328,7 @@ def test_refusals_leave_the_batch_as_it_was():
     fetch into too small a dst; a misaligned d_out for poll_device: each -1 with a message, images, lengths and records
     unchanged, and the next well-formed call correct"""
     import torch
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     ncalls = [4, 11]
     full = [synth.stream_pcm(8000 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     blk = np.zeros((2, 8 * 1152 * 2), np.float32)
@@ -551,7 +383,7 @@ def test_refused_allocation_leaves_the_batch_usable():
     hx_batch_file_image_ptr unchanged - on a batch that has images and on one that has none - status 0, and the next
     hx_batch_ledger_begin and the calls behind it run and fill the images that stood; the same for hx_multi_file_images in
     two blocks of device 0, which then takes images that fit, a begin and a call"""
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     HUGE = 1 << 45
     ncalls = [4, 7]
     full = [synth.stream_pcm(8100 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]

@@ -14,9 +14,10 @@ import numpy as np
 import pytest
 
 import file_tag_cases as K
-from hmp3_amd import synth
-from test_gpu_dense import api, cur_stream, sync
-from test_gpu_file_images import PAT, Files, Out, hip, image_of, prefill, rows_block
+from file_image_cases import PAT, rows_block
+from file_image_support import Files, file_bufs, image_of, prefill
+from gpu_support import cur_stream, hip, sync
+from hmp3_amd import api, synth
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
 CAP = 112004            # slot LONG's file is about 99 000 bytes; not a multiple of 16: the pitch is larger
@@ -24,7 +25,7 @@ S = len(K.SLOTS)
 
 
 def heads():
-    return [K.slot_head(api(), s) for s in range(S)]
+    return [K.slot_head(api, s) for s in range(S)]
 
 
 def snapshot(b):
@@ -44,7 +45,7 @@ def tags_checked(b, idx, tags, head, what):
         h = head[s]
         assert (img1[s][h:] == img0[s][h:]).all(), "%s: slot %d: a byte at or beyond head_bytes %d changed" % (what, s, h)
         if s in idx:
-            want = api().file_tag_build(recs0[s], tags[idx.index(s)])
+            want = api.file_tag_build(recs0[s], tags[idx.index(s)])
             assert len(want) == h, "%s: slot %d: the host builds %d bytes for a head of %d" % (what, s, len(want), h)
             bad = np.flatnonzero(img1[s][:h] != np.frombuffer(want, np.uint8))
             assert not len(bad), "%s: slot %d: the head differs from hx_file_tag_build at byte %d of %d (%d differ)" % (what, s, bad[0], h, len(bad))
@@ -57,7 +58,7 @@ class Shape:
     """the seven-slot batch, run to the end; what was seen on the way"""
 
     def __init__(self):
-        A = api()
+        A = api
         self.head = heads()
         self.b = A.Batch.any([K.control_of(A, s) for s in range(S)], S, cfg=list(range(S)), max_frames=K.CALL)
         b = self.b
@@ -109,7 +110,7 @@ def test_tags_of_live_and_ended_records(shape):
     """mid-run (checked inside the run: Shape.mid_run) and after the end: each head equals hx_file_tag_build of the record read
     at that moment; the long file's table has halved, the CBR file below 64 kbit/s holds points but its frame no TOC, the
     untagged slot has no head and nothing written"""
-    A = api()
+    A = api
     assert shape.mid and len(shape.mid["live"]) >= 3
     assert all(r.ended for r in shape.recs) and shape.recs[K.LONG].every == 2 and shape.recs[K.LONG].npt >= 256
     assert shape.recs[K.COUNTS_ONLY].npt == 0 and shape.recs[K.NO_TOC_CBR].npt > 0 and shape.head[K.UNTAGGED] == 0
@@ -128,7 +129,7 @@ def test_parameter_grid_rebuilds_the_whole_head(shape):
     samprate / 2} - both sides of the trimming compare, the wrapped one included (tests/file_tag_cases.py), the LAME fields
     skipped for 0 - each call the whole head rebuilt: a head built with other parameters leaves no byte behind (the file
     with counts only has no LAME fields, but its frame count is trimmed all the same)"""
-    A = api()
+    A = api
     grids = [K.grid(A, s) for s in range(S)]
     seen = [set() for _ in range(S)]
     for g in range(len(grids[0])):
@@ -140,7 +141,7 @@ def test_parameter_grid_rebuilds_the_whole_head(shape):
 
 
 def test_one_slot_lists_and_the_all_slots_list_give_the_same_heads(shape):
-    A = api()
+    A = api
     every = tags_checked(shape.b, list(range(S)), shape.true_tags, shape.head, "all slots")
     other = [K.slot_tag(A, s, 1, 48000) for s in range(S)]
     scrambled = tags_checked(shape.b, list(range(S)), other, shape.head, "other parameters")
@@ -157,7 +158,7 @@ def test_refusals_leave_batch_and_images_as_they_were(shape):
     stream capture - on the shared batch, whose images, length words and records stay bit-identical; images off and a slot
     never begun (or begun before the images were switched on) on batches of their own"""
     import torch
-    A, L, b = api(), api().lib(), shape.b
+    A, L, b = api, api.lib(), shape.b
     img0, polls0, recs0 = snapshot(b)
     with pytest.raises(RuntimeError, match=r"entry 1: the tag frame takes \d+ bytes, slot 1's record was begun with head_bytes \d+"):
         b.file_tags([0, 1], [shape.true_tags[0], shape.true_tags[0]])
@@ -215,14 +216,14 @@ def test_refusals_leave_batch_and_images_as_they_were(shape):
 def test_behind_a_pipelined_submit_the_tag_reflects_that_submits_update():
     """two hx_batch_submit_f32_device calls, no wait, then hx_batch_file_tags on the same stream: the deferred packing - and
     the ledger update that travels with it - goes out first, so the head is the tag of the record behind both submits"""
-    A = api()
+    A = api
     ncalls = [30, 25]
     full = [synth.stream_pcm(9200 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     tags = [K.tag_of(A, A.default_control(), 2, 3, nc * 1152 - K.TAIL) for nc in ncalls]
     size = A.file_tag_bytes(tags[0])
     r = Files(lambda: A.Batch(A.default_control(), nstreams=2, max_frames=8), full, 20000)
     r.begin([0, 1], ncalls, [size, size])
-    sets, keep = [Out(r.b, 8), Out(r.b, 8, shift=7)], []
+    sets, keep = [file_bufs(r.b, 8), file_bufs(r.b, 8, shift=7)], []
     for c in range(2):
         feed = lambda blk, counts, nf: keep.append(r.device_call(r.b, blk, counts, nf, submit=True, out=sets[c & 1])) and None
         r.step([8, 8], nf=8, feed=feed, check=False)

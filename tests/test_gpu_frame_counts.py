@@ -6,29 +6,19 @@ the stream's frames into calls.  Every comparison is equality.  Before a call th
 0xA5 and the sizes, byte counts and counters with -1, so what a call does not write stays recognisable.  In a call's input
 the samples behind a stream's count are NaN (fp32) or full-scale garbage (int16): they must reach no output and no state."""
 import os
-import subprocess
-import wave
 
 import numpy as np
 import pytest
 
+import gpu_support as G
 import packet_cases as PC
 from conftest import skip_unless_host_libm_is_the_restated_one
-from hmp3_amd import synth
+from gpu_support import FILL, REF_CLI, CallBufs, Image, batch_vs_single_vs_reference, host_crc, oracle_bytes, sync, write_wav
+from hmp3_amd import api, synth
+from output_checks import check_crc, check_dense, check_idle_rows
+from src_cases import Stream, make_batch
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = 0xA5
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def host_crc(data):
-    data = bytes(data)
-    return int(api().lib().hx_xing_update_crc(0, data, len(data)))
 
 
 def make_pcm(seed, kws, F):
@@ -94,89 +84,18 @@ class Streams:
             assert b.frames_bytes(s) == self.counters(s, self.pos[s]), "stream %d: hx_batch_frames_bytes" % s
 
 
-class Outputs:
-    """every device output buffer of one call, prefilled"""
-
-    def __init__(self, b, nf, frame_stride=4096, dense=False):
-        import torch
-        dev = torch.device("cuda:0")
-        self.nf, self.frame_stride, self.stride = nf, frame_stride, b.out_stride(nf)
-        self.out = torch.empty((b.n, self.stride), dtype=torch.uint8, device=dev)
-        self.nb = torch.empty((b.n,), dtype=torch.int32, device=dev)
-        self.pk = torch.empty((b.n, nf, frame_stride), dtype=torch.uint8, device=dev)
-        self.pkb = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
-        self.st = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
-        self.crc = torch.empty((b.n, nf), dtype=torch.int16, device=dev)
-        self.dense = torch.empty((b.dense_bound(nf),), dtype=torch.uint8, device=dev) if dense else None
-        self.off = torch.empty((b.n + 1,), dtype=torch.int64, device=dev) if dense else None
-        self.prefill()
-
-    def prefill(self):
-        import torch
-        self.out.fill_(FILL)
-        self.pk.fill_(FILL)
-        for t in (self.nb, self.pkb, self.st, self.crc):
-            t.fill_(-1)
-        if self.dense is not None:
-            self.dense.fill_(FILL)
-            self.off.fill_(-1)
-        torch.cuda.synchronize()
-
-    def set_on(self, b, crc=False):
-        b.packet_buffers(self.pk.data_ptr(), self.frame_stride, self.pkb.data_ptr())
-        b.frame_stats_buffer(self.st.data_ptr())
-        b.crc_buffer(self.crc.data_ptr() if crc else None)
-        if self.dense is not None:
-            b.dense_buffers(self.dense.data_ptr(), self.dense.numel(), self.off.data_ptr())
-
-    def rows(self):
-        return self.out.cpu().numpy(), self.nb.cpu().numpy()
-
-    def bitstreams(self):
-        o, n = self.rows()
-        assert (n >= 0).all(), "a byte count was not written"
-        return [o[s, :n[s]].tobytes() for s in range(len(n))]
-
-    def host(self):
-        return self.pk.cpu().numpy(), self.pkb.cpu().numpy(), self.st.cpu().numpy()
-
-    def check_idle_rows(self, counts):
-        """a stream that takes no frame: byte count 0, and its row is not written"""
-        o, n = self.rows()
-        for s in range(len(n)):
-            if counts[s] == 0:
-                assert n[s] == 0 and (o[s] == FILL).all(), "stream %d took no frame and its row was written" % s
-
-    def check_crc(self):
-        """d_crc[s][f] = CRC of the row's first e[f] bytes, e[f] from the call's own counters (the header's formula)"""
-        o, n = self.rows()
-        st, crc = self.st.cpu().numpy(), self.crc.cpu().numpy().view(np.uint16)
-        for s in range(len(n)):
-            for f in range(self.nf):
-                e = int(n[s]) - ((int(st[s, -1, 1]) - int(st[s, f, 1])) & 0xFFFFFFFF)
-                assert 0 <= e <= n[s]
-                assert crc[s, f] == host_crc(o[s, :e]), "stream %d frame %d: CRC" % (s, f)
-
-    def check_dense(self):
-        o, n = self.rows()
-        off, img = self.off.cpu().numpy(), self.dense.cpu().numpy()
-        assert off[0] == 0 and (np.diff(off) == (n.astype(np.int64) + 15) // 16 * 16).all()
-        for s in range(len(n)):
-            assert img[off[s]:off[s] + n[s]].tobytes() == o[s, :n[s]].tobytes(), "stream %d: dense segment" % s
+def outputs(b, nf, frame_stride=4096, dense=False):
+    """every device output buffer of one call, prefilled: rows, packets and the dense image with 0xA5, byte counts, sizes,
+    counters, CRCs and offsets with -1"""
+    return CallBufs(b, nf, rows_fill=FILL, counters=True, crc=True, packets=frame_stride, image=Image(b.n, b.dense_bound(nf), guard=0) if dense else None)
 
 
 def device_call(b, st, counts, nf):
     """one plain fp32 device-buffer call under `counts` (None: no counts, every stream takes nf frames), with packet and counter
     buffers of its own"""
-    import torch
-    dtype = np.float32
-    o = Outputs(b, nf)
-    o.set_on(b)
     b.frame_counts(counts)
-    d_pcm = torch.from_numpy(st.block(counts if counts is not None else [nf] * st.S, nf, dtype)).to(torch.device("cuda:0"))
-    torch.cuda.synchronize()
-    b.encode_device(d_pcm.data_ptr(), nf, o.out.data_ptr(), o.stride, o.nb.data_ptr(), torch.cuda.current_stream().cuda_stream, f32=dtype == np.float32)
-    torch.cuda.synchronize()
+    o = G.device_call(b, st.block(counts if counts is not None else [nf] * st.S, nf, np.float32), nf, outputs(b, nf).set_on(b, crc=False))
+    sync()
     assert b.status() == 0
     return o
 
@@ -211,14 +130,14 @@ def test_uneven_calls_equal_each_streams_own_oracle(case):
     S, nf, F = 8, 8, 40
     kws = UNEVEN[case] if isinstance(UNEVEN[case], list) else [UNEVEN[case]] * S
     st = Streams(kws, make_pcm(8100, kws, F))
-    a = api()
+    a = api
     b = a.Batch([a.default_control(**kw) for kw in kws], max_frames=nf)
     c = 0
     while any(st.left(s) for s in range(S)):
         counts = [min(TABLE[c % len(TABLE)][s], st.left(s)) for s in range(S)]
         o = device_call(b, st, counts, nf)
-        st.check(counts, nf, o.bitstreams(), *o.host(), tag="call %d" % c)
-        o.check_idle_rows(counts)
+        st.check(counts, nf, o.bitstreams(), *o.packets(), tag="call %d" % c)
+        check_idle_rows(o, counts)
         c += 1
         assert c < 40
     assert all(p == F for p in st.pos)
@@ -232,10 +151,10 @@ def test_a_stream_that_takes_no_frames_keeps_its_state():
     (4 streams x 2 frames: packed by the one-workgroup form of k_pack)"""
     S, kw = 4, dict()
     st = Streams([kw] * S, make_pcm(8200, [kw] * S, 9))
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=3)
     o = device_call(b, st, [3] * S, 3)
-    st.check([3] * S, 3, o.bitstreams(), *o.host(), tag="uniform")
+    st.check([3] * S, 3, o.bitstreams(), *o.packets(), tag="uniform")
     before = [b.get_stream_state(s) for s in range(S)]
     counts = [0, 2, 0, 2]
     o = device_call(b, st, counts, 2)
@@ -246,10 +165,10 @@ def test_a_stream_that_takes_no_frames_keeps_its_state():
         assert nb[s] == 0 and (rows[s] == FILL).all(), "stream %d took no frame and its row was written" % s
     for s in (1, 3):
         assert after[s] != before[s]
-    st.check(counts, 2, o.bitstreams(), *o.host(), tag="counts")
+    st.check(counts, 2, o.bitstreams(), *o.packets(), tag="counts")
     for c, n in enumerate((2, 2)):
         o = device_call(b, st, None, n)
-        st.check([n] * S, n, o.bitstreams(), *o.host(), tag="uniform again %d" % c)
+        st.check([n] * S, n, o.bitstreams(), *o.packets(), tag="uniform again %d" % c)
     st.check_totals(b)
     b.close()
 
@@ -267,13 +186,13 @@ def test_mpeg2_and_first_generation_allocator_under_counts(kw):
     S, nf, F = 4, 5, 20
     table = [[0, 5, 2, 1], [2, 0, 5, 5], [5, 0, 1, 2], [1, 2, 0, 5], [5, 1, 5, 0]]
     st = Streams([kw] * S, make_pcm(8300, [kw] * S, F))
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=nf)
     c = 0
     while any(st.left(s) for s in range(S)):
         counts = [min(table[c % len(table)][s], st.left(s)) for s in range(S)]
         o = device_call(b, st, counts, nf)
-        st.check(counts, nf, o.bitstreams(), *o.host(), tag="call %d" % c)
+        st.check(counts, nf, o.bitstreams(), *o.packets(), tag="call %d" % c)
         c += 1
         assert c < 30
     st.check_totals(b)
@@ -291,9 +210,9 @@ def test_submits_take_the_counts_in_force_at_the_submit(host):
     st = Streams([kw] * S, make_pcm(8400, [kw] * S, 24))
     dev = torch.device("cuda:0")
     q = torch.cuda.current_stream().cuda_stream
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=nf)
-    outs = [Outputs(b, nf, dense=True) for _ in table]
+    outs = [outputs(b, nf, dense=True) for _ in table]
     pos, blks = [0] * S, []
     for counts in table:        # (the inputs up front: Streams.block cuts at the streams' positions)
         st.pos = list(pos)
@@ -313,7 +232,7 @@ def test_submits_take_the_counts_in_force_at_the_submit(host):
         if host:
             b.submit_host(ins[c].data_ptr(), nf, h_out[c].data_ptr(), outs[c].stride, h_nb[c].data_ptr(), f32=True)
         else:
-            b.submit_device(ins[c].data_ptr(), nf, outs[c].out.data_ptr(), outs[c].stride, outs[c].nb.data_ptr(), q, f32=True)
+            b.submit_device(ins[c].data_ptr(), nf, outs[c].ptr, outs[c].stride, outs[c].nb.data_ptr(), q, f32=True)
     b.frame_counts([nf] * S)     # reaches no submit already made
     if host:
         b.wait_host()
@@ -332,10 +251,10 @@ def test_submits_take_the_counts_in_force_at_the_submit(host):
             o.nb.copy_(h_nb[c])
         else:
             bs = o.bitstreams()
-            o.check_idle_rows(counts)
-        st.check(counts, nf, bs, *o.host(), tag="submit %d" % c)
-        o.check_crc()
-        o.check_dense()
+            check_idle_rows(o, counts)
+        st.check(counts, nf, bs, *o.packets(), tag="submit %d" % c)
+        check_crc(o)
+        check_dense(o)
     b.frame_counts(None)
     st.check_totals(b)
     b.close()
@@ -346,7 +265,7 @@ def test_host_calls_under_counts():
     included, is hx_xing_update_crc over the row's first e[f] bytes; a stream that takes nothing has an empty dense segment"""
     S, nf, kw = 5, 6, dict(vbr_mnr=60)
     st = Streams([kw] * S, make_pcm(8500, [kw] * S, 18))
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=nf)
     for c, counts in enumerate([[6, 0, 3, 1, 5], [2, 0, 6, 0, 4]]):
         b.frame_counts(counts)
@@ -380,11 +299,6 @@ def test_host_calls_under_counts():
     b.close()
 
 
-def oracle_bytes(kw, pcm, nfr):
-    enc = PC.O.OracleEncoder(PC.O.default_control(**kw))
-    return b"".join(enc.encode_s16(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr))
-
-
 def uneven_host_calls(b, pcm, counts_of_call, nf):
     """int16 host calls under counts_of_call(c, durations of the previous call) -> (each stream's bytes, its frames)"""
     S = len(pcm)
@@ -413,7 +327,7 @@ def test_persistent_workgroups_under_counts(monkeypatch):
     kw, S, nf = dict(), 1600, 3
     base = [synth.stream_pcm(8600 + u, 6, rho=PC.RHOS[u % 4], bursts=True) for u in range(50)]
     pcm = np.stack([np.roll(base[i % 50], 1152 * (i // 50), axis=0) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=nf)
     assert b.k6_variant() == 1 and b.resident_streams() < S
     got, pos = uneven_host_calls(b, pcm, lambda c: [(s + c) % 4 for s in range(S)], nf)
     b.close()
@@ -436,7 +350,7 @@ def test_parked_workgroups_wake_when_a_straggler_takes_no_frames(monkeypatch):
     kw, S, nf = dict(), 300, 3
     base = [synth.stream_pcm(8700 + u, 9, rho=PC.RHOS[u % 4], bursts=True) for u in range(30)]
     pcm = np.stack([np.roll(base[i % 30], 1152 * (i // 30), axis=0) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=nf)
     assert b.k6_variant() == 0 and b.resident_streams() >= S
     idle = []
 
@@ -462,34 +376,33 @@ def test_refusals_leave_the_batch_usable():
     import torch
     S, nf, kw = 3, 2, dict(bitrate=64)
     st = Streams([kw] * S, make_pcm(8800, [kw] * S, 6))
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=nf)
-    o = Outputs(b, nf)
-    o.set_on(b)
+    o = outputs(b, nf)
+    o.set_on(b, crc=False)
     d_pcm = torch.from_numpy(st.block([nf] * S, nf)).to(torch.device("cuda:0"))
     q = torch.cuda.current_stream().cuda_stream
     for bad, who in (([2, -1, 2], "stream 1"), ([2, 2, nf + 1], "stream 2")):
         b.frame_counts(bad)
         for call in (b.encode_device, b.submit_device):
             with pytest.raises(RuntimeError, match=who):
-                call(d_pcm.data_ptr(), nf, o.out.data_ptr(), o.stride, o.nb.data_ptr(), q, f32=True)
+                call(d_pcm.data_ptr(), nf, o.ptr, o.stride, o.nb.data_ptr(), q, f32=True)
         with pytest.raises(RuntimeError, match=who):
             b.encode_host(st.block([nf] * S, nf))
         torch.cuda.synchronize()
         rows, nb = o.rows()
-        pk, pkb, stats = o.host()
+        pk, pkb, stats = o.packets()
         assert (rows == FILL).all() and (nb == -1).all() and (pk == FILL).all() and (pkb == -1).all() and (stats == -1).all()
     with pytest.raises(ValueError):
         b.frame_counts([1, 1])
     counts = [1, 0, 2]
     o = device_call(b, st, counts, nf)
-    st.check(counts, nf, o.bitstreams(), *o.host(), tag="valid call")
+    st.check(counts, nf, o.bitstreams(), *o.packets(), tag="valid call")
     o = device_call(b, st, None, nf)
-    st.check([nf] * S, nf, o.bitstreams(), *o.host(), tag="uniform call")
+    st.check([nf] * S, nf, o.bitstreams(), *o.packets(), tag="uniform call")
     bs = b.encode_host(st.block([1] * S, 1))
     st.check([1] * S, 1, bs, tag="uniform host call")
     b.close()
-    from test_gpu_src_batch import Stream, make_batch
     cb = make_batch([Stream(48000, 24, 0, mpeg_select=44100, seed=71), Stream(32000, 32, 1, mpeg_select=44100, seed=72)], 4)
     with pytest.raises(RuntimeError, match="converting batch"):
         cb.frame_counts([1, 1])
@@ -498,17 +411,17 @@ def test_refusals_leave_the_batch_usable():
 
 def multi_call(m, blk, nf, rows=None, nb=None, stats=None):
     """hx_multi_encode_f32_host_stats into the caller's own (prefilled) arrays -> its return value"""
-    return int(api().lib().hx_multi_encode_f32_host_stats(m.h, blk.ctypes.data, nf, rows.ctypes.data, rows.shape[1], nb.ctypes.data, stats.ctypes.data))
+    return int(api.lib().hx_multi_encode_f32_host_stats(m.h, blk.ctypes.data, nf, rows.ctypes.data, rows.shape[1], nb.ctypes.data, stats.ctypes.data))
 
 
 def multi_states(m):
     """the checkpoint of every stream, through the blocks' batches"""
-    L = api().lib()
+    L = api.lib()
     blobs = []
     for k in range(m.ndevices()):
         h, (_, first, count) = L.hx_multi_batch(m.h, k), m.shard(k)
         for i in range(count):
-            buf = (api().C.c_ubyte * int(L.hx_batch_stream_state_bytes(h)))()
+            buf = (api.C.c_ubyte * int(L.hx_batch_stream_state_bytes(h)))()
             assert L.hx_batch_get_stream_state(h, i, buf) == 0
             blobs.append(bytes(buf))
     return blobs
@@ -516,7 +429,7 @@ def multi_states(m):
 
 def test_multi_frame_counts_over_two_blocks():
     """hx_multi_frame_counts: 5 streams in two blocks (3 + 2) on device 0, the counts fanned out to the blocks' batches"""
-    a = api()
+    a = api
     kws = [dict(bitrate=64), dict(vbr_mnr=60), dict(bitrate=96, short_block_threshold=99999), dict(bitrate=64), dict(vbr_mnr=60)]
     S, nf = 5, 4
     st = Streams(kws, make_pcm(8900, kws, 10))
@@ -539,7 +452,7 @@ def test_multi_call_refused_for_one_block_moves_no_stream_of_the_other(bad):
     refused for all five streams before a block starts - the message names the stream by its number over all blocks, every
     checkpoint is the same bytes as before, the prefilled rows, byte counts and counters are untouched, and the next valid call
     continues every stream where the oracle stands"""
-    a = api()
+    a = api
     kws = [dict(bitrate=64), dict(vbr_mnr=60), dict(bitrate=96, short_block_threshold=99999), dict(bitrate=64), dict(vbr_mnr=60)]
     S, nf = 5, 4
     st = Streams(kws, make_pcm(8950, kws, 9))
@@ -565,46 +478,28 @@ def test_multi_call_refused_for_one_block_moves_no_stream_of_the_other(bad):
     m.close()
 
 
-def cli_batch_run(tmp_path):
-    """`hmp3amd -batch` on three 44.1 kHz int16 WAVs of 5, 40 and 130 frames: the first two files end inside the first call of
-    96 frames, and every call gives a file only the frames it still needs -> [(wav, the batch run's mp3 bytes)]"""
-    exe = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-    assert os.path.exists(exe), "hmp3_amd/build.sh builds the CLI"
-    args, files = [], []
+def cli_files(tmp_path):
+    """three 44.1 kHz int16 WAVs of 5, 40 and 130 frames for one `hmp3amd -batch` run: the first two files end inside the first
+    call of 96 frames, and every call gives a file only the frames it still needs -> [(label, wav, mp3)]"""
+    files = []
     for i, frames in enumerate((5, 40, 130)):
         wav, mp3 = str(tmp_path / ("in%d.wav" % i)), str(tmp_path / ("batch%d.mp3" % i))
-        with wave.open(wav, "wb") as w:
-            w.setnchannels(2)
-            w.setsampwidth(2)
-            w.setframerate(44100)
-            w.writeframes(np.ascontiguousarray(synth.stream_pcm(9300 + i, frames, bursts=True)[:frames * 1152 - 211 * i], dtype="<i2").tobytes())
-        args += [wav, mp3]
-        files.append((wav, mp3))
-    r = subprocess.run([exe, "-batch"] + args, capture_output=True, timeout=120)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
-    return [(wav, open(mp3, "rb").read()) for wav, mp3 in files]
+        write_wav(wav, synth.stream_pcm(9300 + i, frames, bursts=True)[:frames * 1152 - 211 * i], 44100, False)
+        files.append((wav, wav, mp3))
+    return files
 
 
 @pytest.mark.one_k6_build
 def test_cli_batch_of_files_of_different_lengths_equals_the_single_file_runs(tmp_path):
     """files, tags, TOC and MusicCRC byte for byte what `hmp3amd in.wav out.mp3` writes for each file alone"""
-    exe = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-    for i, (wav, data) in enumerate(cli_batch_run(tmp_path)):
-        single = str(tmp_path / ("single%d.mp3" % i))
-        r = subprocess.run([exe, wav, single], capture_output=True, timeout=120)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
-        assert len(data) > 1000 and data == open(single, "rb").read(), wav
+    batch_vs_single_vs_reference(cli_files(tmp_path), floor=1000, reference=False)
 
 
 @pytest.mark.one_k6_build
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "hmp3")), reason="oracle/_ref/hmp3 (the reference's CLI, prebuilt) not present")
+@pytest.mark.skipif(not os.path.exists(REF_CLI), reason="oracle/_ref/hmp3 (the reference's CLI, prebuilt) not present")
 def test_cli_batch_of_files_of_different_lengths_equals_the_reference_binary(tmp_path):
     """... and what the reference's own command line writes for each file"""
-    ref = os.path.join(ROOT, "oracle", "_ref", "hmp3")
-    for i, (wav, data) in enumerate(cli_batch_run(tmp_path)):
-        out = str(tmp_path / ("ref%d.mp3" % i))
-        subprocess.run([ref, wav, out], capture_output=True, timeout=120)
-        assert data == open(out, "rb").read(), wav
+    batch_vs_single_vs_reference(cli_files(tmp_path), single=False)
 
 
 RANDOM_CASES = list(range(10))
@@ -619,11 +514,11 @@ def test_fixed_seed_random_slice(case):
     calls = [[int(rng.integers(0, nf + 1)) for _ in range(S)] for _ in range(4)]
     F = max(sum(c[s] for c in calls) for s in range(S))
     st = Streams([kw] * S, make_pcm(9100 + case, [kw] * S, max(F, 1)))
-    a = api()
+    a = api
     b = a.Batch(a.default_control(**kw), nstreams=S, max_frames=nf)
     for c, counts in enumerate(calls):
         o = device_call(b, st, counts, nf)
-        st.check(counts, nf, o.bitstreams(), *o.host(), tag="case %d (%s, S %d, nframes %d) call %d" % (case, PC.case_id(kw), S, nf, c))
-        o.check_idle_rows(counts)
+        st.check(counts, nf, o.bitstreams(), *o.packets(), tag="case %d (%s, S %d, nframes %d) call %d" % (case, PC.case_id(kw), S, nf, c))
+        check_idle_rows(o, counts)
     st.check_totals(b)
     b.close()

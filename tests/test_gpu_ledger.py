@@ -10,59 +10,24 @@ counters and CRCs.  The ledger does not depend on the build of the rate-loop ker
 hx_xing keeps 512 seek points, so its table is first halved at the 512th sampled call and again at the 1024th: the
 seek-point test runs files of 1030 calls."""
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 import pytest
 
-from hmp3_amd import synth
-from test_gpu_dense import Rows, api, cur_stream, dev, sync
-import test_ledger_host as H
+import ledger_cases as H
+from gpu_support import CallBufs, cur_stream, dev, run_cli, sync, write_wav
+from hmp3_amd import api, synth
+from ledger_cases import DRAIN, NEVER, RESTART, SITS_OUT, SMALL_NCALLS, block, small_batch, small_counts, small_pcm, small_restart_pcm
+from output_checks import same_outputs
+from src_cases import Stream, make_batch
 
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-DRAIN = 32              # frames of silence a file may take behind its input
 
 
-class Bufs:
+def ledger_bufs(b, nf, odd=False):
     """every output buffer of one device call: rows, byte counts, frame counters (odd: starting 4 bytes past an 8-byte
     boundary), per-frame CRCs"""
-
-    def __init__(self, b, nf, odd=False):
-        import torch
-        self.S, self.nf = b.n, nf
-        self.rows = Rows(b, nf)
-        self.stats = torch.full((self.S * nf * 2 + 2,), -1, dtype=torch.int32, device=dev())[2 - int(odd):][:self.S * nf * 2].view(self.S, nf, 2)
-        assert self.stats.data_ptr() % 8 == 4 * int(odd)
-        self.crc = torch.full((self.S * nf,), -1, dtype=torch.int16, device=dev())
-
-    def set_on(self, b, stats=True, crc=True):
-        b.frame_stats_buffer(self.stats.data_ptr() if stats else None)
-        b.crc_buffer(self.crc.data_ptr() if crc else None)
-
-    def host(self):
-        rows, nb = self.rows.host()
-        return rows, nb, self.stats.cpu().numpy(), self.crc.cpu().numpy().view(np.uint16).reshape(self.S, self.nf)
-
-
-def block(full, given, counts, nf):
-    """the call's PCM [S, nf * 1152, ch]: stream s's next counts[s] frames of full[s], silence behind its end"""
-    ch = full[0].shape[1]
-    blk = np.zeros((len(full), nf * 1152, ch), np.float32)
-    for s, n in enumerate(counts):
-        part = full[s][given[s] * 1152:(given[s] + n) * 1152]
-        blk[s, :len(part)] = part
-    return blk
-
-
-def same_outputs(a, b, counts, tag):
-    """rows (their used part), byte counts, counters and CRCs of two calls' buffers are identical"""
-    (rows, nb, st, cr), (trows, tnb, tst, tcr) = a, b
-    assert nb.tolist() == tnb.tolist() and (st == tst).all() and (cr == tcr).all(), tag + ": byte counts / counters / CRCs differ from the twin batch's"
-    for s in range(len(nb)):
-        if counts[s]:
-            assert rows[s, :nb[s]].tobytes() == trows[s, :nb[s]].tobytes(), "%s: row %d differs from the twin batch's" % (tag, s)
+    return CallBufs(b, nf, counters=True, odd=odd, crc=True)
 
 
 class Run:
@@ -71,7 +36,7 @@ class Run:
     def __init__(self, make, full, odd=False):
         self.b, self.t, self.full, self.odd = make(), make(), full, odd
         self.S = self.b.n
-        self.want = [api().Ledger() for _ in range(self.S)]
+        self.want = [api.Ledger() for _ in range(self.S)]
         self.given = [0] * self.S
         self.ends, self.frozen, self.calls = [], 0, 0
 
@@ -79,13 +44,13 @@ class Run:
         self.b.ledger_begin(idx, ncalls, head_bytes, flags, stream=cur_stream())
         per_slot = [[v] * len(idx) if np.isscalar(v) else list(v) for v in (ncalls, head_bytes, flags)]
         for e, s in enumerate(idx):
-            self.want[s] = api().ledger_open(per_slot[0][e], fpc, per_slot[1][e], per_slot[2][e])
+            self.want[s] = api.ledger_open(per_slot[0][e], fpc, per_slot[1][e], per_slot[2][e])
 
     def host_update(self, counts, nb, st, cr):
         for s, n in enumerate(counts):
             was_live = self.want[s].open and not self.want[s].ended
             self.frozen += bool(self.want[s].ended and n > 0)
-            if api().ledger_update(self.want[s], st[s, :n], cr[s, :n], nb[s]):
+            if api.ledger_update(self.want[s], st[s, :n], cr[s, :n], nb[s]):
                 self.ends.append((self.want[s].fed - 1 - self.given[s], n))
             assert not (was_live and n > 0 and self.want[s].call_bytes > nb[s])
             self.given[s] += n
@@ -108,10 +73,10 @@ class Run:
         sync()
         outs = []
         for h in (self.b, self.t):
-            o = Bufs(h, nf, self.odd)
+            o = ledger_bufs(h, nf, self.odd)
             o.set_on(h)
             h.frame_counts(counts)
-            h.encode_device(d_pcm.data_ptr(), nf, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=True)
+            h.encode_device(d_pcm.data_ptr(), nf, o.ptr, o.stride, o.nb.data_ptr(), cur_stream(), f32=True)
             outs.append(o)
         sync()
         got, twin = outs[0].host(), outs[1].host()
@@ -126,28 +91,6 @@ class Run:
         assert self.b.status() == 0 and self.t.status() == 0
         self.b.close()
         self.t.close()
-
-
-# ---- the small shape: files of 1 .. 20 calls in calls of 8 frames ----
-# slots 0 - 5: the files; slot 6: a file of 15 calls, whose drain ends on the first frame of a call (the others' ends include
-# one on the last frame of a call); slot 7 is never begun; slot 8 is begun and sits call 1 out
-SMALL_NCALLS = [1, 7, 8, 9, 16, 20, 15, 5, 12]
-NEVER, SITS_OUT, RESTART = 7, 8, 1
-
-
-def small_pcm():
-    return [synth.stream_pcm(6100 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(SMALL_NCALLS)]
-
-
-def small_batch():
-    return api().Batch(api().default_control(bitrate=64), nstreams=len(SMALL_NCALLS), max_frames=8)
-
-
-def small_counts(given, ncalls, call):
-    c = [max(0, min(8, nc + DRAIN - g)) for nc, g in zip(ncalls, given)]
-    if call == 1:
-        c[SITS_OUT] = 0
-    return c
 
 
 def test_small_shape_every_kind_of_end():
@@ -170,7 +113,7 @@ def test_small_shape_every_kind_of_end():
             rec = r.want[SITS_OUT]
             assert r.records()[SITS_OUT] == before and rec.open and not rec.ended and rec.fed == 8
     final = r.records()
-    assert final[NEVER] == bytes(C.sizeof(api().Ledger))
+    assert final[NEVER] == bytes(C.sizeof(api.Ledger))
     assert all(r.want[s].ended for s in begun)
     assert [r.want[s].call_bytes for s in begun] == [0] * len(begun) and r.frozen >= len(begun)
     assert any(f == 0 for f, n in r.ends), "no file's drain ended on the first frame of a call: %s" % r.ends
@@ -186,10 +129,10 @@ def test_seek_points_through_two_halvings():
     S, nf, ncalls = 4, 64, 1030
     base = synth.stream_pcm(6200, ncalls, bursts=True).astype(np.float32)
     full = [np.roll(base, 1152 * 7 * s, axis=0) * (1.0, 0.5, 0.25, 0.8)[s] for s in range(S)]
-    r = Run(lambda: api().Batch(api().default_control(), nstreams=S, max_frames=nf), full)
-    x = api().lib().hx_xing_create()
+    r = Run(lambda: api.Batch(api.default_control(), nstreams=S, max_frames=nf), full)
+    x = api.lib().hx_xing_create()
     _, head = H.tag_frame(x, 1)
-    api().lib().hx_xing_destroy(x)
+    api.lib().hx_xing_destroy(x)
     r.begin(list(range(S)), ncalls, head_bytes=head, flags=1)
     hist = [[] for _ in range(S)]
     data = [b""] * S
@@ -211,7 +154,7 @@ def test_seek_points_through_two_halvings():
         f.fr, f.by = st[:, 0].astype(np.int64), st[:, 1].astype(np.int64)
         f.end = rec.fed - 1
         f.data = np.frombuffer(data[s], np.uint8)
-        f.crc_of = lambda a, b, d=f.data: int(api().lib().hx_xing_update_crc(0, d[a:b].tobytes(), b - a))
+        f.crc_of = lambda a, b, d=f.data: int(api.lib().hx_xing_update_crc(0, d[a:b].tobytes(), b - a))
         tag, frames, nbytes, crc, halvings, n = H.replay(f)
         assert halvings == 2 and n == head
         got = r.b.ledger_read([s])[0]
@@ -224,10 +167,7 @@ def test_files_equal_the_single_file_loops(tmp_path):
     """three WAVs, 44.1 kHz 16-bit, of 5, 40 and 130 frames with -X2 through a batch with the ledger: tag frame from the
     record + the call_bytes of every call + hx_xing_update_info equals, byte for byte, what `hmp3amd in.wav out.mp3 -X2`
     writes for the file"""
-    from test_gpu_crc import write_wav
-    A, L = api(), api().lib()
-    exe = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-    assert os.path.exists(exe), "hmp3_amd/build.sh builds the CLI"
+    A, L = api, api.lib()
     frames = (5, 40, 130)
     S, CH = len(frames), 48
     ec, used, head = A.default_control(samprate=44100), A.EControl(), A.MpegHead()
@@ -236,7 +176,7 @@ def test_files_equal_the_single_file_loops(tmp_path):
     for i, nfr in enumerate(frames):
         pcm = synth.stream_pcm(6300 + i, nfr, bursts=True)[:nfr * 1152 - 311 * i]
         wavs.append(str(tmp_path / ("in%d.wav" % i)))
-        write_wav(wavs[-1], pcm, 44100)
+        write_wav(wavs[-1], pcm, 44100, False)
         # the single-file loop's calls: one per 1152 sample frames while 1153 are left of audio ++ 4 x 1153 frames of zeros
         size = len(pcm) * 4 + 4 * 1153 * 4
         ncalls.append((size - 1153 * 4) // 4608 + 1)
@@ -270,8 +210,7 @@ def test_files_equal_the_single_file_loops(tmp_path):
         assert L.hx_xing_update_info(x, rec.frames, n + rec.bytes, vbr_scale, None, buf, None, None, samples[s], n + rec.bytes, used.freq_limit,
                                      44100, used.samprate, rec.crc) == 1
         out = str(tmp_path / ("single%d.mp3" % s))
-        p = subprocess.run([exe, wavs[s], out, "-X2"], capture_output=True)
-        assert p.returncode == 0, p.stderr.decode()[-400:]
+        run_cli([wavs[s], out, "-X2"])
         assert bytes(buf[:n]) + audio[s] == open(out, "rb").read(), "file %d (%d frames)" % (s, frames[s])
     L.hx_xing_destroy(x)
 
@@ -293,7 +232,7 @@ def test_mpeg2_batch():
     """22.05 kHz: two frames per call, the drain ends when the frame counter reaches 2 x ncalls"""
     ncalls = [3, 10, 17]
     full = [synth.stream_pcm(6400 + i, nc, sr=22050, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
-    r = Run(lambda: api().Batch(api().default_control(samprate=22050), nstreams=3, max_frames=8), full)
+    r = Run(lambda: api.Batch(api.default_control(samprate=22050), nstreams=3, max_frames=8), full)
     run_files(r, ncalls, 8, fpc=2)
     assert all(w.frames_per_call == 2 and w.frames >= 2 * nc for w, nc in zip(r.want, ncalls))
 
@@ -302,14 +241,13 @@ def test_mono_batch():
     """... with the frame-counter buffers 4 bytes past an 8-byte boundary: k_ledger reads the pairs in halves"""
     ncalls = [2, 9, 16, 21]
     full = [synth.stream_pcm(6500 + i, nc, bursts=True)[:, :1].astype(np.float32) for i, nc in enumerate(ncalls)]
-    run_files(Run(lambda: api().Batch(api().default_control(mode=3), nstreams=4, max_frames=16), full, odd=True), ncalls, 16)
+    run_files(Run(lambda: api.Batch(api.default_control(mode=3), nstreams=4, max_frames=16), full, odd=True), ncalls, 16)
 
 
 def test_converting_batch_through_the_host_call():
     """48 kHz 24-bit sources encoded at 44.1 kHz through hx_batch_encode_src_counts_host with stats and crc: files of 5, 9 and
     14 converter calls, whose drain calls read a region of zero bytes through frame_off"""
-    from test_gpu_src_batch import Stream, make_batch
-    A = api()
+    A = api
     streams = [Stream(48000, 24, 0, mpeg_select=44100, seed=95 + i, seconds=0.6) for i in range(3)]
     S, nf, ncalls = 3, 8, [5, 9, 14]
     b, t = make_batch(streams, nf), make_batch(streams, nf)
@@ -348,7 +286,7 @@ def test_converting_batch_through_the_host_call():
 def test_multi_on_one_device():
     """hx_multi_ledger_begin / _read over three blocks of device 0 (4 streams: uneven blocks), host calls with stats and crc
     under hx_multi_frame_counts; a slot listed twice or out of range is refused for all blocks"""
-    A = api()
+    A = api
     ncalls, nf = [3, 8, 13, 6], 8
     full = [synth.stream_pcm(6600 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     ec = A.default_control(bitrate=64)
@@ -382,10 +320,6 @@ def test_multi_on_one_device():
     assert all(w.ended for w in want) and m.status() == 0 and t.status() == 0
     m.close()
     t.close()
-
-
-def small_restart_pcm():
-    return synth.stream_pcm(6190, 6, bursts=True).astype(np.float32)
 
 
 def small_plain_with_restart():
@@ -422,7 +356,7 @@ def test_pipelined_submits_advance_the_records_in_call_order():
     begun = [s for s in range(b.n) if s != NEVER]
     ncalls, given = list(SMALL_NCALLS), [0] * b.n
     b.ledger_begin(begun, [ncalls[s] for s in begun], stream=cur_stream())
-    sets, keep, call = [Bufs(b, 8), Bufs(b, 8)], [], 0
+    sets, keep, call = [ledger_bufs(b, 8), ledger_bufs(b, 8)], [], 0
     while True:
         if call == 3:
             b.ledger_begin([RESTART], 6, stream=cur_stream())
@@ -436,7 +370,7 @@ def test_pipelined_submits_advance_the_records_in_call_order():
         o = sets[call & 1]
         o.set_on(b)
         b.frame_counts(counts)
-        b.submit_device(keep[-1].data_ptr(), 8, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=True)
+        b.submit_device(keep[-1].data_ptr(), 8, o.ptr, o.stride, o.nb.data_ptr(), cur_stream(), f32=True)
         given = [g + c for g, c in zip(given, counts)]
         call += 1
     b.wait(cur_stream())
@@ -454,26 +388,26 @@ def test_refusals_leave_batch_and_records_as_they_were():
     call correct.  A call that feeds no live record needs neither buffer, and a batch that never began a ledger takes calls
     without counters as before"""
     import torch
-    A, L = api(), api().lib()
+    A, L = api, api.lib()
     ncalls = [4, 11, 6]
     full = [synth.stream_pcm(6700 + i, nc, bursts=True).astype(np.float32) for i, nc in enumerate(ncalls)]
     r = Run(lambda: A.Batch(A.default_control(bitrate=64), nstreams=3, max_frames=8), full)
-    o = Bufs(r.t, 8)
+    o = ledger_bufs(r.t, 8)
     d_pcm = torch.from_numpy(block(full, [0] * 3, [8] * 3, 8)).to(dev())
     sync()
     o.set_on(r.t, stats=False, crc=False)       # (the twin never begins a ledger: no counters needed)
-    r.t.encode_device(d_pcm.data_ptr(), 8, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=True)
+    r.t.encode_device(d_pcm.data_ptr(), 8, o.ptr, o.stride, o.nb.data_ptr(), cur_stream(), f32=True)
     sync()
     r.t.reset_streams([0, 1, 2], stream=cur_stream())
     r.begin([0, 1], ncalls[:2])
     r.step([8, 8, 8])
     before = r.records()
-    o = Bufs(r.b, 8)
+    o = ledger_bufs(r.b, 8)
     for stats, crc in ((True, False), (False, False)):
         o.set_on(r.b, stats, crc)
         r.b.frame_counts(None)
         for fn in (L.hx_batch_encode_f32_device, L.hx_batch_submit_f32_device):
-            assert fn(r.b.h, d_pcm.data_ptr(), 8, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream()) == -1
+            assert fn(r.b.h, d_pcm.data_ptr(), 8, o.ptr, o.stride, o.nb.data_ptr(), cur_stream()) == -1
             assert "ledger record" in A.last_error() and "stream 1" in A.last_error()
     blk = np.zeros((3, 8 * 1152, 2), np.float32)
     out, nb = np.zeros((3, r.b.out_stride(8)), np.uint8), np.zeros(3, np.int32)
@@ -490,7 +424,7 @@ def test_refusals_leave_batch_and_records_as_they_were():
     with pytest.raises(RuntimeError, match="listed twice"):
         r.b.ledger_read([1, 1])
     sync()
-    assert r.b.status() == 0 and (o.rows.host()[1] == -1).all() and r.records() == before
+    assert r.b.status() == 0 and (o.rows()[1] == -1).all() and r.records() == before
     r.b.ledger_read_device([2, 0, 1], base, stream=cur_stream())
     sync()
     img = d_out.cpu().numpy()[base - d_out.data_ptr():][:3 * C.sizeof(A.Ledger)].tobytes()
@@ -499,12 +433,12 @@ def test_refusals_leave_batch_and_records_as_they_were():
     assert r.want[0].ended and not r.want[1].ended
     o.set_on(r.b, False, False)
     r.b.frame_counts([8, 0, 8])
-    r.b.encode_device(d_pcm.data_ptr(), 8, o.rows.ptr, o.rows.stride, o.rows.nb.data_ptr(), cur_stream(), f32=True)
+    r.b.encode_device(d_pcm.data_ptr(), 8, o.ptr, o.stride, o.nb.data_ptr(), cur_stream(), f32=True)
     sync()
-    o2 = Bufs(r.t, 8)
+    o2 = ledger_bufs(r.t, 8)
     o2.set_on(r.t, False, False)
     r.t.frame_counts([8, 0, 8])
-    r.t.encode_device(d_pcm.data_ptr(), 8, o2.rows.ptr, o2.rows.stride, o2.rows.nb.data_ptr(), cur_stream(), f32=True)
+    r.t.encode_device(d_pcm.data_ptr(), 8, o2.ptr, o2.stride, o2.nb.data_ptr(), cur_stream(), f32=True)
     sync()
     after = r.records()
     frozen = A.Ledger.from_buffer_copy(before[0])

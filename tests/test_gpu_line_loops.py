@@ -13,37 +13,14 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_support import ROOT
+from hmp3_amd import api
+from line_loop_cases import BATCHES, F, STREAMS, batch_pcm, encode_two_calls
 from oracle import oracle as O
-from hmp3_amd import synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-F, CALL = 24, 12                                            # frames per stream, given as two calls of 12
-STREAMS = [(seed, rho) for seed in (0, 1, 2) for rho in (0.7, 1.0)]
-BASE = dict(bitrate=64, short_block_threshold=99999)        # CBR-128, long blocks
-BATCHES = {
-    "44k": dict(BASE),
-    "48k": dict(BASE, samprate=48000),
-    "32k": dict(BASE, samprate=32000),
-    "lsf_22k": dict(BASE, samprate=22050),
-    "lsf_24k": dict(BASE, samprate=24000),
-    "lsf_16k": dict(BASE, samprate=16000),
-    "44k_freq8000": dict(BASE, freq_limit=8000),
-    "48k_nsb4": dict(BASE, samprate=48000, nsb_limit=4),
-}
 MPEG1_RATES = ("44k", "48k", "32k")
 STAT_INCREASE, STAT_DECREASE = 1, 4                         # hxo_rate_stats: granules that entered increase_bits / decrease_bits
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def batch_pcm(kw, mono=False):
-    sr = kw.get("samprate", 44100)
-    pcm = np.stack([synth.stream_pcm(seed, F, sr, rho) for seed, rho in STREAMS])
-    return np.ascontiguousarray(pcm[:1, :, 0]) if mono else pcm
 
 
 @functools.lru_cache(maxsize=None)
@@ -63,17 +40,8 @@ def reference(name, mono=False):
 
 def run_width(kw):
     w = np.zeros(1, np.int32)
-    assert api().lib().hx_debug_host_table(C.byref(api().default_control(**kw)), b"run_w", w.ctypes.data, 4) == 4
+    assert api.lib().hx_debug_host_table(C.byref(api.default_control(**kw)), b"run_w", w.ctypes.data, 4) == 4
     return int(w[0])
-
-
-def encode_two_calls(kw, pcm):
-    b = api().Batch(api().default_control(**kw), nstreams=pcm.shape[0], max_frames=CALL)
-    got = b.encode_host(pcm[:, :CALL * 1152])
-    got2 = b.encode_host(pcm[:, CALL * 1152:])
-    assert b.status() == 0
-    b.close()
-    return [got[s] + got2[s] for s in range(pcm.shape[0])]
 
 
 def test_the_batches_cover_the_run_widths_the_host_produces():
@@ -111,7 +79,7 @@ def test_line_loops_lsf_byte_identical_to_oracle(name):
 CHILD = """
 import sys
 sys.path.insert(0, %r); sys.path.insert(0, %r)
-import test_gpu_line_loops as T
+import line_loop_cases as T
 got = T.encode_two_calls(T.BATCHES["44k"], T.batch_pcm(T.BATCHES["44k"]))
 sys.stdout.buffer.write(b"".join(len(g).to_bytes(4, "little") + g for g in got))
 """

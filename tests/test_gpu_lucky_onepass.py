@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from hmp3_amd import synth
+from hmp3_amd import api, synth
 
 # (k_alloc / k_alloc_lsf only: the low-footprint build keeps its six candidates per pass and does not count)
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
@@ -27,11 +27,6 @@ CASES = {
     "48k_vbr_hf": dict(samprate=48000, vbr_mnr=100, hf_flag=3, freq_limit=19000, short_block_threshold=99999),
     "48k_nsb4": dict(BASE, samprate=48000, nsb_limit=4),
 }
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 @functools.lru_cache(maxsize=None)
@@ -50,7 +45,7 @@ def reference(name):
 
 def encode(kw, pcm):
     """the batch in two calls on the 256-register build; (bytes per stream, the big_lucky counters)"""
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=CALL)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=CALL)
     got = b.encode_host(pcm[:, :CALL * 1152])
     got2 = b.encode_host(pcm[:, CALL * 1152:])
     assert b.status() == 0

@@ -7,22 +7,17 @@ OracleEncoder.encode_s16 for int16); converting streams go through this library'
 the oracle.  Shapes are the smallest that cross every seam: six streams, three or four frames per call, two calls or more.
 Blob comparisons across batches use device calls into zeroed output buffers: a stream's ring of pending main data keeps
 whatever bytes lie behind its frames in the call's row."""
-import ctypes as C
-import functools
-import os
-import subprocess
-import sys
-
 import numpy as np
 import pytest
 
 import packet_cases as PC
-from oracle import oracle as O
-from hmp3_amd import synth
+from gpu_support import CallBufs, Image, batch_vs_single_vs_reference, controls, plain_call as device_call, write_wav
+from hmp3_amd import api, synth
+from mixed_cases import RHOS, blob_diff, joined, key, mono, rows_of, streams_of, want_f32
+from output_checks import check_call, check_image, expected_crc
+from src_cases import Stream, host_converted
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HERE = os.path.dirname(os.path.abspath(__file__))
 
 # stereo CBR-128 44.1 kHz, mono CBR-64 44.1 kHz, joint-stereo VBR 48 kHz, mono 32 kHz behind the DC blocker (test_gpu_parity's
 # MONO["mono_cbr48_32k_long_dc"]), stereo behind the DC blocker, mono VBR 48 kHz
@@ -31,101 +26,16 @@ ENTRIES = [dict(bitrate=64), dict(bitrate=64, mode=3), dict(samprate=48000),
            dict(bitrate=64, filter_select=1), dict(mode=3, samprate=48000)]
 S = len(ENTRIES)
 CHANNELS = [1 if kw.get("mode") == 3 else 2 for kw in ENTRIES]
-RHOS = [0.7, 0.0, 1.0, 0.3]
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def mono(kw):
-    return kw.get("mode") == 3
-
-
-@functools.lru_cache(maxsize=None)
-def signal(seed, kw_items, rho=None):
-    """int16 [22 * 1152(, 2)] at the control's rate, a burst in frame 5 or 6 (32 kHz: 1) ([n] for a mono control)"""
-    kw = dict(kw_items)
-    x = synth.stream_pcm(seed, 30, sr=kw.get("samprate", 44100), rho=RHOS[seed % 4] if rho is None else rho, bursts=True)[8 * 1152:]
-    x = np.ascontiguousarray(x[:, seed & 1] if mono(kw) else x)
-    x.setflags(write=False)
-    return x
-
-
-def as_f32(x, seed):
-    """the signal as float32 at int16 scale with non-integral samples"""
-    return x.astype(np.float32) + np.random.default_rng(seed).uniform(-0.49, 0.49, x.shape).astype(np.float32)
-
-
-@functools.lru_cache(maxsize=None)
-def want_f32(seed, kw_items, rho=None):
-    """-> (float32 signal, the oracle's [PC.Frame] for it): computed once, shared, never changed"""
-    x = as_f32(signal(seed, kw_items, rho), seed)
-    x.setflags(write=False)
-    return x, tuple(PC.oracle_frames(dict(kw_items), x))
-
-
-@functools.lru_cache(maxsize=None)
-def want_s16(seed, kw_items):
-    x = signal(seed, kw_items)
-    enc = O.OracleEncoder(O.default_control(**dict(kw_items)))
-    return x, tuple(enc.encode_s16(x[f * 1152:(f + 1) * 1152]) for f in range(len(x) // 1152))
-
-
-def key(kw):
-    return tuple(sorted(kw.items()))
 
 
 def six(f32, seed=700):
     """the six streams of ENTRIES: (signals, the oracle's bytes per frame)"""
-    if f32:
-        w = [want_f32(seed + i, key(kw)) for i, kw in enumerate(ENTRIES)]
-        return [x for x, _ in w], [[fr.bs for fr in frames] for _, frames in w]
-    w = [want_s16(seed + i, key(kw)) for i, kw in enumerate(ENTRIES)]
-    return [x for x, _ in w], [list(frames) for _, frames in w]
-
-
-def rows_of(pcm, pos, counts, nf, f32):
-    """the call's PCM [S, nf * 1152 * 2]: stream s's next counts[s] frames from frame pos[s] at the start of its row -
-    interleaved for a stereo stream, contiguous for a mono one - and 0x7FFF / NaN everywhere else"""
-    blk = np.full((len(pcm), nf * 1152 * 2), np.nan if f32 else 0x7FFF, np.float32 if f32 else np.int16)
-    for s, n in enumerate(counts):
-        part = pcm[s][pos[s] * 1152:(pos[s] + n) * 1152].reshape(-1)
-        assert len(part) == n * 1152 * pcm[s].ndim
-        blk[s, :len(part)] = part
-    return blk
-
-
-def controls(menu):
-    return [api().default_control(**kw) for kw in menu]
+    return streams_of(ENTRIES, f32, seed)
 
 
 def mixed_batch(menu=ENTRIES, cfg=None, n=None, max_frames=4):
     n = len(menu) if n is None else n
-    return api().Batch.mixed(controls(menu), n, cfg=list(range(n)) if cfg is None else cfg, max_frames=max_frames)
-
-
-def joined(frames, f0, n):
-    return b"".join(frames[f0:f0 + n])
-
-
-def device_call(b, blk, nf, shift=0):
-    """a plain device call into zeroed rows -> the streams' bytes; shift: int16 elements the PCM starts past its buffer"""
-    import torch
-    dev = torch.device("cuda:0")
-    host = torch.from_numpy(np.array(blk).reshape(-1))      # (a copy: the shared signals are read-only)
-    flat = torch.zeros(blk.size + 16, dtype=host.dtype, device=dev)
-    flat[shift:shift + blk.size] = host.to(dev)
-    ptr = flat.data_ptr() + shift * blk.itemsize
-    stride = b.out_stride(nf)
-    d_out = torch.zeros((b.n, stride), dtype=torch.uint8, device=dev)
-    d_nb = torch.full((b.n,), -1, dtype=torch.int32, device=dev)
-    torch.cuda.synchronize()
-    b.encode_device(ptr, nf, d_out.data_ptr(), stride, d_nb.data_ptr(), None, f32=blk.dtype == np.float32)
-    torch.cuda.synchronize()
-    o, nb = d_out.cpu().numpy(), d_nb.cpu().numpy()
-    return [o[s, :nb[s]].tobytes() for s in range(b.n)], ptr
+    return api.Batch.mixed(controls(menu), n, cfg=list(range(n)) if cfg is None else cfg, max_frames=max_frames)
 
 
 @pytest.mark.parametrize("f32", [False, True], ids=["s16", "f32"])
@@ -176,7 +86,7 @@ def test_a_uniform_menu_is_the_menu_batch(which, k6_build):
     ch = 1 if which == "mono" else 2
     x = [want_f32(740 + i, key(kw))[0] for i, kw in enumerate(menu)]
     res = []
-    for make in (api().Batch.mixed, api().Batch.menu):
+    for make in (api.Batch.mixed, api.Batch.menu):
         b = make(controls(menu), len(menu), cfg=list(range(len(menu))), max_frames=4)
         assert b.pcm_channels() == ch and [b.stream_channels(i) for i in range(b.n)] == [ch] * b.n
         outs = []
@@ -214,23 +124,6 @@ def test_per_stream_counts(k6_build):
     b.close()
 
 
-def blob_diff(a, b, skip_class=False):
-    """where two checkpoint blobs differ, as byte ranges of the blob ("" = nowhere); skip_class: but for the class index, the
-    first word of the stream record behind the 24-byte header - the numbering of the batch the blob was saved from"""
-    x, y = np.frombuffer(a, np.uint8), np.frombuffer(b, np.uint8)
-    if len(x) != len(y):
-        return "sizes %d and %d" % (len(x), len(y))
-    d = x != y
-    if skip_class:
-        d[24:28] = False
-    at = np.nonzero(d)[0]
-    if at.size == 0:
-        return ""
-    cuts = np.nonzero(np.diff(at) > 1)[0]
-    runs = list(zip(at[np.r_[0, cuts + 1]].tolist(), at[np.r_[cuts, at.size - 1]].tolist()))
-    return "%d bytes differ, in [first, last] %s" % (at.size, runs[:12])
-
-
 def test_assign_across_channel_counts(k6_build):
     """four slots on loud stereo for two calls; slots 0 and 2 become mono streams for two calls; slot 0 goes back to stereo
     for two calls.  After each assign the slot's rows are a new stream's, and after its first call its checkpoint blob is
@@ -240,7 +133,7 @@ def test_assign_across_channel_counts(k6_build):
     menu = [dict(bitrate=64), dict(bitrate=64, mode=3)]
     F = 3
     lives = [[800 + i, 0, 0] for i in range(4)]        # per slot: [seed, menu entry, frames done]
-    b = api().Batch.mixed(controls(menu), 4, cfg=[0] * 4, max_frames=F)
+    b = api.Batch.mixed(controls(menu), 4, cfg=[0] * 4, max_frames=F)
     assert b.pcm_channels() == 2
 
     def call(tag, fresh=()):
@@ -252,7 +145,7 @@ def test_assign_across_channel_counts(k6_build):
             assert got[s] == b"".join(f.bs for f in w[s][1][pos[s]:pos[s] + F]), "%s slot %d (entry %d)" % (tag, s, lives[s][1])
             lives[s][2] += F
         for s in fresh:
-            one = api().Batch(api().default_control(**menu[lives[s][1]]), nstreams=1, max_frames=F)
+            one = api.Batch(api.default_control(**menu[lives[s][1]]), nstreams=1, max_frames=F)
             assert device_call(one, np.ascontiguousarray(w[s][0][:F * 1152].reshape(1, -1)), F)[0][0] == got[s]
             alone = one.get_stream_state(0)
             one.close()
@@ -283,10 +176,7 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
     set) and the ledger equal what the host rules derive from the oracle's frames.  The mono file in slot 1 and the
     stereo file in slot 4 end inside the second call."""
     import torch
-    from test_gpu_packets import check_call, FILL
-    from test_gpu_crc import expected_crc
-    from test_gpu_dense import check_image
-    A = api()
+    A = api
     F, NC, PK = 4, 3, 2048
     w = [want_f32(700 + i, key(kw)) for i, kw in enumerate(ENTRIES)]
     pcm, frames = [x for x, _ in w], [list(f) for _, f in w]
@@ -298,31 +188,13 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
     b.ledger_begin(list(range(S)), ncalls, stream=st)
     recs = [A.ledger_open(n, 1, 0, 0) for n in ncalls]
 
-    class Set:
-        def __init__(self):
-            self.pk = torch.full((S, F, PK), FILL, dtype=torch.uint8, device=dev)
-            self.pkb = torch.full((S, F, 2), -1, dtype=torch.int32, device=dev)
-            self.stats = torch.full((S, F, 2), -1, dtype=torch.int32, device=dev)
-            self.crc = torch.full((S, F), -1, dtype=torch.int16, device=dev)
-            self.dense = torch.full((cap,), FILL, dtype=torch.uint8, device=dev)
-            self.off = torch.full((S + 1,), -1, dtype=torch.int64, device=dev)
-            assert self.dense.data_ptr() % 16 == 0
-
-        def set_on(self):
-            b.packet_buffers(self.pk.data_ptr(), PK, self.pkb.data_ptr())
-            b.frame_stats_buffer(self.stats.data_ptr())
-            b.crc_buffer(self.crc.data_ptr())
-            b.dense_buffers(self.dense.data_ptr(), cap, self.off.data_ptr())
-
     # rows and byte counts alternate between two sets, so call 2 overwrites call 0's; the optional outputs are per call
-    sets = [Set() for _ in range(NC)]
-    d_rows = [torch.zeros((S, stride), dtype=torch.uint8, device=dev) for _ in range(2)]
-    d_nb = [torch.full((S,), -1, dtype=torch.int32, device=dev) for _ in range(2)]
+    sets = [CallBufs(b, F, counters=True, crc=True, packets=PK, image=Image(S, cap, guard=0)) for _ in range(NC)]
     d_pcm = [torch.from_numpy(rows_of(pcm, [F * c] * S, [F] * S, F, True)).to(dev) for c in range(NC)]
     torch.cuda.synchronize()
     for c in range(NC):
-        sets[c].set_on()
-        b.submit_device(d_pcm[c].data_ptr(), F, d_rows[c & 1].data_ptr(), stride, d_nb[c & 1].data_ptr(), st, f32=True)
+        sets[c].set_on(b)
+        b.submit_device(d_pcm[c].data_ptr(), F, sets[c & 1].ptr, stride, sets[c & 1].nb.data_ptr(), st, f32=True)
     b.wait(st)
     torch.cuda.synchronize()
     assert b.status() == 0
@@ -340,16 +212,16 @@ def test_optional_outputs_of_pipelined_submits(k6_build):
         ended = [bool(A.ledger_update(recs[s], stats[s], crc[s], nb[s])) for s in range(S)]
         assert ended == [c == 1 and s in (1, 4) for s in range(S)], "call %d: which files the host's rule ends" % c
         o, tag = sets[c], "call %d" % c
-        dense, off = o.dense.cpu().numpy(), o.off.cpu().numpy()
+        dense, off = o.image.host()
         check_image(rows, nb, dense, off, cap, tag=tag)
         if c == 0:      # (its rows are gone: the image holds them)
             got_bs = [dense[off[s]:off[s] + nb[s]].tobytes() for s in range(S)]
         else:
-            g_rows, g_nb = d_rows[c & 1].cpu().numpy(), d_nb[c & 1].cpu().numpy()
+            g_rows, g_nb = sets[c & 1].rows()
             assert g_nb.tolist() == nb.tolist(), tag
             got_bs = [g_rows[s, :g_nb[s]].tobytes() for s in range(S)]
-        check_call(frames, F * c, F, got_bs, o.pk.cpu().numpy(), o.pkb.cpu().numpy(), o.stats.cpu().numpy(), 0, tag)
-        assert (o.crc.cpu().numpy().view(np.uint16) == crc).all(), tag + ": per-frame CRCs"
+        check_call(frames, F * c, F, got_bs, *o.packets(), 0, tag)
+        assert (o.host()[3] == crc).all(), tag + ": per-frame CRCs"
     got = b.ledger_read(list(range(S)))
     for s in range(S):
         assert got[s].tobytes() == recs[s].tobytes(), "the record of slot %d differs from hx_ledger_update's" % s
@@ -363,7 +235,7 @@ def test_blobs_move_between_a_mixed_and_a_uniform_batch(which, k6_build):
     from that uniform batch after one call continues in slot `which` of a new mixed batch"""
     pcm, want = six(True)
     kw = ENTRIES[which]
-    uni = lambda: api().Batch(api().default_control(**kw), nstreams=1, max_frames=4)
+    uni = lambda: api.Batch(api.default_control(**kw), nstreams=1, max_frames=4)
     own = lambda f0: np.ascontiguousarray(pcm[which][f0 * 1152:(f0 + 4) * 1152].reshape(1, -1))
     m = mixed_batch()
     assert m.encode_host(rows_of(pcm, [0] * S, [4] * S, 4, True))[which] == joined(want[which], 0, 4)
@@ -394,7 +266,7 @@ def test_multi_over_two_blocks(k6_build):
     a mono and a stereo row; one call, an assign that crosses both blocks, another call"""
     menu = [dict(bitrate=64), dict(bitrate=64, mode=3)]
     cfg = [0, 1, 1, 0, 1]
-    m = api().Multi.mixed(controls(menu), 5, cfg=cfg, max_frames=3, devices=[0, 0])
+    m = api.Multi.mixed(controls(menu), 5, cfg=cfg, max_frames=3, devices=[0, 0])
     assert m.ndevices() == 2 and [m.shard(k)[1:] for k in range(2)] == [(0, 3), (3, 2)]
     assert m.pcm_channels() == 2 and [m.stream_channels(i) for i in range(5)] == [2, 1, 1, 2, 1]
     w = [want_f32(900 + i, key(menu[c])) for i, c in enumerate(cfg)]
@@ -416,33 +288,12 @@ def test_multi_over_two_blocks(k6_build):
 
 # ---- converting batches ----
 
-def host_converted(s, nframes):
-    """this library's host converter over the source's first nframes calls -> (float32 [nframes * 1152(, 2)], bytes used per call)"""
-    L = api().lib()
-    tch = 1 if (s.channels == 1 or s.mono_convert) else 2
-    h = L.hx_src_create()
-    cut = C.c_int(0)
-    assert L.hx_src_init(h, s.source, s.channels, s.bits, s.is_float, s.mpeg_select or s.source, tch, C.byref(cut)) > 0
-    buf = (C.c_ubyte * len(s.data)).from_buffer_copy(s.data)
-    ys, used, pos = [], [], 0
-    for _ in range(nframes):
-        y = np.zeros(2304, np.float32)
-        n = L.hx_src_convert(h, C.byref(buf, pos), y.ctypes.data, None)
-        used.append(n)
-        pos += n
-        ys.append(y[:1152 * tch])
-    L.hx_src_destroy(h)
-    y = np.concatenate(ys)
-    return (y if tch == 1 else y.reshape(-1, 2)), used, tch
-
-
 @pytest.mark.parametrize("counts", [None, [[3, 1, 2, 0], [2, 3, 0, 3]]], ids=["uniform", "per_stream_counts"])
 def test_converting_mixed_batch(counts, k6_build):
     """stereo s16 44.1 kHz, mono u8 32 -> 44.1 kHz, stereo s24 48 -> 44.1 kHz summed to mono, mono f32 44.1 kHz: the
     converted PCM (the "srcpcm" tap) is hx_src_convert's bit for bit, each stream's calls contiguous at the start of a row
     pitched for two channels, and the rows are the oracle's for that PCM under the control src_encode_control derives"""
-    from test_gpu_src_batch import Stream
-    A = api()
+    A = api
     F = 3
     streams = [Stream(44100, 16, 0, seed=21, seconds=1.0), Stream(32000, 8, 0, channels=1, mpeg_select=44100, seed=22, seconds=1.0),
                Stream(48000, 24, 0, mono_convert=1, mpeg_select=44100, seed=23, seconds=1.0), Stream(44100, 32, 1, channels=1, seed=24, seconds=1.0)]
@@ -483,36 +334,18 @@ def test_converting_mixed_batch(counts, k6_build):
 
 # ---- the command line ----
 
-CLI = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-REF_CLI = os.path.join(ROOT, "oracle", "_ref", "hmp3")
-
-
 @pytest.mark.one_k6_build
 @pytest.mark.parametrize("flags", [[], ["-A32000", "-B64"]], ids=["fp32_frames", "converting"])
 @pytest.mark.parametrize("slots", [[], ["-slots2"]], ids=["batch", "slots2"])
 def test_cli_batch_of_mono_and_stereo_files(tmp_path, flags, slots, k6_build):
     """hmp3amd -batch [-slots2] on five files of either channel count, 5 to 130 frames: every output is the file's
     single-file run and, where the reference binary is built, the reference's"""
-    sys.path.insert(0, os.path.join(HERE, "golden"))
-    from make_golden_cli import write_wav
-    assert os.path.exists(CLI), "hmp3_amd/build.sh builds the CLI"
     # (name, rate, channels, write_wav's format: False s16, True f32, 8 / 24 integer widths, frames)
     files = [("a", 44100, 2, False, 130), ("b", 44100, 1, False, 5), ("c", 48000, 2, 24, 37), ("d", 48000, 1, True, 61), ("e", 32000, 1, 8, 18)]
-    args = []
+    pairs = []
     for k, (name, sr, ch, fmt, frames) in enumerate(files):
         nsamp = frames * 1152 * (sr // 100 if flags else 320) // 320 - 301 * k - 7
         x = synth.stream_pcm(60 + k, nsamp // 1152 + 1, sr=sr, rho=RHOS[k % 4], bursts=True)[:nsamp]
         write_wav(str(tmp_path / (name + ".wav")), x if ch == 2 else np.ascontiguousarray(x[:, 0]), sr, fmt)
-        args += [str(tmp_path / (name + ".wav")), str(tmp_path / (name + ".batch.mp3"))]
-    r = subprocess.run([CLI, "-batch"] + slots + args + flags, capture_output=True, timeout=120)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
-    for name, *_ in files:
-        wav, got = str(tmp_path / (name + ".wav")), open(str(tmp_path / (name + ".batch.mp3")), "rb").read()
-        one = str(tmp_path / (name + ".one.mp3"))
-        r = subprocess.run([CLI, wav, one] + flags, capture_output=True, timeout=120)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
-        assert len(got) > 1000 and got == open(one, "rb").read(), name + ": differs from its single-file run"
-        if os.path.exists(REF_CLI):
-            ref = str(tmp_path / (name + ".ref.mp3"))
-            subprocess.run([REF_CLI, wav, ref] + flags, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=120)
-            assert got == open(ref, "rb").read(), name + ": differs from the reference binary's output"
+        pairs.append((name, str(tmp_path / (name + ".wav")), str(tmp_path / (name + ".batch.mp3"))))
+    batch_vs_single_vs_reference(pairs, flags, slots, floor=1000)

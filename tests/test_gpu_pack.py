@@ -8,14 +8,10 @@ import numpy as np
 import pytest
 
 import pack_cases as P
+from hmp3_amd import api
 
 # (the packer does not depend on which build of the stream walk a batch would run)
 pytestmark = [pytest.mark.gpu, pytest.mark.one_k6_build]
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 def first_difference(got, want):
@@ -28,7 +24,7 @@ def run(name):
     b = P.build(P.tables(), P.case_list(name))
     assert (b["rows"] == 0xA5).all() and (b["packet"] == 0xA5).all()
     rc, status = P.debug_pack(b)
-    assert rc == 0, api().lib().hx_last_error().decode()
+    assert rc == 0, api.lib().hx_last_error().decode()
     return b, status
 
 
@@ -52,5 +48,5 @@ def test_a_refused_record_launches_nothing():
     b = P.build(P.tables(), P.case_list("status"))
     b["ixq"][0, 2, 1, 0] = 9        # above the largest table dimension among the segment's tables
     rc, status = P.debug_pack(b)
-    assert rc != 0 and "above its table's range" in api().lib().hx_last_error().decode()
+    assert rc != 0 and "above its table's range" in api.lib().hx_last_error().decode()
     assert status == -1 and (b["rows"] == 0xA5).all() and (b["packet"] == 0xA5).all()

@@ -8,90 +8,35 @@ what a call does not write stays recognisable, and so does a byte written past a
 import numpy as np
 import pytest
 
+import gpu_support as G
 import packet_cases as PC
 from conftest import skip_unless_host_libm_is_the_restated_one
+from gpu_support import CallBufs, cut, sync
+from hmp3_amd import api
+from output_checks import check_call
+from src_cases import Stream, make_batch
 
 pytestmark = pytest.mark.gpu
-FILL = 0xA5
 
 
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def cut(pcm, f0, nf):
-    return np.ascontiguousarray(pcm[:, f0 * 1152:(f0 + nf) * 1152])
-
-
-class Outputs:
-    """the device buffers of one call, prefilled"""
-
-    def __init__(self, b, nf, frame_stride):
-        import torch
-        dev = torch.device("cuda:0")
-        self.nf, self.frame_stride, self.stride = nf, frame_stride, b.out_stride(nf)
-        self.out = torch.empty((b.n, self.stride), dtype=torch.uint8, device=dev)
-        self.nb = torch.empty((b.n,), dtype=torch.int32, device=dev)
-        self.pk = torch.empty((b.n, nf, frame_stride), dtype=torch.uint8, device=dev)
-        self.pkb = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
-        self.st = torch.empty((b.n, nf, 2), dtype=torch.int32, device=dev)
-        self.prefill()
-
-    def prefill(self):
-        """(again: the same buffers for a further call, the batch's setters untouched)"""
-        import torch
-        self.out.zero_()
-        self.pk.fill_(FILL)
-        for t in (self.nb, self.pkb, self.st):
-            t.fill_(-1)
-        torch.cuda.synchronize()
-
-    def set_on(self, b, stats=True):
-        b.packet_buffers(self.pk.data_ptr(), self.frame_stride, self.pkb.data_ptr())
-        b.frame_stats_buffer(self.st.data_ptr() if stats else None)
-
-    def bitstreams(self):
-        o, n = self.out.cpu().numpy(), self.nb.cpu().numpy()
-        return [o[s, :n[s]].tobytes() for s in range(len(n))]
-
-    def host(self):
-        return self.pk.cpu().numpy(), self.pkb.cpu().numpy(), self.st.cpu().numpy()
-
-
-def check_call(want, f0, nf, bs, pk, pkb, stats, lsf, tag=""):
-    """one call's outputs against the oracle's frames f0 .. f0 + nf of every stream (want[s]: [PC.Frame])"""
-    for s in range(len(want)):
-        assert bs[s] == b"".join(w.bs for w in want[s][f0:f0 + nf]), "%s stream %d: bitstream" % (tag, s)
-        for f in range(nf):
-            w = want[s][f0 + f]
-            at = "%s stream %d frame %d + %d" % (tag, s, f0, f)
-            n0, n1 = w.sizes
-            assert n0 > 0 and (n1 > 0) == bool(lsf), at         # (the expectation itself: one packet, or the MPEG-2 call's two)
-            assert tuple(pkb[s, f]) == (n0, n1), at + ": packet sizes"
-            assert pk[s, f, :n0 + n1].tobytes() == w.packet, at + ": packet"
-            assert (pk[s, f, n0 + n1:] == FILL).all(), at + ": bytes written behind the packet"
-            assert tuple(stats[s, f]) == (w.frames_out, w.bytes_out), at + ": frames / bytes emitted so far"
+def outputs(b, nf, frame_stride):
+    """the device buffers of one call, prefilled: zeroed rows, packets of 0xA5, byte counts, sizes and counters of -1"""
+    return CallBufs(b, nf, counters=True, packets=frame_stride)
 
 
 def device_call(b, blk, nf, frame_stride):
     """a plain fp32 device-buffer call with packet and counter buffers of its own -> (bitstreams, packets, sizes, counters)"""
-    import torch
-    o = Outputs(b, nf, frame_stride)
-    o.set_on(b)
-    d_pcm = torch.from_numpy(blk).to(torch.device("cuda:0"))
-    torch.cuda.synchronize()
-    b.encode_device(d_pcm.data_ptr(), nf, o.out.data_ptr(), o.stride, o.nb.data_ptr(), torch.cuda.current_stream().cuda_stream, f32=True)
-    torch.cuda.synchronize()
-    return (o.bitstreams(),) + o.host()
+    o = G.device_call(b, blk, nf, outputs(b, nf, frame_stride).set_on(b))
+    sync()
+    return (o.bitstreams(),) + o.packets()
 
 
 def host_call(b, blk, nf, frame_stride):
     """the fp32 host-buffer call that returns the counters (hx_batch_encode_f32_host_stats), packets to device buffers"""
-    o = Outputs(b, nf, frame_stride)
+    o = outputs(b, nf, frame_stride)
     o.set_on(b, stats=False)
     bs, stats = b.encode_host(blk, stats=True)
-    pk, pkb, _ = o.host()
+    pk, pkb, _ = o.packets()
     return bs, pk, pkb, stats
 
 
@@ -102,7 +47,7 @@ def run_calls(kw, S, calls, frame_stride, seed, bursts=lambda i: i % 2 == 0):
     pcm = PC.packet_pcm(seed, S, F, kw, bursts=bursts)
     want = [PC.oracle_frames(kw, pcm[s]) for s in range(S)]
     lsf = kw.get("samprate", 44100) < 32000
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=max(nf for nf, _ in calls))
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=max(nf for nf, _ in calls))
     f0, packets, bts = 0, [], []
     for c, (nf, route) in enumerate(calls):
         bs, pk, pkb, stats = route(b, cut(pcm, f0, nf), nf, frame_stride)
@@ -184,8 +129,8 @@ def test_buffers_set_once_hold_across_a_host_call_that_returns_the_counters(S):
     kw, nf = dict(bitrate=64), 2
     pcm = PC.packet_pcm(6800, S, 3 * nf, kw)
     want = [PC.oracle_frames(kw, pcm[s]) for s in range(S)]
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
-    o = Outputs(b, nf, 4096)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=nf)
+    o = outputs(b, nf, 4096)
     o.set_on(b)
     for c in range(3):
         blk = cut(pcm, c * nf, nf)
@@ -193,14 +138,14 @@ def test_buffers_set_once_hold_across_a_host_call_that_returns_the_counters(S):
             o.prefill()
         if c == 1:
             bs, stats = b.encode_host(blk, stats=True)
-            pk, pkb, st = o.host()
+            pk, pkb, st = o.packets()
             assert (st == -1).all(), "the host call wrote the caller's device counter buffer"
         else:
             d_pcm = torch.from_numpy(blk).to(torch.device("cuda:0"))
             torch.cuda.synchronize()
-            b.encode_device(d_pcm.data_ptr(), nf, o.out.data_ptr(), o.stride, o.nb.data_ptr(), torch.cuda.current_stream().cuda_stream, f32=True)
+            b.encode_device(d_pcm.data_ptr(), nf, o.ptr, o.stride, o.nb.data_ptr(), torch.cuda.current_stream().cuda_stream, f32=True)
             torch.cuda.synchronize()
-            bs, (pk, pkb, stats) = o.bitstreams(), o.host()
+            bs, (pk, pkb, stats) = o.bitstreams(), o.packets()
         assert b.status() == 0
         check_call(want, c * nf, nf, bs, pk, pkb, stats, 0, "call %d" % c)
     b.close()
@@ -213,7 +158,7 @@ def test_packets_and_counters_are_indexed_by_stream_under_a_launch_order(monkeyp
     kw, S, nf, calls = dict(vbr_mnr=60), 24, 6, 3
     pcm = PC.packet_pcm(6600, S, nf * calls, kw, bursts=lambda i: i % 3 == 0)
     want = [PC.oracle_frames(kw, pcm[s]) for s in range(S)]
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=nf)
     for c in range(calls):
         bs, pk, pkb, stats = device_call(b, cut(pcm, c * nf, nf), nf, 4096)
         assert b.status() == 0
@@ -237,10 +182,10 @@ def submit_calls(gate, host):
     want = [PC.oracle_frames(kw, pcm[s]) for s in range(S)]
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=nf)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=nf)
     if gate is not None:
         b.set_gate(gate)
-    outs = [Outputs(b, nf, 4096) for _ in range(calls)]
+    outs = [outputs(b, nf, 4096) for _ in range(calls)]
     blks = [cut(pcm, c * nf, nf) if f32[c] else cut(pcm, c * nf, nf).astype(np.int16) for c in range(calls)]
     if host:
         ins = [torch.from_numpy(x).pin_memory() for x in blks]
@@ -254,7 +199,7 @@ def submit_calls(gate, host):
         if host:
             b.submit_host(ins[c].data_ptr(), nf, h_out[c].data_ptr(), outs[c].stride, h_nb[c].data_ptr(), f32=True)
         else:
-            b.submit_device(ins[c].data_ptr(), nf, outs[c].out.data_ptr(), outs[c].stride, outs[c].nb.data_ptr(), st, f32=f32[c])
+            b.submit_device(ins[c].data_ptr(), nf, outs[c].ptr, outs[c].stride, outs[c].nb.data_ptr(), st, f32=f32[c])
     b.packet_buffers(None, 0, None)
     b.frame_stats_buffer(None)
     if host:
@@ -269,7 +214,7 @@ def submit_calls(gate, host):
             bs = [o[s, :n[s]].tobytes() for s in range(S)]
         else:
             bs = outs[c].bitstreams()
-        check_call(want, c * nf, nf, bs, *outs[c].host(), 0, "%s submit %d" % ("host" if host else "device", c))
+        check_call(want, c * nf, nf, bs, *outs[c].packets(), 0, "%s submit %d" % ("host" if host else "device", c))
     b.close()
 
 
@@ -288,8 +233,7 @@ def test_converting_batch_packets_and_counters():
     """a converting batch (hx_batch_create_src): the packets and counters of what k_src converted - expected from the call's
     "srcpcm" tap (pinned to the reference's converter by test_srcpcm_tap_equals_the_reference_converter) through the
     oracle under the control the encoder runs behind the converter"""
-    from test_gpu_src_batch import Stream, make_batch
-    A = api()
+    A = api
     streams = [Stream(48000, 24, 0, mpeg_select=44100, seed=71), Stream(32000, 32, 1, mpeg_select=44100, seed=72)]
     S = len(streams)
     controls = []
@@ -306,11 +250,11 @@ def test_converting_batch_packets_and_counters():
         for i, s in enumerate(streams):
             chunk = np.frombuffer(s.data[pos[i]:pos[i] + stride], np.uint8)
             rows[i, :len(chunk)] = chunk
-        o = Outputs(b, nf, 4096)
+        o = outputs(b, nf, 4096)
         o.set_on(b, stats=False)
         bs, used, stats = b.encode_src_host(rows, nf, stats=True)
         assert b.status() == 0
-        pk, pkb, _ = o.host()
+        pk, pkb, _ = o.packets()
         conv = b.debug_read("srcpcm", np.float32, S * nf * 1152 * 2).reshape(S, nf * 1152, 2)
         assert (conv != np.round(conv)).any()
         want = []

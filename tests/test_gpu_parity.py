@@ -11,12 +11,14 @@ import numpy as np
 import pytest
 
 from oracle import oracle as O
-from hmp3_amd import synth
+from hmp3_amd import api, synth
 from conftest import skip_unless_host_libm_is_the_restated_one
+from gpu_support import GOLD, GOLDEN_CLI as M, SHIM_CLI, oracle_bytes, run_cli
+from oracle_pool import oracle_bytes_many
+from parity_cases import random_control
 from stage_taps import TapBatch
 
 pytestmark = pytest.mark.gpu
-GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 META = json.load(open(os.path.join(GOLD, "streams.json")))
 RHOS = [0.7, 0.0, 1.0, 0.3]
 
@@ -45,27 +47,13 @@ def wants_bursts(kw):
     return kw.get("short_block_threshold", 700) < 99999
 
 
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
-def oracle_bytes(kw, pcm, nfr):
-    enc = O.OracleEncoder(O.default_control(**kw))
-    return b"".join(enc.encode_s16(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr))
-
-
 @pytest.mark.parametrize("name", list(CONFIGS))
 def test_batch_bitstream_byte_identical_to_oracle(name):
     kw = CONFIGS[name]
     sr = kw.get("samprate", 44100)
     S, F = 12, 48
     pcm = np.stack([synth.stream_pcm(100 + i, F, sr=sr, rho=RHOS[i % 4], bursts=wants_bursts(kw)) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     for s in range(S):
@@ -94,18 +82,10 @@ def test_batch_bitstream_byte_identical_to_oracle(name):
 def test_cli_whole_file_byte_identical_to_reference_cli(name, tmp_path):
     """hmp3_amd/hmp3amd (GPU path + Xing/Info tag + WAV front end) against files written by the real
     reference CLI (tests/golden/cli_*.mp3, tests/golden/make_golden_cli.py)"""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tests", "golden"))
-    import make_golden_cli as M
     seed, nsamp, sr, as_float, bursts, flags = M.CASES[name]
     wav, mp3 = str(tmp_path / "in.wav"), str(tmp_path / "out.mp3")
     M.write_wav(wav, M.case_pcm(name), sr, as_float, M.CONTAINER.get(name))
-    exe = os.path.join(root, "hmp3_amd", "hmp3amd")
-    assert os.path.exists(exe), "hmp3_amd/build.sh builds the CLI"
-    r = subprocess.run([exe, wav, mp3] + flags, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
+    run_cli([wav, mp3] + flags, timeout=None)
     assert open(mp3, "rb").read() == open(os.path.join(GOLD, name + ".mp3"), "rb").read()
 
 
@@ -117,7 +97,7 @@ def test_loud_near_mono_material_takes_the_double_table_path(kw):
     sr = kw.get("samprate", 44100)
     S, F = 8, 40
     pcm = np.stack([synth.stream_pcm(8100 + i, F, sr=sr, rho=1.0, bursts=wants_bursts(kw)) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     b.debug_enable(True)
     got = b.encode_host(pcm)
     assert b.status() == 0
@@ -143,7 +123,7 @@ def test_certified_band_sums_and_strict_band_sums_give_the_same_bytes(kw, monkey
     counts = []
     for strict in ("0", "1"):
         monkeypatch.setenv("HMP3AMD_EXACT_SUMS", strict)
-        b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+        b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
         got = b.encode_host(pcm)
         assert b.status() == 0
         for s in range(S):
@@ -171,7 +151,7 @@ def test_negative_scalefactors_go_through_the_unmasked_bit_writer(kw, seed, rho,
     skip_unless_host_libm_is_the_restated_one()
     pcm = synth.stream_pcm(seed, F, sr=kw["samprate"], rho=rho, bursts=bursts)
     pcm = (pcm.astype(np.float64) * 0.02).astype(np.int16)[None]
-    b = api().Batch(api().default_control(**kw), nstreams=1, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=1, max_frames=F)
     got = b.encode_host(pcm)[0]
     assert b.status() == 0
     assert got == oracle_bytes(kw, pcm[0], F)
@@ -183,8 +163,8 @@ def test_packet_variant_matches_oracle(kw):
     """CMp3Enc::L3_audio_encode_Packet: bitstream plus the self-contained packet of every frame"""
     nfr = 30
     pcm = synth.stream_pcm(23, nfr, bursts=True).astype(np.float32)
-    e = api().Mp3Enc()
-    assert e.L3_audio_encode_init(api().default_control(**kw)) == 9216
+    e = api.Mp3Enc()
+    assert e.L3_audio_encode_init(api.default_control(**kw)) == 9216
     o = O.OracleEncoder(O.default_control(**kw))
     for f in range(nfr):
         nin, bs, pk = e.L3_audio_encode_Packet(pcm[f * 1152:(f + 1) * 1152])
@@ -200,8 +180,8 @@ def test_packet_calls_between_plain_and_replayed_calls_of_one_encoder(kw):
     call's bitstream and the two calls' packets against one oracle encoder (MPEG-2: two packets per call)."""
     nfr = 10
     pcm = synth.stream_pcm(29, nfr, sr=kw.get("samprate", 44100), bursts=True).astype(np.float32)
-    e = api().Mp3Enc()
-    assert e.L3_audio_encode_init(api().default_control(**kw)) == 9216
+    e = api.Mp3Enc()
+    assert e.L3_audio_encode_init(api.default_control(**kw)) == 9216
     o = O.OracleEncoder(O.default_control(**kw))
     total = 0
     for f in range(nfr):
@@ -220,9 +200,6 @@ def test_packet_calls_between_plain_and_replayed_calls_of_one_encoder(kw):
     e.close()
 
 
-SHIM_CLI = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "_ref", "hmp3_on_amd")
-
-
 @pytest.mark.skipif(not os.path.exists(SHIM_CLI), reason="oracle/_ref/hmp3_on_amd not built (make -C oracle shimcli)")
 @pytest.mark.parametrize("name", ["cli_cbr128_s16_44k", "cli_vbr75_f32_48k_hf", "cli_cbr192_s16_32k_x1_dc", "cli_vbr50_s24_44k",
                                   "cli_mono_vbr60_f32_48k", "cli_downmix_vbr50_s16_44k", "cli_lsf_cbr64_s16_22k",
@@ -232,16 +209,10 @@ def test_reference_cli_source_on_the_drop_in_library(name, tmp_path):
     """The drop-in claim, exercised by the reference's own driver: its command line (test/tomp3.cpp with its WAV
     parser and tag writer, compiled unmodified where it lies) built against include/shim/mp3enc.h and -lhmp3amd
     must write the same files as the reference CLI built on the reference encoder (tests/golden/cli_*.mp3)."""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tests", "golden"))
-    import make_golden_cli as M
     seed, nsamp, sr, as_float, bursts, flags = M.CASES[name]
     wav, mp3 = str(tmp_path / "in.wav"), str(tmp_path / "out.mp3")
     M.write_wav(wav, M.case_pcm(name), sr, as_float, M.CONTAINER.get(name))
-    r = subprocess.run([SHIM_CLI, wav, mp3] + flags, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
+    run_cli([wav, mp3] + flags, exe=SHIM_CLI, timeout=None)
     assert open(mp3, "rb").read() == open(os.path.join(GOLD, name + ".mp3"), "rb").read()
 
 
@@ -249,11 +220,6 @@ def test_reference_cli_source_on_the_drop_in_library(name, tmp_path):
 def test_cli_batch_mode_files_byte_identical_to_reference_cli(tmp_path, which):
     """`hmp3amd -batch`: files of different rates / sample formats / lengths encoded as one batch of streams;
     every output file must equal what the reference CLI writes for that input alone"""
-    import subprocess
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, os.path.join(root, "tests", "golden"))
-    import make_golden_cli as M
     inputs, bflags = (M.BATCH_INPUTS, M.BATCH_FLAGS) if which == "mpeg1" else (M.BATCH_LSF_INPUTS, M.BATCH_LSF_FLAGS)
     args = []
     for name in inputs:
@@ -261,8 +227,7 @@ def test_cli_batch_mode_files_byte_identical_to_reference_cli(tmp_path, which):
         wav, mp3 = str(tmp_path / (name + ".wav")), str(tmp_path / (name + ".mp3"))
         M.write_wav(wav, M.case_pcm(name), sr, as_float)
         args += [wav, mp3]
-    r = subprocess.run([os.path.join(root, "hmp3_amd", "hmp3amd"), "-batch"] + args + bflags, stdout=subprocess.PIPE, stderr=subprocess.PIPE)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
+    run_cli(["-batch"] + args + bflags, timeout=None)
     for name in inputs:
         got = open(str(tmp_path / (name + ".mp3")), "rb").read()
         assert got == open(os.path.join(GOLD, "batch_" + name[4:] + ".mp3"), "rb").read(), name
@@ -284,7 +249,7 @@ def test_mono_batch_byte_identical_to_oracle(name):
     sr = kw.get("samprate", 44100)
     S, F = 6, 40
     pcm = np.stack([synth.stream_pcm(500 + i, F, sr=sr, bursts=True)[:, i & 1] for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm[:, :25 * 1152])
     got2 = b.encode_host(pcm[:, 25 * 1152:])
     assert b.status() == 0
@@ -322,7 +287,7 @@ def test_mpeg2_batch_byte_identical_to_oracle(name):
     pcm = np.stack([synth.stream_pcm(700 + i, F, sr=sr, rho=RHOS[i % 4], bursts=wants_bursts(kw)) for i in range(S)])
     if mono:
         pcm = np.ascontiguousarray(pcm[:, :, 0])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm[:, :23 * 1152])
     got2 = b.encode_host(pcm[:, 23 * 1152:])
     assert b.status() == 0
@@ -359,7 +324,7 @@ def test_intensity_stereo_and_dual_channel_byte_identical_to_oracle(name):
     kw, sr = A1[name]
     S, F = 8, 40
     pcm = np.stack([synth.stream_pcm(5200 + i, F, sr=sr, rho=RHOS[i % 4], bursts=(i % 2 == 0)) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=24)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=24)
     got = [b"" for _ in range(S)]
     pos = 0
     for n in (3, 24, 13):
@@ -387,7 +352,7 @@ def test_intensity_stereo_stress_signals():
             np.stack([tone, -tone], axis=1), np.stack([tone, np.zeros(n, np.int16)], axis=1)]
     pcm = np.stack(sigs)
     for kw in (dict(bitrate=64, nsbstereo=6), dict(bitrate=64, mode=2), dict(bitrate=16, samprate=22050), dict(bitrate=32, samprate=16000, mode=2)):
-        b = api().Batch(api().default_control(**kw), nstreams=len(sigs), max_frames=F)
+        b = api.Batch(api.default_control(**kw), nstreams=len(sigs), max_frames=F)
         got = b.encode_host(pcm)
         assert b.status() == 0
         for s in range(len(sigs)):
@@ -396,9 +361,9 @@ def test_intensity_stereo_stress_signals():
 
 
 def test_mpeg2_and_mpeg1_cannot_share_a_batch():
-    ecs = [api().default_control(bitrate=32, samprate=22050), api().default_control(bitrate=64)]
+    ecs = [api.default_control(bitrate=32, samprate=22050), api.default_control(bitrate=64)]
     with pytest.raises(RuntimeError, match="cannot share a batch"):
-        api().Batch(ecs, nstreams=2, max_frames=4)
+        api.Batch(ecs, nstreams=2, max_frames=4)
 
 
 @pytest.mark.parametrize("kw", [dict(bitrate=32, samprate=22050), dict(samprate=24000, vbr_mnr=80), dict(bitrate=32, samprate=16000, mode=3)],
@@ -411,8 +376,8 @@ def test_mpeg2_packet_variant_matches_oracle(kw):
     if kw.get("mode") == 3:
         pcm = np.ascontiguousarray(pcm[:, 0])
         nin_want = 4608
-    e = api().Mp3Enc()
-    assert e.L3_audio_encode_init(api().default_control(**kw)) == nin_want
+    e = api.Mp3Enc()
+    assert e.L3_audio_encode_init(api.default_control(**kw)) == nin_want
     o = O.OracleEncoder(O.default_control(**kw))
     for f in range(nfr):
         nin, bs, pk = e.L3_audio_encode_Packet(pcm[f * 1152:(f + 1) * 1152])
@@ -437,7 +402,7 @@ def test_pipelined_submit_equals_plain_calls_and_oracle():
     d_pcm = [torch.from_numpy(np.ascontiguousarray(pcm[:, c * F * 1152:(c + 1) * F * 1152])).to(dev) for c in range(calls)]
     got = {}
     for mode in ("plain", "submit_gate90", "submit_gate0"):
-        b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+        b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
         if mode == "submit_gate0":
             b.set_gate(0)
         stride = b.out_stride(F)
@@ -459,7 +424,6 @@ def test_pipelined_submit_equals_plain_calls_and_oracle():
     assert got["submit_gate90"] == got["plain"] and got["submit_gate0"] == got["plain"]
     # (512 streams on 256 CUs: the launch order is the previous call's durations and, from the second call on, the CU-mates
     # of the eight longest streams park - every stream against the oracle)
-    from oracle_pool import oracle_bytes_many
     want = oracle_bytes_many(kw, pcm, F * calls)
     bad = [s for s in range(S) if got["plain"][s] != want[s]]
     assert not bad, "%d of %d streams differ from the oracle, first: %s" % (len(bad), S, bad[:8])
@@ -479,7 +443,7 @@ def test_parking_changes_no_byte_and_the_placement_tap_names_every_cu(park, monk
     S, F, calls = 1024, 6, 3
     base = [synth.stream_pcm(7100 + u, F * calls, rho=RHOS[u % 4]) for u in range(64)]
     pcm = np.stack([np.roll(base[i % 64], 1152 * (i // 64), axis=0) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = [b"" for _ in range(S)]
     for c in range(calls):
         out = b.encode_host(pcm[:, c * F * 1152:(c + 1) * F * 1152])
@@ -491,7 +455,6 @@ def test_parking_changes_no_byte_and_the_placement_tap_names_every_cu(park, monk
     cus, counts = np.unique(place & 0xFFFFFF00, return_counts=True)
     assert len(cus) == min(ncu, S) and counts.max() <= 4 and len(np.unique(place >> 16)) == 8, (len(cus), counts.max())
     b.close()
-    from oracle_pool import oracle_bytes_many
     want = oracle_bytes_many(kw, pcm, F * calls)
     bad = [s for s in range(S) if got[s] != want[s]]
     assert not bad, "%d of %d streams differ from the oracle, first: %s" % (len(bad), S, bad[:8])
@@ -508,7 +471,7 @@ def test_persistent_workgroups_walk_more_streams_than_slots_over_several_calls(m
     S, F, calls = 1600, 5, 3
     base = [synth.stream_pcm(7300 + u, F * calls, rho=RHOS[u % 4], bursts=True) for u in range(50)]
     pcm = np.stack([np.roll(base[i % 50], 1152 * (i // 50), axis=0) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     assert b.k6_variant() == 1 and b.resident_streams() < S
     got = [b"" for _ in range(S)]
     for c in range(calls):
@@ -517,7 +480,6 @@ def test_persistent_workgroups_walk_more_streams_than_slots_over_several_calls(m
             got[s] += out[s]
     assert b.status() == 0
     b.close()
-    from oracle_pool import oracle_bytes_many
     want = oracle_bytes_many(kw, pcm, F * calls)
     bad = [s for s in range(S) if got[s] != want[s]]
     assert not bad, "%d of %d streams differ from the oracle, first: %s" % (len(bad), S, bad[:8])
@@ -530,10 +492,10 @@ def test_pipelined_host_calls_equal_plain_host_calls():
     kw = dict(vbr_mnr=60)
     S, F, calls = 96, 10, 5
     pcm = np.stack([synth.stream_pcm(1200 + i, F * calls, rho=RHOS[i % 4], bursts=True) for i in range(S)])
-    b0 = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b0 = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     want = [b0.encode_host(pcm[:, c * F * 1152:(c + 1) * F * 1152]) for c in range(calls)]
     b0.close()
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     stride = b.out_stride(F)
     h_pcm = [torch.from_numpy(np.ascontiguousarray(pcm[:, c * F * 1152:(c + 1) * F * 1152])).pin_memory() for c in range(calls)]
     h_out = [torch.zeros((S, stride), dtype=torch.uint8).pin_memory() for _ in range(calls)]
@@ -547,7 +509,7 @@ def test_pipelined_host_calls_equal_plain_host_calls():
         for s in range(S):
             assert o[s, :n[s]].tobytes() == want[c][s], "call %d stream %d" % (c, s)
     # pageable memory works too (the copies just do not overlap)
-    b2 = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b2 = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     p_out = [np.zeros((S, stride), np.uint8) for _ in range(calls)]
     p_nb = [np.zeros((S,), np.int32) for _ in range(calls)]
     p_pcm = [np.ascontiguousarray(pcm[:, c * F * 1152:(c + 1) * F * 1152]) for c in range(calls)]
@@ -558,37 +520,6 @@ def test_pipelined_host_calls_equal_plain_host_calls():
         for s in range(0, S, 7):
             assert p_out[c][s, :p_nb[c][s]].tobytes() == want[c][s]
     b.close(); b2.close()
-
-
-def random_control(rng):
-    """a random but accepted E_CONTROL: rate, mode, CBR/VBR, -HF, DC filter, short-block threshold, tuning knobs"""
-    sr = int(rng.choice([44100, 48000, 32000, 22050, 24000, 16000]))
-    lsf = sr < 32000
-    kw = dict(samprate=sr, mode=int(rng.choice([0, 1, 1, 3])))
-    if rng.random() < 0.5:
-        kw["bitrate"] = int(rng.choice([24, 32, 40, 48, 56, 64, 80] if lsf else [48, 56, 64, 80, 96, 112, 128, 160]))
-    else:
-        kw["vbr_mnr"] = int(rng.integers(0, 151))
-        if rng.random() < 0.3:
-            kw["vbr_br_limit"] = int(rng.choice([40, 64, 96, 160]))
-        if rng.random() < 0.3:
-            kw["vbr_delta_mnr"] = int(rng.integers(-40, 51))
-    if not lsf and rng.random() < 0.3:
-        kw["hf_flag"] = int(rng.choice([1, 3]))
-        kw["freq_limit"] = int(rng.choice([17000, 19000, 22000, 24000]))
-    if rng.random() < 0.2:
-        kw["filter_select"] = 1
-    if rng.random() < 0.3:
-        kw["short_block_threshold"] = int(rng.choice([0, 100, 400, 99999]))
-    if rng.random() < 0.2:
-        kw["freq_limit"] = int(rng.choice([6000, 9000, 14000]))
-    if rng.random() < 0.2:
-        kw["test1"] = int(rng.integers(0, 12))
-    if rng.random() < 0.15:
-        kw["quick"] = 1
-    if rng.random() < 0.2:
-        kw["nsb_limit"] = int(rng.choice([2, 4, 6, 10, 14, 18, 22, 26, 30]))      # subband limit set by the caller
-    return kw
 
 
 def test_random_configurations_against_the_oracle():
@@ -605,7 +536,7 @@ def test_random_configurations_against_the_oracle():
         pcm = np.stack([synth.stream_pcm(3000 + 7 * trial + i, F, sr=sr, rho=RHOS[(trial + i) % 4], bursts=True) for i in range(S)])
         if mono:
             pcm = np.ascontiguousarray(pcm[:, :, 0])
-        b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+        b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
         cut = int(rng.integers(1, F))
         got = b.encode_host(pcm[:, :cut * 1152])
         got2 = b.encode_host(pcm[:, cut * 1152:])
@@ -627,7 +558,7 @@ def test_very_low_subband_limits(kw):
     line buffer, and lines past the coded range must still come out zero (found by the round-3 sweep, 3 cases in 2500)"""
     S, F = 6, 12
     pcm = np.stack([synth.stream_pcm(656405 + i, F, sr=kw["samprate"], rho=[1.0, 0.7, 0.0, 0.3][i % 4], bursts=(i % 2 == 0)) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     for s in range(S):
@@ -646,7 +577,7 @@ def test_band_21_lines_of_an_earlier_hf_pass_survive_the_rate_loop(kw, seed, rho
     pcm = synth.stream_pcm(seed, F, sr=44100, rho=rho, bursts=bursts)[None, :cut * 1152]
     if kw.get("mode") == 3:
         pcm = np.ascontiguousarray(pcm[:, :, 0])
-    b = api().Batch(api().default_control(**kw), nstreams=1, max_frames=cut)
+    b = api.Batch(api.default_control(**kw), nstreams=1, max_frames=cut)
     got = b.encode_host(pcm)
     assert b.status() == 0
     assert got[0] == oracle_bytes(kw, pcm[0], cut)
@@ -658,11 +589,11 @@ def test_reset_stream_starts_a_fresh_stream_in_a_running_batch():
     of that input, and the neighbouring streams carry on undisturbed"""
     kws = [dict(bitrate=64), dict(vbr_mnr=70), dict(bitrate=64, samprate=48000)]
     S, F = 6, 18
-    ctl = [api().default_control(**kws[i % 3]) for i in range(S)]
+    ctl = [api.default_control(**kws[i % 3]) for i in range(S)]
     srs = [kws[i % 3].get("samprate", 44100) for i in range(S)]
     first = np.stack([synth.stream_pcm(1500 + i, F, sr=srs[i], bursts=True) for i in range(S)])
     second = np.stack([synth.stream_pcm(1600 + i, F, sr=srs[i], bursts=True) for i in range(S)])
-    b = api().Batch(ctl, nstreams=S, max_frames=F)
+    b = api.Batch(ctl, nstreams=S, max_frames=F)
     out1 = b.encode_host(first)
     for i in (1, 2, 5):
         b.reset_stream(i)
@@ -683,11 +614,11 @@ def test_stream_checkpoint_resumes_in_another_batch():
     kw = dict(vbr_mnr=55)
     F1, F2 = 13, 17
     pcm = np.stack([synth.stream_pcm(1700 + i, F1 + F2, rho=RHOS[i % 4], bursts=True) for i in range(4)])
-    b1 = api().Batch(api().default_control(**kw), nstreams=4, max_frames=F1)
+    b1 = api.Batch(api.default_control(**kw), nstreams=4, max_frames=F1)
     out1 = b1.encode_host(pcm[:, :F1 * 1152])
     saved = [b1.get_stream_state(i) for i in range(4)]
     b1.close()
-    b2 = api().Batch(api().default_control(**kw), nstreams=6, max_frames=F2)
+    b2 = api.Batch(api.default_control(**kw), nstreams=6, max_frames=F2)
     place = [5, 0, 3, 2]        # stream i of the old batch goes to slot place[i]
     for i, slot in enumerate(place):
         b2.set_stream_state(slot, saved[i])
@@ -710,7 +641,7 @@ def test_float_input_and_dc_filter_mixed_batch():
     pcm += rng.uniform(-0.49, 0.49, pcm.shape).astype(np.float32)
     pcm[1] += 700.0         # a DC offset for the blocker to remove
     kws = [dict(bitrate=64, short_block_threshold=99999, filter_select=(i & 1)) for i in range(S)]
-    b = api().Batch([api().default_control(**k) for k in kws], nstreams=S, max_frames=F)
+    b = api.Batch([api.default_control(**k) for k in kws], nstreams=S, max_frames=F)
     got = b.encode_host(pcm[:, :12 * 1152])
     got2 = b.encode_host(pcm[:, 12 * 1152:])
     assert b.status() == 0
@@ -729,7 +660,7 @@ def test_golden_reference_streams(name):
     nfr = m["frames"]
     pcm = synth.stream_pcm(m["stream_seed"], nfr, sr=m["samprate"], rho=m["rho"], bursts=m["bursts"])
     pcm = np.concatenate([pcm, np.zeros((2 * 1152, 2), dtype=np.int16)])[None]
-    b = api().Batch(api().default_control(**m["control"]), nstreams=1, max_frames=nfr + 2)
+    b = api.Batch(api.default_control(**m["control"]), nstreams=1, max_frames=nfr + 2)
     got = b.encode_host(pcm)[0]
     assert got == open(os.path.join(GOLD, name + ".mp3frames"), "rb").read()
     b.close()
@@ -744,7 +675,7 @@ def test_extra_golden_reference_streams(name):
     import make_golden as M
     kw, nfr = M.EXTRA_CASES[name][0], M.EXTRA_CASES[name][2]
     pcm = np.concatenate([M.extra_case_pcm(name), np.zeros((2 * 1152, 2), dtype=np.int16)])
-    b = api().Batch(api().default_control(**kw), nstreams=3, max_frames=nfr + 2)
+    b = api.Batch(api.default_control(**kw), nstreams=3, max_frames=nfr + 2)
     got = b.encode_host(np.stack([pcm, pcm, pcm]))
     assert b.status() == 0
     want = open(os.path.join(GOLD, name + ".mp3frames"), "rb").read()
@@ -777,7 +708,7 @@ def test_every_stage_bit_exact(name):
     pcm = np.stack([synth.stream_pcm(200 + i, F, sr=sr, rho=RHOS[i % 4], bursts=bursts) for i in range(S)])
     if mono:
         pcm = pcm[:, :, 0]
-    tb = TapBatch(api(), kw, S, F, taps)        # (tests/stage_taps.py: the comparison itself, shared with test_gpu_dynamic_range.py)
+    tb = TapBatch(api, kw, S, F, taps)        # (tests/stage_taps.py: the comparison itself, shared with test_gpu_dynamic_range.py)
     tb.call(pcm)
     assert tb.frames == [F] * S and all(len(g) > 0 for g in tb.got)
     assert tb.msscan_paths == {"vector"} and tb.prep_granules > 0        # NG = 48: k_msscan's eight-granule loop (the scalar one: test_gpu_stage_taps.py)
@@ -792,7 +723,7 @@ def test_full_batch_configs_3_and_5(cfg):
     VBR -V100 -HF2 -F19000) and of config 5 (4096 streams,
     32 / 44.1 / 48 kHz by stream, CBR-128, correlation cycled) at full batch width with 256 distinct signals:
     frame structure of every stream, and byte equality with the oracle on a 16-stream subset."""
-    a = api()
+    a = api
     S, F = 4096, 32
     U = 252 if cfg == "config5_share" else 256  # distinct signals; a multiple of the class count (3) and of the correlation cycle (4)
     if cfg == "config3":
@@ -829,7 +760,7 @@ def test_config_4_share_at_full_length():
     one call (the 4096-stream configs otherwise run at 32 frames here and at full length only in bench.py's verify): 64
     distinct signals rotated in time, ALL 4096 streams byte for byte against the oracle on the low-footprint build (a 64-stream
     subset on the forced four-stream build), frame structure of every 97th stream"""
-    a = api()
+    a = api
     S, F, U = 4096, 128, 64
     kw, sr = dict(samprate=48000, vbr_mnr=100, hf_flag=3, freq_limit=19000), 48000
     base = [synth.stream_pcm(9900 + u, F, sr=sr, rho=RHOS[u % 4], bursts=True) for u in range(U)]
@@ -838,7 +769,6 @@ def test_config_4_share_at_full_length():
     got = b.encode_host(pcm)
     assert b.status() == 0
     assert b.k6_variant() == (1 if os.environ.get("HMP3AMD_K6", "slim") == "slim" else 0)      # beyond the resident set: the low-footprint build unless forced
-    from oracle_pool import oracle_bytes_many
     ids = list(range(S)) if os.environ.get("HMP3AMD_K6", "slim") == "slim" else list(range(1, S, 64))   # (the forced four-stream build: a 64-stream subset)
     want = oracle_bytes_many(kw, pcm, F, ids)
     bad = [s for s in ids if got[s] != want[s]]
@@ -862,7 +792,7 @@ def test_configs_3_and_5_at_full_length_on_the_low_footprint_build(cfg, monkeypa
     48 distinct signals rotated in time (86 rotation classes); ALL 4096 streams byte for byte against the oracle (a process per CPU:
     half a minute), every stream's status word"""
     monkeypatch.setenv("HMP3AMD_K6", "slim")
-    a = api()
+    a = api
     S, F, U = 4096, 256, 48
     classes = [(dict(), 44100)] if cfg == "config3" else [(dict(bitrate=64, samprate=32000), 32000), (dict(bitrate=64), 44100), (dict(bitrate=64, samprate=48000), 48000)]
     base = [synth.stream_pcm(9950 + u, F, sr=classes[u % len(classes)][1], rho=RHOS[u % 4], bursts=True) for u in range(U)]
@@ -872,7 +802,6 @@ def test_configs_3_and_5_at_full_length_on_the_low_footprint_build(cfg, monkeypa
     assert b.k6_variant() == 1
     got = b.encode_host(pcm)
     assert b.status() == 0
-    from oracle_pool import oracle_bytes_many
     ids = list(range(S))
     want = oracle_bytes_many([classes[(s % U) % len(classes)][0] for s in range(S)], pcm, F, ids)
     bad = [s for s in ids if got[s] != want[s]]
@@ -885,10 +814,10 @@ def test_ragged_calls_equal_one_shot():
     kw = CONFIGS["vbr50_sw"]       # block switching on: the carry includes detector and block-type state
     S, F = 5, 32
     pcm = np.stack([synth.stream_pcm(300 + i, F, rho=RHOS[i % 4], bursts=True) for i in range(S)])
-    one = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    one = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     ref = one.encode_host(pcm)
     one.close()
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=24)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=24)
     parts = [b"" for _ in range(S)]
     pos = 0
     for n in (1, 7, 24):
@@ -902,7 +831,7 @@ def test_ragged_calls_equal_one_shot():
 
 def test_mixed_configuration_classes_in_one_batch():
     """per-stream E_CONTROL: 32 / 44.1 / 48 kHz and CBR / VBR side by side (config 5 style)"""
-    a = api()
+    a = api
     kws = [dict(bitrate=64, samprate=32000), dict(bitrate=64), dict(bitrate=64, samprate=48000), dict(),
            dict(bitrate=96, mode=0, short_block_threshold=99999)]
     S, F = 10, 24
@@ -922,7 +851,7 @@ def test_edge_inputs_silence_fullscale_single_stream():
     fs = np.stack([sq, (-sq.astype(np.int32) - 1).astype(np.int16)], axis=1)
     imp = z.copy(); imp[5000, 0] = 32767; imp[9000, 1] = -32768
     pcm = np.stack([z, fs, imp])
-    b = api().Batch(api().default_control(**kw), nstreams=3, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=3, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     for s in range(3):
@@ -968,7 +897,7 @@ def test_stress_signals_rare_paths(name, kw):
     seg = np.concatenate([x[i * 4608:(i + 1) * 4608] for i, x in enumerate([noise, lowtone, clicks, nyq, anti, dc, panned, noise, lowtone] * 2)])[:n]
     pcm = np.stack([noise, lowtone, nyq, dc, clicks, panned, anti, seg])
     S = pcm.shape[0]
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     before = O.path_counts()
@@ -987,7 +916,7 @@ def test_long_run_many_ragged_calls(kw):
     sr = kw.get("samprate", 44100)
     F = 1500
     pcm = np.stack([synth.stream_pcm(40 + i, F, sr=sr, rho=RHOS[i % 4], bursts=(i & 1) == 1) for i in range(3)])
-    b = api().Batch(api().default_control(**kw), nstreams=3, max_frames=37)
+    b = api.Batch(api.default_control(**kw), nstreams=3, max_frames=37)
     rng = np.random.default_rng(3)
     got = [b"", b"", b""]
     f = 0
@@ -1015,7 +944,7 @@ def test_one_call_longer_than_the_flag_staging_block(kw):
     sr = kw.get("samprate", 44100)
     S, F = 4, 300
     pcm = np.stack([synth.stream_pcm(900 + i, F, sr=sr, rho=RHOS[i % 4], bursts=True) for i in range(S)])
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     got = b.encode_host(pcm)
     assert b.status() == 0
     for s in range(S):
@@ -1038,7 +967,7 @@ def test_device_pcm_pointer_without_16_byte_alignment(kw):
     off = 1 if mono else 2                      # int16 elements
     flat[off:off + pcm.size] = torch.from_numpy(pcm.reshape(-1)).to(dev)
     assert (flat.data_ptr() + 2 * off) % 16 != 0
-    b = api().Batch(api().default_control(**kw), nstreams=S, max_frames=F)
+    b = api.Batch(api.default_control(**kw), nstreams=S, max_frames=F)
     stride = b.out_stride(F)
     d_out = torch.zeros((S, stride), dtype=torch.uint8, device=dev); d_nb = torch.zeros((S,), dtype=torch.int32, device=dev)
     torch.cuda.synchronize()
@@ -1052,7 +981,7 @@ def test_device_pcm_pointer_without_16_byte_alignment(kw):
 
 
 def test_api_misuse_fails_loudly_and_leaves_the_batch_usable():
-    a = api()
+    a = api
     with pytest.raises(RuntimeError):           # mono and stereo streams cannot share a batch
         a.Batch([a.default_control(bitrate=64), a.default_control(bitrate=64, mode=3)], nstreams=2, max_frames=4)
     with pytest.raises(RuntimeError):           # streams of the two allocator generations cannot share a batch
@@ -1081,7 +1010,7 @@ def test_api_misuse_fails_loudly_and_leaves_the_batch_usable():
 
 def test_cmp3enc_surface_single_stream():
     """the CMp3Enc-compatible entry points: init return values, per-frame encode, getters"""
-    a = api()
+    a = api
     kw = CONFIGS["cbr128"]
     F = 12
     pcm = synth.stream_pcm(500, F)
@@ -1118,7 +1047,7 @@ def test_per_frame_graph_calls_never_hand_back_stale_results():
     or stale bytes - copies complete in order on the device, their writes do not land in order in host memory.)  200 encoders x
     40 calls of an MPEG-2 mono VBR stream (two frames per call, sizes that change from call to call, so a stale byte count
     shows) against the oracle, every call's bytes."""
-    a = api()
+    a = api
     kw = dict(samprate=24000, mode=3, vbr_mnr=15, short_block_threshold=2000)
     F = 40
     pcm = synth.stream_pcm(377305, F, sr=24000, rho=0.0, bursts=True)[:, 0].copy()
@@ -1136,7 +1065,7 @@ def test_per_frame_graph_calls_never_hand_back_stale_results():
 def test_full_size_config2_properties():
     """BASELINE configs[1] at full size (1024 streams x 256 frames): frame structure, padding
     sequence, determinism, and byte equality with the oracle on a random subset of streams."""
-    a = api()
+    a = api
     kw = CONFIGS["cbr128"]
     S, F = 1024, 256
     # 1024 distinct signals, synthesised on the GPU by the bench's own generator (the host one takes 0.2 s per stream)
@@ -1162,7 +1091,6 @@ def test_full_size_config2_properties():
         assert abs(sum(pads) / len(pads) - (144000 * 128 % 44100) / 44100.0) < 0.02
     assert len(set(got)) == S      # distinct signals give distinct streams
     # every one of the 1024 streams byte for byte against the oracle (a process per CPU: seconds)
-    from oracle_pool import oracle_bytes_many
     want = oracle_bytes_many(kw, pcm, F)
     bad = [s for s in range(S) if got[s] != want[s]]
     assert not bad, "%d of %d streams differ from the oracle, first: %s" % (len(bad), S, bad[:8])

@@ -8,27 +8,19 @@ calls write into zeroed rows, so the streams' checkpoints can be compared across
 they are not: a stream's ring of pending main data keeps the bytes that lie behind its frames in the call's row, and a host
 call's rows are device staging that nobody zeroes).
 k_pcm_spread's chunk is 16 KB (HX_PCM_CHUNK), the size the chunk-edge test's segments are chosen for."""
-import ctypes as C
 import functools
 
 import numpy as np
 import pytest
 
-from hmp3_amd import synth
+import gpu_support as G
+from gpu_support import CallBufs, Pinned, controls, states, sync
+from hmp3_amd import api, synth
 
 pytestmark = pytest.mark.gpu
 POISON = {np.dtype(np.int16): 0x7FFF, np.dtype(np.float32): np.nan}
 FILL = 0xA5
 STEREO, MONO = dict(bitrate=64), dict(bitrate=64, mode=3)
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def controls(menu):
-    return [api().default_control(**kw) for kw in menu]
 
 
 @functools.lru_cache(maxsize=None)
@@ -91,42 +83,20 @@ def spaced(parts, residues, dtype, descending=False):
     return off, int(at + 64)
 
 
-class Dev:
-    """one device call's buffers: the PCM (`shift` elements past a 16-byte boundary) and zeroed rows / byte counts of -1"""
+def call(b, pcm, nf, shift=0, submit=False):
+    """one device call - or submit - on the null stream: the PCM `shift` elements past a 16-byte boundary, zeroed rows"""
+    return G.device_call(b, pcm, nf, CallBufs(b, nf), submit=submit, stream=None, shift=shift)
 
-    def __init__(self, b, pcm, nf, shift=0):
-        import torch
-        dev = torch.device("cuda:0")
-        flat = np.array(pcm).reshape(-1)
-        self.pcm = torch.zeros(flat.size + 16, dtype=torch.from_numpy(flat[:0]).dtype, device=dev)
-        self.pcm[shift:shift + flat.size] = torch.from_numpy(flat).to(dev)
-        self.ptr = self.pcm.data_ptr() + shift * flat.itemsize
-        assert self.pcm.data_ptr() % 16 == 0
-        self.nf, self.f32, self.stride = nf, flat.dtype == np.float32, b.out_stride(nf)
-        self.out = torch.zeros((b.n, self.stride), dtype=torch.uint8, device=dev)
-        self.nb = torch.full((b.n,), -1, dtype=torch.int32, device=dev)
-        torch.cuda.synchronize()
 
-    def call(self, b, submit=False):
-        (b.submit_device if submit else b.encode_device)(self.ptr, self.nf, self.out.data_ptr(), self.stride, self.nb.data_ptr(), None, f32=self.f32)
-        return self
-
-    def result(self):
-        import torch
-        torch.cuda.synchronize()
-        o, nb = self.out.cpu().numpy(), self.nb.cpu().numpy()
-        assert (nb >= 0).all(), "a byte count was not written"
-        return [o[s, :nb[s]].tobytes() for s in range(len(nb))]
+def result(o):
+    sync()
+    return o.bitstreams()
 
 
 def device_call(b, pcm, nf, shift=0):
-    r = Dev(b, pcm, nf, shift).call(b).result()
+    r = result(call(b, pcm, nf, shift))
     assert b.status() == 0
     return r
-
-
-def states(b):
-    return b.get_stream_states(range(b.n))
 
 
 def host_crc_call(b, pcm, nf):
@@ -135,7 +105,7 @@ def host_crc_call(b, pcm, nf):
     out, nb = np.full((b.n, stride), FILL, np.uint8), np.full(b.n, -1, np.int32)
     st, cr = np.full((b.n, nf, 2), -1, np.int32), np.full((b.n, nf), 0xFFFF, np.uint16)
     pcm = np.ascontiguousarray(pcm, dtype=np.float32)
-    rc = api().lib().hx_batch_encode_f32_host_crc(b.h, pcm.ctypes.data, nf, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data, cr.ctypes.data)
+    rc = api.lib().hx_batch_encode_f32_host_crc(b.h, pcm.ctypes.data, nf, out.ctypes.data, stride, nb.ctypes.data, st.ctypes.data, cr.ctypes.data)
     return rc, out, nb, st, cr
 
 
@@ -144,7 +114,7 @@ def test_tight_layout_of_a_uniform_batch_equals_rows_call_after_call(f32):
     """6 stereo 44.1 kHz CBR-128 streams, three device calls of 3 frames fed the tight image: rows and byte counts of every
     call equal the twin's - from the second call on that also holds the PCM history k_msscan carries to the spread rows - and
     so does every stream's checkpoint at the end"""
-    a = api()
+    a = api
     dtype, S, nf = (np.float32 if f32 else np.int16), 6, 3
     b, t = (a.Batch(a.default_control(**STEREO), nstreams=S, max_frames=nf) for _ in range(2))
     feed = Feed([2] * S, 9, dtype)
@@ -165,7 +135,7 @@ def test_counts_and_channels_through_the_host_crc_call():
     """the command line's call: a mixed batch of 8 slots alternating stereo and mono under per-stream counts, fed the tight
     fp32 image through hx_batch_encode_f32_host_crc - rows, out_bytes, frame counters and CRCs equal the twin's, and the host
     rows of the streams that sit a call out are untouched"""
-    a = api()
+    a = api
     S, nf, ch = 8, 3, [2, 1] * 4
     b, t = (a.Batch.mixed(controls([STEREO, MONO]), S, cfg=[0, 1] * 4, max_frames=nf) for _ in range(2))
     feed = Feed(ch, 8, np.float32)
@@ -197,7 +167,7 @@ def test_every_alignment_residue_of_a_segment_start(f32, shift):
     """8 streams whose segments start 0, 2, .. 14 bytes (int16; fp32: 0, 4, 8, 12 twice) past a 16-byte boundary of the image,
     with poisoned gaps between them - and once more with the device image's base itself one sample past a 16-byte boundary,
     which moves every residue on: aligned loads, every word residue of the funnel and, for int16, the half-word ones"""
-    a = api()
+    a = api
     dtype, S, nf = (np.float32 if f32 else np.int16), 8, 2
     b, t = (a.Batch(a.default_control(**STEREO), nstreams=S, max_frames=nf) for _ in range(2))
     parts = Feed([2] * S, nf, dtype, seed=920).take([nf] * S)
@@ -213,7 +183,7 @@ def test_every_alignment_residue_of_a_segment_start(f32, shift):
 def test_chunk_edges_of_the_spread():
     """a max_frames = 32 int16 batch whose segments are 2304 B (one mono frame: less than a 16 KB chunk), 16128 B (7 mono
     frames: just under one), 18432 B (4 stereo frames: just over) and 147456 B (32 stereo frames: exactly nine chunks)"""
-    a = api()
+    a = api
     nf, ch, counts = 32, [1, 1, 2, 2], [1, 7, 4, 32]
     b, t = (a.Batch.mixed(controls([STEREO, MONO]), 4, cfg=[1, 1, 0, 0], max_frames=nf) for _ in range(2))
     parts = Feed(ch, 32, np.int16, seed=930).take(counts)
@@ -235,7 +205,7 @@ def test_no_store_lands_behind_a_segment_or_in_another_row():
     """the "pcmrows" tap: call A at full counts, then call B with smaller counts and other samples - every row holds B's
     segment in its first len_i bytes and, from there to its end, exactly what call A left there; the row of a stream that
     sits B out is A's whole"""
-    a = api()
+    a = api
     S, nf, ch = 6, 3, [2, 1, 2, 1, 2, 1]
     b = a.Batch.mixed(controls([STEREO, MONO]), S, cfg=[0, 1] * 3, max_frames=nf)
     feed = Feed(ch, 6, np.int16, seed=940)
@@ -262,7 +232,7 @@ def test_no_store_lands_behind_a_segment_or_in_another_row():
 def test_gaps_descending_order_and_a_shared_segment():
     """segments in descending order with poisoned gaps between them, and two slots of the same control reading one segment:
     they emit identical rows, and all equal the twin's"""
-    a = api()
+    a = api
     S, nf = 4, 3
     b, t = (a.Batch(a.default_control(**STEREO), nstreams=S, max_frames=nf) for _ in range(2))
     parts = Feed([2] * S, nf, np.float32, seed=950).take([nf] * S)
@@ -277,25 +247,14 @@ def test_gaps_descending_order_and_a_shared_segment():
     b.close(), t.close()
 
 
-PINNED = []
-
-
-def pinned(arr):
-    """a copy of arr in page-locked host memory (kept until the module's teardown releases it)"""
-    L = api().lib()
-    p = L.hx_pinned_alloc(max(arr.nbytes, 16))
-    assert p
-    PINNED.append(p)
-    v = np.frombuffer((C.c_ubyte * arr.nbytes).from_address(p), dtype=arr.dtype).reshape(arr.shape)
-    v[...] = arr
-    return v
+PIN = Pinned()         # (kept until the module's teardown releases it)
+pinned = PIN.copy
 
 
 @pytest.fixture(scope="module", autouse=True)
 def _release_pinned():
     yield
-    while PINNED:
-        api().lib().hx_pinned_free(PINNED.pop())
+    PIN.free()
 
 
 SUBMITS = [[3, 1, 0, 2, 3, 2], [1, 3, 2, 0, 1, 3], [2, 0, 3, 3, 0, 1]]
@@ -306,7 +265,7 @@ def test_segments_travel_with_their_submit():
     under other counts and offsets, the setters called between the submits while the earlier ones are in flight - the rows
     of all six equal the twin's, which makes the same submits fed rows"""
     import torch
-    a = api()
+    a = api
     S, nf, ch = 6, 3, [2, 1] * 3
     b, t = (a.Batch.mixed(controls([STEREO, MONO]), S, cfg=[0, 1] * 3, max_frames=nf) for _ in range(2))
     stride = b.out_stride(nf)
@@ -335,14 +294,14 @@ def test_segments_travel_with_their_submit():
         off, total = spaced(parts, [2 * ((i + 3 * c) % 8) for i in range(S)], np.int16, descending=c == 2)
         b.frame_counts(counts), t.frame_counts(counts)
         b.pcm_segments(off, total)
-        got.append(Dev(b, image_of(parts, off, total, np.int16), nf).call(b, submit=True))
-        want.append(Dev(t, rows_of(parts, nf, 2, np.int16), nf).call(t, submit=True))
+        got.append(call(b, image_of(parts, off, total, np.int16), nf, submit=True))
+        want.append(call(t, rows_of(parts, nf, 2, np.int16), nf, submit=True))
     b.pcm_segments(None)
     b.wait(None), t.wait(None)
     torch.cuda.synchronize()
     for c in range(3):
-        r = got[c].result()
-        assert r == want[c].result() and sum(len(x) for x in r) > 0, "device submit %d" % c
+        r = result(got[c])
+        assert r == result(want[c]) and sum(len(x) for x in r) > 0, "device submit %d" % c
     assert b.status() == 0 and t.status() == 0      # (checkpoints: not compared behind host submits, see above)
     b.close(), t.close()
 
@@ -350,7 +309,7 @@ def test_segments_travel_with_their_submit():
 @pytest.mark.parametrize("f32", [False, True], ids=["s16", "f32"])
 def test_the_dc_blocker_reads_the_spread_rows(f32):
     """a batch with filter_select = 1 streams (k_dcfilter in front of the polyphase), under counts, two calls"""
-    a = api()
+    a = api
     dtype, nf, counts = (np.float32 if f32 else np.int16), 3, [[3, 1, 2, 0], [1, 3, 0, 2]]
     menu = [dict(bitrate=64, filter_select=1), STEREO, dict(bitrate=64, filter_select=1), STEREO]
     b, t = (a.Batch(controls(menu), max_frames=nf) for _ in range(2))
@@ -369,7 +328,7 @@ def test_the_dc_blocker_reads_the_spread_rows(f32):
 @pytest.mark.one_k6_build
 def test_a_batch_of_an_mpeg1_and_an_mpeg2_entry():
     """hx_batch_create_any with an MPEG-1 and an MPEG-2 entry (two frames per block there), one of them mono, under counts"""
-    a = api()
+    a = api
     nf, menu, cfg = 3, [STEREO, dict(bitrate=32, samprate=22050), dict(bitrate=32, samprate=22050, mode=3)], [0, 1, 2, 1, 0]
     b, t = (a.Batch.any(controls(menu), 5, cfg=cfg, max_frames=nf) for _ in range(2))
     ch = [b.stream_channels(i) for i in range(5)]
@@ -389,7 +348,7 @@ def test_a_batch_of_an_mpeg1_and_an_mpeg2_entry():
 def test_multi_blocks_read_one_image():
     """hx_multi_pcm_segments: 5 streams of a mixed menu in two blocks (3 + 2) on device 0; the offsets address the caller's
     one image, each block copies its own span, and every block's result equals the twin's"""
-    a = api()
+    a = api
     nf, cfg = 3, [0, 1, 1, 0, 1]
     m, t = (a.Multi.mixed(controls([STEREO, MONO]), 5, cfg=cfg, max_frames=nf, devices=[0, 0]) for _ in range(2))
     assert [m.shard(k)[1:] for k in range(2)] == [(0, 3), (3, 2)]
@@ -423,7 +382,7 @@ def test_refusals_name_the_stream_and_leave_the_batch_usable():
     """an offset that is no multiple of the sample size, a segment that ends beyond in_bytes and a negative offset are each
     refused with the stream's number, by the device and by the host call; the offset of a stream that takes no frame is not
     looked at; after every refusal the batch encodes the twin's bytes, and pcm_segments(None) restores rows"""
-    a = api()
+    a = api
     S, nf = 4, 2
     b, t = (a.Batch(a.default_control(**STEREO), nstreams=S, max_frames=nf) for _ in range(2))
     feed = Feed([2] * S, 8, np.float32, seed=1010)
@@ -459,7 +418,7 @@ def test_refusals_name_the_stream_and_leave_the_batch_usable():
 
 @pytest.mark.one_k6_build
 def test_a_converting_batch_takes_no_segments():
-    a = api()
+    a = api
     sb = a.SrcBatch(a.default_control(bitrate=64, samprate=48000), a.Source(16, 0, 0, 0), nstreams=2, max_frames=2)
     with pytest.raises(RuntimeError, match="converting batch"):
         sb.pcm_segments([0, 4608], 9216)

@@ -9,29 +9,18 @@ import sys
 import numpy as np
 import pytest
 
+from gpu_support import GOLD, GOLDEN_CLI as M, REF_CLI, ROOT, oracle_bytes, run_cli
 from oracle import oracle as O
-from hmp3_amd import synth
+from hmp3_amd import api, synth
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GOLD = os.path.join(ROOT, "tests", "golden")
 RHOS = [0.7, 0.0, 1.0, 0.3]
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def oracle_bytes(kw, pcm, nfr):
-    enc = O.OracleEncoder(O.default_control(**kw))
-    return b"".join(enc.encode_s16(pcm[f * 1152:(f + 1) * 1152]) for f in range(nfr))
 
 
 def test_multi_device_dispatcher_blocks_streams_and_matches_oracle():
     """hx_multi_*: 7 streams in 3 contiguous blocks (3 + 2 + 2), one host thread per block.  On a one-GPU box the
     three blocks are three batches on device 0 - the host-side dispatch is the same."""
-    a = api()
+    a = api
     kws = [dict(bitrate=64), dict(vbr_mnr=60), dict(bitrate=96, short_block_threshold=99999)]
     S, F = 7, 10
     pcm = np.stack([synth.stream_pcm(3100 + i, F, rho=RHOS[i % 4], bursts=True) for i in range(S)])
@@ -53,7 +42,7 @@ def test_multi_device_dispatcher_blocks_streams_and_matches_oracle():
 
 
 def test_checkpoint_blob_is_refused_under_another_configuration_or_size():
-    a = api()
+    a = api
     b1 = a.Batch(a.default_control(bitrate=64), nstreams=1, max_frames=4)
     b1.encode_host(synth.stream_pcm(1, 4)[None])
     blob = b1.get_stream_state(0)
@@ -70,7 +59,7 @@ def test_checkpoint_blob_is_refused_under_another_configuration_or_size():
 
 
 def test_host_entry_points_check_arguments_before_touching_the_device():
-    a = api()
+    a = api
     L = a.lib()
     b = a.Batch(a.default_control(bitrate=64), nstreams=2, max_frames=4)
     pcm = np.zeros((2, 4 * 1152, 2), np.int16)
@@ -197,15 +186,11 @@ def test_bench_dump_outputs_repeat_and_agree_with_the_line(tmp_path):
 def test_cli_streams_from_a_pipe_with_bounded_buffers(name, tmp_path):
     """`hmp3amd - out.mp3`: the input arrives on a pipe and is encoded frame by frame through a sliding window
     (memory independent of the input length); the file equals the one the reference CLI wrote from the WAV."""
-    sys.path.insert(0, GOLD)
-    import make_golden_cli as M
     seed, nsamp, sr, as_float, bursts, flags = M.CASES[name]
     wav, mp3 = str(tmp_path / "in.wav"), str(tmp_path / "out.mp3")
     M.write_wav(wav, M.case_pcm(name), sr, as_float, M.CONTAINER.get(name))
-    cli = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
     with open(wav, "rb") as f:
-        r = subprocess.run([cli, "-", mp3] + flags + ["-EC"], stdin=f, capture_output=True)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
+        r = run_cli(["-", mp3] + flags + ["-EC"], stdin=f, timeout=None)
     assert b"ec->samprate" in r.stderr            # -EC prints the settings in use
     assert open(mp3, "rb").read() == open(os.path.join(GOLD, name + ".mp3"), "rb").read()
 
@@ -343,7 +328,7 @@ def test_host_submit_behind_device_submits_sees_their_carried_frames():
     the incomplete frames' images into the stream state) goes out on the packing stream, and the host submit's own
     packing must wait for it (a missing wait let k_pack_pre read stale images)."""
     import torch
-    a = api()
+    a = api
     S, F, calls = 6, 4, 6
     kw = dict(bitrate=64)
     pcm = np.stack([synth.stream_pcm(9900 + i, F * calls, rho=RHOS[i % 4], bursts=True) for i in range(S)])
@@ -382,27 +367,24 @@ def test_host_submit_behind_device_submits_sees_their_carried_frames():
 def test_cli_mnr_adjust_file_switch(tmp_path):
     """-W<file> (test/tomp3.cpp:552-555, get_mnr_adjust): 21 per-band offsets, clamped to +-200 and echoed; the reference
     encoder never reads them (bitallo3.cpp:441 is commented out), so the file equals the one written without the switch"""
-    sys.path.insert(0, GOLD)
-    import make_golden_cli as M
     name = "cli_cbr128_s16_44k"
     seed, nsamp, sr, as_float, bursts, flags = M.CASES[name]
     wav, mp3, adj = str(tmp_path / "in.wav"), str(tmp_path / "out.mp3"), str(tmp_path / "adj.txt")
     M.write_wav(wav, M.case_pcm(name), sr, as_float, M.CONTAINER.get(name))
     open(adj, "w").write("10 -300 250 7\n")
-    r = subprocess.run([os.path.join(ROOT, "hmp3_amd", "hmp3amd"), wav, mp3] + flags + ["-W" + adj], capture_output=True)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
+    r = run_cli([wav, mp3] + flags + ["-W" + adj], timeout=None)
     assert b"MNR adjust  10 -200 200 7 0 0" in r.stderr
     assert open(mp3, "rb").read() == open(os.path.join(GOLD, name + ".mp3"), "rb").read()
 
 
 def _ndev():
-    return api().lib().hx_device_count()
+    return api.lib().hx_device_count()
 
 
 @pytest.mark.skipif("_ndev() < 2", reason="needs two physical GPUs")
 def test_multi_device_dispatcher_on_two_physical_gpus():
     """the same dispatcher over two real devices (skipped on a one-GPU box): blocks on device 0 and 1, bytes against the oracle"""
-    a = api()
+    a = api
     kw = dict(bitrate=64)
     S, F = 9, 12
     pcm = np.stack([synth.stream_pcm(4100 + i, F, rho=RHOS[i % 4], bursts=True) for i in range(S)])
@@ -426,7 +408,7 @@ def test_bench_two_ranks_on_two_physical_gpus():
     assert len(line["roofline"]["kernel_ms_per_rank"]) == 2
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(ROOT, "oracle", "_ref", "hmp3")), reason="oracle/_ref/hmp3 (the reference's CLI, prebuilt) not present")
+@pytest.mark.skipif(not os.path.exists(REF_CLI), reason="oracle/_ref/hmp3 (the reference's CLI, prebuilt) not present")
 def test_fuzz_cli_slice_against_the_reference_binary():
     """a slice of tools/fuzz_cli.py: random WAVs (rates incl. the converter's, sample formats, containers) x random flags,
     hmp3amd against the reference's own command line, whole files.  (The sweep found the reference's conditional
@@ -438,7 +420,7 @@ def test_fuzz_cli_slice_against_the_reference_binary():
 def test_stream_walk_build_is_chosen_by_batch_size_and_both_give_the_same_bytes(monkeypatch):
     """more streams than the chip holds at once -> k_alloc_slim (six streams per CU), otherwise k_alloc (four);
     HMP3AMD_K6 overrides.  The same PCM through both builds: identical bytes, identical to the oracle."""
-    a = api()
+    a = api
     kw = dict(bitrate=64)
     monkeypatch.delenv("HMP3AMD_K6", raising=False)
     small = a.Batch(a.default_control(**kw), nstreams=64, max_frames=4)
@@ -481,7 +463,7 @@ def test_host_placement_helpers_are_best_effort_and_harmless(k6_build):
     """hx_device_numa_node / hx_bind_thread_to_device: the node of device 0 (or -1), and binding the calling thread to its
     CPUs never enlarges the thread's CPU set and leaves it usable (bench.py does this in every rank before it allocates
     page-locked buffers); an encode afterwards still matches the oracle"""
-    a = api()
+    a = api
     before = os.sched_getaffinity(0)
     try:
         node = a.device_numa_node(0)

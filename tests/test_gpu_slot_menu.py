@@ -7,34 +7,22 @@ starts a new encoder of the assigned entry's control.  Rows, frame counters and 
 equality; converting batches against the reference's MP3_audio_encode loop where oracle/_ref is built, else against this
 library's one-stream encoder."""
 import ctypes as C
-import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
 import packet_cases as PC
-from oracle import oracle as O
-from hmp3_amd import synth
 from conftest import skip_unless_host_libm_is_the_restated_one
+from gpu_support import batch_vs_single_vs_reference, controls, host_crc, ints, oracle_bytes, states, write_wav
+from hmp3_amd import api, synth
+from oracle import oracle as O
+from src_cases import Stream, ref_converted, run
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 S, MAXF = 6, 7
 # 44.1 kHz CBR-128 joint stereo, 48 kHz VBR-50, 32 kHz CBR-96 (the odd-partition rate), 44.1 kHz CBR-128 behind the DC blocker
 MENU = [dict(bitrate=64), dict(vbr_mnr=50, samprate=48000), dict(bitrate=48, samprate=32000), dict(bitrate=64, filter_select=1)]
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
-
-
-def host_crc(data):
-    data = bytes(data)
-    return int(api().lib().hx_xing_update_crc(0, data, len(data)))
 
 
 def life_pcm(seed, kw, F=24):
@@ -105,16 +93,8 @@ class Slots:
             L.pos = p + n
 
 
-def controls(menu):
-    return [api().default_control(**kw) for kw in menu]
-
-
 def menu_batch(menu, cfg=None, n=S, max_frames=MAXF):
-    return api().Batch.menu(controls(menu), n, cfg=cfg, max_frames=max_frames)
-
-
-def blobs(b, idx=None):
-    return b.get_stream_states(range(b.n) if idx is None else idx)
+    return api.Batch.menu(controls(menu), n, cfg=cfg, max_frames=max_frames)
 
 
 def same_but_class(a, b):
@@ -132,29 +112,29 @@ def test_assign_equals_a_fresh_stream(k6_build):
     sl = Slots(b, MENU, [0] * S, 3000)
     for c, counts in enumerate([[3, 2, 0, 4, 3, 1], [2, 4, 1, 0, 3, 2]]):
         idle = [i for i in range(S) if counts[i] == 0]
-        before = blobs(b, idle)
+        before = states(b, idle)
         sl.call(counts, 4, "call %d" % c)
-        assert blobs(b, idle) == before, "a slot that sat call %d out changed" % c
-    before = blobs(b)
+        assert states(b, idle) == before, "a slot that sat call %d out changed" % c
+    before = states(b)
     sl.assign([4, 1], [2, 3])
-    after = blobs(b)
+    after = states(b)
     # ... a new menu batch whose slots start on those entries, and slot 0 of a batch created with the entry's control alone
     # (whose class index, the first word of the stream record, is that batch's own numbering: 0)
     new = menu_batch(MENU, cfg=[0, 3, 0, 0, 2, 0])
-    fresh = blobs(new)
+    fresh = states(new)
     new.close()
     for i in range(S):
         assert after[i] == (fresh[i] if i in (4, 1) else before[i]), i
     for i, c in ((4, 2), (1, 3)):
-        one = api().Batch(api().default_control(**MENU[c]), nstreams=1, max_frames=MAXF)
+        one = api.Batch(api.default_control(**MENU[c]), nstreams=1, max_frames=MAXF)
         alone = one.get_stream_state(0)
         one.close()
         assert same_but_class(after[i], alone), i
     for c, counts in enumerate([[1, 3, 2, 4, 0, 3], [4, 0, 3, 1, 4, 2], [2, 2, 2, 0, 3, 1]]):
         idle = [i for i in range(S) if counts[i] == 0]
-        before = blobs(b, idle)
+        before = states(b, idle)
         sl.call(counts, 4, "call %d after the assign" % c)
-        assert blobs(b, idle) == before
+        assert states(b, idle) == before
     for i in range(S):
         assert b.frames_bytes(i) == sl.life[i].counters(sl.life[i].pos), i
     b.close()
@@ -163,11 +143,6 @@ def test_assign_equals_a_fresh_stream(k6_build):
 def s16_life(seed, kw, F):
     x = synth.stream_pcm(seed, 24, sr=kw.get("samprate", 44100), bursts=True)[9 * 1152:(9 + F) * 1152]
     return np.ascontiguousarray(x)
-
-
-def oracle_s16(kw, pcm):
-    enc = O.OracleEncoder(O.default_control(**kw))
-    return b"".join(enc.encode_s16(pcm[f * 1152:(f + 1) * 1152]) for f in range(len(pcm) // 1152))
 
 
 @pytest.mark.parametrize("counts", [False, True], ids=["uniform", "per_stream_counts"])
@@ -208,12 +183,12 @@ def test_assign_between_pipelined_submits_without_a_wait(counts, k6_build):
         o, n = d_out[c].cpu().numpy(), d_nb[c].cpu().numpy()
         got.append([o[s, :n[s]].tobytes() for s in range(S)])
     for i in range(S):
-        first = oracle_s16(MENU[0], a1[i][:n1[i] * 1152])
+        first = oracle_bytes(MENU[0], a1[i][:n1[i] * 1152])
         assert got[0][i] == first, i
         if i in idx:
-            assert got[1][i] == oracle_s16(MENU[second[i]], a2[i][:n2[i] * 1152]), i
+            assert got[1][i] == oracle_bytes(MENU[second[i]], a2[i][:n2[i] * 1152]), i
         else:
-            both = oracle_s16(MENU[0], np.concatenate([a1[i][:n1[i] * 1152], a2[i][:n2[i] * 1152]]))
+            both = oracle_bytes(MENU[0], np.concatenate([a1[i][:n1[i] * 1152], a2[i][:n2[i] * 1152]]))
             assert both[:len(first)] == first and got[1][i] == both[len(first):], i
     b.close()
 
@@ -227,14 +202,14 @@ def test_assign_to_the_present_entry_is_reset_streams(k6_build):
     twins = [Slots(menu_batch(MENU, cfg), MENU, cfg, 3300) for _ in range(2)]
     for t in twins:
         t.call([3, 4, 2, 4, 1, 3], 4, "first call")
-    before = [blobs(t.b) for t in twins]
+    before = [states(t.b) for t in twins]
     idx = [5, 0, 2]
     twins[0].b.reset_streams(idx)
     twins[0].started(idx, [cfg[i] for i in idx])
     twins[1].assign(idx, [cfg[i] for i in idx])
-    after = [blobs(t.b) for t in twins]
+    after = [states(t.b) for t in twins]
     new = menu_batch(MENU, cfg)
-    fresh = blobs(new)
+    fresh = states(new)
     new.close()
     for i in range(S):
         for k in range(2):
@@ -281,7 +256,6 @@ def converting_menu():
 
 
 def src_stream(entry, seed):
-    from test_gpu_src_batch import Stream
     rate, bits, is_float, target = converting_menu()[entry]
     return Stream(rate, bits, is_float, mpeg_select=target, seed=seed, seconds=1.0)
 
@@ -296,8 +270,7 @@ def test_converting_batch():
     take two-stage plans (another one: the previous occupant's carried samples are in place and must not be read).  The
     schedule answers as on a new batch, in_used restarts, the bytes are the reference's, and the first call's converted PCM
     is the reference converter's"""
-    from test_gpu_src_batch import ref_converted, run
-    A = api()
+    A = api
     entries = [src_stream(k, 70 + k) for k in range(4)]
     b = A.SrcBatch.menu([s.ec for s in entries], [s.src for s in entries], S, max_frames=MAXF)
     assert b.nconfigs() == 4
@@ -365,7 +338,7 @@ def test_blobs_need_the_assign_first():
     device form.  Without the assign the restore is refused (host) or skipped with status bit 32 (device), and the slot
     goes on as before"""
     import torch
-    A = api()
+    A = api
     F1, F2 = 5, 4
     src = A.Batch(A.default_control(**KWX), nstreams=2, max_frames=F1)
     moved = [Life(3700 + i, KWX) for i in range(2)]
@@ -378,7 +351,7 @@ def test_blobs_need_the_assign_first():
     b = menu_batch(MENU)
     sl = Slots(b, MENU, [0] * S, 3800)
     sl.call([3, 2, 4, 1, 2, 3], 4, "first call")
-    before = blobs(b)
+    before = states(b)
     stride, need = b.states_stride(), len(saved[0])
     with pytest.raises(RuntimeError, match="entry 0: the stream state was saved under a different configuration"):
         b.set_stream_states([3], [saved[0]])
@@ -388,7 +361,7 @@ def test_blobs_need_the_assign_first():
     torch.cuda.synchronize()
     b.set_stream_states_device([5], d_up.data_ptr(), stride, None)
     assert b.status() == 32
-    assert blobs(b) == before
+    assert states(b) == before
     counts = [2, 0, 1, 3, 4, 2]
     b.frame_counts(counts)
     sl.check(counts, 4, b.encode_host(sl.block(counts, 4)), tag="after the refused restores")
@@ -397,7 +370,7 @@ def test_blobs_need_the_assign_first():
     b.set_stream_states([3], [saved[0]])
     b.set_stream_states_device([5], d_up.data_ptr(), stride, None)
     sl.life[3], sl.life[5] = moved
-    for got, want in zip(blobs(b, [3, 5]), saved):
+    for got, want in zip(states(b, [3, 5]), saved):
         assert same_but_class(got, want)
     counts = [1, 2, 0, F2, 3, F2]
     b.frame_counts(counts)
@@ -406,13 +379,9 @@ def test_blobs_need_the_assign_first():
     b.close()
 
 
-def ints(v):
-    return (C.c_int * max(len(v), 1))(*v), len(v)
-
-
 @pytest.mark.one_k6_build
 def test_refusals_leave_the_batch_unchanged():
-    A = api()
+    A = api
     L = A.lib()
     cfg = [0, 1, 0, 2, 0, 0]
     b = menu_batch(MENU, cfg)
@@ -423,7 +392,7 @@ def test_refusals_leave_the_batch_unchanged():
 
     def unchanged(before, what):
         """after a refusal: every blob and every slot's entry as before, and a valid call matches the oracle"""
-        assert blobs(b) == before and [b.stream_config(i) for i in range(S)] == cfg, what
+        assert states(b) == before and [b.stream_config(i) for i in range(S)] == cfg, what
         sl.call(small[made[0] % 3], 2, "valid call after the refusal of " + what)
         made[0] += 1
     for idx, c, n, word in (([1, 3], [0, 4], None, "entry 1: configuration 4 out of range"), ([1, 3], [-1, 0], None, "entry 0: configuration -1"),
@@ -431,17 +400,17 @@ def test_refusals_leave_the_batch_unchanged():
                             ([0, 1], [0, 0], -1, "n = -1")):
         ai, k = ints(idx)
         ac, _ = ints(c)
-        before = blobs(b)
+        before = states(b)
         assert L.hx_batch_assign_streams(b.h, ai, ac, k if n is None else n, None) == -1 and word in A.last_error(), (idx, c, A.last_error())
         unchanged(before, word)
     ai, k = ints([0, 1])
-    before = blobs(b)
+    before = states(b)
     assert L.hx_batch_assign_streams(b.h, None, ai, 2, None) == -1 and "idx" in A.last_error()
     unchanged(before, "a null idx")
-    before = blobs(b)
+    before = states(b)
     assert L.hx_batch_assign_streams(b.h, ai, None, 2, None) == -1 and "cfg" in A.last_error()
     unchanged(before, "a null cfg")
-    before = blobs(b)
+    before = states(b)
     assert L.hx_batch_assign_streams(b.h, None, None, 0, None) == 0         # n = 0: nothing to do, nothing launched
     unchanged(before, "n = 0")
     b.close()
@@ -472,7 +441,7 @@ def test_refusals_leave_the_batch_unchanged():
 def test_multi_assign_over_two_blocks():
     """five slots in two blocks (3 + 2) on device 0: an assign lists slots of both blocks; a bad entry that falls into the
     second block changes nothing in the first"""
-    A = api()
+    A = api
     n, nf = 5, 4
     m = A.Multi.menu(controls(MENU), n, max_frames=nf, devices=[0, 0])
     assert [m.shard(k)[1:] for k in range(2)] == [(0, 3), (3, 2)] and m.nconfigs() == 4
@@ -481,7 +450,7 @@ def test_multi_assign_over_two_blocks():
     sl.assign([4, 1, 3], [3, 2, 1])
     sl.call([2, 4, 1, 3, 4], nf, "after the assign")
 
-    def states():
+    def multi_states():
         out = []
         for k in range(2):
             h, (_, _, count) = m.batch(k), m.shard(k)
@@ -490,12 +459,12 @@ def test_multi_assign_over_two_blocks():
                 assert A.lib().hx_batch_get_stream_state(h, i, buf) == 0
                 out.append(bytes(buf))
         return out
-    before = states()
+    before = multi_states()
     for idx, cfg, word in (([0, 2, 4], [1, 1, 4], "entry 2: configuration 4 out of range"), ([1, 3, 5], [0, 0, 0], "entry 2: slot 5 out of range"),
                            ([2, 4, 4], [1, 1, 1], "entry 2: slot 4 is listed twice")):
         with pytest.raises(RuntimeError, match=word):
             m.assign_streams(idx, cfg)
-    assert states() == before and [m.stream_config(i) for i in range(n)] == sl.cfg
+    assert multi_states() == before and [m.stream_config(i) for i in range(n)] == sl.cfg
     sl.call([1, 2, 3, 0, 2], nf, "valid call after the refusals")
     m.close()
 
@@ -506,29 +475,12 @@ def test_cli_batch_through_two_slots(flags, tmp_path):
     """`hmp3amd -batch -slots2` on five stereo files - 48 kHz s24, 44.1 kHz s16, 32 kHz f32, 44.1 kHz s16 and 48 kHz s16, of
     5, 40, 130, 3 and 101 frames: two slots take the five files one after the other, each handed over by an assign, and
     every file is byte for byte its single-file run's and, where it is built, the reference binary's"""
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import make_golden_cli as M
-    exe = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
-    assert os.path.exists(exe), "hmp3_amd/build.sh builds the CLI"
-    files, args = [], []
+    files = []
     for i, (sr, fmt, frames) in enumerate([(48000, 24, 5), (44100, False, 40), (32000, True, 130), (44100, False, 3), (48000, False, 101)]):
         nsamp = frames * 1152 * (sr // 100 if flags else 320) // 320 - 301 * i - 7
         pcm = synth.stream_pcm(9700 + i, nsamp // 1152 + 1, sr=sr, rho=0.5, bursts=i != 1)[:nsamp]
         wav = str(tmp_path / ("in%d.wav" % i))
-        M.write_wav(wav, pcm, sr, fmt)
-        files.append(wav)
-        args += [wav, str(tmp_path / ("slots%d.mp3" % i))]
-    r = subprocess.run([exe, "-batch", "-slots2"] + args + flags, capture_output=True, timeout=120)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
-    assert "5 files through 2 slots" in r.stderr.decode()
-    ref = os.path.join(ROOT, "oracle", "_ref", "hmp3")
-    for i, wav in enumerate(files):
-        got = open(str(tmp_path / ("slots%d.mp3" % i)), "rb").read()
-        one = str(tmp_path / ("single%d.mp3" % i))
-        r = subprocess.run([exe, wav, one] + flags, capture_output=True, timeout=120)
-        assert r.returncode == 0, r.stderr.decode()[-400:]
-        assert len(got) > 1000 and got == open(one, "rb").read(), "file %d differs from its single-file run" % i
-        if os.path.exists(ref):
-            theirs = str(tmp_path / ("ref%d.mp3" % i))
-            subprocess.run([ref, wav, theirs] + flags, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=120)
-            assert got == open(theirs, "rb").read(), "file %d differs from the reference binary's" % i
+        write_wav(wav, pcm, sr, fmt)
+        files.append(("file %d" % i, wav, str(tmp_path / ("slots%d.mp3" % i))))
+    stderr, _ = batch_vs_single_vs_reference(files, flags, ["-slots2"], floor=1000)
+    assert "5 files through 2 slots" in stderr

@@ -11,9 +11,10 @@ import struct
 import numpy as np
 import pytest
 
-from oracle import oracle as O
-from hmp3_amd import synth
 from conftest import skip_unless_host_libm_is_the_restated_one
+from gpu_support import ints, oracle_bytes, states
+from hmp3_amd import api, synth
+from src_cases import Stream, make_batch, make_rows, run
 
 pytestmark = pytest.mark.gpu
 
@@ -21,11 +22,6 @@ KWS = [dict(bitrate=64), dict(vbr_mnr=70), dict(bitrate=64, samprate=48000)]
 S = 6
 T0 = 9          # the calls start at frame T0 of a 24-frame signal: its first burst lies in frame 13 (44.1 kHz) / 14 (48 kHz)
 RESET = [5, 0, 2]   # not monotone, first and last slot included
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 @functools.lru_cache(maxsize=None)
@@ -38,13 +34,8 @@ def sig(seed, i, rate=None, mono=False):
     return x
 
 
-def cut(seed, F, rate=None, mono=False, n=S):
+def calls_pcm(seed, F, rate=None, mono=False, n=S):
     return np.stack([sig(seed, i, rate, mono)[:F * 1152] for i in range(n)])
-
-
-def oracle_of(kw, pcm):
-    enc = O.OracleEncoder(O.default_control(**kw))
-    return b"".join(enc.encode_s16(pcm[f * 1152:(f + 1) * 1152]) for f in range(len(pcm) // 1152))
 
 
 @functools.lru_cache(maxsize=None)
@@ -52,20 +43,16 @@ def expected(i, n1, n2, fresh):
     """stream i over n1 frames of the first signal and n2 of the second: (bytes of the first call, of the second) - the second
     as a new stream (fresh) or as the continuation"""
     a, b = sig(1500, i)[:n1 * 1152], sig(1600, i)[:n2 * 1152]
-    first = oracle_of(KWS[i % 3], a)
+    first = oracle_bytes(KWS[i % 3], a)
     if fresh:
-        return first, oracle_of(KWS[i % 3], b)
-    both = oracle_of(KWS[i % 3], np.concatenate([a, b]))
+        return first, oracle_bytes(KWS[i % 3], b)
+    both = oracle_bytes(KWS[i % 3], np.concatenate([a, b]))
     assert both[:len(first)] == first
     return first, both[len(first):]
 
 
-def controls():
-    return [api().default_control(**KWS[i % 3]) for i in range(S)]
-
-
-def all_blobs(b):
-    return [b.get_stream_state(i) for i in range(b.n)]
+def slot_controls():
+    return [api.default_control(**KWS[i % 3]) for i in range(S)]
 
 
 @pytest.mark.parametrize("F1,F2", [(6, 5), (7, 2)], ids=["6_then_5", "7_then_2_stale_subband_slots"])
@@ -73,16 +60,16 @@ def test_reset_of_many_slots(F1, F2, k6_build):
     """the reset slots equal a new batch's bit for bit, the others are not touched, and the next call encodes the new
     inputs from scratch - also when it is shorter than the one before, so that subband slots written by the earlier call
     lie beyond its extent (only slots 0..2 are zeroed)"""
-    b = api().Batch(controls(), nstreams=S, max_frames=7)
-    fresh = api().Batch(controls(), nstreams=S, max_frames=7)
-    out1 = b.encode_host(cut(1500, F1))
-    before = all_blobs(b)
+    b = api.Batch(slot_controls(), nstreams=S, max_frames=7)
+    fresh = api.Batch(slot_controls(), nstreams=S, max_frames=7)
+    out1 = b.encode_host(calls_pcm(1500, F1))
+    before = states(b, single=True)
     b.reset_streams(RESET)
-    after, new = all_blobs(b), all_blobs(fresh)
+    after, new = states(b, single=True), states(fresh, single=True)
     for i in range(S):
         assert after[i] == (new[i] if i in RESET else before[i]), i
         assert (before[i] != new[i]), i         # (the first call left something to reset)
-    out2 = b.encode_host(cut(1600, F2))
+    out2 = b.encode_host(calls_pcm(1600, F2))
     assert b.status() == 0
     for i in range(S):
         assert (out1[i], out2[i]) == expected(i, F1, F2, i in RESET), i
@@ -100,8 +87,8 @@ def test_reset_between_pipelined_submits_without_a_wait(counts, k6_build):
     n2 = [5, 5, 3, 0, 4, 5] if counts else [F2] * S
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    d_pcm = [torch.from_numpy(cut(1500, F1)).to(dev), torch.from_numpy(cut(1600, F2)).to(dev)]
-    b = api().Batch(controls(), nstreams=S, max_frames=7)
+    d_pcm = [torch.from_numpy(calls_pcm(1500, F1)).to(dev), torch.from_numpy(calls_pcm(1600, F2)).to(dev)]
+    b = api.Batch(slot_controls(), nstreams=S, max_frames=7)
     stride = b.out_stride(7)
     d_out = [torch.zeros((S, stride), dtype=torch.uint8, device=dev) for _ in range(2)]
     d_nb = [torch.zeros((S,), dtype=torch.int32, device=dev) for _ in range(2)]
@@ -130,11 +117,11 @@ def test_single_slot_reset_over_stale_subband_slots(k6_build):
     2-frame calls of new input - the subband slots the long call wrote lie beyond the short calls' extent.  The reset slots
     encode the new input from scratch, the others continue"""
     F1, F2, reset = 7, 2, [4, 1]
-    b = api().Batch(controls(), nstreams=S, max_frames=7)
-    out1 = b.encode_host(cut(1500, F1))
+    b = api.Batch(slot_controls(), nstreams=S, max_frames=7)
+    out1 = b.encode_host(calls_pcm(1500, F1))
     for i in reset:
         b.reset_stream(i)
-    new = cut(1600, 2 * F2)
+    new = calls_pcm(1600, 2 * F2)
     out2 = [x + y for x, y in zip(b.encode_host(new[:, :F2 * 1152]), b.encode_host(new[:, F2 * 1152:]))]
     assert b.status() == 0
     for i in range(S):
@@ -146,17 +133,13 @@ HEADER = struct.Struct("<IIIIQ")        # HxStateHeader: magic, format version, 
 CARRY = 3 * 576 * 4                     # bytes of the three carried subband granules of one channel
 
 
-def ints(v):
-    return (C.c_int * max(len(v), 1))(*v), len(v)
-
-
 def saved_both_ways(b, idx):
     """the blobs of the slots in idx from the list call - nothing is written behind the array, every blob ends in zeros up to
     the stride - and from the single-slot call, which gives the same bytes -> the blobs"""
-    need, stride = int(api().lib().hx_batch_stream_state_bytes(b.h)), b.states_stride()
+    need, stride = int(api.lib().hx_batch_stream_state_bytes(b.h)), b.states_stride()
     arr, n = ints(idx)
     buf = np.full(n * stride + 64, 0xA5, np.uint8)
-    assert api().lib().hx_batch_get_stream_states(b.h, arr, n, buf.ctypes.data, stride) == 0, api().last_error()
+    assert api.lib().hx_batch_get_stream_states(b.h, arr, n, buf.ctypes.data, stride) == 0, api.last_error()
     assert (buf[n * stride:] == 0xA5).all()
     blobs = []
     for e, i in enumerate(idx):
@@ -186,7 +169,6 @@ def header_state_carry(b, i, blob, magic, max_frames):
 @functools.lru_cache(maxsize=None)
 def converting_streams():
     """six sources over two converter plans and configurations: 48 kHz -> 44.1 kHz (case 4, carried samples) and 44.1 -> 32 kHz"""
-    from test_gpu_src_batch import Stream
     return [Stream(*((48000, 16, 0) if i % 2 == 0 else (44100, 16, 0)), mpeg_select=44100 if i % 2 == 0 else 32000, seed=60 + i, seconds=1.0)
             for i in range(S)]
 
@@ -197,23 +179,21 @@ def test_gather_equals_the_single_slot_call(idx):
     """what a blob holds, after two uneven calls, against the batch's debug taps; the list form and the single-slot form give
     the same bytes.  A plain batch of three classes; a converting batch of two plans, whose blob goes on with the plan's
     fingerprint, the stream's converter call count and the carried samples"""
-    from test_gpu_src_counts import make_rows
-    b = api().Batch(controls(), nstreams=S, max_frames=7)
+    b = api.Batch(slot_controls(), nstreams=S, max_frames=7)
     for seed, F, counts in ((1500, 5, [5, 2, 4, 0, 3, 5]), (1600, 3, [2, 3, 0, 3, 1, 2])):
         b.frame_counts(counts)
-        b.encode_host(cut(seed, F))
+        b.encode_host(calls_pcm(seed, F))
     blobs = saved_both_ways(b, idx)
     for e, i in enumerate(idx):
         cfg, rest = header_state_carry(b, i, blobs[e], b"HX3S", 7)
         assert rest == b"", i
-    cfgs = [HEADER.unpack(x[:HEADER.size])[4] for x in all_blobs(b)]
+    cfgs = [HEADER.unpack(x[:HEADER.size])[4] for x in states(b, single=True)]
     for i in range(S):
         for j in range(S):
             assert (cfgs[i] == cfgs[j]) == (i % 3 == j % 3), (i, j)
     assert b.status() == 0
     b.close()
 
-    from test_gpu_src_batch import make_batch
     streams = converting_streams()
     b = make_batch(streams, 7)
     pos, done = [0] * S, [0] * S
@@ -246,18 +226,17 @@ def test_gather_equals_the_single_slot_call(idx):
 def test_single_slot_save_writes_no_byte_beyond_the_state(kind):
     """hx_batch_get_stream_state into a buffer of hx_batch_stream_state_bytes + 64 bytes: the state, and the 64 bytes behind it
     untouched (the list form's blob goes on with zeros up to its stride; the single-slot call's buffer ends with the state)"""
-    from test_gpu_src_batch import make_batch
-    L = api().lib()
+    L = api.lib()
     if kind == "plain":
-        b = api().Batch(controls(), nstreams=S, max_frames=7)
-        b.encode_host(cut(1500, 4))
+        b = api.Batch(slot_controls(), nstreams=S, max_frames=7)
+        b.encode_host(calls_pcm(1500, 4))
     else:
         b = make_batch(converting_streams(), 7)
     need = int(L.hx_batch_stream_state_bytes(b.h))
     assert need < b.states_stride()
     for i in (0, S - 1):
         buf = (C.c_ubyte * (need + 64))(*([0xA5] * (need + 64)))
-        assert L.hx_batch_get_stream_state(b.h, i, buf) == 0, api().last_error()
+        assert L.hx_batch_get_stream_state(b.h, i, buf) == 0, api.last_error()
         assert bytes(buf[need:]) == b"\xA5" * 64, i
         assert bytes(buf[:need]) == b.get_stream_states([i])[0], i
     assert b.status() == 0
@@ -271,8 +250,8 @@ PLACE = [5, 0, 3, 2]        # stream i of the source batch goes to slot PLACE[i]
 @functools.lru_cache(maxsize=None)
 def moved_expected(i, F1, F2):
     x = sig(1700, i, 44100)[:(F1 + F2) * 1152]
-    first = oracle_of(KW4, x[:F1 * 1152])
-    both = oracle_of(KW4, x)
+    first = oracle_bytes(KW4, x[:F1 * 1152])
+    both = oracle_bytes(KW4, x)
     assert both[:len(first)] == first
     return first, both[len(first):]
 
@@ -289,14 +268,14 @@ def test_scatter_into_another_batch():
     """four streams saved in one call continue in slots [5, 0, 3, 2] of a batch of another size and max_frames; its two
     other slots keep their blobs"""
     F1, F2 = 5, 6
-    b1 = api().Batch(api().default_control(**KW4), nstreams=4, max_frames=5)
-    out1 = b1.encode_host(cut(1700, F1, 44100, n=4))
+    b1 = api.Batch(api.default_control(**KW4), nstreams=4, max_frames=5)
+    out1 = b1.encode_host(calls_pcm(1700, F1, 44100, n=4))
     saved = b1.get_stream_states(range(4))
     b1.close()
-    b2 = api().Batch(api().default_control(**KW4), nstreams=6, max_frames=7)
-    before = all_blobs(b2)
+    b2 = api.Batch(api.default_control(**KW4), nstreams=6, max_frames=7)
+    before = states(b2, single=True)
     b2.set_stream_states(PLACE, saved)
-    after = all_blobs(b2)
+    after = states(b2, single=True)
     for slot in (1, 4):
         assert after[slot] == before[slot]
     for i, slot in enumerate(PLACE):
@@ -315,11 +294,11 @@ def test_single_slot_and_list_forms_cross(kind):
     second batch, and continue there over two calls as if nothing had happened"""
     if kind == "plain":
         F1, F2 = 5, 6
-        b1 = api().Batch(api().default_control(**KW4), nstreams=4, max_frames=5)
-        out1 = b1.encode_host(cut(1700, F1, 44100, n=4))
+        b1 = api.Batch(api.default_control(**KW4), nstreams=4, max_frames=5)
+        out1 = b1.encode_host(calls_pcm(1700, F1, 44100, n=4))
         single, listed = [b1.get_stream_state(i) for i in (0, 1)], b1.get_stream_states([2, 3])
         b1.close()
-        b2 = api().Batch(api().default_control(**KW4), nstreams=6, max_frames=7)
+        b2 = api.Batch(api.default_control(**KW4), nstreams=6, max_frames=7)
         b2.set_stream_states(PLACE[:2], single)
         for slot, blob in zip(PLACE[2:], listed):
             b2.set_stream_state(slot, blob)
@@ -330,7 +309,6 @@ def test_single_slot_and_list_forms_cross(kind):
             assert (out1[i], out2[slot]) == moved_expected(i, F1, F2), i
         b2.close()
         return
-    from test_gpu_src_batch import Stream, make_batch, run
     s0, s1 = (Stream(48000, 16, 0, mpeg_select=44100, seed=k, seconds=1.0) for k in (41, 42))
     b1 = make_batch([s0, s1], 8)
     o1, p1, _ = run(b1, [s0, s1], [6])
@@ -356,9 +334,9 @@ def test_device_blobs_move_streams_without_a_host_wait():
     idx, place = [2, 0, 3], [4, 1, 0]
     dev = torch.device("cuda:0")
     st = torch.cuda.current_stream().cuda_stream
-    b1 = api().Batch(api().default_control(**KW4), nstreams=4, max_frames=5)
-    out1 = b1.encode_host(cut(1700, F1, 44100, n=4))
-    b2 = api().Batch(api().default_control(**KW4), nstreams=6, max_frames=7)
+    b1 = api.Batch(api.default_control(**KW4), nstreams=4, max_frames=5)
+    out1 = b1.encode_host(calls_pcm(1700, F1, 44100, n=4))
+    b2 = api.Batch(api.default_control(**KW4), nstreams=6, max_frames=7)
     need, stride = len(b1.get_stream_state(0)), b1.states_stride() + 32       # (a stride larger than the smallest)
     n, canary = len(idx), 256
     d_blobs = torch.full((n * stride + canary,), 0xA5, dtype=torch.uint8, device=dev)
@@ -391,11 +369,11 @@ def test_device_blobs_move_streams_without_a_host_wait():
 @pytest.mark.one_k6_build
 def test_refusals_leave_the_batch_unchanged():
     import torch
-    A = api()
+    A = api
     L = A.lib()
-    b = A.Batch(controls(), nstreams=S, max_frames=7)
-    b.encode_host(cut(1500, 5))
-    before = all_blobs(b)
+    b = A.Batch(slot_controls(), nstreams=S, max_frames=7)
+    b.encode_host(calls_pcm(1500, 5))
+    before = states(b, single=True)
     need, stride = len(before[0]), b.states_stride()
     assert stride % 16 == 0 and need <= stride < need + 16
     host = np.zeros(S * (stride + 16), dtype=np.uint8)
@@ -427,17 +405,17 @@ def test_refusals_leave_the_batch_unchanged():
     assert L.hx_batch_get_stream_states_device(b.h, None, 0, None, stride, None) == 0
     assert L.hx_batch_set_stream_states_device(b.h, None, 0, None, stride, None) == 0
     assert not host.any() and not d_buf.cpu().numpy().any()
-    assert all_blobs(b) == before
+    assert states(b, single=True) == before
     assert b.status() == 0
 
     # a host blob with a flipped fingerprint: none of the listed slots is written
     saved = b.get_stream_states([0, 1, 2])
     bad = bytearray(saved[1]); bad[16] ^= 1
-    b2 = A.Batch(controls(), nstreams=S, max_frames=7)
-    new = all_blobs(b2)
+    b2 = A.Batch(slot_controls(), nstreams=S, max_frames=7)
+    new = states(b2, single=True)
     with pytest.raises(RuntimeError, match="entry 1: the stream state was saved under a different configuration"):
         b2.set_stream_states([3, 4, 5], [saved[0], bytes(bad), saved[2]])
-    assert all_blobs(b2) == new and b2.status() == 0
+    assert states(b2, single=True) == new and b2.status() == 0
     # the device variant cannot refuse: the kernel leaves that slot alone, restores the others and says so in the status
     up = np.zeros(3 * stride, dtype=np.uint8)
     for e, blob in enumerate([saved[0], bytes(bad), saved[2]]):
@@ -446,7 +424,7 @@ def test_refusals_leave_the_batch_unchanged():
     torch.cuda.synchronize()
     b2.set_stream_states_device([3, 4, 5], d_up.data_ptr(), stride, None)
     assert b2.status() == 32
-    got = all_blobs(b2)
+    got = states(b2, single=True)
     assert got[3] == saved[0] and got[5] == saved[2] and got[4] == new[4]
     assert got[:3] == new[:3]
     b.close(); b2.close()
@@ -465,9 +443,9 @@ def test_other_kinds_of_batch(name):
     if "intensity" in name:
         skip_unless_host_libm_is_the_restated_one()
     F, n, sr = 4, 3, kw.get("samprate", 44100)
-    first, second = cut(1800, F, sr, mono, n), cut(1900, F, sr, mono, n)
-    b = api().Batch(api().default_control(**kw), nstreams=n, max_frames=F)
-    b2 = api().Batch(api().default_control(**kw), nstreams=n, max_frames=F + 1)
+    first, second = calls_pcm(1800, F, sr, mono, n), calls_pcm(1900, F, sr, mono, n)
+    b = api.Batch(api.default_control(**kw), nstreams=n, max_frames=F)
+    b2 = api.Batch(api.default_control(**kw), nstreams=n, max_frames=F + 1)
     out1 = b.encode_host(first)
     b.reset_streams([1])
     b2.set_stream_states([0], b.get_stream_states([2]))
@@ -475,12 +453,12 @@ def test_other_kinds_of_batch(name):
     moved = b2.encode_host(np.stack([second[2], second[0], second[1]]))
     assert b.status() == 0 and b2.status() == 0
     for i in range(n):
-        assert out1[i] == oracle_of(kw, first[i]), i
-    assert out2[1] == oracle_of(kw, second[1])
+        assert out1[i] == oracle_bytes(kw, first[i]), i
+    assert out2[1] == oracle_bytes(kw, second[1])
     for i in (0, 2):
-        assert out1[i] + out2[i] == oracle_of(kw, np.concatenate([first[i], second[i]])), i
+        assert out1[i] + out2[i] == oracle_bytes(kw, np.concatenate([first[i], second[i]])), i
     assert moved[0] == out2[2]
-    assert moved[1] == oracle_of(kw, second[0])
+    assert moved[1] == oracle_bytes(kw, second[0])
     b.close(); b2.close()
 
 
@@ -489,8 +467,7 @@ def test_converting_batch():
     """48 kHz s16 -> 44.1 kHz (a case-4 plan, with carried samples): reset_streams restarts the converter too, the host
     calls move a stream with its converter to another converting batch, and device blobs are refused"""
     import torch
-    from test_gpu_src_batch import Stream, make_batch, run
-    A = api()
+    A = api
     L = A.lib()
     s0, s1, snew = (Stream(48000, 16, 0, mpeg_select=44100, seed=k, seconds=1.0) for k in (41, 42, 43))
     b1 = make_batch([s0, s1], 8)
@@ -516,8 +493,8 @@ def test_converting_batch():
     assert o3[0] == s0.per_frame(5)[0]
     d = torch.zeros(b1.states_stride(), dtype=torch.uint8, device="cuda:0")
     arr, k = ints([0])
-    before = all_blobs(b1)
+    before = states(b1, single=True)
     assert L.hx_batch_get_stream_states_device(b1.h, arr, k, d.data_ptr(), b1.states_stride(), None) == -1 and "converting" in A.last_error()
     assert L.hx_batch_set_stream_states_device(b1.h, arr, k, d.data_ptr(), b1.states_stride(), None) == -1 and "converting" in A.last_error()
-    assert all_blobs(b1) == before and b1.status() == 0
+    assert states(b1, single=True) == before and b1.status() == 0
     b1.close(); b2.close()

@@ -9,7 +9,9 @@ import ctypes as C
 import numpy as np
 import pytest
 
+from hmp3_amd import api
 from oracle import oracle as O
+from src_cases import Stream, make_batch, ref_converted, run, source_signal
 
 pytestmark = [pytest.mark.gpu, pytest.mark.skipif(O.ref() is None, reason="oracle/_ref not built")]
 
@@ -17,142 +19,6 @@ FORMATS = [(8, 0), (16, 0), (24, 0), (32, 0), (32, 1)]
 # (source rate, encode rate): every case of the converter towards MPEG-1 and towards MPEG-2 rates
 PAIRS1 = [(44100, 44100), (22050, 44100), (32000, 44100), (48000, 32000), (44100, 32000), (48000, 44100)]
 PAIRS2 = [(16000, 16000), (8000, 16000), (11025, 16000), (22050, 24000), (48000, 24000), (44100, 24000), (32000, 22050)]
-
-
-def api():
-    from hmp3_amd import api as A
-    return A
-
-
-def ref():
-    R = O.ref()
-    R.ref_src_new.restype = C.c_void_p
-    R.ref_src_free.argtypes = [C.c_void_p]
-    R.ref_src_init.argtypes = [C.c_void_p] + [C.c_int] * 6 + [C.c_void_p]
-    R.ref_src_convert.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    R.ref_init_mp3.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
-    R.ref_encode_mp3.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return R
-
-
-def source_bytes(x, bits, is_float):
-    """float signal in [-1, 1) (interleaved) -> the source format's bytes"""
-    if is_float:
-        return x.astype("<f4").tobytes()
-    if bits == 8:
-        return np.clip(np.round(x * 127 + 128), 0, 255).astype(np.uint8).tobytes()
-    if bits == 16:
-        return np.clip(np.round(x * 32767), -32768, 32767).astype("<i2").tobytes()
-    v = np.clip(np.round(x * 2147483647.0), -2 ** 31, 2 ** 31 - 1).astype("<i4")
-    if bits == 32:
-        return v.tobytes()
-    b = v.view(np.uint8).reshape(-1, 4)
-    return b[:, 1:].tobytes()
-
-
-def signal(seed, nsamp, channels, noise=False):
-    rng = np.random.default_rng(seed)
-    if noise:
-        return rng.uniform(-1, 1, nsamp * channels)
-    t = np.arange(nsamp)[:, None]
-    f = rng.uniform(100, 3000, (1, channels))
-    x = 0.4 * np.sin(2 * np.pi * f * t / 32000.0) + 0.05 * rng.standard_normal((nsamp, channels))
-    x[nsamp // 3:nsamp // 3 + 300] *= 2.0        # an onset
-    return np.clip(x, -1, 0.999).reshape(-1)
-
-
-class Stream:
-    """one source: its control (samprate = source rate), its HX_SOURCE and its bytes"""
-
-    def __init__(self, source, bits, is_float, channels=2, mpeg_select=0, mono_convert=0, seed=0, seconds=3.0, noise=False, **kw):
-        A = api()
-        self.ec = A.default_control(**({"bitrate": 64} | kw))
-        self.ec.samprate = source
-        if channels == 1:
-            self.ec.mode = 3
-        self.src = A.Source(bits, is_float, mpeg_select, mono_convert)
-        self.channels, self.bits, self.is_float, self.source = channels, bits, is_float, source
-        self.mono_convert, self.mpeg_select = mono_convert, mpeg_select
-        n = int(source * seconds)
-        self.data = source_bytes(signal(seed, n, channels, noise), bits, is_float) + bytes(1 << 18)
-        self.fb = channels * bits // 8
-
-    def reference(self, nframes, offsets=None):
-        """the reference's MP3_audio_encode loop: bytes, sum of in_bytes (offsets: the pointer of every call)"""
-        R = ref()
-        A = api()
-        h = R.ref_new()
-        e = A.EControl()
-        C.memmove(C.byref(e), C.byref(self.ec), C.sizeof(e))
-        assert R.ref_init_mp3(h, C.byref(e), self.bits, self.is_float, self.src.mpeg_select, self.src.mono_convert) > 0
-        buf = (C.c_ubyte * len(self.data)).from_buffer_copy(self.data)
-        out = (C.c_ubyte * 65536)()
-        res, pos, used = b"", 0, C.c_int(0)
-        for f in range(nframes):
-            p = pos if offsets is None else int(offsets[f])
-            n = R.ref_encode_mp3(h, C.byref(buf, p), out, C.byref(used))
-            res += bytes(out[:n])
-            pos = p + used.value
-        R.ref_free(h)
-        return res, pos
-
-    def per_frame(self, nframes):
-        """this library's one-stream MP3_audio_encode: bytes, sum of in_bytes"""
-        A = api()
-        L = A.lib()
-        e = A.Mp3Enc()
-        assert e.MP3_audio_encode_init(self.ec, self.bits, self.is_float, self.src.mpeg_select, self.src.mono_convert) > 0
-        buf = (C.c_ubyte * len(self.data)).from_buffer_copy(self.data)
-        res, pos = b"", 0
-        for _ in range(nframes):
-            x = L.hx_enc_MP3_audio_encode(e.h, C.byref(buf, pos), e._out)
-            res += bytes(e._out[:x.out_bytes])
-            pos += x.in_bytes
-        e.close()
-        return res, pos
-
-
-def make_batch(streams, max_frames):
-    A = api()
-    return A.SrcBatch([s.ec for s in streams], [s.src for s in streams], max_frames=max_frames)
-
-
-def run(b, streams, calls, pos=None, taps=False):
-    """consecutive calls of the given frame counts; rows start at each stream's first unconsumed byte"""
-    pos = [0] * len(streams) if pos is None else pos
-    outs = [b""] * len(streams)
-    pcm = []
-    for nf in calls:
-        stride = b.in_stride(nf)
-        rows = np.zeros((len(streams), stride), np.uint8)
-        for i, s in enumerate(streams):
-            chunk = np.frombuffer(s.data[pos[i]:pos[i] + stride], np.uint8)
-            rows[i, :len(chunk)] = chunk
-        res, used = b.encode_src_host(rows, nf)
-        assert b.status() == 0
-        if taps:
-            pcm.append(b.debug_read("srcpcm", np.float32, len(streams) * nf * 1152 * 2).reshape(len(streams), nf * 1152, -1))
-        for i in range(len(streams)):
-            outs[i] += res[i]
-            pos[i] += int(used[i])
-    return outs, pos, pcm
-
-
-def ref_converted(s, target, nframes):
-    """the reference's Csrc over nframes calls: [nframes * 1152][target channels] float32"""
-    R = ref()
-    tch = 1 if (s.channels == 1 or s.mono_convert) else 2
-    h = R.ref_src_new()
-    cut = C.c_int(0)
-    assert R.ref_src_init(h, s.source, s.channels, s.bits, s.is_float, target, tch, C.byref(cut)) > 0
-    buf = (C.c_ubyte * len(s.data)).from_buffer_copy(s.data)
-    ys, pos, ob = [], 0, C.c_int(0)
-    for _ in range(nframes):
-        y = np.zeros(2304, np.float32)
-        pos += R.ref_src_convert(h, C.byref(buf, pos), y.ctypes.data, C.byref(ob))
-        ys.append(y[:1152 * tch].reshape(1152, tch))
-    R.ref_src_free(h)
-    return np.concatenate(ys)
 
 
 def stage_streams(pairs, layout):
@@ -192,7 +58,7 @@ def range_streams(layout):
         for scale in (16.0, 1e-41):
             ch, mono = {"stereo": (2, 0), "downmix": (2, 1)}[layout]
             s = Stream(src, 32, 1, ch, mpeg_select=tgt, mono_convert=mono, seed=900 + k, seconds=1.0)
-            x = signal(900 + k, src, ch) * scale
+            x = source_signal(900 + k, src, ch) * scale
             x[5::97] = scale                    # the level itself, exactly
             s.data = x.astype("<f4").tobytes() + bytes(1 << 18)
             s.target, s.scale = tgt, scale
@@ -284,7 +150,7 @@ def test_ragged_calls_with_dc_filter_equal_one_call(k6_build):
 def test_checkpoint_of_a_converting_stream_resumes_elsewhere(k6_build):
     """a case-4 stream saved mid-way continues in another slot of another batch (another max_frames) byte for byte;
     blobs do not cross between converting and plain batches; reset_stream restarts the converter"""
-    A = api()
+    A = api
     L = A.lib()
     s = Stream(48000, 24, 0, mpeg_select=44100, seed=21)
     other = Stream(44100, 16, 0, mpeg_select=32000, seed=22)
@@ -335,7 +201,7 @@ def test_pointer_switch_to_zero_bytes_equals_the_reference(k6_build):
 
 
 def test_misuse_is_refused_and_leaves_the_batch_usable(k6_build):
-    A = api()
+    A = api
     L = A.lib()
     streams = mixed_stereo()[:3]
     b = make_batch(streams, 8)
@@ -363,7 +229,7 @@ def test_misuse_is_refused_and_leaves_the_batch_usable(k6_build):
 
 def test_several_devices_equal_the_reference_loop(k6_build):
     """hx_multi_create_src: the streams in blocks over every device present, each block a converting batch"""
-    A = api()
+    A = api
     streams = mixed_stereo()
     m = A.SrcMulti([s.ec for s in streams], [s.src for s in streams], max_frames=24)
     stride = m.in_stride(24)
@@ -379,7 +245,7 @@ def test_several_devices_equal_the_reference_loop(k6_build):
 
 
 def test_plain_pcm_calls_are_refused_on_a_converting_batch(k6_build):
-    A = api()
+    A = api
     L = A.lib()
     streams = mixed_stereo()[:2]
     b = make_batch(streams, 4)
@@ -398,7 +264,7 @@ def test_plain_pcm_calls_are_refused_on_a_converting_batch(k6_build):
 def test_phase_beyond_32_bits_equals_the_stepped_converter(k6_build):
     """a stream resumed at call 14000 of a 32 -> 44.1 kHz converter (output index x bank step beyond 2^32) converts what the
     host converter stepped through 14000 calls converts: the kernel's phase is 64-bit"""
-    A = api()
+    A = api
     L = A.lib()
     s = Stream(32000, 16, 0, mpeg_select=44100, seed=41)
     b = make_batch([s], 4)

@@ -10,19 +10,18 @@ batch; a stream without a call in a launch has to copy them across.  Two idle ca
 call, are the sequences that read a stale copy otherwise: the count tables below hold both for every converter case."""
 import ctypes as C
 import os
-import subprocess
-import sys
 
 import numpy as np
 import pytest
 
-from oracle import oracle as O
 from conftest import skip_unless_host_libm_is_the_restated_one
-from test_gpu_src_batch import Stream, make_batch, ref_converted
+from gpu_support import FILL, GOLD, GOLDEN_CLI as M, CallBufs, Image, batch_vs_single_vs_reference, cur_stream, dev, host_crc, run_cli, states, sync
+from hmp3_amd import api, synth
+from oracle import oracle as O
+from output_checks import check_crc, check_dense, check_idle_rows
+from src_cases import Stream, make_batch, make_rows, ref_converted
 
 pytestmark = pytest.mark.gpu
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FILL = 0xA5
 FORMATS = [(8, 0), (16, 0), (24, 0), (32, 0), (32, 1)]
 # (source rate, encode rate) -> the converter's case (hx_src.cpp hx_src_init): 0 copy, 1 exact 1:2, 2 linear up-sampling,
 # 3 one polyphase bank (48000 -> 32000: 2 x 19 taps of memory), 4 two stages with carried intermediate samples
@@ -33,11 +32,6 @@ PAIRS = [(44100, 44100), (22050, 44100), (32000, 44100), (48000, 32000), (44100,
 # take one row each
 TABLE = [[3, 0, 1, 2], [2, 0, 0, 1], [0, 0, 3, 1], [1, 3, 0, 2]]
 HAVE_REF = O.ref() is not None
-
-
-def api():
-    from hmp3_amd import api as A
-    return A
 
 
 def mk(source, bits, is_float, **kw):
@@ -80,23 +74,9 @@ def layout_streams(layout):
     return out
 
 
-def make_rows(b, streams, pos, nf, counts, garbage=None, extra=0):
-    """the call's rows, row i from stream i's first unconsumed byte; garbage: that byte over everything beyond what the
-    stream's counts[i] calls read (the whole row of a stream that sits the call out)"""
-    stride = b.in_stride(nf) + extra
-    rows = np.zeros((len(streams), stride), np.uint8)
-    for i, s in enumerate(streams):
-        chunk = np.frombuffer(s.data[pos[i]:pos[i] + stride], np.uint8)
-        rows[i, :len(chunk)] = chunk
-        if garbage is not None:
-            rd = b.schedule(i, counts[i])[1] if counts[i] else 0
-            rows[i, rd:] = garbage
-    return rows
-
-
 def raw_call(b, rows, nf, counts, off=None, stats=True, crc=True, fn=None, n=None):
     """the C call into prefilled arrays of the caller's -> (return value, rows, out_bytes, in_used, stats, crc)"""
-    A = api()
+    A = api
     n = b.n if n is None else n
     fn = fn or A.lib().hx_batch_encode_src_counts_host
     stride = int(A.lib().hx_multi_out_stride(b.h, nf)) if fn.__name__.startswith("hx_multi") else b.out_stride(nf)
@@ -111,15 +91,6 @@ def raw_call(b, rows, nf, counts, off=None, stats=True, crc=True, fn=None, n=Non
 
 def untouched(out, nb, used, st, cr):
     return (out == FILL).all() and (nb == -7).all() and (used == -7).all() and (st == -1).all() and (cr == 0xBEEF).all()
-
-
-def states(b):
-    return [b.get_stream_state(i) for i in range(b.n)]
-
-
-def host_crc(data):
-    data = bytes(data)
-    return int(api().lib().hx_xing_update_crc(0, data, len(data)))
 
 
 def check_totals(streams, outs, pos, done):
@@ -171,10 +142,10 @@ def test_an_idle_stream_is_untouched_and_garbage_is_never_read(k6_build):
     entered = [(0, 0)] * S
     for c, counts in enumerate(table):
         rcz, outz, nbz, usedz, stz, crz = raw_call(bz, make_rows(bz, streams, pos, nf, counts, garbage=0), nf, counts)
-        before = states(bg)
+        before = states(bg, single=True)
         rc, out, nb, used, st, cr = raw_call(bg, make_rows(bg, streams, pos, nf, counts, garbage=0xFF), nf, counts)
         assert rcz == 0 and rc == 0 and bz.status() == 0 and bg.status() == 0
-        after = states(bg)
+        after = states(bg, single=True)
         for i, n in enumerate(counts):
             at = "call %d stream %d (count %d)" % (c, i, n)
             if n == 0:
@@ -216,7 +187,7 @@ def test_frame_offsets_under_counts(k6_build):
                 else:
                     off[i, f] = -1 if f % 2 else 10 * rows.shape[1]
         rc, out, nb, used, st, cr = raw_call(b, rows, nf, counts, off=off)
-        assert rc == 0, api().last_error()
+        assert rc == 0, api.last_error()
         assert b.status() == 0
         for i, n in enumerate(counts):
             outs[i] += out[i, :nb[i]].tobytes()
@@ -239,30 +210,26 @@ def test_optional_outputs_of_a_converting_call_under_counts(k6_build):
     repeat the end-of-call values, packet sizes are {0, 0} and no packet byte is written, crc[i][f] is the host CRC of row
     i's e[f] bytes, and the dense image follows out_bytes"""
     import torch
-    from test_gpu_frame_counts import Outputs
     streams = [layout_streams("stereo")[i] for i in (1, 2, 4, 7, 8, 11)]
     S, nf = len(streams), 4
     counts = [2, 0, 4, 1, 3, 0]
     bu, bc = make_batch(streams, nf), make_batch(streams, nf)
     rows = make_rows(bu, streams, [0] * S, nf, None)
-    dev = torch.device("cuda:0")
-    d_rows = torch.from_numpy(rows).to(dev)
-    q = torch.cuda.current_stream().cuda_stream
+    d_rows = torch.from_numpy(rows).to(dev())
+    q = cur_stream()
     res = []
     for b, cn in ((bu, None), (bc, counts)):
-        o = Outputs(b, nf, dense=True)
-        o.set_on(b, crc=True)
-        torch.cuda.synchronize()
-        used = b.encode_src_counts_device(d_rows.data_ptr(), rows.shape[1], nf, cn, o.out.data_ptr(), o.stride, o.nb.data_ptr(), stream=q)
-        torch.cuda.synchronize()
+        o = CallBufs(b, nf, rows_fill=FILL, counters=True, crc=True, packets=4096, image=Image(b.n, b.dense_bound(nf), guard=0)).set_on(b)
+        used = b.encode_src_counts_device(d_rows.data_ptr(), rows.shape[1], nf, cn, o.ptr, o.stride, o.nb.data_ptr(), stream=q)
+        sync()
         assert b.status() == 0
-        o.check_crc()
-        o.check_dense()
+        check_crc(o)
+        check_dense(o)
         res.append((o, used))
     (ou, usedu), (oc, usedc) = res
-    oc.check_idle_rows(counts)
+    check_idle_rows(oc, counts)
     (ru, nbu), (rc_, nbc) = ou.rows(), oc.rows()
-    (pku, pkbu, stu), (pkc, pkbc, stc) = ou.host(), oc.host()
+    (pku, pkbu, stu), (pkc, pkbc, stc) = ou.packets(), oc.packets()
     for i, n in enumerate(counts):
         at = "stream %d (count %d)" % (i, n)
         assert (stc[i, :n] == stu[i, :n]).all() and (pkbc[i, :n] == pkbu[i, :n]).all() and (pkc[i, :n] == pku[i, :n]).all(), at
@@ -289,7 +256,7 @@ def test_optional_outputs_of_a_converting_call_under_counts(k6_build):
 
 def make_used(s, n):
     """input bytes the stream's first n calls consume, from the host converter's schedule"""
-    A = api()
+    A = api
     L = A.lib()
     h = L.hx_src_create()
     cut = C.c_int(0)
@@ -305,7 +272,7 @@ def test_refusals_leave_the_batch_usable(k6_build):
     """counts of -1 and nframes + 1, a row too short for a stream's n calls and crc without stats are refused (-1), the count
     refusals naming the stream; a row too short only for nframes calls is accepted.  After each refusal the prefilled outputs
     are untouched, every checkpoint and schedule() are as before, and the calls that follow match the reference"""
-    A = api()
+    A = api
     streams = [layout_streams("stereo")[i] for i in (9, 6, 2)]     # (stream 0: 8 bytes per sample frame, the widest rows)
     S, nf = len(streams), 3
     b = make_batch(streams, nf)
@@ -327,11 +294,11 @@ def test_refusals_leave_the_batch_usable(k6_build):
     refused = [(full, [2, -1, 2], True, "stream 1"), (full, [2, 2, nf + 1], True, "stream 2"),
                (np.ascontiguousarray(full[:, :short]), [2, 1, 1], True, "stream 0"), (full, [1, 1, 1], False, "")]
     for rows, counts, stats, who in refused:
-        before, sched = states(b), [b.schedule(i, nf)[0].tolist() for i in range(S)]
+        before, sched = states(b, single=True), [b.schedule(i, nf)[0].tolist() for i in range(S)]
         rc, *o = raw_call(b, rows, nf, counts, stats=stats)
         assert rc == -1 and who in A.last_error(), (counts, A.last_error())
         assert untouched(*o), "a refused call wrote an output"
-        assert states(b) == before and [b.schedule(i, nf)[0].tolist() for i in range(S)] == sched
+        assert states(b, single=True) == before and [b.schedule(i, nf)[0].tolist() for i in range(S)] == sched
     with pytest.raises(TypeError):
         b.encode_src_counts_host(full, nf, [1, 1, 1], crc=True)
     with pytest.raises(RuntimeError, match="stream 2"):
@@ -376,7 +343,7 @@ def test_multi_over_two_blocks_on_one_device(k6_build):
     """hx_multi_encode_src_counts_host: five streams in blocks of 3 + 2 on device 0, three calls with zeros among the counts,
     bytes per stream as in the first test; a count out of range in the second block refuses the call for all streams before a
     block starts, names the stream by its number over all blocks and moves none"""
-    A = api()
+    A = api
     L = A.lib()
     streams = [layout_streams("stereo")[i] for i in (3, 8, 5, 10, 0)]
     S, nf = len(streams), 3
@@ -423,21 +390,8 @@ def test_multi_over_two_blocks_on_one_device(k6_build):
 
 # ---- the command line: -batch takes files at any rate and -A (hmp3_amd/cli/hmp3amd.cpp, the converting route) ----
 
-EXE = os.path.join(ROOT, "hmp3_amd", "hmp3amd")
 SRC_CASES = ["cli_src_11k_to_22k_s16", "cli_src_8k_to_16k_u8_mono", "cli_src_32k_to_44k_f32", "cli_src_48k_to_24k_s24", "cli_src_44k_to_32k_s16",
              "cli_src_44k_to_22k_downmix", "cli_src_44k_to_16k_f32_nopad", "cli_src_48k_to_22k_s24_nopad", "cli_src_24k_to_22k_s32_nopad"]
-
-
-def golden_cli():
-    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
-    import make_golden_cli as M
-    return M
-
-
-def run_cli(args):
-    assert os.path.exists(EXE), "hmp3_amd/build.sh builds the CLI"
-    r = subprocess.run([EXE] + args, capture_output=True, timeout=120)
-    assert r.returncode == 0, r.stderr.decode()[-400:]
 
 
 @pytest.mark.one_k6_build
@@ -445,12 +399,11 @@ def run_cli(args):
 def test_cli_batch_of_one_converting_file_equals_the_reference_cli(name, tmp_path, k6_build):
     """`hmp3amd -batch in.wav out.mp3 <flags>` on each sample-rate-conversion case of the whole-file goldens: the file the
     reference's command line wrote (tests/golden/<name>.mp3), tag frame, TOC and MusicCRC included"""
-    M = golden_cli()
     seed, nsamp, sr, as_float, bursts, flags = M.CASES[name]
     wav, mp3 = str(tmp_path / "in.wav"), str(tmp_path / "out.mp3")
     M.write_wav(wav, M.case_pcm(name), sr, as_float, M.CONTAINER.get(name))
     run_cli(["-batch", wav, mp3] + flags)
-    assert open(mp3, "rb").read() == open(os.path.join(ROOT, "tests", "golden", name + ".mp3"), "rb").read()
+    assert open(mp3, "rb").read() == open(os.path.join(GOLD, name + ".mp3"), "rb").read()
 
 
 @pytest.mark.one_k6_build
@@ -458,25 +411,12 @@ def test_cli_batch_of_converting_files_of_different_lengths(tmp_path, k6_build):
     """one `-batch -A32000 -B64` run of three stereo files - 48 kHz s24, 44.1 kHz s16, 32 kHz f32, of 5, 40 and 130 output
     frames, so two of them end inside the first call of 96 frames - writes the files of the three single-file runs byte for
     byte, and the reference binary's where it is built"""
-    from hmp3_amd import synth
-    M = golden_cli()
     flags = ["-A32000", "-B64"]
-    files, args = [], []
+    files = []
     for i, (sr, fmt, frames) in enumerate([(48000, 24, 5), (44100, False, 40), (32000, True, 130)]):
         nsamp = frames * 1152 * sr // 32000 - 301 * i - 7
         pcm = synth.stream_pcm(9500 + i, nsamp // 1152 + 1, sr=sr, rho=0.5, bursts=i != 1)[:nsamp]
         wav = str(tmp_path / ("in%d.wav" % i))
         M.write_wav(wav, pcm, sr, fmt)
-        files.append(wav)
-        args += [wav, str(tmp_path / ("batch%d.mp3" % i))]
-    run_cli(["-batch"] + args + flags)
-    ref = os.path.join(ROOT, "oracle", "_ref", "hmp3")
-    for i, wav in enumerate(files):
-        got = open(str(tmp_path / ("batch%d.mp3" % i)), "rb").read()
-        one = str(tmp_path / ("single%d.mp3" % i))
-        run_cli([wav, one] + flags)
-        assert got == open(one, "rb").read(), "file %d differs from its single-file run" % i
-        if os.path.exists(ref):
-            theirs = str(tmp_path / ("ref%d.mp3" % i))
-            subprocess.run([ref, wav, theirs] + flags, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=120)
-            assert got == open(theirs, "rb").read(), "file %d differs from the reference binary's" % i
+        files.append(("file %d" % i, wav, str(tmp_path / ("batch%d.mp3" % i))))
+    batch_vs_single_vs_reference(files, flags)

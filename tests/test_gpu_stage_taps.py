@@ -11,14 +11,10 @@ import pytest
 import stage_tap_cases as K
 from conftest import skip_unless_host_libm_is_the_restated_one
 from stage_taps import TapBatch
+from hmp3_amd import api
 
 pytestmark = pytest.mark.gpu
 COMPARED = {}       # case -> the call-boundary transitions its last run compared
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 def run_case(name):
@@ -27,7 +23,7 @@ def run_case(name):
     pcm = K.case_pcm(name)
     calls = K.plan(name)
     stride = max(max(row) for row in calls)
-    tb = TapBatch(api(), K.control(name), S, stride, K.taps(name))
+    tb = TapBatch(api, K.control(name), S, stride, K.taps(name))
     done = [0] * S
     for row in calls:
         blk = np.zeros((S, stride * 1152) + pcm.shape[2:], dtype=pcm.dtype)

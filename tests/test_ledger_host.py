@@ -13,24 +13,9 @@ import numpy as np
 import pytest
 
 from hmp3_amd import api
+from ledger_cases import record_tag, replay
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-HEAD_FLAGS = 1 | 2 | 8 | 4 | 0x40       # what `-X2` asks for: frames, bytes, scale, TOC, LAME info
-VBR_SCALE = 50                          # a VBR file: the tag keeps its TOC at every bitrate
-
-
-def tag_frame(x, fpc):
-    """a new tag frame through hx_xing_header (which also empties x's seek points) -> (buffer, its size)"""
-    buf = (C.c_ubyte * 2048)()
-    n = api.lib().hx_xing_header(x, 44100 if fpc == 1 else 22050, 1, 1, 1, HEAD_FLAGS, 0, 0, VBR_SCALE, None, buf, None, None, 128)
-    assert n > 0
-    return buf, n
-
-
-def finish(x, buf, n, fpc, frames, nbytes, crc, samples):
-    sr = 44100 if fpc == 1 else 22050
-    assert api.lib().hx_xing_update_info(x, frames, n + nbytes, VBR_SCALE, None, buf, None, None, samples, n + nbytes, 16000, sr, sr, crc) == 1
-    return bytes(buf[:n])
 
 
 class File:
@@ -58,41 +43,6 @@ class File:
     def crc_of(self, a, b, seed=0):
         d = self.data[a:b]
         return int(api.lib().hx_xing_update_crc(seed, d.ctypes.data, len(d)))
-
-
-def replay(f):
-    """Tagger::after_call + job_write -> (tag frame, frames, bytes, crc, halvings of the seek table)"""
-    L = api.lib()
-    x = L.hx_xing_create()
-    buf, n = tag_frame(x, f.fpc)
-    counter, every, halvings = 0, 1, 0
-    for u in range(f.ncalls):
-        counter -= 1
-        if counter <= 0:
-            counter = L.hx_xing_toc(x, int(f.fr[u]) + 1, int(f.by[u]) + n)
-            halvings += counter != every
-            every = counter
-    u = f.ncalls
-    while u < len(f.fr) and f.fr[u - 1] < f.expected:
-        u += 1
-    assert f.fr[u - 1] >= f.expected and u - 1 == f.end
-    frames, nbytes = int(f.fr[u - 1]), int(f.by[u - 1])
-    crc = f.crc_of(0, nbytes)
-    tag = finish(x, buf, n, f.fpc, frames, nbytes, crc, f.samples)
-    L.hx_xing_destroy(x)
-    return tag, frames, nbytes, crc, halvings, n
-
-
-def record_tag(rec, fpc, samples):
-    """the finished tag frame from a record alone: hx_xing_header, hx_xing_load_points, hx_xing_update_info"""
-    L = api.lib()
-    x = L.hx_xing_create()
-    buf, n = tag_frame(x, fpc)
-    assert n == rec.head_bytes
-    api.xing_load_points(x, rec)
-    tag = finish(x, buf, n, fpc, rec.frames, rec.bytes, rec.crc, samples)
-    L.hx_xing_destroy(x)
-    return tag
 
 
 def through_ledger(f, cuts, head_bytes):

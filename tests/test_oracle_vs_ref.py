@@ -221,7 +221,7 @@ def test_carried_state_matches_every_frame():
 
 def test_random_configurations_byte_identical():
     """the random controls of tests/test_gpu_parity.py::test_random_configurations_against_the_oracle, oracle vs reference"""
-    from tests.test_gpu_parity import random_control
+    from parity_cases import random_control
     rng = np.random.default_rng(20240917)
     done = 0
     for trial in range(200):

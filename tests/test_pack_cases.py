@@ -10,13 +10,9 @@ import pytest
 
 import pack_cases as P
 from oracle import oracle as O
+from hmp3_amd import api
 
 ALL_LISTS = P.LIST_NAMES + ("status",)
-
-
-def api():
-    from hmp3_amd import api as a
-    return a
 
 
 def need_ref():
@@ -26,7 +22,7 @@ def need_ref():
 
 def host_table(name, dtype, n, **kw):
     a = np.zeros(n, dtype)
-    assert api().lib().hx_debug_host_table(C.byref(api().default_control(**kw)), name.encode(), a.ctypes.data, a.nbytes) == a.nbytes, name
+    assert api.lib().hx_debug_host_table(C.byref(api.default_control(**kw)), name.encode(), a.ctypes.data, a.nbytes) == a.nbytes, name
     return a
 
 
@@ -261,7 +257,7 @@ def refused(b):
     rows = b["rows"].copy()
     rc, status = P.debug_pack(b)
     assert rc == -1 and status == -1 and np.array_equal(rows, b["rows"])
-    return api().lib().hx_last_error().decode()
+    return api.lib().hx_last_error().decode()
 
 
 def small():
