@@ -1241,16 +1241,51 @@ class Mp3Enc:
         self.packet_sizes = (nb[0], nb[1])
         return x.in_bytes, bytes(self._out[: x.out_bytes]), bytes(pk[: nb[0] + nb[1]])
 
+    def _packet_call(self, fn, pcm_ptr, bs_out, packet):
+        """a *_Packet call; bs_out / packet False: that argument NULL (its part of the result is then None)"""
+        pk = (C.c_ubyte * 4096)() if packet else None
+        nb = (C.c_int * 2)(-1, -1)
+        x = fn(self.h, pcm_ptr, self._out if bs_out else None, pk, nb)
+        self.packet_sizes = (nb[0], nb[1])      # (left at -1, -1 by a call without a packet)
+        return x.in_bytes, x.out_bytes, bytes(self._out[: x.out_bytes]) if bs_out else None, bytes(pk[: nb[0] + nb[1]]) if packet else None
+
     def MP3_audio_encode(self, pcm_i16):
         pcm = np.ascontiguousarray(pcm_i16, dtype=np.int16)
         x = lib().hx_enc_MP3_audio_encode(self.h, pcm.ctypes.data, self._out)
         return x.in_bytes, bytes(self._out[: x.out_bytes])
 
+    def MP3_audio_encode_Packet(self, data, bs_out=True, packet=True):
+        """data: the source's bytes from the first unconsumed one, in the source's format: bytes (copied), or whatever ctypes
+        takes for a pointer, such as byref(buffer, position)
+        -> (in_bytes, out_bytes, bitstream bytes or None, packet bytes or None); self.packet_sizes = nbytes_out[2]"""
+        buf = (C.c_ubyte * len(data)).from_buffer_copy(data) if isinstance(data, (bytes, bytearray)) else data
+        return self._packet_call(lib().hx_enc_MP3_audio_encode_Packet, buf, bs_out, packet)
+
+    def L3_audio_encode_Packet_opt(self, pcm_f32, bs_out=True, packet=True):
+        """L3_audio_encode_Packet whose bs_out or packet argument may be NULL
+        -> (in_bytes, out_bytes, bitstream bytes or None, packet bytes or None)"""
+        pcm = np.ascontiguousarray(pcm_f32, dtype=np.float32)
+        return self._packet_call(lib().hx_enc_L3_audio_encode_Packet, pcm.ctypes.data, bs_out, packet)
+
+    def debug_calls(self):
+        """(calls made the plain way, calls replayed from the recorded graph, the graph's state) since the last init
+        (hx_enc_debug_calls)"""
+        out = (C.c_int * 3)()
+        if lib().hx_enc_debug_calls(self.h, out) != 0:
+            raise RuntimeError("hx_enc_debug_calls failed")
+        return out[0], out[1], out[2]
+
     def L3_audio_encode_get_frames(self):
         return int(lib().hx_enc_get_frames(self.h))
 
+    def L3_audio_encode_get_bitrate(self):
+        return int(lib().hx_enc_get_bitrate(self.h))
+
     def L3_audio_encode_get_bitrate_float(self):
         return float(lib().hx_enc_get_bitrate_float(self.h))
+
+    def L3_audio_encode_get_bitrate2_float(self):
+        return float(lib().hx_enc_get_bitrate2_float(self.h))
 
     def L3_audio_encode_get_frames_bytes(self):
         p = lib().hx_enc_get_frames_bytes(self.h)

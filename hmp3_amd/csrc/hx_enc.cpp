@@ -4,7 +4,18 @@
 #include <stddef.h>
 #include <chrono>
 #include <atomic>
+#include <mutex>
+#include <shared_mutex>
 #include "hx_rt.h"
+
+// While a stream of the process is being captured - in thread-local mode too - the runtime refuses every other thread's
+// hipDeviceSynchronize (hipErrorStreamCaptureUnsupported) and null-stream calls such as hipMemcpy
+// (hipErrorStreamCaptureImplicit), and the refused call invalidates the capture.  The plain calls, init and destroy make
+// such calls, so encoders driven from threads of their own would fail each other's calls and lose their graphs: an
+// encoder records its graph alone (exclusive), and everything else an encoder does on the device shares the lock.
+static std::shared_mutex g_record_lock;
+using EncUse = std::shared_lock<std::shared_mutex>;
+using EncRecord = std::unique_lock<std::shared_mutex>;
 
 struct hx_enc {
     int device = 0;
@@ -29,6 +40,7 @@ struct hx_enc {
     unsigned char *h_out = nullptr;     // page-locked, coherent: [byte count | frame counter | sequence word | ... 256 | the call's bitstream], written by the packing workgroup
     int graph_state = 0;                // 0 = not built yet, 1 = ready, -1 = not available (disabled, or the build failed: plain calls)
     int plain_calls = 0;                // calls made the plain way since init (the first ones: they also load the kernels' code objects)
+    int graph_calls = 0;                // calls replayed from the graph since init (hx_enc_debug_calls)
 };
 #define HX_ENC_GRAPH_OFF 256
 
@@ -42,6 +54,7 @@ static void enc_graph_drop(hx_enc *e)
     if (e->h_out) { hipHostFree(e->h_out); e->h_out = nullptr; }
     e->graph_state = 0;
     e->plain_calls = 0;
+    e->graph_calls = 0;
 }
 
 extern "C" hx_enc *hx_enc_create(int device)
@@ -54,6 +67,7 @@ extern "C" hx_enc *hx_enc_create(int device)
 extern "C" void hx_enc_destroy(hx_enc *e)
 {
     if (!e) return;
+    EncUse use(g_record_lock);
     enc_graph_drop(e);
     if (e->d_packet) hipFree(e->d_packet);
     if (e->d_packet_bytes) hipFree(e->d_packet_bytes);
@@ -64,6 +78,7 @@ extern "C" void hx_enc_destroy(hx_enc *e)
 
 extern "C" int hx_enc_L3_audio_encode_init(hx_enc *e, const HX_E_CONTROL *ec)
 {
+    EncUse use(g_record_lock);
     enc_graph_drop(e);
     if (e->b) { hx_batch_destroy(e->b); e->b = nullptr; }       // re-init is legal (mp3enc.cpp:267-272)
     int r = hx_resolve((const HxControl *) ec, &e->p);
@@ -149,7 +164,8 @@ static bool enc_graph_call(hx_enc *e, const float *pcm, int *nb, unsigned *frame
 }
 
 // opt: the call's optional outputs (the packet of the *_Packet entry points; the encoder's batch has none set)
-static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, int in_bytes, const OptOut &opt = OptOut())
+// packet_call: a *_Packet entry point's call, plain also where its packet argument is NULL (include/hmp3_amd.h)
+static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, int in_bytes, const OptOut &opt = OptOut(), bool packet_call = false)
 {
     HX_IN_OUT x = {in_bytes, 0};
     int nb = 0;
@@ -158,19 +174,22 @@ static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, 
     hx_batch *b = e->b;
     // The graph replays a call with exactly the arguments it was recorded with: anything optional (packets, debug taps)
     // goes the plain way, and so do the first two calls (which load the kernels).
-    const bool plain = b->debug || opt.packet || b->poisoned || b->inflight || e->graph_state < 0 || e->plain_calls < 2;
+    const bool plain = b->debug || opt.packet || packet_call || b->poisoned || b->inflight || e->graph_state < 0 || e->plain_calls < 2;
     if (!plain && e->graph_state == 0) {
         const char *env = getenv("HMP3AMD_ENC_GRAPH");
+        const auto record = [&] { EncRecord alone(g_record_lock); return enc_graph_build(e); };
         if (env && atoi(env) == 0) e->graph_state = -1;
-        else if (enc_graph_build(e) == 0) e->graph_state = 1;
+        else if (record() == 0) e->graph_state = 1;
         else {      // plain calls from here on (the staging stays allocated until the encoder is re-initialised or destroyed)
             if (e->gexec) { hipGraphExecDestroy(e->gexec); e->gexec = nullptr; }
             e->graph_state = -1;
         }
     }
+    EncUse use(g_record_lock);
     if (!plain && e->graph_state == 1) {
         if (!enc_graph_call(e, pcm, &nb, &frames)) return x;
         bs = e->h_out + HX_ENC_GRAPH_OFF;
+        e->graph_calls++;
     } else {
         // (encode_host's steps, with the call's own optional outputs in the record)
         const long long cap = (long long) e->outbuf.size();
@@ -181,7 +200,10 @@ static HX_IN_OUT encode_one(hx_enc *e, const float *pcm, unsigned char *bs_out, 
         frames = (unsigned) hx_batch_frames_bytes(b, 0).a;
         e->plain_calls++;
     }
-    memcpy(bs_out, bs, (size_t) nb);
+    // a *_Packet call without a bitstream buffer: the frames count as sent, their bytes are neither returned nor counted
+    // (mp3enc.cpp:2964-2994: bytesout = bs_out - bs_out0 stays 0)
+    if (bs_out) memcpy(bs_out, bs, (size_t) nb);
+    else nb = 0;
     x.out_bytes = nb;
     e->bytes += nb;
     e->ave = e->ave + ((((nb << 8) - e->ave)) >> (e->p.h_id ? 7 : 6));    // mp3enc.cpp:2328 / :2589
@@ -201,18 +223,18 @@ extern "C" HX_IN_OUT hx_enc_L3_audio_encode(hx_enc *e, const float *pcm, unsigne
 // nbytes_out[1] bytes); packet may be NULL.
 static HX_IN_OUT encode_packet(hx_enc *e, const void *pcm, int mp3_entry, unsigned char *bs_out, unsigned char *packet, int nbytes_out[2])
 {
-    std::vector<unsigned char> scratch;
-    if (!bs_out) { scratch.resize(e->outbuf.size()); bs_out = scratch.data(); }
     OptOut opt;
     if (packet) {
+        EncUse use(g_record_lock);
         hipSetDevice(e->device);
         if (!e->d_packet) { hipMalloc((void **) &e->d_packet, 4096); hipMalloc((void **) &e->d_packet_bytes, 2 * sizeof(int)); }
         opt.packet = e->d_packet; opt.packet_stride = 4096; opt.packet_bytes = e->d_packet_bytes;
     }
     float t[2304];      // (the MP3_audio_encode entry: convert, then encode)
     const int in_bytes = mp3_entry ? hx_src_convert(e->src, (const unsigned char *) pcm, t, nullptr) : 4608 * e->p.nchan;
-    HX_IN_OUT x = encode_one(e, mp3_entry ? t : (const float *) pcm, bs_out, in_bytes, opt);
+    HX_IN_OUT x = encode_one(e, mp3_entry ? t : (const float *) pcm, bs_out, in_bytes, opt, true);
     if (packet) {
+        EncUse use(g_record_lock);
         int n[2] = {0, 0};      // an MPEG-2 call returns two single-granule packets back to back (mp3enc.cpp:3363)
         hipMemcpy(n, e->d_packet_bytes, 2 * sizeof(int), hipMemcpyDeviceToHost);
         hipMemcpy(packet, e->d_packet, (size_t) (n[0] + n[1]), hipMemcpyDeviceToHost);
@@ -330,11 +352,22 @@ extern "C" void hx_enc_out_stats(hx_enc *e)
 {
     int calls = 0;
     if (e && e->b) {
+        EncUse use(g_record_lock);
         hipSetDevice(e->b->device);
         hipDeviceSynchronize();
         hipMemcpy(&calls, (char *) e->b->d_st + offsetof(HxStream, call_count), sizeof(int), hipMemcpyDeviceToHost);
     }
     fprintf(stderr, "\n ba long  %6d %6d %6d %6d %6d %6d %6d %6d %6d", calls, 0, 0, 0, 0, 0, 0, 0, 0);
+}
+
+// Which route the calls since init took (include/hmp3_amd.h, "test taps"): plain calls, replayed calls, graph_state.
+extern "C" int hx_enc_debug_calls(hx_enc *e, int out[3])
+{
+    if (!e || !out) return -1;
+    out[0] = e->plain_calls;
+    out[1] = e->graph_calls;
+    out[2] = e->graph_state;
+    return 0;
 }
 
 extern "C" unsigned hx_enc_get_frames(hx_enc *e) { return e->frames; }

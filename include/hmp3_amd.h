@@ -79,7 +79,8 @@ void hx_enc_info_head(hx_enc *e, HX_MPEG_HEAD *head);       /* mp3enc.cpp:3498 *
    packet: header, side info with main_data_begin 0, unpadded main data; nbytes_out[0] = its size,
    nbytes_out[1] = 0.  At the MPEG-2 rates (16 / 22.05 / 24 kHz) a call yields two single-granule
    frames (mp3enc.cpp:3301-3440): two packets back to back, nbytes_out[0] then nbytes_out[1] bytes.
-   bs_out or packet may be NULL. */
+   bs_out or packet may be NULL.  As in the reference, a call with bs_out NULL returns out_bytes 0 and its frames are
+   counted as sent while their bytes are not (mp3enc.cpp:2964-2994); a call with packet NULL leaves nbytes_out alone. */
 HX_IN_OUT hx_enc_L3_audio_encode_Packet(hx_enc *e, const float *pcm, unsigned char *bs_out, unsigned char *packet, int nbytes_out[2]);
 HX_IN_OUT hx_enc_MP3_audio_encode_Packet(hx_enc *e, const unsigned char *pcm, unsigned char *bs_out, unsigned char *packet, int nbytes_out[2]);
 void hx_enc_info_string(hx_enc *e, char *s);                /* mp3enc.cpp:3505, <= 80 chars */
@@ -864,6 +865,17 @@ int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long l
    bytes, returns bytes, -1 for an unknown name. */
 long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap);
 void hx_batch_debug_enable(hx_batch *b, int on);
+/* Which route the calls of an hx_enc took since its last init (a successful or a rejected one; both reset the counters):
+   out[0] = calls made the plain way, out[1] = calls replayed from the recorded graph, out[2] = the graph's state (0 = not
+   recorded yet, 1 = ready, -1 = not available: HMP3AMD_ENC_GRAPH=0, or the recording failed and the calls go the plain way).
+   Returns 0 (-1: null argument).  Changes nothing.  The contract tests/test_gpu_enc.py holds the encoder to:
+   - the first two calls after an init are plain; from the third on hx_enc_L3_audio_encode and hx_enc_MP3_audio_encode are
+     replays, whatever the control (every kernel family, a call that emits no byte, two frames or three), with the bytes and
+     counters of the plain route;
+   - the *_Packet calls, and every call under HMP3AMD_ENC_GRAPH=0 (read when an encoder first considers recording), are plain;
+   - several live encoders - beside each other and beside a batch with a pipelined submit in flight - may be driven in any
+     interleaving from one thread, and each from a thread of its own; one encoder is driven by one thread at a time. */
+int hx_enc_debug_calls(hx_enc *e, int out[3]);
 /* The first-generation allocator (intensity stereo, dual channel; reference bitallo1.cpp) calls libm's logf / log10f, which
    are not correctly rounded: what the reference encodes depends on the C library it is linked with.  The kernels restate
    glibc 2.35's (hmp3_amd/csrc/hx_libm32.h).  hx_libc_version: the host's C library; hx_libm_spot_check: how many of n

@@ -86,6 +86,9 @@ def ref():
             _ref.ref_dump.argtypes = [C.c_void_p, C.c_void_p]
             _ref.ref_frames.argtypes = [C.c_void_p]
             _ref.ref_frames.restype = C.c_uint
+            if hasattr(_ref, "ref_bitrate2_float"):     # (a reference build made before the harness had the getters lacks them)
+                _ref.ref_bitrate2_float.argtypes = _ref.ref_bitrate_float.argtypes = _ref.ref_bitrate.argtypes = [C.c_void_p]
+                _ref.ref_bitrate2_float.restype = _ref.ref_bitrate_float.restype = C.c_float
             _ref.ref_mbLogC.argtypes = [C.c_float]
             _ref.ref_mbExp.argtypes = [C.c_int]
             _ref.ref_mbExp.restype = C.c_float
@@ -225,6 +228,10 @@ class RefEncoder:
         """L3_audio_encode_get_frames"""
         return int(self.r.ref_frames(self.h))
 
+    def bitrates(self):
+        """(L3_audio_encode_get_bitrate2_float, _get_bitrate_float as float32, _get_bitrate)"""
+        return np.float32(self.r.ref_bitrate2_float(self.h)), np.float32(self.r.ref_bitrate_float(self.h)), int(self.r.ref_bitrate(self.h))
+
     def dump(self):
         d = RefDump()
         self.r.ref_dump(self.h, C.byref(d))
@@ -362,6 +369,11 @@ def _pack_frame_args(segs):
 def ref_has_pack_frame():
     """whether the reference build at hand was made with ref_pack_frame in its harness"""
     return ref() is not None and hasattr(ref(), "ref_pack_frame")
+
+
+def ref_has_getters():
+    """whether the reference build at hand was made with the bitrate getters in its harness"""
+    return ref() is not None and hasattr(ref(), "ref_bitrate2_float")
 
 
 def _ref_pack_frame_direct(n, hdr, val, ln, ix, sg, out, bits):

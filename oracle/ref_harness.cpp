@@ -103,6 +103,10 @@ int ref_encode_packet(void *h, float *pcm, unsigned char *out, unsigned char *pa
 int ref_encode_s16(void *h, short *pcm, unsigned char *out) { return ((CMp3Enc *) h)->MP3_audio_encode((unsigned char *) pcm, out).out_bytes; }
 unsigned ref_frames(void *h) { return ((CMp3Enc *) h)->L3_audio_encode_get_frames(); }
 void ref_info_ec(void *h, E_CONTROL *ec) { ((CMp3Enc *) h)->L3_audio_encode_info_ec(ec); }
+/* the reference's bitrate getters (pin tests/enc_cases.py's restatement of the running average, get_bitrate2_float) */
+float ref_bitrate_float(void *h) { return ((CMp3Enc *) h)->L3_audio_encode_get_bitrate_float(); }
+float ref_bitrate2_float(void *h) { return ((CMp3Enc *) h)->L3_audio_encode_get_bitrate2_float(); }
+int ref_bitrate(void *h) { return ((CMp3Enc *) h)->L3_audio_encode_get_bitrate(); }
 
 /* encode nframes of int16 stereo PCM in one call (timing loop for bench.py's cpu_baseline) */
 long ref_encode_stream_s16(void *h, short *pcm, int nframes, unsigned char *out, long out_cap)

@@ -146,13 +146,15 @@ def ref_converted(s, target, nframes):
     return np.concatenate(ys)
 
 
-def host_converted(s, nframes):
-    """this library's host converter over the source's first nframes calls -> (float32 [nframes * 1152(, 2)], bytes used per call)"""
+def host_converted(s, nframes, target=None):
+    """this library's host converter over the source's first nframes calls -> (float32 [nframes * 1152(, 2)], bytes used per
+    call, channels); target: the encode rate (None: the source's mpeg_select where it is a rate, else the source's rate; a
+    source whose mpeg_select is 1 or 2 - "an MPEG-1 / MPEG-2 rate" - passes the rate api.src_encode_control derives)"""
     L = api.lib()
     tch = 1 if (s.channels == 1 or s.mono_convert) else 2
     h = L.hx_src_create()
     cut = C.c_int(0)
-    assert L.hx_src_init(h, s.source, s.channels, s.bits, s.is_float, s.mpeg_select or s.source, tch, C.byref(cut)) > 0
+    assert L.hx_src_init(h, s.source, s.channels, s.bits, s.is_float, target or s.mpeg_select or s.source, tch, C.byref(cut)) > 0
     buf = (C.c_ubyte * len(s.data)).from_buffer_copy(s.data)
     ys, used, pos = [], [], 0
     for _ in range(nframes):
