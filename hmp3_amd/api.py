@@ -171,6 +171,24 @@ def libm_report(points=1000):
     return {"glibc": L.hx_libc_version().decode(), "points": points, "mismatches": int(L.hx_libm_spot_check(points))}
 
 
+def _math_operands(arrays):
+    """the operands of a debug math call as uint32 [k][n]: each array's 32-bit patterns, none converted"""
+    ops = [np.ascontiguousarray(a).reshape(-1) for a in arrays]
+    if not ops or any(a.dtype.itemsize != 4 or a.size != ops[0].size for a in ops):
+        raise ValueError("operands are equally long arrays of 32-bit values")
+    return np.ascontiguousarray(np.stack([a.view(np.uint32) for a in ops]))
+
+
+def host_math(ec, name, *arrays):
+    """hx_debug_host_math: the host build of the first-generation allocator's logf / log10f restatement on arrays, the
+    host-side counterpart of Batch.debug_math for "logf", "log10f", "a1_mask_db" and "a1_gz" -> uint32 [n]"""
+    ops = _math_operands(arrays)
+    out = np.zeros(ops.shape[1], dtype=np.uint32)
+    if lib().hx_debug_host_math(C.byref(ec), name.encode(), ops.ctypes.data, ops.shape[1], out.ctypes.data) != 0:
+        raise RuntimeError("hx_debug_host_math(%s): rejected" % name)
+    return out
+
+
 def device_numa_node(device):
     return int(lib().hx_device_numa_node(int(device)))
 
@@ -826,6 +844,15 @@ class Batch:
         if n < 0:
             raise RuntimeError("unknown debug buffer " + name)
         return a[: n // a.itemsize]
+
+    def debug_math(self, name, *arrays):
+        """the kernels' device function `name` (hx_batch_debug_math) on equally long arrays of 32-bit values, one per
+        operand: uint32 [n], the result's 32-bit patterns (view them as float32 or int32); at most 2^25 arguments a call"""
+        ops = _math_operands(arrays)
+        out = np.zeros(ops.shape[1], dtype=np.uint32)
+        if lib().hx_batch_debug_math(self.h, name.encode(), ops.ctypes.data, ops.shape[1], out.ctypes.data) != 0:
+            raise RuntimeError("hx_batch_debug_math(%s): %s" % (name, last_error()))
+        return out
 
     def close(self):
         if self.h:

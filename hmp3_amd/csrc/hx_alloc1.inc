@@ -29,7 +29,20 @@ __device__ __forceinline__ float a1_mask_db(const HxParams *gp, float sig, float
 {
     const float r = sig / (mask * (0.1f + 0.0001f * xsxx));
     if (r < 1.0e-10f) return 100.0f;
-    return (float) (-10.0 * (double) hx_log10f(r) - (double) gp->a1_log_cbw[i]);
+    return hx_a1_mask_db_of(r, gp->a1_log_cbw[i]);
+}
+
+// the factor that brings an intensity band's L + R to the pair's energy, before its clamp (a1_smr's intensity bands): e0, e1 the
+// energies of L and R, r that of L + R; at the MPEG-1 rates and at the MPEG-2 ones
+__device__ __forceinline__ float a1_is_scale(float e0, float e1, float r)
+{
+    // (the inner square root is sqrtf: correctly rounded, so the double one rounded to float is the same value)
+    return (float) (sqrt(((double) (e0 + e1) + 2.0 * (double) (float) sqrt((double) (e0 * e1))) / (double) r));
+}
+__device__ __forceinline__ float a1_is_scale_lsf(float e0, float e1, float r)
+{
+    const float a = (e0 > e1) ? e0 : e1;
+    return (float) (sqrt((double) (a / r)));
 }
 
 // signal and mask per scalefactor band from the psy kernel's partition data, with pre-echo control (reference
@@ -122,12 +135,10 @@ __device__ void a1_smr(AllocLds &L, const AllocPrm *p, const HxParams *gp, const
             L.xr[0][k] = v;
         }
         if (!HX_LSF) {
-            // (the inner square root is sqrtf: correctly rounded, so the double one rounded to float is the same value)
-            r = (float) (sqrt(((double) (e0 + e1) + 2.0 * (double) (float) sqrt((double) (e0 * e1))) / (double) r));
+            r = a1_is_scale(e0, e1, r);
             if (r > 1.5f) r = 1.5f;
         } else {
-            const float a = (e0 > e1) ? e0 : e1;
-            r = (float) (sqrt((double) (a / r)));
+            r = a1_is_scale_lsf(e0, e1, r);
             if (r > 1.2f) r = 1.2f;
         }
         for (int k = k0; k < k0 + n; k++) L.xr[0][k] = r * L.xr[0][k];
@@ -171,7 +182,7 @@ __device__ float a1_x34(AllocLds &L, const AllocPrm *p, const HxParams *gp, cons
         }
         L.x34max[ch][i] = m;
         int gz = 0;
-        if (!(m < gp->a1_gz0)) gz = (int) (gp->a1_gz1 * hx_logf(m) + gp->a1_gz2);
+        if (!(m < gp->a1_gz0)) gz = hx_a1_gz_of(gp->a1_gz1, gp->a1_gz2, m);
         L.gzero[ch][i] = gz;
         L.gmin[ch][i] = max(0, gz - GMIN_OFFSET);
     }
@@ -545,3 +556,39 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
     }
     HX_WAVE_SYNC();
 }
+
+#if !HX_LSF
+// ---- k_debug_math (tests only; hx_batch_debug_math): the device math of the kernels on arguments of the caller's ----
+// Lane i evaluates function fn (HxDebugMath) on in[i] (in[n + i], in[2 n + i]: the further operands) and stores out[i];
+// all values are 32-bit patterns.  Every case calls the function the kernels call - this unit carries the allocator group's
+// flags, the ones each of them is built with in the product - on the batch's own tables.  Built here once, not in the
+// MPEG-2 twin of this unit.
+__global__ __launch_bounds__(256) void k_debug_math(int fn, const unsigned *in, long long n, unsigned *out, const HxGlobalTabs *gt, const HxParams *gp)
+{
+    __shared__ unsigned short mblog16[256];     // the mB-log table as the low-footprint layout stages it (hx_alloc3.inc)
+    mblog16[threadIdx.x] = (unsigned short) (gt->mblog[threadIdx.x] + 38227);
+    __syncthreads();
+    const long long i = (long long) blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const unsigned u = in[i];
+    const float x = hx_bits2f(u);
+    unsigned r = 0;
+    switch (fn) {
+    case HX_DM_LOGF: r = hx_f2bits(hx_logf(x)); break;
+    case HX_DM_LOG10F: r = hx_f2bits(hx_log10f(x)); break;
+    case HX_DM_A1_MASK_DB: r = hx_f2bits(hx_a1_mask_db_of(x, hx_bits2f(in[n + i]))); break;
+    case HX_DM_A1_GZ: r = (unsigned) hx_a1_gz_of(gp->a1_gz1, gp->a1_gz2, x); break;
+    case HX_DM_DBLOG: r = hx_f2bits(dblog(x)); break;
+    case HX_DM_DUAL_G: r = (unsigned) dual_gain_step(x); break;
+    case HX_DM_IS_SCALE: r = hx_f2bits(a1_is_scale(x, hx_bits2f(in[n + i]), hx_bits2f(in[2 * n + i]))); break;
+    case HX_DM_IS_SCALE_LSF: r = hx_f2bits(a1_is_scale_lsf(x, hx_bits2f(in[n + i]), hx_bits2f(in[2 * n + i]))); break;
+    case HX_DM_DIV: r = hx_f2bits(x / hx_bits2f(in[n + i])); break;
+    case HX_DM_MBLOG: r = (unsigned) hx_mblog(gt->mblog, x); break;
+    case HX_DM_MBLOG16: r = (unsigned) hx_mblog16(mblog16, x); break;
+    case HX_DM_MBEXP: r = hx_f2bits(hx_mbexp(gt->mbexp_lo, gt->mbexp_hi, (int) u)); break;
+    case HX_DM_POW34: r = hx_f2bits(hx_pow34(gt->pow34_a, gt->pow34_b, gt->pow34_exp, x)); break;
+    case HX_DM_ROUND: r = (unsigned) hx_round(x); break;
+    }
+    out[i] = r;
+}
+#endif

@@ -125,6 +125,12 @@ __device__ HX_HFN void hf_reset_ms(AllocLds &L, int both)
 
 // ---- trade_dual (L/R only; reference bitallo3.cpp:2216-2306): flatten isolated peaks ----
 __device__ HX_COLD float dblog(float x) { return (float) (10.0 * log10((double) x)); }
+// the gain step (before its + 8) at which a band whose largest x^(3/4), scaled by the target's factor, is x quantises to the target
+__device__ __forceinline__ int dual_gain_step(float x)
+{
+    float xg = 1.7717f * dblog(x);
+    return (int) (xg + 1.0f);
+}
 
 __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
 {
@@ -147,8 +153,7 @@ __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
         for (b = p->nsf[ch] - 1; b >= 11; b--) {
             if (L.ix10xmax[ch][b] > 16) break;
             if (L.ixmax[ch][b] == 2) {
-                float xg = 1.7717f * dblog(L.x34max[ch][b] * (1.0f / (1.5f + 0.02799f)));
-                g = (int) (xg + 1.0f);
+                g = dual_gain_step(L.x34max[ch][b] * (1.0f / (1.5f + 0.02799f)));
                 L.gsf[ch][b] = g + 8;
             }
         }
@@ -174,8 +179,7 @@ __device__ void trade_dual(AllocLds &L, const AllocPrm *p)
                     float factor = 1.0f / ((ixtarget + 0.5f) + qo);
                     for (b = k0; b < k1; b++)
                         if (L.ixmax[ch][b] > ixtarget) {
-                            float xg = 1.7717f * dblog(L.x34max[ch][b] * factor);
-                            g = (int) (xg + 1.0f);
+                            g = dual_gain_step(L.x34max[ch][b] * factor);
                             L.gsf[ch][b] = g + 8;
                         }
                 }

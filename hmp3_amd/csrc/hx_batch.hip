@@ -1285,6 +1285,37 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     return n;
 }
 
+// For tests: the device math of the kernels on arguments of the caller's (include/hmp3_amd.h).  k_debug_math lives in the
+// k_alloc1 unit (hx_alloc1.inc), where every function it calls is compiled with the allocator kernels' flags; the tables are
+// this batch's (HxGlobalTabs, the HxParams of its first class).
+static const struct { const char *name; int fn, nin; } debug_math_fns[] = {
+    {"logf", HX_DM_LOGF, 1}, {"log10f", HX_DM_LOG10F, 1}, {"a1_mask_db", HX_DM_A1_MASK_DB, 2}, {"a1_gz", HX_DM_A1_GZ, 1},
+    {"dblog", HX_DM_DBLOG, 1}, {"dual_g", HX_DM_DUAL_G, 1}, {"is_scale", HX_DM_IS_SCALE, 3}, {"is_scale_lsf", HX_DM_IS_SCALE_LSF, 3},
+    {"div", HX_DM_DIV, 2}, {"mblog", HX_DM_MBLOG, 1}, {"mblog16", HX_DM_MBLOG16, 1}, {"mbexp", HX_DM_MBEXP, 1},
+    {"pow34", HX_DM_POW34, 1}, {"round", HX_DM_ROUND, 1}};
+static_assert(sizeof(debug_math_fns) / sizeof(debug_math_fns[0]) == HX_DM_COUNT, "one name per HxDebugMath value");
+
+extern "C" int hx_batch_debug_math(hx_batch *b, const char *name, const void *in, long long n, void *out)
+{
+    if (!b || !name || !in || !out) { set_err("null argument"); return -1; }
+    int fn = -1, nin = 0;
+    for (const auto &f : debug_math_fns) if (!strcmp(name, f.name)) { fn = f.fn; nin = f.nin; }
+    if (fn < 0) { set_err("hx_batch_debug_math: no function named %s", name); return -1; }
+    if (n <= 0 || n > HX_DEBUG_MATH_MAX) { set_err("hx_batch_debug_math takes 1 .. 2^25 arguments per call"); return -1; }
+    if (drain(b) != 0) return -1;
+    struct Dev {
+        unsigned *in = nullptr, *out = nullptr;
+        ~Dev() { (void) hipFree(in); (void) hipFree(out); }
+    } d;
+    const size_t bytes = sizeof(unsigned) * (size_t) n;
+    HIPCHK(hipMalloc(&d.in, bytes * nin));
+    HIPCHK(hipMalloc(&d.out, bytes));
+    HIPCHK(hipMemcpy(d.in, in, bytes * nin, hipMemcpyHostToDevice));
+    LAUNCH(k_debug_math, dim3((unsigned) ((n + 255) / 256)), dim3(256), 0, fn, d.in, n, d.out, b->d_gt, b->d_prm);
+    HIPCHK(hipMemcpy(out, d.out, bytes, hipMemcpyDeviceToHost));
+    return 0;
+}
+
 
 // ---- hx_debug_pack: k_pack on records of the caller's (tests only; include/hmp3_amd.h) ----
 // What the packer reads of a call - segment records, lines, signs, frame records, slot lists - comes from the caller instead

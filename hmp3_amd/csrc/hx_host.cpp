@@ -737,6 +737,27 @@ extern "C" int hx_control_info(const HX_E_CONTROL *ec, HX_E_CONTROL *ec_out, HX_
 extern "C" const char *hx_libc_version(void) { return hx_host_libc_version(); }
 extern "C" int hx_libm_spot_check(int n) { return hx_libm32_spot_check(n); }
 
+// The host build of hx_libm32.h - the build hx_libm_spot_check and tools/check_libm32.c hold to glibc 2.35's libm - on
+// arrays: what hx_batch_debug_math's "logf", "log10f", "a1_mask_db" and "a1_gz" are compared with (same names, same 32-bit
+// patterns, operands as [k][n]; "a1_gz" with the constants this control resolves to).  Returns 0, -1 for a rejected
+// configuration, an unknown name or a null argument.  Host only.
+extern "C" int hx_debug_host_math(const HX_E_CONTROL *ec, const char *name, const void *in, long long n, void *out)
+{
+    static HxParams p;
+    if (!ec || !name || !in || !out || n < 0) return -1;
+    const uint32_t *u = (const uint32_t *) in;
+    uint32_t *o = (uint32_t *) out;
+    std::string k(name);
+    if (k == "logf") for (long long i = 0; i < n; i++) o[i] = hx_f2u(hx_logf(hx_u2f(u[i])));
+    else if (k == "log10f") for (long long i = 0; i < n; i++) o[i] = hx_f2u(hx_log10f(hx_u2f(u[i])));
+    else if (k == "a1_mask_db") for (long long i = 0; i < n; i++) o[i] = hx_f2u(hx_a1_mask_db_of(hx_u2f(u[i]), hx_u2f(u[n + i])));
+    else if (k == "a1_gz") {
+        if (!hx_resolve((const HxControl *) ec, &p)) return -1;
+        for (long long i = 0; i < n; i++) o[i] = (uint32_t) hx_a1_gz_of(p.a1_gz1, p.a1_gz2, hx_u2f(u[i]));
+    } else return -1;
+    return 0;
+}
+
 // 1 if the tables resolved for this control have the structure k_alloc_slim derives them from (hx_slim_tables_ok)
 extern "C" int hx_debug_slim_tables_ok(const HX_E_CONTROL *ec)
 {
@@ -773,7 +794,7 @@ extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *nam
     TAB("lane_run", p.lane_run) TAB("band_last_lane", p.band_last_lane)
     TAB("nchan", p.nchan) TAB("side_bytes", p.side_bytes) TAB("h_id", p.h_id)
     TAB("nsf2", p.nsf2) TAB("nsf3", p.nsf3) TAB("nbmax", p.nbmax) TAB("nbmax2", p.nbmax2) TAB("nbmax3", p.nbmax3)
-    TAB("psy_short_npart", p.psyS.npart) TAB("alloc1", p.alloc1)
+    TAB("psy_short_npart", p.psyS.npart) TAB("alloc1", p.alloc1) TAB("a1_log_cbw", p.a1_log_cbw)
 #undef TAB
     if (k == "sizeof_band_prep") { static int v[1]; v[0] = (int) sizeof(HxBandPrep); src = v; n = sizeof(v); }     // for the tests' mirror of the "band" tap
     if (k == "sizeof_pack_records") {       // for the tests' mirrors of what hx_debug_pack takes; [3]: slots pending from earlier calls

@@ -84,3 +84,11 @@ HX_HD float hx_log10f(float x)
     const float z = y * log10_2lo + ivln10 * hx_logf(m);
     return z + y * log10_2hi;
 }
+
+// The two expressions of the first-generation allocator that end these functions' results in a value the bitstream
+// depends on, named so that the kernels (hx_alloc1.inc), the host build (hx_host.cpp: hx_debug_host_math) and the test
+// kernel (k_debug_math) evaluate one text:
+//   the mask level in dB of a signal-to-mask ratio r in a band of width 10^(cbw / 10) lines (bitallo1.cpp smr_adj);
+//   the gain step at which a band whose largest x^(3/4) is m quantises to zero (bitallo1.cpp compute_x34).
+HX_HD float hx_a1_mask_db_of(float r, float cbw) { return (float) (-10.0 * (double) hx_log10f(r) - (double) cbw); }
+HX_HD int hx_a1_gz_of(float gz1, float gz2, float m) { return (int) (gz1 * hx_logf(m) + gz2); }

@@ -234,6 +234,14 @@ enum HxCounter {
 #define HX_CNT_WORDS (HX_CNT_LUCKY + 3)
 static_assert(HX_CNT_LUCKY == HX_CNT_PARK + HX_PARK_MAX, "the big_lucky counters follow the parking scheme's words");
 
+// What k_debug_math (hx_alloc1.inc; tests only, hx_batch_debug_math) evaluates: the device functions of the kernels on
+// arguments of the caller's, one per lane.  The name table and each function's operand count are in hx_batch.hip.
+enum HxDebugMath {
+    HX_DM_LOGF, HX_DM_LOG10F, HX_DM_A1_MASK_DB, HX_DM_A1_GZ, HX_DM_DBLOG, HX_DM_DUAL_G, HX_DM_IS_SCALE, HX_DM_IS_SCALE_LSF,
+    HX_DM_DIV, HX_DM_MBLOG, HX_DM_MBLOG16, HX_DM_MBEXP, HX_DM_POW34, HX_DM_ROUND, HX_DM_COUNT
+};
+#define HX_DEBUG_MATH_MAX (1LL << 25)   // arguments per call
+
 // Slots of the stream walk's profile (built with -DHX_PROFILE: AllocArgs::prof, 64 per stream; tools/prof_slots.py reads this
 // table for the profile tools).  Master-wave clock64 ticks booked to a phase, except the counts (HX_PROF_N_*).
 enum HxProf {

@@ -865,6 +865,24 @@ int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long l
    bytes, returns bytes, -1 for an unknown name. */
 long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap);
 void hx_batch_debug_enable(hx_batch *b, int on);
+/* The kernels' device math on arguments of the caller's: for each i < n the device evaluates the function `name` - the
+   very function the kernels call, built with the allocator kernels' flags, on this batch's device tables (the class-
+   independent ones and those of the batch's first class) - on in[i] and stores out[i].  Everything crosses as 32-bit
+   patterns, nothing is converted: floats as their bits, ints as int32.  A function of k operands reads in as [k][n].
+     "logf" "log10f"            the restated logf and log10f of hmp3_amd/csrc/hx_libm32.h                   f32 -> f32
+     "a1_mask_db"               (float) (-10.0 * (double) log10f r - (double) cbw), that log10f        (r, cbw) -> f32
+     "a1_gz"                    (int) (a1_gz1 * logf m + a1_gz2), that logf, the class's constants          f32 -> i32
+     "dblog"                    (float) (10.0 * log10((double) x)), the device's double log10               f32 -> f32
+     "dual_g"                   (int) (1.7717f * dblog(x) + 1.0f), trade_dual's gain step                   f32 -> i32
+     "is_scale" "is_scale_lsf"  the intensity bands' rescale before its clamp, MPEG-1 / MPEG-2       (e0, e1, r) -> f32
+     "div"                      a / b in fp32                                                            (a, b) -> f32
+     "mblog" "mblog16"          the millibel log, on the int table and on its 16-bit form                   f32 -> i32
+     "mbexp"                    its inverse                                                                 i32 -> f32
+     "pow34"                    x^(3/4), the piecewise-linear fit                                           f32 -> f32
+     "round"                    (int) (x + copysign(0.5, x))                                                f32 -> i32
+   n is 1 .. 2^25; more, or an unknown name, is refused with -1 and hx_last_error before anything is launched.  Returns 0.
+   Synchronises. */
+int hx_batch_debug_math(hx_batch *b, const char *name, const void *in, long long n, void *out);
 /* Which route the calls of an hx_enc took since its last init (a successful or a rejected one; both reset the counters):
    out[0] = calls made the plain way, out[1] = calls replayed from the recorded graph, out[2] = the graph's state (0 = not
    recorded yet, 1 = ready, -1 = not available: HMP3AMD_ENC_GRAPH=0, or the recording failed and the calls go the plain way).
@@ -882,6 +900,10 @@ int hx_enc_debug_calls(hx_enc *e, int out[3]);
    sample arguments the host's logf / log10f treat differently (0: a reference built on this host and the kernels agree). */
 const char *hx_libc_version(void);
 int hx_libm_spot_check(int n);
+/* The host build of the same restatement on arrays, for tests: "logf", "log10f", "a1_mask_db" and "a1_gz" of
+   hx_batch_debug_math with the same patterns and operand layout ("a1_gz": the constants ec resolves to).  Returns 0;
+   -1 for a rejected configuration, another name or a null argument.  Host only. */
+int hx_debug_host_math(const HX_E_CONTROL *ec, const char *name, const void *in, long long n, void *out);
 /* 1 if the host tables of this control have the structure the low-footprint kernel derives them from (gain tables and
    the x^(3/4) exponent table as ldexp of 4 / 16 constants, mB tables within 16 bits); hx_batch_create checks the same
    before it picks that kernel.  -1 = configuration rejected.  Host only. */

@@ -233,6 +233,8 @@ int   hxo_mblog(float x);                       /* l3math.c:228 */
 float hxo_mbexp(int mb);                        /* l3math.c:342 */
 void  hxo_pow34(const float *x, float *y, int n);   /* pow34.c:132 */
 void  hxo_pow43(int first, int n, double *out);     /* pow(ix, 4/3) as l3math.c:527 calls it, ix = first .. first + n - 1 */
+/* mbLogC, mbExp, the rounding of l3math.c:361, dblog (l3math.c:142) and trade_dual's gain step on arrays (hxo_math.c) */
+int   hxo_math_array(int what, const uint32_t *in, long long n, uint32_t *out);
 void  hxo_polyphase_granule(const hxo_params *p, const float *vbuf, float *samp);   /* sbt.c:293 */
 void  hxo_freq_invert(float *samp, int nsb);    /* hwin.c:282 */
 void  hxo_hybrid_long(const hxo_params *p, const float *prev, const float *cur, float *xr, int btype, int nsb, int clear); /* hwin.c:147 */

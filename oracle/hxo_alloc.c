@@ -730,15 +730,14 @@ static void trade_dual(ba_t *b)
     const hxo_params *p = b->p;
     hxo_state *st = &b->e->s;
     int ch, i, g, k0, k1, ixmax0, ixtarget;
-    float xg, eixmax, feixmax, fetot, factor, ftmp;
+    float eixmax, feixmax, fetot, factor, ftmp;
     for (ch = 0; ch < b->nchan; ch++) {
         ixmax_quant(p, b->x34max[ch], st->ixmax[ch], b->gsf[ch], p->nsf[ch]);
         ix10xmax_quant(p, b->x34max[ch], b->ix10xmax[ch], b->gsf[ch], p->nsf[ch]);
         for (i = p->nsf[ch] - 1; i >= 11; i--) {
             if (b->ix10xmax[ch][i] > 16) break;
             if (st->ixmax[ch][i] == 2) {
-                xg = 1.7717f * hxo_dblog(b->x34max[ch][i] * (1.0f / (1.5f + 0.02799f)));
-                g = (int) (xg + 1.0f);
+                g = hxo_dual_g(b->x34max[ch][i] * (1.0f / (1.5f + 0.02799f)));
                 b->gsf[ch][i] = g + G_OFFSET;
             }
         }
@@ -764,8 +763,7 @@ static void trade_dual(ba_t *b)
         factor = 1.0f / ((ixtarget + 0.5f) + qo[ixtarget]);
         for (i = k0; i < k1; i++)
             if (st->ixmax[ch][i] > ixtarget) {
-                xg = 1.7717f * hxo_dblog(b->x34max[ch][i] * factor);
-                g = (int) (xg + 1.0f);
+                g = hxo_dual_g(b->x34max[ch][i] * factor);
                 b->gsf[ch][i] = g + G_OFFSET;
             }
     }

@@ -12,6 +12,7 @@ void hxo_math_init(void);
 int hxo_round(float x);
 int hxo_logsubber(int n1, int n2);
 float hxo_dblog(float x);
+int hxo_dual_g(float x);
 float hxo_anwin(int n);
 extern float hxo_quant_off[32];
 

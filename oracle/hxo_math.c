@@ -69,6 +69,32 @@ int hxo_logsubber(int n1, int n2)
 /* l3math.c:142-146 */
 float hxo_dblog(float x) { return (float) (10.0 * log10(x)); }
 
+/* bitallo3.cpp:2236-2238, :2296-2298: trade_dual's gain step, before its offset */
+int hxo_dual_g(float x)
+{
+    float xg = 1.7717f * hxo_dblog(x);
+    return (int) (xg + 1.0f);
+}
+
+/* the scalar functions above on arrays of 32-bit patterns, for the tests of the kernels' device math (oracle.math):
+   what = 0 hxo_mblog, 1 hxo_mbexp, 2 hxo_round, 3 hxo_dblog, 4 hxo_dual_g.  Returns 0, -1 for another number. */
+int hxo_math_array(int what, const uint32_t *in, long long n, uint32_t *out)
+{
+    long long i;
+    if (what < 0 || what > 4) return -1;
+    for (i = 0; i < n; i++) {
+        const float x = hxo_bits2f(in[i]);
+        switch (what) {
+        case 0: out[i] = (uint32_t) hxo_mblog(x); break;
+        case 1: out[i] = hxo_f2bits(hxo_mbexp((int) in[i])); break;
+        case 2: out[i] = (uint32_t) hxo_round(x); break;
+        case 3: out[i] = hxo_f2bits(hxo_dblog(x)); break;
+        default: out[i] = (uint32_t) hxo_dual_g(x); break;
+        }
+    }
+    return 0;
+}
+
 /* pow34.c:132-154 (IEEE_FLOAT branch): piecewise-linear mantissa fit times exponent table */
 void hxo_pow34(const float *x, float *y, int n)
 {

@@ -142,6 +142,21 @@ def pow34(x):
     return y
 
 
+MATH = {"mblog": 0, "mbexp": 1, "round": 2, "dblog": 3, "dual_g": 4}
+
+
+def math(name, x):
+    """uint32 [n]: the 32-bit patterns of hxo_mblog / hxo_mbexp / hxo_round / hxo_dblog / hxo_dual_g on the 32-bit patterns
+    x (float32 bits; int32 for mbexp), through the C functions the oracle's encoder calls (this machine's libm)"""
+    x = np.ascontiguousarray(x).reshape(-1)
+    assert x.dtype.itemsize == 4
+    out = np.zeros(x.size, dtype=np.uint32)
+    lib().hxo_math_array.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_void_p]
+    rc = lib().hxo_math_array(MATH[name], x.ctypes.data, x.size, out.ctypes.data)
+    assert rc == 0
+    return out
+
+
 class OracleEncoder:
     """one stream through the restatement"""
 
