@@ -51,9 +51,8 @@
 // The gain search (seek_actual_ch) inlined at its three call sites in the 168-register build: as a call it saved and restored 54
 // registers per lane each time.
 #define HX_SEEK_FORCEINLINE HX_SLIM
-// Candidates per band that one pass of big_lucky_noise measures at the most.  The 256-register builds have room for twelve
-// candidates' terms (the term buffer and the quantised lines behind it, dead until the quantiser runs): 93 % of a CBR-128
-// granule's bands' candidate lists fit one pass, with six 19 %.  The low-footprint build's lines live inside the term buffer.
+// Candidates per band that one pass of big_lucky_noise measures at the most: as many as the results L.lucky and the band
+// lane's replay of them hold.  With twelve 93 % of a CBR-128 granule's bands' candidate lists fit one pass, with six 19 %.
 #define HX_LUCKY_K (HX_SLIM ? 6 : 12)
 #define GMIN_OFFSET 70
 #define PART23 4021
@@ -101,8 +100,8 @@ struct alignas(16) Outbox {
 // HX_SLIM = 1: the low-footprint layout of the stream walk's LDS (26.5 KB instead of 38.3 KB per stream: six workgroups per
 // CU instead of four, for batches with more streams than the chip holds at once).  What differs from the layout it is
 // derived from (all of it bit-identical in its results):
-//  * the quantised lines are int16 and live in the first half of the noise-term buffer: a granule's terms (gain search,
-//    big_lucky) are dead when its lines are quantised and the other way round; inverse_sf2 puts its squares into xr
+//  * the quantised lines are int16 and live in the first half of the noise-term buffer: a granule's terms (the gain search's
+//    strict sums) are dead when its lines are quantised and the other way round; inverse_sf2 puts its squares into xr
 //    (in place) and x34, both dead by then, instead of into the term buffer; the quantiser writes every line (zeros past
 //    the coded range), since the buffer holds terms before it;
 //  * the next granule's band start values land in the second half of the term buffer (the order to fetch them goes out
@@ -112,7 +111,7 @@ struct alignas(16) Outbox {
 //    ldexp of 4 / 16 constants (hx_host.cpp checks that identity on the host's tables before a batch may use this kernel);
 //    the mB-log and log-subtract tables as 16-bit values;
 //  * the short-block allocator's gain-step arrays and the band tables as int16, the scalefactor outputs as bytes; big_lucky
-//    measures six candidates per band and pass, not twelve (its terms cannot run on into the lines: they share the buffer).
+//    measures six candidates per band and pass, not twelve (its results and its work list are half the size).
 #if HX_SLIM
 typedef short ix_t;                     // a quantised line
 typedef short sgs_t;                    // short-block gain steps / scalefactors per band (0 .. 127, flags 0 / -1)
@@ -218,9 +217,6 @@ struct alignas(16) AllocLds {
     unsigned long long candpk[19];      // candidate tables per class of a region's largest value
     unsigned short r_mf[32];            // pending frames: main-data bytes of the slot ...
     int r_off[32];                      // ... and offset of its header in the output buffer
-#if !HX_SLIM
-    float dump[64];                     // per-lane sink for predicated-off stores (keeps hot loops branch-free)
-#endif
     Outbox ob[2];
     const double *pow43;                // HxGlobalTabs::pow43 (global memory)
     int *big_counter;                   // device counter of line passes that took the double table (tests)
@@ -228,6 +224,7 @@ struct alignas(16) AllocLds {
 #if !HX_SLIM
     int nlucky[3];                      // big_lucky_noise of this stream: granules it measured, its passes, granules with a pass of more than six candidates (HX_CNT_LUCKY, when the stream retires)
 #endif
+    int nrounds[3];                     // big_lucky_noise's work lists of this stream: entries summed, rounds beyond a wave's first, the longest list of a pass (HX_CNT_LUCKY_ROUNDS, when the stream retires)
     int cur_s;                          // the stream this workgroup is walking (the helper wave reads it with a fetch order)
     alignas(16) int cmdw[4];            // work order for the helper wave (see HELPER_POST): command + three arguments, one 16-byte read
     alignas(4) unsigned char gflag[HX_SLIM ? 64 : 256];     // block type | stereo decision << 2 of the next granules (frame loop, hx_alloc3.inc)
@@ -236,16 +233,10 @@ struct alignas(16) AllocLds {
 #endif
 };
 
-#if !HX_SLIM
-static_assert(offsetof(AllocLds, ix) == offsetof(AllocLds, term) + sizeof(float) * 2 * 576 && sizeof(int) == sizeof(float),
-              "big_lucky_noise's terms run on from the term buffer into the quantised lines: 2304 words in one piece");
-#endif
-
 // Layout-dependent accessors (see HX_SLIM above)
 #if HX_SLIM
 #define IX(c) (reinterpret_cast<ix_t *>(&L.term[0][0]) + 576 * (c))
 #define BAND_LANDING (reinterpret_cast<HxBandPrep *>(&L.term[1][0]))
-#define LANE_SINK (reinterpret_cast<float *>(&L.lucky[0][0][0]) + LANE)       // big_lucky's results are written after its terms
 #define MBLOG(x) hx_mblog16(L.mblog, (x))
 // 2^((g - 8) / 4) and 2^(-3 (g - 8) / 16) as the tables hold them: float(2^(r / 4)) x 2^q is exact, and so is the period-16 form
 // of the second (hx_host.cpp: slim_tables_ok)
@@ -261,7 +252,6 @@ __device__ __forceinline__ float lk_igain(const float *ig16, int g) { const int 
 #else
 #define IX(c) (&L.ix[(c)][0])
 #define BAND_LANDING (&L.band_next)
-#define LANE_SINK (&L.dump[LANE])
 #define MBLOG(x) hx_mblog(L.mblog, (x))
 #define LK_GAIN(g) L.look_gain[(g)]
 #define LK_IGAIN(g) L.look_34igain[(g)]
@@ -874,107 +864,84 @@ __device__ int scale_factors(AllocLds &L, const AllocPrm *p, int ms)
     return 0;
 }
 
-// Noise terms of up to K candidates for the lines of sfb 0..12 of both channels, flattened to
-// t = ch * nl + line (sfb 0..12 end at line 88 / 90 / 102 at 48 / 44.1 / 32 kHz, so NQ = 3 or 4
-// slots of 64 lanes).  A lane keeps the operands of its slots in registers over the candidates;
-// three candidates x NQ slots are independent LDS chains per block, all loads ahead of the
-// stores.  Terms of (candidate, band) pairs that are not being measured are computed and stored
-// too - nobody reads them, and it keeps the loop free of predicates.
-// A wave takes every other slot: w = 0 the even ones (master), w = 1 the odd ones (helper wave).
-template <int NQ>
-__device__ __forceinline__ void lucky_terms(AllocLds &L, int nl, int ncmax, float *tf, int w)
+// big_lucky_noise's evaluator: one lane per entry (candidate c of band (ch, sfb)) of the work list forms the entry's noise
+// terms and adds them as it goes, in line order - the order of band_sum and of the reference (l3math.c:512-541), so the sum
+// is the reference's by construction.  Entry u of wave w of nw lies in lane (u / nw) & 63 of round u / (64 nw): with two
+// waves each takes every other entry, and since a band's entries are neighbours in the list both waves see the same band
+// widths.  The trip count of a round is its widest band's; a narrower band's lane keeps its sum (a select, no branch: one
+// basic block per iteration), and the next pair of lines is read while the current pair's table reads are on their way.
+// (What is read past a band's end is dropped: sfb 0..12 and a pair beyond them end far below the channel's 576 lines.)
+struct LuckyEntry { int c, cc, b, start, n; float ig, gn; bool ok; };
+__device__ __forceinline__ LuckyEntry lucky_entry(const AllocLds &L, int u, int total)
+{
+    LuckyEntry q;
+    q.ok = u < total;
+    const int e = q.ok ? L.llist[u] : 0;
+    q.c = e >> 8; q.cc = (e >> 7) & 1; q.b = e & 31;
+    q.start = L.startBand[q.b];
+    q.n = q.ok ? L.nBand[q.b] : 0;
+    const int g = min(max(L.geval[q.cc][q.b], 0) + q.c * 2 * (1 + L.scale[q.cc]), 127);
+    q.ig = LK_IGAIN(g); q.gn = LK_GAIN(g);
+    return q;
+}
+
+__device__ __forceinline__ void lucky_eval(AllocLds &L, int total, int w, int nw)
 {
     HX_LANE_DECL;
-    float sx34[NQ], sxr[NQ];
-    int sg[NQ], ssd[NQ], stride[NQ];
-    float *base[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int t = LANE + 64 * (2 * q + w);
-        const bool ok = t < 2 * nl;
-        const int cc = (ok && t >= nl) ? 1 : 0, j = ok ? t - (cc ? nl : 0) : 0;
-        sx34[q] = L.x34[cc][j];
-        sxr[q] = L.xr[cc][j];
-        sg[q] = max(L.geval[cc][BAND_OF_LINE(j)], 0);
-        ssd[q] = 2 * (1 + L.scale[cc]);
-        base[q] = ok ? &tf[t] : LANE_SINK;
-        stride[q] = ok ? 2 * nl : 0;
-    }
-    for (int c0 = 0; c0 < ncmax; c0 += 3) {
-        float v[3][NQ];
-#pragma unroll
-        for (int cu = 0; cu < 3; cu++)
-#pragma unroll
-            for (int q = 0; q < NQ; q++) {
-                const int g = min(sg[q] + (c0 + cu) * ssd[q], 127);
-                v[cu][q] = noise_term_fast(L, LK_IGAIN(g), LK_GAIN(g), sx34[q], sxr[q]);
-            }
-#pragma unroll
-        for (int cu = 0; cu < 3; cu++)
-#pragma unroll
-            for (int q = 0; q < NQ; q++)
-                if (c0 + cu < ncmax) base[q][(c0 + cu) * stride[q]] = v[cu][q];
+    for (int u0 = w; u0 < total; u0 += 64 * nw) {
+        const LuckyEntry q = lucky_entry(L, u0 + LANE * nw, total);
+        const int nmax = hx_wave_max(q.n);
+        float2 a = *reinterpret_cast<const float2 *>(&L.x34[q.cc][q.start]), x = *reinterpret_cast<const float2 *>(&L.xr[q.cc][q.start]);
+        float acc = 0.0f;
+        for (int k = 0; k < nmax; k += 2) {
+            float2 an = *reinterpret_cast<const float2 *>(&L.x34[q.cc][q.start + k + 2]), xn = *reinterpret_cast<const float2 *>(&L.xr[q.cc][q.start + k + 2]);
+            const float t0 = noise_term_fast(L, q.ig, q.gn, a.x, x.x), t1 = noise_term_fast(L, q.ig, q.gn, a.y, x.y);
+            acc = (k < q.n) ? (acc + t0) + t1 : acc;
+            // (the next pair is pinned to this iteration: left to itself the compiler moves its reads to where they are used,
+            // the top of the next iteration, and every pair waits for its lines and then again for its table entries)
+            asm volatile("" : "+v"(an.x), "+v"(an.y), "+v"(xn.x), "+v"(xn.y));
+            a = an; x = xn;
+        }
+        if (q.ok) L.lucky[q.c][q.cc][q.b] = MBLOG(1.0e-12f + acc) - L.logcbw[q.b];
     }
 }
 
-// The same with terms beyond the 256-entry table taken from the double table (see sweep_lines_big): out of line, one
-// candidate at a time.
-template <int NQ>
-__device__ __noinline__ void lucky_terms_big(AllocLds &L, int nl, int ncmax, float *tf, int w)
+// The same with terms beyond the 256-entry table taken from the double table (see sweep_run_stored): out of line, and a
+// pair none of whose lines passes the float table skips the double table's round trip.
+__device__ __noinline__ void lucky_eval_big(AllocLds &L, int total, int w, int nw)
 {
     HX_LANE_DECL;
-    float sx34[NQ], sxr[NQ];
-    int sg[NQ], ssd[NQ], stride[NQ];
-    float *base[NQ];
-#pragma unroll
-    for (int q = 0; q < NQ; q++) {
-        const int t = LANE + 64 * (2 * q + w);
-        const bool ok = t < 2 * nl;
-        const int cc = (ok && t >= nl) ? 1 : 0, j = ok ? t - (cc ? nl : 0) : 0;
-        sx34[q] = L.x34[cc][j];
-        sxr[q] = L.xr[cc][j];
-        sg[q] = max(L.geval[cc][BAND_OF_LINE(j)], 0);
-        ssd[q] = 2 * (1 + L.scale[cc]);
-        base[q] = ok ? &tf[t] : LANE_SINK;
-        stride[q] = ok ? 2 * nl : 0;
-    }
+    if (w == 0 && LANE == 0) atomicAdd(L.big_counter, 1);
 #pragma unroll 1
-    for (int c = 0; c < ncmax; c++) {
-        float v[NQ], gn[NQ];
-        int qx[NQ];
-        double pw[NQ];
+    for (int u0 = w; u0 < total; u0 += 64 * nw) {
+        const LuckyEntry q = lucky_entry(L, u0 + LANE * nw, total);
+        const int nmax = hx_wave_max(q.n);
+        float acc = 0.0f;
+#pragma unroll 1
+        for (int k = 0; k < nmax; k += 2) {
+            const float2 a = *reinterpret_cast<const float2 *>(&L.x34[q.cc][q.start + k]);
+            const float2 x = *reinterpret_cast<const float2 *>(&L.xr[q.cc][q.start + k]);
+            const float x34[2] = {a.x, a.y}, xr[2] = {x.x, x.y};
+            const bool in = k < q.n;
+            float t[2];
+            int qx[2];
 #pragma unroll
-        for (int q = 0; q < NQ; q++) {
-            const int g = min(sg[q] + c * ssd[q], 127);
-            const float ig = LK_IGAIN(g);
-            gn[q] = LK_GAIN(g);
-            const float tmp = (ig * sx34[q] + (0.0f - 0.0946f));
-            qx[q] = (int) (tmp + copysignf(0.5f, tmp));
-            v[q] = noise_term_fast(L, ig, gn[q], sx34[q], sxr[q]);
+            for (int e = 0; e < 2; e++) {
+                const float tmp = (q.ig * x34[e] + (0.0f - 0.0946f));
+                qx[e] = in ? (int) (tmp + copysignf(0.5f, tmp)) : 0;
+                t[e] = noise_term_fast(L, q.ig, q.gn, x34[e], xr[e]);
+            }
+            if (__any(qx[0] >= 256 || qx[1] >= 256)) {
+                double pw[2];
+#pragma unroll
+                for (int e = 0; e < 2; e++) pw[e] = L.pow43[min(max(qx[e], 0), HX_POW43_N - 1)];
+#pragma unroll
+                for (int e = 0; e < 2; e++)
+                    if (qx[e] >= 256) { const float d = xr[e] - noise_xhat_big(L, qx[e], pw[e], q.gn); t[e] = d * d; }
+            }
+            acc = in ? (acc + t[0]) + t[1] : acc;
         }
-        bool anybig = false;
-#pragma unroll
-        for (int q = 0; q < NQ; q++) anybig = anybig || qx[q] >= 256;
-        if (__any(anybig)) {        // (a candidate none of whose lines passes the float table skips the double table's round trip)
-#pragma unroll
-            for (int q = 0; q < NQ; q++) pw[q] = L.pow43[min(max(qx[q], 0), HX_POW43_N - 1)];
-#pragma unroll
-            for (int q = 0; q < NQ; q++)
-                if (qx[q] >= 256) { const float d = sxr[q] - noise_xhat_big(L, qx[q], pw[q], gn[q]); v[q] = d * d; }
-        }
-#pragma unroll
-        for (int q = 0; q < NQ; q++) base[q][c * stride[q]] = v[q];
-    }
-}
-
-__device__ __forceinline__ void lucky_dispatch(AllocLds &L, int nl, int ncmax, float *tf, int w, int big)
-{
-    if (__builtin_expect(big, 0)) {
-        if (!HX_LSF || 2 * nl <= 256) lucky_terms_big<2>(L, nl, ncmax, tf, w);
-        else lucky_terms_big<3>(L, nl, ncmax, tf, w);
-    } else {
-        if (!HX_LSF || 2 * nl <= 256) lucky_terms<2>(L, nl, ncmax, tf, w);
-        else lucky_terms<3>(L, nl, ncmax, tf, w);
+        if (q.ok) L.lucky[q.c][q.cc][q.b] = MBLOG(1.0e-12f + acc) - L.logcbw[q.b];
     }
 }
 
@@ -987,16 +954,11 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
     // bands at once; the band lane then replays the reference's scan over the results in order.
     const int ch = LANE >> 5, i = LANE & 31;
     const int m = min(13, p->nsf[ch]);
-    const int nl = L.startBand[13];                         // lines of sfb 0..12
-    // K: what the terms [K][2][nl] have room for.  The 256-register builds let them run on from the term buffer into the
-    // quantised lines behind it (2304 words: K = 12 at 44.1 / 48 kHz, 11 at 32 kHz, 8 .. 12 with the MPEG-2 band tables): the
-    // lines are not live before do_quant, and what a pass leaves past the coded range is wiped below.
-    const int K = min(HX_LUCKY_K, (HX_SLIM ? 1152 : 2304) / (2 * nl));
-    float *tf = &L.term[0][0];                               // [K][2][nl]
+    const int K = HX_LUCKY_K;
+    const int nw = (p->nchan == 2) ? 2 : 1;                 // waves that share the entries (a mono stream has no helper)
     int mode = 0, s = 0, s0 = 0, g0 = 0, GG = 0, sdelta = 2, smin = 0, nt = 0;
-#if !HX_SLIM
-    int npass = 0, reach = 0;                                // passes of this granule, the most candidates one of them held
-#endif
+    int npass = 0, wide = 0;                                 // passes of this granule, one of them held more than six candidates per band
+    int nent = 0, nround = 0, most = 0;                      // entries summed, rounds beyond a wave's first, the longest list of a pass
     if (i < m && L.active[ch][i] && (L.gsf[ch][i] < (L.gzero[ch][i] - 5))) {
         sdelta = 2 * (1 + L.scale[ch]);
         GG = L.G[ch];
@@ -1018,35 +980,25 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
             const int sh = 1 + L.scale[ch];
             nc = min(K, min(((s - s0) >> sh) + 1, (g0 - GG + s + sdelta - 1) >> sh));
         }
-        if (i < NB) { L.geval[ch][i] = (mode == 1) ? GG - s : -1; L.tmpn[ch][i] = nc; }
-        // work list of the sums: one entry (c, ch, sfb) per candidate, compacted over the band lanes
+        if (i < NB) { L.geval[ch][i] = (mode == 1) ? GG - s : -1; }
+        // the work list: one entry (c, ch, sfb) per candidate, compacted over the band lanes (a band's entries are neighbours)
         unsigned short *list = L.llist;
         const int incl = hx_wave_scan(nc), total = __builtin_amdgcn_readlane(incl, 63);
 #pragma unroll
         for (int c = 0; c < HX_LUCKY_K; c++) if (c < nc) list[incl - nc + c] = (c << 8) | (ch << 7) | i;
         HX_WAVE_SYNC();
         const int ncmax = hx_wave_max(nc);
-#if !HX_SLIM
-        npass++; reach = max(reach, ncmax);
-#endif
+        npass++; wide |= (ncmax > 6);
+        nent += total; nround += (total + 64 * nw - 1) / (64 * nw) - 1; most = max(most, total);
         const bool bslow = mode == 1 && noise_band_needs_pow(LK_IGAIN(GG - s), L.x34max[ch][i]);
         PROF_ACC(HX_PROF_LUCKY_SETUP);
-        // slots of 64 flattened lines: 3 or 4 (MPEG-2 band tables: 5), shared between the two waves
-        const bool two = p->nchan == 2;
         const int big = __any(bslow) ? 1 : 0;       // a band reaches beyond the 256-entry table
-        if (two) { if (LANE == 0) L.cmdw[3] = big; HELPER_POST2(HCMD_LUCKY, nl, ncmax); }
-        lucky_dispatch(L, nl, ncmax, tf, 0, big);
-        if (two) HELPER_JOIN();
-        else lucky_dispatch(L, nl, ncmax, tf, 1, big);
+        if (nw == 2) HELPER_POST2(HCMD_LUCKY, total, big);
+        if (__builtin_expect(big, 0)) lucky_eval_big(L, total, 0, nw);
+        else lucky_eval(L, total, 0, nw);
+        if (nw == 2) HELPER_JOIN();
         HX_WAVE_SYNC();
-        PROF_ACC(HX_PROF_LUCKY_TERMS);
-        for (int u = LANE; u < total; u += 64) {
-            const int e = list[u], c = e >> 8, cc = (e >> 7) & 1, b = e & 31;
-            float sxx = band_sum(tf + c * 2 * nl + cc * nl + L.startBand[b], L.nBand[b], 0.0f);
-            L.lucky[c][cc][b] = MBLOG(1.0e-12f + sxx) - L.logcbw[b];
-        }
-        HX_WAVE_SYNC();
-        PROF_ACC(HX_PROF_LUCKY_SUMS);
+        PROF_ACC(HX_PROF_LUCKY_EVAL);
         {   // replay the reference's scan: the last candidate that meets the target wins
             // (six results at a time; the second six only in a pass that has them: twelve at once are six more registers)
             int best = 0;
@@ -1075,18 +1027,12 @@ __device__ void big_lucky_noise(AllocLds &L, const AllocPrm *p)
         L.sf[ch][i] = smin;
         L.gsf[ch][i] = max(GG - smin, 0);
     }
+    if (npass && LANE == 0) {
 #if !HX_SLIM
-    // A pass of more than 1152 / (2 nl) candidates wrote terms into the line buffers.  The quantiser rewrites the coded lines
-    // only, and lines past the coded range are zero by contract (the bit count's last quadruples and -HF's band 21 rely on it;
-    // with a very low subband limit - E_CONTROL.nsb_limit = 4 at 48 kHz: 72 lines - almost all of a channel is past it): they
-    // are zero again here, as far as the widest pass reached.  (the low-footprint layout's quantiser writes every line)
-    if (reach * 2 * nl > 1152) {
-        const int end = reach * 2 * nl - 1152;      // words of ix[2][576], flat, that held terms
-        for (int j = p->nbmax[0] + LANE; j < min(end, 576); j += 64) IX(0)[j] = 0;
-        for (int j = p->nbmax[1] + LANE; j < end - 576; j += 64) IX(1)[j] = 0;
-    }
-    if (npass && LANE == 0) { L.nlucky[0] += 1; L.nlucky[1] += npass; L.nlucky[2] += (reach > 6); }
+        L.nlucky[0] += 1; L.nlucky[1] += npass; L.nlucky[2] += wide;
 #endif
+        L.nrounds[0] += nent; L.nrounds[1] += nround; L.nrounds[2] = max(L.nrounds[2], most);
+    }
     HX_WAVE_SYNC();
 }
 

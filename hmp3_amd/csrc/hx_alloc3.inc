@@ -285,7 +285,7 @@ __device__ __forceinline__ void helper_serve(const AllocArgs &a, AllocLds &L)
         // most frequent orders first
         if (cmd == HCMD_SEEK) seek_actual_ch(L, &L.P, 1);
         else if (cmd == HCMD_COUNT_BITS) count_bits_ch(L, &L.P, 1, order.y);
-        else if (cmd == HCMD_LUCKY) lucky_dispatch(L, order.y, order.z, &L.term[0][0], 1, order.w);
+        else if (cmd == HCMD_LUCKY) { if (__builtin_expect(order.z, 0)) lucky_eval_big(L, order.y, 1, 2); else lucky_eval(L, order.y, 1, 2); }
         else if (cmd == HCMD_QUANT) quant_lines(L, &L.P, order.y, 1);
         else if (cmd == HCMD_QUANT_COUNT) { quant_lines(L, &L.P, order.y, 1); HX_WAVE_SYNC(); count_bits_ch(L, &L.P, 1, order.z); }
         else if (cmd == HCMD_ISF2) isf2_ch(L, &L.P, 1);
@@ -382,6 +382,7 @@ __device__ __forceinline__ void stage_stream(const AllocArgs &a, AllocLds &L, co
 #if !HX_SLIM
     if (LANE < 3) L.nlucky[LANE] = 0;
 #endif
+    if (LANE < 3) L.nrounds[LANE] = 0;
     if (LANE < 4) L.P.head[LANE] = gp->head[LANE];
     if (LANE < 16) L.P.vbr_main_framebytes[LANE] = gp->vbr_main_framebytes[LANE];
     if (LANE < 22) L.P.rnBand_l[LANE] = gp->rnBand_l[LANE];
@@ -845,6 +846,10 @@ __device__ __forceinline__ void stream_writeback(const AllocArgs &a, AllocLds &L
 #if !HX_SLIM
         if (L.nlucky[0]) for (int k = 0; k < 3; k++) atomicAdd(COLD(done_counter) + HX_CNT_LUCKY + k, L.nlucky[k]);
 #endif
+        if (L.nrounds[0]) {
+            for (int k = 0; k < 2; k++) atomicAdd(COLD(done_counter) + HX_CNT_LUCKY_ROUNDS + k, L.nrounds[k]);
+            atomicMax(COLD(done_counter) + HX_CNT_LUCKY_ROUNDS + 2, L.nrounds[2]);
+        }
         stream_retire(s, idx, t_start);
     }
     tail_fill(s, NGs / 2, a.NG / 2, L.fs.tot_frames_out, L.fs.tot_bytes_out);

@@ -1271,6 +1271,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "big_sweeps") { src = b->d_done + HX_CNT_BIG_SWEEPS; n = sizeof(int); }        // gain-search line passes that took the double x^(4/3) table
     else if (k == "strict_sums") { src = b->d_done + HX_CNT_STRICT_SUMS; n = sizeof(int); }       // certified band sums that fell back to the strict line-order sum
     else if (k == "lucky") { src = b->d_done + HX_CNT_LUCKY; n = 3 * sizeof(int); }       // big_lucky_noise: granules measured, passes, granules with a pass of more than six candidates (k_alloc_slim does not count)
+    else if (k == "lucky_rounds") { src = b->d_done + HX_CNT_LUCKY_ROUNDS; n = 3 * sizeof(int); }       // big_lucky_noise's work lists: entries summed, rounds beyond a wave's first, the longest list of a pass
     else if (k == "bt") { src = f.bt; n = S * NG; }
     else if (k == "eng") { src = b->d_eng; n = sizeof(int) * S * 2 * NG * 9; }
     else if (k == "dbg" && b->d_dbg) { src = b->d_dbg; n = sizeof(HxFrameDebug) * S * (NG / 2); }

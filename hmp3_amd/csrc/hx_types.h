@@ -229,9 +229,11 @@ enum HxCounter {
     HX_CNT_PARK = 8,            // [HX_CNT_PARK ..]: the CU ids of the parking scheme, one per parked position (hx_alloc3.inc)
     HX_CNT_LUCKY = 72,          // [3] big_lucky_noise of the 256-register stream walks: granules it measured, its passes, granules
                                 // one of whose passes held more than six candidates per band
+    HX_CNT_LUCKY_ROUNDS = 75,   // [3] big_lucky_noise's work lists (every stream walk): entries summed, rounds of 64 entries beyond a
+                                // wave's first, the longest list of a pass
 };
 #define HX_PARK_MAX 64
-#define HX_CNT_WORDS (HX_CNT_LUCKY + 3)
+#define HX_CNT_WORDS (HX_CNT_LUCKY_ROUNDS + 3)
 static_assert(HX_CNT_LUCKY == HX_CNT_PARK + HX_PARK_MAX, "the big_lucky counters follow the parking scheme's words");
 
 // What k_debug_math (hx_alloc1.inc; tests only, hx_batch_debug_math) evaluates: the device functions of the kernels on
@@ -269,8 +271,7 @@ enum HxProf {
     HX_PROF_N_LUCKY = 21,           // count: big_lucky passes
     HX_PROF_N_COUNTS = 22,          // count: bit counts
     HX_PROF_LUCKY_SETUP = 23,
-    HX_PROF_LUCKY_TERMS = 24,
-    HX_PROF_LUCKY_SUMS = 25,
+    HX_PROF_LUCKY_EVAL = 24,        // the entries' noise terms, formed and added
     HX_PROF_LUCKY_REPLAY = 26,
     HX_PROF_SWEEP_PUBLISH = 27,     // gain-search sweep: band lanes publish their gain pairs
     HX_PROF_SWEEP_LINES = 28,
