@@ -189,6 +189,30 @@ def host_math(ec, name, *arrays):
     return out
 
 
+COUNT_MODES = {"count": 0, "quant_count": 1, "quant_then_count": 2, "short": 3, "short_count": 4}
+COUNT_UNITS = ("k_alloc", "k_alloc_slim", "k_alloc_lsf", "k_alloc1", "k_alloc1_lsf")
+
+
+def debug_count(ec, unit, mode, hdr, ix, ixmax, x34=None, gsf=None, device=0):
+    """hx_debug_count: the stream walk's quantiser and Huffman counter, as `unit` builds them, on n records (the layouts:
+    include/hmp3_amd.h).  mode is a name of COUNT_MODES.  -> (rc, lines, band maxima, out [n][24]): copies of ix and ixmax
+    as the functions left them; rc = -1: refused (last_error() says why) and nothing was launched"""
+    hdr = np.ascontiguousarray(hdr, dtype=np.int32)
+    n = hdr.shape[0]
+    ix = np.array(ix, dtype=np.int32, order="C")
+    ixmax = np.array(ixmax, dtype=np.int32, order="C")
+    x34 = None if x34 is None else np.ascontiguousarray(x34, dtype=np.float32)
+    gsf = None if gsf is None else np.ascontiguousarray(gsf, dtype=np.int32)
+    nband = 48 if mode.startswith("short") else 22
+    if hdr.shape != (n, 16) or ix.size != n * 1152 or ixmax.size != n * 2 * nband or (x34 is not None and x34.size != n * 1152) or \
+            (gsf is not None and gsf.size != n * 2 * nband):
+        raise ValueError("arrays of %d records expected" % n)
+    out = np.zeros((n, 24), dtype=np.int32)
+    rc = lib().hx_debug_count(int(device), C.byref(ec), unit.encode(), COUNT_MODES[mode], n, hdr.ctypes.data, ix.ctypes.data, ixmax.ctypes.data,
+                              None if x34 is None else x34.ctypes.data, None if gsf is None else gsf.ctypes.data, out.ctypes.data)
+    return rc, ix, ixmax, out
+
+
 def device_numa_node(device):
     return int(lib().hx_device_numa_node(int(device)))
 

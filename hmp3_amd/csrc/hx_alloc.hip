@@ -32,6 +32,9 @@
 #ifndef HX_SLIM
 #define HX_SLIM 0           // 1 when compiled as hx_alloc_slim.hip: the low-footprint LDS layout (see AllocLds below)
 #endif
+#ifndef HX_TAP
+#define HX_TAP 0            // 1 when compiled as one of hx_count*.hip: the unit's twin with the test tap k_debug_count_* in the stream walk's place (hx_alloc3.inc)
+#endif
 #if HX_SLIM && HX_A1
 #error "the low-footprint layout is built for the second-generation allocator only"
 #endif

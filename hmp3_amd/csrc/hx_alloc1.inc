@@ -399,6 +399,14 @@ __device__ int a1_scale_factors(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
     return gmin;
 }
 
+// the Huffman bits of cx's channels, one after the other on the master wave (a1_quant_count; the test tap k_debug_count_*)
+__device__ __forceinline__ int a1_count_channels(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
+{
+    int bits = 0;
+    for (int c = cx.c0; c < cx.c0 + cx.nch; c++) bits += count_bits_ch(L, p, c, p->nsf[c]);
+    return bits;
+}
+
 // quantise the bands whose gain changed since the last time, count the Huffman bits of every channel
 __device__ int a1_quant_count(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
 {
@@ -415,8 +423,7 @@ __device__ int a1_quant_count(AllocLds &L, const AllocPrm *p, const A1Ctx cx)
         }
     }
     HX_WAVE_SYNC();
-    int bits = 0;
-    for (int c = cx.c0; c < cx.c0 + cx.nch; c++) bits += count_bits_ch(L, p, c, p->nsf[c]);
+    const int bits = a1_count_channels(L, p, cx);
     HX_WAVE_SYNC();
     return bits;
 }
@@ -557,7 +564,7 @@ __device__ void bitallo1(AllocLds &L, const AllocPrm *p, const HxParams *gp, con
     HX_WAVE_SYNC();
 }
 
-#if !HX_LSF
+#if !HX_LSF && !HX_TAP
 // ---- k_debug_math (tests only; hx_batch_debug_math): the device math of the kernels on arguments of the caller's ----
 // Lane i evaluates function fn (HxDebugMath) on in[i] (in[n + i], in[2 n + i]: the further operands) and stores out[i];
 // all values are 32-bit patterns.  Every case calls the function the kernels call - this unit carries the allocator group's

@@ -1001,31 +1001,120 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
     walk_exit(L);
 }
 
+// ---- k_debug_count_* (tests only; hx_debug_count): the walk's quantiser and Huffman counter on records of the caller's ----
+// One workgroup of two waves per record, as the walk has them: the master stages the class's tables (stage_stream), copies
+// the record into LDS and calls the functions the rate loop calls; the helper wave serves its work orders (helper_serve), so
+// channel 1 is quantised and counted where the walk does it.  What the functions left in LDS goes back out.  One kernel per
+// stream-walk unit, built with that unit's macros and flags in the unit's twin (HX_TAP, below); the host (hx_batch.hip) has checked every record: nothing a
+// record's value indexes can leave its bounds.  The kernel's first argument is an AllocArgs, which COLD() reads.
+template <int LSF>
+__device__ __forceinline__ void debug_count(const AllocArgs &a, const HxCountArgs &c, AllocLds &L)
+{
+    HX_LANE_DECL;
+    if ((int) blockIdx.x >= c.n) return;
+    if (WAVE == 1) { helper_serve<LSF>(a, L); return; }
+    const long long r = blockIdx.x;
+    const AllocPrm *p = &L.P;
+    stage_stream(a, L, a.st, a.prm, a.gt);
+    const int *h = c.hdr + r * HX_DCH_WORDS;
+    const int mode = c.mode, nchan = h[HX_DCH_NCHAN], opt = h[HX_DCH_OPT], zero21 = h[HX_DCH_ZERO21];
+    const bool shortm = mode == HX_DC_SHORT || mode == HX_DC_SHORT_COUNT;
+    const bool quant = mode == HX_DC_QUANT_COUNT || mode == HX_DC_QUANT_THEN_COUNT || mode == HX_DC_SHORT;
+    if (LANE < 2) {
+        const bool on = LANE < nchan;
+        if (!shortm) {
+            // (the band count a channel is counted to: the rate loop passes one of the class's arrays; here nsf2 holds the record's)
+            L.P.nsf2[LANE] = on ? h[HX_DCH_NCB0 + LANE] : 0;
+            L.P.nsf[LANE] = on ? h[(mode == HX_DC_COUNT ? HX_DCH_NCB0 : HX_DCH_NSF0) + LANE] : 0;
+            L.P.nbmax[LANE] = on ? h[HX_DCH_NBMAX0 + LANE] : 0;
+        }
+        for (int k = 0; k < 4; k++) L.hs_table[LANE][k] = 0;
+        for (int k = 0; k < 3; k++) L.hs_cbreg[LANE][k] = 0;
+        L.hs_nbig[LANE] = 0; L.hs_nquads[LANE] = 0; L.hs_bits[LANE] = 0;
+    }
+    if (LANE == 0) { L.block_type = shortm ? 2 : h[HX_DCH_BT]; L.nchan = nchan; L.P.nchan = nchan; }
+    for (int i = LANE; i < 2 * 576; i += 64) {
+        IX(0)[i] = (ix_t) c.ix[r * 1152 + i];          // (channel 1's lines follow channel 0's in both layouts)
+        (&L.x34[0][0])[i] = quant ? c.x34[r * 1152 + i] : 0.0f;
+    }
+    if (!shortm) {
+        if (LANE < 2 * NB) {
+            const int ch = LANE / NB, b = LANE % NB;
+            L.ixmax[ch][b] = c.ixmax[(r * 2 + ch) * NB + b];
+            if (quant) L.gsf[ch][b] = c.gsf[(r * 2 + ch) * NB + b];
+        }
+    } else {
+        for (int i = LANE; i < 2 * 48; i += 64) {
+            (&L.s_ixmax[0][0][0])[i] = c.ixmax[r * 96 + i];
+            if (quant) (&L.s_gsf[0][0][0])[i] = (sgs_t) c.gsf[r * 96 + i];
+        }
+    }
+    HX_WAVE_SYNC();
+    int bits = 0;
+    if (mode == HX_DC_COUNT) {
+#if HX_A1
+        const A1Ctx cx = {0, nchan, 0, 0};
+        bits = a1_count_channels(L, p, cx);
+#else
+        bits = count_bits(L, p, p->nsf2);
+#endif
+    } else if (mode == HX_DC_QUANT_COUNT) bits = quant_count_bits(L, p, opt, zero21, p->nsf2);
+    else if (mode == HX_DC_QUANT_THEN_COUNT) {      // as bitallo_long and requant_count do it while -HF lines are quantised in between
+        do_quant(L, p, opt);
+        if (zero21) { if (LANE == 0) L.ixmax[0][21] = 0; HX_WAVE_SYNC(); }
+        bits = count_bits(L, p, p->nsf2);
+    } else {
+        if (mode == HX_DC_SHORT) s_do_quant(L, p, opt);
+        bits = s_count_bits_ch(L, p, 0);
+        if (nchan == 2) bits += s_count_bits_ch(L, p, 1);
+    }
+    HX_WAVE_SYNC();
+    for (int i = LANE; i < 2 * 576; i += 64) c.ix[r * 1152 + i] = IX(0)[i];
+    if (!shortm) { if (LANE < 2 * NB) c.ixmax[r * 2 * NB + LANE] = L.ixmax[LANE / NB][LANE % NB]; }
+    else for (int i = LANE; i < 2 * 48; i += 64) c.ixmax[r * 96 + i] = (&L.s_ixmax[0][0][0])[i];
+    if (LANE < 2) {
+        int *o = c.out + r * HX_DCO_WORDS + HX_DCO_CH * LANE;
+        for (int k = 0; k < 4; k++) o[HX_DCO_TABLE + k] = L.hs_table[LANE][k];
+        for (int k = 0; k < 3; k++) o[HX_DCO_CBREG + k] = L.hs_cbreg[LANE][k];
+        o[HX_DCO_NBIG] = L.hs_nbig[LANE]; o[HX_DCO_NQUADS] = L.hs_nquads[LANE]; o[HX_DCO_BITS] = L.hs_bits[LANE];
+    }
+    if (LANE == 0) c.out[r * HX_DCO_WORDS + HX_DCO_SUM] = bits;
+    HELPER_POST(HCMD_EXIT, 0);
+}
+
 // The two instantiations live in separate translation units (hx_alloc.hip, hx_alloc_lsf.hip): with a
 // single caller the allocator's device functions are inlined into the kernel; sharing them between
 // two kernels of one module turns them into real calls (measured: +2 ms on the MPEG-1 kernel).
 // The stream walk's waves issue ahead of the front-end and packing waves that share a SIMD with them in the launch's tail
 // (measured: +0.6 % config 2, +0.8 % config 3).
 #define HX_K6_PRIO __builtin_amdgcn_s_setprio(3)
-#define HX_K6(name, lsf) \
+// Each unit has a twin (hx_count*.hip, HX_TAP) that holds the test tap k_debug_count_* in the stream walk's place: the same
+// sources, macros and flags in a code object of its own.  A second kernel beside the walk's would change what the inliner and
+// the register allocation across calls make of the walk (tried: every function of the unit came out different).
+#if HX_TAP
+#define HX_K6(name, tap, lsf) \
+    __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void tap(AllocArgs a, HxCountArgs c) { __shared__ AllocLds L; debug_count<lsf>(a, c, L); }
+#else
+#define HX_K6(name, tap, lsf) \
     __global__ __launch_bounds__(128) __attribute__((amdgpu_waves_per_eu(HX_WAVES, HX_WAVES))) void name(AllocArgs a) { HX_K6_PRIO; __shared__ AllocLds L; alloc_stream<lsf>(a, L); }
+#endif
 #if HX_A1 && !HX_LSF
 // streams of the first-generation allocator (intensity stereo, dual channel), MPEG-1 rates
-HX_K6(k_alloc1, 0)
+HX_K6(k_alloc1, k_debug_count_a1, 0)
 #elif HX_A1
-HX_K6(k_alloc1_lsf, 1)
+HX_K6(k_alloc1_lsf, k_debug_count_a1_lsf, 1)
 #elif !HX_LSF && HX_SLIM
 // low-footprint layout, three waves per SIMD: six streams per CU (hx_alloc_slim.hip)
 #ifndef HX_PROFILE
 static_assert(sizeof(AllocLds) <= 26880, "six workgroups of the low-footprint stream walk must fit a CU's 160 KB of LDS, which is handed out in pieces of 1280 bytes");
 #endif
-HX_K6(k_alloc_slim, 0)
+HX_K6(k_alloc_slim, k_debug_count_slim, 0)
 #elif !HX_LSF
 #ifndef HX_PROFILE
 static_assert(sizeof(AllocLds) <= 40960, "four workgroups of the stream walk must fit a CU's 160 KB of LDS, which is handed out in pieces of 1280 bytes");
 #endif
-HX_K6(k_alloc, 0)
+HX_K6(k_alloc, k_debug_count, 0)
 #else
 // the same stream walk for MPEG-2 LSF batches (16 / 22.05 / 24 kHz)
-HX_K6(k_alloc_lsf, 1)
+HX_K6(k_alloc_lsf, k_debug_count_lsf, 1)
 #endif

@@ -1482,3 +1482,250 @@ extern "C" int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const
     HIPCHK(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
     return 0;
 }
+
+
+// ---- hx_debug_count: the stream walk's quantiser and Huffman counter on records of the caller's (tests only; include/hmp3_amd.h) ----
+// The kernels are the walk units' twins (k_debug_count_*, hx_alloc3.inc).  Every record is checked on the host first: the
+// quantiser's result is worked out here the way the kernel will (same expression, same tables), and what the counter would
+// then be handed must be something the walk can hand it - so no table index, line index or packed 16-bit sum of the kernel
+// sees a value it was not written for.
+
+static int count_refuse(long long r, int ch, const char *what)
+{
+    char msg[256];
+    if (ch >= 0) snprintf(msg, sizeof msg, "record %lld channel %d: %s", r, ch, what);
+    else snprintf(msg, sizeof msg, "record %lld: %s", r, what);
+    set_err("%s", msg);
+    return -1;
+}
+
+#define HX_IX_MAX 8206      // the largest value the format codes: 15 + 2^13 - 1
+
+// one line through the long-block quantiser (quant_lines, hx_alloc.hip): -1 = not a value the counter takes
+static int count_quant_line(const HxParams &p, const HxGlobalTabs &gt, int gsf, float x34, int tab, bool short_first)
+{
+    if (!(x34 >= 0.0f) || !(x34 <= 3.0e38f)) return -1;
+    const float igain = p.look_34igain[gsf];
+    float q;
+    if (tab) {
+        const float t = igain * x34 + (0.5f - 0.4375f);
+        if (!(t < 16384.0f)) return -1;
+        const int iq = std::max(std::min((int) t, 31), 0);
+        q = t - ((short_first && iq == 0) ? -.30f : gt.quant_off[iq]);
+    } else q = igain * x34 + (0.5f - 0.0946f);
+    if (!(q < 16384.0f)) return -1;
+    const int v = (int) q;
+    return (v < 0 || v > HX_IX_MAX) ? -1 : v;
+}
+
+// what count_bits_ch makes of a channel's band maxima and lines before it reads a pair: where the big values end, how many
+// count1 quadruples follow
+static void count_split(const HxParams &p, int bt, int ncb, const int *ixmax, const int *ix, int *nbig_out, int *nquads_out)
+{
+    int i;
+    for (i = ncb - 1; i >= 0; i--) if (ixmax[i] > 0) break;
+    int cb3 = i + 1;
+    for (; i >= 0; i--) if (ixmax[i] > 1) break;
+    int cb2 = i + 1;
+    if (bt == 0) { if (cb2 < 2) { cb2 = 2; if (cb3 < cb2) cb3 = cb2; } }
+    else { cb2 = std::max(cb2, 8); cb3 = std::max(cb3, cb2); }
+    int j2 = p.startBand_l[cb2 - 1], j3 = p.startBand_l[cb3 - 1];
+    for (int j = p.startBand_l[cb2 - 1]; j < p.startBand_l[cb2]; j++) if (ix[j] > 1) j2 = j;
+    for (int j = p.startBand_l[cb3 - 1]; j < p.startBand_l[cb3]; j++) if (ix[j] > 0) j3 = j;
+    int nbig = (j2 + 2) & ~1;
+    nbig = std::max(nbig, p.startBand_l[bt == 0 ? 2 : 8]);
+    int nquads = (j3 + 4 - nbig) >> 2;
+    if (bt != 0) nquads = std::max(nquads, 0);
+    *nbig_out = nbig; *nquads_out = nquads;
+}
+
+static int check_count_long(const HxParams &p, const HxGlobalTabs &gt, bool slim, int mode, long long r, const int *h,
+                            const int *ix_in, const int *ixmax_in, const float *x34, const int *gsf)
+{
+    const int bt = h[HX_DCH_BT], nchan = h[HX_DCH_NCHAN], opt = h[HX_DCH_OPT], zero21 = h[HX_DCH_ZERO21];
+    const bool quant = mode != HX_DC_COUNT;
+    if (bt != 0 && bt != 1 && bt != 3) return count_refuse(r, -1, "block type is not 0, 1 or 3");
+    if (nchan != 1 && nchan != 2) return count_refuse(r, -1, "channel count is not 1 or 2");
+    if (quant ? (opt != 0 && opt != 1 && opt != 3) || (zero21 != 0 && zero21 != 1) : (opt != 0 || zero21 != 0))
+        return count_refuse(r, -1, quant ? "opt is not 0, 1 or 1 | 2, or zero21 not 0 or 1" : "opt and zero21 are the quantising modes'");
+    for (int k = HX_DCH_NBMAX1 + 1; k < HX_DCH_WORDS; k++) if (h[k]) return count_refuse(r, -1, "a spare header word is not zero");
+    int ix[2][576 + 4], ixmax[2][22];
+    for (int c = 0; c < 2; c++) {
+        for (int j = 0; j < 576; j++) {
+            ix[c][j] = ix_in[576 * c + j];
+            if (ix[c][j] < 0 || ix[c][j] > HX_IX_MAX) return count_refuse(r, c, "a line outside 0 .. 8206");
+        }
+        for (int b = 0; b < 22; b++) {
+            ixmax[c][b] = ixmax_in[22 * c + b];
+            if (ixmax[c][b] < 0 || ixmax[c][b] > HX_IX_MAX) return count_refuse(r, c, "a band maximum outside 0 .. 8206");
+        }
+    }
+    for (int c = 0; c < nchan; c++) {
+        const int ncb = h[HX_DCH_NCB0 + c];
+        if (ncb < 1 || ncb > 22) return count_refuse(r, c, "ncb outside 1 .. 22");
+        if (!quant) {
+            if (h[HX_DCH_NSF0 + c] || h[HX_DCH_NBMAX0 + c]) return count_refuse(r, c, "nsf and nbmax are the quantising modes'");
+            continue;
+        }
+        const int nsf = h[HX_DCH_NSF0 + c], nl = h[HX_DCH_NBMAX0 + c];
+        if (nsf < 1 || nsf > 22) return count_refuse(r, c, "nsf outside 1 .. 22");
+        if (nl != p.startBand_l[nsf]) return count_refuse(r, c, "nbmax is not the first line behind band nsf - 1");
+        // lines at and past nbmax: the low-footprint layout writes zeros there unless opt & 2 (quant_lines), the others leave
+        // them alone, and the walk never hands over anything there but zeros and, under opt & 2, band 21 of an earlier -HF pass
+        const bool cleared = slim && !(opt & 2);
+        for (int j = nl; j < 576; j++) {
+            if (cleared) ix[c][j] = 0;
+            else if (ix[c][j] != 0 && !((opt & 2) && j >= p.startBand_l[21])) return count_refuse(r, c, "a line at or past nbmax is not zero (band 21 under opt & 2 may be)");
+        }
+        for (int b = 0; b < 22; b++) {
+            if (gsf[22 * c + b] < 0 || gsf[22 * c + b] > 127) return count_refuse(r, c, "a gain step outside 0 .. 127");
+            if (b < nsf) ixmax[c][b] = 0;
+        }
+        for (int j = 0; j < nl; j++) {
+            const int b = p.band_of_line[j];
+            const int v = count_quant_line(p, gt, gsf[22 * c + b], x34[576 * c + j], opt & 1, false);
+            if (v < 0) return count_refuse(r, c, "a line that is not a finite magnitude, or that quantises above 8206");
+            ix[c][j] = v;
+            ixmax[c][b] = std::max(ixmax[c][b], v);
+        }
+    }
+    if (quant && zero21) ixmax[0][21] = 0;
+    for (int c = 0; c < nchan; c++) {
+        // a band's maximum covers its lines: the tables are picked from the maxima, and a line above its table's range
+        // would index past the table
+        for (int j = 0; j < 576; j++) {
+            const int b = p.band_of_line[j];
+            if (ix[c][j] > ixmax[c][b] && !(quant && zero21 && c == 0 && b == 21)) return count_refuse(r, c, "a line above its band's maximum");
+        }
+        int nbig, nquads;
+        count_split(p, bt, h[HX_DCH_NCB0 + c], ixmax[c], ix[c], &nbig, &nquads);
+        const int end = nbig + 4 * std::max(nquads, 0);
+        // The last quadruple reaches lines 576 and 577 where the last non-zero line is 574 or 575 and nbig = 2 mod 4.
+        // Channel 0's are then channel 1's first two lines, in the reference's arrays (CMp3Enc::ix[2][576]) as in both LDS
+        // layouts, and a record may say so.  Channel 1's would be the first bytes of the reference's sign array, a mono
+        // stream's whatever channel 1's lines last held.  No stream gets there, on either channel: a band is quantised
+        // only below nsf <= 21 (L3init_sfbl_limit2 caps it; band 20 ends at line 549 at the latest), and band
+        // 21 only under -HF, which the reference keeps to 44.1 and 48 kHz and cuts to 100 lines there (bitallo3.cpp:327-331:
+        // lines up to 517 and 483), and everything above stays zero.  So there is nothing to define for channel 1: such a
+        // record is refused, and so is a mono one.
+        if (end > 576) {
+            if (c == 1 || nchan == 1) return count_refuse(r, c, "the last count1 quadruple reaches past line 575 with no second channel's lines behind it");
+            if (mode == HX_DC_QUANT_COUNT) return count_refuse(r, c, "the last count1 quadruple reads channel 1's lines while the helper wave quantises them: the walk goes unfused there");
+            ix[0][576] = ix[1][0]; ix[0][577] = ix[1][1];       // (as channel 1's quantiser leaves them, where it runs)
+        }
+        for (int j = nbig; j < end; j++) if (ix[c][j] > 1) return count_refuse(r, c, "a count1 quadruple holds a value above 1");
+    }
+    return 0;
+}
+
+static int check_count_short(const HxParams &p, const HxGlobalTabs &gt, int mode, long long r, const int *h,
+                             const int *ix_in, const int *ixmax_in, const float *x34, const int *gsf)
+{
+    const int nchan = h[HX_DCH_NCHAN], opt = h[HX_DCH_OPT];
+    const bool quant = mode == HX_DC_SHORT;
+    if (nchan != 1 && nchan != 2) return count_refuse(r, -1, "channel count is not 1 or 2");
+    if (opt != 0 && !(quant && opt == 1)) return count_refuse(r, -1, "opt is not 0 or 1, or set where nothing is quantised");
+    for (int k = 0; k < HX_DCH_WORDS; k++) if (k != HX_DCH_NCHAN && k != HX_DCH_OPT && h[k]) return count_refuse(r, -1, "a header word a short record does not use is not zero");
+    for (int c = 0; c < 2; c++)             // (s_do_quant quantises both channels' lines, whatever the channel count)
+        for (int w = 0; w < 3; w++) {
+            int bmax[16] = {0};
+            for (int j = 0; j < 192; j++) {
+                int v = ix_in[(3 * c + w) * 192 + j];
+                if (v < 0 || v > HX_IX_MAX) return count_refuse(r, c, "a line outside 0 .. 8206");
+                if (j >= p.nbmax_s) continue;
+                const int b = p.sband_of_line[j];
+                if (quant) {
+                    const int g = gsf[(3 * c + w) * 16 + b];
+                    if (g < 0 || g > 127) return count_refuse(r, c, "a gain step outside 0 .. 127");
+                    v = count_quant_line(p, gt, g, x34[(3 * c + w) * 192 + j], opt, true);
+                    if (v < 0) return count_refuse(r, c, "a line that is not a finite magnitude, or that quantises above 8206");
+                }
+                bmax[b] = std::max(bmax[b], v);
+            }
+            for (int b = 0; b < 16; b++) {
+                const int m = ixmax_in[(3 * c + w) * 16 + b];
+                if (m < 0 || m > HX_IX_MAX) return count_refuse(r, c, "a band maximum outside 0 .. 8206");
+                if (!quant && c < nchan && m < bmax[b]) return count_refuse(r, c, "a line above its band's maximum");
+            }
+        }
+    return 0;
+}
+
+extern "C" int hx_debug_count(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int n, const int *hdr, int *ix, int *ixmax,
+                              const float *x34, const int *gsf, int *out)
+{
+    if (!ec || !unit || !hdr || !ix || !ixmax || !out) { set_err("null buffer"); return -1; }
+    if (mode < 0 || mode >= HX_DC_MODES) { set_err("hx_debug_count: no such mode"); return -1; }
+    const bool quant = mode == HX_DC_QUANT_COUNT || mode == HX_DC_QUANT_THEN_COUNT || mode == HX_DC_SHORT;
+    const bool shortm = mode == HX_DC_SHORT || mode == HX_DC_SHORT_COUNT;
+    if (quant && (!x34 || !gsf)) { set_err("null buffer"); return -1; }
+    if (n <= 0 || n > HX_DEBUG_COUNT_MAX) { set_err("hx_debug_count takes 1 .. 16384 records per call"); return -1; }
+    static const char *const units[5] = {"k_alloc", "k_alloc_slim", "k_alloc_lsf", "k_alloc1", "k_alloc1_lsf"};
+    int u = -1;
+    for (int k = 0; k < 5; k++) if (!strcmp(unit, units[k])) u = k;
+    if (u < 0) { set_err("hx_debug_count: no stream-walk unit named %s", unit); return -1; }
+    std::vector<HxParams> prm(1);
+    if (!hx_resolve((const HxControl *) ec, &prm[0])) { set_err("configuration rejected"); return -1; }
+    std::vector<HxGlobalTabs> gt(1);
+    hx_global_tabs(&gt[0]);
+    // the unit that walks a stream of this control (hx_batch_create: kind = 2 * first-generation + MPEG-2)
+    const int kind = 2 * (prm[0].alloc1 ? 1 : 0) + (prm[0].h_id ? 0 : 1);
+    static const int unit_kind[5] = {0, 0, 1, 2, 3};
+    if (unit_kind[u] != kind) { set_err("hx_debug_count: %s does not run streams of this control", unit); return -1; }
+    if (u == 1 && !hx_slim_tables_ok(&prm[0], &gt[0])) { set_err("hx_debug_count: the host's tables do not have the structure k_alloc_slim derives them from"); return -1; }
+    const int nband = shortm ? 48 : 22;
+    for (long long r = 0; r < n; r++) {
+        const int *h = hdr + r * HX_DCH_WORDS;
+        const int rc = shortm ? check_count_short(prm[0], gt[0], mode, r, h, ix + r * 1152, ixmax + r * 96, quant ? x34 + r * 1152 : nullptr, quant ? gsf + r * 96 : nullptr)
+                              : check_count_long(prm[0], gt[0], u == 1, mode, r, h, ix + r * 1152, ixmax + r * 44, quant ? x34 + r * 1152 : nullptr, quant ? gsf + r * 44 : nullptr);
+        if (rc != 0) return -1;
+    }
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return -1; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return -1; }
+    HIPCHK(hipSetDevice(device));
+    struct Dev {
+        std::vector<void *> mem;
+        ~Dev() { for (void *p : mem) (void) hipFree(p); }
+        void *up(const void *src, size_t bytes)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+            mem.push_back(q);
+            if (src ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(q, 0, bytes) != hipSuccess) return nullptr;
+            return q;
+        }
+    } dev;
+    std::vector<HxStream> st(1);
+    hx_stream_reset(&prm[0], 0, &st[0]);
+    const size_t N = (size_t) n;
+    AllocArgs a = {};
+    HxCountArgs c = {};
+    a.st = (HxStream *) dev.up(st.data(), sizeof(HxStream));
+    a.prm = (const HxParams *) dev.up(prm.data(), sizeof(HxParams));
+    a.gt = (const HxGlobalTabs *) dev.up(gt.data(), sizeof(HxGlobalTabs));
+    a.done_counter = (int *) dev.up(nullptr, sizeof(int) * HX_CNT_WORDS);
+    a.S = 1; a.NG = 2; a.npos = 1;
+    c.mode = mode; c.n = n; c.nband = nband;
+    c.hdr = (const int *) dev.up(hdr, sizeof(int) * HX_DCH_WORDS * N);
+    c.ix = (int *) dev.up(ix, sizeof(int) * 1152 * N);
+    c.ixmax = (int *) dev.up(ixmax, sizeof(int) * 2 * nband * N);
+    c.x34 = quant ? (const float *) dev.up(x34, sizeof(float) * 1152 * N) : nullptr;
+    c.gsf = quant ? (const int *) dev.up(gsf, sizeof(int) * 2 * nband * N) : nullptr;
+    c.out = (int *) dev.up(nullptr, sizeof(int) * HX_DCO_WORDS * N);
+    if (!a.st || !a.prm || !a.gt || !a.done_counter || !c.hdr || !c.ix || !c.ixmax || (quant && (!c.x34 || !c.gsf)) || !c.out) { set_err("hipMalloc or upload failed"); return -1; }
+    const dim3 grid((unsigned) n), block(128);
+    if (u == 0) LAUNCH(k_debug_count, grid, block, 0, a, c);
+    else if (u == 1) LAUNCH(k_debug_count_slim, grid, block, 0, a, c);
+    else if (u == 2) LAUNCH(k_debug_count_lsf, grid, block, 0, a, c);
+    else if (u == 3) LAUNCH(k_debug_count_a1, grid, block, 0, a, c);
+    else LAUNCH(k_debug_count_a1_lsf, grid, block, 0, a, c);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(ix, c.ix, sizeof(int) * 1152 * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(ixmax, c.ixmax, sizeof(int) * 2 * nband * N, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, c.out, sizeof(int) * HX_DCO_WORDS * N, hipMemcpyDeviceToHost));
+    return 0;
+}

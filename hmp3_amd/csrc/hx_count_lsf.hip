@@ -1,0 +1,4 @@
+// hx_count_lsf.hip - the twin of hx_alloc_lsf.hip that holds the test tap k_debug_count_lsf (tests only, hx_debug_count) in the stream walk's
+// place: the same sources, macros and flags (HX_TAP, hx_alloc3.inc).
+#define HX_TAP 1
+#include "hx_alloc_lsf.hip"

@@ -82,6 +82,11 @@ __global__ void k_alloc_slim(AllocArgs a);
 __global__ void k_alloc_lsf(AllocArgs a);
 __global__ void k_alloc1(AllocArgs a);
 __global__ void k_alloc1_lsf(AllocArgs a);
+__global__ void k_debug_count(AllocArgs a, HxCountArgs c);          // (hx_alloc3.inc, one per stream-walk unit: the units' twins hx_count*.hip)
+__global__ void k_debug_count_slim(AllocArgs a, HxCountArgs c);
+__global__ void k_debug_count_lsf(AllocArgs a, HxCountArgs c);
+__global__ void k_debug_count_a1(AllocArgs a, HxCountArgs c);
+__global__ void k_debug_count_a1_lsf(AllocArgs a, HxCountArgs c);
 __global__ void k_debug_math(int fn, const unsigned *in, long long n, unsigned *out, const HxGlobalTabs *gt, const HxParams *gp);     // (hx_alloc1.inc, the k_alloc1 unit)
 
 // every kernel launch is checked where it is made: a bad configuration or a lost device is reported

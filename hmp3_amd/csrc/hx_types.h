@@ -348,6 +348,33 @@ struct AllocArgs {
     int fpc;
 };
 
+// ---- k_debug_count_* (hx_alloc3.inc; tests only, hx_debug_count): the stream walk's quantiser and Huffman counter on
+// records of the caller's, one workgroup per record.  What a record holds, per mode (hx_batch.hip checks every one before
+// a launch; include/hmp3_amd.h describes them for the caller):
+enum HxDebugCount {
+    HX_DC_COUNT,            // count_bits on given lines and band maxima (first-generation units: a1_count_channels)
+    HX_DC_QUANT_COUNT,      // quant_count_bits: one work order to the helper wave
+    HX_DC_QUANT_THEN_COUNT, // do_quant, the M/S clearing of band 21's maximum, count_bits: the route under -HF
+    HX_DC_SHORT,            // s_do_quant, then s_count_bits_ch per channel
+    HX_DC_SHORT_COUNT,      // s_count_bits_ch per channel on given lines and maxima
+    HX_DC_MODES
+};
+// header words of a record
+enum { HX_DCH_BT, HX_DCH_NCHAN, HX_DCH_NCB0, HX_DCH_NCB1, HX_DCH_OPT, HX_DCH_ZERO21, HX_DCH_NSF0, HX_DCH_NSF1, HX_DCH_NBMAX0, HX_DCH_NBMAX1, HX_DCH_WORDS = 16 };
+// result words of a record: per channel the counter's ten outputs, then the returned sum
+enum { HX_DCO_TABLE = 0, HX_DCO_CBREG = 4, HX_DCO_NBIG = 7, HX_DCO_NQUADS = 8, HX_DCO_BITS = 9, HX_DCO_CH = 10, HX_DCO_SUM = 20, HX_DCO_WORDS = 24 };
+#define HX_DEBUG_COUNT_MAX 16384    // records per call
+struct HxCountArgs {
+    int mode, n;
+    int nband;              // band maxima / gain steps per channel: 22 of a long record, 48 = [3][16] of a short one
+    const int *hdr;         // [n][HX_DCH_WORDS]
+    int *ix;                // [n][2][576] lines: as they stand before the call, as the functions left them after it
+    int *ixmax;             // [n][2][nband] band maxima, the same way
+    const float *x34;       // [n][2][576] (the quantising modes)
+    const int *gsf;         // [n][2][nband] gain steps (the quantising modes)
+    int *out;               // [n][HX_DCO_WORDS]
+};
+
 
 // ---- slot operations (hx_slots.hip: k_slot_reset / k_slot_gather / k_slot_scatter) ----
 // One listed slot of an operation: the slot, the receiving batch's class of it, the configuration fingerprint a

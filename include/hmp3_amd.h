@@ -924,6 +924,35 @@ long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *name, void *ds
 int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, int fps, const int *nfr,
                   const void *seg, const short *ixq, const unsigned *sgn, const void *frm, const void *slots,
                   unsigned char *rows, long long out_stride, unsigned char *packet, long long packet_bytes, int *status);
+/* For tests: the stream walk's quantiser and Huffman counter - do_quant, quant_count_bits, count_bits, s_do_quant,
+   s_count_bits_ch and what they call, unmodified - on records of the caller's.  One workgroup of two waves per record, as
+   the walk has them: channel 1 runs on the helper wave, through the walk's work orders.  All pointers are host memory.
+   unit names the build of the walk whose twin runs the records: "k_alloc", "k_alloc_slim", "k_alloc_lsf", "k_alloc1",
+   "k_alloc1_lsf"; ec is a control whose streams that unit walks (its band tables are the records'), any other is refused.
+   mode: 0 count            count_bits (the first-generation units: the channels one after the other, as their walk does)
+         1 quant_count      quant_count_bits: quantise and count in one work order
+         2 quant, count     do_quant, the clearing of channel 0's band-21 maximum if zero21, count_bits: the walk's route
+                            while -HF lines are quantised in between
+         3 short            s_do_quant, then s_count_bits_ch per channel
+         4 short count      s_count_bits_ch per channel
+   n records, 1 .. 16384.  hdr [n][16]: {block type 0 / 1 / 3, channels 1 / 2, ncb[2], opt, zero21, nsf[2], nbmax[2]}, the
+   rest zero; the quantising modes alone read opt (0, 1, or 1 | 2; short: 0 or 1), zero21, nsf and nbmax (= the first line
+   behind band nsf - 1); a short record has the channel count and opt only.  ix [n][2][576] (short: [n][2][3][192]): the
+   lines as they stand before the call, and after it as the functions left them.  ixmax [n][2][22] (short: [n][2][3][16]):
+   the band maxima, the same way.  x34 [n][2][576] and gsf [n][2][22] (short: [n][2][3][16]): magnitudes^(3/4) and gain
+   steps, read by the quantising modes (null otherwise).  out [n][24]: per channel {table[4], cbreg[3], nbig, nquads, bits}
+   as the counter left them (zeros for a channel that was not counted), then at [20] the returned sum.
+   A record is checked on the host before anything is launched, its quantiser's result worked out there first, and refused
+   with -1 and hx_last_error unless the walk could hand it over: lines and maxima 0 .. 8206, gain steps 0 .. 127, finite
+   magnitudes that quantise to at most 8206, every line at most its band's maximum, lines at and past nbmax zero (band 21
+   under opt & 2 excepted; the low-footprint unit without opt & 2 writes them itself and takes anything), count1
+   quadruples of 0 and 1 only.  The last quadruple of channel 0 may reach lines 576 and 577 - channel 1's lines 0 and 1, as
+   in the reference - in modes 0 and 2 of a two-channel record; in mode 1 the helper wave would be writing them.  Channel
+   1's, or a mono record's, may not: the reference would read its sign bytes there, and no stream gets there on either
+   channel - nothing is quantised above line 549 without -HF or above line 517 with it (check_count_long in
+   hmp3_amd/csrc/hx_batch.hip has the argument) - so there is nothing to define.  Returns 0.  Synchronises. */
+int hx_debug_count(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int n, const int *hdr, int *ix, int *ixmax,
+                   const float *x34, const int *gsf, int *out);
 
 /* ---- Xing / Info / LAME tag frame (first frame of a file; reference pub/xhead.h) ----
    Same arguments and return values as the reference functions; the seek-table state that the

@@ -252,6 +252,13 @@ void  hxo_bitallo_long(hxo_encoder *e, float xr[2][576], hxo_sigmask sm[2][36],
 /* Huffman bit count + table/region choice for one channel (bitalloc.cpp:470) */
 typedef struct { int table[4]; int cbreg[3]; int nbig, nquads, bits; } hxo_huffsel;
 int   hxo_count_bits(const hxo_params *p, const int *ixmax, const int *ix, int ncb, int opti, int block_type, hxo_huffsel *out);
+/* the quantisers and the counters on arrays and on the records of the quantise-and-count tests (hxo_alloc.c, hxo_short.c) */
+void  hxo_do_quant(const hxo_params *p, int nchan, const int nsf[2], int opt, float x34[][576], int gsf[][22], int ix[][576], int ixmax[][22]);
+int   hxo_quant_lines(const hxo_params *p, int rule, const float *x34, int *ix, int gsf, int n);
+int   hxo_count_record(const hxo_params *p, int quant, int clear_past, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out);
+int   hxo_count_record_short(const hxo_params *p, int quant, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out);
+const hxo_params *hxo_params_of(const hxo_encoder *e);
+void  hxo_band_tables(const hxo_params *p, int *tl, int *ts);
 void  hxo_huffsel_to_gr(const hxo_params *p, const hxo_huffsel *s, hxo_gr *g);  /* bitalloc.cpp:758 */
 
 /* bit writer (l3pack.c:107-152) */

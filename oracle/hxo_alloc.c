@@ -599,19 +599,55 @@ static void big_lucky_noise(ba_t *b)
     }
 }
 
-static void do_quant(ba_t *b, int opt)      /* bitallo3.cpp:1540-1585 */
+/* bitallo3.cpp:1540-1585 on arrays: every band below nsf[ch] of every channel, opt = the magnitude-dependent offset */
+void hxo_do_quant(const hxo_params *p, int nchan, const int nsf[2], int opt, float x34[][576], int gsf[][22], int ix[][576], int ixmax[][22])
 {
-    const hxo_params *p = b->p;
     int ch, i;
-    for (ch = 0; ch < b->nchan; ch++) {
-        const float *x = b->x34[ch];
-        int *qx = b->ix[ch];
-        for (i = 0; i < p->nsf[ch]; i++) {
+    for (ch = 0; ch < nchan; ch++) {
+        const float *x = x34[ch];
+        int *qx = ix[ch];
+        for (i = 0; i < nsf[ch]; i++) {
             int n = p->nBand_l[i];
-            b->e->s.ixmax[ch][i] = opt ? quant_opt(p, x, qx, b->gsf[ch][i], n) : quant_plain(p, x, qx, b->gsf[ch][i], n);
+            ixmax[ch][i] = opt ? quant_opt(p, x, qx, gsf[ch][i], n) : quant_plain(p, x, qx, gsf[ch][i], n);
             x += n; qx += n;
         }
     }
+}
+
+static void do_quant(ba_t *b, int opt) { hxo_do_quant(b->p, b->nchan, b->p->nsf, opt, b->x34, b->gsf, b->ix, b->e->s.ixmax); }
+
+/* the three quantisers on one run of lines (tests): rule 0 = vect_quant, 1 = vect_quantB, 2 = vect_quantB2 with the -HF band's -0.30 */
+int hxo_quant_lines(const hxo_params *p, int rule, const float *x34, int *ix, int gsf, int n)
+{
+    return rule == 0 ? quant_plain(p, x34, ix, gsf, n) : (rule == 1 ? quant_opt(p, x34, ix, gsf, n) : quant_opt2(p, x34, ix, gsf, n, -.30f));
+}
+
+/* One long-block record of the quantise-and-count tests (tests/count_cases.py) through do_quant and the counter; the layout
+   is hx_debug_count's (include/hmp3_amd.h).  quant = 0: count the lines as given.  quant = 1: quantise first, as the rate loop
+   does before either of its two count calls; clear_past: the rule of the low-footprint line buffer, which holds something
+   else before the quantiser runs - lines at and past nbmax are written as zero unless opt & 2.  hxo_count_bits reads channel
+   0's lines 576 and 577 where its last quadruple reaches them: channel 1's first two, the record's arrays being the reference's. */
+int hxo_count_record(const hxo_params *p, int quant, int clear_past, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out)
+{
+    const int bt = hdr[0], nchan = hdr[1], opt = hdr[4], zero21 = hdr[5];
+    int ch, j, bits = 0;
+    memset(out, 0, 24 * sizeof(int));
+    if (quant) {
+        hxo_do_quant(p, nchan, hdr + 6, opt & 1, (float (*)[576]) x34, (int (*)[22]) gsf, (int (*)[576]) ix, (int (*)[22]) ixmax);
+        if (clear_past && !(opt & 2))
+            for (ch = 0; ch < nchan; ch++) for (j = p->startBand_l[hdr[6 + ch]]; j < 576; j++) ix[576 * ch + j] = 0;
+        if (zero21) ixmax[21] = 0;
+    }
+    for (ch = 0; ch < nchan; ch++) {
+        hxo_huffsel hs;
+        int *o = out + 10 * ch;
+        bits += hxo_count_bits(p, ixmax + 22 * ch, ix + 576 * ch, hdr[2 + ch], 1, bt, &hs);
+        for (j = 0; j < 4; j++) o[j] = hs.table[j];
+        for (j = 0; j < 3; j++) o[4 + j] = hs.cbreg[j];
+        o[7] = hs.nbig; o[8] = hs.nquads; o[9] = hs.bits;
+    }
+    out[20] = bits;
+    return bits;
 }
 
 static int count_bits_n(ba_t *b, const int ncb[2])      /* bitallo3.cpp:1740-1780 */

@@ -21,6 +21,14 @@ unsigned hxo_frames_out(const hxo_encoder *e) { return e->s.tot_frames_out; }
 unsigned hxo_bytes_out(const hxo_encoder *e) { return e->s.tot_bytes_out; }
 /* which kernel a stream of this configuration runs on (path census): bit 0 MPEG-1 rates, bit 1 first-generation allocator,
    bit 2 mono, bit 3 -HF in force */
+const hxo_params *hxo_params_of(const hxo_encoder *e) { return &e->p; }
+/* tests: the allocators' band tables, long {nBand_l[22], startBand_l[24]} and short {nBand_s[13], startBand_s[14], nsfs} */
+void hxo_band_tables(const hxo_params *p, int *tl, int *ts)
+{
+    memcpy(tl, p->nBand_l, 22 * sizeof(int)); memcpy(tl + 22, p->startBand_l, 24 * sizeof(int));
+    memcpy(ts, p->nBand_s, 13 * sizeof(int)); memcpy(ts + 13, p->startBand_s, 14 * sizeof(int));
+    ts[27] = p->nsfs;
+}
 int hxo_stream_kind(const hxo_encoder *e) { return e->p.h_id | (e->p.alloc1 << 1) | ((e->p.nchan == 1) << 2) | ((e->p.hf_flag != 0) << 3); }
 void hxo_range_counts_get(const hxo_encoder *e, int short_blocks, long long out[3])
 {

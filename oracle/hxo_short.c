@@ -455,6 +455,39 @@ static int count_bits(sba_t *b)
     return bits;
 }
 
+/* One short-block record of the quantise-and-count tests (tests/count_cases.py) through do_quant (quant = 1) and the counter
+   of every channel; the layout is hx_debug_count's (include/hmp3_amd.h). */
+int hxo_count_record_short(const hxo_params *p, int quant, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out)
+{
+    sba_t *b = (sba_t *) calloc(1, sizeof(sba_t));
+    const int nchan = hdr[1], opt = hdr[4];
+    int ch, j, bits;
+    memset(out, 0, 24 * sizeof(int));
+    if (!b) return -1;
+    b->p = p;
+    b->nchan = nchan;
+    b->nsf[0] = b->nsf[1] = p->nsfs;
+    memcpy(b->ix, ix, sizeof(b->ix));
+    memcpy(b->ixmax, ixmax, sizeof(b->ixmax));
+    if (quant) {
+        memcpy(b->x34, x34, sizeof(b->x34));
+        memcpy(b->gsf, gsf, sizeof(b->gsf));
+        do_quant(b, opt);
+    }
+    bits = count_bits(b);
+    memcpy(ix, b->ix, sizeof(b->ix));
+    memcpy(ixmax, b->ixmax, sizeof(b->ixmax));
+    for (ch = 0; ch < nchan; ch++) {
+        int *o = out + 10 * ch;
+        for (j = 0; j < 4; j++) o[j] = b->save[ch].table[j];
+        for (j = 0; j < 3; j++) o[4 + j] = b->save[ch].cbreg[j];
+        o[7] = b->save[ch].nbig; o[8] = b->save[ch].nquads; o[9] = b->save[ch].bits;
+    }
+    out[20] = bits;
+    free(b);
+    return bits;
+}
+
 static void bump_gsf(sba_t *b, int delta, int only_over)
 {
     int ch, w, i;

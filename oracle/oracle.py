@@ -441,6 +441,104 @@ def huff_pair_len(t, x, y):
     return int(lib().hxo_huff_pair_len(int(t), int(x), int(y)))
 
 
+# ---- the quantisers and Huffman counters on records (hxo_count_record*, oracle/hxo.h; ref_count_record*, oracle/ref_harness.cpp) ----
+# The record layout is hx_debug_count's (include/hmp3_amd.h): hdr [n][16], lines [n][2][576], band maxima [n][2][22] or, of a
+# short record, [n][2][3][16], x34 and gain steps likewise.  COUNT_GR: what output_subdivide2 hands on of a long channel.
+COUNT_OUT = ["table0", "table1", "table2", "count1table", "cb0", "cb1", "cb2", "nbig", "nquads", "bits"]
+COUNT_GR = ["table_select0", "table_select1", "table_select2", "count1table_select", "big_values", "region0_count", "region1_count",
+            "aux_nreg0", "aux_nreg1", "aux_nreg2", "aux_nquads"]
+
+
+class CountTables:
+    """the tables of one control that the records are built on and counted with: an initialised oracle encoder's (and, with
+    use_ref, a reference encoder's of the same control)"""
+
+    def __init__(self, ec, use_ref=False):
+        self.enc = OracleEncoder(ec)
+        assert self.enc.ok()
+        l = lib()
+        l.hxo_params_of.restype = C.c_void_p
+        l.hxo_params_of.argtypes = [C.c_void_p]
+        self.p = l.hxo_params_of(self.enc.h)
+        tl, ts = np.zeros(46, np.int32), np.zeros(28, np.int32)
+        l.hxo_band_tables.argtypes = [C.c_void_p] * 3
+        l.hxo_band_tables(self.p, tl.ctypes.data, ts.ctypes.data)
+        self.nBand_l, self.startBand_l = tl[:22].copy(), tl[22:].copy()
+        self.nBand_s, self.startBand_s, self.nsfs = ts[:13].copy(), ts[13:27].copy(), int(ts[27])
+        self.ref = RefEncoder(ec) if use_ref else None
+        if use_ref:
+            rl, rs = np.zeros(46, np.int32), np.zeros(28, np.int32)
+            ref().ref_band_tables.argtypes = [C.c_void_p] * 3
+            ref().ref_band_tables(self.ref.h, rl.ctypes.data, rs.ctypes.data)
+            assert (rl == tl).all() and (rs == ts).all(), "the oracle's band tables are not the reference's"
+
+    def quant_lines(self, rule, x34, gsf, use_ref=False):
+        """int32 [n]: x34 through quantiser `rule` (0 plain, 1 table offsets, 2 the same with the first offset at -0.30) at gain step gsf"""
+        x = np.ascontiguousarray(x34, dtype=np.float32).copy()
+        out = np.zeros(x.size, np.int32)
+        if use_ref:
+            f = ref().ref_quant_lines
+            f.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            f(int(rule), x.ctypes.data, out.ctypes.data, int(gsf), x.size)
+        else:
+            f = lib().hxo_quant_lines
+            f.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+            f(self.p, int(rule), x.ctypes.data, out.ctypes.data, int(gsf), x.size)
+        return out
+
+
+def ref_has_count_records():
+    """whether the reference build at hand was made with the quantise-and-count entries in its harness"""
+    return ref() is not None and hasattr(ref(), "ref_count_record")
+
+
+def count_records(tabs, mode, hdr, ix, ixmax, x34=None, gsf=None, clear_past=False, use_ref=False):
+    """n records through the oracle's quantiser and counter (use_ref: the reference's own).  mode: "count", "quant" (either of
+    the device's two long routes), "short", "short_count".  -> (lines, band maxima, out, sums): copies of ix and ixmax as
+    the functions left them; the returned sum of every record; out [n][24] as hx_debug_count leaves it (oracle) or, from the
+    reference, per channel at [.., 12 ch:] the returned bits and COUNT_GR (long) / at [.., 10 ch:] COUNT_OUT (short)."""
+    hdr = np.ascontiguousarray(hdr, dtype=np.int32)
+    n = hdr.shape[0]
+    short = mode.startswith("short")
+    quant = mode in ("quant", "short")
+    nb = 96 if short else 44
+    ix = np.array(ix, dtype=np.int32, order="C").reshape(n, 1152)
+    ixmax = np.array(ixmax, dtype=np.int32, order="C").reshape(n, nb)
+    x34 = np.zeros((n, 1152), np.float32) if x34 is None else np.array(x34, dtype=np.float32, order="C").reshape(n, 1152)
+    gsf = np.zeros((n, nb), np.int32) if gsf is None else np.ascontiguousarray(gsf, dtype=np.int32).reshape(n, nb)
+    out = np.zeros((n, 24), np.int32)
+    total = np.zeros(n, np.int32)
+    V = C.c_void_p
+    if use_ref:
+        f = ref().ref_count_record_short if short else ref().ref_count_record
+        f.argtypes = [V, C.c_int] + [V] * 6
+        for r in range(n):
+            total[r] = f(tabs.ref.h, int(quant), hdr[r].ctypes.data, ix[r].ctypes.data, ixmax[r].ctypes.data, x34[r].ctypes.data, gsf[r].ctypes.data, out[r].ctypes.data)
+        return ix, ixmax, out, total
+    elif short:
+        f = lib().hxo_count_record_short
+        f.argtypes = [V, C.c_int] + [V] * 6
+        for r in range(n):
+            f(tabs.p, int(quant), hdr[r].ctypes.data, ix[r].ctypes.data, ixmax[r].ctypes.data, x34[r].ctypes.data, gsf[r].ctypes.data, out[r].ctypes.data)
+    else:
+        f = lib().hxo_count_record
+        f.argtypes = [V, C.c_int, C.c_int] + [V] * 6
+        for r in range(n):
+            f(tabs.p, int(quant), int(clear_past), hdr[r].ctypes.data, ix[r].ctypes.data, ixmax[r].ctypes.data, x34[r].ctypes.data, gsf[r].ctypes.data, out[r].ctypes.data)
+    return ix, ixmax, out, out[:, 20].copy()
+
+
+def count_out_to_gr(tabs, out10):
+    """COUNT_GR of a long channel's COUNT_OUT, by the oracle's output_subdivide2 (hxo_huffsel_to_gr)"""
+    hs = np.ascontiguousarray(out10, dtype=np.int32)
+    g = np.zeros(27, np.int32)
+    f = lib().hxo_huffsel_to_gr
+    f.argtypes = [C.c_void_p] * 3
+    f.restype = None
+    f(tabs.p, hs.ctypes.data, g.ctypes.data)
+    return [int(g[7]), int(g[8]), int(g[9]), int(g[17]), int(g[1]), int(g[13]), int(g[14]), int(g[21]), int(g[22]), int(g[23]), int(g[18])]
+
+
 def huff_tables():
     """the oracle's code tables: {"dim": [32], "linbits": [32], "len": {(t, x, y): bits}, "code": {(t, x, y): word},
     "quada": [(code, len)] * 16}; x, y below the table's dimension"""

@@ -186,6 +186,90 @@ void ref_psy_tables(void *h, int *nsumL, int *cntoffL, float *wL, int *nsumS, in
     memcpy(wS, e->w_spdShort, sizeof(float) * 1000);
 }
 
+/* The reference's quantisers and Huffman counters on the records of the quantise-and-count tests (tests/count_cases.py; the
+ * layout is hx_debug_count's, include/hmp3_amd.h; pins hxo_count_record / hxo_count_record_short, oracle/hxo.h).  h: an
+ * encoder initialised with a control of the second-generation allocator, whose band tables the allocator objects hold.
+ * Long records: vect_quant / vect_quantB band by band as CBitAllo3::quant / quantB walk them (quant = 1), then
+ * CBitAllo::subdivide2 (which goes on to subdivide2BT13 at block types 1 and 3) per channel on the record's own arrays - ix is
+ * [2][576] like CMp3Enc::ix, so what a last quadruple reads behind channel 0 is channel 1 - and output_subdivide2, the one
+ * way to what subdivide2 keeps in file statics.  out [2][12] per channel: {bits returned, table_select[3],
+ * count1table_select, big_values, region0_count, region1_count, aux_nreg[3], aux_nquads}. */
+int ref_count_record(void *h, int quant, const int *hdr, int *ix, int *ixmax, float *x34, const int *gsf, int *out)
+{
+    CBitAllo3 *b = (CBitAllo3 *) ((CMp3Enc *) h)->BitAllo;
+    const int bt = hdr[0], nchan = hdr[1], opt = hdr[4], zero21 = hdr[5];
+    const int saved_bt = b->block_type;
+    int bits = 0;
+    memset(out, 0, 2 * 12 * sizeof(int));
+    if (quant) {
+        for (int ch = 0; ch < nchan; ch++) {
+            float *x = x34 + 576 * ch;
+            int *qx = ix + 576 * ch;
+            for (int i = 0; i < hdr[6 + ch]; i++) {
+                const int n = b->nBand_l[i];
+                ixmax[22 * ch + i] = (opt & 1) ? vect_quantB(x, qx, gsf[22 * ch + i], n) : vect_quant(x, qx, gsf[22 * ch + i], n);
+                x += n; qx += n;
+            }
+        }
+        if (zero21) ixmax[21] = 0;
+    }
+    b->block_type = bt;
+    for (int ch = 0; ch < nchan; ch++) {
+        int *o = out + 12 * ch;
+        GR g;
+        memset(&g, 0, sizeof(g));
+        o[0] = b->subdivide2(ixmax + 22 * ch, ix + 576 * ch, hdr[2 + ch], 1, ch);
+        b->output_subdivide2(&g, ch);
+        o[1] = g.table_select[0]; o[2] = g.table_select[1]; o[3] = g.table_select[2]; o[4] = g.count1table_select;
+        o[5] = g.big_values; o[6] = g.region0_count; o[7] = g.region1_count;
+        o[8] = g.aux_nreg[0]; o[9] = g.aux_nreg[1]; o[10] = g.aux_nreg[2]; o[11] = g.aux_nquads;
+        bits += o[0];
+    }
+    b->block_type = saved_bt;
+    return bits;
+}
+/* Short records: vect_quant, or vect_quantB2 with the first offset at -0.30 (opt), band by band as CBitAlloShort::quant /
+ * quantB walk them, then CBitAlloShort::subdivide2 per channel.  out [2][10] per channel: what subdivide2 saved -
+ * {ntable_out[4], cbreg[3], nbig, nquads, bits}; returns the sum. */
+int ref_count_record_short(void *h, int quant, const int *hdr, int *ix, int *ixmax, float *x34, const int *gsf, int *out)
+{
+    CBitAlloShort *s = &((CBitAllo3 *) ((CMp3Enc *) h)->BitAllo)->BitAlloShort;
+    const int nchan = hdr[1], opt = hdr[4];
+    int bits = 0;
+    memset(out, 0, 2 * 10 * sizeof(int));
+    for (int ch = 0; ch < nchan; ch++) {
+        if (quant)
+            for (int w = 0; w < 3; w++) {
+                float *x = x34 + (3 * ch + w) * 192;
+                int *qx = ix + (3 * ch + w) * 192;
+                for (int i = 0; i < s->nsf[ch]; i++) {
+                    const int n = s->nBand_s[i], g = gsf[(3 * ch + w) * 16 + i];
+                    ixmax[(3 * ch + w) * 16 + i] = opt ? vect_quantB2(x, qx, g, n, -.30f) : vect_quant(x, qx, g, n);
+                    x += n; qx += n;
+                }
+            }
+        int *o = out + 10 * ch;
+        bits += s->subdivide2((int (*)[16]) (ixmax + 48 * ch), (int (*)[192]) (ix + 576 * ch), s->nsf[ch], ch);
+        for (int k = 0; k < 4; k++) o[k] = s->save[ch].ntable_out[k];
+        for (int k = 0; k < 3; k++) o[4 + k] = s->save[ch].cbreg[k];
+        o[7] = s->save[ch].nbig; o[8] = s->save[ch].nquads; o[9] = s->save[ch].bits;
+    }
+    return bits;
+}
+/* the three quantisers on one run of lines (rule 0 = vect_quant, 1 = vect_quantB, 2 = vect_quantB2 at -0.30); returns the maximum */
+int ref_quant_lines(int rule, float *x34, int *ix, int gsf, int n)
+{
+    return rule == 0 ? vect_quant(x34, ix, gsf, n) : (rule == 1 ? vect_quantB(x34, ix, gsf, n) : vect_quantB2(x34, ix, gsf, n, -.30f));
+}
+/* the band tables the handle's allocators hold: long {nBand_l[22], startBand_l[24]}, short {nBand_s[13], startBand_s[14], nsf} */
+void ref_band_tables(void *h, int *tl, int *ts)
+{
+    CBitAllo3 *b = (CBitAllo3 *) ((CMp3Enc *) h)->BitAllo;
+    memcpy(tl, b->nBand_l, 22 * sizeof(int)); memcpy(tl + 22, b->startBand_l, 24 * sizeof(int));
+    memcpy(ts, b->BitAlloShort.nBand_s, 13 * sizeof(int)); memcpy(ts + 13, b->BitAlloShort.startBand_s, 14 * sizeof(int));
+    ts[27] = b->BitAlloShort.nsf[0];
+}
+
 /* stage functions of the reference, callable on their own (mp3low.h, pub/balow.h) */
 int ref_mbLogC(float x) { return mbLogC(x); }
 float ref_mbExp(int x) { return mbExp(x); }
