@@ -242,6 +242,11 @@ def last_error():
     return lib().hx_last_error().decode()
 
 
+def recon_delay():
+    """D: the samples a batch's decoded PCM (Batch.recon_buffer) trails its input by (hx_recon_delay)"""
+    return int(lib().hx_recon_delay())
+
+
 def crc_combine(a, b, n):
     """the MusicCRC of A ++ B from a = CRC(0, A), b = CRC(0, B) and n = len(B) (hx_xing_crc_combine)"""
     return int(lib().hx_xing_crc_combine(int(a), int(b), int(n)))
@@ -562,6 +567,26 @@ class Batch:
         frame to (include/hmp3_amd.h, "MusicCRC"; needs a frame_stats_buffer in force); None switches it off"""
         if lib().hx_batch_crc_buffer(self.h, d_crc_ptr) != 0:
             raise RuntimeError("hx_batch_crc_buffer failed: " + last_error())
+
+    def recon_buffer(self, d_recon_ptr):
+        """device buffer [n, nframes * 1152 * P] float32 that the calls that follow write their decoded PCM to
+        (include/hmp3_amd.h, "decoded PCM"): laid out like the f32 PCM rows; None switches it off"""
+        if lib().hx_batch_recon_buffer(self.h, d_recon_ptr) != 0:
+            raise RuntimeError("hx_batch_recon_buffer failed: " + last_error())
+
+    def encode_host_recon(self, pcm):
+        """encode_host of float32 PCM that also returns the call's decoded PCM -> (list of bytes per stream, float32
+        [n, nframes * 1152 * P]; what lies behind a stream's blocks of the call is zero)"""
+        pcm, nfr = _pcm_rows(pcm, self.n, _pitch(self.h))
+        if pcm.dtype != np.float32:
+            raise TypeError("encode_host_recon takes float32 PCM (hx_batch_encode_f32_host_recon)")
+        stride = self.out_stride(nfr)
+        out = np.zeros((self.n, stride), dtype=np.uint8)
+        nb = np.zeros(self.n, dtype=np.int32)
+        rec = np.zeros((self.n, nfr * 1152 * _pitch(self.h)), dtype=np.float32)
+        if lib().hx_batch_encode_f32_host_recon(self.h, pcm.ctypes.data, nfr, out.ctypes.data, stride, nb.ctypes.data, rec.ctypes.data) != 0:
+            raise RuntimeError("hx_batch_encode_f32_host_recon failed: " + last_error())
+        return [out[i, :nb[i]].tobytes() for i in range(self.n)], rec
 
     def frame_counts(self, counts):
         """per-stream frame counts of the calls that follow: a sequence of n ints (stream i takes the first counts[i] frames of

@@ -58,6 +58,7 @@ static int alloc_set(hx_batch *b, int k)
         return -1;
     w.pre_len = b->d_lens + 2 * k * S;
     w.carry_len = w.pre_len + S;
+    if (b->d_recon_state && dev_alloc(b, w.rec, sizeof(HxFrameDebug) * S * b->maxF)) return -1;     // (a set made after the first switch-on of the decoded PCM)
     const long long sgn_bytes = sizeof(unsigned) * S * NG * 2 * HX_SGN_WORDS;
     return (dev_alloc(b, b->sgn[k], sgn_bytes) || (k == 1 && dev_alloc(b, b->sgn[2], sgn_bytes))) ? -1 : 0;
 }
@@ -312,6 +313,65 @@ extern "C" int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc)
     return 0;
 }
 
+// Decoded PCM (include/hmp3_amd.h, "decoded PCM"; kernels: hx_recon.hip).  recon_refused: a menu with a class of another kind
+// than 0 - the frame record that gives the kernels their side information holds, for an MPEG-2 block, only the second frame's
+// ms (hx_alloc3.inc, place_frame: the (!LSF || part) write), and the first-generation allocator's intensity positions are not
+// in it at all.  recon_reserve: everything the output needs on the device, made once and kept; the carried state starts at zero.
+int recon_refused(const hx_batch *b)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    for (size_t c = 0; c < b->params.size(); c++)
+        if (b->cls_kind[c] != 0) {
+            const HxParams &p = b->params[c];
+            char msg[256];
+            snprintf(msg, sizeof msg, "decoded PCM covers MPEG-1 streams of the second-generation allocator only: class %d of the batch (%d Hz, mode %d%s) is %s",
+                     (int) c, p.samprate, p.h_mode, p.is_flag ? ", intensity stereo" : "", p.h_id ? "coded by the first-generation allocator" : "an MPEG-2 rate");
+            set_err("%s", msg);
+            return -1;
+        }
+    return 0;
+}
+int recon_reserve(hx_batch *b)
+{
+    if (recon_refused(b) != 0) return -1;
+    if (b->d_recon_state) return 0;
+    int dev0 = -1;
+    HIPCHK(hipGetDevice(&dev0));
+    HIPCHK(hipSetDevice(b->device));
+    const long long S = b->S, NG = 2LL * b->maxF;
+    HxReconTabs *t = new HxReconTabs;
+    HxGlobalTabs *g = new HxGlobalTabs;
+    hx_global_tabs(g);
+    hx_recon_tabs(t, g);
+    float *state = nullptr;
+    int rc = -1;
+    // (the state last: it is what says that everything is there; a call that fails half way leaves the rest to hx_batch_destroy)
+    if (drain(b) == 0 && dev_alloc(b, b->d_recon_tabs, sizeof(HxReconTabs)) == 0 && dev_alloc(b, b->d_recon_hyb, sizeof(float) * S * NG * 1152) == 0 &&
+        dev_alloc(b, b->d_recon_tails, sizeof(float) * S * HX_RECON_TAIL_FLOATS) == 0 &&
+        (b->walk[0].rec || dev_alloc(b, b->walk[0].rec, sizeof(HxFrameDebug) * S * b->maxF) == 0) &&
+        (!b->walk[1].ixq || b->walk[1].rec || dev_alloc(b, b->walk[1].rec, sizeof(HxFrameDebug) * S * b->maxF) == 0) &&
+        dev_alloc(b, state, sizeof(float) * S * HX_RECON_STATE_FLOATS) == 0 &&
+        hipMemcpy(b->d_recon_tabs, t, sizeof(HxReconTabs), hipMemcpyHostToDevice) == hipSuccess &&
+        hipMemset(state, 0, sizeof(float) * S * HX_RECON_STATE_FLOATS) == hipSuccess && hipDeviceSynchronize() == hipSuccess) {
+        b->d_recon_state = state;
+        rc = 0;
+    } else if (!b->poisoned && rc != 0) set_err("decoded PCM: the device buffers could not be made");
+    delete t;
+    delete g;
+    (void) hipSetDevice(dev0);
+    return rc;
+}
+extern "C" int hx_batch_recon_buffer(hx_batch *b, float *d_recon)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (!d_recon) { b->opt.recon = nullptr; return 0; }
+    if (((unsigned long long) d_recon & 3) != 0) { set_err("d_recon must be 4-byte aligned"); return -1; }
+    if (check_poisoned(b) != 0 || recon_reserve(b) != 0) return -1;
+    b->opt.recon = d_recon;
+    return 0;
+}
+extern "C" int hx_recon_delay(void) { return 2209; }
+
 // Per-stream frame counts of the calls that follow.  Only the host copy changes here: a call checks it against its nframes
 // (check_args) and uploads it for itself (encode_pass), so what is set later never reaches a call already made.
 // counts_reserve: everything that can fail - whether the batch takes counts at all, and (buffers) at the first use their
@@ -539,6 +599,33 @@ static int enqueue_crc(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
     return 0;
 }
 
+// The frame records a pass's stream walk writes (AllocArgs::dbg) and its decoded-PCM kernels read: the debug taps' array, or -
+// with the decoded PCM on - the buffer set's own, so that a deferred packing reads what its own walk wrote.  With both on, a
+// plain call's records go to the taps' array and serve both; a submit's go to its set's own array, so the "dbg" tap is not
+// written for a submit made with the decoded PCM on (include/hmp3_amd.h says so).
+static HxFrameDebug *frame_records(const hx_batch *b, const Call &c, int set, PassKind kind)
+{
+    if (b->debug && (kind == PASS_PLAIN || !c.opt.recon)) return b->d_dbg;
+    return c.opt.recon ? b->walk[set].rec : nullptr;
+}
+// the decoded PCM of one call on stream qp, behind its packing (hx_recon.hip): the hybrid over (stream, granule), the
+// synthesis over (stream, frame), then the carried state per stream
+static int enqueue_recon(hx_batch *b, const Call &c, int nframes, int set, int sset, PassKind kind, hipStream_t qp)
+{
+    if (!c.opt.recon) return 0;
+    const WalkSet &w = b->walk[set];
+    const int S = b->S, NG = 2 * nframes;
+    const dim3 grid((unsigned) ((long long) S * NG));
+    LAUNCH(k_recon_hybrid, grid, dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxGlobalTabs *) b->d_gt, (const HxReconTabs *) b->d_recon_tabs,
+           (const short *) w.ixq, (const unsigned *) b->sgn[sset], (const HxSegOut *) w.seg, (const HxFrameDebug *) frame_records(b, c, set, kind), b->d_recon_hyb,
+           b->d_recon_tails, (const float *) b->d_recon_state, NG, c.nfr);
+    LAUNCH(k_recon_synth, dim3((unsigned) ((long long) S * nframes)), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxReconTabs *) b->d_recon_tabs, (const float *) b->d_recon_hyb,
+           (const float *) b->d_recon_state, c.opt.recon, (long long) nframes * 1152 * b->nchan, NG, c.nfr);
+    LAUNCH(k_recon_carry, dim3(S), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const float *) b->d_recon_hyb, (const float *) b->d_recon_tails,
+           b->d_recon_state, NG, c.nfr);
+    return 0;
+}
+
 // the file ledger's update from one call on stream qp, behind its CRC kernel (hx_ledger.hip): one wave per stream.  A call
 // made before the batch's first hx_batch_ledger_begin has no ledger in its record
 static int enqueue_ledger(hx_batch *b, const Call &c, int nframes, hipStream_t qp)
@@ -582,7 +669,7 @@ static int flush_pack(hx_batch *b, long long gate_base)
     if (gate_base >= 0 && launch_gate(b, b->s_pack, (unsigned) gate_base) != 0) return -1;
     if (enqueue_pack(b, j.call, j.nframes, j.set, j.sset, b->s_pack) != 0 || enqueue_dense(b, j.call, j.nframes, b->s_pack) != 0 ||
         enqueue_crc(b, j.call, j.nframes, b->s_pack) != 0 || enqueue_ledger(b, j.call, j.nframes, b->s_pack) != 0 ||
-        enqueue_file(b, j.call, j.nframes, b->s_pack) != 0) return -1;
+        enqueue_file(b, j.call, j.nframes, b->s_pack) != 0 || enqueue_recon(b, j.call, j.nframes, j.set, j.sset, PASS_SUBMIT_DEVICE, b->s_pack) != 0) return -1;
     HIPCHK(hipEventRecord(b->ev_alloc[j.set], b->s_pack));
     HIPCHK(hipEventRecord(b->ev_sgn[j.sset], b->s_pack));
     return 0;
@@ -775,7 +862,7 @@ static int fill_alloc_args(hx_batch *b, const Pass &p, AllocArgs &a)
     const Call &c = p.call;
     a.st = b->d_st; a.prm = b->d_prm; a.gt = b->d_gt; a.xr = f.xr; a.etab = f.etab; a.thr = f.thr;
     a.msbase = f.msbase; a.bt = f.bt; a.btprev = f.btprev; a.out = c.out; a.out_bytes = c.out_bytes;
-    a.dbg = b->debug ? b->d_dbg : nullptr; a.out_stride = c.out_stride; a.NG = 2 * p.nframes; a.S = S; a.nfr = c.nfr; a.status = b->d_status; a.prof = b->d_prof;
+    a.dbg = frame_records(b, c, p.set, p.kind); a.out_stride = c.out_stride; a.NG = 2 * p.nframes; a.S = S; a.nfr = c.nfr; a.status = b->d_status; a.prof = b->d_prof;
     a.packet = c.opt.packet; a.packet_stride = c.opt.packet_stride; a.packet_bytes = c.opt.packet_bytes; a.frame_stats = c.opt.frame_stats;
     a.done_counter = b->d_done;
     a.strict_sums = b->strict_sums;
@@ -860,7 +947,8 @@ static int place_pack(hx_batch *b, const Pass &p)
     // the carried frame images that this call's k_pack_pre reads
     if (p.flushed_set >= 0) HIPCHK(hipStreamWaitEvent(qa, b->ev_alloc[p.flushed_set], 0));
     if (enqueue_pack(b, p.call, p.nframes, p.set, p.sset, qa) != 0 || enqueue_dense(b, p.call, p.nframes, qa) != 0 || enqueue_crc(b, p.call, p.nframes, qa) != 0 ||
-        enqueue_ledger(b, p.call, p.nframes, qa) != 0 || enqueue_file(b, p.call, p.nframes, qa) != 0) return -1;
+        enqueue_ledger(b, p.call, p.nframes, qa) != 0 || enqueue_file(b, p.call, p.nframes, qa) != 0 ||
+        enqueue_recon(b, p.call, p.nframes, p.set, p.sset, p.kind, qa) != 0) return -1;
     if (p.kind != PASS_PLAIN) { HIPCHK(hipEventRecord(b->ev_alloc[p.set], qa)); HIPCHK(hipEventRecord(b->ev_sgn[p.sset], qa)); }
     return 0;
 }
@@ -1104,7 +1192,7 @@ extern "C" float hx_batch_alloc_kernel_ms(hx_batch *b, int *ncalls)
 // With `stats` also the per-frame counters (see hx_batch_frame_stats_buffer); with hd the dense image instead of the rows.
 // files (encode_host_files): no host outputs at all, see host_call.
 int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd,
-                unsigned short *crc, bool files)
+                unsigned short *crc, bool files, float *recon)
 {
     if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes, !files) != 0) return -1;
     if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
@@ -1117,7 +1205,7 @@ int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long lon
         PcmIn up = in;
         up.p = b->d_in; up.shift = lo;
         return encode_pass(b, up, nframes, c, nullptr, PASS_PLAIN);
-    }, hd, crc, files);
+    }, hd, crc, files, recon);
 }
 
 // what every *_host_files call needs of the batch (hx_multi: for all blocks before one starts)
@@ -1156,6 +1244,15 @@ extern "C" int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int n
 {
     if (!stats || !crc) { set_err("null buffer"); return -1; }
     return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, stats, nullptr, crc);
+}
+
+// ... with the decoded PCM of the call (hx_batch_recon_buffer) in host memory, through staging: a buffer set on the batch is not written
+extern "C" int hx_batch_encode_f32_host_recon(hx_batch *b, const float *pcm, int nframes, unsigned char *out,
+                                              long long out_stride, int *out_bytes, float *recon)
+{
+    if (!recon) { set_err("null buffer"); return -1; }
+    if (recon_refused(b) != 0) return -1;
+    return encode_host(b, {pcm, true}, nframes, out, out_stride, out_bytes, nullptr, nullptr, nullptr, false, recon);
 }
 
 extern "C" int hx_batch_encode_f32_host(hx_batch *b, const float *pcm, int nframes, unsigned char *out,

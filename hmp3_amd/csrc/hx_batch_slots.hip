@@ -132,6 +132,7 @@ static int slot_op(hx_batch *b, SlotOp op, const int *idx, int n, void *d_blobs,
     a.S = b->S; a.src_par = b->src_par;
     a.magic = b->nsrc ? HX_STATE_MAGIC_SRC : HX_STATE_MAGIC; a.version = HX_STATE_VERSION;
     a.status = b->d_status;
+    a.recon_state = b->d_recon_state;
     a.blob_words = stride / 8;
     // words behind the header that the kernel walks (a reset leaves the converter's carried samples - call 0 of any plan
     // reads none - and its lane behind the two call counts writes the slot's plan and plan fingerprint)

@@ -60,6 +60,41 @@ void hx_host_default_control(HxControl *ec)
     ec->quick = -1; ec->test1 = -1; ec->short_block_threshold = 700;
 }
 
+// What a decoder's back half multiplies by (ISO 11172-3, 2.4.3.4), in double and rounded once.
+// The synthesis window is D[n] = 32 C[n] with C the analysis window of Table C.1.  g->anwin holds that table in the analysis
+// kernel's own layout - per-tap weights with the fold's signs, taps n % 64 != 16 at half scale, taps n % 64 == 48 absent
+// (their cosine term is zero) - so C is put back together here: magnitudes from anwin and the prototype's symmetry
+// h[n] = h[512 - n], the prototype's sign from its six zero crossings (main lobe 201 .. 311, side lobes alternating), and
+// C[n] = (-1)^(n >> 6) h[n].
+void hx_recon_tabs(HxReconTabs *t, const HxGlobalTabs *g)
+{
+    const double pi = 3.14159265358979323846;
+    static const double ci[8] = {-0.6, -0.535, -0.33, -0.185, -0.095, -0.041, -0.0142, -0.0037};
+    static const int cross[6] = {86, 144, 201, 312, 369, 427};      // first tap of every lobe but the outermost left one
+    memset(t, 0, sizeof(*t));
+    for (int k = 0; k < 4; k++) t->pow2q[k] = pow(2.0, 0.25 * k);
+    for (int i = 0; i < 36; i++) for (int k = 0; k < 18; k++) t->cos36[i][k] = (float) cos(pi / 72.0 * (2 * i + 19) * (2 * k + 1));
+    for (int i = 0; i < 12; i++) for (int k = 0; k < 6; k++) t->cos12[i][k] = (float) cos(pi / 24.0 * (2 * i + 7) * (2 * k + 1));
+    for (int i = 0; i < 36; i++) {
+        const double wl = sin(pi / 36.0 * (i + 0.5));
+        t->win[0][i] = (float) wl;
+        t->win[1][i] = (float) (i < 18 ? wl : i < 24 ? 1.0 : i < 30 ? sin(pi / 12.0 * (i - 18 + 0.5)) : 0.0);
+        t->win[2][i] = (float) (i < 12 ? sin(pi / 12.0 * (i + 0.5)) : 0.0);
+        t->win[3][i] = (float) (i < 6 ? 0.0 : i < 12 ? sin(pi / 12.0 * (i - 6 + 0.5)) : i < 18 ? 1.0 : wl);
+    }
+    for (int i = 0; i < 8; i++) { const double r = sqrt(1.0 + ci[i] * ci[i]); t->cs[i] = (float) (1.0 / r); t->ca[i] = (float) (ci[i] / r); }
+    for (int k = 0; k < 32; k++) for (int i = 0; i < 64; i++) t->synth[k][i] = (float) cos((16 + i) * (2 * k + 1) * pi / 64.0);
+    double h[512];
+    for (int n = 0; n < 512; n++) h[n] = fabs((double) g->anwin[n]) * ((n & 63) == 16 ? 1.0 : 2.0);
+    for (int n = 48; n < 512; n += 64) h[n] = h[512 - n];
+    for (int n = 0; n < 512; n++) {
+        int lobe = 0;
+        while (lobe < 6 && n >= cross[lobe]) lobe++;
+        const double sign = ((lobe & 1) ? 1.0 : -1.0) * (((n >> 6) & 1) ? -1.0 : 1.0);
+        t->dwin[n] = (float) (32768.0 * 32.0 * sign * h[n]);
+    }
+}
+
 void hx_global_tabs(HxGlobalTabs *g)
 {
     static const double q[32] = {

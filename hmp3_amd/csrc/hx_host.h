@@ -3,6 +3,8 @@
 #include "hx_types.h"
 void hx_host_default_control(HxControl *ec);
 void hx_global_tabs(HxGlobalTabs *g);
+// the decoded-PCM kernels' tables (hx_recon.hip), the synthesis window from g->anwin
+void hx_recon_tabs(HxReconTabs *t, const HxGlobalTabs *g);
 int hx_resolve(const HxControl *ec, HxParams *p);
 // after hx_resolve returned 0 on this thread: "" if the reference rejects the configuration too, else the limit of this
 // library's kernel layout that it ran into (hx_host.cpp band_runs)

@@ -512,3 +512,6 @@ __global__ __launch_bounds__(256) void k_dense_gather(const unsigned char *__res
 
 // ---- file images (hx_batch_file_images): k_file_append, k_file_begin, k_ledger_brief, a file of its own, built as part of this unit ----
 #include "hx_fileimg.hip"
+
+// ---- decoded PCM (hx_batch_recon_buffer): k_recon_hybrid, k_recon_synth, k_recon_carry, a file of its own, built as part of this unit ----
+#include "hx_recon.hip"

@@ -58,6 +58,11 @@ __global__ void k_dense_off(const int *out_bytes, long long *off, long long *off
 __global__ void k_dense_gather(const unsigned char *out, long long out_stride, const int *out_bytes, const long long *off, unsigned char *dense,
                                long long cap, int chunks);
 __global__ void k_crc(const unsigned char *out, long long out_stride, const int *out_bytes, const int *stats, int nframes, unsigned short *crc);
+__global__ void k_recon_hybrid(const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const HxReconTabs *rt, const short *ixq, const unsigned *sgn,
+                               const HxSegOut *seg, const HxFrameDebug *rec, float *hyb, float *tails, const float *state, int NG, const int *nfr);
+__global__ void k_recon_synth(const HxStream *st, const HxParams *prm, const HxReconTabs *rt, const float *hyb, const float *state, float *out,
+                              long long row, int NG, const int *nfr);
+__global__ void k_recon_carry(const HxStream *st, const HxParams *prm, const float *hyb, const float *tails, float *state, int NG, const int *nfr);
 __global__ void k_slot_reset(SlotArgs a);
 __global__ void k_slot_gather(SlotArgs a, uint2 *blobs);
 __global__ void k_slot_scatter(SlotArgs a, const uint2 *blobs);
@@ -114,6 +119,8 @@ struct WalkSet {
     HxFrameOut *frm;
     HxSlot *slots;
     int *pre_len, *carry_len;
+    HxFrameDebug *rec;                  // [S][maxF] the set's own frame records, which the decoded-PCM kernels read (made when
+                                        // hx_batch_recon_buffer is first switched on, null before)
 };
 
 // Where a call's dense image goes (hx_batch_dense_buffers): buf null = off.  off_copy: a second place for the offsets (the
@@ -121,8 +128,9 @@ struct WalkSet {
 struct DenseOut { unsigned char *buf = nullptr; long long cap = 0; long long *off = nullptr, *off_copy = nullptr; };
 // The optional outputs of a call, all in device memory, null = off: every frame as a packet (hx_batch_packet_buffers), the
 // per-frame counters (hx_batch_frame_stats_buffer), the dense image and the per-frame MusicCRC (hx_batch_crc_buffer; k_crc
-// reads the counters, so a call with crc needs frame_stats: check_opt).
-struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; unsigned short *crc = nullptr; };
+// reads the counters, so a call with crc needs frame_stats: check_opt) and the decoded PCM (hx_batch_recon_buffer).
+struct OptOut { unsigned char *packet = nullptr; long long packet_stride = 0; int *packet_bytes = nullptr, *frame_stats = nullptr; DenseOut dense; unsigned short *crc = nullptr;
+                float *recon = nullptr; };
 // The file images of a batch (hx_batch_file_images): img null = off.  [S] images of `pitch` bytes each, of which `cap` count;
 // fw [S][2]: per slot {image_bytes, the record has an image} (hx_fileimg.hip) - made at the first switch-on and kept
 struct FileImages { unsigned char *img = nullptr; long long pitch = 0, cap = 0; unsigned *fw = nullptr; };
@@ -254,6 +262,13 @@ struct hx_batch {
     long long *d_many_off = nullptr;
     int many_k = 0;
     bool debug = false;
+    // decoded PCM (hx_batch_recon_buffer), all made at the first switch-on (recon_reserve) and kept: the kernels' tables, the
+    // streams' carried state [S][HX_RECON_STATE_FLOATS] (outside HxStream and the checkpoint blob), the hybrid output of the
+    // call being reconstructed [S][2 maxF][2][576] and its last tails [S][2][576] - one of each: the decoded-PCM kernels of
+    // consecutive calls run one after the other, behind their packing, which is ordered the same way by the frames it carries
+    HxReconTabs *d_recon_tabs = nullptr;
+    float *d_recon_state = nullptr, *d_recon_hyb = nullptr, *d_recon_tails = nullptr;
+    float *d_reconh = nullptr; long long reconh_cap = 0;        // the *_host_recon calls' device staging
     // staging for the host-buffer entry points (host_call): the caller's input as it came (PCM, or a converting batch's
     // source bytes), the bitstream, its byte counts and the per-frame counters of the calls that return them
     void *d_in = nullptr; unsigned char *d_out = nullptr; int *d_outbytes = nullptr, *d_stats = nullptr;
@@ -476,7 +491,10 @@ HX_LOCAL int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, v
 // the host-buffer PCM calls; hd: the *_host_dense calls' image, its capacity and offsets in host memory (see host_call)
 struct HostDense { unsigned char *dense; long long cap; long long *off; long long bound; };
 HX_LOCAL int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, int *stats, const HostDense *hd = nullptr,
-                         unsigned short *crc = nullptr, bool files = false);
+                         unsigned short *crc = nullptr, bool files = false, float *recon = nullptr);
+// decoded PCM: what hx_batch_recon_buffer refuses about the batch, and everything it allocates at the first switch-on
+HX_LOCAL int recon_refused(const hx_batch *b);
+HX_LOCAL int recon_reserve(hx_batch *b);
 // the *_host_files calls (file images): what they need of the batch, and the PCM form
 HX_LOCAL int check_files(const hx_batch *b);
 HX_LOCAL int encode_host_files(hx_batch *b, PcmIn in, int nframes);
@@ -567,7 +585,7 @@ static inline int rows_to_host(const hx_batch *b, unsigned char *out, const unsi
 template <class Encode>
 static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain_first, int nframes, unsigned char *out,
                      long long out_stride, int *out_bytes, int *stats, Encode encode, const HostDense *hd = nullptr, unsigned short *crc = nullptr,
-                     bool files = false)
+                     bool files = false, float *recon = nullptr)
 {
     if (!files) {   // (the optional outputs the call will take, checked before anything is allocated or copied; files: it takes both)
         OptOut o = b->opt;
@@ -580,6 +598,9 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     const long long cbytes = (crc || files) ? (long long) sizeof(unsigned short) * b->S * nframes : 0;
     if (dev_grow(b, b->d_in, b->in_cap, in_bytes) || dev_grow(b, b->d_out, b->out_cap, obytes) || dev_grow(b, b->d_stats, b->stats_cap, sbytes) ||
         dev_grow(b, b->d_crc, b->crc_cap, cbytes)) return -1;
+    // (the *_host_recon calls: the decoded PCM goes to staging laid out like the input rows, and comes back below)
+    const long long rrow = (long long) nframes * 1152 * b->nchan;
+    if (recon && (recon_reserve(b) != 0 || dev_grow(b, b->d_reconh, b->reconh_cap, (long long) sizeof(float) * b->S * rrow))) return -1;
     if (hd && (dev_grow(b, b->d_dense, b->dense_cap, std::max(16LL, std::min(hd->cap, hd->bound))) ||
                (!b->d_dense_off && dev_alloc(b, b->d_dense_off, (long long) sizeof(long long) * (b->S + 1))))) return -1;
     if (drain_first && drain(b) != 0) return -1;
@@ -588,6 +609,7 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     if (stats || files) c.opt.frame_stats = b->d_stats;
     if (crc || files) c.opt.crc = b->d_crc;
     if (hd) c.opt.dense = DenseOut{b->d_dense, hd->cap, b->d_dense_off, nullptr};
+    if (recon) c.opt.recon = b->d_reconh;
     if (encode(c) != 0 || drain(b) != 0) return -1;
     if (files) {
         int v = -1;
@@ -603,5 +625,17 @@ static int host_call(hx_batch *b, const void *in, long long in_bytes, bool drain
     } else if (rows_to_host(b, out, b->d_out, out_stride, nullptr) != 0) return -1;
     if (stats) HIPCHK(hipMemcpy(stats, b->d_stats, (size_t) sbytes, hipMemcpyDeviceToHost));
     if (crc) HIPCHK(hipMemcpy(crc, b->d_crc, (size_t) cbytes, hipMemcpyDeviceToHost));
+    // each stream's blocks of the call and no more: what lies behind them in the caller's row is not written.  One copy
+    // when every stream fills its row (no counts, every stream of P channels), else one copy to the host and a trim there
+    if (recon) {
+        bool full = b->nfr.empty();
+        for (int s = 0; full && s < b->S; s++) full = b->params[b->cls_of[s]].nchan == b->nchan;
+        std::vector<float> tmp(full ? 0 : (size_t) b->S * rrow);
+        HIPCHK(hipMemcpy(full ? recon : tmp.data(), b->d_reconh, sizeof(float) * (size_t) b->S * rrow, hipMemcpyDeviceToHost));
+        for (int s = 0; !full && s < b->S; s++) {
+            const size_t n = (size_t) (b->nfr.empty() ? nframes : b->nfr[s]) * 1152 * b->params[b->cls_of[s]].nchan;
+            memcpy(recon + (size_t) s * rrow, tmp.data() + (size_t) s * rrow, sizeof(float) * n);
+        }
+    }
     return 0;
 }

@@ -37,7 +37,8 @@ __device__ __forceinline__ uint2 *slot_word(const SlotArgs &a, int slot, int w)
 
 // Every listed slot becomes a new stream of its entry's class: the class's initial HxStream, a zero subband carry and
 // (converting batches) zero call counts in both copies, the entry's plan in the slot's word of src_cls and that plan's
-// fingerprint in its word of src_fp - the same values as before when the slot keeps its configuration.  The converter's
+// fingerprint in its word of src_fp - the same values as before when the slot keeps its configuration - and, where the batch
+// has one, a zero decoded-PCM state.  The converter's
 // carried samples stay: call 0 of any plan reads none (hx_src.hip: qstart(0) = u(0) = 0).  Only slots 0..2 of the two subband rows are zeroed: k_polyphase writes slots
 // 3 .. NG + 2 of a call before k_spec (slots 0 .. NG) and k_msscan (slots NG .. NG + 2) read them, and its own read is of
 // slot 2.
@@ -59,6 +60,9 @@ __global__ __launch_bounds__(256) void k_slot_reset(SlotArgs a)
         else if (a.src_calls && w < HX_SLOT_SRC_WORD + 2) a.src_calls[(long long) (w - HX_SLOT_SRC_WORD) * a.S + en.slot] = 0;
         else if (a.src_calls && w == HX_SLOT_SRC_WORD + 2) { a.src_cls[en.slot] = en.plan; a.src_fp[en.slot] = a.plan_fp[en.plan]; }
     }
+    // the decoded PCM's carried state (hx_batch_recon_buffer): a new stream's decoder starts from zero; the entry's workgroups share the floats
+    if (a.recon_state)
+        for (int i = c * 256 + (int) threadIdx.x; i < HX_RECON_STATE_FLOATS; i += a.chunks * 256) a.recon_state[(long long) en.slot * HX_RECON_STATE_FLOATS + i] = 0.0f;
 }
 
 // Blob e of blobs [n][blob_words] = the stream-state blob of entry e's slot (layout: hx_types.h), and zeros from the blob's
@@ -91,7 +95,7 @@ __global__ __launch_bounds__(256) void k_slot_gather(SlotArgs a, uint2 *__restri
 // The reverse.  Every workgroup of an entry checks the blob's header (and, converting batches, the plan fingerprint)
 // against what the slot takes; on a mismatch none of them writes anything and status bit 32 is set.  HxStream goes in with
 // cls replaced by the entry's (the class index is the receiving batch's), the carry into slots 0..2 of both channels, the
-// converter's call count into both copies.
+// converter's call count into both copies; where the batch has a decoded-PCM state, the slot's is zeroed.
 __global__ __launch_bounds__(256) void k_slot_scatter(SlotArgs a, const uint2 *__restrict__ blobs)
 {
     const int e = blockIdx.x / a.chunks, c = blockIdx.x - e * a.chunks;
@@ -122,4 +126,8 @@ __global__ __launch_bounds__(256) void k_slot_scatter(SlotArgs a, const uint2 *_
             a.src_calls[(long long) a.S + en.slot] = (long long) slot_join(v[k]);
         }
     }
+    // the decoded PCM's carried state is not part of a blob: a restored stream's decoder starts from zero, whatever the slot
+    // ran before (an accepted blob only; the entry's workgroups share the floats)
+    if (a.recon_state)
+        for (int i = c * 256 + (int) threadIdx.x; i < HX_RECON_STATE_FLOATS; i += a.chunks * 256) a.recon_state[(long long) en.slot * HX_RECON_STATE_FLOATS + i] = 0.0f;
 }

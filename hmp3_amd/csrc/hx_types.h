@@ -98,6 +98,23 @@ struct HxGlobalTabs {
     unsigned char quada_code[16], quada_len[16];
 };
 
+// Tables of the decoded-PCM kernels (hx_recon.hip; hx_host.cpp hx_recon_tabs builds them in double from their closed forms
+// and from anwin): what an ISO 11172-3 decoder's back half multiplies by.
+struct HxReconTabs {
+    double pow2q[4];            // 2^(k / 4): the fractional part of a requantisation exponent
+    float cos36[36][18];        // cos(pi / 72 (2 i + 19) (2 k + 1)): the 36-point IMDCT, output i, line k
+    float cos12[12][6];         // cos(pi / 24 (2 i + 7) (2 k + 1)): the 12-point IMDCT
+    float win[4][36];           // the windows of block types 0 .. 3 (type 2: 12 taps)
+    float cs[8], ca[8];         // alias reduction butterflies
+    float synth[32][64];        // [k][i] cos((16 + i) (2 k + 1) pi / 64): the synthesis bank's matrixing, transposed
+    float dwin[512];            // the synthesis window D[n] = 32 C[n], times 32768 (the output is at int16 scale)
+};
+// Carried state of a stream's decoded PCM, floats: the previous granule's IMDCT tails [2][32][18], then the last 15 time
+// slots of hybrid output [2][15][32], oldest first (hx_batch::d_recon_state, [S] of these)
+#define HX_RECON_TAIL_FLOATS (2 * 576)
+#define HX_RECON_HIST_SLOTS 15
+#define HX_RECON_STATE_FLOATS (HX_RECON_TAIL_FLOATS + 2 * HX_RECON_HIST_SLOTS * 32)
+
 // Side information of one granule/channel (pub/l3e.h:72-96)
 struct HxGr {
     int part2_3_length, big_values, global_gain, scalefac_compress;
@@ -448,4 +465,6 @@ struct SlotArgs {
     int *status;                // bit 32: k_slot_scatter refused a blob
     int chunks;                 // workgroups per entry
     long long blob_words;       // blob_stride / 8
+    float *recon_state;         // [S][HX_RECON_STATE_FLOATS] the decoded PCM's carried state, which k_slot_reset zeroes for the
+                                // listed slots, or null: the batch never had hx_batch_recon_buffer switched on
 };

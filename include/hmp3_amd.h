@@ -383,6 +383,52 @@ int hx_batch_crc_buffer(hx_batch *b, unsigned short *d_crc);
    crc[nstreams][nframes]; both are required */
 int hx_batch_encode_f32_host_crc(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride,
                                  int *out_bytes, int *stats, unsigned short *crc);
+/* ---- decoded PCM: a call's frames reconstructed on the GPU (no reference equivalent: the reference has no decoder) ----
+   For every stream and every 1152-sample input block of a call, the 1152 samples per channel that an ISO 11172-3 decoder
+   outputs for the frame the encoder coded from that block: float at int16 scale, neither clipped nor rounded.  It is
+   computed from what the stream walk hands to the packing (quantised lines, signs, scalefactors, side information), not
+   from the bytes; the decoder's steps are requantisation, M/S, reorder of short blocks, alias reduction, IMDCT with the
+   block-type windows, overlap-add, frequency inversion and polyphase synthesis.
+   Layout: d_recon [nstreams][nframes * 1152 * P] float, P = hx_batch_pcm_channels(b) - exactly the layout of the f32 PCM
+   rows (a stream of P channels interleaved, a mono stream of a P = 2 batch contiguous at the start of its row), so a recon
+   row can be fed straight back as input.  d_recon must be 4-byte aligned (else -1).  NULL = off: nothing is launched for
+   it, and before the first switch-on nothing is allocated for it.
+   Meaning: call c of a stream codes frame c of its bitstream, and block f of the row is the decoder's output for that
+   frame given the decoder's state after the stream's earlier frames: concatenated over calls, a stream's recon is what a
+   decoder outputs for its concatenated bitstream.  It trails the input by D = hx_recon_delay() = 2209 samples: the 1680
+   of the encoder that the file tag carries (1152 of look-ahead and the analysis side of the filter banks) and the
+   decoder's 529.  Recon is tied to what a call codes, not to what it emits: the bit reservoir may hold a frame's bytes
+   back for several calls, its recon is there at once.
+   State: per stream the previous granule's IMDCT tails and the last 15 time slots of hybrid output per channel, about
+   8 KB, in an array of the batch made at the first switch-on - outside the stream state: hx_batch_get / set_stream_state
+   blobs, their size and HX_STATE_VERSION are unchanged.  A new batch starts from zero state; hx_batch_reset_streams,
+   hx_batch_assign_streams and every hx_batch_set_stream_state* call (an accepted blob) zero it for the listed slots, in
+   stream order.  The state advances only with calls that have a
+   recon buffer in force.
+   Determinism: a sample depends on its stream's own records only, every value is formed in one fixed operation order and
+   the state is carried as the floats themselves, so recon is bit-identical however the frames are split over calls,
+   whichever slot and batch size the stream runs in, on either build of the stream walk, on plain calls and submits.
+   Per-stream frame counts: blocks f < n are written, blocks f >= n are not touched; n = 0 leaves the state unchanged.
+   Submits: the kernels travel with the submit's deferred packing; a submit writes the buffer in force when it was made,
+   the buffer is valid after the hx_batch_wait behind it, and consecutive submits take two buffers in turn.
+   Honoured by every encode and submit entry point of a plain batch and by hx_batch_encode_src_device and its counts
+   form.  The rows, out_bytes, packets, counters, CRCs, dense image, ledger and file images are byte for byte what they
+   are without it.  While it is on, the stream walk writes a frame record per frame (one lane, cold code): DESIGN.md has
+   the cost.  With the debug taps on as well (hx_batch_debug_enable), a plain call's frame records serve both; a submit's
+   go to an array of its own buffer set, so the "dbg" tap is not written for a submit made with recon on.
+   Refused by the setter (-1, hx_last_error): a null batch, a misaligned pointer, and a batch whose menu holds a class
+   that is not MPEG-1 on the second-generation allocator (an MPEG-2 rate, intensity stereo, dual channel): the message
+   names the class.  The stream walk's frame record lacks what those need (the first MPEG-2 frame's ms, intensity positions).
+   Not covered: those kinds; recon state in the checkpoint blob - a restored stream continues from ZERO recon state, so
+   the first two granules after hx_batch_set_stream_state carry a transient; hx_multi_*; the hx_enc_* encoder; the
+   command line. */
+int hx_batch_recon_buffer(hx_batch *b, float *d_recon);
+/* fp32 host call that returns the call's recon to a host array recon[nstreams][nframes * 1152 * P] (each stream's blocks
+   of the call and nothing behind them); a recon buffer set on the batch is not written by it */
+int hx_batch_encode_f32_host_recon(hx_batch *b, const float *pcm, int nframes, unsigned char *out, long long out_stride,
+                                   int *out_bytes, float *recon);
+/* D: the samples recon trails the input by, a constant of this encoder / decoder pair */
+int hx_recon_delay(void);
 /* ---- per-stream frame counts: each stream of a call advances on its own (no reference equivalent; per stream it is the
    reference called nfr[i] times) ----
    nfr: HOST array [nstreams], copied by this function; NULL = every stream takes the call's nframes (the default).
