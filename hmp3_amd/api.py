@@ -213,6 +213,27 @@ def debug_count(ec, unit, mode, hdr, ix, ixmax, x34=None, gsf=None, device=0):
     return rc, ix, ixmax, out
 
 
+def debug_recon(ecs, cls, NG, nfr, ixq, sgn, seg, rec, state, hyb, out, device=0):
+    """hx_debug_recon: the decoded-PCM kernels on records of the caller's (the layouts: include/hmp3_amd.h).  ecs: the
+    controls of the classes in play, cls [S] each stream's class, nfr [S] or None; seg and rec are arrays of the records'
+    bytes.  -> (rc, state, hyb, out): copies of state [S][2112], hyb [S][NG][2][576] and out [S][row] as the kernels left
+    them; rc = -1: refused (last_error() says why) and nothing was launched"""
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    S = cls.size
+    nfr = None if nfr is None else np.ascontiguousarray(nfr, dtype=np.int32)
+    ixq = np.ascontiguousarray(ixq, dtype=np.int16)
+    sgn = np.ascontiguousarray(sgn, dtype=np.uint32)
+    seg, rec = np.ascontiguousarray(seg), np.ascontiguousarray(rec)
+    state, hyb, out = (np.array(a, dtype=np.float32, order="C") for a in (state, hyb, out))
+    if ixq.size != S * NG * 1152 or sgn.size * 576 != ixq.size * (sgn.shape[-1] if sgn.ndim else 1) or hyb.size != ixq.size or \
+            out.ndim != 2 or out.shape[0] != S or state.shape[0] != S or (nfr is not None and nfr.size != S):
+        raise ValueError("arrays of %d streams x %d granules expected" % (S, NG))
+    arr = (EControl * len(ecs))(*ecs)
+    rc = lib().hx_debug_recon(int(device), arr, len(ecs), cls.ctypes.data, S, int(NG), None if nfr is None else nfr.ctypes.data, ixq.ctypes.data,
+                              sgn.ctypes.data, seg.ctypes.data, rec.ctypes.data, state.ctypes.data, hyb.ctypes.data, out.ctypes.data, out.shape[1])
+    return rc, state, hyb, out
+
+
 def device_numa_node(device):
     return int(lib().hx_device_numa_node(int(device)))
 

@@ -1,6 +1,7 @@
 // hx_batch.hip - the batch of the C ABI (include/hmp3_amd.h) and its launch sequence.
 // Owns the device buffers of a batch (subband carry, spectra, psy data, stream state), groups streams into
 // configuration classes and launches K1..K8: create / destroy, the pass, submits, host-buffer calls, reads.
+#include <cmath>
 #include <string>
 #include "hx_rt.h"
 
@@ -608,22 +609,26 @@ static HxFrameDebug *frame_records(const hx_batch *b, const Call &c, int set, Pa
     if (b->debug && (kind == PASS_PLAIN || !c.opt.recon)) return b->d_dbg;
     return c.opt.recon ? b->walk[set].rec : nullptr;
 }
-// the decoded PCM of one call on stream qp, behind its packing (hx_recon.hip): the hybrid over (stream, granule), the
-// synthesis over (stream, frame), then the carried state per stream
+// The decoded PCM of S streams x NG granule positions on stream qp (hx_recon.hip): the hybrid over (stream, granule), the
+// synthesis over (stream, frame), then the carried state per stream.  The one launch expression: a batch's call and hx_debug_recon.
+static int launch_recon(hipStream_t qp, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt, const HxReconTabs *rt, const short *ixq,
+                        const unsigned *sgn, const HxSegOut *seg, const HxFrameDebug *rec, float *hyb, float *tails, float *state, float *out,
+                        long long row, int S, int NG, const int *nfr)
+{
+    const dim3 grid((unsigned) ((long long) S * NG));
+    LAUNCH(k_recon_hybrid, grid, dim3(256), qp, st, prm, gt, rt, ixq, sgn, seg, rec, hyb, tails, (const float *) state, NG, nfr);
+    LAUNCH(k_recon_synth, dim3((unsigned) ((long long) S * (NG / 2))), dim3(256), qp, st, prm, rt, (const float *) hyb, (const float *) state, out, row, NG, nfr);
+    LAUNCH(k_recon_carry, dim3(S), dim3(256), qp, st, prm, (const float *) hyb, (const float *) tails, state, NG, nfr);
+    return 0;
+}
+// the decoded PCM of one call on stream qp, behind its packing
 static int enqueue_recon(hx_batch *b, const Call &c, int nframes, int set, int sset, PassKind kind, hipStream_t qp)
 {
     if (!c.opt.recon) return 0;
     const WalkSet &w = b->walk[set];
-    const int S = b->S, NG = 2 * nframes;
-    const dim3 grid((unsigned) ((long long) S * NG));
-    LAUNCH(k_recon_hybrid, grid, dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxGlobalTabs *) b->d_gt, (const HxReconTabs *) b->d_recon_tabs,
-           (const short *) w.ixq, (const unsigned *) b->sgn[sset], (const HxSegOut *) w.seg, (const HxFrameDebug *) frame_records(b, c, set, kind), b->d_recon_hyb,
-           b->d_recon_tails, (const float *) b->d_recon_state, NG, c.nfr);
-    LAUNCH(k_recon_synth, dim3((unsigned) ((long long) S * nframes)), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxReconTabs *) b->d_recon_tabs, (const float *) b->d_recon_hyb,
-           (const float *) b->d_recon_state, c.opt.recon, (long long) nframes * 1152 * b->nchan, NG, c.nfr);
-    LAUNCH(k_recon_carry, dim3(S), dim3(256), qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const float *) b->d_recon_hyb, (const float *) b->d_recon_tails,
-           b->d_recon_state, NG, c.nfr);
-    return 0;
+    return launch_recon(qp, (const HxStream *) b->d_st, (const HxParams *) b->d_prm, (const HxGlobalTabs *) b->d_gt, (const HxReconTabs *) b->d_recon_tabs,
+                        (const short *) w.ixq, (const unsigned *) b->sgn[sset], (const HxSegOut *) w.seg, (const HxFrameDebug *) frame_records(b, c, set, kind),
+                        b->d_recon_hyb, b->d_recon_tails, b->d_recon_state, c.opt.recon, (long long) nframes * 1152 * b->nchan, b->S, 2 * nframes, c.nfr);
 }
 
 // the file ledger's update from one call on stream qp, behind its CRC kernel (hx_ledger.hip): one wave per stream.  A call
@@ -1577,6 +1582,146 @@ extern "C" int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const
     HIPCHK(hipMemcpy(rows, d_rows, (size_t) S * out_stride, hipMemcpyDeviceToHost));
     if (packet && packet_bytes) HIPCHK(hipMemcpy(packet, d_packet, (size_t) packet_bytes, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(status, d_status, sizeof(int), hipMemcpyDeviceToHost));
+    return 0;
+}
+
+
+// ---- hx_debug_recon: the decoded-PCM kernels on records of the caller's (tests only; include/hmp3_amd.h) ----
+// What the three kernels read of a call - lines, signs, segment records, frame records, the carried state - comes from the
+// caller instead of the stream walk; the kernels and their launch are the batch's (launch_recon), the tables hx_recon_tabs'.
+// Every record a kernel will read is checked on the host first: one the kind-0 stream walk cannot hand over is refused with
+// a message before anything is launched.  What no kernel reads - records behind a stream's count, a mono stream's second
+// channel, lines from the coded range on - is not looked at.
+
+static int recon_refuse(long long s, int g, int ch, const char *what)
+{
+    char msg[256];
+    if (g < 0) snprintf(msg, sizeof msg, "hx_debug_recon: stream %lld: %s", s, what);
+    else if (ch < 0) snprintf(msg, sizeof msg, "hx_debug_recon: stream %lld granule %d: %s", s, g, what);
+    else snprintf(msg, sizeof msg, "hx_debug_recon: stream %lld granule %d channel %d: %s", s, g, ch, what);
+    set_err("%s", msg);
+    return -1;
+}
+
+static int check_recon_records(const std::vector<HxParams> &prm, const int *cls, int S, int NG, const int *nfr, const short *ixq,
+                               const HxSegOut *seg, const HxFrameDebug *rec, const float *state, long long row)
+{
+    // (previous, this) block types a stream can have: long 0 -> 0 / 1, start 1 -> 2, short 2 -> 2 / 3, stop 3 -> 0 / 1
+    static const unsigned char legal[4][4] = {{1, 1, 0, 0}, {0, 0, 1, 0}, {0, 0, 1, 1}, {1, 1, 0, 0}};
+    for (long long s = 0; s < S; s++) {
+        const int nchan = prm[cls[s]].nchan, nf = nfr ? nfr[s] : NG / 2;
+        if (nf == 0) continue;
+        if ((long long) nf * 1152 * nchan > row) return recon_refuse(s, -1, -1, "row is shorter than the stream's blocks");
+        const float *st = state + s * HX_RECON_STATE_FLOATS;
+        for (int ch = 0; ch < nchan; ch++) {
+            for (int i = 0; i < 576; i++) if (!std::isfinite(st[ch * 576 + i])) return recon_refuse(s, -1, -1, "state: a tail that is not finite");
+            for (int i = 0; i < HX_RECON_HIST_SLOTS * 32; i++)
+                if (!std::isfinite(st[HX_RECON_TAIL_FLOATS + ch * HX_RECON_HIST_SLOTS * 32 + i])) return recon_refuse(s, -1, -1, "state: a carried slot that is not finite");
+        }
+        int bt_prev = -1;
+        for (int g = 0; g < 2 * nf; g++) {
+            const HxFrameDebug &fr = rec[s * (NG / 2) + (g >> 1)];
+            if (fr.ms != 0 && fr.ms != 1) return recon_refuse(s, g, -1, "ms is neither 0 nor 1");
+            const int bt = fr.gr[g & 1][0].block_type;
+            for (int ch = 0; ch < nchan; ch++) {
+                const HxGr &q = fr.gr[g & 1][ch];
+                const long long unit = (s * NG + g) * 2 + ch;
+                if (q.block_type < 0 || q.block_type > 3) return recon_refuse(s, g, ch, "block_type outside 0 .. 3");
+                if (q.block_type != bt) return recon_refuse(s, g, ch, "block_type differs between the channels");
+                if (q.mixed_block_flag != 0) return recon_refuse(s, g, ch, "mixed_block_flag set");
+                if (q.global_gain < 0 || q.global_gain > 255) return recon_refuse(s, g, ch, "global_gain outside 0 .. 255");
+                for (int w = 0; w < 3; w++) if (q.subblock_gain[w] < 0 || q.subblock_gain[w] > 7) return recon_refuse(s, g, ch, "subblock_gain outside 0 .. 7");
+                if (q.big_values < 0 || q.big_values > 288) return recon_refuse(s, g, ch, "big_values outside 0 .. 288");
+                if (q.aux_nquads < 0) return recon_refuse(s, g, ch, "aux_nquads negative");
+                if (bt == 2) {
+                    for (int j = 0; j < 36; j++) {
+                        const int fld = seg[unit].sf[j], v = fld & 255;
+                        if (fld & 0x8000) return recon_refuse(s, g, ch, "a negative short scalefactor field");
+                        if (v > (j < 18 ? 15 : 7)) return recon_refuse(s, g, ch, "a short scalefactor field above 15 (bands 0 .. 5) or 7 (bands 6 .. 11)");
+                    }
+                } else {
+                    for (int b = 0; b < 22; b++) {
+                        const int v = fr.sf[g & 1][ch][b];
+                        if (v < 0 || v > (b < 11 ? 15 : b < 21 ? 7 : 0)) return recon_refuse(s, g, ch, "sf: a long scalefactor outside 0 .. 15 (bands 0 .. 10), 0 .. 7 (bands 11 .. 20) or 0 (band 21)");
+                    }
+                }
+                const int ncoded = q.aux_not_null ? std::min(576, 2 * q.big_values + 4 * q.aux_nquads) : 0;
+                for (int j = 0; j < ncoded; j++) {
+                    const int mag = ixq[unit * 576 + j];
+                    if (mag < 0 || mag > 8206) return recon_refuse(s, g, ch, "ixq: a magnitude outside 0 .. 8206 within the coded range");
+                }
+            }
+            if (bt_prev >= 0 && !legal[bt_prev][bt]) return recon_refuse(s, g, -1, "block_type cannot follow the granule before it");
+            bt_prev = bt;
+        }
+    }
+    return 0;
+}
+
+extern "C" int hx_debug_recon(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, const int *nfr,
+                              const short *ixq, const unsigned *sgn, const void *seg, const void *rec, float *state, float *hyb,
+                              float *out, long long row)
+{
+    if (!ec || !cls || !ixq || !sgn || !seg || !rec || !state || !hyb || !out) { set_err("null buffer"); return -1; }
+    if (ncls <= 0 || S <= 0 || NG <= 0 || (NG & 1) || (long long) S * NG > (1LL << 16) || row <= 0 || row > (1LL << 26)) { set_err("bad arguments"); return -1; }
+    std::vector<HxParams> prm(ncls);
+    for (int k = 0; k < ncls; k++) {
+        if (!hx_resolve((const HxControl *) (ec + k), &prm[k])) { set_err("configuration rejected"); return -1; }
+        const HxParams &p = prm[k];
+        if (p.alloc1 || !p.h_id) {     // (recon_refused's rule and words)
+            char msg[256];
+            snprintf(msg, sizeof msg, "decoded PCM covers MPEG-1 streams of the second-generation allocator only: class %d (%d Hz, mode %d%s) is %s",
+                     k, p.samprate, p.h_mode, p.is_flag ? ", intensity stereo" : "", p.h_id ? "coded by the first-generation allocator" : "an MPEG-2 rate");
+            set_err("%s", msg);
+            return -1;
+        }
+    }
+    for (int s = 0; s < S; s++) if (cls[s] < 0 || cls[s] >= ncls) { set_err("a stream's class is out of range"); return -1; }
+    if (check_counts_arg(nfr, S, NG / 2, 0) != 0) return -1;
+    if (check_recon_records(prm, cls, S, NG, nfr, ixq, (const HxSegOut *) seg, (const HxFrameDebug *) rec, state, row) != 0) return -1;
+    std::vector<HxGlobalTabs> gt_host(1);
+    std::vector<HxReconTabs> rt_host(1);
+    hx_global_tabs(&gt_host[0]);
+    hx_recon_tabs(&rt_host[0], &gt_host[0]);
+    std::vector<HxStream> st(S);
+    for (int s = 0; s < S; s++) hx_stream_reset(&prm[cls[s]], cls[s], &st[s]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return -1; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return -1; }
+    HIPCHK(hipSetDevice(device));
+    struct Dev {        // device copies: everything is released on every way out
+        std::vector<void *> mem;
+        ~Dev() { for (void *p : mem) (void) hipFree(p); }
+        void *up(const void *src, size_t bytes)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes) != hipSuccess) return nullptr;
+            mem.push_back(q);
+            if ((src ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) : hipMemset(q, 0, bytes)) != hipSuccess) return nullptr;
+            return q;
+        }
+    } dev;
+    const size_t units = (size_t) S * NG * 2;
+    void *d_st = dev.up(st.data(), sizeof(HxStream) * S), *d_prm = dev.up(prm.data(), sizeof(HxParams) * ncls), *d_gt = dev.up(&gt_host[0], sizeof(HxGlobalTabs));
+    void *d_rt = dev.up(&rt_host[0], sizeof(HxReconTabs)), *d_ixq = dev.up(ixq, sizeof(short) * 576 * units), *d_sgn = dev.up(sgn, sizeof(unsigned) * HX_SGN_WORDS * units);
+    void *d_seg = dev.up(seg, sizeof(HxSegOut) * units), *d_rec = dev.up(rec, sizeof(HxFrameDebug) * (size_t) S * (NG / 2));
+    void *d_state = dev.up(state, sizeof(float) * HX_RECON_STATE_FLOATS * (size_t) S), *d_hyb = dev.up(hyb, sizeof(float) * 576 * units);
+    void *d_tails = dev.up(nullptr, sizeof(float) * HX_RECON_TAIL_FLOATS * (size_t) S), *d_out = dev.up(out, sizeof(float) * (size_t) S * row);
+    void *d_nfr = nfr ? dev.up(nfr, sizeof(int) * S) : nullptr;
+    if (!d_st || !d_prm || !d_gt || !d_rt || !d_ixq || !d_sgn || !d_seg || !d_rec || !d_state || !d_hyb || !d_tails || !d_out || (nfr && !d_nfr)) {
+        set_err("hipMalloc or upload failed");
+        return -1;
+    }
+    if (launch_recon(nullptr, (const HxStream *) d_st, (const HxParams *) d_prm, (const HxGlobalTabs *) d_gt, (const HxReconTabs *) d_rt, (const short *) d_ixq,
+                     (const unsigned *) d_sgn, (const HxSegOut *) d_seg, (const HxFrameDebug *) d_rec, (float *) d_hyb, (float *) d_tails, (float *) d_state,
+                     (float *) d_out, row, S, NG, (const int *) d_nfr) != 0) return -1;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(state, d_state, sizeof(float) * HX_RECON_STATE_FLOATS * (size_t) S, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(hyb, d_hyb, sizeof(float) * 576 * units, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, d_out, sizeof(float) * (size_t) S * row, hipMemcpyDeviceToHost));
     return 0;
 }
 

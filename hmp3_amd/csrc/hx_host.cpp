@@ -7,6 +7,7 @@
 #include <math.h>
 #include <string.h>
 #include <stdlib.h>
+#include <stddef.h>
 #include <string>
 #include "../../include/hmp3_amd.h"
 #include "hx_types.h"
@@ -809,8 +810,10 @@ extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *nam
 {
     static HxParams p;
     static HxGlobalTabs g;
+    static HxReconTabs r;
     if (!hx_resolve((const HxControl *) ec, &p)) return 0;
     hx_global_tabs(&g);
+    hx_recon_tabs(&r, &g);
     std::string k(name);
     const void *src = nullptr;
     long long n = 0;
@@ -830,11 +833,20 @@ extern "C" long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *nam
     TAB("nchan", p.nchan) TAB("side_bytes", p.side_bytes) TAB("h_id", p.h_id)
     TAB("nsf2", p.nsf2) TAB("nsf3", p.nsf3) TAB("nbmax", p.nbmax) TAB("nbmax2", p.nbmax2) TAB("nbmax3", p.nbmax3)
     TAB("psy_short_npart", p.psyS.npart) TAB("alloc1", p.alloc1) TAB("a1_log_cbw", p.a1_log_cbw)
+    TAB("nBand_l_iso", p.nBand_l_iso) TAB("nBand_s", p.nBand_s) TAB("pow43", g.pow43)
+    TAB("recon_pow2q", r.pow2q) TAB("recon_cos36", r.cos36) TAB("recon_cos12", r.cos12) TAB("recon_win", r.win) TAB("recon_cs", r.cs) TAB("recon_ca", r.ca)
+    TAB("recon_synth", r.synth) TAB("recon_dwin", r.dwin)
 #undef TAB
     if (k == "sizeof_band_prep") { static int v[1]; v[0] = (int) sizeof(HxBandPrep); src = v; n = sizeof(v); }     // for the tests' mirror of the "band" tap
     if (k == "sizeof_pack_records") {       // for the tests' mirrors of what hx_debug_pack takes; [3]: slots pending from earlier calls
         static int v[5];
         v[0] = (int) sizeof(HxSegOut); v[1] = (int) sizeof(HxFrameOut); v[2] = (int) sizeof(HxSlot); v[3] = HX_SLOTS_EXTRA; v[4] = HX_SGN_WORDS;
+        src = v; n = sizeof(v);
+    }
+    if (k == "sizeof_recon_records") {      // for the tests' mirrors of what hx_debug_recon takes; [3]: floats of a stream's carried state, [4]: of its tails
+        static int v[8];
+        v[0] = (int) sizeof(HxSegOut); v[1] = (int) sizeof(HxFrameDebug); v[2] = HX_SGN_WORDS; v[3] = HX_RECON_STATE_FLOATS; v[4] = HX_RECON_TAIL_FLOATS;
+        v[5] = HX_RECON_HIST_SLOTS; v[6] = (int) sizeof(HxGr); v[7] = (int) offsetof(HxSegOut, sf);
         src = v; n = sizeof(v);
     }
     if (k == "run_w") { static int v[1]; v[0] = p.run_w; src = v; n = sizeof(v); }

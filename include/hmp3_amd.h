@@ -970,6 +970,29 @@ long long hx_debug_host_table(const HX_E_CONTROL *ec, const char *name, void *ds
 int hx_debug_pack(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, int fps, const int *nfr,
                   const void *seg, const short *ixq, const unsigned *sgn, const void *frm, const void *slots,
                   unsigned char *rows, long long out_stride, unsigned char *packet, long long packet_bytes, int *status);
+/* For tests: the decoded-PCM kernels (k_recon_hybrid, k_recon_synth, k_recon_carry) on records of the caller's instead of
+   the stream walk's, launched the way a batch's call launches them, with the tables a batch gives them.  All pointers are
+   host memory.  ec [ncls]: the controls of the classes in play - MPEG-1 streams of the second-generation allocator only, any
+   other class is refused by name as hx_batch_recon_buffer refuses it; cls [S]: each stream's class; NG: granule positions
+   per stream (even); nfr [S] or null: per-stream frame counts (0 .. NG / 2).  ixq [S][NG][2][576], sgn [S][NG][2][20],
+   seg [S][NG][2] and rec [S][NG / 2] in the layouts of hmp3_amd/csrc/hx_types.h (quantised magnitudes in bitstream order, one
+   sign bit per line, HxSegOut - of which only sf is read, for short blocks: field 3 * band + window - and HxFrameDebug: ms,
+   gr and sf; the record sizes: hx_debug_host_table "sizeof_recon_records").  state [S][1152 + 2 * 15 * 32] goes to the
+   device as the caller filled it and comes back as k_recon_carry left it; hyb [S][NG][2][18 time slots][32 subbands], the
+   hybrid output, and out [S][row], the rows in the layout of hx_batch_recon_buffer's, go the same way and come back as the
+   kernels left them: what no kernel writes - blocks behind a stream's count, a mono stream's second channel - keeps the
+   caller's bytes.
+   Every record a kernel will read is checked on the host first: one the stream walk cannot hand over is refused with -1 and
+   hx_last_error, which names stream, granule, channel and field, before anything is launched - block_type outside 0 .. 3,
+   unequal in a granule's channels or not a legal successor of the granule before it; mixed_block_flag set; global_gain
+   outside 0 .. 255; a subblock_gain outside 0 .. 7; a long scalefactor above 15 (bands 0 .. 10), 7 (11 .. 20) or 0 (21); a
+   short field above 15 (bands 0 .. 5) or 7 (6 .. 11) or negative; a magnitude outside 0 .. 8206 within the coded range
+   2 * big_values + 4 * aux_nquads (clipped at 576; nothing with aux_not_null 0); big_values above 288, aux_nquads negative;
+   ms neither 0 nor 1; a count outside 0 .. NG / 2; a row shorter than a stream's blocks; state that is not finite.  What
+   lies from the coded range on is not looked at: the kernels ignore it.  Returns 0.  Synchronises. */
+int hx_debug_recon(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, const int *nfr,
+                   const short *ixq, const unsigned *sgn, const void *seg, const void *rec, float *state, float *hyb,
+                   float *out, long long row);
 /* For tests: the stream walk's quantiser and Huffman counter - do_quant, quant_count_bits, count_bits, s_do_quant,
    s_count_bits_ch and what they call, unmodified - on records of the caller's.  One workgroup of two waves per record, as
    the walk has them: channel 1 runs on the helper wave, through the walk's work orders.  All pointers are host memory.

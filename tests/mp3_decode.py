@@ -94,16 +94,26 @@ class _Bits:
 class Decoder:
     """feed(bytes) decodes every complete frame; frames: one dict per frame (header and side information, per granule
     and channel the decoded lines `ix`, `sign`, `sf` and `huff_end` = the bit the Huffman decode stopped at, counted like
-    part2_3_length), pcm: one [1152, nch] float64 array per frame."""
+    part2_3_length), pcm: one [1152, nch] float64 array per frame.
 
-    def __init__(self, huff):
+    The back half can be driven without a bitstream (huff=None; tests/recon_granule_cases.py): back_half(info) takes a
+    frame's dict with "samprate", "nch", "ms" and per granule and channel "ix", "sign", "sf", "global_gain",
+    "subblock_gain", "scalefac_scale", "preflag" and "block_type", tail / vhist may be seeded, and with taps = [] every
+    granule-channel's hybrid output [18][32] is appended to it.  magnitude=True makes the second pass of that module: the
+    same formulas with every operand, table entry and partial product replaced by its absolute value and every subtraction
+    by an addition - what a forward error bound of the sums of products is taken of."""
+
+    def __init__(self, huff, magnitude=False):
         self.cos36, self.cos12, self.win, self.cs, self.ca, self.matrix, self.D = _tables()
+        self.mag, self.taps = bool(magnitude), None
+        if self.mag:
+            self.cos36, self.cos12, self.ca, self.matrix, self.D = (np.abs(t) for t in (self.cos36, self.cos12, self.ca, self.matrix, self.D))
         self.dec = {}
-        for (t, x, y), ln in huff["len"].items():
+        for (t, x, y), ln in (huff["len"].items() if huff else ()):
             if ln > 0:
                 self.dec.setdefault(t, {})[(ln, huff["code"][t, x, y])] = (x, y)
-        self.linbits = huff["linbits"]
-        self.quada = {(ln, code): v for v, (code, ln) in enumerate(huff["quada"])}
+        self.linbits = huff["linbits"] if huff else None
+        self.quada = {(ln, code): v for v, (code, ln) in enumerate(huff["quada"])} if huff else {}
         self.buf = b""
         self.main = bytearray()
         self.tail = np.zeros((2, 32, 18))
@@ -241,7 +251,7 @@ class Decoder:
     # ---- back half ----
     def _requantise(self, info, g, ch):
         q, sr = info["gr"][g][ch], info["samprate"]
-        mag = q["ix"].astype(np.float64) ** (4.0 / 3.0) * np.where(q["sign"], -1.0, 1.0)
+        mag = q["ix"].astype(np.float64) ** (4.0 / 3.0) * (1.0 if self.mag else np.where(q["sign"], -1.0, 1.0))
         mult = 1.0 if q["scalefac_scale"] else 0.5
         if q["block_type"] == 2:        # bitstream order: band, window, line; out: [window][line of the window]
             xs = np.zeros((3, 192))
@@ -271,12 +281,17 @@ class Decoder:
             x = x.copy()
             for sb in range(1, 32):
                 lo, hi = x[18 * sb - 1 - np.arange(8)].copy(), x[18 * sb + np.arange(8)].copy()
+                if self.mag:        # (ca holds magnitudes here)
+                    x[18 * sb - 1 - np.arange(8)] = lo * self.cs + hi * self.ca
+                    x[18 * sb + np.arange(8)] = hi * self.cs + lo * self.ca
+                    continue
                 x[18 * sb - 1 - np.arange(8)] = lo * self.cs - hi * self.ca
                 x[18 * sb + np.arange(8)] = hi * self.cs + lo * self.ca
             out = (x.reshape(32, 18) @ self.cos36.T) * self.win[bt]
         res = out[:, :18] + self.tail[ch]
         self.tail[ch] = out[:, 18:]
-        res[1::2, 1::2] *= -1.0
+        if not self.mag:
+            res[1::2, 1::2] *= -1.0
         return res.T
 
     def _synth(self, sb, ch):
@@ -296,12 +311,19 @@ class Decoder:
         for g in range(2):
             bt = info["gr"][g][0]["block_type"]
             x = [self._requantise(info, g, ch) for ch in range(nch)]
-            if info["ms"]:
+            if info["ms"] and self.mag:
+                x = [(x[0] + x[1]) / np.sqrt(2.0), (x[0] + x[1]) / np.sqrt(2.0)]
+            elif info["ms"]:
                 assert info["gr"][g][1]["block_type"] == bt
                 x = [(x[0] + x[1]) / np.sqrt(2.0), (x[0] - x[1]) / np.sqrt(2.0)]
             for ch in range(nch):
-                pcm[576 * g:576 * (g + 1), ch] = self._synth(self._hybrid(x[ch], info["gr"][g][ch]["block_type"], ch), ch)
+                hyb = self._hybrid(x[ch], info["gr"][g][ch]["block_type"], ch)
+                if self.taps is not None:
+                    self.taps.append(hyb)
+                pcm[576 * g:576 * (g + 1), ch] = self._synth(hyb, ch)
         return 32768.0 * pcm
+
+    back_half = _back_half
 
 
 def decode(data, huff):
