@@ -213,6 +213,30 @@ def debug_count(ec, unit, mode, hdr, ix, ixmax, x34=None, gsf=None, device=0):
     return rc, ix, ixmax, out
 
 
+SEEK_MODES = {"seek": 0, "isf2": 1}
+SEEK_UNITS = COUNT_UNITS[:3]
+
+
+def debug_seek(ec, unit, mode, hdr, xr, band, x34=None, x34max=None, ix=None, strict_sums=False, device=0):
+    """hx_debug_seek: the stream walk's gain search ("seek") or inverse_sf2 ("isf2"), as `unit` builds them, on n records (the
+    layouts: include/hmp3_amd.h).  -> (rc, out [n][184]); rc = -1: refused (last_error() says why), nothing was launched and
+    out is zeros"""
+    hdr = np.ascontiguousarray(hdr, dtype=np.int32)
+    n = hdr.shape[0]
+    xr = np.ascontiguousarray(xr, dtype=np.float32)
+    band = np.ascontiguousarray(band, dtype=np.int32)
+    x34, x34max = (None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (x34, x34max))
+    ix = None if ix is None else np.ascontiguousarray(ix, dtype=np.int32)
+    if hdr.shape != (n, 16) or xr.size != n * 1152 or band.size != n * 44 * 8 or (x34 is not None and x34.size != n * 1152) or \
+            (x34max is not None and x34max.size != n * 44) or (ix is not None and ix.size != n * 1152):
+        raise ValueError("arrays of %d records expected" % n)
+    out = np.zeros((n, 184), dtype=np.int32)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    rc = lib().hx_debug_seek(int(device), C.byref(ec), unit.encode(), SEEK_MODES[mode], int(bool(strict_sums)), n, hdr.ctypes.data, xr.ctypes.data,
+                             ptr(x34), ptr(ix), band.ctypes.data, ptr(x34max), out.ctypes.data)
+    return rc, out
+
+
 def debug_recon(ecs, cls, NG, nfr, ixq, sgn, seg, rec, state, hyb, out, device=0):
     """hx_debug_recon: the decoded-PCM kernels on records of the caller's (the layouts: include/hmp3_amd.h).  ecs: the
     controls of the classes in play, cls [S] each stream's class, nfr [S] or None; seg and rec are arrays of the records'

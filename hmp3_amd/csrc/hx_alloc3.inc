@@ -1007,6 +1007,55 @@ __device__ __forceinline__ void alloc_stream(const AllocArgs &a, AllocLds &L)
 // channel 1 is quantised and counted where the walk does it.  What the functions left in LDS goes back out.  One kernel per
 // stream-walk unit, built with that unit's macros and flags in the unit's twin (HX_TAP, below); the host (hx_batch.hip) has checked every record: nothing a
 // record's value indexes can leave its bounds.  The kernel's first argument is an AllocArgs, which COLD() reads.
+// The same kernel serves hx_debug_seek: from HX_DS_SEEK on, HxCountArgs::mode names a noise mode (debug_seek, below).
+#if !HX_A1
+// The noise modes (hx_debug_seek; HxDebugSeek in hx_types.h): the master has staged the tables; it copies record r into LDS
+// where startup and the rate loop would have left the values, calls seek_actual or inverse_sf2 as allocate() does - channel 1
+// goes to the helper wave through HCMD_SEEK / HCMD_ISF2 from inside them - and hands back what they left.  The double-table
+// counter is the record's own result word, not the launch's.
+__device__ __forceinline__ void debug_seek(const HxCountArgs &c, AllocLds &L, long long r)
+{
+    HX_LANE_DECL;
+    const AllocPrm *p = &L.P;
+    const int *h = c.hdr + r * HX_DSH_WORDS;
+    int *out = c.out + r * HX_DSO_WORDS;
+    const bool isf2 = c.mode == HX_DS_ISF2;
+    const int nchan = h[HX_DSH_NCHAN];
+    if (LANE < 2) {
+        const bool on = LANE < nchan;
+        L.P.nsf[LANE] = on ? h[HX_DSH_NSF0 + LANE] : 0;
+        L.P.nbmax[LANE] = on ? h[HX_DSH_NBMAX0 + LANE] : 0;
+        L.G[LANE] = h[HX_DSH_G0 + LANE]; L.scale[LANE] = h[HX_DSH_SCALE0 + LANE];
+    }
+    if (LANE == 0) { L.nchan = nchan; L.P.nchan = nchan; L.big_counter = out + HX_DSO_BIG; }
+    for (int i = LANE; i < 2 * 576; i += 64) {
+        (&L.xr[0][0])[i] = c.xr[r * 1152 + i];
+        (&L.x34[0][0])[i] = isf2 ? 0.0f : c.x34[r * 1152 + i];
+    }
+    if (isf2) for (int i = LANE; i < 2 * 576; i += 64) IX(0)[i] = (ix_t) c.ix[r * 1152 + i];
+    if (LANE < 2 * NB) {
+        const int ch = LANE / NB, b = LANE % NB;
+        const int *w = c.band + ((r * 2 + ch) * NB + b) * HX_DSB_WORDS;
+        if (isf2) { L.up[ch][b] = w[HX_DSB_UP]; L.lo[ch][b] = w[HX_DSB_LO]; L.sf[ch][b] = w[HX_DSB_SF]; L.ixmax[ch][b] = w[HX_DSB_IXMAX]; }
+        else {
+            L.NT[ch][b] = w[HX_DSB_NT]; L.Noise0[ch][b] = w[HX_DSB_NOISE0]; L.gsf[ch][b] = w[HX_DSB_GSF]; L.gzero[ch][b] = w[HX_DSB_GZERO];
+            L.NTadjust[ch][b] = w[HX_DSB_NTADJUST]; L.x34max[ch][b] = c.x34max[(r * 2 + ch) * NB + b];
+        }
+    }
+    HX_WAVE_SYNC();
+    if (isf2) inverse_sf2(L, p);
+    else seek_actual(L, p);
+    HX_WAVE_SYNC();
+    if (LANE < 2 * NB) {
+        const int ch = LANE / NB, b = LANE % NB;
+        int *o = out + HX_DSO_BAND * LANE;
+        if (isf2) { o[0] = L.sf[ch][b]; o[1] = L.geval[ch][b]; }
+        else { o[0] = L.gsf[ch][b]; o[1] = L.Noise[ch][b]; o[2] = L.NTadjust[ch][b]; o[3] = L.geval[ch][b]; }
+    }
+    if (LANE == 0) out[HX_DSO_NSTRICT] = L.nstrict;
+}
+#endif
+
 template <int LSF>
 __device__ __forceinline__ void debug_count(const AllocArgs &a, const HxCountArgs &c, AllocLds &L)
 {
@@ -1016,6 +1065,9 @@ __device__ __forceinline__ void debug_count(const AllocArgs &a, const HxCountArg
     const long long r = blockIdx.x;
     const AllocPrm *p = &L.P;
     stage_stream(a, L, a.st, a.prm, a.gt);
+#if !HX_A1
+    if (c.mode >= HX_DS_SEEK) { debug_seek(c, L, r); HELPER_POST(HCMD_EXIT, 0); return; }
+#endif
     const int *h = c.hdr + r * HX_DCH_WORDS;
     const int mode = c.mode, nchan = h[HX_DCH_NCHAN], opt = h[HX_DCH_OPT], zero21 = h[HX_DCH_ZERO21];
     const bool shortm = mode == HX_DC_SHORT || mode == HX_DC_SHORT_COUNT;

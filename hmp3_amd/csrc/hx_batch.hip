@@ -1971,3 +1971,146 @@ extern "C" int hx_debug_count(int device, const HX_E_CONTROL *ec, const char *un
     HIPCHK(hipMemcpy(out, c.out, sizeof(int) * HX_DCO_WORDS * N, hipMemcpyDeviceToHost));
     return 0;
 }
+
+// ---- hx_debug_seek: the stream walk's gain search and inverse_sf2 on records of the caller's (tests only; include/hmp3_amd.h) ----
+// The kernels are hx_debug_count's (the noise modes of k_debug_count_*, hx_alloc3.inc).  One rule per field, checked for every
+// record before anything is launched; what a value indexes on the device - gain tables, band tables, the lanes' runs - stays
+// inside its bounds under these rules (hx_types.h states the one for the gain steps).
+
+static int seek_refuse(long long r, int ch, int b, const char *field, const char *rule)
+{
+    char msg[256];
+    if (b >= 0) snprintf(msg, sizeof msg, "record %lld channel %d band %d: %s %s", r, ch, b, field, rule);
+    else if (ch >= 0) snprintf(msg, sizeof msg, "record %lld channel %d: %s %s", r, ch, field, rule);
+    else snprintf(msg, sizeof msg, "record %lld: %s %s", r, field, rule);
+    set_err("%s", msg);
+    return -1;
+}
+
+static int check_seek_record(const HxParams &p, bool isf2, long long r, const int *h, const float *xr, const float *x34, const int *ix,
+                             const int *band, const float *x34max)
+{
+    const int nchan = h[HX_DSH_NCHAN];
+    if (nchan != 1 && nchan != 2) return seek_refuse(r, -1, -1, "nchan", "is not 1 or 2");
+    if (h[HX_DSH_NSFS]) return seek_refuse(r, -1, -1, "the short-block band count", "is not zero: neither function reads it");
+    if (h[HX_DSH_HF]) return seek_refuse(r, -1, -1, "the -HF count", "is not zero: neither function reads it");
+    for (int k = HX_DSH_HF + 1; k < HX_DSH_WORDS; k++) if (h[k]) return seek_refuse(r, -1, -1, "a spare header word", "is not zero");
+    // the bands that have lanes: the runs are cut for the class's measured bands (hx_host.cpp band_runs)
+    const int nbcls = std::max(p.nsf[0], p.nchan == 2 ? p.nsf[1] : 0);
+    for (int c = 0; c < 2; c++) {
+        const int nsf = h[HX_DSH_NSF0 + c], nl = h[HX_DSH_NBMAX0 + c], G = h[HX_DSH_G0 + c], scale = h[HX_DSH_SCALE0 + c];
+        if (c >= nchan) {
+            if (nsf) return seek_refuse(r, c, -1, "nsf", "of a channel the record does not have is not zero");
+            if (nl) return seek_refuse(r, c, -1, "nbmax", "of a channel the record does not have is not zero");
+        } else {
+            if (nsf < 1 || nsf > nbcls) return seek_refuse(r, c, -1, "nsf", "is outside 1 .. the class's band count");
+            if (nl != p.startBand_l[nsf]) return seek_refuse(r, c, -1, "nbmax", "is not the first line behind band nsf - 1");
+        }
+        if (isf2 ? (G < 0 || G > 255) : G != 0) return seek_refuse(r, c, -1, "G", isf2 ? "is outside 0 .. 255" : "is inverse_sf2's: not zero");
+        if (isf2 ? (scale != 0 && scale != 1) : scale != 0) return seek_refuse(r, c, -1, "scale", isf2 ? "is not 0 or 1" : "is inverse_sf2's: not zero");
+        for (int j = 0; j < 576; j++) {
+            const int b = p.band_of_line[j];
+            if (!(fabsf(xr[576 * c + j]) <= 3.0e38f)) return seek_refuse(r, c, b, "xr", "holds a line that is not finite");
+            if (isf2) { if (ix[576 * c + j] < 0 || ix[576 * c + j] > HX_IX_MAX) return seek_refuse(r, c, b, "ix", "holds a line outside 0 .. 8206"); }
+            else if (!(x34[576 * c + j] >= 0.0f && x34[576 * c + j] <= HX_DS_X34_MAX)) return seek_refuse(r, c, b, "x34", "holds a line outside 0 .. 2^28");
+        }
+        for (int b = 0; b < 22; b++) {
+            const int *w = band + (22 * c + b) * HX_DSB_WORDS;
+            const int j0 = p.startBand_l[b], j1 = b < 21 ? p.startBand_l[b + 1] : 576;
+            if (isf2) {
+                int m = 0;
+                for (int j = j0; j < j1; j++) m = std::max(m, ix[576 * c + j]);
+                if (w[HX_DSB_IXMAX] != m) return seek_refuse(r, c, b, "ixmax", "is not the maximum of the band's lines");
+                if (w[HX_DSB_LO] < 0 || w[HX_DSB_LO] > 255) return seek_refuse(r, c, b, "lo", "is outside 0 .. 255");
+                if (w[HX_DSB_UP] < w[HX_DSB_LO] || w[HX_DSB_UP] > 255) return seek_refuse(r, c, b, "up", "is below lo or above 255");
+                if (w[HX_DSB_SF] < 0 || w[HX_DSB_SF] > 255) return seek_refuse(r, c, b, "sf", "is outside 0 .. 255");
+                for (int k = HX_DSB_IXMAX + 1; k < HX_DSB_WORDS; k++) if (w[k]) return seek_refuse(r, c, b, "a spare band word", "is not zero");
+            } else {
+                float m = 0.0f;
+                for (int j = j0; j < j1; j++) m = std::max(m, x34[576 * c + j]);
+                // (noise_band_needs_pow picks the sweep's route from it)
+                if (!(x34max[22 * c + b] == m)) return seek_refuse(r, c, b, "x34max", "is not the maximum of the band's x34");
+                if (abs(w[HX_DSB_NT]) > HX_DS_INT_MAX) return seek_refuse(r, c, b, "NT", "is outside -2^20 .. 2^20");
+                if (abs(w[HX_DSB_NOISE0]) > HX_DS_INT_MAX) return seek_refuse(r, c, b, "Noise0", "is outside -2^20 .. 2^20");
+                if (abs(w[HX_DSB_NTADJUST]) > HX_DS_INT_MAX) return seek_refuse(r, c, b, "NTadjust", "is outside -2^20 .. 2^20");
+                if (w[HX_DSB_GSF] < 0 || w[HX_DSB_GSF] > HX_DS_GSF_MAX) return seek_refuse(r, c, b, "gsf", "is outside 0 .. 107: 20 steps up from it must stay inside the gain tables");
+                if (w[HX_DSB_GZERO] < 0 || w[HX_DSB_GZERO] > 127) return seek_refuse(r, c, b, "gzero", "is outside 0 .. 127");
+                for (int k = HX_DSB_NTADJUST + 1; k < HX_DSB_WORDS; k++) if (w[k]) return seek_refuse(r, c, b, "a spare band word", "is not zero");
+            }
+        }
+    }
+    return 0;
+}
+
+extern "C" int hx_debug_seek(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int strict_sums, int n, const int *hdr,
+                             const float *xr, const float *x34, const int *ix, const int *band, const float *x34max, int *out)
+{
+    if (!ec || !unit || !hdr || !xr || !band || !out) { set_err("null buffer"); return -1; }
+    if (mode != 0 && mode != 1) { set_err("hx_debug_seek: no such mode"); return -1; }
+    const bool isf2 = mode == 1;
+    if (isf2 ? !ix : (!x34 || !x34max)) { set_err("null buffer"); return -1; }
+    if (strict_sums != 0 && strict_sums != 1) { set_err("hx_debug_seek: strict_sums is 0 or 1"); return -1; }
+    if (n <= 0 || n > HX_DEBUG_COUNT_MAX) { set_err("hx_debug_seek takes 1 .. 16384 records per call"); return -1; }
+    static const char *const units[5] = {"k_alloc", "k_alloc_slim", "k_alloc_lsf", "k_alloc1", "k_alloc1_lsf"};
+    int u = -1;
+    for (int k = 0; k < 5; k++) if (!strcmp(unit, units[k])) u = k;
+    if (u < 0) { set_err("hx_debug_seek: no stream-walk unit named %s", unit); return -1; }
+    if (u >= 3) { set_err("hx_debug_seek: %s is a first-generation unit, which runs neither seek_actual nor inverse_sf2", unit); return -1; }
+    std::vector<HxParams> prm(1);
+    if (!hx_resolve((const HxControl *) ec, &prm[0])) { set_err("configuration rejected"); return -1; }
+    std::vector<HxGlobalTabs> gt(1);
+    hx_global_tabs(&gt[0]);
+    const int kind = 2 * (prm[0].alloc1 ? 1 : 0) + (prm[0].h_id ? 0 : 1);
+    static const int unit_kind[3] = {0, 0, 1};
+    if (unit_kind[u] != kind) { set_err("hx_debug_seek: %s does not run streams of this control", unit); return -1; }
+    if (u == 1 && !hx_slim_tables_ok(&prm[0], &gt[0])) { set_err("hx_debug_seek: the host's tables do not have the structure k_alloc_slim derives them from"); return -1; }
+    for (long long r = 0; r < n; r++)
+        if (check_seek_record(prm[0], isf2, r, hdr + r * HX_DSH_WORDS, xr + r * 1152, isf2 ? nullptr : x34 + r * 1152, isf2 ? ix + r * 1152 : nullptr,
+                              band + r * 44 * HX_DSB_WORDS, isf2 ? nullptr : x34max + r * 44) != 0) return -1;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return -1; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return -1; }
+    HIPCHK(hipSetDevice(device));
+    struct Dev {
+        std::vector<void *> mem;
+        ~Dev() { for (void *p : mem) (void) hipFree(p); }
+        void *up(const void *src, size_t bytes)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes ? bytes : 16) != hipSuccess) return nullptr;
+            mem.push_back(q);
+            if (src ? hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess : hipMemset(q, 0, bytes) != hipSuccess) return nullptr;
+            return q;
+        }
+    } dev;
+    std::vector<HxStream> st(1);
+    hx_stream_reset(&prm[0], 0, &st[0]);
+    const size_t N = (size_t) n;
+    AllocArgs a = {};
+    HxCountArgs c = {};
+    a.st = (HxStream *) dev.up(st.data(), sizeof(HxStream));
+    a.prm = (const HxParams *) dev.up(prm.data(), sizeof(HxParams));
+    a.gt = (const HxGlobalTabs *) dev.up(gt.data(), sizeof(HxGlobalTabs));
+    a.done_counter = (int *) dev.up(nullptr, sizeof(int) * HX_CNT_WORDS);
+    a.S = 1; a.NG = 2; a.npos = 1;
+    a.strict_sums = strict_sums;
+    c.mode = HX_DS_SEEK + mode; c.n = n; c.nband = 22;
+    c.hdr = (const int *) dev.up(hdr, sizeof(int) * HX_DSH_WORDS * N);
+    c.xr = (const float *) dev.up(xr, sizeof(float) * 1152 * N);
+    c.band = (const int *) dev.up(band, sizeof(int) * 44 * HX_DSB_WORDS * N);
+    c.x34 = isf2 ? nullptr : (const float *) dev.up(x34, sizeof(float) * 1152 * N);
+    c.x34max = isf2 ? nullptr : (const float *) dev.up(x34max, sizeof(float) * 44 * N);
+    c.ix = isf2 ? (int *) dev.up(ix, sizeof(int) * 1152 * N) : nullptr;
+    c.out = (int *) dev.up(nullptr, sizeof(int) * HX_DSO_WORDS * N);
+    if (!a.st || !a.prm || !a.gt || !a.done_counter || !c.hdr || !c.xr || !c.band || (isf2 ? !c.ix : (!c.x34 || !c.x34max)) || !c.out) { set_err("hipMalloc or upload failed"); return -1; }
+    const dim3 grid((unsigned) n), block(128);
+    if (u == 0) LAUNCH(k_debug_count, grid, block, 0, a, c);
+    else if (u == 1) LAUNCH(k_debug_count_slim, grid, block, 0, a, c);
+    else LAUNCH(k_debug_count_lsf, grid, block, 0, a, c);
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, c.out, sizeof(int) * HX_DSO_WORDS * N, hipMemcpyDeviceToHost));
+    return 0;
+}

@@ -389,8 +389,36 @@ struct HxCountArgs {
     int *ixmax;             // [n][2][nband] band maxima, the same way
     const float *x34;       // [n][2][576] (the quantising modes)
     const int *gsf;         // [n][2][nband] gain steps (the quantising modes)
-    int *out;               // [n][HX_DCO_WORDS]
+    int *out;               // [n][HX_DCO_WORDS]; the noise modes: [n][HX_DSO_WORDS]
+    // the noise modes (below) only
+    const float *xr;        // [n][2][576] magnitudes
+    const int *band;        // [n][2][22][HX_DSB_WORDS]
+    const float *x34max;    // [n][2][22] (seek)
 };
+
+// ---- the same kernels' noise modes (hx_debug_seek): the walk's two certified band sums - the gain search seek_actual and
+// inverse_sf2, with everything they call - on records of the caller's.  HxCountArgs::mode goes on where HxDebugCount ends; hdr,
+// x34 (seek), ix (isf2: read only) and out are HxCountArgs' own, in the layouts below.  The first-generation units have neither
+// function.  include/hmp3_amd.h describes a record for the caller, hx_batch.hip (check_seek_record) has the rule of every field.
+enum HxDebugSeek { HX_DS_SEEK = HX_DC_MODES, HX_DS_ISF2, HX_DS_END };
+// header words of a record; NSFS and HF stand for the short-block and -HF fields of the walk, which neither function reads: zero
+enum { HX_DSH_NCHAN, HX_DSH_NSF0, HX_DSH_NSF1, HX_DSH_NBMAX0, HX_DSH_NBMAX1, HX_DSH_G0, HX_DSH_G1, HX_DSH_SCALE0, HX_DSH_SCALE1,
+       HX_DSH_NSFS, HX_DSH_HF, HX_DSH_WORDS = 16 };
+// words of a band (seek | isf2)
+enum { HX_DSB_NT = 0, HX_DSB_NOISE0, HX_DSB_GSF, HX_DSB_GZERO, HX_DSB_NTADJUST, HX_DSB_WORDS = 8 };
+enum { HX_DSB_UP = 0, HX_DSB_LO, HX_DSB_SF, HX_DSB_IXMAX };
+// A gain step of a seek record, bands below nsf: every step the search can evaluate from start step s must index the 128-entry
+// gain tables, and the kernel clamps its indices for the reads that run a sweep ahead only.  Walking down it measures
+// s - 1 .. s - min(s - 1, 20), which is >= 1 whatever s >= 0 is; walking up it measures s + 1 .. s + 20.  So 0 <= s <= 107 is
+// the whole rule, and it needs no search to state.
+#define HX_DS_GSF_MAX 107
+// x^(3/4) of a seek record's line: at most 2^28, so that its quantised value at the largest 1 / gain^(3/4) (2^1.5, step 0) is
+// an int - the conversion of a larger float is undefined in C, which the oracle and the reference are written in
+#define HX_DS_X34_MAX 268435456.0f
+#define HX_DS_INT_MAX (1 << 20)     // targets, start noise, estimator feedback: |v| at most this (no sum of them overflows)
+// result words of a record: per (channel, band) four - seek {gsf, Noise, NTadjust, geval}, isf2 {sf, geval, 0, 0} - then the
+// stream's count of strict fall-backs (AllocLds::nstrict) and the double-table passes (what the walk adds to HX_CNT_BIG_SWEEPS)
+enum { HX_DSO_BAND = 4, HX_DSO_NSTRICT = 2 * 22 * 4, HX_DSO_BIG, HX_DSO_WORDS = 2 * 22 * 4 + 8 };
 
 
 // ---- slot operations (hx_slots.hip: k_slot_reset / k_slot_gather / k_slot_scatter) ----

@@ -1022,6 +1022,30 @@ int hx_debug_recon(int device, const HX_E_CONTROL *ec, int ncls, const int *cls,
    hmp3_amd/csrc/hx_batch.hip has the argument) - so there is nothing to define.  Returns 0.  Synchronises. */
 int hx_debug_count(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int n, const int *hdr, int *ix, int *ixmax,
                    const float *x34, const int *gsf, int *out);
+/* For tests: the stream walk's two certified band sums - the gain search (seek_actual: noise_sweep, the lanes' line runs, the
+   segmented scan, the bucket certificate, the strict and the double-table fall-backs) and inverse_sf2, unmodified - on records
+   of the caller's, by the kernels of hx_debug_count: one workgroup of two waves per record, channel 1 on the helper wave
+   through the walk's work orders.  All pointers are host memory.  unit: "k_alloc", "k_alloc_slim" or "k_alloc_lsf" (the
+   first-generation units run neither function and are refused); ec: a control whose streams that unit walks - its band
+   tables and the line runs cut for its measured bands are the records'.  strict_sums 1: as a batch under
+   HMP3AMD_EXACT_SUMS=1, no certificate passes.  n records, 1 .. 16384.
+   hdr [n][16]: {nchan, nsf[2], nbmax[2], G[2], scale[2], 0 (short-block bands), 0 (-HF lines)}, the rest zero; a mono record
+   has nsf[1] = nbmax[1] = 0.  xr [n][2][576]: the magnitudes.  band [n][2][22][8] and out [n][184]:
+   mode 0 seek     x34 [n][2][576], x34max [n][2][22]; a band's words {NT, Noise0, gsf (the start step), gzero, NTadjust, 0, 0, 0};
+                   out per (channel, band) {gsf, Noise, NTadjust, geval}
+   mode 1 isf2     ix [n][2][576] the quantised lines; a band's words {up, lo, sf, ixmax, 0 ...}; G and scale in the header;
+                   out per (channel, band) {sf, geval, 0, 0}
+   and at out[176] the strict fall-backs the record's two waves counted (one per sweep with a band whose bucket was not
+   proven; with strict_sums one per sweep), at out[177] the sweeps that took the double table.  Arrays of the other mode are
+   null.  Every record is checked before anything is launched and refused with -1 and hx_last_error, which names record,
+   channel, band and field, leaving out alone: nchan 1 or 2; nsf 1 .. the class's measured bands, nbmax the first line behind
+   band nsf - 1 (both 0 for a channel the record does not have); the short-block and -HF words zero; lines and x34 finite,
+   0 <= x34 <= 2^28; x34max the exact maximum of its band's x34, ixmax of its band's lines (0 .. 8206); start steps 0 .. 107
+   (every step a search can evaluate then lies in the 128-entry gain tables: hmp3_amd/csrc/hx_types.h has the argument);
+   gzero 0 .. 127; NT, Noise0, NTadjust within +-2^20; G 0 .. 255, scale 0 or 1, 0 <= lo <= up <= 255, sf 0 .. 255 (seek: G and
+   scale zero).  Returns 0.  Synchronises. */
+int hx_debug_seek(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int strict_sums, int n, const int *hdr,
+                  const float *xr, const float *x34, const int *ix, const int *band, const float *x34max, int *out);
 
 /* ---- Xing / Info / LAME tag frame (first frame of a file; reference pub/xhead.h) ----
    Same arguments and return values as the reference functions; the seek-table state that the

@@ -257,6 +257,10 @@ void  hxo_do_quant(const hxo_params *p, int nchan, const int nsf[2], int opt, fl
 int   hxo_quant_lines(const hxo_params *p, int rule, const float *x34, int *ix, int gsf, int n);
 int   hxo_count_record(const hxo_params *p, int quant, int clear_past, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out);
 int   hxo_count_record_short(const hxo_params *p, int quant, const int *hdr, int *ix, int *ixmax, const float *x34, const int *gsf, int *out);
+/* the gain search and inverse_sf2 on the records of the noise-search tests (hxo_alloc.c; layouts: include/hmp3_amd.h, hx_debug_seek) */
+void  hxo_seek_record(hxo_encoder *e, const int *hdr, const float *xr, const float *x34, const int *band, int *out);
+void  hxo_isf2_record(hxo_encoder *e, const int *hdr, const float *xr, const int *ix, const int *band, int *out);
+int   hxo_noise_band(hxo_encoder *e, const float *x34, const float *x, int gsf, int n, int logn);     /* l3math.c:512 on one band */
 const hxo_params *hxo_params_of(const hxo_encoder *e);
 void  hxo_band_tables(const hxo_params *p, int *tl, int *ts);
 void  hxo_huffsel_to_gr(const hxo_params *p, const hxo_huffsel *s, hxo_gr *g);  /* bitalloc.cpp:758 */

@@ -948,6 +948,80 @@ static void inverse_sf2(ba_t *b)
     }
 }
 
+/* One record of the noise-search tests (tests/noise_cases.py; the layout is hx_debug_seek's, include/hmp3_amd.h) through
+   seek_actual or inverse_sf2 above, as they stand: the record's values go where startup and the rate loop would have left
+   them, the encoder's own band counts, estimator feedback and band maxima are put back afterwards.  out [184] as the device
+   leaves it, with what only the device has stated by rule: geval is -1 behind a search and 1 on the bands inverse_sf2
+   refines, -1 elsewhere; the two counters at [176], [177] stay zero.  At [178..180] what the record reached: seek - lines
+   dequantised beyond the float table, those quantised to 16384 or more, the largest quantised value beyond it (hxo_range_counts);
+   isf2 - bands refined, clamped at up, clamped at lo (the path census's counts). */
+static void record_ba(ba_t *b, hxo_encoder *e, const int *hdr, const float *xr, int saved_nsf[2])
+{
+    memset(b, 0, sizeof(*b));
+    b->e = e; b->p = &e->p;
+    b->xr = (float (*)[576]) xr;
+    b->nchan = hdr[0];
+    saved_nsf[0] = e->p.nsf[0]; saved_nsf[1] = e->p.nsf[1];
+    e->p.nsf[0] = hdr[1]; e->p.nsf[1] = hdr[2];
+}
+void hxo_seek_record(hxo_encoder *e, const int *hdr, const float *xr, const float *x34, const int *band, int *out)
+{
+    static ba_t b;
+    int ch, i, saved_nsf[2], saved_adj[2][22];
+    const hxo_range_counts saved_range = e->range[0];
+    record_ba(&b, e, hdr, xr, saved_nsf);
+    memcpy(saved_adj, e->s.NTadjust, sizeof(saved_adj));
+    memcpy(b.x34, x34, sizeof(b.x34));
+    memset(&e->range[0], 0, sizeof(e->range[0]));
+    for (ch = 0; ch < 2; ch++) for (i = 0; i < 22; i++) {
+        const int *w = band + (22 * ch + i) * 8;
+        b.NT[ch][i] = w[0]; b.Noise0[ch][i] = w[1]; b.gsf[ch][i] = w[2]; b.gzero[ch][i] = w[3]; e->s.NTadjust[ch][i] = w[4];
+    }
+    seek_actual(&b);
+    memset(out, 0, 184 * sizeof(int));
+    for (ch = 0; ch < 2; ch++) for (i = 0; i < 22; i++) {
+        int *o = out + 4 * (22 * ch + i);
+        o[0] = b.gsf[ch][i]; o[1] = b.Noise[ch][i]; o[2] = e->s.NTadjust[ch][i]; o[3] = -1;
+    }
+    out[178] = (int) e->range[0].beyond_table; out[179] = (int) e->range[0].from_16384; out[180] = e->range[0].max_qx;
+    e->range[0] = saved_range;
+    memcpy(e->s.NTadjust, saved_adj, sizeof(saved_adj));
+    e->p.nsf[0] = saved_nsf[0]; e->p.nsf[1] = saved_nsf[1];
+}
+void hxo_isf2_record(hxo_encoder *e, const int *hdr, const float *xr, const int *ix, const int *band, int *out)
+{
+    static ba_t b;
+    int ch, i, saved_nsf[2], saved_max[2][22];
+    const long long c0 = hxo_path_counts[HXO_P_L_isf2_refined], c1 = hxo_path_counts[HXO_P_L_isf2_clamp_up], c2 = hxo_path_counts[HXO_P_L_isf2_clamp_lo];
+    record_ba(&b, e, hdr, xr, saved_nsf);
+    memcpy(saved_max, e->s.ixmax, sizeof(saved_max));
+    b.ix = (int (*)[576]) ix;
+    for (ch = 0; ch < 2; ch++) {
+        b.G[ch] = hdr[5 + ch]; b.scale[ch] = hdr[7 + ch];
+        for (i = 0; i < 22; i++) {
+            const int *w = band + (22 * ch + i) * 8;
+            b.up[ch][i] = w[0]; b.lo[ch][i] = w[1]; b.sf[ch][i] = w[2]; e->s.ixmax[ch][i] = w[3];
+        }
+    }
+    inverse_sf2(&b);
+    memset(out, 0, 184 * sizeof(int));
+    for (ch = 0; ch < 2; ch++) for (i = 0; i < 22; i++) {
+        int *o = out + 4 * (22 * ch + i);
+        o[0] = b.sf[ch][i];
+        o[1] = (ch < b.nchan && i < e->p.nsf[ch] && (e->s.ixmax[ch][i] == 1 || e->s.ixmax[ch][i] == 2)) ? 1 : -1;
+    }
+    out[178] = (int) (hxo_path_counts[HXO_P_L_isf2_refined] - c0); out[179] = (int) (hxo_path_counts[HXO_P_L_isf2_clamp_up] - c1);
+    out[180] = (int) (hxo_path_counts[HXO_P_L_isf2_clamp_lo] - c2);
+    memcpy(e->s.ixmax, saved_max, sizeof(saved_max));
+    e->p.nsf[0] = saved_nsf[0]; e->p.nsf[1] = saved_nsf[1];
+}
+/* noise_actual on one band's lines (tests: the search's steps one by one) */
+int hxo_noise_band(hxo_encoder *e, const float *x34, const float *x, int gsf, int n, int logn)
+{
+    hxo_range_counts rc = {0, 0, 0};
+    return noise_actual(&e->p, &rc, x34, x, gsf, n, logn);
+}
+
 /* bitallo3.cpp:2948-3046 (ms = 0) / 3048-3149 (ms = 1) */
 static int allocate(ba_t *b, int ms)
 {

@@ -528,6 +528,40 @@ def count_records(tabs, mode, hdr, ix, ixmax, x34=None, gsf=None, clear_past=Fal
     return ix, ixmax, out, out[:, 20].copy()
 
 
+def ref_has_noise_records():
+    """whether the reference build at hand was made with the noise-search entries in its harness"""
+    return ref() is not None and hasattr(ref(), "ref_seek_record")
+
+
+def noise_records(tabs, mode, hdr, xr, band, x34=None, ix=None, use_ref=False):
+    """n records (the layout: hx_debug_seek, include/hmp3_amd.h) through the oracle's seek_actual (mode "seek") or inverse_sf2
+    ("isf2"), or with use_ref through CBitAllo3::noise_seek_actual / inverse_sf2 -> out [n][184]: per (channel, band) four
+    words as hx_debug_seek leaves them - the reference fills gsf, Noise, NTadjust / sf only - and from the oracle at [178:181]
+    what the record reached (hxo_seek_record)"""
+    hdr = np.ascontiguousarray(hdr, dtype=np.int32)
+    n = hdr.shape[0]
+    xr = np.array(xr, dtype=np.float32, order="C").reshape(n, 1152)
+    band = np.ascontiguousarray(band, dtype=np.int32).reshape(n, 352)
+    other = np.array(x34, dtype=np.float32, order="C").reshape(n, 1152) if mode == "seek" else np.array(ix, dtype=np.int32, order="C").reshape(n, 1152)
+    out = np.zeros((n, 184), np.int32)
+    if use_ref:
+        f, h = (ref().ref_seek_record if mode == "seek" else ref().ref_isf2_record), tabs.ref.h
+    else:
+        f, h = (lib().hxo_seek_record if mode == "seek" else lib().hxo_isf2_record), tabs.enc.h
+    f.argtypes, f.restype = [C.c_void_p] * 6, None
+    for r in range(n):
+        f(h, hdr[r].ctypes.data, xr[r].ctypes.data, other[r].ctypes.data, band[r].ctypes.data, out[r].ctypes.data)
+    return out
+
+
+def noise_band(tabs, x34, x, gsf, logn):
+    """the oracle's noise_actual (l3math.c:512) of one band's lines at gain step gsf"""
+    x34, x = (np.ascontiguousarray(a, dtype=np.float32) for a in (x34, x))
+    f = lib().hxo_noise_band
+    f.argtypes, f.restype = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int], C.c_int
+    return int(f(tabs.enc.h, x34.ctypes.data, x.ctypes.data, int(gsf), x.size, int(logn)))
+
+
 def count_out_to_gr(tabs, out10):
     """COUNT_GR of a long channel's COUNT_OUT, by the oracle's output_subdivide2 (hxo_huffsel_to_gr)"""
     hs = np.ascontiguousarray(out10, dtype=np.int32)

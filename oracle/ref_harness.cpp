@@ -256,6 +256,55 @@ int ref_count_record_short(void *h, int quant, const int *hdr, int *ix, int *ixm
     }
     return bits;
 }
+/* The reference's gain search and scalefactor refinement on the records of the noise-search tests (tests/noise_cases.py; the
+ * layout is hx_debug_seek's, include/hmp3_amd.h; pins hxo_seek_record / hxo_isf2_record, oracle/hxo.h).  h: an encoder
+ * initialised with a control of the second-generation allocator.  The record's values go into the allocator object's members,
+ * CBitAllo3::noise_seek_actual (with ifnc_noise_actual, decrease_noise and increase_noise behind it) or CBitAllo3::inverse_sf2
+ * runs on them, and the object is put back byte for byte.  out [2][22][4]: seek {gsf, Noise, NTadjust, 0}, isf2 {sf, 0, 0, 0}. */
+void ref_seek_record(void *h, const int *hdr, float *xr, const float *x34, const int *band, int *out)
+{
+    CBitAllo3 *b = (CBitAllo3 *) ((CMp3Enc *) h)->BitAllo;
+    std::vector<char> saved(sizeof(*b));
+    memcpy(saved.data(), (void *) b, sizeof(*b));
+    b->nchan = hdr[0]; b->nsf[0] = hdr[1]; b->nsf[1] = hdr[2];
+    b->xr = (float (*)[576]) xr;
+    memcpy(b->x34, x34, sizeof(b->x34));
+    for (int ch = 0; ch < 2; ch++) for (int i = 0; i < 22; i++) {
+        const int *w = band + (22 * ch + i) * 8;
+        b->NT[ch][i] = w[0]; b->Noise0[ch][i] = w[1]; b->gsf[ch][i] = w[2]; b->gzero[ch][i] = w[3]; b->NTadjust[ch][i] = w[4];
+        b->Noise[ch][i] = 0;
+    }
+    b->noise_seek_actual();
+    for (int ch = 0; ch < 2; ch++) for (int i = 0; i < 22; i++) {
+        int *o = out + 4 * (22 * ch + i);
+        o[0] = b->gsf[ch][i]; o[1] = b->Noise[ch][i]; o[2] = b->NTadjust[ch][i]; o[3] = 0;
+    }
+    memcpy((void *) b, saved.data(), sizeof(*b));
+}
+void ref_isf2_record(void *h, const int *hdr, float *xr, int *ix, const int *band, int *out)
+{
+    CBitAllo3 *b = (CBitAllo3 *) ((CMp3Enc *) h)->BitAllo;
+    std::vector<char> saved(sizeof(*b));
+    int up[2][22], lo[2][22];
+    memcpy(saved.data(), (void *) b, sizeof(*b));
+    b->nchan = hdr[0]; b->nsf[0] = hdr[1]; b->nsf[1] = hdr[2];
+    b->xr = (float (*)[576]) xr;
+    b->ix = (int (*)[576]) ix;
+    for (int ch = 0; ch < 2; ch++) {
+        b->G[ch] = hdr[5 + ch]; b->scalefactor_scale[ch] = hdr[7 + ch];
+        b->psf_upper_limit[ch] = up[ch]; b->psf_lower_limit[ch] = lo[ch];
+        for (int i = 0; i < 22; i++) {
+            const int *w = band + (22 * ch + i) * 8;
+            up[ch][i] = w[0]; lo[ch][i] = w[1]; b->sf[ch][i] = w[2]; b->ixmax[ch][i] = w[3];
+        }
+    }
+    b->inverse_sf2();
+    for (int ch = 0; ch < 2; ch++) for (int i = 0; i < 22; i++) {
+        int *o = out + 4 * (22 * ch + i);
+        o[0] = b->sf[ch][i]; o[1] = o[2] = o[3] = 0;
+    }
+    memcpy((void *) b, saved.data(), sizeof(*b));
+}
 /* the three quantisers on one run of lines (rule 0 = vect_quant, 1 = vect_quantB, 2 = vect_quantB2 at -0.30); returns the maximum */
 int ref_quant_lines(int rule, float *x34, int *ix, int gsf, int n)
 {
