@@ -258,6 +258,30 @@ def debug_recon(ecs, cls, NG, nfr, ixq, sgn, seg, rec, state, hyb, out, device=0
     return rc, state, hyb, out
 
 
+SPEC_SAMPLE_MAX = 2.0 ** 33        # HX_SPEC_SAMPLE_MAX (include/hmp3_amd.h)
+
+
+def debug_spec(ecs, cls, NG, nfr, direct, sb, bt, xr, etab, thr, msbase, device=0):
+    """hx_debug_spec: K4 (direct False: k_spec, True: k_spec_direct) on subband blocks of the caller's (the layouts:
+    include/hmp3_amd.h).  ecs: the controls of the classes in play, cls [S] each stream's class, nfr [S] or None;
+    sb [S][2][NG + 1][576], bt [S][NG].  -> (rc, xr [S][NG][2][576], etab [S][NG][2][64], thr [S][NG][2][64], msbase [S][NG]):
+    copies of the caller's arrays as the kernel left them; rc = -1: refused (last_error() says why) and nothing was launched"""
+    cls = np.ascontiguousarray(cls, dtype=np.int32)
+    S = cls.size
+    nfr = None if nfr is None else np.ascontiguousarray(nfr, dtype=np.int32)
+    sb = np.ascontiguousarray(sb, dtype=np.float32)
+    bt = np.ascontiguousarray(bt, dtype=np.uint8)
+    xr, etab, thr = (np.array(a, dtype=np.float32, order="C") for a in (xr, etab, thr))
+    msbase = np.array(msbase, dtype=np.int32, order="C")
+    if sb.size != S * 2 * (NG + 1) * 576 or bt.size != S * NG or xr.size != S * NG * 1152 or etab.size != S * NG * 128 or \
+            thr.size != S * NG * 128 or msbase.size != S * NG or (nfr is not None and nfr.size != S):
+        raise ValueError("arrays of %d streams x %d granules expected" % (S, NG))
+    arr = (EControl * len(ecs))(*ecs)
+    rc = lib().hx_debug_spec(int(device), arr, len(ecs), cls.ctypes.data, S, int(NG), None if nfr is None else nfr.ctypes.data, int(bool(direct)),
+                             sb.ctypes.data, bt.ctypes.data, xr.ctypes.data, etab.ctypes.data, thr.ctypes.data, msbase.ctypes.data)
+    return rc, xr, etab, thr, msbase
+
+
 def device_numa_node(device):
     return int(lib().hx_device_numa_node(int(device)))
 

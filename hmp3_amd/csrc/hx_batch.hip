@@ -789,6 +789,18 @@ static int rows_reserve(hx_batch *b, PcmIn in, int nframes)
     return 0;
 }
 
+// K4 over S streams x NG granule positions on stream q (hx_spec.hip): one workgroup of two waves per pair of granules,
+// in the form that goes with the stream-walk kernel (direct: spec_granule<true>).  sb holds SG subband slots per (stream,
+// channel); granule g reads slots g and g + 1.  The one launch expression: a batch's call and hx_debug_spec.
+static int launch_spec(hipStream_t q, bool direct, const float *sb, const HxStream *st, const HxParams *prm, const HxGlobalTabs *gt,
+                       const unsigned char *bt, float *xr, float *etab, float *thr, int *msbase, int S, int NG, int SG, const int *nfr)
+{
+    const dim3 grid((unsigned) ((long long) S * (NG / 2)));
+    if (direct) LAUNCH(k_spec_direct, grid, dim3(128), q, sb, st, prm, gt, bt, xr, etab, thr, msbase, NG, SG, nfr);
+    else LAUNCH(k_spec, grid, dim3(128), q, sb, st, prm, gt, bt, xr, etab, thr, msbase, NG, SG, nfr);
+    return 0;
+}
+
 // the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]
 static int launch_front(hx_batch *b, const Pass &p)
 {
@@ -823,8 +835,7 @@ static int launch_front(hx_batch *b, const Pass &p)
     LAUNCH(k_polyphase, g1, dim3(K1_THREADS), q, d_pcm, nsamp, b->d_st, b->d_prm, b->d_gt, b->d_sb, NG, SG, pcmf, b->nchan, b->d_eng, nfr);
     LAUNCH(k_detect, dim3((S + 3) / 4), dim3(256), q, b->d_st, b->d_prm, b->d_eng, b->d_flg, b->debug ? b->d_dbgmetric : nullptr, f.bt, f.btprev, NG, S, nfr);
     // (the form of K4 that goes with the stream-walk kernel: hx_spec.hip, spec_granule)
-    if (b->slim) LAUNCH(k_spec_direct, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
-    else LAUNCH(k_spec, dim3((unsigned) ((long long) S * nframes)), dim3(128), q, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, NG, SG, nfr);
+    if (launch_spec(q, b->slim != 0, b->d_sb, b->d_st, b->d_prm, b->d_gt, f.bt, f.xr, f.etab, f.thr, f.msbase, S, NG, SG, nfr) != 0) return -1;
     // stereo decisions and the pre-echo hand-over (serial per stream) with the carries of the subband buffer and the PCM
     // history (they belong to the front end: k_alloc does not touch them), then the allocator's state-independent start
     // values per granule; the magnitudes replace the spectrum in place, so the tests' tap of it is taken first
@@ -1722,6 +1733,90 @@ extern "C" int hx_debug_recon(int device, const HX_E_CONTROL *ec, int ncls, cons
     HIPCHK(hipMemcpy(state, d_state, sizeof(float) * HX_RECON_STATE_FLOATS * (size_t) S, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(hyb, d_hyb, sizeof(float) * 576 * units, hipMemcpyDeviceToHost));
     HIPCHK(hipMemcpy(out, d_out, sizeof(float) * (size_t) S * row, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+
+// ---- hx_debug_spec: K4 on subband blocks of the caller's (tests only; include/hmp3_amd.h) ----
+// What k_spec / k_spec_direct read of a call - the subband slots k_polyphase fills and k_detect's block types - comes from the
+// caller; the kernels and their launch are the batch's (launch_spec), HxParams, HxGlobalTabs and HxStream staged as
+// batch_create stages them.  Every block a wave will read is checked on the host first.
+
+static int spec_refuse(long long s, int g, int ch, const char *field, const char *what)
+{
+    char msg[256];
+    if (g < 0) snprintf(msg, sizeof msg, "hx_debug_spec: stream %lld: %s: %s", s, field, what);
+    else if (ch < 0) snprintf(msg, sizeof msg, "hx_debug_spec: stream %lld granule %d: %s: %s", s, g, field, what);
+    else snprintf(msg, sizeof msg, "hx_debug_spec: stream %lld granule %d channel %d: %s: %s", s, g, ch, field, what);
+    set_err("%s", msg);
+    return -1;
+}
+
+extern "C" int hx_debug_spec(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, const int *nfr, int direct,
+                             const float *sb, const unsigned char *bt, float *xr, float *etab, float *thr, int *msbase)
+{
+    if (!ec || !cls || !sb || !bt || !xr || !etab || !thr || !msbase) { set_err("null buffer"); return -1; }
+    if (ncls <= 0 || S <= 0 || NG <= 0 || (NG & 1) || (direct != 0 && direct != 1)) { set_err("bad arguments"); return -1; }
+    if ((long long) S * NG > (1LL << 16)) { set_err("hx_debug_spec takes at most 65536 granule positions (S * NG) per call"); return -1; }
+    std::vector<HxParams> prm(ncls + 1);        // (one more: k_spec reads a spreading row in 16-byte pieces, up to 60 bytes past its end)
+    for (int k = 0; k < ncls; k++)
+        if (!hx_resolve((const HxControl *) (ec + k), &prm[k])) { set_err("configuration rejected"); return -1; }
+    memset((void *) &prm[ncls], 0, sizeof(HxParams));
+    for (int s = 0; s < S; s++) if (cls[s] < 0 || cls[s] >= ncls) { set_err("a stream's class is out of range"); return -1; }
+    if (check_counts_arg(nfr, S, NG / 2, 0) != 0) return -1;
+    const int SG = NG + 1;
+    for (long long s = 0; s < S; s++) {
+        const int ng = nfr ? 2 * nfr[s] : NG;
+        for (int g = 0; g < ng; g++)
+            if (bt[s * NG + g] > 3) return spec_refuse(s, g, -1, "bt", "a block type outside 0 .. 3");
+        // (the first-generation allocator's streams run no detector: k_detect hands their granules type 0, and their metric is the long one's)
+        for (int g = 0; g < ng && prm[cls[s]].alloc1; g++)
+            if (bt[s * NG + g] != 0) return spec_refuse(s, g, -1, "bt", "a block type other than 0 in a stream of the first-generation allocator, which codes long blocks only");
+        for (int ch = 0; ch < 2 && ng > 0; ch++)
+            for (int g = 0; g <= ng; g++) {     // (block g is read by granules g - 1 and g)
+                const float *v = sb + ((s * 2 + ch) * SG + g) * 576;
+                for (int i = 0; i < 576; i++) {
+                    if (!std::isfinite(v[i])) return spec_refuse(s, g, ch, "sb", "a sample that is not finite");
+                    if (std::fabs(v[i]) > HX_SPEC_SAMPLE_MAX) return spec_refuse(s, g, ch, "sb", "a sample above HX_SPEC_SAMPLE_MAX in magnitude");
+                }
+            }
+    }
+    std::vector<HxGlobalTabs> gt_host(1);
+    hx_global_tabs(&gt_host[0]);
+    std::vector<HxStream> st(S);
+    for (int s = 0; s < S; s++) hx_stream_reset(&prm[cls[s]], cls[s], &st[s]);
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) { set_err("no HIP device available: the encoder has no CPU fallback"); return -1; }
+    if (device < 0 || device >= ndev) { set_err("device index out of range"); return -1; }
+    hipDeviceProp_t prop;
+    HIPCHK(hipGetDeviceProperties(&prop, device));
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0) { set_err("device is %s: this library runs on gfx950 (MI355X) only", prop.gcnArchName); return -1; }
+    HIPCHK(hipSetDevice(device));
+    struct Dev {        // device copies: everything is released on every way out
+        std::vector<void *> mem;
+        ~Dev() { for (void *p : mem) (void) hipFree(p); }
+        void *up(const void *src, size_t bytes)
+        {
+            void *q = nullptr;
+            if (hipMalloc(&q, bytes) != hipSuccess) return nullptr;
+            mem.push_back(q);
+            if (hipMemcpy(q, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return nullptr;
+            return q;
+        }
+    } dev;
+    const size_t units = (size_t) S * NG;
+    void *d_st = dev.up(st.data(), sizeof(HxStream) * S), *d_prm = dev.up(prm.data(), sizeof(HxParams) * (ncls + 1)), *d_gt = dev.up(&gt_host[0], sizeof(HxGlobalTabs));
+    void *d_sb = dev.up(sb, sizeof(float) * 576 * 2 * (size_t) S * SG), *d_bt = dev.up(bt, units);
+    void *d_xr = dev.up(xr, sizeof(float) * 1152 * units), *d_etab = dev.up(etab, sizeof(float) * 128 * units), *d_thr = dev.up(thr, sizeof(float) * 128 * units);
+    void *d_ms = dev.up(msbase, sizeof(int) * units), *d_nfr = nfr ? dev.up(nfr, sizeof(int) * S) : nullptr;
+    if (!d_st || !d_prm || !d_gt || !d_sb || !d_bt || !d_xr || !d_etab || !d_thr || !d_ms || (nfr && !d_nfr)) { set_err("hipMalloc or upload failed"); return -1; }
+    if (launch_spec(nullptr, direct != 0, (const float *) d_sb, (const HxStream *) d_st, (const HxParams *) d_prm, (const HxGlobalTabs *) d_gt,
+                    (const unsigned char *) d_bt, (float *) d_xr, (float *) d_etab, (float *) d_thr, (int *) d_ms, S, NG, SG, (const int *) d_nfr) != 0) return -1;
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(xr, d_xr, sizeof(float) * 1152 * units, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(etab, d_etab, sizeof(float) * 128 * units, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(thr, d_thr, sizeof(float) * 128 * units, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(msbase, d_ms, sizeof(int) * units, hipMemcpyDeviceToHost));
     return 0;
 }
 

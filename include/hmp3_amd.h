@@ -1046,6 +1046,31 @@ int hx_debug_count(int device, const HX_E_CONTROL *ec, const char *unit, int mod
    scale zero).  Returns 0.  Synchronises. */
 int hx_debug_seek(int device, const HX_E_CONTROL *ec, const char *unit, int mode, int strict_sums, int n, const int *hdr,
                   const float *xr, const float *x34, const int *ix, const int *band, const float *x34max, int *out);
+/* For tests: K4 - k_spec (direct 0) or k_spec_direct (direct 1): hybrid MDCT, alias reduction, the long and short psy models
+   and the L/R-vs-M/S metric before hysteresis, unmodified - on subband blocks of the caller's instead of k_polyphase's,
+   launched the way a batch's call launches it (same grid, block size and slot arithmetic), with HxParams, HxGlobalTabs and
+   HxStream staged as a batch stages them.  All pointers are host memory.  ec [ncls]: the controls of the classes in play, of
+   any kind a batch accepts (MPEG-1 and MPEG-2 rates, both allocators, mono); cls [S]: each stream's class; NG: granule
+   positions per stream (even), S * NG at most 65536; nfr [S] or null: per-stream frame counts (0 .. NG / 2).  sb [S][2][NG + 1][576]: the subband
+   blocks in the kernel's layout (18 samples of subband 0, 18 of subband 1 ..., frequency inversion not applied); granule g
+   reads blocks g and g + 1, so neighbouring granules share a block as they do in a call.  bt [S][NG]: the block types.
+   xr [S][NG][2][576], etab [S][NG][128], thr [S][NG][128] and msbase [S][NG] go to the device as the caller filled them and
+   come back as the kernel left them: what no wave writes - granules at or past 2 * nfr[s] - keeps the caller's bytes.
+   Checked on the host before anything is launched, refused with -1 and hx_last_error, which names stream, granule, channel
+   and field: a count outside 0 .. NG / 2; a block type outside 0 .. 3, or other than 0 in a stream of the first-generation
+   allocator (intensity stereo, dual channel: it codes long blocks only), among a stream's 2 * nfr[s] granules; a sample that
+   is not finite or above HX_SPEC_SAMPLE_MAX in magnitude among the 2 * nfr[s] + 1 blocks of either channel a wave reads.
+   HX_SPEC_SAMPLE_MAX = 2^33: the reference's polyphase filter gives at most 2230539264 = 1.04 * 2^31 on the loudest input the
+   parity tests feed (2^16 x full scale, tests/dynamic_range_cases.py; DESIGN.md has the measurement), rounded up to a power of
+   two, 2^32, with one binade of margin.  No band sum of squares overflows at that bound: a line before the alias butterflies
+   is a row of the windowed MDCT (18 x 36, absolute row sums at most 1.67 at every block type) times 36 samples, a butterfly
+   adds at most |cs| + |ca| <= 1.38 times the larger of its two lines, so |line| < 2.3 * 2^33 < 2^35 and a square is below
+   2^70; the widest band's 192 squares, the 100 in front, el + er and es + ed <= 4 (el + er) stay below 2^70 * 192 * 4 + 800
+   < 2^80, far from FLT_MAX = 2^128, and so do the partition energies of the psy models (at most 576 squares).  Returns 0.
+   Synchronises. */
+#define HX_SPEC_SAMPLE_MAX 8589934592.0f
+int hx_debug_spec(int device, const HX_E_CONTROL *ec, int ncls, const int *cls, int S, int NG, const int *nfr, int direct,
+                  const float *sb, const unsigned char *bt, float *xr, float *etab, float *thr, int *msbase);
 
 /* ---- Xing / Info / LAME tag frame (first frame of a file; reference pub/xhead.h) ----
    Same arguments and return values as the reference functions; the seek-table state that the

@@ -261,6 +261,10 @@ int   hxo_count_record_short(const hxo_params *p, int quant, const int *hdr, int
 void  hxo_seek_record(hxo_encoder *e, const int *hdr, const float *xr, const float *x34, const int *band, int *out);
 void  hxo_isf2_record(hxo_encoder *e, const int *hdr, const float *xr, const int *ix, const int *band, int *out);
 int   hxo_noise_band(hxo_encoder *e, const float *x34, const float *x, int gsf, int n, int logn);     /* l3math.c:512 on one band */
+/* one granule's front end on the caller's two subband blocks per channel, hysteresis memory zeroed around the call (hxo_enc.c) */
+void  hxo_spec_record(hxo_encoder *e, const float *prev, const float *cur, int bt, float *xr, float *etab, float *thr, int *metric,
+                       float *esave, float *smout);
+void  hxo_last_ms_metric(const hxo_encoder *e, int out[2]);
 const hxo_params *hxo_params_of(const hxo_encoder *e);
 void  hxo_band_tables(const hxo_params *p, int *tl, int *ts);
 void  hxo_huffsel_to_gr(const hxo_params *p, const hxo_huffsel *s, hxo_gr *g);  /* bitalloc.cpp:758 */

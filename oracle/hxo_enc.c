@@ -426,6 +426,8 @@ static void transform_granule(hxo_encoder *e, int igr)
         }
         /* audio_buf[ch][0] = buf + 576, [ch][1] = buf (mp3enc.cpp:193-196) */
         hxo_polyphase_granule(p, s->buf[ch] + (igr == 0 ? 576 : 0), s->sample[ch][ahead]);
+        /* (every path's tap of the subband granule this call computed for (igr, ch)) */
+        if (e->dbg) memcpy(e->dbg->sample_new[igr][ch], s->sample[ch][ahead], 576 * sizeof(float));
     }
     s->igrx = (s->igrx + 1) & 3;
 }
@@ -1097,4 +1099,69 @@ long long hxo_debug_table(const hxo_encoder *e, const char *name, void *dst, lon
     if (n > cap) n = cap;
     memcpy(dst, src, (size_t) n);
     return n;
+}
+
+/* ---- one granule through the front end on blocks of the caller's (tests/spec_cases.py) ----
+   What every frame path above does between the polyphase filter and the allocator, composed as they call it:
+   transform_granule's stages with the path's nsb (nsb_limitMS[0] on every path), the path's metric - hxo_ms_metric_long,
+   hxo_ms_metric_short or, for the first-generation classes, hxo_a1_ms_metric - with the hysteresis memory zeroed around the
+   call and put back, then the psy model per channel with its taps.  prev / cur [2][576]: the granule's two subband blocks per
+   channel as the polyphase filter leaves them (not frequency-inverted).  Out, in the kernels' layout: xr [2][576] (lines
+   from 18 nsb on zero: the frame paths never leave anything else there), etab / thr [2][64] (long: the partitions' energy +
+   absolute threshold and unclamped thresholds, zero from npart rounded up to even on; short: etab zero, thr [12 w + sfb]
+   the spread sums before pre-echo control), *metric (0 without ms_flag).  A mono class fills channel 0 and zeroes channel 1.
+   esave [2][64] and sm [2][36][2] (null: not wanted): what the psy function leaves in a pre-echo memory that was zero and
+   the {sig, mask} pairs it returns (short: previous block type 0) - all the reference's own functions hand out. */
+void hxo_spec_record(hxo_encoder *e, const float *prev, const float *cur, int bt, float *xr, float *etab, float *thr, int *metric,
+                     float *esave, float *smout)
+{
+    const hxo_params *p = &e->p;
+    const int nsb = p->nsb_limitMS[0];
+    float a[576], b[576], ecsave[64], ts[36], *save_e = hxo_tap_etab, *save_t = hxo_tap_thr, *save_s = hxo_tap_thr_short;
+    hxo_sigmask sm[36];
+    int ch, i;
+    memset(xr, 0, 2 * 576 * sizeof(float));
+    memset(etab, 0, 2 * 64 * sizeof(float));
+    memset(thr, 0, 2 * 64 * sizeof(float));
+    if (esave) memset(esave, 0, 2 * 64 * sizeof(float));
+    if (smout) memset(smout, 0, 2 * 72 * sizeof(float));
+    for (ch = 0; ch < p->nchan; ch++) {
+        memcpy(a, prev + 576 * ch, sizeof a);
+        memcpy(b, cur + 576 * ch, sizeof b);
+        hxo_freq_invert(a, nsb);            /* (the frame path inverted the block in place when it was the current one) */
+        hxo_freq_invert(b, nsb);
+        if (bt != 2) {
+            hxo_hybrid_long(p, a, b, xr + 576 * ch, bt, nsb, 1);
+            hxo_antialias(p, xr + 576 * ch, nsb);
+        } else hxo_hybrid_short(p, a, b, xr + 576 * ch, nsb);
+    }
+    *metric = 0;
+    if (p->ms_flag) {
+        const int mem = e->s.ms_correlation_memory;
+        e->s.ms_correlation_memory = 0;
+        if (p->alloc1) *metric = hxo_a1_ms_metric(e, (const float (*)[576]) xr);
+        else if (bt == 2) *metric = hxo_ms_metric_short(e, (const float (*)[576]) xr);
+        else *metric = hxo_ms_metric_long(e, (const float (*)[576]) xr);
+        e->s.ms_correlation_memory = mem;
+    }
+    for (ch = 0; ch < p->nchan; ch++) {
+        memset(ecsave, 0, sizeof ecsave);
+        memset(ts, 0, sizeof ts);
+        memset(sm, 0, sizeof sm);
+        hxo_tap_etab = etab + 64 * ch; hxo_tap_thr = thr + 64 * ch; hxo_tap_thr_short = ts;
+        if (bt != 2) hxo_psy_long(p, xr + 576 * ch, ecsave, sm, bt);
+        else {
+            hxo_psy_short(p, xr + 576 * ch, ecsave, sm, 0);
+            for (i = 0; i < 36; i++) thr[64 * ch + i] = ts[i];
+        }
+        if (esave) memcpy(esave + 64 * ch, ecsave, sizeof ecsave);
+        if (smout) for (i = 0; i < 36; i++) { smout[72 * ch + 2 * i] = sm[i].sig; smout[72 * ch + 2 * i + 1] = sm[i].mask; }
+    }
+    hxo_tap_etab = save_e; hxo_tap_thr = save_t; hxo_tap_thr_short = save_s;
+}
+
+/* the two granules' metrics of the last frame as the frame path left them, hysteresis included (every path; for tests) */
+void hxo_last_ms_metric(const hxo_encoder *e, int out[2])
+{
+    out[0] = e->s.last_ms_metric[0]; out[1] = e->s.last_ms_metric[1];
 }

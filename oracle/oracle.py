@@ -586,3 +586,49 @@ def huff_tables():
                 tabs["len"][t, x, y] = int(l.hxo_huff_len(t, x, y))
                 tabs["code"][t, x, y] = int(l.hxo_huff_code(t, x, y))
     return tabs
+
+
+# ---- one granule's front end on subband blocks (hxo_spec_record, oracle/hxo.h; ref_spec_record, oracle/ref_harness.cpp) ----
+def ref_has_spec_record():
+    """whether the reference build at hand was made with the front-end entry in its harness"""
+    return ref() is not None and hasattr(ref(), "ref_spec_record")
+
+
+def ref_zero_has_spec_record():
+    """the same of the build with uninitialised locals defined as zero (make -C oracle ref_zero)"""
+    return ref_zero() is not None and hasattr(ref_zero(), "ref_spec_record")
+
+
+def last_ms_metric(enc):
+    """the two granules' metrics of the frame an OracleEncoder coded last, hysteresis included (every path)"""
+    v = (C.c_int * 2)()
+    lib().hxo_last_ms_metric.argtypes = [C.c_void_p, C.c_void_p]
+    lib().hxo_last_ms_metric(enc.h, v)
+    return int(v[0]), int(v[1])
+
+
+def spec_records(enc, prev, cur, bt, use_ref=False, nchan=2, want_metric=True):
+    """n granules through the front end between the polyphase filter and the allocator: prev / cur [n][2][576] the two
+    subband blocks per channel, bt [n] the block types; enc an OracleEncoder (use_ref: a RefEncoder of the same control, with
+    the channel count and whether the path forms a metric, which the reference's objects do not tell).  -> dict of copies:
+    xr [n][2][576], metric [n] (before hysteresis), esave [n][2][64], sm [n][2][36][2], and from the oracle etab and thr
+    [n][2][64] in the kernels' layout"""
+    prev, cur = (np.ascontiguousarray(a, dtype=np.float32) for a in (prev, cur))
+    n = prev.shape[0]
+    assert prev.shape == cur.shape == (n, 2, 576) and len(bt) == n
+    out = dict(xr=np.zeros((n, 2, 576), np.float32), etab=np.zeros((n, 2, 64), np.float32), thr=np.zeros((n, 2, 64), np.float32),
+               metric=np.zeros(n, np.int32), esave=np.zeros((n, 2, 64), np.float32), sm=np.zeros((n, 2, 36, 2), np.float32))
+    V = C.c_void_p
+    if use_ref:
+        f = enc.r.ref_spec_record       # (the build the RefEncoder was made with: the plain one or ref_zero's)
+        f.argtypes, f.restype = [V, V, V, C.c_int, C.c_int, C.c_int, V, V, V, V], None
+        for r in range(n):
+            f(enc.h, prev[r].ctypes.data, cur[r].ctypes.data, int(bt[r]), int(nchan), int(want_metric), out["xr"][r].ctypes.data,
+              out["esave"][r].ctypes.data, out["sm"][r].ctypes.data, out["metric"][r:].ctypes.data)
+        return out
+    f = lib().hxo_spec_record
+    f.argtypes, f.restype = [V, V, V, C.c_int, V, V, V, V, V, V], None
+    for r in range(n):
+        f(enc.h, prev[r].ctypes.data, cur[r].ctypes.data, int(bt[r]), out["xr"][r].ctypes.data, out["etab"][r].ctypes.data,
+          out["thr"][r].ctypes.data, out["metric"][r:].ctypes.data, out["esave"][r].ctypes.data, out["sm"][r].ctypes.data)
+    return out

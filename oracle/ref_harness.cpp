@@ -305,6 +305,51 @@ void ref_isf2_record(void *h, const int *hdr, float *xr, int *ix, const int *ban
     }
     memcpy((void *) b, saved.data(), sizeof(*b));
 }
+/* The reference's front end between the polyphase filter and the allocator on one granule of the caller's (tests/spec_cases.py;
+ * pins hxo_spec_record, oracle/hxo.h, which documents the arguments): FreqInvert on copies of the two blocks per channel,
+ * hybridLong + antialias or hybridShort with the encoder's nsb_limitMS[0], the allocator object's ms_correlation2 (CBitAllo3's,
+ * with ms_correlation_memory zeroed around the call, or CBitAllo1's) when want_metric, then L3acousticQuick - emapLong +
+ * spd_smrLongEcho or emapShort + spd_smrShort with the encoder's tables - per channel on a zeroed pre-echo memory.  The
+ * reference hands out no partition table: esave [2][64] is the memory it leaves (twice the unclamped thresholds; short: twice
+ * window 2's sums), sm [2][36][2] the {sig, mask} pairs.  The encoder's members are put back. */
+void ref_spec_record(void *h, const float *prev, const float *cur, int bt, int nchan, int want_metric, float *xr, float *esave, float *sm, int *metric)
+{
+    CMp3Enc *e = (CMp3Enc *) h;
+    const int nsb = e->nsb_limitMS[0];
+    float a[576], b[576], xr_saved[2][576], ec_saved[2][2][64], eng_saved[3][64];
+    SIG_MASK sm_saved[2][36];
+    memset(xr, 0, 2 * 576 * sizeof(float));
+    memset(esave, 0, 2 * 64 * sizeof(float));
+    memset(sm, 0, 2 * 72 * sizeof(float));
+    for (int ch = 0; ch < nchan; ch++) {
+        memcpy(a, prev + 576 * ch, sizeof a);
+        memcpy(b, cur + 576 * ch, sizeof b);
+        FreqInvert(a, nsb);
+        FreqInvert(b, nsb);
+        if (bt != 2) { hybridLong(a, b, xr + 576 * ch, bt, nsb, 1); antialias(xr + 576 * ch, nsb); }
+        else hybridShort(a, b, xr + 576 * ch, nsb);
+    }
+    *metric = 0;
+    if (want_metric) {
+        CBitAllo3 *b3 = dynamic_cast<CBitAllo3 *>(e->BitAllo);
+        const int mem = b3 ? b3->ms_correlation_memory : 0;
+        if (b3) b3->ms_correlation_memory = 0;
+        *metric = e->BitAllo->ms_correlation2((float (*)[576]) xr, bt);
+        if (b3) b3->ms_correlation_memory = mem;
+    }
+    memcpy(xr_saved, e->xr[0], sizeof xr_saved); memcpy(ec_saved, e->ecsave, sizeof ec_saved);
+    memcpy(eng_saved, e->eng, sizeof eng_saved); memcpy(sm_saved, e->sig_mask, sizeof sm_saved);
+    for (int ch = 0; ch < nchan; ch++) {
+        memcpy(e->xr[0][ch], xr + 576 * ch, 576 * sizeof(float));
+        memset(e->ecsave[ch][0], 0, 64 * sizeof(float));
+        memset(e->sig_mask[ch], 0, sizeof(e->sig_mask[ch]));
+        e->L3acousticQuick(ch, 0, bt, 0);
+        memcpy(esave + 64 * ch, e->ecsave[ch][0], 64 * sizeof(float));
+        for (int i = 0; i < 36; i++) { sm[72 * ch + 2 * i] = e->sig_mask[ch][i].sig; sm[72 * ch + 2 * i + 1] = e->sig_mask[ch][i].mask; }
+    }
+    memcpy(e->xr[0], xr_saved, sizeof xr_saved); memcpy(e->ecsave, ec_saved, sizeof ec_saved);
+    memcpy(e->eng, eng_saved, sizeof eng_saved); memcpy(e->sig_mask, sm_saved, sizeof sm_saved);
+}
 /* the three quantisers on one run of lines (rule 0 = vect_quant, 1 = vect_quantB, 2 = vect_quantB2 at -0.30); returns the maximum */
 int ref_quant_lines(int rule, float *x34, int *ix, int gsf, int n)
 {
