@@ -500,6 +500,58 @@ def _pcm_segments(setter, handle, n, off, in_bytes):
         raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
 
 
+def planar_layout(nframes, channels, counts=None, f32=False):
+    """the tight planar layout of a call's PCM image (hx_pcm_planar_layout; host only): stream i's channels[i] planes of
+    counts[i] (None: nframes) frames back to back, the streams back to back -> (offsets int64 [n + 1], chan_stride int64 [n],
+    the image's bytes = offsets[n])"""
+    ch = [int(c) for c in channels]
+    n = len(ch)
+    off, stride = np.zeros(n + 1, dtype=np.int64), np.zeros(max(n, 1), dtype=np.int64)
+    total = int(lib().hx_pcm_planar_layout(n, int(nframes), _counts_array(n, counts), (C.c_int * max(n, 1))(*ch), 4 if f32 else 2, off.ctypes.data,
+                                           stride.ctypes.data))
+    if total < 0:
+        raise ValueError("hx_pcm_planar_layout: bad arguments (channels 1 or 2, counts within 0 .. nframes)")
+    return off, stride[:n], total
+
+
+def _pcm_planes(setter, handle, n, off, chan_stride, in_bytes, unit_scale):
+    if off is not None:
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        if len(off) not in (n, n + 1):
+            raise ValueError("PCM planes: %d offsets for %d streams" % (len(off), n))
+        if chan_stride is not None:
+            chan_stride = np.ascontiguousarray(chan_stride, dtype=np.int64).reshape(-1)
+            if len(chan_stride) != n:
+                raise ValueError("PCM planes: %d strides for %d streams" % (len(chan_stride), n))
+    if setter(handle, None if off is None else off.ctypes.data, None if off is None or chan_stride is None else chan_stride.ctypes.data,
+              int(in_bytes), int(unit_scale)) != 0:
+        raise RuntimeError("%s failed: %s" % (setter.__name__, last_error()))
+
+
+def tensor_planes(shape, strides, itemsize):
+    """the PCM planes of a waveform tensor [S, C, T] or [S, T], from its shape and its strides in elements alone (nothing of
+    the tensor is read or copied) -> (off int64 [S], chan_stride int64 [S], in_bytes, first): byte offsets and strides for
+    pcm_planes, relative to the lowest element the tensor addresses, which lies `first` elements from element [0, .. 0] (0
+    unless a stride is negative).  T must be a positive multiple of 1152 and the last dimension's stride 1."""
+    shape, strides = [int(v) for v in shape], [int(v) for v in strides]
+    if len(shape) == 2:
+        shape, strides = [shape[0], 1, shape[1]], [strides[0], 0, strides[1]]
+    if len(shape) != 3 or len(strides) != 3:
+        raise ValueError("a waveform is [streams, channels, time] or [streams, time], not %d-dimensional" % len(shape))
+    S, Cn, T = shape
+    if Cn not in (1, 2):
+        raise ValueError("a waveform has 1 or 2 channels, not %d" % Cn)
+    if T <= 0 or T % 1152 != 0:
+        raise ValueError("a waveform's time dimension must be a positive multiple of 1152, not %d" % T)
+    if strides[2] != 1:
+        raise ValueError("the last (time) dimension of a waveform must have stride 1, not %d: planes are consecutive samples" % strides[2])
+    start = [s * strides[0] + c * strides[1] for s in range(S) for c in range(Cn)]
+    first = min(start) if start else 0
+    off = np.array([(s * strides[0] - first) * itemsize for s in range(S)], dtype=np.int64)
+    chan_stride = np.full(S, strides[1] * itemsize, dtype=np.int64)
+    return off, chan_stride, ((max(start) - first + T) if start else 0) * itemsize, first
+
+
 def _pcm_image(image):
     """-> a host call's flat PCM image as the C ABI takes it: contiguous int16 or float32 (at int16 scale), any shape"""
     f32 = np.asarray(image).dtype == np.float32
@@ -549,7 +601,7 @@ class Batch:
             self.h = L.hx_batch_create(device, self.n, arr, 0, max_frames)
         if not self.h:
             raise RuntimeError("hx_batch_create failed: " + last_error())
-        self.max_frames = max_frames
+        self.max_frames, self.device = max_frames, int(device)
 
     @classmethod
     def menu(cls, controls, nstreams, cfg=None, max_frames=256, device=0, sources=None):
@@ -579,7 +631,7 @@ class Batch:
         self.h = getattr(lib(), create)(device, self.n, self._ec, nmenu, self._src, arr, max_frames)
         if not self.h:
             raise RuntimeError(create + " failed: " + last_error())
-        self.max_frames = max_frames
+        self.max_frames, self.device = max_frames, int(device)
         return self
 
     def pcm_channels(self):
@@ -668,6 +720,49 @@ class Batch:
         them, is taken too) into one image of in_bytes bytes - the pcm / d_pcm argument of every encode and submit call is
         then the image's base, and stream i's input the bytes at off[i]; None = back to rows"""
         _pcm_segments(lib().hx_batch_pcm_segments, self.h, self.n, off, in_bytes)
+
+    def pcm_planes(self, off, chan_stride=None, in_bytes=0, unit_scale=False):
+        """PCM planes of the calls that follow (hx_batch_pcm_planes): off = n byte offsets (n + 1, as planar_layout returns them,
+        is taken too) of the streams' first planes in one image of in_bytes bytes, chan_stride = n byte distances to their
+        second planes (None: tight) - the pcm / d_pcm argument of every encode and submit call is then the image's base;
+        unit_scale: float32 samples are in [-1, 1) and taken as x * 32768; off None = back to rows"""
+        _pcm_planes(lib().hx_batch_pcm_planes, self.h, self.n, off, chan_stride, in_bytes, unit_scale)
+
+    def encode_tensor(self, waveform, d_out_ptr=None, out_stride=None, d_out_bytes_ptr=None, stream=None, unit_scale=None, stats=False, crc=False):
+        """encode a torch waveform [n, C, T] or [n, T], int16 or float32, T a multiple of 1152, where it lies: its planes are
+        derived from waveform.stride() (tensor_planes; the last dimension must have stride 1) and set with pcm_planes, which
+        stay in force.  unit_scale (None: True for float32): the samples are in [-1, 1).  A tensor on the batch's device
+        makes the device call into d_out_ptr / out_stride / d_out_bytes_ptr on `stream`, as encode_device; a host tensor
+        the host call and returns what encode_host returns (stats, crc: as there).  The waveform has as many channels as
+        the batch's rows (pcm_channels()).  Every argument is checked before the planes are set: a call that raises
+        ValueError or TypeError leaves the batch as it was"""
+        import torch
+        if waveform.dtype not in (torch.int16, torch.float32):
+            raise TypeError("encode_tensor takes an int16 or float32 waveform, not %s" % waveform.dtype)
+        f32 = waveform.dtype == torch.float32
+        item = 4 if f32 else 2
+        if waveform.shape[0] != self.n:
+            raise ValueError("a waveform of %d streams for a batch of %d" % (waveform.shape[0], self.n))
+        off, chan_stride, in_bytes, first = tensor_planes(waveform.shape, waveform.stride(), item)
+        nch = 1 if waveform.dim() == 2 else int(waveform.shape[1])
+        if nch != self.pcm_channels():
+            raise ValueError("a waveform of %d channel(s) for a batch whose rows have %d" % (nch, self.pcm_channels()))
+        nframes = int(waveform.shape[-1]) // 1152
+        if nframes > self.max_frames:
+            raise ValueError("a waveform of %d frames for a batch of max_frames = %d" % (nframes, self.max_frames))
+        if waveform.is_cuda:
+            if waveform.device.index != self.device:
+                raise ValueError("the waveform lies on device %s, the batch on device %d" % (waveform.device.index, self.device))
+            if d_out_ptr is None or d_out_bytes_ptr is None:
+                raise ValueError("a device waveform needs d_out_ptr and d_out_bytes_ptr, as encode_device")
+        elif waveform.device.type != "cpu":
+            raise ValueError("a waveform lies on the batch's device or on the host, not on %s" % waveform.device)
+        base = waveform.data_ptr() + first * item
+        self.pcm_planes(off, chan_stride, in_bytes, (f32 if unit_scale is None else unit_scale))
+        if waveform.is_cuda:
+            return self.encode_device(base, nframes, d_out_ptr, self.out_stride(nframes) if out_stride is None else out_stride, d_out_bytes_ptr, stream, f32=f32)
+        image = np.frombuffer((C.c_ubyte * in_bytes).from_address(base), dtype=np.float32 if f32 else np.int16)     # (a view: waveform stays alive through the call)
+        return self._encode_host(image, nframes, stats, crc)
 
     def packed_layout(self, nframes, f32=False):
         """the tight layout (api.packed_layout) of a call of nframes made now: the counts in force (frame_counts) and the
@@ -963,6 +1058,12 @@ class Batch:
             raise RuntimeError("unknown debug buffer " + name)
         return a[: n // a.itemsize]
 
+    def debug_pcm_rows(self, d_pcm_ptr, nframes, f32=False, stream=None):
+        """the row kernel of a call under pcm_segments / pcm_planes alone (hx_batch_debug_pcm_rows): fills the row buffer from
+        the device image at d_pcm_ptr and runs nothing behind it; read the rows with debug_read("pcmrows", ...)"""
+        if lib().hx_batch_debug_pcm_rows(self.h, d_pcm_ptr, nframes, int(f32), stream) != 0:
+            raise RuntimeError("hx_batch_debug_pcm_rows failed: " + last_error())
+
     def debug_math(self, name, *arrays):
         """the kernels' device function `name` (hx_batch_debug_math) on equally long arrays of 32-bit values, one per
         operand: uint32 [n], the result's 32-bit patterns (view them as float32 or int32); at most 2^25 arguments a call"""
@@ -1007,7 +1108,7 @@ class SrcBatch(Batch):
         self.h = L.hx_batch_create_src(device, self.n, ec_arg, shared_ec, src_arg, shared_src, max_frames)
         if not self.h:
             raise RuntimeError("hx_batch_create_src failed: " + last_error())
-        self.max_frames = max_frames
+        self.max_frames, self.device = max_frames, int(device)
 
     @classmethod
     def menu(cls, controls, sources, nstreams, cfg=None, max_frames=256, device=0):
@@ -1248,6 +1349,10 @@ class Multi:
     def pcm_segments(self, off, in_bytes=0):
         """as Batch.pcm_segments, over all streams: the offsets address the caller's one image (hx_multi_pcm_segments)"""
         _pcm_segments(lib().hx_multi_pcm_segments, self.h, self.n, off, in_bytes)
+
+    def pcm_planes(self, off, chan_stride=None, in_bytes=0, unit_scale=False):
+        """as Batch.pcm_planes, over all streams: offsets and strides address the caller's one image (hx_multi_pcm_planes)"""
+        _pcm_planes(lib().hx_multi_pcm_planes, self.h, self.n, off, chan_stride, in_bytes, unit_scale)
 
     def packed_layout(self, nframes, f32=False):
         """as Batch.packed_layout, over all streams"""

@@ -405,7 +405,7 @@ extern "C" int hx_batch_frame_counts(hx_batch *b, const int *nfr)
 
 // PCM segments of the calls that follow.  Like the counts, only the host copy changes here: a call checks it against its
 // nframes, its sample size and the counts and channels as of the call (check_segments) and uploads it for itself
-// (upload_segments), so what is set later never reaches a call already made.
+// (upload_image), so what is set later never reaches a call already made.
 extern "C" long long hx_pcm_packed_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off)
 {
     if (nstreams < 0 || nframes < 0 || !off || !channels || (sample_bytes != 2 && sample_bytes != 4)) return -1;
@@ -419,11 +419,11 @@ int segs_reserve(hx_batch *b, bool buffers)
 {
     if (!b) { set_err("null batch"); return -1; }
     if (b->nsrc) { set_err("a converting batch takes no PCM segments: its input is per stream already (in_stride, frame_off)"); return -1; }
-    if (!buffers || b->seg_stage.d) return 0;
+    if (!buffers || b->img_stage.d) return 0;
     int dev0 = -1;
     HIPCHK(hipGetDevice(&dev0));
     HIPCHK(hipSetDevice(b->device));
-    const int rc = staging_make(b, b->seg_stage, sizeof(long long) * (size_t) b->S);
+    const int rc = staging_make(b, b->img_stage, planes_stage_bytes(b));       // (the wider of the two layouts)
     (void) hipSetDevice(dev0);
     return rc;
 }
@@ -433,6 +433,7 @@ extern "C" int hx_batch_pcm_segments(hx_batch *b, const long long *off, long lon
     if (off && in_bytes < 0) { set_err("in_bytes < 0"); return -1; }
     if (off) { b->seg_off.assign(off, off + b->S); b->seg_bytes = in_bytes; }
     else { b->seg_off.clear(); b->seg_bytes = 0; }
+    b->pl_off.clear(); b->pl_stride.clear(); b->pl_bytes = 0; b->pl_unit = false;       // (segments and planes exclude each other)
     return 0;
 }
 int check_segments(const hx_batch *b, int nframes, int sample_bytes, int first)
@@ -448,6 +449,62 @@ int check_segments(const hx_batch *b, int nframes, int sample_bytes, int first)
             snprintf(msg, sizeof msg, "stream %d: PCM segment at offset %lld (%lld bytes, in_bytes = %lld) %s", first + i, o, n, b->seg_bytes, what);
             set_err("%s", msg);
             return -1;
+        }
+    }
+    return 0;
+}
+
+// PCM planes of the calls that follow: segments' sibling (include/hmp3_amd.h, "PCM planes").  Only the host copy changes
+// here; a call checks it (check_planes) and uploads offsets and strides for itself (upload_image).
+extern "C" long long hx_pcm_planar_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off,
+                                          long long *chan_stride)
+{
+    if (nstreams < 0 || nframes < 0 || !off || !chan_stride || !channels || (sample_bytes != 2 && sample_bytes != 4)) return -1;
+    for (int i = 0; i < nstreams; i++)
+        if ((channels[i] != 1 && channels[i] != 2) || (nfr && (nfr[i] < 0 || nfr[i] > nframes))) return -1;
+    off[0] = 0;
+    for (int i = 0; i < nstreams; i++) {
+        chan_stride[i] = (long long) (nfr ? nfr[i] : nframes) * 1152 * sample_bytes;
+        off[i + 1] = off[i] + chan_stride[i] * channels[i];
+    }
+    return off[nstreams];
+}
+int planes_args(const long long *off, long long in_bytes, int unit_scale)
+{
+    if (off && in_bytes < 0) { set_err("in_bytes < 0"); return -1; }
+    if (off && unit_scale != 0 && unit_scale != 1) { set_err("unit_scale must be 0 (int16 scale) or 1 (x * 32768.0f)"); return -1; }
+    return 0;
+}
+extern "C" int hx_batch_pcm_planes(hx_batch *b, const long long *off, const long long *chan_stride, long long in_bytes, int unit_scale)
+{
+    if (segs_reserve(b, off != nullptr) != 0 || planes_args(off, in_bytes, unit_scale) != 0) return -1;
+    b->seg_off.clear(); b->seg_bytes = 0;               // (segments and planes exclude each other)
+    b->pl_off.clear(); b->pl_stride.clear(); b->pl_bytes = 0; b->pl_unit = false;
+    if (!off) return 0;
+    b->pl_off.assign(off, off + b->S);
+    if (chan_stride) b->pl_stride.assign(chan_stride, chan_stride + b->S);
+    b->pl_bytes = in_bytes; b->pl_unit = unit_scale == 1;
+    return 0;
+}
+int check_planes(const hx_batch *b, int nframes, int sample_bytes, int first)
+{
+    if (!b || b->pl_off.empty()) return 0;
+    if (b->pl_unit && sample_bytes != 4) { set_err("an s16 call under PCM planes with unit_scale = 1: unit scale is defined for fp32 samples only"); return -1; }
+    for (int i = 0; i < b->S; i++) {
+        const long long n = plane_len(b, i, nframes, sample_bytes), d = plane_stride(b, i, nframes, sample_bytes);
+        if (n <= 0) continue;
+        for (int c = 0; c < b->params[b->cls_of[i]].nchan; c++) {
+            // (offset and stride are the caller's: a sum that leaves the i64 range is refused like any other start outside the image)
+            long long o = 0;
+            const bool wild = __builtin_add_overflow(b->pl_off[i], c * d, &o);
+            const char *what = wild ? "lies outside the image" : o < 0 ? "starts below 0" : (o % sample_bytes) != 0 ? "is no multiple of the call's sample size" :
+                               (n > b->pl_bytes || o > b->pl_bytes - n) ? "ends beyond in_bytes" : nullptr;
+            if (what) {
+                char msg[224];
+                snprintf(msg, sizeof msg, "stream %d channel %d: PCM plane at offset %lld (%lld bytes, in_bytes = %lld) %s", first + i, c, o, n, b->pl_bytes, what);
+                set_err("%s", msg);
+                return -1;
+            }
         }
     }
     return 0;
@@ -687,7 +744,8 @@ struct Pass {
     int set = 0, sset = 0;              // buffer set; set of signs (also read by the packing, which may still be busy with
                                         // submit n-2 when the front end of submit n writes them: three sets in rotation)
     int flushed_set = -1;               // the buffer set of a deferred packing that pipe_enter sent out
-    const long long *d_seg = nullptr;   // under PCM segments: the device copy of the call's offsets, relative to in.p (upload_segments)
+    const long long *d_img = nullptr;   // under PCM segments: the device copy of the call's offsets, relative to in.p (upload_image);
+                                        // under PCM planes: of its offsets and strides, [2][S]
 };
 
 int order_behind_submits(hx_batch *b, hipStream_t q)
@@ -757,29 +815,35 @@ static int upload_counts(hx_batch *b, Pass &p)
     return p.kind == PASS_PLAIN ? counts_upload_plain(b, p.q, p.call.nfr) : counts_upload(b, p.sset, p.q, p.call.nfr);
 }
 
-// The call's PCM segments to the device, like its counts and in their rotation: through page-locked staging into copy k of
+// The call's PCM segments - or its planes' offsets and strides - to the device, like its counts and in their rotation: through page-locked staging into copy k of
 // three on the stream the front end runs on, where k_pcm_spread - the only reader - follows.  The same two notes apply: the
 // host may wait for the upload of the call three before, and the call is not made under stream capture.  What goes up is
 // relative to the pointer the kernel gets (PcmIn::shift); the offset of a stream that takes no frame is not looked at.
-static int upload_segments(hx_batch *b, Pass &p)
+static int upload_image(hx_batch *b, Pass &p)
 {
-    if (!p.in.seg) return 0;
-    Staging &s = b->seg_stage;
-    const int k = p.kind == PASS_PLAIN ? (int) (b->nplain_seg++ % 3) : p.sset;
+    if (!p.in.image()) return 0;
+    Staging &s = b->img_stage;
+    const int k = p.kind == PASS_PLAIN ? (int) (b->nplain_img++ % 3) : p.sset;
     long long *h = (long long *) staging_take(s, k);
     if (!h) return -1;
-    for (int i = 0; i < b->S; i++) h[i] = seg_len(b, i, p.nframes, p.in.sample_bytes()) > 0 ? p.in.seg[i] - p.in.shift : 0;
-    if (staging_upload(s, k, s.bytes, p.q) != 0 || staging_done(s, k, p.q) != 0) return -1;
-    p.d_seg = s.dev<long long>(k);
+    if (p.in.seg)
+        for (int i = 0; i < b->S; i++) h[i] = seg_len(b, i, p.nframes, p.in.sample_bytes()) > 0 ? p.in.seg[i] - p.in.shift : 0;
+    else    // (planes: the host fills in the stride of a mono stream and of a stream that takes no frame)
+        for (int i = 0; i < b->S; i++) {
+            h[i] = plane_len(b, i, p.nframes, p.in.sample_bytes()) > 0 ? p.in.pl[i] - p.in.shift : 0;
+            h[b->S + i] = plane_stride(b, i, p.nframes, p.in.sample_bytes());
+        }
+    if (staging_upload(s, k, p.in.seg ? segs_stage_bytes(b) : planes_stage_bytes(b), p.q) != 0 || staging_done(s, k, p.q) != 0) return -1;
+    p.d_img = s.dev<long long>(k);
     return 0;
 }
-// ... and the row buffer of a call under segments, before the pass touches anything: made at the first such call, grown
+// ... and the row buffer of a call under segments or planes, before the pass touches anything: made at the first such call, grown
 // behind a drain (an earlier call's front end may still read it)
 static int rows_reserve(hx_batch *b, PcmIn in, int nframes)
 {
     const long long need = in.bytes(b->S, nframes, b->nchan);
     const long long chunks = (in.bytes(1, nframes, b->nchan) + HX_PCM_CHUNK - 1) / HX_PCM_CHUNK;
-    if ((long long) b->S * chunks > INT_MAX) { set_err("nstreams * nframes too large for a call under PCM segments: split the call"); return -1; }
+    if ((long long) b->S * chunks > INT_MAX) { set_err("nstreams * nframes too large for a call under PCM segments or planes: split the call"); return -1; }
     if (need <= b->rows_cap) return 0;
     HIPCHK(hipSetDevice(b->device));
     if (b->rows_cap > 0 && drain(b) != 0) return -1;
@@ -801,6 +865,25 @@ static int launch_spec(hipStream_t q, bool direct, const float *sb, const HxStre
     return 0;
 }
 
+// K-1, the head of the front end under segments or planes: k_pcm_spread or k_pcm_planes (hx_pcmin.hip) fills the row buffer
+// from the call's image on stream p.q, behind the upload of the image's layout (upload_image).  A call fed rows: nothing.
+static int launch_rows(hx_batch *b, const Pass &p)
+{
+    if (!p.d_img) return 0;
+    const int S = b->S, nframes = p.nframes;
+    const long long row_bytes = p.in.bytes(1, nframes, b->nchan);
+    const int chunks = (int) ((row_bytes + HX_PCM_CHUNK - 1) / HX_PCM_CHUNK);
+    const dim3 grid((unsigned) ((long long) S * chunks));
+    if (p.in.pl)
+        LAUNCH(k_pcm_planes, grid, dim3(256), p.q, (const unsigned char *) p.in.p, p.d_img, S, b->d_rows, row_bytes, nframes, p.in.sample_bytes(), (int) p.in.unit,
+               (const HxStream *) b->d_st, (const HxParams *) b->d_prm, p.call.nfr, chunks);
+    else
+        LAUNCH(k_pcm_spread, grid, dim3(256), p.q, (const unsigned char *) p.in.p, p.d_img, b->d_rows, row_bytes, nframes, p.in.sample_bytes(),
+               (const HxStream *) b->d_st, (const HxParams *) b->d_prm, p.call.nfr, chunks);
+    b->rows_bytes = row_bytes * S;
+    return 0;
+}
+
 // the front end: PCM to spectra, psy data and the allocator's start values, into front[set] and sgn[sset]
 static int launch_front(hx_batch *b, const Pass &p)
 {
@@ -808,16 +891,9 @@ static int launch_front(hx_batch *b, const Pass &p)
     const hipStream_t q = p.q;
     const int S = b->S, nframes = p.nframes, NG = 2 * nframes;
     const long long nsamp = 1152LL * nframes;
-    // under segments: the rows come from k_pcm_spread (hx_pcmin.hip), and the kernels below read them in place of the caller's pointer
-    const void *pcm = p.in.p;
-    if (p.d_seg) {
-        const long long row_bytes = p.in.bytes(1, nframes, b->nchan);
-        const int chunks = (int) ((row_bytes + HX_PCM_CHUNK - 1) / HX_PCM_CHUNK);
-        LAUNCH(k_pcm_spread, dim3((unsigned) ((long long) S * chunks)), dim3(256), q, (const unsigned char *) p.in.p, p.d_seg, b->d_rows, row_bytes, nframes,
-               p.in.sample_bytes(), (const HxStream *) b->d_st, (const HxParams *) b->d_prm, p.call.nfr, chunks);
-        b->rows_bytes = row_bytes * S;
-        pcm = b->d_rows;
-    }
+    // under segments or planes: the rows come from K-1 (launch_rows), and the kernels below read them in place of the caller's pointer
+    if (launch_rows(b, p) != 0) return -1;
+    const void *pcm = p.d_img ? b->d_rows : p.in.p;
     const int16_t *d_pcm = p.in.f32 ? nullptr : (const int16_t *) pcm;
     const float *d_pcm32 = p.in.f32 ? (const float *) pcm : nullptr;
     // The subband carry sits in slots NG_prev..NG_prev+2 only if the previous call used another
@@ -988,12 +1064,12 @@ static void reap_timings(hx_batch *b)
 
 int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
-    if (in.seg && rows_reserve(b, in, nframes) != 0) return -1;
+    if (in.image() && rows_reserve(b, in, nframes) != 0) return -1;
     Poison poison{b};
     Pass p = {in, nframes, c, kind, (hipStream_t) stream, (hipStream_t) stream};
     AllocArgs a;
     HIPCHK(hipSetDevice(b->device));
-    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || upload_segments(b, p) != 0 || launch_front(b, p) != 0) return -1;
+    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || upload_image(b, p) != 0 || launch_front(b, p) != 0) return -1;
     if (kind != PASS_PLAIN && pipe_front_done(b, p) != 0) return -1;
     if (fill_alloc_args(b, p, a) != 0 || launch_walk(b, p, a) != 0 || place_pack(b, p) != 0) return -1;
     if (!c.recording) reap_timings(b);
@@ -1008,8 +1084,28 @@ int encode_pass(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream,
 int encode_checked(hx_batch *b, PcmIn in, int nframes, const Call &c, void *stream, PassKind kind)
 {
     if (check_call(b, in.p, nframes, c.out, c.out_stride, c.out_bytes) != 0 || check_opt(b, c.opt, counts_in_force(b)) != 0 ||
-        check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
+        check_image(b, nframes, in.sample_bytes(), 0) != 0) return -1;
     return encode_pass(b, in, nframes, c, stream, kind);
+}
+
+// K-1 alone (include/hmp3_amd.h, hx_batch_debug_pcm_rows): a plain device call's checks, its layout upload and its row
+// kernel, and nothing behind them - no stream moves, no output is written; the rows are read with the "pcmrows" tap.
+extern "C" int hx_batch_debug_pcm_rows(hx_batch *b, const void *d_pcm, int nframes, int f32, void *stream)
+{
+    if (!b) { set_err("null batch"); return -1; }
+    if (check_poisoned(b) != 0) return -1;
+    if (b->nsrc) { set_err("a converting batch has no PCM rows of its own"); return -1; }
+    if (!d_pcm) { set_err("null buffer"); return -1; }
+    if (nframes <= 0 || nframes > b->maxF) { set_err("nframes out of range (1 .. max_frames)"); return -1; }
+    const PcmIn in = pcm_in(b, d_pcm, f32 != 0);
+    if (!in.image()) { set_err("hx_batch_debug_pcm_rows needs PCM segments or PCM planes in force"); return -1; }
+    if (check_counts(b, nframes, 0) != 0 || check_image(b, nframes, in.sample_bytes(), 0) != 0 || rows_reserve(b, in, nframes) != 0) return -1;
+    Poison poison{b};
+    Pass p = {in, nframes, Call(), PASS_PLAIN, (hipStream_t) stream, (hipStream_t) stream};
+    HIPCHK(hipSetDevice(b->device));
+    if (pipe_enter(b, p) != 0 || upload_counts(b, p) != 0 || upload_image(b, p) != 0 || launch_rows(b, p) != 0) return -1;
+    HIPCHK(hipGetLastError());
+    return poison.ok();
 }
 
 extern "C" int hx_batch_encode_s16_device(hx_batch *b, const int16_t *d_pcm, int nframes, unsigned char *d_out,
@@ -1073,12 +1169,12 @@ extern "C" void hx_pinned_free(void *p) { if (p) hipHostFree(p); }
 static int submit_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long long out_stride, int *out_bytes, const DenseOut *img = nullptr)
 {
     if (check_call(b, in.p, nframes, img ? img->buf : out, out_stride, out_bytes) != 0 || check_opt(b, b->opt, counts_in_force(b)) != 0 ||
-        check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
+        check_image(b, nframes, in.sample_bytes(), 0) != 0) return -1;
     // (under segments: the span of the image its segments cover, as in encode_host; the staging is sized by what goes up)
     in = pcm_in(b, in.p, in.f32);
     long long lo = 0, hi = in.bytes(b->S, nframes, b->nchan);
-    if (in.seg) seg_span(b, nframes, in.sample_bytes(), lo, hi);
-    if (in.seg && rows_reserve(b, in, nframes) != 0) return -1;
+    if (in.image()) image_span(b, in, nframes, lo, hi);
+    if (in.image() && rows_reserve(b, in, nframes) != 0) return -1;
     Poison poison{b};                   // (staging buffers, events and the call counter are touched from here on)
     HIPCHK(hipSetDevice(b->device));
     const long long pbytes = hi - lo, obytes = (long long) b->S * out_stride;
@@ -1212,11 +1308,11 @@ int encode_host(hx_batch *b, PcmIn in, int nframes, unsigned char *out, long lon
 {
     if (check_call(b, in.p, nframes, hd ? hd->dense : out, out_stride, out_bytes, !files) != 0) return -1;
     if (hd && (!hd->off || hd->cap < 0)) { set_err("null buffer"); return -1; }
-    if (check_segments(b, nframes, in.sample_bytes(), 0) != 0) return -1;
-    // under segments one span of the image goes up, from the lowest segment start to the highest segment end; rows: all of them
+    if (check_image(b, nframes, in.sample_bytes(), 0) != 0) return -1;
+    // under segments or planes one span of the image goes up, from the lowest segment (plane) start to the highest end; rows: all of them
     in = pcm_in(b, in.p, in.f32);
     long long lo = 0, hi = in.bytes(b->S, nframes, b->nchan);
-    if (in.seg) seg_span(b, nframes, in.sample_bytes(), lo, hi);
+    if (in.image()) image_span(b, in, nframes, lo, hi);
     return host_call(b, (const char *) in.p + lo, hi - lo, false, nframes, out, out_stride, out_bytes, stats, [&](const Call &c) {
         PcmIn up = in;
         up.p = b->d_in; up.shift = lo;
@@ -1391,7 +1487,7 @@ extern "C" long long hx_batch_debug_read(hx_batch *b, const char *name, void *ds
     else if (k == "prof" && b->d_prof) { src = b->d_prof; n = sizeof(unsigned long long) * S * HX_PROF_WORDS; }
     else if (k == "state") { src = b->d_st; n = sizeof(HxStream) * S; }
     else if (k == "srcpcm" && b->d_src_pcm) { src = b->d_src_pcm; n = sizeof(float) * S * b->src_lastF * 1152 * b->nchan; }   // the converted PCM of the last call
-    else if (k == "pcmrows" && b->d_rows) { src = b->d_rows; n = b->rows_bytes; }      // the row buffer as the last call under PCM segments left it (its stride: that call's nframes and sample type)
+    else if (k == "pcmrows" && b->d_rows) { src = b->d_rows; n = b->rows_bytes; }      // the row buffer as the last call under PCM segments or planes left it (its stride: that call's nframes and sample type)
     else if (k == "attack" && b->d_dbgmetric) { src = b->d_dbgmetric; n = sizeof(int) * S * NG * 4; }      // [S][NG][4]: the attack metric of channel 0 / 1 for short_flag_prev = 0, then for 1
     if (!src) return -1;
     if (n > cap) n = cap;

@@ -328,6 +328,18 @@ extern "C" int hx_multi_pcm_segments(hx_multi *m, const long long *off, long lon
     return 0;
 }
 
+// hx_batch_pcm_planes over all streams, the same way
+extern "C" int hx_multi_pcm_planes(hx_multi *m, const long long *off, const long long *chan_stride, long long in_bytes, int unit_scale)
+{
+    if (!m) { set_err("null handle"); return -1; }
+    for (hx_batch *b : m->part) if (segs_reserve(b, off != nullptr) != 0) return -1;
+    if (planes_args(off, in_bytes, unit_scale) != 0) return -1;
+    for (size_t k = 0; k < m->part.size(); k++)
+        if (hx_batch_pcm_planes(m->part[k], off ? off + m->first[k] : nullptr, off && chan_stride ? chan_stride + m->first[k] : nullptr, in_bytes, unit_scale) != 0)
+            return -1;      // (cannot fail any more)
+    return 0;
+}
+
 // Argument checks of the calls over all devices, the per-stream frame counts of every block included: a call that one
 // block would refuse for its counts starts on no block, and its message names the stream by the caller's number.
 // Then fn(k) on one thread per device, bound to the CPUs next to it.
@@ -377,10 +389,10 @@ static int multi_encode_host(hx_multi *m, PcmIn in, int nframes, unsigned char *
     // PCM segments: checked for all blocks, with the caller's stream numbers, before one starts - behind the counts, which
     // a segment's length comes from (an nframes out of range is multi_fanout's to refuse); each block then gets the image's
     // base and copies its own span
-    const bool segs = m && !m->part[0]->seg_off.empty();
+    const bool segs = m && (!m->part[0]->seg_off.empty() || !m->part[0]->pl_off.empty());      // (segments or planes: one image)
     if (segs && nframes > 0 && nframes <= m->part[0]->maxF)
         for (size_t k = 0; k < m->part.size(); k++)
-            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_segments(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
+            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_image(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
     return multi_fanout(m, in.p && out && out_bytes, nframes, out_stride, [&](size_t k) {
         const long long f = m->first[k];
         const char *p = (const char *) in.p + (segs ? 0 : in.bytes(f, nframes, m->nchan));
@@ -562,10 +574,10 @@ static int multi_check_files(const hx_multi *m)
 static int multi_encode_host_files(hx_multi *m, PcmIn in, int nframes)
 {
     if (multi_check_files(m) != 0) return -1;
-    const bool segs = !m->part[0]->seg_off.empty();
+    const bool segs = !m->part[0]->seg_off.empty() || !m->part[0]->pl_off.empty();
     if (segs && nframes > 0 && nframes <= m->part[0]->maxF)
         for (size_t k = 0; k < m->part.size(); k++)
-            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_segments(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
+            if (check_counts(m->part[k], nframes, m->first[k]) != 0 || check_image(m->part[k], nframes, in.sample_bytes(), m->first[k]) != 0) return -1;
     std::vector<int> st(m->part.size(), 0);
     const int rc = multi_fanout(m, in.p != nullptr, nframes, hx_multi_out_stride(m, nframes), [&](size_t k) {
         const char *p = (const char *) in.p + (segs ? 0 : in.bytes(m->first[k], nframes, m->nchan));

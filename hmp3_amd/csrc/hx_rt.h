@@ -71,6 +71,8 @@ __global__ void k_ledger_begin(HX_LEDGER *led, const HxLedgerEntry *ent);
 __global__ void k_ledger_gather(const HX_LEDGER *led, const HxLedgerEntry *ent, HX_LEDGER *out);
 __global__ void k_pcm_spread(const unsigned char *img, const long long *off, unsigned char *rows, long long row_bytes, int nframes, int sample_bytes,
                              const HxStream *st, const HxParams *prm, const int *nfr, int chunks);
+__global__ void k_pcm_planes(const unsigned char *img, const long long *pl, int S, unsigned char *rows, long long row_bytes, int nframes, int sample_bytes,
+                             int unit, const HxStream *st, const HxParams *prm, const int *nfr, int chunks);
 __global__ void k_file_append(const HX_LEDGER *led, uint2 *fw, unsigned char *img, long long pitch, long long cap, const unsigned char *out, long long out_stride,
                               const int *nfr, int nframes, int chunks, int *status);
 __global__ void k_file_begin(uint2 *fw, const HxLedgerEntry *ent, int n, unsigned on);
@@ -206,14 +208,22 @@ struct hx_batch {
     long long nplain = 0;               // plain calls made under counts (they rotate the copies too: no call waits for its predecessor's upload)
     // PCM segments (hx_batch_pcm_segments): the host copy a call checks and takes - seg_off [S] byte offsets into the call's
     // image of seg_bytes bytes, empty = rows - and its staging, [S] offsets per copy, in the rotation of the counts' (a
-    // submit: the copy of its set of signs; plain calls: their own count, nplain_seg).  d_rows: the row buffer k_pcm_spread
+    // submit: the copy of its set of signs; plain calls: their own count, nplain_img).  d_rows: the row buffer k_pcm_spread
     // fills and the front end reads in place of the caller's pointer, [S][nframes * 1152 * P] samples of the call's type; one
     // for all pass kinds (the front end's stream is in order), made at the first call under segments and grown behind a
-    // drain.  rows_bytes: what the last call under segments used of it (the "pcmrows" tap).
+    // drain.  rows_bytes: what the last call under segments or planes used of it (the "pcmrows" tap).
+    // PCM planes (hx_batch_pcm_planes) exclude segments and share all of this but the host copy: pl_off [S] the byte offsets of
+    // the streams' plane 0 in the image of pl_bytes bytes (empty = not in force), pl_stride [S] the byte distance from a
+    // stream's plane 0 to its plane 1 (empty = tight, the plane's own length as of the call), pl_unit: fp32 samples are at
+    // unit scale.  img_stage is sized for the planes' layout (planes_stage_bytes); a call under segments sends the first
+    // segs_stage_bytes of its copy.
     std::vector<long long> seg_off;
     long long seg_bytes = 0;
-    Staging seg_stage;
-    long long nplain_seg = 0;
+    std::vector<long long> pl_off, pl_stride;
+    long long pl_bytes = 0;
+    bool pl_unit = false;
+    Staging img_stage;
+    long long nplain_img = 0;
     unsigned char *d_rows = nullptr; long long rows_cap = 0, rows_bytes = 0;
     // converting batches (hx_batch_create_src): k_src turns each stream's source into the fp32 PCM the front end reads
     int nsrc = 0;                       // converter plans, deduplicated (0: not a converting batch)
@@ -413,17 +423,26 @@ HX_LOCAL int check_poisoned(const hx_batch *b);
 // Under PCM segments (pcm_in): p is not rows but an image, seg [S] the host's byte offsets of the streams' segments in the
 // caller's image as of the call, and p stands for byte `shift` of that image - a device call's p is the image's base, a host
 // call copies up only the span its segments cover (seg_span) and shifts by the span's start.
+// Under PCM planes: the same with pl [S] the offsets of the streams' plane 0, pl_stride [S] (null: tight) the distance to
+// plane 1, unit: an fp32 call's samples are at unit scale; the span is plane_span's.  At most one of seg and pl is set.
 struct PcmIn {
     const void *p; bool f32;
     const long long *seg = nullptr; long long shift = 0;
+    const long long *pl = nullptr, *pl_stride = nullptr; bool unit = false;
+    bool image() const { return seg || pl; }
     int sample_bytes() const { return f32 ? (int) sizeof(float) : (int) sizeof(int16_t); }
     long long bytes(long long S, int nframes, int nchan) const { return S * nframes * 1152 * nchan * (long long) sample_bytes(); }
 };
-// a call's PCM argument as the batch takes it now: rows, or the segments in force
+// a call's PCM argument as the batch takes it now: rows, or the segments or planes in force
 static inline PcmIn pcm_in(const hx_batch *b, const void *p, bool f32)
 {
     PcmIn in = {p, f32};
     if (b && !b->seg_off.empty()) in.seg = b->seg_off.data();
+    else if (b && !b->pl_off.empty()) {
+        in.pl = b->pl_off.data();
+        in.pl_stride = b->pl_stride.empty() ? nullptr : b->pl_stride.data();
+        in.unit = f32 && b->pl_unit;
+    }
     return in;
 }
 // bytes of stream i's segment in a call of nframes: its count in force (or nframes) x 1152 x its channels as of now x sample_bytes
@@ -442,6 +461,41 @@ static inline void seg_span(const hx_batch *b, int nframes, int sample_bytes, lo
         hi = std::max(hi, b->seg_off[i] + n);
     }
     if (lo > hi) lo = hi = 0;
+}
+// what a call sends up of its image's layout through img_stage: under segments [S] i64 offsets, under planes [2][S] i64,
+// offsets and then strides
+static inline size_t segs_stage_bytes(const hx_batch *b) { return sizeof(long long) * (size_t) b->S; }
+static inline size_t planes_stage_bytes(const hx_batch *b) { return 2 * sizeof(long long) * (size_t) b->S; }
+// PCM planes in force: the bytes of one plane of stream i in a call of nframes, and the distance from its plane 0 to its
+// plane 1 (0 for a mono stream and for one that takes no frame: theirs is not looked at)
+static inline long long plane_len(const hx_batch *b, int i, int nframes, int sample_bytes)
+{
+    return (long long) (b->nfr.empty() ? nframes : b->nfr[i]) * 1152 * sample_bytes;
+}
+static inline long long plane_stride(const hx_batch *b, int i, int nframes, int sample_bytes)
+{
+    const long long n = plane_len(b, i, nframes, sample_bytes);
+    if (n <= 0 || b->params[b->cls_of[i]].nchan < 2) return 0;
+    return b->pl_stride.empty() ? n : b->pl_stride[i];
+}
+// [lo, hi): from the lowest plane start to the highest plane end among the streams that take frames (none: lo = hi = 0);
+// the planes in force must have passed check_planes
+static inline void plane_span(const hx_batch *b, int nframes, int sample_bytes, long long &lo, long long &hi)
+{
+    lo = LLONG_MAX; hi = 0;
+    for (int i = 0; i < b->S; i++) {
+        const long long n = plane_len(b, i, nframes, sample_bytes), d = plane_stride(b, i, nframes, sample_bytes);
+        if (n <= 0) continue;
+        lo = std::min(lo, b->pl_off[i] + std::min(0LL, d));
+        hi = std::max(hi, b->pl_off[i] + std::max(0LL, d) + n);
+    }
+    if (lo > hi) lo = hi = 0;
+}
+// the span of the image a host call copies up under segments or planes (in.image())
+static inline void image_span(const hx_batch *b, const PcmIn &in, int nframes, long long &lo, long long &hi)
+{
+    if (in.seg) seg_span(b, nframes, in.sample_bytes(), lo, hi);
+    else plane_span(b, nframes, in.sample_bytes(), lo, hi);
 }
 // a call that writes the caller's rows and the optional outputs set on the batch (a null batch: the argument checks refuse it)
 static inline Call call_on(const hx_batch *b, unsigned char *out, long long out_stride, int *out_bytes)
@@ -475,6 +529,16 @@ HX_LOCAL int counts_upload_plain(hx_batch *b, hipStream_t q, const int *&d_nfr);
 // passed check_counts.
 HX_LOCAL int segs_reserve(hx_batch *b, bool buffers);
 HX_LOCAL int check_segments(const hx_batch *b, int nframes, int sample_bytes, int first);
+// PCM planes, the same way (none in force: 0): every plane of every stream that takes frames starts at or above 0, on a
+// multiple of the sample size, and ends within in_bytes; an s16 call under unit_scale is refused.  The message names stream
+// and channel.  planes_args: the setters' own argument checks (hx_multi: before one block is set).
+HX_LOCAL int check_planes(const hx_batch *b, int nframes, int sample_bytes, int first);
+HX_LOCAL int planes_args(const long long *off, long long in_bytes, int unit_scale);
+// both, as every PCM entry point makes them
+static inline int check_image(const hx_batch *b, int nframes, int sample_bytes, int first)
+{
+    return check_segments(b, nframes, sample_bytes, first) != 0 || check_planes(b, nframes, sample_bytes, first) != 0 ? -1 : 0;
+}
 // ... and the range check of counts that come as a call's argument (first: as for check_counts)
 HX_LOCAL int check_counts_arg(const int *nfr, int S, int nframes, int first);
 // A converting call's input extents against its rows, per stream under its count (nfr null: nframes), before anything runs;

@@ -491,6 +491,47 @@ int hx_batch_frame_counts(hx_batch *b, const int *nfr);
    Not covered: converting batches, the hx_enc_* encoder, and bench.py, which measures calls fed rows. */
 long long hx_pcm_packed_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off);
 int hx_batch_pcm_segments(hx_batch *b, const long long *off, long long in_bytes);
+/* ---- PCM planes: a call's channel planes interleaved on the GPU (no reference equivalent) ----
+   Every PCM entry point of a plain batch takes a stream's channels interleaved, floats at int16 scale.  A waveform tensor
+   is channel-major ([streams, channels, time]) and usually fp32 in [-1, 1).  With planes in force the `pcm` / `d_pcm`
+   argument of every encode and submit entry point of the batch is the base of one image of in_bytes bytes, and channel c
+   of stream i is the n_i * 1152 consecutive samples at pcm + off[i] + c * chan_stride[i]:
+     n_i = the frame count in force (hx_batch_frame_counts) or nframes, c < hx_batch_stream_channels(b, i) as of the call.
+   A kernel at the head of the call's front end (k_pcm_planes, in k_pcm_spread's place) interleaves the planes into the row
+   buffer the batch owns, and the front end reads that: everything a call writes or leaves in the stream state is exactly
+   what the same call writes when fed rows holding the same samples.  Device calls read the caller's image where it lies.
+   A sibling of PCM segments, with their contract wherever it is not restated here:
+   hx_batch_pcm_planes: off and chan_stride are HOST arrays [nstreams], copied by the function.  A NULL chan_stride means
+   the tight stride n_i * 1152 * sample size, formed per call; a NULL off switches back to rows.  Returns 0 / -1; sticky: a
+   call takes the planes in force when it is made, and a submit's stay its own whatever is set afterwards.  It either sets
+   the planes or (-1) changes nothing, and leaves the calling thread's current device alone.  Honoured by every encode and
+   submit entry point of a plain batch: device and host buffers, s16 and f32, *_stats, *_crc, *_host_dense, *_host_files,
+   *_host_recon, submit_*.  A converting batch returns -1.
+   Segments and planes exclude each other: setting one replaces the other, and either setter with a NULL off goes back to
+   rows.  A batch that never calls this setter behaves as before.
+   chan_stride[i] may be any multiple of the call's sample size: [S, C, T] and [C, S, T] tensors, a negative stride, and 0,
+   where both channels read one plane.  Planes may overlap between channels and between streams (they are only read).  A
+   mono stream's stride is not looked at; neither are the offset and stride of a stream with n_i = 0.  No 16-byte alignment
+   is asked of the offsets, the strides or a device image's base.
+   unit_scale takes effect on fp32 calls only: 0 takes the samples as they are, at int16 scale; 1 takes every sample as
+   x * 32768.0f, one IEEE float multiplication formed once in the interleaving kernel (subnormal inputs are kept, not
+   flushed; an input beyond 2^113 gives an infinity).  Any other value is refused by the setter.  An s16 call made while
+   unit_scale = 1 is in force is refused by name, not silently taken unscaled.
+   A call is refused (-1, hx_last_error names stream and channel) before anything is allocated, copied or launched, and the
+   batch stays usable, unless for every stream with n_i > 0 and each of its channels: the plane start is at or above 0, it
+   is a multiple of the call's sample size, and the plane ends at or below in_bytes.
+   Host calls copy one span of the image up: from the lowest plane start to the highest plane end among the streams that
+   take frames.  hx_batch_submit_*_host size their staging by the span.
+   Offsets and strides travel to the device as the segments' offsets do, in the same staging, with the same two notes.
+   hx_pcm_planar_layout: pure host code.  The tight layout: a stream's planes back to back in channel order, the streams
+   back to back in stream order: chan_stride[i] = n_i * 1152 * sample_bytes, off[0] = 0, off[i + 1] = off[i] + ch_i *
+   chan_stride[i]; off has nstreams + 1 entries, chan_stride nstreams.  Returns the image's size, or -1 under
+   hx_pcm_packed_layout's rules (and for a null chan_stride), writing nothing.  Every plane is a multiple of 2304 bytes, so
+   the layout is 16-byte aligned.
+   Not covered: converting batches, the hx_enc_* encoder, the command line, planar decoded PCM (hx_batch_recon_buffer
+   keeps the rows' layout), and bench.py, which measures calls fed rows. */
+long long hx_pcm_planar_layout(int nstreams, int nframes, const int *nfr, const int *channels, int sample_bytes, long long *off, long long *chan_stride);
+int hx_batch_pcm_planes(hx_batch *b, const long long *off, const long long *chan_stride, long long in_bytes, int unit_scale);
 /* ---- dense output: a call's bitstreams back to back (no reference equivalent) ----
    The rows [nstreams][out_stride] are sized for the worst case and mostly empty.  With dense output on, a call also
    gathers them on the GPU, behind its packing, into one image.  With nb[i] = out_bytes[i]:
@@ -861,6 +902,9 @@ int hx_multi_frame_counts(hx_multi *m, const int *nfr);
    bytes, whose base every hx_multi_encode_*_host* call then takes as pcm; each block copies only its own streams' span.
    All blocks or (-1) none.  A call's segment checks run for all blocks, with the caller's stream numbers, before any block starts */
 int hx_multi_pcm_segments(hx_multi *m, const long long *off, long long in_bytes);
+/* hx_batch_pcm_planes over all blocks ("PCM planes" above), the same way: off and chan_stride [nstreams] address the caller's
+   one image, and a call is checked for all blocks, with the caller's stream numbers, before one block starts. */
+int hx_multi_pcm_planes(hx_multi *m, const long long *off, const long long *chan_stride, long long in_bytes, int unit_scale);
 int hx_multi_status(hx_multi *m);
 /* converting batches (hx_batch_create_src) in the same blocks: in [nstreams][in_stride], frame_off [nstreams][nframes] or NULL,
    in_used [nstreams], stats NULL or [nstreams][nframes][2], all as in hx_batch_encode_src_host over all streams */
@@ -906,10 +950,17 @@ int hx_multi_encode_src_counts_host(hx_multi *m, const unsigned char *in, long l
    order ran: XCC id << 16 | HW_ID[15:0], i.e. CU [11:8], SH [12], SE [15:13]), "state", and two device counters (one int
    each, running over the batch's calls): "big_sweeps" = noise passes that took the double-precision x^(4/3) table,
    "strict_sums" = certified band sums that fell back to the reference's strict line-order sum (DESIGN.md section 2;
-   HMP3AMD_EXACT_SUMS=1 sends every sum there), and "pcmrows" (the row buffer as the last call under PCM segments left it,
+   HMP3AMD_EXACT_SUMS=1 sends every sum there), and "pcmrows" (the row buffer as the last call under PCM segments or PCM planes left it,
    [nstreams][that call's nframes * 1152 * P] samples of its type; -1 before the first such call).  Copies at most cap
    bytes, returns bytes, -1 for an unknown name. */
 long long hx_batch_debug_read(hx_batch *b, const char *name, void *dst, long long cap);
+/* Test tap: the head of a call's front end alone.  With PCM segments or PCM planes in force, makes a plain device call's
+   checks of d_pcm (the image's base in device memory; f32: 0 = int16, 1 = fp32) and nframes, uploads the image's layout
+   and launches the row kernel (k_pcm_spread / k_pcm_planes) on `stream` - and nothing behind it: no stream of the batch
+   moves, no output is written.  The rows are then read with hx_batch_debug_read's "pcmrows" tap.  This is how the row
+   kernels are held on samples the encoder behind them is not defined for (an fp32 product that overflows to an infinity).
+   Returns 0 / -1 with hx_last_error; -1 without segments or planes in force, and on a converting batch. */
+int hx_batch_debug_pcm_rows(hx_batch *b, const void *d_pcm, int nframes, int f32, void *stream);
 void hx_batch_debug_enable(hx_batch *b, int on);
 /* The kernels' device math on arguments of the caller's: for each i < n the device evaluates the function `name` - the
    very function the kernels call, built with the allocator kernels' flags, on this batch's device tables (the class-
